@@ -7,10 +7,12 @@ A "step" is one pass of K1 (address map + residue transform + quantiser) over on
 Infinity Cache and the launch period was 16.5 us; from 24 slots on it is flat at the HBM-bound figure (tools/k1_slots.py,
 DESIGN.md section 7). Ranks hold independent images (one process per GPU, no data-path collective): weak scaling.
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Rank 0 prints ONE JSON line (contract in the task statement) with `roofline` and `cpu_baseline` objects.
+With --dump-outputs DIR rank 0 also writes the coefficients its last timed step computed as DIR/*.npy (dump_outputs()): the inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -25,7 +27,35 @@ if ROOT not in sys.path:
 W = H = 4096
 CHANNELS = 1
 SPIN_UP_LAUNCHES = 4000  # ~70 ms of untimed work before the warm-up steps, see main()
-HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8 TB/s spec
+HBM_PEAK_GBS = 8000.0  # MI355X HBM3E 8 TB/s spec
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE_CELLS = 24576  # 48 MiB of float32: the whole 4096x4096 plane (33289 cells) would be 65 MiB
+DUMP_SEED = 0xF7A5D
+
+
+def dump_outputs(out_dir, coefs):
+    """Writes the coefficient planes [C][F][512] int32 of one step as DIR/<name>.npy, at most DUMP_MAX_BYTES in all:
+    coefs_sample        float32 [C][n][512]  every coefficient of n cells drawn with a fixed seed (the same cells in every run)
+    coefs_sample_cells  float64 [n]          those cells' indices, ascending
+    coefs_cell_sums     float64 [C][F]       the sum of each cell's 512 coefficients, for every cell of the plane
+    Every value is exact: float32 holds each sampled coefficient (None is INT32_MIN, a power of two), float64 each sum."""
+    import numpy as np
+
+    f = coefs.shape[1]
+    cells = np.sort(np.random.default_rng(DUMP_SEED).choice(f, min(f, DUMP_SAMPLE_CELLS), replace=False))
+    sample = coefs[:, cells]
+    arrays = {
+        "coefs_sample": sample.astype(np.float32),
+        "coefs_sample_cells": cells.astype(np.float64),
+        "coefs_cell_sums": coefs.sum(axis=2, dtype=np.int64).astype(np.float64),
+    }
+    if not np.array_equal(arrays["coefs_sample"].astype(np.int64), sample):
+        raise ValueError("a coefficient is not exactly representable in float32")
+    if sum(a.nbytes for a in arrays.values()) > DUMP_MAX_BYTES:
+        raise ValueError(f"the dump would exceed {DUMP_MAX_BYTES} bytes")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def measured_traffic(name="k1_traffic", tiling=None):
@@ -264,10 +294,13 @@ def main():
     ap.add_argument("--no-tune", action="store_true", help="keep fri_hip_plan_create's default forward tiling instead of measuring (fri_hip_plan_tune_forward)")
     ap.add_argument("--no-extras", action="store_true", help="leave the event-timed figures of K2 / K3 / K4 / K1-RGB / the chain out of the line")
     ap.add_argument("--extras", action="store_true", help="(kept for older command lines: the extras are in the default line now; adds the PCIe byte counts)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the coefficients of the last timed step as DIR/*.npy (rank 0; see dump_outputs)")
     args = ap.parse_args()
 
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0 or args.slots < 1:
+        ap.error("--steps and --slots must be >= 1, --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: this process has not touched the GPU and never will - it starts the N ranks as a child
         # process (torch.distributed.run, one rank per GPU over RCCL), relays rank 0's line and exits with the child's code; a line for another
@@ -379,6 +412,8 @@ def main():
     elapsed = timed_region(timed_steps, dist=dist, device_sync=torch.cuda.synchronize, device="cuda", device_idle=torch.cuda.current_stream().query)
     kernel_us = timed["kernel_us"]
     achieved = alg_bytes / (kernel_us * 1e-6) / 1e9
+    if args.dump_outputs and rank == 0:  # before anything else is launched: the native loop's last launch wrote slot (steps - 1) mod slots
+        dump_outputs(args.dump_outputs, d_co[(args.steps - 1) % args.slots].view(CHANNELS, F, 512).cpu().numpy())
 
     out = {
         "metric": "Mpixels/s encode (transform+quant) at 4096x4096",

@@ -1,6 +1,6 @@
 import os, sys
 os.environ["FRI_HIP_TUNING"]="1"; os.environ["FRI_HIP_TRACE"]="1"
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch, frave_amd
 ctx = frave_amd.Context(0)
 plan = frave_amd.Plan(ctx, 4096, 4096, 1)
