@@ -13,8 +13,10 @@
 #include <memory>
 #include <mutex>
 #include <new>
+#include <optional>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "geometry.hpp"
@@ -32,21 +34,90 @@ struct fri_hip_ctx {
 
 namespace {
 
+// Owners of the library's HIP resources: move-only, each gives its resource back when it goes. A plan's go with the plan's device current
+// (fri_hip_plan_destroy): a plan of fri_hip_multi's device d > 0 frees on that device.
+template <typename T, auto Release>
+class Owned {
+  public:
+    Owned() = default;
+    Owned(Owned &&o) noexcept : h_(std::exchange(o.h_, T{})) {}
+    Owned &operator=(Owned &&o) noexcept {
+        if (this != &o) reset(), h_ = std::exchange(o.h_, T{});
+        return *this;
+    }
+    ~Owned() { reset(); }
+    operator T() const { return h_; }
+    T get() const { return h_; }
+    T *put() { // the out-parameter of a hipMalloc / hipEventCreate / ...: whatever was held goes first
+        reset();
+        return &h_;
+    }
+    void reset() {
+        if (h_) (void)Release(h_);
+        h_ = T{};
+    }
+
+  private:
+    T h_{};
+};
+template <typename T> using DevMem = Owned<T *, hipFree>;
+template <typename T> using HostMem = Owned<T *, hipHostFree>; // pinned
+using Event = Owned<hipEvent_t, hipEventDestroy>;
+using Stream = Owned<hipStream_t, hipStreamDestroy>;
+
+// a grow-only device buffer of n elements (the plan's staging, its compact planes)
+template <typename T>
+struct Grown : DevMem<T> {
+    size_t n = 0;
+};
+
+// staging of the host-pointer entry points: each call grows the buffers it uses to what it needs of them (grow)
+struct Staging {
+    Grown<uint8_t> pixels, bucket;
+    Grown<int32_t> coefs, prediction;
+    Grown<uint32_t> hist;            // [channels][10][1024]
+    Grown<unsigned long long> oob;   // [channels]
+    Grown<uint16_t> symbols;         // fri_hip_encode_image_symbols: [C][geo.n_some]
+};
+
 constexpr int kBatchSlots = 3;
 
 struct Slot {
-    hipStream_t stream = nullptr;
-    uint8_t *h_pixels = nullptr; // pinned
-    int32_t *h_coefs = nullptr;  // pinned
-    uint8_t *d_pixels = nullptr;
-    int32_t *d_coefs = nullptr;
+    Stream stream;
+    HostMem<uint8_t> h_pixels;
+    HostMem<int32_t> h_coefs;
+    DevMem<uint8_t> d_pixels;
+    DevMem<int32_t> d_coefs;
     int pending = -1; // image index whose result sits in h_coefs once the stream drains
     // the rest of an image's encode outputs (fri_hip_encode_image_batch), allocated on first use
-    uint8_t *h_bucket = nullptr, *d_bucket = nullptr;
-    int32_t *h_prediction = nullptr, *d_prediction = nullptr;
-    uint32_t *h_hist = nullptr, *d_hist = nullptr;             // [C][10][1024]
-    unsigned long long *h_oob = nullptr, *d_oob = nullptr;     // [C] out of alphabet, then [C] the fit's out-of-range counts
-    float *h_params = nullptr, *d_params = nullptr;            // [C][2][3][6]
+    HostMem<uint8_t> h_bucket;
+    DevMem<uint8_t> d_bucket;
+    HostMem<int32_t> h_prediction;
+    DevMem<int32_t> d_prediction;
+    HostMem<uint32_t> h_hist;
+    DevMem<uint32_t> d_hist;             // [C][10][1024]
+    HostMem<unsigned long long> h_oob;
+    DevMem<unsigned long long> d_oob;    // [C] out of alphabet, then [C] the fit's out-of-range counts
+    HostMem<float> h_params;
+    DevMem<float> d_params;              // [C][2][3][6]
+};
+
+// (a deleter of this file's own: std::default_delete<fri_hip_plan> would be exported with the ABI's types)
+struct PlanDelete {
+    void operator()(fri_hip_plan *p) const;
+};
+
+// the device buffers of an accumulator slot (fri_hip_plan::acc_slots)
+struct AccBufs {
+    DevMem<uint32_t> pred_acc;           // [planes][kPredAccWords]: K2's hand-over bookkeeping (kernels.hpp), grown on demand, zero when allocated
+    DevMem<unsigned long long> fit_acc;  // [planes][kFitShards][kFitAccWords]
+    // scratch of the device-side fit (fit_chain): the sums of a launch's planes on their way to the solve kernels, their out-of-range
+    // counts, and parameter sets for callers that keep theirs on the host. Per stream like the accumulators: chains of several streams
+    // (fri_hip_multi_encode_image's slots) run side by side on one plan.
+    DevMem<unsigned long long> sums_int; // [planes][3][28]
+    DevMem<double> sums_dbl;             // [planes][3][6]
+    DevMem<unsigned long long> range;    // [planes]
+    DevMem<float> params;                // [planes][2][3][6]
 };
 
 } // namespace
@@ -62,68 +133,47 @@ struct fri_hip_plan {
     bool own_inverse_tiling = false;
     DevicePlan dev_inv;
     const Geometry &inv_geo() const { return own_inverse_tiling ? geo_inv : geo; }
-    std::vector<void *> owned; // device allocations backing dev.*
-    // staging for the host-pointer entry points (lazy)
-    uint8_t *d_pixels = nullptr;
-    int32_t *d_coefs = nullptr;
-    uint8_t *d_bucket = nullptr;
-    int32_t *d_prediction = nullptr;
-    uint32_t *d_hist = nullptr;
-    unsigned long long *d_oob = nullptr;
-    unsigned long long *d_fit_int = nullptr; // [3][28]
-    double *d_fit_dbl = nullptr;             // [3][6]
+    std::vector<DevMem<void>> owned; // device allocations backing dev.*
+    Staging staging;
     Slot slots[kBatchSlots];
     bool slots_ready = false;
     // K2 / K4 hand their sums over through plan-owned accumulators that are all zero between launches (kernels.hpp). One
     // accumulator per stream that launches on this plan: launches of one stream are ordered anyway; when more streams than
     // accumulators are in play a stream taking over an accumulator first waits (on the device) for its previous user.
-    struct AccSlot {
+    struct AccSlot : AccBufs {
         hipStream_t stream = nullptr;
         bool used = false;
-        hipEvent_t handed_over = nullptr;
-        uint32_t *pred_acc = nullptr;           // [planes][kPredAccWords]: K2's hand-over bookkeeping (kernels.hpp), grown on demand, zero when allocated
-        uint32_t pred_serial = 0;               // launches of K2 on this accumulator so far: every launch publishes and polls for its own number
-        unsigned long long *fit_acc = nullptr;  // [planes][kFitShards][kFitAccWords]
-        // scratch of the device-side fit (fit_chain): the sums of a launch's planes on their way to the solve kernels, their out-of-range
-        // counts, and parameter sets for callers that keep theirs on the host. Per stream like the accumulators: chains of several streams
-        // (fri_hip_multi_encode_image's slots) run side by side on one plan.
-        unsigned long long *sums_int = nullptr; // [planes][3][28]
-        double *sums_dbl = nullptr;             // [planes][3][6]
-        unsigned long long *range = nullptr;    // [planes]
-        float *params = nullptr;                // [planes][2][3][6]
+        Event handed_over;
+        uint32_t pred_serial = 0; // launches of K2 on this accumulator so far: every launch publishes and polls for its own number
         uint32_t planes = 0;
     } acc_slots[kPredAccRing];
-    std::vector<void *> retired_acc; // accumulators outgrown by a larger batch: freed with the plan (a launch may still be draining them)
-    // fri_hip_encode_image (host form): all channels' outputs on the device
-    uint8_t *d_bucket_all = nullptr;
-    int32_t *d_prediction_all = nullptr;
-    uint32_t *d_hist_all = nullptr;           // [C][10][1024]
-    unsigned long long *d_oob_all = nullptr;  // [C]
+    std::vector<AccBufs> retired_acc; // accumulators outgrown by a larger batch: freed with the plan (a launch may still be draining them)
     // host-facing fit (fri_hip_encode_image_dev / fri_hip_predict_image_dev with fit != 0): the fitted parameters and the range counts come
     // back through pinned memory behind an event, while the scan kernel that follows them is already queued
-    void *h_fit = nullptr;     // pinned + mapped: [3] PredictParams + [3] u64
+    HostMem<void> h_fit;       // pinned + mapped: [3] PredictParams + [3] u64
     void *d_h_fit = nullptr;   // the device's address of h_fit
-    hipEvent_t ev_fit = nullptr;
+    Event ev_fit;
     bool assume_forward = false; // fri_hip_plan_assume_forward_coefficients
-    uint32_t *d_stream_order = nullptr; // fri_hip_plan_set_stream_order: node index of the i-th symbol of a channel, [geo.n_some]
-    uint32_t *d_stream_pos = nullptr;   // ... and its inverse, [F][512]: the position of a node's symbol in a channel's stream (None nodes: ~0, never used) - the scan's STREAM form
+    DevMem<uint32_t> d_stream_order; // fri_hip_plan_set_stream_order: node index of the i-th symbol of a channel, [geo.n_some]
+    DevMem<uint32_t> d_stream_pos;   // ... and its inverse, [F][512]: the position of a node's symbol in a channel's stream (None nodes: ~0, never used) - the scan's STREAM form
     // The symbol-stream chains' compact coefficient planes (round 5): int16, None as 0, [planes][F][512] - between the forward kernel, the fit and the scan when the
     // caller does not ask for the coefficients (fri_hip_encode_image_symbols; fri_hip_encode_symbols_batch_dev with d_coefs == NULL). Half the bytes written and read three times.
-    int16_t *d_coefs16 = nullptr;
-    size_t coefs16_planes = 0;
-    hipEvent_t ev_coefs16 = nullptr;    // behind the last chain that used them: a chain on ANOTHER stream waits for it before it overwrites the planes
+    // A chain holds them through a Coefs16Lease.
+    Grown<int16_t> coefs16;
+    Event ev_coefs16;                   // behind the last chain that used them: a chain on ANOTHER stream waits for it before it overwrites the planes
     hipStream_t coefs16_stream = nullptr;
     bool coefs16_used = false;
-    uint16_t *d_symbols = nullptr;      // fri_hip_encode_image_symbols: [C][geo.n_some]
     uint32_t acc_next = 0;
     bool acc_dirty = false; // a launch on this plan failed: the accumulators are re-zeroed before the next use
-    hipEvent_t ev_begin = nullptr, ev_end = nullptr; // timing helper's events, created with the plan (creating an event is not work to be timed)
+    Event ev_begin, ev_end; // timing helper's events, created with the plan (creating an event is not work to be timed)
     // fri_hip_plan_tune_forward: the parameters the forward tiling was built with, and whether the plan may exchange it (a plan whose tiling the
     // environment pinned, whose inverse kernel shares the forward tiles, or that is cut into many short shares keeps what it has)
     TilingParams fwd_tp;
     bool fwd_tunable = false;
     std::string fwd_tiling_note = "default";
 };
+
+void PlanDelete::operator()(fri_hip_plan *p) const { delete p; }
 
 struct fri_hip_multi {
     std::vector<fri_hip_ctx *> ctxs;
@@ -147,14 +197,13 @@ int fail_hip(fri_hip_ctx *ctx, hipError_t e, const char *what) {
 
 template <typename T>
 int upload(fri_hip_plan *p, const std::vector<T> &v, const T *&out, size_t pad = 0) { // pad: zeroed elements behind the array
-    void *d = nullptr;
     size_t bytes = (v.size() + pad) * sizeof(T);
     if (!bytes) bytes = sizeof(T);
-    HIP_TRY(p->ctx, hipMalloc(&d, bytes));
-    p->owned.push_back(d);
-    if (pad) HIP_TRY(p->ctx, hipMemset(static_cast<T *>(d) + v.size(), 0, pad * sizeof(T)));
+    auto &d = p->owned.emplace_back();
+    HIP_TRY(p->ctx, hipMalloc(d.put(), bytes));
+    if (pad) HIP_TRY(p->ctx, hipMemset(static_cast<T *>(d.get()) + v.size(), 0, pad * sizeof(T)));
     if (!v.empty()) HIP_TRY(p->ctx, hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    out = static_cast<const T *>(d);
+    out = static_cast<const T *>(d.get());
     return FRI_HIP_OK;
 }
 
@@ -184,17 +233,13 @@ int env_int(const char *name) {
     return s ? std::atoi(s) : 0;
 }
 
-int ensure_staging(fri_hip_plan *p) {
-    fri_hip_ctx *c = p->ctx;
-    const size_t F = p->geo.centers.size();
-    if (!p->d_pixels) HIP_TRY(c, hipMalloc((void **)&p->d_pixels, fri_hip_plan_pixel_bytes(p)));
-    if (!p->d_coefs) HIP_TRY(c, hipMalloc((void **)&p->d_coefs, fri_hip_plan_coef_count(p) * sizeof(int32_t)));
-    if (!p->d_bucket) HIP_TRY(c, hipMalloc((void **)&p->d_bucket, F * kCell));
-    if (!p->d_prediction) HIP_TRY(c, hipMalloc((void **)&p->d_prediction, F * kCell * sizeof(int32_t)));
-    if (!p->d_hist) HIP_TRY(c, hipMalloc((void **)&p->d_hist, 10 * 1024 * sizeof(uint32_t)));
-    if (!p->d_oob) HIP_TRY(c, hipMalloc((void **)&p->d_oob, sizeof(unsigned long long)));
-    if (!p->d_fit_int) HIP_TRY(c, hipMalloc((void **)&p->d_fit_int, 3 * 28 * sizeof(unsigned long long)));
-    if (!p->d_fit_dbl) HIP_TRY(c, hipMalloc((void **)&p->d_fit_dbl, 18 * sizeof(double)));
+// at least n elements in b (n == 0: the call does not use it). Growing frees the old buffer first: hipFree waits for the device, so nothing queued still uses it.
+template <typename T>
+int grow(fri_hip_ctx *c, Grown<T> &b, size_t n) {
+    if (b.n >= n) return FRI_HIP_OK;
+    b.n = 0;
+    HIP_TRY(c, hipMalloc((void **)b.put(), n * sizeof(T)));
+    b.n = n;
     return FRI_HIP_OK;
 }
 
@@ -227,7 +272,7 @@ int acquire_acc(fri_hip_plan *p, hipStream_t stream, uint32_t n_planes = 1) {
         auto &v = p->acc_slots[p->acc_next];
         idx = (int)p->acc_next;
         p->acc_next = (p->acc_next + 1) % kPredAccRing;
-        if (!v.handed_over) HIP_TRY(c, hipEventCreateWithFlags(&v.handed_over, hipEventDisableTiming));
+        if (!v.handed_over) HIP_TRY(c, hipEventCreateWithFlags(v.handed_over.put(), hipEventDisableTiming));
         // everything the previous owner has queued so far finishes before the new owner's kernel starts. The previous owner is known by
         // its handle only: the caller may have destroyed that stream since (the record then fails, or lands on a recycled handle). Either
         // way the slot must come out usable: without a valid event, wait for the whole device once - whatever was queued on a stream
@@ -244,48 +289,24 @@ int acquire_acc(fri_hip_plan *p, hipStream_t stream, uint32_t n_planes = 1) {
     if (a.planes < n_planes) { // grow: the old buffers may still be in use by queued launches, so they are retired, not freed
         // (geometric: a caller whose batches grow by one plane per call retires at most 16 generations per slot - ADVICE r3)
         const uint32_t planes = std::min<uint32_t>(65535u, std::max<uint32_t>({4u, n_planes, 2u * a.planes}));
-        void *pa = nullptr, *fa = nullptr, *si = nullptr, *sd = nullptr, *rg = nullptr, *pr = nullptr;
+        AccBufs n;
         const size_t pb = (size_t)planes * kPredAccWords * sizeof(uint32_t), fb = (size_t)planes * kFitShards * kFitAccWords * sizeof(unsigned long long);
-        hipError_t e = hipMalloc(&pa, pb);
-        if (e == hipSuccess) e = hipMalloc(&fa, fb);
-        if (e == hipSuccess) e = hipMalloc(&si, (size_t)planes * 3 * 28 * sizeof(unsigned long long));
-        if (e == hipSuccess) e = hipMalloc(&sd, (size_t)planes * 18 * sizeof(double));
-        if (e == hipSuccess) e = hipMalloc(&rg, (size_t)planes * sizeof(unsigned long long));
-        if (e == hipSuccess) e = hipMalloc(&pr, (size_t)planes * sizeof(PredictParams));
+        hipError_t e = hipMalloc((void **)n.pred_acc.put(), pb);
+        if (e == hipSuccess) e = hipMalloc((void **)n.fit_acc.put(), fb);
+        if (e == hipSuccess) e = hipMalloc((void **)n.sums_int.put(), (size_t)planes * 3 * 28 * sizeof(unsigned long long));
+        if (e == hipSuccess) e = hipMalloc((void **)n.sums_dbl.put(), (size_t)planes * 18 * sizeof(double));
+        if (e == hipSuccess) e = hipMalloc((void **)n.range.put(), (size_t)planes * sizeof(unsigned long long));
+        if (e == hipSuccess) e = hipMalloc((void **)n.params.put(), (size_t)planes * sizeof(PredictParams));
         // zeroed ON THE LAUNCHING STREAM: a hipMemset on the null stream is not ordered against a non-blocking stream, and a memset that lands while
         // the first kernel is adding into the accumulator wipes its partial sums (seen with twelve torch streams: an all-zero Gram matrix)
-        if (e == hipSuccess) e = hipMemsetAsync(pa, 0, pb, stream);
-        if (e == hipSuccess) e = hipMemsetAsync(fa, 0, fb, stream);
-        if (e != hipSuccess) {
-            for (void *d : {pa, fa, si, sd, rg, pr})
-                if (d) (void)hipFree(d);
-            return fail_hip(c, e, "accumulator allocation");
-        }
-        for (void *d : {(void *)a.pred_acc, (void *)a.fit_acc, (void *)a.sums_int, (void *)a.sums_dbl, (void *)a.range, (void *)a.params})
-            if (d) p->retired_acc.push_back(d);
-        a.pred_acc = static_cast<uint32_t *>(pa);
-        a.fit_acc = static_cast<unsigned long long *>(fa);
-        a.sums_int = static_cast<unsigned long long *>(si);
-        a.sums_dbl = static_cast<double *>(sd);
-        a.range = static_cast<unsigned long long *>(rg);
-        a.params = static_cast<float *>(pr);
+        if (e == hipSuccess) e = hipMemsetAsync(n.pred_acc, 0, pb, stream);
+        if (e == hipSuccess) e = hipMemsetAsync(n.fit_acc, 0, fb, stream);
+        if (e != hipSuccess) return fail_hip(c, e, "accumulator allocation");
+        std::swap(static_cast<AccBufs &>(a), n);
+        if (a.planes) p->retired_acc.push_back(std::move(n));
         a.planes = planes;
     }
     return idx;
-}
-
-void free_slots(fri_hip_plan *p) {
-    for (Slot &s : p->slots) {
-        if (s.stream) (void)hipStreamDestroy(s.stream);
-        if (s.h_pixels) (void)hipHostFree(s.h_pixels);
-        if (s.h_coefs) (void)hipHostFree(s.h_coefs);
-        for (void *d : {(void *)s.d_pixels, (void *)s.d_coefs, (void *)s.d_bucket, (void *)s.d_prediction, (void *)s.d_hist, (void *)s.d_oob, (void *)s.d_params})
-            if (d) (void)hipFree(d);
-        for (void *h : {(void *)s.h_bucket, (void *)s.h_prediction, (void *)s.h_hist, (void *)s.h_oob, (void *)s.h_params})
-            if (h) (void)hipHostFree(h);
-        s = Slot{};
-    }
-    p->slots_ready = false;
 }
 
 int ensure_slots(fri_hip_plan *p) {
@@ -294,16 +315,16 @@ int ensure_slots(fri_hip_plan *p) {
     const size_t pb = fri_hip_plan_pixel_bytes(p), cb = fri_hip_plan_coef_count(p) * sizeof(int32_t);
     auto alloc_all = [&]() -> int {
         for (Slot &s : p->slots) {
-            HIP_TRY(c, hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
-            HIP_TRY(c, hipHostMalloc((void **)&s.h_pixels, pb, hipHostMallocDefault));
-            HIP_TRY(c, hipHostMalloc((void **)&s.h_coefs, cb, hipHostMallocDefault));
-            HIP_TRY(c, hipMalloc((void **)&s.d_pixels, pb));
-            HIP_TRY(c, hipMalloc((void **)&s.d_coefs, cb));
+            HIP_TRY(c, hipStreamCreateWithFlags(s.stream.put(), hipStreamNonBlocking));
+            HIP_TRY(c, hipHostMalloc((void **)s.h_pixels.put(), pb, hipHostMallocDefault));
+            HIP_TRY(c, hipHostMalloc((void **)s.h_coefs.put(), cb, hipHostMallocDefault));
+            HIP_TRY(c, hipMalloc((void **)s.d_pixels.put(), pb));
+            HIP_TRY(c, hipMalloc((void **)s.d_coefs.put(), cb));
         }
         return FRI_HIP_OK;
     };
     if (int rc = alloc_all()) { // a partial set is of no use: give everything back, the next call starts over
-        free_slots(p);
+        for (Slot &s : p->slots) s = Slot{};
         return rc;
     }
     p->slots_ready = true;
@@ -316,21 +337,22 @@ int ensure_encode_slots(fri_hip_plan *p, bool want_bucket, bool want_prediction)
     fri_hip_ctx *c = p->ctx;
     const size_t C = p->geo.channels, n = fri_hip_plan_coef_count(p);
     for (Slot &s : p->slots) {
-        if (want_bucket && !s.d_bucket) {
-            HIP_TRY(c, hipMalloc((void **)&s.d_bucket, n));
-            HIP_TRY(c, hipHostMalloc((void **)&s.h_bucket, n, hipHostMallocDefault));
+        // (each group is complete once its last buffer exists: a group that failed part-way is allocated again)
+        if (want_bucket && !s.h_bucket) {
+            HIP_TRY(c, hipMalloc((void **)s.d_bucket.put(), n));
+            HIP_TRY(c, hipHostMalloc((void **)s.h_bucket.put(), n, hipHostMallocDefault));
         }
-        if (want_prediction && !s.d_prediction) {
-            HIP_TRY(c, hipMalloc((void **)&s.d_prediction, n * sizeof(int32_t)));
-            HIP_TRY(c, hipHostMalloc((void **)&s.h_prediction, n * sizeof(int32_t), hipHostMallocDefault));
+        if (want_prediction && !s.h_prediction) {
+            HIP_TRY(c, hipMalloc((void **)s.d_prediction.put(), n * sizeof(int32_t)));
+            HIP_TRY(c, hipHostMalloc((void **)s.h_prediction.put(), n * sizeof(int32_t), hipHostMallocDefault));
         }
-        if (!s.d_hist) {
-            HIP_TRY(c, hipMalloc((void **)&s.d_hist, C * 10 * 1024 * sizeof(uint32_t)));
-            HIP_TRY(c, hipHostMalloc((void **)&s.h_hist, C * 10 * 1024 * sizeof(uint32_t), hipHostMallocDefault));
-            HIP_TRY(c, hipMalloc((void **)&s.d_oob, 2 * C * sizeof(unsigned long long)));
-            HIP_TRY(c, hipHostMalloc((void **)&s.h_oob, 2 * C * sizeof(unsigned long long), hipHostMallocDefault));
-            HIP_TRY(c, hipMalloc((void **)&s.d_params, C * sizeof(PredictParams)));
-            HIP_TRY(c, hipHostMalloc((void **)&s.h_params, C * sizeof(PredictParams), hipHostMallocDefault));
+        if (!s.h_params) {
+            HIP_TRY(c, hipMalloc((void **)s.d_hist.put(), C * 10 * 1024 * sizeof(uint32_t)));
+            HIP_TRY(c, hipHostMalloc((void **)s.h_hist.put(), C * 10 * 1024 * sizeof(uint32_t), hipHostMallocDefault));
+            HIP_TRY(c, hipMalloc((void **)s.d_oob.put(), 2 * C * sizeof(unsigned long long)));
+            HIP_TRY(c, hipHostMalloc((void **)s.h_oob.put(), 2 * C * sizeof(unsigned long long), hipHostMallocDefault));
+            HIP_TRY(c, hipMalloc((void **)s.d_params.put(), C * sizeof(PredictParams)));
+            HIP_TRY(c, hipHostMalloc((void **)s.h_params.put(), C * sizeof(PredictParams), hipHostMallocDefault));
         }
     }
     return FRI_HIP_OK;
@@ -347,7 +369,7 @@ struct FwdTiling {  // one candidate: host geometry + its device tables
     TilingParams tp;
     Geometry geo;
     DevicePlan dev;            // p->dev with this candidate's tiling swapped in
-    std::vector<void *> bufs;  // device tables of this candidate
+    std::vector<DevMem<void>> bufs; // device tables of this candidate
     std::string label;
     double us = 0;
 };
@@ -365,14 +387,13 @@ void fill_forward_tiling(DevicePlan &d, const Geometry &g) {
 }
 
 template <typename T>
-hipError_t upload_raw(const std::vector<T> &v, const T *&out, std::vector<void *> &bufs) {
-    void *d = nullptr;
+hipError_t upload_raw(const std::vector<T> &v, const T *&out, std::vector<DevMem<void>> &bufs) {
     const size_t bytes = std::max(v.size(), (size_t)1) * sizeof(T);
-    if (hipError_t e = hipMalloc(&d, bytes)) return e;
-    bufs.push_back(d);
+    auto &d = bufs.emplace_back();
+    if (hipError_t e = hipMalloc(d.put(), bytes)) return e;
     if (!v.empty())
         if (hipError_t e = hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice)) return e;
-    out = static_cast<const T *>(d);
+    out = static_cast<const T *>(d.get());
     return hipSuccess;
 }
 
@@ -413,7 +434,7 @@ void adopt_forward_tiling(fri_hip_plan *p, FwdTiling &c) {
     d.tiles = c.dev.tiles, d.tile_cells = c.dev.tile_cells, d.tile_meta = c.dev.tile_meta, d.wg_tiles = c.dev.wg_tiles, d.wg_tiles_batch = c.dev.wg_tiles_batch;
     fill_forward_tiling(d, g);
     d.inv_max_wg_tiles = d.max_wg_tiles, d.inv_max_wg_cells = d.max_wg_cells; // (only read by an inverse kernel on the forward tiling; tunable plans have their own)
-    for (void *b : c.bufs) p->owned.push_back(b);
+    for (auto &b : c.bufs) p->owned.push_back(std::move(b));
     c.bufs.clear();
     p->fwd_tp = c.tp;
     p->fwd_tiling_note = c.label;
@@ -451,13 +472,68 @@ void adopt_cached_forward_tiling(fri_hip_plan *p) {
     FwdTiling c;
     c.tp = tp;
     if (!build_forward_candidate(p, c)) return;
-    if (upload_forward_candidate(p, c) != hipSuccess) {
-        for (void *b : c.bufs) (void)hipFree(b);
+    if (upload_forward_candidate(p, c) != hipSuccess) { // (c's tables go with it)
         (void)hipGetLastError();
         return;
     }
     c.label = tiling_label(c.tp, c.geo) + " (measured earlier in this process)";
     adopt_forward_tiling(p, c);
+}
+
+// Runs work(plan, images) for every device of m on one thread per device (the calling thread drives the first): `images` are the indices of the device's
+// shard (fri_hip_shard_size / fri_hip_shard_image), devices whose shard is empty are left out. Returns the first failure by device.
+template <typename Work>
+int run_shards(fri_hip_multi *m, uint32_t n_images, Work &&work) {
+    const uint32_t n_devices = (uint32_t)m->plans.size();
+    std::vector<int> rcs(n_devices, FRI_HIP_OK);
+    auto shard = [&](uint32_t d) {
+        std::vector<uint32_t> images(fri_hip_shard_size(n_images, d, n_devices));
+        for (uint32_t k = 0; k < images.size(); k++) images[k] = fri_hip_shard_image(k, d, n_devices);
+        if (!images.empty()) rcs[d] = work(m->plans[d], images);
+    };
+    std::vector<std::thread> threads;
+    for (uint32_t d = 1; d < n_devices; d++) threads.emplace_back(shard, d);
+    shard(0);
+    for (auto &t : threads) t.join();
+    for (int rc : rcs)
+        if (rc != FRI_HIP_OK) return rc;
+    return FRI_HIP_OK;
+}
+// the entries of a per-image array (may be NULL: then none) that belong to a shard
+template <typename T>
+std::vector<T> pick(const T *all, const std::vector<uint32_t> &images) {
+    std::vector<T> v;
+    if (all)
+        for (uint32_t i : images) v.push_back(all[i]);
+    return v;
+}
+
+// Waits for `ev` by polling: a sleeping wait (hipEventSynchronize) goes to sleep after a few hundred microseconds and wakes up 15-20 us late - a tenth of a
+// chain, or charged to a measurement of twenty 17-us launches (plus as much again in the caller's next synchronize). After seconds of spinning it is not a
+// short wait any more: the sleeping wait takes over.
+int wait_event_polling(fri_hip_ctx *c, hipEvent_t ev) {
+    for (uint64_t spins = 0;; spins++) {
+        const hipError_t q = hipEventQuery(ev);
+        if (q == hipSuccess) return FRI_HIP_OK;
+        if (q != hipErrorNotReady) HIP_TRY(c, q);
+        if (spins > (1ull << 22)) {
+            HIP_TRY(c, hipEventSynchronize(ev));
+            return FRI_HIP_OK;
+        }
+    }
+}
+
+// The scan's histogram hand-over numbers its launches on the HOST (pred_serial, a kernel argument): a captured launch would freeze that number, and from the
+// second replay on the clearing workgroups' flags already hold it - nothing would order the clearing of the histogram before the other workgroups' adds any more
+// (counts wiped or doubled). So every entry point that reaches the scan refuses a capturing stream, loudly, before it queues or allocates anything,
+// instead of recording something that must not be replayed.
+int refuse_capture(fri_hip_plan *p, hipStream_t stream) {
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+    if (stream && hipStreamIsCapturing(stream, &capturing) == hipSuccess && capturing != hipStreamCaptureStatusNone) {
+        if (p->ctx) p->ctx->last_error = "the predict + histogram kernel cannot be captured into a HIP graph (its hand-over counts launches on the host): launch it on a stream";
+        return FRI_HIP_ERR_INVALID_ARGUMENT;
+    }
+    return FRI_HIP_OK;
 }
 
 } // namespace
@@ -512,8 +588,10 @@ int fri_hip_plan_create(fri_hip_ctx *ctx, uint32_t width, uint32_t height, uint3
     *out = nullptr;
     const StaticTables &st = static_tables();
     if (!st.error.empty() || !device_footprint_matches(st)) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    fri_hip_plan *p = new (std::nothrow) fri_hip_plan;
-    if (!p) return FRI_HIP_ERR_OUT_OF_MEMORY;
+    // held until it is handed out: a plan that fails part-way goes with whatever it has allocated (with its device current, bound below before the first allocation)
+    std::unique_ptr<fri_hip_plan, PlanDelete> plan(new (std::nothrow) fri_hip_plan);
+    if (!plan) return FRI_HIP_ERR_OUT_OF_MEMORY;
+    fri_hip_plan *p = plan.get();
     p->ctx = ctx;
     TilingParams tp;
     tp.band_rows = env_int("FRI_HIP_BAND_ROWS");
@@ -559,11 +637,7 @@ int fri_hip_plan_create(fri_hip_ctx *ctx, uint32_t width, uint32_t height, uint3
     // makes a few tiles wider than the average; RGB triples the bytes per pixel).
     for (;;) {
         std::string err = build_geometry(width, height, channels, tp, p->geo);
-        if (!err.empty()) {
-            int rc = err == "empty lattice" ? FRI_HIP_ERR_EMPTY_LATTICE : FRI_HIP_ERR_INVALID_ARGUMENT;
-            delete p;
-            return rc;
-        }
+        if (!err.empty()) return err == "empty lattice" ? FRI_HIP_ERR_EMPTY_LATTICE : FRI_HIP_ERR_INVALID_ARGUMENT;
         DevicePlan probe;
         probe.channels = (int32_t)channels;
         probe.lds_pitch = p->geo.lds_pitch;
@@ -599,10 +673,7 @@ int fri_hip_plan_create(fri_hip_ctx *ctx, uint32_t width, uint32_t height, uint3
         if (tp.cells_per_tile < 1) {
             tp.cells_per_tile = 1;
             tp.band_rows = p->geo.band_rows / 2;
-            if (tp.band_rows < 1) {
-                delete p;
-                return FRI_HIP_ERR_INVALID_ARGUMENT;
-            }
+            if (tp.band_rows < 1) return FRI_HIP_ERR_INVALID_ARGUMENT;
         }
     }
     const TilingParams tp_forward = tp; // what the forward tiling was built with (fri_hip_plan_tune_forward starts from it)
@@ -656,10 +727,7 @@ int fri_hip_plan_create(fri_hip_ctx *ctx, uint32_t width, uint32_t height, uint3
         }
     }
     if (ctx) {
-        if (hipSetDevice(ctx->device) != hipSuccess) {
-            delete p;
-            return FRI_HIP_ERR_HIP;
-        }
+        if (hipSetDevice(ctx->device) != hipSuccess) return FRI_HIP_ERR_HIP;
         const Geometry &g = p->geo;
         DevicePlan &d = p->dev;
         int rc = FRI_HIP_OK;
@@ -674,17 +742,14 @@ int fri_hip_plan_create(fri_hip_ctx *ctx, uint32_t width, uint32_t height, uint3
         for (int n = 2; n < kCell; n++)
             for (int k = 0; k < 6; k++) node0_gathered |= !(tab[(size_t)n * 6 + k] & 0x8000u) && (tab[(size_t)n * 6 + k] & 511u) == 0;
         if (halo_list[0] == 0xFFFFFFFFu || node0_gathered || pair_pos[0] != 0) { // (pair 0 = heap nodes 0 and 1 at the head of a cell: where the fit kernels' zero lives) // more halo values than threads / ...: the neighbour table is not the one the kernels were laid out for
-            fri_hip_plan_destroy(p);
             return FRI_HIP_ERR_INVALID_ARGUMENT;
         }
         if ((rc = upload(p, g.tiles, d.tiles)) || (rc = upload(p, g.tile_cells, d.tile_cells)) || (rc = upload(p, g.tile_meta, d.tile_meta)) || (rc = upload(p, g.wg_tiles, d.wg_tiles)) || (rc = upload(p, g.wg_tiles_batch, d.wg_tiles_batch)) || (rc = upload(p, g.centers, d.centers)) ||
             (rc = upload(p, g.interior, d.interior)) || (rc = upload(p, g.valid_mask, d.valid_mask)) ||
             (rc = upload(p, g.nbr_cells, d.nbr_cells)) || (rc = upload(p, g.pred_slots, d.pred_slots)) || (rc = upload(p, tab, d.nbr_table)) ||
             (rc = upload(p, gather_off, d.gather_off)) || (rc = upload(p, pair_pos, d.pair_pos)) || (rc = upload(p, heap_of_pos, d.heap_of_pos)) ||
-            (rc = upload(p, halo_list, d.halo_list))) {
-            fri_hip_plan_destroy(p);
+            (rc = upload(p, halo_list, d.halo_list)))
             return rc;
-        }
         d.n_pred_tiles = g.n_pred_tiles;
         d.n_tiles = (uint32_t)g.tiles.size();
         d.F = (uint32_t)g.centers.size();
@@ -711,13 +776,9 @@ int fri_hip_plan_create(fri_hip_ctx *ctx, uint32_t width, uint32_t height, uint3
         d.pred_blocks = (uint32_t)ctx->cu_count;
         if (env_int("FRI_HIP_PRED_BLOCKS") > 0) d.pred_blocks = (uint32_t)env_int("FRI_HIP_PRED_BLOCKS");
         {
-            void *j = nullptr;
-            if (hipMalloc(&j, (size_t)d.pred_blocks * kPredJunkWaves * kPredJunkBytes) != hipSuccess) {
-                fri_hip_plan_destroy(p);
-                return FRI_HIP_ERR_HIP;
-            }
-            p->owned.push_back(j);
-            d.junk = static_cast<uint8_t *>(j);
+            auto &j = p->owned.emplace_back();
+            if (hipMalloc(j.put(), (size_t)d.pred_blocks * kPredJunkWaves * kPredJunkBytes) != hipSuccess) return FRI_HIP_ERR_HIP;
+            d.junk = static_cast<uint8_t *>(j.get());
         }
         d.hist_blocks = 2u * (uint32_t)ctx->cu_count; // two resident 512-thread workgroups per CU (LDS: 2 x 78 KiB)
         d.k1_ablate = env_int("FRI_HIP_K1_ABLATE");
@@ -732,38 +793,27 @@ int fri_hip_plan_create(fri_hip_ctx *ctx, uint32_t width, uint32_t height, uint3
             const Geometry &gi = p->inv_geo();
             if (!gi.inv_lists.empty()) {
                 if ((rc = upload(p, gi.inv_lists, d.inv_lists)) || (rc = upload(p, gi.inv_quads, d.inv_quads, kInvListPad)) || (rc = upload(p, gi.inv_dwords, d.inv_dwords, kInvListPad)) ||
-                    (rc = upload(p, gi.inv_parts, d.inv_parts, kInvListPad))) {
-                    fri_hip_plan_destroy(p);
+                    (rc = upload(p, gi.inv_parts, d.inv_parts, kInvListPad)))
                     return rc;
-                }
                 d.inv_rect_bytes = gi.inv_rect_bytes;
             }
         }
         if (env_int("FRI_HIP_TRACE") > 0) {
             const size_t bytes = (size_t)std::max<size_t>(d.n_wg, p->own_inverse_tiling ? p->geo_inv.wg_tiles.size() : 0) * 16 * sizeof(unsigned long long);
-            void *t = nullptr;
-            if (hipMalloc(&t, bytes) != hipSuccess || hipMemset(t, 0, bytes) != hipSuccess) {
-                fri_hip_plan_destroy(p);
-                return FRI_HIP_ERR_HIP;
-            }
-            p->owned.push_back(t);
-            d.trace = static_cast<unsigned long long *>(t);
+            auto &t = p->owned.emplace_back();
+            if (hipMalloc(t.put(), bytes) != hipSuccess || hipMemset(t, 0, bytes) != hipSuccess) return FRI_HIP_ERR_HIP;
+            d.trace = static_cast<unsigned long long *>(t.get());
         }
         int hb = env_int("FRI_HIP_HIST_BLOCKS");
         if (hb > 0) d.hist_blocks = (uint32_t)hb;
-        if (hipEventCreate(&p->ev_begin) != hipSuccess || hipEventCreate(&p->ev_end) != hipSuccess) {
-            fri_hip_plan_destroy(p);
-            return FRI_HIP_ERR_HIP;
-        }
+        if (hipEventCreate(p->ev_begin.put()) != hipSuccess || hipEventCreate(p->ev_end.put()) != hipSuccess) return FRI_HIP_ERR_HIP;
         // the inverse kernel's view of the plan: everything of `dev`, with its own tiles, cell records and shares swapped in
         p->dev_inv = d;
         if (p->own_inverse_tiling) {
             Geometry &gi = p->geo_inv;
             DevicePlan &di = p->dev_inv;
-            if ((rc = upload(p, gi.tiles, di.tiles)) || (rc = upload(p, gi.tile_cells, di.tile_cells)) || (rc = upload(p, gi.tile_meta, di.tile_meta)) || (rc = upload(p, gi.wg_tiles, di.wg_tiles))) {
-                fri_hip_plan_destroy(p);
+            if ((rc = upload(p, gi.tiles, di.tiles)) || (rc = upload(p, gi.tile_cells, di.tile_cells)) || (rc = upload(p, gi.tile_meta, di.tile_meta)) || (rc = upload(p, gi.wg_tiles, di.wg_tiles)))
                 return rc;
-            }
             di.wg_tiles_batch = nullptr, di.n_wg_batch = 0;
             di.n_tiles = (uint32_t)gi.tiles.size();
             di.n_wg = (uint32_t)gi.wg_tiles.size() - 1;
@@ -780,36 +830,12 @@ int fri_hip_plan_create(fri_hip_ctx *ctx, uint32_t width, uint32_t height, uint3
                      !env_str("FRI_HIP_CELLS_PER_WG") && !env_str("FRI_HIP_STRIDED_SHARES") && !env_str("FRI_HIP_TARGET_WGS") && !env_str("FRI_HIP_RANKS") &&
                      !env_str("FRI_HIP_TILE_BYTES") && !env_str("FRI_HIP_RANK_WEIGHTS");
     if (p->fwd_tunable) adopt_cached_forward_tiling(p); // a tiling measured for this device and shape earlier in the process (fri_hip_plan_tune_forward)
-    *out = p;
+    *out = plan.release();
     return FRI_HIP_OK;
 }
 
 int fri_hip_plan_destroy(fri_hip_plan *p) {
-    if (!p) return FRI_HIP_OK;
-    if (p->ctx) {
-        (void)hipSetDevice(p->ctx->device);
-        for (void *d : p->owned) (void)hipFree(d);
-        for (void *d : {(void *)p->d_pixels, (void *)p->d_coefs, (void *)p->d_bucket, (void *)p->d_prediction, (void *)p->d_hist, (void *)p->d_oob, (void *)p->d_fit_int, (void *)p->d_fit_dbl})
-            if (d) (void)hipFree(d);
-        free_slots(p);
-        for (auto &a : p->acc_slots) {
-            if (a.handed_over) (void)hipEventDestroy(a.handed_over);
-            for (void *d : {(void *)a.pred_acc, (void *)a.fit_acc, (void *)a.sums_int, (void *)a.sums_dbl, (void *)a.range, (void *)a.params})
-                if (d) (void)hipFree(d);
-        }
-        for (void *d : p->retired_acc) (void)hipFree(d);
-        for (void *d : {(void *)p->d_bucket_all, (void *)p->d_prediction_all, (void *)p->d_hist_all, (void *)p->d_oob_all})
-            if (d) (void)hipFree(d);
-        if (p->d_stream_order) (void)hipFree(p->d_stream_order);
-        if (p->d_stream_pos) (void)hipFree(p->d_stream_pos);
-        if (p->d_coefs16) (void)hipFree(p->d_coefs16);
-        if (p->ev_coefs16) (void)hipEventDestroy(p->ev_coefs16);
-        if (p->d_symbols) (void)hipFree(p->d_symbols);
-        if (p->h_fit) (void)hipHostFree(p->h_fit);
-        if (p->ev_fit) (void)hipEventDestroy(p->ev_fit);
-        if (p->ev_begin) (void)hipEventDestroy(p->ev_begin);
-        if (p->ev_end) (void)hipEventDestroy(p->ev_end);
-    }
+    if (p && p->ctx) (void)hipSetDevice(p->ctx->device); // the plan's owners free their resources on its device
     delete p;
     return FRI_HIP_OK;
 }
@@ -912,10 +938,12 @@ int fri_hip_transform_quant(fri_hip_plan *p, const uint8_t *pixels, const int32_
     QMatrix q;
     if (int rc = check_q(qmatrix, q)) return rc;
     HIP_TRY(p->ctx, hipSetDevice(p->ctx->device));
-    if (int rc = ensure_staging(p)) return rc;
-    HIP_TRY(p->ctx, hipMemcpy(p->d_pixels, pixels, fri_hip_plan_pixel_bytes(p), hipMemcpyHostToDevice));
-    HIP_TRY(p->ctx, launch_fwd_transform_quant(p->dev, 1, p->d_pixels, 0, p->d_coefs, 0, q, nullptr));
-    HIP_TRY(p->ctx, hipMemcpy(coefs, p->d_coefs, fri_hip_plan_coef_count(p) * sizeof(int32_t), hipMemcpyDeviceToHost));
+    auto &st = p->staging;
+    int rc;
+    if ((rc = grow(p->ctx, st.pixels, fri_hip_plan_pixel_bytes(p))) || (rc = grow(p->ctx, st.coefs, fri_hip_plan_coef_count(p)))) return rc;
+    HIP_TRY(p->ctx, hipMemcpy(st.pixels, pixels, fri_hip_plan_pixel_bytes(p), hipMemcpyHostToDevice));
+    HIP_TRY(p->ctx, launch_fwd_transform_quant(p->dev, 1, st.pixels, 0, st.coefs, 0, q, nullptr));
+    HIP_TRY(p->ctx, hipMemcpy(coefs, st.coefs, fri_hip_plan_coef_count(p) * sizeof(int32_t), hipMemcpyDeviceToHost));
     return FRI_HIP_OK;
 }
 
@@ -991,27 +1019,11 @@ fri_hip_plan *fri_hip_multi_plan(fri_hip_multi *m, uint32_t d) { return m && d <
 
 int fri_hip_multi_transform_quant(fri_hip_multi *m, uint32_t n_images, const uint8_t *const *pixels, const int32_t qmatrix[32], int32_t *const *coefs) {
     if (!m || !pixels || !coefs || !qmatrix) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    const uint32_t n_devices = (uint32_t)m->plans.size();
-    std::vector<int> rcs(n_devices, FRI_HIP_OK);
-    auto work = [&](uint32_t d) {
-        const uint32_t n = fri_hip_shard_size(n_images, d, n_devices);
-        if (!n) return;
-        std::vector<const uint8_t *> in(n);
-        std::vector<int32_t *> out(n);
-        for (uint32_t k = 0; k < n; k++) {
-            const uint32_t i = fri_hip_shard_image(k, d, n_devices);
-            in[k] = pixels[i];
-            out[k] = coefs[i];
-        }
-        rcs[d] = fri_hip_transform_quant_batch(m->plans[d], n, in.data(), qmatrix, out.data());
-    };
-    std::vector<std::thread> threads;
-    for (uint32_t d = 1; d < n_devices; d++) threads.emplace_back(work, d);
-    work(0); // the calling thread drives the first device
-    for (auto &t : threads) t.join();
-    for (int rc : rcs)
-        if (rc != FRI_HIP_OK) return rc;
-    return FRI_HIP_OK;
+    return run_shards(m, n_images, [&](fri_hip_plan *p, const std::vector<uint32_t> &images) {
+        const auto in = pick(pixels, images);
+        const auto out = pick(coefs, images);
+        return fri_hip_transform_quant_batch(p, (uint32_t)images.size(), in.data(), qmatrix, out.data());
+    });
 }
 
 // In a chain that goes straight from the forward kernel to the scan (parameters given: no fit in between) the forward kernel writes its coefficients with
@@ -1024,15 +1036,7 @@ static bool chain_wants_cached_coefficients(const fri_hip_plan *p, uint32_t n_im
 
 /* ---- prediction + histogram ----------------------------------------------------------------- */
 static int predict_launch(fri_hip_plan *p, const PredBatch &b, uint8_t *d_bucket, int32_t *d_prediction, uint32_t *d_hist, uint64_t *d_oob, int trust,
-                          hipStream_t stream) {
-    // The scan's histogram hand-over numbers its launches on the HOST (pred_serial below, a kernel argument): a captured launch would freeze that number, and from the
-    // second replay on the clearing workgroups' flags already hold it - nothing would order the clearing of the histogram before the other workgroups' adds any more
-    // (counts wiped or doubled). So a scan launch refuses to be captured, loudly, instead of recording something that must not be replayed.
-    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-    if (stream && hipStreamIsCapturing(stream, &capturing) == hipSuccess && capturing != hipStreamCaptureStatusNone) {
-        if (p->ctx) p->ctx->last_error = "the predict + histogram kernel cannot be captured into a HIP graph (its hand-over counts launches on the host): launch it on a stream";
-        return FRI_HIP_ERR_INVALID_ARGUMENT;
-    }
+                          hipStream_t stream) { // (the entry points have refused a capturing stream: refuse_capture)
     (void)hipGetLastError();
     const int slot = acquire_acc(p, stream, b.n_planes);
     if (slot < 0) return slot;
@@ -1069,6 +1073,7 @@ int fri_hip_predict_histogram_batch_dev(fri_hip_plan *p, uint32_t n_planes, cons
     b.coef_stride = coef_stride;
     b.out_stride = out_stride;
     b.params = reinterpret_cast<const PredictParams *>(d_params);
+    if (int rc = refuse_capture(p, (hipStream_t)stream)) return rc;
     return predict_launch(p, b, d_bucket, d_prediction, d_hist, d_n_out_of_alphabet, p->assume_forward ? kPredPromised : kPredAnyInt32, (hipStream_t)stream);
 }
 
@@ -1081,6 +1086,7 @@ int fri_hip_predict_histogram_dev(fri_hip_plan *p, const int32_t *d_coefs, uint3
     std::memcpy(b.pp[0].value, value_params, sizeof(b.pp[0].value));
     std::memcpy(b.pp[0].width, width_params, sizeof(b.pp[0].width));
     b.coefs = d_coefs + (size_t)channel * p->geo.centers.size() * kCell;
+    if (int rc = refuse_capture(p, (hipStream_t)stream)) return rc;
     return predict_launch(p, b, d_bucket, d_prediction, d_hist, d_n_out_of_alphabet, p->assume_forward ? kPredPromised : kPredAnyInt32, (hipStream_t)stream);
 }
 
@@ -1090,17 +1096,21 @@ int fri_hip_predict_histogram(fri_hip_plan *p, const int32_t *coefs, uint32_t ch
     if (int rc = need_device(p)) return rc;
     if (!coefs || !hist || channel >= p->geo.channels) return FRI_HIP_ERR_INVALID_ARGUMENT;
     HIP_TRY(p->ctx, hipSetDevice(p->ctx->device));
-    if (int rc = ensure_staging(p)) return rc;
-    const size_t F = p->geo.centers.size();
-    HIP_TRY(p->ctx, hipMemcpy(p->d_coefs, coefs, fri_hip_plan_coef_count(p) * sizeof(int32_t), hipMemcpyHostToDevice));
-    if (int rc = fri_hip_predict_histogram_dev(p, p->d_coefs, channel, value_params, width_params, bucket ? p->d_bucket : nullptr,
-                                               prediction ? p->d_prediction : nullptr, p->d_hist, (uint64_t *)p->d_oob, nullptr))
+    const size_t plane = p->geo.centers.size() * kCell;
+    auto &st = p->staging;
+    int rc;
+    if ((rc = grow(p->ctx, st.coefs, fri_hip_plan_coef_count(p))) || (rc = grow(p->ctx, st.bucket, bucket ? plane : 0)) ||
+        (rc = grow(p->ctx, st.prediction, prediction ? plane : 0)) || (rc = grow(p->ctx, st.hist, 10 * 1024)) || (rc = grow(p->ctx, st.oob, 1)))
         return rc;
-    HIP_TRY(p->ctx, hipMemcpy(hist, p->d_hist, 10 * 1024 * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (bucket) HIP_TRY(p->ctx, hipMemcpy(bucket, p->d_bucket, F * kCell, hipMemcpyDeviceToHost));
-    if (prediction) HIP_TRY(p->ctx, hipMemcpy(prediction, p->d_prediction, F * kCell * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(p->ctx, hipMemcpy(st.coefs, coefs, fri_hip_plan_coef_count(p) * sizeof(int32_t), hipMemcpyHostToDevice));
+    if ((rc = fri_hip_predict_histogram_dev(p, st.coefs, channel, value_params, width_params, bucket ? st.bucket.get() : nullptr, prediction ? st.prediction.get() : nullptr,
+                                            st.hist, (uint64_t *)st.oob.get(), nullptr)))
+        return rc;
+    HIP_TRY(p->ctx, hipMemcpy(hist, st.hist, 10 * 1024 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (bucket) HIP_TRY(p->ctx, hipMemcpy(bucket, st.bucket, plane, hipMemcpyDeviceToHost));
+    if (prediction) HIP_TRY(p->ctx, hipMemcpy(prediction, st.prediction, plane * sizeof(int32_t), hipMemcpyDeviceToHost));
     unsigned long long oob = 0;
-    HIP_TRY(p->ctx, hipMemcpy(&oob, p->d_oob, sizeof(oob), hipMemcpyDeviceToHost));
+    HIP_TRY(p->ctx, hipMemcpy(&oob, st.oob, sizeof(oob), hipMemcpyDeviceToHost));
     if (n_out_of_alphabet) *n_out_of_alphabet = oob;
     return FRI_HIP_OK;
 }
@@ -1151,16 +1161,17 @@ int fri_hip_fit_value_sums(fri_hip_plan *p, const int32_t *coefs, uint32_t chann
     if (int rc = need_device(p)) return rc;
     if (!coefs || !gram || channel >= p->geo.channels) return FRI_HIP_ERR_INVALID_ARGUMENT;
     HIP_TRY(p->ctx, hipSetDevice(p->ctx->device));
-    if (int rc = ensure_staging(p)) return rc;
-    HIP_TRY(p->ctx, hipMemcpy(p->d_coefs, coefs, fri_hip_plan_coef_count(p) * sizeof(int32_t), hipMemcpyHostToDevice));
-    {
-        PredBatch b;
-        b.coefs = p->d_coefs + (size_t)channel * p->geo.centers.size() * kCell;
-        if (int rc = fit_launch(p, 0, b, (int64_t *)p->d_fit_int, nullptr, p->d_oob, nullptr)) return rc;
-    }
-    HIP_TRY(p->ctx, hipMemcpy(gram, p->d_fit_int, 3 * 28 * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (int rc = grow(p->ctx, p->staging.coefs, fri_hip_plan_coef_count(p))) return rc;
+    HIP_TRY(p->ctx, hipMemcpy(p->staging.coefs, coefs, fri_hip_plan_coef_count(p) * sizeof(int32_t), hipMemcpyHostToDevice));
+    const int slot = acquire_acc(p, nullptr); // the null stream's fit scratch (fit_chain's) takes the sums and the range count
+    if (slot < 0) return slot;
+    auto &k = p->acc_slots[slot];
+    PredBatch b;
+    b.coefs = p->staging.coefs + (size_t)channel * p->geo.centers.size() * kCell;
+    if (int rc = fit_launch(p, 0, b, (int64_t *)k.sums_int.get(), nullptr, k.range, nullptr)) return rc;
+    HIP_TRY(p->ctx, hipMemcpy(gram, k.sums_int, 3 * 28 * sizeof(int64_t), hipMemcpyDeviceToHost));
     unsigned long long out_of_range = 0;
-    HIP_TRY(p->ctx, hipMemcpy(&out_of_range, p->d_oob, sizeof(out_of_range), hipMemcpyDeviceToHost));
+    HIP_TRY(p->ctx, hipMemcpy(&out_of_range, k.range, sizeof(out_of_range), hipMemcpyDeviceToHost));
     return out_of_range ? FRI_HIP_ERR_OUT_OF_RANGE : FRI_HIP_OK;
 }
 
@@ -1169,19 +1180,20 @@ int fri_hip_fit_width_sums(fri_hip_plan *p, const int32_t *coefs, uint32_t chann
     if (int rc = need_device(p)) return rc;
     if (!coefs || !value_params || !wtw || !wtr || channel >= p->geo.channels) return FRI_HIP_ERR_INVALID_ARGUMENT;
     HIP_TRY(p->ctx, hipSetDevice(p->ctx->device));
-    if (int rc = ensure_staging(p)) return rc;
-    HIP_TRY(p->ctx, hipMemcpy(p->d_coefs, coefs, fri_hip_plan_coef_count(p) * sizeof(int32_t), hipMemcpyHostToDevice));
-    {
-        PredBatch b;
-        std::memcpy(b.pp[0].value, value_params, sizeof(b.pp[0].value));
-        b.coefs = p->d_coefs + (size_t)channel * p->geo.centers.size() * kCell;
-        if (int rc = fit_launch(p, 1, b, (int64_t *)p->d_fit_int, p->d_fit_dbl, p->d_oob, nullptr)) return rc;
-    }
+    if (int rc = grow(p->ctx, p->staging.coefs, fri_hip_plan_coef_count(p))) return rc;
+    HIP_TRY(p->ctx, hipMemcpy(p->staging.coefs, coefs, fri_hip_plan_coef_count(p) * sizeof(int32_t), hipMemcpyHostToDevice));
+    const int slot = acquire_acc(p, nullptr); // (as above)
+    if (slot < 0) return slot;
+    auto &k = p->acc_slots[slot];
+    PredBatch b;
+    std::memcpy(b.pp[0].value, value_params, sizeof(b.pp[0].value));
+    b.coefs = p->staging.coefs + (size_t)channel * p->geo.centers.size() * kCell;
+    if (int rc = fit_launch(p, 1, b, (int64_t *)k.sums_int.get(), k.sums_dbl, k.range, nullptr)) return rc;
     unsigned long long out_of_range = 0;
-    HIP_TRY(p->ctx, hipMemcpy(&out_of_range, p->d_oob, sizeof(out_of_range), hipMemcpyDeviceToHost));
+    HIP_TRY(p->ctx, hipMemcpy(&out_of_range, k.range, sizeof(out_of_range), hipMemcpyDeviceToHost));
     if (out_of_range) return FRI_HIP_ERR_OUT_OF_RANGE;
-    HIP_TRY(p->ctx, hipMemcpy(wtw, p->d_fit_int, 3 * 21 * sizeof(int64_t), hipMemcpyDeviceToHost));
-    HIP_TRY(p->ctx, hipMemcpy(wtr, p->d_fit_dbl, 18 * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(p->ctx, hipMemcpy(wtw, k.sums_int, 3 * 21 * sizeof(int64_t), hipMemcpyDeviceToHost));
+    HIP_TRY(p->ctx, hipMemcpy(wtr, k.sums_dbl, 18 * sizeof(double), hipMemcpyDeviceToHost));
     if (rows) { // num_ctx_last_layer / num_ctx_middle_layer, context_modeling.rs:84-85
         const uint64_t F = p->geo.centers.size();
         rows[0] = F * 256;
@@ -1211,38 +1223,37 @@ void fri_hip_fit_width_params(const int64_t wtw[3][21], const double wtr[3][6], 
 }
 
 /* ---- the device part of FRIEncoder::encode in one call ------------------------------------------------ */
-// the plan's compact coefficient planes for `planes` planes (grown, never shrunk; a growing call waits for the device: hipFree synchronises)
-static int ensure_coefs16(fri_hip_plan *p, size_t planes) {
-    if (p->coefs16_planes >= planes) return FRI_HIP_OK;
-    fri_hip_ctx *c = p->ctx;
-    if (p->d_coefs16) {
-        HIP_TRY(c, hipFree(p->d_coefs16));
-        p->d_coefs16 = nullptr, p->coefs16_planes = 0;
+// A chain's hold on the plan's compact coefficient planes. The planes belong to one chain at a time. Chains on one stream are ordered by it; a chain on another
+// stream first waits for the event the previous one left. Taking the lease grows the planes to `planes` planes (never shrunk; a growing call waits for the
+// device: hipFree synchronises) and queues that wait; the lease leaves this chain's event on every way out, an error included - once K1 is queued the planes
+// are in use whatever the chain returns.
+class Coefs16Lease {
+  public:
+    Coefs16Lease(fri_hip_plan *p, hipStream_t s, size_t planes) : p_(p), s_(s) { rc = take(planes); }
+    ~Coefs16Lease() {
+        if (rc) return;
+        p_->coefs16_stream = s_, p_->coefs16_used = true;
+        if (hipEventRecord(p_->ev_coefs16, s_) != hipSuccess) { // nothing to wait for: let the chain drain instead, the next one finds the planes free
+            (void)hipGetLastError();
+            (void)hipDeviceSynchronize();
+            p_->coefs16_used = false;
+        }
     }
-    HIP_TRY(c, hipMalloc((void **)&p->d_coefs16, planes * p->geo.centers.size() * kCell * sizeof(int16_t)));
-    p->coefs16_planes = planes;
-    return FRI_HIP_OK;
-}
-// The planes belong to one chain at a time. Chains on one stream are ordered by it; a chain on another stream first waits for the event the previous one left.
-static int coefs16_begin(fri_hip_plan *p, hipStream_t s) {
-    if (p->coefs16_used && p->coefs16_stream != s && p->ev_coefs16) HIP_TRY(p->ctx, hipStreamWaitEvent(s, p->ev_coefs16, 0));
-    return FRI_HIP_OK;
-}
-static int coefs16_end(fri_hip_plan *p, hipStream_t s) {
-    if (!p->ev_coefs16) HIP_TRY(p->ctx, hipEventCreateWithFlags(&p->ev_coefs16, hipEventDisableTiming));
-    HIP_TRY(p->ctx, hipEventRecord(p->ev_coefs16, s));
-    p->coefs16_stream = s, p->coefs16_used = true;
-    return FRI_HIP_OK;
-}
-static int ensure_encode_staging(fri_hip_plan *p, bool node_arrays = true) {
-    fri_hip_ctx *c = p->ctx;
-    const size_t C = p->geo.channels, plane = p->geo.centers.size() * kCell;
-    if (node_arrays && !p->d_bucket_all) HIP_TRY(c, hipMalloc((void **)&p->d_bucket_all, C * plane));
-    if (node_arrays && !p->d_prediction_all) HIP_TRY(c, hipMalloc((void **)&p->d_prediction_all, C * plane * sizeof(int32_t)));
-    if (!p->d_hist_all) HIP_TRY(c, hipMalloc((void **)&p->d_hist_all, C * 10 * 1024 * sizeof(uint32_t)));
-    if (!p->d_oob_all) HIP_TRY(c, hipMalloc((void **)&p->d_oob_all, C * sizeof(unsigned long long)));
-    return FRI_HIP_OK;
-}
+    Coefs16Lease(const Coefs16Lease &) = delete;
+    Coefs16Lease &operator=(const Coefs16Lease &) = delete;
+    int rc; // FRI_HIP_OK: the lease is held
+
+  private:
+    int take(size_t planes) {
+        fri_hip_ctx *c = p_->ctx;
+        if (int r = grow(c, p_->coefs16, planes * p_->geo.centers.size() * kCell)) return r;
+        if (!p_->ev_coefs16) HIP_TRY(c, hipEventCreateWithFlags(p_->ev_coefs16.put(), hipEventDisableTiming));
+        if (p_->coefs16_used && p_->coefs16_stream != s_) HIP_TRY(c, hipStreamWaitEvent(s_, p_->ev_coefs16, 0));
+        return FRI_HIP_OK;
+    }
+    fri_hip_plan *p_;
+    hipStream_t s_;
+};
 
 // ContextModeler::optimize_parameters for the planes of `b` (prediction.rs:232-235, context_modeling.rs:204-213), entirely on the device and
 // without a word to the host: value sums -> 6 x 6 solves -> width sums (with the value parameters just written) -> solves. The parameters land
@@ -1263,9 +1274,9 @@ static int fit_chain(fri_hip_plan *p, const PredBatch &b, unsigned long long *d_
     FitSolve solve;
     solve.params = params, solve.host_params = host_params, solve.host_range = host_range;
     for (int g = 0; g < 3; g++) solve.rows[g] = rows[g];
-    if (int rc = fit_launch(p, 0, b, (int64_t *)k.sums_int, nullptr, range, s, &solve, trust)) return rc;
+    if (int rc = fit_launch(p, 0, b, (int64_t *)k.sums_int.get(), nullptr, range, s, &solve, trust)) return rc;
     solve.host_range = nullptr; // (the width pass does not count)
-    return fit_launch(p, 1, b, (int64_t *)k.sums_int, k.sums_dbl, nullptr, s, &solve, trust);
+    return fit_launch(p, 1, b, (int64_t *)k.sums_int.get(), k.sums_dbl, nullptr, s, &solve, trust);
 }
 
 // prediction::encode for all channels of one image whose coefficients are in device memory (prediction.rs:224-323 minus the host's ANS
@@ -1297,28 +1308,19 @@ static int predict_image_dev(fri_hip_plan *p, const int32_t *d_coefs, int fit, f
     if (slot < 0) return slot;
     auto &k = p->acc_slots[slot];
     constexpr size_t kFitBytes = 3 * sizeof(PredictParams) + 3 * sizeof(unsigned long long);
-    if (!p->h_fit) { // mapped and fine-grained: the solve kernels write the parameters straight into it
-        HIP_TRY(c, hipHostMalloc(&p->h_fit, kFitBytes, hipHostMallocMapped | hipHostMallocCoherent));
+    if (!p->d_h_fit) { // mapped and fine-grained: the solve kernels write the parameters straight into it
+        HIP_TRY(c, hipHostMalloc(p->h_fit.put(), kFitBytes, hipHostMallocMapped | hipHostMallocCoherent));
         std::memset(p->h_fit, 0, kFitBytes);
         HIP_TRY(c, hipHostGetDevicePointer(&p->d_h_fit, p->h_fit, 0));
     }
-    if (!p->ev_fit) HIP_TRY(c, hipEventCreateWithFlags(&p->ev_fit, hipEventDisableTiming));
-    b.params = reinterpret_cast<const PredictParams *>(k.params);
-    char *const h = static_cast<char *>(p->h_fit), *const dh = static_cast<char *>(p->d_h_fit);
+    if (!p->ev_fit) HIP_TRY(c, hipEventCreateWithFlags(p->ev_fit.put(), hipEventDisableTiming));
+    b.params = reinterpret_cast<const PredictParams *>(k.params.get());
+    char *const h = static_cast<char *>(p->h_fit.get()), *const dh = static_cast<char *>(p->d_h_fit);
     if (int rc = fit_chain(p, b, k.range, s, reinterpret_cast<float *>(dh), reinterpret_cast<unsigned long long *>(dh + 3 * sizeof(PredictParams)), trust)) return rc;
     HIP_TRY(c, hipEventRecord(p->ev_fit, s));
     // the scan is queued before the host looks at the fit: it runs while the host picks the parameters up
     const int rc_scan = predict_launch(p, b, d_bucket, d_prediction, d_hist, d_oob, trust, s);
-    // poll: a sleeping wait (hipEventSynchronize) wakes up 15-20 us late, a tenth of the chain
-    for (uint64_t spins = 0;; spins++) {
-        const hipError_t q = hipEventQuery(p->ev_fit);
-        if (q == hipSuccess) break;
-        if (q != hipErrorNotReady) HIP_TRY(c, q);
-        if (spins > (1ull << 22)) {
-            HIP_TRY(c, hipEventSynchronize(p->ev_fit));
-            break;
-        }
-    }
+    if (int rc = wait_event_polling(c, p->ev_fit)) return rc;
     std::atomic_thread_fence(std::memory_order_acquire);
     const unsigned long long *h_range = reinterpret_cast<const unsigned long long *>(h + 3 * sizeof(PredictParams));
     const PredictParams *h_params = reinterpret_cast<const PredictParams *>(h);
@@ -1337,6 +1339,7 @@ int fri_hip_encode_image_dev(fri_hip_plan *p, const uint8_t *d_pixels, const int
     if (!d_pixels || !value_params || !width_params || !d_coefs || !d_hist || !d_n_out_of_alphabet) return FRI_HIP_ERR_INVALID_ARGUMENT;
     QMatrix q;
     if (int rc = check_q(qmatrix, q)) return rc;
+    if (int rc = refuse_capture(p, (hipStream_t)stream)) return rc;
     HIP_TRY(p->ctx, hipSetDevice(p->ctx->device));
     // wavelet_transform::encode + quantization::encode (encoder.rs:24-31): one kernel, all channels; the coefficients then stay where they are
     HIP_TRY(p->ctx, launch_fwd_transform_quant(p->dev, 1, d_pixels, 0, d_coefs, 0, q, (hipStream_t)stream, chain_wants_cached_coefficients(p, 1, fit)));
@@ -1358,8 +1361,9 @@ int fri_hip_encode_image_batch_dev(fri_hip_plan *p, uint32_t n_images, const uin
     if (C > 1 && n_images > 1 && (coef_stride != image || ((d_bucket || d_prediction) && out_stride != image))) return FRI_HIP_ERR_INVALID_ARGUMENT;
     QMatrix q;
     if (int rc = check_q(qmatrix, q)) return rc;
-    HIP_TRY(p->ctx, hipSetDevice(p->ctx->device));
     hipStream_t s = (hipStream_t)stream;
+    if (int rc = refuse_capture(p, s)) return rc;
+    HIP_TRY(p->ctx, hipSetDevice(p->ctx->device));
     HIP_TRY(p->ctx, launch_fwd_transform_quant(p->dev, n_images, d_pixels, pixel_stride, d_coefs, coef_stride, q, s, chain_wants_cached_coefficients(p, n_images, fit)));
     PredBatch b;
     b.n_planes = n_images * C;
@@ -1392,18 +1396,17 @@ int fri_hip_encode_symbols_batch_dev(fri_hip_plan *p, uint32_t n_images, const u
     if (C > 1 && n_images > 1 && (coef_stride != image || word_stride != image || symbol_stride != (size_t)C * n)) return FRI_HIP_ERR_INVALID_ARGUMENT;
     QMatrix q;
     if (int rc = check_q(qmatrix, q)) return rc;
-    HIP_TRY(p->ctx, hipSetDevice(p->ctx->device));
     hipStream_t s = (hipStream_t)stream;
-    if (compact) {
-        if (int rc = ensure_coefs16(p, (size_t)n_images * C)) return rc;
-        if (int rc = coefs16_begin(p, s)) return rc;
-    }
+    if (int rc = refuse_capture(p, s)) return rc;
+    HIP_TRY(p->ctx, hipSetDevice(p->ctx->device));
+    std::optional<Coefs16Lease> lease; // (held to the end: the scan is the planes' last reader, and the event sits behind the gather, later than it must be, at no cost)
+    if (compact && lease.emplace(p, s, (size_t)n_images * C).rc) return lease->rc;
     HIP_TRY(p->ctx, launch_fwd_transform_quant(p->dev, n_images, d_pixels, pixel_stride, d_coefs, coef_stride, q, s, chain_wants_cached_coefficients(p, n_images, fit),
-                                               compact ? p->d_coefs16 : nullptr));
+                                               compact ? p->coefs16.get() : nullptr));
     PredBatch b;
     b.n_planes = n_images * C;
     b.coefs = d_coefs;
-    b.coefs16 = compact ? p->d_coefs16 : nullptr;
+    b.coefs16 = compact ? p->coefs16.get() : nullptr;
     b.coef_stride = C > 1 || compact ? plane : coef_stride;
     b.out_stride = C > 1 ? plane : word_stride;
     b.params = reinterpret_cast<const PredictParams *>(d_params);
@@ -1413,8 +1416,6 @@ int fri_hip_encode_symbols_batch_dev(fri_hip_plan *p, uint32_t n_images, const u
         if (int rc = fit_chain(p, b, (unsigned long long *)d_fit_out_of_range, s, nullptr, nullptr, kPredForwardOutput)) return rc;
     if (int rc = predict_launch(p, b, nullptr, nullptr, d_hist, d_n_out_of_alphabet, kPredForwardOutput, s)) return rc;
     if (!direct) HIP_TRY(p->ctx, launch_symbol_gather(p->d_stream_order, n, b.n_planes, d_node_words, b.out_stride, d_symbols, C > 1 ? n : symbol_stride, s));
-    if (compact) // (the scan was the planes' last reader; the event sits behind the gather, which is later than it must be and costs nothing)
-        if (int rc = coefs16_end(p, s)) return rc;
     return FRI_HIP_OK;
 }
 
@@ -1452,6 +1453,7 @@ int fri_hip_predict_image_dev(fri_hip_plan *p, const int32_t *d_coefs, int fit, 
                               uint32_t *d_hist, uint64_t *d_n_out_of_alphabet, void *stream) {
     if (int rc = need_device(p)) return rc;
     if (!d_coefs || !value_params || !width_params || !d_hist || !d_n_out_of_alphabet) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    if (int rc = refuse_capture(p, (hipStream_t)stream)) return rc;
     HIP_TRY(p->ctx, hipSetDevice(p->ctx->device));
     return predict_image_dev(p, d_coefs, fit, value_params, width_params, d_bucket, d_prediction, d_hist, d_n_out_of_alphabet, kPredAnyInt32, (hipStream_t)stream);
 }
@@ -1462,17 +1464,20 @@ int fri_hip_predict_image(fri_hip_plan *p, const int32_t *coefs, int fit, float 
     if (!coefs || !value_params || !width_params || !hist || !n_out_of_alphabet) return FRI_HIP_ERR_INVALID_ARGUMENT;
     fri_hip_ctx *c = p->ctx;
     HIP_TRY(c, hipSetDevice(c->device));
-    if (int rc = ensure_staging(p)) return rc;
-    if (int rc = ensure_encode_staging(p)) return rc;
     const size_t C = p->geo.channels, plane = p->geo.centers.size() * kCell;
-    HIP_TRY(c, hipMemcpy(p->d_coefs, coefs, C * plane * sizeof(int32_t), hipMemcpyHostToDevice)); // once, for the fit and the scan of every channel
-    if (int rc = predict_image_dev(p, p->d_coefs, fit, value_params, width_params, bucket ? p->d_bucket_all : nullptr, prediction ? p->d_prediction_all : nullptr, p->d_hist_all,
-                                   (uint64_t *)p->d_oob_all, kPredAnyInt32, nullptr))
+    auto &st = p->staging;
+    int rc;
+    if ((rc = grow(c, st.coefs, C * plane)) || (rc = grow(c, st.bucket, bucket ? C * plane : 0)) || (rc = grow(c, st.prediction, prediction ? C * plane : 0)) ||
+        (rc = grow(c, st.hist, C * 10 * 1024)) || (rc = grow(c, st.oob, C)))
         return rc;
-    if (bucket) HIP_TRY(c, hipMemcpy(bucket, p->d_bucket_all, C * plane, hipMemcpyDeviceToHost));
-    if (prediction) HIP_TRY(c, hipMemcpy(prediction, p->d_prediction_all, C * plane * sizeof(int32_t), hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(hist, p->d_hist_all, C * 10 * 1024 * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(n_out_of_alphabet, p->d_oob_all, C * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(st.coefs, coefs, C * plane * sizeof(int32_t), hipMemcpyHostToDevice)); // once, for the fit and the scan of every channel
+    if ((rc = predict_image_dev(p, st.coefs, fit, value_params, width_params, bucket ? st.bucket.get() : nullptr, prediction ? st.prediction.get() : nullptr, st.hist,
+                                (uint64_t *)st.oob.get(), kPredAnyInt32, nullptr)))
+        return rc;
+    if (bucket) HIP_TRY(c, hipMemcpy(bucket, st.bucket, C * plane, hipMemcpyDeviceToHost));
+    if (prediction) HIP_TRY(c, hipMemcpy(prediction, st.prediction, C * plane * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(hist, st.hist, C * 10 * 1024 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(n_out_of_alphabet, st.oob, C * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return FRI_HIP_OK;
 }
 
@@ -1482,19 +1487,22 @@ int fri_hip_encode_image(fri_hip_plan *p, const uint8_t *pixels, const int32_t q
     if (!pixels || !value_params || !width_params || !coefs || !hist || !n_out_of_alphabet) return FRI_HIP_ERR_INVALID_ARGUMENT;
     fri_hip_ctx *c = p->ctx;
     HIP_TRY(c, hipSetDevice(c->device));
-    if (int rc = ensure_staging(p)) return rc;
-    if (int rc = ensure_encode_staging(p)) return rc;
     const size_t C = p->geo.channels, plane = p->geo.centers.size() * kCell;
-    // one upload of the pixels, one download of each output; the coefficients stay on the device between the stages
-    HIP_TRY(c, hipMemcpy(p->d_pixels, pixels, fri_hip_plan_pixel_bytes(p), hipMemcpyHostToDevice));
-    if (int rc = fri_hip_encode_image_dev(p, p->d_pixels, qmatrix, fit, value_params, width_params, p->d_coefs, bucket ? p->d_bucket_all : nullptr,
-                                          prediction ? p->d_prediction_all : nullptr, p->d_hist_all, (uint64_t *)p->d_oob_all, nullptr))
+    auto &st = p->staging;
+    int rc;
+    if ((rc = grow(c, st.pixels, fri_hip_plan_pixel_bytes(p))) || (rc = grow(c, st.coefs, C * plane)) || (rc = grow(c, st.bucket, bucket ? C * plane : 0)) ||
+        (rc = grow(c, st.prediction, prediction ? C * plane : 0)) || (rc = grow(c, st.hist, C * 10 * 1024)) || (rc = grow(c, st.oob, C)))
         return rc;
-    HIP_TRY(c, hipMemcpy(coefs, p->d_coefs, C * plane * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (bucket) HIP_TRY(c, hipMemcpy(bucket, p->d_bucket_all, C * plane, hipMemcpyDeviceToHost));
-    if (prediction) HIP_TRY(c, hipMemcpy(prediction, p->d_prediction_all, C * plane * sizeof(int32_t), hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(hist, p->d_hist_all, C * 10 * 1024 * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(n_out_of_alphabet, p->d_oob_all, C * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    // one upload of the pixels, one download of each output; the coefficients stay on the device between the stages
+    HIP_TRY(c, hipMemcpy(st.pixels, pixels, fri_hip_plan_pixel_bytes(p), hipMemcpyHostToDevice));
+    if ((rc = fri_hip_encode_image_dev(p, st.pixels, qmatrix, fit, value_params, width_params, st.coefs, bucket ? st.bucket.get() : nullptr,
+                                       prediction ? st.prediction.get() : nullptr, st.hist, (uint64_t *)st.oob.get(), nullptr)))
+        return rc;
+    HIP_TRY(c, hipMemcpy(coefs, st.coefs, C * plane * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (bucket) HIP_TRY(c, hipMemcpy(bucket, st.bucket, C * plane, hipMemcpyDeviceToHost));
+    if (prediction) HIP_TRY(c, hipMemcpy(prediction, st.prediction, C * plane * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(hist, st.hist, C * 10 * 1024 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(n_out_of_alphabet, st.oob, C * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return FRI_HIP_OK;
 }
 
@@ -1539,7 +1547,7 @@ int fri_hip_encode_image_batch(fri_hip_plan *p, uint32_t n_images, const uint8_t
             HIP_TRY(c, hipMemcpyAsync(s.d_params, s.h_params, C * sizeof(PredictParams), hipMemcpyHostToDevice, s.stream));
         }
         if (int rc = fri_hip_encode_image_batch_dev(p, 1, s.d_pixels, 0, qmatrix, fit, s.d_params, s.d_coefs, 0, bucket && bucket[i] ? s.d_bucket : nullptr,
-                                                    prediction && prediction[i] ? s.d_prediction : nullptr, 0, s.d_hist, (uint64_t *)s.d_oob, (uint64_t *)(s.d_oob + C), s.stream))
+                                                    prediction && prediction[i] ? s.d_prediction : nullptr, 0, s.d_hist, (uint64_t *)s.d_oob.get(), (uint64_t *)(s.d_oob + C), s.stream))
             return rc;
         HIP_TRY(c, hipMemcpyAsync(s.h_coefs, s.d_coefs, n * sizeof(int32_t), hipMemcpyDeviceToHost, s.stream));
         if (bucket && bucket[i]) HIP_TRY(c, hipMemcpyAsync(s.h_bucket, s.d_bucket, n, hipMemcpyDeviceToHost, s.stream));
@@ -1558,32 +1566,16 @@ int fri_hip_encode_image_batch(fri_hip_plan *p, uint32_t n_images, const uint8_t
 int fri_hip_multi_encode_image(fri_hip_multi *m, uint32_t n_images, const uint8_t *const *pixels, const int32_t qmatrix[32], int fit, float *const *params,
                                int32_t *const *coefs, uint8_t *const *bucket, int32_t *const *prediction, uint32_t *const *hist, uint64_t *const *n_out_of_alphabet) {
     if (!m || !pixels || !params || !coefs || !hist || !n_out_of_alphabet || !qmatrix) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    const uint32_t n_devices = (uint32_t)m->plans.size();
-    std::vector<int> rcs(n_devices, FRI_HIP_OK);
-    auto work = [&](uint32_t d) {
-        const uint32_t n = fri_hip_shard_size(n_images, d, n_devices);
-        if (!n) return;
-        std::vector<const uint8_t *> in(n);
-        std::vector<float *> par(n);
-        std::vector<int32_t *> co(n), pr(n);
-        std::vector<uint8_t *> bu(n);
-        std::vector<uint32_t *> hi(n);
-        std::vector<uint64_t *> oo(n);
-        for (uint32_t k = 0; k < n; k++) {
-            const uint32_t i = fri_hip_shard_image(k, d, n_devices);
-            in[k] = pixels[i], par[k] = params[i], co[k] = coefs[i], hi[k] = hist[i], oo[k] = n_out_of_alphabet[i];
-            bu[k] = bucket ? bucket[i] : nullptr, pr[k] = prediction ? prediction[i] : nullptr;
-        }
-        rcs[d] = fri_hip_encode_image_batch(m->plans[d], n, in.data(), qmatrix, fit, par.data(), co.data(), bucket ? bu.data() : nullptr, prediction ? pr.data() : nullptr, hi.data(),
-                                            oo.data());
-    };
-    std::vector<std::thread> threads;
-    for (uint32_t d = 1; d < n_devices; d++) threads.emplace_back(work, d);
-    work(0); // the calling thread drives the first device
-    for (auto &t : threads) t.join();
-    for (int rc : rcs)
-        if (rc != FRI_HIP_OK) return rc;
-    return FRI_HIP_OK;
+    return run_shards(m, n_images, [&](fri_hip_plan *p, const std::vector<uint32_t> &images) {
+        const auto in = pick(pixels, images);
+        const auto par = pick(params, images);
+        const auto co = pick(coefs, images), pr = pick(prediction, images);
+        const auto bu = pick(bucket, images);
+        const auto hi = pick(hist, images);
+        const auto oo = pick(n_out_of_alphabet, images);
+        return fri_hip_encode_image_batch(p, (uint32_t)images.size(), in.data(), qmatrix, fit, par.data(), co.data(), bucket ? bu.data() : nullptr,
+                                          prediction ? pr.data() : nullptr, hi.data(), oo.data());
+    });
 }
 
 /* ---- the ordered symbol stream (K5) ------------------------------------------------------------------------- */
@@ -1600,14 +1592,16 @@ int fri_hip_plan_set_stream_order(fri_hip_plan *p, const uint32_t *order, uint64
     }
     fri_hip_ctx *c = p->ctx;
     HIP_TRY(c, hipSetDevice(c->device));
-    if (!p->d_stream_order) HIP_TRY(c, hipMalloc((void **)&p->d_stream_order, (n ? n : 1) * sizeof(uint32_t)));
-    HIP_TRY(c, hipMemcpy(p->d_stream_order, order, n * sizeof(uint32_t), hipMemcpyHostToDevice));
-    { // the inverse: where a node's symbol sits in the stream (the scan writes the stream directly when nobody asks for the node words)
-        std::vector<uint32_t> pos(F * kCell, 0xFFFFFFFFu);
-        for (uint64_t i = 0; i < n; i++) pos[order[i]] = (uint32_t)i;
-        if (!p->d_stream_pos) HIP_TRY(c, hipMalloc((void **)&p->d_stream_pos, pos.size() * sizeof(uint32_t)));
-        HIP_TRY(c, hipMemcpy(p->d_stream_pos, pos.data(), pos.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    }
+    // the inverse: where a node's symbol sits in the stream (the scan writes the stream directly when nobody asks for the node words)
+    std::vector<uint32_t> pos(F * kCell, 0xFFFFFFFFu);
+    for (uint64_t i = 0; i < n; i++) pos[order[i]] = (uint32_t)i;
+    // both tables are uploaded to new buffers and replace the plan's together, or not at all (the old ones go then: hipFree waits for the chains reading them)
+    DevMem<uint32_t> d_order, d_pos;
+    HIP_TRY(c, hipMalloc((void **)d_order.put(), (n ? n : 1) * sizeof(uint32_t)));
+    HIP_TRY(c, hipMemcpy(d_order, order, n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMalloc((void **)d_pos.put(), pos.size() * sizeof(uint32_t)));
+    HIP_TRY(c, hipMemcpy(d_pos, pos.data(), pos.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    p->d_stream_order = std::move(d_order), p->d_stream_pos = std::move(d_pos);
     return FRI_HIP_OK;
 }
 
@@ -1632,25 +1626,28 @@ int fri_hip_encode_image_symbols(fri_hip_plan *p, const uint8_t *pixels, const i
     if (!pixels || !value_params || !width_params || !symbols || !hist || !n_out_of_alphabet || !p->d_stream_order) return FRI_HIP_ERR_INVALID_ARGUMENT;
     fri_hip_ctx *c = p->ctx;
     HIP_TRY(c, hipSetDevice(c->device));
-    if (!p->d_pixels) HIP_TRY(c, hipMalloc((void **)&p->d_pixels, fri_hip_plan_pixel_bytes(p))); // (of the single-image staging only the pixels: no int32 planes, no node arrays here)
-    if (int rc = ensure_encode_staging(p, false)) return rc;
     const size_t C = p->geo.channels, n = p->geo.n_some;
-    if (!p->d_symbols) HIP_TRY(c, hipMalloc((void **)&p->d_symbols, (C * n ? C * n : 1) * sizeof(uint16_t)));
-    QMatrix q;
-    if (int rc = check_q(qmatrix, q)) return rc;
-    HIP_TRY(c, hipMemcpy(p->d_pixels, pixels, fri_hip_plan_pixel_bytes(p), hipMemcpyHostToDevice));
-    // nobody outside sees the coefficients of this call: compact planes (int16, None as 0) between the forward kernel, the fit and the scan
-    if (int rc = ensure_coefs16(p, C)) return rc;
-    if (int rc = coefs16_begin(p, nullptr)) return rc;
-    HIP_TRY(c, launch_fwd_transform_quant(p->dev, 1, p->d_pixels, 0, nullptr, 0, q, nullptr, false, p->d_coefs16));
-    // the scan in its stream form: no bucket / prediction arrays, no node words, no gather kernel - every symbol goes straight to its place in its channel's stream
-    if (int rc = predict_image_dev(p, nullptr, fit, value_params, width_params, nullptr, nullptr, p->d_hist_all, (uint64_t *)p->d_oob_all, kPredForwardOutput, nullptr, nullptr,
-                                   p->d_coefs16, p->d_symbols))
+    auto &st = p->staging; // (no int32 planes, no node arrays here)
+    int rc;
+    if ((rc = grow(c, st.pixels, fri_hip_plan_pixel_bytes(p))) || (rc = grow(c, st.hist, C * 10 * 1024)) || (rc = grow(c, st.oob, C)) ||
+        (rc = grow(c, st.symbols, std::max<size_t>(C * n, 1))))
         return rc;
-    if (int rc = coefs16_end(p, nullptr)) return rc;
-    HIP_TRY(c, hipMemcpy(symbols, p->d_symbols, C * n * sizeof(uint16_t), hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(hist, p->d_hist_all, C * 10 * 1024 * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(n_out_of_alphabet, p->d_oob_all, C * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    QMatrix q;
+    if ((rc = check_q(qmatrix, q))) return rc;
+    HIP_TRY(c, hipMemcpy(st.pixels, pixels, fri_hip_plan_pixel_bytes(p), hipMemcpyHostToDevice));
+    {
+        // nobody outside sees the coefficients of this call: compact planes (int16, None as 0) between the forward kernel, the fit and the scan
+        Coefs16Lease lease(p, nullptr, C);
+        if (lease.rc) return lease.rc;
+        HIP_TRY(c, launch_fwd_transform_quant(p->dev, 1, st.pixels, 0, nullptr, 0, q, nullptr, false, p->coefs16));
+        // the scan in its stream form: no bucket / prediction arrays, no node words, no gather kernel - every symbol goes straight to its place in its channel's stream
+        if ((rc = predict_image_dev(p, nullptr, fit, value_params, width_params, nullptr, nullptr, st.hist, (uint64_t *)st.oob.get(), kPredForwardOutput, nullptr, nullptr,
+                                    p->coefs16, st.symbols)))
+            return rc;
+    }
+    HIP_TRY(c, hipMemcpy(symbols, st.symbols, C * n * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(hist, st.hist, C * 10 * 1024 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(n_out_of_alphabet, st.oob, C * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return FRI_HIP_OK;
 }
 
@@ -1674,10 +1671,12 @@ int fri_hip_inverse_transform(fri_hip_plan *p, const int32_t *coefs, const int32
     if (int rc = need_device(p)) return rc;
     if (!coefs || !pixels) return FRI_HIP_ERR_INVALID_ARGUMENT;
     HIP_TRY(p->ctx, hipSetDevice(p->ctx->device));
-    if (int rc = ensure_staging(p)) return rc;
-    HIP_TRY(p->ctx, hipMemcpy(p->d_coefs, coefs, fri_hip_plan_coef_count(p) * sizeof(int32_t), hipMemcpyHostToDevice));
-    if (int rc = fri_hip_inverse_transform_dev(p, p->d_coefs, qmatrix, p->d_pixels, nullptr)) return rc;
-    HIP_TRY(p->ctx, hipMemcpy(pixels, p->d_pixels, fri_hip_plan_pixel_bytes(p), hipMemcpyDeviceToHost));
+    auto &st = p->staging;
+    int rc;
+    if ((rc = grow(p->ctx, st.coefs, fri_hip_plan_coef_count(p))) || (rc = grow(p->ctx, st.pixels, fri_hip_plan_pixel_bytes(p)))) return rc;
+    HIP_TRY(p->ctx, hipMemcpy(st.coefs, coefs, fri_hip_plan_coef_count(p) * sizeof(int32_t), hipMemcpyHostToDevice));
+    if ((rc = fri_hip_inverse_transform_dev(p, st.coefs, qmatrix, st.pixels, nullptr))) return rc;
+    HIP_TRY(p->ctx, hipMemcpy(pixels, st.pixels, fri_hip_plan_pixel_bytes(p), hipMemcpyDeviceToHost));
     return FRI_HIP_OK;
 }
 
@@ -1690,8 +1689,8 @@ int fri_hip_time_transform_quant_dev(fri_hip_plan *p, uint32_t n_images, const u
     QMatrix q;
     if (int rc = check_q(qmatrix, q)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if (!p->ev_begin) HIP_TRY(p->ctx, hipEventCreate(&p->ev_begin)); // normally made by fri_hip_plan_create; owned by the plan either way
-    if (!p->ev_end) HIP_TRY(p->ctx, hipEventCreate(&p->ev_end));
+    if (!p->ev_begin) HIP_TRY(p->ctx, hipEventCreate(p->ev_begin.put())); // normally made by fri_hip_plan_create; owned by the plan either way
+    if (!p->ev_end) HIP_TRY(p->ctx, hipEventCreate(p->ev_end.put()));
     const hipEvent_t e0 = p->ev_begin, e1 = p->ev_end;
     HIP_TRY(p->ctx, hipEventRecord(e0, s));
     for (uint32_t i = 0; i < iters; i++) {
@@ -1699,17 +1698,7 @@ int fri_hip_time_transform_quant_dev(fri_hip_plan *p, uint32_t n_images, const u
         HIP_TRY(p->ctx, launch_fwd_transform_quant(p->dev, 1, d_pixels + (size_t)k * pixel_stride, 0, d_coefs + (size_t)k * coef_stride, 0, q, s));
     }
     HIP_TRY(p->ctx, hipEventRecord(e1, s));
-    // Poll instead of hipEventSynchronize: after a few hundred microseconds the runtime's wait goes to sleep, and the wake-up (15-20 us,
-    // plus as much again in the caller's next synchronize) would be charged to a measurement of twenty 17-us launches.
-    for (uint64_t spins = 0;; spins++) {
-        const hipError_t q = hipEventQuery(e1);
-        if (q == hipSuccess) break;
-        if (q != hipErrorNotReady) HIP_TRY(p->ctx, q);
-        if (spins > (1ull << 22)) { // seconds: not a measurement any more
-            HIP_TRY(p->ctx, hipEventSynchronize(e1));
-            break;
-        }
-    }
+    if (int rc = wait_event_polling(p->ctx, e1)) return rc;
     float ms = 0.f;
     HIP_TRY(p->ctx, hipEventElapsedTime(&ms, e0, e1));
     *mean_us = (double)ms * 1000.0 / iters;
@@ -1728,67 +1717,38 @@ int fri_hip_time_transform_quant_streams_dev(fri_hip_plan *p, uint32_t n_images,
     if (int rc = check_q(qmatrix, q)) return rc;
     fri_hip_ctx *c = p->ctx;
     HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t st[8] = {};
-    hipEvent_t done[8] = {}, e0 = nullptr, e1 = nullptr;
-    int rc = FRI_HIP_OK;
-    auto cleanup = [&]() {
-        for (uint32_t k = 0; k < n_streams; k++) {
-            if (done[k]) (void)hipEventDestroy(done[k]);
-            if (st[k]) (void)hipStreamDestroy(st[k]);
-        }
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-    };
-#define TRY_OR_CLEAN(expr)                                  \
-    do {                                                    \
-        hipError_t e_ = (expr);                             \
-        if (e_ != hipSuccess) {                             \
-            rc = fail_hip(c, e_, #expr);                    \
-            (void)hipDeviceSynchronize();                   \
-            cleanup();                                      \
-            return rc;                                      \
-        }                                                   \
-    } while (0)
+    Stream st[8];
+    Event done[8], e0, e1;
     for (uint32_t k = 0; k < n_streams; k++) {
-        TRY_OR_CLEAN(hipStreamCreateWithFlags(&st[k], hipStreamNonBlocking));
-        TRY_OR_CLEAN(hipEventCreateWithFlags(&done[k], hipEventDisableTiming));
+        HIP_TRY(c, hipStreamCreateWithFlags(st[k].put(), hipStreamNonBlocking));
+        HIP_TRY(c, hipEventCreateWithFlags(done[k].put(), hipEventDisableTiming));
     }
-    TRY_OR_CLEAN(hipEventCreate(&e0));
-    TRY_OR_CLEAN(hipEventCreate(&e1));
-    TRY_OR_CLEAN(hipDeviceSynchronize()); // whatever the caller has queued is done before the clock starts
-    TRY_OR_CLEAN(hipEventRecord(e0, st[0]));
-    for (uint32_t k = 1; k < n_streams; k++) TRY_OR_CLEAN(hipStreamWaitEvent(st[k], e0, 0)); // nobody starts before the begin event
+    HIP_TRY(c, hipEventCreate(e0.put()));
+    HIP_TRY(c, hipEventCreate(e1.put()));
+    HIP_TRY(c, hipDeviceSynchronize()); // whatever the caller has queued is done before the clock starts
+    HIP_TRY(c, hipEventRecord(e0, st[0]));
+    for (uint32_t k = 1; k < n_streams; k++) HIP_TRY(c, hipStreamWaitEvent(st[k], e0, 0)); // nobody starts before the begin event
     for (uint32_t i = 0; i < iters; i++) {
         const uint32_t k = i % n_images;
-        TRY_OR_CLEAN(launch_fwd_transform_quant(p->dev, 1, d_pixels + (size_t)k * pixel_stride, 0, d_coefs + (size_t)k * coef_stride, 0, q, st[i % n_streams]));
+        HIP_TRY(c, launch_fwd_transform_quant(p->dev, 1, d_pixels + (size_t)k * pixel_stride, 0, d_coefs + (size_t)k * coef_stride, 0, q, st[i % n_streams]));
     }
     for (uint32_t k = 1; k < n_streams; k++) {
-        TRY_OR_CLEAN(hipEventRecord(done[k], st[k]));
-        TRY_OR_CLEAN(hipStreamWaitEvent(st[0], done[k], 0)); // the end event is behind every stream's last launch
+        HIP_TRY(c, hipEventRecord(done[k], st[k]));
+        HIP_TRY(c, hipStreamWaitEvent(st[0], done[k], 0)); // the end event is behind every stream's last launch
     }
-    TRY_OR_CLEAN(hipEventRecord(e1, st[0]));
-    TRY_OR_CLEAN(hipEventSynchronize(e1));
+    HIP_TRY(c, hipEventRecord(e1, st[0]));
+    HIP_TRY(c, hipEventSynchronize(e1));
     float ms = 0.f;
-    TRY_OR_CLEAN(hipEventElapsedTime(&ms, e0, e1));
-#undef TRY_OR_CLEAN
+    HIP_TRY(c, hipEventElapsedTime(&ms, e0, e1));
     *mean_us = (double)ms * 1000.0 / iters;
-    cleanup();
-    return rc;
+    return FRI_HIP_OK;
 }
 
 /* Measures candidate tilings of the forward kernel on this plan's device and keeps the fastest (see "forward tiling chosen by measurement" above). */
-int fri_hip_plan_tune_forward(fri_hip_plan *p, uint32_t launches, char *report, size_t report_bytes) {
-    if (int rc = need_device(p)) return rc;
-    std::string rep;
-    auto finish = [&](int rc) {
-        if (report && report_bytes) {
-            std::snprintf(report, report_bytes, "%s", rep.c_str());
-        }
-        return rc;
-    };
+static int tune_forward(fri_hip_plan *p, uint32_t launches, std::string &rep) {
     if (!p->fwd_tunable) {
         rep = "{\"tuned\": false, \"kept\": \"" + p->fwd_tiling_note + "\", \"why\": \"tiling pinned by the environment, shared with the inverse kernel, or a many-shares plan\"}";
-        return finish(FRI_HIP_OK);
+        return FRI_HIP_OK;
     }
     fri_hip_ctx *c = p->ctx;
     HIP_TRY(c, hipSetDevice(c->device));
@@ -1817,7 +1777,7 @@ int fri_hip_plan_tune_forward(fri_hip_plan *p, uint32_t launches, char *report, 
     add(-1, 0, 0);
     if (cand.empty()) {
         rep = "{\"tuned\": false, \"why\": \"the plan's own tiling could not be rebuilt\"}";
-        return finish(FRI_HIP_OK);
+        return FRI_HIP_OK;
     }
     if (!rgb) {
         add(0, 72, 0), add(1, 16, 1), add(1, 32, 0), add(1, 8, 0), add(0, 8, 0), add(1, 24, 0), add(0, 48, 0), add(0, 96, 0);
@@ -1828,39 +1788,18 @@ int fri_hip_plan_tune_forward(fri_hip_plan *p, uint32_t launches, char *report, 
     const size_t px_bytes = fri_hip_plan_pixel_bytes(p), co_bytes = fri_hip_plan_coef_count(p) * sizeof(int32_t);
     const uint32_t px_slots = (uint32_t)std::min<size_t>(64, std::max<size_t>(2, ((size_t)420 << 20) / px_bytes + 1));
     const uint32_t co_slots = (uint32_t)std::min<size_t>(px_slots, std::max<size_t>(2, ((size_t)512 << 20) / co_bytes + 1));
-    uint8_t *d_px = nullptr;
-    int32_t *d_co = nullptr;
-    unsigned long long *d_stat = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipStream_t stream = nullptr;
-    int rc = FRI_HIP_OK;
-    auto cleanup = [&]() {
-        (void)hipDeviceSynchronize();
-        for (auto &t : cand)
-            for (void *b : t->bufs) (void)hipFree(b);
-        if (d_stat) (void)hipFree(d_stat);
-        if (d_px) (void)hipFree(d_px);
-        if (d_co) (void)hipFree(d_co);
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-        if (stream) (void)hipStreamDestroy(stream);
-    };
-#define TRY_OR_CLEAN(expr)                                  \
-    do {                                                    \
-        hipError_t e_ = (expr);                             \
-        if (e_ != hipSuccess) {                             \
-            rc = fail_hip(c, e_, #expr);                    \
-            cleanup();                                      \
-            return finish(rc);                              \
-        }                                                   \
-    } while (0)
-    TRY_OR_CLEAN(hipMalloc((void **)&d_px, (size_t)px_slots * px_bytes));
-    TRY_OR_CLEAN(hipMalloc((void **)&d_co, (size_t)co_slots * co_bytes));
-    TRY_OR_CLEAN(hipMemset(d_px, 0x5A, (size_t)px_slots * px_bytes)); // the forward kernel's time does not depend on the pixel values
-    TRY_OR_CLEAN(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-    TRY_OR_CLEAN(hipEventCreate(&e0));
-    TRY_OR_CLEAN(hipEventCreate(&e1));
-    for (auto &t : cand) TRY_OR_CLEAN(upload_forward_candidate(p, *t));
+    Stream stream; // (declared before the buffers: they go first, and hipFree waits for what is queued)
+    Event e0, e1;
+    DevMem<uint8_t> d_px;
+    DevMem<int32_t> d_co;
+    DevMem<unsigned long long> d_stat;
+    HIP_TRY(c, hipMalloc((void **)d_px.put(), (size_t)px_slots * px_bytes));
+    HIP_TRY(c, hipMalloc((void **)d_co.put(), (size_t)co_slots * co_bytes));
+    HIP_TRY(c, hipMemset(d_px, 0x5A, (size_t)px_slots * px_bytes)); // the forward kernel's time does not depend on the pixel values
+    HIP_TRY(c, hipStreamCreateWithFlags(stream.put(), hipStreamNonBlocking));
+    HIP_TRY(c, hipEventCreate(e0.put()));
+    HIP_TRY(c, hipEventCreate(e1.put()));
+    for (auto &t : cand) HIP_TRY(c, upload_forward_candidate(p, *t));
     QMatrix q;
     for (int i = 0; i < 32; i++) q.q[i] = 1;
     constexpr int kRounds = 5;
@@ -1890,10 +1829,10 @@ int fri_hip_plan_tune_forward(fri_hip_plan *p, uint32_t launches, char *report, 
         }
         return hipSuccess;
     };
-    TRY_OR_CLEAN(run(*cand[0], 4 * launches)); // clocks and translations up before anything is compared
+    HIP_TRY(c, run(*cand[0], 4 * launches)); // clocks and translations up before anything is compared
     std::vector<size_t> all(cand.size());
     for (size_t k = 0; k < cand.size(); k++) all[k] = k;
-    TRY_OR_CLEAN(measure(all));
+    HIP_TRY(c, measure(all));
     size_t best = 0;
     for (size_t k = 0; k < cand.size(); k++)
         if (cand[k]->us < cand[best]->us) best = k;
@@ -1934,11 +1873,11 @@ int fri_hip_plan_tune_forward(fri_hip_plan *p, uint32_t launches, char *report, 
             }
         }
         for (size_t k = n0; k < cand.size(); k++) {
-            TRY_OR_CLEAN(upload_forward_candidate(p, *cand[k]));
+            HIP_TRY(c, upload_forward_candidate(p, *cand[k]));
             round2.push_back(k);
         }
         if (round2.size() > 1) {
-            TRY_OR_CLEAN(measure(round2));
+            HIP_TRY(c, measure(round2));
             size_t b2 = best;
             for (size_t k : round2)
                 if (cand[k]->us < cand[b2]->us) b2 = k;
@@ -1948,22 +1887,21 @@ int fri_hip_plan_tune_forward(fri_hip_plan *p, uint32_t launches, char *report, 
     // How long each XCD's workgroups live under the winner (FwdArgs::xcd_stat; a diagnostic for the report: re-cutting the XCDs' shares in proportion was tried and
     // does not transfer from the tuner's scratch buffers to the caller's - which XCD is slow changes with the buffers' placement).
     std::string xcd_note;
-    if (hipMalloc((void **)&d_stat, 16 * sizeof(unsigned long long)) == hipSuccess) {
+    if (hipMalloc((void **)d_stat.put(), 16 * sizeof(unsigned long long)) == hipSuccess) {
         unsigned long long h_stat[16];
-        TRY_OR_CLEAN(hipMemsetAsync(d_stat, 0, sizeof h_stat, stream));
+        HIP_TRY(c, hipMemsetAsync(d_stat, 0, sizeof h_stat, stream));
         cand[best]->dev.k1_xcd_stat = d_stat;
         const hipError_t e_run = run(*cand[best], launches);
         cand[best]->dev.k1_xcd_stat = nullptr;
-        TRY_OR_CLEAN(e_run);
-        TRY_OR_CLEAN(hipStreamSynchronize(stream));
-        TRY_OR_CLEAN(hipMemcpy(h_stat, d_stat, sizeof h_stat, hipMemcpyDeviceToHost));
+        HIP_TRY(c, e_run);
+        HIP_TRY(c, hipStreamSynchronize(stream));
+        HIP_TRY(c, hipMemcpy(h_stat, d_stat, sizeof h_stat, hipMemcpyDeviceToHost));
         for (int x = 0; x < 8; x++) {
             char b[32];
             std::snprintf(b, sizeof b, "%s%.2f", x ? " " : "", h_stat[2 * x + 1] ? (double)h_stat[2 * x] / (double)h_stat[2 * x + 1] / 100.0 : 0.0);
             xcd_note += b;
         }
     }
-#undef TRY_OR_CLEAN
     char b[160];
     rep = "{\"tuned\": true, \"launches\": " + std::to_string(launches) + ", \"rounds\": " + std::to_string(kRounds) + ", \"pixel_slots\": " + std::to_string(px_slots) +
           ", \"coef_slots\": " + std::to_string(co_slots) + ", \"winner\": \"" + cand[best]->label + "\", \"candidates_us\": {";
@@ -1982,8 +1920,15 @@ int fri_hip_plan_tune_forward(fri_hip_plan *p, uint32_t launches, char *report, 
         if (itc == g_tuned.end()) g_tuned.emplace_back(k, p->fwd_tp);
         else itc->second = p->fwd_tp;
     }
-    cleanup();
-    return finish(FRI_HIP_OK);
+    return FRI_HIP_OK;
+}
+
+int fri_hip_plan_tune_forward(fri_hip_plan *p, uint32_t launches, char *report, size_t report_bytes) {
+    if (int rc = need_device(p)) return rc;
+    std::string rep;
+    const int rc = tune_forward(p, launches, rep);
+    if (report && report_bytes) std::snprintf(report, report_bytes, "%s", rep.c_str());
+    return rc;
 }
 
 } // extern "C"

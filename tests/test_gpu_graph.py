@@ -93,3 +93,66 @@ def test_the_scan_refuses_a_capturing_stream(ctx, hip):
     s.synchronize()
     assert torch.equal(d_h, want)
     P.close()
+
+
+def _symbol_chain(P, torch, d_px, params, fit, direct, stream):
+    """one image through fri_hip_encode_symbols_batch_dev on the compact planes (d_coefs = NULL); the caller's buffers, allocated before any capture"""
+    plane, n = P.num_cells * 512, P.num_some
+    out = dict(w=torch.full((plane,), 0xEEEE, dtype=torch.uint16, device="cuda"), st=torch.full((n,), 0xFFFF, dtype=torch.uint16, device="cuda"),
+               h=torch.full((10, 1024), -1, dtype=torch.int32, device="cuda"), o=torch.full((1,), -1, dtype=torch.int64, device="cuda"),
+               r=torch.full((1,), -1, dtype=torch.int64, device="cuda"), par=torch.from_numpy(params.reshape(-1).copy()).cuda())
+    torch.cuda.synchronize()
+
+    def run():
+        P.encode_symbols_batch_dev(1, d_px.data_ptr(), P.pixel_bytes, None, fit, out["par"].data_ptr(), 0, plane, 0 if direct else out["w"].data_ptr(), plane, out["st"].data_ptr(), n,
+                                   out["h"].data_ptr(), out["o"].data_ptr(), out["r"].data_ptr() if fit else None, stream=stream)
+
+    return out, run
+
+
+def test_a_refused_symbol_chain_leaves_the_graph_empty(ctx, hip):
+    # the compact chains refuse a capturing stream before K1 is queued: nothing of them lands in the caller's graph, with the fit or without it
+    import torch
+
+    import frave_amd as fa
+    from tests.common import random_params
+
+    w, h, c = 320, 200, 1
+    d_px = torch.from_numpy(gen_image("smooth", w, h, c, 9).reshape(-1).copy()).cuda()
+    vp, wp = random_params(5)
+    params = np.stack([np.asarray(vp, np.float32).reshape(3, 6), np.asarray(wp, np.float32).reshape(3, 6)])
+    s = torch.cuda.Stream()
+    sp = C.c_void_p(s.cuda_stream)
+    forms = [(False, True), (True, False)]  # (fit, direct): the stream form without the fit, the node-word form with it
+    R = fa.Plan(ctx, w, h, c)  # a plan that never sees a capture
+    R.set_stream_order()
+    want = []
+    for fit, direct in forms:
+        out, run = _symbol_chain(R, torch, d_px, params, fit, direct, s.cuda_stream)
+        run()
+        s.synchronize()
+        want.append(out)
+    P = fa.Plan(ctx, w, h, c)
+    P.set_stream_order()
+    chains = [_symbol_chain(P, torch, d_px, params, fit, direct, s.cuda_stream) for fit, direct in forms]
+    graph = C.c_void_p()
+    assert hip.hipStreamBeginCapture(sp, RELAXED) == 0
+    try:
+        for _, run in chains:
+            with pytest.raises(fa.FriHipError) as e:
+                run()
+            assert e.value.code == -1 and "graph" in str(e.value)  # FRI_HIP_ERR_INVALID_ARGUMENT
+    finally:
+        assert hip.hipStreamEndCapture(sp, C.byref(graph)) == 0
+    n_nodes = C.c_size_t(12345)
+    rc = hip.hipGraphGetNodes(graph, None, C.byref(n_nodes))
+    hip.hipGraphDestroy(graph)
+    assert rc == 0 and n_nodes.value == 0
+    # outside the capture the same chains compute what the other plan computed
+    for (fit, _), (out, run), ref in zip(forms, chains, want):
+        run()
+        s.synchronize()
+        for k in ("st", "h", "o") + (("par", "r") if fit else ()):
+            assert torch.equal(out[k], ref[k]), (fit, k)
+    P.close()
+    R.close()
