@@ -195,16 +195,17 @@ int fail_hip(fri_hip_ctx *ctx, hipError_t e, const char *what) {
         if (e_ != hipSuccess) return fail_hip(ctx, e_, #expr); \
     } while (0)
 
+// copies v into a new device buffer that `bufs` owns, followed by `pad` zeroed elements (an empty array still gets one element)
 template <typename T>
-int upload(fri_hip_plan *p, const std::vector<T> &v, const T *&out, size_t pad = 0) { // pad: zeroed elements behind the array
-    size_t bytes = (v.size() + pad) * sizeof(T);
-    if (!bytes) bytes = sizeof(T);
-    auto &d = p->owned.emplace_back();
-    HIP_TRY(p->ctx, hipMalloc(d.put(), bytes));
-    if (pad) HIP_TRY(p->ctx, hipMemset(static_cast<T *>(d.get()) + v.size(), 0, pad * sizeof(T)));
-    if (!v.empty()) HIP_TRY(p->ctx, hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+hipError_t upload(std::vector<DevMem<void>> &bufs, const std::vector<T> &v, const T *&out, size_t pad = 0) {
+    auto &d = bufs.emplace_back();
+    if (hipError_t e = hipMalloc(d.put(), std::max<size_t>(v.size() + pad, 1) * sizeof(T))) return e;
+    if (pad)
+        if (hipError_t e = hipMemset(static_cast<T *>(d.get()) + v.size(), 0, pad * sizeof(T))) return e;
+    if (!v.empty())
+        if (hipError_t e = hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice)) return e;
     out = static_cast<const T *>(d.get());
-    return FRI_HIP_OK;
+    return hipSuccess;
 }
 
 int check_q(const int32_t q[32], QMatrix &out) {
@@ -222,15 +223,52 @@ int need_device(const fri_hip_plan *p) {
 }
 
 // Tuning knobs (tile shapes, share weights, kernel A/B switches, trace) are read from the environment only when the caller opts
-// in with FRI_HIP_TUNING=1; otherwise the library's behaviour does not depend on the process environment.
-bool tuning_enabled() {
-    const char *s = std::getenv("FRI_HIP_TUNING");
-    return s && s[0] == '1' && s[1] == 0;
-}
-const char *env_str(const char *name) { return tuning_enabled() ? std::getenv(name) : nullptr; }
-int env_int(const char *name) {
-    const char *s = env_str(name);
-    return s ? std::atoi(s) : 0;
+// in with FRI_HIP_TUNING=1; otherwise the library's behaviour does not depend on the process environment. A plan reads them once,
+// when it is created (read_knobs). Integers: 0 when unset; the optional ones tell "unset" from "set to 0".
+struct Knobs {
+    // the forward tiling: setting any of these pins it (fri_hip_plan_tune_forward keeps what the plan has)
+    int band_rows = 0, cells_per_tile = 0, cells_per_wg = 0, target_wgs = 0, tile_bytes = 0;
+    int ranks = 0; // FRI_HIP_RANKS, at most 4
+    std::optional<int> strided_shares;
+    bool has_rank_weights = false; // FRI_HIP_RANK_WEIGHTS="w0,w1,w2,w3" with all four parsed ("1,1,1,1" = equal shares)
+    float rank_weight[4] = {0, 0, 0, 0};
+    bool pins_forward = false;
+    // (does not pin: the tuner's candidates start from the plan's TilingParams and keep it)
+    int batch_share_tiles = 0;
+    // the inverse tiling
+    std::optional<int> inv_shared, inv_strided_shares;
+    int inv_band_rows = 0;
+    // kernel switches, grids, diagnostics
+    int pred_blocks = 0, hist_blocks = 0, trace = 0, k3_scan = 0;
+    int k1_ablate = 0, k2_ablate = 0, k3_ablate = 0, k4_ablate = 0;
+    std::optional<int> k1_cached_stores, k1_batch_shares, k4_older_eighths;
+};
+
+Knobs read_knobs() {
+    Knobs k;
+    const char *on = std::getenv("FRI_HIP_TUNING");
+    if (!on || on[0] != '1' || on[1] != 0) return k;
+    auto env = [](const char *name) { return std::getenv(name); };
+    auto pin = [&](const char *name) { // a knob of the forward tiling
+        const char *s = env(name);
+        k.pins_forward |= s != nullptr;
+        return s;
+    };
+    auto opt = [](const char *s) { return s ? std::optional<int>(std::atoi(s)) : std::nullopt; };
+    auto num = [&](const char *s) { return opt(s).value_or(0); };
+    k.band_rows = num(pin("FRI_HIP_BAND_ROWS")), k.cells_per_tile = num(pin("FRI_HIP_CELLS_PER_TILE")), k.cells_per_wg = num(pin("FRI_HIP_CELLS_PER_WG"));
+    k.target_wgs = num(pin("FRI_HIP_TARGET_WGS")), k.tile_bytes = num(pin("FRI_HIP_TILE_BYTES")), k.ranks = std::min(num(pin("FRI_HIP_RANKS")), 4);
+    k.strided_shares = opt(pin("FRI_HIP_STRIDED_SHARES"));
+    if (const char *s = pin("FRI_HIP_RANK_WEIGHTS")) {
+        float *w = k.rank_weight;
+        k.has_rank_weights = std::sscanf(s, "%f,%f,%f,%f", &w[0], &w[1], &w[2], &w[3]) == 4;
+    }
+    k.batch_share_tiles = num(env("FRI_HIP_BATCH_SHARE_TILES"));
+    k.inv_shared = opt(env("FRI_HIP_INV_SHARED")), k.inv_strided_shares = opt(env("FRI_HIP_INV_STRIDED_SHARES")), k.inv_band_rows = num(env("FRI_HIP_INV_BAND_ROWS"));
+    k.pred_blocks = num(env("FRI_HIP_PRED_BLOCKS")), k.hist_blocks = num(env("FRI_HIP_HIST_BLOCKS")), k.trace = num(env("FRI_HIP_TRACE")), k.k3_scan = num(env("FRI_HIP_K3_SCAN"));
+    k.k1_ablate = num(env("FRI_HIP_K1_ABLATE")), k.k2_ablate = num(env("FRI_HIP_K2_ABLATE")), k.k3_ablate = num(env("FRI_HIP_K3_ABLATE")), k.k4_ablate = num(env("FRI_HIP_K4_ABLATE"));
+    k.k1_cached_stores = opt(env("FRI_HIP_K1_CACHED_STORES")), k.k1_batch_shares = opt(env("FRI_HIP_K1_BATCH_SHARES")), k.k4_older_eighths = opt(env("FRI_HIP_K4_OLDER_EIGHTHS"));
+    return k;
 }
 
 // at least n elements in b (n == 0: the call does not use it). Growing frees the old buffer first: hipFree waits for the device, so nothing queued still uses it.
@@ -358,6 +396,155 @@ int ensure_encode_slots(fri_hip_plan *p, bool want_bucket, bool want_prediction)
     return FRI_HIP_OK;
 }
 
+// ---- the plan's tilings --------------------------------------------------------------------------------------------------------------------------------
+// How the kernels cut the image: tiles, bands and shares for the forward kernel (whose shares K2 / K4 size their grids by), the inverse kernel's own tiling.
+// Host logic only: the shape, the device's CU count (none for a host-only plan) and the knobs go in, TilingParams and a Geometry come out.
+
+// the tiling fields of a DevicePlan: the forward kernel's view (the batch shares' maximum included) ...
+void fill_forward_tiling(DevicePlan &d, const Geometry &g) {
+    d.n_tiles = (uint32_t)g.tiles.size(), d.n_wg = (uint32_t)g.wg_tiles.size() - 1, d.n_wg_batch = (uint32_t)g.wg_tiles_batch.size() - 1;
+    d.lds_pitch = g.lds_pitch, d.lds_rows = g.lds_rows, d.cells_per_tile = g.cells_per_tile, d.max_tile_cells = g.max_tile_cells;
+    d.max_wg_tiles = std::max(g.max_wg_tiles, g.max_wg_tiles_batch), d.max_wg_cells = g.max_wg_cells;
+}
+// ... and the inverse kernel's: one share per workgroup, no batch shares
+void fill_inverse_tiling(DevicePlan &d, const Geometry &g) {
+    fill_forward_tiling(d, g);
+    d.wg_tiles_batch = nullptr, d.n_wg_batch = 0, d.max_wg_tiles = g.max_wg_tiles;
+    d.inv_group = 1, d.inv_max_wg_tiles = g.max_wg_tiles, d.inv_max_wg_cells = g.max_wg_cells;
+}
+
+// uploads tiling g's tables into `bufs` and points d at them, with the fields of the forward kernel's view of g or the inverse kernel's
+hipError_t upload_tiling(std::vector<DevMem<void>> &bufs, const Geometry &g, DevicePlan &d, bool inverse) {
+    hipError_t e;
+    if ((e = upload(bufs, g.tiles, d.tiles)) || (e = upload(bufs, g.tile_cells, d.tile_cells)) || (e = upload(bufs, g.tile_meta, d.tile_meta)) ||
+        (e = upload(bufs, g.wg_tiles, d.wg_tiles)) || (!inverse && (e = upload(bufs, g.wg_tiles_batch, d.wg_tiles_batch))))
+        return e;
+    inverse ? fill_inverse_tiling(d, g) : fill_forward_tiling(d, g);
+    return hipSuccess;
+}
+
+// Resident forward workgroups per CU on tiling g: 4 by registers, fewer when the LDS of one workgroup (two tile buffers) does not fit four times (RGB tiles
+// need ~47 KB, so three). 0: g does not fit the forward kernel's static register / LDS budget at all.
+int fwd_resident(const Geometry &g, uint32_t channels) {
+    DevicePlan d;
+    d.channels = (int32_t)channels;
+    fill_forward_tiling(d, g);
+    return fwd_plan_fits(d) ? (int)std::min<size_t>(4, (160 * 1024) / fwd_lds_bytes(d)) : 0;
+}
+// Does g fit the inverse kernels' own limits (the forward kernel's budget says nothing about them)? with_lists: the lists kernel's LDS rectangle
+// too, known once the lists are built.
+bool inv_fits(const Geometry &g, uint32_t channels, bool with_lists) {
+    DevicePlan d;
+    d.channels = (int32_t)channels;
+    fill_inverse_tiling(d, g);
+    d.inv_rect_bytes = g.inv_rect_bytes;
+    return inv_plan_fits(d, with_lists);
+}
+
+// One step of shrinking tiling g (built from tp) that does not fit its kernel: irregular centre spacing makes a few tiles wider than the average, RGB
+// triples the bytes per pixel. A cell fewer per tile; at one cell per tile, bands of half the height. False: the bands cannot get any lower.
+bool shrink_tiling(TilingParams &tp, const Geometry &g) {
+    tp.band_rows = g.band_rows;
+    tp.cells_per_tile = g.cells_per_tile - 1;
+    if (tp.cells_per_tile < 1) {
+        tp.cells_per_tile = 1;
+        tp.band_rows = g.band_rows / 2;
+        if (tp.band_rows < 1) return false;
+    }
+    return true;
+}
+
+// One share per resident workgroup (`ranks` per CU), sized by dispatch rank. Measured on MI355X at 4096^2 (tools/sweep_rank_weights.sh): equal shares
+// 22.3-23.4 us, these weights 20.5-21.7 us; steeper is worse again. Host-only plans keep equal shares.
+void set_ranks(TilingParams &tp, int ranks, std::optional<int> cus, const Knobs &k) {
+    tp.ranks = ranks;
+    // (three ranks = RGB: 1.3 / 1.1 / 0.6 through round 3; with interleaved shares and all bytes from HBM 1.2 / 1.0 / 0.8 is 2 % faster: 51.9 -> 50.6 us)
+    static const float w4[4] = {1.3f, 1.1f, 0.9f, 0.7f}, w3[4] = {1.2f, 1.0f, 0.8f, 0.f}, w2[4] = {1.15f, 0.85f, 0.f, 0.f}, w1[4] = {1.f, 0.f, 0.f, 0.f};
+    const float *w = ranks >= 4 ? w4 : ranks == 3 ? w3 : ranks == 2 ? w2 : w1;
+    for (int i = 0; i < 4; i++) tp.rank_weight[i] = k.has_rank_weights ? k.rank_weight[i] : cus ? w[i] : 0.f;
+    tp.target_wgs = k.target_wgs;
+    if (tp.target_wgs <= 0 && cus) tp.target_wgs = *cus * ranks;
+}
+
+struct Tiling {
+    TilingParams tp; // what geo was built with
+    Geometry geo;
+    bool many_shares = false; // (forward) many short shares handed out in dispatch order instead of one per resident workgroup
+};
+
+constexpr size_t kStridedMaxCells = 200000, kOwnInverseMaxCells = 400000;
+constexpr size_t kInvListsMaxBytes = (size_t)256 << 20; // the inverse kernel's write-out lists: 6 MB at 4096^2; beyond 256 MB the kernel scans the rectangle instead
+
+// The forward kernel's tiling for a width x height x channels image on a device of `cus` CUs (none: a host-only plan). Returns FRI_HIP_OK or the plan's error.
+int choose_forward_tiling(uint32_t width, uint32_t height, uint32_t channels, std::optional<int> cus, const Knobs &k, Tiling &t) {
+    TilingParams &tp = t.tp;
+    tp.band_rows = k.band_rows;
+    tp.cells_per_tile = k.cells_per_tile;
+    tp.cells_per_wg = k.cells_per_wg;
+    tp.batch_share_tiles = k.batch_share_tiles;
+    // Interleaved shares (geometry.cpp): the resident workgroups work on one window sliding over the image. Default since round 4 (4096^2 from HBM: planes
+    // 20.3 -> 19.1 us, RGB 55.5 -> 51.9 us, the inverse 29.6 -> 27.8 / 86 -> 72 us); FRI_HIP_STRIDED_SHARES=0 (tuning) restores one contiguous run per share.
+    // Up to ~200 000 cells, that is: at 12000^2 and 16384^2 (282 K / 526 K cells, many short shares dispatched in order: the resident set slides already) the
+    // interleaving costs 6 % (150 -> 160 us, 270 -> 285 us), at 8192^2 (131 K) it still gains 7 % (80 -> 74 us).
+    tp.strided_shares = k.strided_shares ? *k.strided_shares > 0 : cus.has_value();
+    if (!k.strided_shares && (size_t)width * height / kCell >= kStridedMaxCells) tp.strided_shares = false; // (a cell per 512 pixels: spares the large plan a geometry pass)
+    // Band height of the forward tiles: 16 rows for planes and RGB (planes were 32 through round 3 - tuned while the bench's pixels came out of the Infinity
+    // Cache; from HBM 16 with interleaved shares is 3-5 % faster at 4096^2 and 15 % at 6000 x 4000). The inverse kernel keeps 32 for planes (choose_inverse_tiling).
+    if (tp.band_rows <= 0 && cus) tp.band_rows = 16;
+    // LDS budget of one forward tile buffer: 4 chunks of 16 bytes per thread for planes (the tuned variant), 6 for RGB
+    tp.tile_buffer_bytes = k.tile_bytes > 0 ? k.tile_bytes : (channels == 1 ? 4 : 6) * 256 * 16;
+    set_ranks(tp, k.ranks > 0 ? k.ranks : 4, cus, k);
+    for (;;) {
+        const std::string err = build_geometry(width, height, channels, tp, t.geo);
+        if (!err.empty()) return err == "empty lattice" ? FRI_HIP_ERR_EMPTY_LATTICE : FRI_HIP_ERR_INVALID_ARGUMENT;
+        const int resident = fwd_resident(t.geo, channels);
+        const size_t F = t.geo.centers.size();
+        if (!resident) {
+            if (!shrink_tiling(tp, t.geo)) return FRI_HIP_ERR_INVALID_ARGUMENT;
+        } else if (cus && !k.strided_shares && tp.strided_shares && F >= kStridedMaxCells) { // large image: contiguous shares (see above)
+            tp.strided_shares = false;
+        } else if (cus && k.ranks <= 0 && resident < tp.ranks) { // e.g. RGB: three workgroups per CU
+            set_ranks(tp, resident, cus, k);
+        } else if (cus && !t.many_shares && k.target_wgs <= 0 && tp.cells_per_wg <= 0 && F >= 128 * (size_t)(*cus * tp.ranks)) {
+            // Large images: with one share per resident workgroup every workgroup streams through its own 1/1024 of the image for the whole
+            // launch - 1024 read and 1024 write fronts spread over all of it (1.4 GB at 16384^2). Many short shares (~32 cells), handed
+            // out in dispatch order, let the resident set slide over the image instead: 8192^2 60.2 -> 56.5 us, 12000^2 120.7 -> 107.1 us,
+            // 16384^2 297-311 -> 275-279 us (tools/sweep_16k_shares.sh; equal shares: the dispatch-rank weights are for a launch of one round).
+            // Below ~128 cells per workgroup (8192^2: neutral) the one-round launch with weighted shares is kept.
+            t.many_shares = true;
+            tp.target_wgs = (int)(((F / 32 + 1023) / 1024) * 1024);
+            for (int i = 0; i < 4; i++) tp.rank_weight[i] = i < tp.ranks ? 1.f : 0.f;
+        } else {
+            return FRI_HIP_OK;
+        }
+    }
+}
+
+// The inverse kernel's own tiling (round 4), given the forward one: one share per resident workgroup (it prefers that at every size), dispatch-rank weights,
+// interleaved, bands of 32 rows for planes / 16 for RGB; shrunk like the forward tiles until the kernel's limits hold. True: `inv` holds it, its write-out
+// lists built. False: the inverse kernel shares the forward tiling (host-only plans, FRI_HIP_INV_SHARED=1, large images, or no tiling of its own fits).
+bool choose_inverse_tiling(uint32_t width, uint32_t height, uint32_t channels, std::optional<int> cus, const Knobs &k, const Tiling &fwd, Tiling &inv) {
+    // (from ~400 000 cells on - 16384^2 - the inverse kernel is fastest on groups of the forward plan's short shares, as in round 3: 386 against 408 us)
+    if (!cus || (k.inv_shared ? *k.inv_shared > 0 : fwd.geo.centers.size() >= kOwnInverseMaxCells)) return false;
+    TilingParams &ti = inv.tp;
+    ti = fwd.tp;
+    set_ranks(ti, fwd.tp.ranks, cus, k); // (restores the dispatch-rank weights a many-shares forward tiling had flattened)
+    ti.band_rows = k.inv_band_rows > 0 ? k.inv_band_rows : (channels == 1 ? 32 : 16);
+    ti.cells_per_tile = k.cells_per_tile;
+    ti.cells_per_wg = 0;
+    ti.target_wgs = *cus * ti.ranks;
+    ti.strided_shares = k.inv_strided_shares ? *k.inv_strided_shares > 0 : k.strided_shares.value_or(1) > 0; // interleaved at every size it is built for
+    for (int guard = 0; guard < 64; guard++) {
+        if (!build_geometry(width, height, channels, ti, inv.geo).empty()) return false;
+        // (the forward budget too, as through round 4: it keeps the tiles at the size the kernel was tuned for)
+        if (fwd_resident(inv.geo, channels) && inv_fits(inv.geo, channels, false)) {
+            build_inverse_lists(inv.geo, kInvListsMaxBytes);
+            return inv.geo.inv_lists.empty() || inv_fits(inv.geo, channels, true); // with the lists built their LDS rectangle is known
+        }
+        if (!shrink_tiling(ti, inv.geo)) return false;
+    }
+    return false;
+}
 
 // ---- forward tiling chosen by measurement (fri_hip_plan_tune_forward) ---------------------------------------------------------------------------------
 // Which tiling the forward kernel runs fastest on is not monotonic in any parameter and differs by image size (at 4096^2 contiguous
@@ -374,54 +561,19 @@ struct FwdTiling {  // one candidate: host geometry + its device tables
     double us = 0;
 };
 
-void fill_forward_tiling(DevicePlan &d, const Geometry &g) {
-    d.n_tiles = (uint32_t)g.tiles.size();
-    d.lds_pitch = g.lds_pitch;
-    d.lds_rows = g.lds_rows;
-    d.cells_per_tile = g.cells_per_tile;
-    d.max_tile_cells = g.max_tile_cells;
-    d.max_wg_tiles = std::max(g.max_wg_tiles, g.max_wg_tiles_batch);
-    d.n_wg_batch = (uint32_t)g.wg_tiles_batch.size() - 1;
-    d.max_wg_cells = g.max_wg_cells;
-    d.n_wg = (uint32_t)g.wg_tiles.size() - 1;
-}
-
-template <typename T>
-hipError_t upload_raw(const std::vector<T> &v, const T *&out, std::vector<DevMem<void>> &bufs) {
-    const size_t bytes = std::max(v.size(), (size_t)1) * sizeof(T);
-    auto &d = bufs.emplace_back();
-    if (hipError_t e = hipMalloc(d.put(), bytes)) return e;
-    if (!v.empty())
-        if (hipError_t e = hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice)) return e;
-    out = static_cast<const T *>(d.get());
-    return hipSuccess;
-}
-
 // builds candidate `c.tp` for the plan's shape; false = it does not fit the forward kernel with the plan's resident workgroup count (not a candidate)
 bool build_forward_candidate(const fri_hip_plan *p, FwdTiling &c) {
     const Geometry &g0 = p->geo;
     if (!build_geometry(g0.width, g0.height, g0.channels, c.tp, c.geo).empty()) return false;
     if (c.geo.centers.size() != g0.centers.size()) return false;
-    DevicePlan probe;
-    probe.channels = (int32_t)g0.channels;
-    probe.lds_pitch = c.geo.lds_pitch;
-    probe.lds_rows = c.geo.lds_rows;
-    probe.max_tile_cells = c.geo.max_tile_cells;
-    probe.max_wg_tiles = std::max(c.geo.max_wg_tiles, c.geo.max_wg_tiles_batch);
-    if (!fwd_plan_fits(probe)) return false;
-    if ((int)std::min<size_t>(4, (160 * 1024) / fwd_lds_bytes(probe)) < c.tp.ranks) return false; // the shares are sized for tp.ranks resident workgroups per CU
-    return true;
+    const int resident = fwd_resident(c.geo, g0.channels);
+    return resident > 0 && resident >= c.tp.ranks; // the shares are sized for tp.ranks resident workgroups per CU
 }
 
 hipError_t upload_forward_candidate(const fri_hip_plan *p, FwdTiling &c) {
     c.dev = p->dev;
     c.dev.k1_measuring = true; // (adopt_forward_tiling copies the tables into the plan's own DevicePlan, not this flag)
-    hipError_t e;
-    if ((e = upload_raw(c.geo.tiles, c.dev.tiles, c.bufs)) || (e = upload_raw(c.geo.tile_cells, c.dev.tile_cells, c.bufs)) || (e = upload_raw(c.geo.tile_meta, c.dev.tile_meta, c.bufs)) ||
-        (e = upload_raw(c.geo.wg_tiles, c.dev.wg_tiles, c.bufs)) || (e = upload_raw(c.geo.wg_tiles_batch, c.dev.wg_tiles_batch, c.bufs)))
-        return e;
-    fill_forward_tiling(c.dev, c.geo);
-    return hipSuccess;
+    return upload_tiling(c.bufs, c.geo, c.dev, false);
 }
 
 // the plan takes the candidate's tiling: host vectors and device tables (the old tables stay allocated until the plan is destroyed - a launch may still read them)
@@ -593,242 +745,86 @@ int fri_hip_plan_create(fri_hip_ctx *ctx, uint32_t width, uint32_t height, uint3
     if (!plan) return FRI_HIP_ERR_OUT_OF_MEMORY;
     fri_hip_plan *p = plan.get();
     p->ctx = ctx;
-    TilingParams tp;
-    tp.band_rows = env_int("FRI_HIP_BAND_ROWS");
-    tp.cells_per_tile = env_int("FRI_HIP_CELLS_PER_TILE");
-    tp.cells_per_wg = env_int("FRI_HIP_CELLS_PER_WG");
-    tp.batch_share_tiles = env_int("FRI_HIP_BATCH_SHARE_TILES");
-    // Interleaved shares (geometry.cpp): the resident workgroups work on one window sliding over the image. Default since round 4 (4096^2 from HBM: planes
-    // 20.3 -> 19.1 us, RGB 55.5 -> 51.9 us, the inverse 29.6 -> 27.8 / 86 -> 72 us); FRI_HIP_STRIDED_SHARES=0 (tuning) restores one contiguous run per share.
-    // Up to ~200 000 cells, that is: at 12000^2 and 16384^2 (282 K / 526 K cells, many short shares dispatched in order: the resident set slides already) the
-    // interleaving costs 6 % (150 -> 160 us, 270 -> 285 us), at 8192^2 (131 K) it still gains 7 % (80 -> 74 us).
-    const bool strided_env = env_str("FRI_HIP_STRIDED_SHARES") != nullptr;
-    tp.strided_shares = strided_env ? env_int("FRI_HIP_STRIDED_SHARES") > 0 : ctx != nullptr;
-    constexpr size_t kStridedMaxCells = 200000, kOwnInverseMaxCells = 400000;
-    if (!strided_env && (size_t)width * height / kCell >= kStridedMaxCells) tp.strided_shares = false; // (a cell per 512 pixels: spares the large plan a geometry pass)
-    // Band height of the forward tiles: 16 rows for planes and RGB (planes were 32 through round 3 - tuned while the bench's pixels came out of the Infinity
-    // Cache; from HBM 16 with interleaved shares is 3-5 % faster at 4096^2 and 15 % at 6000 x 4000). The inverse kernel keeps 32 for planes (below).
-    if (tp.band_rows <= 0 && ctx) tp.band_rows = 16;
-    // LDS budget of one forward tile buffer: 4 chunks of 16 bytes per thread for planes (the tuned variant), 6 for RGB
-    tp.tile_buffer_bytes = (channels == 1 ? 4 : 6) * 256 * 16;
-    if (env_int("FRI_HIP_TILE_BYTES") > 0) tp.tile_buffer_bytes = env_int("FRI_HIP_TILE_BYTES");
-    // Shares by dispatch rank, measured on MI355X at 4096^2 (tools/sweep_rank_weights.sh): equal shares 22.3-23.4 us,
-    // these weights 20.5-21.7 us; steeper is worse again. Host-only plans keep equal shares.
-    // Resident K1 workgroups per CU: 4 by registers; fewer when the LDS of one workgroup (two tile buffers) does not fit four times:
-    // RGB tiles need ~47 KB, so three. One share per resident workgroup, sized by dispatch rank.
-    auto set_ranks = [&](int ranks) {
-        tp.ranks = ranks;
-        // (three ranks = RGB: 1.3 / 1.1 / 0.6 through round 3; with interleaved shares and all bytes from HBM 1.2 / 1.0 / 0.8 is 2 % faster: 51.9 -> 50.6 us)
-        static const float w4[4] = {1.3f, 1.1f, 0.9f, 0.7f}, w3[4] = {1.2f, 1.0f, 0.8f, 0.f}, w2[4] = {1.15f, 0.85f, 0.f, 0.f}, w1[4] = {1.f, 0.f, 0.f, 0.f};
-        const float *w = ranks >= 4 ? w4 : ranks == 3 ? w3 : ranks == 2 ? w2 : w1;
-        for (int i = 0; i < 4; i++) tp.rank_weight[i] = ctx ? w[i] : 0.f;
-        if (const char *e = env_str("FRI_HIP_RANK_WEIGHTS")) { // "w0,w1,w2,w3" (tuning; "1,1,1,1" = equal shares)
-            float v[4];
-            if (std::sscanf(e, "%f,%f,%f,%f", &v[0], &v[1], &v[2], &v[3]) == 4)
-                for (int i = 0; i < 4; i++) tp.rank_weight[i] = v[i];
-        }
-        tp.target_wgs = env_int("FRI_HIP_TARGET_WGS");
-        if (tp.target_wgs <= 0 && ctx) tp.target_wgs = ctx->cu_count * ranks;
-    };
-    set_ranks(env_int("FRI_HIP_RANKS") > 0 ? std::min(env_int("FRI_HIP_RANKS"), 4) : 4);
-    bool many_shares = false;
-    auto ctx_wgs = [](const fri_hip_ctx *c, int ranks) { return c ? c->cu_count * ranks : 1024; };
-    // Shrink the tiles until they fit the forward kernel's static register / LDS budget (irregular centre spacing
-    // makes a few tiles wider than the average; RGB triples the bytes per pixel).
-    for (;;) {
-        std::string err = build_geometry(width, height, channels, tp, p->geo);
-        if (!err.empty()) return err == "empty lattice" ? FRI_HIP_ERR_EMPTY_LATTICE : FRI_HIP_ERR_INVALID_ARGUMENT;
-        DevicePlan probe;
-        probe.channels = (int32_t)channels;
-        probe.lds_pitch = p->geo.lds_pitch;
-        probe.lds_rows = p->geo.lds_rows;
-        probe.max_tile_cells = p->geo.max_tile_cells;
-        probe.max_wg_tiles = std::max(p->geo.max_wg_tiles, p->geo.max_wg_tiles_batch);
-        if (fwd_plan_fits(probe)) {
-            if (ctx && !strided_env && tp.strided_shares && p->geo.centers.size() >= kStridedMaxCells) { // large image: contiguous shares (see above)
-                tp.strided_shares = false;
-                continue;
-            }
-            const int resident = (int)std::min<size_t>(4, (160 * 1024) / fwd_lds_bytes(probe));
-            if (ctx && env_int("FRI_HIP_RANKS") <= 0 && resident >= 1 && resident < tp.ranks) { // e.g. RGB: three workgroups per CU
-                set_ranks(resident);
-                continue;
-            }
-            // Large images: with one share per resident workgroup every workgroup streams through its own 1/1024 of the image for the whole
-            // launch - 1024 read and 1024 write fronts spread over all of it (1.4 GB at 16384^2). Many short shares (~32 cells), handed
-            // out in dispatch order, let the resident set slide over the image instead: 8192^2 60.2 -> 56.5 us, 12000^2 120.7 -> 107.1 us,
-            // 16384^2 297-311 -> 275-279 us (tools/sweep_16k_shares.sh; equal shares: the dispatch-rank weights are for a launch of one round).
-            // Below ~128 cells per workgroup (8192^2: neutral) the one-round launch with weighted shares is kept.
-            const size_t F = p->geo.centers.size(), one_round = (size_t)ctx_wgs(ctx, tp.ranks);
-            if (ctx && !many_shares && env_int("FRI_HIP_TARGET_WGS") <= 0 && tp.cells_per_wg <= 0 && F >= 128 * one_round) {
-                many_shares = true;
-                tp.target_wgs = (int)(((F / 32 + 1023) / 1024) * 1024);
-                for (int i = 0; i < 4; i++) tp.rank_weight[i] = i < tp.ranks ? 1.f : 0.f;
-                continue;
-            }
-            break;
-        }
-        tp.band_rows = p->geo.band_rows;
-        tp.cells_per_tile = p->geo.cells_per_tile - 1;
-        if (tp.cells_per_tile < 1) {
-            tp.cells_per_tile = 1;
-            tp.band_rows = p->geo.band_rows / 2;
-            if (tp.band_rows < 1) return FRI_HIP_ERR_INVALID_ARGUMENT;
-        }
+    const Knobs k = read_knobs();
+    const std::optional<int> cus = ctx ? std::optional<int>(ctx->cu_count) : std::nullopt;
+    Tiling fwd, inv;
+    if (int rc = choose_forward_tiling(width, height, channels, cus, k, fwd)) return rc;
+    p->own_inverse_tiling = choose_inverse_tiling(width, height, channels, cus, k, fwd, inv);
+    p->geo = std::move(fwd.geo);
+    p->fwd_tp = fwd.tp; // (fri_hip_plan_tune_forward starts from it)
+    if (p->own_inverse_tiling) {
+        p->geo_inv = std::move(inv.geo);
+        // what the plan keeps of geo_inv on the host: the tiling and its lists (fri_hip_plan_inverse_lists reads their sizes); the lattice arrays are geo's
+        std::vector<uint32_t>().swap(p->geo_inv.valid_mask), std::vector<int32_t>().swap(p->geo_inv.nbr_cells), std::vector<int32_t>().swap(p->geo_inv.pred_slots);
+    } else {
+        build_inverse_lists(p->geo, kInvListsMaxBytes);
     }
-    const TilingParams tp_forward = tp; // what the forward tiling was built with (fri_hip_plan_tune_forward starts from it)
-    // (from ~400 000 cells on - 16384^2 - the inverse kernel is fastest on groups of the forward plan's short shares, as in round 3: 386 against 408 us)
-    if (ctx && (env_str("FRI_HIP_INV_SHARED") ? env_int("FRI_HIP_INV_SHARED") <= 0 : p->geo.centers.size() < kOwnInverseMaxCells)) {
-        // the inverse kernel's own tiling: one share per resident workgroup (it prefers that at every size), dispatch-rank weights, interleaved, bands of
-        // 32 rows for planes / 16 for RGB (FRI_HIP_INV_BAND_ROWS); shrunk like the forward tiles until the (shared) LDS rectangle budget holds
-        set_ranks(tp.ranks); // (the forward plan is built: tp is free; this restores the dispatch-rank weights a many-shares forward plan had flattened)
-        TilingParams ti = tp;
-        ti.band_rows = env_int("FRI_HIP_INV_BAND_ROWS") > 0 ? env_int("FRI_HIP_INV_BAND_ROWS") : (channels == 1 ? 32 : 16);
-        ti.cells_per_tile = env_int("FRI_HIP_CELLS_PER_TILE");
-        ti.cells_per_wg = 0;
-        ti.target_wgs = ctx_wgs(ctx, tp.ranks);
-        ti.strided_shares = env_str("FRI_HIP_INV_STRIDED_SHARES") ? env_int("FRI_HIP_INV_STRIDED_SHARES") > 0 : (strided_env ? tp.strided_shares : true); // interleaved at every size it is built for
-        bool ok = false;
-        for (int guard = 0; guard < 64; guard++) {
-            if (!build_geometry(width, height, channels, ti, p->geo_inv).empty()) break;
-            DevicePlan probe;
-            probe.channels = (int32_t)channels;
-            probe.lds_pitch = p->geo_inv.lds_pitch;
-            probe.lds_rows = p->geo_inv.lds_rows;
-            probe.max_tile_cells = p->geo_inv.max_tile_cells;
-            probe.max_wg_tiles = std::max(p->geo_inv.max_wg_tiles, p->geo_inv.max_wg_tiles_batch);
-            probe.inv_max_wg_tiles = p->geo_inv.max_wg_tiles, probe.inv_max_wg_cells = p->geo_inv.max_wg_cells;
-            // the inverse kernel's OWN limits (the forward kernel's budget said nothing about them); the lists' rectangle is checked once they are built
-            if (fwd_plan_fits(probe) && inv_plan_fits(probe, false)) { // (the forward budget too, as through round 4: it keeps the tiles at the size the kernel was tuned for)
-                ok = true;
-                break;
-            }
-            ti.band_rows = p->geo_inv.band_rows;
-            ti.cells_per_tile = p->geo_inv.cells_per_tile - 1;
-            if (ti.cells_per_tile < 1) {
-                ti.cells_per_tile = 1;
-                ti.band_rows = p->geo_inv.band_rows / 2;
-                if (ti.band_rows < 1) break;
-            }
-        }
-        p->own_inverse_tiling = ok;
-        if (!ok) p->geo_inv = Geometry{};
+    if (!ctx) { // a host-only plan: the tilings are all there is
+        *out = plan.release();
+        return FRI_HIP_OK;
     }
-    build_inverse_lists(p->own_inverse_tiling ? p->geo_inv : p->geo, (size_t)256 << 20); // 6 MB at 4096^2; beyond 256 MB the inverse kernel scans the rectangle instead
-    if (p->own_inverse_tiling) { // with the lists built their LDS rectangle is known: a tiling whose lists kernel would not fit falls back to the shared (forward) tiling
-        DevicePlan probe;
-        probe.channels = (int32_t)channels;
-        probe.lds_pitch = p->geo_inv.lds_pitch, probe.lds_rows = p->geo_inv.lds_rows, probe.max_tile_cells = p->geo_inv.max_tile_cells;
-        probe.inv_max_wg_tiles = p->geo_inv.max_wg_tiles, probe.inv_max_wg_cells = p->geo_inv.max_wg_cells, probe.inv_rect_bytes = p->geo_inv.inv_rect_bytes;
-        if (!p->geo_inv.inv_lists.empty() && !inv_plan_fits(probe, true)) {
-            p->own_inverse_tiling = false;
-            p->geo_inv = Geometry{};
-            build_inverse_lists(p->geo, (size_t)256 << 20);
-        }
+    if (hipSetDevice(ctx->device) != hipSuccess) return FRI_HIP_ERR_HIP;
+    const Geometry &g = p->geo, &gi = p->inv_geo();
+    DevicePlan &d = p->dev;
+    std::vector<uint16_t> tab(&st.nbr_table[0][0], &st.nbr_table[0][0] + kCell * 6);
+    std::vector<uint32_t> gather_off((size_t)kCell * 4);
+    std::vector<uint16_t> pair_pos(256), heap_of_pos(kCell);
+    build_gather_tables(tab.data(), gather_off.data(), pair_pos.data(), heap_of_pos.data());
+    std::vector<uint32_t> halo_list(1024);
+    build_halo_list(tab.data(), pair_pos.data(), halo_list.data());
+    build_lf_deltas(tab.data(), d.lf_delta);
+    bool node0_gathered = false; // the fit kernels stage heap node 0 (the DC value) as the zero their "never a node" entries read: no node with a row may gather it
+    for (int n = 2; n < kCell; n++)
+        for (int i = 0; i < 6; i++) node0_gathered |= !(tab[(size_t)n * 6 + i] & 0x8000u) && (tab[(size_t)n * 6 + i] & 511u) == 0;
+    if (halo_list[0] == 0xFFFFFFFFu || node0_gathered || pair_pos[0] != 0) { // (pair 0 = heap nodes 0 and 1 at the head of a cell: where the fit kernels' zero lives) // more halo values than threads / ...: the neighbour table is not the one the kernels were laid out for
+        return FRI_HIP_ERR_INVALID_ARGUMENT;
     }
-    if (ctx) {
-        if (hipSetDevice(ctx->device) != hipSuccess) return FRI_HIP_ERR_HIP;
-        const Geometry &g = p->geo;
-        DevicePlan &d = p->dev;
-        int rc = FRI_HIP_OK;
-        std::vector<uint16_t> tab(&st.nbr_table[0][0], &st.nbr_table[0][0] + kCell * 6);
-        std::vector<uint32_t> gather_off((size_t)kCell * 4);
-        std::vector<uint16_t> pair_pos(256), heap_of_pos(kCell);
-        build_gather_tables(tab.data(), gather_off.data(), pair_pos.data(), heap_of_pos.data());
-        std::vector<uint32_t> halo_list(1024);
-        build_halo_list(tab.data(), pair_pos.data(), halo_list.data());
-        build_lf_deltas(tab.data(), d.lf_delta);
-        bool node0_gathered = false; // the fit kernels stage heap node 0 (the DC value) as the zero their "never a node" entries read: no node with a row may gather it
-        for (int n = 2; n < kCell; n++)
-            for (int k = 0; k < 6; k++) node0_gathered |= !(tab[(size_t)n * 6 + k] & 0x8000u) && (tab[(size_t)n * 6 + k] & 511u) == 0;
-        if (halo_list[0] == 0xFFFFFFFFu || node0_gathered || pair_pos[0] != 0) { // (pair 0 = heap nodes 0 and 1 at the head of a cell: where the fit kernels' zero lives) // more halo values than threads / ...: the neighbour table is not the one the kernels were laid out for
-            return FRI_HIP_ERR_INVALID_ARGUMENT;
-        }
-        if ((rc = upload(p, g.tiles, d.tiles)) || (rc = upload(p, g.tile_cells, d.tile_cells)) || (rc = upload(p, g.tile_meta, d.tile_meta)) || (rc = upload(p, g.wg_tiles, d.wg_tiles)) || (rc = upload(p, g.wg_tiles_batch, d.wg_tiles_batch)) || (rc = upload(p, g.centers, d.centers)) ||
-            (rc = upload(p, g.interior, d.interior)) || (rc = upload(p, g.valid_mask, d.valid_mask)) ||
-            (rc = upload(p, g.nbr_cells, d.nbr_cells)) || (rc = upload(p, g.pred_slots, d.pred_slots)) || (rc = upload(p, tab, d.nbr_table)) ||
-            (rc = upload(p, gather_off, d.gather_off)) || (rc = upload(p, pair_pos, d.pair_pos)) || (rc = upload(p, heap_of_pos, d.heap_of_pos)) ||
-            (rc = upload(p, halo_list, d.halo_list)))
-            return rc;
-        d.n_pred_tiles = g.n_pred_tiles;
-        d.n_tiles = (uint32_t)g.tiles.size();
-        d.F = (uint32_t)g.centers.size();
-        d.width = (int32_t)g.width;
-        d.height = (int32_t)g.height;
-        d.channels = (int32_t)g.channels;
-        d.lds_pitch = g.lds_pitch;
-        d.lds_rows = g.lds_rows;
-            d.cells_per_tile = g.cells_per_tile;
-        d.max_tile_cells = g.max_tile_cells;
-        d.covers_image = g.n_valid_leaves == (uint64_t)g.width * g.height;
-        d.max_wg_tiles = std::max(g.max_wg_tiles, g.max_wg_tiles_batch);
-        d.n_wg_batch = (uint32_t)g.wg_tiles_batch.size() - 1;
-        d.max_wg_cells = g.max_wg_cells;
-        // the inverse kernel keeps one share per resident workgroup: with the forward kernel's many short shares it walks groups of them
-        d.inv_group = many_shares && g.wg_tiles.size() > 1 && (g.wg_tiles.size() - 1) % 1024 == 0 ? (int32_t)((g.wg_tiles.size() - 1) / 1024) : 1;
-        d.inv_max_wg_tiles = d.inv_group > 1 ? 0 : d.max_wg_tiles, d.inv_max_wg_cells = d.inv_group > 1 ? 0 : d.max_wg_cells;
-        for (size_t sh = 0; d.inv_group > 1 && sh + d.inv_group < g.wg_tiles.size(); sh += d.inv_group) {
-            const Tile &first = g.tiles[g.wg_tiles[sh]], &last = g.tiles[g.wg_tiles[sh + d.inv_group] - 1];
-            d.inv_max_wg_cells = std::max(d.inv_max_wg_cells, last.cell_begin + last.cell_count - first.cell_begin);
-            d.inv_max_wg_tiles = std::max(d.inv_max_wg_tiles, g.wg_tiles[sh + d.inv_group] - g.wg_tiles[sh]);
-        }
-        d.n_wg = (uint32_t)g.wg_tiles.size() - 1;
-        d.pred_blocks = (uint32_t)ctx->cu_count;
-        if (env_int("FRI_HIP_PRED_BLOCKS") > 0) d.pred_blocks = (uint32_t)env_int("FRI_HIP_PRED_BLOCKS");
-        {
-            auto &j = p->owned.emplace_back();
-            if (hipMalloc(j.put(), (size_t)d.pred_blocks * kPredJunkWaves * kPredJunkBytes) != hipSuccess) return FRI_HIP_ERR_HIP;
-            d.junk = static_cast<uint8_t *>(j.get());
-        }
-        d.hist_blocks = 2u * (uint32_t)ctx->cu_count; // two resident 512-thread workgroups per CU (LDS: 2 x 78 KiB)
-        d.k1_ablate = env_int("FRI_HIP_K1_ABLATE");
-        if (env_str("FRI_HIP_K1_CACHED_STORES")) d.k1_cached_stores = env_int("FRI_HIP_K1_CACHED_STORES") > 0 ? 1 : 0; // tuning: force plain (1) / nontemporal (0) coefficient stores everywhere
-        d.k2_ablate = env_int("FRI_HIP_K2_ABLATE");
-        if (const char *e = env_str("FRI_HIP_K1_BATCH_SHARES")) d.k1_batch_shares = std::atoi(e) != 0;
-        d.k3_ablate = env_int("FRI_HIP_K3_ABLATE");
-        d.k4_ablate = env_int("FRI_HIP_K4_ABLATE");
-        if (const char *e = env_str("FRI_HIP_K4_OLDER_EIGHTHS")) d.k4_older_eighths = std::atoi(e);
-        d.k3_scan = env_int("FRI_HIP_K3_SCAN") > 0;
-        {
-            const Geometry &gi = p->inv_geo();
-            if (!gi.inv_lists.empty()) {
-                if ((rc = upload(p, gi.inv_lists, d.inv_lists)) || (rc = upload(p, gi.inv_quads, d.inv_quads, kInvListPad)) || (rc = upload(p, gi.inv_dwords, d.inv_dwords, kInvListPad)) ||
-                    (rc = upload(p, gi.inv_parts, d.inv_parts, kInvListPad)))
-                    return rc;
-                d.inv_rect_bytes = gi.inv_rect_bytes;
-            }
-        }
-        if (env_int("FRI_HIP_TRACE") > 0) {
-            const size_t bytes = (size_t)std::max<size_t>(d.n_wg, p->own_inverse_tiling ? p->geo_inv.wg_tiles.size() : 0) * 16 * sizeof(unsigned long long);
-            auto &t = p->owned.emplace_back();
-            if (hipMalloc(t.put(), bytes) != hipSuccess || hipMemset(t, 0, bytes) != hipSuccess) return FRI_HIP_ERR_HIP;
-            d.trace = static_cast<unsigned long long *>(t.get());
-        }
-        int hb = env_int("FRI_HIP_HIST_BLOCKS");
-        if (hb > 0) d.hist_blocks = (uint32_t)hb;
-        if (hipEventCreate(p->ev_begin.put()) != hipSuccess || hipEventCreate(p->ev_end.put()) != hipSuccess) return FRI_HIP_ERR_HIP;
-        // the inverse kernel's view of the plan: everything of `dev`, with its own tiles, cell records and shares swapped in
-        p->dev_inv = d;
-        if (p->own_inverse_tiling) {
-            Geometry &gi = p->geo_inv;
-            DevicePlan &di = p->dev_inv;
-            if ((rc = upload(p, gi.tiles, di.tiles)) || (rc = upload(p, gi.tile_cells, di.tile_cells)) || (rc = upload(p, gi.tile_meta, di.tile_meta)) || (rc = upload(p, gi.wg_tiles, di.wg_tiles)))
-                return rc;
-            di.wg_tiles_batch = nullptr, di.n_wg_batch = 0;
-            di.n_tiles = (uint32_t)gi.tiles.size();
-            di.n_wg = (uint32_t)gi.wg_tiles.size() - 1;
-            di.lds_pitch = gi.lds_pitch, di.lds_rows = gi.lds_rows, di.cells_per_tile = gi.cells_per_tile, di.max_tile_cells = gi.max_tile_cells;
-            di.max_wg_tiles = gi.max_wg_tiles, di.max_wg_cells = gi.max_wg_cells;
-            di.inv_group = 1, di.inv_max_wg_tiles = gi.max_wg_tiles, di.inv_max_wg_cells = gi.max_wg_cells;
-            // what the plan keeps of geo_inv on the host: the tiling (fri_hip_plan_inverse_lists reads the list sizes); the lattice arrays are geo's
-            for (auto *v : {&gi.valid_mask}) std::vector<uint32_t>().swap(*v);
-            std::vector<int32_t>().swap(gi.nbr_cells), std::vector<int32_t>().swap(gi.pred_slots);
-        }
+    auto &bufs = p->owned;
+    hipError_t e;
+    if ((e = upload_tiling(bufs, g, d, false)) || (e = upload(bufs, g.centers, d.centers)) || (e = upload(bufs, g.interior, d.interior)) || (e = upload(bufs, g.valid_mask, d.valid_mask)) ||
+        (e = upload(bufs, g.nbr_cells, d.nbr_cells)) || (e = upload(bufs, g.pred_slots, d.pred_slots)) || (e = upload(bufs, tab, d.nbr_table)) ||
+        (e = upload(bufs, gather_off, d.gather_off)) || (e = upload(bufs, pair_pos, d.pair_pos)) || (e = upload(bufs, heap_of_pos, d.heap_of_pos)) ||
+        (e = upload(bufs, halo_list, d.halo_list)))
+        return fail_hip(ctx, e, "plan tables");
+    if (!gi.inv_lists.empty()) {
+        if ((e = upload(bufs, gi.inv_lists, d.inv_lists)) || (e = upload(bufs, gi.inv_quads, d.inv_quads, kInvListPad)) || (e = upload(bufs, gi.inv_dwords, d.inv_dwords, kInvListPad)) ||
+            (e = upload(bufs, gi.inv_parts, d.inv_parts, kInvListPad)))
+            return fail_hip(ctx, e, "inverse lists");
+        d.inv_rect_bytes = gi.inv_rect_bytes;
     }
-    p->fwd_tp = tp_forward;
-    p->fwd_tunable = ctx && p->own_inverse_tiling && !many_shares && !p->dev.trace && !env_str("FRI_HIP_BAND_ROWS") && !env_str("FRI_HIP_CELLS_PER_TILE") &&
-                     !env_str("FRI_HIP_CELLS_PER_WG") && !env_str("FRI_HIP_STRIDED_SHARES") && !env_str("FRI_HIP_TARGET_WGS") && !env_str("FRI_HIP_RANKS") &&
-                     !env_str("FRI_HIP_TILE_BYTES") && !env_str("FRI_HIP_RANK_WEIGHTS");
+    d.F = (uint32_t)g.centers.size(), d.width = (int32_t)g.width, d.height = (int32_t)g.height, d.channels = (int32_t)g.channels, d.n_pred_tiles = g.n_pred_tiles;
+    d.covers_image = g.n_valid_leaves == (uint64_t)g.width * g.height;
+    // the inverse kernel keeps one share per resident workgroup: with the forward kernel's many short shares it walks groups of them
+    d.inv_group = fwd.many_shares && g.wg_tiles.size() > 1 && (g.wg_tiles.size() - 1) % 1024 == 0 ? (int32_t)((g.wg_tiles.size() - 1) / 1024) : 1;
+    d.inv_max_wg_tiles = d.inv_group > 1 ? 0 : d.max_wg_tiles, d.inv_max_wg_cells = d.inv_group > 1 ? 0 : d.max_wg_cells;
+    for (size_t sh = 0; d.inv_group > 1 && sh + d.inv_group < g.wg_tiles.size(); sh += d.inv_group) {
+        const Tile &first = g.tiles[g.wg_tiles[sh]], &last = g.tiles[g.wg_tiles[sh + d.inv_group] - 1];
+        d.inv_max_wg_cells = std::max(d.inv_max_wg_cells, last.cell_begin + last.cell_count - first.cell_begin);
+        d.inv_max_wg_tiles = std::max(d.inv_max_wg_tiles, g.wg_tiles[sh + d.inv_group] - g.wg_tiles[sh]);
+    }
+    d.pred_blocks = k.pred_blocks > 0 ? (uint32_t)k.pred_blocks : (uint32_t)ctx->cu_count;
+    d.hist_blocks = k.hist_blocks > 0 ? (uint32_t)k.hist_blocks : 2u * (uint32_t)ctx->cu_count; // two resident 512-thread workgroups per CU (LDS: 2 x 78 KiB)
+    d.k1_ablate = k.k1_ablate;
+    if (k.k1_cached_stores) d.k1_cached_stores = *k.k1_cached_stores > 0 ? 1 : 0; // tuning: force plain (1) / nontemporal (0) coefficient stores everywhere
+    if (k.k1_batch_shares) d.k1_batch_shares = *k.k1_batch_shares != 0;
+    d.k2_ablate = k.k2_ablate;
+    d.k3_ablate = k.k3_ablate;
+    d.k3_scan = k.k3_scan > 0;
+    d.k4_ablate = k.k4_ablate;
+    if (k.k4_older_eighths) d.k4_older_eighths = *k.k4_older_eighths;
+    if (hipMalloc(bufs.emplace_back().put(), (size_t)d.pred_blocks * kPredJunkWaves * kPredJunkBytes) != hipSuccess) return FRI_HIP_ERR_HIP;
+    d.junk = static_cast<uint8_t *>(bufs.back().get());
+    if (k.trace > 0) {
+        const size_t bytes = (size_t)std::max<size_t>(d.n_wg, p->own_inverse_tiling ? gi.wg_tiles.size() : 0) * 16 * sizeof(unsigned long long);
+        auto &t = bufs.emplace_back();
+        if (hipMalloc(t.put(), bytes) != hipSuccess || hipMemset(t, 0, bytes) != hipSuccess) return FRI_HIP_ERR_HIP;
+        d.trace = static_cast<unsigned long long *>(t.get());
+    }
+    if (hipEventCreate(p->ev_begin.put()) != hipSuccess || hipEventCreate(p->ev_end.put()) != hipSuccess) return FRI_HIP_ERR_HIP;
+    // the inverse kernel's view of the plan: everything of `dev`, with its own tiles, cell records and shares swapped in
+    p->dev_inv = d;
+    if (p->own_inverse_tiling && (e = upload_tiling(bufs, gi, p->dev_inv, true))) return fail_hip(ctx, e, "inverse tiling");
+    p->fwd_tunable = p->own_inverse_tiling && !fwd.many_shares && !d.trace && !k.pins_forward;
     if (p->fwd_tunable) adopt_cached_forward_tiling(p); // a tiling measured for this device and shape earlier in the process (fri_hip_plan_tune_forward)
     *out = plan.release();
     return FRI_HIP_OK;
