@@ -29,7 +29,9 @@ SYMBOLS = [
     "fri_hip_plan_assume_forward_coefficients", "fri_hip_encode_image_batch", "fri_hip_multi_encode_image",
     "fri_hip_plan_set_stream_order", "fri_hip_symbol_stream_batch_dev", "fri_hip_encode_image_symbols", "fri_hip_encode_symbols_batch_dev",
     "fri_hip_plan_set_dequantiser", "fri_hip_plan_tune_forward", "fri_hip_time_transform_quant_streams_dev",
+    "fri_hip_plan_set_colour_transform",
 ]
+COLOUR_NONE, COLOUR_RCT = 0, 1  # fri_hip_plan_set_colour_transform
 
 
 class FriHipError(RuntimeError):
@@ -145,6 +147,7 @@ def load_library():
     L.fri_hip_fit_params_batch_dev.argtypes = [vp, u32, vp, sz, vp, vp, vp]
     L.fri_hip_plan_assume_forward_coefficients.argtypes = [vp, i32]
     L.fri_hip_plan_set_dequantiser.argtypes = [vp, i32]
+    L.fri_hip_plan_set_colour_transform.argtypes = [vp, i32]
     L.fri_hip_plan_set_stream_order.argtypes = [vp, vp, C.c_uint64]
     L.fri_hip_symbol_stream_batch_dev.argtypes = [vp, u32, vp, sz, vp, vp, sz, vp, sz, vp]
     L.fri_hip_encode_image_symbols.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp]
@@ -269,6 +272,12 @@ class Multi:
         return _encode_batch(load_library().fri_hip_multi_encode_image, self._h, "fri_hip_multi_encode_image", None, images, self.channels, self.num_cells, qmatrix, fit, params,
                              want_bucket, want_prediction)
 
+    def set_colour_transform(self, mode):
+        """fri_hip_plan_set_colour_transform on every device's plan (see Plan.set_colour_transform)."""
+        L = load_library()
+        for d in range(self.num_devices):
+            _check(L.fri_hip_plan_set_colour_transform(L.fri_hip_multi_plan(self._h, d), int(mode)), "fri_hip_plan_set_colour_transform")
+
     def close(self):
         if self._h:
             load_library().fri_hip_multi_destroy(self._h)
@@ -314,6 +323,7 @@ class Plan:
         self._h = None
         self.ctx = ctx
         self.width, self.height, self.channels = width, height, channels
+        self.colour_transform = COLOUR_NONE
         h = C.c_void_p()
         _check(load_library().fri_hip_plan_create(ctx._h if ctx else None, width, height, channels, C.byref(h)), "fri_hip_plan_create", ctx)
         self._h = h
@@ -362,6 +372,12 @@ class Plan:
     def set_dequantiser(self, multiply):
         """fri_hip_plan_set_dequantiser: False = the reference's dividing quantization::decode (default), True = coefficient x qmatrix[layer]."""
         _check(load_library().fri_hip_plan_set_dequantiser(self._h, 1 if multiply else 0), "fri_hip_plan_set_dequantiser")
+
+    def set_colour_transform(self, mode):
+        """fri_hip_plan_set_colour_transform: COLOUR_NONE (default) or COLOUR_RCT (C = 3 plans): every forward entry point then codes the planes
+        (Y, Cb, Cr) = (G, B - G + 128, R - G + 128) mod 256 of the R, G, B pixels, and every inverse entry point writes R, G, B back."""
+        _check(load_library().fri_hip_plan_set_colour_transform(self._h, int(mode)), "fri_hip_plan_set_colour_transform")
+        self.colour_transform = int(mode)
 
     def assume_forward_coefficients(self, on=True):
         """fri_hip_plan_assume_forward_coefficients: the predict entry points then skip the exact-kernel guard launch."""

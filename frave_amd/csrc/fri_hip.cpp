@@ -855,6 +855,12 @@ int fri_hip_plan_set_dequantiser(fri_hip_plan *p, int mode) {
     return FRI_HIP_OK;
 }
 
+int fri_hip_plan_set_colour_transform(fri_hip_plan *p, int mode) {
+    if (!p || (mode != FRI_HIP_COLOUR_NONE && mode != FRI_HIP_COLOUR_RCT) || (mode == FRI_HIP_COLOUR_RCT && p->geo.channels != 3)) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    p->dev.rct = p->dev_inv.rct = mode == FRI_HIP_COLOUR_RCT;
+    return FRI_HIP_OK;
+}
+
 int fri_hip_plan_centers(const fri_hip_plan *p, int32_t *centers) {
     if (!p || !centers) return FRI_HIP_ERR_INVALID_ARGUMENT;
     std::memcpy(centers, p->geo.centers.data(), p->geo.centers.size() * sizeof(Int2));

@@ -336,6 +336,47 @@ __device__ __forceinline__ void fetch_windows_rgb(int buf_off, const int (&rb)[3
     w[5] = __builtin_amdgcn_alignbyte(d21, d20, b2 & 3u);
     w[6] = __builtin_amdgcn_alignbyte(d22, d21, b2 & 3u);
 }
+// RCT (fri_hip_plan_set_colour_transform): the G windows next to a channel-0 (R) or channel-2 (B) item's windows, out of the same dwords. A pixel's G byte
+// sits one byte after its R byte and one before its B byte, so the G window of w[k] starts at byte s + 1 (R) or s - 1 (B) of the dwords w[k] was aligned
+// out of (s = the window's byte offset in its first dword): one more v_alignbyte per window, and one more dword per row in front of the row's first for B
+// (s - 1 < 0). A channel-1 (G) item gets a constant 0x80 in every byte: rct_leaves then leaves its leaves as they are.
+template <int DELTA>
+__device__ __forceinline__ uint32_t g_window(uint32_t dm, uint32_t d0, uint32_t d1, uint32_t s) {
+    if constexpr (DELTA > 0) return s == 3u ? d1 : __builtin_amdgcn_alignbyte(d1, d0, s + 1u);
+    else return s == 0u ? __builtin_amdgcn_alignbyte(d0, dm, 3u) : __builtin_amdgcn_alignbyte(d1, d0, s - 1u);
+}
+template <int DELTA>
+__device__ __forceinline__ void fetch_g_windows_rgb(int buf_off, const int (&rb)[3], uint32_t (&g)[7]) {
+    const uint32_t b0 = (uint32_t)(buf_off + rb[0]), b1 = (uint32_t)(buf_off + rb[1] - 3), b2 = (uint32_t)(buf_off + rb[2] - 3);
+    const LdsDwordPtr p0 = (LdsDwordPtr)(uintptr_t)(b0 & ~3u), p1 = (LdsDwordPtr)(uintptr_t)(b1 & ~3u), p2 = (LdsDwordPtr)(uintptr_t)(b2 & ~3u);
+    // (the same addresses as fetch_windows_rgb: the compiler merges the loads.) DELTA < 0: the dword holding byte b - 1, which is the one in front of the row's
+    // first dword exactly when s = 0, the only case g_window looks at it - and then b - 1 is still a byte of the staged row, so no read leaves the buffer.
+    auto before = [](uint32_t b) { return DELTA < 0 ? *(LdsDwordPtr)(uintptr_t)((b - 1u) & ~3u) : 0u; };
+    const uint32_t d0m = before(b0), d00 = p0[0], d01 = p0[1], d02 = p0[2];
+    const uint32_t d1m = before(b1), d10 = p1[0], d11 = p1[1], d12 = p1[2], d13 = p1[3];
+    const uint32_t d2m = before(b2), d20 = p2[0], d21 = p2[1], d22 = p2[2];
+    g[0] = g_window<DELTA>(d0m, d00, d01, b0 & 3u);
+    g[1] = g_window<DELTA>(d00, d01, d02, b0 & 3u);
+    g[2] = g_window<DELTA>(d1m, d10, d11, b1 & 3u);
+    g[3] = g_window<DELTA>(d10, d11, d12, b1 & 3u);
+    g[4] = g_window<DELTA>(d11, d12, d13, b1 & 3u);
+    g[5] = g_window<DELTA>(d2m, d20, d21, b2 & 3u);
+    g[6] = g_window<DELTA>(d20, d21, d22, b2 & 3u);
+}
+// ch: the byte of the pixel the item reads (wave-uniform): 0 = R, 2 = B, 1 = G (the Y plane)
+__device__ __forceinline__ void fetch_g_windows_item(int buf_off, const int (&rb)[3], int ch, uint32_t (&g)[7]) {
+    if (ch == 0) {
+        fetch_g_windows_rgb<1>(buf_off, rb, g);
+    } else if (ch == 2) {
+        fetch_g_windows_rgb<-1>(buf_off, rb, g);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 7; k++) g[k] = 0x80808080u;
+    }
+}
+// Per 16-bit half: (x - g + 128) mod 256 (Cb, Cr; the G plane keeps its values because its g is 128). x + 384 - g stays in [129, 639]: no borrow between the halves.
+__device__ __forceinline__ uint32_t rct_leaf(uint32_t x, uint32_t g) { return (x + 0x01800180u - g) & 0x00FF00FFu; }
+
 // {byte I of a, byte I of b} zero-extended into the two 16-bit halves.
 template <int I>
 __device__ __forceinline__ uint32_t pair_bytes(uint32_t a, uint32_t b) {
@@ -350,13 +391,16 @@ struct ItemAddr {
     uint32_t elem_off;  // (ch * F + cell) * 512
 };
 
-template <int C, bool FAST>
+// RCT: plane ch of the output is read from byte rct_source(ch) of the pixel: Y (plane 0) from G, Cb (plane 1) from B, Cr (plane 2) from R.
+__device__ __forceinline__ int rct_source(int ch) { return ch == 2 ? 0 : ch + 1; }
+
+template <int C, bool FAST, bool RCT = false>
 __device__ __forceinline__ ItemAddr item_addr(const FwdArgs &a, const Tile &t, const TileCell *meta, int it, int ldx, int ldy, int lane_rb, int buf_off,
                                                uint32_t sh_base, uint32_t wc16) {
-    const int cl = it / C, ch = it - cl * C;
+    const int cl = it / C, plane = it - cl * C, ch = RCT ? rct_source(plane) : plane; // ch: the byte of the pixel the item reads
     const TileCell m = meta[cl];
     ItemAddr r;
-    r.elem_off = ((uint32_t)ch * a.F + (uint32_t)__builtin_amdgcn_readfirstlane(m.cell)) * kCell;
+    r.elem_off = ((uint32_t)plane * a.F + (uint32_t)__builtin_amdgcn_readfirstlane(m.cell)) * kCell;
     const int x0 = m.cx + ldx, y0 = m.cy + ldy;
     // row y of the staged rectangle starts (a16 + (y * width + x_lo) * C) & 15 bytes into its LDS row
     const int col = __mul24(x0 - t.x_lo, C) + ch;
@@ -391,7 +435,10 @@ __device__ __forceinline__ ItemAddr item_addr(const FwdArgs &a, const Tile &t, c
 // rectangle of tile i+1 is already in flight from HBM/L2 into registers and is committed to the other buffer.
 // MEASURE: the same kernel under another name - the launches fri_hip_plan_tune_forward times on its scratch buffers (candidate tilings, most of them slower than
 // the one kept) must not sit in the same row of a kernel trace's statistics as the caller's launches.
-template <int C, bool EDGE, bool FAST, int NCH, bool QID, bool NT, bool MEASURE = false, bool C16 = false>
+// RCT (C = 3 only): the kernel codes the planes (Y, Cb, Cr) = (G, B - G + 128, R - G + 128) mod 256 of the reversible colour transform
+// (fri_hip_plan_set_colour_transform) as channels 0, 1, 2: the items of plane 0 read the G bytes, those of planes 1 and 2 the B and R bytes, whose leaves are
+// then replaced by their difference to the G byte of the same pixel before the transform.
+template <int C, bool EDGE, bool FAST, int NCH, bool QID, bool NT, bool MEASURE = false, bool C16 = false, bool RCT = false>
 __global__ void __launch_bounds__(kFwdThreads) fwd_transform_quant_kernel(const FwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     if (ablate_flags(a.ablate) & 8) return; // timing only: what dispatching the grid alone costs
@@ -467,8 +514,8 @@ __global__ void __launch_bounds__(kFwdThreads) fwd_transform_quant_kernel(const 
             valid[c] = 0xFFFFFFFFu;
             if (itA < n_items) {
                 const int itB = itA + 1 < n_items ? itA + 1 : itA; // odd tail: item B mirrors A and is not stored
-                const ItemAddr A = item_addr<C, FAST>(a, t, meta, itA, ldx, ldy, lane_rb, buf_off, sh_base, wc16);
-                const ItemAddr B = item_addr<C, FAST>(a, t, meta, itB, ldx, ldy, lane_rb, buf_off, sh_base, wc16);
+                const ItemAddr A = item_addr<C, FAST, RCT>(a, t, meta, itA, ldx, ldy, lane_rb, buf_off, sh_base, wc16);
+                const ItemAddr B = item_addr<C, FAST, RCT>(a, t, meta, itB, ldx, ldy, lane_rb, buf_off, sh_base, wc16);
                 offA[c] = A.elem_off;
                 offB[c] = B.elem_off;
                 uint32_t leaf[8];
@@ -506,6 +553,20 @@ __global__ void __launch_bounds__(kFwdThreads) fwd_transform_quant_kernel(const 
                     leaf[5] = pair_bytes<1>(wA[4], wB[4]);
                     leaf[3] = pair_bytes<0>(wA[5], wB[5]);
                     leaf[7] = pair_bytes<2>(wA[6], wB[6]);
+                    if constexpr (RCT) { // before the mask below: leaves outside the image still enter as 0
+                        const int chA = rct_source(itA % 3), chB = rct_source(itB % 3); // the bytes the items read (item_addr)
+                        uint32_t gA[7], gB[7];
+                        fetch_g_windows_item(buf_off, A.rb, chA, gA);
+                        fetch_g_windows_item(buf_off, B.rb, chB, gB);
+                        leaf[0] = rct_leaf(leaf[0], pair_bytes<0>(gA[0], gB[0]));
+                        leaf[4] = rct_leaf(leaf[4], pair_bytes<2>(gA[1], gB[1]));
+                        leaf[2] = rct_leaf(leaf[2], pair_bytes<0>(gA[2], gB[2]));
+                        leaf[1] = rct_leaf(leaf[1], pair_bytes<3>(gA[2], gB[2]));
+                        leaf[6] = rct_leaf(leaf[6], pair_bytes<2>(gA[3], gB[3]));
+                        leaf[5] = rct_leaf(leaf[5], pair_bytes<1>(gA[4], gB[4]));
+                        leaf[3] = rct_leaf(leaf[3], pair_bytes<0>(gA[5], gB[5]));
+                        leaf[7] = rct_leaf(leaf[7], pair_bytes<2>(gA[6], gB[6]));
+                    }
                     if ((A.leaf_mask & B.leaf_mask) != 0xFFu) { // some lane has a leaf outside the image: it enters as 0, the None outputs come from the validity tree
 #pragma unroll
                         for (int j = 0; j < 8; j++) {
@@ -616,23 +677,24 @@ hipError_t launch_fwd_transform_quant(const DevicePlan &p, uint32_t n_images, co
     const bool edge = (reinterpret_cast<uintptr_t>(pixels) & 15) || (img_bytes & 15) || (n_images > 1 && (pixel_stride & 15));
     const bool fast = !edge && (((size_t)p.width * p.channels) & 15) == 0; // every image row starts at the same offset mod 16
     const bool small = fwd_chunks(p) <= 4 * (size_t)kFwdThreads;           // 4 chunks per thread suffice (the common, tuned case)
+    const bool rct = p.rct && p.channels == 3; // (fri_hip_plan_set_colour_transform refuses RCT on other plans)
     void (*kern)(FwdArgs);
-#define FRI_PICK_T(CH, E, FA, N, QI) (plain ? fwd_transform_quant_kernel<CH, E, FA, N, QI, false> : fwd_transform_quant_kernel<CH, E, FA, N, QI, true>)
-#define FRI_PICK_Q(CH, E, FA, N) (a.q_identity ? FRI_PICK_T(CH, E, FA, N, true) : FRI_PICK_T(CH, E, FA, N, false))
-#define FRI_PICK_N(CH, E, FA) (small ? FRI_PICK_Q(CH, E, FA, 4) : FRI_PICK_Q(CH, E, FA, kMaxChunksPerThread))
-#define FRI_PICK(CH) (edge ? FRI_PICK_N(CH, true, false) : fast ? FRI_PICK_N(CH, false, true) : FRI_PICK_N(CH, false, false))
-    kern = p.channels == 1 ? FRI_PICK(1) : FRI_PICK(3);
+#define FRI_PICK_T(CH, E, FA, N, QI, R) (plain ? fwd_transform_quant_kernel<CH, E, FA, N, QI, false, false, false, R> : fwd_transform_quant_kernel<CH, E, FA, N, QI, true, false, false, R>)
+#define FRI_PICK_Q(CH, E, FA, N, R) (a.q_identity ? FRI_PICK_T(CH, E, FA, N, true, R) : FRI_PICK_T(CH, E, FA, N, false, R))
+#define FRI_PICK_N(CH, E, FA, R) (small ? FRI_PICK_Q(CH, E, FA, 4, R) : FRI_PICK_Q(CH, E, FA, kMaxChunksPerThread, R))
+#define FRI_PICK(CH, R) (edge ? FRI_PICK_N(CH, true, false, R) : fast ? FRI_PICK_N(CH, false, true, R) : FRI_PICK_N(CH, false, false, R))
+    kern = p.channels == 1 ? FRI_PICK(1, false) : rct ? FRI_PICK(3, true) : FRI_PICK(3, false);
     if (p.k1_measuring && !edge && !plain && a.q_identity) { // the tuner's launches (aligned scratch, all-ones matrix, nontemporal stores): the MEASURE instance
-#define FRI_PICK_M(CH) (fast ? (small ? fwd_transform_quant_kernel<CH, false, true, 4, true, true, true> : fwd_transform_quant_kernel<CH, false, true, kMaxChunksPerThread, true, true, true>) \
-                             : (small ? fwd_transform_quant_kernel<CH, false, false, 4, true, true, true> : fwd_transform_quant_kernel<CH, false, false, kMaxChunksPerThread, true, true, true>))
-        kern = p.channels == 1 ? FRI_PICK_M(1) : FRI_PICK_M(3);
+#define FRI_PICK_M(CH, R) (fast ? (small ? fwd_transform_quant_kernel<CH, false, true, 4, true, true, true, false, R> : fwd_transform_quant_kernel<CH, false, true, kMaxChunksPerThread, true, true, true, false, R>) \
+                                : (small ? fwd_transform_quant_kernel<CH, false, false, 4, true, true, true, false, R> : fwd_transform_quant_kernel<CH, false, false, kMaxChunksPerThread, true, true, true, false, R>))
+        kern = p.channels == 1 ? FRI_PICK_M(1, false) : rct ? FRI_PICK_M(3, true) : FRI_PICK_M(3, false);
 #undef FRI_PICK_M
     }
     if (coefs16) { // (plain stores, no MEASURE instance)
-#define FRI_PICK_C(CH, E, FA, N) (a.q_identity ? fwd_transform_quant_kernel<CH, E, FA, N, true, false, false, true> : fwd_transform_quant_kernel<CH, E, FA, N, false, false, false, true>)
-#define FRI_PICK_CN(CH, E, FA) (small ? FRI_PICK_C(CH, E, FA, 4) : FRI_PICK_C(CH, E, FA, kMaxChunksPerThread))
-#define FRI_PICK_CC(CH) (edge ? FRI_PICK_CN(CH, true, false) : fast ? FRI_PICK_CN(CH, false, true) : FRI_PICK_CN(CH, false, false))
-        kern = p.channels == 1 ? FRI_PICK_CC(1) : FRI_PICK_CC(3);
+#define FRI_PICK_C(CH, E, FA, N, R) (a.q_identity ? fwd_transform_quant_kernel<CH, E, FA, N, true, false, false, true, R> : fwd_transform_quant_kernel<CH, E, FA, N, false, false, false, true, R>)
+#define FRI_PICK_CN(CH, E, FA, R) (small ? FRI_PICK_C(CH, E, FA, 4, R) : FRI_PICK_C(CH, E, FA, kMaxChunksPerThread, R))
+#define FRI_PICK_CC(CH, R) (edge ? FRI_PICK_CN(CH, true, false, R) : fast ? FRI_PICK_CN(CH, false, true, R) : FRI_PICK_CN(CH, false, false, R))
+        kern = p.channels == 1 ? FRI_PICK_CC(1, false) : rct ? FRI_PICK_CC(3, true) : FRI_PICK_CC(3, false);
 #undef FRI_PICK_CC
 #undef FRI_PICK_CN
 #undef FRI_PICK_C

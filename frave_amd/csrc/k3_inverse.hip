@@ -175,7 +175,62 @@ __device__ __forceinline__ InvTileLists scalar_lists(const InvTileLists &l) {
     return r;
 }
 
-template <int NI>
+// ---- RCT (fri_hip_plan_set_colour_transform): the tile's rectangle holds (Cr, Y, Cb) = (R - G + 128, G, B - G + 128) of every pixel its cells own, and is turned
+// into (R, G, B) in place once it is complete, before the write-out: R = Cr + Y - 128, B = Cb + Y - 128 (mod 256), G = Y. The three channels of a pixel first
+// meet there (an item is one channel of one cell). Y never changes, so a thread may read the Y bytes of pixels that straddle its part while their owner rewrites
+// their other bytes.
+// The items of plane 0 (Y) write the G byte of their pixels, those of plane 1 (Cb) the B byte, plane 2 (Cr) the R byte.
+__device__ __forceinline__ int rct_target(int plane) { return plane == 2 ? 0 : plane + 1; }
+// Scanning kernel (16 bit per byte, ownership in bit 8): one pixel per thread; a pixel no cell owns stays 0 (all three of its channels are unowned).
+__device__ __forceinline__ void rct_inverse_rect16(uint16_t *img16, const Tile &t, int pitch16, uint32_t base_lo, uint32_t wc, int tid) {
+    const int n_px = t.n_rows * t.width_px;
+    const float inv_w = 1.0f / (float)t.width_px;
+    for (int q = tid; q < n_px; q += kInvThreads) {
+        int r = (int)(((float)q + 0.5f) * inv_w), i = q - r * t.width_px;
+        if (i < 0) r--, i += t.width_px; // (the float quotient may be off by one for large q)
+        else if (i >= t.width_px) r++, i -= t.width_px;
+        const uint32_t g = (uint32_t)(t.y_lo + r) * wc + (uint32_t)(t.x_lo * 3); // byte offset of the staged row (only bits 0-3 matter)
+        uint16_t *px = img16 + r * pitch16 + (int)((base_lo + g) & 15u) + 3 * i;
+        const uint32_t y = px[1];
+        if (y & 0x100u) {
+            px[0] = (uint16_t)(0x100u | ((px[0] + y + 128u) & 0xFFu));
+            px[2] = (uint16_t)(0x100u | ((px[2] + y + 128u) & 0xFFu));
+        }
+    }
+}
+// Lists kernel (one byte per byte, rows start at image column a0, a multiple of 16, and every image row at a multiple of 16 and of 3): the byte at offset j of a
+// staged row is channel (a0 + j) % 3 of its pixel. One 16-byte quad per thread, with the dword on either side for the Y bytes of the pixels it shares with its
+// neighbours: per byte (c ^ 0x80) + y without carries between the bytes. Bytes of pixels the tile does not own are transformed too and never written out.
+__device__ __forceinline__ uint32_t rct_inverse_dword(uint32_t d, uint32_t before, uint32_t after, int phase) {
+    // phase = channel of byte 0. Bytes of channel 0 (R) take Y from the byte after, channel 2 (B) from the byte before, channel 1 (G) stays.
+    const uint32_t m0 = phase == 0 ? 0xFF0000FFu : phase == 1 ? 0x00FF0000u : 0x0000FF00u;
+    const uint32_t m2 = phase == 0 ? 0x00FF0000u : phase == 1 ? 0x0000FF00u : 0xFF0000FFu;
+    const uint32_t y = (__builtin_amdgcn_alignbyte(after, d, 1u) & m0) | (__builtin_amdgcn_alignbyte(d, before, 3u) & m2);
+    const uint32_t c = d ^ 0x80808080u;
+    const uint32_t sum = ((c & 0x7F7F7F7Fu) + (y & 0x7F7F7F7Fu)) ^ ((c ^ y) & 0x80808080u);
+    return (sum & (m0 | m2)) | (d & ~(m0 | m2));
+}
+__device__ __forceinline__ void rct_inverse_rect8(uint8_t *img, const Tile &t, int pitch, int a0, int tid) {
+    const int qpr = pitch >> 4, n_quads = t.n_rows * qpr;
+    const float inv_q = 1.0f / (float)qpr;
+    for (int q = tid; q < n_quads; q += kInvThreads) {
+        int r = (int)(((float)q + 0.5f) * inv_q), k = q - r * qpr;
+        if (k < 0) r--, k += qpr;
+        else if (k >= qpr) r++, k -= qpr;
+        uint32_t *row = reinterpret_cast<uint32_t *>(img + r * pitch);
+        u32x4 v = reinterpret_cast<u32x4 *>(row)[k];
+        // the row's ends: a byte there that needs a neighbour outside the row belongs to a pixel outside the tile's columns (value unused)
+        const uint32_t before = row[k > 0 ? 4 * k - 1 : 0], after = row[k + 1 < qpr ? 4 * k + 4 : 4 * k + 3];
+        const int ph = (a0 + 16 * k) % 3; // channel of the quad's byte 0; dword i starts at channel (ph + i) % 3
+        const uint32_t o0 = rct_inverse_dword(v.x, before, v.y, ph);
+        const uint32_t o1 = rct_inverse_dword(v.y, v.x, v.z, ph == 2 ? 0 : ph + 1);
+        const uint32_t o2 = rct_inverse_dword(v.z, v.y, v.w, ph == 0 ? 2 : ph - 1);
+        const uint32_t o3 = rct_inverse_dword(v.w, v.z, after, ph);
+        reinterpret_cast<u32x4 *>(row)[k] = u32x4{o0, o1, o2, o3};
+    }
+}
+
+template <int NI, bool RCT = false>
 __global__ void __launch_bounds__(kInvThreads) inverse_transform_kernel(const InvArgs a) {
     // this image of the batch (grid.y). Scalars, not a modified copy of the argument struct: a copy would live in scratch memory
     // (the quantiser array inside is indexed dynamically) and every argument access with it.
@@ -236,7 +291,7 @@ __global__ void __launch_bounds__(kInvThreads) inverse_transform_kernel(const In
         for (int s = 0; s < NI; s++) {
             const int item = wave + kInvWaves * s;
             if (item < n_items && !(ablate_flags(a.ablate) & 2)) {
-                const int cl = item / C, ch = item - cl * C;
+                const int cl = item / C, plane = item - cl * C, ch = RCT ? rct_target(plane) : plane; // ch: the byte of the pixel the item writes
                 const TileCell tc = lds_cells[t.cell_begin - cell0 + cl];
                 const int x0 = tc.cx + lane_dx(lane), y0 = tc.cy + lane_dy(lane);
                 int rowbase[3];
@@ -260,6 +315,10 @@ __global__ void __launch_bounds__(kInvThreads) inverse_transform_kernel(const In
             }
         }
         lds_barrier(); // the rectangle is complete
+        if constexpr (RCT) {
+            rct_inverse_rect16(img16, t, pitch16, base_lo, wc, tid);
+            lds_barrier();
+        }
 
         // Quad pass over the flattened rectangle: a quad whose 16 bytes are all owned goes out as one store, a partly owned
         // one is queued as (row << 8 | quad).
@@ -334,7 +393,7 @@ __global__ void __launch_bounds__(kInvThreads) inverse_transform_kernel(const In
 // width * channels multiples of 16): the launcher falls back to inverse_transform_kernel otherwise.
 constexpr int kInvListPre = 3; // list entries a thread holds in flight per list and tile (more are loaded on demand)
 static_assert((size_t)kInvListPre * kInvThreads <= kInvListPad, "the lists' pad covers a thread's unconditional loads");
-template <int NI>
+template <int NI, bool RCT = false>
 __global__ void __launch_bounds__(kInvThreads) inverse_transform_lists_kernel(const InvArgs a) {
     const int32_t *const img_coefs = a.coefs + blockIdx.y * a.coef_stride; // this image of the batch, see inverse_transform_kernel
     uint8_t *const img_pixels = a.pixels + blockIdx.y * a.pixel_stride;
@@ -427,6 +486,7 @@ __global__ void __launch_bounds__(kInvThreads) inverse_transform_lists_kernel(co
             if (item < n_items && !(ablate_flags(a.ablate) & 2)) {
                 int cl, ch;
                 inv_item_split(item, C, cl, ch);
+                if (RCT) ch = rct_target(ch); // the byte of the pixel the item writes
                 const TileCell tc = lds_cells[t.cell_begin - cell0 + cl];
                 const int x0 = tc.cx + lane_dx(lane), y0 = tc.cy + lane_dy(lane);
                 // (cell part: scalar) + (lane part): one vector multiply-add per item
@@ -451,6 +511,10 @@ __global__ void __launch_bounds__(kInvThreads) inverse_transform_lists_kernel(co
         // to arrive, is slower - 30.2-31.5 us: gpurun_out/r5_k3f.)
         inv_land<NI>(pre);
         lds_barrier(); // the rectangle holds every byte this tile owns
+        if constexpr (RCT) {
+            rct_inverse_rect8(img, t, pitch, a0, tid);
+            lds_barrier();
+        }
         uint8_t *out0 = img_pixels + (size_t)t.y_lo * wc + (size_t)a0; // quad (r, k) -> out0 + r * wc + 16 k, 16-byte aligned
         // (a tile's rows x the image's row bytes stay far below 2^32, r < 256 and the row bytes below 2^24: 24-bit multiplies, a 32-bit offset on a uniform base)
         const uint32_t wc24 = (uint32_t)wc, pitch24 = (uint32_t)pitch;
@@ -540,6 +604,7 @@ hipError_t launch_inverse_transform(const DevicePlan &p, uint32_t n_images, cons
     a.q_multiply = p.k3_multiply ? 1 : 0;
     a.queue_bytes = (int32_t)inv_queue_bytes(p);
     const int items_per_wave = (p.max_tile_cells * p.channels + kInvWaves - 1) / kInvWaves;
+    const bool rct = p.rct && p.channels == 3; // (fri_hip_plan_set_colour_transform refuses RCT on other plans)
     if (!inv_plan_fits(p, false)) return hipErrorInvalidConfiguration;
     // static write-out lists when every image row starts 16-byte aligned (and their rectangle fits: fri_hip_plan_create checks that for the tilings it builds)
     const bool lists = p.inv_lists && !p.k3_scan && inv_plan_fits(p, true) && (reinterpret_cast<uintptr_t>(pixels) & 15) == 0 && (((size_t)p.width * p.channels) & 15) == 0 &&
@@ -551,7 +616,8 @@ hipError_t launch_inverse_transform(const DevicePlan &p, uint32_t n_images, cons
         a.parts = p.inv_parts;
         a.rect_bytes = p.inv_rect_bytes;
         const size_t lds2 = (size_t)p.inv_rect_bytes + (size_t)p.inv_max_wg_tiles * (sizeof(Tile) + sizeof(InvTileLists)) + (size_t)p.inv_max_wg_cells * sizeof(TileCell);
-        void (*k2)(const InvArgs) = items_per_wave <= 1 ? inverse_transform_lists_kernel<1> : items_per_wave == 2 ? inverse_transform_lists_kernel<2> : inverse_transform_lists_kernel<4>;
+        void (*k2)(const InvArgs) = rct ? (items_per_wave <= 1 ? inverse_transform_lists_kernel<1, true> : items_per_wave == 2 ? inverse_transform_lists_kernel<2, true> : inverse_transform_lists_kernel<4, true>)
+                                        : (items_per_wave <= 1 ? inverse_transform_lists_kernel<1> : items_per_wave == 2 ? inverse_transform_lists_kernel<2> : inverse_transform_lists_kernel<4>);
         if (lds2 > 48 * 1024) {
             hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k2), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
             if (e != hipSuccess) return e;
@@ -561,7 +627,8 @@ hipError_t launch_inverse_transform(const DevicePlan &p, uint32_t n_images, cons
         return hipGetLastError();
     }
     const size_t lds = inv_lds_bytes(p);
-    void (*kern)(const InvArgs) = items_per_wave <= 1 ? inverse_transform_kernel<1> : items_per_wave == 2 ? inverse_transform_kernel<2> : inverse_transform_kernel<4>;
+    void (*kern)(const InvArgs) = rct ? (items_per_wave <= 1 ? inverse_transform_kernel<1, true> : items_per_wave == 2 ? inverse_transform_kernel<2, true> : inverse_transform_kernel<4, true>)
+                                      : (items_per_wave <= 1 ? inverse_transform_kernel<1> : items_per_wave == 2 ? inverse_transform_kernel<2> : inverse_transform_kernel<4>);
     if (lds > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;

@@ -49,6 +49,7 @@ struct DevicePlan {
     int k1_cached_stores = -1; // tuning (FRI_HIP_K1_CACHED_STORES=0 / 1): force nontemporal / plain coefficient stores; -1: the caller of the launch decides
     int32_t k1_ablate = 0; // timing-only ablation flags, see FwdArgs::ablate
     int32_t k2_ablate = 0; // the same for K2, see PredArgs::ablate
+    bool rct = false; // fri_hip_plan_set_colour_transform(FRI_HIP_COLOUR_RCT), C = 3 only: K1 codes (G, B - G + 128, R - G + 128), K3 undoes it
     bool k3_multiply = false; // fri_hip_plan_set_dequantiser: the inverse kernel multiplies by the quantiser instead of reproducing the reference's division
     unsigned long long *trace = nullptr; // [n_wg][16] diagnostic timeline (FRI_HIP_TRACE=1), else null
     bool k1_measuring = false; // fri_hip_plan_tune_forward's measuring copies: their forward launches run the kernel's MEASURE instance (a name of its own in traces)

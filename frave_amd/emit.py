@@ -8,6 +8,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_HERE, "libfri_emit.so")
 _lib = None
+RCT = 0x100  # FRI_EMIT_RCT: `channels = 3 | RCT` - the planes are Y, Cb, Cr of the reversible colour transform (include/fri_emit.h)
 
 
 class EmitError(RuntimeError):
@@ -73,8 +74,9 @@ def channel_symbols(centers, coefs, bucket, prediction):
     return sym[: n.value].copy(), bk[: n.value].copy()
 
 
-def encode_image(width, height, centers, coefs, bucket, prediction, hist, value_params, width_params):
-    """.frv bytes. coefs/bucket/prediction [C][F][512], hist [C][10][1024], params [C][3][6]."""
+def encode_image(width, height, centers, coefs, bucket, prediction, hist, value_params, width_params, rct=False):
+    """.frv bytes. coefs/bucket/prediction [C][F][512], hist [C][10][1024], params [C][3][6]. rct: the three planes are Y, Cb, Cr of the reversible colour
+    transform (Plan.set_colour_transform): the file says YCbCr and carries the flag."""
     c = np.ascontiguousarray(centers, np.int32)
     co, b, p = np.ascontiguousarray(coefs, np.int32), np.ascontiguousarray(bucket, np.uint8), np.ascontiguousarray(prediction, np.int32)
     h = np.ascontiguousarray(hist, np.uint32)
@@ -87,10 +89,11 @@ def encode_image(width, height, centers, coefs, bucket, prediction, hist, value_
     # one call in the common case: a symbol costs at most max_freq_bits (< 32) bits, so 4 bytes per coefficient + the container
     # overhead always suffice; the library reports the needed size (-3) if they should not
     out = np.empty(co.size * 4 + channels * (10 * 2070 + 256) + 64, np.uint8)
-    rc = L.fri_emit_encode_image(width, height, channels, _p(c), len(c), _p(co), _p(b), _p(p), _p(h), _p(vp), _p(wp), _p(out), out.size, C.addressof(n), err, 256)
+    arg = channels | (RCT if rct else 0)
+    rc = L.fri_emit_encode_image(width, height, arg, _p(c), len(c), _p(co), _p(b), _p(p), _p(h), _p(vp), _p(wp), _p(out), out.size, C.addressof(n), err, 256)
     if rc == -3:
         out = np.empty(n.value, np.uint8)
-        rc = L.fri_emit_encode_image(width, height, channels, _p(c), len(c), _p(co), _p(b), _p(p), _p(h), _p(vp), _p(wp), _p(out), out.size, C.addressof(n), err, 256)
+        rc = L.fri_emit_encode_image(width, height, arg, _p(c), len(c), _p(co), _p(b), _p(p), _p(h), _p(vp), _p(wp), _p(out), out.size, C.addressof(n), err, 256)
     if rc != 0:
         raise EmitError(err.value.decode() or f"fri_emit_encode_image: {rc}")
     out = out[: n.value]
@@ -108,8 +111,8 @@ def stream_order(centers, valid_mask):
     return out[: n.value].copy()
 
 
-def encode_image_from_streams(width, height, streams, hist, value_params, width_params):
-    """.frv bytes from the device's symbol streams: streams uint16 [C][n_symbols] (bucket << 10 | symbol), hist [C][10][1024], params [C][3][6]."""
+def encode_image_from_streams(width, height, streams, hist, value_params, width_params, rct=False):
+    """.frv bytes from the device's symbol streams: streams uint16 [C][n_symbols] (bucket << 10 | symbol), hist [C][10][1024], params [C][3][6]. rct: see encode_image."""
     st = np.ascontiguousarray(streams, np.uint16)
     h = np.ascontiguousarray(hist, np.uint32)
     channels = h.size // 10240
@@ -119,20 +122,21 @@ def encode_image_from_streams(width, height, streams, hist, value_params, width_
     n = C.c_size_t(0)
     err = C.create_string_buffer(256)
     out = np.empty(st.size * 4 + channels * (10 * 2070 + 256) + 64, np.uint8)
-    rc = load_library().fri_emit_encode_image_from_streams(width, height, channels, _p(st), n_symbols, _p(h), _p(vp), _p(wp), _p(out), out.size, C.addressof(n), err, 256)
+    rc = load_library().fri_emit_encode_image_from_streams(width, height, channels | (RCT if rct else 0), _p(st), n_symbols, _p(h), _p(vp), _p(wp), _p(out), out.size, C.addressof(n), err, 256)
     if rc != 0:
         raise EmitError(err.value.decode() or f"fri_emit_encode_image_from_streams: {rc}")
     return out[: n.value].tobytes()
 
 
-def check_image(frv, centers, coefs, bucket, prediction):
-    """Entropy-layer self-check: parse, rebuild the models from the container, decode every symbol, compare. Raises on mismatch."""
+def check_image(frv, centers, coefs, bucket, prediction, rct=False):
+    """Entropy-layer self-check: parse, rebuild the models from the container, decode every symbol, compare. Raises on mismatch (the colour transform
+    flag included)."""
     c = np.ascontiguousarray(centers, np.int32)
     co, b, p = np.ascontiguousarray(coefs, np.int32), np.ascontiguousarray(bucket, np.uint8), np.ascontiguousarray(prediction, np.int32)
     data = np.frombuffer(frv, np.uint8)
     channels = co.size // (len(c) * 512)
     err = C.create_string_buffer(256)
-    rc = load_library().fri_emit_check_image(_p(data), data.size, channels, _p(c), len(c), _p(co), _p(b), _p(p), err, 256)
+    rc = load_library().fri_emit_check_image(_p(data), data.size, channels | (RCT if rct else 0), _p(c), len(c), _p(co), _p(b), _p(p), err, 256)
     if rc != 0:
         raise EmitError(err.value.decode() or f"fri_emit_check_image: {rc}")
 
@@ -145,9 +149,15 @@ def rans_selfcheck(n_symbols, seed=1):
         raise EmitError(err.value.decode() or f"fri_emit_rans_selfcheck: {rc}")
 
 
+class DecodedImage(tuple):
+    """(width, height, channels, centers, coefs), and .rct: True if the planes are Y, Cb, Cr of the reversible colour transform."""
+
+    rct = False
+
+
 def decode_image(frv):
     """A .frv back to coefficient planes (serialize::decode + entropy_coding::decode of the reference, host only).
-    Returns (width, height, channels, centers [F][2] int32, coefs [channels][F][512] int32 with None = INT32_MIN)."""
+    Returns (width, height, channels, centers [F][2] int32, coefs [channels][F][512] int32 with None = INT32_MIN); its .rct is the file's colour transform flag."""
     data = np.frombuffer(frv, np.uint8)
     info = np.zeros(4, np.uint32)
     err = C.create_string_buffer(256)
@@ -156,9 +166,13 @@ def decode_image(frv):
     if rc != -3:
         raise EmitError(err.value.decode() or f"fri_emit_decode_image: {rc}")
     w, h, c, f = (int(x) for x in info)
+    rct = bool(c & RCT)
+    c &= ~RCT
     coefs = np.empty((c, f, 512), np.int32)
     centers = np.empty((f, 2), np.int32)
     rc = L.fri_emit_decode_image(_p(data), data.size, _p(info), _p(coefs), coefs.size, _p(centers), err, 256)
     if rc != 0:
         raise EmitError(err.value.decode() or f"fri_emit_decode_image: {rc}")
-    return w, h, c, centers, coefs
+    out = DecodedImage((w, h, c, centers, coefs))
+    out.rct = rct
+    return out

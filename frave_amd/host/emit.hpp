@@ -136,10 +136,14 @@ struct ChannelParams {
     float width[3][6];
 };
 enum ColorSpaceCode : uint32_t { kLuma = 1, kRGB = 2, kYCbCr = 3 }; // images.rs:23-29
+// Bit 0 of the metadata word (which the reference's serialize::decode does not read, serialize.rs:132-136): the planes are Y, Cb, Cr of the reversible colour
+// transform (fri_hip_plan_set_colour_transform) - always with cs = kYCbCr. A reader that ignores the bit gets the planes, labelled YCbCr, which is what they are.
+constexpr uint32_t kMdatRct = 1u;
 std::vector<uint8_t> serialize(uint32_t height, uint32_t width, ColorSpaceCode cs, const std::vector<ChannelStream> &channels,
-                               const std::vector<ChannelParams> &params);
+                               const std::vector<ChannelParams> &params, bool rct = false);
 struct ParsedImage {
     uint32_t height = 0, width = 0, colorspace = 0, variant = 0;
+    bool rct = false; // kYCbCr with kMdatRct set
     std::vector<ChannelStream> channels; // contexts rebuilt from (max_freq_bits, off_distribution_values) like serialize.rs:214-237
     std::vector<ChannelParams> params;
 };
@@ -154,6 +158,7 @@ std::string deserialize(const std::vector<uint8_t> &bytes, ParsedImage &out);
 std::string decode_channel(const fri::Geometry &g, const SymbolOrder &order, const ChannelStream &s, const ChannelParams &p, int32_t *coefs);
 struct DecodedImage {
     uint32_t height = 0, width = 0, colorspace = 0, channels = 0, n_cells = 0;
+    bool rct = false; // the planes are Y, Cb, Cr of the reversible colour transform (ParsedImage::rct)
     std::vector<int32_t> centers;     // [n_cells][2], canonical order (the one fri_hip_plan_centers reports)
     std::vector<int32_t> coefs;       // [channels][n_cells][512]: what fri_hip_inverse_transform takes
     std::vector<ChannelParams> params;

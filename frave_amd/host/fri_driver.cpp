@@ -4,10 +4,12 @@
 //   fri_driver batch <width> <height> <channels> <n> [--gpus N] [--chain]   n images sharded by image over N GPUs: the forward stage, or (--chain) the whole encoder
 //   fri_driver encode <width> <height> <channels> <out.frv>  the whole encode pipeline on a synthetic image: device stages, then
 //                                                            symbol order / ANS models / rANS / frif container on the host; self-checks the stream
-//   fri_driver encode-file <in.pgm|in.ppm|in.bmp> <out.frv>  the same pipeline on a binary PGM (P5, one plane), PPM (P6, RGB) or uncompressed
-//                                                            24-bit BMP file, 8 bits per sample (fri-cli encode, crates/fri-cli/src/commands/encode.rs:8-54)
+//   fri_driver encode-file <in.pgm|in.ppm|in.bmp> <out.frv> [--rct]  the same pipeline on a binary PGM (P5, one plane), PPM (P6, RGB) or uncompressed
+//                                                            24-bit BMP file, 8 bits per sample (fri-cli encode, crates/fri-cli/src/commands/encode.rs:8-54);
+//                                                            --rct: an RGB image is coded as Y, Cb, Cr of the reversible colour transform (flagged file)
 //   fri_driver decode-file <in.frv> <out.pgm|.ppm|.bmp>     container -> rANS / context decoding on the host -> dequantisation + inverse
-//                                                            transform on the device (fri-cli decode, crates/fri-cli/src/commands/decode.rs)
+//                                                            transform on the device (fri-cli decode, crates/fri-cli/src/commands/decode.rs); a flagged file
+//                                                            comes back as RGB
 //   fri_driver batch <width> <height> <channels> <n_images> [--gpus N]
 //                                                            BASELINE config 3: host batch with H2D / kernel / D2H overlap; with --gpus N
 //                                                            BASELINE config 4: the batch sharded over N GPUs of this node (image i -> GPU i mod N,
@@ -215,6 +217,7 @@ int main(int argc, char **argv) {
             return 1;
         }
         libfri::EncoderOpts file_opts; // parameters are fitted on the device sums (fit_parameters defaults to true)
+        for (int i = 4; i < argc; i++) file_opts.colour_transform = file_opts.colour_transform || std::string(argv[i]) == "--rct";
         return encode_image_to_file(std::move(img), fw, fh, fc, file_opts, argv[3]);
     }
     if (argc >= 4 && std::string(argv[1]) == "decode-file") {
@@ -253,7 +256,7 @@ int main(int argc, char **argv) {
         return 0;
     }
     if (argc < 5) {
-        std::fprintf(stderr, "usage: %s roundtrip|encode|batch|batch-frv <width> <height> <channels> [n_images | out.frv]\n       %s encode-file <in.pgm|in.ppm|in.bmp> <out.frv>\n       %s decode-file <in.frv> <out.pgm|out.ppm|out.bmp>\n", argv[0], argv[0], argv[0]);
+        std::fprintf(stderr, "usage: %s roundtrip|encode|batch|batch-frv <width> <height> <channels> [n_images | out.frv]\n       %s encode-file <in.pgm|in.ppm|in.bmp> <out.frv> [--rct]\n       %s decode-file <in.frv> <out.pgm|out.ppm|out.bmp>\n", argv[0], argv[0], argv[0]);
         return 2;
     }
     const std::string cmd = argv[1];

@@ -49,6 +49,20 @@ fri_hip_plan *Device::plan(uint32_t width, uint32_t height, uint32_t channels, s
     return p;
 }
 
+namespace {
+// The colour transform is plan state and a Device's plans are shared by shape: every caller sets the mode its launches need.
+std::string set_colour_transform(fri_hip_plan *plan, bool rct, Device &dev) {
+    const int rc = fri_hip_plan_set_colour_transform(plan, rct ? FRI_HIP_COLOUR_RCT : FRI_HIP_COLOUR_NONE);
+    return rc == FRI_HIP_OK ? std::string() : dev.describe(rc);
+}
+// what an encode of `colorspace` pixels codes: RGB with the option on goes out as Y, Cb, Cr (colour space YCbCr, flagged)
+ImageMetadata coded_metadata(uint32_t height, uint32_t width, ColorSpace colorspace, const EncoderOpts &opts) {
+    const bool rct = opts.colour_transform && colorspace == ColorSpace::RGB;
+    return ImageMetadata{height, width, rct ? ColorSpace::YCbCr : colorspace, rct};
+}
+emit::ColorSpaceCode colour_code(ColorSpace c) { return c == ColorSpace::Luma ? emit::kLuma : c == ColorSpace::RGB ? emit::kRGB : emit::kYCbCr; }
+} // namespace
+
 std::array<double, 6> ContextModeler::solve_normal_equations(const double (&m)[6][6], const double (&y)[6]) {
     std::array<double, 6> x{};
     fri_hip_solve6(m, y, x.data());
@@ -96,7 +110,8 @@ Result<WaveletImage> encode(const RasterImage &raster, const EncoderOpts &opts, 
     fri_hip_plan *plan = dev.plan(raster.metadata.width, raster.metadata.height, c, r.error);
     if (!plan) return r;
     WaveletImage &w = r.value;
-    w.metadata = raster.metadata;
+    w.metadata = coded_metadata(raster.metadata.height, raster.metadata.width, raster.metadata.colorspace, opts);
+    if (!(r.error = set_colour_transform(plan, w.metadata.rct, dev)).empty()) return r;
     w.num_cells = fri_hip_plan_num_cells(plan);
     w.centers.resize((size_t)w.num_cells * 2);
     w.coefficients.resize(fri_hip_plan_coef_count(plan));
@@ -120,7 +135,9 @@ Result<RasterImage> decode(const WaveletImage &image, const EncoderOpts &opts, D
         r.error = "coefficient array does not match the image geometry";
         return r;
     }
+    if (!(r.error = set_colour_transform(plan, image.metadata.rct, dev)).empty()) return r;
     r.value.metadata = image.metadata;
+    if (image.metadata.rct) r.value.metadata.colorspace = ColorSpace::RGB, r.value.metadata.rct = false; // the kernel writes R, G, B
     r.value.data.resize(fri_hip_plan_pixel_bytes(plan));
     int rc = fri_hip_inverse_transform(plan, image.coefficients.data(), opts.quantization_matrix.data(), r.value.data.data());
     if (rc != FRI_HIP_OK) {
@@ -212,7 +229,8 @@ Result<EncodedStages> FRIEncoder::encode(std::vector<uint8_t> data, uint32_t hei
     // RawImage -> ChannelTransform (identity, channel_transform.rs:4-10) -> WaveletTransform -> Quantization -> Prediction (encoder.rs:19-38) as
     // ONE device-resident call: the pixels go up once, the coefficients stay in device memory between the stages, every output comes down once.
     WaveletImage &w = r.value.image;
-    w.metadata = ImageMetadata{height, width, colorspace};
+    w.metadata = coded_metadata(height, width, colorspace, opts_);
+    if (const std::string e = set_colour_transform(plan, w.metadata.rct, dev); !e.empty()) return fail(e);
     w.num_cells = fri_hip_plan_num_cells(plan);
     w.centers.resize((size_t)w.num_cells * 2);
     w.coefficients.resize(fri_hip_plan_coef_count(plan));
@@ -271,8 +289,7 @@ Result<CompressedImage> stages::entropy_coding::encode(const WaveletImage &image
 }
 
 std::vector<uint8_t> stages::serialize::encode(const CompressedImage &image) {
-    const emit::ColorSpaceCode cs = image.metadata.colorspace == ColorSpace::Luma ? emit::kLuma : image.metadata.colorspace == ColorSpace::RGB ? emit::kRGB : emit::kYCbCr;
-    return emit::serialize(image.metadata.height, image.metadata.width, cs, image.channel_data, image.params);
+    return emit::serialize(image.metadata.height, image.metadata.width, colour_code(image.metadata.colorspace), image.channel_data, image.params, image.metadata.rct);
 }
 
 Result<CompressedImage> stages::serialize::decode(const std::vector<uint8_t> &bytes) {
@@ -283,6 +300,7 @@ Result<CompressedImage> stages::serialize::decode(const std::vector<uint8_t> &by
     r.value.metadata.height = p.height;
     r.value.metadata.width = p.width;
     r.value.metadata.colorspace = p.colorspace == emit::kLuma ? ColorSpace::Luma : p.colorspace == emit::kRGB ? ColorSpace::RGB : ColorSpace::YCbCr;
+    r.value.metadata.rct = p.rct;
     r.value.variant = p.variant;
     r.value.channel_data = std::move(p.channels);
     r.value.params = std::move(p.params);
@@ -343,7 +361,7 @@ std::string set_plan_stream_order(fri_hip_plan *plan, Device &dev) {
     rc = fri_hip_plan_set_stream_order(plan, order.data(), order.size());
     return rc == FRI_HIP_OK ? std::string() : dev.describe(rc);
 }
-std::string emit_streamed(const StreamedImage &im, uint32_t c, uint64_t n, uint32_t height, uint32_t width, ColorSpace colorspace, std::vector<uint8_t> &out) {
+std::string emit_streamed(const StreamedImage &im, uint32_t c, uint64_t n, const ImageMetadata &md, std::vector<uint8_t> &out) {
     std::vector<emit::ChannelStream> streams;
     const std::string e = emit::encode_channels_from_streams(c, im.symbols.data(), (size_t)n, im.hist.data(), streams);
     if (!e.empty()) return e;
@@ -351,8 +369,7 @@ std::string emit_streamed(const StreamedImage &im, uint32_t c, uint64_t n, uint3
     for (uint32_t ch = 0; ch < c; ch++)
         for (int g = 0; g < 3; g++)
             for (int k = 0; k < 6; k++) params[ch].value[g][k] = im.vp[ch][g][k], params[ch].width[g][k] = im.wp[ch][g][k];
-    const emit::ColorSpaceCode cs = colorspace == ColorSpace::Luma ? emit::kLuma : colorspace == ColorSpace::RGB ? emit::kRGB : emit::kYCbCr;
-    out = emit::serialize(height, width, cs, streams, params);
+    out = emit::serialize(md.height, md.width, colour_code(md.colorspace), streams, params, md.rct);
     return std::string();
 }
 } // namespace
@@ -383,6 +400,8 @@ Result<std::vector<uint8_t>> FRIEncoder::encode_bytes_streamed(std::vector<uint8
     std::string err;
     fri_hip_plan *plan = dev.plan(width, height, c, err);
     if (!plan) return fail(err);
+    const ImageMetadata md = coded_metadata(height, width, colorspace, opts_);
+    if (const std::string e = set_colour_transform(plan, md.rct, dev); !e.empty()) return fail(e);
     const uint64_t n = fri_hip_plan_num_some(plan);
     if (const std::string e = set_plan_stream_order(plan, dev); !e.empty()) return fail(e); // geometry only, once per plan (the plan is new here: Device lives for this call, as in encode())
     std::vector<uint16_t> symbols((size_t)c * n);
@@ -402,8 +421,7 @@ Result<std::vector<uint8_t>> FRIEncoder::encode_bytes_streamed(std::vector<uint8
     for (uint32_t ch = 0; ch < c; ch++)
         for (int g = 0; g < 3; g++)
             for (int k = 0; k < 6; k++) params[ch].value[g][k] = vp[ch][g][k], params[ch].width[g][k] = wp[ch][g][k];
-    const emit::ColorSpaceCode cs = colorspace == ColorSpace::Luma ? emit::kLuma : colorspace == ColorSpace::RGB ? emit::kRGB : emit::kYCbCr;
-    r.value = emit::serialize(height, width, cs, streams, params);
+    r.value = emit::serialize(height, width, colour_code(md.colorspace), streams, params, md.rct);
     r.ok = true;
     return r;
 }
@@ -424,6 +442,7 @@ Result<std::vector<std::vector<uint8_t>>> encode_batch_bytes(const std::vector<c
     Result<std::vector<std::vector<uint8_t>>> r;
     const size_t n_images = images.size();
     const uint32_t c = num_channels(colorspace);
+    const ImageMetadata md = coded_metadata(height, width, colorspace, opts);
     const uint32_t n_dev = (uint32_t)devices.size();
     if (!n_dev || !emit_threads) {
         r.error = "encode_batch_bytes: no device / no emitter thread";
@@ -469,6 +488,7 @@ Result<std::vector<std::vector<uint8_t>>> encode_batch_bytes(const std::vector<c
             std::string err;
             fri_hip_plan *plan = dev.ok() ? dev.stream_plan(width, height, c, err) : nullptr;
             if (!plan && err.empty()) err = dev.error();
+            if (plan) err = set_colour_transform(plan, md.rct, dev);
             if (!err.empty()) fail(err);
             const uint64_t n = plan ? fri_hip_plan_num_some(plan) : 0;
             if (n) n_some.store(n, std::memory_order_relaxed);
@@ -517,7 +537,7 @@ Result<std::vector<std::vector<uint8_t>>> encode_batch_bytes(const std::vector<c
                 const auto t0 = std::chrono::steady_clock::now();
                 uint64_t n = n_some.load(std::memory_order_relaxed); // (set before the first image was queued: the queue's mutex orders it)
                 if (!n) n = im.symbols.size() / c;
-                const std::string e = emit_streamed(im, c, n, height, width, colorspace, r.value[im.index]);
+                const std::string e = emit_streamed(im, c, n, md, r.value[im.index]);
                 emit_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
                 if (!e.empty()) {
                     fail(e);

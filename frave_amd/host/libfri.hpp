@@ -33,6 +33,7 @@ inline uint32_t num_channels(ColorSpace c) { return c == ColorSpace::Luma ? 1u :
 struct ImageMetadata { // images.rs:68-79
     uint32_t height = 0, width = 0;
     ColorSpace colorspace = ColorSpace::RGB;
+    bool rct = false; // the planes are Y, Cb, Cr of the reversible colour transform of RGB pixels (colorspace is then YCbCr; the file's metadata bit 0)
 };
 struct RasterImage { // images.rs:82-85
     ImageMetadata metadata;
@@ -55,6 +56,7 @@ struct EncoderOpts { // encoder.rs:58-64
     std::array<int32_t, 32> quantization_matrix;               // get_quantization_matrix(), quantization.rs:3-5
     bool fit_parameters = true; // like the reference (prediction.rs:232-235); false = use the parameters given above
     int device = 0;
+    bool colour_transform = false; // RGB input: code Y, Cb, Cr of the reversible colour transform (fri_hip_plan_set_colour_transform) and flag the file
     EncoderOpts() { quantization_matrix.fill(1); }
 };
 

@@ -14,7 +14,13 @@
  * Conventions: plain pointers and sizes, caller-owned buffers; every function returns 0 or a negative code
  * (-1 invalid argument, -2 the condition under which libfri would panic or report an error: message in `err`,
  *  -3 output buffer too small: the needed size is reported, -4 self-check mismatch). Cells are in the canonical order of
- * fri_hip_plan_centers; planes are [channels][n_cells][512] in heap order with None = INT32_MIN. */
+ * fri_hip_plan_centers; planes are [channels][n_cells][512] in heap order with None = INT32_MIN.
+ *
+ * Colour transform: `channels` of fri_emit_encode_image, fri_emit_encode_image_from_streams and fri_emit_check_image is 1, 3 or 3 | FRI_EMIT_RCT - the three
+ * planes are Y, Cb, Cr of the reversible colour transform (fri_hip_plan_set_colour_transform, include/fri_hip.h). Such a file has the colour space YCbCr and
+ * bit 0 of its metadata word set, and is otherwise byte for byte the file of the same planes without the flag; fri_emit_decode_image reports the flag the same
+ * way, in info[2]. Any other high bit in `channels` is an invalid argument. */
+#define FRI_EMIT_RCT 0x100u
 #ifndef FRI_EMIT_H
 #define FRI_EMIT_H
 

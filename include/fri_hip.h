@@ -349,6 +349,19 @@ int fri_hip_inverse_transform(fri_hip_plan *plan, const int32_t *coefs, const in
 #define FRI_HIP_DEQUANT_REFERENCE 0
 #define FRI_HIP_DEQUANT_MULTIPLY 1
 int fri_hip_plan_set_dequantiser(fri_hip_plan *plan, int mode);
+/* Which colour transform the plan's forward and inverse entry points apply (the container's YCbCr colour space). FRI_HIP_COLOUR_NONE (default): the channels
+ * are coded as they are. FRI_HIP_COLOUR_RCT (plans with C = 3 only): the reversible colour transform of JPEG-LS on interleaved R, G, B bytes, all arithmetic
+ * mod 256 - lossless and 8 bit:
+ *     forward:  Y = G    Cb = (B - G + 128) & 255    Cr = (R - G + 128) & 255    coded as channels (0, 1, 2) = (Y, Cb, Cr)
+ *     inverse:  G = Y    B  = (Cb + Y - 128) & 255   R  = (Cr + Y - 128) & 255
+ * Every forward entry point (transform_quant*, encode_image*, encode_symbols_batch_dev, encode_image_symbols, multi_* through the device plans it is set on,
+ * time_transform_quant*) reads pixels as R, G, B and codes Y, Cb, Cr; every inverse entry point writes R, G, B from them. The forward kernel forms Y, Cb, Cr out
+ * of the staged pixels; the inverse kernel undoes it after the clamp, in the tile's pixel rectangle. Pixels no retained cell covers stay 0 in all three
+ * channels. The tilings (and fri_hip_plan_tune_forward's cache) do not depend on the mode. A launch captured into a graph keeps the mode that was set when it
+ * was captured. Returns FRI_HIP_ERR_INVALID_ARGUMENT for an unknown mode or RCT on a plan with C != 3; works on host-only plans. */
+#define FRI_HIP_COLOUR_NONE 0
+#define FRI_HIP_COLOUR_RCT 1
+int fri_hip_plan_set_colour_transform(fri_hip_plan *plan, int mode);
 int fri_hip_inverse_transform_dev(fri_hip_plan *plan, const int32_t *d_coefs, const int32_t qmatrix[32], uint8_t *d_pixels,
                                   void *stream);
 /* n independent images in one launch: image k at d_coefs + k * coef_stride (int32 elements), d_pixels + k * pixel_stride (bytes). */
