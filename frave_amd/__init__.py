@@ -11,10 +11,15 @@ from .api import (  # noqa: F401
     FriHipError,
     Multi,
     Plan,
+    DEQUANT_MIDPOINT,
+    DEQUANT_MULTIPLY,
+    DEQUANT_REFERENCE,
     build_library,
+    distortion_psnr,
     fit_value_params,
     fit_width_params,
     library_path,
     load_library,
+    quality_matrix,
     shard_images,
 )

@@ -29,9 +29,11 @@ SYMBOLS = [
     "fri_hip_plan_assume_forward_coefficients", "fri_hip_encode_image_batch", "fri_hip_multi_encode_image",
     "fri_hip_plan_set_stream_order", "fri_hip_symbol_stream_batch_dev", "fri_hip_encode_image_symbols", "fri_hip_encode_symbols_batch_dev",
     "fri_hip_plan_set_dequantiser", "fri_hip_plan_tune_forward", "fri_hip_time_transform_quant_streams_dev",
-    "fri_hip_plan_set_colour_transform",
+    "fri_hip_plan_set_colour_transform", "fri_hip_quality_matrix", "fri_hip_measure_distortion_dev", "fri_hip_search_quality",
+    "fri_hip_search_quality_dev",
 ]
 COLOUR_NONE, COLOUR_RCT = 0, 1  # fri_hip_plan_set_colour_transform
+DEQUANT_REFERENCE, DEQUANT_MULTIPLY, DEQUANT_MIDPOINT = 0, 1, 2  # fri_hip_plan_set_dequantiser
 
 
 class FriHipError(RuntimeError):
@@ -148,6 +150,10 @@ def load_library():
     L.fri_hip_plan_assume_forward_coefficients.argtypes = [vp, i32]
     L.fri_hip_plan_set_dequantiser.argtypes = [vp, i32]
     L.fri_hip_plan_set_colour_transform.argtypes = [vp, i32]
+    L.fri_hip_quality_matrix.argtypes = [i32, vp]
+    L.fri_hip_measure_distortion_dev.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.fri_hip_search_quality.argtypes = [vp, vp, C.c_double, vp, vp]
+    L.fri_hip_search_quality_dev.argtypes = [vp, vp, C.c_double, vp, vp, vp]
     L.fri_hip_plan_set_stream_order.argtypes = [vp, vp, C.c_uint64]
     L.fri_hip_symbol_stream_batch_dev.argtypes = [vp, u32, vp, sz, vp, vp, sz, vp, sz, vp]
     L.fri_hip_encode_image_symbols.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp]
@@ -204,6 +210,23 @@ def shard_images(n_images, shard, n_shards):
     """Global indices of the images of `shard` (fri_hip_shard_size / fri_hip_shard_image: image i -> shard i mod n_shards)."""
     L = load_library()
     return [L.fri_hip_shard_image(k, shard, n_shards) for k in range(L.fri_hip_shard_size(n_images, shard, n_shards))]
+
+
+def quality_matrix(quality):
+    """fri_hip_quality_matrix: the int32 [32] quantisation matrix of quality 1..100 (100 = all ones, lossless). Needs no GPU."""
+    out = np.empty(32, np.int32)
+    _check(load_library().fri_hip_quality_matrix(int(quality), _p(out)), "fri_hip_quality_matrix")
+    return out
+
+
+def distortion_psnr(measure, channels):
+    """PSNR in dB of a fri_hip_measure_distortion_dev result (uint64 [2 C + 1]): 10 log10(255^2 N / SSE) pooled over the channels,
+    N = owned pixels x C; +inf when SSE = 0."""
+    m = [int(x) for x in np.asarray(measure).ravel()[: 2 * channels + 1]]
+    sse = sum(m[2 * c] for c in range(channels))
+    if sse == 0:
+        return float("inf")
+    return 10.0 * np.log10(255.0 * 255.0 * m[2 * channels] * channels / sse)
 
 
 def fit_value_params(gram_tri):
@@ -370,8 +393,29 @@ class Plan:
                                                                word_stride, d_symbols, symbol_stride, d_hist, d_oob, d_fit_range, stream), "fri_hip_encode_symbols_batch_dev", self.ctx)
 
     def set_dequantiser(self, multiply):
-        """fri_hip_plan_set_dequantiser: False = the reference's dividing quantization::decode (default), True = coefficient x qmatrix[layer]."""
-        _check(load_library().fri_hip_plan_set_dequantiser(self._h, 1 if multiply else 0), "fri_hip_plan_set_dequantiser")
+        """fri_hip_plan_set_dequantiser: False = the reference's dividing quantization::decode (default), True = coefficient x qmatrix[layer];
+        or one of DEQUANT_REFERENCE, DEQUANT_MULTIPLY, DEQUANT_MIDPOINT (the middle of the truncating quantiser's interval)."""
+        mode = (1 if multiply else 0) if isinstance(multiply, bool) else int(multiply)
+        _check(load_library().fri_hip_plan_set_dequantiser(self._h, mode), "fri_hip_plan_set_dequantiser")
+
+    def measure_distortion_dev(self, d_coefs, d_reference_pixels, d_out, qmatrix=None, stream=0):
+        """fri_hip_measure_distortion_dev: K3 with the plan's dequantiser and colour transform compared with d_reference_pixels instead of written;
+        d_out (uint64 [2 C + 1], device) = per channel c the sum of squared errors at 2 c and the largest absolute error at 2 c + 1, the owned pixels at 2 C."""
+        q = _q(qmatrix)
+        _check(load_library().fri_hip_measure_distortion_dev(self._h, d_coefs, _p(q), d_reference_pixels, d_out, stream), "fri_hip_measure_distortion_dev", self.ctx)
+
+    def search_quality(self, pixels, target_db, stream=0):
+        """fri_hip_search_quality (pixels: a host array) or fri_hip_search_quality_dev (pixels: a device pointer, an int): the lowest quality whose
+        midpoint-dequantised round trip reaches target_db, by the bisection the header describes. Returns (quality, psnr_db)."""
+        qual, db = C.c_int32(0), C.c_double(0.0)
+        L = load_library()
+        if isinstance(pixels, int):
+            _check(L.fri_hip_search_quality_dev(self._h, pixels, float(target_db), C.byref(qual), C.byref(db), stream), "fri_hip_search_quality_dev", self.ctx)
+        else:
+            px = np.ascontiguousarray(pixels, np.uint8)
+            assert px.size == self.pixel_bytes
+            _check(L.fri_hip_search_quality(self._h, _p(px), float(target_db), C.byref(qual), C.byref(db)), "fri_hip_search_quality", self.ctx)
+        return qual.value, db.value
 
     def set_colour_transform(self, mode):
         """fri_hip_plan_set_colour_transform: COLOUR_NONE (default) or COLOUR_RCT (C = 3 plans): every forward entry point then codes the planes

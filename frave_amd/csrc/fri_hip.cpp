@@ -78,6 +78,8 @@ struct Staging {
     Grown<uint32_t> hist;            // [channels][10][1024]
     Grown<unsigned long long> oob;   // [channels]
     Grown<uint16_t> symbols;         // fri_hip_encode_image_symbols: [C][geo.n_some]
+    Grown<int32_t> search_coefs;     // fri_hip_search_quality*: the probes' coefficient planes [C][F][512]
+    Grown<unsigned long long> measure; // fri_hip_search_quality*: a probe's distortion sums [2 C + 1]
 };
 
 constexpr int kBatchSlots = 3;
@@ -679,13 +681,22 @@ int wait_event_polling(fri_hip_ctx *c, hipEvent_t ev) {
 // second replay on the clearing workgroups' flags already hold it - nothing would order the clearing of the histogram before the other workgroups' adds any more
 // (counts wiped or doubled). So every entry point that reaches the scan refuses a capturing stream, loudly, before it queues or allocates anything,
 // instead of recording something that must not be replayed.
-int refuse_capture(fri_hip_plan *p, hipStream_t stream) {
+int refuse_capture(fri_hip_plan *p, hipStream_t stream,
+                   const char *why = "the predict + histogram kernel cannot be captured into a HIP graph (its hand-over counts launches on the host): launch it on a stream") {
     hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
     if (stream && hipStreamIsCapturing(stream, &capturing) == hipSuccess && capturing != hipStreamCaptureStatusNone) {
-        if (p->ctx) p->ctx->last_error = "the predict + histogram kernel cannot be captured into a HIP graph (its hand-over counts launches on the host): launch it on a stream";
+        if (p->ctx) p->ctx->last_error = why;
         return FRI_HIP_ERR_INVALID_ARGUMENT;
     }
     return FRI_HIP_OK;
+}
+
+// PSNR of a measurement (fri_hip_measure_distortion_dev's d_out): 10 log10(255^2 N / SSE) pooled over the channels, N = owned pixels x C; +inf for SSE = 0.
+double distortion_psnr(const unsigned long long *m, uint32_t channels) {
+    unsigned long long sse = 0;
+    for (uint32_t c = 0; c < channels; c++) sse += m[2 * c];
+    if (sse == 0) return HUGE_VAL;
+    return 10.0 * std::log10(255.0 * 255.0 * (double)m[2 * channels] * (double)channels / (double)sse);
 }
 
 } // namespace
@@ -850,8 +861,19 @@ int fri_hip_plan_assume_forward_coefficients(fri_hip_plan *p, int on) {
 }
 
 int fri_hip_plan_set_dequantiser(fri_hip_plan *p, int mode) {
-    if (!p || (mode != FRI_HIP_DEQUANT_REFERENCE && mode != FRI_HIP_DEQUANT_MULTIPLY)) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    if (!p || (mode != FRI_HIP_DEQUANT_REFERENCE && mode != FRI_HIP_DEQUANT_MULTIPLY && mode != FRI_HIP_DEQUANT_MIDPOINT)) return FRI_HIP_ERR_INVALID_ARGUMENT;
     p->dev.k3_multiply = p->dev_inv.k3_multiply = mode == FRI_HIP_DEQUANT_MULTIPLY;
+    p->dev.k3_midpoint = p->dev_inv.k3_midpoint = mode == FRI_HIP_DEQUANT_MIDPOINT;
+    return FRI_HIP_OK;
+}
+
+int fri_hip_quality_matrix(int quality, int32_t qmatrix[32]) {
+    // per-layer weights, layers 0..9 (layer 9 is heap node 511 alone: it follows layer 8). Part of the file format: a lossy file names only its quality.
+    // The division rounds up, so every quality below 100 quantises layers 3..9 (rounding down made 94..99 all ones, i.e. lossless); layers 0..2 (4 of a
+    // cell's 512 coefficients) are never quantised. DESIGN.md has the rate and PSNR this gives.
+    static constexpr int kWeight[10] = {0, 0, 0, 1, 2, 4, 6, 10, 16, 16};
+    if (!qmatrix || quality < 1 || quality > 100) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    for (int l = 0; l < 32; l++) qmatrix[l] = l < 10 ? 1 + ((100 - quality) * kWeight[l] + 99) / 100 : 1;
     return FRI_HIP_OK;
 }
 
@@ -1680,6 +1702,64 @@ int fri_hip_inverse_transform(fri_hip_plan *p, const int32_t *coefs, const int32
     if ((rc = fri_hip_inverse_transform_dev(p, st.coefs, qmatrix, st.pixels, nullptr))) return rc;
     HIP_TRY(p->ctx, hipMemcpy(pixels, st.pixels, fri_hip_plan_pixel_bytes(p), hipMemcpyDeviceToHost));
     return FRI_HIP_OK;
+}
+
+int fri_hip_measure_distortion_dev(fri_hip_plan *p, const int32_t *d_coefs, const int32_t qmatrix[32], const uint8_t *d_reference_pixels, uint64_t *d_out, void *stream) {
+    if (int rc = need_device(p)) return rc;
+    if (!d_coefs || !d_reference_pixels || !d_out) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    QMatrix q;
+    if (int rc = check_q(qmatrix, q)) return rc;
+    auto *out = reinterpret_cast<unsigned long long *>(d_out);
+    HIP_TRY(p->ctx, hipMemsetAsync(out, 0, (2 * (size_t)p->geo.channels + 1) * sizeof(uint64_t), (hipStream_t)stream));
+    HIP_TRY(p->ctx, launch_inverse_transform(p->dev_inv, 1, d_coefs, 0, q, const_cast<uint8_t *>(d_reference_pixels), 0, (hipStream_t)stream, out));
+    return FRI_HIP_OK;
+}
+
+int fri_hip_search_quality_dev(fri_hip_plan *p, const uint8_t *d_pixels, double target_db, int32_t *quality, double *psnr_db, void *stream) {
+    if (!p || !d_pixels || !quality || !psnr_db || !(target_db > 0) || p->dev.rct) return FRI_HIP_ERR_INVALID_ARGUMENT; // (!(x > 0): NaN too)
+    if (int rc = need_device(p)) return rc;
+    const hipStream_t s = (hipStream_t)stream;
+    if (int rc = refuse_capture(p, s, "fri_hip_search_quality_dev reads every probe back: it cannot be captured into a HIP graph")) return rc;
+    fri_hip_ctx *c = p->ctx;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const uint32_t C = p->geo.channels;
+    auto &st = p->staging;
+    int rc;
+    if ((rc = grow(c, st.search_coefs, fri_hip_plan_coef_count(p))) || (rc = grow(c, st.measure, 2 * (size_t)C + 1))) return rc;
+    // the probes' K3: the plan's inverse tiling with the midpoint dequantiser, whatever the caller has set on the plan
+    DevicePlan inv = p->dev_inv;
+    inv.k3_multiply = false;
+    inv.k3_midpoint = true;
+    int lo = 0, hi = 100; // lo: a failure (0 is never probed), hi: a success (100 = lossless is never probed)
+    double hi_db = HUGE_VAL;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) / 2;
+        int32_t qm[32];
+        QMatrix q;
+        fri_hip_quality_matrix(mid, qm);
+        check_q(qm, q);
+        HIP_TRY(c, launch_fwd_transform_quant(p->dev, 1, d_pixels, 0, st.search_coefs, 0, q, s));
+        HIP_TRY(c, hipMemsetAsync(st.measure, 0, (2 * (size_t)C + 1) * sizeof(uint64_t), s));
+        HIP_TRY(c, launch_inverse_transform(inv, 1, st.search_coefs, 0, q, const_cast<uint8_t *>(d_pixels), 0, s, st.measure));
+        unsigned long long m[7];
+        HIP_TRY(c, hipMemcpyAsync(m, st.measure, (2 * (size_t)C + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        const double db = distortion_psnr(m, C);
+        if (db >= target_db) hi = mid, hi_db = db;
+        else lo = mid;
+    }
+    *quality = hi;
+    *psnr_db = hi_db;
+    return FRI_HIP_OK;
+}
+
+int fri_hip_search_quality(fri_hip_plan *p, const uint8_t *pixels, double target_db, int32_t *quality, double *psnr_db) {
+    if (!p || !pixels || !quality || !psnr_db || !(target_db > 0) || p->dev.rct) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    if (int rc = need_device(p)) return rc;
+    HIP_TRY(p->ctx, hipSetDevice(p->ctx->device));
+    if (int rc = grow(p->ctx, p->staging.pixels, fri_hip_plan_pixel_bytes(p))) return rc;
+    HIP_TRY(p->ctx, hipMemcpy(p->staging.pixels, pixels, fri_hip_plan_pixel_bytes(p), hipMemcpyHostToDevice));
+    return fri_hip_search_quality_dev(p, p->staging.pixels, target_db, quality, psnr_db, nullptr);
 }
 
 /* ---- timing helper ------------------------------------------------------------------------------ */

@@ -1,5 +1,7 @@
 // k3_inverse.hip -- K3 inverse_transform: dequantisation + inverse residue transform + clamp
 // (stages/quantization.rs:27-45; stages/wavelet_transform.rs:358-381; images.rs:103-111).
+#include <algorithm>
+
 #include "device_common.hpp"
 
 namespace fri {
@@ -46,11 +48,21 @@ struct InvArgs {
     const uint32_t *parts;
     int32_t rect_bytes; // LDS bytes of the largest tile rectangle (1 byte per byte)
     QMatrix q;
+    unsigned long long *measure; // MEASURE instances only (fri_hip_measure_distortion_dev): [2 C + 1] sums, `pixels` is then the reference image and is only read
 };
 
+// MID (fri_hip_plan_set_dequantiser(plan, FRI_HIP_DEQUANT_MIDPOINT)): K1 truncates c / q toward zero, so v = trunc(c / q) says c lay in
+// [v q, v q + q - 1] (v > 0), [v q - q + 1, v q] (v < 0) or (-q, q) (v = 0): the middle of that interval, v q +- (q - 1) / 2, and 0 for v = 0.
+// Wrapping 32-bit arithmetic like the multiply mode.
+template <bool MID = false>
 __device__ __forceinline__ int dequant_ref(int v, int heap_index, const InvArgs &a) {
     // quantization::decode divides like encode (quantization.rs:37); reproduced bit for bit.
     if (a.q_identity || v == kNone) return v;
+    if constexpr (MID) {
+        const int q = a.q.q[quant_layer(heap_index)];
+        const unsigned m = (unsigned)v * (unsigned)q, h = (unsigned)(q - 1) >> 1;
+        return v > 0 ? (int)(m + h) : v < 0 ? (int)(m - h) : 0;
+    }
     if (a.q_multiply) return (int)((unsigned)v * (unsigned)a.q.q[quant_layer(heap_index)]); // fri_hip_plan_set_dequantiser(plan, FRI_HIP_DEQUANT_MULTIPLY)
     return v / a.q.q[quant_layer(heap_index)];
 }
@@ -88,15 +100,15 @@ __device__ __forceinline__ void unpair_t(int low, int d, int &left, int &right) 
         left = add_w(d, right);
     }
 }
-template <bool SOME>
+template <bool SOME, bool MID = false>
 __device__ __forceinline__ void inv_wave(InvRegs c, int lane, const InvArgs &a, int (&leaf)[8]) {
     if (!a.q_identity) {
 #pragma unroll
-        for (int i = 0; i < 4; i++) c.d8[i] = dequant_ref(c.d8[i], 256 + 4 * lane + i, a);
+        for (int i = 0; i < 4; i++) c.d8[i] = dequant_ref<MID>(c.d8[i], 256 + 4 * lane + i, a);
 #pragma unroll
-        for (int i = 0; i < 2; i++) c.d7[i] = dequant_ref(c.d7[i], 128 + 2 * lane + i, a);
-        c.d6 = dequant_ref(c.d6, 64 + lane, a);
-        c.low = dequant_ref(c.low, lane, a);
+        for (int i = 0; i < 2; i++) c.d7[i] = dequant_ref<MID>(c.d7[i], 128 + 2 * lane + i, a);
+        c.d6 = dequant_ref<MID>(c.d6, 64 + lane, a);
+        c.low = dequant_ref<MID>(c.low, lane, a);
     }
     int s = __shfl(c.low, 0); // low_pass_values[1] = coefficients[0].unwrap()  (:361)
 #pragma unroll
@@ -230,7 +242,90 @@ __device__ __forceinline__ void rct_inverse_rect8(uint8_t *img, const Tile &t, i
     }
 }
 
-template <int NI, bool RCT = false>
+// ---- MEASURE (fri_hip_measure_distortion_dev): where a K3 instance stores a byte, its MEASURE twin loads the same byte of the reference image (a.pixels) and
+// accumulates, per channel, the squared and the largest absolute difference, and the number of owned pixels (bytes of channel 0). Nothing is written but the
+// workgroup's totals: a wave reduction, then one 64-bit add and one 32-bit max per channel (and one add of the pixel count) per workgroup - exact integers,
+// the same in every run.
+struct MeasureAcc {
+    unsigned long long sse[3] = {0ull, 0ull, 0ull}; // 64 bit: a thread's share of a 16384^2 plane can exceed 2^32
+    uint32_t mx[3] = {0u, 0u, 0u};
+    uint32_t n = 0; // owned bytes of channel 0
+};
+// NW words of reconstructed and reference bytes, `mask` = the bytes that count (bit per byte), ph = channel of byte 0 (C = 3; the image's byte index mod 3).
+// Bytes are summed by their index mod 3 first (static registers), then rotated onto the channels.
+template <int NW>
+__device__ __forceinline__ void measure_words(MeasureAcc &m, const uint32_t (&r)[NW], const uint32_t (&f)[NW], uint32_t mask, int ph, int C) {
+    uint32_t s[3] = {0u, 0u, 0u}, x[3] = {0u, 0u, 0u}, n[3] = {0u, 0u, 0u}; // <= 16 bytes: s stays below 2^21
+#pragma unroll
+    for (int b = 0; b < 4 * NW; b++) {
+        const int e = (int)((r[b >> 2] >> (8 * (b & 3))) & 255u) - (int)((f[b >> 2] >> (8 * (b & 3))) & 255u);
+        const uint32_t on = (mask >> b) & 1u, d = on ? (uint32_t)(e < 0 ? -e : e) : 0u;
+        s[b % 3] += d * d;
+        x[b % 3] = max(x[b % 3], d);
+        n[b % 3] += on;
+    }
+    if (C == 1) {
+        m.sse[0] += s[0] + s[1] + s[2];
+        m.mx[0] = max(m.mx[0], max(x[0], max(x[1], x[2])));
+        m.n += n[0] + n[1] + n[2];
+        return;
+    }
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        const int k = c >= ph ? c - ph : c - ph + 3; // the bytes of channel c: index = k mod 3
+        m.sse[c] += k == 0 ? s[0] : k == 1 ? s[1] : s[2];
+        m.mx[c] = max(m.mx[c], k == 0 ? x[0] : k == 1 ? x[1] : x[2]);
+        if (c == 0) m.n += k == 0 ? n[0] : k == 1 ? n[1] : n[2];
+    }
+}
+// the owned bytes (nib) of the reference dword at p (4-byte aligned): byte loads unless all four are owned - a byte no cell owns may lie outside the image
+[[maybe_unused]] __device__ __forceinline__ uint32_t measure_ref_dword(const uint8_t *p, uint32_t nib) {
+    if (nib == 15u) return *reinterpret_cast<const uint32_t *>(p);
+    uint32_t f = 0;
+#pragma unroll
+    for (int b = 0; b < 4; b++)
+        if (nib & (1u << b)) f |= (uint32_t)p[b] << (8 * b);
+    return f;
+}
+// After the last tile: the workgroup's totals into out[2 c] (sum of squares), out[2 c + 1] (max, low 32 bits) and out[2 C] (owned pixels). Reuses the start
+// of the dynamic LDS (the launcher gives a MEASURE instance at least kMeasureLds bytes).
+constexpr int kMeasureLds = kInvWaves * (4 * 8 + 3 * 4);
+[[maybe_unused]] __device__ __forceinline__ void measure_flush(MeasureAcc m, unsigned long long *out, int C, uint8_t *lds, int tid) {
+    const int lane = tid & 63, wave = tid >> 6;
+    unsigned long long n = m.n;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            m.sse[c] += __shfl_xor(m.sse[c], o);
+            m.mx[c] = max(m.mx[c], (uint32_t)__shfl_xor((int)m.mx[c], o));
+        }
+        n += __shfl_xor(n, o);
+    }
+    unsigned long long *ws = reinterpret_cast<unsigned long long *>(lds); // [kInvWaves][4]: three sums, the count
+    uint32_t *wx = reinterpret_cast<uint32_t *>(ws + 4 * kInvWaves);      // [kInvWaves][3]
+    __syncthreads(); // every wave is done with the rectangle
+    if (lane == 0) {
+#pragma unroll
+        for (int c = 0; c < 3; c++) ws[4 * wave + c] = m.sse[c], wx[3 * wave + c] = m.mx[c];
+        ws[4 * wave + 3] = n;
+    }
+    __syncthreads();
+    if (tid < C) {
+        unsigned long long s = 0;
+        uint32_t x = 0;
+        for (int w = 0; w < kInvWaves; w++) s += ws[4 * w + tid], x = max(x, wx[3 * w + tid]);
+        atomicAdd(out + 2 * tid, s);
+        atomicMax(reinterpret_cast<uint32_t *>(out + 2 * tid + 1), x); // (little endian: the low half; the entry point zeroed the high half)
+    } else if (tid == C) {
+        unsigned long long s = 0;
+        for (int w = 0; w < kInvWaves; w++) s += ws[4 * w + 3];
+        atomicAdd(out + 2 * C, s);
+    }
+}
+
+// MID: the midpoint dequantiser (dequant_ref). MEASURE: see MeasureAcc.
+template <int NI, bool RCT = false, bool MID = false, bool MEASURE = false>
 __global__ void __launch_bounds__(kInvThreads) inverse_transform_kernel(const InvArgs a) {
     // this image of the batch (grid.y). Scalars, not a modified copy of the argument struct: a copy would live in scratch memory
     // (the quantiser array inside is indexed dynamically) and every argument access with it.
@@ -267,6 +362,7 @@ __global__ void __launch_bounds__(kInvThreads) inverse_transform_kernel(const In
 
     InvRegs pre[NI];
     inv_prefetch<NI>(a, img_coefs, scalar_tile(lds_tiles[0]), lds_cells, wave, lane, pre);
+    [[maybe_unused]] MeasureAcc acc;
     for (int ti = tb; ti < te; ti++) {
         const Tile t = scalar_tile(lds_tiles[ti - tb]);
         InvRegs cur[NI];
@@ -284,8 +380,8 @@ __global__ void __launch_bounds__(kInvThreads) inverse_transform_kernel(const In
         int leaf[NI][8];
 #pragma unroll
         for (int s = 0; s < NI; s++) {
-            if (inv_has_none(cur[s])) inv_wave<false>(cur[s], lane, a, leaf[s]);
-            else inv_wave<true>(cur[s], lane, a, leaf[s]);
+            if (inv_has_none(cur[s])) inv_wave<false, MID>(cur[s], lane, a, leaf[s]);
+            else inv_wave<true, MID>(cur[s], lane, a, leaf[s]);
         }
 #pragma unroll
         for (int s = 0; s < NI; s++) {
@@ -345,7 +441,13 @@ __global__ void __launch_bounds__(kInvThreads) inverse_transform_kernel(const In
                 uint8_t *p = img_pixels + g - (int)((base_lo + (uint32_t)g) & 15u) + 16 * k; // 16-byte aligned
                 const u32x4 out{__builtin_amdgcn_perm(lo.y, lo.x, 0x06040200u), __builtin_amdgcn_perm(lo.w, lo.z, 0x06040200u),
                                 __builtin_amdgcn_perm(hi.y, hi.x, 0x06040200u), __builtin_amdgcn_perm(hi.w, hi.z, 0x06040200u)};
-                if (!(ablate_flags(a.ablate) & 1)) *reinterpret_cast<u32x4 *>(p) = out;
+                if constexpr (MEASURE) {
+                    const u32x4 f = *reinterpret_cast<const u32x4 *>(p);
+                    const uint32_t rw[4] = {out.x, out.y, out.z, out.w}, fw[4] = {f.x, f.y, f.z, f.w};
+                    measure_words<4>(acc, rw, fw, 0xFFFFu, (16 * k + 48 - (int)((base_lo + (uint32_t)g) & 15u)) % 3, C); // p is 0..15 bytes in front of pixel byte g
+                } else if (!(ablate_flags(a.ablate) & 1)) {
+                    *reinterpret_cast<u32x4 *>(p) = out;
+                }
             }
             const unsigned long long m = __ballot(rim);
             if (rim) queue[qn + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = (uint16_t)(r << 8 | k);
@@ -363,7 +465,18 @@ __global__ void __launch_bounds__(kInvThreads) inverse_transform_kernel(const In
                 src[0] = u32x4{0u, 0u, 0u, 0u};
                 src[1] = u32x4{0u, 0u, 0u, 0u};
                 const uint32_t u[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-                if (!(ablate_flags(a.ablate) & 1)) {
+                if constexpr (MEASURE) {
+                    const int ph = 16 * k + 48 - (int)((base_lo + (uint32_t)g) & 15u);
+#pragma unroll
+                    for (int d = 0; d < 4; d++) {
+                        const uint32_t v0 = u[2 * d], v1 = u[2 * d + 1];
+                        const uint32_t nib = ((v0 >> 8) & 1u) | ((v0 >> 23) & 2u) | ((v1 >> 6) & 4u) | ((v1 >> 21) & 8u);
+                        if (nib) {
+                            const uint32_t rw[1] = {__builtin_amdgcn_perm(v1, v0, 0x06040200u)}, fw[1] = {measure_ref_dword(p + 4 * d, nib)};
+                            measure_words<1>(acc, rw, fw, nib, (ph + 4 * d) % 3, C);
+                        }
+                    }
+                } else if (!(ablate_flags(a.ablate) & 1)) {
 #pragma unroll
                     for (int d = 0; d < 4; d++) {
                         const uint32_t v0 = u[2 * d], v1 = u[2 * d + 1];
@@ -383,6 +496,7 @@ __global__ void __launch_bounds__(kInvThreads) inverse_transform_kernel(const In
         lds_barrier(); // the rectangle is all zero again
         trace_stamp(a.trace, wg, 2 + ti - tb, tid);
     }
+    if constexpr (MEASURE) measure_flush(acc, a.measure, C, lds, tid);
     trace_exit(a.trace, wg, tid);
 }
 
@@ -393,7 +507,7 @@ __global__ void __launch_bounds__(kInvThreads) inverse_transform_kernel(const In
 // width * channels multiples of 16): the launcher falls back to inverse_transform_kernel otherwise.
 constexpr int kInvListPre = 3; // list entries a thread holds in flight per list and tile (more are loaded on demand)
 static_assert((size_t)kInvListPre * kInvThreads <= kInvListPad, "the lists' pad covers a thread's unconditional loads");
-template <int NI, bool RCT = false>
+template <int NI, bool RCT = false, bool MID = false, bool MEASURE = false>
 __global__ void __launch_bounds__(kInvThreads) inverse_transform_lists_kernel(const InvArgs a) {
     const int32_t *const img_coefs = a.coefs + blockIdx.y * a.coef_stride; // this image of the batch, see inverse_transform_kernel
     uint8_t *const img_pixels = a.pixels + blockIdx.y * a.pixel_stride;
@@ -427,6 +541,7 @@ __global__ void __launch_bounds__(kInvThreads) inverse_transform_lists_kernel(co
 
     InvRegs pre[NI];
     inv_prefetch<NI>(a, img_coefs, scalar_tile(lds_tiles[0]), lds_cells, wave, lane, pre);
+    [[maybe_unused]] MeasureAcc acc;
     for (int ti = tb; ti < te; ti++) {
         const Tile t = scalar_tile(lds_tiles[ti - tb]);
         const InvTileLists L = scalar_lists(lds_lists[ti - tb]);
@@ -467,16 +582,16 @@ __global__ void __launch_bounds__(kInvThreads) inverse_transform_lists_kernel(co
                 for (int s = 0; s < NI; s++) none |= inv_has_none(cur[s]);
                 if (none) {
 #pragma unroll
-                    for (int s = 0; s < NI; s++) inv_wave<false>(cur[s], lane, a, leaf[s]);
+                    for (int s = 0; s < NI; s++) inv_wave<false, MID>(cur[s], lane, a, leaf[s]);
                 } else {
 #pragma unroll
-                    for (int s = 0; s < NI; s++) inv_wave<true>(cur[s], lane, a, leaf[s]);
+                    for (int s = 0; s < NI; s++) inv_wave<true, MID>(cur[s], lane, a, leaf[s]);
                 }
             } else {
 #pragma unroll
                 for (int s = 0; s < NI; s++) {
-                    if (inv_has_none(cur[s])) inv_wave<false>(cur[s], lane, a, leaf[s]);
-                    else inv_wave<true>(cur[s], lane, a, leaf[s]);
+                    if (inv_has_none(cur[s])) inv_wave<false, MID>(cur[s], lane, a, leaf[s]);
+                    else inv_wave<true, MID>(cur[s], lane, a, leaf[s]);
                 }
             }
         }
@@ -522,20 +637,34 @@ __global__ void __launch_bounds__(kInvThreads) inverse_transform_lists_kernel(co
             const uint32_t rk = m < kInvListPre ? (m == 0 ? qe[0] : m == 1 ? qe[1] : qe[2]) : a.quads[L.quad_begin + e];
             const uint32_t r = rk >> 8, k = rk & 255u;
             const u32x4 v = *reinterpret_cast<const u32x4 *>(img + __umul24(r, pitch24) + 16 * k);
-            if (!(ablate_flags(a.ablate) & 1)) *reinterpret_cast<u32x4 *>(out0 + (__umul24(r, wc24) + 16 * k)) = v;
+            if constexpr (MEASURE) { // (channel of a byte: its column mod 3 - every image row starts at a multiple of 3)
+                const u32x4 f = *reinterpret_cast<const u32x4 *>(out0 + (__umul24(r, wc24) + 16 * k));
+                const uint32_t rw[4] = {v.x, v.y, v.z, v.w}, fw[4] = {f.x, f.y, f.z, f.w};
+                measure_words<4>(acc, rw, fw, 0xFFFFu, (a0 + 16 * (int)k) % 3, C);
+            } else if (!(ablate_flags(a.ablate) & 1)) {
+                *reinterpret_cast<u32x4 *>(out0 + (__umul24(r, wc24) + 16 * k)) = v;
+            }
         }
         for (uint32_t e = tid, m = 0; e < L.dword_count; e += kInvThreads, m++) { // whole dwords of partly owned quads
             const uint32_t rd = m < kInvListPre ? (m == 0 ? de[0] : m == 1 ? de[1] : de[2]) : a.dwords[L.dword_begin + e];
             const uint32_t r = rd >> 8, d = rd & 255u;
             const uint32_t v = *reinterpret_cast<const uint32_t *>(img + __umul24(r, pitch24) + 4 * d);
-            if (!(ablate_flags(a.ablate) & 1)) *reinterpret_cast<uint32_t *>(out0 + (__umul24(r, wc24) + 4 * d)) = v;
+            if constexpr (MEASURE) {
+                const uint32_t rw[1] = {v}, fw[1] = {*reinterpret_cast<const uint32_t *>(out0 + (__umul24(r, wc24) + 4 * d))};
+                measure_words<1>(acc, rw, fw, 15u, (a0 + 4 * (int)d) % 3, C);
+            } else if (!(ablate_flags(a.ablate) & 1)) {
+                *reinterpret_cast<uint32_t *>(out0 + (__umul24(r, wc24) + 4 * d)) = v;
+            }
         }
         for (uint32_t e = tid, m = 0; e < L.part_count; e += kInvThreads, m++) { // the fractal rim proper: byte stores
             const uint32_t ent = m < kInvListPre ? (m == 0 ? pe[0] : m == 1 ? pe[1] : pe[2]) : a.parts[L.part_begin + e];
             const uint32_t r = ent >> 12, d = (ent >> 4) & 255u, nib = ent & 15u;
             const uint32_t v = *reinterpret_cast<const uint32_t *>(img + __umul24(r, pitch24) + 4 * d);
             uint8_t *p = out0 + (__umul24(r, wc24) + 4 * d);
-            if (!(ablate_flags(a.ablate) & 1)) {
+            if constexpr (MEASURE) {
+                const uint32_t rw[1] = {v}, fw[1] = {measure_ref_dword(p, nib)};
+                measure_words<1>(acc, rw, fw, nib, (a0 + 4 * (int)d) % 3, C);
+            } else if (!(ablate_flags(a.ablate) & 1)) {
                 if (nib & 1u) p[0] = (uint8_t)v;
                 if (nib & 2u) p[1] = (uint8_t)(v >> 8);
                 if (nib & 4u) p[2] = (uint8_t)(v >> 16);
@@ -545,11 +674,26 @@ __global__ void __launch_bounds__(kInvThreads) inverse_transform_lists_kernel(co
         if (!(ablate_flags(a.ablate) & 16)) lds_barrier(); // everyone is done reading before the next tile scatters (16: timing only - what a second rectangle would save)
         trace_stamp(a.trace, wg, 2 + ti - tb, tid);
     }
+    if constexpr (MEASURE) measure_flush(acc, a.measure, C, lds, tid);
     trace_exit(a.trace, wg, tid);
 }
 
 
 } // namespace
+
+using InvKernel = void (*)(const InvArgs);
+template <bool RCT, bool MID, bool MEASURE>
+static InvKernel pick_inverse(bool lists, int items_per_wave) {
+    if (lists)
+        return items_per_wave <= 1 ? inverse_transform_lists_kernel<1, RCT, MID, MEASURE> : items_per_wave == 2 ? inverse_transform_lists_kernel<2, RCT, MID, MEASURE>
+                                                                                                                 : inverse_transform_lists_kernel<4, RCT, MID, MEASURE>;
+    return items_per_wave <= 1 ? inverse_transform_kernel<1, RCT, MID, MEASURE> : items_per_wave == 2 ? inverse_transform_kernel<2, RCT, MID, MEASURE>
+                                                                                                       : inverse_transform_kernel<4, RCT, MID, MEASURE>;
+}
+// The midpoint and measuring instances live in k3_lossy.hip, which compiles this file's kernels again: instantiated here, next to the reference and multiply
+// instances, they changed the register allocation of those (a module-level effect), which then no longer compiled to the instructions they had before.
+const void *pick_inverse_lossy(bool rct, bool lists, int items_per_wave, bool mid, bool measure);
+#ifndef FRI_K3_LOSSY_INSTANCES
 
 // 16 bit per staged byte; a staged row holds <= lds_pitch bytes including its lead-in (lds_pitch >= widest row + 15).
 static size_t inv_buf_bytes(const DevicePlan &p) { return (size_t)p.lds_rows * (size_t)p.lds_pitch * 2; }
@@ -569,12 +713,19 @@ bool inv_plan_fits(const DevicePlan &p, bool with_lists) {
     return true;
 }
 
+// the kernel for a launch: the reference / multiply instances of this file, or the lossy ones of k3_lossy.hip
+static const void *pick_inverse(bool rct, bool lists, int items_per_wave, bool mid, bool measure) {
+    if (mid || measure) return pick_inverse_lossy(rct, lists, items_per_wave, mid, measure);
+    return reinterpret_cast<const void *>(rct ? pick_inverse<true, false, false>(lists, items_per_wave) : pick_inverse<false, false, false>(lists, items_per_wave));
+}
+
 hipError_t launch_inverse_transform(const DevicePlan &p, uint32_t n_images, const int32_t *coefs, size_t coef_stride, const QMatrix &q, uint8_t *pixels, size_t pixel_stride,
-                                    hipStream_t stream) {
-    if (!n_images || n_images > 65535u) return hipErrorInvalidValue;
+                                    hipStream_t stream, unsigned long long *measure) {
+    if (!n_images || n_images > 65535u || (measure && n_images != 1)) return hipErrorInvalidValue;
     // RasterImage::from_wavelet starts from an all-zero raster (wavelet_transform.rs:309-317). When every pixel belongs to a
     // retained cell the kernel writes all of them (zeros included); only a lattice with holes (very thin images) needs the fill.
-    if (!p.covers_image) {
+    // (A measuring launch reads `pixels` and counts only owned bytes.)
+    if (!p.covers_image && !measure) {
         for (uint32_t k = 0; k < n_images; k++) {
             hipError_t e = hipMemsetAsync(pixels + k * pixel_stride, 0, (size_t)p.width * p.height * p.channels, stream);
             if (e != hipSuccess) return e;
@@ -602,9 +753,11 @@ hipError_t launch_inverse_transform(const DevicePlan &p, uint32_t n_images, cons
     a.q_identity = 1;
     for (int i = 0; i <= 9; i++) a.q_identity &= (q.q[i] == 1);
     a.q_multiply = p.k3_multiply ? 1 : 0;
+    a.measure = measure;
     a.queue_bytes = (int32_t)inv_queue_bytes(p);
     const int items_per_wave = (p.max_tile_cells * p.channels + kInvWaves - 1) / kInvWaves;
     const bool rct = p.rct && p.channels == 3; // (fri_hip_plan_set_colour_transform refuses RCT on other plans)
+    const bool mid = p.k3_midpoint, meas = measure != nullptr;
     if (!inv_plan_fits(p, false)) return hipErrorInvalidConfiguration;
     // static write-out lists when every image row starts 16-byte aligned (and their rectangle fits: fri_hip_plan_create checks that for the tilings it builds)
     const bool lists = p.inv_lists && !p.k3_scan && inv_plan_fits(p, true) && (reinterpret_cast<uintptr_t>(pixels) & 15) == 0 && (((size_t)p.width * p.channels) & 15) == 0 &&
@@ -615,27 +768,29 @@ hipError_t launch_inverse_transform(const DevicePlan &p, uint32_t n_images, cons
         a.dwords = p.inv_dwords;
         a.parts = p.inv_parts;
         a.rect_bytes = p.inv_rect_bytes;
-        const size_t lds2 = (size_t)p.inv_rect_bytes + (size_t)p.inv_max_wg_tiles * (sizeof(Tile) + sizeof(InvTileLists)) + (size_t)p.inv_max_wg_cells * sizeof(TileCell);
-        void (*k2)(const InvArgs) = rct ? (items_per_wave <= 1 ? inverse_transform_lists_kernel<1, true> : items_per_wave == 2 ? inverse_transform_lists_kernel<2, true> : inverse_transform_lists_kernel<4, true>)
-                                        : (items_per_wave <= 1 ? inverse_transform_lists_kernel<1> : items_per_wave == 2 ? inverse_transform_lists_kernel<2> : inverse_transform_lists_kernel<4>);
+        size_t lds2 = (size_t)p.inv_rect_bytes + (size_t)p.inv_max_wg_tiles * (sizeof(Tile) + sizeof(InvTileLists)) + (size_t)p.inv_max_wg_cells * sizeof(TileCell);
+        if (meas) lds2 = std::max(lds2, (size_t)kMeasureLds);
+        const void *k2 = pick_inverse(rct, true, items_per_wave, mid, meas);
         if (lds2 > 48 * 1024) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k2), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
+            hipError_t e = hipFuncSetAttribute(k2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
             if (e != hipSuccess) return e;
         }
         (void)hipGetLastError(); // the check behind the launch must not pick up an error an earlier, unrelated call left behind
-        hipLaunchKernelGGL(k2, dim3(a.n_wg, n_images), dim3(kInvThreads), lds2, stream, a);
-        return hipGetLastError();
+        void *args[] = {&a};
+        hipError_t e = hipLaunchKernel(k2, dim3(a.n_wg, n_images), dim3(kInvThreads), args, lds2, stream);
+        return e != hipSuccess ? e : hipGetLastError();
     }
-    const size_t lds = inv_lds_bytes(p);
-    void (*kern)(const InvArgs) = rct ? (items_per_wave <= 1 ? inverse_transform_kernel<1, true> : items_per_wave == 2 ? inverse_transform_kernel<2, true> : inverse_transform_kernel<4, true>)
-                                      : (items_per_wave <= 1 ? inverse_transform_kernel<1> : items_per_wave == 2 ? inverse_transform_kernel<2> : inverse_transform_kernel<4>);
+    const size_t lds = meas ? std::max(inv_lds_bytes(p), (size_t)kMeasureLds) : inv_lds_bytes(p);
+    const void *kern = pick_inverse(rct, false, items_per_wave, mid, meas);
     if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
     (void)hipGetLastError(); // the check behind the launch must not pick up an error an earlier, unrelated call left behind
-    hipLaunchKernelGGL(kern, dim3(a.n_wg, n_images), dim3(kInvThreads), lds, stream, a);
-    return hipGetLastError();
+    void *args[] = {&a};
+    hipError_t e = hipLaunchKernel(kern, dim3(a.n_wg, n_images), dim3(kInvThreads), args, lds, stream);
+    return e != hipSuccess ? e : hipGetLastError();
 }
+#endif // FRI_K3_LOSSY_INSTANCES
 
 } // namespace fri

@@ -51,6 +51,7 @@ struct DevicePlan {
     int32_t k2_ablate = 0; // the same for K2, see PredArgs::ablate
     bool rct = false; // fri_hip_plan_set_colour_transform(FRI_HIP_COLOUR_RCT), C = 3 only: K1 codes (G, B - G + 128, R - G + 128), K3 undoes it
     bool k3_multiply = false; // fri_hip_plan_set_dequantiser: the inverse kernel multiplies by the quantiser instead of reproducing the reference's division
+    bool k3_midpoint = false; // fri_hip_plan_set_dequantiser(FRI_HIP_DEQUANT_MIDPOINT): ... or reconstructs the middle of the truncating quantiser's interval
     unsigned long long *trace = nullptr; // [n_wg][16] diagnostic timeline (FRI_HIP_TRACE=1), else null
     bool k1_measuring = false; // fri_hip_plan_tune_forward's measuring copies: their forward launches run the kernel's MEASURE instance (a name of its own in traces)
     unsigned long long *k1_xcd_stat = nullptr; // [8][2] per-XCD workgroup lifetimes of the forward kernel: set by fri_hip_plan_tune_forward on its measuring copies only
@@ -132,8 +133,10 @@ hipError_t launch_fit_solve(int mode, uint32_t n_planes, const unsigned long lon
                             hipStream_t stream, float *host_params = nullptr, const unsigned long long *range = nullptr, unsigned long long *host_range = nullptr);
 // K3: (reference-faithful) dequantisation + inverse transform + clamp.
 // n_images images of the plan's shape: image k at coefs + k * coef_stride (int32 elements), pixels + k * pixel_stride (bytes)
+// measure (n_images = 1 only): the kernel's MEASURE instance - `pixels` is the reference image and only read; measure[2 c] += the sum of squared differences of
+// channel c over the bytes the kernel would write, measure[2 c + 1] = max(.., largest absolute difference), measure[2 C] += owned pixels. The caller zeroes it.
 hipError_t launch_inverse_transform(const DevicePlan &p, uint32_t n_images, const int32_t *coefs, size_t coef_stride, const QMatrix &q, uint8_t *pixels, size_t pixel_stride,
-                                    hipStream_t stream);
+                                    hipStream_t stream, unsigned long long *measure = nullptr);
 
 // K5, gather form: out[i] = words[order[i]] for the halfword planes K2 writes with PredBatch::words (order: n_symbols entries, cell << 9 | heap index in
 // the reference's stream order with the None nodes taken out; 16-byte aligned).

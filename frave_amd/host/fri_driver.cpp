@@ -6,15 +6,18 @@
 //                                                            symbol order / ANS models / rANS / frif container on the host; self-checks the stream
 //   fri_driver encode-file <in.pgm|in.ppm|in.bmp> <out.frv> [--rct]  the same pipeline on a binary PGM (P5, one plane), PPM (P6, RGB) or uncompressed
 //                                                            24-bit BMP file, 8 bits per sample (fri-cli encode, crates/fri-cli/src/commands/encode.rs:8-54);
-//                                                            --rct: an RGB image is coded as Y, Cb, Cr of the reversible colour transform (flagged file)
+//                                                            --rct: an RGB image is coded as Y, Cb, Cr of the reversible colour transform (flagged file);
+//                                                            --quality Q (1..99): lossy, quantised with fri_hip_quality_matrix(Q), the quality in the file;
+//                                                            --psnr DB: lossy at the lowest quality that reaches DB (fri_hip_search_quality); prints both
 //   fri_driver decode-file <in.frv> <out.pgm|.ppm|.bmp>     container -> rANS / context decoding on the host -> dequantisation + inverse
 //                                                            transform on the device (fri-cli decode, crates/fri-cli/src/commands/decode.rs); a flagged file
-//                                                            comes back as RGB
+//                                                            comes back as RGB, a lossy file with its quality's matrix and the midpoint dequantiser
 //   fri_driver batch <width> <height> <channels> <n_images> [--gpus N]
 //                                                            BASELINE config 3: host batch with H2D / kernel / D2H overlap; with --gpus N
 //                                                            BASELINE config 4: the batch sharded over N GPUs of this node (image i -> GPU i mod N,
 //                                                            one host thread + ctx per GPU, no collective; fri_hip_multi_transform_quant)
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -137,8 +140,24 @@ static bool has_suffix(const char *path, const char *suffix) {
 // over PCIe) - the default since round 4. Self-checks: the array route (stage functions one by one, 9 bytes per node over PCIe, gather on the host) must give
 // the same bytes - it does bit for bit since the fit's W^T r sums are fixed-point integers (k4_fit.hip): both routes fit the same parameters - ; the container
 // parses and every symbol decodes; FRIDecoder::decode returns the input.
-static int encode_image_to_file(std::vector<uint8_t> img, uint32_t w, uint32_t h, uint32_t c, const libfri::EncoderOpts &opts, const char *out_path) {
+// Lossy (--quality / --psnr): the decoded image must equal the direct round trip K1 with the quality's matrix -> K3 with the midpoint dequantiser.
+static int encode_image_to_file(std::vector<uint8_t> img, uint32_t w, uint32_t h, uint32_t c, libfri::EncoderOpts opts, const char *out_path) {
     const libfri::ColorSpace cs = c == 1 ? libfri::ColorSpace::Luma : libfri::ColorSpace::RGB;
+    if (opts.target_psnr > 0) { // the quality first (the same search FRIEncoder::encode runs), then both routes code with it
+        libfri::Device dev(opts.device);
+        std::string err;
+        fri_hip_plan *plan = dev.ok() ? dev.plan(w, h, c, err) : nullptr;
+        int32_t q = 100;
+        double db = 0;
+        const int rc = plan ? fri_hip_search_quality(plan, img.data(), opts.target_psnr, &q, &db) : FRI_HIP_ERR_NO_DEVICE;
+        if (rc != FRI_HIP_OK) {
+            std::fprintf(stderr, "quality search: %s\n", plan ? dev.describe(rc).c_str() : (dev.ok() ? err.c_str() : dev.error().c_str()));
+            return 1;
+        }
+        std::printf("target %.2f dB: quality %d (%.2f dB)\n", opts.target_psnr, q, db);
+        opts.quality = q < 100 ? q : 0;
+        opts.target_psnr = 0;
+    }
     auto t0 = std::chrono::steady_clock::now();
     libfri::FRIEncoder streamed_encoder(opts);
     auto streamed = streamed_encoder.encode_bytes_streamed(img, h, w, cs);
@@ -191,10 +210,25 @@ static int encode_image_to_file(std::vector<uint8_t> img, uint32_t w, uint32_t h
     t0 = std::chrono::steady_clock::now();
     auto back = libfri::FRIDecoder().decode(bytes, opts);
     const double t_dec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    if (!back.ok || back.value.data != img) {
-        std::fprintf(stderr, "self-check failed: %s\n", back.ok ? "decoded image differs from the input" : back.error.c_str());
+    std::vector<uint8_t> expected = img;
+    if (opts.quality && back.ok) {
+        libfri::Device dev(opts.device);
+        libfri::RasterImage raster{libfri::ImageMetadata{h, w, cs}, img};
+        auto coded = libfri::stages::wavelet_transform::encode(raster, opts, dev);
+        auto direct = coded.ok ? libfri::stages::wavelet_transform::decode(coded.value, opts, dev) : libfri::Result<libfri::RasterImage>{};
+        if (!direct.ok) {
+            std::fprintf(stderr, "self-check failed: direct round trip: %s\n", coded.ok ? direct.error.c_str() : coded.error.c_str());
+            return 1;
+        }
+        expected = std::move(direct.value.data);
+    }
+    if (!back.ok || back.value.data != expected) {
+        std::fprintf(stderr, "self-check failed: %s\n", back.ok ? (opts.quality ? "decoded image differs from the direct lossy round trip" : "decoded image differs from the input") : back.error.c_str());
         return 1;
     }
+    double sse = 0;
+    for (size_t i = 0; i < img.size(); i++) sse += ((double)back.value.data[i] - img[i]) * ((double)back.value.data[i] - img[i]);
+    const double psnr = sse > 0 ? 10.0 * std::log10(255.0 * 255.0 * (double)img.size() / sse) : HUGE_VAL;
     if (FILE *f = std::fopen(out_path, "wb")) {
         std::fwrite(bytes.data(), 1, bytes.size(), f);
         std::fclose(f);
@@ -202,8 +236,9 @@ static int encode_image_to_file(std::vector<uint8_t> img, uint32_t w, uint32_t h
         std::fprintf(stderr, "cannot write %s\n", out_path);
         return 1;
     }
-    std::printf("%ux%ux%u: %zu bytes, %.3f bits per pixel; symbol stream route end to end (context, plan, stream order, chain, emit) %.3f s; self-checks: array route, device stages (incl. plan + PCIe) %.3f s + host emit %.3f s: same bytes; decoded back in %.3f s: lossless\n", w, h, c,
-                bytes.size(), 8.0 * bytes.size() / ((double)w * h), t_streamed, t_dev, t_host, t_dec);
+    std::printf("%ux%ux%u: %zu bytes, %.3f bits per pixel; symbol stream route end to end (context, plan, stream order, chain, emit) %.3f s; self-checks: array route, device stages (incl. plan + PCIe) %.3f s + host emit %.3f s: same bytes; decoded back in %.3f s: %s\n", w, h, c,
+                bytes.size(), 8.0 * bytes.size() / ((double)w * h), t_streamed, t_dev, t_host, t_dec, opts.quality ? "the direct lossy round trip" : "lossless");
+    if (opts.quality) std::printf("quality %d: PSNR %.2f dB\n", opts.quality, psnr);
     return 0;
 }
 
@@ -217,7 +252,21 @@ int main(int argc, char **argv) {
             return 1;
         }
         libfri::EncoderOpts file_opts; // parameters are fitted on the device sums (fit_parameters defaults to true)
-        for (int i = 4; i < argc; i++) file_opts.colour_transform = file_opts.colour_transform || std::string(argv[i]) == "--rct";
+        for (int i = 4; i < argc; i++) {
+            const std::string a = argv[i];
+            if (a == "--rct") file_opts.colour_transform = true;
+            else if (a == "--quality" && i + 1 < argc) file_opts.quality = std::atoi(argv[++i]);
+            else if (a == "--psnr" && i + 1 < argc) file_opts.target_psnr = std::atof(argv[++i]);
+            else {
+                std::fprintf(stderr, "encode-file: unknown option %s\n", a.c_str());
+                return 2;
+            }
+        }
+        if (file_opts.quality < 0 || file_opts.quality > 99 || file_opts.target_psnr < 0 || (file_opts.quality && file_opts.target_psnr > 0) ||
+            ((file_opts.quality || file_opts.target_psnr > 0) && file_opts.colour_transform)) {
+            std::fprintf(stderr, "encode-file: --quality 1..99 or --psnr DB (> 0), not both, and neither with --rct\n");
+            return 2;
+        }
         return encode_image_to_file(std::move(img), fw, fh, fc, file_opts, argv[3]);
     }
     if (argc >= 4 && std::string(argv[1]) == "decode-file") {
@@ -256,7 +305,7 @@ int main(int argc, char **argv) {
         return 0;
     }
     if (argc < 5) {
-        std::fprintf(stderr, "usage: %s roundtrip|encode|batch|batch-frv <width> <height> <channels> [n_images | out.frv]\n       %s encode-file <in.pgm|in.ppm|in.bmp> <out.frv> [--rct]\n       %s decode-file <in.frv> <out.pgm|out.ppm|out.bmp>\n", argv[0], argv[0], argv[0]);
+        std::fprintf(stderr, "usage: %s roundtrip|encode|batch|batch-frv <width> <height> <channels> [n_images | out.frv]\n       %s encode-file <in.pgm|in.ppm|in.bmp> <out.frv> [--rct | --quality Q | --psnr DB]\n       %s decode-file <in.frv> <out.pgm|out.ppm|out.bmp>\n", argv[0], argv[0], argv[0]);
         return 2;
     }
     const std::string cmd = argv[1];

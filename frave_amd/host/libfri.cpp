@@ -58,7 +58,19 @@ std::string set_colour_transform(fri_hip_plan *plan, bool rct, Device &dev) {
 // what an encode of `colorspace` pixels codes: RGB with the option on goes out as Y, Cb, Cr (colour space YCbCr, flagged)
 ImageMetadata coded_metadata(uint32_t height, uint32_t width, ColorSpace colorspace, const EncoderOpts &opts) {
     const bool rct = opts.colour_transform && colorspace == ColorSpace::RGB;
-    return ImageMetadata{height, width, rct ? ColorSpace::YCbCr : colorspace, rct};
+    return ImageMetadata{height, width, rct ? ColorSpace::YCbCr : colorspace, rct, (uint32_t)(opts.quality > 0 && opts.quality < 100 ? opts.quality : 0)};
+}
+// The matrix an encode quantises with: fri_hip_quality_matrix(opts.quality) for a lossy encode, else opts.quantization_matrix. "" or the error.
+std::string coding_matrix(const EncoderOpts &opts, std::array<int32_t, 32> &q) {
+    if (opts.quality < 0 || opts.quality > 99) return "quality must be 0 (lossless) or 1..99";
+    if (!(opts.target_psnr >= 0)) return "target_psnr must be >= 0";
+    if ((opts.quality || opts.target_psnr > 0) && opts.colour_transform) return "lossy coding (quality / target_psnr) cannot be combined with colour_transform";
+    if (opts.quality && opts.target_psnr > 0) return "set quality or target_psnr, not both";
+    const bool ones = std::all_of(opts.quantization_matrix.begin(), opts.quantization_matrix.end(), [](int32_t v) { return v == 1; });
+    if (opts.quality && !ones) return "set quality or a quantization_matrix, not both";
+    q = opts.quantization_matrix;
+    if (opts.quality) fri_hip_quality_matrix(opts.quality, q.data());
+    return std::string();
 }
 emit::ColorSpaceCode colour_code(ColorSpace c) { return c == ColorSpace::Luma ? emit::kLuma : c == ColorSpace::RGB ? emit::kRGB : emit::kYCbCr; }
 } // namespace
@@ -111,12 +123,14 @@ Result<WaveletImage> encode(const RasterImage &raster, const EncoderOpts &opts, 
     if (!plan) return r;
     WaveletImage &w = r.value;
     w.metadata = coded_metadata(raster.metadata.height, raster.metadata.width, raster.metadata.colorspace, opts);
+    std::array<int32_t, 32> qm;
+    if (!(r.error = coding_matrix(opts, qm)).empty()) return r;
     if (!(r.error = set_colour_transform(plan, w.metadata.rct, dev)).empty()) return r;
     w.num_cells = fri_hip_plan_num_cells(plan);
     w.centers.resize((size_t)w.num_cells * 2);
     w.coefficients.resize(fri_hip_plan_coef_count(plan));
     int rc = fri_hip_plan_centers(plan, w.centers.data());
-    if (rc == FRI_HIP_OK) rc = fri_hip_transform_quant(plan, raster.data.data(), opts.quantization_matrix.data(), w.coefficients.data());
+    if (rc == FRI_HIP_OK) rc = fri_hip_transform_quant(plan, raster.data.data(), qm.data(), w.coefficients.data());
     if (rc != FRI_HIP_OK) {
         r.error = dev.describe(rc);
         return r;
@@ -136,10 +150,21 @@ Result<RasterImage> decode(const WaveletImage &image, const EncoderOpts &opts, D
         return r;
     }
     if (!(r.error = set_colour_transform(plan, image.metadata.rct, dev)).empty()) return r;
+    // a lossy image: the matrix of its quality and the midpoint dequantiser; otherwise the caller's matrix and the reference's dequantiser
+    std::array<int32_t, 32> qm = opts.quantization_matrix;
+    if (image.metadata.quality && fri_hip_quality_matrix((int)image.metadata.quality, qm.data()) != FRI_HIP_OK) {
+        r.error = "invalid quality";
+        return r;
+    }
+    if (int rc = fri_hip_plan_set_dequantiser(plan, image.metadata.quality ? FRI_HIP_DEQUANT_MIDPOINT : FRI_HIP_DEQUANT_REFERENCE); rc != FRI_HIP_OK) {
+        r.error = dev.describe(rc);
+        return r;
+    }
     r.value.metadata = image.metadata;
+    r.value.metadata.quality = 0; // (the raster is what the lossy planes decode to)
     if (image.metadata.rct) r.value.metadata.colorspace = ColorSpace::RGB, r.value.metadata.rct = false; // the kernel writes R, G, B
     r.value.data.resize(fri_hip_plan_pixel_bytes(plan));
-    int rc = fri_hip_inverse_transform(plan, image.coefficients.data(), opts.quantization_matrix.data(), r.value.data.data());
+    int rc = fri_hip_inverse_transform(plan, image.coefficients.data(), qm.data(), r.value.data.data());
     if (rc != FRI_HIP_OK) {
         r.error = dev.describe(rc);
         return r;
@@ -229,7 +254,18 @@ Result<EncodedStages> FRIEncoder::encode(std::vector<uint8_t> data, uint32_t hei
     // RawImage -> ChannelTransform (identity, channel_transform.rs:4-10) -> WaveletTransform -> Quantization -> Prediction (encoder.rs:19-38) as
     // ONE device-resident call: the pixels go up once, the coefficients stay in device memory between the stages, every output comes down once.
     WaveletImage &w = r.value.image;
-    w.metadata = coded_metadata(height, width, colorspace, opts_);
+    std::array<int32_t, 32> qm;
+    if (const std::string e = coding_matrix(opts_, qm); !e.empty()) return fail(e);
+    EncoderOpts coded = opts_;
+    if (opts_.target_psnr > 0) { // the lowest quality that reaches the target, searched on the device; 100 = lossless
+        int32_t q = 100;
+        double db = 0;
+        if (int rc = fri_hip_search_quality(plan, data.data(), opts_.target_psnr, &q, &db); rc != FRI_HIP_OK) return fail(dev.describe(rc));
+        coded.quality = q < 100 ? q : 0;
+        r.value.psnr_db = db;
+        if (coded.quality) fri_hip_quality_matrix(coded.quality, qm.data());
+    }
+    w.metadata = coded_metadata(height, width, colorspace, coded);
     if (const std::string e = set_colour_transform(plan, w.metadata.rct, dev); !e.empty()) return fail(e);
     w.num_cells = fri_hip_plan_num_cells(plan);
     w.centers.resize((size_t)w.num_cells * 2);
@@ -242,7 +278,7 @@ Result<EncodedStages> FRIEncoder::encode(std::vector<uint8_t> data, uint32_t hei
     uint64_t oob[3] = {0, 0, 0};
     int rc = fri_hip_plan_centers(plan, w.centers.data());
     if (rc == FRI_HIP_OK)
-        rc = fri_hip_encode_image(plan, data.data(), opts_.quantization_matrix.data(), opts_.fit_parameters ? 1 : 0, &vp[0][0][0], &wp[0][0][0], w.coefficients.data(),
+        rc = fri_hip_encode_image(plan, data.data(), qm.data(), opts_.fit_parameters ? 1 : 0, &vp[0][0][0], &wp[0][0][0], w.coefficients.data(),
                                   w.bucket.data(), w.prediction.data(), hist.data(), oob);
     if (rc != FRI_HIP_OK) return fail(dev.describe(rc));
     w.quantized = true;
@@ -289,7 +325,7 @@ Result<CompressedImage> stages::entropy_coding::encode(const WaveletImage &image
 }
 
 std::vector<uint8_t> stages::serialize::encode(const CompressedImage &image) {
-    return emit::serialize(image.metadata.height, image.metadata.width, colour_code(image.metadata.colorspace), image.channel_data, image.params, image.metadata.rct);
+    return emit::serialize(image.metadata.height, image.metadata.width, colour_code(image.metadata.colorspace), image.channel_data, image.params, image.metadata.rct, image.metadata.quality);
 }
 
 Result<CompressedImage> stages::serialize::decode(const std::vector<uint8_t> &bytes) {
@@ -301,6 +337,7 @@ Result<CompressedImage> stages::serialize::decode(const std::vector<uint8_t> &by
     r.value.metadata.width = p.width;
     r.value.metadata.colorspace = p.colorspace == emit::kLuma ? ColorSpace::Luma : p.colorspace == emit::kRGB ? ColorSpace::RGB : ColorSpace::YCbCr;
     r.value.metadata.rct = p.rct;
+    r.value.metadata.quality = p.quality;
     r.value.variant = p.variant;
     r.value.channel_data = std::move(p.channels);
     r.value.params = std::move(p.params);
@@ -369,7 +406,7 @@ std::string emit_streamed(const StreamedImage &im, uint32_t c, uint64_t n, const
     for (uint32_t ch = 0; ch < c; ch++)
         for (int g = 0; g < 3; g++)
             for (int k = 0; k < 6; k++) params[ch].value[g][k] = im.vp[ch][g][k], params[ch].width[g][k] = im.wp[ch][g][k];
-    out = emit::serialize(md.height, md.width, colour_code(md.colorspace), streams, params, md.rct);
+    out = emit::serialize(md.height, md.width, colour_code(md.colorspace), streams, params, md.rct, md.quality);
     return std::string();
 }
 } // namespace
@@ -401,6 +438,9 @@ Result<std::vector<uint8_t>> FRIEncoder::encode_bytes_streamed(std::vector<uint8
     fri_hip_plan *plan = dev.plan(width, height, c, err);
     if (!plan) return fail(err);
     const ImageMetadata md = coded_metadata(height, width, colorspace, opts_);
+    std::array<int32_t, 32> qm;
+    if (const std::string e = coding_matrix(opts_, qm); !e.empty()) return fail(e);
+    if (opts_.target_psnr > 0) return fail("target_psnr: FRIEncoder::encode only (search first, then pass the quality)");
     if (const std::string e = set_colour_transform(plan, md.rct, dev); !e.empty()) return fail(e);
     const uint64_t n = fri_hip_plan_num_some(plan);
     if (const std::string e = set_plan_stream_order(plan, dev); !e.empty()) return fail(e); // geometry only, once per plan (the plan is new here: Device lives for this call, as in encode())
@@ -409,7 +449,7 @@ Result<std::vector<uint8_t>> FRIEncoder::encode_bytes_streamed(std::vector<uint8
     float vp[3][3][6], wp[3][3][6];
     stages::prediction::params_to_flat(opts_, c, vp, wp);
     uint64_t oob[3] = {0, 0, 0};
-    const int rc = fri_hip_encode_image_symbols(plan, data.data(), opts_.quantization_matrix.data(), opts_.fit_parameters ? 1 : 0, &vp[0][0][0], &wp[0][0][0], symbols.data(),
+    const int rc = fri_hip_encode_image_symbols(plan, data.data(), qm.data(), opts_.fit_parameters ? 1 : 0, &vp[0][0][0], &wp[0][0][0], symbols.data(),
                                                 hist.data(), oob);
     if (rc != FRI_HIP_OK) return fail(dev.describe(rc));
     stages::prediction::params_from_flat(opts_, c, vp, wp);
@@ -421,7 +461,7 @@ Result<std::vector<uint8_t>> FRIEncoder::encode_bytes_streamed(std::vector<uint8
     for (uint32_t ch = 0; ch < c; ch++)
         for (int g = 0; g < 3; g++)
             for (int k = 0; k < 6; k++) params[ch].value[g][k] = vp[ch][g][k], params[ch].width[g][k] = wp[ch][g][k];
-    r.value = emit::serialize(height, width, colour_code(md.colorspace), streams, params, md.rct);
+    r.value = emit::serialize(height, width, colour_code(md.colorspace), streams, params, md.rct, md.quality);
     r.ok = true;
     return r;
 }
@@ -443,6 +483,12 @@ Result<std::vector<std::vector<uint8_t>>> encode_batch_bytes(const std::vector<c
     const size_t n_images = images.size();
     const uint32_t c = num_channels(colorspace);
     const ImageMetadata md = coded_metadata(height, width, colorspace, opts);
+    std::array<int32_t, 32> qm;
+    if (!(r.error = coding_matrix(opts, qm)).empty()) return r;
+    if (opts.target_psnr > 0) {
+        r.error = "encode_batch_bytes: target_psnr is not supported (no per-image search); pass a quality";
+        return r;
+    }
     const uint32_t n_dev = (uint32_t)devices.size();
     if (!n_dev || !emit_threads) {
         r.error = "encode_batch_bytes: no device / no emitter thread";
@@ -502,7 +548,7 @@ Result<std::vector<std::vector<uint8_t>>> encode_batch_bytes(const std::vector<c
                 stages::prediction::params_to_flat(o, c, im.vp, im.wp);
                 uint64_t oob[3] = {0, 0, 0};
                 const auto t0 = std::chrono::steady_clock::now();
-                const int rc = fri_hip_encode_image_symbols(plan, images[i], o.quantization_matrix.data(), o.fit_parameters ? 1 : 0, &im.vp[0][0][0], &im.wp[0][0][0], im.symbols.data(),
+                const int rc = fri_hip_encode_image_symbols(plan, images[i], qm.data(), o.fit_parameters ? 1 : 0, &im.vp[0][0][0], &im.wp[0][0][0], im.symbols.data(),
                                                             im.hist.data(), oob);
                 dev_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
                 if (rc != FRI_HIP_OK) {

@@ -34,6 +34,7 @@ struct ImageMetadata { // images.rs:68-79
     uint32_t height = 0, width = 0;
     ColorSpace colorspace = ColorSpace::RGB;
     bool rct = false; // the planes are Y, Cb, Cr of the reversible colour transform of RGB pixels (colorspace is then YCbCr; the file's metadata bit 0)
+    uint32_t quality = 0; // 0 = lossless, 1..99: the planes were quantised with fri_hip_quality_matrix(quality) (the file's metadata bits 8..14)
 };
 struct RasterImage { // images.rs:82-85
     ImageMetadata metadata;
@@ -48,6 +49,9 @@ struct AnsContext {                                     // entropy_coding.rs:32-
 
 using PredictionParams = std::array<std::array<float, 6>, 3>; // Vec<[f32; 6]> with 3 layer groups (prediction.rs:165-179)
 
+// encoder.rs:51-56 (which nothing in the reference reads): the presets as qualities of fri_hip_quality_matrix - Low 50, Medium 75, High 90, Lossless 0.
+enum class EncoderQuality { Low, Medium, High, Lossless };
+inline int quality_of(EncoderQuality q) { return q == EncoderQuality::Low ? 50 : q == EncoderQuality::Medium ? 75 : q == EncoderQuality::High ? 90 : 0; }
 struct EncoderOpts { // encoder.rs:58-64
     bool emit_coefficients = false;
     bool verbose = false;
@@ -57,6 +61,12 @@ struct EncoderOpts { // encoder.rs:58-64
     bool fit_parameters = true; // like the reference (prediction.rs:232-235); false = use the parameters given above
     int device = 0;
     bool colour_transform = false; // RGB input: code Y, Cb, Cr of the reversible colour transform (fri_hip_plan_set_colour_transform) and flag the file
+    // Lossy coding: 0 = lossless, 1..99 = quantise with fri_hip_quality_matrix(quality) and record it in the file (every encode path). Not together with a
+    // quantization_matrix other than all ones, nor with colour_transform.
+    int quality = 0;
+    // FRIEncoder::encode only: > 0 = search the lowest quality whose round trip reaches this PSNR in dB (fri_hip_search_quality) and code with it; a result of
+    // 100 codes an ordinary lossless file. Not together with quality or colour_transform.
+    double target_psnr = 0;
     EncoderOpts() { quantization_matrix.fill(1); }
 };
 
@@ -159,6 +169,7 @@ Result<WaveletImage> decode(const CompressedImage &image);
 struct EncodedStages { // EncoderStage::EntropyEncoding(WaveletImage, [Vec<AnsContext>; 3]), encoder.rs:12
     WaveletImage image;
     std::array<std::vector<AnsContext>, 3> contexts;
+    double psnr_db = 0; // with EncoderOpts::target_psnr: the PSNR of the chosen quality (image.metadata.quality; +inf for lossless)
 };
 
 class FRIEncoder { // encoder.rs:66-109

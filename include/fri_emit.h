@@ -19,8 +19,16 @@
  * Colour transform: `channels` of fri_emit_encode_image, fri_emit_encode_image_from_streams and fri_emit_check_image is 1, 3 or 3 | FRI_EMIT_RCT - the three
  * planes are Y, Cb, Cr of the reversible colour transform (fri_hip_plan_set_colour_transform, include/fri_hip.h). Such a file has the colour space YCbCr and
  * bit 0 of its metadata word set, and is otherwise byte for byte the file of the same planes without the flag; fri_emit_decode_image reports the flag the same
- * way, in info[2]. Any other high bit in `channels` is an invalid argument. */
+ * way, in info[2]. Any other high bit in `channels` is an invalid argument.
+ *
+ * Quality: `channels` may also carry FRI_EMIT_QUALITY(q), q = 1..99 - the planes were quantised with fri_hip_quality_matrix(q) (include/fri_hip.h) and decode
+ * with FRI_HIP_DEQUANT_MIDPOINT. Such a file holds q in bits 8..14 of its metadata word and is otherwise byte for byte the file of the same planes without it;
+ * a lossless file (no quality) keeps 0 there. fri_emit_decode_image reports the field the same way, in info[2]. Refused: a quality together with
+ * FRI_EMIT_RCT, and q = 0 or q >= 100 in the field; a file whose field holds 100..127 is "Invalid metadata". The reference's serialize::decode reads
+ * bits 28..31 only: it returns the quantised planes of a lossy file, i.e. the wrong pixels (as it returns Y, Cb, Cr for an RCT file). */
 #define FRI_EMIT_RCT 0x100u
+#define FRI_EMIT_QUALITY(q) ((uint32_t)(q) << 16)
+#define FRI_EMIT_QUALITY_OF(channels) (((uint32_t)(channels) >> 16) & 0x7Fu)
 #ifndef FRI_EMIT_H
 #define FRI_EMIT_H
 

@@ -346,9 +346,34 @@ int fri_hip_inverse_transform(fri_hip_plan *plan, const int32_t *coefs, const in
  * (stages/quantization.rs:27-45), which DIVIDES by the matrix entry like the encoder does - bit for bit the reference's decoder, and a defect of the
  * reference as soon as the matrix is not all ones. FRI_HIP_DEQUANT_MULTIPLY: the inverse of the quantiser, coefficient x
  * qmatrix[layer] in wrapping 32-bit arithmetic - what a lossy round trip needs. With today's all-ones matrix the two are the same kernel instance. */
+/* FRI_HIP_DEQUANT_MIDPOINT: the middle of the interval the truncating quantiser mapped the coefficient from - v = trunc(c / q) gives
+ * v q + (q - 1) / 2 for v > 0, v q - (q - 1) / 2 for v < 0 and 0 for v = 0 (wrapping 32-bit arithmetic, None stays None); what lossy files
+ * (fri_hip_quality_matrix) decode with. All three are the identity for the all-ones matrix. */
 #define FRI_HIP_DEQUANT_REFERENCE 0
 #define FRI_HIP_DEQUANT_MULTIPLY 1
+#define FRI_HIP_DEQUANT_MIDPOINT 2
 int fri_hip_plan_set_dequantiser(fri_hip_plan *plan, int mode);
+
+/* ---- lossy coding by quality -------------------------------------------------------------------- */
+/* The quantisation matrix of quality 1..100 (anything else: FRI_HIP_ERR_INVALID_ARGUMENT); host only, needs no device. Layer l <= 9 gets
+ * 1 + ((100 - quality) * w[l] + 99) / 100 with w = {0, 0, 0, 1, 2, 4, 6, 10, 16, 16}, layers >= 10 get 1: quality 100 is all ones (lossless) and
+ * every quality below it is lossy, entry 0 (the DC) is always 1, entry 9 equals entry 8, and every entry is non-increasing in quality. Part of
+ * the file format: a lossy file records only its quality (FRI_EMIT_QUALITY, include/fri_emit.h), the decoder rebuilds the matrix from this table. */
+int fri_hip_quality_matrix(int quality, int32_t qmatrix[32]);
+/* K3 with the plan's dequantiser and colour transform that writes nothing: where it would store a pixel byte it reads the same byte of
+ * d_reference_pixels (K3's output layout) and accumulates, per channel c, d_out[2c] = sum of (recon - ref)^2 and d_out[2c + 1] = max |recon - ref|,
+ * and d_out[2C] = the owned pixels (the pixels some retained cell covers - the only ones counted; every pixel for ordinary shapes). d_out holds 2C + 1
+ * uint64, zeroed on `stream` first; exact integers, the same in every run. PSNR = 10 log10(255^2 N / SSE) pooled over the channels, N = d_out[2C] x C
+ * samples, +inf for SSE = 0. Enqueued on `stream`, not synchronised. */
+int fri_hip_measure_distortion_dev(fri_hip_plan *plan, const int32_t *d_coefs, const int32_t qmatrix[32], const uint8_t *d_reference_pixels, uint64_t *d_out,
+                                   void *stream);
+/* The lowest quality whose lossy round trip (K1 with fri_hip_quality_matrix(q), K3 with FRI_HIP_DEQUANT_MIDPOINT) reaches target_db, by bisection:
+ * lo = 0, hi = 100; while hi - lo > 1: mid = (lo + hi) / 2, hi = mid if PSNR(mid) >= target_db, else lo = mid. Returns quality = hi and its PSNR
+ * (+inf for 100, which is never probed): at most 7 probes. Each probe reads its sums back, so the call synchronises `stream` and refuses a capturing one.
+ * FRI_HIP_ERR_INVALID_ARGUMENT for target_db NaN or <= 0 and on an RCT plan (the mod-256 colour transform turns quantisation error into wrap-around).
+ * The plan's dequantiser setting is left as it is. The host form stages the pixels through the plan's buffers. */
+int fri_hip_search_quality(fri_hip_plan *plan, const uint8_t *pixels, double target_db, int32_t *quality, double *psnr_db);
+int fri_hip_search_quality_dev(fri_hip_plan *plan, const uint8_t *d_pixels, double target_db, int32_t *quality, double *psnr_db, void *stream);
 /* Which colour transform the plan's forward and inverse entry points apply (the container's YCbCr colour space). FRI_HIP_COLOUR_NONE (default): the channels
  * are coded as they are. FRI_HIP_COLOUR_RCT (plans with C = 3 only): the reversible colour transform of JPEG-LS on interleaved R, G, B bytes, all arithmetic
  * mod 256 - lossless and 8 bit:
