@@ -30,7 +30,8 @@ SYMBOLS = [
     "fri_hip_plan_set_stream_order", "fri_hip_symbol_stream_batch_dev", "fri_hip_encode_image_symbols", "fri_hip_encode_symbols_batch_dev",
     "fri_hip_plan_set_dequantiser", "fri_hip_plan_tune_forward", "fri_hip_time_transform_quant_streams_dev",
     "fri_hip_plan_set_colour_transform", "fri_hip_quality_matrix", "fri_hip_measure_distortion_dev", "fri_hip_search_quality",
-    "fri_hip_search_quality_dev",
+    "fri_hip_search_quality_dev", "fri_hip_estimate_size_dev", "fri_hip_estimate_size", "fri_hip_search_quality_for_size",
+    "fri_hip_search_quality_for_size_dev",
 ]
 COLOUR_NONE, COLOUR_RCT = 0, 1  # fri_hip_plan_set_colour_transform
 DEQUANT_REFERENCE, DEQUANT_MULTIPLY, DEQUANT_MIDPOINT = 0, 1, 2  # fri_hip_plan_set_dequantiser
@@ -154,6 +155,10 @@ def load_library():
     L.fri_hip_measure_distortion_dev.argtypes = [vp, vp, vp, vp, vp, vp]
     L.fri_hip_search_quality.argtypes = [vp, vp, C.c_double, vp, vp]
     L.fri_hip_search_quality_dev.argtypes = [vp, vp, C.c_double, vp, vp, vp]
+    L.fri_hip_estimate_size_dev.argtypes = [vp, u32, vp, vp, vp, vp, vp]
+    L.fri_hip_estimate_size.argtypes = [vp, vp, vp, vp]
+    L.fri_hip_search_quality_for_size.argtypes = [vp, vp, C.c_uint64, vp, vp]
+    L.fri_hip_search_quality_for_size_dev.argtypes = [vp, vp, C.c_uint64, vp, vp, vp]
     L.fri_hip_plan_set_stream_order.argtypes = [vp, vp, C.c_uint64]
     L.fri_hip_symbol_stream_batch_dev.argtypes = [vp, u32, vp, sz, vp, vp, sz, vp, sz, vp]
     L.fri_hip_encode_image_symbols.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp]
@@ -416,6 +421,37 @@ class Plan:
             assert px.size == self.pixel_bytes
             _check(L.fri_hip_search_quality(self._h, _p(px), float(target_db), C.byref(qual), C.byref(db)), "fri_hip_search_quality", self.ctx)
         return qual.value, db.value
+
+    def estimate_size(self, hist, oob=None, stream=0, n_images=1, d_bytes=None, d_models=None):
+        """The estimated .frv bytes of the histograms (include/fri_hip.h gives the formula); UINT64_MAX where the emitter would refuse the image.
+        hist as a host array [C][10][1024] (oob [C] or None): fri_hip_estimate_size, returns an int. hist as a device pointer (an int, [n_images][C][10][1024];
+        oob a device pointer or None): fri_hip_estimate_size_dev, which only enqueues on `stream` - d_bytes (uint64 [n_images]) and d_models (uint32
+        [n_images][C][10][4] or None) are device pointers then, and the call returns None."""
+        L = load_library()
+        if isinstance(hist, int):
+            assert d_bytes
+            _check(L.fri_hip_estimate_size_dev(self._h, n_images, hist, oob or None, d_bytes, d_models or None, stream), "fri_hip_estimate_size_dev", self.ctx)
+            return None
+        h = np.ascontiguousarray(hist, np.uint32)
+        assert h.size == self.channels * 10 * 1024
+        o = None if oob is None else np.ascontiguousarray(oob, np.uint64)
+        assert o is None or o.size == self.channels
+        out = C.c_uint64(0)
+        _check(L.fri_hip_estimate_size(self._h, _p(h), None if o is None else _p(o), C.byref(out)), "fri_hip_estimate_size", self.ctx)
+        return out.value
+
+    def search_quality_for_size(self, pixels, max_bytes, stream=0):
+        """fri_hip_search_quality_for_size (pixels: a host array) or its _dev form (pixels: a device pointer, an int): the highest quality whose estimated
+        file is at most max_bytes, by the bisection the header describes. Returns (quality, estimated bytes); FriHipError with code -7 when nothing fits."""
+        qual, est = C.c_int32(0), C.c_uint64(0)
+        L = load_library()
+        if isinstance(pixels, int):
+            _check(L.fri_hip_search_quality_for_size_dev(self._h, pixels, int(max_bytes), C.byref(qual), C.byref(est), stream), "fri_hip_search_quality_for_size_dev", self.ctx)
+        else:
+            px = np.ascontiguousarray(pixels, np.uint8)
+            assert px.size == self.pixel_bytes
+            _check(L.fri_hip_search_quality_for_size(self._h, _p(px), int(max_bytes), C.byref(qual), C.byref(est)), "fri_hip_search_quality_for_size", self.ctx)
+        return qual.value, est.value
 
     def set_colour_transform(self, mode):
         """fri_hip_plan_set_colour_transform: COLOUR_NONE (default) or COLOUR_RCT (C = 3 plans): every forward entry point then codes the planes

@@ -80,6 +80,10 @@ struct Staging {
     Grown<uint16_t> symbols;         // fri_hip_encode_image_symbols: [C][geo.n_some]
     Grown<int32_t> search_coefs;     // fri_hip_search_quality*: the probes' coefficient planes [C][F][512]
     Grown<unsigned long long> measure; // fri_hip_search_quality*: a probe's distortion sums [2 C + 1]
+    Grown<uint32_t> search_hist;       // fri_hip_search_quality_for_size*: a probe's histograms [C][10][1024] ...
+    Grown<unsigned long long> search_oob; // ... its out-of-alphabet counts [C]
+    Grown<float> search_params;        // ... its fitted parameters [C][2][3][6]
+    Grown<unsigned long long> rate;    // fri_hip_estimate_size, fri_hip_search_quality_for_size*: the estimate [1]
 };
 
 constexpr int kBatchSlots = 3;
@@ -155,6 +159,7 @@ struct fri_hip_plan {
     HostMem<void> h_fit;       // pinned + mapped: [3] PredictParams + [3] u64
     void *d_h_fit = nullptr;   // the device's address of h_fit
     Event ev_fit;
+    const float *laplace = nullptr; // the rate kernel's [10][1024] Laplace shapes (laplace_table), uploaded with the plan
     bool assume_forward = false; // fri_hip_plan_assume_forward_coefficients
     DevMem<uint32_t> d_stream_order; // fri_hip_plan_set_stream_order: node index of the i-th symbol of a channel, [geo.n_some]
     DevMem<uint32_t> d_stream_pos;   // ... and its inverse, [F][512]: the position of a node's symbol in a channel's stream (None nodes: ~0, never used) - the scan's STREAM form
@@ -209,6 +214,23 @@ hipError_t upload(std::vector<DevMem<void>> &bufs, const std::vector<T> &v, cons
     out = static_cast<const T *>(d.get());
     return hipSuccess;
 }
+
+// The emitter's Laplace shape of every (context, symbol) in f32 (host/emit.cpp AnsContext::finalize, prediction.rs:219-221), with the same expression and the
+// platform libm's expf as the emitter - on the host, because the device's expf need not round like libm's, and one ulp moves (u32)(lap x 2^max_freq_bits)
+// across a truncation boundary. The rate kernel multiplies by 2^max_freq_bits, which is exact.
+std::vector<float> laplace_table() {
+    static const float width[10] = {2.5f, 4.5f, 6.3f, 8.5f, 12.7f, 16.f, 20.f, 24.f, 28.f, 36.f}; // width_from_bucket, prediction.rs:70-84
+    std::vector<float> t(10 * 1024);
+    for (int b = 0; b < 10; b++)
+        for (uint32_t j = 0; j < 1024; j++) {
+            const float x = (float)((j & 1u) ? (int32_t)(j + 1) / -2 : (int32_t)(j / 2)); // unpack_signed, utils.rs:42-48
+            t[b * 1024 + j] = std::exp(-std::fabs(x - 0.0f) / width[b]) / (2.0f * width[b]);
+        }
+    return t;
+}
+// the container around the rANS data (serialize.rs:40-117, host/emit.cpp serialize): "frif" + height + width + metadata word + EOI; per channel PRD +
+// 36 f32, DAT + u64 length, EOC, plus the estimate of the flush of the ten rANS states; per context EHD + u32 max_freq_bits + u64 n_off (+ 2 bytes per listed value)
+constexpr RateLayout kRateLayout = {16 + 2, (2 + 36 * 4) + (2 + 8) + 2 + 60, 2 + 4 + 8};
 
 int check_q(const int32_t q[32], QMatrix &out) {
     if (!q) return FRI_HIP_ERR_INVALID_ARGUMENT;
@@ -712,7 +734,7 @@ const char *fri_hip_strerror(int code) {
     case FRI_HIP_ERR_OUT_OF_MEMORY: return "out of device or pinned memory";
     case FRI_HIP_ERR_DIVIDE_BY_ZERO: return "quantisation matrix has a zero divisor";
     case FRI_HIP_ERR_EMPTY_LATTICE: return "no cell of the lattice touches the image";
-    case FRI_HIP_ERR_OUT_OF_RANGE: return "a Some coefficient lies outside [-256, 255]: the fit sums would overflow (the forward transform never produces one)";
+    case FRI_HIP_ERR_OUT_OF_RANGE: return "out of range: a Some coefficient outside [-256, 255] (the fit sums would overflow; the forward transform never produces one), or no quality fits the size budget";
     default: return "unknown error";
     }
 }
@@ -795,7 +817,7 @@ int fri_hip_plan_create(fri_hip_ctx *ctx, uint32_t width, uint32_t height, uint3
     if ((e = upload_tiling(bufs, g, d, false)) || (e = upload(bufs, g.centers, d.centers)) || (e = upload(bufs, g.interior, d.interior)) || (e = upload(bufs, g.valid_mask, d.valid_mask)) ||
         (e = upload(bufs, g.nbr_cells, d.nbr_cells)) || (e = upload(bufs, g.pred_slots, d.pred_slots)) || (e = upload(bufs, tab, d.nbr_table)) ||
         (e = upload(bufs, gather_off, d.gather_off)) || (e = upload(bufs, pair_pos, d.pair_pos)) || (e = upload(bufs, heap_of_pos, d.heap_of_pos)) ||
-        (e = upload(bufs, halo_list, d.halo_list)))
+        (e = upload(bufs, halo_list, d.halo_list)) || (e = upload(bufs, laplace_table(), p->laplace)))
         return fail_hip(ctx, e, "plan tables");
     if (!gi.inv_lists.empty()) {
         if ((e = upload(bufs, gi.inv_lists, d.inv_lists)) || (e = upload(bufs, gi.inv_quads, d.inv_quads, kInvListPad)) || (e = upload(bufs, gi.inv_dwords, d.inv_dwords, kInvListPad)) ||
@@ -1760,6 +1782,81 @@ int fri_hip_search_quality(fri_hip_plan *p, const uint8_t *pixels, double target
     if (int rc = grow(p->ctx, p->staging.pixels, fri_hip_plan_pixel_bytes(p))) return rc;
     HIP_TRY(p->ctx, hipMemcpy(p->staging.pixels, pixels, fri_hip_plan_pixel_bytes(p), hipMemcpyHostToDevice));
     return fri_hip_search_quality_dev(p, p->staging.pixels, target_db, quality, psnr_db, nullptr);
+}
+
+/* ---- lossy coding to a target size ---------------------------------------------------------------- */
+int fri_hip_estimate_size_dev(fri_hip_plan *p, uint32_t n_images, const uint32_t *d_hist, const uint64_t *d_n_out_of_alphabet, uint64_t *d_bytes, uint32_t *d_models,
+                              void *stream) {
+    if (int rc = need_device(p)) return rc;
+    if (!d_hist || !d_bytes || !n_images || (uint64_t)n_images * p->geo.channels > 65535u) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    HIP_TRY(p->ctx, hipSetDevice(p->ctx->device));
+    HIP_TRY(p->ctx, launch_rate_estimate(n_images, p->geo.channels, d_hist, reinterpret_cast<const unsigned long long *>(d_n_out_of_alphabet), p->laplace,
+                                         reinterpret_cast<unsigned long long *>(d_bytes), d_models, kRateLayout, (hipStream_t)stream));
+    return FRI_HIP_OK;
+}
+
+int fri_hip_estimate_size(fri_hip_plan *p, const uint32_t *hist, const uint64_t *n_out_of_alphabet, uint64_t *bytes) {
+    if (int rc = need_device(p)) return rc;
+    if (!hist || !bytes) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    fri_hip_ctx *c = p->ctx;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t C = p->geo.channels;
+    auto &st = p->staging;
+    int rc;
+    if ((rc = grow(c, st.hist, C * 10 * 1024)) || (rc = grow(c, st.oob, C)) || (rc = grow(c, st.rate, 1))) return rc;
+    HIP_TRY(c, hipMemcpy(st.hist, hist, C * 10 * 1024 * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (n_out_of_alphabet) HIP_TRY(c, hipMemcpy(st.oob, n_out_of_alphabet, C * sizeof(uint64_t), hipMemcpyHostToDevice));
+    if ((rc = fri_hip_estimate_size_dev(p, 1, st.hist, n_out_of_alphabet ? (const uint64_t *)st.oob.get() : nullptr, (uint64_t *)st.rate.get(), nullptr, nullptr)))
+        return rc;
+    HIP_TRY(c, hipMemcpy(bytes, st.rate, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return FRI_HIP_OK;
+}
+
+int fri_hip_search_quality_for_size_dev(fri_hip_plan *p, const uint8_t *d_pixels, uint64_t max_bytes, int32_t *quality, uint64_t *est_bytes, void *stream) {
+    if (!p || !d_pixels || !quality || !est_bytes || max_bytes == 0 || p->dev.rct) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    if (int rc = need_device(p)) return rc;
+    const hipStream_t s = (hipStream_t)stream;
+    if (int rc = refuse_capture(p, s, "fri_hip_search_quality_for_size_dev reads every probe back: it cannot be captured into a HIP graph")) return rc;
+    fri_hip_ctx *c = p->ctx;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t C = p->geo.channels;
+    auto &st = p->staging;
+    int rc;
+    if ((rc = grow(c, st.search_coefs, fri_hip_plan_coef_count(p))) || (rc = grow(c, st.search_hist, C * 10 * 1024)) || (rc = grow(c, st.search_oob, C)) ||
+        (rc = grow(c, st.search_params, C * 36)) || (rc = grow(c, st.rate, 1)))
+        return rc;
+    // a probe: the chain of fri_hip_encode_image_symbols at quality q (K1, the device-side fit, K2; the same histograms), then the rate kernel
+    auto probe = [&](int q, uint64_t &est) -> int {
+        int32_t qm[32];
+        fri_hip_quality_matrix(q, qm);
+        if (int r = fri_hip_encode_image_batch_dev(p, 1, d_pixels, 0, qm, 1, st.search_params, st.search_coefs, 0, nullptr, nullptr, 0, st.search_hist,
+                                                   (uint64_t *)st.search_oob.get(), nullptr, stream))
+            return r;
+        if (int r = fri_hip_estimate_size_dev(p, 1, st.search_hist, (const uint64_t *)st.search_oob.get(), (uint64_t *)st.rate.get(), nullptr, stream)) return r;
+        HIP_TRY(c, hipMemcpyAsync(&est, st.rate, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        return FRI_HIP_OK;
+    };
+    int lo = 0, hi = 101; // lo: fits (0 is never probed), hi: does not fit (101 is never probed)
+    uint64_t lo_est = 0, last = UINT64_MAX;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) / 2;
+        if ((rc = probe(mid, last))) return rc;
+        if (last != UINT64_MAX && last <= max_bytes) lo = mid, lo_est = last;
+        else hi = mid;
+    }
+    *quality = lo;
+    *est_bytes = lo ? lo_est : last; // nothing fits: the last probe was quality 1
+    return lo ? FRI_HIP_OK : FRI_HIP_ERR_OUT_OF_RANGE;
+}
+
+int fri_hip_search_quality_for_size(fri_hip_plan *p, const uint8_t *pixels, uint64_t max_bytes, int32_t *quality, uint64_t *est_bytes) {
+    if (!p || !pixels || !quality || !est_bytes || max_bytes == 0 || p->dev.rct) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    if (int rc = need_device(p)) return rc;
+    HIP_TRY(p->ctx, hipSetDevice(p->ctx->device));
+    if (int rc = grow(p->ctx, p->staging.pixels, fri_hip_plan_pixel_bytes(p))) return rc;
+    HIP_TRY(p->ctx, hipMemcpy(p->staging.pixels, pixels, fri_hip_plan_pixel_bytes(p), hipMemcpyHostToDevice));
+    return fri_hip_search_quality_for_size_dev(p, p->staging.pixels, max_bytes, quality, est_bytes, nullptr);
 }
 
 /* ---- timing helper ------------------------------------------------------------------------------ */

@@ -1,4 +1,5 @@
-// kernels.hpp -- launch interface between the C ABI (fri_hip.cpp) and the gfx950 kernels (k1_forward.hip, k2_predict.hip, k3_inverse.hip, k4_fit.hip).
+// kernels.hpp -- launch interface between the C ABI (fri_hip.cpp) and the gfx950 kernels (k1_forward.hip, k2_predict.hip, k3_inverse.hip, k4_fit.hip,
+// k5_stream.hip, k6_rate.hip).
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -145,6 +146,15 @@ hipError_t launch_symbol_gather(const uint32_t *order, uint64_t n_symbols, uint3
 // K5 from the three arrays of the scan's array form: out[k][i] = bucket << 10 | pack_signed(coef - prediction) of node order[i].
 hipError_t launch_symbol_stream(const uint32_t *order, uint64_t n_symbols, uint32_t n_planes, const int32_t *coefs, size_t coef_stride, const uint8_t *bucket,
                                 const int32_t *prediction, size_t out_stride, uint16_t *out, size_t stream_stride, hipStream_t stream);
+
+// K6 (k6_rate.hip): the estimated .frv size of n_images images from their histograms hist [n_images * channels][10][1024] (and out-of-alphabet counts
+// oob [n_images * channels], may be NULL) - bytes [n_images] (zeroed here first), UINT64_MAX where the emitter would refuse the image. laplace: [10][1024]
+// f32 exp(-|x| / w) / (2 w) of the emitter's shape; models (may be NULL): [n_images * channels][10][4] = {max_freq_bits, n_off, collapsed slots, status}.
+struct RateLayout {
+    uint32_t header_bytes, channel_bytes, context_bytes; // the container's bytes per image, per channel (with the rANS flush) and per context (without the list)
+};
+hipError_t launch_rate_estimate(uint32_t n_images, uint32_t channels, const uint32_t *hist, const unsigned long long *oob, const float *laplace,
+                                unsigned long long *bytes, uint32_t *models, const RateLayout &layout, hipStream_t stream);
 
 // K2's per-node neighbour offsets (LDS halfword offsets relative to the own slot, two per word) from the static neighbour table
 void build_lf_deltas(const uint16_t *nbr_table, int8_t *out /* [8] */);

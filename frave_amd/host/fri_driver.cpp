@@ -9,6 +9,8 @@
 //                                                            --rct: an RGB image is coded as Y, Cb, Cr of the reversible colour transform (flagged file);
 //                                                            --quality Q (1..99): lossy, quantised with fri_hip_quality_matrix(Q), the quality in the file;
 //                                                            --psnr DB: lossy at the lowest quality that reaches DB (fri_hip_search_quality); prints both
+//                                                            --size BYTES / --bpp B (BYTES = floor(B w h / 8)): the highest quality whose file is at most BYTES
+//                                                            (fri_hip_search_quality_for_size, then FRIEncoder::encode's check); prints quality, estimate, size
 //   fri_driver decode-file <in.frv> <out.pgm|.ppm|.bmp>     container -> rANS / context decoding on the host -> dequantisation + inverse
 //                                                            transform on the device (fri-cli decode, crates/fri-cli/src/commands/decode.rs); a flagged file
 //                                                            comes back as RGB, a lossy file with its quality's matrix and the midpoint dequantiser
@@ -158,6 +160,19 @@ static int encode_image_to_file(std::vector<uint8_t> img, uint32_t w, uint32_t h
         opts.quality = q < 100 ? q : 0;
         opts.target_psnr = 0;
     }
+    const uint64_t budget = opts.target_bytes;
+    if (budget) { // the quality FRIEncoder::encode settles on (search, then its file checked against the budget); then both routes code with it
+        libfri::FRIEncoder sized(opts);
+        auto st = sized.encode(img, h, w, cs);
+        if (!st.ok) {
+            std::fprintf(stderr, "size search: %s\n", st.error.c_str());
+            return 1;
+        }
+        opts.quality = (int)st.value.image.metadata.quality;
+        opts.target_bytes = 0;
+        std::printf("target %llu bytes: quality %d, estimate %llu bytes, file %llu bytes\n", (unsigned long long)budget, opts.quality ? opts.quality : 100,
+                    (unsigned long long)st.value.est_bytes, (unsigned long long)st.value.file_bytes);
+    }
     auto t0 = std::chrono::steady_clock::now();
     libfri::FRIEncoder streamed_encoder(opts);
     auto streamed = streamed_encoder.encode_bytes_streamed(img, h, w, cs);
@@ -229,6 +244,10 @@ static int encode_image_to_file(std::vector<uint8_t> img, uint32_t w, uint32_t h
     double sse = 0;
     for (size_t i = 0; i < img.size(); i++) sse += ((double)back.value.data[i] - img[i]) * ((double)back.value.data[i] - img[i]);
     const double psnr = sse > 0 ? 10.0 * std::log10(255.0 * 255.0 * (double)img.size() / sse) : HUGE_VAL;
+    if (budget && bytes.size() > budget) {
+        std::fprintf(stderr, "self-check failed: %zu bytes over the budget of %llu\n", bytes.size(), (unsigned long long)budget);
+        return 1;
+    }
     if (FILE *f = std::fopen(out_path, "wb")) {
         std::fwrite(bytes.data(), 1, bytes.size(), f);
         std::fclose(f);
@@ -252,11 +271,15 @@ int main(int argc, char **argv) {
             return 1;
         }
         libfri::EncoderOpts file_opts; // parameters are fitted on the device sums (fit_parameters defaults to true)
+        double bpp = 0;
+        bool has_size = false, has_bpp = false;
         for (int i = 4; i < argc; i++) {
             const std::string a = argv[i];
             if (a == "--rct") file_opts.colour_transform = true;
             else if (a == "--quality" && i + 1 < argc) file_opts.quality = std::atoi(argv[++i]);
             else if (a == "--psnr" && i + 1 < argc) file_opts.target_psnr = std::atof(argv[++i]);
+            else if (a == "--size" && i + 1 < argc) file_opts.target_bytes = std::strtoull(argv[++i], nullptr, 10), has_size = true;
+            else if (a == "--bpp" && i + 1 < argc) bpp = std::atof(argv[++i]), has_bpp = true;
             else {
                 std::fprintf(stderr, "encode-file: unknown option %s\n", a.c_str());
                 return 2;
@@ -265,6 +288,12 @@ int main(int argc, char **argv) {
         if (file_opts.quality < 0 || file_opts.quality > 99 || file_opts.target_psnr < 0 || (file_opts.quality && file_opts.target_psnr > 0) ||
             ((file_opts.quality || file_opts.target_psnr > 0) && file_opts.colour_transform)) {
             std::fprintf(stderr, "encode-file: --quality 1..99 or --psnr DB (> 0), not both, and neither with --rct\n");
+            return 2;
+        }
+        const bool sized = has_size || has_bpp;
+        if (has_bpp && bpp > 0) file_opts.target_bytes = (uint64_t)std::floor(bpp * fw * fh / 8.0);
+        if ((has_size && has_bpp) || (sized && !file_opts.target_bytes) || (sized && (file_opts.quality || file_opts.target_psnr > 0 || file_opts.colour_transform))) {
+            std::fprintf(stderr, "encode-file: --size BYTES (> 0) or --bpp B (> 0), not both, and neither with --quality, --psnr or --rct\n");
             return 2;
         }
         return encode_image_to_file(std::move(img), fw, fh, fc, file_opts, argv[3]);
@@ -305,7 +334,7 @@ int main(int argc, char **argv) {
         return 0;
     }
     if (argc < 5) {
-        std::fprintf(stderr, "usage: %s roundtrip|encode|batch|batch-frv <width> <height> <channels> [n_images | out.frv]\n       %s encode-file <in.pgm|in.ppm|in.bmp> <out.frv> [--rct | --quality Q | --psnr DB]\n       %s decode-file <in.frv> <out.pgm|out.ppm|out.bmp>\n", argv[0], argv[0], argv[0]);
+        std::fprintf(stderr, "usage: %s roundtrip|encode|batch|batch-frv <width> <height> <channels> [n_images | out.frv]\n       %s encode-file <in.pgm|in.ppm|in.bmp> <out.frv> [--rct | --quality Q | --psnr DB | --size BYTES | --bpp B]\n       %s decode-file <in.frv> <out.pgm|out.ppm|out.bmp>\n", argv[0], argv[0], argv[0]);
         return 2;
     }
     const std::string cmd = argv[1];

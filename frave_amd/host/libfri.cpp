@@ -66,6 +66,7 @@ std::string coding_matrix(const EncoderOpts &opts, std::array<int32_t, 32> &q) {
     if (!(opts.target_psnr >= 0)) return "target_psnr must be >= 0";
     if ((opts.quality || opts.target_psnr > 0) && opts.colour_transform) return "lossy coding (quality / target_psnr) cannot be combined with colour_transform";
     if (opts.quality && opts.target_psnr > 0) return "set quality or target_psnr, not both";
+    if (opts.target_bytes && (opts.quality || opts.target_psnr > 0 || opts.colour_transform)) return "target_bytes cannot be combined with quality, target_psnr or colour_transform";
     const bool ones = std::all_of(opts.quantization_matrix.begin(), opts.quantization_matrix.end(), [](int32_t v) { return v == 1; });
     if (opts.quality && !ones) return "set quality or a quantization_matrix, not both";
     q = opts.quantization_matrix;
@@ -257,6 +258,35 @@ Result<EncodedStages> FRIEncoder::encode(std::vector<uint8_t> data, uint32_t hei
     std::array<int32_t, 32> qm;
     if (const std::string e = coding_matrix(opts_, qm); !e.empty()) return fail(e);
     EncoderOpts coded = opts_;
+    if (opts_.target_bytes) { // the highest quality whose estimated file fits, searched on the device; 100 = lossless
+        int32_t q = 0;
+        uint64_t est = 0;
+        const int rc = fri_hip_search_quality_for_size(plan, data.data(), opts_.target_bytes, &q, &est);
+        if (rc == FRI_HIP_ERR_OUT_OF_RANGE) return fail("no quality fits in " + std::to_string(opts_.target_bytes) + " bytes (quality 1: about " + std::to_string(est) + ")");
+        if (rc != FRI_HIP_OK) return fail(dev.describe(rc));
+        // the estimate is a few bytes per channel off the coder's output: code at q, emit, and go one quality lower while the file is over
+        constexpr int kMaxSteps = 8;
+        EncoderOpts at = opts_;
+        at.target_bytes = 0;
+        for (int step = 0; step <= kMaxSteps && q >= 1; step++, q--) {
+            at.quality = q < 100 ? q : 0;
+            FRIEncoder inner(at);
+            Result<EncodedStages> st = inner.encode(data, height, width, colorspace);
+            if (!st.ok) return st;
+            auto comp = stages::entropy_coding::encode(st.value.image, st.value.contexts, inner.opts());
+            if (!comp.ok) return fail(comp.error);
+            const uint64_t size = stages::serialize::encode(comp.value).size();
+            if (size <= opts_.target_bytes) {
+                st.value.est_bytes = est, st.value.file_bytes = size;
+                const uint64_t target = opts_.target_bytes;
+                opts_ = inner.opts(); // the fitted parameters, as a plain encode leaves them; the options stay a size target
+                opts_.quality = 0, opts_.target_bytes = target;
+                return st;
+            }
+            est = 0; // (est_bytes is the estimate of the searched quality: a stepped-down result reports 0)
+        }
+        return fail("no file of at most " + std::to_string(opts_.target_bytes) + " bytes within " + std::to_string(kMaxSteps) + " qualities below the estimate's");
+    }
     if (opts_.target_psnr > 0) { // the lowest quality that reaches the target, searched on the device; 100 = lossless
         int32_t q = 100;
         double db = 0;
@@ -441,6 +471,7 @@ Result<std::vector<uint8_t>> FRIEncoder::encode_bytes_streamed(std::vector<uint8
     std::array<int32_t, 32> qm;
     if (const std::string e = coding_matrix(opts_, qm); !e.empty()) return fail(e);
     if (opts_.target_psnr > 0) return fail("target_psnr: FRIEncoder::encode only (search first, then pass the quality)");
+    if (opts_.target_bytes) return fail("target_bytes: FRIEncoder::encode only (search first, then pass the quality)");
     if (const std::string e = set_colour_transform(plan, md.rct, dev); !e.empty()) return fail(e);
     const uint64_t n = fri_hip_plan_num_some(plan);
     if (const std::string e = set_plan_stream_order(plan, dev); !e.empty()) return fail(e); // geometry only, once per plan (the plan is new here: Device lives for this call, as in encode())
@@ -485,8 +516,8 @@ Result<std::vector<std::vector<uint8_t>>> encode_batch_bytes(const std::vector<c
     const ImageMetadata md = coded_metadata(height, width, colorspace, opts);
     std::array<int32_t, 32> qm;
     if (!(r.error = coding_matrix(opts, qm)).empty()) return r;
-    if (opts.target_psnr > 0) {
-        r.error = "encode_batch_bytes: target_psnr is not supported (no per-image search); pass a quality";
+    if (opts.target_psnr > 0 || opts.target_bytes) {
+        r.error = "encode_batch_bytes: target_psnr / target_bytes are not supported (no per-image search); pass a quality";
         return r;
     }
     const uint32_t n_dev = (uint32_t)devices.size();

@@ -67,6 +67,10 @@ struct EncoderOpts { // encoder.rs:58-64
     // FRIEncoder::encode only: > 0 = search the lowest quality whose round trip reaches this PSNR in dB (fri_hip_search_quality) and code with it; a result of
     // 100 codes an ordinary lossless file. Not together with quality or colour_transform.
     double target_psnr = 0;
+    // FRIEncoder::encode only: > 0 = search the highest quality whose estimated file is at most this many bytes (fri_hip_search_quality_for_size), code with
+    // it and check the file the emitter writes: while it is over, one quality lower (a few steps at most; quality 1 over the budget is an error). A result
+    // of 100 codes an ordinary lossless file. Not together with quality, target_psnr or colour_transform.
+    uint64_t target_bytes = 0;
     EncoderOpts() { quantization_matrix.fill(1); }
 };
 
@@ -170,6 +174,7 @@ struct EncodedStages { // EncoderStage::EntropyEncoding(WaveletImage, [Vec<AnsCo
     WaveletImage image;
     std::array<std::vector<AnsContext>, 3> contexts;
     double psnr_db = 0; // with EncoderOpts::target_psnr: the PSNR of the chosen quality (image.metadata.quality; +inf for lossless)
+    uint64_t est_bytes = 0, file_bytes = 0; // with EncoderOpts::target_bytes: the estimate of the quality the search found (0 if the file needed a lower one), the file's size
 };
 
 class FRIEncoder { // encoder.rs:66-109

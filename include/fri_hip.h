@@ -54,7 +54,7 @@ extern "C" {
 #define FRI_HIP_ERR_OUT_OF_MEMORY (-4)
 #define FRI_HIP_ERR_DIVIDE_BY_ZERO (-5) /* a used qmatrix entry is 0 (Rust: division panic, quantization.rs:17) */
 #define FRI_HIP_ERR_EMPTY_LATTICE (-6)  /* no retained cell (Rust: index panic, wavelet_transform.rs:664) */
-#define FRI_HIP_ERR_OUT_OF_RANGE (-7)   /* fit sums: a Some coefficient outside [-256, 255] (see fri_hip_fit_value_sums) */
+#define FRI_HIP_ERR_OUT_OF_RANGE (-7)   /* fit sums: a Some coefficient outside [-256, 255] (see fri_hip_fit_value_sums); size search: no quality fits */
 
 typedef struct fri_hip_ctx fri_hip_ctx;
 typedef struct fri_hip_plan fri_hip_plan;
@@ -374,6 +374,36 @@ int fri_hip_measure_distortion_dev(fri_hip_plan *plan, const int32_t *d_coefs, c
  * The plan's dequantiser setting is left as it is. The host form stages the pixels through the plan's buffers. */
 int fri_hip_search_quality(fri_hip_plan *plan, const uint8_t *pixels, double target_db, int32_t *quality, double *psnr_db);
 int fri_hip_search_quality_dev(fri_hip_plan *plan, const uint8_t *d_pixels, double target_db, int32_t *quality, double *psnr_db, void *stream);
+/* ---- lossy coding to a target size --------------------------------------------------------------- */
+/* The size of the .frv file the emitter (include/fri_emit.h) writes from a set of histograms, without running the rANS coder. An encoder's ANS model of a
+ * context depends on the context's counts alone (AnsContext::finalize, entropy_coding.rs:82-159): the rate kernel rebuilds every model bit for bit - the
+ * Laplace shape (f32 values made on the host with libm's expf and uploaded with the plan), the off-distribution symbols, the normalisation with its
+ * collapsed-slot loop - and adds up the code length. Per image:
+ *     bytes = ceil((8 x container + sum of bits) / 8)
+ *     container = 18 + sum over channels (218 + sum over the ten contexts (14 + 2 n_off))
+ *     bits = sum over the used symbols s of a context of count[s] x (max_freq_bits - log2 freq[s] + (start[s] - (freq[s] - 1)(M - freq[s]) / (2 freq[s])) / B)
+ * with freq, start (the cdf) and max_freq_bits of the finished model, M = 2^max_freq_bits, B = 2^31 ln(2^32) ln 2: the ideal cost plus the average by
+ * which rans64 codes a symbol above or below it (tens of bytes per 4096^2 plane). 18 = header and EOI; 218 = PRD + 36 f32, DAT + u64 length, EOC and
+ * 60 bytes for the flush of the ten rANS states; 14 + 2 n_off = EHD, max_freq_bits, n_off and the off-distribution list. The container part is exact;
+ * the data part is within a few bytes per channel of the coder's.
+ * Each symbol's cost is rounded to 2^-16 bit and the sums are integers: a run gives the same bytes every time. UINT64_MAX where the emitter refuses the
+ * image: a context without symbols, an out-of-alphabet symbol, or a used symbol whose final frequency is 0.
+ * d_hist [n_images][C][10][1024] (the layout of fri_hip_encode_image_batch_dev), d_n_out_of_alphabet [n_images][C] (may be NULL: not looked at),
+ * d_bytes [n_images]; d_models (may be NULL): [n_images][C][10][4] uint32 = {max_freq_bits, n_off, collapsed used slots, status (0 ok, 1 no symbols,
+ * 2 a used symbol of frequency 0)} - the max_freq_bits and off-distribution count the file carries. Only enqueues (a memset and two kernels, one
+ * workgroup per (plane, context)): no read-back, capturable. The host form does one image (n_out_of_alphabet may be NULL) and synchronises. */
+int fri_hip_estimate_size_dev(fri_hip_plan *plan, uint32_t n_images, const uint32_t *d_hist, const uint64_t *d_n_out_of_alphabet, uint64_t *d_bytes, uint32_t *d_models,
+                              void *stream);
+int fri_hip_estimate_size(fri_hip_plan *plan, const uint32_t *hist, const uint64_t *n_out_of_alphabet, uint64_t *bytes);
+/* The highest quality whose file fits in max_bytes: fits(q) = the estimate of the histograms the chain of fri_hip_encode_image_symbols gives at
+ * fri_hip_quality_matrix(q) (with the fit) is not UINT64_MAX and at most max_bytes. Bisection: lo = 0, hi = 101; while hi - lo > 1: mid = (lo + hi) / 2,
+ * lo = mid if fits(mid), else hi = mid - at most 7 probes, 100 (lossless) reachable. Returns quality = lo and its estimate; when nothing fits,
+ * FRI_HIP_ERR_OUT_OF_RANGE with quality = 0 and est_bytes = the estimate of quality 1. The probes run on plan-owned buffers and read their estimate
+ * back: the call synchronises `stream` and refuses a capturing one. FRI_HIP_ERR_INVALID_ARGUMENT for max_bytes == 0 and on an RCT plan (as
+ * fri_hip_search_quality). The plan's dequantiser, colour transform and stream order are left as they are. The rate need not be monotone in the
+ * quality; the bisection is all that is promised. The host form stages the pixels through the plan's buffers. */
+int fri_hip_search_quality_for_size(fri_hip_plan *plan, const uint8_t *pixels, uint64_t max_bytes, int32_t *quality, uint64_t *est_bytes);
+int fri_hip_search_quality_for_size_dev(fri_hip_plan *plan, const uint8_t *d_pixels, uint64_t max_bytes, int32_t *quality, uint64_t *est_bytes, void *stream);
 /* Which colour transform the plan's forward and inverse entry points apply (the container's YCbCr colour space). FRI_HIP_COLOUR_NONE (default): the channels
  * are coded as they are. FRI_HIP_COLOUR_RCT (plans with C = 3 only): the reversible colour transform of JPEG-LS on interleaved R, G, B bytes, all arithmetic
  * mod 256 - lossless and 8 bit:
