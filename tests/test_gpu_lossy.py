@@ -6,12 +6,11 @@ import numpy as np
 import pytest
 
 from tests.common import gen_image
+from tests.oracle_ref import LAYER, midpoint
 
 pytestmark = pytest.mark.gpu
 NONE = -(2 ** 31)
 MIDPOINT = 2
-# heap index -> quantiser layer, floor(log2(i + 1))
-LAYER = np.floor(np.log2(np.arange(512) + 1)).astype(np.int64)
 
 
 @pytest.fixture(scope="module")
@@ -21,16 +20,6 @@ def ctx():
     c = fa.Context(0)
     yield c
     c.close()
-
-
-def midpoint(coefs, qm):
-    """FRI_HIP_DEQUANT_MIDPOINT in numpy: v q + (q - 1) / 2 (v > 0), v q - (q - 1) / 2 (v < 0), 0, None stays None; wrapping int32"""
-    v = np.asarray(coefs, np.int64)
-    q = np.asarray(qm, np.int64)[LAYER]
-    m, h = v * q, (q - 1) // 2
-    out = np.where(v > 0, m + h, np.where(v < 0, m - h, 0))
-    out = ((out + 2 ** 31) % 2 ** 32 - 2 ** 31).astype(np.int32)
-    return np.where(v == NONE, NONE, out).astype(np.int32)
 
 
 def _image(w, h, c, seed):

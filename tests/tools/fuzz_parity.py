@@ -1,5 +1,5 @@
-"""Random-shape parity sweep of K1 / K2 / K3 / K4 against the CPU oracle (GPU box). Complements tests/test_gpu_parity.py, whose
-shapes are fixed. usage: fuzz_parity.py [n_cases] [seed]"""
+"""Random-shape parity sweep of K1 / K2 / K3 / K4 against the CPU oracle (GPU box), and on about half the cases the lossy paths (colour transform,
+dequantisers, quality matrices, MEASURE). Complements tests/test_gpu_parity.py, whose shapes are fixed. usage: fuzz_parity.py [n_cases] [seed]"""
 import os
 import sys
 import time
@@ -11,12 +11,46 @@ import torch
 import frave_amd
 from oracle import fri_oracle as O
 from tests.common import gen_image, random_params
+from tests.oracle_ref import numpy_measure, oracle_coefficients, oracle_owned, oracle_raster
+
+
+def lossy_checks(ctx, img, w, h, c, rng):
+    """a colour transform (3 channels), a dequantiser and a quality drawn from rng: K1 against the oracle on rct(img), K3 against the oracle's raster of the
+    numpy-dequantised oracle coefficients, MEASURE against numpy's sums over that raster and the oracle's covered pixels. Returns the names of the mismatches."""
+    rct = c == 3 and rng.random() < 0.5
+    mode = int(rng.integers(0, 3))  # reference division, multiply, midpoint
+    quality = int(rng.integers(1, 100))
+    qm = frave_amd.quality_matrix(quality)
+    P = frave_amd.Plan(ctx, w, h, c)
+    if rct:
+        P.set_colour_transform(1)
+    P.set_dequantiser(mode)
+    tag = f"(rct={int(rct)} dequantiser={mode} quality={quality})"
+    msgs = []
+    want = oracle_coefficients(O, img, w, h, c, qm, rct)
+    if not np.array_equal(P.transform_quant(img, qm), want):
+        msgs.append("K1-lossy" + tag)
+    owned = oracle_owned(O, w, h, c)
+    recon = oracle_raster(O, want, qm, mode, w, h, c, rct, owned)
+    if not np.array_equal(P.inverse_transform(want, qm), recon):
+        msgs.append("K3-lossy" + tag)
+    d_px = torch.from_numpy(img.reshape(-1).copy()).cuda()
+    d_co = torch.from_numpy(want.reshape(-1).copy()).cuda()
+    d_out = torch.full((2 * c + 1,), 77, dtype=torch.int64, device="cuda")
+    P.measure_distortion_dev(d_co.data_ptr(), d_px.data_ptr(), d_out.data_ptr(), qm)
+    torch.cuda.synchronize()
+    if [int(x) for x in d_out.cpu().numpy().astype(np.uint64)] != numpy_measure(recon, img, owned, c):
+        msgs.append("MEASURE" + tag)
+    P.close()
+    return msgs
+
 
 def run(n_cases, seed, ctx=None):
     """n_cases random (shape, content, channel count, quantiser, parameters) cases; returns the number of mismatching ones."""
     rng = np.random.default_rng(seed)
+    lossy_rng = np.random.default_rng([seed, 1])  # the lossy checks draw from a stream of their own: the cases rng draws stay those of earlier sweeps
     ctx = ctx or frave_amd.Context(0)
-    bad = chains = 0
+    bad = chains = lossy = 0
     t0 = time.time()
     for case in range(n_cases):
         kind = ["noise", "smooth", "const"][int(rng.integers(0, 3))]
@@ -96,6 +130,9 @@ def run(n_cases, seed, ctx=None):
                             msgs.append(f"K5 ch{cc}")
             except frave_amd.api.FriHipError as e:
                 msgs.append(f"chain error {e}")
+        if lossy_rng.random() < 0.5:
+            lossy += 1
+            msgs += lossy_checks(ctx, img, w, h, c, lossy_rng)
         if msgs:
             bad += 1
             print(f"case {case}: {w}x{h}x{c} {kind} q={q[:10].tolist()}: MISMATCH in {msgs}", flush=True)
@@ -103,7 +140,7 @@ def run(n_cases, seed, ctx=None):
             print(f"... {case + 1} cases, {bad} mismatching, {time.time() - t0:.0f} s", flush=True)
         P.close()
         W.close()
-    print(f"{n_cases} cases ({chains} with the fitted chain and the symbol stream route), {bad} mismatching, {time.time() - t0:.0f} s")
+    print(f"{n_cases} cases ({chains} with the fitted chain and the symbol stream route, {lossy} with the lossy checks), {bad} mismatching, {time.time() - t0:.0f} s")
     return bad
 
 
