@@ -31,7 +31,7 @@ SYMBOLS = [
     "fri_hip_plan_set_dequantiser", "fri_hip_plan_tune_forward", "fri_hip_time_transform_quant_streams_dev",
     "fri_hip_plan_set_colour_transform", "fri_hip_quality_matrix", "fri_hip_measure_distortion_dev", "fri_hip_search_quality",
     "fri_hip_search_quality_dev", "fri_hip_estimate_size_dev", "fri_hip_estimate_size", "fri_hip_search_quality_for_size",
-    "fri_hip_search_quality_for_size_dev",
+    "fri_hip_search_quality_for_size_dev", "fri_hip_plan_predict_grid",
 ]
 COLOUR_NONE, COLOUR_RCT = 0, 1  # fri_hip_plan_set_colour_transform
 DEQUANT_REFERENCE, DEQUANT_MULTIPLY, DEQUANT_MIDPOINT = 0, 1, 2  # fri_hip_plan_set_dequantiser
@@ -126,6 +126,7 @@ def load_library():
     L.fri_hip_inverse_transform_dev.argtypes = [vp, vp, vp, vp, vp]
     L.fri_hip_plan_read_trace.argtypes = [vp, vp]
     L.fri_hip_plan_inverse_lists.argtypes = [vp, vp]
+    L.fri_hip_plan_predict_grid.argtypes = [vp, vp]
     L.fri_hip_time_transform_quant_dev.argtypes = [vp, u32, vp, sz, vp, vp, sz, u32, vp, C.POINTER(C.c_double)]
     L.fri_hip_time_transform_quant_streams_dev.argtypes = [vp, u32, vp, sz, vp, vp, sz, u32, u32, C.POINTER(C.c_double)]
     L.fri_hip_plan_tune_forward.argtypes = [vp, u32, C.c_char_p, sz]
@@ -488,6 +489,12 @@ class Plan:
         out = np.empty(8, np.int32)
         _check(load_library().fri_hip_plan_tiling(self._h, _p(out)), "fri_hip_plan_tiling")
         return dict(zip(("n_wg", "n_tiles", "lds_pitch", "lds_rows", "max_tile_cells", "band_rows", "cells_per_tile", "cells_per_wg"), (int(v) for v in out)))
+
+    def predict_grid(self):
+        """fri_hip_plan_predict_grid: the tiles K2 / K4 walk and the grid limits of their launchers (a host-only plan: the knobs, 0 where unset)."""
+        out = np.zeros(4, np.uint32)
+        _check(load_library().fri_hip_plan_predict_grid(self._h, _p(out)), "fri_hip_plan_predict_grid")
+        return dict(zip(("n_pred_tiles", "pred_blocks", "hist_blocks", "k4_older_eighths"), (int(v) for v in out)))
 
     def inverse_lists(self):
         out = np.zeros(5, np.uint64)

@@ -792,7 +792,10 @@ int fri_hip_plan_create(fri_hip_ctx *ctx, uint32_t width, uint32_t height, uint3
     } else {
         build_inverse_lists(p->geo, kInvListsMaxBytes);
     }
-    if (!ctx) { // a host-only plan: the tilings are all there is
+    if (!ctx) { // a host-only plan: the tilings are all there is, and the prediction grid is what the knobs pin (0: the device's default)
+        p->dev.n_pred_tiles = p->geo.n_pred_tiles;
+        p->dev.pred_blocks = (uint32_t)std::max(k.pred_blocks, 0), p->dev.hist_blocks = (uint32_t)std::max(k.hist_blocks, 0);
+        p->dev.k4_older_eighths = k.k4_older_eighths.value_or(0);
         *out = plan.release();
         return FRI_HIP_OK;
     }
@@ -924,6 +927,13 @@ int fri_hip_plan_tiling(const fri_hip_plan *p, int32_t out[8]) {
     if (!p || !out) return FRI_HIP_ERR_INVALID_ARGUMENT;
     const Geometry &g = p->geo;
     const int32_t v[8] = {(int32_t)g.wg_tiles.size() - 1, (int32_t)g.tiles.size(), g.lds_pitch, g.lds_rows, g.max_tile_cells, g.band_rows, g.cells_per_tile, g.cells_per_wg};
+    std::memcpy(out, v, sizeof(v));
+    return FRI_HIP_OK;
+}
+int fri_hip_plan_predict_grid(const fri_hip_plan *p, uint32_t out[4]) {
+    if (!p || !out) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    const DevicePlan &d = p->dev;
+    const uint32_t v[4] = {p->geo.n_pred_tiles, d.pred_blocks, d.hist_blocks, (uint32_t)d.k4_older_eighths};
     std::memcpy(out, v, sizeof(v));
     return FRI_HIP_OK;
 }

@@ -102,6 +102,10 @@ int fri_hip_plan_neighbour_table(const fri_hip_plan *plan, uint16_t *table);
  * cells per workgroup}: how the forward kernel decomposes the image (diagnostics / tuning; FRI_HIP_BAND_ROWS,
  * FRI_HIP_CELLS_PER_TILE, FRI_HIP_CELLS_PER_WG override the defaults at plan creation). */
 int fri_hip_plan_tiling(const fri_hip_plan *plan, int32_t out[8]);
+/* out[4] = {prediction tiles, K2 workgroups, K4 workgroups, K4 older workgroup's share in eighths}: the tiles the K2 / K4 kernels
+ * walk and the grid limits their launchers start from (FRI_HIP_PRED_BLOCKS, FRI_HIP_HIST_BLOCKS, FRI_HIP_K4_OLDER_EIGHTHS override
+ * the defaults at plan creation). A host-only plan has no device: out[1..3] are the knobs it was created under, 0 where none is set. */
+int fri_hip_plan_predict_grid(const fri_hip_plan *plan, uint32_t out[4]);
 /* The decomposition itself (any pointer may be NULL): tiles[n_tiles][6] = {x_lo, y_lo, width_px, n_rows, cell_begin,
  * cell_count}; tile_cells[F] = cell ids in tile order; wg_tiles[n_wg + 1] = tile range of each workgroup share. */
 int fri_hip_plan_tile_table(const fri_hip_plan *plan, int32_t *tiles, int32_t *tile_cells, int32_t *wg_tiles);

@@ -50,7 +50,8 @@ TILINGS = {
     "c_ni4": {"FRI_HIP_BAND_ROWS": "48", "FRI_HIP_CELLS_PER_TILE": "3"},  # RGB: NI 4, N 4
     "c_n6": {"FRI_HIP_BAND_ROWS": "16", "FRI_HIP_CELLS_PER_TILE": "4"},  # RGB: N 6
 }
-ALL_KNOBS = sorted(set(BASE_KNOBS) | {k for t in TILINGS.values() for k in t} | {"FRI_HIP_K3_SCAN", "FRI_HIP_K1_CACHED_STORES", "FRI_HIP_CELLS_PER_WG"})
+ALL_KNOBS = sorted(set(BASE_KNOBS) | {k for t in TILINGS.values() for k in t} | {"FRI_HIP_K3_SCAN", "FRI_HIP_K1_CACHED_STORES", "FRI_HIP_CELLS_PER_WG"}
+                  | {"FRI_HIP_PRED_BLOCKS", "FRI_HIP_HIST_BLOCKS", "FRI_HIP_K4_OLDER_EIGHTHS"})  # (the K2 / K4 grid knobs of tests/predict_cases.py)
 
 
 @dataclass

@@ -1,5 +1,6 @@
 """Plain references for K3 that involve no GPU code: the three dequantisers in numpy, the oracle's raster of dequantised coefficients (with the inverse
-colour transform on top), the pixels the oracle's cells cover, and the [2 C + 1] distortion sums of fri_hip_measure_distortion_dev."""
+colour transform on top), the pixels the oracle's cells cover, and the [2 C + 1] distortion sums of fri_hip_measure_distortion_dev; for K4 the fit's
+normal-equation sums over the oracle's neighbour values."""
 import numpy as np
 
 from tests.test_rct_host import inverse_rct
@@ -85,3 +86,40 @@ def numpy_measure(recon, ref, owned, c):
         ec = e[:, ch][own[:, ch]]
         out += [int((ec * ec).sum()), int(ec.max()) if ec.size else 0]
     return out + [int(own[:, 0].sum())]
+
+
+def _fit_groups():
+    """per heap node its layer group (level 8 -> 0, level 7 -> 1, levels 0-6 -> 2) and whether it is a row of the fit (heap nodes 0 and 1 are not)"""
+    p = np.arange(512)
+    level = np.floor(np.log2(np.maximum(p, 1))).astype(int)
+    return np.where(level == 8, 0, np.where(level == 7, 1, 2)), p >= 2
+
+
+def cpu_fit_sums(oracle, W, ch, value_params):
+    """the sums K4 accumulates for channel ch of the oracle Wavelet W: gram [3][7][7] and wtw [3][6][6] (exact int64), wtr [3][6] (float64)"""
+    co = W.coefficients()[ch].astype(np.int64)  # [F][512]
+    some = co != oracle.NONE
+    nv = W.neighbour_values(ch).astype(np.int64)  # [F][512][6]
+    g, fit_row = _fit_groups()
+    use = some & fit_row[None, :]
+    gram = np.zeros((3, 7, 7), np.int64)
+    wtw = np.zeros((3, 6, 6), np.int64)
+    wtr = np.zeros((3, 6), np.float64)
+    vp = np.asarray(value_params, np.float32)
+    for grp in range(3):
+        m = use & (g == grp)[None, :]
+        v = nv[m]  # [n][6]
+        val = co[m]
+        u = np.concatenate([v, val[:, None]], axis=1)
+        gram[grp] = u.T @ u
+        # f32 prediction, left to right, one rounding per op (prediction.rs:199-204 / nalgebra gemv)
+        vf = v.astype(np.float32)
+        pf = vf[:, 0] * vp[grp, 0]
+        for k in range(1, 6):
+            pf = (pf + vf[:, k] * vp[grp, k]).astype(np.float32)
+        res = np.abs(val.astype(np.float32) - pf).astype(np.float32)
+        w = np.stack([np.ones(len(v), np.int64), np.abs(v[:, 0] - v[:, 3]), np.abs(v[:, 1] - v[:, 2]), np.abs(v[:, 4] - v[:, 5]), np.abs(v[:, 1] - v[:, 5]),
+                      np.abs(v[:, 2] - v[:, 4])], axis=1)
+        wtw[grp] = w.T @ w
+        wtr[grp] = (w.astype(np.float64) * res.astype(np.float64)[:, None]).sum(0)
+    return gram, wtw, wtr

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from tests.common import KAT_VALUE_PARAMS, gen_image, random_params
+from tests.oracle_ref import cpu_fit_sums
 
 pytestmark = pytest.mark.gpu
 
@@ -25,35 +26,6 @@ def _groups():
     return g, p >= 2
 
 
-def _cpu_sums(oracle, W, ch, value_params):
-    co = W.coefficients()[ch].astype(np.int64)  # [F][512]
-    some = co != oracle.NONE
-    nv = W.neighbour_values(ch).astype(np.int64)  # [F][512][6]
-    g, fit_row = _groups()
-    use = some & fit_row[None, :]
-    gram = np.zeros((3, 7, 7), np.int64)
-    wtw = np.zeros((3, 6, 6), np.int64)
-    wtr = np.zeros((3, 6), np.float64)
-    vp = np.asarray(value_params, np.float32)
-    for grp in range(3):
-        m = use & (g == grp)[None, :]
-        v = nv[m]  # [n][6]
-        val = co[m]
-        u = np.concatenate([v, val[:, None]], axis=1)
-        gram[grp] = u.T @ u
-        # f32 prediction, left to right, one rounding per op (prediction.rs:199-204 / nalgebra gemv)
-        vf = v.astype(np.float32)
-        pf = vf[:, 0] * vp[grp, 0]
-        for k in range(1, 6):
-            pf = (pf + vf[:, k] * vp[grp, k]).astype(np.float32)
-        res = np.abs(val.astype(np.float32) - pf).astype(np.float32)
-        w = np.stack([np.ones(len(v), np.int64), np.abs(v[:, 0] - v[:, 3]), np.abs(v[:, 1] - v[:, 2]), np.abs(v[:, 4] - v[:, 5]), np.abs(v[:, 1] - v[:, 5]),
-                      np.abs(v[:, 2] - v[:, 4])], axis=1)
-        wtw[grp] = w.T @ w
-        wtr[grp] = (w.astype(np.float64) * res.astype(np.float64)[:, None]).sum(0)
-    return gram, wtw, wtr
-
-
 @pytest.mark.parametrize("shape", [(10, 10, 3), (100, 37, 3), (300, 200, 1), (512, 512, 3)])
 @pytest.mark.parametrize("kind", ["noise", "smooth"])
 def test_fit_sums_match_cpu(ctx, oracle, shape, kind):
@@ -66,7 +38,7 @@ def test_fit_sums_match_cpu(ctx, oracle, shape, kind):
     co = P.transform_quant(img)
     for ch in range(c):
         vp, _ = random_params(3 + ch, scale=0.2)
-        want_gram, want_wtw, want_wtr = _cpu_sums(oracle, W, ch, vp)
+        want_gram, want_wtw, want_wtr = cpu_fit_sums(oracle, W, ch, vp)
         gram = P.fit_value_sums(co, ch)
         assert np.array_equal(gram, want_gram)
         wtw, wtr, rows = P.fit_width_sums(co, ch, vp)
@@ -247,7 +219,7 @@ def test_fit_at_4096_against_the_oracle(ctx, oracle):
     co, vp, wp, b, p, hist, oob = P.encode_image(img, fit=True)
     assert np.array_equal(co, W.coefficients())
     iu7, iu6 = np.triu_indices(7), np.triu_indices(6)
-    want_gram, want_wtw, want_wtr = _cpu_sums(oracle, W, 0, vp[0])
+    want_gram, want_wtw, want_wtr = cpu_fit_sums(oracle, W, 0, vp[0])
     assert np.array_equal(P.fit_value_sums(co, 0), want_gram)
     assert np.array_equal(vp[0].view(np.uint32), fa.fit_value_params(np.stack([want_gram[g][iu7] for g in range(3)])).view(np.uint32))
     wtw, wtr, rows = P.fit_width_sums(co, 0, vp[0])

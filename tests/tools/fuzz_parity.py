@@ -1,5 +1,5 @@
 """Random-shape parity sweep of K1 / K2 / K3 / K4 against the CPU oracle (GPU box), and on about half the cases the lossy paths (colour transform,
-dequantisers, quality matrices, MEASURE). Complements tests/test_gpu_parity.py, whose shapes are fixed. usage: fuzz_parity.py [n_cases] [seed]"""
+dequantisers, quality matrices, MEASURE), and on about half K2 / K4 on a random pinned grid. Complements tests/test_gpu_parity.py, whose shapes are fixed. usage: fuzz_parity.py [n_cases] [seed]"""
 import os
 import sys
 import time
@@ -11,6 +11,7 @@ import torch
 import frave_amd
 from oracle import fri_oracle as O
 from tests.common import gen_image, random_params
+from tests.instance_cases import knobs
 from tests.oracle_ref import numpy_measure, oracle_coefficients, oracle_owned, oracle_raster
 
 
@@ -49,6 +50,7 @@ def run(n_cases, seed, ctx=None):
     """n_cases random (shape, content, channel count, quantiser, parameters) cases; returns the number of mismatching ones."""
     rng = np.random.default_rng(seed)
     lossy_rng = np.random.default_rng([seed, 1])  # the lossy checks draw from a stream of their own: the cases rng draws stay those of earlier sweeps
+    grid_rng = np.random.default_rng([seed, 2])  # and so do the K2 / K4 grid knobs
     ctx = ctx or frave_amd.Context(0)
     bad = chains = lossy = 0
     t0 = time.time()
@@ -64,8 +66,14 @@ def run(n_cases, seed, ctx=None):
             w, h = int(rng.integers(46, 1400)), int(rng.integers(46, 900))
         c = 1 if rng.random() < 0.5 else 3
         img = gen_image(kind, w, h, c, int(rng.integers(0, 1 << 30)))
+        grid = None
+        if grid_rng.random() < 0.5:  # about half the plans launch K2 / K4 on a pinned grid: other workgroup counts, tile walks and K4 splits
+            hist = int(grid_rng.integers(1, 40)) * (16 if grid_rng.random() < 0.5 else 1)
+            grid = {"FRI_HIP_TUNING": "1", "FRI_HIP_PRED_BLOCKS": str(int(grid_rng.integers(1, 300))), "FRI_HIP_HIST_BLOCKS": str(hist),
+                    "FRI_HIP_K4_OLDER_EIGHTHS": str(int(grid_rng.integers(0, 9)))}
         try:
-            P = frave_amd.Plan(ctx, w, h, c)
+            with knobs(grid):
+                P = frave_amd.Plan(ctx, w, h, c)
         except frave_amd.api.FriHipError as e:
             print(f"case {case}: {w}x{h}x{c}: plan error {e}")
             continue
@@ -135,7 +143,7 @@ def run(n_cases, seed, ctx=None):
             msgs += lossy_checks(ctx, img, w, h, c, lossy_rng)
         if msgs:
             bad += 1
-            print(f"case {case}: {w}x{h}x{c} {kind} q={q[:10].tolist()}: MISMATCH in {msgs}", flush=True)
+            print(f"case {case}: {w}x{h}x{c} {kind} q={q[:10].tolist()} grid={grid}: MISMATCH in {msgs}", flush=True)
         if (case + 1) % (10 if os.environ.get("FUZZ_LARGE") == "1" else 250) == 0:  # a sign of life for long runs (a silent command is taken to be hung after a few minutes)
             print(f"... {case + 1} cases, {bad} mismatching, {time.time() - t0:.0f} s", flush=True)
         P.close()
