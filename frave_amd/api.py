@@ -33,7 +33,7 @@ SYMBOLS = [
     "fri_hip_search_quality_dev", "fri_hip_estimate_size_dev", "fri_hip_estimate_size", "fri_hip_search_quality_for_size",
     "fri_hip_search_quality_for_size_dev", "fri_hip_plan_predict_grid",
 ]
-COLOUR_NONE, COLOUR_RCT = 0, 1  # fri_hip_plan_set_colour_transform
+COLOUR_NONE, COLOUR_RCT, COLOUR_YCBCR = 0, 1, 3  # fri_hip_plan_set_colour_transform (bit 0: chroma planes, bit 1: irreversible)
 DEQUANT_REFERENCE, DEQUANT_MULTIPLY, DEQUANT_MIDPOINT = 0, 1, 2  # fri_hip_plan_set_dequantiser
 
 
@@ -455,8 +455,9 @@ class Plan:
         return qual.value, est.value
 
     def set_colour_transform(self, mode):
-        """fri_hip_plan_set_colour_transform: COLOUR_NONE (default) or COLOUR_RCT (C = 3 plans): every forward entry point then codes the planes
-        (Y, Cb, Cr) = (G, B - G + 128, R - G + 128) mod 256 of the R, G, B pixels, and every inverse entry point writes R, G, B back."""
+        """fri_hip_plan_set_colour_transform: COLOUR_NONE (default), COLOUR_RCT or COLOUR_YCBCR (C = 3 plans): every forward entry point then codes the
+        planes (Y, Cb, Cr) of the R, G, B pixels - (G, B - G + 128, R - G + 128) mod 256 for the RCT, the JFIF transform in 16-bit fixed point for YCbCr (lossy,
+        include/fri_hip.h) - and every inverse entry point writes R, G, B back."""
         _check(load_library().fri_hip_plan_set_colour_transform(self._h, int(mode)), "fri_hip_plan_set_colour_transform")
         self.colour_transform = int(mode)
 

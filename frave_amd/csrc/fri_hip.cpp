@@ -903,8 +903,11 @@ int fri_hip_quality_matrix(int quality, int32_t qmatrix[32]) {
 }
 
 int fri_hip_plan_set_colour_transform(fri_hip_plan *p, int mode) {
-    if (!p || (mode != FRI_HIP_COLOUR_NONE && mode != FRI_HIP_COLOUR_RCT) || (mode == FRI_HIP_COLOUR_RCT && p->geo.channels != 3)) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    // bit 0: chroma planes, bit 1: irreversible (2 alone means nothing)
+    if (!p || (mode != FRI_HIP_COLOUR_NONE && mode != FRI_HIP_COLOUR_RCT && mode != FRI_HIP_COLOUR_YCBCR) || (mode != FRI_HIP_COLOUR_NONE && p->geo.channels != 3))
+        return FRI_HIP_ERR_INVALID_ARGUMENT;
     p->dev.rct = p->dev_inv.rct = mode == FRI_HIP_COLOUR_RCT;
+    p->dev.ycc = p->dev_inv.ycc = mode == FRI_HIP_COLOUR_YCBCR;
     return FRI_HIP_OK;
 }
 
@@ -1847,7 +1850,8 @@ int fri_hip_search_quality_for_size_dev(fri_hip_plan *p, const uint8_t *d_pixels
         HIP_TRY(c, hipStreamSynchronize(s));
         return FRI_HIP_OK;
     };
-    int lo = 0, hi = 101; // lo: fits (0 is never probed), hi: does not fit (101 is never probed)
+    // lo: fits (0 is never probed), hi: does not fit (never probed): 101, or 100 on a YCbCr plan, whose quality 100 is not lossless and has no file (fri_emit)
+    int lo = 0, hi = p->dev.ycc ? 100 : 101;
     uint64_t lo_est = 0, last = UINT64_MAX;
     while (hi - lo > 1) {
         const int mid = (lo + hi) / 2;

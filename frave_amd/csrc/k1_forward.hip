@@ -377,6 +377,48 @@ __device__ __forceinline__ void fetch_g_windows_item(int buf_off, const int (&rb
 // Per 16-bit half: (x - g + 128) mod 256 (Cb, Cr; the G plane keeps its values because its g is 128). x + 384 - g stays in [129, 639]: no borrow between the halves.
 __device__ __forceinline__ uint32_t rct_leaf(uint32_t x, uint32_t g) { return (x + 0x01800180u - g) & 0x00FF00FFu; }
 
+// YCbCr (fri_hip_plan_set_colour_transform(FRI_HIP_COLOUR_YCBCR)): every item reads the R byte of its pixels (item_addr), and the G and B windows come out of
+// the same ten dwords fetch_windows_rgb loads: window k starts at byte s + DELTA of its pair of dwords (s = its byte offset in the first one, DELTA = 1 for
+// G, 2 for B), i.e. in the next pair once s + DELTA > 3. d2 is the dword after the pair where fetch_windows_rgb loads one, else d1 again: the window bytes the
+// leaves use (item_window_bytes below) then never reach past d1 - every leaf's R, G and B bytes lie inside the row's loaded dwords.
+template <int DELTA>
+__device__ __forceinline__ uint32_t shifted_window(uint32_t d0, uint32_t d1, uint32_t d2, uint32_t s) {
+    return s + DELTA < 4u ? __builtin_amdgcn_alignbyte(d1, d0, s + DELTA) : __builtin_amdgcn_alignbyte(d2, d1, s + DELTA - 4u);
+}
+[[maybe_unused]] __device__ __forceinline__ void fetch_windows_ycc(int buf_off, const int (&rb)[3], uint32_t (&r)[7], uint32_t (&g)[7], uint32_t (&b)[7]) {
+    const uint32_t b0 = (uint32_t)(buf_off + rb[0]), b1 = (uint32_t)(buf_off + rb[1] - 3), b2 = (uint32_t)(buf_off + rb[2] - 3);
+    const LdsDwordPtr p0 = (LdsDwordPtr)(uintptr_t)(b0 & ~3u), p1 = (LdsDwordPtr)(uintptr_t)(b1 & ~3u), p2 = (LdsDwordPtr)(uintptr_t)(b2 & ~3u);
+    const uint32_t d00 = p0[0], d01 = p0[1], d02 = p0[2];
+    const uint32_t d10 = p1[0], d11 = p1[1], d12 = p1[2], d13 = p1[3];
+    const uint32_t d20 = p2[0], d21 = p2[1], d22 = p2[2];
+    const uint32_t s0 = b0 & 3u, s1 = b1 & 3u, s2 = b2 & 3u;
+    // (d0, d1, next) of the seven windows; the used bytes: w[1] byte 2, w[3] byte 2, w[4] byte 1, w[6] byte 2 stay inside (d0, d1) for DELTA <= 2
+    r[0] = __builtin_amdgcn_alignbyte(d01, d00, s0), g[0] = shifted_window<1>(d00, d01, d02, s0), b[0] = shifted_window<2>(d00, d01, d02, s0);
+    r[1] = __builtin_amdgcn_alignbyte(d02, d01, s0), g[1] = shifted_window<1>(d01, d02, d02, s0), b[1] = shifted_window<2>(d01, d02, d02, s0);
+    r[2] = __builtin_amdgcn_alignbyte(d11, d10, s1), g[2] = shifted_window<1>(d10, d11, d12, s1), b[2] = shifted_window<2>(d10, d11, d12, s1);
+    r[3] = __builtin_amdgcn_alignbyte(d12, d11, s1), g[3] = shifted_window<1>(d11, d12, d13, s1), b[3] = shifted_window<2>(d11, d12, d13, s1);
+    r[4] = __builtin_amdgcn_alignbyte(d13, d12, s1), g[4] = shifted_window<1>(d12, d13, d13, s1), b[4] = shifted_window<2>(d12, d13, d13, s1);
+    r[5] = __builtin_amdgcn_alignbyte(d21, d20, s2), g[5] = shifted_window<1>(d20, d21, d22, s2), b[5] = shifted_window<2>(d20, d21, d22, s2);
+    r[6] = __builtin_amdgcn_alignbyte(d22, d21, s2), g[6] = shifted_window<1>(d21, d22, d22, s2), b[6] = shifted_window<2>(d21, d22, d22, s2);
+}
+// The fixed-point weights of plane p (JFIF / BT.601 full range, libjpeg's 16-bit fixed point; part of the file format, include/fri_hip.h):
+// value = (kr R + kg G + kb B + bias) >> 16, in 0..255 for every R, G, B in 0..255.
+struct YccWeights {
+    int kr, kg, kb, bias;
+};
+[[maybe_unused]] __device__ __forceinline__ YccWeights ycc_weights(int plane) {
+    if (plane == 0) return {19595, 38470, 7471, 32768};
+    if (plane == 1) return {-11059, -21709, 32768, (128 << 16) + 32767};
+    return {32768, -27439, -5329, (128 << 16) + 32767};
+}
+// One packed leaf pair: R, G, B of item A in the low halves, of item B in the high halves -> plane values of A (weights wa) and B (wb), packed the same way.
+[[maybe_unused]] __device__ __forceinline__ uint32_t ycc_leaf(uint32_t r, uint32_t g, uint32_t b, const YccWeights &wa, const YccWeights &wb) {
+    // (24-bit multiplies: the weights fit 17 bits and the bytes 8; the sums stay inside int32)
+    const int va = (__mul24(wa.kr, (int)(r & 0xFFFFu)) + __mul24(wa.kg, (int)(g & 0xFFFFu)) + __mul24(wa.kb, (int)(b & 0xFFFFu)) + wa.bias) >> 16;
+    const int vb = (__mul24(wb.kr, (int)(r >> 16)) + __mul24(wb.kg, (int)(g >> 16)) + __mul24(wb.kb, (int)(b >> 16)) + wb.bias) >> 16;
+    return (uint32_t)va | ((uint32_t)vb << 16);
+}
+
 // {byte I of a, byte I of b} zero-extended into the two 16-bit halves.
 template <int I>
 __device__ __forceinline__ uint32_t pair_bytes(uint32_t a, uint32_t b) {
@@ -394,10 +436,11 @@ struct ItemAddr {
 // RCT: plane ch of the output is read from byte rct_source(ch) of the pixel: Y (plane 0) from G, Cb (plane 1) from B, Cr (plane 2) from R.
 __device__ __forceinline__ int rct_source(int ch) { return ch == 2 ? 0 : ch + 1; }
 
-template <int C, bool FAST, bool RCT = false>
+// YCC: every plane reads the R byte (fetch_windows_ycc finds G and B next to it).
+template <int C, bool FAST, bool RCT = false, bool YCC = false>
 __device__ __forceinline__ ItemAddr item_addr(const FwdArgs &a, const Tile &t, const TileCell *meta, int it, int ldx, int ldy, int lane_rb, int buf_off,
                                                uint32_t sh_base, uint32_t wc16) {
-    const int cl = it / C, plane = it - cl * C, ch = RCT ? rct_source(plane) : plane; // ch: the byte of the pixel the item reads
+    const int cl = it / C, plane = it - cl * C, ch = YCC ? 0 : RCT ? rct_source(plane) : plane; // ch: the byte of the pixel the item reads
     const TileCell m = meta[cl];
     ItemAddr r;
     r.elem_off = ((uint32_t)plane * a.F + (uint32_t)__builtin_amdgcn_readfirstlane(m.cell)) * kCell;
@@ -438,7 +481,9 @@ __device__ __forceinline__ ItemAddr item_addr(const FwdArgs &a, const Tile &t, c
 // RCT (C = 3 only): the kernel codes the planes (Y, Cb, Cr) = (G, B - G + 128, R - G + 128) mod 256 of the reversible colour transform
 // (fri_hip_plan_set_colour_transform) as channels 0, 1, 2: the items of plane 0 read the G bytes, those of planes 1 and 2 the B and R bytes, whose leaves are
 // then replaced by their difference to the G byte of the same pixel before the transform.
-template <int C, bool EDGE, bool FAST, int NCH, bool QID, bool NT, bool MEASURE = false, bool C16 = false, bool RCT = false>
+// YCC (C = 3 only, not with RCT): the kernel codes the planes (Y, Cb, Cr) of the irreversible JFIF transform (ycc_weights) as channels 0, 1, 2: every item
+// reads the R, G and B bytes of its leaves and forms its plane's value from them before the transform. Compiled in k1_ycbcr.hip (pick_forward_ycbcr).
+template <int C, bool EDGE, bool FAST, int NCH, bool QID, bool NT, bool MEASURE = false, bool C16 = false, bool RCT = false, bool YCC = false>
 __global__ void __launch_bounds__(kFwdThreads) fwd_transform_quant_kernel(const FwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     if (ablate_flags(a.ablate) & 8) return; // timing only: what dispatching the grid alone costs
@@ -514,8 +559,8 @@ __global__ void __launch_bounds__(kFwdThreads) fwd_transform_quant_kernel(const 
             valid[c] = 0xFFFFFFFFu;
             if (itA < n_items) {
                 const int itB = itA + 1 < n_items ? itA + 1 : itA; // odd tail: item B mirrors A and is not stored
-                const ItemAddr A = item_addr<C, FAST, RCT>(a, t, meta, itA, ldx, ldy, lane_rb, buf_off, sh_base, wc16);
-                const ItemAddr B = item_addr<C, FAST, RCT>(a, t, meta, itB, ldx, ldy, lane_rb, buf_off, sh_base, wc16);
+                const ItemAddr A = item_addr<C, FAST, RCT, YCC>(a, t, meta, itA, ldx, ldy, lane_rb, buf_off, sh_base, wc16);
+                const ItemAddr B = item_addr<C, FAST, RCT, YCC>(a, t, meta, itB, ldx, ldy, lane_rb, buf_off, sh_base, wc16);
                 offA[c] = A.elem_off;
                 offB[c] = B.elem_off;
                 uint32_t leaf[8];
@@ -539,6 +584,26 @@ __global__ void __launch_bounds__(kFwdThreads) fwd_transform_quant_kernel(const 
                     leaf[5] = pair_bytes<3>(wA[1], wB[1]);
                     leaf[6] = pair_bytes<2>(wA[1], wB[1]);
                     leaf[7] = pair_bytes<2>(wA[2], wB[2]);
+                } else if constexpr (YCC) { // (the leaf layout of the branch below, three windows per leaf; the mask after the conversion: leaves outside the image enter as 0)
+                    uint32_t rA[7], gA[7], bA[7], rB[7], gB[7], bB[7];
+                    fetch_windows_ycc(buf_off, A.rb, rA, gA, bA);
+                    fetch_windows_ycc(buf_off, B.rb, rB, gB, bB);
+                    const YccWeights kA = ycc_weights(itA % 3), kB = ycc_weights(itB % 3);
+                    leaf[0] = ycc_leaf(pair_bytes<0>(rA[0], rB[0]), pair_bytes<0>(gA[0], gB[0]), pair_bytes<0>(bA[0], bB[0]), kA, kB);
+                    leaf[4] = ycc_leaf(pair_bytes<2>(rA[1], rB[1]), pair_bytes<2>(gA[1], gB[1]), pair_bytes<2>(bA[1], bB[1]), kA, kB);
+                    leaf[2] = ycc_leaf(pair_bytes<0>(rA[2], rB[2]), pair_bytes<0>(gA[2], gB[2]), pair_bytes<0>(bA[2], bB[2]), kA, kB);
+                    leaf[1] = ycc_leaf(pair_bytes<3>(rA[2], rB[2]), pair_bytes<3>(gA[2], gB[2]), pair_bytes<3>(bA[2], bB[2]), kA, kB);
+                    leaf[6] = ycc_leaf(pair_bytes<2>(rA[3], rB[3]), pair_bytes<2>(gA[3], gB[3]), pair_bytes<2>(bA[3], bB[3]), kA, kB);
+                    leaf[5] = ycc_leaf(pair_bytes<1>(rA[4], rB[4]), pair_bytes<1>(gA[4], gB[4]), pair_bytes<1>(bA[4], bB[4]), kA, kB);
+                    leaf[3] = ycc_leaf(pair_bytes<0>(rA[5], rB[5]), pair_bytes<0>(gA[5], gB[5]), pair_bytes<0>(bA[5], bB[5]), kA, kB);
+                    leaf[7] = ycc_leaf(pair_bytes<2>(rA[6], rB[6]), pair_bytes<2>(gA[6], gB[6]), pair_bytes<2>(bA[6], bB[6]), kA, kB);
+                    if ((A.leaf_mask & B.leaf_mask) != 0xFFu) {
+#pragma unroll
+                        for (int j = 0; j < 8; j++) {
+                            if (!((A.leaf_mask >> j) & 1u)) leaf[j] &= 0xFFFF0000u;
+                            if (!((B.leaf_mask >> j) & 1u)) leaf[j] &= 0x0000FFFFu;
+                        }
+                    }
                 } else {
                     // window byte of leaf j: row 0: leaf0 -> w[0] byte 0, leaf4 -> w[1] byte 2; row 1: leaf2 -> w[2] byte 0, leaf1 -> w[2] byte 3,
                     // leaf6 -> w[3] byte 2, leaf5 -> w[4] byte 1; row 2: leaf3 -> w[5] byte 0, leaf7 -> w[6] byte 2
@@ -621,6 +686,11 @@ __global__ void __launch_bounds__(kFwdThreads) fwd_transform_quant_kernel(const 
 
 } // namespace
 
+// The YCbCr instances live in k1_ycbcr.hip, which compiles this file's kernel again: a module of their own leaves the register allocation, and so the
+// instructions, of the instances above as they were (see k3_lossy.hip). The kernel for the launch's axes, as launch_fwd_transform_quant picks them.
+const void *pick_forward_ycbcr(bool edge, bool fast, bool small, bool qid, bool plain, bool measure, bool c16);
+#ifndef FRI_K1_YCBCR_INSTANCES
+
 static size_t fwd_meta_offset(const DevicePlan &p) { return ((size_t)p.lds_pitch * p.lds_rows + 15) & ~(size_t)15; }
 static size_t fwd_buf_bytes(const DevicePlan &p) { return fwd_meta_offset(p) + (size_t)p.max_tile_cells * sizeof(TileCell); }
 size_t fwd_lds_bytes(const DevicePlan &p) { return 2 * fwd_buf_bytes(p) + 16 * kFwdThreads + (size_t)p.max_wg_tiles * sizeof(Tile); }
@@ -678,6 +748,7 @@ hipError_t launch_fwd_transform_quant(const DevicePlan &p, uint32_t n_images, co
     const bool fast = !edge && (((size_t)p.width * p.channels) & 15) == 0; // every image row starts at the same offset mod 16
     const bool small = fwd_chunks(p) <= 4 * (size_t)kFwdThreads;           // 4 chunks per thread suffice (the common, tuned case)
     const bool rct = p.rct && p.channels == 3; // (fri_hip_plan_set_colour_transform refuses RCT on other plans)
+    const bool ycc = p.ycc && p.channels == 3;  // (and YCbCr)
     void (*kern)(FwdArgs);
 #define FRI_PICK_T(CH, E, FA, N, QI, R) (plain ? fwd_transform_quant_kernel<CH, E, FA, N, QI, false, false, false, R> : fwd_transform_quant_kernel<CH, E, FA, N, QI, true, false, false, R>)
 #define FRI_PICK_Q(CH, E, FA, N, R) (a.q_identity ? FRI_PICK_T(CH, E, FA, N, true, R) : FRI_PICK_T(CH, E, FA, N, false, R))
@@ -703,6 +774,7 @@ hipError_t launch_fwd_transform_quant(const DevicePlan &p, uint32_t n_images, co
 #undef FRI_PICK_N
 #undef FRI_PICK_Q
 #undef FRI_PICK_T
+    if (ycc) kern = reinterpret_cast<void (*)(FwdArgs)>(const_cast<void *>(pick_forward_ycbcr(edge, fast, small, a.q_identity != 0, plain, p.k1_measuring && !edge && !plain && a.q_identity, coefs16 != nullptr)));
     if (lds > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
@@ -711,5 +783,6 @@ hipError_t launch_fwd_transform_quant(const DevicePlan &p, uint32_t n_images, co
     hipLaunchKernelGGL(kern, grid, block, lds, stream, a);
     return hipGetLastError();
 }
+#endif // FRI_K1_YCBCR_INSTANCES
 
 } // namespace fri

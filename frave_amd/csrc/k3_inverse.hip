@@ -242,6 +242,52 @@ __device__ __forceinline__ void rct_inverse_rect8(uint8_t *img, const Tile &t, i
     }
 }
 
+// ---- YCbCr (fri_hip_plan_set_colour_transform(FRI_HIP_COLOUR_YCBCR)): the items of plane p write byte p of their pixels as without a colour transform, so the
+// complete rectangle holds the clamped (Y, Cb, Cr) of every pixel its cells own; one in-place pass per pixel then turns them into (R, G, B) with the inverse
+// JFIF transform (include/fri_hip.h), before the write-out. A pixel's three channels belong to the same cell, so one thread converts each pixel whole.
+[[maybe_unused]] __device__ __forceinline__ int clamp255(int v) { return min(max(v, 0), 255); }
+[[maybe_unused]] __device__ __forceinline__ void ycc_to_rgb(int y, int cb, int cr, int &r, int &g, int &b) {
+    const int db = cb - 128, dr = cr - 128; // (24-bit multiplies: the weights fit 18 bits, db and dr 8 bits plus sign)
+    r = clamp255(y + ((__mul24(91881, dr) + 32768) >> 16));
+    g = clamp255(y + ((__mul24(-22554, db) + __mul24(-46802, dr) + 32768) >> 16));
+    b = clamp255(y + ((__mul24(116130, db) + 32768) >> 16));
+}
+// Scanning kernel (16 bit per byte, ownership in bit 8): a pixel no cell owns stays 0 (all three of its channels are unowned).
+[[maybe_unused]] __device__ __forceinline__ void ycc_inverse_rect16(uint16_t *img16, const Tile &t, int pitch16, uint32_t base_lo, uint32_t wc, int tid) {
+    const int n_px = t.n_rows * t.width_px;
+    const float inv_w = 1.0f / (float)t.width_px;
+    for (int q = tid; q < n_px; q += kInvThreads) {
+        int r = (int)(((float)q + 0.5f) * inv_w), i = q - r * t.width_px;
+        if (i < 0) r--, i += t.width_px; // (the float quotient may be off by one for large q)
+        else if (i >= t.width_px) r++, i -= t.width_px;
+        const uint32_t g = (uint32_t)(t.y_lo + r) * wc + (uint32_t)(t.x_lo * 3); // byte offset of the staged row (only bits 0-3 matter)
+        uint16_t *px = img16 + r * pitch16 + (int)((base_lo + g) & 15u) + 3 * i;
+        const uint32_t y = px[0];
+        if (y & 0x100u) {
+            int R, G, B;
+            ycc_to_rgb((int)(y & 0xFFu), (int)(px[1] & 0xFFu), (int)(px[2] & 0xFFu), R, G, B);
+            px[0] = (uint16_t)(0x100 | R);
+            px[1] = (uint16_t)(0x100 | G);
+            px[2] = (uint16_t)(0x100 | B);
+        }
+    }
+}
+// Lists kernel (one byte per byte, staged rows start at image byte column a0): pixel i of the tile's row r sits at byte 3 (x_lo + i) - a0 of the staged row.
+// Bytes of pixels the tile does not own are converted too and never written out.
+[[maybe_unused]] __device__ __forceinline__ void ycc_inverse_rect8(uint8_t *img, const Tile &t, int pitch, int a0, int tid) {
+    const int n_px = t.n_rows * t.width_px;
+    const float inv_w = 1.0f / (float)t.width_px;
+    for (int q = tid; q < n_px; q += kInvThreads) {
+        int r = (int)(((float)q + 0.5f) * inv_w), i = q - r * t.width_px;
+        if (i < 0) r--, i += t.width_px;
+        else if (i >= t.width_px) r++, i -= t.width_px;
+        uint8_t *px = img + r * pitch + 3 * (t.x_lo + i) - a0;
+        int R, G, B;
+        ycc_to_rgb(px[0], px[1], px[2], R, G, B);
+        px[0] = (uint8_t)R, px[1] = (uint8_t)G, px[2] = (uint8_t)B;
+    }
+}
+
 // ---- MEASURE (fri_hip_measure_distortion_dev): where a K3 instance stores a byte, its MEASURE twin loads the same byte of the reference image (a.pixels) and
 // accumulates, per channel, the squared and the largest absolute difference, and the number of owned pixels (bytes of channel 0). Nothing is written but the
 // workgroup's totals: a wave reduction, then one 64-bit add and one 32-bit max per channel (and one add of the pixel count) per workgroup - exact integers,
@@ -324,8 +370,8 @@ constexpr int kMeasureLds = kInvWaves * (4 * 8 + 3 * 4);
     }
 }
 
-// MID: the midpoint dequantiser (dequant_ref). MEASURE: see MeasureAcc.
-template <int NI, bool RCT = false, bool MID = false, bool MEASURE = false>
+// MID: the midpoint dequantiser (dequant_ref). MEASURE: see MeasureAcc. YCC: see ycc_inverse_rect16 (compiled in k3_ycbcr.hip).
+template <int NI, bool RCT = false, bool MID = false, bool MEASURE = false, bool YCC = false>
 __global__ void __launch_bounds__(kInvThreads) inverse_transform_kernel(const InvArgs a) {
     // this image of the batch (grid.y). Scalars, not a modified copy of the argument struct: a copy would live in scratch memory
     // (the quantiser array inside is indexed dynamically) and every argument access with it.
@@ -413,6 +459,10 @@ __global__ void __launch_bounds__(kInvThreads) inverse_transform_kernel(const In
         lds_barrier(); // the rectangle is complete
         if constexpr (RCT) {
             rct_inverse_rect16(img16, t, pitch16, base_lo, wc, tid);
+            lds_barrier();
+        }
+        if constexpr (YCC) {
+            ycc_inverse_rect16(img16, t, pitch16, base_lo, wc, tid);
             lds_barrier();
         }
 
@@ -507,7 +557,7 @@ __global__ void __launch_bounds__(kInvThreads) inverse_transform_kernel(const In
 // width * channels multiples of 16): the launcher falls back to inverse_transform_kernel otherwise.
 constexpr int kInvListPre = 3; // list entries a thread holds in flight per list and tile (more are loaded on demand)
 static_assert((size_t)kInvListPre * kInvThreads <= kInvListPad, "the lists' pad covers a thread's unconditional loads");
-template <int NI, bool RCT = false, bool MID = false, bool MEASURE = false>
+template <int NI, bool RCT = false, bool MID = false, bool MEASURE = false, bool YCC = false>
 __global__ void __launch_bounds__(kInvThreads) inverse_transform_lists_kernel(const InvArgs a) {
     const int32_t *const img_coefs = a.coefs + blockIdx.y * a.coef_stride; // this image of the batch, see inverse_transform_kernel
     uint8_t *const img_pixels = a.pixels + blockIdx.y * a.pixel_stride;
@@ -630,6 +680,10 @@ __global__ void __launch_bounds__(kInvThreads) inverse_transform_lists_kernel(co
             rct_inverse_rect8(img, t, pitch, a0, tid);
             lds_barrier();
         }
+        if constexpr (YCC) {
+            ycc_inverse_rect8(img, t, pitch, a0, tid);
+            lds_barrier();
+        }
         uint8_t *out0 = img_pixels + (size_t)t.y_lo * wc + (size_t)a0; // quad (r, k) -> out0 + r * wc + 16 k, 16-byte aligned
         // (a tile's rows x the image's row bytes stay far below 2^32, r < 256 and the row bytes below 2^24: 24-bit multiplies, a 32-bit offset on a uniform base)
         const uint32_t wc24 = (uint32_t)wc, pitch24 = (uint32_t)pitch;
@@ -682,17 +736,19 @@ __global__ void __launch_bounds__(kInvThreads) inverse_transform_lists_kernel(co
 } // namespace
 
 using InvKernel = void (*)(const InvArgs);
-template <bool RCT, bool MID, bool MEASURE>
+template <bool RCT, bool MID, bool MEASURE, bool YCC = false>
 static InvKernel pick_inverse(bool lists, int items_per_wave) {
     if (lists)
-        return items_per_wave <= 1 ? inverse_transform_lists_kernel<1, RCT, MID, MEASURE> : items_per_wave == 2 ? inverse_transform_lists_kernel<2, RCT, MID, MEASURE>
-                                                                                                                 : inverse_transform_lists_kernel<4, RCT, MID, MEASURE>;
-    return items_per_wave <= 1 ? inverse_transform_kernel<1, RCT, MID, MEASURE> : items_per_wave == 2 ? inverse_transform_kernel<2, RCT, MID, MEASURE>
-                                                                                                       : inverse_transform_kernel<4, RCT, MID, MEASURE>;
+        return items_per_wave <= 1 ? inverse_transform_lists_kernel<1, RCT, MID, MEASURE, YCC> : items_per_wave == 2 ? inverse_transform_lists_kernel<2, RCT, MID, MEASURE, YCC>
+                                                                                                                      : inverse_transform_lists_kernel<4, RCT, MID, MEASURE, YCC>;
+    return items_per_wave <= 1 ? inverse_transform_kernel<1, RCT, MID, MEASURE, YCC> : items_per_wave == 2 ? inverse_transform_kernel<2, RCT, MID, MEASURE, YCC>
+                                                                                                            : inverse_transform_kernel<4, RCT, MID, MEASURE, YCC>;
 }
 // The midpoint and measuring instances live in k3_lossy.hip, which compiles this file's kernels again: instantiated here, next to the reference and multiply
 // instances, they changed the register allocation of those (a module-level effect), which then no longer compiled to the instructions they had before.
+// The YCbCr instances (every dequantiser, measuring or not) live in k3_ycbcr.hip for the same reason.
 const void *pick_inverse_lossy(bool rct, bool lists, int items_per_wave, bool mid, bool measure);
+const void *pick_inverse_ycbcr(bool lists, int items_per_wave, bool mid, bool measure);
 #ifndef FRI_K3_LOSSY_INSTANCES
 
 // 16 bit per staged byte; a staged row holds <= lds_pitch bytes including its lead-in (lds_pitch >= widest row + 15).
@@ -714,7 +770,8 @@ bool inv_plan_fits(const DevicePlan &p, bool with_lists) {
 }
 
 // the kernel for a launch: the reference / multiply instances of this file, or the lossy ones of k3_lossy.hip
-static const void *pick_inverse(bool rct, bool lists, int items_per_wave, bool mid, bool measure) {
+static const void *pick_inverse(bool rct, bool ycc, bool lists, int items_per_wave, bool mid, bool measure) {
+    if (ycc) return pick_inverse_ycbcr(lists, items_per_wave, mid, measure);
     if (mid || measure) return pick_inverse_lossy(rct, lists, items_per_wave, mid, measure);
     return reinterpret_cast<const void *>(rct ? pick_inverse<true, false, false>(lists, items_per_wave) : pick_inverse<false, false, false>(lists, items_per_wave));
 }
@@ -757,6 +814,7 @@ hipError_t launch_inverse_transform(const DevicePlan &p, uint32_t n_images, cons
     a.queue_bytes = (int32_t)inv_queue_bytes(p);
     const int items_per_wave = (p.max_tile_cells * p.channels + kInvWaves - 1) / kInvWaves;
     const bool rct = p.rct && p.channels == 3; // (fri_hip_plan_set_colour_transform refuses RCT on other plans)
+    const bool ycc = p.ycc && p.channels == 3;  // (and YCbCr)
     const bool mid = p.k3_midpoint, meas = measure != nullptr;
     if (!inv_plan_fits(p, false)) return hipErrorInvalidConfiguration;
     // static write-out lists when every image row starts 16-byte aligned (and their rectangle fits: fri_hip_plan_create checks that for the tilings it builds)
@@ -770,7 +828,7 @@ hipError_t launch_inverse_transform(const DevicePlan &p, uint32_t n_images, cons
         a.rect_bytes = p.inv_rect_bytes;
         size_t lds2 = (size_t)p.inv_rect_bytes + (size_t)p.inv_max_wg_tiles * (sizeof(Tile) + sizeof(InvTileLists)) + (size_t)p.inv_max_wg_cells * sizeof(TileCell);
         if (meas) lds2 = std::max(lds2, (size_t)kMeasureLds);
-        const void *k2 = pick_inverse(rct, true, items_per_wave, mid, meas);
+        const void *k2 = pick_inverse(rct, ycc, true, items_per_wave, mid, meas);
         if (lds2 > 48 * 1024) {
             hipError_t e = hipFuncSetAttribute(k2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
             if (e != hipSuccess) return e;
@@ -781,7 +839,7 @@ hipError_t launch_inverse_transform(const DevicePlan &p, uint32_t n_images, cons
         return e != hipSuccess ? e : hipGetLastError();
     }
     const size_t lds = meas ? std::max(inv_lds_bytes(p), (size_t)kMeasureLds) : inv_lds_bytes(p);
-    const void *kern = pick_inverse(rct, false, items_per_wave, mid, meas);
+    const void *kern = pick_inverse(rct, ycc, false, items_per_wave, mid, meas);
     if (lds > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;

@@ -51,6 +51,7 @@ struct DevicePlan {
     int32_t k1_ablate = 0; // timing-only ablation flags, see FwdArgs::ablate
     int32_t k2_ablate = 0; // the same for K2, see PredArgs::ablate
     bool rct = false; // fri_hip_plan_set_colour_transform(FRI_HIP_COLOUR_RCT), C = 3 only: K1 codes (G, B - G + 128, R - G + 128), K3 undoes it
+    bool ycc = false; // fri_hip_plan_set_colour_transform(FRI_HIP_COLOUR_YCBCR), C = 3 only: K1 codes the JFIF Y, Cb, Cr of R, G, B, K3 turns them back (lossy)
     bool k3_multiply = false; // fri_hip_plan_set_dequantiser: the inverse kernel multiplies by the quantiser instead of reproducing the reference's division
     bool k3_midpoint = false; // fri_hip_plan_set_dequantiser(FRI_HIP_DEQUANT_MIDPOINT): ... or reconstructs the middle of the truncating quantiser's interval
     unsigned long long *trace = nullptr; // [n_wg][16] diagnostic timeline (FRI_HIP_TRACE=1), else null

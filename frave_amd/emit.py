@@ -9,6 +9,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_HERE, "libfri_emit.so")
 _lib = None
 RCT = 0x100  # FRI_EMIT_RCT: `channels = 3 | RCT` - the planes are Y, Cb, Cr of the reversible colour transform (include/fri_emit.h)
+YCBCR = 0x400  # FRI_EMIT_YCBCR: `channels = 3 | YCBCR | QUALITY(q)` - the planes are Y, Cb, Cr of the irreversible JFIF transform (lossy files only)
 
 
 def QUALITY(q):
@@ -16,8 +17,8 @@ def QUALITY(q):
     return int(q) << 16
 
 
-def _arg(channels, rct, quality):
-    return channels | (RCT if rct else 0) | QUALITY(quality or 0)
+def _arg(channels, rct, quality, ycbcr=False):
+    return channels | (RCT if rct else 0) | (YCBCR if ycbcr else 0) | QUALITY(quality or 0)
 
 
 class EmitError(RuntimeError):
@@ -83,10 +84,11 @@ def channel_symbols(centers, coefs, bucket, prediction):
     return sym[: n.value].copy(), bk[: n.value].copy()
 
 
-def encode_image(width, height, centers, coefs, bucket, prediction, hist, value_params, width_params, rct=False, quality=0):
+def encode_image(width, height, centers, coefs, bucket, prediction, hist, value_params, width_params, rct=False, quality=0, ycbcr=False):
     """.frv bytes. coefs/bucket/prediction [C][F][512], hist [C][10][1024], params [C][3][6]. rct: the three planes are Y, Cb, Cr of the reversible colour
     transform (Plan.set_colour_transform): the file says YCbCr and carries the flag. quality: 0 (lossless) or 1..99, the quality whose matrix
-    (frave_amd.quality_matrix) quantised the planes: the file records it."""
+    (frave_amd.quality_matrix) quantised the planes: the file records it. ycbcr: the planes are Y, Cb, Cr of the irreversible JFIF transform
+    (COLOUR_YCBCR); needs C = 3 and a quality, not with rct."""
     c = np.ascontiguousarray(centers, np.int32)
     co, b, p = np.ascontiguousarray(coefs, np.int32), np.ascontiguousarray(bucket, np.uint8), np.ascontiguousarray(prediction, np.int32)
     h = np.ascontiguousarray(hist, np.uint32)
@@ -99,7 +101,7 @@ def encode_image(width, height, centers, coefs, bucket, prediction, hist, value_
     # one call in the common case: a symbol costs at most max_freq_bits (< 32) bits, so 4 bytes per coefficient + the container
     # overhead always suffice; the library reports the needed size (-3) if they should not
     out = np.empty(co.size * 4 + channels * (10 * 2070 + 256) + 64, np.uint8)
-    arg = _arg(channels, rct, quality)
+    arg = _arg(channels, rct, quality, ycbcr)
     rc = L.fri_emit_encode_image(width, height, arg, _p(c), len(c), _p(co), _p(b), _p(p), _p(h), _p(vp), _p(wp), _p(out), out.size, C.addressof(n), err, 256)
     if rc == -3:
         out = np.empty(n.value, np.uint8)
@@ -121,9 +123,9 @@ def stream_order(centers, valid_mask):
     return out[: n.value].copy()
 
 
-def encode_image_from_streams(width, height, streams, hist, value_params, width_params, rct=False, quality=0):
+def encode_image_from_streams(width, height, streams, hist, value_params, width_params, rct=False, quality=0, ycbcr=False):
     """.frv bytes from the device's symbol streams: streams uint16 [C][n_symbols] (bucket << 10 | symbol), hist [C][10][1024], params [C][3][6].
-    rct, quality: see encode_image."""
+    rct, quality, ycbcr: see encode_image."""
     st = np.ascontiguousarray(streams, np.uint16)
     h = np.ascontiguousarray(hist, np.uint32)
     channels = h.size // 10240
@@ -133,21 +135,21 @@ def encode_image_from_streams(width, height, streams, hist, value_params, width_
     n = C.c_size_t(0)
     err = C.create_string_buffer(256)
     out = np.empty(st.size * 4 + channels * (10 * 2070 + 256) + 64, np.uint8)
-    rc = load_library().fri_emit_encode_image_from_streams(width, height, _arg(channels, rct, quality), _p(st), n_symbols, _p(h), _p(vp), _p(wp), _p(out), out.size, C.addressof(n), err, 256)
+    rc = load_library().fri_emit_encode_image_from_streams(width, height, _arg(channels, rct, quality, ycbcr), _p(st), n_symbols, _p(h), _p(vp), _p(wp), _p(out), out.size, C.addressof(n), err, 256)
     if rc != 0:
         raise EmitError(err.value.decode() or f"fri_emit_encode_image_from_streams: {rc}")
     return out[: n.value].tobytes()
 
 
-def check_image(frv, centers, coefs, bucket, prediction, rct=False, quality=0):
+def check_image(frv, centers, coefs, bucket, prediction, rct=False, quality=0, ycbcr=False):
     """Entropy-layer self-check: parse, rebuild the models from the container, decode every symbol, compare. Raises on mismatch (the colour transform
-    flag included)."""
+    flags and the quality included)."""
     c = np.ascontiguousarray(centers, np.int32)
     co, b, p = np.ascontiguousarray(coefs, np.int32), np.ascontiguousarray(bucket, np.uint8), np.ascontiguousarray(prediction, np.int32)
     data = np.frombuffer(frv, np.uint8)
     channels = co.size // (len(c) * 512)
     err = C.create_string_buffer(256)
-    rc = load_library().fri_emit_check_image(_p(data), data.size, _arg(channels, rct, quality), _p(c), len(c), _p(co), _p(b), _p(p), err, 256)
+    rc = load_library().fri_emit_check_image(_p(data), data.size, _arg(channels, rct, quality, ycbcr), _p(c), len(c), _p(co), _p(b), _p(p), err, 256)
     if rc != 0:
         raise EmitError(err.value.decode() or f"fri_emit_check_image: {rc}")
 
@@ -162,10 +164,12 @@ def rans_selfcheck(n_symbols, seed=1):
 
 class DecodedImage(tuple):
     """(width, height, channels, centers, coefs), and .rct: True if the planes are Y, Cb, Cr of the reversible colour transform; .quality: 0 for a
-    lossless file, else the quality 1..99 whose matrix quantised the planes (decode with the midpoint dequantiser)."""
+    lossless file, else the quality 1..99 whose matrix quantised the planes (decode with the midpoint dequantiser); .ycbcr: True if the planes are Y, Cb, Cr
+    of the irreversible JFIF transform (decode with COLOUR_YCBCR)."""
 
     rct = False
     quality = 0
+    ycbcr = False
 
 
 def decode_image(frv):
@@ -180,6 +184,7 @@ def decode_image(frv):
         raise EmitError(err.value.decode() or f"fri_emit_decode_image: {rc}")
     w, h, c, f = (int(x) for x in info)
     rct = bool(c & RCT)
+    ycbcr = bool(c & YCBCR)
     quality = (c >> 16) & 0x7F
     c &= 0xFF
     coefs = np.empty((c, f, 512), np.int32)
@@ -190,4 +195,5 @@ def decode_image(frv):
     out = DecodedImage((w, h, c, centers, coefs))
     out.rct = rct
     out.quality = quality
+    out.ycbcr = ycbcr
     return out

@@ -810,6 +810,7 @@ std::string decode_parsed(const ParsedImage &img, DecodedImage &out) {
     out.height = img.height, out.width = img.width, out.colorspace = img.colorspace, out.channels = channels, out.n_cells = (uint32_t)F;
     out.rct = img.rct;
     out.quality = img.quality;
+    out.ycbcr = img.ycbcr;
     out.centers.resize(F * 2);
     for (size_t c = 0; c < F; c++) out.centers[2 * c] = g.centers[c].x, out.centers[2 * c + 1] = g.centers[c].y;
     out.coefs.assign(channels * plane, 0);
@@ -845,12 +846,12 @@ constexpr uint8_t kEHD[2] = {0xFF, 0xB2}, kDAT[2] = {0xFF, 0xB4}, kEOC[2] = {0xF
 } // namespace
 
 std::vector<uint8_t> serialize(uint32_t height, uint32_t width, ColorSpaceCode cs, const std::vector<ChannelStream> &channels, const std::vector<ChannelParams> &params,
-                               bool rct, uint32_t quality) {
+                               bool rct, uint32_t quality, bool ycbcr) {
     std::vector<uint8_t> s;
     s.insert(s.end(), {'f', 'r', 'i', 'f'});
     put_u32(s, height);
     put_u32(s, width);
-    put_u32(s, (uint32_t)cs << 30 | 1u << 28 | (rct ? kMdatRct : 0u) | (quality & kMdatQualityMask) << kMdatQualityShift); // variant: TameTwindragon = 0b01 (images.rs:49-55)
+    put_u32(s, (uint32_t)cs << 30 | 1u << 28 | (rct ? kMdatRct : 0u) | (ycbcr ? kMdatYcbcr : 0u) | (quality & kMdatQualityMask) << kMdatQualityShift); // variant: TameTwindragon = 0b01 (images.rs:49-55)
     for (size_t ch = 0; ch < channels.size(); ch++) {
         s.insert(s.end(), kPRD, kPRD + 2);
         for (int g = 0; g < 3; g++)
@@ -894,9 +895,10 @@ std::string deserialize(const std::vector<uint8_t> &b, ParsedImage &out) {
     out.colorspace = mdat >> 30 & 3u;
     out.variant = mdat >> 28 & 3u;
     if (out.colorspace == 0 || out.variant == 0) return "Invalid metadata";
-    out.rct = out.colorspace == kYCbCr && (mdat & kMdatRct); // (bits 1..7 and 15..27 stay ignored)
+    out.rct = out.colorspace == kYCbCr && (mdat & kMdatRct); // (bits 2..7 and 15..27 stay ignored, and bit 1 outside YCbCr)
+    out.ycbcr = out.colorspace == kYCbCr && (mdat & kMdatYcbcr);
     out.quality = mdat >> kMdatQualityShift & kMdatQualityMask;
-    if (out.quality >= 100) return "Invalid metadata";
+    if (out.quality >= 100 || (out.ycbcr && (out.rct || out.quality == 0))) return "Invalid metadata";
     ChannelStream cur;
     ChannelParams prm{};
     int n_ctx = 0;

@@ -141,12 +141,16 @@ enum ColorSpaceCode : uint32_t { kLuma = 1, kRGB = 2, kYCbCr = 3 }; // images.rs
 constexpr uint32_t kMdatRct = 1u;
 // Bits 8..14 of the metadata word: the quality of a lossy file (fri_hip_quality_matrix), 0 = lossless; 100..127 are invalid. Also unread by the reference.
 constexpr uint32_t kMdatQualityShift = 8, kMdatQualityMask = 0x7Fu;
+// Bit 1 of the metadata word, with cs = kYCbCr: the planes are Y, Cb, Cr of the irreversible JFIF transform (FRI_HIP_COLOUR_YCBCR) - a lossy file only
+// (quality 1..99), never together with kMdatRct. Bit 1 of a Luma or RGB file stays ignored.
+constexpr uint32_t kMdatYcbcr = 2u;
 std::vector<uint8_t> serialize(uint32_t height, uint32_t width, ColorSpaceCode cs, const std::vector<ChannelStream> &channels,
-                               const std::vector<ChannelParams> &params, bool rct = false, uint32_t quality = 0);
+                               const std::vector<ChannelParams> &params, bool rct = false, uint32_t quality = 0, bool ycbcr = false);
 struct ParsedImage {
     uint32_t height = 0, width = 0, colorspace = 0, variant = 0;
     bool rct = false; // kYCbCr with kMdatRct set
     uint32_t quality = 0; // 0 = lossless, 1..99 (bits 8..14)
+    bool ycbcr = false; // kYCbCr with kMdatYcbcr set
     std::vector<ChannelStream> channels; // contexts rebuilt from (max_freq_bits, off_distribution_values) like serialize.rs:214-237
     std::vector<ChannelParams> params;
 };
@@ -163,6 +167,7 @@ struct DecodedImage {
     uint32_t height = 0, width = 0, colorspace = 0, channels = 0, n_cells = 0;
     bool rct = false; // the planes are Y, Cb, Cr of the reversible colour transform (ParsedImage::rct)
     uint32_t quality = 0; // ParsedImage::quality
+    bool ycbcr = false; // the planes are Y, Cb, Cr of the irreversible JFIF transform (ParsedImage::ycbcr)
     std::vector<int32_t> centers;     // [n_cells][2], canonical order (the one fri_hip_plan_centers reports)
     std::vector<int32_t> coefs;       // [channels][n_cells][512]: what fri_hip_inverse_transform takes
     std::vector<ChannelParams> params;

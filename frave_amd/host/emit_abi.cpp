@@ -13,13 +13,20 @@ int fail(char *err, size_t cap, const std::string &msg, int code = -1) {
     if (err && cap) std::snprintf(err, cap, "%s", msg.c_str());
     return code;
 }
-// `channels` of the encoders and the check: 1 or 3, with FRI_EMIT_RCT (3 only) or FRI_EMIT_QUALITY(1..99) (not both). False for anything else.
-bool split_channels(uint32_t arg, uint32_t &channels, bool &rct, uint32_t &quality) {
+// `channels` of the encoders and the check: 1 or 3, with FRI_EMIT_RCT (3 only) or FRI_EMIT_QUALITY(1..99) (not both); FRI_EMIT_YCBCR only as
+// 3 | FRI_EMIT_YCBCR | FRI_EMIT_QUALITY(1..99). False for anything else.
+bool split_channels(uint32_t arg, uint32_t &channels, bool &rct, uint32_t &quality, bool &ycbcr) {
     rct = (arg & FRI_EMIT_RCT) != 0;
+    ycbcr = (arg & FRI_EMIT_YCBCR) != 0;
     quality = FRI_EMIT_QUALITY_OF(arg);
-    channels = arg & ~(uint32_t)FRI_EMIT_RCT & ~FRI_EMIT_QUALITY(0x7Fu);
+    channels = arg & ~(uint32_t)FRI_EMIT_RCT & ~(uint32_t)FRI_EMIT_YCBCR & ~FRI_EMIT_QUALITY(0x7Fu);
     if (quality >= 100 || (quality && rct)) return false;
+    if (ycbcr && (channels != 3 || !quality)) return false;
     return channels == 3 || (channels == 1 && !rct);
+}
+ColorSpaceCode colour_space(uint32_t channels, bool rct, bool ycbcr) { return channels == 1 ? kLuma : rct || ycbcr ? kYCbCr : kRGB; }
+uint32_t channels_info(uint32_t channels, bool rct, uint32_t quality, bool ycbcr) {
+    return channels | (rct ? FRI_EMIT_RCT : 0u) | (ycbcr ? FRI_EMIT_YCBCR : 0u) | FRI_EMIT_QUALITY(quality);
 }
 } // namespace
 
@@ -77,9 +84,9 @@ int fri_emit_encode_image(uint32_t width, uint32_t height, uint32_t channels_arg
                           const uint8_t *bucket, const int32_t *prediction, const uint32_t *hist, const float *value_params, const float *width_params, uint8_t *out,
                           size_t cap, size_t *len, char *err, size_t err_cap) {
     uint32_t channels;
-    bool rct;
+    bool rct, ycbcr;
     uint32_t quality;
-    if (!centers_re_im || !coefs || !bucket || !prediction || !hist || !value_params || !width_params || !len || !split_channels(channels_arg, channels, rct, quality))
+    if (!centers_re_im || !coefs || !bucket || !prediction || !hist || !value_params || !width_params || !len || !split_channels(channels_arg, channels, rct, quality, ycbcr))
         return fail(err, err_cap, "invalid argument");
     std::vector<ChannelStream> streams;
     std::vector<ChannelParams> params(channels);
@@ -91,7 +98,7 @@ int fri_emit_encode_image(uint32_t width, uint32_t height, uint32_t channels_arg
         std::memcpy(params[ch].value, value_params + (size_t)ch * 18, sizeof(params[ch].value));
         std::memcpy(params[ch].width, width_params + (size_t)ch * 18, sizeof(params[ch].width));
     }
-    const std::vector<uint8_t> bytes = serialize(height, width, channels == 1 ? kLuma : rct ? kYCbCr : kRGB, streams, params, rct, quality);
+    const std::vector<uint8_t> bytes = serialize(height, width, colour_space(channels, rct, ycbcr), streams, params, rct, quality, ycbcr);
     *len = bytes.size();
     if (!out || cap < bytes.size()) return -3;
     std::memcpy(out, bytes.data(), bytes.size());
@@ -111,9 +118,9 @@ int fri_emit_stream_order(const int32_t *centers_re_im, uint32_t n_cells, const 
 int fri_emit_encode_image_from_streams(uint32_t width, uint32_t height, uint32_t channels_arg, const uint16_t *streams, uint64_t n_symbols, const uint32_t *hist,
                                        const float *value_params, const float *width_params, uint8_t *out, size_t cap, size_t *len, char *err, size_t err_cap) {
     uint32_t channels;
-    bool rct;
+    bool rct, ycbcr;
     uint32_t quality;
-    if (!streams || !hist || !value_params || !width_params || !len || !split_channels(channels_arg, channels, rct, quality)) return fail(err, err_cap, "invalid argument");
+    if (!streams || !hist || !value_params || !width_params || !len || !split_channels(channels_arg, channels, rct, quality, ycbcr)) return fail(err, err_cap, "invalid argument");
     std::vector<ChannelStream> chans;
     std::vector<ChannelParams> params(channels);
     const std::string e = encode_channels_from_streams(channels, streams, (size_t)n_symbols, hist, chans);
@@ -122,7 +129,7 @@ int fri_emit_encode_image_from_streams(uint32_t width, uint32_t height, uint32_t
         std::memcpy(params[ch].value, value_params + (size_t)ch * 18, sizeof(params[ch].value));
         std::memcpy(params[ch].width, width_params + (size_t)ch * 18, sizeof(params[ch].width));
     }
-    const std::vector<uint8_t> bytes = serialize(height, width, channels == 1 ? kLuma : rct ? kYCbCr : kRGB, chans, params, rct, quality);
+    const std::vector<uint8_t> bytes = serialize(height, width, colour_space(channels, rct, ycbcr), chans, params, rct, quality, ycbcr);
     *len = bytes.size();
     if (!out || cap < bytes.size()) return -3;
     std::memcpy(out, bytes.data(), bytes.size());
@@ -134,15 +141,16 @@ int fri_emit_encode_image_from_streams(uint32_t width, uint32_t height, uint32_t
 int fri_emit_check_image(const uint8_t *frv, size_t len, uint32_t channels_arg, const int32_t *centers_re_im, uint32_t n_cells, const int32_t *coefs,
                          const uint8_t *bucket, const int32_t *prediction, char *err, size_t err_cap) {
     uint32_t channels;
-    bool rct;
+    bool rct, ycbcr;
     uint32_t quality;
-    if (!frv || !centers_re_im || !coefs || !bucket || !prediction || !split_channels(channels_arg, channels, rct, quality)) return fail(err, err_cap, "invalid argument");
+    if (!frv || !centers_re_im || !coefs || !bucket || !prediction || !split_channels(channels_arg, channels, rct, quality, ycbcr)) return fail(err, err_cap, "invalid argument");
     ParsedImage img;
     std::string e = deserialize(std::vector<uint8_t>(frv, frv + len), img);
     if (!e.empty()) return fail(err, err_cap, e, -2);
     if (img.channels.size() != channels) return fail(err, err_cap, "channel count", -2);
     if (img.rct != rct) return fail(err, err_cap, "colour transform flag", -2);
     if (img.quality != quality) return fail(err, err_cap, "quality", -2);
+    if (img.ycbcr != ycbcr) return fail(err, err_cap, "YCbCr flag", -2);
     const size_t plane = (size_t)n_cells * kNodes;
     const auto order_ptr = shared_symbol_order(centers_re_im, n_cells);
     const SymbolOrder &order = *order_ptr;
@@ -176,13 +184,13 @@ int fri_emit_decode_image(const uint8_t *frv, size_t len, uint32_t info[4], int3
         uint32_t n_cells = 0;
         const std::string ge = count_cells(img.width, img.height, channels, n_cells);
         if (!ge.empty()) return fail(err, err_cap, ge, -2);
-        info[0] = img.width, info[1] = img.height, info[2] = channels | (img.rct ? FRI_EMIT_RCT : 0u) | FRI_EMIT_QUALITY(img.quality), info[3] = n_cells;
+        info[0] = img.width, info[1] = img.height, info[2] = channels_info(channels, img.rct, img.quality, img.ycbcr), info[3] = n_cells;
         return -3;
     }
     DecodedImage d;
     const std::string e = decode_image(std::vector<uint8_t>(frv, frv + len), d);
     if (!e.empty()) return fail(err, err_cap, e, -2);
-    info[0] = d.width, info[1] = d.height, info[2] = d.channels | (d.rct ? FRI_EMIT_RCT : 0u) | FRI_EMIT_QUALITY(d.quality), info[3] = d.n_cells;
+    info[0] = d.width, info[1] = d.height, info[2] = channels_info(d.channels, d.rct, d.quality, d.ycbcr), info[3] = d.n_cells;
     if (coef_cap < d.coefs.size()) return -3;
     std::memcpy(coefs, d.coefs.data(), d.coefs.size() * sizeof(int32_t));
     if (centers) std::memcpy(centers, d.centers.data(), d.centers.size() * sizeof(int32_t));

@@ -11,6 +11,8 @@
 //                                                            --psnr DB: lossy at the lowest quality that reaches DB (fri_hip_search_quality); prints both
 //                                                            --size BYTES / --bpp B (BYTES = floor(B w h / 8)): the highest quality whose file is at most BYTES
 //                                                            (fri_hip_search_quality_for_size, then FRIEncoder::encode's check); prints quality, estimate, size
+//                                                            --ycbcr (RGB, with --quality / --psnr / --size / --bpp): lossy in Y, Cb, Cr of the JFIF transform
+//                                                            (flagged file; searches measure PSNR in R, G, B). A PSNR no quality 1..99 reaches: lossless RCT file
 //   fri_driver decode-file <in.frv> <out.pgm|.ppm|.bmp>     container -> rANS / context decoding on the host -> dequantisation + inverse
 //                                                            transform on the device (fri-cli decode, crates/fri-cli/src/commands/decode.rs); a flagged file
 //                                                            comes back as RGB, a lossy file with its quality's matrix and the midpoint dequantiser
@@ -151,14 +153,19 @@ static int encode_image_to_file(std::vector<uint8_t> img, uint32_t w, uint32_t h
         fri_hip_plan *plan = dev.ok() ? dev.plan(w, h, c, err) : nullptr;
         int32_t q = 100;
         double db = 0;
-        const int rc = plan ? fri_hip_search_quality(plan, img.data(), opts.target_psnr, &q, &db) : FRI_HIP_ERR_NO_DEVICE;
+        int rc = plan ? fri_hip_plan_set_colour_transform(plan, opts.ycbcr ? FRI_HIP_COLOUR_YCBCR : FRI_HIP_COLOUR_NONE) : FRI_HIP_ERR_NO_DEVICE;
+        if (rc == FRI_HIP_OK) rc = fri_hip_search_quality(plan, img.data(), opts.target_psnr, &q, &db);
         if (rc != FRI_HIP_OK) {
             std::fprintf(stderr, "quality search: %s\n", plan ? dev.describe(rc).c_str() : (dev.ok() ? err.c_str() : dev.error().c_str()));
             return 1;
         }
-        std::printf("target %.2f dB: quality %d (%.2f dB)\n", opts.target_psnr, q, db);
+        std::printf("target %.2f dB: quality %d (%.2f dB)%s\n", opts.target_psnr, q, db, opts.ycbcr ? " in YCbCr" : "");
         opts.quality = q < 100 ? q : 0;
         opts.target_psnr = 0;
+        if (q == 100 && opts.ycbcr) { // YCbCr does not reach the target at any quality 1..99: code losslessly, with the RCT
+            opts.ycbcr = false, opts.colour_transform = true;
+            std::printf("no YCbCr quality reaches the target: a lossless RCT file\n");
+        }
     }
     const uint64_t budget = opts.target_bytes;
     if (budget) { // the quality FRIEncoder::encode settles on (search, then its file checked against the budget); then both routes code with it
@@ -276,6 +283,7 @@ int main(int argc, char **argv) {
         for (int i = 4; i < argc; i++) {
             const std::string a = argv[i];
             if (a == "--rct") file_opts.colour_transform = true;
+            else if (a == "--ycbcr") file_opts.ycbcr = true;
             else if (a == "--quality" && i + 1 < argc) file_opts.quality = std::atoi(argv[++i]);
             else if (a == "--psnr" && i + 1 < argc) file_opts.target_psnr = std::atof(argv[++i]);
             else if (a == "--size" && i + 1 < argc) file_opts.target_bytes = std::strtoull(argv[++i], nullptr, 10), has_size = true;
@@ -291,6 +299,10 @@ int main(int argc, char **argv) {
             return 2;
         }
         const bool sized = has_size || has_bpp;
+        if (file_opts.ycbcr && (fc != 3 || file_opts.colour_transform || !(file_opts.quality || file_opts.target_psnr > 0 || sized))) {
+            std::fprintf(stderr, "encode-file: --ycbcr needs an RGB image and one of --quality, --psnr, --size or --bpp, and not --rct\n");
+            return 2;
+        }
         if (has_bpp && bpp > 0) file_opts.target_bytes = (uint64_t)std::floor(bpp * fw * fh / 8.0);
         if ((has_size && has_bpp) || (sized && !file_opts.target_bytes) || (sized && (file_opts.quality || file_opts.target_psnr > 0 || file_opts.colour_transform))) {
             std::fprintf(stderr, "encode-file: --size BYTES (> 0) or --bpp B (> 0), not both, and neither with --quality, --psnr or --rct\n");
@@ -334,7 +346,7 @@ int main(int argc, char **argv) {
         return 0;
     }
     if (argc < 5) {
-        std::fprintf(stderr, "usage: %s roundtrip|encode|batch|batch-frv <width> <height> <channels> [n_images | out.frv]\n       %s encode-file <in.pgm|in.ppm|in.bmp> <out.frv> [--rct | --quality Q | --psnr DB | --size BYTES | --bpp B]\n       %s decode-file <in.frv> <out.pgm|out.ppm|out.bmp>\n", argv[0], argv[0], argv[0]);
+        std::fprintf(stderr, "usage: %s roundtrip|encode|batch|batch-frv <width> <height> <channels> [n_images | out.frv]\n       %s encode-file <in.pgm|in.ppm|in.bmp> <out.frv> [--rct | [--ycbcr] (--quality Q | --psnr DB | --size BYTES | --bpp B)]\n       %s decode-file <in.frv> <out.pgm|out.ppm|out.bmp>\n", argv[0], argv[0], argv[0]);
         return 2;
     }
     const std::string cmd = argv[1];

@@ -51,14 +51,16 @@ fri_hip_plan *Device::plan(uint32_t width, uint32_t height, uint32_t channels, s
 
 namespace {
 // The colour transform is plan state and a Device's plans are shared by shape: every caller sets the mode its launches need.
-std::string set_colour_transform(fri_hip_plan *plan, bool rct, Device &dev) {
-    const int rc = fri_hip_plan_set_colour_transform(plan, rct ? FRI_HIP_COLOUR_RCT : FRI_HIP_COLOUR_NONE);
+std::string set_colour_transform(fri_hip_plan *plan, bool rct, Device &dev, bool ycbcr = false) {
+    const int rc = fri_hip_plan_set_colour_transform(plan, ycbcr ? FRI_HIP_COLOUR_YCBCR : rct ? FRI_HIP_COLOUR_RCT : FRI_HIP_COLOUR_NONE);
     return rc == FRI_HIP_OK ? std::string() : dev.describe(rc);
 }
-// what an encode of `colorspace` pixels codes: RGB with the option on goes out as Y, Cb, Cr (colour space YCbCr, flagged)
+// what an encode of `colorspace` pixels codes: RGB with either option on goes out as Y, Cb, Cr (colour space YCbCr, flagged); YCbCr only with a quality
 ImageMetadata coded_metadata(uint32_t height, uint32_t width, ColorSpace colorspace, const EncoderOpts &opts) {
     const bool rct = opts.colour_transform && colorspace == ColorSpace::RGB;
-    return ImageMetadata{height, width, rct ? ColorSpace::YCbCr : colorspace, rct, (uint32_t)(opts.quality > 0 && opts.quality < 100 ? opts.quality : 0)};
+    const uint32_t quality = (uint32_t)(opts.quality > 0 && opts.quality < 100 ? opts.quality : 0);
+    const bool ycbcr = opts.ycbcr && colorspace == ColorSpace::RGB && quality;
+    return ImageMetadata{height, width, rct || ycbcr ? ColorSpace::YCbCr : colorspace, rct, quality, ycbcr};
 }
 // The matrix an encode quantises with: fri_hip_quality_matrix(opts.quality) for a lossy encode, else opts.quantization_matrix. "" or the error.
 std::string coding_matrix(const EncoderOpts &opts, std::array<int32_t, 32> &q) {
@@ -67,6 +69,8 @@ std::string coding_matrix(const EncoderOpts &opts, std::array<int32_t, 32> &q) {
     if ((opts.quality || opts.target_psnr > 0) && opts.colour_transform) return "lossy coding (quality / target_psnr) cannot be combined with colour_transform";
     if (opts.quality && opts.target_psnr > 0) return "set quality or target_psnr, not both";
     if (opts.target_bytes && (opts.quality || opts.target_psnr > 0 || opts.colour_transform)) return "target_bytes cannot be combined with quality, target_psnr or colour_transform";
+    if (opts.ycbcr && opts.colour_transform) return "ycbcr cannot be combined with colour_transform";
+    if (opts.ycbcr && !opts.quality && !(opts.target_psnr > 0) && !opts.target_bytes) return "ycbcr needs lossy coding (quality, target_psnr or target_bytes)";
     const bool ones = std::all_of(opts.quantization_matrix.begin(), opts.quantization_matrix.end(), [](int32_t v) { return v == 1; });
     if (opts.quality && !ones) return "set quality or a quantization_matrix, not both";
     q = opts.quantization_matrix;
@@ -126,7 +130,7 @@ Result<WaveletImage> encode(const RasterImage &raster, const EncoderOpts &opts, 
     w.metadata = coded_metadata(raster.metadata.height, raster.metadata.width, raster.metadata.colorspace, opts);
     std::array<int32_t, 32> qm;
     if (!(r.error = coding_matrix(opts, qm)).empty()) return r;
-    if (!(r.error = set_colour_transform(plan, w.metadata.rct, dev)).empty()) return r;
+    if (!(r.error = set_colour_transform(plan, w.metadata.rct, dev, w.metadata.ycbcr)).empty()) return r;
     w.num_cells = fri_hip_plan_num_cells(plan);
     w.centers.resize((size_t)w.num_cells * 2);
     w.coefficients.resize(fri_hip_plan_coef_count(plan));
@@ -150,7 +154,7 @@ Result<RasterImage> decode(const WaveletImage &image, const EncoderOpts &opts, D
         r.error = "coefficient array does not match the image geometry";
         return r;
     }
-    if (!(r.error = set_colour_transform(plan, image.metadata.rct, dev)).empty()) return r;
+    if (!(r.error = set_colour_transform(plan, image.metadata.rct, dev, image.metadata.ycbcr)).empty()) return r;
     // a lossy image: the matrix of its quality and the midpoint dequantiser; otherwise the caller's matrix and the reference's dequantiser
     std::array<int32_t, 32> qm = opts.quantization_matrix;
     if (image.metadata.quality && fri_hip_quality_matrix((int)image.metadata.quality, qm.data()) != FRI_HIP_OK) {
@@ -163,7 +167,8 @@ Result<RasterImage> decode(const WaveletImage &image, const EncoderOpts &opts, D
     }
     r.value.metadata = image.metadata;
     r.value.metadata.quality = 0; // (the raster is what the lossy planes decode to)
-    if (image.metadata.rct) r.value.metadata.colorspace = ColorSpace::RGB, r.value.metadata.rct = false; // the kernel writes R, G, B
+    if (image.metadata.rct || image.metadata.ycbcr) // the kernel writes R, G, B
+        r.value.metadata.colorspace = ColorSpace::RGB, r.value.metadata.rct = false, r.value.metadata.ycbcr = false;
     r.value.data.resize(fri_hip_plan_pixel_bytes(plan));
     int rc = fri_hip_inverse_transform(plan, image.coefficients.data(), qm.data(), r.value.data.data());
     if (rc != FRI_HIP_OK) {
@@ -258,6 +263,8 @@ Result<EncodedStages> FRIEncoder::encode(std::vector<uint8_t> data, uint32_t hei
     std::array<int32_t, 32> qm;
     if (const std::string e = coding_matrix(opts_, qm); !e.empty()) return fail(e);
     EncoderOpts coded = opts_;
+    // the searches probe the planes the file will hold: YCbCr for an RGB image with the option (a fresh plan of this Device otherwise has no transform)
+    if (const std::string e = set_colour_transform(plan, false, dev, opts_.ycbcr && colorspace == ColorSpace::RGB); !e.empty()) return fail(e);
     if (opts_.target_bytes) { // the highest quality whose estimated file fits, searched on the device; 100 = lossless
         int32_t q = 0;
         uint64_t est = 0;
@@ -293,10 +300,12 @@ Result<EncodedStages> FRIEncoder::encode(std::vector<uint8_t> data, uint32_t hei
         if (int rc = fri_hip_search_quality(plan, data.data(), opts_.target_psnr, &q, &db); rc != FRI_HIP_OK) return fail(dev.describe(rc));
         coded.quality = q < 100 ? q : 0;
         r.value.psnr_db = db;
+        if (q == 100 && coded.ycbcr && colorspace == ColorSpace::RGB) // YCbCr does not reach the target at any quality: a lossless file, with the RCT
+            coded.ycbcr = false, coded.colour_transform = true, r.value.lossless_rct = true;
         if (coded.quality) fri_hip_quality_matrix(coded.quality, qm.data());
     }
     w.metadata = coded_metadata(height, width, colorspace, coded);
-    if (const std::string e = set_colour_transform(plan, w.metadata.rct, dev); !e.empty()) return fail(e);
+    if (const std::string e = set_colour_transform(plan, w.metadata.rct, dev, w.metadata.ycbcr); !e.empty()) return fail(e);
     w.num_cells = fri_hip_plan_num_cells(plan);
     w.centers.resize((size_t)w.num_cells * 2);
     w.coefficients.resize(fri_hip_plan_coef_count(plan));
@@ -355,7 +364,8 @@ Result<CompressedImage> stages::entropy_coding::encode(const WaveletImage &image
 }
 
 std::vector<uint8_t> stages::serialize::encode(const CompressedImage &image) {
-    return emit::serialize(image.metadata.height, image.metadata.width, colour_code(image.metadata.colorspace), image.channel_data, image.params, image.metadata.rct, image.metadata.quality);
+    return emit::serialize(image.metadata.height, image.metadata.width, colour_code(image.metadata.colorspace), image.channel_data, image.params, image.metadata.rct, image.metadata.quality,
+                           image.metadata.ycbcr);
 }
 
 Result<CompressedImage> stages::serialize::decode(const std::vector<uint8_t> &bytes) {
@@ -368,6 +378,7 @@ Result<CompressedImage> stages::serialize::decode(const std::vector<uint8_t> &by
     r.value.metadata.colorspace = p.colorspace == emit::kLuma ? ColorSpace::Luma : p.colorspace == emit::kRGB ? ColorSpace::RGB : ColorSpace::YCbCr;
     r.value.metadata.rct = p.rct;
     r.value.metadata.quality = p.quality;
+    r.value.metadata.ycbcr = p.ycbcr;
     r.value.variant = p.variant;
     r.value.channel_data = std::move(p.channels);
     r.value.params = std::move(p.params);
@@ -436,7 +447,7 @@ std::string emit_streamed(const StreamedImage &im, uint32_t c, uint64_t n, const
     for (uint32_t ch = 0; ch < c; ch++)
         for (int g = 0; g < 3; g++)
             for (int k = 0; k < 6; k++) params[ch].value[g][k] = im.vp[ch][g][k], params[ch].width[g][k] = im.wp[ch][g][k];
-    out = emit::serialize(md.height, md.width, colour_code(md.colorspace), streams, params, md.rct, md.quality);
+    out = emit::serialize(md.height, md.width, colour_code(md.colorspace), streams, params, md.rct, md.quality, md.ycbcr);
     return std::string();
 }
 } // namespace
@@ -472,7 +483,7 @@ Result<std::vector<uint8_t>> FRIEncoder::encode_bytes_streamed(std::vector<uint8
     if (const std::string e = coding_matrix(opts_, qm); !e.empty()) return fail(e);
     if (opts_.target_psnr > 0) return fail("target_psnr: FRIEncoder::encode only (search first, then pass the quality)");
     if (opts_.target_bytes) return fail("target_bytes: FRIEncoder::encode only (search first, then pass the quality)");
-    if (const std::string e = set_colour_transform(plan, md.rct, dev); !e.empty()) return fail(e);
+    if (const std::string e = set_colour_transform(plan, md.rct, dev, md.ycbcr); !e.empty()) return fail(e);
     const uint64_t n = fri_hip_plan_num_some(plan);
     if (const std::string e = set_plan_stream_order(plan, dev); !e.empty()) return fail(e); // geometry only, once per plan (the plan is new here: Device lives for this call, as in encode())
     std::vector<uint16_t> symbols((size_t)c * n);
@@ -492,7 +503,7 @@ Result<std::vector<uint8_t>> FRIEncoder::encode_bytes_streamed(std::vector<uint8
     for (uint32_t ch = 0; ch < c; ch++)
         for (int g = 0; g < 3; g++)
             for (int k = 0; k < 6; k++) params[ch].value[g][k] = vp[ch][g][k], params[ch].width[g][k] = wp[ch][g][k];
-    r.value = emit::serialize(height, width, colour_code(md.colorspace), streams, params, md.rct, md.quality);
+    r.value = emit::serialize(height, width, colour_code(md.colorspace), streams, params, md.rct, md.quality, md.ycbcr);
     r.ok = true;
     return r;
 }
@@ -565,7 +576,7 @@ Result<std::vector<std::vector<uint8_t>>> encode_batch_bytes(const std::vector<c
             std::string err;
             fri_hip_plan *plan = dev.ok() ? dev.stream_plan(width, height, c, err) : nullptr;
             if (!plan && err.empty()) err = dev.error();
-            if (plan) err = set_colour_transform(plan, md.rct, dev);
+            if (plan) err = set_colour_transform(plan, md.rct, dev, md.ycbcr);
             if (!err.empty()) fail(err);
             const uint64_t n = plan ? fri_hip_plan_num_some(plan) : 0;
             if (n) n_some.store(n, std::memory_order_relaxed);

@@ -25,8 +25,15 @@
  * with FRI_HIP_DEQUANT_MIDPOINT. Such a file holds q in bits 8..14 of its metadata word and is otherwise byte for byte the file of the same planes without it;
  * a lossless file (no quality) keeps 0 there. fri_emit_decode_image reports the field the same way, in info[2]. Refused: a quality together with
  * FRI_EMIT_RCT, and q = 0 or q >= 100 in the field; a file whose field holds 100..127 is "Invalid metadata". The reference's serialize::decode reads
- * bits 28..31 only: it returns the quantised planes of a lossy file, i.e. the wrong pixels (as it returns Y, Cb, Cr for an RCT file). */
+ * bits 28..31 only: it returns the quantised planes of a lossy file, i.e. the wrong pixels (as it returns Y, Cb, Cr for an RCT file).
+ *
+ * YCbCr: `channels` = 3 | FRI_EMIT_YCBCR | FRI_EMIT_QUALITY(q), q = 1..99 - the planes are Y, Cb, Cr of the irreversible JFIF transform
+ * (FRI_HIP_COLOUR_YCBCR, include/fri_hip.h), quantised with fri_hip_quality_matrix(q). Such a file has the colour space YCbCr, bit 1 of its metadata word set
+ * and bit 0 clear, and is otherwise byte for byte the lossy file of the same planes. Refused: FRI_EMIT_YCBCR with one channel, without a quality or together
+ * with FRI_EMIT_RCT. fri_emit_decode_image reports it in info[2]; a YCbCr file with bits 0 and 1 both set, or with bit 1 and quality 0, is "Invalid
+ * metadata". Bit 1 of a Luma or RGB file is ignored. */
 #define FRI_EMIT_RCT 0x100u
+#define FRI_EMIT_YCBCR 0x400u
 #define FRI_EMIT_QUALITY(q) ((uint32_t)(q) << 16)
 #define FRI_EMIT_QUALITY_OF(channels) (((uint32_t)(channels) >> 16) & 0x7Fu)
 #ifndef FRI_EMIT_H

@@ -375,6 +375,9 @@ int fri_hip_measure_distortion_dev(fri_hip_plan *plan, const int32_t *d_coefs, c
  * lo = 0, hi = 100; while hi - lo > 1: mid = (lo + hi) / 2, hi = mid if PSNR(mid) >= target_db, else lo = mid. Returns quality = hi and its PSNR
  * (+inf for 100, which is never probed): at most 7 probes. Each probe reads its sums back, so the call synchronises `stream` and refuses a capturing one.
  * FRI_HIP_ERR_INVALID_ARGUMENT for target_db NaN or <= 0 and on an RCT plan (the mod-256 colour transform turns quantisation error into wrap-around).
+ * On a YCbCr plan the probes run K1 and K3 with the transform and the PSNR is that of R, G, B. There, quality 100 is not lossless (the transform alone costs
+ * up to 1 per channel): a result of 100 - no quality 1..99 reaches target_db - means "code losslessly", i.e. the caller writes a lossless file (with the
+ * RCT, for example), not a YCbCr file of quality 100, which the emitter refuses.
  * The plan's dequantiser setting is left as it is. The host form stages the pixels through the plan's buffers. */
 int fri_hip_search_quality(fri_hip_plan *plan, const uint8_t *pixels, double target_db, int32_t *quality, double *psnr_db);
 int fri_hip_search_quality_dev(fri_hip_plan *plan, const uint8_t *d_pixels, double target_db, int32_t *quality, double *psnr_db, void *stream);
@@ -404,7 +407,7 @@ int fri_hip_estimate_size(fri_hip_plan *plan, const uint32_t *hist, const uint64
  * lo = mid if fits(mid), else hi = mid - at most 7 probes, 100 (lossless) reachable. Returns quality = lo and its estimate; when nothing fits,
  * FRI_HIP_ERR_OUT_OF_RANGE with quality = 0 and est_bytes = the estimate of quality 1. The probes run on plan-owned buffers and read their estimate
  * back: the call synchronises `stream` and refuses a capturing one. FRI_HIP_ERR_INVALID_ARGUMENT for max_bytes == 0 and on an RCT plan (as
- * fri_hip_search_quality). The plan's dequantiser, colour transform and stream order are left as they are. The rate need not be monotone in the
+ * fri_hip_search_quality). On a YCbCr plan hi starts at 100: the search covers qualities 1..99 only, the qualities a YCbCr file can have. The plan's dequantiser, colour transform and stream order are left as they are. The rate need not be monotone in the
  * quality; the bisection is all that is promised. The host form stages the pixels through the plan's buffers. */
 int fri_hip_search_quality_for_size(fri_hip_plan *plan, const uint8_t *pixels, uint64_t max_bytes, int32_t *quality, uint64_t *est_bytes);
 int fri_hip_search_quality_for_size_dev(fri_hip_plan *plan, const uint8_t *d_pixels, uint64_t max_bytes, int32_t *quality, uint64_t *est_bytes, void *stream);
@@ -417,9 +420,21 @@ int fri_hip_search_quality_for_size_dev(fri_hip_plan *plan, const uint8_t *d_pix
  * time_transform_quant*) reads pixels as R, G, B and codes Y, Cb, Cr; every inverse entry point writes R, G, B from them. The forward kernel forms Y, Cb, Cr out
  * of the staged pixels; the inverse kernel undoes it after the clamp, in the tile's pixel rectangle. Pixels no retained cell covers stay 0 in all three
  * channels. The tilings (and fri_hip_plan_tune_forward's cache) do not depend on the mode. A launch captured into a graph keeps the mode that was set when it
- * was captured. Returns FRI_HIP_ERR_INVALID_ARGUMENT for an unknown mode or RCT on a plan with C != 3; works on host-only plans. */
+ * was captured. Returns FRI_HIP_ERR_INVALID_ARGUMENT for an unknown mode or RCT on a plan with C != 3; works on host-only plans.
+ * FRI_HIP_COLOUR_YCBCR (C = 3 only): the irreversible JFIF / BT.601 full-range transform in libjpeg's 16-bit fixed point, for lossy files only. Part of the
+ * file format (FRI_EMIT_YCBCR); 32-bit signed arithmetic, >> is an arithmetic shift:
+ *     forward:  Y  = ( 19595 R + 38470 G +  7471 B + 32768) >> 16
+ *               Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16
+ *               Cr = ( 32768 R - 27439 G -  5329 B + (128 << 16) + 32767) >> 16            each in 0..255
+ *     inverse (after the clamp of every plane to 0..255; db = Cb - 128, dr = Cr - 128):
+ *               R = clamp255(Y + (( 91881 dr + 32768) >> 16))
+ *               G = clamp255(Y + ((-22554 db - 46802 dr + 32768) >> 16))
+ *               B = clamp255(Y + ((116130 db + 32768) >> 16))
+ * Forward then inverse is off by at most 1 per channel. The coded planes are the plain transform of the raster ycc(pixels): a leaf outside the image enters
+ * every plane as 0. The mode reads as bits - bit 0: chroma planes, bit 1: irreversible - and 2 has no meaning (refused). */
 #define FRI_HIP_COLOUR_NONE 0
 #define FRI_HIP_COLOUR_RCT 1
+#define FRI_HIP_COLOUR_YCBCR 3
 int fri_hip_plan_set_colour_transform(fri_hip_plan *plan, int mode);
 int fri_hip_inverse_transform_dev(fri_hip_plan *plan, const int32_t *d_coefs, const int32_t qmatrix[32], uint8_t *d_pixels,
                                   void *stream);
