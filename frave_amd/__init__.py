@@ -22,4 +22,5 @@ from .api import (  # noqa: F401
     load_library,
     quality_matrix,
     shard_images,
+    ssim_of,
 )

@@ -31,7 +31,8 @@ SYMBOLS = [
     "fri_hip_plan_set_dequantiser", "fri_hip_plan_tune_forward", "fri_hip_time_transform_quant_streams_dev",
     "fri_hip_plan_set_colour_transform", "fri_hip_quality_matrix", "fri_hip_measure_distortion_dev", "fri_hip_search_quality",
     "fri_hip_search_quality_dev", "fri_hip_estimate_size_dev", "fri_hip_estimate_size", "fri_hip_search_quality_for_size",
-    "fri_hip_search_quality_for_size_dev", "fri_hip_plan_predict_grid",
+    "fri_hip_search_quality_for_size_dev", "fri_hip_plan_predict_grid", "fri_hip_measure_ssim_dev", "fri_hip_measure_ssim", "fri_hip_search_quality_ssim",
+    "fri_hip_search_quality_ssim_dev",
 ]
 COLOUR_NONE, COLOUR_RCT, COLOUR_YCBCR = 0, 1, 3  # fri_hip_plan_set_colour_transform (bit 0: chroma planes, bit 1: irreversible)
 DEQUANT_REFERENCE, DEQUANT_MULTIPLY, DEQUANT_MIDPOINT = 0, 1, 2  # fri_hip_plan_set_dequantiser
@@ -160,6 +161,10 @@ def load_library():
     L.fri_hip_estimate_size.argtypes = [vp, vp, vp, vp]
     L.fri_hip_search_quality_for_size.argtypes = [vp, vp, C.c_uint64, vp, vp]
     L.fri_hip_search_quality_for_size_dev.argtypes = [vp, vp, C.c_uint64, vp, vp, vp]
+    L.fri_hip_measure_ssim_dev.argtypes = [vp, u32, vp, vp, sz, vp, vp]
+    L.fri_hip_measure_ssim.argtypes = [vp, vp, vp, vp]
+    L.fri_hip_search_quality_ssim.argtypes = [vp, vp, C.c_double, vp, vp]
+    L.fri_hip_search_quality_ssim_dev.argtypes = [vp, vp, C.c_double, vp, vp, vp]
     L.fri_hip_plan_set_stream_order.argtypes = [vp, vp, C.c_uint64]
     L.fri_hip_symbol_stream_batch_dev.argtypes = [vp, u32, vp, sz, vp, vp, sz, vp, sz, vp]
     L.fri_hip_encode_image_symbols.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp]
@@ -233,6 +238,14 @@ def distortion_psnr(measure, channels):
     if sse == 0:
         return float("inf")
     return 10.0 * np.log10(255.0 * 255.0 * m[2 * channels] * channels / sse)
+
+
+def ssim_of(measure, channels):
+    """(SSIM, [SSIM_c per channel]) of a fri_hip_measure_ssim result (int64 [C + 1]: the channels' sums of window values in units of 2^-32, then the
+    window count N): SSIM = (sum over c of sum_c) / (C N 2^32), the integer sum first; SSIM_c = sum_c / (N 2^32)."""
+    m = [int(x) for x in np.asarray(measure).ravel()[: channels + 1]]
+    n = m[channels]
+    return float(sum(m[:channels])) / (float(channels * n) * 2.0 ** 32), [float(m[c]) / (float(n) * 2.0 ** 32) for c in range(channels)]
 
 
 def fit_value_params(gram_tri):
@@ -422,6 +435,33 @@ class Plan:
             assert px.size == self.pixel_bytes
             _check(L.fri_hip_search_quality(self._h, _p(px), float(target_db), C.byref(qual), C.byref(db)), "fri_hip_search_quality", self.ctx)
         return qual.value, db.value
+
+    def measure_ssim(self, a, b):
+        """fri_hip_measure_ssim: the SSIM sums of two host rasters of the plan's shape (a the source, b the reconstruction) - int64 [C + 1], per channel
+        the sum of the window values in units of 2^-32, then the window count (ssim_of turns them into SSIM)."""
+        pa, pb = np.ascontiguousarray(a, np.uint8), np.ascontiguousarray(b, np.uint8)
+        assert pa.size == self.pixel_bytes and pb.size == self.pixel_bytes
+        out = np.zeros(self.channels + 1, np.int64)
+        _check(load_library().fri_hip_measure_ssim(self._h, _p(pa), _p(pb), _p(out)), "fri_hip_measure_ssim", self.ctx)
+        return out
+
+    def measure_ssim_dev(self, d_a, d_b, d_out, n_images=1, pixel_stride=0, stream=0):
+        """fri_hip_measure_ssim_dev: K7 over n_images raster pairs (pair k at d_a / d_b + k pixel_stride bytes) into d_out (int64 [n_images][C + 1], device),
+        which it zeroes on `stream` first; only enqueues."""
+        _check(load_library().fri_hip_measure_ssim_dev(self._h, n_images, d_a, d_b, pixel_stride, d_out, stream), "fri_hip_measure_ssim_dev", self.ctx)
+
+    def search_quality_ssim(self, pixels, target, stream=0):
+        """fri_hip_search_quality_ssim (pixels: a host array) or its _dev form (pixels: a device pointer, an int): the lowest quality whose midpoint-dequantised
+        round trip reaches an SSIM of target (0 < target <= 1), by the bisection of search_quality. Returns (quality, ssim); 100 means "code losslessly"."""
+        qual, v = C.c_int32(0), C.c_double(0.0)
+        L = load_library()
+        if isinstance(pixels, int):
+            _check(L.fri_hip_search_quality_ssim_dev(self._h, pixels, float(target), C.byref(qual), C.byref(v), stream), "fri_hip_search_quality_ssim_dev", self.ctx)
+        else:
+            px = np.ascontiguousarray(pixels, np.uint8)
+            assert px.size == self.pixel_bytes
+            _check(L.fri_hip_search_quality_ssim(self._h, _p(px), float(target), C.byref(qual), C.byref(v)), "fri_hip_search_quality_ssim", self.ctx)
+        return qual.value, v.value
 
     def estimate_size(self, hist, oob=None, stream=0, n_images=1, d_bytes=None, d_models=None):
         """The estimated .frv bytes of the histograms (include/fri_hip.h gives the formula); UINT64_MAX where the emitter would refuse the image.

@@ -84,6 +84,8 @@ struct Staging {
     Grown<unsigned long long> search_oob; // ... its out-of-alphabet counts [C]
     Grown<float> search_params;        // ... its fitted parameters [C][2][3][6]
     Grown<unsigned long long> rate;    // fri_hip_estimate_size, fri_hip_search_quality_for_size*: the estimate [1]
+    Grown<uint8_t> ssim_pixels;        // fri_hip_measure_ssim: the second raster; fri_hip_search_quality_ssim*: a probe's reconstruction
+    Grown<unsigned long long> ssim;    // fri_hip_measure_ssim, fri_hip_search_quality_ssim*: the SSIM sums [C + 1]
 };
 
 constexpr int kBatchSlots = 3;
@@ -719,6 +721,19 @@ double distortion_psnr(const unsigned long long *m, uint32_t channels) {
     for (uint32_t c = 0; c < channels; c++) sse += m[2 * c];
     if (sse == 0) return HUGE_VAL;
     return 10.0 * std::log10(255.0 * 255.0 * (double)m[2 * channels] * (double)channels / (double)sse);
+}
+
+// The SSIM window grid of a plan's shape (fri_hip_measure_ssim_dev): FRI_HIP_ERR_INVALID_ARGUMENT without a window or with more than 2^29 per channel.
+int ssim_shape(const fri_hip_plan *p) {
+    if (p->geo.width < 8 || p->geo.height < 8) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    return (uint64_t)(p->geo.width / 4 - 1) * (p->geo.height / 4 - 1) > (1ull << 29) ? FRI_HIP_ERR_INVALID_ARGUMENT : FRI_HIP_OK;
+}
+
+// SSIM of a measurement (d_out of fri_hip_measure_ssim_dev): the channels' integer sums added first, then one division.
+double ssim_of(const unsigned long long *m, uint32_t channels) {
+    long long total = 0;
+    for (uint32_t c = 0; c < channels; c++) total += (long long)m[c];
+    return (double)total / ((double)((unsigned long long)channels * m[channels]) * 4294967296.0);
 }
 
 } // namespace
@@ -1871,6 +1886,87 @@ int fri_hip_search_quality_for_size(fri_hip_plan *p, const uint8_t *pixels, uint
     if (int rc = grow(p->ctx, p->staging.pixels, fri_hip_plan_pixel_bytes(p))) return rc;
     HIP_TRY(p->ctx, hipMemcpy(p->staging.pixels, pixels, fri_hip_plan_pixel_bytes(p), hipMemcpyHostToDevice));
     return fri_hip_search_quality_for_size_dev(p, p->staging.pixels, max_bytes, quality, est_bytes, nullptr);
+}
+
+/* ---- SSIM ------------------------------------------------------------------------------------------- */
+int fri_hip_measure_ssim_dev(fri_hip_plan *p, uint32_t n_images, const uint8_t *d_a, const uint8_t *d_b, size_t pixel_stride, int64_t *d_out, void *stream) {
+    if (!p || !d_a || !d_b || !d_out || !n_images || n_images > 65535u) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    if (n_images > 1 && pixel_stride < fri_hip_plan_pixel_bytes(p)) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    if (int rc = ssim_shape(p)) return rc;
+    if (int rc = need_device(p)) return rc;
+    const uint32_t C = p->geo.channels;
+    auto *out = reinterpret_cast<unsigned long long *>(d_out);
+    HIP_TRY(p->ctx, hipSetDevice(p->ctx->device));
+    HIP_TRY(p->ctx, hipMemsetAsync(out, 0, (size_t)n_images * (C + 1) * sizeof(int64_t), (hipStream_t)stream));
+    HIP_TRY(p->ctx, launch_ssim(n_images, d_a, d_b, pixel_stride, p->geo.width, p->geo.height, C, out, (hipStream_t)stream));
+    return FRI_HIP_OK;
+}
+
+int fri_hip_measure_ssim(fri_hip_plan *p, const uint8_t *a, const uint8_t *b, int64_t *out) {
+    if (!p || !a || !b || !out) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    if (int rc = ssim_shape(p)) return rc;
+    if (int rc = need_device(p)) return rc;
+    fri_hip_ctx *c = p->ctx;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t n = fri_hip_plan_pixel_bytes(p), C = p->geo.channels;
+    auto &st = p->staging;
+    int rc;
+    if ((rc = grow(c, st.pixels, n)) || (rc = grow(c, st.ssim_pixels, n)) || (rc = grow(c, st.ssim, C + 1))) return rc;
+    HIP_TRY(c, hipMemcpy(st.pixels, a, n, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(st.ssim_pixels, b, n, hipMemcpyHostToDevice));
+    if ((rc = fri_hip_measure_ssim_dev(p, 1, st.pixels, st.ssim_pixels, 0, (int64_t *)st.ssim.get(), nullptr))) return rc;
+    HIP_TRY(c, hipMemcpy(out, st.ssim, (C + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
+    return FRI_HIP_OK;
+}
+
+int fri_hip_search_quality_ssim_dev(fri_hip_plan *p, const uint8_t *d_pixels, double target, int32_t *quality, double *ssim, void *stream) {
+    if (!p || !d_pixels || !quality || !ssim || !(target > 0 && target <= 1) || p->dev.rct) return FRI_HIP_ERR_INVALID_ARGUMENT; // (NaN fails both)
+    if (int rc = ssim_shape(p)) return rc;
+    if (int rc = need_device(p)) return rc;
+    const hipStream_t s = (hipStream_t)stream;
+    if (int rc = refuse_capture(p, s, "fri_hip_search_quality_ssim_dev reads every probe back: it cannot be captured into a HIP graph")) return rc;
+    fri_hip_ctx *c = p->ctx;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const uint32_t C = p->geo.channels;
+    auto &st = p->staging;
+    int rc;
+    if ((rc = grow(c, st.search_coefs, fri_hip_plan_coef_count(p))) || (rc = grow(c, st.ssim_pixels, fri_hip_plan_pixel_bytes(p))) || (rc = grow(c, st.ssim, C + 1)))
+        return rc;
+    // the probes' K3: the plan's inverse tiling with the midpoint dequantiser, whatever the caller has set on the plan, writing the raster a decoder gets
+    DevicePlan inv = p->dev_inv;
+    inv.k3_multiply = false;
+    inv.k3_midpoint = true;
+    int lo = 0, hi = 100; // lo: a failure (0 is never probed), hi: a success (100 = lossless is never probed)
+    double hi_ssim = 1.0;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) / 2;
+        int32_t qm[32];
+        QMatrix q;
+        fri_hip_quality_matrix(mid, qm);
+        check_q(qm, q);
+        HIP_TRY(c, launch_fwd_transform_quant(p->dev, 1, d_pixels, 0, st.search_coefs, 0, q, s));
+        HIP_TRY(c, launch_inverse_transform(inv, 1, st.search_coefs, 0, q, st.ssim_pixels, 0, s));
+        if ((rc = fri_hip_measure_ssim_dev(p, 1, d_pixels, st.ssim_pixels, 0, (int64_t *)st.ssim.get(), stream))) return rc;
+        unsigned long long m[4];
+        HIP_TRY(c, hipMemcpyAsync(m, st.ssim, (C + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        const double v = ssim_of(m, C);
+        if (v >= target) hi = mid, hi_ssim = v;
+        else lo = mid;
+    }
+    *quality = hi;
+    *ssim = hi_ssim;
+    return FRI_HIP_OK;
+}
+
+int fri_hip_search_quality_ssim(fri_hip_plan *p, const uint8_t *pixels, double target, int32_t *quality, double *ssim) {
+    if (!p || !pixels || !quality || !ssim || !(target > 0 && target <= 1) || p->dev.rct) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    if (int rc = ssim_shape(p)) return rc;
+    if (int rc = need_device(p)) return rc;
+    HIP_TRY(p->ctx, hipSetDevice(p->ctx->device));
+    if (int rc = grow(p->ctx, p->staging.pixels, fri_hip_plan_pixel_bytes(p))) return rc;
+    HIP_TRY(p->ctx, hipMemcpy(p->staging.pixels, pixels, fri_hip_plan_pixel_bytes(p), hipMemcpyHostToDevice));
+    return fri_hip_search_quality_ssim_dev(p, p->staging.pixels, target, quality, ssim, nullptr);
 }
 
 /* ---- timing helper ------------------------------------------------------------------------------ */

@@ -157,6 +157,12 @@ struct RateLayout {
 hipError_t launch_rate_estimate(uint32_t n_images, uint32_t channels, const uint32_t *hist, const unsigned long long *oob, const float *laplace,
                                 unsigned long long *bytes, uint32_t *models, const RateLayout &layout, hipStream_t stream);
 
+// K7 (k7_ssim.hip): the SSIM sums of n_images raster pairs of width x height x channels (interleaved u8; image k at a / b + k * pixel_stride bytes):
+// out[k][c] += the sum of the window values of channel c, out[k][channels] += the number of windows (include/fri_hip.h, fri_hip_measure_ssim_dev).
+// The caller zeroes out. width, height >= 8, channels 1 or 3.
+hipError_t launch_ssim(uint32_t n_images, const uint8_t *a, const uint8_t *b, size_t pixel_stride, uint32_t width, uint32_t height, uint32_t channels,
+                       unsigned long long *out, hipStream_t stream);
+
 // K2's per-node neighbour offsets (LDS halfword offsets relative to the own slot, two per word) from the static neighbour table
 void build_lf_deltas(const uint16_t *nbr_table, int8_t *out /* [8] */);
 void build_gather_tables(const uint16_t *nbr_table, uint32_t *gather_off /* [512][4] */, uint16_t *pair_pos /* [256] */, uint16_t *heap_of_pos /* [512] */);

@@ -11,8 +11,11 @@
 //                                                            --psnr DB: lossy at the lowest quality that reaches DB (fri_hip_search_quality); prints both
 //                                                            --size BYTES / --bpp B (BYTES = floor(B w h / 8)): the highest quality whose file is at most BYTES
 //                                                            (fri_hip_search_quality_for_size, then FRIEncoder::encode's check); prints quality, estimate, size
-//                                                            --ycbcr (RGB, with --quality / --psnr / --size / --bpp): lossy in Y, Cb, Cr of the JFIF transform
-//                                                            (flagged file; searches measure PSNR in R, G, B). A PSNR no quality 1..99 reaches: lossless RCT file
+//                                                            --ssim S (0 < S <= 1): lossy at the lowest quality whose round trip reaches an SSIM of S
+//                                                            (fri_hip_search_quality_ssim); prints the quality, and the decoded image's SSIM (fri_hip_measure_ssim)
+//                                                            --ycbcr (RGB, with --quality / --psnr / --ssim / --size / --bpp): lossy in Y, Cb, Cr of the JFIF
+//                                                            transform (flagged file; searches measure in R, G, B). A PSNR or SSIM no quality 1..99 reaches:
+//                                                            lossless RCT file
 //   fri_driver decode-file <in.frv> <out.pgm|.ppm|.bmp>     container -> rANS / context decoding on the host -> dequantisation + inverse
 //                                                            transform on the device (fri-cli decode, crates/fri-cli/src/commands/decode.rs); a flagged file
 //                                                            comes back as RGB, a lossy file with its quality's matrix and the midpoint dequantiser
@@ -144,7 +147,7 @@ static bool has_suffix(const char *path, const char *suffix) {
 // over PCIe) - the default since round 4. Self-checks: the array route (stage functions one by one, 9 bytes per node over PCIe, gather on the host) must give
 // the same bytes - it does bit for bit since the fit's W^T r sums are fixed-point integers (k4_fit.hip): both routes fit the same parameters - ; the container
 // parses and every symbol decodes; FRIDecoder::decode returns the input.
-// Lossy (--quality / --psnr): the decoded image must equal the direct round trip K1 with the quality's matrix -> K3 with the midpoint dequantiser.
+// Lossy (--quality / --psnr / --ssim): the decoded image must equal the direct round trip K1 with the quality's matrix -> K3 with the midpoint dequantiser.
 static int encode_image_to_file(std::vector<uint8_t> img, uint32_t w, uint32_t h, uint32_t c, libfri::EncoderOpts opts, const char *out_path) {
     const libfri::ColorSpace cs = c == 1 ? libfri::ColorSpace::Luma : libfri::ColorSpace::RGB;
     if (opts.target_psnr > 0) { // the quality first (the same search FRIEncoder::encode runs), then both routes code with it
@@ -162,6 +165,27 @@ static int encode_image_to_file(std::vector<uint8_t> img, uint32_t w, uint32_t h
         std::printf("target %.2f dB: quality %d (%.2f dB)%s\n", opts.target_psnr, q, db, opts.ycbcr ? " in YCbCr" : "");
         opts.quality = q < 100 ? q : 0;
         opts.target_psnr = 0;
+        if (q == 100 && opts.ycbcr) { // YCbCr does not reach the target at any quality 1..99: code losslessly, with the RCT
+            opts.ycbcr = false, opts.colour_transform = true;
+            std::printf("no YCbCr quality reaches the target: a lossless RCT file\n");
+        }
+    }
+    const double ssim_target = opts.target_ssim;
+    if (ssim_target > 0) { // the quality first (the same search FRIEncoder::encode runs), then both routes code with it
+        libfri::Device dev(opts.device);
+        std::string err;
+        fri_hip_plan *plan = dev.ok() ? dev.plan(w, h, c, err) : nullptr;
+        int32_t q = 100;
+        double v = 0;
+        int rc = plan ? fri_hip_plan_set_colour_transform(plan, opts.ycbcr ? FRI_HIP_COLOUR_YCBCR : FRI_HIP_COLOUR_NONE) : FRI_HIP_ERR_NO_DEVICE;
+        if (rc == FRI_HIP_OK) rc = fri_hip_search_quality_ssim(plan, img.data(), ssim_target, &q, &v);
+        if (rc != FRI_HIP_OK) {
+            std::fprintf(stderr, "quality search: %s\n", plan ? dev.describe(rc).c_str() : (dev.ok() ? err.c_str() : dev.error().c_str()));
+            return 1;
+        }
+        std::printf("target SSIM %.4f: quality %d (SSIM %.6f)%s\n", ssim_target, q, v, opts.ycbcr ? " in YCbCr" : "");
+        opts.quality = q < 100 ? q : 0;
+        opts.target_ssim = 0;
         if (q == 100 && opts.ycbcr) { // YCbCr does not reach the target at any quality 1..99: code losslessly, with the RCT
             opts.ycbcr = false, opts.colour_transform = true;
             std::printf("no YCbCr quality reaches the target: a lossless RCT file\n");
@@ -265,6 +289,20 @@ static int encode_image_to_file(std::vector<uint8_t> img, uint32_t w, uint32_t h
     std::printf("%ux%ux%u: %zu bytes, %.3f bits per pixel; symbol stream route end to end (context, plan, stream order, chain, emit) %.3f s; self-checks: array route, device stages (incl. plan + PCIe) %.3f s + host emit %.3f s: same bytes; decoded back in %.3f s: %s\n", w, h, c,
                 bytes.size(), 8.0 * bytes.size() / ((double)w * h), t_streamed, t_dev, t_host, t_dec, opts.quality ? "the direct lossy round trip" : "lossless");
     if (opts.quality) std::printf("quality %d: PSNR %.2f dB\n", opts.quality, psnr);
+    if (ssim_target > 0) { // the decoded image against the input, on the device (K7)
+        libfri::Device dev(opts.device);
+        std::string e;
+        fri_hip_plan *plan = dev.ok() ? dev.plan(w, h, c, e) : nullptr;
+        int64_t m[4] = {0, 0, 0, 0};
+        const int rc = plan ? fri_hip_measure_ssim(plan, img.data(), back.value.data.data(), m) : FRI_HIP_ERR_NO_DEVICE;
+        if (rc != FRI_HIP_OK) {
+            std::fprintf(stderr, "SSIM of the decoded image: %s\n", plan ? dev.describe(rc).c_str() : (dev.ok() ? e.c_str() : dev.error().c_str()));
+            return 1;
+        }
+        int64_t total = 0;
+        for (uint32_t k = 0; k < c; k++) total += m[k];
+        std::printf("decoded SSIM %.6f\n", (double)total / ((double)((uint64_t)c * (uint64_t)m[c]) * 4294967296.0));
+    }
     return 0;
 }
 
@@ -279,13 +317,14 @@ int main(int argc, char **argv) {
         }
         libfri::EncoderOpts file_opts; // parameters are fitted on the device sums (fit_parameters defaults to true)
         double bpp = 0;
-        bool has_size = false, has_bpp = false;
+        bool has_size = false, has_bpp = false, has_ssim = false;
         for (int i = 4; i < argc; i++) {
             const std::string a = argv[i];
             if (a == "--rct") file_opts.colour_transform = true;
             else if (a == "--ycbcr") file_opts.ycbcr = true;
             else if (a == "--quality" && i + 1 < argc) file_opts.quality = std::atoi(argv[++i]);
             else if (a == "--psnr" && i + 1 < argc) file_opts.target_psnr = std::atof(argv[++i]);
+            else if (a == "--ssim" && i + 1 < argc) file_opts.target_ssim = std::atof(argv[++i]), has_ssim = true;
             else if (a == "--size" && i + 1 < argc) file_opts.target_bytes = std::strtoull(argv[++i], nullptr, 10), has_size = true;
             else if (a == "--bpp" && i + 1 < argc) bpp = std::atof(argv[++i]), has_bpp = true;
             else {
@@ -299,7 +338,12 @@ int main(int argc, char **argv) {
             return 2;
         }
         const bool sized = has_size || has_bpp;
-        if (file_opts.ycbcr && (fc != 3 || file_opts.colour_transform || !(file_opts.quality || file_opts.target_psnr > 0 || sized))) {
+        if (has_ssim && (!(file_opts.target_ssim > 0 && file_opts.target_ssim <= 1) || file_opts.quality || file_opts.target_psnr > 0 || sized || file_opts.colour_transform)) {
+            std::fprintf(stderr, "encode-file: --ssim S (0 < S <= 1), not with --quality, --psnr, --size, --bpp or --rct\n");
+            return 2;
+        }
+        // (--ssim counts as a lossy target too; the message is the one --ycbcr has always printed)
+        if (file_opts.ycbcr && (fc != 3 || file_opts.colour_transform || !(file_opts.quality || file_opts.target_psnr > 0 || sized || has_ssim))) {
             std::fprintf(stderr, "encode-file: --ycbcr needs an RGB image and one of --quality, --psnr, --size or --bpp, and not --rct\n");
             return 2;
         }
@@ -346,7 +390,7 @@ int main(int argc, char **argv) {
         return 0;
     }
     if (argc < 5) {
-        std::fprintf(stderr, "usage: %s roundtrip|encode|batch|batch-frv <width> <height> <channels> [n_images | out.frv]\n       %s encode-file <in.pgm|in.ppm|in.bmp> <out.frv> [--rct | [--ycbcr] (--quality Q | --psnr DB | --size BYTES | --bpp B)]\n       %s decode-file <in.frv> <out.pgm|out.ppm|out.bmp>\n", argv[0], argv[0], argv[0]);
+        std::fprintf(stderr, "usage: %s roundtrip|encode|batch|batch-frv <width> <height> <channels> [n_images | out.frv]\n       %s encode-file <in.pgm|in.ppm|in.bmp> <out.frv> [--rct | [--ycbcr] (--quality Q | --psnr DB | --ssim S | --size BYTES | --bpp B)]\n       %s decode-file <in.frv> <out.pgm|out.ppm|out.bmp>\n", argv[0], argv[0], argv[0]);
         return 2;
     }
     const std::string cmd = argv[1];

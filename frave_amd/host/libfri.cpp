@@ -69,8 +69,12 @@ std::string coding_matrix(const EncoderOpts &opts, std::array<int32_t, 32> &q) {
     if ((opts.quality || opts.target_psnr > 0) && opts.colour_transform) return "lossy coding (quality / target_psnr) cannot be combined with colour_transform";
     if (opts.quality && opts.target_psnr > 0) return "set quality or target_psnr, not both";
     if (opts.target_bytes && (opts.quality || opts.target_psnr > 0 || opts.colour_transform)) return "target_bytes cannot be combined with quality, target_psnr or colour_transform";
+    if (!(opts.target_ssim >= 0 && opts.target_ssim <= 1)) return "target_ssim must be in (0, 1], or 0 (off)";
+    if (opts.target_ssim > 0 && (opts.quality || opts.target_psnr > 0 || opts.target_bytes || opts.colour_transform))
+        return "target_ssim cannot be combined with quality, target_psnr, target_bytes or colour_transform";
     if (opts.ycbcr && opts.colour_transform) return "ycbcr cannot be combined with colour_transform";
-    if (opts.ycbcr && !opts.quality && !(opts.target_psnr > 0) && !opts.target_bytes) return "ycbcr needs lossy coding (quality, target_psnr or target_bytes)";
+    if (opts.ycbcr && !opts.quality && !(opts.target_psnr > 0) && !opts.target_bytes && !(opts.target_ssim > 0))
+        return "ycbcr needs lossy coding (quality, target_psnr, target_bytes or target_ssim)";
     const bool ones = std::all_of(opts.quantization_matrix.begin(), opts.quantization_matrix.end(), [](int32_t v) { return v == 1; });
     if (opts.quality && !ones) return "set quality or a quantization_matrix, not both";
     q = opts.quantization_matrix;
@@ -304,6 +308,16 @@ Result<EncodedStages> FRIEncoder::encode(std::vector<uint8_t> data, uint32_t hei
             coded.ycbcr = false, coded.colour_transform = true, r.value.lossless_rct = true;
         if (coded.quality) fri_hip_quality_matrix(coded.quality, qm.data());
     }
+    if (opts_.target_ssim > 0) { // the same with the SSIM of the round trip (K7): the lowest quality that reaches it; 100 = lossless
+        int32_t q = 100;
+        double v = 0;
+        if (int rc = fri_hip_search_quality_ssim(plan, data.data(), opts_.target_ssim, &q, &v); rc != FRI_HIP_OK) return fail(dev.describe(rc));
+        coded.quality = q < 100 ? q : 0;
+        r.value.ssim = v;
+        if (q == 100 && coded.ycbcr && colorspace == ColorSpace::RGB) // YCbCr does not reach the target at any quality: a lossless file, with the RCT
+            coded.ycbcr = false, coded.colour_transform = true, r.value.lossless_rct = true;
+        if (coded.quality) fri_hip_quality_matrix(coded.quality, qm.data());
+    }
     w.metadata = coded_metadata(height, width, colorspace, coded);
     if (const std::string e = set_colour_transform(plan, w.metadata.rct, dev, w.metadata.ycbcr); !e.empty()) return fail(e);
     w.num_cells = fri_hip_plan_num_cells(plan);
@@ -483,6 +497,7 @@ Result<std::vector<uint8_t>> FRIEncoder::encode_bytes_streamed(std::vector<uint8
     if (const std::string e = coding_matrix(opts_, qm); !e.empty()) return fail(e);
     if (opts_.target_psnr > 0) return fail("target_psnr: FRIEncoder::encode only (search first, then pass the quality)");
     if (opts_.target_bytes) return fail("target_bytes: FRIEncoder::encode only (search first, then pass the quality)");
+    if (opts_.target_ssim > 0) return fail("target_ssim: FRIEncoder::encode only (search first, then pass the quality)");
     if (const std::string e = set_colour_transform(plan, md.rct, dev, md.ycbcr); !e.empty()) return fail(e);
     const uint64_t n = fri_hip_plan_num_some(plan);
     if (const std::string e = set_plan_stream_order(plan, dev); !e.empty()) return fail(e); // geometry only, once per plan (the plan is new here: Device lives for this call, as in encode())
@@ -527,8 +542,8 @@ Result<std::vector<std::vector<uint8_t>>> encode_batch_bytes(const std::vector<c
     const ImageMetadata md = coded_metadata(height, width, colorspace, opts);
     std::array<int32_t, 32> qm;
     if (!(r.error = coding_matrix(opts, qm)).empty()) return r;
-    if (opts.target_psnr > 0 || opts.target_bytes) {
-        r.error = "encode_batch_bytes: target_psnr / target_bytes are not supported (no per-image search); pass a quality";
+    if (opts.target_psnr > 0 || opts.target_bytes || opts.target_ssim > 0) {
+        r.error = "encode_batch_bytes: target_psnr / target_bytes / target_ssim are not supported (no per-image search); pass a quality";
         return r;
     }
     const uint32_t n_dev = (uint32_t)devices.size();

@@ -72,9 +72,12 @@ struct EncoderOpts { // encoder.rs:58-64
     // it and check the file the emitter writes: while it is over, one quality lower (a few steps at most; quality 1 over the budget is an error). A result
     // of 100 codes an ordinary lossless file. Not together with quality, target_psnr or colour_transform.
     uint64_t target_bytes = 0;
-    // RGB input, lossy coding only (one of quality, target_psnr, target_bytes): code Y, Cb, Cr of the irreversible JFIF transform
+    // FRIEncoder::encode only: in (0, 1] = search the lowest quality whose round trip reaches this SSIM (fri_hip_search_quality_ssim) and code with it; a
+    // result of 100 codes an ordinary lossless file, as target_psnr does. 0 = off. Not together with quality, target_psnr, target_bytes or colour_transform.
+    double target_ssim = 0;
+    // RGB input, lossy coding only (one of quality, target_psnr, target_bytes, target_ssim): code Y, Cb, Cr of the irreversible JFIF transform
     // (fri_hip_plan_set_colour_transform(FRI_HIP_COLOUR_YCBCR)) and flag the file. Not together with colour_transform. The searches run on the YCbCr planes
-    // and measure in R, G, B; a PSNR search that returns 100 codes a lossless RCT file instead (EncodedStages::lossless_rct says so); a size search covers
+    // and measure in R, G, B; a PSNR or SSIM search that returns 100 codes a lossless RCT file instead (EncodedStages::lossless_rct says so); a size search covers
     // qualities 1..99 only and never falls back to a lossless file.
     bool ycbcr = false;
     EncoderOpts() { quantization_matrix.fill(1); }
@@ -180,7 +183,8 @@ struct EncodedStages { // EncoderStage::EntropyEncoding(WaveletImage, [Vec<AnsCo
     WaveletImage image;
     std::array<std::vector<AnsContext>, 3> contexts;
     double psnr_db = 0; // with EncoderOpts::target_psnr: the PSNR of the chosen quality (image.metadata.quality; +inf for lossless)
-    bool lossless_rct = false; // with EncoderOpts::ycbcr and target_psnr: no quality 1..99 reached the target, the image was coded losslessly with the RCT
+    double ssim = 0;    // with EncoderOpts::target_ssim: the SSIM of the chosen quality (1.0 for lossless)
+    bool lossless_rct = false; // with EncoderOpts::ycbcr and target_psnr / target_ssim: no quality 1..99 reached the target, the image was coded losslessly with the RCT
     uint64_t est_bytes = 0, file_bytes = 0; // with EncoderOpts::target_bytes: the estimate of the quality the search found (0 if the file needed a lower one), the file's size
 };
 

@@ -411,6 +411,36 @@ int fri_hip_estimate_size(fri_hip_plan *plan, const uint32_t *hist, const uint64
  * quality; the bisection is all that is promised. The host form stages the pixels through the plan's buffers. */
 int fri_hip_search_quality_for_size(fri_hip_plan *plan, const uint8_t *pixels, uint64_t max_bytes, int32_t *quality, uint64_t *est_bytes);
 int fri_hip_search_quality_for_size_dev(fri_hip_plan *plan, const uint8_t *d_pixels, uint64_t max_bytes, int32_t *quality, uint64_t *est_bytes, void *stream);
+/* ---- SSIM ------------------------------------------------------------------------------------------ */
+/* The structural similarity of two rasters a (the source) and b (the reconstruction) of the plan's shape, interleaved u8 at (y W + x) C + c, each channel
+ * on its own - exact, the same bits on every run and on the host (tests/ssim_ref.py):
+ *   windows  8 x 8 pixels at origins (4 i, 4 j) with 4 i + 8 <= W, 4 j + 8 <= H: nx = W / 4 - 1 by ny = H / 4 - 1 of them (integer division; the x264 /
+ *            libvpx window set). Pixels in the last W % 4 columns or H % 4 rows are in no window.
+ *   sums     Sa, Sb, Saa, Sbb, Sab over the window's 64 pixels, integers.
+ *   value    c1 = 26634, c2 = 239708 (64^2 (0.01 x 255)^2 and 64^2 (0.03 x 255)^2, truncated):
+ *              n = (2 Sa Sb + c1) (2 (64 Sab - Sa Sb) + c2)                  int64, exact (|n| < 2^57)
+ *              d = (Sa^2 + Sb^2 + c1) (64 Saa - Sa^2 + 64 Sbb - Sb^2 + c2)   int64, exact, d > 0
+ *              v = rint((double)n / (double)d x 2^32)                        IEEE round-to-nearest-even conversions, a correctly rounded division,
+ *                                                                            an exact scaling, round half to even; |v| <= 2^32
+ *   channel  sum_c = the sum of v over the windows (int64); SSIM_c = sum_c / (2^32 nx ny).
+ *   image    SSIM = (double)(sum over c of sum_c) / ((double)(C nx ny) x 2^32): the integer sum first, then one division - channels weigh the same.
+ * Identical rasters give v = 2^32 in every window, SSIM exactly 1; the value is symmetric in a and b. Shapes with W < 8 or H < 8 (no window) or more than
+ * 2^29 windows per channel are refused with FRI_HIP_ERR_INVALID_ARGUMENT before any device check; below that cap the sum over three channels fits in int64.
+ * The rasters are taken as they are: on a YCbCr plan they are R, G, B.
+ * _dev: n_images pairs in one launch (K7, k7_ssim.hip), pair k at d_a / d_b + k x pixel_stride bytes (pixel_stride >= the plan's pixel bytes when
+ * n_images > 1); d_out [n_images][C + 1] int64 = per channel sum_c, then nx ny. Zeroes d_out on `stream`, then only enqueues: no synchronisation.
+ * The host form measures one pair, staged through the plan's buffers, into out[C + 1], and synchronises. */
+int fri_hip_measure_ssim_dev(fri_hip_plan *plan, uint32_t n_images, const uint8_t *d_a, const uint8_t *d_b, size_t pixel_stride, int64_t *d_out, void *stream);
+int fri_hip_measure_ssim(fri_hip_plan *plan, const uint8_t *a, const uint8_t *b, int64_t *out);
+/* The lowest quality whose lossy round trip reaches an SSIM of target (0 < target <= 1): K1 with fri_hip_quality_matrix(q), K3 with FRI_HIP_DEQUANT_MIDPOINT
+ * into a raster the plan owns (zero where the lattice has holes, as the decoder writes it), K7 against the source. The bisection of fri_hip_search_quality:
+ * lo = 0, hi = 100; while hi - lo > 1: mid = (lo + hi) / 2, hi = mid if SSIM(mid) >= target, else lo = mid. Returns quality = hi and its SSIM (1.0 for 100,
+ * which is never probed): at most 7 probes. 100 means "code losslessly" - on a YCbCr plan also that no quality 1..99 reaches the target.
+ * FRI_HIP_ERR_INVALID_ARGUMENT for a target that is NaN, <= 0 or > 1, for the shapes the measurement refuses and on an RCT plan; the call reads every probe
+ * back, so it synchronises `stream` and refuses a capturing one. The plan's dequantiser setting is left as it is. The host form stages the pixels
+ * through the plan's buffers. */
+int fri_hip_search_quality_ssim(fri_hip_plan *plan, const uint8_t *pixels, double target, int32_t *quality, double *ssim);
+int fri_hip_search_quality_ssim_dev(fri_hip_plan *plan, const uint8_t *d_pixels, double target, int32_t *quality, double *ssim, void *stream);
 /* Which colour transform the plan's forward and inverse entry points apply (the container's YCbCr colour space). FRI_HIP_COLOUR_NONE (default): the channels
  * are coded as they are. FRI_HIP_COLOUR_RCT (plans with C = 3 only): the reversible colour transform of JPEG-LS on interleaved R, G, B bytes, all arithmetic
  * mod 256 - lossless and 8 bit:
