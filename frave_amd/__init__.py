@@ -11,6 +11,7 @@ from .api import (  # noqa: F401
     FriHipError,
     Multi,
     Plan,
+    Plan420,
     DEQUANT_MIDPOINT,
     DEQUANT_MULTIPLY,
     DEQUANT_REFERENCE,

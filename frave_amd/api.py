@@ -33,6 +33,9 @@ SYMBOLS = [
     "fri_hip_search_quality_dev", "fri_hip_estimate_size_dev", "fri_hip_estimate_size", "fri_hip_search_quality_for_size",
     "fri_hip_search_quality_for_size_dev", "fri_hip_plan_predict_grid", "fri_hip_measure_ssim_dev", "fri_hip_measure_ssim", "fri_hip_search_quality_ssim",
     "fri_hip_search_quality_ssim_dev",
+    "fri_hip_plan420_create", "fri_hip_plan420_destroy", "fri_hip_plan420_luma", "fri_hip_plan420_chroma", "fri_hip_split420_dev", "fri_hip_merge420_dev",
+    "fri_hip_measure_distortion420_dev", "fri_hip_encode_image420_symbols", "fri_hip_decode_image420", "fri_hip_search_quality420", "fri_hip_search_quality420_dev",
+    "fri_hip_search_quality_for_size420", "fri_hip_search_quality_for_size420_dev", "fri_hip_search_quality_ssim420", "fri_hip_search_quality_ssim420_dev",
 ]
 COLOUR_NONE, COLOUR_RCT, COLOUR_YCBCR = 0, 1, 3  # fri_hip_plan_set_colour_transform (bit 0: chroma planes, bit 1: irreversible)
 DEQUANT_REFERENCE, DEQUANT_MULTIPLY, DEQUANT_MIDPOINT = 0, 1, 2  # fri_hip_plan_set_dequantiser
@@ -174,6 +177,21 @@ def load_library():
     L.fri_hip_fit_value_params_batch_dev.argtypes = [vp, u32, vp, vp, vp]
     L.fri_hip_fit_width_params_batch_dev.argtypes = [vp, u32, vp, vp, vp, vp]
     L.fri_hip_encode_image_batch_dev.argtypes = [vp, u32, vp, sz, vp, i32, vp, vp, sz, vp, vp, sz, vp, vp, vp, vp]
+    L.fri_hip_plan420_create.argtypes = [vp, u32, u32, C.POINTER(vp)]
+    L.fri_hip_plan420_destroy.argtypes = [vp]
+    L.fri_hip_plan420_luma.restype, L.fri_hip_plan420_luma.argtypes = vp, [vp]
+    L.fri_hip_plan420_chroma.restype, L.fri_hip_plan420_chroma.argtypes = vp, [vp]
+    L.fri_hip_split420_dev.argtypes = [vp, vp, vp, vp, vp]
+    L.fri_hip_merge420_dev.argtypes = [vp, vp, vp, vp, vp]
+    L.fri_hip_measure_distortion420_dev.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.fri_hip_encode_image420_symbols.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp]
+    L.fri_hip_decode_image420.argtypes = [vp, vp, i32, vp]
+    L.fri_hip_search_quality420.argtypes = [vp, vp, C.c_double, vp, vp]
+    L.fri_hip_search_quality420_dev.argtypes = [vp, vp, C.c_double, vp, vp, vp]
+    L.fri_hip_search_quality_for_size420.argtypes = [vp, vp, C.c_uint64, vp, vp]
+    L.fri_hip_search_quality_for_size420_dev.argtypes = [vp, vp, C.c_uint64, vp, vp, vp]
+    L.fri_hip_search_quality_ssim420.argtypes = [vp, vp, C.c_double, vp, vp]
+    L.fri_hip_search_quality_ssim420_dev.argtypes = [vp, vp, C.c_double, vp, vp, vp]
     _lib = L
     return L
 
@@ -361,13 +379,17 @@ class Context:
 class Plan:
     """fri_hip_plan: geometry of one (width, height, channels). ctx=None gives a host-only plan (getters only)."""
 
-    def __init__(self, ctx, width, height, channels):
+    def __init__(self, ctx, width, height, channels, _handle=None):
         self._h = None
         self.ctx = ctx
         self.width, self.height, self.channels = width, height, channels
         self.colour_transform = COLOUR_NONE
-        h = C.c_void_p()
-        _check(load_library().fri_hip_plan_create(ctx._h if ctx else None, width, height, channels, C.byref(h)), "fri_hip_plan_create", ctx)
+        self._owns = _handle is None
+        if _handle is None:
+            h = C.c_void_p()
+            _check(load_library().fri_hip_plan_create(ctx._h if ctx else None, width, height, channels, C.byref(h)), "fri_hip_plan_create", ctx)
+        else:  # a view of a plan somebody else owns (Plan420's inner plans): close() leaves it alone
+            h = C.c_void_p(_handle)
         self._h = h
         L = load_library()
         self.num_cells = L.fri_hip_plan_num_cells(h)
@@ -379,7 +401,8 @@ class Plan:
 
     def close(self):
         if self._h:
-            load_library().fri_hip_plan_destroy(self._h)
+            if self._owns:
+                load_library().fri_hip_plan_destroy(self._h)
             self._h = None
 
     def __del__(self):
@@ -759,3 +782,102 @@ class Plan:
         _check(load_library().fri_hip_time_transform_quant_dev(self._h, n_images, d_pixels, pixel_stride, _p(q), d_coefs, coef_stride, iters, stream,
                                                                C.byref(us)), "fri_hip_time_transform_quant_dev", self.ctx)
         return us.value
+
+
+class Plan420:
+    """fri_hip_plan420: lossy YCbCr coding with 4:2:0 chroma subsampling (include/fri_hip.h has the format). Owns two ordinary C = 1 plans, .luma (W x H) and
+    .chroma (cw x ch; Cb and Cr are planes 0 and 1 of a batch) - Plan views that do not own their handle and die with this object. ctx=None gives a
+    host-only plan (getters only)."""
+
+    def __init__(self, ctx, width, height):
+        self._h = None
+        self.ctx = ctx
+        self.width, self.height = width, height
+        self.cw, self.ch = (width + 1) // 2, (height + 1) // 2
+        h = C.c_void_p()
+        L = load_library()
+        _check(L.fri_hip_plan420_create(ctx._h if ctx else None, width, height, C.byref(h)), "fri_hip_plan420_create", ctx)
+        self._h = h
+        self.luma = Plan(ctx, width, height, 1, _handle=L.fri_hip_plan420_luma(h))
+        self.chroma = Plan(ctx, self.cw, self.ch, 1, _handle=L.fri_hip_plan420_chroma(h))
+        self.pixel_bytes = 3 * width * height
+        self.plane_bytes = width * height + 2 * self.cw * self.ch
+        self.num_symbols = self.luma.num_some + 2 * self.chroma.num_some
+        self.coef_count = (self.luma.num_cells + 2 * self.chroma.num_cells) * 512
+
+    def close(self):
+        if self._h:
+            self.luma.close()
+            self.chroma.close()
+            load_library().fri_hip_plan420_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_stream_order(self):
+        """fri_hip_plan_set_stream_order on both inner plans (encode_image420_symbols needs it)."""
+        self.luma.set_stream_order()
+        self.chroma.set_stream_order()
+
+    # ---- device-pointer entry points (pointers are ints) --------------------------------------------
+    def split420_dev(self, d_rgb, d_y, d_cbcr, stream=0):
+        """fri_hip_split420_dev: R, G, B [H][W][3] -> Y [H][W] and Cb, Cr [ch][cw] each (contiguous); only enqueues."""
+        _check(load_library().fri_hip_split420_dev(self._h, d_rgb, d_y, d_cbcr, stream), "fri_hip_split420_dev", self.ctx)
+
+    def merge420_dev(self, d_y, d_cbcr, d_rgb, stream=0):
+        """fri_hip_merge420_dev: the three planes -> R, G, B with the chroma planes upsampled by the (3, 1) / 4 triangle filter; only enqueues."""
+        _check(load_library().fri_hip_merge420_dev(self._h, d_y, d_cbcr, d_rgb, stream), "fri_hip_merge420_dev", self.ctx)
+
+    def measure_distortion420_dev(self, d_y, d_cbcr, d_reference_rgb, d_out, stream=0):
+        """fri_hip_measure_distortion420_dev: the merge compared with d_reference_rgb instead of written; d_out uint64 [7] (device) as
+        Plan.measure_distortion_dev at C = 3, d_out[6] = W H."""
+        _check(load_library().fri_hip_measure_distortion420_dev(self._h, d_y, d_cbcr, d_reference_rgb, d_out, stream), "fri_hip_measure_distortion420_dev", self.ctx)
+
+    # ---- host-pointer entry points ----------------------------------------------------------------
+    def encode_image420_symbols(self, pixels, quality):
+        """fri_hip_encode_image420_symbols: (symbols uint16 [n_y + 2 n_c] = Y, Cb, Cr streams, value_params [3][3][6], width_params [3][3][6],
+        hist [3][10][1024], oob [3]); needs set_stream_order()."""
+        px = np.ascontiguousarray(pixels, np.uint8).reshape(-1)
+        assert px.size == self.pixel_bytes
+        vp, wp = np.zeros((3, 3, 6), np.float32), np.zeros((3, 3, 6), np.float32)
+        sym = np.empty(self.num_symbols, np.uint16)
+        hist = np.empty((3, 10, 1024), np.uint32)
+        oob = np.zeros(3, np.uint64)
+        _check(load_library().fri_hip_encode_image420_symbols(self._h, _p(px), int(quality), _p(vp), _p(wp), _p(sym), _p(hist), _p(oob)),
+               "fri_hip_encode_image420_symbols", self.ctx)
+        return sym, vp, wp, hist, oob
+
+    def decode_image420(self, coefs, quality):
+        """fri_hip_decode_image420: coefs int32 = Y [F_y][512], Cb [F_c][512], Cr [F_c][512] (flat) -> pixels uint8 [H * W * 3]."""
+        co = np.ascontiguousarray(coefs, np.int32).reshape(-1)
+        assert co.size == self.coef_count
+        out = np.empty(self.pixel_bytes, np.uint8)
+        _check(load_library().fri_hip_decode_image420(self._h, _p(co), int(quality), _p(out)), "fri_hip_decode_image420", self.ctx)
+        return out
+
+    def _search(self, name, pixels, target, ctype, stream):
+        qual, v = C.c_int32(0), ctype(0)
+        L = load_library()
+        if isinstance(pixels, int):
+            _check(getattr(L, name + "_dev")(self._h, pixels, target, C.byref(qual), C.byref(v), stream), name + "_dev", self.ctx)
+        else:
+            px = np.ascontiguousarray(pixels, np.uint8)
+            assert px.size == self.pixel_bytes
+            _check(getattr(L, name)(self._h, _p(px), target, C.byref(qual), C.byref(v)), name, self.ctx)
+        return qual.value, v.value
+
+    def search_quality(self, pixels, target_db, stream=0):
+        """fri_hip_search_quality420[_dev] (pixels: a host array or a device pointer): (quality, RGB PSNR in dB); 100 = code losslessly."""
+        return self._search("fri_hip_search_quality420", pixels, float(target_db), C.c_double, stream)
+
+    def search_quality_ssim(self, pixels, target, stream=0):
+        """fri_hip_search_quality_ssim420[_dev]: (quality, RGB SSIM); 100 = code losslessly."""
+        return self._search("fri_hip_search_quality_ssim420", pixels, float(target), C.c_double, stream)
+
+    def search_quality_for_size(self, pixels, max_bytes, stream=0):
+        """fri_hip_search_quality_for_size420[_dev]: (quality, estimated bytes); FriHipError with code -7 when nothing fits."""
+        return self._search("fri_hip_search_quality_for_size420", pixels, int(max_bytes), C.c_uint64, stream)

@@ -163,6 +163,15 @@ hipError_t launch_rate_estimate(uint32_t n_images, uint32_t channels, const uint
 hipError_t launch_ssim(uint32_t n_images, const uint8_t *a, const uint8_t *b, size_t pixel_stride, uint32_t width, uint32_t height, uint32_t channels,
                        unsigned long long *out, hipStream_t stream);
 
+// K8 (k8_chroma420.hip): 4:2:0 chroma subsampling on rasters (include/fri_hip.h has the format). Split: interleaved R, G, B of width x height -> y [H][W] and
+// cbcr = Cb [ch][cw] then Cr [ch][cw], cw = (W + 1) / 2, ch = (H + 1) / 2. Merge: the reverse, with the chroma planes upsampled by the (3, 1) / 4 triangle
+// filter. measure != NULL: the merge's MEASURE instance - `rgb` is the reference raster and only read; measure[2 c] += the sum of squared differences of
+// channel c, measure[2 c + 1] = max(.., largest absolute difference), measure[6] += pixels. The caller zeroes it - with launch_clear_sums (n <= 64 words). Any shape,
+// any pointer alignment.
+hipError_t launch_clear_sums(unsigned long long *sums, uint32_t n, hipStream_t stream);
+hipError_t launch_split420(const uint8_t *rgb, uint32_t width, uint32_t height, uint8_t *y, uint8_t *cbcr, hipStream_t stream);
+hipError_t launch_merge420(const uint8_t *y, const uint8_t *cbcr, uint32_t width, uint32_t height, uint8_t *rgb, hipStream_t stream, unsigned long long *measure = nullptr);
+
 // K2's per-node neighbour offsets (LDS halfword offsets relative to the own slot, two per word) from the static neighbour table
 void build_lf_deltas(const uint16_t *nbr_table, int8_t *out /* [8] */);
 void build_gather_tables(const uint16_t *nbr_table, uint32_t *gather_off /* [512][4] */, uint16_t *pair_pos /* [256] */, uint16_t *heap_of_pos /* [512] */);

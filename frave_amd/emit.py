@@ -10,6 +10,7 @@ _SO = os.path.join(_HERE, "libfri_emit.so")
 _lib = None
 RCT = 0x100  # FRI_EMIT_RCT: `channels = 3 | RCT` - the planes are Y, Cb, Cr of the reversible colour transform (include/fri_emit.h)
 YCBCR = 0x400  # FRI_EMIT_YCBCR: `channels = 3 | YCBCR | QUALITY(q)` - the planes are Y, Cb, Cr of the irreversible JFIF transform (lossy files only)
+S420 = 0x800  # FRI_EMIT_420: `channels = 3 | YCBCR | S420 | QUALITY(q)` in encode_image_from_streams - 4:2:0, Cb and Cr are streams of the half-resolution lattice
 
 
 def QUALITY(q):
@@ -17,8 +18,8 @@ def QUALITY(q):
     return int(q) << 16
 
 
-def _arg(channels, rct, quality, ycbcr=False):
-    return channels | (RCT if rct else 0) | (YCBCR if ycbcr else 0) | QUALITY(quality or 0)
+def _arg(channels, rct, quality, ycbcr=False, s420=False):
+    return channels | (RCT if rct else 0) | (YCBCR if ycbcr else 0) | (S420 if s420 else 0) | QUALITY(quality or 0)
 
 
 class EmitError(RuntimeError):
@@ -123,19 +124,20 @@ def stream_order(centers, valid_mask):
     return out[: n.value].copy()
 
 
-def encode_image_from_streams(width, height, streams, hist, value_params, width_params, rct=False, quality=0, ycbcr=False):
+def encode_image_from_streams(width, height, streams, hist, value_params, width_params, rct=False, quality=0, ycbcr=False, n_luma=None):
     """.frv bytes from the device's symbol streams: streams uint16 [C][n_symbols] (bucket << 10 | symbol), hist [C][10][1024], params [C][3][6].
-    rct, quality, ycbcr: see encode_image."""
+    rct, quality, ycbcr: see encode_image. n_luma: a 4:2:0 file (implies the flag; needs ycbcr and a quality) - streams is the concatenation Y [n_luma],
+    Cb [n_c], Cr [n_c] that Plan420.encode_image420_symbols returns; the emitter works n_c out from the geometry."""
     st = np.ascontiguousarray(streams, np.uint16)
     h = np.ascontiguousarray(hist, np.uint32)
     channels = h.size // 10240
-    n_symbols = st.size // channels
+    n_symbols = st.size // channels if n_luma is None else int(n_luma)
     vp, wp = np.ascontiguousarray(value_params, np.float32), np.ascontiguousarray(width_params, np.float32)
-    assert st.size == channels * n_symbols and vp.size == channels * 18 and wp.size == channels * 18
+    assert (n_luma is not None or st.size == channels * n_symbols) and vp.size == channels * 18 and wp.size == channels * 18
     n = C.c_size_t(0)
     err = C.create_string_buffer(256)
     out = np.empty(st.size * 4 + channels * (10 * 2070 + 256) + 64, np.uint8)
-    rc = load_library().fri_emit_encode_image_from_streams(width, height, _arg(channels, rct, quality, ycbcr), _p(st), n_symbols, _p(h), _p(vp), _p(wp), _p(out), out.size, C.addressof(n), err, 256)
+    rc = load_library().fri_emit_encode_image_from_streams(width, height, _arg(channels, rct, quality, ycbcr, n_luma is not None), _p(st), n_symbols, _p(h), _p(vp), _p(wp), _p(out), out.size, C.addressof(n), err, 256)
     if rc != 0:
         raise EmitError(err.value.decode() or f"fri_emit_encode_image_from_streams: {rc}")
     return out[: n.value].tobytes()
@@ -165,11 +167,13 @@ def rans_selfcheck(n_symbols, seed=1):
 class DecodedImage(tuple):
     """(width, height, channels, centers, coefs), and .rct: True if the planes are Y, Cb, Cr of the reversible colour transform; .quality: 0 for a
     lossless file, else the quality 1..99 whose matrix quantised the planes (decode with the midpoint dequantiser); .ycbcr: True if the planes are Y, Cb, Cr
-    of the irreversible JFIF transform (decode with COLOUR_YCBCR)."""
+    of the irreversible JFIF transform (decode with COLOUR_YCBCR); .s420: True for a 4:2:0 file - coefs is then the tuple (Y [F_y][512], Cb [F_c][512],
+    Cr [F_c][512]), centers the luma lattice's (decode with Plan420.decode_image420 of the three concatenated)."""
 
     rct = False
     quality = 0
     ycbcr = False
+    s420 = False
 
 
 def decode_image(frv):
@@ -186,14 +190,24 @@ def decode_image(frv):
     rct = bool(c & RCT)
     ycbcr = bool(c & YCBCR)
     quality = (c >> 16) & 0x7F
+    s420 = bool(c & S420)
     c &= 0xFF
-    coefs = np.empty((c, f, 512), np.int32)
+    if s420:  # F_c: the cells of the half-resolution lattice, from a host-only subsampled plan (no GPU involved)
+        from .api import Plan420
+
+        sub = Plan420(None, w, h)
+        fc = sub.chroma.num_cells
+        sub.close()
+        coefs = np.empty((f + 2 * fc, 512), np.int32)
+    else:
+        coefs = np.empty((c, f, 512), np.int32)
     centers = np.empty((f, 2), np.int32)
     rc = L.fri_emit_decode_image(_p(data), data.size, _p(info), _p(coefs), coefs.size, _p(centers), err, 256)
     if rc != 0:
         raise EmitError(err.value.decode() or f"fri_emit_decode_image: {rc}")
-    out = DecodedImage((w, h, c, centers, coefs))
+    out = DecodedImage((w, h, c, centers, (coefs[:f], coefs[f:f + fc], coefs[f + fc:]) if s420 else coefs))
     out.rct = rct
     out.quality = quality
     out.ycbcr = ycbcr
+    out.s420 = s420
     return out

@@ -618,12 +618,13 @@ std::string encode_channel_from_stream(const uint16_t *stream, size_t n, const u
     return "";
 }
 
-std::string encode_channels_from_streams(uint32_t channels, const uint16_t *streams, size_t n_symbols, const uint32_t *hist, std::vector<ChannelStream> &out) {
+std::string encode_channels_from_streams(uint32_t channels, const uint16_t *streams, size_t n_symbols, const uint32_t *hist, std::vector<ChannelStream> &out, size_t n_chroma) {
     out.assign(channels, ChannelStream{});
     std::vector<std::string> errs(channels);
     std::vector<std::thread> workers;
+    const size_t n_rest = n_chroma ? n_chroma : n_symbols; // symbols of every channel behind the first
     for (uint32_t ch = 1; ch < channels; ch++)
-        workers.emplace_back([&, ch] { errs[ch] = encode_channel_from_stream(streams + (size_t)ch * n_symbols, n_symbols, hist + (size_t)ch * kContexts * kAlphabet, out[ch]); });
+        workers.emplace_back([&, ch] { errs[ch] = encode_channel_from_stream(streams + n_symbols + (size_t)(ch - 1) * n_rest, n_rest, hist + (size_t)ch * kContexts * kAlphabet, out[ch]); });
     if (channels) errs[0] = encode_channel_from_stream(streams, n_symbols, hist, out[0]);
     for (std::thread &t : workers) t.join();
     for (uint32_t ch = 0; ch < channels; ch++)
@@ -790,6 +791,53 @@ std::string count_cells(uint32_t width, uint32_t height, uint32_t channels, uint
     return err;
 }
 
+std::string lattice_counts(uint32_t width, uint32_t height, uint32_t &n_cells, uint64_t &n_some) {
+    struct Entry {
+        uint32_t width, height, n_cells;
+        uint64_t n_some;
+    };
+    static std::mutex mu;
+    static std::vector<Entry> cache;
+    {
+        std::lock_guard<std::mutex> lock(mu);
+        for (const Entry &e : cache)
+            if (e.width == width && e.height == height) return n_cells = e.n_cells, n_some = e.n_some, "";
+    }
+    fri::Geometry g;
+    const std::string err = fri::build_geometry(width, height, 1, fri::TilingParams{}, g);
+    if (!err.empty()) return err;
+    n_cells = (uint32_t)g.centers.size(), n_some = g.n_some;
+    std::lock_guard<std::mutex> lock(mu);
+    if (cache.size() >= 16) cache.erase(cache.begin());
+    cache.push_back(Entry{width, height, n_cells, n_some});
+    return "";
+}
+
+// A 4:2:0 file: channel 0 on the lattice of the image, channels 1 and 2 on the lattice of the half-resolution planes, each with its own geometry and order.
+static std::string decode_parsed_420(const ParsedImage &img, DecodedImage &out) {
+    fri::Geometry gy, gc;
+    std::string err = fri::build_geometry(img.width, img.height, 1, fri::TilingParams{}, gy);
+    if (err.empty()) err = fri::build_geometry((img.width + 1) / 2, (img.height + 1) / 2, 1, fri::TilingParams{}, gc);
+    if (!err.empty()) return err;
+    const size_t Fy = gy.centers.size(), Fc = gc.centers.size();
+    out.n_cells = (uint32_t)Fy, out.n_cells_chroma = (uint32_t)Fc;
+    out.centers.resize(Fy * 2);
+    for (size_t c = 0; c < Fy; c++) out.centers[2 * c] = gy.centers[c].x, out.centers[2 * c + 1] = gy.centers[c].y;
+    std::vector<int32_t> cc(Fc * 2);
+    for (size_t c = 0; c < Fc; c++) cc[2 * c] = gc.centers[c].x, cc[2 * c + 1] = gc.centers[c].y;
+    out.coefs.assign((Fy + 2 * Fc) * kNodes, 0);
+    const auto order_y = shared_symbol_order(out.centers.data(), (uint32_t)Fy), order_c = shared_symbol_order(cc.data(), (uint32_t)Fc);
+    std::string errs[3];
+    std::vector<std::thread> workers;
+    for (uint32_t ch = 1; ch < 3; ch++)
+        workers.emplace_back([&, ch] { errs[ch] = decode_channel(gc, *order_c, img.channels[ch], img.params[ch], out.coefs.data() + (Fy + (ch - 1) * Fc) * kNodes); });
+    errs[0] = decode_channel(gy, *order_y, img.channels[0], img.params[0], out.coefs.data());
+    for (std::thread &t : workers) t.join();
+    for (uint32_t ch = 0; ch < 3; ch++)
+        if (!errs[ch].empty()) return "channel " + std::to_string(ch) + ": " + errs[ch];
+    return "";
+}
+
 std::string decode_image(const std::vector<uint8_t> &frv, DecodedImage &out) {
     ParsedImage img;
     const std::string err = deserialize(frv, img);
@@ -803,14 +851,18 @@ std::string decode_parsed(const ParsedImage &img, DecodedImage &out) {
     for (const ChannelStream &c : img.channels)
         for (const AnsContext &a : c.contexts)
             if (a.max_freq_bits == 0) return "Malformed image bytes"; // fewer than ten EHD segments
+    out.height = img.height, out.width = img.width, out.colorspace = img.colorspace, out.channels = channels;
+    out.rct = img.rct;
+    out.quality = img.quality;
+    out.ycbcr = img.ycbcr;
+    out.s420 = img.s420;
+    out.params = img.params;
+    if (img.s420) return decode_parsed_420(img, out);
     fri::Geometry g;
     err = fri::build_geometry(img.width, img.height, channels, fri::TilingParams{}, g);
     if (!err.empty()) return err;
     const size_t F = g.centers.size(), plane = F * kNodes;
-    out.height = img.height, out.width = img.width, out.colorspace = img.colorspace, out.channels = channels, out.n_cells = (uint32_t)F;
-    out.rct = img.rct;
-    out.quality = img.quality;
-    out.ycbcr = img.ycbcr;
+    out.n_cells = (uint32_t)F;
     out.centers.resize(F * 2);
     for (size_t c = 0; c < F; c++) out.centers[2 * c] = g.centers[c].x, out.centers[2 * c + 1] = g.centers[c].y;
     out.coefs.assign(channels * plane, 0);
@@ -846,12 +898,12 @@ constexpr uint8_t kEHD[2] = {0xFF, 0xB2}, kDAT[2] = {0xFF, 0xB4}, kEOC[2] = {0xF
 } // namespace
 
 std::vector<uint8_t> serialize(uint32_t height, uint32_t width, ColorSpaceCode cs, const std::vector<ChannelStream> &channels, const std::vector<ChannelParams> &params,
-                               bool rct, uint32_t quality, bool ycbcr) {
+                               bool rct, uint32_t quality, bool ycbcr, bool s420) {
     std::vector<uint8_t> s;
     s.insert(s.end(), {'f', 'r', 'i', 'f'});
     put_u32(s, height);
     put_u32(s, width);
-    put_u32(s, (uint32_t)cs << 30 | 1u << 28 | (rct ? kMdatRct : 0u) | (ycbcr ? kMdatYcbcr : 0u) | (quality & kMdatQualityMask) << kMdatQualityShift); // variant: TameTwindragon = 0b01 (images.rs:49-55)
+    put_u32(s, (uint32_t)cs << 30 | 1u << 28 | (rct ? kMdatRct : 0u) | (ycbcr ? kMdatYcbcr : 0u) | (s420 ? kMdat420 : 0u) | (quality & kMdatQualityMask) << kMdatQualityShift); // variant: TameTwindragon = 0b01 (images.rs:49-55)
     for (size_t ch = 0; ch < channels.size(); ch++) {
         s.insert(s.end(), kPRD, kPRD + 2);
         for (int g = 0; g < 3; g++)
@@ -895,10 +947,11 @@ std::string deserialize(const std::vector<uint8_t> &b, ParsedImage &out) {
     out.colorspace = mdat >> 30 & 3u;
     out.variant = mdat >> 28 & 3u;
     if (out.colorspace == 0 || out.variant == 0) return "Invalid metadata";
-    out.rct = out.colorspace == kYCbCr && (mdat & kMdatRct); // (bits 2..7 and 15..27 stay ignored, and bit 1 outside YCbCr)
+    out.rct = out.colorspace == kYCbCr && (mdat & kMdatRct); // (bits 3..7 and 15..27 stay ignored, and bits 1 and 2 outside YCbCr)
     out.ycbcr = out.colorspace == kYCbCr && (mdat & kMdatYcbcr);
+    out.s420 = out.colorspace == kYCbCr && (mdat & kMdat420);
     out.quality = mdat >> kMdatQualityShift & kMdatQualityMask;
-    if (out.quality >= 100 || (out.ycbcr && (out.rct || out.quality == 0))) return "Invalid metadata";
+    if (out.quality >= 100 || (out.ycbcr && (out.rct || out.quality == 0)) || (out.s420 && (out.rct || !out.ycbcr))) return "Invalid metadata";
     ChannelStream cur;
     ChannelParams prm{};
     int n_ctx = 0;

@@ -122,8 +122,9 @@ std::string encode_channels(const SymbolOrder &order, uint32_t channels, const i
 // the 9 bytes per node of (coefficient, prediction, bucket), and the emitter is the pure rANS loop.
 std::vector<uint32_t> stream_order(const SymbolOrder &order, const uint32_t *valid_mask /* [n_cells][16] */);
 std::string encode_channel_from_stream(const uint16_t *stream, size_t n_symbols, const uint32_t *hist, ChannelStream &out);
+// n_chroma != 0 (4:2:0 files, three channels): channels 1 and 2 are streams of n_chroma symbols each, directly behind channel 0's n_symbols.
 std::string encode_channels_from_streams(uint32_t channels, const uint16_t *streams /* [channels][n_symbols] */, size_t n_symbols, const uint32_t *hist,
-                                         std::vector<ChannelStream> &out);
+                                         std::vector<ChannelStream> &out, size_t n_chroma = 0);
 // The (symbol, bucket) sequence in stream order (what encode_channel feeds to the coder); for self-checks.
 void channel_symbols(const SymbolOrder &order, const int32_t *coefs, const uint8_t *bucket, const int32_t *prediction, std::vector<uint16_t> &symbols,
                      std::vector<uint8_t> &buckets);
@@ -144,13 +145,21 @@ constexpr uint32_t kMdatQualityShift = 8, kMdatQualityMask = 0x7Fu;
 // Bit 1 of the metadata word, with cs = kYCbCr: the planes are Y, Cb, Cr of the irreversible JFIF transform (FRI_HIP_COLOUR_YCBCR) - a lossy file only
 // (quality 1..99), never together with kMdatRct. Bit 1 of a Luma or RGB file stays ignored.
 constexpr uint32_t kMdatYcbcr = 2u;
+// Bit 2 of the metadata word, with cs = kYCbCr and kMdatYcbcr: 4:2:0 chroma subsampling (include/fri_hip.h) - channel 0 is a stream of the width x height lattice,
+// channels 1 and 2 are streams of the (width + 1) / 2 x (height + 1) / 2 lattice. Without kMdatYcbcr or with kMdatRct it is invalid; bit 2 of a Luma or RGB file
+// stays ignored.
+constexpr uint32_t kMdat420 = 4u;
 std::vector<uint8_t> serialize(uint32_t height, uint32_t width, ColorSpaceCode cs, const std::vector<ChannelStream> &channels,
-                               const std::vector<ChannelParams> &params, bool rct = false, uint32_t quality = 0, bool ycbcr = false);
+                               const std::vector<ChannelParams> &params, bool rct = false, uint32_t quality = 0, bool ycbcr = false, bool s420 = false);
+// (cells, Some nodes per channel) of the lattice of a width x height image, from a small process-wide cache: what the 4:2:0 paths need to know of the
+// chroma lattice. Returns "" or the geometry's error.
+std::string lattice_counts(uint32_t width, uint32_t height, uint32_t &n_cells, uint64_t &n_some);
 struct ParsedImage {
     uint32_t height = 0, width = 0, colorspace = 0, variant = 0;
     bool rct = false; // kYCbCr with kMdatRct set
     uint32_t quality = 0; // 0 = lossless, 1..99 (bits 8..14)
     bool ycbcr = false; // kYCbCr with kMdatYcbcr set
+    bool s420 = false;  // ... and kMdat420: channels 1 and 2 are coded on the half-resolution lattice
     std::vector<ChannelStream> channels; // contexts rebuilt from (max_freq_bits, off_distribution_values) like serialize.rs:214-237
     std::vector<ChannelParams> params;
 };
@@ -168,7 +177,9 @@ struct DecodedImage {
     bool rct = false; // the planes are Y, Cb, Cr of the reversible colour transform (ParsedImage::rct)
     uint32_t quality = 0; // ParsedImage::quality
     bool ycbcr = false; // the planes are Y, Cb, Cr of the irreversible JFIF transform (ParsedImage::ycbcr)
-    std::vector<int32_t> centers;     // [n_cells][2], canonical order (the one fri_hip_plan_centers reports)
+    bool s420 = false;  // 4:2:0 (ParsedImage::s420): coefs = Y [n_cells][512], Cb [n_cells_chroma][512], Cr [n_cells_chroma][512] - what fri_hip_decode_image420 takes
+    uint32_t n_cells_chroma = 0;
+    std::vector<int32_t> centers;     // [n_cells][2], canonical order (the one fri_hip_plan_centers reports); 4:2:0: the luma lattice's
     std::vector<int32_t> coefs;       // [channels][n_cells][512]: what fri_hip_inverse_transform takes
     std::vector<ChannelParams> params;
 };

@@ -306,6 +306,55 @@ static int encode_image_to_file(std::vector<uint8_t> img, uint32_t w, uint32_t h
     return 0;
 }
 
+// encode-file --420: lossy YCbCr with 4:2:0 chroma subsampling (libfri::encode_bytes_420). Self-check: the file decodes (FRIDecoder) to the direct round trip at
+// its quality (libfri::round_trip_420: host split, forward and inverse kernels, merge) - or, for the lossless fallback, to the input.
+static int encode_image_420_to_file(const std::vector<uint8_t> &img, uint32_t w, uint32_t h, const libfri::EncoderOpts &opts, const char *out_path) {
+    auto t0 = std::chrono::steady_clock::now();
+    auto enc = libfri::encode_bytes_420(img, h, w, opts);
+    const double t_enc = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (!enc.ok) {
+        std::fprintf(stderr, "%s\n", enc.error.c_str());
+        return 1;
+    }
+    const std::vector<uint8_t> &bytes = enc.value.bytes;
+    if (opts.target_psnr > 0) std::printf("target %.2f dB: quality %d (%.2f dB) in 4:2:0\n", opts.target_psnr, enc.value.lossless_rct ? 100 : enc.value.quality, enc.value.psnr_db);
+    if (opts.target_ssim > 0) std::printf("target SSIM %.4f: quality %d (SSIM %.6f) in 4:2:0\n", opts.target_ssim, enc.value.lossless_rct ? 100 : enc.value.quality, enc.value.ssim);
+    if (opts.target_bytes)
+        std::printf("target %llu bytes: quality %d, estimate %llu bytes, file %zu bytes\n", (unsigned long long)opts.target_bytes, enc.value.quality, (unsigned long long)enc.value.est_bytes, bytes.size());
+    if (enc.value.lossless_rct) std::printf("no 4:2:0 quality reaches the target: a lossless RCT file\n");
+    auto back = libfri::FRIDecoder().decode(bytes, opts);
+    std::vector<uint8_t> expected = img;
+    if (!enc.value.lossless_rct && back.ok) {
+        auto direct = libfri::round_trip_420(img, h, w, enc.value.quality, opts.device);
+        if (!direct.ok) {
+            std::fprintf(stderr, "self-check failed: direct round trip: %s\n", direct.error.c_str());
+            return 1;
+        }
+        expected = std::move(direct.value.data);
+    }
+    if (!back.ok || back.value.data != expected) {
+        std::fprintf(stderr, "self-check failed: %s\n", back.ok ? "decoded image differs from the direct 4:2:0 round trip" : back.error.c_str());
+        return 1;
+    }
+    if (opts.target_bytes && bytes.size() > opts.target_bytes) {
+        std::fprintf(stderr, "self-check failed: %zu bytes over the budget of %llu\n", bytes.size(), (unsigned long long)opts.target_bytes);
+        return 1;
+    }
+    double sse = 0;
+    for (size_t i = 0; i < img.size(); i++) sse += ((double)back.value.data[i] - img[i]) * ((double)back.value.data[i] - img[i]);
+    if (FILE *f = std::fopen(out_path, "wb")) {
+        std::fwrite(bytes.data(), 1, bytes.size(), f);
+        std::fclose(f);
+    } else {
+        std::fprintf(stderr, "cannot write %s\n", out_path);
+        return 1;
+    }
+    std::printf("%ux%ux3 4:2:0: %zu bytes, %.3f bits per pixel; search, device chain and emit %.3f s; self-check: decodes to %s\n", w, h, bytes.size(), 8.0 * bytes.size() / ((double)w * h),
+                t_enc, enc.value.lossless_rct ? "the input" : "the direct 4:2:0 round trip");
+    if (!enc.value.lossless_rct) std::printf("quality %d: PSNR %.2f dB\n", enc.value.quality, sse > 0 ? 10.0 * std::log10(255.0 * 255.0 * (double)img.size() / sse) : HUGE_VAL);
+    return 0;
+}
+
 int main(int argc, char **argv) {
     if (argc >= 4 && std::string(argv[1]) == "encode-file") {
         std::vector<uint8_t> img;
@@ -317,10 +366,11 @@ int main(int argc, char **argv) {
         }
         libfri::EncoderOpts file_opts; // parameters are fitted on the device sums (fit_parameters defaults to true)
         double bpp = 0;
-        bool has_size = false, has_bpp = false, has_ssim = false;
+        bool has_size = false, has_bpp = false, has_ssim = false, sub420 = false;
         for (int i = 4; i < argc; i++) {
             const std::string a = argv[i];
             if (a == "--rct") file_opts.colour_transform = true;
+            else if (a == "--420") sub420 = file_opts.ycbcr = true; // 4:2:0 implies YCbCr
             else if (a == "--ycbcr") file_opts.ycbcr = true;
             else if (a == "--quality" && i + 1 < argc) file_opts.quality = std::atoi(argv[++i]);
             else if (a == "--psnr" && i + 1 < argc) file_opts.target_psnr = std::atof(argv[++i]);
@@ -352,6 +402,7 @@ int main(int argc, char **argv) {
             std::fprintf(stderr, "encode-file: --size BYTES (> 0) or --bpp B (> 0), not both, and neither with --quality, --psnr or --rct\n");
             return 2;
         }
+        if (sub420) return encode_image_420_to_file(img, fw, fh, file_opts, argv[3]); // (the --ycbcr checks above hold: an RGB image, a lossy target, no --rct)
         return encode_image_to_file(std::move(img), fw, fh, fc, file_opts, argv[3]);
     }
     if (argc >= 4 && std::string(argv[1]) == "decode-file") {
@@ -390,7 +441,7 @@ int main(int argc, char **argv) {
         return 0;
     }
     if (argc < 5) {
-        std::fprintf(stderr, "usage: %s roundtrip|encode|batch|batch-frv <width> <height> <channels> [n_images | out.frv]\n       %s encode-file <in.pgm|in.ppm|in.bmp> <out.frv> [--rct | [--ycbcr] (--quality Q | --psnr DB | --ssim S | --size BYTES | --bpp B)]\n       %s decode-file <in.frv> <out.pgm|out.ppm|out.bmp>\n", argv[0], argv[0], argv[0]);
+        std::fprintf(stderr, "usage: %s roundtrip|encode|batch|batch-frv <width> <height> <channels> [n_images | out.frv]\n       %s encode-file <in.pgm|in.ppm|in.bmp> <out.frv> [--rct | [--ycbcr | --420] (--quality Q | --psnr DB | --ssim S | --size BYTES | --bpp B)]\n       %s decode-file <in.frv> <out.pgm|out.ppm|out.bmp>\n", argv[0], argv[0], argv[0]);
         return 2;
     }
     const std::string cmd = argv[1];

@@ -22,6 +22,7 @@ Device::Device(int device) {
     }
 }
 Device::~Device() {
+    for (auto &kv : plans420_) fri_hip_plan420_destroy(kv.second);
     for (auto &kv : plans_) fri_hip_plan_destroy(kv.second);
     if (ctx_) fri_hip_ctx_destroy(ctx_);
 }
@@ -151,6 +152,21 @@ Result<WaveletImage> encode(const RasterImage &raster, const EncoderOpts &opts, 
 
 Result<RasterImage> decode(const WaveletImage &image, const EncoderOpts &opts, Device &dev) {
     Result<RasterImage> r;
+    if (image.metadata.s420) { // three planes on two lattices: the subsampled plan's inverse kernels and merge
+        fri_hip_plan420 *sub = dev.plan420(image.metadata.width, image.metadata.height, r.error);
+        if (!sub) return r;
+        const size_t want = ((size_t)fri_hip_plan_num_cells(fri_hip_plan420_luma(sub)) + 2 * (size_t)fri_hip_plan_num_cells(fri_hip_plan420_chroma(sub))) * FRI_HIP_CELL_SIZE;
+        if (image.coefficients.size() != want) {
+            r.error = "coefficient array does not match the image geometry";
+            return r;
+        }
+        r.value.metadata = ImageMetadata{image.metadata.height, image.metadata.width, ColorSpace::RGB};
+        r.value.data.resize((size_t)image.metadata.width * image.metadata.height * 3);
+        const int rc = fri_hip_decode_image420(sub, image.coefficients.data(), (int)image.metadata.quality, r.value.data.data());
+        if (rc != FRI_HIP_OK) r.error = dev.describe(rc);
+        r.ok = rc == FRI_HIP_OK;
+        return r;
+    }
     const uint32_t c = num_channels(image.metadata.colorspace);
     fri_hip_plan *plan = dev.plan(image.metadata.width, image.metadata.height, c, r.error);
     if (!plan) return r;
@@ -393,6 +409,7 @@ Result<CompressedImage> stages::serialize::decode(const std::vector<uint8_t> &by
     r.value.metadata.rct = p.rct;
     r.value.metadata.quality = p.quality;
     r.value.metadata.ycbcr = p.ycbcr;
+    r.value.metadata.s420 = p.s420;
     r.value.variant = p.variant;
     r.value.channel_data = std::move(p.channels);
     r.value.params = std::move(p.params);
@@ -407,11 +424,13 @@ Result<WaveletImage> stages::entropy_coding::decode(const CompressedImage &image
     p.colorspace = image.metadata.colorspace == ColorSpace::Luma ? emit::kLuma : image.metadata.colorspace == ColorSpace::RGB ? emit::kRGB : emit::kYCbCr;
     p.channels = image.channel_data;
     p.params = image.params;
+    p.rct = image.metadata.rct, p.quality = image.metadata.quality, p.ycbcr = image.metadata.ycbcr, p.s420 = image.metadata.s420;
     emit::DecodedImage d;
     r.error = emit::decode_parsed(p, d);
     if (!r.error.empty()) return r;
     r.value.metadata = image.metadata;
     r.value.num_cells = d.n_cells;
+    r.value.num_cells_chroma = d.n_cells_chroma;
     r.value.centers = std::move(d.centers);
     r.value.coefficients = std::move(d.coefs);
     r.value.quantized = true;
@@ -474,6 +493,127 @@ fri_hip_plan *Device::stream_plan(uint32_t width, uint32_t height, uint32_t chan
     if (!err.empty()) return nullptr;
     ordered_.push_back(p);
     return p;
+}
+
+fri_hip_plan420 *Device::plan420(uint32_t width, uint32_t height, std::string &err) {
+    if (!ctx_) {
+        err = error_;
+        return nullptr;
+    }
+    const auto key = std::make_pair(width, height);
+    auto it = plans420_.find(key);
+    if (it != plans420_.end()) return it->second;
+    fri_hip_plan420 *p = nullptr;
+    const int rc = fri_hip_plan420_create(ctx_, width, height, &p);
+    if (rc != FRI_HIP_OK) {
+        err = describe(rc);
+        return nullptr;
+    }
+    for (fri_hip_plan *inner : {fri_hip_plan420_luma(p), fri_hip_plan420_chroma(p)})
+        if (!(err = set_plan_stream_order(inner, *this)).empty()) {
+            fri_hip_plan420_destroy(p);
+            return nullptr;
+        }
+    plans420_[key] = p;
+    return p;
+}
+
+Result<Encoded420> encode_bytes_420(const std::vector<uint8_t> &rgb, uint32_t height, uint32_t width, const EncoderOpts &opts) {
+    Result<Encoded420> r;
+    auto fail = [&](const std::string &why) {
+        r.error = "Failed to decode: " + why; // sic, encoder.rs:106
+        return r;
+    };
+    const int targets = (opts.quality != 0) + (opts.target_psnr > 0) + (opts.target_ssim > 0) + (opts.target_bytes != 0);
+    if (targets != 1 || opts.colour_transform || opts.quality < 0 || opts.quality > 99 || !(opts.target_psnr >= 0) || !(opts.target_ssim >= 0 && opts.target_ssim <= 1))
+        return fail("4:2:0 coding needs exactly one of quality (1..99), target_psnr, target_ssim and target_bytes, and no colour_transform");
+    if (rgb.size() != (size_t)width * height * 3) return fail("4:2:0 coding takes width x height RGB pixels");
+    Device dev(opts.device);
+    std::string err;
+    fri_hip_plan420 *sub = dev.ok() ? dev.plan420(width, height, err) : nullptr;
+    if (!sub) return fail(dev.ok() ? err : dev.error());
+    int32_t q = opts.quality;
+    int rc = FRI_HIP_OK;
+    if (opts.target_psnr > 0) rc = fri_hip_search_quality420(sub, rgb.data(), opts.target_psnr, &q, &r.value.psnr_db);
+    if (opts.target_ssim > 0) rc = fri_hip_search_quality_ssim420(sub, rgb.data(), opts.target_ssim, &q, &r.value.ssim);
+    if (opts.target_bytes) rc = fri_hip_search_quality_for_size420(sub, rgb.data(), opts.target_bytes, &q, &r.value.est_bytes);
+    if (rc != FRI_HIP_OK) return fail(rc == FRI_HIP_ERR_OUT_OF_RANGE ? "no quality fits in target_bytes" : dev.describe(rc));
+    if (q == 100) { // no quality 1..99 reaches the target: code losslessly, with the RCT
+        EncoderOpts lossless = opts;
+        lossless.quality = 0, lossless.target_psnr = 0, lossless.target_ssim = 0, lossless.ycbcr = false, lossless.colour_transform = true;
+        auto out = FRIEncoder(lossless).encode_bytes_streamed(rgb, height, width, ColorSpace::RGB);
+        if (!out.ok) return fail(out.error);
+        r.value.bytes = std::move(out.value), r.value.lossless_rct = true, r.ok = true;
+        return r;
+    }
+    const uint64_t n_y = fri_hip_plan_num_some(fri_hip_plan420_luma(sub)), n_c = fri_hip_plan_num_some(fri_hip_plan420_chroma(sub));
+    for (;; q--) { // (a size search's file is checked: while it is over the budget, one quality lower)
+        StreamedImage im;
+        im.symbols.resize(n_y + 2 * n_c);
+        im.hist.resize(3 * 10 * 1024);
+        uint64_t oob[3] = {0, 0, 0};
+        rc = fri_hip_encode_image420_symbols(sub, rgb.data(), q, &im.vp[0][0][0], &im.wp[0][0][0], im.symbols.data(), im.hist.data(), oob);
+        if (rc != FRI_HIP_OK) return fail(dev.describe(rc));
+        if (oob[0] || oob[1] || oob[2]) return fail("symbol outside the alphabet (libfri panics, entropy_coding.rs:99)");
+        std::vector<emit::ChannelStream> streams;
+        const std::string e = emit::encode_channels_from_streams(3, im.symbols.data(), (size_t)n_y, im.hist.data(), streams, (size_t)n_c);
+        if (!e.empty()) return fail(e);
+        std::vector<emit::ChannelParams> params(3);
+        for (uint32_t ch = 0; ch < 3; ch++)
+            for (int g = 0; g < 3; g++)
+                for (int k = 0; k < 6; k++) params[ch].value[g][k] = im.vp[ch][g][k], params[ch].width[g][k] = im.wp[ch][g][k];
+        r.value.bytes = emit::serialize(height, width, emit::kYCbCr, streams, params, false, (uint32_t)q, true, true);
+        if (!opts.target_bytes || r.value.bytes.size() <= opts.target_bytes) break;
+        r.value.est_bytes = 0;
+        if (q == 1) return fail("the file of quality 1 is over target_bytes");
+    }
+    r.value.quality = q;
+    r.ok = true;
+    return r;
+}
+
+Result<RasterImage> round_trip_420(const std::vector<uint8_t> &rgb, uint32_t height, uint32_t width, int quality, int device) {
+    Result<RasterImage> r;
+    int32_t qm[32];
+    if (rgb.size() != (size_t)width * height * 3 || quality < 1 || quality > 99 || fri_hip_quality_matrix(quality, qm) != FRI_HIP_OK) {
+        r.error = "invalid argument";
+        return r;
+    }
+    Device dev(device);
+    fri_hip_plan420 *sub = dev.ok() ? dev.plan420(width, height, r.error) : nullptr;
+    if (!sub) {
+        if (!dev.ok()) r.error = dev.error();
+        return r;
+    }
+    // the format's forward steps on the host (include/fri_hip.h): per pixel Y, Cb, Cr; each chroma sample the rounded mean of its 2 x 2 block, edges replicated
+    const uint32_t W = width, H = height, cw = (W + 1) / 2, ch = (H + 1) / 2;
+    std::vector<uint8_t> y((size_t)W * H), cbcr((size_t)W * H * 2), sub_cb((size_t)cw * ch), sub_cr((size_t)cw * ch);
+    for (size_t i = 0; i < (size_t)W * H; i++) {
+        const int R = rgb[3 * i], G = rgb[3 * i + 1], B = rgb[3 * i + 2];
+        y[i] = (uint8_t)((19595 * R + 38470 * G + 7471 * B + 32768) >> 16);
+        cbcr[2 * i] = (uint8_t)((-11059 * R - 21709 * G + 32768 * B + (128 << 16) + 32767) >> 16);
+        cbcr[2 * i + 1] = (uint8_t)((32768 * R - 27439 * G - 5329 * B + (128 << 16) + 32767) >> 16);
+    }
+    for (uint32_t j = 0; j < ch; j++)
+        for (uint32_t i = 0; i < cw; i++) {
+            const size_t x0 = 2 * i, x1 = std::min(2 * i + 1, W - 1), y0 = 2 * j, y1 = std::min(2 * j + 1, H - 1);
+            const size_t at[4] = {y0 * W + x0, y0 * W + x1, y1 * W + x0, y1 * W + x1};
+            int sb = 2, sr = 2;
+            for (size_t a : at) sb += cbcr[2 * a], sr += cbcr[2 * a + 1];
+            sub_cb[(size_t)j * cw + i] = (uint8_t)(sb >> 2), sub_cr[(size_t)j * cw + i] = (uint8_t)(sr >> 2);
+        }
+    fri_hip_plan *luma = fri_hip_plan420_luma(sub), *chroma = fri_hip_plan420_chroma(sub);
+    const size_t fy = fri_hip_plan_coef_count(luma), fc = fri_hip_plan_coef_count(chroma);
+    std::vector<int32_t> coefs(fy + 2 * fc);
+    int rc = fri_hip_transform_quant(luma, y.data(), qm, coefs.data());
+    if (rc == FRI_HIP_OK) rc = fri_hip_transform_quant(chroma, sub_cb.data(), qm, coefs.data() + fy);
+    if (rc == FRI_HIP_OK) rc = fri_hip_transform_quant(chroma, sub_cr.data(), qm, coefs.data() + fy + fc);
+    r.value.metadata = ImageMetadata{height, width, ColorSpace::RGB};
+    r.value.data.resize(rgb.size());
+    if (rc == FRI_HIP_OK) rc = fri_hip_decode_image420(sub, coefs.data(), quality, r.value.data.data());
+    if (rc != FRI_HIP_OK) r.error = dev.describe(rc);
+    r.ok = rc == FRI_HIP_OK;
+    return r;
 }
 
 // FRIEncoder::encode (encoder.rs:87-109) end to end through the symbol stream route: the device runs the stage chain AND the emitter's gather

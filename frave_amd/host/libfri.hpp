@@ -36,6 +36,7 @@ struct ImageMetadata { // images.rs:68-79
     bool rct = false; // the planes are Y, Cb, Cr of the reversible colour transform of RGB pixels (colorspace is then YCbCr; the file's metadata bit 0)
     uint32_t quality = 0; // 0 = lossless, 1..99: the planes were quantised with fri_hip_quality_matrix(quality) (the file's metadata bits 8..14)
     bool ycbcr = false; // the planes are Y, Cb, Cr of the irreversible JFIF transform of RGB pixels (colorspace YCbCr, quality 1..99; the file's metadata bit 1)
+    bool s420 = false;  // ... with 4:2:0 chroma subsampling: Cb and Cr are coded at half the resolution on a lattice of their own (the file's metadata bit 2)
 };
 struct RasterImage { // images.rs:82-85
     ImageMetadata metadata;
@@ -88,6 +89,7 @@ struct WaveletImage {
     ImageMetadata metadata;
     uint32_t num_cells = 0;
     std::vector<int32_t> centers;      // [F][2] (re, im)
+    uint32_t num_cells_chroma = 0;     // a 4:2:0 image: the cells of the half-resolution lattice; coefficients = Y [F][512], Cb [Fc][512], Cr [Fc][512]
     std::vector<int32_t> coefficients; // [C][F][512], FRI_HIP_NONE = None          (Fractal.coefficients)
     std::vector<uint8_t> bucket;       // [C][F][512]                           (Fractal.parameter_predictors.0)
     std::vector<int32_t> prediction;   // [C][F][512]                           (Fractal.parameter_predictors.1)
@@ -119,6 +121,8 @@ class Device {
     void measure_forward_tiling(bool on) { tune_ = on; }
     // the plan of that shape with the emitter's symbol order installed (fri_hip_plan_set_stream_order; geometry only: computed and uploaded once per plan)
     fri_hip_plan *stream_plan(uint32_t width, uint32_t height, uint32_t channels, std::string &err);
+    // the subsampled plan of that shape (fri_hip_plan420), cached like the others, with the symbol order installed on both of its inner plans
+    fri_hip_plan420 *plan420(uint32_t width, uint32_t height, std::string &err);
     std::string describe(int code) const;
 
   private:
@@ -127,6 +131,7 @@ class Device {
     bool tune_ = false;
     std::map<std::tuple<uint32_t, uint32_t, uint32_t>, fri_hip_plan *> plans_;
     std::vector<fri_hip_plan *> ordered_; // plans whose stream order is installed
+    std::map<std::pair<uint32_t, uint32_t>, fri_hip_plan420 *> plans420_;
 };
 
 // ContextModeler (context_modeling.rs:13-213): the least-squares fit of the value / width predictors. The device
@@ -215,6 +220,22 @@ Result<std::vector<std::vector<uint8_t>>> encode_batch_bytes(const std::vector<c
 // batch pays for contexts, plans and the symbol order (0.2-0.3 s per 4096^2 shape) once, not per call.
 Result<std::vector<std::vector<uint8_t>>> encode_batch_bytes(const std::vector<const uint8_t *> &images, uint32_t height, uint32_t width, ColorSpace colorspace,
                                                              const EncoderOpts &opts, const std::vector<Device *> &devices, unsigned emit_threads, BatchStats *stats = nullptr);
+
+// Lossy YCbCr coding with 4:2:0 chroma subsampling (include/fri_hip.h, FRI_EMIT_420) of RGB pixels: the quality is opts.quality (1..99), or the one the 4:2:0
+// search for opts.target_psnr, target_ssim or target_bytes returns (fri_hip_search_quality*420; a size search's file is checked against the budget and coded one
+// quality lower while it is over, as FRIEncoder::encode does). A PSNR or SSIM search that returns 100 - no quality 1..99 reaches the target - codes a lossless RCT
+// file instead (lossless_rct). The device runs fri_hip_encode_image420_symbols, the emitter writes the three streams. FRIDecoder::decode reads such files.
+struct Encoded420 {
+    std::vector<uint8_t> bytes;
+    int quality = 0;     // 1..99; 0 for the lossless fallback
+    double psnr_db = 0, ssim = 0;
+    uint64_t est_bytes = 0;
+    bool lossless_rct = false;
+};
+Result<Encoded420> encode_bytes_420(const std::vector<uint8_t> &rgb, uint32_t height, uint32_t width, const EncoderOpts &opts);
+// The direct 4:2:0 round trip at `quality` without the entropy coder, for self-checks: the split restated on the host, the forward kernel on the three planes
+// through the inner plans, then fri_hip_decode_image420 - what a 4:2:0 file of that quality decodes to.
+Result<RasterImage> round_trip_420(const std::vector<uint8_t> &rgb, uint32_t height, uint32_t width, int quality, int device = 0);
 
 class FRIDecoder { // decoder.rs:44-59
   public:

@@ -31,9 +31,20 @@
  * (FRI_HIP_COLOUR_YCBCR, include/fri_hip.h), quantised with fri_hip_quality_matrix(q). Such a file has the colour space YCbCr, bit 1 of its metadata word set
  * and bit 0 clear, and is otherwise byte for byte the lossy file of the same planes. Refused: FRI_EMIT_YCBCR with one channel, without a quality or together
  * with FRI_EMIT_RCT. fri_emit_decode_image reports it in info[2]; a YCbCr file with bits 0 and 1 both set, or with bit 1 and quality 0, is "Invalid
- * metadata". Bit 1 of a Luma or RGB file is ignored. */
+ * metadata". Bit 1 of a Luma or RGB file is ignored.
+ *
+ * 4:2:0: `channels` = 3 | FRI_EMIT_YCBCR | FRI_EMIT_420 | FRI_EMIT_QUALITY(q), q = 1..99, in fri_emit_encode_image_from_streams only - the chroma planes are
+ * subsampled (include/fri_hip.h, "4:2:0 chroma subsampling"): channel 0 is a stream of the width x height lattice, channels 1 and 2 are streams of the lattice of
+ * cw x ch = (width + 1) / 2 x (height + 1) / 2. `n_symbols` is the luma count and must be that lattice's; `streams` = Y [n_symbols], Cb [n_c], Cr [n_c], where the
+ * emitter learns n_c from the cw x ch geometry it builds itself (cached). Such a file is a YCbCr file with bit 2 of its metadata word set as well; each channel's
+ * bytes are what the function writes for that stream and histogram in any other file. Refused (-1): the flag in fri_emit_encode_image and fri_emit_check_image,
+ * without FRI_EMIT_YCBCR, without a quality, with FRI_EMIT_RCT or with one channel. fri_emit_decode_image reports the flag in info[2]; info[3] = F_y, the luma
+ * lattice's cells, and the planes come back as Y [F_y][512], Cb [F_c][512], Cr [F_c][512] (what fri_hip_decode_image420 takes), F_c = the cells of the cw x ch
+ * lattice (fri_hip_plan_num_cells of the chroma plan of a host-only fri_hip_plan420); coef_cap < (F_y + 2 F_c) x 512 returns -3 with `info` filled; `centers` is the
+ * luma lattice's. A YCbCr file with bit 2 but not bit 1, or with bits 2 and 0, is "Invalid metadata". Bit 2 of a Luma or RGB file is ignored. */
 #define FRI_EMIT_RCT 0x100u
 #define FRI_EMIT_YCBCR 0x400u
+#define FRI_EMIT_420 0x800u
 #define FRI_EMIT_QUALITY(q) ((uint32_t)(q) << 16)
 #define FRI_EMIT_QUALITY_OF(channels) (((uint32_t)(channels) >> 16) & 0x7Fu)
 #ifndef FRI_EMIT_H

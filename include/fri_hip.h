@@ -472,6 +472,62 @@ int fri_hip_inverse_transform_dev(fri_hip_plan *plan, const int32_t *d_coefs, co
 int fri_hip_inverse_transform_batch_dev(fri_hip_plan *plan, uint32_t n_images, const int32_t *d_coefs, size_t coef_stride, const int32_t qmatrix[32], uint8_t *d_pixels,
                                         size_t pixel_stride, void *stream);
 
+/* ---- 4:2:0 chroma subsampling --------------------------------------------------------------------- */
+/* Lossy YCbCr coding with the two chroma planes at half the resolution in both directions: 1.5 W H coded samples instead of 3 W H. Part of the file format
+ * (FRI_EMIT_420, include/fri_emit.h). The image is W x H interleaved R, G, B; cw = (W + 1) / 2, ch = (H + 1) / 2; all arithmetic is 32-bit signed and >> is an
+ * arithmetic shift.
+ *   forward  1. per pixel (Y, Cb, Cr) by the forward formula of FRI_HIP_COLOUR_YCBCR.
+ *            2. the luma plane [H][W] = Y.
+ *            3. chroma sample (i, j), i < cw, j < ch: (Cb(x0, y0) + Cb(x1, y0) + Cb(x0, y1) + Cb(x1, y1) + 2) >> 2 with x0 = 2 i, x1 = min(2 i + 1, W - 1),
+ *               y0 = 2 j, y1 = min(2 j + 1, H - 1) - an odd last column or row is replicated. Cr alike. The chroma planes are [ch][cw] each, Cb then Cr, contiguous.
+ *   inverse  1. the three planes are what the inverse kernel wrote: bytes, clamped to 0..255, with FRI_HIP_DEQUANT_MIDPOINT at the file's quality.
+ *            2. pixel (x, y): i = x >> 1, j = y >> 1; i' = i + 1 for odd x and i - 1 for even x, clamped to 0..cw - 1; j' the same from y and ch. For each chroma
+ *               plane p: c = (9 p[j][i] + 3 p[j][i'] + 3 p[j'][i] + p[j'][i'] + 8) >> 4 - the (3, 1) / 4 triangle filter in both directions.
+ *            3. (R, G, B) by the inverse formula of FRI_HIP_COLOUR_YCBCR from (Y[y][x], Cb_up, Cr_up).
+ *            4. a pixel no luma cell covers (shapes thinner than a cell only) holds Y = 0 in the luma plane and comes out as the inverse of (0, Cb_up, Cr_up).
+ * The luma plane is coded as a C = 1 image of W x H and the chroma planes as two C = 1 images of cw x ch, with the quantiser, the kernels and the per-channel
+ * container of every other file: a fri_hip_plan420 owns the two ordinary plans. ctx may be NULL: the plan is then host-only (the getters work, compute returns
+ * FRI_HIP_ERR_NO_DEVICE). fri_hip_plan420_luma / _chroma give the inner plans (owned by p; Cb and Cr are planes 0 and 1 of a batch on the chroma plan) for the
+ * getters, fri_hip_plan_set_stream_order - which fri_hip_encode_image420_symbols needs on both and create does not do - and any other entry point. */
+typedef struct fri_hip_plan420 fri_hip_plan420;
+int fri_hip_plan420_create(fri_hip_ctx *ctx, uint32_t width, uint32_t height, fri_hip_plan420 **out);
+int fri_hip_plan420_destroy(fri_hip_plan420 *p);
+fri_hip_plan *fri_hip_plan420_luma(fri_hip_plan420 *p);
+fri_hip_plan *fri_hip_plan420_chroma(fri_hip_plan420 *p);
+/* The raster kernels (K8, k8_chroma420.hip), any pointer alignment; they only enqueue on `stream`, and split and merge can be captured into a graph. d_rgb [H][W][3];
+ * d_y [H][W]; d_cbcr = Cb [ch][cw] then Cr [ch][cw]. split: forward steps 1-3. merge: inverse steps 2-3 of whatever the planes hold.
+ * measure_distortion: the merge that stores nothing - it compares with d_reference_rgb and accumulates d_out, uint64 [7] with the layout of
+ * fri_hip_measure_distortion_dev at C = 3: d_out[2 c] = sum of squared errors of channel c (R, G, B), d_out[2 c + 1] = largest absolute error, d_out[6] = W H
+ * (every pixel is counted). d_out is zeroed on `stream` first; exact integers, the same in every run. */
+int fri_hip_split420_dev(fri_hip_plan420 *p, const uint8_t *d_rgb, uint8_t *d_y, uint8_t *d_cbcr, void *stream);
+int fri_hip_merge420_dev(fri_hip_plan420 *p, const uint8_t *d_y, const uint8_t *d_cbcr, uint8_t *d_rgb, void *stream);
+int fri_hip_measure_distortion420_dev(fri_hip_plan420 *p, const uint8_t *d_y, const uint8_t *d_cbcr, const uint8_t *d_reference_rgb, uint64_t *d_out, void *stream);
+/* The device part of a 4:2:0 encode for host buffers: the pixels are staged through buffers the plan owns, split, and fri_hip_encode_symbols_batch_dev runs in its
+ * direct form (compact planes, no node words, the fit on) with fri_hip_quality_matrix(quality) on the luma plan (n = 1) and on the chroma plan (n = 2). Both inner
+ * plans need their stream order. quality is 1..99, anything else FRI_HIP_ERR_INVALID_ARGUMENT. Outputs: symbols = Y [n_y], Cb [n_c], Cr [n_c] u16, contiguous
+ * (n_y, n_c = fri_hip_plan_num_some of the two plans); value_params / width_params [3][3][6]; hist [3][10][1024]; n_out_of_alphabet [3]. Synchronous.
+ * FRI_HIP_ERR_OUT_OF_RANGE as in fri_hip_encode_image. */
+int fri_hip_encode_image420_symbols(fri_hip_plan420 *p, const uint8_t *pixels, int quality, float *value_params, float *width_params, uint16_t *symbols, uint32_t *hist,
+                                    uint64_t *n_out_of_alphabet);
+/* The device part of a 4:2:0 decode: coefs = Y [F_y][512], Cb [F_c][512], Cr [F_c][512] int32 (F = fri_hip_plan_num_cells of the two plans; what
+ * fri_emit_decode_image returns for such a file) -> pixels [H][W][3]. The inverse kernel with fri_hip_quality_matrix(quality) and FRI_HIP_DEQUANT_MIDPOINT on both
+ * plans, whatever is set on them, then the merge. Synchronous. */
+int fri_hip_decode_image420(fri_hip_plan420 *p, const int32_t *coefs, int quality, uint8_t *pixels);
+/* The searches of fri_hip_search_quality, fri_hip_search_quality_for_size and fri_hip_search_quality_ssim for 4:2:0 coding: exactly those bisections - PSNR and
+ * SSIM lo = 0, hi = 100 with 100 never probed; size lo = 0, hi = 100 as on YCbCr plans, i.e. over the qualities 1..99 a 4:2:0 file can have. A result of 100 means
+ * "no quality 1..99 reaches it: code losslessly". The split runs once per call. A PSNR probe is the forward and the inverse kernel (midpoint dequantiser) on both
+ * plans and the measuring merge; an SSIM probe merges into a raster the plan owns and runs K7; PSNR and SSIM are those of R, G, B against the source pixels. A size
+ * probe is forward + fit + scan on both plans, then the rate kernel once over the three histograms as one C = 3 image: the formula of fri_hip_estimate_size_dev
+ * unchanged, one 18-byte header and one final rounding. They synchronise `stream`, refuse a capturing one, and refuse what the plain searches refuse (a target that
+ * is NaN or <= 0, an SSIM target > 1 or a shape under 8 x 8, max_bytes == 0); FRI_HIP_ERR_OUT_OF_RANGE from the size search when nothing fits (quality = 0,
+ * est_bytes = the estimate of quality 1). The inner plans' settings are left as they are. The host forms stage the pixels through the plan's buffers. */
+int fri_hip_search_quality420(fri_hip_plan420 *p, const uint8_t *pixels, double target_db, int32_t *quality, double *psnr_db);
+int fri_hip_search_quality420_dev(fri_hip_plan420 *p, const uint8_t *d_pixels, double target_db, int32_t *quality, double *psnr_db, void *stream);
+int fri_hip_search_quality_for_size420(fri_hip_plan420 *p, const uint8_t *pixels, uint64_t max_bytes, int32_t *quality, uint64_t *est_bytes);
+int fri_hip_search_quality_for_size420_dev(fri_hip_plan420 *p, const uint8_t *d_pixels, uint64_t max_bytes, int32_t *quality, uint64_t *est_bytes, void *stream);
+int fri_hip_search_quality_ssim420(fri_hip_plan420 *p, const uint8_t *pixels, double target, int32_t *quality, double *ssim);
+int fri_hip_search_quality_ssim420_dev(fri_hip_plan420 *p, const uint8_t *d_pixels, double target, int32_t *quality, double *ssim, void *stream);
+
 /* ---- timing helper ---------------------------------------------------------------------------- */
 /* Runs the forward kernel `iters` times on `stream` bracketed by HIP events recorded on that same
  * stream and returns the mean kernel-to-kernel time per launch in microseconds (bench.py uses it
