@@ -12,6 +12,7 @@ from .api import (  # noqa: F401
     Multi,
     Plan,
     Plan420,
+    PlanRGBA,
     DEQUANT_MIDPOINT,
     DEQUANT_MULTIPLY,
     DEQUANT_REFERENCE,

@@ -36,7 +36,10 @@ SYMBOLS = [
     "fri_hip_plan420_create", "fri_hip_plan420_destroy", "fri_hip_plan420_luma", "fri_hip_plan420_chroma", "fri_hip_split420_dev", "fri_hip_merge420_dev",
     "fri_hip_measure_distortion420_dev", "fri_hip_encode_image420_symbols", "fri_hip_decode_image420", "fri_hip_search_quality420", "fri_hip_search_quality420_dev",
     "fri_hip_search_quality_for_size420", "fri_hip_search_quality_for_size420_dev", "fri_hip_search_quality_ssim420", "fri_hip_search_quality_ssim420_dev",
+    "fri_hip_plan_rgba_create", "fri_hip_plan_rgba_destroy", "fri_hip_plan_rgba_colour", "fri_hip_plan_rgba_alpha", "fri_hip_split_rgba_dev", "fri_hip_merge_rgba_dev",
+    "fri_hip_encode_symbols_rgba_dev", "fri_hip_encode_image_rgba_symbols", "fri_hip_decode_image_rgba",
 ]
+ALPHA_KEEP, ALPHA_CLEAN = 0, 1  # `clean` of fri_hip_split_rgba_dev and the RGBA encodes: CLEAN zeroes the colour of pixels with A == 0
 COLOUR_NONE, COLOUR_RCT, COLOUR_YCBCR = 0, 1, 3  # fri_hip_plan_set_colour_transform (bit 0: chroma planes, bit 1: irreversible)
 DEQUANT_REFERENCE, DEQUANT_MULTIPLY, DEQUANT_MIDPOINT = 0, 1, 2  # fri_hip_plan_set_dequantiser
 
@@ -192,6 +195,15 @@ def load_library():
     L.fri_hip_search_quality_for_size420_dev.argtypes = [vp, vp, C.c_uint64, vp, vp, vp]
     L.fri_hip_search_quality_ssim420.argtypes = [vp, vp, C.c_double, vp, vp]
     L.fri_hip_search_quality_ssim420_dev.argtypes = [vp, vp, C.c_double, vp, vp, vp]
+    L.fri_hip_plan_rgba_create.argtypes = [vp, u32, u32, C.POINTER(vp)]
+    L.fri_hip_plan_rgba_destroy.argtypes = [vp]
+    L.fri_hip_plan_rgba_colour.restype, L.fri_hip_plan_rgba_colour.argtypes = vp, [vp]
+    L.fri_hip_plan_rgba_alpha.restype, L.fri_hip_plan_rgba_alpha.argtypes = vp, [vp]
+    L.fri_hip_split_rgba_dev.argtypes = [vp, vp, i32, vp, vp, vp]
+    L.fri_hip_merge_rgba_dev.argtypes = [vp, vp, vp, vp, vp]
+    L.fri_hip_encode_symbols_rgba_dev.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp]
+    L.fri_hip_encode_image_rgba_symbols.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp]
+    L.fri_hip_decode_image_rgba.argtypes = [vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -881,3 +893,82 @@ class Plan420:
     def search_quality_for_size(self, pixels, max_bytes, stream=0):
         """fri_hip_search_quality_for_size420[_dev]: (quality, estimated bytes); FriHipError with code -7 when nothing fits."""
         return self._search("fri_hip_search_quality_for_size420", pixels, int(max_bytes), C.c_uint64, stream)
+
+
+class PlanRGBA:
+    """fri_hip_plan_rgba: RGBA coding - the colour as any C = 3 image, the alpha plane losslessly as a C = 1 image (include/fri_hip.h has the format). Owns two
+    ordinary plans on the same W x H lattice, .colour (C = 3: set the colour transform and the dequantiser of a decode here) and .alpha (C = 1) - Plan views that do
+    not own their handle and die with this object. ctx=None gives a host-only plan (getters only). Calls on one PlanRGBA must be ordered on one stream: they share
+    the plan's staging buffers."""
+
+    def __init__(self, ctx, width, height):
+        self._h = None
+        self.ctx = ctx
+        self.width, self.height = width, height
+        h = C.c_void_p()
+        L = load_library()
+        _check(L.fri_hip_plan_rgba_create(ctx._h if ctx else None, width, height, C.byref(h)), "fri_hip_plan_rgba_create", ctx)
+        self._h = h
+        self.colour = Plan(ctx, width, height, 3, _handle=L.fri_hip_plan_rgba_colour(h))
+        self.alpha = Plan(ctx, width, height, 1, _handle=L.fri_hip_plan_rgba_alpha(h))
+        self.pixel_bytes = 4 * width * height
+        self.num_cells = self.colour.num_cells
+        self.num_some = self.colour.num_some  # symbols per channel, the same for all four
+        self.coef_count = 4 * self.num_cells * 512
+
+    def close(self):
+        if self._h:
+            self.colour.close()
+            self.alpha.close()
+            load_library().fri_hip_plan_rgba_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_stream_order(self):
+        """fri_hip_plan_set_stream_order on both inner plans (the encodes need it)."""
+        self.colour.set_stream_order()
+        self.alpha.set_stream_order()
+
+    # ---- device-pointer entry points (pointers are ints) --------------------------------------------
+    def split_rgba_dev(self, d_rgba, d_rgb, d_a, clean=ALPHA_KEEP, stream=0):
+        """fri_hip_split_rgba_dev: R, G, B, A [H][W][4] -> R, G, B [H][W][3] and A [H][W] (contiguous); ALPHA_CLEAN zeroes the colour where A == 0; only enqueues."""
+        _check(load_library().fri_hip_split_rgba_dev(self._h, d_rgba, int(clean), d_rgb, d_a, stream), "fri_hip_split_rgba_dev", self.ctx)
+
+    def merge_rgba_dev(self, d_rgb, d_a, d_rgba, stream=0):
+        """fri_hip_merge_rgba_dev: the inverse interleave; only enqueues."""
+        _check(load_library().fri_hip_merge_rgba_dev(self._h, d_rgb, d_a, d_rgba, stream), "fri_hip_merge_rgba_dev", self.ctx)
+
+    def encode_symbols_rgba_dev(self, d_rgba, d_params, d_symbols, d_hist, d_oob, d_fit_out_of_range=None, clean=ALPHA_KEEP, qmatrix=None, fit=True, stream=0):
+        """fri_hip_encode_symbols_rgba_dev: the split and the direct stream chain on both inner plans, everything on the device: d_params float32 [4][2][3][6],
+        d_symbols uint16 [4][num_some], d_hist uint32 [4][10][1024], d_oob uint64 [4], d_fit_out_of_range uint64 [4] or None - the colour channels, then alpha.
+        qmatrix is the colour's; alpha always takes ones. Needs set_stream_order()."""
+        _check(load_library().fri_hip_encode_symbols_rgba_dev(self._h, d_rgba, int(clean), _p(_q(qmatrix)), int(bool(fit)), d_params, d_symbols, d_hist, d_oob,
+                                                             d_fit_out_of_range, stream), "fri_hip_encode_symbols_rgba_dev", self.ctx)
+
+    # ---- host-pointer entry points ----------------------------------------------------------------
+    def encode_image_rgba_symbols(self, pixels, qmatrix=None, clean=ALPHA_KEEP):
+        """fri_hip_encode_image_rgba_symbols: (symbols uint16 [4][num_some], value_params [4][3][6], width_params [4][3][6], hist [4][10][1024], oob [4]) - the
+        colour channels, coded with qmatrix and the colour plan's transform, then the alpha plane, coded with ones; the fit is on. Needs set_stream_order()."""
+        px = np.ascontiguousarray(pixels, np.uint8).reshape(-1)
+        assert px.size == self.pixel_bytes
+        vp, wp = np.zeros((4, 3, 6), np.float32), np.zeros((4, 3, 6), np.float32)
+        sym = np.empty((4, self.num_some), np.uint16)
+        hist = np.empty((4, 10, 1024), np.uint32)
+        oob = np.zeros(4, np.uint64)
+        _check(load_library().fri_hip_encode_image_rgba_symbols(self._h, _p(px), int(clean), _p(_q(qmatrix)), _p(vp), _p(wp), _p(sym), _p(hist), _p(oob)),
+               "fri_hip_encode_image_rgba_symbols", self.ctx)
+        return sym, vp, wp, hist, oob
+
+    def decode_image_rgba(self, coefs, qmatrix=None):
+        """fri_hip_decode_image_rgba: coefs int32 [4][F][512] (what emit.decode_image returns for a file with alpha) -> pixels uint8 [H * W * 4]. The colour planes
+        go through the inverse kernel with qmatrix and the colour plan's transform and dequantiser, the alpha plane with ones."""
+        co = np.ascontiguousarray(coefs, np.int32).reshape(-1)
+        assert co.size == self.coef_count
+        out = np.empty(self.pixel_bytes, np.uint8)
+        _check(load_library().fri_hip_decode_image_rgba(self._h, _p(co), _p(_q(qmatrix)), _p(out)), "fri_hip_decode_image_rgba", self.ctx)
+        return out

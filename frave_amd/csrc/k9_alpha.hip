@@ -1,0 +1,156 @@
+// k9_alpha.hip -- K9: the raster kernels of RGBA coding (include/fri_hip.h, "RGBA: a lossless alpha plane", has the format bit for bit).
+//
+// split_rgba_kernel<CLEAN>: interleaved R, G, B, A [H][W][4] -> the colour raster [H][W][3] and the alpha plane [H][W]. CLEAN: a pixel with A == 0 gets
+// R = G = B = 0. merge_rgba_kernel: the inverse interleave.
+//
+// None of the three rasters has a row pitch, so the kernels see a flat run of N = W H pixels. A lane owns one strip of 16 consecutive pixels: 64 bytes of
+// R, G, B, A as four 16-byte accesses, 48 bytes of R, G, B as three and 16 bytes of A as one. The bytes change places in registers with v_perm_b32
+// (__builtin_amdgcn_perm(a, b, sel): selector values 0..3 take a byte of b, 4..7 a byte of a) - four pixels are four dwords on one side and three + one on the
+// other - and CLEAN is one select per pixel. The buffers start at any byte: the vector accesses are the target's unaligned global loads and stores (the compiler
+// is told the alignment is 1). Only the last strip, when N is no multiple of 16, is walked byte by byte. Every byte offset is 64-bit: 4 W H can pass 2^32.
+#include "device_common.hpp"
+
+namespace fri {
+namespace {
+
+constexpr int kAlphaThreads = 256;
+constexpr int kAlphaStrip = 16; // pixels per lane
+
+struct RgbaArgs {
+    const uint8_t *in0, *in1; // split: rgba, -; merge: rgb, a
+    uint8_t *out0, *out1;     // split: rgb, a;  merge: rgba, -
+    uint64_t n_pixels;
+    uint32_t n_strips;
+};
+
+template <typename V>
+__device__ __forceinline__ V load_unaligned(const uint8_t *p) {
+    V v;
+    __builtin_memcpy(&v, p, sizeof(V));
+    return v;
+}
+template <typename V>
+__device__ __forceinline__ void store_unaligned(uint8_t *p, const V &v) {
+    __builtin_memcpy(p, &v, sizeof(V));
+}
+
+template <bool CLEAN>
+__global__ void __launch_bounds__(kAlphaThreads) split_rgba_kernel(const RgbaArgs p) {
+    const uint32_t t = blockIdx.x * kAlphaThreads + threadIdx.x;
+    if (t >= p.n_strips) return;
+    const uint64_t first = (uint64_t)t * kAlphaStrip;
+    const uint8_t *src = p.in0 + first * 4;
+    uint8_t *rgb = p.out0 + first * 3, *al = p.out1 + first;
+    if (first + kAlphaStrip <= p.n_pixels) {
+        uint32_t px[16];
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const u32x4 v = load_unaligned<u32x4>(src + 16 * q);
+            px[4 * q] = v.x, px[4 * q + 1] = v.y, px[4 * q + 2] = v.z, px[4 * q + 3] = v.w;
+        }
+        if (CLEAN) {
+#pragma unroll
+            for (int k = 0; k < 16; k++) px[k] = px[k] >> 24 ? px[k] : 0u;
+        }
+        uint32_t c[12], a[4];
+#pragma unroll
+        for (int g = 0; g < 4; g++) { // four pixels R G B A x 4 -> R0 G0 B0 R1 | G1 B1 R2 G2 | B2 R3 G3 B3 and A0 A1 A2 A3
+            const uint32_t p0 = px[4 * g], p1 = px[4 * g + 1], p2 = px[4 * g + 2], p3 = px[4 * g + 3];
+            c[3 * g] = __builtin_amdgcn_perm(p1, p0, 0x04020100u);
+            c[3 * g + 1] = __builtin_amdgcn_perm(p2, p1, 0x05040201u);
+            c[3 * g + 2] = __builtin_amdgcn_perm(p3, p2, 0x06050402u);
+            const uint32_t a01 = __builtin_amdgcn_perm(p1, p0, 0x07030703u), a23 = __builtin_amdgcn_perm(p3, p2, 0x07030703u);
+            a[g] = __builtin_amdgcn_perm(a23, a01, 0x05040100u);
+        }
+#pragma unroll
+        for (int q = 0; q < 3; q++) {
+            const u32x4 v = {c[4 * q], c[4 * q + 1], c[4 * q + 2], c[4 * q + 3]};
+            store_unaligned(rgb + 16 * q, v);
+        }
+        const u32x4 v = {a[0], a[1], a[2], a[3]};
+        store_unaligned(al, v);
+    } else { // the last, partial strip
+        const int n = (int)(p.n_pixels - first);
+        for (int k = 0; k < n; k++) {
+            const uint8_t A = src[4 * k + 3];
+            const bool zero = CLEAN && A == 0;
+            rgb[3 * k] = zero ? (uint8_t)0 : src[4 * k];
+            rgb[3 * k + 1] = zero ? (uint8_t)0 : src[4 * k + 1];
+            rgb[3 * k + 2] = zero ? (uint8_t)0 : src[4 * k + 2];
+            al[k] = A;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(kAlphaThreads) merge_rgba_kernel(const RgbaArgs p) {
+    const uint32_t t = blockIdx.x * kAlphaThreads + threadIdx.x;
+    if (t >= p.n_strips) return;
+    const uint64_t first = (uint64_t)t * kAlphaStrip;
+    const uint8_t *rgb = p.in0 + first * 3, *al = p.in1 + first;
+    uint8_t *dst = p.out0 + first * 4;
+    if (first + kAlphaStrip <= p.n_pixels) {
+        uint32_t c[12];
+#pragma unroll
+        for (int q = 0; q < 3; q++) {
+            const u32x4 v = load_unaligned<u32x4>(rgb + 16 * q);
+            c[4 * q] = v.x, c[4 * q + 1] = v.y, c[4 * q + 2] = v.z, c[4 * q + 3] = v.w;
+        }
+        const u32x4 av = load_unaligned<u32x4>(al);
+        const uint32_t a[4] = {av.x, av.y, av.z, av.w};
+        uint32_t px[16];
+#pragma unroll
+        for (int g = 0; g < 4; g++) { // R0 G0 B0 R1 | G1 B1 R2 G2 | B2 R3 G3 B3 and A0 A1 A2 A3 -> four pixels
+            const uint32_t c0 = c[3 * g], c1 = c[3 * g + 1], c2 = c[3 * g + 2];
+            px[4 * g] = __builtin_amdgcn_perm(a[g], c0, 0x04020100u);
+            px[4 * g + 1] = __builtin_amdgcn_perm(a[g], __builtin_amdgcn_perm(c1, c0, 0x00050403u), 0x05020100u);
+            px[4 * g + 2] = __builtin_amdgcn_perm(a[g], __builtin_amdgcn_perm(c2, c1, 0x00040302u), 0x06020100u);
+            px[4 * g + 3] = __builtin_amdgcn_perm(a[g], c2, 0x07030201u);
+        }
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const u32x4 v = {px[4 * q], px[4 * q + 1], px[4 * q + 2], px[4 * q + 3]};
+            store_unaligned(dst + 16 * q, v);
+        }
+    } else { // the last, partial strip
+        const int n = (int)(p.n_pixels - first);
+        for (int k = 0; k < n; k++) {
+            dst[4 * k] = rgb[3 * k];
+            dst[4 * k + 1] = rgb[3 * k + 1];
+            dst[4 * k + 2] = rgb[3 * k + 2];
+            dst[4 * k + 3] = al[k];
+        }
+    }
+}
+
+// N pixels as a 1-D grid of kAlphaThreads-thread workgroups, one strip per lane; false when the shape does not fit one
+bool grid_of(uint32_t width, uint32_t height, RgbaArgs &p, uint32_t &groups) {
+    p.n_pixels = (uint64_t)width * height;
+    const uint64_t strips = (p.n_pixels + kAlphaStrip - 1) / kAlphaStrip;
+    if (!width || !height || strips > 0x7FFFFFFFull) return false;
+    p.n_strips = (uint32_t)strips;
+    groups = (uint32_t)((strips + kAlphaThreads - 1) / kAlphaThreads);
+    return true;
+}
+
+} // namespace
+
+hipError_t launch_split_rgba(const uint8_t *rgba, uint32_t width, uint32_t height, bool clean, uint8_t *rgb, uint8_t *a, hipStream_t stream) {
+    RgbaArgs p{};
+    uint32_t groups = 0;
+    if (!rgba || !rgb || !a || !grid_of(width, height, p, groups)) return hipErrorInvalidValue;
+    p.in0 = rgba, p.out0 = rgb, p.out1 = a;
+    if (clean) hipLaunchKernelGGL(split_rgba_kernel<true>, dim3(groups), dim3(kAlphaThreads), 0, stream, p);
+    else hipLaunchKernelGGL(split_rgba_kernel<false>, dim3(groups), dim3(kAlphaThreads), 0, stream, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_merge_rgba(const uint8_t *rgb, const uint8_t *a, uint32_t width, uint32_t height, uint8_t *rgba, hipStream_t stream) {
+    RgbaArgs p{};
+    uint32_t groups = 0;
+    if (!rgba || !rgb || !a || !grid_of(width, height, p, groups)) return hipErrorInvalidValue;
+    p.in0 = rgb, p.in1 = a, p.out0 = rgba;
+    hipLaunchKernelGGL(merge_rgba_kernel, dim3(groups), dim3(kAlphaThreads), 0, stream, p);
+    return hipGetLastError();
+}
+
+} // namespace fri

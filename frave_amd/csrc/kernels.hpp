@@ -172,6 +172,11 @@ hipError_t launch_clear_sums(unsigned long long *sums, uint32_t n, hipStream_t s
 hipError_t launch_split420(const uint8_t *rgb, uint32_t width, uint32_t height, uint8_t *y, uint8_t *cbcr, hipStream_t stream);
 hipError_t launch_merge420(const uint8_t *y, const uint8_t *cbcr, uint32_t width, uint32_t height, uint8_t *rgb, hipStream_t stream, unsigned long long *measure = nullptr);
 
+// K9 (k9_alpha.hip): RGBA split and merge on rasters (include/fri_hip.h has the format). Split: interleaved R, G, B, A of width x height -> rgb [H][W][3] and
+// a [H][W]; clean: a pixel with A == 0 gets R = G = B = 0. Merge: the inverse interleave. Any shape, any pointer alignment.
+hipError_t launch_split_rgba(const uint8_t *rgba, uint32_t width, uint32_t height, bool clean, uint8_t *rgb, uint8_t *a, hipStream_t stream);
+hipError_t launch_merge_rgba(const uint8_t *rgb, const uint8_t *a, uint32_t width, uint32_t height, uint8_t *rgba, hipStream_t stream);
+
 // K2's per-node neighbour offsets (LDS halfword offsets relative to the own slot, two per word) from the static neighbour table
 void build_lf_deltas(const uint16_t *nbr_table, int8_t *out /* [8] */);
 void build_gather_tables(const uint16_t *nbr_table, uint32_t *gather_off /* [512][4] */, uint16_t *pair_pos /* [256] */, uint16_t *heap_of_pos /* [512] */);

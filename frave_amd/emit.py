@@ -11,6 +11,7 @@ _lib = None
 RCT = 0x100  # FRI_EMIT_RCT: `channels = 3 | RCT` - the planes are Y, Cb, Cr of the reversible colour transform (include/fri_emit.h)
 YCBCR = 0x400  # FRI_EMIT_YCBCR: `channels = 3 | YCBCR | QUALITY(q)` - the planes are Y, Cb, Cr of the irreversible JFIF transform (lossy files only)
 S420 = 0x800  # FRI_EMIT_420: `channels = 3 | YCBCR | S420 | QUALITY(q)` in encode_image_from_streams - 4:2:0, Cb and Cr are streams of the half-resolution lattice
+FRI_EMIT_ALPHA = ALPHA = 0x1000  # FRI_EMIT_ALPHA: `channels = 3 | ALPHA [| RCT | YCBCR | QUALITY(q)]` in encode_image_from_streams - a fourth, lossless channel: the alpha plane
 
 
 def QUALITY(q):
@@ -18,8 +19,8 @@ def QUALITY(q):
     return int(q) << 16
 
 
-def _arg(channels, rct, quality, ycbcr=False, s420=False):
-    return channels | (RCT if rct else 0) | (YCBCR if ycbcr else 0) | (S420 if s420 else 0) | QUALITY(quality or 0)
+def _arg(channels, rct, quality, ycbcr=False, s420=False, alpha=False):
+    return channels | (RCT if rct else 0) | (YCBCR if ycbcr else 0) | (S420 if s420 else 0) | (ALPHA if alpha else 0) | QUALITY(quality or 0)
 
 
 class EmitError(RuntimeError):
@@ -124,20 +125,25 @@ def stream_order(centers, valid_mask):
     return out[: n.value].copy()
 
 
-def encode_image_from_streams(width, height, streams, hist, value_params, width_params, rct=False, quality=0, ycbcr=False, n_luma=None):
+def encode_image_from_streams(width, height, streams, hist, value_params, width_params, rct=False, quality=0, ycbcr=False, n_luma=None, alpha=False):
     """.frv bytes from the device's symbol streams: streams uint16 [C][n_symbols] (bucket << 10 | symbol), hist [C][10][1024], params [C][3][6].
     rct, quality, ycbcr: see encode_image. n_luma: a 4:2:0 file (implies the flag; needs ycbcr and a quality) - streams is the concatenation Y [n_luma],
-    Cb [n_c], Cr [n_c] that Plan420.encode_image420_symbols returns; the emitter works n_c out from the geometry."""
+    Cb [n_c], Cr [n_c] that Plan420.encode_image420_symbols returns; the emitter works n_c out from the geometry. alpha: streams [4][n_symbols], hist
+    [4][10][1024], params [4][3][6] - the three colour channels, which rct, quality and ycbcr describe, then the lossless alpha plane
+    (PlanRGBA.encode_image_rgba_symbols returns them so); not with n_luma."""
     st = np.ascontiguousarray(streams, np.uint16)
     h = np.ascontiguousarray(hist, np.uint32)
     channels = h.size // 10240
-    n_symbols = st.size // channels if n_luma is None else int(n_luma)
+    planes = channels
+    if alpha:  # the flag rides on the three colour channels; a wrong count reaches the library as it is and is refused there
+        channels -= 1
+    n_symbols = st.size // planes if n_luma is None else int(n_luma)
     vp, wp = np.ascontiguousarray(value_params, np.float32), np.ascontiguousarray(width_params, np.float32)
-    assert (n_luma is not None or st.size == channels * n_symbols) and vp.size == channels * 18 and wp.size == channels * 18
+    assert (n_luma is not None or st.size == planes * n_symbols) and vp.size == planes * 18 and wp.size == planes * 18
     n = C.c_size_t(0)
     err = C.create_string_buffer(256)
-    out = np.empty(st.size * 4 + channels * (10 * 2070 + 256) + 64, np.uint8)
-    rc = load_library().fri_emit_encode_image_from_streams(width, height, _arg(channels, rct, quality, ycbcr, n_luma is not None), _p(st), n_symbols, _p(h), _p(vp), _p(wp), _p(out), out.size, C.addressof(n), err, 256)
+    out = np.empty(st.size * 4 + planes * (10 * 2070 + 256) + 64, np.uint8)
+    rc = load_library().fri_emit_encode_image_from_streams(width, height, _arg(channels, rct, quality, ycbcr, n_luma is not None, alpha), _p(st), n_symbols, _p(h), _p(vp), _p(wp), _p(out), out.size, C.addressof(n), err, 256)
     if rc != 0:
         raise EmitError(err.value.decode() or f"fri_emit_encode_image_from_streams: {rc}")
     return out[: n.value].tobytes()
@@ -168,12 +174,14 @@ class DecodedImage(tuple):
     """(width, height, channels, centers, coefs), and .rct: True if the planes are Y, Cb, Cr of the reversible colour transform; .quality: 0 for a
     lossless file, else the quality 1..99 whose matrix quantised the planes (decode with the midpoint dequantiser); .ycbcr: True if the planes are Y, Cb, Cr
     of the irreversible JFIF transform (decode with COLOUR_YCBCR); .s420: True for a 4:2:0 file - coefs is then the tuple (Y [F_y][512], Cb [F_c][512],
-    Cr [F_c][512]), centers the luma lattice's (decode with Plan420.decode_image420 of the three concatenated)."""
+    Cr [F_c][512]), centers the luma lattice's (decode with Plan420.decode_image420 of the three concatenated); .alpha: True for a file with an alpha
+    plane - channels stays 3 and coefs is [4][F][512], the colour planes then alpha (decode with PlanRGBA.decode_image_rgba)."""
 
     rct = False
     quality = 0
     ycbcr = False
     s420 = False
+    alpha = False
 
 
 def decode_image(frv):
@@ -191,6 +199,7 @@ def decode_image(frv):
     ycbcr = bool(c & YCBCR)
     quality = (c >> 16) & 0x7F
     s420 = bool(c & S420)
+    alpha = bool(c & ALPHA)
     c &= 0xFF
     if s420:  # F_c: the cells of the half-resolution lattice, from a host-only subsampled plan (no GPU involved)
         from .api import Plan420
@@ -200,7 +209,7 @@ def decode_image(frv):
         sub.close()
         coefs = np.empty((f + 2 * fc, 512), np.int32)
     else:
-        coefs = np.empty((c, f, 512), np.int32)
+        coefs = np.empty((c + 1 if alpha else c, f, 512), np.int32)
     centers = np.empty((f, 2), np.int32)
     rc = L.fri_emit_decode_image(_p(data), data.size, _p(info), _p(coefs), coefs.size, _p(centers), err, 256)
     if rc != 0:
@@ -210,4 +219,5 @@ def decode_image(frv):
     out.quality = quality
     out.ycbcr = ycbcr
     out.s420 = s420
+    out.alpha = alpha
     return out

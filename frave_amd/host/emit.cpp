@@ -847,7 +847,8 @@ std::string decode_image(const std::vector<uint8_t> &frv, DecodedImage &out) {
 std::string decode_parsed(const ParsedImage &img, DecodedImage &out) {
     std::string err;
     const uint32_t channels = img.colorspace == kLuma ? 1u : 3u; // ColorSpace::num_channels, images.rs:31-38
-    if (img.channels.size() != channels) return "Malformed image bytes";
+    const uint32_t planes = channels + (img.alpha ? 1u : 0u);     // an alpha plane follows the colour channels, on the same lattice
+    if (img.channels.size() != planes) return "Malformed image bytes";
     for (const ChannelStream &c : img.channels)
         for (const AnsContext &a : c.contexts)
             if (a.max_freq_bits == 0) return "Malformed image bytes"; // fewer than ten EHD segments
@@ -856,6 +857,7 @@ std::string decode_parsed(const ParsedImage &img, DecodedImage &out) {
     out.quality = img.quality;
     out.ycbcr = img.ycbcr;
     out.s420 = img.s420;
+    out.alpha = img.alpha;
     out.params = img.params;
     if (img.s420) return decode_parsed_420(img, out);
     fri::Geometry g;
@@ -865,17 +867,17 @@ std::string decode_parsed(const ParsedImage &img, DecodedImage &out) {
     out.n_cells = (uint32_t)F;
     out.centers.resize(F * 2);
     for (size_t c = 0; c < F; c++) out.centers[2 * c] = g.centers[c].x, out.centers[2 * c + 1] = g.centers[c].y;
-    out.coefs.assign(channels * plane, 0);
+    out.coefs.assign(planes * plane, 0);
     out.params = img.params;
     const auto order_ptr = shared_symbol_order(out.centers.data(), (uint32_t)F);
     const SymbolOrder &order = *order_ptr;
-    std::vector<std::string> errs(channels);
+    std::vector<std::string> errs(planes);
     std::vector<std::thread> workers;
-    for (uint32_t ch = 1; ch < channels; ch++)
+    for (uint32_t ch = 1; ch < planes; ch++)
         workers.emplace_back([&, ch] { errs[ch] = decode_channel(g, order, img.channels[ch], img.params[ch], out.coefs.data() + ch * plane); });
     errs[0] = decode_channel(g, order, img.channels[0], img.params[0], out.coefs.data());
     for (std::thread &t : workers) t.join();
-    for (uint32_t ch = 0; ch < channels; ch++)
+    for (uint32_t ch = 0; ch < planes; ch++)
         if (!errs[ch].empty()) return "channel " + std::to_string(ch) + ": " + errs[ch];
     return "";
 }
@@ -898,12 +900,12 @@ constexpr uint8_t kEHD[2] = {0xFF, 0xB2}, kDAT[2] = {0xFF, 0xB4}, kEOC[2] = {0xF
 } // namespace
 
 std::vector<uint8_t> serialize(uint32_t height, uint32_t width, ColorSpaceCode cs, const std::vector<ChannelStream> &channels, const std::vector<ChannelParams> &params,
-                               bool rct, uint32_t quality, bool ycbcr, bool s420) {
+                               bool rct, uint32_t quality, bool ycbcr, bool s420, bool alpha) {
     std::vector<uint8_t> s;
     s.insert(s.end(), {'f', 'r', 'i', 'f'});
     put_u32(s, height);
     put_u32(s, width);
-    put_u32(s, (uint32_t)cs << 30 | 1u << 28 | (rct ? kMdatRct : 0u) | (ycbcr ? kMdatYcbcr : 0u) | (s420 ? kMdat420 : 0u) | (quality & kMdatQualityMask) << kMdatQualityShift); // variant: TameTwindragon = 0b01 (images.rs:49-55)
+    put_u32(s, (uint32_t)cs << 30 | 1u << 28 | (rct ? kMdatRct : 0u) | (ycbcr ? kMdatYcbcr : 0u) | (s420 ? kMdat420 : 0u) | (alpha ? kMdatAlpha : 0u) | (quality & kMdatQualityMask) << kMdatQualityShift); // variant: TameTwindragon = 0b01 (images.rs:49-55)
     for (size_t ch = 0; ch < channels.size(); ch++) {
         s.insert(s.end(), kPRD, kPRD + 2);
         for (int g = 0; g < 3; g++)
@@ -947,10 +949,12 @@ std::string deserialize(const std::vector<uint8_t> &b, ParsedImage &out) {
     out.colorspace = mdat >> 30 & 3u;
     out.variant = mdat >> 28 & 3u;
     if (out.colorspace == 0 || out.variant == 0) return "Invalid metadata";
-    out.rct = out.colorspace == kYCbCr && (mdat & kMdatRct); // (bits 3..7 and 15..27 stay ignored, and bits 1 and 2 outside YCbCr)
+    out.rct = out.colorspace == kYCbCr && (mdat & kMdatRct); // (bits 4..7 and 15..27 stay ignored, bits 1 and 2 outside YCbCr, and every flag bit of a Luma file)
     out.ycbcr = out.colorspace == kYCbCr && (mdat & kMdatYcbcr);
     out.s420 = out.colorspace == kYCbCr && (mdat & kMdat420);
+    out.alpha = out.colorspace != kLuma && (mdat & kMdatAlpha);
     out.quality = mdat >> kMdatQualityShift & kMdatQualityMask;
+    if (out.alpha && (mdat & kMdat420)) return "Invalid metadata";
     if (out.quality >= 100 || (out.ycbcr && (out.rct || out.quality == 0)) || (out.s420 && (out.rct || !out.ycbcr))) return "Invalid metadata";
     ChannelStream cur;
     ChannelParams prm{};

@@ -149,8 +149,13 @@ constexpr uint32_t kMdatYcbcr = 2u;
 // channels 1 and 2 are streams of the (width + 1) / 2 x (height + 1) / 2 lattice. Without kMdatYcbcr or with kMdatRct it is invalid; bit 2 of a Luma or RGB file
 // stays ignored.
 constexpr uint32_t kMdat420 = 4u;
+// Bit 3 of the metadata word, with cs = kRGB or kYCbCr: an alpha plane (include/fri_hip.h, "RGBA") - a fourth channel follows the third, a lossless stream of the
+// width x height lattice, byte for byte the channel of a Luma file of that stream. The colour-space field, bits 0..2 and the quality describe the three colour
+// channels only. Together with bit 2 it is invalid; bit 3 of a Luma file stays ignored.
+constexpr uint32_t kMdatAlpha = 8u;
 std::vector<uint8_t> serialize(uint32_t height, uint32_t width, ColorSpaceCode cs, const std::vector<ChannelStream> &channels,
-                               const std::vector<ChannelParams> &params, bool rct = false, uint32_t quality = 0, bool ycbcr = false, bool s420 = false);
+                               const std::vector<ChannelParams> &params, bool rct = false, uint32_t quality = 0, bool ycbcr = false, bool s420 = false,
+                               bool alpha = false);
 // (cells, Some nodes per channel) of the lattice of a width x height image, from a small process-wide cache: what the 4:2:0 paths need to know of the
 // chroma lattice. Returns "" or the geometry's error.
 std::string lattice_counts(uint32_t width, uint32_t height, uint32_t &n_cells, uint64_t &n_some);
@@ -160,6 +165,7 @@ struct ParsedImage {
     uint32_t quality = 0; // 0 = lossless, 1..99 (bits 8..14)
     bool ycbcr = false; // kYCbCr with kMdatYcbcr set
     bool s420 = false;  // ... and kMdat420: channels 1 and 2 are coded on the half-resolution lattice
+    bool alpha = false; // kRGB or kYCbCr with kMdatAlpha set: a fourth channel, the lossless alpha plane
     std::vector<ChannelStream> channels; // contexts rebuilt from (max_freq_bits, off_distribution_values) like serialize.rs:214-237
     std::vector<ChannelParams> params;
 };
@@ -179,6 +185,7 @@ struct DecodedImage {
     bool ycbcr = false; // the planes are Y, Cb, Cr of the irreversible JFIF transform (ParsedImage::ycbcr)
     bool s420 = false;  // 4:2:0 (ParsedImage::s420): coefs = Y [n_cells][512], Cb [n_cells_chroma][512], Cr [n_cells_chroma][512] - what fri_hip_decode_image420 takes
     uint32_t n_cells_chroma = 0;
+    bool alpha = false; // an alpha plane (ParsedImage::alpha): coefs = [4][n_cells][512], the colour planes then alpha - what fri_hip_decode_image_rgba takes; channels stays 3
     std::vector<int32_t> centers;     // [n_cells][2], canonical order (the one fri_hip_plan_centers reports); 4:2:0: the luma lattice's
     std::vector<int32_t> coefs;       // [channels][n_cells][512]: what fri_hip_inverse_transform takes
     std::vector<ChannelParams> params;

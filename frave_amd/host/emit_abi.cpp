@@ -15,22 +15,25 @@ int fail(char *err, size_t cap, const std::string &msg, int code = -1) {
 }
 // `channels` of the encoders and the check: 1 or 3, with FRI_EMIT_RCT (3 only) or FRI_EMIT_QUALITY(1..99) (not both); FRI_EMIT_YCBCR only as
 // 3 | FRI_EMIT_YCBCR | FRI_EMIT_QUALITY(1..99); FRI_EMIT_420 only on top of that, and only where the caller takes it (s420 != NULL: the stream route).
-// False for anything else.
-bool split_channels(uint32_t arg, uint32_t &channels, bool &rct, uint32_t &quality, bool &ycbcr, bool *s420 = nullptr) {
+// FRI_EMIT_ALPHA only with three channels, never with FRI_EMIT_420, and only where the caller takes it (alpha != NULL: the stream route). False for anything else.
+bool split_channels(uint32_t arg, uint32_t &channels, bool &rct, uint32_t &quality, bool &ycbcr, bool *s420 = nullptr, bool *alpha = nullptr) {
     rct = (arg & FRI_EMIT_RCT) != 0;
     ycbcr = (arg & FRI_EMIT_YCBCR) != 0;
     const bool sub = (arg & FRI_EMIT_420) != 0;
     quality = FRI_EMIT_QUALITY_OF(arg);
-    channels = arg & ~(uint32_t)FRI_EMIT_RCT & ~(uint32_t)FRI_EMIT_YCBCR & ~(uint32_t)FRI_EMIT_420 & ~FRI_EMIT_QUALITY(0x7Fu);
+    const bool has_alpha = (arg & FRI_EMIT_ALPHA) != 0;
+    channels = arg & ~(uint32_t)FRI_EMIT_RCT & ~(uint32_t)FRI_EMIT_YCBCR & ~(uint32_t)FRI_EMIT_420 & ~(uint32_t)FRI_EMIT_ALPHA & ~FRI_EMIT_QUALITY(0x7Fu);
     if (quality >= 100 || (quality && rct)) return false;
     if (ycbcr && (channels != 3 || !quality)) return false;
     if (sub && (!s420 || !ycbcr)) return false;
+    if (has_alpha && (!alpha || channels != 3 || sub)) return false;
     if (s420) *s420 = sub;
+    if (alpha) *alpha = has_alpha;
     return channels == 3 || (channels == 1 && !rct);
 }
 ColorSpaceCode colour_space(uint32_t channels, bool rct, bool ycbcr) { return channels == 1 ? kLuma : rct || ycbcr ? kYCbCr : kRGB; }
-uint32_t channels_info(uint32_t channels, bool rct, uint32_t quality, bool ycbcr, bool s420) {
-    return channels | (rct ? FRI_EMIT_RCT : 0u) | (ycbcr ? FRI_EMIT_YCBCR : 0u) | (s420 ? FRI_EMIT_420 : 0u) | FRI_EMIT_QUALITY(quality);
+uint32_t channels_info(uint32_t channels, bool rct, uint32_t quality, bool ycbcr, bool s420, bool alpha) {
+    return channels | (rct ? FRI_EMIT_RCT : 0u) | (ycbcr ? FRI_EMIT_YCBCR : 0u) | (s420 ? FRI_EMIT_420 : 0u) | (alpha ? FRI_EMIT_ALPHA : 0u) | FRI_EMIT_QUALITY(quality);
 }
 } // namespace
 
@@ -124,8 +127,9 @@ int fri_emit_encode_image_from_streams(uint32_t width, uint32_t height, uint32_t
     uint32_t channels;
     bool rct, ycbcr;
     uint32_t quality;
-    bool s420 = false;
-    if (!streams || !hist || !value_params || !width_params || !len || !split_channels(channels_arg, channels, rct, quality, ycbcr, &s420)) return fail(err, err_cap, "invalid argument");
+    bool s420 = false, alpha = false;
+    if (!streams || !hist || !value_params || !width_params || !len || !split_channels(channels_arg, channels, rct, quality, ycbcr, &s420, &alpha)) return fail(err, err_cap, "invalid argument");
+    const uint32_t planes = channels + (alpha ? 1u : 0u); // the alpha plane's stream, histograms and parameters follow the colour channels'
     uint64_t n_chroma = 0;
     if (s420) { // the streams of Cb and Cr are those of the half-resolution lattice: the emitter learns their length from the geometry, like its decoder
         uint32_t cells = 0;
@@ -136,14 +140,14 @@ int fri_emit_encode_image_from_streams(uint32_t width, uint32_t height, uint32_t
         if (n_symbols != n_luma) return fail(err, err_cap, "n_symbols is not the symbol count of the width x height lattice");
     }
     std::vector<ChannelStream> chans;
-    std::vector<ChannelParams> params(channels);
-    const std::string e = encode_channels_from_streams(channels, streams, (size_t)n_symbols, hist, chans, (size_t)n_chroma);
+    std::vector<ChannelParams> params(planes);
+    const std::string e = encode_channels_from_streams(planes, streams, (size_t)n_symbols, hist, chans, (size_t)n_chroma);
     if (!e.empty()) return fail(err, err_cap, e, -2);
-    for (uint32_t ch = 0; ch < channels; ch++) {
+    for (uint32_t ch = 0; ch < planes; ch++) {
         std::memcpy(params[ch].value, value_params + (size_t)ch * 18, sizeof(params[ch].value));
         std::memcpy(params[ch].width, width_params + (size_t)ch * 18, sizeof(params[ch].width));
     }
-    const std::vector<uint8_t> bytes = serialize(height, width, colour_space(channels, rct, ycbcr), chans, params, rct, quality, ycbcr, s420);
+    const std::vector<uint8_t> bytes = serialize(height, width, colour_space(channels, rct, ycbcr), chans, params, rct, quality, ycbcr, s420, alpha);
     *len = bytes.size();
     if (!out || cap < bytes.size()) return -3;
     std::memcpy(out, bytes.data(), bytes.size());
@@ -187,7 +191,7 @@ int fri_emit_rans_selfcheck(uint64_t n_symbols, uint64_t seed, char *err, size_t
 }
 
 // A .frv back to coefficient planes. info = {width, height, channels, n_cells}; coefs: [channels][n_cells][512] (None = INT32_MIN),
-// centers: [n_cells][2] or null. Returns -3 with `info` filled if coef_cap (in elements) is too small: call once with coef_cap = 0.
+// a file with an alpha plane: [4][n_cells][512], info[2] = 3 | ... | FRI_EMIT_ALPHA; centers: [n_cells][2] or null. Returns -3 with `info` filled if coef_cap (in elements) is too small: call once with coef_cap = 0.
 int fri_emit_decode_image(const uint8_t *frv, size_t len, uint32_t info[4], int32_t *coefs, size_t coef_cap, int32_t *centers, char *err, size_t err_cap) {
     if (!frv || !info) return fail(err, err_cap, "invalid argument");
     if (!coefs || coef_cap == 0) { // size query: header + geometry only
@@ -198,13 +202,13 @@ int fri_emit_decode_image(const uint8_t *frv, size_t len, uint32_t info[4], int3
         uint32_t n_cells = 0;
         const std::string ge = count_cells(img.width, img.height, channels, n_cells);
         if (!ge.empty()) return fail(err, err_cap, ge, -2);
-        info[0] = img.width, info[1] = img.height, info[2] = channels_info(channels, img.rct, img.quality, img.ycbcr, img.s420), info[3] = n_cells;
+        info[0] = img.width, info[1] = img.height, info[2] = channels_info(channels, img.rct, img.quality, img.ycbcr, img.s420, img.alpha), info[3] = n_cells;
         return -3;
     }
     DecodedImage d;
     const std::string e = decode_image(std::vector<uint8_t>(frv, frv + len), d);
     if (!e.empty()) return fail(err, err_cap, e, -2);
-    info[0] = d.width, info[1] = d.height, info[2] = channels_info(d.channels, d.rct, d.quality, d.ycbcr, d.s420), info[3] = d.n_cells;
+    info[0] = d.width, info[1] = d.height, info[2] = channels_info(d.channels, d.rct, d.quality, d.ycbcr, d.s420, d.alpha), info[3] = d.n_cells;
     if (coef_cap < d.coefs.size()) return -3;
     std::memcpy(coefs, d.coefs.data(), d.coefs.size() * sizeof(int32_t));
     if (centers) std::memcpy(centers, d.centers.data(), d.centers.size() * sizeof(int32_t));

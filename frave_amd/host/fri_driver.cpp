@@ -16,7 +16,10 @@
 //                                                            --ycbcr (RGB, with --quality / --psnr / --ssim / --size / --bpp): lossy in Y, Cb, Cr of the JFIF
 //                                                            transform (flagged file; searches measure in R, G, B). A PSNR or SSIM no quality 1..99 reaches:
 //                                                            lossless RCT file
-//   fri_driver decode-file <in.frv> <out.pgm|.ppm|.bmp>     container -> rANS / context decoding on the host -> dequantisation + inverse
+//                                                            in.pam: a binary PAM (P7, DEPTH 4, MAXVAL 255, TUPLTYPE RGB_ALPHA) - RGBA: the colour as the options
+//                                                            say (--rct, --quality, --psnr, --ssim, --ycbcr; no --size / --bpp / --420), the alpha plane
+//                                                            losslessly beside it; --clean-alpha: the colour of pixels with A = 0 is coded as 0
+//   fri_driver decode-file <in.frv> <out.pgm|.ppm|.bmp|.pam>  (.pam for a file with an alpha plane, and for no other) container -> rANS / context decoding on the host -> dequantisation + inverse
 //                                                            transform on the device (fri-cli decode, crates/fri-cli/src/commands/decode.rs); a flagged file
 //                                                            comes back as RGB, a lossy file with its quality's matrix and the midpoint dequantiser
 //   fri_driver batch <width> <height> <channels> <n_images> [--gpus N]
@@ -88,6 +91,54 @@ static bool read_pnm(const char *path, std::vector<uint8_t> &data, uint32_t &w, 
     std::fclose(f);
     if (!ok) err = "file shorter than its header says";
     return ok;
+}
+
+// Binary PAM (P7) with DEPTH 4, MAXVAL 255 and TUPLTYPE RGB_ALPHA: R, G, B, A bytes, the one RGBA format that needs no library.
+static bool read_pam(const char *path, std::vector<uint8_t> &data, uint32_t &w, uint32_t &h, std::string &err) {
+    FILE *f = std::fopen(path, "rb");
+    if (!f) {
+        err = std::string("cannot open ") + path;
+        return false;
+    }
+    auto line = [&](std::string &t) {
+        t.clear();
+        int ch;
+        while ((ch = std::fgetc(f)) != EOF && ch != '\n')
+            if (ch != '\r') t.push_back((char)ch);
+        return ch != EOF || !t.empty();
+    };
+    std::string t, tupl;
+    long width = 0, height = 0, depth = 0, maxval = 0;
+    bool ok = line(t) && t == "P7", ended = false;
+    while (ok && !ended && line(t)) {
+        if (t.empty() || t[0] == '#') continue;
+        if (t == "ENDHDR") ended = true;
+        else if (t.compare(0, 6, "WIDTH ") == 0) width = std::atol(t.c_str() + 6);
+        else if (t.compare(0, 7, "HEIGHT ") == 0) height = std::atol(t.c_str() + 7);
+        else if (t.compare(0, 6, "DEPTH ") == 0) depth = std::atol(t.c_str() + 6);
+        else if (t.compare(0, 7, "MAXVAL ") == 0) maxval = std::atol(t.c_str() + 7);
+        else if (t.compare(0, 9, "TUPLTYPE ") == 0) tupl = t.substr(9);
+        else ok = false;
+    }
+    ok = ok && ended && width > 0 && height > 0 && width <= 0x7FFFFFFFl && height <= 0x7FFFFFFFl && depth == 4 && maxval == 255 && tupl == "RGB_ALPHA";
+    if (!ok) {
+        err = "not a binary PAM with DEPTH 4, MAXVAL 255 and TUPLTYPE RGB_ALPHA";
+        std::fclose(f);
+        return false;
+    }
+    w = (uint32_t)width, h = (uint32_t)height;
+    data.resize((size_t)w * h * 4);
+    ok = std::fread(data.data(), 1, data.size(), f) == data.size();
+    std::fclose(f);
+    if (!ok) err = "file shorter than its header says";
+    return ok;
+}
+static bool write_pam(const char *path, const std::vector<uint8_t> &rgba, uint32_t w, uint32_t h) {
+    FILE *f = std::fopen(path, "wb");
+    if (!f) return false;
+    std::fprintf(f, "P7\nWIDTH %u\nHEIGHT %u\nDEPTH 4\nMAXVAL 255\nTUPLTYPE RGB_ALPHA\nENDHDR\n", w, h);
+    std::fwrite(rgba.data(), 1, rgba.size(), f);
+    return std::fclose(f) == 0;
 }
 
 // Uncompressed 24-bit BMP (BITMAPINFOHEADER, BI_RGB): rows bottom-up (top-down if the height is negative), BGR, padded to 4 bytes.
@@ -355,23 +406,72 @@ static int encode_image_420_to_file(const std::vector<uint8_t> &img, uint32_t w,
     return 0;
 }
 
+// encode-file of a PAM: RGBA (libfri::encode_bytes_rgba). Self-check: the file decodes (FRIDecoder) to the direct round trip of what it holds
+// (libfri::round_trip_rgba: host split, forward kernels, fri_hip_decode_image_rgba) - for a lossless file that is the input, cleaned if --clean-alpha says so.
+static int encode_image_rgba_to_file(const std::vector<uint8_t> &img, uint32_t w, uint32_t h, const libfri::EncoderOpts &opts, bool clean, const char *out_path) {
+    auto t0 = std::chrono::steady_clock::now();
+    auto enc = libfri::encode_bytes_rgba(img, h, w, opts, clean);
+    const double t_enc = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (!enc.ok) {
+        std::fprintf(stderr, "%s\n", enc.error.c_str());
+        return 1;
+    }
+    const std::vector<uint8_t> &bytes = enc.value.bytes;
+    if (opts.target_psnr > 0) std::printf("target %.2f dB: quality %d (%.2f dB, colour only)\n", opts.target_psnr, enc.value.quality ? enc.value.quality : 100, enc.value.psnr_db);
+    if (opts.target_ssim > 0) std::printf("target SSIM %.4f: quality %d (SSIM %.6f, colour only)\n", opts.target_ssim, enc.value.quality ? enc.value.quality : 100, enc.value.ssim);
+    if (enc.value.lossless_rct) std::printf("no YCbCr quality reaches the target: a lossless RCT file\n");
+    auto back = libfri::FRIDecoder().decode(bytes, opts);
+    auto direct = libfri::round_trip_rgba(img, h, w, enc.value.quality, enc.value.rct, enc.value.ycbcr, clean, opts.device);
+    if (!direct.ok) {
+        std::fprintf(stderr, "self-check failed: direct round trip: %s\n", direct.error.c_str());
+        return 1;
+    }
+    if (!back.ok || !back.value.metadata.alpha || back.value.data != direct.value.data) {
+        std::fprintf(stderr, "self-check failed: %s\n", back.ok ? "decoded image differs from the direct RGBA round trip" : back.error.c_str());
+        return 1;
+    }
+    bool exact = true; // a lossless file: the input, with the colour of fully transparent pixels zeroed if asked for; any file: the alpha plane
+    for (size_t i = 0; i < (size_t)w * h && exact; i++) {
+        const bool zero = clean && img[4 * i + 3] == 0;
+        exact = back.value.data[4 * i + 3] == img[4 * i + 3];
+        for (int k = 0; k < 3 && exact && !enc.value.quality; k++) exact = back.value.data[4 * i + k] == (zero ? 0 : img[4 * i + k]);
+    }
+    if (!exact) {
+        std::fprintf(stderr, "self-check failed: %s\n", enc.value.quality ? "the alpha plane did not come back exactly" : "the lossless file does not decode to the input");
+        return 1;
+    }
+    if (FILE *f = std::fopen(out_path, "wb")) {
+        std::fwrite(bytes.data(), 1, bytes.size(), f);
+        std::fclose(f);
+    } else {
+        std::fprintf(stderr, "cannot write %s\n", out_path);
+        return 1;
+    }
+    std::printf("%ux%ux4 RGBA: %zu bytes, %.3f bits per pixel; device chain and emit %.3f s; self-check: decodes to the direct RGBA round trip, alpha exact\n", w, h, bytes.size(),
+                8.0 * bytes.size() / ((double)w * h), t_enc);
+    if (enc.value.quality) std::printf("quality %d%s\n", enc.value.quality, enc.value.ycbcr ? " in YCbCr" : "");
+    return 0;
+}
+
 int main(int argc, char **argv) {
     if (argc >= 4 && std::string(argv[1]) == "encode-file") {
         std::vector<uint8_t> img;
         uint32_t fw = 0, fh = 0, fc = 0;
         std::string err;
-        if (!(has_suffix(argv[2], ".bmp") ? read_bmp(argv[2], img, fw, fh, fc, err) : read_pnm(argv[2], img, fw, fh, fc, err))) {
+        const bool rgba = has_suffix(argv[2], ".pam");
+        if (rgba ? (fc = 3, !read_pam(argv[2], img, fw, fh, err)) : !(has_suffix(argv[2], ".bmp") ? read_bmp(argv[2], img, fw, fh, fc, err) : read_pnm(argv[2], img, fw, fh, fc, err))) {
             std::fprintf(stderr, "%s\n", err.c_str());
             return 1;
         }
         libfri::EncoderOpts file_opts; // parameters are fitted on the device sums (fit_parameters defaults to true)
         double bpp = 0;
-        bool has_size = false, has_bpp = false, has_ssim = false, sub420 = false;
+        bool has_size = false, has_bpp = false, has_ssim = false, sub420 = false, clean_alpha = false;
         for (int i = 4; i < argc; i++) {
             const std::string a = argv[i];
             if (a == "--rct") file_opts.colour_transform = true;
             else if (a == "--420") sub420 = file_opts.ycbcr = true; // 4:2:0 implies YCbCr
             else if (a == "--ycbcr") file_opts.ycbcr = true;
+            else if (a == "--clean-alpha") clean_alpha = true;
             else if (a == "--quality" && i + 1 < argc) file_opts.quality = std::atoi(argv[++i]);
             else if (a == "--psnr" && i + 1 < argc) file_opts.target_psnr = std::atof(argv[++i]);
             else if (a == "--ssim" && i + 1 < argc) file_opts.target_ssim = std::atof(argv[++i]), has_ssim = true;
@@ -402,6 +502,15 @@ int main(int argc, char **argv) {
             std::fprintf(stderr, "encode-file: --size BYTES (> 0) or --bpp B (> 0), not both, and neither with --quality, --psnr or --rct\n");
             return 2;
         }
+        if (clean_alpha && !rgba) {
+            std::fprintf(stderr, "encode-file: --clean-alpha needs an RGBA image (a .pam file)\n");
+            return 2;
+        }
+        if (rgba && (sub420 || sized)) {
+            std::fprintf(stderr, "encode-file: an RGBA image takes no --420, --size or --bpp (alpha with 4:2:0 and a size search with alpha are out of scope)\n");
+            return 2;
+        }
+        if (rgba) return encode_image_rgba_to_file(img, fw, fh, file_opts, clean_alpha, argv[3]);
         if (sub420) return encode_image_420_to_file(img, fw, fh, file_opts, argv[3]); // (the --ycbcr checks above hold: an RGB image, a lossy target, no --rct)
         return encode_image_to_file(std::move(img), fw, fh, fc, file_opts, argv[3]);
     }
@@ -421,6 +530,22 @@ int main(int argc, char **argv) {
             return 1;
         }
         const uint32_t ch = libfri::num_channels(img.value.metadata.colorspace);
+        if (img.value.metadata.alpha) { // R, G, B, A: a PAM and nothing else
+            if (!has_suffix(argv[3], ".pam")) {
+                std::fprintf(stderr, "cannot write %s: the file has an alpha plane, which a PGM, PPM or BMP cannot hold (write a .pam)\n", argv[3]);
+                return 1;
+            }
+            if (!write_pam(argv[3], img.value.data, img.value.metadata.width, img.value.metadata.height)) {
+                std::fprintf(stderr, "cannot write %s\n", argv[3]);
+                return 1;
+            }
+            std::printf("%ux%ux4 decoded\n", img.value.metadata.width, img.value.metadata.height);
+            return 0;
+        }
+        if (has_suffix(argv[3], ".pam")) {
+            std::fprintf(stderr, "cannot write %s: the file has no alpha plane (write a .pgm, .ppm or .bmp)\n", argv[3]);
+            return 1;
+        }
         if (has_suffix(argv[3], ".bmp")) {
             if (ch != 3 || !write_bmp(argv[3], img.value.data, img.value.metadata.width, img.value.metadata.height)) {
                 std::fprintf(stderr, "cannot write %s%s\n", argv[3], ch != 3 ? " (a BMP takes an RGB image)" : "");
@@ -441,7 +566,7 @@ int main(int argc, char **argv) {
         return 0;
     }
     if (argc < 5) {
-        std::fprintf(stderr, "usage: %s roundtrip|encode|batch|batch-frv <width> <height> <channels> [n_images | out.frv]\n       %s encode-file <in.pgm|in.ppm|in.bmp> <out.frv> [--rct | [--ycbcr | --420] (--quality Q | --psnr DB | --ssim S | --size BYTES | --bpp B)]\n       %s decode-file <in.frv> <out.pgm|out.ppm|out.bmp>\n", argv[0], argv[0], argv[0]);
+        std::fprintf(stderr, "usage: %s roundtrip|encode|batch|batch-frv <width> <height> <channels> [n_images | out.frv]\n       %s encode-file <in.pgm|in.ppm|in.bmp|in.pam> <out.frv> [--rct | [--ycbcr | --420] (--quality Q | --psnr DB | --ssim S | --size BYTES | --bpp B)] [--clean-alpha]\n       %s decode-file <in.frv> <out.pgm|out.ppm|out.bmp|out.pam>\n", argv[0], argv[0], argv[0]);
         return 2;
     }
     const std::string cmd = argv[1];

@@ -12,6 +12,8 @@
 #include <thread>
 #include <utility>
 
+#include <hip/hip_runtime_api.h> // encode_bytes_rgba: the device buffers of its searches
+
 namespace libfri {
 
 Device::Device(int device) {
@@ -23,6 +25,7 @@ Device::Device(int device) {
 }
 Device::~Device() {
     for (auto &kv : plans420_) fri_hip_plan420_destroy(kv.second);
+    for (auto &kv : plans_rgba_) fri_hip_plan_rgba_destroy(kv.second);
     for (auto &kv : plans_) fri_hip_plan_destroy(kv.second);
     if (ctx_) fri_hip_ctx_destroy(ctx_);
 }
@@ -163,6 +166,29 @@ Result<RasterImage> decode(const WaveletImage &image, const EncoderOpts &opts, D
         r.value.metadata = ImageMetadata{image.metadata.height, image.metadata.width, ColorSpace::RGB};
         r.value.data.resize((size_t)image.metadata.width * image.metadata.height * 3);
         const int rc = fri_hip_decode_image420(sub, image.coefficients.data(), (int)image.metadata.quality, r.value.data.data());
+        if (rc != FRI_HIP_OK) r.error = dev.describe(rc);
+        r.ok = rc == FRI_HIP_OK;
+        return r;
+    }
+    if (image.metadata.alpha) { // four planes on one lattice: the inverse kernel on the colour and the alpha plan, then the merge
+        fri_hip_plan_rgba *both = dev.plan_rgba(image.metadata.width, image.metadata.height, r.error);
+        if (!both) return r;
+        fri_hip_plan *colour = fri_hip_plan_rgba_colour(both);
+        if (image.metadata.colorspace == ColorSpace::Luma || image.coefficients.size() != 4 * (size_t)fri_hip_plan_num_cells(colour) * FRI_HIP_CELL_SIZE) {
+            r.error = "coefficient array does not match the image geometry";
+            return r;
+        }
+        if (!(r.error = set_colour_transform(colour, image.metadata.rct, dev, image.metadata.ycbcr)).empty()) return r;
+        std::array<int32_t, 32> qm = opts.quantization_matrix;
+        if (image.metadata.quality && fri_hip_quality_matrix((int)image.metadata.quality, qm.data()) != FRI_HIP_OK) {
+            r.error = "invalid quality";
+            return r;
+        }
+        int rc = fri_hip_plan_set_dequantiser(colour, image.metadata.quality ? FRI_HIP_DEQUANT_MIDPOINT : FRI_HIP_DEQUANT_REFERENCE);
+        r.value.metadata = ImageMetadata{image.metadata.height, image.metadata.width, ColorSpace::RGB};
+        r.value.metadata.alpha = true;
+        r.value.data.resize((size_t)image.metadata.width * image.metadata.height * 4);
+        if (rc == FRI_HIP_OK) rc = fri_hip_decode_image_rgba(both, image.coefficients.data(), qm.data(), r.value.data.data());
         if (rc != FRI_HIP_OK) r.error = dev.describe(rc);
         r.ok = rc == FRI_HIP_OK;
         return r;
@@ -410,6 +436,7 @@ Result<CompressedImage> stages::serialize::decode(const std::vector<uint8_t> &by
     r.value.metadata.quality = p.quality;
     r.value.metadata.ycbcr = p.ycbcr;
     r.value.metadata.s420 = p.s420;
+    r.value.metadata.alpha = p.alpha;
     r.value.variant = p.variant;
     r.value.channel_data = std::move(p.channels);
     r.value.params = std::move(p.params);
@@ -424,7 +451,7 @@ Result<WaveletImage> stages::entropy_coding::decode(const CompressedImage &image
     p.colorspace = image.metadata.colorspace == ColorSpace::Luma ? emit::kLuma : image.metadata.colorspace == ColorSpace::RGB ? emit::kRGB : emit::kYCbCr;
     p.channels = image.channel_data;
     p.params = image.params;
-    p.rct = image.metadata.rct, p.quality = image.metadata.quality, p.ycbcr = image.metadata.ycbcr, p.s420 = image.metadata.s420;
+    p.rct = image.metadata.rct, p.quality = image.metadata.quality, p.ycbcr = image.metadata.ycbcr, p.s420 = image.metadata.s420, p.alpha = image.metadata.alpha;
     emit::DecodedImage d;
     r.error = emit::decode_parsed(p, d);
     if (!r.error.empty()) return r;
@@ -611,6 +638,138 @@ Result<RasterImage> round_trip_420(const std::vector<uint8_t> &rgb, uint32_t hei
     r.value.metadata = ImageMetadata{height, width, ColorSpace::RGB};
     r.value.data.resize(rgb.size());
     if (rc == FRI_HIP_OK) rc = fri_hip_decode_image420(sub, coefs.data(), quality, r.value.data.data());
+    if (rc != FRI_HIP_OK) r.error = dev.describe(rc);
+    r.ok = rc == FRI_HIP_OK;
+    return r;
+}
+
+fri_hip_plan_rgba *Device::plan_rgba(uint32_t width, uint32_t height, std::string &err) {
+    if (!ctx_) {
+        err = error_;
+        return nullptr;
+    }
+    const auto key = std::make_pair(width, height);
+    auto it = plans_rgba_.find(key);
+    if (it != plans_rgba_.end()) return it->second;
+    fri_hip_plan_rgba *p = nullptr;
+    const int rc = fri_hip_plan_rgba_create(ctx_, width, height, &p);
+    if (rc != FRI_HIP_OK) {
+        err = describe(rc);
+        return nullptr;
+    }
+    for (fri_hip_plan *inner : {fri_hip_plan_rgba_colour(p), fri_hip_plan_rgba_alpha(p)})
+        if (!(err = set_plan_stream_order(inner, *this)).empty()) {
+            fri_hip_plan_rgba_destroy(p);
+            return nullptr;
+        }
+    plans_rgba_[key] = p;
+    return p;
+}
+
+namespace {
+// device memory of one call
+struct DeviceBytes {
+    uint8_t *p = nullptr;
+    DeviceBytes() = default;
+    DeviceBytes(const DeviceBytes &) = delete;
+    DeviceBytes &operator=(const DeviceBytes &) = delete;
+    ~DeviceBytes() {
+        if (p) (void)hipFree(p);
+    }
+};
+} // namespace
+
+Result<EncodedRGBA> encode_bytes_rgba(const std::vector<uint8_t> &rgba, uint32_t height, uint32_t width, const EncoderOpts &opts, bool clean_alpha) {
+    Result<EncodedRGBA> r;
+    auto fail = [&](const std::string &why) {
+        r.error = "Failed to decode: " + why; // sic, encoder.rs:106
+        return r;
+    };
+    std::array<int32_t, 32> qm;
+    if (const std::string e = coding_matrix(opts, qm); !e.empty()) return fail(e);
+    if (opts.target_bytes) return fail("target_bytes is not supported with an alpha plane: there is no size search with alpha (pass a quality, target_psnr or target_ssim)");
+    const size_t n_pixels = (size_t)width * height;
+    if (!n_pixels || rgba.size() != n_pixels * 4) return fail("RGBA coding takes width x height R, G, B, A pixels");
+    Device dev(opts.device);
+    std::string err;
+    fri_hip_plan_rgba *both = dev.ok() ? dev.plan_rgba(width, height, err) : nullptr;
+    if (!both) return fail(dev.ok() ? err : dev.error());
+    fri_hip_plan *colour = fri_hip_plan_rgba_colour(both);
+    const int clean = clean_alpha ? FRI_HIP_ALPHA_CLEAN : FRI_HIP_ALPHA_KEEP;
+    EncoderOpts coded = opts;
+    if (opts.target_psnr > 0 || opts.target_ssim > 0) { // the lowest quality at which the colour reaches the target: split once, search on the inner colour plan
+        if (const std::string e = set_colour_transform(colour, false, dev, opts.ycbcr); !e.empty()) return fail(e);
+        DeviceBytes buf; // R, G, B, A [4 N], then R, G, B [3 N], then A [N]
+        if (hipSetDevice(opts.device) != hipSuccess || hipMalloc((void **)&buf.p, 8 * n_pixels) != hipSuccess) return fail("no device memory for the search");
+        if (hipMemcpy(buf.p, rgba.data(), 4 * n_pixels, hipMemcpyHostToDevice) != hipSuccess) return fail("staging the pixels failed");
+        int rc = fri_hip_split_rgba_dev(both, buf.p, clean, buf.p + 4 * n_pixels, buf.p + 7 * n_pixels, nullptr);
+        int32_t q = 100;
+        if (rc == FRI_HIP_OK && opts.target_psnr > 0) rc = fri_hip_search_quality_dev(colour, buf.p + 4 * n_pixels, opts.target_psnr, &q, &r.value.psnr_db, nullptr);
+        if (rc == FRI_HIP_OK && opts.target_ssim > 0) rc = fri_hip_search_quality_ssim_dev(colour, buf.p + 4 * n_pixels, opts.target_ssim, &q, &r.value.ssim, nullptr);
+        if (rc != FRI_HIP_OK) return fail(dev.describe(rc));
+        coded.target_psnr = 0, coded.target_ssim = 0;
+        coded.quality = q < 100 ? q : 0;
+        if (q == 100 && coded.ycbcr) // YCbCr does not reach the target at any quality: a lossless file, with the RCT
+            coded.ycbcr = false, coded.colour_transform = true, r.value.lossless_rct = true;
+        if (coded.quality) fri_hip_quality_matrix(coded.quality, qm.data());
+    }
+    ImageMetadata md = coded_metadata(height, width, ColorSpace::RGB, coded);
+    md.alpha = true;
+    if (const std::string e = set_colour_transform(colour, md.rct, dev, md.ycbcr); !e.empty()) return fail(e);
+    const uint64_t n = fri_hip_plan_num_some(colour);
+    std::vector<uint16_t> symbols(4 * (size_t)n);
+    std::vector<uint32_t> hist(4 * (size_t)CONTEXT_AMOUNT * ALPHABET_SIZE);
+    float vp[4][3][6], wp[4][3][6];
+    uint64_t oob[4] = {0, 0, 0, 0};
+    const int rc = fri_hip_encode_image_rgba_symbols(both, rgba.data(), clean, qm.data(), &vp[0][0][0], &wp[0][0][0], symbols.data(), hist.data(), oob);
+    if (rc != FRI_HIP_OK) return fail(dev.describe(rc));
+    if (oob[0] | oob[1] | oob[2] | oob[3]) return fail("symbol outside the 1024-entry alphabet"); // the reference panics: bump_freq, entropy_coding.rs:99
+    std::vector<emit::ChannelStream> streams;
+    const std::string e = emit::encode_channels_from_streams(4, symbols.data(), (size_t)n, hist.data(), streams);
+    if (!e.empty()) return fail(e);
+    std::vector<emit::ChannelParams> params(4);
+    for (uint32_t ch = 0; ch < 4; ch++)
+        for (int g = 0; g < 3; g++)
+            for (int k = 0; k < 6; k++) params[ch].value[g][k] = vp[ch][g][k], params[ch].width[g][k] = wp[ch][g][k];
+    r.value.bytes = emit::serialize(height, width, colour_code(md.colorspace), streams, params, md.rct, md.quality, md.ycbcr, false, true);
+    r.value.quality = (int)md.quality, r.value.rct = md.rct, r.value.ycbcr = md.ycbcr;
+    r.ok = true;
+    return r;
+}
+
+Result<RasterImage> round_trip_rgba(const std::vector<uint8_t> &rgba, uint32_t height, uint32_t width, int quality, bool rct, bool ycbcr, bool clean_alpha, int device) {
+    Result<RasterImage> r;
+    int32_t qm[32], ones[32];
+    const size_t n_pixels = (size_t)width * height;
+    if (rgba.size() != n_pixels * 4 || quality < 0 || quality > 99 || (rct && (ycbcr || quality)) || (ycbcr && !quality) || fri_hip_quality_matrix(100, ones) != FRI_HIP_OK ||
+        fri_hip_quality_matrix(quality ? quality : 100, qm) != FRI_HIP_OK) {
+        r.error = "invalid argument";
+        return r;
+    }
+    Device dev(device);
+    fri_hip_plan_rgba *both = dev.ok() ? dev.plan_rgba(width, height, r.error) : nullptr;
+    if (!both) {
+        if (!dev.ok()) r.error = dev.error();
+        return r;
+    }
+    // the format's forward split on the host (include/fri_hip.h)
+    std::vector<uint8_t> rgb(n_pixels * 3), a(n_pixels);
+    for (size_t i = 0; i < n_pixels; i++) {
+        const bool zero = clean_alpha && rgba[4 * i + 3] == 0;
+        for (int k = 0; k < 3; k++) rgb[3 * i + k] = zero ? (uint8_t)0 : rgba[4 * i + k];
+        a[i] = rgba[4 * i + 3];
+    }
+    fri_hip_plan *colour = fri_hip_plan_rgba_colour(both), *alpha = fri_hip_plan_rgba_alpha(both);
+    if (!(r.error = set_colour_transform(colour, rct, dev, ycbcr)).empty()) return r;
+    const size_t plane = fri_hip_plan_coef_count(alpha);
+    std::vector<int32_t> coefs(4 * plane);
+    int rc = fri_hip_transform_quant(colour, rgb.data(), qm, coefs.data());
+    if (rc == FRI_HIP_OK) rc = fri_hip_transform_quant(alpha, a.data(), ones, coefs.data() + 3 * plane);
+    if (rc == FRI_HIP_OK) rc = fri_hip_plan_set_dequantiser(colour, quality ? FRI_HIP_DEQUANT_MIDPOINT : FRI_HIP_DEQUANT_REFERENCE);
+    r.value.metadata = ImageMetadata{height, width, ColorSpace::RGB};
+    r.value.metadata.alpha = true;
+    r.value.data.resize(rgba.size());
+    if (rc == FRI_HIP_OK) rc = fri_hip_decode_image_rgba(both, coefs.data(), qm, r.value.data.data());
     if (rc != FRI_HIP_OK) r.error = dev.describe(rc);
     r.ok = rc == FRI_HIP_OK;
     return r;

@@ -37,6 +37,7 @@ struct ImageMetadata { // images.rs:68-79
     uint32_t quality = 0; // 0 = lossless, 1..99: the planes were quantised with fri_hip_quality_matrix(quality) (the file's metadata bits 8..14)
     bool ycbcr = false; // the planes are Y, Cb, Cr of the irreversible JFIF transform of RGB pixels (colorspace YCbCr, quality 1..99; the file's metadata bit 1)
     bool s420 = false;  // ... with 4:2:0 chroma subsampling: Cb and Cr are coded at half the resolution on a lattice of their own (the file's metadata bit 2)
+    bool alpha = false; // a lossless alpha plane follows the colour channels (the file's metadata bit 3); a raster with it holds R, G, B, A, four bytes per pixel
 };
 struct RasterImage { // images.rs:82-85
     ImageMetadata metadata;
@@ -123,6 +124,8 @@ class Device {
     fri_hip_plan *stream_plan(uint32_t width, uint32_t height, uint32_t channels, std::string &err);
     // the subsampled plan of that shape (fri_hip_plan420), cached like the others, with the symbol order installed on both of its inner plans
     fri_hip_plan420 *plan420(uint32_t width, uint32_t height, std::string &err);
+    // the RGBA plan of that shape (fri_hip_plan_rgba), cached like the others, with the symbol order installed on both of its inner plans
+    fri_hip_plan_rgba *plan_rgba(uint32_t width, uint32_t height, std::string &err);
     std::string describe(int code) const;
 
   private:
@@ -132,6 +135,7 @@ class Device {
     std::map<std::tuple<uint32_t, uint32_t, uint32_t>, fri_hip_plan *> plans_;
     std::vector<fri_hip_plan *> ordered_; // plans whose stream order is installed
     std::map<std::pair<uint32_t, uint32_t>, fri_hip_plan420 *> plans420_;
+    std::map<std::pair<uint32_t, uint32_t>, fri_hip_plan_rgba *> plans_rgba_;
 };
 
 // ContextModeler (context_modeling.rs:13-213): the least-squares fit of the value / width predictors. The device
@@ -236,6 +240,24 @@ Result<Encoded420> encode_bytes_420(const std::vector<uint8_t> &rgb, uint32_t he
 // The direct 4:2:0 round trip at `quality` without the entropy coder, for self-checks: the split restated on the host, the forward kernel on the three planes
 // through the inner plans, then fri_hip_decode_image420 - what a 4:2:0 file of that quality decodes to.
 Result<RasterImage> round_trip_420(const std::vector<uint8_t> &rgb, uint32_t height, uint32_t width, int quality, int device = 0);
+
+// RGBA coding (include/fri_hip.h, "RGBA: a lossless alpha plane"; FRI_EMIT_ALPHA) of width x height R, G, B, A pixels: the colour is coded as opts says - lossless
+// (plain or colour_transform), or lossy in RGB or YCbCr at opts.quality or at the quality the search for opts.target_psnr / target_ssim returns - and the alpha
+// plane losslessly. The searches run on the colour alone: the pixels are split once on the device and fri_hip_search_quality_dev / _ssim_dev run on the inner colour
+// plan with the split raster; a YCbCr search that returns 100 codes a lossless RCT file instead (lossless_rct). target_bytes is refused: there is no size search
+// with alpha. clean_alpha: FRI_HIP_ALPHA_CLEAN - the colour of pixels with A == 0 is coded as 0. The device runs fri_hip_encode_image_rgba_symbols, the emitter
+// writes the four streams. FRIDecoder::decode reads such files and returns four bytes per pixel.
+struct EncodedRGBA {
+    std::vector<uint8_t> bytes;
+    int quality = 0; // 1..99; 0 for a lossless file
+    bool rct = false, ycbcr = false; // what the colour channels hold
+    double psnr_db = 0, ssim = 0;
+    bool lossless_rct = false;
+};
+Result<EncodedRGBA> encode_bytes_rgba(const std::vector<uint8_t> &rgba, uint32_t height, uint32_t width, const EncoderOpts &opts, bool clean_alpha = false);
+// The direct RGBA round trip without the entropy coder, for self-checks: the split restated on the host, the forward kernel on the colour raster (quality 0: ones,
+// else the quality's matrix; rct / ycbcr: the colour transform) and on the alpha plane (ones), then fri_hip_decode_image_rgba - what such a file decodes to.
+Result<RasterImage> round_trip_rgba(const std::vector<uint8_t> &rgba, uint32_t height, uint32_t width, int quality, bool rct, bool ycbcr, bool clean_alpha, int device = 0);
 
 class FRIDecoder { // decoder.rs:44-59
   public:

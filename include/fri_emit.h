@@ -41,10 +41,21 @@
  * without FRI_EMIT_YCBCR, without a quality, with FRI_EMIT_RCT or with one channel. fri_emit_decode_image reports the flag in info[2]; info[3] = F_y, the luma
  * lattice's cells, and the planes come back as Y [F_y][512], Cb [F_c][512], Cr [F_c][512] (what fri_hip_decode_image420 takes), F_c = the cells of the cw x ch
  * lattice (fri_hip_plan_num_cells of the chroma plan of a host-only fri_hip_plan420); coef_cap < (F_y + 2 F_c) x 512 returns -3 with `info` filled; `centers` is the
- * luma lattice's. A YCbCr file with bit 2 but not bit 1, or with bits 2 and 0, is "Invalid metadata". Bit 2 of a Luma or RGB file is ignored. */
+ * luma lattice's. A YCbCr file with bit 2 but not bit 1, or with bits 2 and 0, is "Invalid metadata". Bit 2 of a Luma or RGB file is ignored.
+ *
+ * Alpha: `channels` = 3 | FRI_EMIT_ALPHA, alone or with FRI_EMIT_RCT, FRI_EMIT_QUALITY(q) or FRI_EMIT_YCBCR | FRI_EMIT_QUALITY(q), in
+ * fri_emit_encode_image_from_streams only - a lossless alpha plane follows the three colour channels (include/fri_hip.h, "RGBA: a lossless alpha plane"). All
+ * four are streams of the width x height lattice: `streams` = [4][n_symbols], `hist` [4][10][1024], `value_params` and `width_params` [4][3][6], the colour
+ * channels first (what fri_hip_encode_image_rgba_symbols returns). Such a file is the RGB or YCbCr file of the three colour channels with bit 3 of its metadata word
+ * set - the colour-space field, bits 0..2 and the quality describe the colour channels only - and a fourth channel behind the third, byte for byte the channel the
+ * function writes for the same stream, histogram and parameters in a Luma file. Refused (-1): the flag in fri_emit_encode_image and fri_emit_check_image, with one
+ * channel or with FRI_EMIT_420. fri_emit_decode_image reports the flag in info[2] (whose channel count stays 3) and returns four planes [4][F][512], the colour
+ * planes then alpha (what fri_hip_decode_image_rgba takes); coef_cap < 4 x F x 512 returns -3 with `info` filled. An RGB or YCbCr file with bits 3 and 2 both
+ * set is "Invalid metadata". Bit 3 of a Luma file is ignored, as all flag bits of Luma files are. */
 #define FRI_EMIT_RCT 0x100u
 #define FRI_EMIT_YCBCR 0x400u
 #define FRI_EMIT_420 0x800u
+#define FRI_EMIT_ALPHA 0x1000u
 #define FRI_EMIT_QUALITY(q) ((uint32_t)(q) << 16)
 #define FRI_EMIT_QUALITY_OF(channels) (((uint32_t)(channels) >> 16) & 0x7Fu)
 #ifndef FRI_EMIT_H

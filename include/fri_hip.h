@@ -528,6 +528,52 @@ int fri_hip_search_quality_for_size420_dev(fri_hip_plan420 *p, const uint8_t *d_
 int fri_hip_search_quality_ssim420(fri_hip_plan420 *p, const uint8_t *pixels, double target, int32_t *quality, double *ssim);
 int fri_hip_search_quality_ssim420_dev(fri_hip_plan420 *p, const uint8_t *d_pixels, double target, int32_t *quality, double *ssim, void *stream);
 
+/* ---- RGBA: a lossless alpha plane ---------------------------------------------------------------- */
+/* Images with transparency: the colour is coded as any three-channel image, the alpha plane losslessly beside it. Part of the file format (FRI_EMIT_ALPHA,
+ * include/fri_emit.h). The image is W x H interleaved R, G, B, A bytes, [H][W][4]; the colour raster is [H][W][3] and the alpha plane [H][W]; all three are
+ * contiguous, without a row pitch.
+ *   forward split, per pixel   FRI_HIP_ALPHA_KEEP (0): (R, G, B) and A are copied unchanged.
+ *                              FRI_HIP_ALPHA_CLEAN (1): a pixel with A == 0 gets R = G = B = 0, every other pixel is copied. The colour under fully transparent
+ *                              pixels is then not preserved - opt-in; a lossless file made with it decodes to 0 there.
+ *   merge                      the inverse interleave: (R, G, B) from the colour raster, A from the alpha plane.
+ * The colour raster is coded by an ordinary C = 3 plan exactly as without alpha, with whatever colour transform, quality matrix and dequantiser are set on it; the
+ * alpha plane by an ordinary C = 1 plan of the same W x H with the all-ones matrix and FRI_HIP_DEQUANT_REFERENCE, always. Both lattices are the same (the retain
+ * rule is channel 0's), so fri_hip_plan_num_cells and fri_hip_plan_num_some are equal for the two; create checks it. The file is the RGB or YCbCr file of the colour
+ * channels with metadata bit 3 set and a fourth channel behind the third: byte for byte the channel of a Luma file of that stream.
+ * A fri_hip_plan_rgba owns the two plans and the staging buffers (R, G, B, A; R, G, B; A). ctx may be NULL: the plan is then host-only (the getters work, compute
+ * returns FRI_HIP_ERR_NO_DEVICE). fri_hip_plan_rgba_colour / _alpha give the inner plans (owned by p) for the getters, fri_hip_plan_set_colour_transform and
+ * fri_hip_plan_set_dequantiser on the colour plan, fri_hip_plan_set_stream_order - which the encodes need on both and create does not do - and any other entry
+ * point, the searches among them: fri_hip_search_quality_dev / _ssim_dev on the colour plan with the split raster serve a PSNR or SSIM target.
+ * Calls on one fri_hip_plan_rgba must be ordered on one stream: the staging buffers are shared.
+ * Out of scope: alpha with 4:2:0, lossy alpha, grey + alpha, premultiplication, a size search with alpha, batch and multi-GPU forms. */
+#define FRI_HIP_ALPHA_KEEP 0
+#define FRI_HIP_ALPHA_CLEAN 1
+typedef struct fri_hip_plan_rgba fri_hip_plan_rgba;
+int fri_hip_plan_rgba_create(fri_hip_ctx *ctx, uint32_t width, uint32_t height, fri_hip_plan_rgba **out);
+int fri_hip_plan_rgba_destroy(fri_hip_plan_rgba *p);
+fri_hip_plan *fri_hip_plan_rgba_colour(fri_hip_plan_rgba *p);
+fri_hip_plan *fri_hip_plan_rgba_alpha(fri_hip_plan_rgba *p);
+/* The raster kernels (K9, k9_alpha.hip), any pointer alignment; they only enqueue on `stream` and can be captured into a graph. d_rgba [H][W][4]; d_rgb [H][W][3];
+ * d_a [H][W]. `clean` is FRI_HIP_ALPHA_KEEP or FRI_HIP_ALPHA_CLEAN, anything else FRI_HIP_ERR_INVALID_ARGUMENT. */
+int fri_hip_split_rgba_dev(fri_hip_plan_rgba *p, const uint8_t *d_rgba, int clean, uint8_t *d_rgb, uint8_t *d_a, void *stream);
+int fri_hip_merge_rgba_dev(fri_hip_plan_rgba *p, const uint8_t *d_rgb, const uint8_t *d_a, uint8_t *d_rgba, void *stream);
+/* The device part of an RGBA encode, everything in device memory and on `stream`, nothing but enqueues: the split into the plan's buffers, then
+ * fri_hip_encode_symbols_batch_dev in its direct form (d_coefs = NULL, d_node_words = NULL) twice - on the colour plan with n = 1 and `qmatrix`, on the alpha
+ * plan with n = 1 and the all-ones matrix. Both inner plans need their stream order; whatever the inner call refuses (a capturing stream among it) is refused.
+ * fit = 0 reads all four channels' parameters from d_params. Outputs, the colour channels followed by alpha: d_symbols u16 [4][num_some], d_params [4][2][3][6],
+ * d_hist [4][10][1024], d_n_out_of_alphabet [4], d_fit_out_of_range [4] (may be NULL as in the inner call). */
+int fri_hip_encode_symbols_rgba_dev(fri_hip_plan_rgba *p, const uint8_t *d_rgba, int clean, const int32_t qmatrix[32], int fit, float *d_params, uint16_t *d_symbols,
+                                    uint32_t *d_hist, uint64_t *d_n_out_of_alphabet, uint64_t *d_fit_out_of_range, void *stream);
+/* The host form: the pixels are staged, the call above runs with the fit on, everything is read back. value_params / width_params [4][3][6], laid out as
+ * fri_hip_encode_image_symbols lays them out; symbols [4][num_some]; hist [4][10][1024]; n_out_of_alphabet [4]. Synchronous. FRI_HIP_ERR_OUT_OF_RANGE as in
+ * fri_hip_encode_image. */
+int fri_hip_encode_image_rgba_symbols(fri_hip_plan_rgba *p, const uint8_t *pixels, int clean, const int32_t qmatrix[32], float *value_params, float *width_params,
+                                      uint16_t *symbols, uint32_t *hist, uint64_t *n_out_of_alphabet);
+/* The device part of an RGBA decode: coefs [4][F][512] int32 (what fri_emit_decode_image returns for a file with alpha) -> pixels [H][W][4]. The inverse kernel on
+ * the colour plan with `qmatrix` and the colour transform and dequantiser set on that plan; on the alpha plan with ones and FRI_HIP_DEQUANT_REFERENCE, whatever is
+ * set on it - that setting is restored afterwards; then the merge. Synchronous. */
+int fri_hip_decode_image_rgba(fri_hip_plan_rgba *p, const int32_t *coefs, const int32_t qmatrix[32], uint8_t *pixels);
+
 /* ---- timing helper ---------------------------------------------------------------------------- */
 /* Runs the forward kernel `iters` times on `stream` bracketed by HIP events recorded on that same
  * stream and returns the mean kernel-to-kernel time per launch in microseconds (bench.py uses it
