@@ -13,6 +13,8 @@ from .api import (  # noqa: F401
     Plan,
     Plan420,
     PlanRGBA,
+    PlanTiled,
+    TILED_ALLOW_HOLES,
     DEQUANT_MIDPOINT,
     DEQUANT_MULTIPLY,
     DEQUANT_REFERENCE,
@@ -25,4 +27,5 @@ from .api import (  # noqa: F401
     quality_matrix,
     shard_images,
     ssim_of,
+    tile_shape,
 )

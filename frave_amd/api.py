@@ -38,7 +38,10 @@ SYMBOLS = [
     "fri_hip_search_quality_for_size420", "fri_hip_search_quality_for_size420_dev", "fri_hip_search_quality_ssim420", "fri_hip_search_quality_ssim420_dev",
     "fri_hip_plan_rgba_create", "fri_hip_plan_rgba_destroy", "fri_hip_plan_rgba_colour", "fri_hip_plan_rgba_alpha", "fri_hip_split_rgba_dev", "fri_hip_merge_rgba_dev",
     "fri_hip_encode_symbols_rgba_dev", "fri_hip_encode_image_rgba_symbols", "fri_hip_decode_image_rgba",
+    "fri_hip_plan_owned_pixels", "fri_hip_tile_shape", "fri_hip_plan_tiled_create", "fri_hip_plan_tiled_destroy", "fri_hip_plan_tiled_tile", "fri_hip_plan_tiled_grid",
+    "fri_hip_split_tiles_dev", "fri_hip_merge_tiles_dev", "fri_hip_encode_symbols_tiled_dev", "fri_hip_encode_image_tiled_symbols", "fri_hip_decode_image_tiled",
 ]
+TILED_ALLOW_HOLES = 1  # FRI_HIP_TILED_ALLOW_HOLES: `flags` of fri_hip_plan_tiled_create - accept a tile shape whose lattice does not own every pixel
 ALPHA_KEEP, ALPHA_CLEAN = 0, 1  # `clean` of fri_hip_split_rgba_dev and the RGBA encodes: CLEAN zeroes the colour of pixels with A == 0
 COLOUR_NONE, COLOUR_RCT, COLOUR_YCBCR = 0, 1, 3  # fri_hip_plan_set_colour_transform (bit 0: chroma planes, bit 1: irreversible)
 DEQUANT_REFERENCE, DEQUANT_MULTIPLY, DEQUANT_MIDPOINT = 0, 1, 2  # fri_hip_plan_set_dequantiser
@@ -204,6 +207,17 @@ def load_library():
     L.fri_hip_encode_symbols_rgba_dev.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp]
     L.fri_hip_encode_image_rgba_symbols.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp]
     L.fri_hip_decode_image_rgba.argtypes = [vp, vp, vp, vp]
+    L.fri_hip_plan_owned_pixels.restype, L.fri_hip_plan_owned_pixels.argtypes = C.c_uint64, [vp]
+    L.fri_hip_tile_shape.argtypes = [u32, u32, u32, vp, vp]
+    L.fri_hip_plan_tiled_create.argtypes = [vp, u32, u32, u32, u32, u32, u32, C.POINTER(vp)]
+    L.fri_hip_plan_tiled_destroy.argtypes = [vp]
+    L.fri_hip_plan_tiled_tile.restype, L.fri_hip_plan_tiled_tile.argtypes = vp, [vp]
+    L.fri_hip_plan_tiled_grid.argtypes = [vp, vp]
+    L.fri_hip_split_tiles_dev.argtypes = [vp, vp, vp, vp]
+    L.fri_hip_merge_tiles_dev.argtypes = [vp, vp, vp, vp]
+    L.fri_hip_encode_symbols_tiled_dev.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
+    L.fri_hip_encode_image_tiled_symbols.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+    L.fri_hip_decode_image_tiled.argtypes = [vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -251,6 +265,14 @@ def shard_images(n_images, shard, n_shards):
     """Global indices of the images of `shard` (fri_hip_shard_size / fri_hip_shard_image: image i -> shard i mod n_shards)."""
     L = load_library()
     return [L.fri_hip_shard_image(k, shard, n_shards) for k in range(L.fri_hip_shard_size(n_images, shard, n_shards))]
+
+
+def tile_shape(width, height, target=512):
+    """fri_hip_tile_shape: (tile_w, tile_h) of about target x target for a width x height image - the first shape of the documented walk whose C = 1 lattice owns
+    every pixel; FriHipError with code -7 when the walk finds none. Host only."""
+    tw, th = C.c_uint32(0), C.c_uint32(0)
+    _check(load_library().fri_hip_tile_shape(width, height, target, C.addressof(tw), C.addressof(th)), "fri_hip_tile_shape")
+    return tw.value, th.value
 
 
 def quality_matrix(quality):
@@ -422,6 +444,10 @@ class Plan:
             self.close()
         except Exception:
             pass
+
+    def owned_pixels(self):
+        """fri_hip_plan_owned_pixels: the pixels that are a leaf of a retained cell (width * height unless the lattice has holes)."""
+        return int(load_library().fri_hip_plan_owned_pixels(self._h))
 
     def set_stream_order(self, order=None):
         """fri_hip_plan_set_stream_order; order = None builds it with the host emitter library (frave_amd.emit.stream_order). Returns the order."""
@@ -971,4 +997,86 @@ class PlanRGBA:
         assert co.size == self.coef_count
         out = np.empty(self.pixel_bytes, np.uint8)
         _check(load_library().fri_hip_decode_image_rgba(self._h, _p(co), _p(_q(qmatrix)), _p(out)), "fri_hip_decode_image_rgba", self.ctx)
+        return out
+
+
+class PlanTiled:
+    """fri_hip_plan_tiled: an image as a batch of independently coded tiles (include/fri_hip.h has the format). Owns one ordinary plan of the tile's shape, .tile -
+    a Plan view that does not own its handle and dies with this object: set the colour transform, the dequantiser and the stream order there. ctx=None gives a
+    host-only plan (getters only). flags: TILED_ALLOW_HOLES accepts a tile shape whose lattice does not own every pixel. Calls on one PlanTiled must be ordered on
+    one stream: they share the plan's staging buffers."""
+
+    def __init__(self, ctx, width, height, channels, tile_w, tile_h, flags=0):
+        self._h = None
+        self.ctx = ctx
+        self.width, self.height, self.channels = width, height, channels
+        h = C.c_void_p()
+        L = load_library()
+        _check(L.fri_hip_plan_tiled_create(ctx._h if ctx else None, width, height, channels, tile_w, tile_h, flags, C.byref(h)), "fri_hip_plan_tiled_create", ctx)
+        self._h = h
+        self.tile = Plan(ctx, tile_w, tile_h, channels, _handle=L.fri_hip_plan_tiled_tile(h))
+        grid = np.zeros(4, np.uint32)
+        _check(L.fri_hip_plan_tiled_grid(h, _p(grid)), "fri_hip_plan_tiled_grid", ctx)
+        self.nx, self.ny, self.tile_w, self.tile_h = (int(v) for v in grid)
+        self.n_tiles = self.nx * self.ny
+        self.pixel_bytes = width * height * channels
+        self.tile_bytes = self.n_tiles * tile_w * tile_h * channels  # the tile raster [ny nx][tile_h][tile_w][C]
+        self.num_cells = self.tile.num_cells
+        self.num_some = self.tile.num_some  # symbols per channel of one tile
+        self.coef_count = self.n_tiles * channels * self.num_cells * 512
+
+    def close(self):
+        if self._h:
+            self.tile.close()
+            load_library().fri_hip_plan_tiled_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_stream_order(self):
+        """fri_hip_plan_set_stream_order on the inner plan (the encodes need it)."""
+        return self.tile.set_stream_order()
+
+    # ---- device-pointer entry points (pointers are ints) --------------------------------------------
+    def split_tiles_dev(self, d_raster, d_tiles, stream=0):
+        """fri_hip_split_tiles_dev: [H][W][C] -> [ny nx][tile_h][tile_w][C] with edge replication; only enqueues."""
+        _check(load_library().fri_hip_split_tiles_dev(self._h, d_raster, d_tiles, stream), "fri_hip_split_tiles_dev", self.ctx)
+
+    def merge_tiles_dev(self, d_tiles, d_raster, stream=0):
+        """fri_hip_merge_tiles_dev: the tile raster's in-image pixels back into [H][W][C]; only enqueues."""
+        _check(load_library().fri_hip_merge_tiles_dev(self._h, d_tiles, d_raster, stream), "fri_hip_merge_tiles_dev", self.ctx)
+
+    def encode_symbols_tiled_dev(self, d_raster, d_params, d_symbols, d_hist, d_oob, d_fit_out_of_range=None, qmatrix=None, fit=True, stream=0):
+        """fri_hip_encode_symbols_tiled_dev: the split and one direct stream chain over all tiles, everything on the device: d_params float32
+        [n_tiles][C][2][3][6], d_symbols uint16 [n_tiles][C][num_some], d_hist uint32 [n_tiles][C][10][1024], d_oob uint64 [n_tiles][C], d_fit_out_of_range uint64
+        [n_tiles][C] or None. Needs set_stream_order()."""
+        _check(load_library().fri_hip_encode_symbols_tiled_dev(self._h, d_raster, _p(_q(qmatrix)), int(bool(fit)), d_params, d_symbols, d_hist, d_oob, d_fit_out_of_range,
+                                                              stream), "fri_hip_encode_symbols_tiled_dev", self.ctx)
+
+    # ---- host-pointer entry points ----------------------------------------------------------------
+    def encode_image_tiled_symbols(self, pixels, qmatrix=None):
+        """fri_hip_encode_image_tiled_symbols: (symbols uint16 [n_tiles][C][num_some], value_params [n_tiles][C][3][6], width_params [n_tiles][C][3][6], hist
+        [n_tiles][C][10][1024], oob [n_tiles][C]) - what emit.tiled_encode_from_streams takes; the fit is on. Needs set_stream_order()."""
+        px = np.ascontiguousarray(pixels, np.uint8).reshape(-1)
+        assert px.size == self.pixel_bytes
+        n, c = self.n_tiles, self.channels
+        vp, wp = np.zeros((n, c, 3, 6), np.float32), np.zeros((n, c, 3, 6), np.float32)
+        sym = np.empty((n, c, self.num_some), np.uint16)
+        hist = np.empty((n, c, 10, 1024), np.uint32)
+        oob = np.zeros((n, c), np.uint64)
+        _check(load_library().fri_hip_encode_image_tiled_symbols(self._h, _p(px), _p(_q(qmatrix)), _p(vp), _p(wp), _p(sym), _p(hist), _p(oob)),
+               "fri_hip_encode_image_tiled_symbols", self.ctx)
+        return sym, vp, wp, hist, oob
+
+    def decode_image_tiled(self, coefs, qmatrix=None):
+        """fri_hip_decode_image_tiled: coefs int32 [n_tiles][C][F][512] (what emit.tiled_decode returns) -> pixels uint8 [H * W * C], through the inverse kernel with
+        qmatrix and the inner plan's colour transform and dequantiser, then the merge."""
+        co = np.ascontiguousarray(coefs, np.int32).reshape(-1)
+        assert co.size == self.coef_count
+        out = np.empty(self.pixel_bytes, np.uint8)
+        _check(load_library().fri_hip_decode_image_tiled(self._h, _p(co), _p(_q(qmatrix)), _p(out)), "fri_hip_decode_image_tiled", self.ctx)
         return out

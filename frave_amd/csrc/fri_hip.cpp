@@ -2676,3 +2676,166 @@ int fri_hip_decode_image_rgba(fri_hip_plan_rgba *p, const int32_t *coefs, const 
 }
 
 } // extern "C"
+
+/* ---- tiled coding: an image as a batch of independently coded tiles ---------------------------------------- */
+// A tiled plan: one ordinary plan of the tile's shape, the grid, and the staging buffers, which every call on the plan shares.
+struct fri_hip_plan_tiled {
+    fri_hip_ctx *ctx = nullptr;
+    uint32_t width = 0, height = 0, channels = 0, tile_w = 0, tile_h = 0, nx = 0, ny = 0;
+    std::unique_ptr<fri_hip_plan, PlanDelete> tile;
+    Grown<uint8_t> raster;            // the host forms' pixels
+    Grown<uint8_t> tiles;             // the split's output, the merge's input: [ny nx][tile_h][tile_w][C]
+    Grown<int32_t> coefs;             // fri_hip_decode_image_tiled: [n_tiles][C][F][512]
+    Grown<uint16_t> symbols;          // the host encode's outputs: [n_tiles][C][n_some] ...
+    Grown<uint32_t> hist;             // ... [n_tiles][C][10][1024]
+    Grown<unsigned long long> counts; // ... [n_tiles][C] out of alphabet, then [n_tiles][C] the fit's out-of-range counts
+    Grown<float> params;              // ... [n_tiles][C][2][3][6]
+    size_t n_tiles() const { return (size_t)nx * ny; }
+    size_t raster_bytes() const { return (size_t)width * height * channels; }
+    size_t tile_bytes() const { return (size_t)tile_w * tile_h * channels; }
+};
+
+namespace {
+
+int need_device_tiled(const fri_hip_plan_tiled *p) {
+    if (!p) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    return p->ctx ? FRI_HIP_OK : FRI_HIP_ERR_NO_DEVICE;
+}
+
+} // namespace
+
+extern "C" {
+
+uint64_t fri_hip_plan_owned_pixels(const fri_hip_plan *p) { return p ? p->geo.n_valid_leaves : 0; }
+
+int fri_hip_tile_shape(uint32_t width, uint32_t height, uint32_t target, uint32_t *tile_w, uint32_t *tile_h) {
+    if (!width || !height || !target || !tile_w || !tile_h) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    auto first = [&](uint32_t size) { // ceil(size / max(1, round(size / target)))
+        const uint64_t parts = std::max<uint64_t>(1, (2ull * size + target) / (2ull * target));
+        return (uint32_t)((size + parts - 1) / parts);
+    };
+    const uint32_t w0 = first(width), h0 = first(height);
+    for (uint32_t s = 0; s <= 64; s++)
+        for (uint32_t a = 0; a <= s; a++) {
+            const uint64_t w = (uint64_t)w0 + a, h = (uint64_t)h0 + (s - a);
+            if (w > 0xFFFFFFFFull || h > 0xFFFFFFFFull) continue;
+            Geometry g;
+            if (!build_geometry((uint32_t)w, (uint32_t)h, 1, TilingParams{}, g).empty()) continue;
+            if (g.n_valid_leaves == w * h) return *tile_w = (uint32_t)w, *tile_h = (uint32_t)h, FRI_HIP_OK;
+        }
+    return FRI_HIP_ERR_OUT_OF_RANGE;
+}
+
+int fri_hip_plan_tiled_create(fri_hip_ctx *ctx, uint32_t width, uint32_t height, uint32_t channels, uint32_t tile_w, uint32_t tile_h, uint32_t flags,
+                              fri_hip_plan_tiled **out) {
+    if (!out) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    *out = nullptr;
+    if (!width || !height || !tile_w || !tile_h || (channels != 1 && channels != 3) || (flags & ~(uint32_t)FRI_HIP_TILED_ALLOW_HOLES)) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    const uint64_t nx = ((uint64_t)width + tile_w - 1) / tile_w, ny = ((uint64_t)height + tile_h - 1) / tile_h;
+    if (nx * ny * channels > 65535u) return FRI_HIP_ERR_INVALID_ARGUMENT; // one batch launch of the inner plan takes all tiles
+    fri_hip_plan_tiled *p = new (std::nothrow) fri_hip_plan_tiled;
+    if (!p) return FRI_HIP_ERR_OUT_OF_MEMORY;
+    p->ctx = ctx, p->width = width, p->height = height, p->channels = channels, p->tile_w = tile_w, p->tile_h = tile_h, p->nx = (uint32_t)nx, p->ny = (uint32_t)ny;
+    fri_hip_plan *inner = nullptr;
+    int rc = fri_hip_plan_create(ctx, tile_w, tile_h, channels, &inner);
+    p->tile.reset(inner);
+    // a pixel no retained cell owns would be a defect in the middle of the picture
+    if (!rc && !(flags & FRI_HIP_TILED_ALLOW_HOLES) && p->tile->geo.n_valid_leaves != (uint64_t)tile_w * tile_h) rc = FRI_HIP_ERR_INVALID_ARGUMENT;
+    if (rc) { // a plan that fails part-way goes with what it has
+        fri_hip_plan_tiled_destroy(p);
+        return rc;
+    }
+    *out = p;
+    return FRI_HIP_OK;
+}
+
+int fri_hip_plan_tiled_destroy(fri_hip_plan_tiled *p) {
+    if (p && p->ctx) (void)hipSetDevice(p->ctx->device); // the buffers and the inner plan free their resources on the plan's device
+    delete p;
+    return FRI_HIP_OK;
+}
+
+fri_hip_plan *fri_hip_plan_tiled_tile(fri_hip_plan_tiled *p) { return p ? p->tile.get() : nullptr; }
+
+int fri_hip_plan_tiled_grid(const fri_hip_plan_tiled *p, uint32_t out[4]) {
+    if (!p || !out) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    out[0] = p->nx, out[1] = p->ny, out[2] = p->tile_w, out[3] = p->tile_h;
+    return FRI_HIP_OK;
+}
+
+int fri_hip_split_tiles_dev(fri_hip_plan_tiled *p, const uint8_t *d_raster, uint8_t *d_tiles, void *stream) {
+    if (int rc = need_device_tiled(p)) return rc;
+    if (!d_raster || !d_tiles) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    HIP_TRY(p->ctx, launch_split_tiles(d_raster, p->width, p->height, p->channels, p->tile_w, p->tile_h, d_tiles, (hipStream_t)stream));
+    return FRI_HIP_OK;
+}
+
+int fri_hip_merge_tiles_dev(fri_hip_plan_tiled *p, const uint8_t *d_tiles, uint8_t *d_raster, void *stream) {
+    if (int rc = need_device_tiled(p)) return rc;
+    if (!d_raster || !d_tiles) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    HIP_TRY(p->ctx, launch_merge_tiles(d_tiles, p->width, p->height, p->channels, p->tile_w, p->tile_h, d_raster, (hipStream_t)stream));
+    return FRI_HIP_OK;
+}
+
+int fri_hip_encode_symbols_tiled_dev(fri_hip_plan_tiled *p, const uint8_t *d_raster, const int32_t qmatrix[32], int fit, float *d_params, uint16_t *d_symbols, uint32_t *d_hist,
+                                     uint64_t *d_n_out_of_alphabet, uint64_t *d_fit_out_of_range, void *stream) {
+    if (int rc = need_device_tiled(p)) return rc;
+    if (!d_raster || !qmatrix || !d_params || !d_symbols || !d_hist || !d_n_out_of_alphabet || !p->tile->d_stream_order) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    fri_hip_ctx *c = p->ctx;
+    const hipStream_t s = (hipStream_t)stream;
+    QMatrix q;
+    if (int rc = check_q(qmatrix, q)) return rc;
+    if (int rc = refuse_capture(p->tile.get(), s)) return rc; // (what the inner call refuses, before anything is enqueued or allocated)
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int rc = grow(c, p->tiles, p->n_tiles() * p->tile_bytes())) return rc;
+    HIP_TRY(c, launch_split_tiles(d_raster, p->width, p->height, p->channels, p->tile_w, p->tile_h, p->tiles, s));
+    return fri_hip_encode_symbols_batch_dev(p->tile.get(), (uint32_t)p->n_tiles(), p->tiles, p->tile_bytes(), qmatrix, fit, d_params, nullptr, 0, nullptr, 0, d_symbols,
+                                            (size_t)p->channels * p->tile->geo.n_some, d_hist, d_n_out_of_alphabet, d_fit_out_of_range, stream);
+}
+
+int fri_hip_encode_image_tiled_symbols(fri_hip_plan_tiled *p, const uint8_t *pixels, const int32_t qmatrix[32], float *value_params, float *width_params, uint16_t *symbols,
+                                       uint32_t *hist, uint64_t *n_out_of_alphabet) {
+    if (int rc = need_device_tiled(p)) return rc;
+    if (!pixels || !qmatrix || !value_params || !width_params || !symbols || !hist || !n_out_of_alphabet) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    fri_hip_ctx *c = p->ctx;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t planes = p->n_tiles() * p->channels, n = p->tile->geo.n_some;
+    int rc;
+    if ((rc = grow(c, p->raster, p->raster_bytes())) || (rc = grow(c, p->symbols, std::max<size_t>(planes * n, 1))) || (rc = grow(c, p->hist, planes * 10 * 1024)) ||
+        (rc = grow(c, p->counts, 2 * planes)) || (rc = grow(c, p->params, planes * 36)))
+        return rc;
+    HIP_TRY(c, hipMemcpy(p->raster, pixels, p->raster_bytes(), hipMemcpyHostToDevice));
+    uint64_t *oob = reinterpret_cast<uint64_t *>(p->counts.get());
+    if ((rc = fri_hip_encode_symbols_tiled_dev(p, p->raster, qmatrix, 1, p->params, p->symbols, p->hist, oob, oob + planes, nullptr))) return rc;
+    std::vector<float> params(planes * 36);
+    std::vector<uint64_t> counts(2 * planes);
+    HIP_TRY(c, hipMemcpy(symbols, p->symbols, planes * n * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(hist, p->hist, planes * 10 * 1024 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(params.data(), p->params, planes * 36 * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(counts.data(), p->counts, 2 * planes * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    bool out_of_range = false;
+    for (size_t k = 0; k < planes; k++) {
+        std::memcpy(value_params + k * 18, params.data() + k * 36, 18 * sizeof(float));
+        std::memcpy(width_params + k * 18, params.data() + k * 36 + 18, 18 * sizeof(float));
+        n_out_of_alphabet[k] = counts[k];
+        out_of_range = out_of_range || counts[planes + k];
+    }
+    return out_of_range ? FRI_HIP_ERR_OUT_OF_RANGE : FRI_HIP_OK;
+}
+
+int fri_hip_decode_image_tiled(fri_hip_plan_tiled *p, const int32_t *coefs, const int32_t qmatrix[32], uint8_t *pixels) {
+    if (int rc = need_device_tiled(p)) return rc;
+    if (!coefs || !qmatrix || !pixels) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    fri_hip_ctx *c = p->ctx;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t image = fri_hip_plan_coef_count(p->tile.get()), n = p->n_tiles();
+    int rc;
+    if ((rc = grow(c, p->coefs, n * image)) || (rc = grow(c, p->tiles, n * p->tile_bytes())) || (rc = grow(c, p->raster, p->raster_bytes()))) return rc;
+    HIP_TRY(c, hipMemcpy(p->coefs, coefs, n * image * sizeof(int32_t), hipMemcpyHostToDevice));
+    if ((rc = fri_hip_inverse_transform_batch_dev(p->tile.get(), (uint32_t)n, p->coefs, image, qmatrix, p->tiles, p->tile_bytes(), nullptr))) return rc;
+    HIP_TRY(c, launch_merge_tiles(p->tiles, p->width, p->height, p->channels, p->tile_w, p->tile_h, p->raster, nullptr));
+    HIP_TRY(c, hipMemcpy(pixels, p->raster, p->raster_bytes(), hipMemcpyDeviceToHost));
+    return FRI_HIP_OK;
+}
+
+} // extern "C"

@@ -177,6 +177,11 @@ hipError_t launch_merge420(const uint8_t *y, const uint8_t *cbcr, uint32_t width
 hipError_t launch_split_rgba(const uint8_t *rgba, uint32_t width, uint32_t height, bool clean, uint8_t *rgb, uint8_t *a, hipStream_t stream);
 hipError_t launch_merge_rgba(const uint8_t *rgb, const uint8_t *a, uint32_t width, uint32_t height, uint8_t *rgba, hipStream_t stream);
 
+// K10 (k10_tiles.hip): the raster kernels of tiled coding (include/fri_hip.h has the format). Split: the image [H][W][C] -> the tile raster
+// [ny nx][tile_h][tile_w][C] with edge replication. Merge: the tile raster's in-image pixels back. C is 1 or 3; any shape, any pointer alignment.
+hipError_t launch_split_tiles(const uint8_t *image, uint32_t width, uint32_t height, uint32_t channels, uint32_t tile_w, uint32_t tile_h, uint8_t *tiles, hipStream_t stream);
+hipError_t launch_merge_tiles(const uint8_t *tiles, uint32_t width, uint32_t height, uint32_t channels, uint32_t tile_w, uint32_t tile_h, uint8_t *image, hipStream_t stream);
+
 // K2's per-node neighbour offsets (LDS halfword offsets relative to the own slot, two per word) from the static neighbour table
 void build_lf_deltas(const uint16_t *nbr_table, int8_t *out /* [8] */);
 void build_gather_tables(const uint16_t *nbr_table, uint32_t *gather_off /* [512][4] */, uint16_t *pair_pos /* [256] */, uint16_t *heap_of_pos /* [512] */);

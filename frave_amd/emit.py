@@ -12,6 +12,7 @@ RCT = 0x100  # FRI_EMIT_RCT: `channels = 3 | RCT` - the planes are Y, Cb, Cr of 
 YCBCR = 0x400  # FRI_EMIT_YCBCR: `channels = 3 | YCBCR | QUALITY(q)` - the planes are Y, Cb, Cr of the irreversible JFIF transform (lossy files only)
 S420 = 0x800  # FRI_EMIT_420: `channels = 3 | YCBCR | S420 | QUALITY(q)` in encode_image_from_streams - 4:2:0, Cb and Cr are streams of the half-resolution lattice
 FRI_EMIT_ALPHA = ALPHA = 0x1000  # FRI_EMIT_ALPHA: `channels = 3 | ALPHA [| RCT | YCBCR | QUALITY(q)]` in encode_image_from_streams - a fourth, lossless channel: the alpha plane
+FRI_EMIT_EMPTY_OK = EMPTY_OK = 0x2000  # FRI_EMIT_EMPTY_OK: in encode_image_from_streams - a context without symbols gets the model of max_freq_bits = 0 instead of the error
 
 
 def QUALITY(q):
@@ -45,6 +46,9 @@ def load_library():
         L.fri_emit_rans_selfcheck.argtypes = [C.c_uint64, C.c_uint64, C.c_char_p, sz]
         L.fri_emit_stream_order.argtypes = [vp, u32, vp, vp, vp]
         L.fri_emit_encode_image_from_streams.argtypes = [u32, u32, u32, vp, C.c_uint64, vp, vp, vp, vp, sz, vp, C.c_char_p, sz]
+        L.fri_tiled_encode_from_streams.argtypes = [u32, u32, u32, u32, u32, vp, C.c_uint64, vp, vp, vp, u32, vp, sz, vp, C.c_char_p, sz]
+        L.fri_tiled_info.argtypes = [vp, sz, vp]
+        L.fri_tiled_decode.argtypes = [vp, sz, u32, vp, vp, sz, C.c_char_p, sz]
         _lib = L
     return _lib
 
@@ -125,12 +129,12 @@ def stream_order(centers, valid_mask):
     return out[: n.value].copy()
 
 
-def encode_image_from_streams(width, height, streams, hist, value_params, width_params, rct=False, quality=0, ycbcr=False, n_luma=None, alpha=False):
+def encode_image_from_streams(width, height, streams, hist, value_params, width_params, rct=False, quality=0, ycbcr=False, n_luma=None, alpha=False, empty_ok=False):
     """.frv bytes from the device's symbol streams: streams uint16 [C][n_symbols] (bucket << 10 | symbol), hist [C][10][1024], params [C][3][6].
     rct, quality, ycbcr: see encode_image. n_luma: a 4:2:0 file (implies the flag; needs ycbcr and a quality) - streams is the concatenation Y [n_luma],
     Cb [n_c], Cr [n_c] that Plan420.encode_image420_symbols returns; the emitter works n_c out from the geometry. alpha: streams [4][n_symbols], hist
     [4][10][1024], params [4][3][6] - the three colour channels, which rct, quality and ycbcr describe, then the lossless alpha plane
-    (PlanRGBA.encode_image_rgba_symbols returns them so); not with n_luma."""
+    (PlanRGBA.encode_image_rgba_symbols returns them so); not with n_luma. empty_ok: FRI_EMIT_EMPTY_OK - a context without symbols is coded instead of refused."""
     st = np.ascontiguousarray(streams, np.uint16)
     h = np.ascontiguousarray(hist, np.uint32)
     channels = h.size // 10240
@@ -143,7 +147,7 @@ def encode_image_from_streams(width, height, streams, hist, value_params, width_
     n = C.c_size_t(0)
     err = C.create_string_buffer(256)
     out = np.empty(st.size * 4 + planes * (10 * 2070 + 256) + 64, np.uint8)
-    rc = load_library().fri_emit_encode_image_from_streams(width, height, _arg(channels, rct, quality, ycbcr, n_luma is not None, alpha), _p(st), n_symbols, _p(h), _p(vp), _p(wp), _p(out), out.size, C.addressof(n), err, 256)
+    rc = load_library().fri_emit_encode_image_from_streams(width, height, _arg(channels, rct, quality, ycbcr, n_luma is not None, alpha) | (EMPTY_OK if empty_ok else 0), _p(st), n_symbols, _p(h), _p(vp), _p(wp), _p(out), out.size, C.addressof(n), err, 256)
     if rc != 0:
         raise EmitError(err.value.decode() or f"fri_emit_encode_image_from_streams: {rc}")
     return out[: n.value].tobytes()
@@ -221,3 +225,73 @@ def decode_image(frv):
     out.s420 = s420
     out.alpha = alpha
     return out
+
+
+# ---- the tile container `frit` (include/fri_emit.h) ---------------------------------------------------------------------------
+class TiledInfo(tuple):
+    """(width, height, tile_w, tile_h, nx, ny, channels, n_cells) of a tiled file, and .rct / .quality / .ycbcr as DecodedImage has them: what every tile is."""
+
+    rct = False
+    quality = 0
+    ycbcr = False
+
+
+def _tiled_info(info):
+    w, h, tw, th, nx, ny, c, f = (int(x) for x in info)
+    out = TiledInfo((w, h, tw, th, nx, ny, c & 0xFF, f))
+    out.rct, out.ycbcr, out.quality = bool(c & RCT), bool(c & YCBCR), (c >> 16) & 0x7F
+    return out
+
+
+def tiled_encode_from_streams(width, height, tile_w, tile_h, streams, hist, value_params, width_params, rct=False, quality=0, ycbcr=False, threads=0):
+    """fri_tiled_encode_from_streams: the `frit` bytes from what PlanTiled.encode_image_tiled_symbols returns - streams uint16 [n_tiles][C][n_symbols], hist
+    [n_tiles][C][10][1024], params [n_tiles][C][3][6]. Tiles are coded on `threads` workers (0: the hardware concurrency, capped at 16); the bytes do not depend
+    on it. rct, quality, ycbcr: see encode_image - they hold for every tile."""
+    st = np.ascontiguousarray(streams, np.uint16)
+    h = np.ascontiguousarray(hist, np.uint32)
+    vp, wp = np.ascontiguousarray(value_params, np.float32), np.ascontiguousarray(width_params, np.float32)
+    n_tiles = -(-width // tile_w) * -(-height // tile_h)
+    planes = h.size // 10240
+    channels = planes // n_tiles
+    assert planes == n_tiles * channels and h.size == planes * 10240 and vp.size == planes * 18 and wp.size == planes * 18 and st.size % planes == 0
+    n_symbols = st.size // planes
+    n = C.c_size_t(0)
+    err = C.create_string_buffer(256)
+    out = np.empty(st.size * 4 + planes * (10 * 2070 + 256) + n_tiles * 72 + 64, np.uint8)
+    args = (width, height, tile_w, tile_h, _arg(channels, rct, quality, ycbcr), _p(st), n_symbols, _p(h), _p(vp), _p(wp), threads)
+    L = load_library()
+    rc = L.fri_tiled_encode_from_streams(*args, _p(out), out.size, C.addressof(n), err, 256)
+    if rc == -3:
+        out = np.empty(n.value, np.uint8)
+        rc = L.fri_tiled_encode_from_streams(*args, _p(out), out.size, C.addressof(n), err, 256)
+    if rc != 0:
+        raise EmitError(err.value.decode() or f"fri_tiled_encode_from_streams: {rc}")
+    return out[: n.value].tobytes()
+
+
+def tiled_info(frv):
+    """fri_tiled_info: the TiledInfo of a `frit` file (header, table and every payload's header are checked; nothing is decoded)."""
+    data = np.frombuffer(frv, np.uint8)
+    info = np.zeros(8, np.uint32)
+    rc = load_library().fri_tiled_info(_p(data), data.size, _p(info))
+    if rc != 0:
+        raise EmitError(f"fri_tiled_info: {rc}")
+    return _tiled_info(info)
+
+
+def tiled_decode(frv, threads=0):
+    """fri_tiled_decode: (TiledInfo, coefs int32 [n_tiles][C][F][512] with None = INT32_MIN) - what PlanTiled.decode_image_tiled takes. Tiles are decoded on
+    `threads` workers (0: the hardware concurrency, capped at 16)."""
+    data = np.frombuffer(frv, np.uint8)
+    info = np.zeros(8, np.uint32)
+    err = C.create_string_buffer(256)
+    L = load_library()
+    rc = L.fri_tiled_decode(_p(data), data.size, threads, _p(info), None, 0, err, 256)
+    if rc != -3:
+        raise EmitError(err.value.decode() or f"fri_tiled_decode: {rc}")
+    ti = _tiled_info(info)
+    coefs = np.empty((ti[4] * ti[5], ti[6], ti[7], 512), np.int32)
+    rc = L.fri_tiled_decode(_p(data), data.size, threads, _p(info), _p(coefs), coefs.size, err, 256)
+    if rc != 0:
+        raise EmitError(err.value.decode() or f"fri_tiled_decode: {rc}")
+    return ti, coefs

@@ -540,7 +540,7 @@ int rans_selfcheck(uint64_t n_symbols, uint64_t seed, std::string &err) {
     return 0;
 }
 
-static std::string contexts_from_hist(const uint32_t *hist, ChannelStream &out);
+static std::string contexts_from_hist(const uint32_t *hist, ChannelStream &out, bool empty_ok = false);
 std::string encode_channel(const SymbolOrder &order, const int32_t *coefs, const uint8_t *bucket, const int32_t *prediction, const uint32_t *hist,
                            ChannelStream &out) {
     const std::string cerr = contexts_from_hist(hist, out);
@@ -561,17 +561,20 @@ std::string encode_channel(const SymbolOrder &order, const int32_t *coefs, const
     return "";
 }
 
-// The channel's ANS models from the histogram K2 measured (prediction.rs:302-305)
-static std::string contexts_from_hist(const uint32_t *hist, ChannelStream &out) {
+// The channel's ANS models from the histogram K2 measured (prediction.rs:302-305). empty_ok (FRI_EMIT_EMPTY_OK): a context without symbols gets the model finalize
+// builds from max_freq_bits = 0 - raised to its floor of 8, the Laplace shape, no off-distribution values - instead of the error; no symbol ever looks it up.
+static std::string contexts_from_hist(const uint32_t *hist, ChannelStream &out, bool empty_ok) {
     for (int b = 0; b < kContexts; b++) {
         AnsContext &c = out.contexts[b];
         uint64_t sum = 0;
+        bool any = false;
         for (int j = 0; j < kAlphabet; j++) {
             c.freqs[j] = hist[b * kAlphabet + j];
             sum = (uint32_t)(sum + c.freqs[j]);
+            any = any || c.freqs[j] != 0;
         }
         c.off_distribution_values.clear();
-        c.max_freq_bits = trailing_zeros64(prev_power_two(sum));
+        c.max_freq_bits = empty_ok && !any ? 0u : trailing_zeros64(prev_power_two(sum));
         const std::string err = c.finalize(b);
         if (!err.empty()) return "context " + std::to_string(b) + ": " + err;
     }
@@ -597,8 +600,8 @@ std::vector<uint32_t> stream_order(const SymbolOrder &order, const uint32_t *val
 }
 
 // One channel from the symbol stream the device wrote: stream[i] = bucket << 10 | symbol of the i-th Some node in stream order.
-std::string encode_channel_from_stream(const uint16_t *stream, size_t n, const uint32_t *hist, ChannelStream &out) {
-    const std::string cerr = contexts_from_hist(hist, out);
+std::string encode_channel_from_stream(const uint16_t *stream, size_t n, const uint32_t *hist, ChannelStream &out, bool empty_ok, bool one_thread) {
+    const std::string cerr = contexts_from_hist(hist, out, empty_ok);
     if (!cerr.empty()) return cerr;
     std::vector<uint16_t> symbols(n);
     std::vector<uint8_t> buckets(n);
@@ -612,20 +615,28 @@ std::string encode_channel_from_stream(const uint16_t *stream, size_t n, const u
             const AnsContext &c = out.contexts[b];
             tab[(size_t)b * kAlphabet + j] = c.freqs[j] ? RansEncoderMulti::make_symbol(c.cdf[j], c.freqs[j], c.max_freq_bits) : RansEncoderMulti::EncSymbol{0, 0, 0, 0, 0, 0};
         }
-    const std::string err = encode_symbols(symbols, buckets, tab, out.data);
+    const std::string err = encode_symbols(symbols, buckets, tab, out.data, one_thread); // (the one-loop coder writes the same bytes: fri_emit_rans_selfcheck)
     if (!err.empty()) return err;
     out.n_symbols = n;
     return "";
 }
 
-std::string encode_channels_from_streams(uint32_t channels, const uint16_t *streams, size_t n_symbols, const uint32_t *hist, std::vector<ChannelStream> &out, size_t n_chroma) {
+std::string encode_channels_from_streams(uint32_t channels, const uint16_t *streams, size_t n_symbols, const uint32_t *hist, std::vector<ChannelStream> &out, size_t n_chroma,
+                                         bool empty_ok, bool one_thread) {
     out.assign(channels, ChannelStream{});
+    if (one_thread) { // a tile of a tiled image: the caller's workers are the threads
+        for (uint32_t ch = 0; ch < channels; ch++) {
+            const std::string e = encode_channel_from_stream(streams + (size_t)ch * n_symbols, n_symbols, hist + (size_t)ch * kContexts * kAlphabet, out[ch], empty_ok, true);
+            if (!e.empty()) return "channel " + std::to_string(ch) + ": " + e;
+        }
+        return "";
+    }
     std::vector<std::string> errs(channels);
     std::vector<std::thread> workers;
     const size_t n_rest = n_chroma ? n_chroma : n_symbols; // symbols of every channel behind the first
     for (uint32_t ch = 1; ch < channels; ch++)
-        workers.emplace_back([&, ch] { errs[ch] = encode_channel_from_stream(streams + n_symbols + (size_t)(ch - 1) * n_rest, n_rest, hist + (size_t)ch * kContexts * kAlphabet, out[ch]); });
-    if (channels) errs[0] = encode_channel_from_stream(streams, n_symbols, hist, out[0]);
+        workers.emplace_back([&, ch] { errs[ch] = encode_channel_from_stream(streams + n_symbols + (size_t)(ch - 1) * n_rest, n_rest, hist + (size_t)ch * kContexts * kAlphabet, out[ch], empty_ok); });
+    if (channels) errs[0] = encode_channel_from_stream(streams, n_symbols, hist, out[0], empty_ok);
     for (std::thread &t : workers) t.join();
     for (uint32_t ch = 0; ch < channels; ch++)
         if (!errs[ch].empty()) return "channel " + std::to_string(ch) + ": " + errs[ch];
@@ -1007,6 +1018,145 @@ std::string deserialize(const std::vector<uint8_t> &b, ParsedImage &out) {
             return "Malformed image bytes";
         }
     }
+}
+
+// ---- the tile container `frit` (include/fri_emit.h has it bit for bit) ----------------------------------------------------------------
+namespace {
+constexpr size_t kTiledHeader = 32;
+const char *const kMalformedTiled = "Malformed tiled image";
+uint32_t get_u32(const uint8_t *b) { return (uint32_t)b[0] | (uint32_t)b[1] << 8 | (uint32_t)b[2] << 16 | (uint32_t)b[3] << 24; }
+uint64_t get_u64(const uint8_t *b) { return (uint64_t)get_u32(b) | (uint64_t)get_u32(b + 4) << 32; }
+
+unsigned tile_workers(unsigned threads, size_t n_tiles) {
+    if (!threads) {
+        const unsigned hw = std::thread::hardware_concurrency();
+        threads = hw ? std::min(hw, 16u) : 4u;
+    }
+    return (unsigned)std::max<size_t>(1, std::min<size_t>(threads, n_tiles));
+}
+
+// work(t) for every tile on `threads` workers that take the next tile from a shared counter; the error of the lowest failing tile, whatever the thread count
+template <typename Work>
+std::string for_each_tile(size_t n_tiles, unsigned threads, Work &&work) {
+    std::vector<std::string> errs(n_tiles);
+    std::atomic<size_t> next{0};
+    auto run = [&] {
+        for (size_t t; (t = next.fetch_add(1)) < n_tiles;) errs[t] = work(t);
+    };
+    const unsigned n = tile_workers(threads, n_tiles);
+    std::vector<std::thread> workers;
+    for (unsigned k = 1; k < n; k++) workers.emplace_back(run);
+    run();
+    for (std::thread &w : workers) w.join();
+    for (size_t t = 0; t < n_tiles; t++)
+        if (!errs[t].empty()) return "tile " + std::to_string(t) + ": " + errs[t];
+    return "";
+}
+} // namespace
+
+std::string encode_tiled_from_streams(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t channels, bool rct, uint32_t quality, bool ycbcr,
+                                      const uint16_t *streams, size_t n_symbols, const uint32_t *hist, const float *value_params, const float *width_params, unsigned threads,
+                                      std::vector<uint8_t> &out) {
+    if (!width || !height || !tile_w || !tile_h || (channels != 1 && channels != 3)) return "invalid argument";
+    const uint64_t nx = ((uint64_t)width + tile_w - 1) / tile_w, ny = ((uint64_t)height + tile_h - 1) / tile_h;
+    if (nx * ny > 0xFFFFFFFFull) return "invalid argument";
+    const size_t n_tiles = (size_t)(nx * ny);
+    { // the tile geometry, once: every tile's streams are streams of this lattice
+        fri::Geometry g;
+        const std::string ge = fri::build_geometry(tile_w, tile_h, channels, fri::TilingParams{}, g);
+        if (!ge.empty()) return ge;
+        if (g.n_some != n_symbols) return "n_symbols is not the symbol count of the tile_w x tile_h lattice";
+    }
+    const ColorSpaceCode cs = channels == 1 ? kLuma : rct || ycbcr ? kYCbCr : kRGB;
+    std::vector<std::vector<uint8_t>> payload(n_tiles);
+    const std::string e = for_each_tile(n_tiles, threads, [&](size_t t) -> std::string {
+        const size_t plane0 = t * channels;
+        std::vector<ChannelStream> chans;
+        const std::string ce = encode_channels_from_streams(channels, streams + plane0 * n_symbols, n_symbols, hist + plane0 * kContexts * kAlphabet, chans, 0, true, true);
+        if (!ce.empty()) return ce;
+        std::vector<ChannelParams> params(channels);
+        for (uint32_t ch = 0; ch < channels; ch++) {
+            std::memcpy(params[ch].value, value_params + (plane0 + ch) * 18, sizeof(params[ch].value));
+            std::memcpy(params[ch].width, width_params + (plane0 + ch) * 18, sizeof(params[ch].width));
+        }
+        payload[t] = serialize(tile_h, tile_w, cs, chans, params, rct, quality, ycbcr);
+        return "";
+    });
+    if (!e.empty()) return e;
+    out.clear();
+    uint64_t total = kTiledHeader + 8 * (n_tiles + 1);
+    for (const auto &b : payload) total += b.size();
+    out.reserve(total);
+    out.insert(out.end(), {'f', 'r', 'i', 't'});
+    put_u32(out, 1);
+    put_u32(out, height), put_u32(out, width), put_u32(out, tile_h), put_u32(out, tile_w), put_u32(out, (uint32_t)ny), put_u32(out, (uint32_t)nx);
+    uint64_t at = kTiledHeader + 8 * (n_tiles + 1);
+    for (size_t t = 0; t < n_tiles; t++) put_u64(out, at), at += payload[t].size();
+    put_u64(out, at);
+    for (const auto &b : payload) out.insert(out.end(), b.begin(), b.end());
+    return "";
+}
+
+std::string parse_tiled(const uint8_t *b, size_t len, TiledInfo &info, std::vector<uint64_t> &offset) {
+    if (len < kTiledHeader + 16 || std::memcmp(b, "frit", 4) != 0 || get_u32(b + 4) != 1) return kMalformedTiled;
+    info.height = get_u32(b + 8), info.width = get_u32(b + 12), info.tile_h = get_u32(b + 16), info.tile_w = get_u32(b + 20), info.ny = get_u32(b + 24), info.nx = get_u32(b + 28);
+    if (!info.height || !info.width || !info.tile_h || !info.tile_w) return kMalformedTiled;
+    if (info.nx != ((uint64_t)info.width + info.tile_w - 1) / info.tile_w || info.ny != ((uint64_t)info.height + info.tile_h - 1) / info.tile_h) return kMalformedTiled;
+    const uint64_t n = (uint64_t)info.nx * info.ny;
+    if (n > (len - kTiledHeader) / 8 - 1) return kMalformedTiled; // (the table alone would not fit)
+    offset.resize(n + 1);
+    for (uint64_t t = 0; t <= n; t++) offset[t] = get_u64(b + kTiledHeader + 8 * t);
+    if (offset[0] != kTiledHeader + 8 * (n + 1) || offset[n] != len) return kMalformedTiled;
+    for (uint64_t t = 0; t < n; t++)
+        if (offset[t + 1] <= offset[t] || offset[t + 1] - offset[t] < 16) return kMalformedTiled;
+    // tile 0's header says what every tile is
+    const uint8_t *p0 = b + offset[0];
+    if (std::memcmp(p0, "frif", 4) != 0 || get_u32(p0 + 4) != info.tile_h || get_u32(p0 + 8) != info.tile_w) return kMalformedTiled;
+    info.mdat = get_u32(p0 + 12);
+    const uint32_t cs = info.mdat >> 30 & 3u;
+    if (cs == 0 || (info.mdat >> 28 & 3u) == 0) return kMalformedTiled;
+    info.channels = cs == kLuma ? 1u : 3u;
+    info.rct = cs == kYCbCr && (info.mdat & kMdatRct);
+    info.ycbcr = cs == kYCbCr && (info.mdat & kMdatYcbcr);
+    info.quality = info.mdat >> kMdatQualityShift & kMdatQualityMask;
+    for (uint64_t t = 1; t < n; t++) { // every payload is a file of a tile_h x tile_w image with that metadata word
+        const uint8_t *p = b + offset[t];
+        if (std::memcmp(p, "frif", 4) != 0 || get_u32(p + 4) != info.tile_h || get_u32(p + 8) != info.tile_w || get_u32(p + 12) != info.mdat) return kMalformedTiled;
+    }
+    if ((cs == kYCbCr && (info.mdat & kMdat420)) || (cs != kLuma && (info.mdat & kMdatAlpha))) return kMalformedTiled; // 4:2:0 and alpha inside tiles are refused
+    if (info.quality >= 100 || (info.ycbcr && (info.rct || info.quality == 0))) return kMalformedTiled;
+    return "";
+}
+
+std::string decode_tiled(const uint8_t *b, size_t len, unsigned threads, TiledInfo &info, int32_t *coefs, size_t coef_cap, bool &too_small) {
+    too_small = false;
+    std::vector<uint64_t> offset;
+    std::string e = parse_tiled(b, len, info, offset);
+    if (!e.empty()) return e;
+    fri::Geometry g; // one geometry and one symbol order for all tiles
+    e = fri::build_geometry(info.tile_w, info.tile_h, info.channels, fri::TilingParams{}, g);
+    if (!e.empty()) return e;
+    const size_t F = g.centers.size(), plane = F * kNodes, n_tiles = (size_t)info.nx * info.ny;
+    info.n_cells = (uint32_t)F;
+    if (!coefs || coef_cap < n_tiles * info.channels * plane) return too_small = true, "";
+    std::vector<int32_t> centers(F * 2);
+    for (size_t c = 0; c < F; c++) centers[2 * c] = g.centers[c].x, centers[2 * c + 1] = g.centers[c].y;
+    const auto order = shared_symbol_order(centers.data(), (uint32_t)F);
+    return for_each_tile(n_tiles, threads, [&](size_t t) -> std::string {
+        const uint8_t *p = b + offset[t];
+        ParsedImage img;
+        const std::string de = deserialize(std::vector<uint8_t>(p, b + offset[t + 1]), img);
+        if (!de.empty()) return de;
+        if (img.channels.size() != info.channels) return kMalformedTiled;
+        for (const ChannelStream &c : img.channels)
+            for (const AnsContext &a : c.contexts)
+                if (a.max_freq_bits == 0) return "Malformed image bytes"; // fewer than ten EHD segments
+        for (uint32_t ch = 0; ch < info.channels; ch++) {
+            const std::string ce = decode_channel(g, *order, img.channels[ch], img.params[ch], coefs + (t * info.channels + ch) * plane);
+            if (!ce.empty()) return "channel " + std::to_string(ch) + ": " + ce;
+        }
+        return "";
+    });
 }
 
 } // namespace emit

@@ -121,10 +121,12 @@ std::string encode_channels(const SymbolOrder &order, uint32_t channels, const i
 // per symbol, geometry only: uploaded once per plan); a channel's stream is then stream[i] = bucket << 10 | symbol, 2 bytes per symbol instead of
 // the 9 bytes per node of (coefficient, prediction, bucket), and the emitter is the pure rANS loop.
 std::vector<uint32_t> stream_order(const SymbolOrder &order, const uint32_t *valid_mask /* [n_cells][16] */);
-std::string encode_channel_from_stream(const uint16_t *stream, size_t n_symbols, const uint32_t *hist, ChannelStream &out);
+// empty_ok (FRI_EMIT_EMPTY_OK, include/fri_emit.h): a context without symbols gets the model of max_freq_bits = 0 instead of the error. one_thread: the plain
+// one-loop coder and no channel threads - the same bytes; for callers that run many images on workers of their own (the tiled container).
+std::string encode_channel_from_stream(const uint16_t *stream, size_t n_symbols, const uint32_t *hist, ChannelStream &out, bool empty_ok = false, bool one_thread = false);
 // n_chroma != 0 (4:2:0 files, three channels): channels 1 and 2 are streams of n_chroma symbols each, directly behind channel 0's n_symbols.
 std::string encode_channels_from_streams(uint32_t channels, const uint16_t *streams /* [channels][n_symbols] */, size_t n_symbols, const uint32_t *hist,
-                                         std::vector<ChannelStream> &out, size_t n_chroma = 0);
+                                         std::vector<ChannelStream> &out, size_t n_chroma = 0, bool empty_ok = false, bool one_thread = false);
 // The (symbol, bucket) sequence in stream order (what encode_channel feeds to the coder); for self-checks.
 void channel_symbols(const SymbolOrder &order, const int32_t *coefs, const uint8_t *bucket, const int32_t *prediction, std::vector<uint16_t> &symbols,
                      std::vector<uint8_t> &buckets);
@@ -194,6 +196,27 @@ struct DecodedImage {
 std::string decode_image(const std::vector<uint8_t> &frv, DecodedImage &out);
 std::string decode_parsed(const ParsedImage &img, DecodedImage &out); // the entropy_coding::decode half of it
 std::string count_cells(uint32_t width, uint32_t height, uint32_t channels, uint32_t &n_cells); // retained cells of a width x height image
+
+// ---- the tile container `frit` (include/fri_emit.h has the format bit for bit) -----------------------------------------------------
+// A layer above the image emitter: a header, a table of offsets and, per tile, a complete `frif` file of a tile_h x tile_w image - exactly what
+// fri_emit_encode_image_from_streams writes for that tile's streams with FRI_EMIT_EMPTY_OK. Tiles are coded and decoded on workers that share one geometry and
+// one symbol order; the bytes do not depend on the thread count. threads = 0: the hardware concurrency, capped at 16.
+struct TiledInfo {
+    uint32_t width = 0, height = 0, tile_w = 0, tile_h = 0, nx = 0, ny = 0;
+    uint32_t mdat = 0; // the metadata word every tile carries, and what it says:
+    uint32_t channels = 0, quality = 0;
+    bool rct = false, ycbcr = false;
+    uint32_t n_cells = 0; // F of the tile lattice (decode_tiled only)
+};
+// streams [n_tiles][channels][n_symbols], hist [n_tiles][channels][10][1024], value_params / width_params [n_tiles][channels][3][6]: what
+// fri_hip_encode_image_tiled_symbols returns. Returns "" or the error ("tile t: channel c: reason" from a tile).
+std::string encode_tiled_from_streams(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t channels, bool rct, uint32_t quality, bool ycbcr,
+                                      const uint16_t *streams, size_t n_symbols, const uint32_t *hist, const float *value_params, const float *width_params, unsigned threads,
+                                      std::vector<uint8_t> &out);
+// Header, table and every payload's 16-byte header; "Malformed tiled image" for anything that does not hold together. offset: [n_tiles + 1].
+std::string parse_tiled(const uint8_t *frv, size_t len, TiledInfo &info, std::vector<uint64_t> &offset);
+// coefs [n_tiles][channels][F][512]. too_small: coefs is NULL or coef_cap (elements) does not hold them - `info` is filled, nothing is decoded.
+std::string decode_tiled(const uint8_t *frv, size_t len, unsigned threads, TiledInfo &info, int32_t *coefs, size_t coef_cap, bool &too_small);
 
 } // namespace emit
 } // namespace libfri

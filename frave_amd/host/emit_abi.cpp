@@ -15,8 +15,13 @@ int fail(char *err, size_t cap, const std::string &msg, int code = -1) {
 }
 // `channels` of the encoders and the check: 1 or 3, with FRI_EMIT_RCT (3 only) or FRI_EMIT_QUALITY(1..99) (not both); FRI_EMIT_YCBCR only as
 // 3 | FRI_EMIT_YCBCR | FRI_EMIT_QUALITY(1..99); FRI_EMIT_420 only on top of that, and only where the caller takes it (s420 != NULL: the stream route).
-// FRI_EMIT_ALPHA only with three channels, never with FRI_EMIT_420, and only where the caller takes it (alpha != NULL: the stream route). False for anything else.
-bool split_channels(uint32_t arg, uint32_t &channels, bool &rct, uint32_t &quality, bool &ycbcr, bool *s420 = nullptr, bool *alpha = nullptr) {
+// FRI_EMIT_ALPHA only with three channels, never with FRI_EMIT_420, and only where the caller takes it (alpha != NULL: the stream route). FRI_EMIT_EMPTY_OK only
+// where the caller takes it (empty_ok != NULL: the stream route). False for anything else.
+bool split_channels(uint32_t arg, uint32_t &channels, bool &rct, uint32_t &quality, bool &ycbcr, bool *s420 = nullptr, bool *alpha = nullptr, bool *empty_ok = nullptr) {
+    const bool has_empty_ok = (arg & FRI_EMIT_EMPTY_OK) != 0;
+    if (has_empty_ok && !empty_ok) return false;
+    if (empty_ok) *empty_ok = has_empty_ok;
+    arg &= ~(uint32_t)FRI_EMIT_EMPTY_OK;
     rct = (arg & FRI_EMIT_RCT) != 0;
     ycbcr = (arg & FRI_EMIT_YCBCR) != 0;
     const bool sub = (arg & FRI_EMIT_420) != 0;
@@ -127,8 +132,9 @@ int fri_emit_encode_image_from_streams(uint32_t width, uint32_t height, uint32_t
     uint32_t channels;
     bool rct, ycbcr;
     uint32_t quality;
-    bool s420 = false, alpha = false;
-    if (!streams || !hist || !value_params || !width_params || !len || !split_channels(channels_arg, channels, rct, quality, ycbcr, &s420, &alpha)) return fail(err, err_cap, "invalid argument");
+    bool s420 = false, alpha = false, empty_ok = false;
+    if (!streams || !hist || !value_params || !width_params || !len || !split_channels(channels_arg, channels, rct, quality, ycbcr, &s420, &alpha, &empty_ok))
+        return fail(err, err_cap, "invalid argument");
     const uint32_t planes = channels + (alpha ? 1u : 0u); // the alpha plane's stream, histograms and parameters follow the colour channels'
     uint64_t n_chroma = 0;
     if (s420) { // the streams of Cb and Cr are those of the half-resolution lattice: the emitter learns their length from the geometry, like its decoder
@@ -141,7 +147,7 @@ int fri_emit_encode_image_from_streams(uint32_t width, uint32_t height, uint32_t
     }
     std::vector<ChannelStream> chans;
     std::vector<ChannelParams> params(planes);
-    const std::string e = encode_channels_from_streams(planes, streams, (size_t)n_symbols, hist, chans, (size_t)n_chroma);
+    const std::string e = encode_channels_from_streams(planes, streams, (size_t)n_symbols, hist, chans, (size_t)n_chroma, empty_ok);
     if (!e.empty()) return fail(err, err_cap, e, -2);
     for (uint32_t ch = 0; ch < planes; ch++) {
         std::memcpy(params[ch].value, value_params + (size_t)ch * 18, sizeof(params[ch].value));
@@ -213,6 +219,53 @@ int fri_emit_decode_image(const uint8_t *frv, size_t len, uint32_t info[4], int3
     std::memcpy(coefs, d.coefs.data(), d.coefs.size() * sizeof(int32_t));
     if (centers) std::memcpy(centers, d.centers.data(), d.centers.size() * sizeof(int32_t));
     return 0;
+}
+
+// ---- the tile container (fri_tiled_*, include/fri_emit.h) ---------------------------------------------------------------------------
+namespace {
+void fill_tiled_info(const TiledInfo &t, uint32_t info[8]) {
+    info[0] = t.width, info[1] = t.height, info[2] = t.tile_w, info[3] = t.tile_h, info[4] = t.nx, info[5] = t.ny;
+    info[6] = channels_info(t.channels, t.rct, t.quality, t.ycbcr, false, false), info[7] = t.n_cells;
+}
+} // namespace
+
+int fri_tiled_encode_from_streams(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t channels_arg, const uint16_t *streams, uint64_t n_symbols,
+                                  const uint32_t *hist, const float *value_params, const float *width_params, uint32_t threads, uint8_t *out, size_t cap, size_t *len, char *err,
+                                  size_t err_cap) {
+    uint32_t channels;
+    bool rct, ycbcr;
+    uint32_t quality;
+    // (4:2:0 and alpha inside tiles are refused: split_channels is not given a place for them; FRI_EMIT_EMPTY_OK is always on and may be passed)
+    bool empty_ok = false;
+    if (!streams || !hist || !value_params || !width_params || !len || !split_channels(channels_arg, channels, rct, quality, ycbcr, nullptr, nullptr, &empty_ok))
+        return fail(err, err_cap, "invalid argument");
+    std::vector<uint8_t> bytes;
+    const std::string e = encode_tiled_from_streams(width, height, tile_w, tile_h, channels, rct, quality, ycbcr, streams, (size_t)n_symbols, hist, value_params, width_params, threads, bytes);
+    if (e == "invalid argument") return fail(err, err_cap, e);
+    if (!e.empty()) return fail(err, err_cap, e, -2);
+    *len = bytes.size();
+    if (!out || cap < bytes.size()) return -3;
+    std::memcpy(out, bytes.data(), bytes.size());
+    return 0;
+}
+
+int fri_tiled_info(const uint8_t *frv, size_t len, uint32_t info[8]) {
+    if (!frv || !info) return -1;
+    TiledInfo t;
+    bool too_small = false;
+    if (!decode_tiled(frv, len, 1, t, nullptr, 0, too_small).empty()) return -2;
+    fill_tiled_info(t, info);
+    return 0;
+}
+
+int fri_tiled_decode(const uint8_t *frv, size_t len, uint32_t threads, uint32_t info[8], int32_t *coefs, size_t coef_cap, char *err, size_t err_cap) {
+    if (!frv || !info) return fail(err, err_cap, "invalid argument");
+    TiledInfo t;
+    bool too_small = false;
+    const std::string e = decode_tiled(frv, len, threads, t, coefs, coef_cap, too_small);
+    if (!e.empty()) return fail(err, err_cap, e, -2);
+    fill_tiled_info(t, info);
+    return too_small ? -3 : 0;
 }
 
 #pragma GCC visibility pop

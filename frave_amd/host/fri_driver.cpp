@@ -19,6 +19,9 @@
 //                                                            in.pam: a binary PAM (P7, DEPTH 4, MAXVAL 255, TUPLTYPE RGB_ALPHA) - RGBA: the colour as the options
 //                                                            say (--rct, --quality, --psnr, --ssim, --ycbcr; no --size / --bpp / --420), the alpha plane
 //                                                            losslessly beside it; --clean-alpha: the colour of pixels with A = 0 is coded as 0
+//                                                            --tile-size T (any mode flag but --420; no alpha): the image as a batch of independently coded tiles
+//                                                            of about T x T (fri_hip_tile_shape), a `frit` file; --psnr / --ssim / --size search on the whole image
+//                                                            and code the tiles with that quality (a file over a --size budget: one quality lower until it fits)
 //   fri_driver decode-file <in.frv> <out.pgm|.ppm|.bmp|.pam>  (.pam for a file with an alpha plane, and for no other) container -> rANS / context decoding on the host -> dequantisation + inverse
 //                                                            transform on the device (fri-cli decode, crates/fri-cli/src/commands/decode.rs); a flagged file
 //                                                            comes back as RGB, a lossy file with its quality's matrix and the midpoint dequantiser
@@ -194,12 +197,9 @@ static bool has_suffix(const char *path, const char *suffix) {
     return n >= m && std::strcmp(path + n - m, suffix) == 0;
 }
 
-// `encode` / `encode-file`: the .frv comes from the symbol stream route (FRIEncoder::encode_bytes_streamed: the emitter's gather on the device, 2 bytes per symbol
-// over PCIe) - the default since round 4. Self-checks: the array route (stage functions one by one, 9 bytes per node over PCIe, gather on the host) must give
-// the same bytes - it does bit for bit since the fit's W^T r sums are fixed-point integers (k4_fit.hip): both routes fit the same parameters - ; the container
-// parses and every symbol decodes; FRIDecoder::decode returns the input.
-// Lossy (--quality / --psnr / --ssim): the decoded image must equal the direct round trip K1 with the quality's matrix -> K3 with the midpoint dequantiser.
-static int encode_image_to_file(std::vector<uint8_t> img, uint32_t w, uint32_t h, uint32_t c, libfri::EncoderOpts opts, const char *out_path) {
+// --psnr / --ssim / --size: the quality first - the searches FRIEncoder::encode runs, on the whole image - then the caller codes with it: opts comes back with the
+// quality set and the targets cleared. 0, or 1 after printing the error.
+static int resolve_quality_targets(const std::vector<uint8_t> &img, uint32_t w, uint32_t h, uint32_t c, libfri::EncoderOpts &opts) {
     const libfri::ColorSpace cs = c == 1 ? libfri::ColorSpace::Luma : libfri::ColorSpace::RGB;
     if (opts.target_psnr > 0) { // the quality first (the same search FRIEncoder::encode runs), then both routes code with it
         libfri::Device dev(opts.device);
@@ -255,6 +255,19 @@ static int encode_image_to_file(std::vector<uint8_t> img, uint32_t w, uint32_t h
         std::printf("target %llu bytes: quality %d, estimate %llu bytes, file %llu bytes\n", (unsigned long long)budget, opts.quality ? opts.quality : 100,
                     (unsigned long long)st.value.est_bytes, (unsigned long long)st.value.file_bytes);
     }
+    return 0;
+}
+
+// `encode` / `encode-file`: the .frv comes from the symbol stream route (FRIEncoder::encode_bytes_streamed: the emitter's gather on the device, 2 bytes per symbol
+// over PCIe) - the default since round 4. Self-checks: the array route (stage functions one by one, 9 bytes per node over PCIe, gather on the host) must give
+// the same bytes - it does bit for bit since the fit's W^T r sums are fixed-point integers (k4_fit.hip): both routes fit the same parameters - ; the container
+// parses and every symbol decodes; FRIDecoder::decode returns the input.
+// Lossy (--quality / --psnr / --ssim): the decoded image must equal the direct round trip K1 with the quality's matrix -> K3 with the midpoint dequantiser.
+static int encode_image_to_file(std::vector<uint8_t> img, uint32_t w, uint32_t h, uint32_t c, libfri::EncoderOpts opts, const char *out_path) {
+    const libfri::ColorSpace cs = c == 1 ? libfri::ColorSpace::Luma : libfri::ColorSpace::RGB;
+    const double ssim_target = opts.target_ssim;
+    const uint64_t budget = opts.target_bytes;
+    if (resolve_quality_targets(img, w, h, c, opts)) return 1;
     auto t0 = std::chrono::steady_clock::now();
     libfri::FRIEncoder streamed_encoder(opts);
     auto streamed = streamed_encoder.encode_bytes_streamed(img, h, w, cs);
@@ -453,6 +466,64 @@ static int encode_image_rgba_to_file(const std::vector<uint8_t> &img, uint32_t w
     return 0;
 }
 
+// encode-file --tile-size T: the image as a batch of independently coded tiles (libfri::encode_bytes_tiled; a `frit` file). Self-check: the file decodes
+// (FRIDecoder) to the direct tiled round trip of what it holds (libfri::round_trip_tiled: host split, forward kernel per tile, fri_hip_decode_image_tiled) - for a
+// lossless file that is the input. --psnr / --ssim / --size: there are no searches over tiles, so the quality is the one the whole-image search finds
+// (resolve_quality_targets) and the tiles are coded with it; a tiled file over a --size budget is coded one quality lower until it fits.
+static int encode_image_tiled_to_file(const std::vector<uint8_t> &img, uint32_t w, uint32_t h, uint32_t c, libfri::EncoderOpts opts, uint32_t tile_size, const char *out_path) {
+    const uint64_t budget = opts.target_bytes;
+    if (opts.target_psnr > 0 || opts.target_ssim > 0 || budget) {
+        if (resolve_quality_targets(img, w, h, c, opts)) return 1;
+        std::printf("(the quality of the whole image's search; the tiles are coded with it)\n");
+    }
+    auto t0 = std::chrono::steady_clock::now();
+    auto enc = libfri::encode_bytes_tiled(img, h, w, c == 1 ? libfri::ColorSpace::Luma : libfri::ColorSpace::RGB, opts, tile_size);
+    while (budget && enc.ok && enc.value.bytes.size() > budget) { // tiles cost a few per cent: one quality lower while the file is over
+        const int q = enc.value.quality ? enc.value.quality - 1 : 99;
+        if (q < 1) {
+            std::fprintf(stderr, "quality 1 is %zu bytes in tiles, over the budget of %llu\n", enc.value.bytes.size(), (unsigned long long)budget);
+            return 1;
+        }
+        opts.quality = q;
+        enc = libfri::encode_bytes_tiled(img, h, w, c == 1 ? libfri::ColorSpace::Luma : libfri::ColorSpace::RGB, opts, tile_size);
+    }
+    const double t_enc = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (!enc.ok) {
+        std::fprintf(stderr, "%s\n", enc.error.c_str());
+        return 1;
+    }
+    const std::vector<uint8_t> &bytes = enc.value.bytes;
+    auto back = libfri::FRIDecoder().decode(bytes, opts);
+    std::vector<uint8_t> expected = img;
+    if (enc.value.quality && back.ok) {
+        auto direct = libfri::round_trip_tiled(img, h, w, c, enc.value.tile_w, enc.value.tile_h, enc.value.quality, enc.value.rct, enc.value.ycbcr, opts.device);
+        if (!direct.ok) {
+            std::fprintf(stderr, "self-check failed: direct round trip: %s\n", direct.error.c_str());
+            return 1;
+        }
+        expected = std::move(direct.value.data);
+    }
+    if (!back.ok || back.value.metadata.width != w || back.value.metadata.height != h || back.value.data != expected) {
+        std::fprintf(stderr, "self-check failed: %s\n", back.ok ? (enc.value.quality ? "decoded image differs from the direct tiled round trip" : "the lossless file does not decode to the input") : back.error.c_str());
+        return 1;
+    }
+    if (FILE *f = std::fopen(out_path, "wb")) {
+        std::fwrite(bytes.data(), 1, bytes.size(), f);
+        std::fclose(f);
+    } else {
+        std::fprintf(stderr, "cannot write %s\n", out_path);
+        return 1;
+    }
+    std::printf("%ux%ux%u in %u x %u tiles of %ux%u: %zu bytes, %.3f bits per pixel; device chain and emit %.3f s; self-check: decodes to %s\n", w, h, c, enc.value.nx, enc.value.ny,
+                enc.value.tile_w, enc.value.tile_h, bytes.size(), 8.0 * bytes.size() / ((double)w * h), t_enc, enc.value.quality ? "the direct tiled round trip" : "the input");
+    if (enc.value.quality) {
+        double sse = 0;
+        for (size_t i = 0; i < img.size(); i++) sse += ((double)back.value.data[i] - img[i]) * ((double)back.value.data[i] - img[i]);
+        std::printf("quality %d%s: PSNR %.2f dB\n", enc.value.quality, enc.value.ycbcr ? " in YCbCr" : "", sse > 0 ? 10.0 * std::log10(255.0 * 255.0 * (double)img.size() / sse) : HUGE_VAL);
+    }
+    return 0;
+}
+
 int main(int argc, char **argv) {
     if (argc >= 4 && std::string(argv[1]) == "encode-file") {
         std::vector<uint8_t> img;
@@ -465,7 +536,8 @@ int main(int argc, char **argv) {
         }
         libfri::EncoderOpts file_opts; // parameters are fitted on the device sums (fit_parameters defaults to true)
         double bpp = 0;
-        bool has_size = false, has_bpp = false, has_ssim = false, sub420 = false, clean_alpha = false;
+        bool has_size = false, has_bpp = false, has_ssim = false, sub420 = false, clean_alpha = false, tiled = false;
+        long tile_size = 0;
         for (int i = 4; i < argc; i++) {
             const std::string a = argv[i];
             if (a == "--rct") file_opts.colour_transform = true;
@@ -477,6 +549,7 @@ int main(int argc, char **argv) {
             else if (a == "--ssim" && i + 1 < argc) file_opts.target_ssim = std::atof(argv[++i]), has_ssim = true;
             else if (a == "--size" && i + 1 < argc) file_opts.target_bytes = std::strtoull(argv[++i], nullptr, 10), has_size = true;
             else if (a == "--bpp" && i + 1 < argc) bpp = std::atof(argv[++i]), has_bpp = true;
+            else if (a == "--tile-size" && i + 1 < argc) tile_size = std::atol(argv[++i]), tiled = true;
             else {
                 std::fprintf(stderr, "encode-file: unknown option %s\n", a.c_str());
                 return 2;
@@ -510,6 +583,11 @@ int main(int argc, char **argv) {
             std::fprintf(stderr, "encode-file: an RGBA image takes no --420, --size or --bpp (alpha with 4:2:0 and a size search with alpha are out of scope)\n");
             return 2;
         }
+        if (tiled && (tile_size < 1 || tile_size > 65535 || rgba || sub420)) {
+            std::fprintf(stderr, "encode-file: --tile-size T (1..65535) takes a PGM, PPM or BMP and every mode flag but --420; no alpha (4:2:0 and alpha in tiles are out of scope)\n");
+            return 2;
+        }
+        if (tiled) return encode_image_tiled_to_file(img, fw, fh, fc, file_opts, (uint32_t)tile_size, argv[3]);
         if (rgba) return encode_image_rgba_to_file(img, fw, fh, file_opts, clean_alpha, argv[3]);
         if (sub420) return encode_image_420_to_file(img, fw, fh, file_opts, argv[3]); // (the --ycbcr checks above hold: an RGB image, a lossy target, no --rct)
         return encode_image_to_file(std::move(img), fw, fh, fc, file_opts, argv[3]);
@@ -566,7 +644,7 @@ int main(int argc, char **argv) {
         return 0;
     }
     if (argc < 5) {
-        std::fprintf(stderr, "usage: %s roundtrip|encode|batch|batch-frv <width> <height> <channels> [n_images | out.frv]\n       %s encode-file <in.pgm|in.ppm|in.bmp|in.pam> <out.frv> [--rct | [--ycbcr | --420] (--quality Q | --psnr DB | --ssim S | --size BYTES | --bpp B)] [--clean-alpha]\n       %s decode-file <in.frv> <out.pgm|out.ppm|out.bmp|out.pam>\n", argv[0], argv[0], argv[0]);
+        std::fprintf(stderr, "usage: %s roundtrip|encode|batch|batch-frv <width> <height> <channels> [n_images | out.frv]\n       %s encode-file <in.pgm|in.ppm|in.bmp|in.pam> <out.frv> [--rct | [--ycbcr | --420] (--quality Q | --psnr DB | --ssim S | --size BYTES | --bpp B)] [--clean-alpha] [--tile-size T]\n       %s decode-file <in.frv> <out.pgm|out.ppm|out.bmp|out.pam>\n", argv[0], argv[0], argv[0]);
         return 2;
     }
     const std::string cmd = argv[1];

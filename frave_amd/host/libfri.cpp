@@ -5,6 +5,7 @@
 #include <atomic>
 #include <chrono>
 #include <cmath>
+#include <cstring>
 #include <condition_variable>
 #include <deque>
 #include <memory>
@@ -465,7 +466,49 @@ Result<WaveletImage> stages::entropy_coding::decode(const CompressedImage &image
     return r;
 }
 
+namespace {
+struct TiledPlanDelete {
+    void operator()(fri_hip_plan_tiled *p) const { fri_hip_plan_tiled_destroy(p); }
+};
+using TiledPlan = std::unique_ptr<fri_hip_plan_tiled, TiledPlanDelete>;
+
+// a `frit` file: the tiles' planes from the emitter's workers, then the inverse kernel over all tiles and the merge
+Result<RasterImage> decode_tiled_bytes(const std::vector<uint8_t> &data, const EncoderOpts &opts) {
+    Result<RasterImage> r;
+    auto fail = [&](const std::string &why) {
+        r.error = "Failed to decode: " + why;
+        return r;
+    };
+    emit::TiledInfo ti;
+    bool too_small = false;
+    std::string e = emit::decode_tiled(data.data(), data.size(), 0, ti, nullptr, 0, too_small); // header, table, geometry
+    if (!e.empty()) return fail(e);
+    std::vector<int32_t> coefs((size_t)ti.nx * ti.ny * ti.channels * ti.n_cells * FRI_HIP_CELL_SIZE);
+    e = emit::decode_tiled(data.data(), data.size(), 0, ti, coefs.data(), coefs.size(), too_small);
+    if (!e.empty() || too_small) return fail(e.empty() ? "coefficient array does not match the tile geometry" : e);
+    Device dev(opts.device);
+    if (!dev.ok()) return fail(dev.error());
+    fri_hip_plan_tiled *raw = nullptr;
+    // (a file may hold tiles with holes: whoever wrote it asked for them)
+    if (const int rc = fri_hip_plan_tiled_create(dev.ctx(), ti.width, ti.height, ti.channels, ti.tile_w, ti.tile_h, FRI_HIP_TILED_ALLOW_HOLES, &raw); rc != FRI_HIP_OK) return fail(dev.describe(rc));
+    TiledPlan plan(raw);
+    fri_hip_plan *tile = fri_hip_plan_tiled_tile(raw);
+    if (fri_hip_plan_num_cells(tile) != ti.n_cells) return fail("coefficient array does not match the tile geometry");
+    if (e = set_colour_transform(tile, ti.rct, dev, ti.ycbcr); !e.empty()) return fail(e);
+    std::array<int32_t, 32> qm = opts.quantization_matrix;
+    if (ti.quality && fri_hip_quality_matrix((int)ti.quality, qm.data()) != FRI_HIP_OK) return fail("invalid quality");
+    int rc = fri_hip_plan_set_dequantiser(tile, ti.quality ? FRI_HIP_DEQUANT_MIDPOINT : FRI_HIP_DEQUANT_REFERENCE);
+    r.value.metadata = ImageMetadata{ti.height, ti.width, ti.channels == 1 ? ColorSpace::Luma : ColorSpace::RGB};
+    r.value.data.resize((size_t)ti.width * ti.height * ti.channels);
+    if (rc == FRI_HIP_OK) rc = fri_hip_decode_image_tiled(raw, coefs.data(), qm.data(), r.value.data.data());
+    if (rc != FRI_HIP_OK) return fail(dev.describe(rc));
+    r.ok = true;
+    return r;
+}
+} // namespace
+
 Result<RasterImage> FRIDecoder::decode(const std::vector<uint8_t> &data, const EncoderOpts &opts) {
+    if (data.size() >= 4 && std::memcmp(data.data(), "frit", 4) == 0) return decode_tiled_bytes(data, opts);
     Result<RasterImage> r;
     auto c = stages::serialize::decode(data);
     if (!c.ok) {
@@ -988,6 +1031,99 @@ Result<RasterImage> FRIDecoder::decode(const WaveletImage &image, const EncoderO
     }
     r = stages::wavelet_transform::decode(image, opts, dev);
     if (!r.ok) r.error = "Failed to decode: " + r.error;
+    return r;
+}
+
+// ---- tiled coding ----------------------------------------------------------------------------------------------------------------------------------
+Result<EncodedTiled> encode_bytes_tiled(const std::vector<uint8_t> &pixels, uint32_t height, uint32_t width, ColorSpace colorspace, const EncoderOpts &opts, uint32_t tile_size,
+                                        unsigned threads) {
+    Result<EncodedTiled> r;
+    auto fail = [&](const std::string &why) {
+        r.error = "Failed to decode: " + why; // sic, encoder.rs:106
+        return r;
+    };
+    std::array<int32_t, 32> qm;
+    if (const std::string e = coding_matrix(opts, qm); !e.empty()) return fail(e);
+    if (opts.target_psnr > 0 || opts.target_ssim > 0 || opts.target_bytes) return fail("target_psnr, target_ssim and target_bytes are not supported with tiles: there are no searches over tiles (pass a quality)");
+    const uint32_t c = num_channels(colorspace);
+    if (!width || !height || pixels.size() != (size_t)width * height * c) return fail("raster size does not match its metadata");
+    uint32_t tw = 0, th = 0;
+    if (const int rc = fri_hip_tile_shape(width, height, tile_size, &tw, &th); rc != FRI_HIP_OK) return fail(std::string("no tile shape of that size owns every pixel: ") + fri_hip_strerror(rc));
+    Device dev(opts.device);
+    if (!dev.ok()) return fail(dev.error());
+    fri_hip_plan_tiled *raw = nullptr;
+    if (const int rc = fri_hip_plan_tiled_create(dev.ctx(), width, height, c, tw, th, 0, &raw); rc != FRI_HIP_OK) return fail(dev.describe(rc));
+    TiledPlan plan(raw);
+    fri_hip_plan *tile = fri_hip_plan_tiled_tile(raw);
+    const ImageMetadata md = coded_metadata(th, tw, colorspace, opts);
+    if (const std::string e = set_colour_transform(tile, md.rct, dev, md.ycbcr); !e.empty()) return fail(e);
+    if (const std::string e = set_plan_stream_order(tile, dev); !e.empty()) return fail(e);
+    uint32_t grid[4];
+    fri_hip_plan_tiled_grid(raw, grid);
+    const size_t planes = (size_t)grid[0] * grid[1] * c;
+    const uint64_t n = fri_hip_plan_num_some(tile);
+    std::vector<uint16_t> symbols(planes * (size_t)n);
+    std::vector<uint32_t> hist(planes * CONTEXT_AMOUNT * ALPHABET_SIZE);
+    std::vector<float> vp(planes * 18), wp(planes * 18);
+    std::vector<uint64_t> oob(planes, 0);
+    if (const int rc = fri_hip_encode_image_tiled_symbols(raw, pixels.data(), qm.data(), vp.data(), wp.data(), symbols.data(), hist.data(), oob.data()); rc != FRI_HIP_OK)
+        return fail(dev.describe(rc));
+    for (uint64_t v : oob)
+        if (v) return fail("symbol outside the 1024-entry alphabet"); // the reference panics: bump_freq, entropy_coding.rs:99
+    const std::string e = emit::encode_tiled_from_streams(width, height, tw, th, c, md.rct, md.quality, md.ycbcr, symbols.data(), (size_t)n, hist.data(), vp.data(), wp.data(), threads,
+                                                          r.value.bytes);
+    if (!e.empty()) return fail(e);
+    r.value.tile_w = tw, r.value.tile_h = th, r.value.nx = grid[0], r.value.ny = grid[1];
+    r.value.quality = (int)md.quality, r.value.rct = md.rct, r.value.ycbcr = md.ycbcr;
+    r.ok = true;
+    return r;
+}
+
+Result<RasterImage> round_trip_tiled(const std::vector<uint8_t> &pixels, uint32_t height, uint32_t width, uint32_t channels, uint32_t tile_w, uint32_t tile_h, int quality, bool rct,
+                                     bool ycbcr, int device) {
+    Result<RasterImage> r;
+    int32_t qm[32];
+    if (!width || !height || !tile_w || !tile_h || (channels != 1 && channels != 3) || pixels.size() != (size_t)width * height * channels || quality < 0 || quality > 99 ||
+        (rct && (ycbcr || quality)) || (ycbcr && !quality) || fri_hip_quality_matrix(quality ? quality : 100, qm) != FRI_HIP_OK) {
+        r.error = "invalid argument";
+        return r;
+    }
+    Device dev(device);
+    if (!dev.ok()) {
+        r.error = dev.error();
+        return r;
+    }
+    fri_hip_plan_tiled *raw = nullptr;
+    int rc = fri_hip_plan_tiled_create(dev.ctx(), width, height, channels, tile_w, tile_h, FRI_HIP_TILED_ALLOW_HOLES, &raw);
+    if (rc != FRI_HIP_OK) {
+        r.error = dev.describe(rc);
+        return r;
+    }
+    TiledPlan plan(raw);
+    fri_hip_plan *tile = fri_hip_plan_tiled_tile(raw);
+    if (!(r.error = set_colour_transform(tile, rct, dev, ycbcr)).empty()) return r;
+    uint32_t grid[4];
+    fri_hip_plan_tiled_grid(raw, grid);
+    const size_t image = fri_hip_plan_coef_count(tile), n_tiles = (size_t)grid[0] * grid[1];
+    std::vector<int32_t> coefs(n_tiles * image);
+    std::vector<uint8_t> one((size_t)tile_w * tile_h * channels);
+    for (size_t t = 0; t < n_tiles && rc == FRI_HIP_OK; t++) { // the format's split with edge replication on the host (include/fri_hip.h)
+        const size_t j = t / grid[0], i = t % grid[0];
+        for (uint32_t y = 0; y < tile_h; y++) {
+            const size_t sy = std::min<size_t>(j * tile_h + y, height - 1);
+            for (uint32_t x = 0; x < tile_w; x++) {
+                const size_t sx = std::min<size_t>(i * tile_w + x, width - 1);
+                for (uint32_t k = 0; k < channels; k++) one[((size_t)y * tile_w + x) * channels + k] = pixels[(sy * width + sx) * channels + k];
+            }
+        }
+        rc = fri_hip_transform_quant(tile, one.data(), qm, coefs.data() + t * image);
+    }
+    if (rc == FRI_HIP_OK) rc = fri_hip_plan_set_dequantiser(tile, quality ? FRI_HIP_DEQUANT_MIDPOINT : FRI_HIP_DEQUANT_REFERENCE);
+    r.value.metadata = ImageMetadata{height, width, channels == 1 ? ColorSpace::Luma : ColorSpace::RGB};
+    r.value.data.resize(pixels.size());
+    if (rc == FRI_HIP_OK) rc = fri_hip_decode_image_tiled(raw, coefs.data(), qm, r.value.data.data());
+    if (rc != FRI_HIP_OK) r.error = dev.describe(rc);
+    r.ok = rc == FRI_HIP_OK;
     return r;
 }
 

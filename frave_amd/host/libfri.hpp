@@ -115,6 +115,7 @@ class Device {
     Device(const Device &) = delete;
     Device &operator=(const Device &) = delete;
     bool ok() const { return ctx_ != nullptr; }
+    fri_hip_ctx *ctx() const { return ctx_; } // for plans the caller owns (fri_hip_plan_tiled)
     const std::string &error() const { return error_; }
     fri_hip_plan *plan(uint32_t width, uint32_t height, uint32_t channels, std::string &err);
     // Plans of this device measure their forward tiling when they are made (fri_hip_plan_tune_forward: tens of milliseconds and ~1 GB of scratch memory per
@@ -259,10 +260,28 @@ Result<EncodedRGBA> encode_bytes_rgba(const std::vector<uint8_t> &rgba, uint32_t
 // else the quality's matrix; rct / ycbcr: the colour transform) and on the alpha plane (ones), then fri_hip_decode_image_rgba - what such a file decodes to.
 Result<RasterImage> round_trip_rgba(const std::vector<uint8_t> &rgba, uint32_t height, uint32_t width, int quality, bool rct, bool ycbcr, bool clean_alpha, int device = 0);
 
+// Tiled coding (include/fri_hip.h, "tiled coding"; the `frit` container of include/fri_emit.h) of width x height Luma or RGB pixels: the image is cut into tiles of
+// about tile_size x tile_size (fri_hip_tile_shape), the device codes them as one batch (fri_hip_encode_image_tiled_symbols, the fit on), the emitter codes them on
+// `threads` workers (0: the hardware concurrency, capped at 16). The tiles are coded as opts says - lossless (plain or colour_transform) or lossy in RGB or YCbCr
+// at opts.quality. target_psnr, target_ssim and target_bytes are refused: there are no searches over tiles. FRIDecoder::decode reads such files.
+struct EncodedTiled {
+    std::vector<uint8_t> bytes;
+    uint32_t tile_w = 0, tile_h = 0, nx = 0, ny = 0;
+    int quality = 0; // 1..99; 0 for a lossless file
+    bool rct = false, ycbcr = false;
+};
+Result<EncodedTiled> encode_bytes_tiled(const std::vector<uint8_t> &pixels, uint32_t height, uint32_t width, ColorSpace colorspace, const EncoderOpts &opts, uint32_t tile_size,
+                                        unsigned threads = 0);
+// The direct tiled round trip without the entropy coder, for self-checks: the split restated on the host, the forward kernel on every tile through the inner plan
+// (quality 0: ones, else the quality's matrix; rct / ycbcr: the colour transform), then fri_hip_decode_image_tiled - what such a file decodes to.
+Result<RasterImage> round_trip_tiled(const std::vector<uint8_t> &pixels, uint32_t height, uint32_t width, uint32_t channels, uint32_t tile_w, uint32_t tile_h, int quality, bool rct,
+                                     bool ycbcr, int device = 0);
+
 class FRIDecoder { // decoder.rs:44-59
   public:
     // the whole pipeline of decoder.rs:16-40: EncodedImage -> EntropyDecoding -> Dequantization -> WaveletTransform -> RawImage.
-    // Container parsing and entropy decoding run on the host, dequantisation + inverse transform on the device.
+    // Container parsing and entropy decoding run on the host, dequantisation + inverse transform on the device. A tiled file (`frit`) is recognised by its magic:
+    // fri_tiled_decode's workers, then fri_hip_decode_image_tiled.
     Result<RasterImage> decode(const std::vector<uint8_t> &data, const EncoderOpts &opts = EncoderOpts());
     // from the WaveletTransform stage on
     Result<RasterImage> decode(const WaveletImage &image, const EncoderOpts &opts = EncoderOpts());

@@ -51,7 +51,28 @@
  * function writes for the same stream, histogram and parameters in a Luma file. Refused (-1): the flag in fri_emit_encode_image and fri_emit_check_image, with one
  * channel or with FRI_EMIT_420. fri_emit_decode_image reports the flag in info[2] (whose channel count stays 3) and returns four planes [4][F][512], the colour
  * planes then alpha (what fri_hip_decode_image_rgba takes); coef_cap < 4 x F x 512 returns -3 with `info` filled. An RGB or YCbCr file with bits 3 and 2 both
- * set is "Invalid metadata". Bit 3 of a Luma file is ignored, as all flag bits of Luma files are. */
+ * set is "Invalid metadata". Bit 3 of a Luma file is ignored, as all flag bits of Luma files are.
+ *
+ * Empty contexts: `channels` may also carry FRI_EMIT_EMPTY_OK, in fri_emit_encode_image_from_streams only (anywhere else -1). A context without symbols - all
+ * 1024 counts of its histogram are 0 - then gets the model AnsContext::finalize builds from max_freq_bits = 0 and no off-distribution values (the floor of 8 bits
+ * and the Laplace shape of the bucket) instead of the error "empty context"; no symbol ever looks that model up. The file needs no new bit and existing decoders
+ * read it: the context's two serialised fields are those of any context. Without the flag everything stays as it is, the error included; the file of an image
+ * that leaves no context empty is byte-identical with and without the flag. Small images and the tiles of a tiled image leave contexts empty often.
+ *
+ * Tiled images (the `frit` container, fri_tiled_* below): a layer above the image emitter. The image is cut into tiles (include/fri_hip.h, "tiled coding", has
+ * the grid, the split with edge replication and the merge) and every tile is coded as a complete, independent image. All fields little-endian:
+ *     offset  0  "frit"
+ *             4  u32 version = 1
+ *             8  u32 H          12  u32 W
+ *            16  u32 tile_h     20  u32 tile_w
+ *            24  u32 ny         28  u32 nx         ny = ceil(H / tile_h), nx = ceil(W / tile_w)
+ *            32  u64 offset[ny nx + 1]
+ * The payloads follow the table: tile t = j nx + i is the bytes [offset[t], offset[t + 1]). offset[0] = 32 + 8 (ny nx + 1), offset[ny nx] is the file length and
+ * the offsets are strictly increasing. A payload is a complete `frif` file of a tile_h x tile_w image: exactly what fri_emit_encode_image_from_streams writes
+ * for that tile's streams, histograms and parameters with FRI_EMIT_EMPTY_OK set. All tiles carry the same metadata word. 4:2:0 and alpha inside tiles are
+ * refused, by the encoder (-1) and by the decoder ("Malformed tiled image"). fri_emit_decode_image does not know the magic: a `frit` file is "Invalid signature"
+ * to it. Out of scope: region (tile-range) decode. */
+#define FRI_EMIT_EMPTY_OK 0x2000u
 #define FRI_EMIT_RCT 0x100u
 #define FRI_EMIT_YCBCR 0x400u
 #define FRI_EMIT_420 0x800u
@@ -117,6 +138,24 @@ int fri_emit_decode_image(const uint8_t *frv, size_t len, uint32_t info[4], int3
  * plain one-loop coder (the reference's order of operations, entropy_coding.rs:332-347) and once by the library's context-parallel
  * coder; 0 = the two streams are byte-identical, -4 = they differ, -1 = invalid argument. Host only. */
 int fri_emit_rans_selfcheck(uint64_t n_symbols, uint64_t seed, char *err, size_t err_cap);
+
+/* ---- the tile container `frit` (format above) ---- */
+/* The whole file from the arrays fri_hip_encode_image_tiled_symbols returns: streams [n_tiles][C][n_symbols] u16, hist [n_tiles][C][10][1024], value_params /
+ * width_params [n_tiles][C][3][6], n_tiles = ny nx; n_symbols must be the symbol count of the tile_w x tile_h lattice (-2 otherwise). `channels` is what
+ * fri_emit_encode_image_from_streams takes, without FRI_EMIT_420 and FRI_EMIT_ALPHA (-1); FRI_EMIT_EMPTY_OK is always in force. Tiles are coded on `threads`
+ * workers (0: the hardware concurrency, capped at 16); the tile geometry is built once and the bytes are the same for every thread count. An error of a tile
+ * reads "tile t: channel c: reason" (-2). Returns 0 and *len, or -3 with *len = needed size. */
+int fri_tiled_encode_from_streams(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t channels, const uint16_t *streams, uint64_t n_symbols,
+                                  const uint32_t *hist, const float *value_params, const float *width_params, uint32_t threads, uint8_t *out, size_t cap, size_t *len, char *err,
+                                  size_t err_cap);
+/* info = {W, H, tile_w, tile_h, nx, ny, the info[2] fri_emit_decode_image reports for tile 0, F = the cells of the tile lattice}. Checks the header, the table
+ * and every payload's 16-byte header, decodes nothing. -2 for a file that is not a well-formed `frit` file. */
+int fri_tiled_info(const uint8_t *frv, size_t len, uint32_t info[8]);
+/* A `frit` file back to the coefficient planes fri_hip_decode_image_tiled takes: coefs [n_tiles][C][F][512] int32, None = INT32_MIN. Checks the table, and each
+ * payload's height, width and metadata word against the header and tile 0: a mismatch - and any file that is not a `frit` file, a `frif` file among them -
+ * returns "Malformed tiled image" (-2). Tiles are decoded on `threads` workers (0 as above) that share one geometry and one symbol order. Returns -3 with `info`
+ * filled when coefs is NULL or coef_cap (in elements) is too small. */
+int fri_tiled_decode(const uint8_t *frv, size_t len, uint32_t threads, uint32_t info[8], int32_t *coefs, size_t coef_cap, char *err, size_t err_cap);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

@@ -574,6 +574,59 @@ int fri_hip_encode_image_rgba_symbols(fri_hip_plan_rgba *p, const uint8_t *pixel
  * set on it - that setting is restored afterwards; then the merge. Synchronous. */
 int fri_hip_decode_image_rgba(fri_hip_plan_rgba *p, const int32_t *coefs, const int32_t qmatrix[32], uint8_t *pixels);
 
+/* ---- tiled coding: an image as a batch of independently coded tiles ------------------------------- */
+/* The image is cut into tiles that are coded as complete, independent images: the device codes them as one batch, the emitter and the decoder work on them on
+ * threads (include/fri_emit.h, fri_tiled_*), and one small plan serves an image of any size. Part of the file format (the `frit` container, include/fri_emit.h).
+ * The image is W x H x C interleaved bytes, [H][W][C], C = 1 or 3; the tile is tile_w x tile_h.
+ *   grid         nx = ceil(W / tile_w), ny = ceil(H / tile_h); tile t = j nx + i is column i of row j of the grid.
+ *   tile raster  [ny nx][tile_h][tile_w][C], contiguous, without a row pitch.
+ *   split        edge replication: tile(t, y, x, c) = image(min(j tile_h + y, H - 1), min(i tile_w + x, W - 1), c).
+ *   merge        copies back the pixels with j tile_h + y < H and i tile_w + x < W; every image pixel is written exactly once.
+ * Every tile is an ordinary image of tile_w x tile_h, coded by an ordinary plan of that shape - the inner plan - with whatever colour transform, quality matrix
+ * and dequantiser are set on it.
+ * The lattice does not own every pixel of every shape: a tile_w x tile_h image may have corner pixels that are a leaf of no retained cell (140 x 140: 14 of them,
+ * 64 x 64: 8), and such a pixel decodes to 0. Inside a tiled image these would be defects in the middle of the picture, so a tile shape is checked, not assumed.
+ * fri_hip_plan_owned_pixels: the plan's count of pixels that are a leaf of a retained cell (W x H when the lattice owns them all); works on host-only plans.
+ * fri_hip_tile_shape (host only): a tile shape of about target x target for a W x H image. tile_w0 = ceil(W / max(1, round(W / target))), round = half up, and
+ * tile_h0 alike from H; the shapes (tile_w0 + a, tile_h0 + b) are walked for s = a + b = 0, 1, 2, ... with a ascending from 0 to s; the first whose C = 1 lattice
+ * owns every pixel is returned. The search stops after s = 64: FRI_HIP_ERR_OUT_OF_RANGE. FRI_HIP_ERR_INVALID_ARGUMENT for a zero size or target.
+ * fri_hip_plan_tiled_create: refuses (FRI_HIP_ERR_INVALID_ARGUMENT) zero sizes, C other than 1 or 3, unknown flag bits, nx ny C > 65535 (one batch launch takes
+ * all tiles) and - without FRI_HIP_TILED_ALLOW_HOLES in `flags` - a tile shape whose lattice (of the inner plan, C channels) does not own all tile_w tile_h
+ * pixels. ctx may be NULL: the plan is then host-only (the getters work, compute returns FRI_HIP_ERR_NO_DEVICE). fri_hip_plan_tiled_tile gives the inner plan
+ * (owned by p) for the getters, fri_hip_plan_set_colour_transform, fri_hip_plan_set_dequantiser and fri_hip_plan_set_stream_order, which the encodes need and
+ * create does not do. fri_hip_plan_tiled_grid: out[4] = {nx, ny, tile_w, tile_h}. The plan owns the tile staging buffers: calls on one fri_hip_plan_tiled must
+ * be ordered on one stream, as for fri_hip_plan_rgba.
+ * Out of scope: the quality searches and the size estimate over tiles (fri_hip_estimate_size* keeps reporting UINT64_MAX for a histogram with a context
+ * without symbols, which tiles make frequent and FRI_EMIT_EMPTY_OK codes), 4:2:0 and alpha in tiles, region (tile-range) decode, multi-GPU forms. */
+#define FRI_HIP_TILED_ALLOW_HOLES 1u
+typedef struct fri_hip_plan_tiled fri_hip_plan_tiled;
+uint64_t fri_hip_plan_owned_pixels(const fri_hip_plan *plan);
+int fri_hip_tile_shape(uint32_t width, uint32_t height, uint32_t target, uint32_t *tile_w, uint32_t *tile_h);
+int fri_hip_plan_tiled_create(fri_hip_ctx *ctx, uint32_t width, uint32_t height, uint32_t channels, uint32_t tile_w, uint32_t tile_h, uint32_t flags,
+                              fri_hip_plan_tiled **out);
+int fri_hip_plan_tiled_destroy(fri_hip_plan_tiled *p);
+fri_hip_plan *fri_hip_plan_tiled_tile(fri_hip_plan_tiled *p);
+int fri_hip_plan_tiled_grid(const fri_hip_plan_tiled *p, uint32_t out[4]);
+/* The raster kernels (K10, k10_tiles.hip), any pointer alignment; they only enqueue on `stream` and can be captured into a graph. d_raster [H][W][C]; d_tiles
+ * [ny nx][tile_h][tile_w][C]. */
+int fri_hip_split_tiles_dev(fri_hip_plan_tiled *p, const uint8_t *d_raster, uint8_t *d_tiles, void *stream);
+int fri_hip_merge_tiles_dev(fri_hip_plan_tiled *p, const uint8_t *d_tiles, uint8_t *d_raster, void *stream);
+/* The device part of a tiled encode, everything in device memory and on `stream`, nothing but enqueues: the split into the plan's buffer, then one
+ * fri_hip_encode_symbols_batch_dev in its direct form (d_coefs = NULL, d_node_words = NULL) on the inner plan with n_images = nx ny. The inner plan needs its
+ * stream order; whatever the inner call refuses (a capturing stream among it) is refused. fit = 0 reads every plane's parameters from d_params. Outputs, tile
+ * after tile: d_symbols u16 [n_tiles][C][num_some], d_params [n_tiles][C][2][3][6], d_hist [n_tiles][C][10][1024], d_n_out_of_alphabet [n_tiles][C],
+ * d_fit_out_of_range [n_tiles][C] (may be NULL as in the inner call); num_some is the inner plan's. */
+int fri_hip_encode_symbols_tiled_dev(fri_hip_plan_tiled *p, const uint8_t *d_raster, const int32_t qmatrix[32], int fit, float *d_params, uint16_t *d_symbols, uint32_t *d_hist,
+                                     uint64_t *d_n_out_of_alphabet, uint64_t *d_fit_out_of_range, void *stream);
+/* The host form: the pixels are staged, the call above runs with the fit on, everything is read back - what fri_tiled_encode_from_streams (include/fri_emit.h)
+ * takes. value_params / width_params [n_tiles][C][3][6], each tile's laid out as fri_hip_encode_image_symbols lays them out; symbols [n_tiles][C][num_some]; hist
+ * [n_tiles][C][10][1024]; n_out_of_alphabet [n_tiles][C]. Synchronous. FRI_HIP_ERR_OUT_OF_RANGE as in fri_hip_encode_image. */
+int fri_hip_encode_image_tiled_symbols(fri_hip_plan_tiled *p, const uint8_t *pixels, const int32_t qmatrix[32], float *value_params, float *width_params, uint16_t *symbols,
+                                       uint32_t *hist, uint64_t *n_out_of_alphabet);
+/* The device part of a tiled decode: coefs [n_tiles][C][F][512] int32 (what fri_tiled_decode returns; F = the inner plan's cells) -> pixels [H][W][C].
+ * fri_hip_inverse_transform_batch_dev on the inner plan with `qmatrix` and the colour transform and dequantiser set on that plan, then the merge. Synchronous. */
+int fri_hip_decode_image_tiled(fri_hip_plan_tiled *p, const int32_t *coefs, const int32_t qmatrix[32], uint8_t *pixels);
+
 /* ---- timing helper ---------------------------------------------------------------------------- */
 /* Runs the forward kernel `iters` times on `stream` bracketed by HIP events recorded on that same
  * stream and returns the mean kernel-to-kernel time per launch in microseconds (bench.py uses it
