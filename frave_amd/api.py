@@ -40,6 +40,8 @@ SYMBOLS = [
     "fri_hip_encode_symbols_rgba_dev", "fri_hip_encode_image_rgba_symbols", "fri_hip_decode_image_rgba",
     "fri_hip_plan_owned_pixels", "fri_hip_tile_shape", "fri_hip_plan_tiled_create", "fri_hip_plan_tiled_destroy", "fri_hip_plan_tiled_tile", "fri_hip_plan_tiled_grid",
     "fri_hip_split_tiles_dev", "fri_hip_merge_tiles_dev", "fri_hip_encode_symbols_tiled_dev", "fri_hip_encode_image_tiled_symbols", "fri_hip_decode_image_tiled",
+    "fri_hip_measure_distortion_tiled_dev", "fri_hip_estimate_size_tiled_dev", "fri_hip_estimate_size_tiled", "fri_hip_search_quality_tiled", "fri_hip_search_quality_tiled_dev",
+    "fri_hip_search_quality_ssim_tiled", "fri_hip_search_quality_ssim_tiled_dev", "fri_hip_search_quality_for_size_tiled", "fri_hip_search_quality_for_size_tiled_dev",
 ]
 TILED_ALLOW_HOLES = 1  # FRI_HIP_TILED_ALLOW_HOLES: `flags` of fri_hip_plan_tiled_create - accept a tile shape whose lattice does not own every pixel
 ALPHA_KEEP, ALPHA_CLEAN = 0, 1  # `clean` of fri_hip_split_rgba_dev and the RGBA encodes: CLEAN zeroes the colour of pixels with A == 0
@@ -218,6 +220,15 @@ def load_library():
     L.fri_hip_encode_symbols_tiled_dev.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
     L.fri_hip_encode_image_tiled_symbols.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
     L.fri_hip_decode_image_tiled.argtypes = [vp, vp, vp, vp]
+    L.fri_hip_measure_distortion_tiled_dev.argtypes = [vp, vp, vp, vp, vp]
+    L.fri_hip_estimate_size_tiled_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.fri_hip_estimate_size_tiled.argtypes = [vp, vp, vp, vp, vp]
+    L.fri_hip_search_quality_tiled.argtypes = [vp, vp, C.c_double, vp, vp]
+    L.fri_hip_search_quality_tiled_dev.argtypes = [vp, vp, C.c_double, vp, vp, vp]
+    L.fri_hip_search_quality_ssim_tiled.argtypes = [vp, vp, C.c_double, vp, vp]
+    L.fri_hip_search_quality_ssim_tiled_dev.argtypes = [vp, vp, C.c_double, vp, vp, vp]
+    L.fri_hip_search_quality_for_size_tiled.argtypes = [vp, vp, C.c_uint64, vp, vp]
+    L.fri_hip_search_quality_for_size_tiled_dev.argtypes = [vp, vp, C.c_uint64, vp, vp, vp]
     _lib = L
     return L
 
@@ -1080,3 +1091,50 @@ class PlanTiled:
         out = np.empty(self.pixel_bytes, np.uint8)
         _check(load_library().fri_hip_decode_image_tiled(self._h, _p(co), _p(_q(qmatrix)), _p(out)), "fri_hip_decode_image_tiled", self.ctx)
         return out
+
+    # ---- the measure, the size estimate and the searches over tiles ----------------------------------
+    def measure_distortion_tiled_dev(self, d_tiles, d_reference_raster, d_out, stream=0):
+        """fri_hip_measure_distortion_tiled_dev: the tile raster's in-image pixels against a raster [H][W][C]; d_out (uint64 [2 C + 1], device) = per channel c the
+        sum of squared differences at 2 c and the largest absolute difference at 2 c + 1, the pixels counted (W H) at 2 C. Only enqueues."""
+        _check(load_library().fri_hip_measure_distortion_tiled_dev(self._h, d_tiles, d_reference_raster, d_out, stream), "fri_hip_measure_distortion_tiled_dev", self.ctx)
+
+    def estimate_size_tiled_dev(self, d_hist, d_oob, d_file_bytes, d_tile_bytes, d_models=None, stream=0):
+        """fri_hip_estimate_size_tiled_dev: d_hist uint32 [n_tiles][C][10][1024], d_oob uint64 [n_tiles][C] or None -> d_file_bytes uint64 [1], d_tile_bytes uint64
+        [n_tiles] and, if given, d_models uint32 [n_tiles][C][10][4]; device pointers. Only enqueues."""
+        _check(load_library().fri_hip_estimate_size_tiled_dev(self._h, d_hist, d_oob or None, d_file_bytes, d_tile_bytes, d_models or None, stream),
+               "fri_hip_estimate_size_tiled_dev", self.ctx)
+
+    def estimate_size_tiled(self, hist, oob=None):
+        """fri_hip_estimate_size_tiled: hist [n_tiles][C][10][1024] (oob [n_tiles][C] or None), host arrays -> (file bytes, tile bytes uint64 [n_tiles]): the
+        estimated size of the `frit` file and of its payloads (include/fri_hip.h gives the formula); UINT64_MAX where the emitter would refuse a tile."""
+        h = np.ascontiguousarray(hist, np.uint32)
+        assert h.size == self.n_tiles * self.channels * 10 * 1024
+        o = None if oob is None else np.ascontiguousarray(oob, np.uint64)
+        assert o is None or o.size == self.n_tiles * self.channels
+        total, tiles = C.c_uint64(0), np.zeros(self.n_tiles, np.uint64)
+        _check(load_library().fri_hip_estimate_size_tiled(self._h, _p(h), None if o is None else _p(o), C.byref(total), _p(tiles)), "fri_hip_estimate_size_tiled", self.ctx)
+        return total.value, tiles
+
+    def _search(self, name, pixels, target, ctype, stream):
+        qual, v = C.c_int32(0), ctype(0)
+        L = load_library()
+        if isinstance(pixels, int):
+            _check(getattr(L, name + "_dev")(self._h, pixels, target, C.byref(qual), C.byref(v), stream), name + "_dev", self.ctx)
+        else:
+            px = np.ascontiguousarray(pixels, np.uint8)
+            assert px.size == self.pixel_bytes
+            _check(getattr(L, name)(self._h, _p(px), target, C.byref(qual), C.byref(v)), name, self.ctx)
+        return qual.value, v.value
+
+    def search_quality(self, pixels, target_db, stream=0):
+        """fri_hip_search_quality_tiled[_dev] (pixels: a host array or a device pointer): (quality, PSNR in dB of the tiled round trip); 100 = code losslessly."""
+        return self._search("fri_hip_search_quality_tiled", pixels, float(target_db), C.c_double, stream)
+
+    def search_quality_ssim(self, pixels, target, stream=0):
+        """fri_hip_search_quality_ssim_tiled[_dev]: (quality, SSIM of the tiled round trip); 100 = code losslessly."""
+        return self._search("fri_hip_search_quality_ssim_tiled", pixels, float(target), C.c_double, stream)
+
+    def search_quality_for_size(self, pixels, max_bytes, stream=0):
+        """fri_hip_search_quality_for_size_tiled[_dev]: (quality, estimated bytes of the `frit` file); FriHipError with code -7 when nothing fits. Needs
+        set_stream_order()."""
+        return self._search("fri_hip_search_quality_for_size_tiled", pixels, int(max_bytes), C.c_uint64, stream)

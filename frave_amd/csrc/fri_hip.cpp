@@ -2690,6 +2690,11 @@ struct fri_hip_plan_tiled {
     Grown<uint32_t> hist;             // ... [n_tiles][C][10][1024]
     Grown<unsigned long long> counts; // ... [n_tiles][C] out of alphabet, then [n_tiles][C] the fit's out-of-range counts
     Grown<float> params;              // ... [n_tiles][C][2][3][6]
+    Grown<uint8_t> recon;             // the searches: a probe's reconstructed tiles, the tile raster's layout (zeroed once per call: a pixel no cell owns stays 0)
+    Grown<uint8_t> recon_raster;      // fri_hip_search_quality_ssim_tiled*: a probe's merged raster
+    Grown<unsigned long long> measure; // a probe's sums: distortion [2 C + 1], SSIM [C + 1] or the file's bytes [1]
+    Grown<unsigned long long> rate;   // the size estimate: the tiles' payload bytes [n_tiles]
+    Grown<unsigned long long> oob_in; // fri_hip_estimate_size_tiled: the host's out-of-alphabet counts [n_tiles][C]
     size_t n_tiles() const { return (size_t)nx * ny; }
     size_t raster_bytes() const { return (size_t)width * height * channels; }
     size_t tile_bytes() const { return (size_t)tile_w * tile_h * channels; }
@@ -2701,6 +2706,46 @@ int need_device_tiled(const fri_hip_plan_tiled *p) {
     if (!p) return FRI_HIP_ERR_INVALID_ARGUMENT;
     return p->ctx ? FRI_HIP_OK : FRI_HIP_ERR_NO_DEVICE;
 }
+
+// the host forms' pixels into p->raster
+int stage_pixels_tiled(fri_hip_plan_tiled *p, const uint8_t *pixels) {
+    HIP_TRY(p->ctx, hipSetDevice(p->ctx->device));
+    if (int rc = grow(p->ctx, p->raster, p->raster_bytes())) return rc;
+    HIP_TRY(p->ctx, hipMemcpy(p->raster, pixels, p->raster_bytes(), hipMemcpyHostToDevice));
+    return FRI_HIP_OK;
+}
+
+// What the PSNR and SSIM searches share: the image split once into p->tiles, and a probe that runs K1 over all tiles into p->coefs and K3 - the inner plan's
+// inverse tiling with the midpoint dequantiser, whatever the caller has set on that plan - into p->recon, zeroed once before the first probe.
+struct TiledProbe {
+    fri_hip_plan_tiled *p;
+    hipStream_t s;
+    DevicePlan inv;
+    size_t image; // coefficients of one tile
+    int begin(const uint8_t *d_pixels) {
+        fri_hip_ctx *c = p->ctx;
+        const size_t n = p->n_tiles();
+        image = fri_hip_plan_coef_count(p->tile.get());
+        int rc;
+        if ((rc = grow(c, p->tiles, n * p->tile_bytes())) || (rc = grow(c, p->recon, n * p->tile_bytes())) || (rc = grow(c, p->coefs, n * image))) return rc;
+        inv = p->tile->dev_inv;
+        inv.k3_multiply = false;
+        inv.k3_midpoint = true;
+        HIP_TRY(c, launch_split_tiles(d_pixels, p->width, p->height, p->channels, p->tile_w, p->tile_h, p->tiles, s));
+        HIP_TRY(c, hipMemsetAsync(p->recon, 0, n * p->tile_bytes(), s));
+        return FRI_HIP_OK;
+    }
+    int round_trip(int quality) {
+        int32_t qm[32];
+        QMatrix q;
+        fri_hip_quality_matrix(quality, qm);
+        check_q(qm, q);
+        const uint32_t n = (uint32_t)p->n_tiles();
+        HIP_TRY(p->ctx, launch_fwd_transform_quant(p->tile->dev, n, p->tiles, p->tile_bytes(), p->coefs, image, q, s));
+        HIP_TRY(p->ctx, launch_inverse_transform(inv, n, p->coefs, image, q, p->recon, p->tile_bytes(), s));
+        return FRI_HIP_OK;
+    }
+};
 
 } // namespace
 
@@ -2836,6 +2881,178 @@ int fri_hip_decode_image_tiled(fri_hip_plan_tiled *p, const int32_t *coefs, cons
     HIP_TRY(c, launch_merge_tiles(p->tiles, p->width, p->height, p->channels, p->tile_w, p->tile_h, p->raster, nullptr));
     HIP_TRY(c, hipMemcpy(pixels, p->raster, p->raster_bytes(), hipMemcpyDeviceToHost));
     return FRI_HIP_OK;
+}
+
+/* ---- the measure, the size estimate and the searches over tiles ---- */
+int fri_hip_measure_distortion_tiled_dev(fri_hip_plan_tiled *p, const uint8_t *d_tiles, const uint8_t *d_reference_raster, uint64_t *d_out, void *stream) {
+    if (!p || !d_tiles || !d_reference_raster || !d_out) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    if (int rc = need_device_tiled(p)) return rc;
+    auto *out = reinterpret_cast<unsigned long long *>(d_out);
+    HIP_TRY(p->ctx, launch_clear_sums(out, 2 * p->channels + 1, (hipStream_t)stream));
+    HIP_TRY(p->ctx, launch_measure_tiles(d_tiles, p->width, p->height, p->channels, p->tile_w, p->tile_h, d_reference_raster, out, (hipStream_t)stream));
+    return FRI_HIP_OK;
+}
+
+int fri_hip_estimate_size_tiled_dev(fri_hip_plan_tiled *p, const uint32_t *d_hist, const uint64_t *d_n_out_of_alphabet, uint64_t *d_file_bytes, uint64_t *d_tile_bytes,
+                                    uint32_t *d_models, void *stream) {
+    if (!p || !d_hist || !d_file_bytes || !d_tile_bytes) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    if (int rc = need_device_tiled(p)) return rc;
+    HIP_TRY(p->ctx, hipSetDevice(p->ctx->device));
+    HIP_TRY(p->ctx, launch_rate_estimate_tiled((uint32_t)p->n_tiles(), p->channels, d_hist, reinterpret_cast<const unsigned long long *>(d_n_out_of_alphabet), p->tile->laplace,
+                                               reinterpret_cast<unsigned long long *>(d_tile_bytes), reinterpret_cast<unsigned long long *>(d_file_bytes), d_models, kRateLayout,
+                                               (hipStream_t)stream));
+    return FRI_HIP_OK;
+}
+
+int fri_hip_estimate_size_tiled(fri_hip_plan_tiled *p, const uint32_t *hist, const uint64_t *n_out_of_alphabet, uint64_t *file_bytes, uint64_t *tile_bytes) {
+    if (!p || !hist || !file_bytes) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    if (int rc = need_device_tiled(p)) return rc;
+    fri_hip_ctx *c = p->ctx;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t n = p->n_tiles(), planes = n * p->channels;
+    int rc;
+    if ((rc = grow(c, p->hist, planes * 10 * 1024)) || (rc = grow(c, p->oob_in, planes)) || (rc = grow(c, p->rate, n)) || (rc = grow(c, p->measure, 2 * (size_t)p->channels + 1)))
+        return rc;
+    HIP_TRY(c, hipMemcpy(p->hist, hist, planes * 10 * 1024 * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (n_out_of_alphabet) HIP_TRY(c, hipMemcpy(p->oob_in, n_out_of_alphabet, planes * sizeof(uint64_t), hipMemcpyHostToDevice));
+    if ((rc = fri_hip_estimate_size_tiled_dev(p, p->hist, n_out_of_alphabet ? (const uint64_t *)p->oob_in.get() : nullptr, (uint64_t *)p->measure.get(), (uint64_t *)p->rate.get(),
+                                              nullptr, nullptr)))
+        return rc;
+    HIP_TRY(c, hipMemcpy(file_bytes, p->measure, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (tile_bytes) HIP_TRY(c, hipMemcpy(tile_bytes, p->rate, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return FRI_HIP_OK;
+}
+
+int fri_hip_search_quality_tiled_dev(fri_hip_plan_tiled *p, const uint8_t *d_pixels, double target_db, int32_t *quality, double *psnr_db, void *stream) {
+    if (!p || !d_pixels || !quality || !psnr_db || !(target_db > 0) || p->tile->dev.rct) return FRI_HIP_ERR_INVALID_ARGUMENT; // (!(x > 0): NaN too)
+    if (int rc = need_device_tiled(p)) return rc;
+    const hipStream_t s = (hipStream_t)stream;
+    if (int rc = refuse_capture(p->tile.get(), s, "fri_hip_search_quality_tiled_dev reads every probe back: it cannot be captured into a HIP graph")) return rc;
+    fri_hip_ctx *c = p->ctx;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const uint32_t C = p->channels;
+    TiledProbe probe{p, s, {}, 0};
+    int rc;
+    if ((rc = grow(c, p->measure, 2 * (size_t)C + 1)) || (rc = probe.begin(d_pixels))) return rc;
+    int lo = 0, hi = 100; // lo: a failure (0 is never probed), hi: a success (100 = lossless is never probed)
+    double hi_db = HUGE_VAL;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) / 2;
+        if ((rc = probe.round_trip(mid))) return rc;
+        HIP_TRY(c, launch_clear_sums(p->measure, 2 * C + 1, s));
+        HIP_TRY(c, launch_measure_tiles(p->recon, p->width, p->height, C, p->tile_w, p->tile_h, d_pixels, p->measure, s));
+        unsigned long long m[7];
+        HIP_TRY(c, hipMemcpyAsync(m, p->measure, (2 * (size_t)C + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        const double db = distortion_psnr(m, C);
+        if (db >= target_db) hi = mid, hi_db = db;
+        else lo = mid;
+    }
+    *quality = hi;
+    *psnr_db = hi_db;
+    return FRI_HIP_OK;
+}
+
+int fri_hip_search_quality_tiled(fri_hip_plan_tiled *p, const uint8_t *pixels, double target_db, int32_t *quality, double *psnr_db) {
+    if (!p || !pixels || !quality || !psnr_db || !(target_db > 0) || p->tile->dev.rct) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    if (int rc = need_device_tiled(p)) return rc;
+    if (int rc = stage_pixels_tiled(p, pixels)) return rc;
+    return fri_hip_search_quality_tiled_dev(p, p->raster, target_db, quality, psnr_db, nullptr);
+}
+
+// The SSIM window grid of the whole image, as ssim_shape gives it for a plan's shape
+static int ssim_shape_tiled(const fri_hip_plan_tiled *p) {
+    if (p->width < 8 || p->height < 8) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    return (uint64_t)(p->width / 4 - 1) * (p->height / 4 - 1) > (1ull << 29) ? FRI_HIP_ERR_INVALID_ARGUMENT : FRI_HIP_OK;
+}
+
+int fri_hip_search_quality_ssim_tiled_dev(fri_hip_plan_tiled *p, const uint8_t *d_pixels, double target, int32_t *quality, double *ssim, void *stream) {
+    if (!p || !d_pixels || !quality || !ssim || !(target > 0 && target <= 1) || p->tile->dev.rct) return FRI_HIP_ERR_INVALID_ARGUMENT; // (NaN fails both)
+    if (int rc = ssim_shape_tiled(p)) return rc;
+    if (int rc = need_device_tiled(p)) return rc;
+    const hipStream_t s = (hipStream_t)stream;
+    if (int rc = refuse_capture(p->tile.get(), s, "fri_hip_search_quality_ssim_tiled_dev reads every probe back: it cannot be captured into a HIP graph")) return rc;
+    fri_hip_ctx *c = p->ctx;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const uint32_t C = p->channels;
+    TiledProbe probe{p, s, {}, 0};
+    int rc;
+    if ((rc = grow(c, p->measure, 2 * (size_t)C + 1)) || (rc = grow(c, p->recon_raster, p->raster_bytes())) || (rc = probe.begin(d_pixels))) return rc;
+    int lo = 0, hi = 100; // lo: a failure (0 is never probed), hi: a success (100 = lossless is never probed)
+    double hi_ssim = 1.0;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) / 2;
+        if ((rc = probe.round_trip(mid))) return rc;
+        HIP_TRY(c, launch_merge_tiles(p->recon, p->width, p->height, C, p->tile_w, p->tile_h, p->recon_raster, s));
+        HIP_TRY(c, hipMemsetAsync(p->measure, 0, ((size_t)C + 1) * sizeof(uint64_t), s));
+        HIP_TRY(c, launch_ssim(1, d_pixels, p->recon_raster, 0, p->width, p->height, C, p->measure, s));
+        unsigned long long m[4];
+        HIP_TRY(c, hipMemcpyAsync(m, p->measure, ((size_t)C + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        const double v = ssim_of(m, C);
+        if (v >= target) hi = mid, hi_ssim = v;
+        else lo = mid;
+    }
+    *quality = hi;
+    *ssim = hi_ssim;
+    return FRI_HIP_OK;
+}
+
+int fri_hip_search_quality_ssim_tiled(fri_hip_plan_tiled *p, const uint8_t *pixels, double target, int32_t *quality, double *ssim) {
+    if (!p || !pixels || !quality || !ssim || !(target > 0 && target <= 1) || p->tile->dev.rct) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    if (int rc = ssim_shape_tiled(p)) return rc;
+    if (int rc = need_device_tiled(p)) return rc;
+    if (int rc = stage_pixels_tiled(p, pixels)) return rc;
+    return fri_hip_search_quality_ssim_tiled_dev(p, p->raster, target, quality, ssim, nullptr);
+}
+
+int fri_hip_search_quality_for_size_tiled_dev(fri_hip_plan_tiled *p, const uint8_t *d_pixels, uint64_t max_bytes, int32_t *quality, uint64_t *est_bytes, void *stream) {
+    if (!p || !d_pixels || !quality || !est_bytes || max_bytes == 0 || p->tile->dev.rct) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    if (int rc = need_device_tiled(p)) return rc;
+    if (!p->tile->d_stream_order) return FRI_HIP_ERR_INVALID_ARGUMENT; // (the probes run the encode's chain, which needs it)
+    const hipStream_t s = (hipStream_t)stream;
+    if (int rc = refuse_capture(p->tile.get(), s, "fri_hip_search_quality_for_size_tiled_dev reads every probe back: it cannot be captured into a HIP graph")) return rc;
+    fri_hip_ctx *c = p->ctx;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t n = p->n_tiles(), planes = n * p->channels, n_some = p->tile->geo.n_some;
+    int rc;
+    if ((rc = grow(c, p->tiles, n * p->tile_bytes())) || (rc = grow(c, p->symbols, std::max<size_t>(planes * n_some, 1))) || (rc = grow(c, p->hist, planes * 10 * 1024)) ||
+        (rc = grow(c, p->counts, 2 * planes)) || (rc = grow(c, p->params, planes * 36)) || (rc = grow(c, p->rate, n)) || (rc = grow(c, p->measure, 2 * (size_t)p->channels + 1)))
+        return rc;
+    HIP_TRY(c, launch_split_tiles(d_pixels, p->width, p->height, p->channels, p->tile_w, p->tile_h, p->tiles, s));
+    uint64_t *oob = reinterpret_cast<uint64_t *>(p->counts.get());
+    // a probe: the chain of fri_hip_encode_image_tiled_symbols at quality q on the tiles cut above (K1, the device-side fit, K2 over all tiles; the same histograms),
+    // then the tiled estimate
+    auto probe = [&](int q, uint64_t &est) -> int {
+        int32_t qm[32];
+        fri_hip_quality_matrix(q, qm);
+        if (int r = fri_hip_encode_symbols_batch_dev(p->tile.get(), (uint32_t)n, p->tiles, p->tile_bytes(), qm, 1, p->params, nullptr, 0, nullptr, 0, p->symbols,
+                                                     (size_t)p->channels * n_some, p->hist, oob, nullptr, stream))
+            return r;
+        if (int r = fri_hip_estimate_size_tiled_dev(p, p->hist, oob, (uint64_t *)p->measure.get(), (uint64_t *)p->rate.get(), nullptr, stream)) return r;
+        HIP_TRY(c, hipMemcpyAsync(&est, p->measure, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        return FRI_HIP_OK;
+    };
+    // lo: fits (0 is never probed), hi: does not fit (never probed): 101, or 100 on a YCbCr inner plan, whose quality 100 is not lossless and has no file
+    int lo = 0, hi = p->tile->dev.ycc ? 100 : 101;
+    uint64_t lo_est = 0, last = UINT64_MAX;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) / 2;
+        if ((rc = probe(mid, last))) return rc;
+        if (last != UINT64_MAX && last <= max_bytes) lo = mid, lo_est = last;
+        else hi = mid;
+    }
+    *quality = lo;
+    *est_bytes = lo ? lo_est : last; // nothing fits: the last probe was quality 1
+    return lo ? FRI_HIP_OK : FRI_HIP_ERR_OUT_OF_RANGE;
+}
+
+int fri_hip_search_quality_for_size_tiled(fri_hip_plan_tiled *p, const uint8_t *pixels, uint64_t max_bytes, int32_t *quality, uint64_t *est_bytes) {
+    if (!p || !pixels || !quality || !est_bytes || max_bytes == 0 || p->tile->dev.rct) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    if (int rc = need_device_tiled(p)) return rc;
+    if (int rc = stage_pixels_tiled(p, pixels)) return rc;
+    return fri_hip_search_quality_for_size_tiled_dev(p, p->raster, max_bytes, quality, est_bytes, nullptr);
 }
 
 } // extern "C"

@@ -2,12 +2,14 @@
 //
 // split_tiles_kernel<C>: the image [H][W][C] -> the tile raster [ny nx][tile_h][tile_w][C], tile t = j nx + i, with edge replication:
 // tile(t, y, x, c) = image(min(j tile_h + y, H - 1), min(i tile_w + x, W - 1), c). merge_tiles_kernel<C>: the tile raster -> the image, the pixels with
-// j tile_h + y < H and i tile_w + x < W.
+// j tile_h + y < H and i tile_w + x < W. measure_tiles_kernel<C>: the merge's pixels compared with a reference raster instead of stored (the tiled searches' PSNR).
 //
 // Neither raster has a row pitch. The tile raster is a flat run of ny nx tile_h rows of tile_w C bytes, and a lane owns one strip of 16 consecutive bytes of one
 // such row. Away from the clamped edge those are 16 consecutive bytes of one image row: one 16-byte load and one 16-byte store, the target's unaligned global
 // accesses (the compiler is told the alignment is 1), so both buffers start at any byte. A strip that reaches past the image row (the replicated edge) and a
 // row's last, partial strip go byte by byte. Every byte offset is 64-bit: W H C can pass 2^32.
+#include <algorithm>
+
 #include "device_common.hpp"
 
 namespace fri {
@@ -96,6 +98,104 @@ __global__ void __launch_bounds__(kTileThreads) merge_tiles_kernel(const TileArg
     }
 }
 
+// measure_tiles_kernel<C>: the merge's walk with nothing stored. A lane loads a strip of the tile raster and the same bytes of a reference raster [H][W][C] and
+// adds up, per channel, the squared differences and the largest absolute difference, and the pixels it saw: every in-image pixel once, no replicated one. The
+// channel of a byte is its index in the tile row mod C, and 16 mod 3 = 1: the phase moves from strip to strip. The lane therefore sums byte k of a strip into
+// slot k mod C - constant indices, registers - and turns the slots into channels after each strip. Reduced as merge420_kernel<true> does (k8_chroma420.hip):
+// 32-bit sums per lane, a wave reduction, LDS, one 64-bit atomic per sum and workgroup. Those atomics all go to the same 2 C + 1 words and take some 8 ns each
+// there, one after the other: with one strip per lane a 4096^2 plane's 4096 workgroups spent 100 us on them, 13 times what the merge takes. A lane therefore
+// walks up to kMeasureStrips strips, a whole grid apart (so a wave's loads stay 1 KiB runs): 32 x 16 x 255^2 < 2^25 per lane and < 2^31 per wave in 32 bits,
+// the waves added in 64. Integers: a run is the same sums every time.
+constexpr uint32_t kMeasureStrips = 32, kMeasureGroups = 512; // strips per lane at most; the grid up to which a lane keeps to one strip
+struct MeasureTileArgs {
+    TileArgs g;              // in: the tile raster; out is not used
+    const uint8_t *ref;      // the reference raster, only read
+    unsigned long long *out; // [2 C + 1], zeroed by the caller
+    uint32_t per_lane;       // strips per lane: the lane of workgroup b walks strips ((k gridDim.x + b) 256 + thread), k < per_lane
+};
+
+__device__ __forceinline__ int byte_of(const u32x4 &v, int k) {
+    const uint32_t w = (k >> 2) == 0 ? v.x : (k >> 2) == 1 ? v.y : (k >> 2) == 2 ? v.z : v.w;
+    return (int)((w >> ((k & 3) * 8)) & 0xFFu);
+}
+
+template <uint32_t C>
+__global__ void __launch_bounds__(kTileThreads) measure_tiles_kernel(const MeasureTileArgs a) {
+    const TileArgs &p = a.g;
+    const uint32_t image_row_bytes = p.width * C;
+    uint32_t part[2 * C + 1]; // by channel: sum of squares at 2 c, largest difference at 2 c + 1; the pixels at 2 C
+#pragma unroll
+    for (uint32_t i = 0; i < 2 * C + 1; i++) part[i] = 0;
+    for (uint32_t it = 0; it < a.per_lane; it++) {
+        const uint64_t g64 = ((uint64_t)it * gridDim.x + blockIdx.x) * kTileThreads + threadIdx.x;
+        if (g64 >= p.n_strips) break;
+        const Strip st = strip_of(p, (uint32_t)g64, C);
+        if (st.gy >= p.height) continue; // a replicated row counts nothing
+        uint32_t sse[C], worst[C], seen[C]; // by slot: byte k of the strip goes to slot k mod C
+#pragma unroll
+        for (uint32_t c = 0; c < C; c++) sse[c] = worst[c] = seen[c] = 0;
+        const uint8_t *src = p.in + st.tile_off;
+        const uint8_t *ref_row = a.ref + (uint64_t)st.gy * image_row_bytes;
+        const uint32_t at0 = st.x0_bytes + st.b0;
+        if (st.n == kTileStrip && at0 + kTileStrip <= image_row_bytes) {
+            const u32x4 tv = load_unaligned<u32x4>(src), rv = load_unaligned<u32x4>(ref_row + at0);
+#pragma unroll
+            for (int k = 0; k < (int)kTileStrip; k++) {
+                const int d = byte_of(tv, k) - byte_of(rv, k);
+                const uint32_t e = (uint32_t)(d < 0 ? -d : d);
+                sse[k % C] += e * e;
+                worst[k % C] = max(worst[k % C], e);
+                seen[k % C] += 1;
+            }
+        } else { // the strip reaches past the image row, or is the row's last
+#pragma unroll
+            for (uint32_t k = 0; k < kTileStrip; k++) {
+                if (k < st.n && at0 + k < image_row_bytes) {
+                    const int d = (int)src[k] - (int)ref_row[at0 + k];
+                    const uint32_t e = (uint32_t)(d < 0 ? -d : d);
+                    sse[k % C] += e * e;
+                    worst[k % C] = max(worst[k % C], e);
+                    seen[k % C] += 1;
+                }
+            }
+        }
+        // slot j holds channel (phase + j) mod C, phase = the channel of the strip's first byte: channel c is slot (c - phase) mod C
+        const uint32_t phase = st.b0 % C;
+        auto of_channel = [&](const uint32_t(&v)[C], uint32_t c) {
+            if constexpr (C == 1) return v[0];
+            else return phase == 0 ? v[c] : phase == 1 ? v[(c + 2) % 3] : v[(c + 1) % 3];
+        };
+#pragma unroll
+        for (uint32_t c = 0; c < C; c++) part[2 * c] += of_channel(sse, c), part[2 * c + 1] = max(part[2 * c + 1], of_channel(worst, c));
+        part[2 * C] += of_channel(seen, 0); // the bytes of channel 0: one per pixel
+    }
+    __shared__ uint32_t s_part[kTileThreads / 64][2 * C + 1];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+        for (uint32_t i = 0; i < 2 * C + 1; i++) {
+            const uint32_t other = (uint32_t)__shfl_xor((int)part[i], o);
+            part[i] = (i < 2 * C && (i & 1)) ? max(part[i], other) : part[i] + other;
+        }
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (uint32_t i = 0; i < 2 * C + 1; i++) s_part[wave][i] = part[i];
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 * C + 1) {
+        const bool is_max = threadIdx.x < 2 * C && (threadIdx.x & 1);
+        unsigned long long v = 0;
+#pragma unroll
+        for (int w = 0; w < kTileThreads / 64; w++) v = is_max ? max(v, (unsigned long long)s_part[w][threadIdx.x]) : v + s_part[w][threadIdx.x];
+        if (v) {
+            if (is_max) atomicMax(a.out + threadIdx.x, v);
+            else atomicAdd(a.out + threadIdx.x, v);
+        }
+    }
+}
+
 // The tile raster's strips as a 1-D grid of kTileThreads-thread workgroups, one strip per lane; false for a shape that does not fit one
 bool grid_of(uint32_t width, uint32_t height, uint32_t channels, uint32_t tile_w, uint32_t tile_h, TileArgs &p, uint32_t &groups) {
     if (!width || !height || !tile_w || !tile_h || (channels != 1 && channels != 3)) return false;
@@ -130,6 +230,20 @@ hipError_t launch_merge_tiles(const uint8_t *tiles, uint32_t width, uint32_t hei
     p.in = tiles, p.out = image;
     if (channels == 3) hipLaunchKernelGGL(merge_tiles_kernel<3>, dim3(groups), dim3(kTileThreads), 0, stream, p);
     else hipLaunchKernelGGL(merge_tiles_kernel<1>, dim3(groups), dim3(kTileThreads), 0, stream, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_measure_tiles(const uint8_t *tiles, uint32_t width, uint32_t height, uint32_t channels, uint32_t tile_w, uint32_t tile_h, const uint8_t *reference,
+                                unsigned long long *sums, hipStream_t stream) {
+    MeasureTileArgs a{};
+    uint32_t groups = 0;
+    if (!reference || !tiles || !sums || !grid_of(width, height, channels, tile_w, tile_h, a.g, groups)) return hipErrorInvalidValue;
+    a.g.in = tiles, a.ref = reference, a.out = sums;
+    // one strip per lane up to kMeasureGroups workgroups, then more strips per lane, and past kMeasureStrips of them more workgroups again
+    a.per_lane = std::min(kMeasureStrips, (groups + kMeasureGroups - 1) / kMeasureGroups);
+    groups = (groups + a.per_lane - 1) / a.per_lane;
+    if (channels == 3) hipLaunchKernelGGL(measure_tiles_kernel<3>, dim3(groups), dim3(kTileThreads), 0, stream, a);
+    else hipLaunchKernelGGL(measure_tiles_kernel<1>, dim3(groups), dim3(kTileThreads), 0, stream, a);
     return hipGetLastError();
 }
 

@@ -97,6 +97,10 @@ __device__ uint32_t block_exclusive_scan_u32(const uint32_t (&v)[kRatePer], uint
 }
 
 // grid (10, n_planes): workgroup (b, plane) rebuilds context b of plane `plane`. Thread t owns symbols 4t .. 4t + 3.
+// EMPTY_OK: the emitter's FRI_EMIT_EMPTY_OK, which codes the tiles of a `frit` file - a context whose counts sum to zero takes max_freq_bits = 0 before the floor,
+// its model is rebuilt like any other (models[0] is the max_freq_bits the file carries), it costs its container bytes and 16 bits (the flush of a rANS state that
+// never moved is 8 bytes, the channel's constant counts 6 per state) and its status 1 no longer marks the image uncodable. <false> is the kernel as it always was.
+template <bool EMPTY_OK>
 __global__ void __launch_bounds__(kRateThreads) rate_kernel(const RateArgs a) {
     const uint32_t b = blockIdx.x, plane = blockIdx.y, image = plane / a.channels, ch = plane % a.channels;
     const int t = threadIdx.x, lane = t & 63;
@@ -116,7 +120,9 @@ __global__ void __launch_bounds__(kRateThreads) rate_kernel(const RateArgs a) {
     uint32_t local = 0;
 #pragma unroll
     for (int k = 0; k < kRatePer; k++) local += count[k];
-    uint32_t mfb = log2_floor_or_64(block_sum_u32(local, s_u32));
+    const uint32_t count_sum = block_sum_u32(local, s_u32);
+    const bool empty = EMPTY_OK && count_sum == 0;
+    uint32_t mfb = empty ? 0u : log2_floor_or_64(count_sum);
     if (mfb < 8) mfb = 8;
     const uint32_t target = 1u << (mfb & 31u); // shl1_release
     const float scale = (float)(int32_t)target; // exact: a power of two (or -2^31, whose products all saturate to 0 as in the emitter)
@@ -226,7 +232,7 @@ __global__ void __launch_bounds__(kRateThreads) rate_kernel(const RateArgs a) {
     if (t != 0) return;
     if (a.models) {
         uint32_t *m = a.models + ((size_t)plane * 10 + b) * 4;
-        m[0] = mfb_final, m[1] = n_off, m[2] = n_collapsed, m[3] = status;
+        m[0] = mfb_final, m[1] = n_off, m[2] = n_collapsed, m[3] = empty && !status ? 1u : status;
     }
     const bool oob = a.oob && b == 0 && a.oob[plane] != 0;
     if (status || oob) {
@@ -235,7 +241,7 @@ __global__ void __launch_bounds__(kRateThreads) rate_kernel(const RateArgs a) {
     }
     // (a negative cost needs a used last slot, whose wrapped frequency exceeds 2^max_freq_bits: no real histogram gets there; counted as 0)
     unsigned long long add = (unsigned long long)(cost > 0 ? cost : 0);
-    add += (unsigned long long)(a.context_bits + 16u * n_off) << kRateFrac;
+    add += (unsigned long long)(a.context_bits + 16u * n_off + (empty ? 16u : 0u)) << kRateFrac;
     if (b == 0) add += (unsigned long long)a.channel_bits << kRateFrac;
     if (b == 0 && ch == 0) add += (unsigned long long)a.header_bits << kRateFrac;
     atomicAdd(a.total + image, add);
@@ -249,6 +255,27 @@ __global__ void __launch_bounds__(64) rate_bytes_kernel(unsigned long long *tota
     total[i] = (v & kRateUncodable) ? ~0ull : (v + (8ull << kRateFrac) - 1) >> (kRateFrac + 3);
 }
 
+// The size of a tiled file from its tiles' payload bytes: 32 + 8 (n_tiles + 1) + their sum, UINT64_MAX if any tile is uncodable. One workgroup, integer adds.
+__global__ void __launch_bounds__(kRateThreads) rate_file_kernel(const unsigned long long *tile_bytes, uint32_t n_tiles, unsigned long long *file_bytes) {
+    __shared__ unsigned long long s_sum[kRateWaves];
+    __shared__ uint32_t s_bad[kRateWaves];
+    unsigned long long sum = 0;
+    uint32_t bad = 0;
+    for (uint32_t i = threadIdx.x; i < n_tiles; i += kRateThreads) {
+        const unsigned long long v = tile_bytes[i];
+        if (v == ~0ull) bad = 1;
+        else sum += v;
+    }
+    sum = (unsigned long long)wave_sum_i64((long long)sum);
+    bad = wave_sum_u32(bad);
+    if ((threadIdx.x & 63) == 0) s_sum[threadIdx.x >> 6] = sum, s_bad[threadIdx.x >> 6] = bad;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    sum = 0, bad = 0;
+    for (int w = 0; w < kRateWaves; w++) sum += s_sum[w], bad += s_bad[w];
+    *file_bytes = bad ? ~0ull : 32ull + 8ull * ((unsigned long long)n_tiles + 1) + sum;
+}
+
 } // namespace
 
 hipError_t launch_rate_estimate(uint32_t n_images, uint32_t channels, const uint32_t *hist, const unsigned long long *oob, const float *laplace,
@@ -257,8 +284,20 @@ hipError_t launch_rate_estimate(uint32_t n_images, uint32_t channels, const uint
     RateArgs a;
     a.hist = hist, a.oob = oob, a.laplace = laplace, a.total = bytes, a.models = models, a.channels = channels;
     a.header_bits = 8u * layout.header_bytes, a.channel_bits = 8u * layout.channel_bytes, a.context_bits = 8u * layout.context_bytes;
-    hipLaunchKernelGGL(rate_kernel, dim3(10, n_images * channels), dim3(kRateThreads), 0, stream, a);
+    hipLaunchKernelGGL(rate_kernel<false>, dim3(10, n_images * channels), dim3(kRateThreads), 0, stream, a);
     hipLaunchKernelGGL(rate_bytes_kernel, dim3((n_images + 63) / 64), dim3(64), 0, stream, bytes, n_images);
+    return hipGetLastError();
+}
+
+hipError_t launch_rate_estimate_tiled(uint32_t n_tiles, uint32_t channels, const uint32_t *hist, const unsigned long long *oob, const float *laplace,
+                                      unsigned long long *tile_bytes, unsigned long long *file_bytes, uint32_t *models, const RateLayout &layout, hipStream_t stream) {
+    if (hipError_t e = hipMemsetAsync(tile_bytes, 0, (size_t)n_tiles * sizeof(unsigned long long), stream)) return e;
+    RateArgs a;
+    a.hist = hist, a.oob = oob, a.laplace = laplace, a.total = tile_bytes, a.models = models, a.channels = channels;
+    a.header_bits = 8u * layout.header_bytes, a.channel_bits = 8u * layout.channel_bytes, a.context_bits = 8u * layout.context_bytes;
+    hipLaunchKernelGGL(rate_kernel<true>, dim3(10, n_tiles * channels), dim3(kRateThreads), 0, stream, a);
+    hipLaunchKernelGGL(rate_bytes_kernel, dim3((n_tiles + 63) / 64), dim3(64), 0, stream, tile_bytes, n_tiles);
+    hipLaunchKernelGGL(rate_file_kernel, dim3(1), dim3(kRateThreads), 0, stream, tile_bytes, n_tiles, file_bytes);
     return hipGetLastError();
 }
 

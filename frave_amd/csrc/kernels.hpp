@@ -156,6 +156,11 @@ struct RateLayout {
 };
 hipError_t launch_rate_estimate(uint32_t n_images, uint32_t channels, const uint32_t *hist, const unsigned long long *oob, const float *laplace,
                                 unsigned long long *bytes, uint32_t *models, const RateLayout &layout, hipStream_t stream);
+// The same for the tiles of a `frit` file, which the emitter codes with FRI_EMIT_EMPTY_OK (rate_kernel<true>: a context without symbols costs its container bytes
+// + 2 and no longer makes the tile uncodable; models reports status 1 for it all the same): tile_bytes [n_tiles] = the payloads, each rounded up on its own,
+// file_bytes [1] = 32 + 8 (n_tiles + 1) + their sum, UINT64_MAX if a tile is uncodable.
+hipError_t launch_rate_estimate_tiled(uint32_t n_tiles, uint32_t channels, const uint32_t *hist, const unsigned long long *oob, const float *laplace,
+                                      unsigned long long *tile_bytes, unsigned long long *file_bytes, uint32_t *models, const RateLayout &layout, hipStream_t stream);
 
 // K7 (k7_ssim.hip): the SSIM sums of n_images raster pairs of width x height x channels (interleaved u8; image k at a / b + k * pixel_stride bytes):
 // out[k][c] += the sum of the window values of channel c, out[k][channels] += the number of windows (include/fri_hip.h, fri_hip_measure_ssim_dev).
@@ -181,6 +186,10 @@ hipError_t launch_merge_rgba(const uint8_t *rgb, const uint8_t *a, uint32_t widt
 // [ny nx][tile_h][tile_w][C] with edge replication. Merge: the tile raster's in-image pixels back. C is 1 or 3; any shape, any pointer alignment.
 hipError_t launch_split_tiles(const uint8_t *image, uint32_t width, uint32_t height, uint32_t channels, uint32_t tile_w, uint32_t tile_h, uint8_t *tiles, hipStream_t stream);
 hipError_t launch_merge_tiles(const uint8_t *tiles, uint32_t width, uint32_t height, uint32_t channels, uint32_t tile_w, uint32_t tile_h, uint8_t *image, hipStream_t stream);
+// Measure: the merge's walk with nothing stored - the tile raster's in-image pixels against `reference` [H][W][C]: sums[2 c] += the sum of squared differences of
+// channel c, sums[2 c + 1] = max(.., largest absolute difference), sums[2 C] += pixels (W H in all). The caller zeroes sums with launch_clear_sums.
+hipError_t launch_measure_tiles(const uint8_t *tiles, uint32_t width, uint32_t height, uint32_t channels, uint32_t tile_w, uint32_t tile_h, const uint8_t *reference,
+                                unsigned long long *sums, hipStream_t stream);
 
 // K2's per-node neighbour offsets (LDS halfword offsets relative to the own slot, two per word) from the static neighbour table
 void build_lf_deltas(const uint16_t *nbr_table, int8_t *out /* [8] */);

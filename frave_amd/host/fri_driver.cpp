@@ -20,8 +20,8 @@
 //                                                            say (--rct, --quality, --psnr, --ssim, --ycbcr; no --size / --bpp / --420), the alpha plane
 //                                                            losslessly beside it; --clean-alpha: the colour of pixels with A = 0 is coded as 0
 //                                                            --tile-size T (any mode flag but --420; no alpha): the image as a batch of independently coded tiles
-//                                                            of about T x T (fri_hip_tile_shape), a `frit` file; --psnr / --ssim / --size search on the whole image
-//                                                            and code the tiles with that quality (a file over a --size budget: one quality lower until it fits)
+//                                                            of about T x T (fri_hip_tile_shape), a `frit` file; --psnr / --ssim / --size search on the tiled plan
+//                                                            (fri_hip_search_quality*_tiled): the target holds for the file that is written
 //   fri_driver decode-file <in.frv> <out.pgm|.ppm|.bmp|.pam>  (.pam for a file with an alpha plane, and for no other) container -> rANS / context decoding on the host -> dequantisation + inverse
 //                                                            transform on the device (fri-cli decode, crates/fri-cli/src/commands/decode.rs); a flagged file
 //                                                            comes back as RGB, a lossy file with its quality's matrix and the midpoint dequantiser
@@ -468,31 +468,24 @@ static int encode_image_rgba_to_file(const std::vector<uint8_t> &img, uint32_t w
 
 // encode-file --tile-size T: the image as a batch of independently coded tiles (libfri::encode_bytes_tiled; a `frit` file). Self-check: the file decodes
 // (FRIDecoder) to the direct tiled round trip of what it holds (libfri::round_trip_tiled: host split, forward kernel per tile, fri_hip_decode_image_tiled) - for a
-// lossless file that is the input. --psnr / --ssim / --size: there are no searches over tiles, so the quality is the one the whole-image search finds
-// (resolve_quality_targets) and the tiles are coded with it; a tiled file over a --size budget is coded one quality lower until it fits.
+// lossless file that is the input. --psnr / --ssim / --size: the searches over tiles (libfri::encode_bytes_tiled with a target), measured on the tiled round trip
+// and estimated for the tiled file.
 static int encode_image_tiled_to_file(const std::vector<uint8_t> &img, uint32_t w, uint32_t h, uint32_t c, libfri::EncoderOpts opts, uint32_t tile_size, const char *out_path) {
-    const uint64_t budget = opts.target_bytes;
-    if (opts.target_psnr > 0 || opts.target_ssim > 0 || budget) {
-        if (resolve_quality_targets(img, w, h, c, opts)) return 1;
-        std::printf("(the quality of the whole image's search; the tiles are coded with it)\n");
-    }
     auto t0 = std::chrono::steady_clock::now();
     auto enc = libfri::encode_bytes_tiled(img, h, w, c == 1 ? libfri::ColorSpace::Luma : libfri::ColorSpace::RGB, opts, tile_size);
-    while (budget && enc.ok && enc.value.bytes.size() > budget) { // tiles cost a few per cent: one quality lower while the file is over
-        const int q = enc.value.quality ? enc.value.quality - 1 : 99;
-        if (q < 1) {
-            std::fprintf(stderr, "quality 1 is %zu bytes in tiles, over the budget of %llu\n", enc.value.bytes.size(), (unsigned long long)budget);
-            return 1;
-        }
-        opts.quality = q;
-        enc = libfri::encode_bytes_tiled(img, h, w, c == 1 ? libfri::ColorSpace::Luma : libfri::ColorSpace::RGB, opts, tile_size);
-    }
     const double t_enc = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (!enc.ok) {
         std::fprintf(stderr, "%s\n", enc.error.c_str());
         return 1;
     }
     const std::vector<uint8_t> &bytes = enc.value.bytes;
+    if (opts.target_psnr > 0) std::printf("target %.2f dB: quality %d (%.2f dB over the tiles)\n", opts.target_psnr, enc.value.search_quality, enc.value.psnr_db);
+    if (opts.target_ssim > 0) std::printf("target SSIM %.4f: quality %d (SSIM %.6f over the tiles)\n", opts.target_ssim, enc.value.search_quality, enc.value.ssim);
+    if (opts.target_bytes) {
+        if (enc.value.est_bytes) std::printf("target %llu bytes: quality %d (estimated %llu bytes, file %zu)\n", (unsigned long long)opts.target_bytes, enc.value.search_quality, (unsigned long long)enc.value.est_bytes, bytes.size());
+        else std::printf("target %llu bytes: quality %d by the estimate, coded at %d (file %zu bytes)\n", (unsigned long long)opts.target_bytes, enc.value.search_quality, enc.value.quality, bytes.size());
+    }
+    if (enc.value.lossless_rct) std::printf("no YCbCr quality reaches the target: a lossless RCT file\n");
     auto back = libfri::FRIDecoder().decode(bytes, opts);
     std::vector<uint8_t> expected = img;
     if (enc.value.quality && back.ok) {

@@ -1044,7 +1044,6 @@ Result<EncodedTiled> encode_bytes_tiled(const std::vector<uint8_t> &pixels, uint
     };
     std::array<int32_t, 32> qm;
     if (const std::string e = coding_matrix(opts, qm); !e.empty()) return fail(e);
-    if (opts.target_psnr > 0 || opts.target_ssim > 0 || opts.target_bytes) return fail("target_psnr, target_ssim and target_bytes are not supported with tiles: there are no searches over tiles (pass a quality)");
     const uint32_t c = num_channels(colorspace);
     if (!width || !height || pixels.size() != (size_t)width * height * c) return fail("raster size does not match its metadata");
     uint32_t tw = 0, th = 0;
@@ -1055,26 +1054,73 @@ Result<EncodedTiled> encode_bytes_tiled(const std::vector<uint8_t> &pixels, uint
     if (const int rc = fri_hip_plan_tiled_create(dev.ctx(), width, height, c, tw, th, 0, &raw); rc != FRI_HIP_OK) return fail(dev.describe(rc));
     TiledPlan plan(raw);
     fri_hip_plan *tile = fri_hip_plan_tiled_tile(raw);
-    const ImageMetadata md = coded_metadata(th, tw, colorspace, opts);
-    if (const std::string e = set_colour_transform(tile, md.rct, dev, md.ycbcr); !e.empty()) return fail(e);
     if (const std::string e = set_plan_stream_order(tile, dev); !e.empty()) return fail(e);
     uint32_t grid[4];
     fri_hip_plan_tiled_grid(raw, grid);
+    r.value.tile_w = tw, r.value.tile_h = th, r.value.nx = grid[0], r.value.ny = grid[1];
     const size_t planes = (size_t)grid[0] * grid[1] * c;
     const uint64_t n = fri_hip_plan_num_some(tile);
     std::vector<uint16_t> symbols(planes * (size_t)n);
     std::vector<uint32_t> hist(planes * CONTEXT_AMOUNT * ALPHABET_SIZE);
     std::vector<float> vp(planes * 18), wp(planes * 18);
     std::vector<uint64_t> oob(planes, 0);
-    if (const int rc = fri_hip_encode_image_tiled_symbols(raw, pixels.data(), qm.data(), vp.data(), wp.data(), symbols.data(), hist.data(), oob.data()); rc != FRI_HIP_OK)
-        return fail(dev.describe(rc));
-    for (uint64_t v : oob)
-        if (v) return fail("symbol outside the 1024-entry alphabet"); // the reference panics: bump_freq, entropy_coding.rs:99
-    const std::string e = emit::encode_tiled_from_streams(width, height, tw, th, c, md.rct, md.quality, md.ycbcr, symbols.data(), (size_t)n, hist.data(), vp.data(), wp.data(), threads,
-                                                          r.value.bytes);
-    if (!e.empty()) return fail(e);
-    r.value.tile_w = tw, r.value.tile_h = th, r.value.nx = grid[0], r.value.ny = grid[1];
-    r.value.quality = (int)md.quality, r.value.rct = md.rct, r.value.ycbcr = md.ycbcr;
+    // the device batch and the emitter for what `coded` says (a quality or lossless, no targets): "" or the error; the file in r.value.bytes
+    auto code = [&](const EncoderOpts &coded) -> std::string {
+        if (const std::string e = coding_matrix(coded, qm); !e.empty()) return e;
+        const ImageMetadata md = coded_metadata(th, tw, colorspace, coded);
+        if (const std::string e = set_colour_transform(tile, md.rct, dev, md.ycbcr); !e.empty()) return e;
+        if (const int rc = fri_hip_encode_image_tiled_symbols(raw, pixels.data(), qm.data(), vp.data(), wp.data(), symbols.data(), hist.data(), oob.data()); rc != FRI_HIP_OK)
+            return dev.describe(rc);
+        for (uint64_t v : oob)
+            if (v) return "symbol outside the 1024-entry alphabet"; // the reference panics: bump_freq, entropy_coding.rs:99
+        r.value.bytes.clear();
+        const std::string e = emit::encode_tiled_from_streams(width, height, tw, th, c, md.rct, md.quality, md.ycbcr, symbols.data(), (size_t)n, hist.data(), vp.data(), wp.data(), threads,
+                                                              r.value.bytes);
+        if (!e.empty()) return e;
+        r.value.quality = (int)md.quality, r.value.rct = md.rct, r.value.ycbcr = md.ycbcr;
+        return std::string();
+    };
+    EncoderOpts coded = opts;
+    coded.target_psnr = 0, coded.target_ssim = 0, coded.target_bytes = 0;
+    const bool ycc = opts.ycbcr && colorspace == ColorSpace::RGB;
+    if (opts.target_psnr > 0 || opts.target_ssim > 0 || opts.target_bytes) {
+        // the searches run on the tiled plan and probe the planes the file will hold: what they return holds for the file that is written
+        if (const std::string e = set_colour_transform(tile, false, dev, ycc); !e.empty()) return fail(e);
+    }
+    if (opts.target_bytes) { // the highest quality whose estimated file fits; 100 = lossless
+        int32_t q = 0;
+        uint64_t est = 0;
+        const int rc = fri_hip_search_quality_for_size_tiled(raw, pixels.data(), opts.target_bytes, &q, &est);
+        if (rc == FRI_HIP_ERR_OUT_OF_RANGE) return fail("no quality fits in " + std::to_string(opts.target_bytes) + " bytes (quality 1: about " + std::to_string(est) + ")");
+        if (rc != FRI_HIP_OK) return fail(dev.describe(rc));
+        r.value.search_quality = q;
+        // the estimate is a few bytes per channel and tile off the coder's output: code at q, emit, and go one quality lower while the file is over
+        constexpr int kMaxSteps = 8;
+        for (int step = 0; step <= kMaxSteps && q >= 1; step++, q--) {
+            coded.quality = q < 100 ? q : 0;
+            if (const std::string e = code(coded); !e.empty()) return fail(e);
+            if (r.value.bytes.size() <= opts.target_bytes) {
+                r.value.est_bytes = est;
+                r.ok = true;
+                return r;
+            }
+            est = 0; // (est_bytes is the estimate of the searched quality: a stepped-down result reports 0)
+        }
+        r.value.bytes.clear();
+        return fail("no file of at most " + std::to_string(opts.target_bytes) + " bytes within " + std::to_string(kMaxSteps) + " qualities below the estimate's");
+    }
+    if (opts.target_psnr > 0 || opts.target_ssim > 0) { // the lowest quality that reaches the target; 100 = lossless
+        int32_t q = 100;
+        int rc;
+        if (opts.target_psnr > 0) rc = fri_hip_search_quality_tiled(raw, pixels.data(), opts.target_psnr, &q, &r.value.psnr_db);
+        else rc = fri_hip_search_quality_ssim_tiled(raw, pixels.data(), opts.target_ssim, &q, &r.value.ssim);
+        if (rc != FRI_HIP_OK) return fail(dev.describe(rc));
+        r.value.search_quality = q;
+        coded.quality = q < 100 ? q : 0;
+        if (q == 100 && ycc) // YCbCr does not reach the target at any quality: a lossless file, with the RCT
+            coded.ycbcr = false, coded.colour_transform = true, r.value.lossless_rct = true;
+    }
+    if (const std::string e = code(coded); !e.empty()) return fail(e);
     r.ok = true;
     return r;
 }

@@ -263,12 +263,20 @@ Result<RasterImage> round_trip_rgba(const std::vector<uint8_t> &rgba, uint32_t h
 // Tiled coding (include/fri_hip.h, "tiled coding"; the `frit` container of include/fri_emit.h) of width x height Luma or RGB pixels: the image is cut into tiles of
 // about tile_size x tile_size (fri_hip_tile_shape), the device codes them as one batch (fri_hip_encode_image_tiled_symbols, the fit on), the emitter codes them on
 // `threads` workers (0: the hardware concurrency, capped at 16). The tiles are coded as opts says - lossless (plain or colour_transform) or lossy in RGB or YCbCr
-// at opts.quality. target_psnr, target_ssim and target_bytes are refused: there are no searches over tiles. FRIDecoder::decode reads such files.
+// at opts.quality, or at the quality one of the targets finds. target_psnr / target_ssim: fri_hip_search_quality_tiled / fri_hip_search_quality_ssim_tiled on the
+// tiled plan - the lowest quality at which the tiled round trip reaches the target; 100 codes a lossless file (a YCbCr request then becomes the RCT). target_bytes:
+// fri_hip_search_quality_for_size_tiled, then code, emit and step one quality down while the file is over the budget, at most 8 steps, as FRIEncoder::encode does.
+// FRIDecoder::decode reads such files.
 struct EncodedTiled {
     std::vector<uint8_t> bytes;
     uint32_t tile_w = 0, tile_h = 0, nx = 0, ny = 0;
     int quality = 0; // 1..99; 0 for a lossless file
     bool rct = false, ycbcr = false;
+    int search_quality = 0;    // what a target's search returned (1..100), 0 without a target
+    double psnr_db = 0;        // target_psnr: the PSNR the search measured at that quality (+inf for 100)
+    double ssim = 0;           // target_ssim: the SSIM likewise (1 for 100)
+    uint64_t est_bytes = 0;    // target_bytes: the estimate of the searched quality; 0 when the file was coded at a lower one
+    bool lossless_rct = false; // no YCbCr quality reached the target: a lossless RCT file
 };
 Result<EncodedTiled> encode_bytes_tiled(const std::vector<uint8_t> &pixels, uint32_t height, uint32_t width, ColorSpace colorspace, const EncoderOpts &opts, uint32_t tile_size,
                                         unsigned threads = 0);

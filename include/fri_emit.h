@@ -71,7 +71,8 @@
  * the offsets are strictly increasing. A payload is a complete `frif` file of a tile_h x tile_w image: exactly what fri_emit_encode_image_from_streams writes
  * for that tile's streams, histograms and parameters with FRI_EMIT_EMPTY_OK set. All tiles carry the same metadata word. 4:2:0 and alpha inside tiles are
  * refused, by the encoder (-1) and by the decoder ("Malformed tiled image"). fri_emit_decode_image does not know the magic: a `frit` file is "Invalid signature"
- * to it. Out of scope: region (tile-range) decode. */
+ * to it. The size of such a file is estimated from the tiles' histograms, without the coder, by fri_hip_estimate_size_tiled_dev (include/fri_hip.h), which knows
+ * the rule of FRI_EMIT_EMPTY_OK. Out of scope: region (tile-range) decode. */
 #define FRI_EMIT_EMPTY_OK 0x2000u
 #define FRI_EMIT_RCT 0x100u
 #define FRI_EMIT_YCBCR 0x400u

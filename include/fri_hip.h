@@ -596,8 +596,8 @@ int fri_hip_decode_image_rgba(fri_hip_plan_rgba *p, const int32_t *coefs, const 
  * (owned by p) for the getters, fri_hip_plan_set_colour_transform, fri_hip_plan_set_dequantiser and fri_hip_plan_set_stream_order, which the encodes need and
  * create does not do. fri_hip_plan_tiled_grid: out[4] = {nx, ny, tile_w, tile_h}. The plan owns the tile staging buffers: calls on one fri_hip_plan_tiled must
  * be ordered on one stream, as for fri_hip_plan_rgba.
- * Out of scope: the quality searches and the size estimate over tiles (fri_hip_estimate_size* keeps reporting UINT64_MAX for a histogram with a context
- * without symbols, which tiles make frequent and FRI_EMIT_EMPTY_OK codes), 4:2:0 and alpha in tiles, region (tile-range) decode, multi-GPU forms. */
+ * Out of scope: per-tile qualities (all tiles of a file carry one metadata word: one quality per file, which is what the searches below return), 4:2:0 and alpha
+ * in tiles, region (tile-range) decode, multi-GPU forms. */
 #define FRI_HIP_TILED_ALLOW_HOLES 1u
 typedef struct fri_hip_plan_tiled fri_hip_plan_tiled;
 uint64_t fri_hip_plan_owned_pixels(const fri_hip_plan *plan);
@@ -626,6 +626,50 @@ int fri_hip_encode_image_tiled_symbols(fri_hip_plan_tiled *p, const uint8_t *pix
 /* The device part of a tiled decode: coefs [n_tiles][C][F][512] int32 (what fri_tiled_decode returns; F = the inner plan's cells) -> pixels [H][W][C].
  * fri_hip_inverse_transform_batch_dev on the inner plan with `qmatrix` and the colour transform and dequantiser set on that plan, then the merge. Synchronous. */
 int fri_hip_decode_image_tiled(fri_hip_plan_tiled *p, const int32_t *coefs, const int32_t qmatrix[32], uint8_t *pixels);
+/* The distortion of a tile raster against a raster (K10's measuring kernel): the merge's walk with nothing stored. d_tiles [ny nx][tile_h][tile_w][C] is compared
+ * with the same bytes of d_reference_raster [H][W][C]; replicated rows and columns are skipped, so every image pixel is counted once and no replicated one.
+ * d_out uint64 [2 C + 1], the layout of fri_hip_measure_distortion_dev: d_out[2 c] = the sum of (tile - reference)^2 of channel c, d_out[2 c + 1] = the largest
+ * |tile - reference| of channel c, d_out[2 C] = the pixels counted, W H exactly. Exact integers, the same in every run. Zeroes d_out on `stream`, then one kernel;
+ * only enqueues, capturable; any pointer alignment; both inputs are only read. */
+int fri_hip_measure_distortion_tiled_dev(fri_hip_plan_tiled *p, const uint8_t *d_tiles, const uint8_t *d_reference_raster, uint64_t *d_out, void *stream);
+/* The size of the `frit` file the emitter writes from the tiles' histograms, without running the coder. The formula of fri_hip_estimate_size_dev per tile, with
+ * the rule of FRI_EMIT_EMPTY_OK (include/fri_emit.h), which codes the tiles: a context without symbols (its counts sum to zero) gets the model of
+ * max_freq_bits = 0, which the floor raises to 8, lists no value and codes no bit. It costs its 14 container bytes and the 8 flush bytes of a rANS state that
+ * never moved - 2 more than the 6 per state that the channel's constant of 60 counts:
+ *     payload(t) = ceil((8 x container(t) + sum of bits) / 8),  each tile rounded up on its own
+ *     container(t) = 18 + sum over channels (218 + sum over the ten contexts (a context with symbols: 14 + 2 n_off; one without: 14 + 2))
+ *     bits = as in fri_hip_estimate_size_dev, over the contexts with symbols
+ *     file = 32 + 8 (n_tiles + 1) + sum over the tiles of payload(t)
+ * 32 = the container's header, 8 (n_tiles + 1) = its offset table. A tile with an out-of-alphabet symbol or a used symbol whose final frequency is 0 is
+ * uncodable: its payload and the file are UINT64_MAX, the other tiles' payloads are what they are. fri_hip_estimate_size* on the inner plan is unchanged and
+ * keeps reporting UINT64_MAX for a histogram with a context without symbols.
+ * d_hist [n_tiles][C][10][1024] as fri_hip_encode_symbols_tiled_dev writes it; d_n_out_of_alphabet [n_tiles][C] (may be NULL: not looked at); d_tile_bytes
+ * [n_tiles] (required: the payloads, and the kernels' scratch); d_file_bytes [1]; d_models (may be NULL) [n_tiles][C][10][4] as in fri_hip_estimate_size_dev -
+ * a context without symbols reports the max_freq_bits the file carries (8) and status 1, and is coded all the same. Integer sums, the same bytes in every run.
+ * The _dev form only enqueues (a memset and three kernels) and is capturable. The host form stages the histograms (n_out_of_alphabet and tile_bytes may be NULL)
+ * and synchronises. */
+int fri_hip_estimate_size_tiled_dev(fri_hip_plan_tiled *p, const uint32_t *d_hist, const uint64_t *d_n_out_of_alphabet, uint64_t *d_file_bytes, uint64_t *d_tile_bytes,
+                                    uint32_t *d_models, void *stream);
+int fri_hip_estimate_size_tiled(fri_hip_plan_tiled *p, const uint32_t *hist, const uint64_t *n_out_of_alphabet, uint64_t *file_bytes, uint64_t *tile_bytes);
+/* The searches of fri_hip_search_quality, fri_hip_search_quality_ssim and fri_hip_search_quality_for_size on a tiled plan: exactly those bisections, return
+ * values, argument checks and refusals (an RCT inner plan: FRI_HIP_ERR_INVALID_ARGUMENT; a YCbCr inner plan: qualities 1..99, and a PSNR or SSIM result of 100
+ * means "code losslessly"; a capturing stream is refused before anything is enqueued or allocated; a host-only plan: FRI_HIP_ERR_NO_DEVICE; SSIM needs W, H >= 8),
+ * measured on what the tiled file of that quality holds: all tiles carry one quality, and that is what is returned. The image is split once per call into the
+ * plan's tile buffer and every probe runs on plan-owned buffers that grow on first use. The inner plan's dequantiser, colour transform and stream order are left
+ * as they are; the probes' inverse kernel uses the midpoint dequantiser whatever is set.
+ *   PSNR  a probe = the forward kernel over all tiles, the inverse kernel over all tiles into a second tile buffer (zeroed once per call, so a pixel that no cell
+ *         owns - FRI_HIP_TILED_ALLOW_HOLES - counts as the 0 the decoder writes), the measuring kernel above against d_pixels: the PSNR of
+ *         fri_hip_search_quality's formula over W H pixels.
+ *   SSIM  a probe = the same two kernels, the merge into a raster the plan owns, K7 on the whole W x H image against d_pixels.
+ *   size  a probe = the chain of fri_hip_encode_image_tiled_symbols with the fit over all tiles (the same histograms; the inner plan needs its stream order),
+ *         then fri_hip_estimate_size_tiled_dev: est_bytes is the file's estimate.
+ * The host forms stage the pixels through the plan's raster buffer. */
+int fri_hip_search_quality_tiled(fri_hip_plan_tiled *p, const uint8_t *pixels, double target_db, int32_t *quality, double *psnr_db);
+int fri_hip_search_quality_tiled_dev(fri_hip_plan_tiled *p, const uint8_t *d_pixels, double target_db, int32_t *quality, double *psnr_db, void *stream);
+int fri_hip_search_quality_ssim_tiled(fri_hip_plan_tiled *p, const uint8_t *pixels, double target, int32_t *quality, double *ssim);
+int fri_hip_search_quality_ssim_tiled_dev(fri_hip_plan_tiled *p, const uint8_t *d_pixels, double target, int32_t *quality, double *ssim, void *stream);
+int fri_hip_search_quality_for_size_tiled(fri_hip_plan_tiled *p, const uint8_t *pixels, uint64_t max_bytes, int32_t *quality, uint64_t *est_bytes);
+int fri_hip_search_quality_for_size_tiled_dev(fri_hip_plan_tiled *p, const uint8_t *d_pixels, uint64_t max_bytes, int32_t *quality, uint64_t *est_bytes, void *stream);
 
 /* ---- timing helper ---------------------------------------------------------------------------- */
 /* Runs the forward kernel `iters` times on `stream` bracketed by HIP events recorded on that same
