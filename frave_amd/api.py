@@ -42,7 +42,10 @@ SYMBOLS = [
     "fri_hip_split_tiles_dev", "fri_hip_merge_tiles_dev", "fri_hip_encode_symbols_tiled_dev", "fri_hip_encode_image_tiled_symbols", "fri_hip_decode_image_tiled",
     "fri_hip_measure_distortion_tiled_dev", "fri_hip_estimate_size_tiled_dev", "fri_hip_estimate_size_tiled", "fri_hip_search_quality_tiled", "fri_hip_search_quality_tiled_dev",
     "fri_hip_search_quality_ssim_tiled", "fri_hip_search_quality_ssim_tiled_dev", "fri_hip_search_quality_for_size_tiled", "fri_hip_search_quality_for_size_tiled_dev",
+    "fri_hip_rans_scratch_bytes", "fri_hip_rans_encode_planes_dev", "fri_hip_rans_time_planes_dev", "fri_hip_encode_image_tiled_coded",
 ]
+RANS_EMPTY_OK = 1  # FRI_HIP_RANS_EMPTY_OK: `flags` of fri_hip_rans_encode_planes_dev - a context without counts is coded (the emitter's FRI_EMIT_EMPTY_OK)
+RANS_TOO_SMALL, RANS_BAD_MODEL, RANS_ZERO_FREQ, RANS_BAD_BUCKET = 1, 2, 4, 8  # bits of a plane's status word (include/fri_hip.h)
 TILED_ALLOW_HOLES = 1  # FRI_HIP_TILED_ALLOW_HOLES: `flags` of fri_hip_plan_tiled_create - accept a tile shape whose lattice does not own every pixel
 ALPHA_KEEP, ALPHA_CLEAN = 0, 1  # `clean` of fri_hip_split_rgba_dev and the RGBA encodes: CLEAN zeroes the colour of pixels with A == 0
 COLOUR_NONE, COLOUR_RCT, COLOUR_YCBCR = 0, 1, 3  # fri_hip_plan_set_colour_transform (bit 0: chroma planes, bit 1: irreversible)
@@ -223,6 +226,10 @@ def load_library():
     L.fri_hip_measure_distortion_tiled_dev.argtypes = [vp, vp, vp, vp, vp]
     L.fri_hip_estimate_size_tiled_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.fri_hip_estimate_size_tiled.argtypes = [vp, vp, vp, vp, vp]
+    L.fri_hip_rans_scratch_bytes.restype, L.fri_hip_rans_scratch_bytes.argtypes = C.c_uint64, [u32, C.c_uint64]
+    L.fri_hip_rans_encode_planes_dev.argtypes = [vp, u32, vp, sz, C.c_uint64, vp, u32, vp, sz, vp, vp, vp, vp, vp, vp]
+    L.fri_hip_rans_time_planes_dev.argtypes = [vp, u32, vp, sz, C.c_uint64, vp, u32, vp, sz, vp, vp, vp, vp, vp, vp, vp]
+    L.fri_hip_encode_image_tiled_coded.argtypes = [vp, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp]
     L.fri_hip_search_quality_tiled.argtypes = [vp, vp, C.c_double, vp, vp]
     L.fri_hip_search_quality_tiled_dev.argtypes = [vp, vp, C.c_double, vp, vp, vp]
     L.fri_hip_search_quality_ssim_tiled.argtypes = [vp, vp, C.c_double, vp, vp]
@@ -284,6 +291,27 @@ def tile_shape(width, height, target=512):
     tw, th = C.c_uint32(0), C.c_uint32(0)
     _check(load_library().fri_hip_tile_shape(width, height, target, C.addressof(tw), C.addressof(th)), "fri_hip_tile_shape")
     return tw.value, th.value
+
+
+def rans_scratch_bytes(n_planes, n_symbols):
+    """fri_hip_rans_scratch_bytes: the device scratch fri_hip_rans_encode_planes_dev needs for n_planes planes of n_symbols symbols (0: counts out of range)."""
+    return int(load_library().fri_hip_rans_scratch_bytes(n_planes, n_symbols))
+
+
+def rans_encode_planes_dev(ctx, n_planes, d_symbols, symbol_stride, n_symbols, d_hist, flags, d_words, word_stride, d_n_words, d_models, d_off_values, d_status, d_scratch,
+                           stream=0, timed=False):
+    """fri_hip_rans_encode_planes_dev (K11), device pointers as ints: d_symbols uint16 streams symbol_stride apart, d_hist uint32 [n_planes][10][1024] -> d_words uint32
+    [n_planes][word_stride], d_n_words uint32 [n_planes], d_models uint32 [n_planes][10][4], d_off_values uint16 [n_planes][10][1024], d_status uint32 [n_planes][4];
+    d_scratch: rans_scratch_bytes(..) bytes, 256-byte aligned. Only enqueues. timed=True: fri_hip_rans_time_planes_dev - synchronises and returns the microseconds of
+    the model, coder and stitch kernels."""
+    L = load_library()
+    args = (ctx._h if ctx else None, n_planes, d_symbols, symbol_stride, n_symbols, d_hist, flags, d_words, word_stride, d_n_words, d_models, d_off_values, d_status, d_scratch,
+            stream)
+    if timed:
+        us = np.zeros(3, np.float64)
+        _check(L.fri_hip_rans_time_planes_dev(*args, _p(us)), "fri_hip_rans_time_planes_dev", ctx)
+        return us
+    _check(L.fri_hip_rans_encode_planes_dev(*args), "fri_hip_rans_encode_planes_dev", ctx)
 
 
 def quality_matrix(quality):
@@ -1082,6 +1110,24 @@ class PlanTiled:
         _check(load_library().fri_hip_encode_image_tiled_symbols(self._h, _p(px), _p(_q(qmatrix)), _p(vp), _p(wp), _p(sym), _p(hist), _p(oob)),
                "fri_hip_encode_image_tiled_symbols", self.ctx)
         return sym, vp, wp, hist, oob
+
+    def encode_image_tiled_coded(self, pixels, qmatrix=None, word_stride=None):
+        """fri_hip_encode_image_tiled_coded: the tiled chain with the fit, then the device rANS coder - (words uint32 [n_tiles C][word_stride], n_words uint32
+        [n_tiles C], models uint32 [n_tiles C][10][4], off_values uint16 [n_tiles C][10][1024], status uint32 [n_tiles C][4], value_params, width_params
+        [n_tiles][C][3][6]): what emit.tiled_encode_from_coded takes. word_stride: words per plane of the returned array (default num_some + 20, which always
+        suffices). Needs set_stream_order()."""
+        px = np.ascontiguousarray(pixels, np.uint8).reshape(-1)
+        assert px.size == self.pixel_bytes
+        n, c = self.n_tiles, self.channels
+        planes = n * c
+        stride = self.num_some + 20 if word_stride is None else int(word_stride)
+        vp, wp = np.zeros((n, c, 3, 6), np.float32), np.zeros((n, c, 3, 6), np.float32)
+        words = np.zeros((planes, stride), np.uint32)
+        n_words, models = np.zeros(planes, np.uint32), np.zeros((planes, 10, 4), np.uint32)
+        off, status = np.zeros((planes, 10, 1024), np.uint16), np.zeros((planes, 4), np.uint32)
+        _check(load_library().fri_hip_encode_image_tiled_coded(self._h, _p(px), _p(_q(qmatrix)), _p(vp), _p(wp), _p(words), stride, _p(n_words), _p(models), _p(off), _p(status)),
+               "fri_hip_encode_image_tiled_coded", self.ctx)
+        return words, n_words, models, off, status, vp, wp
 
     def decode_image_tiled(self, coefs, qmatrix=None):
         """fri_hip_decode_image_tiled: coefs int32 [n_tiles][C][F][512] (what emit.tiled_decode returns) -> pixels uint8 [H * W * C], through the inverse kernel with

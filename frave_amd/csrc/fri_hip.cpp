@@ -30,6 +30,7 @@ struct fri_hip_ctx {
     std::string arch;
     int cu_count = 256;
     std::string last_error;
+    float *rans_laplace = nullptr; // K11's [10][1024] Laplace shapes (laplace_table), uploaded with the context: fri_hip_rans_encode_planes_dev takes no plan
 };
 
 namespace {
@@ -771,11 +772,21 @@ int fri_hip_ctx_create(int device, fri_hip_ctx **out) {
     c->device = device;
     c->arch = prop.gcnArchName;
     c->cu_count = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    const std::vector<float> laplace = laplace_table();
+    if (hipMalloc(&c->rans_laplace, laplace.size() * sizeof(float)) != hipSuccess ||
+        hipMemcpy(c->rans_laplace, laplace.data(), laplace.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+        fri_hip_ctx_destroy(c);
+        return FRI_HIP_ERR_OUT_OF_MEMORY;
+    }
     *out = c;
     return FRI_HIP_OK;
 }
 
 int fri_hip_ctx_destroy(fri_hip_ctx *ctx) {
+    if (ctx && ctx->rans_laplace) {
+        (void)hipSetDevice(ctx->device);
+        (void)hipFree(ctx->rans_laplace);
+    }
     delete ctx;
     return FRI_HIP_OK;
 }
@@ -2695,6 +2706,10 @@ struct fri_hip_plan_tiled {
     Grown<unsigned long long> measure; // a probe's sums: distortion [2 C + 1], SSIM [C + 1] or the file's bytes [1]
     Grown<unsigned long long> rate;   // the size estimate: the tiles' payload bytes [n_tiles]
     Grown<unsigned long long> oob_in; // fri_hip_estimate_size_tiled: the host's out-of-alphabet counts [n_tiles][C]
+    Grown<uint32_t> rans_words;       // fri_hip_encode_image_tiled_coded: K11's outputs [n_tiles C][stride] ...
+    Grown<uint32_t> rans_counts;      // ... n_words [n_tiles C], then status [n_tiles C][4], then models [n_tiles C][10][4]
+    Grown<uint16_t> rans_off;         // ... [n_tiles C][10][1024]
+    Grown<uint8_t> rans_scratch;      // ... and its scratch
     size_t n_tiles() const { return (size_t)nx * ny; }
     size_t raster_bytes() const { return (size_t)width * height * channels; }
     size_t tile_bytes() const { return (size_t)tile_w * tile_h * channels; }
@@ -3053,6 +3068,118 @@ int fri_hip_search_quality_for_size_tiled(fri_hip_plan_tiled *p, const uint8_t *
     if (int rc = need_device_tiled(p)) return rc;
     if (int rc = stage_pixels_tiled(p, pixels)) return rc;
     return fri_hip_search_quality_for_size_tiled_dev(p, p->raster, max_bytes, quality, est_bytes, nullptr);
+}
+
+} // extern "C"
+
+/* ---- K11: the rANS coder on the device ---------------------------------------------------------------------- */
+namespace {
+bool rans_counts_ok(uint32_t n_planes, uint64_t n_symbols) { return n_planes >= 1 && n_planes <= 65535u && n_symbols >= 1 && n_symbols < (1ull << 31); }
+
+int rans_encode(fri_hip_ctx *ctx, uint32_t n_planes, const uint16_t *d_symbols, size_t symbol_stride, uint64_t n_symbols, const uint32_t *d_hist, uint32_t flags,
+                uint32_t *d_words, size_t word_stride, uint32_t *d_n_words, uint32_t *d_models, uint16_t *d_off_values, uint32_t *d_status, void *d_scratch, void *stream,
+                const hipEvent_t *events) {
+    if (!ctx) return FRI_HIP_ERR_NO_DEVICE;
+    if (!d_symbols || !d_hist || !d_words || !d_n_words || !d_models || !d_off_values || !d_status || !d_scratch || (flags & ~(uint32_t)FRI_HIP_RANS_EMPTY_OK) ||
+        !rans_counts_ok(n_planes, n_symbols) || symbol_stride < n_symbols || ((uintptr_t)d_scratch & 255u))
+        return FRI_HIP_ERR_INVALID_ARGUMENT;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, launch_rans_encode(n_planes, d_symbols, symbol_stride, (uint32_t)n_symbols, d_hist, (flags & FRI_HIP_RANS_EMPTY_OK) != 0, ctx->rans_laplace, d_words, word_stride,
+                                    d_n_words, d_models, d_off_values, d_status, d_scratch, (hipStream_t)stream, events));
+    return FRI_HIP_OK;
+}
+} // namespace
+
+extern "C" {
+
+uint64_t fri_hip_rans_scratch_bytes(uint32_t n_planes, uint64_t n_symbols) { return rans_counts_ok(n_planes, n_symbols) ? rans_scratch_layout(n_planes, n_symbols).total : 0; }
+
+int fri_hip_rans_encode_planes_dev(fri_hip_ctx *ctx, uint32_t n_planes, const uint16_t *d_symbols, size_t symbol_stride, uint64_t n_symbols, const uint32_t *d_hist,
+                                   uint32_t flags, uint32_t *d_words, size_t word_stride, uint32_t *d_n_words, uint32_t *d_models, uint16_t *d_off_values,
+                                   uint32_t *d_status, void *d_scratch, void *stream) {
+    return rans_encode(ctx, n_planes, d_symbols, symbol_stride, n_symbols, d_hist, flags, d_words, word_stride, d_n_words, d_models, d_off_values, d_status, d_scratch, stream,
+                       nullptr);
+}
+
+int fri_hip_rans_time_planes_dev(fri_hip_ctx *ctx, uint32_t n_planes, const uint16_t *d_symbols, size_t symbol_stride, uint64_t n_symbols, const uint32_t *d_hist,
+                                 uint32_t flags, uint32_t *d_words, size_t word_stride, uint32_t *d_n_words, uint32_t *d_models, uint16_t *d_off_values,
+                                 uint32_t *d_status, void *d_scratch, void *stream, double us[3]) {
+    if (!ctx) return FRI_HIP_ERR_NO_DEVICE;
+    if (!us) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    Event ev[4];
+    hipEvent_t raw[4];
+    for (int i = 0; i < 4; i++) {
+        HIP_TRY(ctx, hipEventCreate(ev[i].put()));
+        raw[i] = ev[i];
+    }
+    if (int rc = rans_encode(ctx, n_planes, d_symbols, symbol_stride, n_symbols, d_hist, flags, d_words, word_stride, d_n_words, d_models, d_off_values, d_status, d_scratch,
+                             stream, raw))
+        return rc;
+    HIP_TRY(ctx, hipEventSynchronize(raw[3]));
+    for (int i = 0; i < 3; i++) {
+        float ms = 0;
+        HIP_TRY(ctx, hipEventElapsedTime(&ms, raw[i], raw[i + 1]));
+        us[i] = 1000.0 * ms;
+    }
+    return FRI_HIP_OK;
+}
+
+int fri_hip_encode_image_tiled_coded(fri_hip_plan_tiled *p, const uint8_t *pixels, const int32_t qmatrix[32], float *value_params, float *width_params, uint32_t *words,
+                                     size_t word_stride, uint32_t *n_words, uint32_t *models, uint16_t *off_values, uint32_t *status) {
+    if (int rc = need_device_tiled(p)) return rc;
+    if (!pixels || !qmatrix || !value_params || !width_params || !words || !n_words || !models || !off_values || !status) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    fri_hip_ctx *c = p->ctx;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t planes = p->n_tiles() * p->channels, n = p->tile->geo.n_some;
+    if (!rans_counts_ok((uint32_t)planes, n)) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    int rc;
+    if ((rc = grow(c, p->raster, p->raster_bytes())) || (rc = grow(c, p->symbols, planes * n)) || (rc = grow(c, p->hist, planes * 10 * 1024)) ||
+        (rc = grow(c, p->counts, 2 * planes)) || (rc = grow(c, p->params, planes * 36)) || (rc = grow(c, p->rans_counts, planes * 45)) ||
+        (rc = grow(c, p->rans_off, planes * 10 * 1024)) || (rc = grow(c, p->rans_scratch, rans_scratch_layout((uint32_t)planes, n).total)))
+        return rc;
+    HIP_TRY(c, hipMemcpy(p->raster, pixels, p->raster_bytes(), hipMemcpyHostToDevice));
+    uint64_t *oob = reinterpret_cast<uint64_t *>(p->counts.get());
+    if ((rc = fri_hip_encode_symbols_tiled_dev(p, p->raster, qmatrix, 1, p->params, p->symbols, p->hist, oob, oob + planes, nullptr))) return rc;
+    // K11 into a buffer with room for 8 bits per symbol; a plane that needs more makes the one second pass, with the hard bound: a step emits at most one word
+    uint32_t *d_n_words = p->rans_counts, *d_status = d_n_words + planes, *d_models = d_status + 4 * planes;
+    const size_t bound = n + 20;
+    size_t stride = std::min(bound, n / 4 + 20);
+    std::vector<uint32_t> counts(planes * 45);
+    for (;;) {
+        if ((rc = grow(c, p->rans_words, planes * stride))) return rc;
+        if ((rc = fri_hip_rans_encode_planes_dev(c, (uint32_t)planes, p->symbols, n, n, p->hist, FRI_HIP_RANS_EMPTY_OK, p->rans_words, stride, d_n_words, d_models, p->rans_off,
+                                                 d_status, p->rans_scratch, nullptr)))
+            return rc;
+        HIP_TRY(c, hipMemcpy(counts.data(), p->rans_counts, counts.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        bool too_small = false;
+        for (size_t k = 0; k < planes; k++) too_small = too_small || (counts[planes + 4 * k] & FRI_HIP_RANS_TOO_SMALL);
+        if (!too_small || stride == bound) break;
+        stride = bound;
+    }
+    std::vector<float> params(planes * 36);
+    std::vector<uint64_t> range(2 * planes);
+    HIP_TRY(c, hipMemcpy(params.data(), p->params, planes * 36 * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(range.data(), p->counts, 2 * planes * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    std::memcpy(n_words, counts.data(), planes * sizeof(uint32_t));
+    std::memcpy(status, counts.data() + planes, planes * 4 * sizeof(uint32_t));
+    std::memcpy(models, counts.data() + 5 * planes, planes * 40 * sizeof(uint32_t));
+    bool out_of_range = false, refused = false;
+    size_t most_words = 0, most_off = 0;
+    for (size_t k = 0; k < planes; k++) {
+        std::memcpy(value_params + k * 18, params.data() + k * 36, 18 * sizeof(float));
+        std::memcpy(width_params + k * 18, params.data() + k * 36 + 18, 18 * sizeof(float));
+        out_of_range = out_of_range || range[k] || range[planes + k] || n_words[k] > word_stride;
+        refused = refused || status[4 * k];
+        if (n_words[k] <= word_stride && n_words[k] <= stride) most_words = std::max<size_t>(most_words, n_words[k]);
+        for (int b = 0; b < 10; b++) most_off = std::max<size_t>(most_off, std::min<uint32_t>(models[(k * 10 + b) * 4 + 1], 1024u));
+    }
+    // the coded planes only: every plane's row up to the longest row that fits the caller's, every context's list up to the longest list
+    if (most_words)
+        HIP_TRY(c, hipMemcpy2D(words, word_stride * sizeof(uint32_t), p->rans_words, stride * sizeof(uint32_t), most_words * sizeof(uint32_t), planes, hipMemcpyDeviceToHost));
+    if (most_off)
+        HIP_TRY(c, hipMemcpy2D(off_values, 1024 * sizeof(uint16_t), p->rans_off, 1024 * sizeof(uint16_t), most_off * sizeof(uint16_t), planes * 10, hipMemcpyDeviceToHost));
+    return out_of_range ? FRI_HIP_ERR_OUT_OF_RANGE : refused ? FRI_HIP_ERR_INVALID_ARGUMENT : FRI_HIP_OK;
 }
 
 } // extern "C"

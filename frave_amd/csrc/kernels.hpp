@@ -1,5 +1,5 @@
 // kernels.hpp -- launch interface between the C ABI (fri_hip.cpp) and the gfx950 kernels (k1_forward.hip, k2_predict.hip, k3_inverse.hip, k4_fit.hip,
-// k5_stream.hip, k6_rate.hip).
+// k5_stream.hip, k6_rate.hip, ..., k11_rans.hip).
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -190,6 +190,19 @@ hipError_t launch_merge_tiles(const uint8_t *tiles, uint32_t width, uint32_t hei
 // channel c, sums[2 c + 1] = max(.., largest absolute difference), sums[2 C] += pixels (W H in all). The caller zeroes sums with launch_clear_sums.
 hipError_t launch_measure_tiles(const uint8_t *tiles, uint32_t width, uint32_t height, uint32_t channels, uint32_t tile_w, uint32_t tile_h, const uint8_t *reference,
                                 unsigned long long *sums, hipStream_t stream);
+
+// K11 (k11_rans.hip): the rANS coder on the device (include/fri_hip.h, fri_hip_rans_encode_planes_dev, has the layouts and the status values). Three
+// kernels on `stream`: the models and coding tables from hist [n_planes][10][1024] (empty_ok: the emitter's FRI_EMIT_EMPTY_OK), one chain per (plane, context)
+// over symbols [n_planes] streams of n_symbols entries symbol_stride apart, the stitch into words [n_planes][word_stride]. scratch: rans_scratch_layout(..).total
+// bytes, 256-byte aligned. n_planes <= 65535, 1 <= n_symbols < 2^31. events (may be NULL): four events recorded in front of, between and behind the three kernels.
+struct RansScratch {
+    size_t table, state, chain, refused, flags, emitted, total; // byte offsets, and the size
+    size_t flag_stride;
+};
+RansScratch rans_scratch_layout(uint32_t n_planes, uint64_t n_symbols);
+hipError_t launch_rans_encode(uint32_t n_planes, const uint16_t *symbols, size_t symbol_stride, uint32_t n_symbols, const uint32_t *hist, bool empty_ok, const float *laplace,
+                              uint32_t *words, size_t word_stride, uint32_t *n_words, uint32_t *models, uint16_t *off_values, uint32_t *status, void *scratch,
+                              hipStream_t stream, const hipEvent_t *events = nullptr);
 
 // K2's per-node neighbour offsets (LDS halfword offsets relative to the own slot, two per word) from the static neighbour table
 void build_lf_deltas(const uint16_t *nbr_table, int8_t *out /* [8] */);

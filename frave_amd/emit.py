@@ -47,6 +47,8 @@ def load_library():
         L.fri_emit_stream_order.argtypes = [vp, u32, vp, vp, vp]
         L.fri_emit_encode_image_from_streams.argtypes = [u32, u32, u32, vp, C.c_uint64, vp, vp, vp, vp, sz, vp, C.c_char_p, sz]
         L.fri_tiled_encode_from_streams.argtypes = [u32, u32, u32, u32, u32, vp, C.c_uint64, vp, vp, vp, u32, vp, sz, vp, C.c_char_p, sz]
+        L.fri_tiled_encode_from_coded.argtypes = [u32, u32, u32, u32, u32, vp, C.c_uint64, vp, vp, vp, vp, vp, u32, vp, sz, vp, C.c_char_p, sz]
+        L.fri_coded_encode_image.argtypes = [u32, u32, u32, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, sz, vp, C.c_char_p, sz]
         L.fri_tiled_info.argtypes = [vp, sz, vp]
         L.fri_tiled_decode.argtypes = [vp, sz, u32, vp, vp, sz, C.c_char_p, sz]
         _lib = L
@@ -266,6 +268,47 @@ def tiled_encode_from_streams(width, height, tile_w, tile_h, streams, hist, valu
         rc = L.fri_tiled_encode_from_streams(*args, _p(out), out.size, C.addressof(n), err, 256)
     if rc != 0:
         raise EmitError(err.value.decode() or f"fri_tiled_encode_from_streams: {rc}")
+    return out[: n.value].tobytes()
+
+
+def _coded(words, n_words, models, off_values, value_params, width_params):
+    w = np.ascontiguousarray(words, np.uint32)
+    nw, m, off = np.ascontiguousarray(n_words, np.uint32), np.ascontiguousarray(models, np.uint32), np.ascontiguousarray(off_values, np.uint16)
+    vp, wp = np.ascontiguousarray(value_params, np.float32), np.ascontiguousarray(width_params, np.float32)
+    planes = nw.size
+    assert planes and w.size % planes == 0 and m.size == planes * 40 and off.size == planes * 10240 and vp.size == planes * 18 and wp.size == planes * 18
+    return w, w.size // planes, nw, m, off, vp, wp, planes
+
+
+def tiled_encode_from_coded(width, height, tile_w, tile_h, words, n_words, models, off_values, value_params, width_params, rct=False, quality=0, ycbcr=False, threads=0):
+    """fri_tiled_encode_from_coded: the `frit` bytes from what PlanTiled.encode_image_tiled_coded returns - words uint32 [n_tiles C][word_stride], n_words
+    [n_tiles C], models [n_tiles C][10][4], off_values uint16 [n_tiles C][10][1024], params [n_tiles][C][3][6]. Nothing is coded here; the file is
+    tiled_encode_from_streams's, byte for byte."""
+    w, stride, nw, m, off, vp, wp, planes = _coded(words, n_words, models, off_values, value_params, width_params)
+    n_tiles = -(-width // tile_w) * -(-height // tile_h)
+    channels = planes // n_tiles
+    assert planes == n_tiles * channels
+    n = C.c_size_t(0)
+    err = C.create_string_buffer(256)
+    out = np.empty(int(nw.sum()) * 4 + planes * (10 * 2070 + 256) + n_tiles * 72 + 64, np.uint8)
+    rc = load_library().fri_tiled_encode_from_coded(width, height, tile_w, tile_h, _arg(channels, rct, quality, ycbcr), _p(w), stride, _p(nw), _p(m), _p(off), _p(vp), _p(wp),
+                                                    threads, _p(out), out.size, C.addressof(n), err, 256)
+    if rc != 0:
+        raise EmitError(err.value.decode() or f"fri_tiled_encode_from_coded: {rc}")
+    return out[: n.value].tobytes()
+
+
+def coded_encode_image(width, height, words, n_words, models, off_values, value_params, width_params, rct=False, quality=0, ycbcr=False):
+    """fri_coded_encode_image: the `frif` bytes of an ordinary image of 1 or 3 channels from its coded planes (the layouts of tiled_encode_from_coded with C planes):
+    encode_image_from_streams's file, byte for byte."""
+    w, stride, nw, m, off, vp, wp, planes = _coded(words, n_words, models, off_values, value_params, width_params)
+    n = C.c_size_t(0)
+    err = C.create_string_buffer(256)
+    out = np.empty(int(nw.sum()) * 4 + planes * (10 * 2070 + 256) + 64, np.uint8)
+    rc = load_library().fri_coded_encode_image(width, height, _arg(planes, rct, quality, ycbcr), _p(w), stride, _p(nw), _p(m), _p(off), _p(vp), _p(wp), _p(out), out.size,
+                                               C.addressof(n), err, 256)
+    if rc != 0:
+        raise EmitError(err.value.decode() or f"fri_coded_encode_image: {rc}")
     return out[: n.value].tobytes()
 
 

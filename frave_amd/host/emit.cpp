@@ -198,40 +198,8 @@ std::string AnsContext::finalize(int bucket) {
 
 // ---- rANS (ryg_rans rans64: state in [2^31, 2^63), 32-bit renormalisation) ----------------------------------------------
 void RansEncoderMulti::put_at(int s, uint32_t start, uint32_t freq, uint32_t scale_bits) {
-    uint64_t x = x_[s];
-    const uint64_t x_max = ((((uint64_t)1 << 31) >> scale_bits) << 32) * freq;
-    if (x >= x_max) {
-        rev_.push_back((uint32_t)x);
-        x >>= 32;
-    }
-    x_[s] = ((x / freq) << scale_bits) + (x % freq) + start;
-}
-// ryg_rans' Rans64EncSymbol: the division and the remainder of put_at replaced by a multiplication with a precomputed 64-bit
-// reciprocal (rans64.h, Rans64EncSymbolInit / Rans64EncPutSymbol). Exact: q below equals x / freq for every state x < 2^63, so
-// x + bias + q * cmpl_freq is the same new state as ((x / freq) << scale_bits) + x % freq + start.
-RansEncoderMulti::EncSymbol RansEncoderMulti::make_symbol(uint32_t start, uint32_t freq, uint32_t scale_bits) {
-    EncSymbol s;
-    s.freq = freq;
-    s.cmpl_freq = (uint32_t)((1ull << scale_bits) - freq);
-    s.x_max = ((((uint64_t)1 << 31) >> scale_bits) << 32) * freq;
-    if (freq < 2) { // q = mul_hi(x, ~0) = x - 1 for x > 0; new state = x + start + (2^scale - 1) + (x - 1) * (2^scale - 1) = (x << scale) + start
-        s.rcp_freq = ~0ull;
-        s.rcp_shift = 0;
-        s.bias = start + (uint32_t)((1ull << scale_bits) - 1);
-    } else {
-        uint32_t shift = 0;
-        while (freq > (1u << shift)) shift++;
-        // ceil(2^(shift + 63) / freq) by long division in two 32-bit digits
-        uint64_t x0 = freq - 1;
-        const uint64_t x1 = 1ull << (shift + 31);
-        const uint64_t t1 = x1 / freq;
-        x0 += (x1 % freq) << 32;
-        const uint64_t t0 = x0 / freq;
-        s.rcp_freq = t0 + (t1 << 32);
-        s.rcp_shift = shift - 1;
-        s.bias = start;
-    }
-    return s;
+    uint32_t word;
+    if (fri::rans::put_division(x_[s], start, freq, scale_bits, word)) rev_.push_back(word);
 }
 void RansEncoderMulti::flush_all() {
     for (int s = 0; s < kContexts; s++) { // each flush prepends two words: state kContexts-1 ends up first in the stream
@@ -428,13 +396,11 @@ std::string encode_symbols(const std::vector<uint16_t> &symbols, const std::vect
                     c.error_at = k, c.error = "symbol with zero model frequency";
                     return;
                 }
-                if (x >= e.x_max) {
-                    c.words.push_back((uint32_t)x);
+                uint32_t word;
+                if (fri::rans::put_symbol(x, e, word)) {
+                    c.words.push_back(word);
                     emitted[k] = 1;
-                    x >>= 32;
                 }
-                const uint64_t q = (uint64_t)(((unsigned __int128)x * e.rcp_freq) >> 64) >> e.rcp_shift;
-                x = x + e.bias + q * e.cmpl_freq;
             }
         }
         c.x = x;
@@ -1054,6 +1020,9 @@ std::string for_each_tile(size_t n_tiles, unsigned threads, Work &&work) {
 }
 } // namespace
 
+static void assemble_tiled(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint64_t nx, uint64_t ny, const std::vector<std::vector<uint8_t>> &payload,
+                           std::vector<uint8_t> &out);
+
 std::string encode_tiled_from_streams(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t channels, bool rct, uint32_t quality, bool ycbcr,
                                       const uint16_t *streams, size_t n_symbols, const uint32_t *hist, const float *value_params, const float *width_params, unsigned threads,
                                       std::vector<uint8_t> &out) {
@@ -1083,6 +1052,53 @@ std::string encode_tiled_from_streams(uint32_t width, uint32_t height, uint32_t 
         return "";
     });
     if (!e.empty()) return e;
+    assemble_tiled(width, height, tile_w, tile_h, nx, ny, payload, out);
+    return "";
+}
+
+// A channel from its coded parts (the device coder K11, include/fri_hip.h): serialize reads a context's max_freq_bits and off-distribution list and the data bytes, nothing else
+static std::string channel_from_coded(const uint32_t *words, uint32_t n_words, const uint32_t *models /* [10][4] */, const uint16_t *off_values /* [10][1024] */, ChannelStream &out) {
+    if (n_words < 2u * kContexts) return "coded plane: fewer words than the flush of the ten states";
+    for (int b = 0; b < kContexts; b++) {
+        const uint32_t n_off = models[4 * b + 1];
+        if (n_off > (uint32_t)kAlphabet) return "coded plane: more off-distribution values than symbols";
+        out.contexts[b].max_freq_bits = models[4 * b];
+        out.contexts[b].off_distribution_values.assign(off_values + (size_t)b * kAlphabet, off_values + (size_t)b * kAlphabet + n_off);
+    }
+    out.data.resize((size_t)n_words * 4);
+#if defined(__BYTE_ORDER__) && __BYTE_ORDER__ == __ORDER_LITTLE_ENDIAN__
+    std::memcpy(out.data.data(), words, (size_t)n_words * 4); // the data is the words, little-endian
+#else
+    for (size_t i = 0; i < n_words; i++) {
+        const uint32_t w = words[i];
+        uint8_t *d = out.data.data() + 4 * i;
+        d[0] = (uint8_t)w, d[1] = (uint8_t)(w >> 8), d[2] = (uint8_t)(w >> 16), d[3] = (uint8_t)(w >> 24);
+    }
+#endif
+    return "";
+}
+
+std::string encode_image_from_coded(uint32_t width, uint32_t height, uint32_t channels, bool rct, uint32_t quality, bool ycbcr, const uint32_t *words, size_t word_stride,
+                                    const uint32_t *n_words, const uint32_t *models, const uint16_t *off_values, const float *value_params, const float *width_params,
+                                    std::vector<uint8_t> &out) {
+    if (!width || !height || (channels != 1 && channels != 3)) return "invalid argument";
+    std::vector<ChannelStream> chans(channels);
+    std::vector<ChannelParams> params(channels);
+    for (uint32_t ch = 0; ch < channels; ch++) {
+        if (n_words[ch] > word_stride) return "channel " + std::to_string(ch) + ": coded plane: more words than the stride holds";
+        const std::string e = channel_from_coded(words + ch * word_stride, n_words[ch], models + (size_t)ch * kContexts * 4, off_values + (size_t)ch * kContexts * kAlphabet, chans[ch]);
+        if (!e.empty()) return "channel " + std::to_string(ch) + ": " + e;
+        std::memcpy(params[ch].value, value_params + ch * 18, sizeof(params[ch].value));
+        std::memcpy(params[ch].width, width_params + ch * 18, sizeof(params[ch].width));
+    }
+    out = serialize(height, width, channels == 1 ? kLuma : rct || ycbcr ? kYCbCr : kRGB, chans, params, rct, quality, ycbcr);
+    return "";
+}
+
+// the `frit` file around its tiles' payloads
+static void assemble_tiled(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint64_t nx, uint64_t ny, const std::vector<std::vector<uint8_t>> &payload,
+                           std::vector<uint8_t> &out) {
+    const size_t n_tiles = payload.size();
     out.clear();
     uint64_t total = kTiledHeader + 8 * (n_tiles + 1);
     for (const auto &b : payload) total += b.size();
@@ -1094,6 +1110,23 @@ std::string encode_tiled_from_streams(uint32_t width, uint32_t height, uint32_t 
     for (size_t t = 0; t < n_tiles; t++) put_u64(out, at), at += payload[t].size();
     put_u64(out, at);
     for (const auto &b : payload) out.insert(out.end(), b.begin(), b.end());
+}
+
+std::string encode_tiled_from_coded(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t channels, bool rct, uint32_t quality, bool ycbcr,
+                                    const uint32_t *words, size_t word_stride, const uint32_t *n_words, const uint32_t *models, const uint16_t *off_values,
+                                    const float *value_params, const float *width_params, unsigned threads, std::vector<uint8_t> &out) {
+    if (!width || !height || !tile_w || !tile_h || (channels != 1 && channels != 3)) return "invalid argument";
+    const uint64_t nx = ((uint64_t)width + tile_w - 1) / tile_w, ny = ((uint64_t)height + tile_h - 1) / tile_h;
+    if (nx * ny > 0xFFFFFFFFull) return "invalid argument";
+    const size_t n_tiles = (size_t)(nx * ny);
+    std::vector<std::vector<uint8_t>> payload(n_tiles);
+    const std::string e = for_each_tile(n_tiles, threads, [&](size_t t) -> std::string {
+        const size_t plane0 = t * channels;
+        return encode_image_from_coded(tile_w, tile_h, channels, rct, quality, ycbcr, words + plane0 * word_stride, word_stride, n_words + plane0, models + plane0 * kContexts * 4,
+                                       off_values + plane0 * kContexts * kAlphabet, value_params + plane0 * 18, width_params + plane0 * 18, payload[t]);
+    });
+    if (!e.empty()) return e;
+    assemble_tiled(width, height, tile_w, tile_h, nx, ny, payload, out);
     return "";
 }
 

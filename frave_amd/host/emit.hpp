@@ -17,6 +17,8 @@
 #include <string>
 #include <vector>
 
+#include "../csrc/rans_step.hpp"
+
 namespace fri {
 struct Geometry;
 }
@@ -64,20 +66,12 @@ int32_t unpack_signed(uint32_t k);                         // utils.rs:42-48
 class RansEncoderMulti {
   public:
     void put_at(int state, uint32_t start, uint32_t freq, uint32_t scale_bits);
-    // the same step with the division precomputed per (model, symbol): see make_symbol in emit.cpp
-    struct EncSymbol {
-        uint64_t x_max, rcp_freq;
-        uint32_t freq, bias, cmpl_freq, rcp_shift;
-    };
-    static EncSymbol make_symbol(uint32_t start, uint32_t freq, uint32_t scale_bits);
+    // the same step with the division precomputed per (model, symbol): csrc/rans_step.hpp, the one source the device coder (k11_rans.hip) shares
+    using EncSymbol = fri::rans::EncSymbol;
+    static EncSymbol make_symbol(uint32_t start, uint32_t freq, uint32_t scale_bits) { return fri::rans::make_symbol(start, freq, scale_bits); }
     void put_symbol(int state, const EncSymbol &s) {
-        uint64_t x = x_[state];
-        if (x >= s.x_max) {
-            rev_.push_back((uint32_t)x);
-            x >>= 32;
-        }
-        const uint64_t q = (uint64_t)(((unsigned __int128)x * s.rcp_freq) >> 64) >> s.rcp_shift;
-        x_[state] = x + s.bias + q * s.cmpl_freq;
+        uint32_t word;
+        if (fri::rans::put_symbol(x_[state], s, word)) rev_.push_back(word);
     }
     void reserve(size_t n_symbols) { rev_.reserve(n_symbols / 2 + 64); }
     void flush_all();
@@ -213,6 +207,17 @@ struct TiledInfo {
 std::string encode_tiled_from_streams(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t channels, bool rct, uint32_t quality, bool ycbcr,
                                       const uint16_t *streams, size_t n_symbols, const uint32_t *hist, const float *value_params, const float *width_params, unsigned threads,
                                       std::vector<uint8_t> &out);
+// The same file from planes the device coded (K11; include/fri_hip.h, fri_hip_rans_encode_planes_dev, has the layouts): words [n_tiles channels][word_stride] of which
+// the first n_words [n_tiles channels] of a plane are its rANS data as little-endian words, models [n_tiles channels][10][4] = {max_freq_bits, n_off, -, -}, off_values
+// [n_tiles channels][10][1024] of which a context's first n_off are its list. Through the same serialize: byte for byte encode_tiled_from_streams's file when the planes
+// are what the host coder makes of the streams.
+std::string encode_tiled_from_coded(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t channels, bool rct, uint32_t quality, bool ycbcr,
+                                    const uint32_t *words, size_t word_stride, const uint32_t *n_words, const uint32_t *models, const uint16_t *off_values,
+                                    const float *value_params, const float *width_params, unsigned threads, std::vector<uint8_t> &out);
+// ... and one ordinary image (`frif`) of 1 or 3 channels from its coded planes [channels]
+std::string encode_image_from_coded(uint32_t width, uint32_t height, uint32_t channels, bool rct, uint32_t quality, bool ycbcr, const uint32_t *words, size_t word_stride,
+                                    const uint32_t *n_words, const uint32_t *models, const uint16_t *off_values, const float *value_params, const float *width_params,
+                                    std::vector<uint8_t> &out);
 // Header, table and every payload's 16-byte header; "Malformed tiled image" for anything that does not hold together. offset: [n_tiles + 1].
 std::string parse_tiled(const uint8_t *frv, size_t len, TiledInfo &info, std::vector<uint64_t> &offset);
 // coefs [n_tiles][channels][F][512]. too_small: coefs is NULL or coef_cap (elements) does not hold them - `info` is filled, nothing is decoded.

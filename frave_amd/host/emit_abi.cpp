@@ -249,6 +249,40 @@ int fri_tiled_encode_from_streams(uint32_t width, uint32_t height, uint32_t tile
     return 0;
 }
 
+int fri_tiled_encode_from_coded(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t channels_arg, const uint32_t *words, uint64_t word_stride,
+                                const uint32_t *n_words, const uint32_t *models, const uint16_t *off_values, const float *value_params, const float *width_params,
+                                uint32_t threads, uint8_t *out, size_t cap, size_t *len, char *err, size_t err_cap) {
+    uint32_t channels, quality;
+    bool rct, ycbcr, empty_ok = false;
+    if (!words || !n_words || !models || !off_values || !value_params || !width_params || !len || !split_channels(channels_arg, channels, rct, quality, ycbcr, nullptr, nullptr, &empty_ok))
+        return fail(err, err_cap, "invalid argument");
+    std::vector<uint8_t> bytes;
+    const std::string e = encode_tiled_from_coded(width, height, tile_w, tile_h, channels, rct, quality, ycbcr, words, (size_t)word_stride, n_words, models, off_values, value_params,
+                                                  width_params, threads, bytes);
+    if (e == "invalid argument") return fail(err, err_cap, e);
+    if (!e.empty()) return fail(err, err_cap, e, -2);
+    *len = bytes.size();
+    if (!out || cap < bytes.size()) return -3;
+    std::memcpy(out, bytes.data(), bytes.size());
+    return 0;
+}
+
+int fri_coded_encode_image(uint32_t width, uint32_t height, uint32_t channels_arg, const uint32_t *words, uint64_t word_stride, const uint32_t *n_words, const uint32_t *models,
+                           const uint16_t *off_values, const float *value_params, const float *width_params, uint8_t *out, size_t cap, size_t *len, char *err, size_t err_cap) {
+    uint32_t channels, quality;
+    bool rct, ycbcr, empty_ok = false;
+    if (!words || !n_words || !models || !off_values || !value_params || !width_params || !len || !split_channels(channels_arg, channels, rct, quality, ycbcr, nullptr, nullptr, &empty_ok))
+        return fail(err, err_cap, "invalid argument");
+    std::vector<uint8_t> bytes;
+    const std::string e = encode_image_from_coded(width, height, channels, rct, quality, ycbcr, words, (size_t)word_stride, n_words, models, off_values, value_params, width_params, bytes);
+    if (e == "invalid argument") return fail(err, err_cap, e);
+    if (!e.empty()) return fail(err, err_cap, e, -2);
+    *len = bytes.size();
+    if (!out || cap < bytes.size()) return -3;
+    std::memcpy(out, bytes.data(), bytes.size());
+    return 0;
+}
+
 int fri_tiled_info(const uint8_t *frv, size_t len, uint32_t info[8]) {
     if (!frv || !info) return -1;
     TiledInfo t;

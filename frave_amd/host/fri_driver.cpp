@@ -22,6 +22,8 @@
 //                                                            --tile-size T (any mode flag but --420; no alpha): the image as a batch of independently coded tiles
 //                                                            of about T x T (fri_hip_tile_shape), a `frit` file; --psnr / --ssim / --size search on the tiled plan
 //                                                            (fri_hip_search_quality*_tiled): the target holds for the file that is written
+//                                                            --device-rans (with --tile-size): the rANS coder runs on the device too (K11), the host writes the
+//                                                            container around the coded planes - the same file
 //   fri_driver decode-file <in.frv> <out.pgm|.ppm|.bmp|.pam>  (.pam for a file with an alpha plane, and for no other) container -> rANS / context decoding on the host -> dequantisation + inverse
 //                                                            transform on the device (fri-cli decode, crates/fri-cli/src/commands/decode.rs); a flagged file
 //                                                            comes back as RGB, a lossy file with its quality's matrix and the midpoint dequantiser
@@ -543,6 +545,7 @@ int main(int argc, char **argv) {
             else if (a == "--size" && i + 1 < argc) file_opts.target_bytes = std::strtoull(argv[++i], nullptr, 10), has_size = true;
             else if (a == "--bpp" && i + 1 < argc) bpp = std::atof(argv[++i]), has_bpp = true;
             else if (a == "--tile-size" && i + 1 < argc) tile_size = std::atol(argv[++i]), tiled = true;
+            else if (a == "--device-rans") file_opts.device_rans = true;
             else {
                 std::fprintf(stderr, "encode-file: unknown option %s\n", a.c_str());
                 return 2;
@@ -578,6 +581,10 @@ int main(int argc, char **argv) {
         }
         if (tiled && (tile_size < 1 || tile_size > 65535 || rgba || sub420)) {
             std::fprintf(stderr, "encode-file: --tile-size T (1..65535) takes a PGM, PPM or BMP and every mode flag but --420; no alpha (4:2:0 and alpha in tiles are out of scope)\n");
+            return 2;
+        }
+        if (file_opts.device_rans && !tiled) {
+            std::fprintf(stderr, "encode-file: --device-rans codes the tiles of --tile-size T on the device (ordinary, 4:2:0 and RGBA files are coded on the host)\n");
             return 2;
         }
         if (tiled) return encode_image_tiled_to_file(img, fw, fh, fc, file_opts, (uint32_t)tile_size, argv[3]);
@@ -637,7 +644,7 @@ int main(int argc, char **argv) {
         return 0;
     }
     if (argc < 5) {
-        std::fprintf(stderr, "usage: %s roundtrip|encode|batch|batch-frv <width> <height> <channels> [n_images | out.frv]\n       %s encode-file <in.pgm|in.ppm|in.bmp|in.pam> <out.frv> [--rct | [--ycbcr | --420] (--quality Q | --psnr DB | --ssim S | --size BYTES | --bpp B)] [--clean-alpha] [--tile-size T]\n       %s decode-file <in.frv> <out.pgm|out.ppm|out.bmp|out.pam>\n", argv[0], argv[0], argv[0]);
+        std::fprintf(stderr, "usage: %s roundtrip|encode|batch|batch-frv <width> <height> <channels> [n_images | out.frv]\n       %s encode-file <in.pgm|in.ppm|in.bmp|in.pam> <out.frv> [--rct | [--ycbcr | --420] (--quality Q | --psnr DB | --ssim S | --size BYTES | --bpp B)] [--clean-alpha] [--tile-size T [--device-rans]]\n       %s decode-file <in.frv> <out.pgm|out.ppm|out.bmp|out.pam>\n", argv[0], argv[0], argv[0]);
         return 2;
     }
     const std::string cmd = argv[1];

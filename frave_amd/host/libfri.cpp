@@ -1060,8 +1060,8 @@ Result<EncodedTiled> encode_bytes_tiled(const std::vector<uint8_t> &pixels, uint
     r.value.tile_w = tw, r.value.tile_h = th, r.value.nx = grid[0], r.value.ny = grid[1];
     const size_t planes = (size_t)grid[0] * grid[1] * c;
     const uint64_t n = fri_hip_plan_num_some(tile);
-    std::vector<uint16_t> symbols(planes * (size_t)n);
-    std::vector<uint32_t> hist(planes * CONTEXT_AMOUNT * ALPHABET_SIZE);
+    std::vector<uint16_t> symbols(opts.device_rans ? 0 : planes * (size_t)n); // (the device coder's route reads neither streams nor histograms back)
+    std::vector<uint32_t> hist(opts.device_rans ? 0 : planes * CONTEXT_AMOUNT * ALPHABET_SIZE);
     std::vector<float> vp(planes * 18), wp(planes * 18);
     std::vector<uint64_t> oob(planes, 0);
     // the device batch and the emitter for what `coded` says (a quality or lossless, no targets): "" or the error; the file in r.value.bytes
@@ -1069,11 +1069,28 @@ Result<EncodedTiled> encode_bytes_tiled(const std::vector<uint8_t> &pixels, uint
         if (const std::string e = coding_matrix(coded, qm); !e.empty()) return e;
         const ImageMetadata md = coded_metadata(th, tw, colorspace, coded);
         if (const std::string e = set_colour_transform(tile, md.rct, dev, md.ycbcr); !e.empty()) return e;
+        r.value.bytes.clear();
+        if (opts.device_rans) { // K11: the planes come back coded, the host writes the container around them
+            const size_t stride = (size_t)n + 20; // a step emits at most one word
+            std::vector<uint32_t> words(planes * stride), n_words(planes), models(planes * CONTEXT_AMOUNT * 4), status(planes * 4);
+            std::vector<uint16_t> off(planes * CONTEXT_AMOUNT * ALPHABET_SIZE);
+            if (const int rc = fri_hip_encode_image_tiled_coded(raw, pixels.data(), qm.data(), vp.data(), wp.data(), words.data(), stride, n_words.data(), models.data(), off.data(),
+                                                                status.data());
+                rc != FRI_HIP_OK) {
+                for (size_t k = 0; k < planes; k++)
+                    if (status[4 * k]) return "tile " + std::to_string(k / c) + ": channel " + std::to_string(k % c) + ": the device coder refuses the plane (status " + std::to_string(status[4 * k]) + ")";
+                return dev.describe(rc);
+            }
+            const std::string e = emit::encode_tiled_from_coded(width, height, tw, th, c, md.rct, md.quality, md.ycbcr, words.data(), stride, n_words.data(), models.data(), off.data(),
+                                                                vp.data(), wp.data(), threads, r.value.bytes);
+            if (!e.empty()) return e;
+            r.value.quality = (int)md.quality, r.value.rct = md.rct, r.value.ycbcr = md.ycbcr;
+            return std::string();
+        }
         if (const int rc = fri_hip_encode_image_tiled_symbols(raw, pixels.data(), qm.data(), vp.data(), wp.data(), symbols.data(), hist.data(), oob.data()); rc != FRI_HIP_OK)
             return dev.describe(rc);
         for (uint64_t v : oob)
             if (v) return "symbol outside the 1024-entry alphabet"; // the reference panics: bump_freq, entropy_coding.rs:99
-        r.value.bytes.clear();
         const std::string e = emit::encode_tiled_from_streams(width, height, tw, th, c, md.rct, md.quality, md.ycbcr, symbols.data(), (size_t)n, hist.data(), vp.data(), wp.data(), threads,
                                                               r.value.bytes);
         if (!e.empty()) return e;

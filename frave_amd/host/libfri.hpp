@@ -82,6 +82,9 @@ struct EncoderOpts { // encoder.rs:58-64
     // and measure in R, G, B; a PSNR or SSIM search that returns 100 codes a lossless RCT file instead (EncodedStages::lossless_rct says so); a size search covers
     // qualities 1..99 only and never falls back to a lossless file.
     bool ycbcr = false;
+    // encode_bytes_tiled only: the rANS coder runs on the device too (K11, fri_hip_encode_image_tiled_coded) and the host only assembles the container
+    // (emit::encode_tiled_from_coded) - the same file, byte for byte, as the host coder writes.
+    bool device_rans = false;
     EncoderOpts() { quantization_matrix.fill(1); }
 };
 
@@ -266,6 +269,7 @@ Result<RasterImage> round_trip_rgba(const std::vector<uint8_t> &rgba, uint32_t h
 // at opts.quality, or at the quality one of the targets finds. target_psnr / target_ssim: fri_hip_search_quality_tiled / fri_hip_search_quality_ssim_tiled on the
 // tiled plan - the lowest quality at which the tiled round trip reaches the target; 100 codes a lossless file (a YCbCr request then becomes the RCT). target_bytes:
 // fri_hip_search_quality_for_size_tiled, then code, emit and step one quality down while the file is over the budget, at most 8 steps, as FRIEncoder::encode does.
+// opts.device_rans: the device codes the planes as well (fri_hip_encode_image_tiled_coded) and only the coded planes come back; the file is the same.
 // FRIDecoder::decode reads such files.
 struct EncodedTiled {
     std::vector<uint8_t> bytes;

@@ -149,6 +149,18 @@ int fri_emit_rans_selfcheck(uint64_t n_symbols, uint64_t seed, char *err, size_t
 int fri_tiled_encode_from_streams(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t channels, const uint16_t *streams, uint64_t n_symbols,
                                   const uint32_t *hist, const float *value_params, const float *width_params, uint32_t threads, uint8_t *out, size_t cap, size_t *len, char *err,
                                   size_t err_cap);
+/* The same file from planes the device coded (K11: fri_hip_rans_encode_planes_dev / fri_hip_encode_image_tiled_coded, include/fri_hip.h, which defines the layouts): the
+ * arguments of fri_tiled_encode_from_streams with the coded planes in the place of the streams and histograms. words uint32 [n_tiles C][word_stride]: the first
+ * n_words[p] of plane p are its rANS data as little-endian words (at least 20, at most word_stride, -2 otherwise); models uint32 [n_tiles C][10][4], of which
+ * {max_freq_bits, n_off} are read; off_values uint16 [n_tiles C][10][1024], of which a context's first n_off (<= 1024) are read. Nothing is coded here: the
+ * container is written around the parts through the same serializer, so the file is byte for byte fri_tiled_encode_from_streams's when the planes are what the
+ * host coder makes of the streams. The status the device reported is the caller's to check. Returns 0 and *len, or -3 with *len = needed size. */
+int fri_tiled_encode_from_coded(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t channels, const uint32_t *words, uint64_t word_stride,
+                                const uint32_t *n_words, const uint32_t *models, const uint16_t *off_values, const float *value_params, const float *width_params,
+                                uint32_t threads, uint8_t *out, size_t cap, size_t *len, char *err, size_t err_cap);
+/* ... and one ordinary `frif` image of 1 or 3 channels from its C coded planes (`channels` as above): byte for byte fri_emit_encode_image_from_streams's file. */
+int fri_coded_encode_image(uint32_t width, uint32_t height, uint32_t channels, const uint32_t *words, uint64_t word_stride, const uint32_t *n_words, const uint32_t *models,
+                           const uint16_t *off_values, const float *value_params, const float *width_params, uint8_t *out, size_t cap, size_t *len, char *err, size_t err_cap);
 /* info = {W, H, tile_w, tile_h, nx, ny, the info[2] fri_emit_decode_image reports for tile 0, F = the cells of the tile lattice}. Checks the header, the table
  * and every payload's 16-byte header, decodes nothing. -2 for a file that is not a well-formed `frit` file. */
 int fri_tiled_info(const uint8_t *frv, size_t len, uint32_t info[8]);

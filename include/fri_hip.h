@@ -671,6 +671,67 @@ int fri_hip_search_quality_ssim_tiled_dev(fri_hip_plan_tiled *p, const uint8_t *
 int fri_hip_search_quality_for_size_tiled(fri_hip_plan_tiled *p, const uint8_t *pixels, uint64_t max_bytes, int32_t *quality, uint64_t *est_bytes);
 int fri_hip_search_quality_for_size_tiled_dev(fri_hip_plan_tiled *p, const uint8_t *d_pixels, uint64_t max_bytes, int32_t *quality, uint64_t *est_bytes, void *stream);
 
+/* ---- the rANS coder on the device (K11, k11_rans.hip) ------------------------------------------- */
+/* The emitter's last stage - symbols to rANS words (host/emit.cpp, encode_symbols) - for a batch of planes, a plane being one channel of one tile or of an
+ * ordinary image. A plane's ten rANS states are independent chains (a state's history depends on its own context's symbols only), so a batch of n_planes planes
+ * is 10 n_planes sequential chains that run side by side, and the shared word stream is put together by a prefix sum. The coder step is the host's, from one
+ * header (csrc/rans_step.hpp), and the model is the one K6 rebuilds from the histogram (csrc/ans_model.hpp): the words are bit for bit what
+ * fri_emit_encode_image_from_streams puts between a channel's DAT marker and its EOC marker.
+ *
+ * Inputs (device memory): d_symbols = n_planes streams of n_symbols uint16 entries `bucket << 10 | symbol`, symbol_stride entries apart (what
+ * fri_hip_encode_symbols_batch_dev and fri_hip_encode_symbols_tiled_dev write); d_hist uint32 [n_planes][10][1024], K2's counts. flags: 0 or
+ * FRI_HIP_RANS_EMPTY_OK - the emitter's FRI_EMIT_EMPTY_OK (include/fri_emit.h): a context whose counts sum to zero is coded with the model of
+ * max_freq_bits = 0 instead of refused (the tiles of a `frit` file are coded so). 1 <= n_planes <= 65535, 1 <= n_symbols < 2^31, symbol_stride >= n_symbols.
+ *
+ * Outputs (device memory), per plane p:
+ *   d_words   uint32 [n_planes][word_stride]: the channel's rANS data as little-endian 32-bit words, word k = bytes 4k .. 4k + 3 of the data. Words 0 .. 19 are
+ *             the flush of the ten states - state 9's low word, state 9's high word, state 8's low word, ... state 0's high word at word 19 (state s codes
+ *             context s; a state that coded nothing flushes 2^31) - then one word per coder step that renormalised, in ascending symbol index.
+ *   d_n_words uint32 [n_planes]: the number of words of the plane's data, 20 + the renormalising steps - at most n_symbols + 20, since a step emits at most one
+ *             word. Reported in full even when it exceeds word_stride; nothing is written at or beyond word_stride then, and the status says so.
+ *   d_models  uint32 [n_planes][10][4] = {max_freq_bits, n_off, collapsed slots, status word}, exactly what fri_hip_estimate_size_dev reports: max_freq_bits
+ *             and n_off are what the container's EHD segment of the context carries.
+ *   d_off_values uint16 [n_planes][10][1024]: the first n_off entries of a context are its off-distribution values, ascending - the order the emitter lists
+ *             them in; the rest is not written.
+ *   d_status  uint32 [n_planes][4] = {bits, zero_at, bucket_at, 0}. bits = 0: the plane's outputs are what the emitter writes. Otherwise the words are not a
+ *             stream to keep, and bits says why:
+ *               FRI_HIP_RANS_TOO_SMALL   (1)  n_words > word_stride: call again with a larger stride (n_symbols + 20 always suffices); models and lists are valid
+ *               FRI_HIP_RANS_BAD_MODEL   (2)  a context's model is refused: the emitter's "empty context" error (never with FRI_HIP_RANS_EMPTY_OK for a
+ *                                             context without counts)
+ *               FRI_HIP_RANS_ZERO_FREQ   (4)  a symbol of the stream has model frequency 0 (the emitter's "symbol with zero model frequency"; the histogram is
+ *                                             not the stream's); zero_at = 1 + the highest symbol index at which that happened, where the host's one-loop coder stops
+ *               FRI_HIP_RANS_BAD_BUCKET  (8)  a stream entry has a bucket above 9 and belongs to no chain; bucket_at = 1 + the highest such index
+ *             zero_at and bucket_at are 0 when their bit is clear. A step that meets a zero frequency is skipped, the chain goes on.
+ *
+ * d_scratch: fri_hip_rans_scratch_bytes(n_planes, n_symbols) bytes of device memory, 256-byte aligned, the caller's - 320 KiB of coding tables per plane plus
+ * 5 bytes per symbol (0 for arguments out of range). The _dev call only enqueues on `stream` - three kernels, none of which waits for another
+ * workgroup - and can be captured into a graph; ctx supplies the device and the Laplace table uploaded when it was created. Nothing is accumulated with atomics:
+ * the same inputs give the same bytes in every run. FRI_HIP_ERR_INVALID_ARGUMENT for a null pointer, an unknown flag or a count out of range. */
+#define FRI_HIP_RANS_EMPTY_OK 1u
+#define FRI_HIP_RANS_TOO_SMALL 1u
+#define FRI_HIP_RANS_BAD_MODEL 2u
+#define FRI_HIP_RANS_ZERO_FREQ 4u
+#define FRI_HIP_RANS_BAD_BUCKET 8u
+uint64_t fri_hip_rans_scratch_bytes(uint32_t n_planes, uint64_t n_symbols);
+int fri_hip_rans_encode_planes_dev(fri_hip_ctx *ctx, uint32_t n_planes, const uint16_t *d_symbols, size_t symbol_stride, uint64_t n_symbols, const uint32_t *d_hist,
+                                   uint32_t flags, uint32_t *d_words, size_t word_stride, uint32_t *d_n_words, uint32_t *d_models, uint16_t *d_off_values,
+                                   uint32_t *d_status, void *d_scratch, void *stream);
+/* The same launch bracketed by events on `stream`: us[3] = the microseconds of the model, coder and stitch kernels. Synchronises; for measurements. */
+int fri_hip_rans_time_planes_dev(fri_hip_ctx *ctx, uint32_t n_planes, const uint16_t *d_symbols, size_t symbol_stride, uint64_t n_symbols, const uint32_t *d_hist,
+                                 uint32_t flags, uint32_t *d_words, size_t word_stride, uint32_t *d_n_words, uint32_t *d_models, uint16_t *d_off_values,
+                                 uint32_t *d_status, void *d_scratch, void *stream, double us[3]);
+/* A tiled image from pixels to coded planes: fri_hip_encode_image_tiled_symbols's chain with the fit (the inner plan needs its stream order), then K11 with
+ * FRI_HIP_RANS_EMPTY_OK over all n_tiles C planes, and only the coded planes come back - what fri_tiled_encode_from_coded (include/fri_emit.h) takes.
+ * value_params / width_params [n_tiles][C][3][6] as fri_hip_encode_image_tiled_symbols returns them; words uint32 [n_tiles C][word_stride], of which the first
+ * n_words[p] of plane p are written; n_words [n_tiles C]; models [n_tiles C][10][4]; off_values uint16 [n_tiles C][10][1024], of which the first n_off of a
+ * context are written; status [n_tiles C][4]. The library codes into a buffer of its own with room for 8 bits per symbol and, when a plane reports
+ * FRI_HIP_RANS_TOO_SMALL, runs K11 once more with n_symbols + 20 words per plane, the hard upper bound. Returns FRI_HIP_OK when every plane's bits are 0;
+ * FRI_HIP_ERR_OUT_OF_RANGE when a plane needs more than the caller's word_stride (its n_words says how much; its words are not written), when the fit
+ * reports coefficients out of range or when a plane has an out-of-alphabet symbol; FRI_HIP_ERR_INVALID_ARGUMENT with the status filled when a plane is refused
+ * for another reason. Synchronous. */
+int fri_hip_encode_image_tiled_coded(fri_hip_plan_tiled *p, const uint8_t *pixels, const int32_t qmatrix[32], float *value_params, float *width_params, uint32_t *words,
+                                     size_t word_stride, uint32_t *n_words, uint32_t *models, uint16_t *off_values, uint32_t *status);
+
 /* ---- timing helper ---------------------------------------------------------------------------- */
 /* Runs the forward kernel `iters` times on `stream` bracketed by HIP events recorded on that same
  * stream and returns the mean kernel-to-kernel time per launch in microseconds (bench.py uses it
