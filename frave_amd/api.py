@@ -43,6 +43,7 @@ SYMBOLS = [
     "fri_hip_measure_distortion_tiled_dev", "fri_hip_estimate_size_tiled_dev", "fri_hip_estimate_size_tiled", "fri_hip_search_quality_tiled", "fri_hip_search_quality_tiled_dev",
     "fri_hip_search_quality_ssim_tiled", "fri_hip_search_quality_ssim_tiled_dev", "fri_hip_search_quality_for_size_tiled", "fri_hip_search_quality_for_size_tiled_dev",
     "fri_hip_rans_scratch_bytes", "fri_hip_rans_encode_planes_dev", "fri_hip_rans_time_planes_dev", "fri_hip_encode_image_tiled_coded",
+    "fri_hip_plan_tiled_region", "fri_hip_merge_tiles_region_dev", "fri_hip_decode_region_tiled_dev", "fri_hip_decode_region_tiled",
 ]
 RANS_EMPTY_OK = 1  # FRI_HIP_RANS_EMPTY_OK: `flags` of fri_hip_rans_encode_planes_dev - a context without counts is coded (the emitter's FRI_EMIT_EMPTY_OK)
 RANS_TOO_SMALL, RANS_BAD_MODEL, RANS_ZERO_FREQ, RANS_BAD_BUCKET = 1, 2, 4, 8  # bits of a plane's status word (include/fri_hip.h)
@@ -223,6 +224,10 @@ def load_library():
     L.fri_hip_encode_symbols_tiled_dev.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
     L.fri_hip_encode_image_tiled_symbols.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
     L.fri_hip_decode_image_tiled.argtypes = [vp, vp, vp, vp]
+    L.fri_hip_plan_tiled_region.argtypes = [vp, u32, u32, u32, u32, vp]
+    L.fri_hip_merge_tiles_region_dev.argtypes = [vp, vp, u32, u32, u32, u32, vp, vp]
+    L.fri_hip_decode_region_tiled_dev.argtypes = [vp, vp, vp, u32, u32, u32, u32, vp, vp]
+    L.fri_hip_decode_region_tiled.argtypes = [vp, vp, vp, u32, u32, u32, u32, vp]
     L.fri_hip_measure_distortion_tiled_dev.argtypes = [vp, vp, vp, vp, vp]
     L.fri_hip_estimate_size_tiled_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.fri_hip_estimate_size_tiled.argtypes = [vp, vp, vp, vp, vp]
@@ -1136,6 +1141,33 @@ class PlanTiled:
         assert co.size == self.coef_count
         out = np.empty(self.pixel_bytes, np.uint8)
         _check(load_library().fri_hip_decode_image_tiled(self._h, _p(co), _p(_q(qmatrix)), _p(out)), "fri_hip_decode_image_tiled", self.ctx)
+        return out
+
+    # ---- region decode: only the tiles a rectangle touches -------------------------------------------
+    def region_tiles(self, x, y, w, h):
+        """fri_hip_plan_tiled_region: (i0, j0, ni, nj), the sub-grid of tiles the region x, y, w, h (image pixels) touches; sub-tile b ni + a is tile
+        (j0 + b) nx + (i0 + a). Works on a host-only plan. FriHipError (-1) for an empty region or one that leaves the image."""
+        out = np.zeros(4, np.uint32)
+        _check(load_library().fri_hip_plan_tiled_region(self._h, x, y, w, h, _p(out)), "fri_hip_plan_tiled_region", self.ctx)
+        return tuple(int(v) for v in out)
+
+    def merge_tiles_region_dev(self, d_tiles, x, y, w, h, d_region, stream=0):
+        """fri_hip_merge_tiles_region_dev: the sub-grid's tile raster [nj ni][tile_h][tile_w][C] -> the region raster [h][w][C]; only enqueues."""
+        _check(load_library().fri_hip_merge_tiles_region_dev(self._h, d_tiles, x, y, w, h, d_region, stream), "fri_hip_merge_tiles_region_dev", self.ctx)
+
+    def decode_region_tiled_dev(self, d_coefs, x, y, w, h, d_region, qmatrix=None, stream=0):
+        """fri_hip_decode_region_tiled_dev: d_coefs int32 [nj ni][C][F][512] -> d_region uint8 [h][w][C], device pointers: the inverse kernel over the touched tiles
+        into the plan's tile buffer, then the region kernel. Refuses a capturing stream."""
+        _check(load_library().fri_hip_decode_region_tiled_dev(self._h, d_coefs, _p(_q(qmatrix)), x, y, w, h, d_region, stream), "fri_hip_decode_region_tiled_dev", self.ctx)
+
+    def decode_region_tiled(self, coefs, x, y, w, h, qmatrix=None):
+        """fri_hip_decode_region_tiled: coefs int32 [nj ni][C][F][512] (what emit.tiled_decode_region returns) -> pixels uint8 [h * w * C]: the crop
+        [y : y + h, x : x + w] of what decode_image_tiled returns for the same file."""
+        _, _, ni, nj = self.region_tiles(x, y, w, h)
+        co = np.ascontiguousarray(coefs, np.int32).reshape(-1)
+        assert co.size == ni * nj * self.channels * self.num_cells * 512
+        out = np.empty(w * h * self.channels, np.uint8)
+        _check(load_library().fri_hip_decode_region_tiled(self._h, _p(co), _p(_q(qmatrix)), x, y, w, h, _p(out)), "fri_hip_decode_region_tiled", self.ctx)
         return out
 
     # ---- the measure, the size estimate and the searches over tiles ----------------------------------

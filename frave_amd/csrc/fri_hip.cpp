@@ -2710,6 +2710,7 @@ struct fri_hip_plan_tiled {
     Grown<uint32_t> rans_counts;      // ... n_words [n_tiles C], then status [n_tiles C][4], then models [n_tiles C][10][4]
     Grown<uint16_t> rans_off;         // ... [n_tiles C][10][1024]
     Grown<uint8_t> rans_scratch;      // ... and its scratch
+    Grown<uint8_t> region;            // fri_hip_decode_region_tiled: the region raster [h][w][C]
     size_t n_tiles() const { return (size_t)nx * ny; }
     size_t raster_bytes() const { return (size_t)width * height * channels; }
     size_t tile_bytes() const { return (size_t)tile_w * tile_h * channels; }
@@ -2895,6 +2896,55 @@ int fri_hip_decode_image_tiled(fri_hip_plan_tiled *p, const int32_t *coefs, cons
     if ((rc = fri_hip_inverse_transform_batch_dev(p->tile.get(), (uint32_t)n, p->coefs, image, qmatrix, p->tiles, p->tile_bytes(), nullptr))) return rc;
     HIP_TRY(c, launch_merge_tiles(p->tiles, p->width, p->height, p->channels, p->tile_w, p->tile_h, p->raster, nullptr));
     HIP_TRY(c, hipMemcpy(pixels, p->raster, p->raster_bytes(), hipMemcpyDeviceToHost));
+    return FRI_HIP_OK;
+}
+
+/* ---- region decode: only the tiles a rectangle touches ---- */
+int fri_hip_plan_tiled_region(const fri_hip_plan_tiled *p, uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint32_t out[4]) {
+    if (!p || !out || !w || !h || (uint64_t)x + w > p->width || (uint64_t)y + h > p->height) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    out[0] = x / p->tile_w, out[1] = y / p->tile_h;
+    out[2] = (uint32_t)(((uint64_t)x + w - 1) / p->tile_w) - out[0] + 1, out[3] = (uint32_t)(((uint64_t)y + h - 1) / p->tile_h) - out[1] + 1;
+    return FRI_HIP_OK;
+}
+
+int fri_hip_merge_tiles_region_dev(fri_hip_plan_tiled *p, const uint8_t *d_tiles, uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint8_t *d_region, void *stream) {
+    uint32_t range[4];
+    if (!p || !d_tiles || !d_region || fri_hip_plan_tiled_region(p, x, y, w, h, range)) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    if (int rc = need_device_tiled(p)) return rc;
+    HIP_TRY(p->ctx, launch_merge_tiles_region(d_tiles, p->width, p->height, p->channels, p->tile_w, p->tile_h, x, y, w, h, d_region, (hipStream_t)stream));
+    return FRI_HIP_OK;
+}
+
+int fri_hip_decode_region_tiled_dev(fri_hip_plan_tiled *p, const int32_t *d_coefs, const int32_t qmatrix[32], uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint8_t *d_region,
+                                    void *stream) {
+    uint32_t range[4];
+    if (!p || !d_coefs || !qmatrix || !d_region || fri_hip_plan_tiled_region(p, x, y, w, h, range)) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    if (int rc = need_device_tiled(p)) return rc;
+    fri_hip_ctx *c = p->ctx;
+    const hipStream_t s = (hipStream_t)stream;
+    QMatrix q;
+    if (int rc = check_q(qmatrix, q)) return rc;
+    if (int rc = refuse_capture(p->tile.get(), s, "fri_hip_decode_region_tiled_dev grows the plan's tile buffer: it cannot be captured into a HIP graph")) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t n = (size_t)range[2] * range[3]; // the touched tiles: the buffer grows to the region's size, never to the image's
+    if (int rc = grow(c, p->tiles, n * p->tile_bytes())) return rc;
+    if (int rc = fri_hip_inverse_transform_batch_dev(p->tile.get(), (uint32_t)n, d_coefs, fri_hip_plan_coef_count(p->tile.get()), qmatrix, p->tiles, p->tile_bytes(), stream)) return rc;
+    HIP_TRY(c, launch_merge_tiles_region(p->tiles, p->width, p->height, p->channels, p->tile_w, p->tile_h, x, y, w, h, d_region, s));
+    return FRI_HIP_OK;
+}
+
+int fri_hip_decode_region_tiled(fri_hip_plan_tiled *p, const int32_t *coefs, const int32_t qmatrix[32], uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint8_t *pixels) {
+    uint32_t range[4];
+    if (!p || !coefs || !qmatrix || !pixels || fri_hip_plan_tiled_region(p, x, y, w, h, range)) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    if (int rc = need_device_tiled(p)) return rc;
+    fri_hip_ctx *c = p->ctx;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t n = (size_t)range[2] * range[3], image = fri_hip_plan_coef_count(p->tile.get()), bytes = (size_t)w * h * p->channels;
+    int rc;
+    if ((rc = grow(c, p->coefs, n * image)) || (rc = grow(c, p->region, bytes))) return rc;
+    HIP_TRY(c, hipMemcpy(p->coefs, coefs, n * image * sizeof(int32_t), hipMemcpyHostToDevice));
+    if ((rc = fri_hip_decode_region_tiled_dev(p, p->coefs, qmatrix, x, y, w, h, p->region, nullptr))) return rc;
+    HIP_TRY(c, hipMemcpy(pixels, p->region, bytes, hipMemcpyDeviceToHost));
     return FRI_HIP_OK;
 }
 

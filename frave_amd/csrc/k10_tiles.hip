@@ -4,6 +4,9 @@
 // tile(t, y, x, c) = image(min(j tile_h + y, H - 1), min(i tile_w + x, W - 1), c). merge_tiles_kernel<C>: the tile raster -> the image, the pixels with
 // j tile_h + y < H and i tile_w + x < W. measure_tiles_kernel<C>: the merge's pixels compared with a reference raster instead of stored (the tiled searches' PSNR).
 //
+// merge_tiles_region_kernel<C>: a sub-grid's tile raster [nj ni][tile_h][tile_w][C] -> the region raster [h][w][C] (include/fri_emit.h, "Region decode", has the
+// arithmetic); region pixel (ry, rx) is image pixel (y + ry, x + rx), never a replicated one.
+//
 // Neither raster has a row pitch. The tile raster is a flat run of ny nx tile_h rows of tile_w C bytes, and a lane owns one strip of 16 consecutive bytes of one
 // such row. Away from the clamped edge those are 16 consecutive bytes of one image row: one 16-byte load and one 16-byte store, the target's unaligned global
 // accesses (the compiler is told the alignment is 1), so both buffers start at any byte. A strip that reaches past the image row (the replicated edge) and a
@@ -94,6 +97,44 @@ __global__ void __launch_bounds__(kTileThreads) merge_tiles_kernel(const TileArg
         for (uint32_t k = 0; k < st.n; k++) {
             const uint32_t at = st.x0_bytes + st.b0 + k;
             if (at < image_row_bytes) dst_row[at] = src[k];
+        }
+    }
+}
+
+// merge_tiles_region_kernel<C>: the work follows the region, not the tiles. The region raster is h rows of w C bytes and a lane owns 16 bytes of one such row. The
+// sub-grid is nj tile_h rows of ni tile_w C bytes, cut into tiles; the region's row ry is its row oy + ry and starts at its byte ox_bytes, where (ox_bytes / C, oy)
+// is the region's corner within the sub-grid's first tile. A strip whose 16 bytes lie in one tile row is one unaligned 16-byte load and one 16-byte store. One
+// that crosses a tile column (every strip when tile_w C < 16) and the row's last, partial strip go byte by byte, stepping into the next tile where the tile row
+// ends. Nothing outside the region is read for it or written: the sub-grid's other pixels, its replicated ones among them, are not touched.
+struct RegionArgs {
+    const uint8_t *in; // the sub-grid's tile raster
+    uint8_t *out;      // the region raster
+    uint32_t tile_h, ni;
+    uint32_t row_bytes;        // tile_w C
+    uint32_t ox_bytes, oy;     // (x - i0 tile_w) C, y - j0 tile_h
+    uint32_t region_row_bytes; // w C
+    uint32_t strips_per_row;   // ceil(region_row_bytes / 16)
+    uint32_t n_strips;         // h strips_per_row
+};
+
+template <uint32_t C>
+__global__ void __launch_bounds__(kTileThreads) merge_tiles_region_kernel(const RegionArgs p) {
+    const uint32_t g = blockIdx.x * kTileThreads + threadIdx.x;
+    if (g >= p.n_strips) return;
+    const uint32_t ry = g / p.strips_per_row, b0 = (g - ry * p.strips_per_row) * kTileStrip;
+    const uint32_t n = min(kTileStrip, p.region_row_bytes - b0);
+    const uint32_t gy = p.oy + ry, b = gy / p.tile_h, y = gy - b * p.tile_h; // row y of the tiles of sub-grid row b
+    const uint32_t gx = p.ox_bytes + b0;                                     // the strip's first byte in the sub-grid's row: < ni row_bytes
+    uint32_t a = gx / p.row_bytes, xb = gx - a * p.row_bytes;                // byte xb of the row of tile (b, a)
+    const uint64_t tile_stride = (uint64_t)p.tile_h * p.row_bytes;
+    const uint8_t *src = p.in + ((uint64_t)b * p.ni + a) * tile_stride + (uint64_t)y * p.row_bytes;
+    uint8_t *dst = p.out + (uint64_t)ry * p.region_row_bytes + b0;
+    if (n == kTileStrip && xb + kTileStrip <= p.row_bytes) {
+        store_unaligned(dst, load_unaligned<u32x4>(src + xb));
+    } else { // the strip crosses a tile column, or is the row's last
+        for (uint32_t k = 0; k < n; k++) {
+            dst[k] = src[xb];
+            if (++xb == p.row_bytes) xb = 0, src += tile_stride; // the same row of the next tile
         }
     }
 }
@@ -230,6 +271,29 @@ hipError_t launch_merge_tiles(const uint8_t *tiles, uint32_t width, uint32_t hei
     p.in = tiles, p.out = image;
     if (channels == 3) hipLaunchKernelGGL(merge_tiles_kernel<3>, dim3(groups), dim3(kTileThreads), 0, stream, p);
     else hipLaunchKernelGGL(merge_tiles_kernel<1>, dim3(groups), dim3(kTileThreads), 0, stream, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_merge_tiles_region(const uint8_t *tiles, uint32_t width, uint32_t height, uint32_t channels, uint32_t tile_w, uint32_t tile_h, uint32_t x, uint32_t y, uint32_t w,
+                                     uint32_t h, uint8_t *region, hipStream_t stream) {
+    TileArgs whole{};
+    uint32_t groups = 0;
+    if (!region || !tiles || !grid_of(width, height, channels, tile_w, tile_h, whole, groups)) return hipErrorInvalidValue; // (the shape's limits: a row's bytes fit 31 bits)
+    if (!w || !h || (uint64_t)x + w > width || (uint64_t)y + h > height) return hipErrorInvalidValue;
+    const uint32_t i0 = x / tile_w, j0 = y / tile_h;
+    RegionArgs p{};
+    p.in = tiles, p.out = region;
+    p.tile_h = tile_h, p.ni = (x + w - 1) / tile_w - i0 + 1;
+    p.row_bytes = whole.row_bytes;
+    p.ox_bytes = (x - i0 * tile_w) * channels, p.oy = y - j0 * tile_h;
+    p.region_row_bytes = w * channels;
+    p.strips_per_row = (p.region_row_bytes + kTileStrip - 1) / kTileStrip;
+    const uint64_t n_strips = (uint64_t)h * p.strips_per_row;
+    if (n_strips > 0xFFFFFFFFull - kTileThreads) return hipErrorInvalidValue; // (one u32 strip index per lane)
+    p.n_strips = (uint32_t)n_strips;
+    groups = (uint32_t)((n_strips + kTileThreads - 1) / kTileThreads);
+    if (channels == 3) hipLaunchKernelGGL(merge_tiles_region_kernel<3>, dim3(groups), dim3(kTileThreads), 0, stream, p);
+    else hipLaunchKernelGGL(merge_tiles_region_kernel<1>, dim3(groups), dim3(kTileThreads), 0, stream, p);
     return hipGetLastError();
 }
 

@@ -186,6 +186,10 @@ hipError_t launch_merge_rgba(const uint8_t *rgb, const uint8_t *a, uint32_t widt
 // [ny nx][tile_h][tile_w][C] with edge replication. Merge: the tile raster's in-image pixels back. C is 1 or 3; any shape, any pointer alignment.
 hipError_t launch_split_tiles(const uint8_t *image, uint32_t width, uint32_t height, uint32_t channels, uint32_t tile_w, uint32_t tile_h, uint8_t *tiles, hipStream_t stream);
 hipError_t launch_merge_tiles(const uint8_t *tiles, uint32_t width, uint32_t height, uint32_t channels, uint32_t tile_w, uint32_t tile_h, uint8_t *image, hipStream_t stream);
+// Region merge: the tile raster of the sub-grid a region touches, [nj ni][tile_h][tile_w][C] (include/fri_emit.h, "Region decode") -> the region raster [h][w][C]. The
+// region must lie in the width x height image (hipErrorInvalidValue otherwise).
+hipError_t launch_merge_tiles_region(const uint8_t *tiles, uint32_t width, uint32_t height, uint32_t channels, uint32_t tile_w, uint32_t tile_h, uint32_t x, uint32_t y, uint32_t w,
+                                     uint32_t h, uint8_t *region, hipStream_t stream);
 // Measure: the merge's walk with nothing stored - the tile raster's in-image pixels against `reference` [H][W][C]: sums[2 c] += the sum of squared differences of
 // channel c, sums[2 c + 1] = max(.., largest absolute difference), sums[2 C] += pixels (W H in all). The caller zeroes sums with launch_clear_sums.
 hipError_t launch_measure_tiles(const uint8_t *tiles, uint32_t width, uint32_t height, uint32_t channels, uint32_t tile_w, uint32_t tile_h, const uint8_t *reference,

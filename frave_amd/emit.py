@@ -51,6 +51,8 @@ def load_library():
         L.fri_coded_encode_image.argtypes = [u32, u32, u32, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, sz, vp, C.c_char_p, sz]
         L.fri_tiled_info.argtypes = [vp, sz, vp]
         L.fri_tiled_decode.argtypes = [vp, sz, u32, vp, vp, sz, C.c_char_p, sz]
+        L.fri_tiled_region_tiles.argtypes = [u32, u32, u32, u32, u32, u32, u32, u32, vp]
+        L.fri_tiled_decode_region.argtypes = [vp, sz, u32, u32, u32, u32, u32, vp, vp, vp, sz, C.c_char_p, sz]
         _lib = L
     return _lib
 
@@ -338,3 +340,31 @@ def tiled_decode(frv, threads=0):
     if rc != 0:
         raise EmitError(err.value.decode() or f"fri_tiled_decode: {rc}")
     return ti, coefs
+
+
+def tiled_region_tiles(width, height, tile_w, tile_h, x, y, w, h):
+    """fri_tiled_region_tiles: (i0, j0, ni, nj), the sub-grid of tiles the region x, y, w, h (image pixels) touches. EmitError for a zero size or a region that
+    leaves the image."""
+    out = np.zeros(4, np.uint32)
+    rc = load_library().fri_tiled_region_tiles(width, height, tile_w, tile_h, x, y, w, h, _p(out))
+    if rc != 0:
+        raise EmitError(f"fri_tiled_region_tiles: {rc}")
+    return tuple(int(v) for v in out)
+
+
+def tiled_decode_region(frv, x, y, w, h, threads=0):
+    """fri_tiled_decode_region: (TiledInfo, (i0, j0, ni, nj), coefs int32 [nj ni][C][F][512]) - what PlanTiled.decode_region_tiled takes. The file is checked as
+    tiled_decode checks it; only the tiles the region touches are decoded, and damage inside the body of an untouched tile is not looked at."""
+    data = np.frombuffer(frv, np.uint8)
+    info, tiles = np.zeros(8, np.uint32), np.zeros(4, np.uint32)
+    err = C.create_string_buffer(256)
+    L = load_library()
+    rc = L.fri_tiled_decode_region(_p(data), data.size, threads, x, y, w, h, _p(info), _p(tiles), None, 0, err, 256)
+    if rc != -3:
+        raise EmitError(err.value.decode() or f"fri_tiled_decode_region: {rc}")
+    ti = _tiled_info(info)
+    coefs = np.empty((int(tiles[2]) * int(tiles[3]), ti[6], ti[7], 512), np.int32)
+    rc = L.fri_tiled_decode_region(_p(data), data.size, threads, x, y, w, h, _p(info), _p(tiles), _p(coefs), coefs.size, err, 256)
+    if rc != 0:
+        raise EmitError(err.value.decode() or f"fri_tiled_decode_region: {rc}")
+    return ti, tuple(int(v) for v in tiles), coefs

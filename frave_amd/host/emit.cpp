@@ -1001,9 +1001,10 @@ unsigned tile_workers(unsigned threads, size_t n_tiles) {
     return (unsigned)std::max<size_t>(1, std::min<size_t>(threads, n_tiles));
 }
 
-// work(t) for every tile on `threads` workers that take the next tile from a shared counter; the error of the lowest failing tile, whatever the thread count
-template <typename Work>
-std::string for_each_tile(size_t n_tiles, unsigned threads, Work &&work) {
+// work(t) for every tile on `threads` workers that take the next tile from a shared counter; the error of the lowest failing tile, whatever the thread count,
+// named name(t): the tile's index in the file's grid
+template <typename Work, typename Name>
+std::string for_each_tile(size_t n_tiles, unsigned threads, Work &&work, Name &&name) {
     std::vector<std::string> errs(n_tiles);
     std::atomic<size_t> next{0};
     auto run = [&] {
@@ -1015,8 +1016,12 @@ std::string for_each_tile(size_t n_tiles, unsigned threads, Work &&work) {
     run();
     for (std::thread &w : workers) w.join();
     for (size_t t = 0; t < n_tiles; t++)
-        if (!errs[t].empty()) return "tile " + std::to_string(t) + ": " + errs[t];
+        if (!errs[t].empty()) return "tile " + std::to_string(name(t)) + ": " + errs[t];
     return "";
+}
+template <typename Work>
+std::string for_each_tile(size_t n_tiles, unsigned threads, Work &&work) {
+    return for_each_tile(n_tiles, threads, work, [](size_t t) { return t; });
 }
 } // namespace
 
@@ -1161,21 +1166,36 @@ std::string parse_tiled(const uint8_t *b, size_t len, TiledInfo &info, std::vect
     return "";
 }
 
-std::string decode_tiled(const uint8_t *b, size_t len, unsigned threads, TiledInfo &info, int32_t *coefs, size_t coef_cap, bool &too_small) {
+bool region_tiles(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, const Region &r, TileRange &out) {
+    if (!width || !height || !tile_w || !tile_h || !r.w || !r.h) return false;
+    if ((uint64_t)r.x + r.w > width || (uint64_t)r.y + r.h > height) return false;
+    out.i0 = r.x / tile_w, out.j0 = r.y / tile_h;
+    out.ni = (uint32_t)(((uint64_t)r.x + r.w - 1) / tile_w) - out.i0 + 1;
+    out.nj = (uint32_t)(((uint64_t)r.y + r.h - 1) / tile_h) - out.j0 + 1;
+    return true;
+}
+
+std::string decode_tiled(const uint8_t *b, size_t len, unsigned threads, TiledInfo &info, int32_t *coefs, size_t coef_cap, bool &too_small, const Region *region,
+                         TileRange *range) {
     too_small = false;
     std::vector<uint64_t> offset;
     std::string e = parse_tiled(b, len, info, offset);
     if (!e.empty()) return e;
+    TileRange tr{0, 0, info.nx, info.ny}; // without a region: the whole grid
+    if (region && !region_tiles(info.width, info.height, info.tile_w, info.tile_h, *region, tr)) return "invalid region";
+    if (range) *range = tr;
     fri::Geometry g; // one geometry and one symbol order for all tiles
     e = fri::build_geometry(info.tile_w, info.tile_h, info.channels, fri::TilingParams{}, g);
     if (!e.empty()) return e;
-    const size_t F = g.centers.size(), plane = F * kNodes, n_tiles = (size_t)info.nx * info.ny;
+    const size_t F = g.centers.size(), plane = F * kNodes, n_tiles = (size_t)tr.ni * tr.nj;
+    const auto file_tile = [&](size_t s) { return ((size_t)tr.j0 + s / tr.ni) * info.nx + tr.i0 + s % tr.ni; }; // sub-tile s of the range in the file's grid
     info.n_cells = (uint32_t)F;
     if (!coefs || coef_cap < n_tiles * info.channels * plane) return too_small = true, "";
     std::vector<int32_t> centers(F * 2);
     for (size_t c = 0; c < F; c++) centers[2 * c] = g.centers[c].x, centers[2 * c + 1] = g.centers[c].y;
     const auto order = shared_symbol_order(centers.data(), (uint32_t)F);
-    return for_each_tile(n_tiles, threads, [&](size_t t) -> std::string {
+    return for_each_tile(n_tiles, threads, [&](size_t s) -> std::string {
+        const size_t t = file_tile(s);
         const uint8_t *p = b + offset[t];
         ParsedImage img;
         const std::string de = deserialize(std::vector<uint8_t>(p, b + offset[t + 1]), img);
@@ -1185,11 +1205,11 @@ std::string decode_tiled(const uint8_t *b, size_t len, unsigned threads, TiledIn
             for (const AnsContext &a : c.contexts)
                 if (a.max_freq_bits == 0) return "Malformed image bytes"; // fewer than ten EHD segments
         for (uint32_t ch = 0; ch < info.channels; ch++) {
-            const std::string ce = decode_channel(g, *order, img.channels[ch], img.params[ch], coefs + (t * info.channels + ch) * plane);
+            const std::string ce = decode_channel(g, *order, img.channels[ch], img.params[ch], coefs + (s * info.channels + ch) * plane);
             if (!ce.empty()) return "channel " + std::to_string(ch) + ": " + ce;
         }
         return "";
-    });
+    }, file_tile);
 }
 
 } // namespace emit

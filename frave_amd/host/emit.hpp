@@ -220,8 +220,21 @@ std::string encode_image_from_coded(uint32_t width, uint32_t height, uint32_t ch
                                     std::vector<uint8_t> &out);
 // Header, table and every payload's 16-byte header; "Malformed tiled image" for anything that does not hold together. offset: [n_tiles + 1].
 std::string parse_tiled(const uint8_t *frv, size_t len, TiledInfo &info, std::vector<uint64_t> &offset);
+// A region x, y, w, h in image pixels and the sub-grid of tiles it touches (include/fri_emit.h, "Region decode", has the arithmetic): ni columns from i0, nj rows
+// from j0; sub-tile s = b ni + a is tile (j0 + b) nx + (i0 + a) of the file.
+struct Region {
+    uint32_t x = 0, y = 0, w = 0, h = 0;
+};
+struct TileRange {
+    uint32_t i0 = 0, j0 = 0, ni = 0, nj = 0;
+};
+// false for a zero size or a region that leaves the width x height image (compared in 64 bits)
+bool region_tiles(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, const Region &r, TileRange &out);
 // coefs [n_tiles][channels][F][512]. too_small: coefs is NULL or coef_cap (elements) does not hold them - `info` is filled, nothing is decoded.
-std::string decode_tiled(const uint8_t *frv, size_t len, unsigned threads, TiledInfo &info, int32_t *coefs, size_t coef_cap, bool &too_small);
+// With a region: the file is checked as without one, then only the tiles the region touches are decoded, coefs [nj ni][channels][F][512] in the sub-grid's order;
+// `range` is filled whenever `info` is. "invalid region" for a region region_tiles refuses. A tile's error names its index in the file's grid.
+std::string decode_tiled(const uint8_t *frv, size_t len, unsigned threads, TiledInfo &info, int32_t *coefs, size_t coef_cap, bool &too_small, const Region *region = nullptr,
+                         TileRange *range = nullptr);
 
 } // namespace emit
 } // namespace libfri

@@ -302,5 +302,27 @@ int fri_tiled_decode(const uint8_t *frv, size_t len, uint32_t threads, uint32_t 
     return too_small ? -3 : 0;
 }
 
+int fri_tiled_region_tiles(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint32_t out[4]) {
+    TileRange r;
+    if (!out || !region_tiles(width, height, tile_w, tile_h, Region{x, y, w, h}, r)) return -1;
+    out[0] = r.i0, out[1] = r.j0, out[2] = r.ni, out[3] = r.nj;
+    return 0;
+}
+
+int fri_tiled_decode_region(const uint8_t *frv, size_t len, uint32_t threads, uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint32_t info[8], uint32_t tiles[4], int32_t *coefs,
+                            size_t coef_cap, char *err, size_t err_cap) {
+    if (!frv || !info || !tiles) return fail(err, err_cap, "invalid argument");
+    TiledInfo t;
+    TileRange r;
+    const Region region{x, y, w, h};
+    bool too_small = false;
+    const std::string e = decode_tiled(frv, len, threads, t, coefs, coef_cap, too_small, &region, &r);
+    if (e == "invalid region") return fail(err, err_cap, e);
+    if (!e.empty()) return fail(err, err_cap, e, -2);
+    fill_tiled_info(t, info);
+    tiles[0] = r.i0, tiles[1] = r.j0, tiles[2] = r.ni, tiles[3] = r.nj;
+    return too_small ? -3 : 0;
+}
+
 #pragma GCC visibility pop
 } // extern "C"

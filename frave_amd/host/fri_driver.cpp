@@ -24,9 +24,11 @@
 //                                                            (fri_hip_search_quality*_tiled): the target holds for the file that is written
 //                                                            --device-rans (with --tile-size): the rANS coder runs on the device too (K11), the host writes the
 //                                                            container around the coded planes - the same file
-//   fri_driver decode-file <in.frv> <out.pgm|.ppm|.bmp|.pam>  (.pam for a file with an alpha plane, and for no other) container -> rANS / context decoding on the host -> dequantisation + inverse
+//   fri_driver decode-file <in.frv> <out.pgm|.ppm|.bmp|.pam> [--region X,Y,W,H]  (.pam for a file with an alpha plane, and for no other) container -> rANS / context decoding on the host -> dequantisation + inverse
 //                                                            transform on the device (fri-cli decode, crates/fri-cli/src/commands/decode.rs); a flagged file
 //                                                            comes back as RGB, a lossy file with its quality's matrix and the midpoint dequantiser
+//                                                            --region X,Y,W,H: only that rectangle of the image (FRIDecoder::decode_region) - of a `frit` file only
+//                                                            the tiles it touches are decoded; a `frif` file is decoded whole and cropped; no 4:2:0 or alpha file
 //   fri_driver batch <width> <height> <channels> <n_images> [--gpus N]
 //                                                            BASELINE config 3: host batch with H2D / kernel / D2H overlap; with --gpus N
 //                                                            BASELINE config 4: the batch sharded over N GPUs of this node (image i -> GPU i mod N,
@@ -602,7 +604,17 @@ int main(int argc, char **argv) {
             std::fprintf(stderr, "cannot open %s\n", argv[2]);
             return 1;
         }
-        auto img = libfri::FRIDecoder().decode(bytes);
+        bool has_region = false;
+        unsigned rx = 0, ry = 0, rw = 0, rh = 0;
+        for (int i = 4; i < argc; i++) {
+            char tail = 0;
+            if (std::string(argv[i]) == "--region" && i + 1 < argc && std::sscanf(argv[i + 1], "%u,%u,%u,%u%c", &rx, &ry, &rw, &rh, &tail) == 4) has_region = true, i++;
+            else {
+                std::fprintf(stderr, "decode-file: unknown or incomplete option %s (--region X,Y,W,H)\n", argv[i]);
+                return 2;
+            }
+        }
+        auto img = has_region ? libfri::FRIDecoder().decode_region(bytes, rx, ry, rw, rh) : libfri::FRIDecoder().decode(bytes);
         if (!img.ok) {
             std::fprintf(stderr, "%s\n", img.error.c_str());
             return 1;
@@ -644,7 +656,7 @@ int main(int argc, char **argv) {
         return 0;
     }
     if (argc < 5) {
-        std::fprintf(stderr, "usage: %s roundtrip|encode|batch|batch-frv <width> <height> <channels> [n_images | out.frv]\n       %s encode-file <in.pgm|in.ppm|in.bmp|in.pam> <out.frv> [--rct | [--ycbcr | --420] (--quality Q | --psnr DB | --ssim S | --size BYTES | --bpp B)] [--clean-alpha] [--tile-size T [--device-rans]]\n       %s decode-file <in.frv> <out.pgm|out.ppm|out.bmp|out.pam>\n", argv[0], argv[0], argv[0]);
+        std::fprintf(stderr, "usage: %s roundtrip|encode|batch|batch-frv <width> <height> <channels> [n_images | out.frv]\n       %s encode-file <in.pgm|in.ppm|in.bmp|in.pam> <out.frv> [--rct | [--ycbcr | --420] (--quality Q | --psnr DB | --ssim S | --size BYTES | --bpp B)] [--clean-alpha] [--tile-size T [--device-rans]]\n       %s decode-file <in.frv> <out.pgm|out.ppm|out.bmp|out.pam> [--region X,Y,W,H]\n", argv[0], argv[0], argv[0]);
         return 2;
     }
     const std::string cmd = argv[1];

@@ -472,19 +472,21 @@ struct TiledPlanDelete {
 };
 using TiledPlan = std::unique_ptr<fri_hip_plan_tiled, TiledPlanDelete>;
 
-// a `frit` file: the tiles' planes from the emitter's workers, then the inverse kernel over all tiles and the merge
-Result<RasterImage> decode_tiled_bytes(const std::vector<uint8_t> &data, const EncoderOpts &opts) {
+// a `frit` file: the tiles' planes from the emitter's workers, then the inverse kernel over all tiles and the merge. With a region: only the tiles it touches, on
+// both sides (emit::decode_tiled with the region, fri_hip_decode_region_tiled), and the raster is the region's.
+Result<RasterImage> decode_tiled_bytes(const std::vector<uint8_t> &data, const EncoderOpts &opts, const emit::Region *region = nullptr) {
     Result<RasterImage> r;
     auto fail = [&](const std::string &why) {
         r.error = "Failed to decode: " + why;
         return r;
     };
     emit::TiledInfo ti;
+    emit::TileRange range;
     bool too_small = false;
-    std::string e = emit::decode_tiled(data.data(), data.size(), 0, ti, nullptr, 0, too_small); // header, table, geometry
+    std::string e = emit::decode_tiled(data.data(), data.size(), 0, ti, nullptr, 0, too_small, region, &range); // header, table, geometry
     if (!e.empty()) return fail(e);
-    std::vector<int32_t> coefs((size_t)ti.nx * ti.ny * ti.channels * ti.n_cells * FRI_HIP_CELL_SIZE);
-    e = emit::decode_tiled(data.data(), data.size(), 0, ti, coefs.data(), coefs.size(), too_small);
+    std::vector<int32_t> coefs((size_t)range.ni * range.nj * ti.channels * ti.n_cells * FRI_HIP_CELL_SIZE);
+    e = emit::decode_tiled(data.data(), data.size(), 0, ti, coefs.data(), coefs.size(), too_small, region, &range);
     if (!e.empty() || too_small) return fail(e.empty() ? "coefficient array does not match the tile geometry" : e);
     Device dev(opts.device);
     if (!dev.ok()) return fail(dev.error());
@@ -498,14 +500,47 @@ Result<RasterImage> decode_tiled_bytes(const std::vector<uint8_t> &data, const E
     std::array<int32_t, 32> qm = opts.quantization_matrix;
     if (ti.quality && fri_hip_quality_matrix((int)ti.quality, qm.data()) != FRI_HIP_OK) return fail("invalid quality");
     int rc = fri_hip_plan_set_dequantiser(tile, ti.quality ? FRI_HIP_DEQUANT_MIDPOINT : FRI_HIP_DEQUANT_REFERENCE);
-    r.value.metadata = ImageMetadata{ti.height, ti.width, ti.channels == 1 ? ColorSpace::Luma : ColorSpace::RGB};
-    r.value.data.resize((size_t)ti.width * ti.height * ti.channels);
-    if (rc == FRI_HIP_OK) rc = fri_hip_decode_image_tiled(raw, coefs.data(), qm.data(), r.value.data.data());
+    const uint32_t out_w = region ? region->w : ti.width, out_h = region ? region->h : ti.height;
+    r.value.metadata = ImageMetadata{out_h, out_w, ti.channels == 1 ? ColorSpace::Luma : ColorSpace::RGB};
+    r.value.data.resize((size_t)out_w * out_h * ti.channels);
+    if (rc == FRI_HIP_OK)
+        rc = region ? fri_hip_decode_region_tiled(raw, coefs.data(), qm.data(), region->x, region->y, region->w, region->h, r.value.data.data())
+                    : fri_hip_decode_image_tiled(raw, coefs.data(), qm.data(), r.value.data.data());
     if (rc != FRI_HIP_OK) return fail(dev.describe(rc));
     r.ok = true;
     return r;
 }
 } // namespace
+
+Result<RasterImage> FRIDecoder::decode_region(const std::vector<uint8_t> &data, uint32_t x, uint32_t y, uint32_t w, uint32_t h, const EncoderOpts &opts) {
+    const emit::Region region{x, y, w, h};
+    if (data.size() >= 4 && std::memcmp(data.data(), "frit", 4) == 0) return decode_tiled_bytes(data, opts, &region);
+    // an ordinary file has no tiles to choose from: all of it is decoded and the region cut out on the host
+    Result<RasterImage> r;
+    auto c = stages::serialize::decode(data);
+    if (!c.ok) {
+        r.error = "Failed to decode: " + c.error;
+        return r;
+    }
+    if (c.value.metadata.s420 || c.value.metadata.alpha) {
+        r.error = "Failed to decode: a region of a 4:2:0 or alpha file is not supported";
+        return r;
+    }
+    if (!w || !h || (uint64_t)x + w > c.value.metadata.width || (uint64_t)y + h > c.value.metadata.height) {
+        r.error = "Failed to decode: invalid region";
+        return r;
+    }
+    auto whole = decode(data, opts);
+    if (!whole.ok) return whole;
+    const size_t pixel = whole.value.data.size() / ((size_t)whole.value.metadata.width * whole.value.metadata.height);
+    r.value.metadata = whole.value.metadata;
+    r.value.metadata.width = w, r.value.metadata.height = h;
+    r.value.data.resize((size_t)w * h * pixel);
+    for (uint32_t ry = 0; ry < h; ry++)
+        std::memcpy(r.value.data.data() + (size_t)ry * w * pixel, whole.value.data.data() + (((size_t)y + ry) * whole.value.metadata.width + x) * pixel, (size_t)w * pixel);
+    r.ok = true;
+    return r;
+}
 
 Result<RasterImage> FRIDecoder::decode(const std::vector<uint8_t> &data, const EncoderOpts &opts) {
     if (data.size() >= 4 && std::memcmp(data.data(), "frit", 4) == 0) return decode_tiled_bytes(data, opts);

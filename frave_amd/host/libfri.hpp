@@ -295,6 +295,11 @@ class FRIDecoder { // decoder.rs:44-59
     // Container parsing and entropy decoding run on the host, dequantisation + inverse transform on the device. A tiled file (`frit`) is recognised by its magic:
     // fri_tiled_decode's workers, then fri_hip_decode_image_tiled.
     Result<RasterImage> decode(const std::vector<uint8_t> &data, const EncoderOpts &opts = EncoderOpts());
+    // The region x, y, w, h (image pixels; include/fri_emit.h, "Region decode") of the image `data` holds: the crop [y : y + h, x : x + w] of what decode returns,
+    // as a raster of w x h. A tiled file pays for the tiles the region touches and no others: fri_tiled_decode_region's workers, then
+    // fri_hip_decode_region_tiled. An ordinary `frif` file has no tiles: it is decoded whole and cropped on the host, which buys nothing and only makes the call
+    // work on any file. 4:2:0 and alpha files are refused.
+    Result<RasterImage> decode_region(const std::vector<uint8_t> &data, uint32_t x, uint32_t y, uint32_t w, uint32_t h, const EncoderOpts &opts = EncoderOpts());
     // from the WaveletTransform stage on
     Result<RasterImage> decode(const WaveletImage &image, const EncoderOpts &opts = EncoderOpts());
 };

@@ -72,7 +72,16 @@
  * for that tile's streams, histograms and parameters with FRI_EMIT_EMPTY_OK set. All tiles carry the same metadata word. 4:2:0 and alpha inside tiles are
  * refused, by the encoder (-1) and by the decoder ("Malformed tiled image"). fri_emit_decode_image does not know the magic: a `frit` file is "Invalid signature"
  * to it. The size of such a file is estimated from the tiles' histograms, without the coder, by fri_hip_estimate_size_tiled_dev (include/fri_hip.h), which knows
- * the rule of FRI_EMIT_EMPTY_OK. Out of scope: region (tile-range) decode. */
+ * the rule of FRI_EMIT_EMPTY_OK.
+ *
+ * Region decode (fri_tiled_region_tiles, fri_tiled_decode_region below; the device side is fri_hip_decode_region_tiled, include/fri_hip.h): the offset table and
+ * the independence of the tiles are what random access needs. A region is x, y, w, h in image pixels with w, h >= 1, x + w <= W and y + h <= H, compared in 64
+ * bits. The tiles it touches are a sub-grid of the file's grid:
+ *     i0 = x / tile_w                          j0 = y / tile_h
+ *     ni = (x + w - 1) / tile_w - i0 + 1       nj = (y + h - 1) / tile_h - j0 + 1
+ * stored row-major: sub-tile s = b ni + a is tile (j0 + b) nx + (i0 + a) of the file. The region raster is [h][w][C] without a pitch; its pixel (ry, rx) is image
+ * pixel (y + ry, x + rx), which is pixel (y + ry - j tile_h, x + rx - i tile_w) of tile (j, i): no replicated pixel is ever copied. By definition the region
+ * raster is the crop [y : y + h, x : x + w] of what fri_hip_decode_image_tiled returns for the same file. */
 #define FRI_EMIT_EMPTY_OK 0x2000u
 #define FRI_EMIT_RCT 0x100u
 #define FRI_EMIT_YCBCR 0x400u
@@ -169,6 +178,18 @@ int fri_tiled_info(const uint8_t *frv, size_t len, uint32_t info[8]);
  * returns "Malformed tiled image" (-2). Tiles are decoded on `threads` workers (0 as above) that share one geometry and one symbol order. Returns -3 with `info`
  * filled when coefs is NULL or coef_cap (in elements) is too small. */
 int fri_tiled_decode(const uint8_t *frv, size_t len, uint32_t threads, uint32_t info[8], int32_t *coefs, size_t coef_cap, char *err, size_t err_cap);
+/* The tile range of a region ("Region decode" above): out = {i0, j0, ni, nj} by that arithmetic and nothing else. -1 for a zero size (of the image, the tile or
+ * the region), a region that leaves the image, or out = NULL. */
+int fri_tiled_region_tiles(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint32_t out[4]);
+/* fri_tiled_decode for the tiles a region touches: coefs [nj ni][C][F][512] int32 in the sub-grid's order - what fri_hip_decode_region_tiled takes - and
+ * tiles = {i0, j0, ni, nj}. The header, the table and every payload's 16-byte header are checked exactly as fri_tiled_decode checks them, whatever the region: a
+ * file is a well-formed `frit` file or it is not (-2), and `info` is the same. Only the ni nj touched tiles are entropy-decoded, on the same workers with the
+ * shared geometry and symbol order; the bytes are the same for every thread count and equal those tiles' planes of fri_tiled_decode. Damage inside the body of
+ * a payload the region does not touch is not looked at: such a file decodes here and fails in fri_tiled_decode. A tile's error names its index in the file's
+ * grid ("tile t: channel c: ..."). -1 for a region fri_tiled_region_tiles refuses ("invalid region"); -3 with `info` and `tiles` filled when coefs is NULL or
+ * coef_cap (in elements) is too small. */
+int fri_tiled_decode_region(const uint8_t *frv, size_t len, uint32_t threads, uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint32_t info[8], uint32_t tiles[4],
+                            int32_t *coefs, size_t coef_cap, char *err, size_t err_cap);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

@@ -597,7 +597,13 @@ int fri_hip_decode_image_rgba(fri_hip_plan_rgba *p, const int32_t *coefs, const 
  * create does not do. fri_hip_plan_tiled_grid: out[4] = {nx, ny, tile_w, tile_h}. The plan owns the tile staging buffers: calls on one fri_hip_plan_tiled must
  * be ordered on one stream, as for fri_hip_plan_rgba.
  * Out of scope: per-tile qualities (all tiles of a file carry one metadata word: one quality per file, which is what the searches below return), 4:2:0 and alpha
- * in tiles, region (tile-range) decode, multi-GPU forms. */
+ * in tiles, multi-GPU forms.
+ * Region decode: a region x, y, w, h in image pixels (w, h >= 1, x + w <= W, y + h <= H, compared in 64 bits) touches the sub-grid of ni x nj tiles from column
+ * i0 = x / tile_w and row j0 = y / tile_h, ni = (x + w - 1) / tile_w - i0 + 1, nj = (y + h - 1) / tile_h - j0 + 1, stored row-major: sub-tile s = b ni + a is
+ * tile (j0 + b) nx + (i0 + a). The region raster is [h][w][C] without a pitch: pixel (ry, rx) is image pixel (y + ry, x + rx), which is pixel
+ * (y + ry - j tile_h, x + rx - i tile_w) of tile (j, i); no replicated pixel is ever copied. By definition it is the crop [y : y + h, x : x + w] of what
+ * fri_hip_decode_image_tiled returns for the same file. Only the touched tiles are entropy-decoded (fri_tiled_decode_region, include/fri_emit.h), inverted and
+ * copied, and the plan's buffers grow to the region's size, never to the image's. Out of scope: regions of 4:2:0 and alpha files, several regions in one call. */
 #define FRI_HIP_TILED_ALLOW_HOLES 1u
 typedef struct fri_hip_plan_tiled fri_hip_plan_tiled;
 uint64_t fri_hip_plan_owned_pixels(const fri_hip_plan *plan);
@@ -626,6 +632,20 @@ int fri_hip_encode_image_tiled_symbols(fri_hip_plan_tiled *p, const uint8_t *pix
 /* The device part of a tiled decode: coefs [n_tiles][C][F][512] int32 (what fri_tiled_decode returns; F = the inner plan's cells) -> pixels [H][W][C].
  * fri_hip_inverse_transform_batch_dev on the inner plan with `qmatrix` and the colour transform and dequantiser set on that plan, then the merge. Synchronous. */
 int fri_hip_decode_image_tiled(fri_hip_plan_tiled *p, const int32_t *coefs, const int32_t qmatrix[32], uint8_t *pixels);
+/* Region decode (defined above). fri_hip_plan_tiled_region: out[4] = {i0, j0, ni, nj} of the region on the plan's grid; works on host-only plans.
+ * fri_hip_merge_tiles_region_dev (K10's merge_tiles_region_kernel): d_tiles, the sub-grid's tile raster [nj ni][tile_h][tile_w][C] -> d_region [h][w][C]; only
+ * enqueues on `stream`, can be captured into a graph, any pointer alignment.
+ * fri_hip_decode_region_tiled_dev: d_coefs [nj ni][C][F][512] int32 (what fri_tiled_decode_region returns, in device memory) -> d_region. Grows the plan's tile
+ * buffer to ni nj tiles, runs fri_hip_inverse_transform_batch_dev on the inner plan with n_images = ni nj (`qmatrix` and the colour transform and dequantiser set
+ * on that plan), then the region kernel, all on `stream`. A capturing stream is refused (FRI_HIP_ERR_INVALID_ARGUMENT) before anything is enqueued or allocated.
+ * fri_hip_decode_region_tiled: the host form - coefs and pixels [h][w][C] are host memory. Synchronous.
+ * All four: FRI_HIP_ERR_INVALID_ARGUMENT for a NULL pointer or a region that is empty or leaves the image; the three that compute: FRI_HIP_ERR_NO_DEVICE on a
+ * host-only plan. */
+int fri_hip_plan_tiled_region(const fri_hip_plan_tiled *p, uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint32_t out[4]);
+int fri_hip_merge_tiles_region_dev(fri_hip_plan_tiled *p, const uint8_t *d_tiles, uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint8_t *d_region, void *stream);
+int fri_hip_decode_region_tiled_dev(fri_hip_plan_tiled *p, const int32_t *d_coefs, const int32_t qmatrix[32], uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint8_t *d_region,
+                                    void *stream);
+int fri_hip_decode_region_tiled(fri_hip_plan_tiled *p, const int32_t *coefs, const int32_t qmatrix[32], uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint8_t *pixels);
 /* The distortion of a tile raster against a raster (K10's measuring kernel): the merge's walk with nothing stored. d_tiles [ny nx][tile_h][tile_w][C] is compared
  * with the same bytes of d_reference_raster [H][W][C]; replicated rows and columns are skipped, so every image pixel is counted once and no replicated one.
  * d_out uint64 [2 C + 1], the layout of fri_hip_measure_distortion_dev: d_out[2 c] = the sum of (tile - reference)^2 of channel c, d_out[2 c + 1] = the largest
