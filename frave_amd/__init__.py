@@ -14,6 +14,7 @@ from .api import (  # noqa: F401
     Plan420,
     PlanRGBA,
     PlanTiled,
+    PlanTiled420,
     TILED_ALLOW_HOLES,
     DEQUANT_MIDPOINT,
     DEQUANT_MULTIPLY,
@@ -28,4 +29,5 @@ from .api import (  # noqa: F401
     shard_images,
     ssim_of,
     tile_shape,
+    tile_shape420,
 )

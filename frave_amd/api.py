@@ -44,6 +44,10 @@ SYMBOLS = [
     "fri_hip_search_quality_ssim_tiled", "fri_hip_search_quality_ssim_tiled_dev", "fri_hip_search_quality_for_size_tiled", "fri_hip_search_quality_for_size_tiled_dev",
     "fri_hip_rans_scratch_bytes", "fri_hip_rans_encode_planes_dev", "fri_hip_rans_time_planes_dev", "fri_hip_encode_image_tiled_coded",
     "fri_hip_plan_tiled_region", "fri_hip_merge_tiles_region_dev", "fri_hip_decode_region_tiled_dev", "fri_hip_decode_region_tiled",
+    "fri_hip_tile_shape420", "fri_hip_plan_tiled420_create", "fri_hip_plan_tiled420_destroy", "fri_hip_plan_tiled420_luma", "fri_hip_plan_tiled420_chroma",
+    "fri_hip_plan_tiled420_grid", "fri_hip_plan_tiled420_region", "fri_hip_plan_tiled420_buffer_tiles", "fri_hip_split_tiles420_dev", "fri_hip_merge_tiles420_dev",
+    "fri_hip_merge_tiles420_region_dev", "fri_hip_encode_symbols_tiled420_dev", "fri_hip_encode_image_tiled420_symbols", "fri_hip_decode_image_tiled420",
+    "fri_hip_decode_region_tiled420_dev", "fri_hip_decode_region_tiled420",
 ]
 RANS_EMPTY_OK = 1  # FRI_HIP_RANS_EMPTY_OK: `flags` of fri_hip_rans_encode_planes_dev - a context without counts is coded (the emitter's FRI_EMIT_EMPTY_OK)
 RANS_TOO_SMALL, RANS_BAD_MODEL, RANS_ZERO_FREQ, RANS_BAD_BUCKET = 1, 2, 4, 8  # bits of a plane's status word (include/fri_hip.h)
@@ -241,6 +245,22 @@ def load_library():
     L.fri_hip_search_quality_ssim_tiled_dev.argtypes = [vp, vp, C.c_double, vp, vp, vp]
     L.fri_hip_search_quality_for_size_tiled.argtypes = [vp, vp, C.c_uint64, vp, vp]
     L.fri_hip_search_quality_for_size_tiled_dev.argtypes = [vp, vp, C.c_uint64, vp, vp, vp]
+    L.fri_hip_tile_shape420.argtypes = [u32, u32, u32, vp, vp]
+    L.fri_hip_plan_tiled420_create.argtypes = [vp, u32, u32, u32, u32, u32, C.POINTER(vp)]
+    L.fri_hip_plan_tiled420_destroy.argtypes = [vp]
+    L.fri_hip_plan_tiled420_luma.restype, L.fri_hip_plan_tiled420_luma.argtypes = vp, [vp]
+    L.fri_hip_plan_tiled420_chroma.restype, L.fri_hip_plan_tiled420_chroma.argtypes = vp, [vp]
+    L.fri_hip_plan_tiled420_grid.argtypes = [vp, vp]
+    L.fri_hip_plan_tiled420_region.argtypes = [vp, u32, u32, u32, u32, vp]
+    L.fri_hip_plan_tiled420_buffer_tiles.argtypes = [vp, vp]
+    L.fri_hip_split_tiles420_dev.argtypes = [vp, vp, vp, vp, vp]
+    L.fri_hip_merge_tiles420_dev.argtypes = [vp, vp, vp, vp, vp]
+    L.fri_hip_merge_tiles420_region_dev.argtypes = [vp, vp, vp, u32, u32, u32, u32, vp, vp]
+    L.fri_hip_encode_symbols_tiled420_dev.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
+    L.fri_hip_encode_image_tiled420_symbols.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp]
+    L.fri_hip_decode_image_tiled420.argtypes = [vp, vp, i32, vp]
+    L.fri_hip_decode_region_tiled420_dev.argtypes = [vp, vp, i32, u32, u32, u32, u32, vp, vp]
+    L.fri_hip_decode_region_tiled420.argtypes = [vp, vp, i32, u32, u32, u32, u32, vp]
     _lib = L
     return L
 
@@ -295,6 +315,15 @@ def tile_shape(width, height, target=512):
     every pixel; FriHipError with code -7 when the walk finds none. Host only."""
     tw, th = C.c_uint32(0), C.c_uint32(0)
     _check(load_library().fri_hip_tile_shape(width, height, target, C.addressof(tw), C.addressof(th)), "fri_hip_tile_shape")
+    return tw.value, th.value
+
+
+def tile_shape420(width, height, target=512):
+    """fri_hip_tile_shape420: (tile_w, tile_h) of about target x target for tiled 4:2:0 coding - the first shape of tile_shape's walk at which the C = 1 lattice of
+    the tile AND the C = 1 lattice of its (tile_w + 1) / 2 x (tile_h + 1) / 2 chroma planes own every pixel; FriHipError with code -7 when the walk finds none.
+    Host only."""
+    tw, th = C.c_uint32(0), C.c_uint32(0)
+    _check(load_library().fri_hip_tile_shape420(width, height, target, C.addressof(tw), C.addressof(th)), "fri_hip_tile_shape420")
     return tw.value, th.value
 
 
@@ -1216,3 +1245,123 @@ class PlanTiled:
         """fri_hip_search_quality_for_size_tiled[_dev]: (quality, estimated bytes of the `frit` file); FriHipError with code -7 when nothing fits. Needs
         set_stream_order()."""
         return self._search("fri_hip_search_quality_for_size_tiled", pixels, int(max_bytes), C.c_uint64, stream)
+
+
+class PlanTiled420:
+    """fri_hip_plan_tiled420: an image as a batch of independently coded 4:2:0 tiles (include/fri_hip.h, "Tiled 4:2:0 coding", has the format). Owns two ordinary
+    C = 1 plans, .luma (tile_w x tile_h) and .chroma (cw x ch) - Plan views that do not own their handle and die with this object. Every per-plane array is in
+    plane order: with n tiles, plane(t, Y) = t, plane(t, Cb) = n + 2 t, plane(t, Cr) = n + 2 t + 1. ctx=None gives a host-only plan (getters only). flags:
+    TILED_ALLOW_HOLES accepts a tile shape at which a lattice does not own every pixel. Calls on one PlanTiled420 must be ordered on one stream: they share the
+    plan's staging buffers."""
+
+    def __init__(self, ctx, width, height, tile_w, tile_h, flags=0):
+        self._h = None
+        self.ctx = ctx
+        self.width, self.height = width, height
+        h = C.c_void_p()
+        L = load_library()
+        _check(L.fri_hip_plan_tiled420_create(ctx._h if ctx else None, width, height, tile_w, tile_h, flags, C.byref(h)), "fri_hip_plan_tiled420_create", ctx)
+        self._h = h
+        self.cw, self.ch = (tile_w + 1) // 2, (tile_h + 1) // 2
+        self.luma = Plan(ctx, tile_w, tile_h, 1, _handle=L.fri_hip_plan_tiled420_luma(h))
+        self.chroma = Plan(ctx, self.cw, self.ch, 1, _handle=L.fri_hip_plan_tiled420_chroma(h))
+        grid = np.zeros(4, np.uint32)
+        _check(L.fri_hip_plan_tiled420_grid(h, _p(grid)), "fri_hip_plan_tiled420_grid", ctx)
+        self.nx, self.ny, self.tile_w, self.tile_h = (int(v) for v in grid)
+        self.n_tiles = self.nx * self.ny
+        self.pixel_bytes = width * height * 3
+        self.y_tile_bytes = self.n_tiles * tile_w * tile_h      # y_tiles [n][tile_h][tile_w]
+        self.c_tile_bytes = self.n_tiles * 2 * self.cw * self.ch  # c_tiles [n][2][ch][cw]
+        self.n_luma, self.n_chroma = self.luma.num_some, self.chroma.num_some  # symbols of a tile's luma plane and of one of its chroma planes
+        self.num_symbols = self.n_tiles * (self.n_luma + 2 * self.n_chroma)
+        self.tile_coef_count = (self.luma.num_cells + 2 * self.chroma.num_cells) * 512
+        self.coef_count = self.n_tiles * self.tile_coef_count
+
+    def close(self):
+        if self._h:
+            self.luma.close()
+            self.chroma.close()
+            load_library().fri_hip_plan_tiled420_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_stream_order(self):
+        """fri_hip_plan_set_stream_order on both inner plans (the encodes need it)."""
+        self.luma.set_stream_order()
+        self.chroma.set_stream_order()
+
+    def region_tiles(self, x, y, w, h):
+        """fri_hip_plan_tiled420_region: (i0, j0, ni, nj), the sub-grid of tiles the region touches. Works on a host-only plan. FriHipError (-1) for an empty
+        region or one that leaves the image."""
+        out = np.zeros(4, np.uint32)
+        _check(load_library().fri_hip_plan_tiled420_region(self._h, x, y, w, h, _p(out)), "fri_hip_plan_tiled420_region", self.ctx)
+        return tuple(int(v) for v in out)
+
+    def buffer_tiles(self):
+        """fri_hip_plan_tiled420_buffer_tiles: the tiles the plan's (luma, chroma) tile buffers hold room for at the moment."""
+        out = np.zeros(2, np.uint64)
+        _check(load_library().fri_hip_plan_tiled420_buffer_tiles(self._h, _p(out)), "fri_hip_plan_tiled420_buffer_tiles", self.ctx)
+        return int(out[0]), int(out[1])
+
+    # ---- device-pointer entry points (pointers are ints) --------------------------------------------
+    def split_tiles420_dev(self, d_rgb, d_y_tiles, d_c_tiles, stream=0):
+        """fri_hip_split_tiles420_dev: [H][W][3] -> y_tiles [n][tile_h][tile_w] and c_tiles [n][2][ch][cw] in one pass; only enqueues."""
+        _check(load_library().fri_hip_split_tiles420_dev(self._h, d_rgb, d_y_tiles, d_c_tiles, stream), "fri_hip_split_tiles420_dev", self.ctx)
+
+    def merge_tiles420_dev(self, d_y_tiles, d_c_tiles, d_rgb, stream=0):
+        """fri_hip_merge_tiles420_dev: the tiles' planes -> [H][W][3], every pixel upsampled within its own tile; only enqueues."""
+        _check(load_library().fri_hip_merge_tiles420_dev(self._h, d_y_tiles, d_c_tiles, d_rgb, stream), "fri_hip_merge_tiles420_dev", self.ctx)
+
+    def merge_tiles420_region_dev(self, d_y_tiles, d_c_tiles, x, y, w, h, d_region, stream=0):
+        """fri_hip_merge_tiles420_region_dev: the sub-grid's planes -> the region raster [h][w][3]; only enqueues."""
+        _check(load_library().fri_hip_merge_tiles420_region_dev(self._h, d_y_tiles, d_c_tiles, x, y, w, h, d_region, stream), "fri_hip_merge_tiles420_region_dev", self.ctx)
+
+    def encode_symbols_tiled420_dev(self, d_rgb, quality, d_params, d_symbols, d_hist, d_oob, d_fit_out_of_range=None, fit=True, stream=0):
+        """fri_hip_encode_symbols_tiled420_dev: the split and the direct stream chain on both inner plans, everything on the device and in plane order: d_params
+        float32 [3 n][2][3][6], d_symbols uint16 [n][n_luma] then [n][2][n_chroma], d_hist uint32 [3 n][10][1024], d_oob uint64 [3 n], d_fit_out_of_range uint64
+        [3 n] or None. Needs set_stream_order()."""
+        _check(load_library().fri_hip_encode_symbols_tiled420_dev(self._h, d_rgb, int(quality), int(bool(fit)), d_params, d_symbols, d_hist, d_oob, d_fit_out_of_range, stream),
+               "fri_hip_encode_symbols_tiled420_dev", self.ctx)
+
+    def decode_region_tiled420_dev(self, d_coefs, quality, x, y, w, h, d_region, stream=0):
+        """fri_hip_decode_region_tiled420_dev: d_coefs int32, the sub-grid's planes in plane order -> d_region uint8 [h][w][3], device pointers. Refuses a
+        capturing stream."""
+        _check(load_library().fri_hip_decode_region_tiled420_dev(self._h, d_coefs, int(quality), x, y, w, h, d_region, stream), "fri_hip_decode_region_tiled420_dev", self.ctx)
+
+    # ---- host-pointer entry points ----------------------------------------------------------------
+    def encode_image_tiled420_symbols(self, pixels, quality):
+        """fri_hip_encode_image_tiled420_symbols: (symbols uint16 flat = [n][n_luma] then [n][2][n_chroma], value_params [3 n][3][6], width_params [3 n][3][6],
+        hist [3 n][10][1024], oob [3 n]), all in plane order - what emit.tiled_encode_from_streams420 takes; the fit is on. Needs set_stream_order()."""
+        px = np.ascontiguousarray(pixels, np.uint8).reshape(-1)
+        assert px.size == self.pixel_bytes
+        planes = 3 * self.n_tiles
+        vp, wp = np.zeros((planes, 3, 6), np.float32), np.zeros((planes, 3, 6), np.float32)
+        sym = np.empty(self.num_symbols, np.uint16)
+        hist = np.empty((planes, 10, 1024), np.uint32)
+        oob = np.zeros(planes, np.uint64)
+        _check(load_library().fri_hip_encode_image_tiled420_symbols(self._h, _p(px), int(quality), _p(vp), _p(wp), _p(sym), _p(hist), _p(oob)),
+               "fri_hip_encode_image_tiled420_symbols", self.ctx)
+        return sym, vp, wp, hist, oob
+
+    def decode_image_tiled420(self, coefs, quality):
+        """fri_hip_decode_image_tiled420: coefs int32 in plane order (what emit.tiled_decode returns for a tiled 4:2:0 file) -> pixels uint8 [H * W * 3]."""
+        co = np.ascontiguousarray(coefs, np.int32).reshape(-1)
+        assert co.size == self.coef_count
+        out = np.empty(self.pixel_bytes, np.uint8)
+        _check(load_library().fri_hip_decode_image_tiled420(self._h, _p(co), int(quality), _p(out)), "fri_hip_decode_image_tiled420", self.ctx)
+        return out
+
+    def decode_region_tiled420(self, coefs, quality, x, y, w, h):
+        """fri_hip_decode_region_tiled420: coefs int32, the sub-grid's planes in plane order (what emit.tiled_decode_region returns) -> pixels uint8 [h * w * 3]:
+        the crop [y : y + h, x : x + w] of what decode_image_tiled420 returns for the same file."""
+        _, _, ni, nj = self.region_tiles(x, y, w, h)
+        co = np.ascontiguousarray(coefs, np.int32).reshape(-1)
+        assert co.size == ni * nj * self.tile_coef_count
+        out = np.empty(w * h * 3, np.uint8)
+        _check(load_library().fri_hip_decode_region_tiled420(self._h, _p(co), int(quality), x, y, w, h, _p(out)), "fri_hip_decode_region_tiled420", self.ctx)
+        return out

@@ -1,0 +1,283 @@
+// k12_tiles420.hip -- K12: the raster kernels of tiled 4:2:0 coding (include/fri_hip.h, "Tiled 4:2:0 coding", has the format bit for bit).
+//
+// split_tiles420_kernel: the image [H][W][3] -> y_tiles [n][tile_h][tile_w] and c_tiles [n][2][ch][cw], cw = (tile_w + 1) / 2, ch = (tile_h + 1) / 2, in one pass:
+// K10's split (edge replication, tile t = j nx + i) fused with K8's split (the forward YCbCr formula, the 2 x 2 chroma mean with an odd last column or row of
+// the TILE replicated). An item is (tile, chroma row of the tile, strip of 16 tile columns); a lane owns the strip on the two tile rows of the chroma row: 48
+// bytes of pixels per row come in as three 16-byte loads, 16 bytes of Y per row and 8 bytes of each chroma plane go out as one store each. A pixel is read once
+// per tile that replicates it and never written anywhere but in its tile's planes.
+// merge_tiles420_region_kernel: a sub-grid's y_tiles and c_tiles [nj ni]... -> the region raster [h][w][3] (include/fri_emit.h, "Region decode", has the
+// arithmetic). The work follows the region: a lane owns 16 pixels of one region row. Where they lie in one tile row: 16 bytes of Y, 8 + 2 bytes of two rows of
+// each chroma plane of THAT tile come in - the (3, 1) / 4 triangle filter clamped to the tile's own planes, first down the columns, then along the row - and
+// 48 bytes of pixels go out as three 16-byte stores. The strip may start at an odd tile column (a region's origin, an odd tile_w): the two parities are two
+// instances of the strip, so that every register index is a constant. A strip that crosses a tile column and the row's last, partial strip go pixel by pixel.
+// The whole-image merge is this kernel with the region (0, 0, W, H) on the full grid. Nothing outside the region raster is written and no replicated pixel is
+// read for it.
+//
+// No raster has a row pitch and every buffer starts at any byte: the vector accesses are the target's unaligned global loads and stores (the compiler is told
+// the alignment is 1). Every byte offset is 64-bit. No LDS, no atomics: the kernels only enqueue and can be captured into a graph.
+#include "device_common.hpp"
+
+namespace fri {
+namespace {
+
+constexpr int kT420Threads = 256;
+constexpr int kT420Strip = 16; // pixels of a row per lane
+
+struct SplitTiles420Args {
+    const uint8_t *rgb;
+    uint8_t *y, *c;
+    uint32_t width, height, tile_w, tile_h, nx, cw, ch;
+    uint32_t n_strips; // strips per tile row
+    uint32_t n_items;  // tiles x ch x n_strips
+};
+
+struct MergeTiles420Args {
+    const uint8_t *y, *c; // the sub-grid's planes
+    uint8_t *out;         // the region raster
+    uint32_t tile_w, tile_h, cw, ch, ni;
+    uint32_t ox, oy;   // x - i0 tile_w, y - j0 tile_h: the region's corner within the sub-grid's first tile
+    uint32_t w;        // the region's width
+    uint32_t n_strips; // strips per region row
+    uint32_t n_items;  // h x n_strips
+};
+
+template <typename V>
+__device__ __forceinline__ V load_unaligned(const uint8_t *p) {
+    V v;
+    __builtin_memcpy(&v, p, sizeof(V));
+    return v;
+}
+template <typename V>
+__device__ __forceinline__ void store_unaligned(uint8_t *p, const V &v) {
+    __builtin_memcpy(p, &v, sizeof(V));
+}
+__device__ __forceinline__ int byte_of(const uint32_t *w, int n) { return (int)((w[n >> 2] >> ((n & 3) * 8)) & 255u); }
+__device__ __forceinline__ int clamp255(int v) { return min(max(v, 0), 255); }
+
+// 16 pixels of the image row at src_row for the tile columns x0 .. x0 + 15 of a tile whose columns start at image column gx0, as 12 dwords. !FULL: a tile
+// column past the tile repeats the tile's last one (the chroma's odd column), an image column past the image repeats the image's last one (the tile's edge).
+template <bool FULL>
+__device__ __forceinline__ void load_tile_pixels(const uint8_t *src_row, const SplitTiles420Args &p, uint32_t gx0, uint32_t x0, uint32_t (&px)[12]) {
+    if (FULL) {
+#pragma unroll
+        for (int q = 0; q < 3; q++) {
+            const u32x4 v = load_unaligned<u32x4>(src_row + (uint64_t)(gx0 + x0) * 3 + 16 * q);
+            px[4 * q] = v.x, px[4 * q + 1] = v.y, px[4 * q + 2] = v.z, px[4 * q + 3] = v.w;
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < 12; i++) px[i] = 0;
+#pragma unroll
+        for (int k = 0; k < kT420Strip; k++) {
+            const uint32_t tx = min(x0 + (uint32_t)k, p.tile_w - 1);
+            const uint8_t *s = src_row + (uint64_t)min(gx0 + tx, p.width - 1) * 3;
+#pragma unroll
+            for (int c = 0; c < 3; c++) px[(3 * k + c) >> 2] |= (uint32_t)s[c] << (((3 * k + c) & 3) * 8);
+        }
+    }
+}
+
+template <bool FULL>
+__device__ __forceinline__ void split_tile_strip(const SplitTiles420Args &p, uint32_t t, uint32_t jc, uint32_t x0) {
+    const uint32_t tj = t / p.nx, ti = t - tj * p.nx;
+    const uint32_t gx0 = ti * p.tile_w, gy0 = tj * p.tile_h;
+    uint8_t *y_tile = p.y + (uint64_t)t * p.tile_h * p.tile_w;
+    uint8_t *c_tile = p.c + (uint64_t)t * 2 * p.ch * p.cw;
+    int cb[kT420Strip / 2], cr[kT420Strip / 2];
+#pragma unroll
+    for (int m = 0; m < kT420Strip / 2; m++) cb[m] = 0, cr[m] = 0;
+#pragma unroll
+    for (uint32_t r = 0; r < 2; r++) {
+        const uint32_t ty = min(2 * jc + r, p.tile_h - 1);  // an odd tile_h: the tile's last row twice ...
+        const uint32_t gy = min(gy0 + ty, p.height - 1);    // ... which at the image's bottom edge is itself a clamped row
+        uint32_t px[12];
+        load_tile_pixels<FULL>(p.rgb + (uint64_t)gy * p.width * 3, p, gx0, x0, px);
+        uint32_t yw[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int k = 0; k < kT420Strip; k++) {
+            const int R = byte_of(px, 3 * k), G = byte_of(px, 3 * k + 1), B = byte_of(px, 3 * k + 2);
+            const int Y = (19595 * R + 38470 * G + 7471 * B + 32768) >> 16;
+            yw[k >> 2] |= (uint32_t)Y << ((k & 3) * 8);
+            cb[k >> 1] += (-11059 * R - 21709 * G + 32768 * B + (128 << 16) + 32767) >> 16;
+            cr[k >> 1] += (32768 * R - 27439 * G - 5329 * B + (128 << 16) + 32767) >> 16;
+        }
+        if (2 * jc + r < p.tile_h) { // (an odd last row of the tile has no second luma row)
+            uint8_t *dst = y_tile + (uint64_t)ty * p.tile_w + x0;
+            if (FULL) {
+                const u32x4 v = {yw[0], yw[1], yw[2], yw[3]};
+                store_unaligned(dst, v);
+            } else {
+#pragma unroll
+                for (int k = 0; k < kT420Strip; k++)
+                    if (x0 + k < p.tile_w) dst[k] = (uint8_t)(yw[k >> 2] >> ((k & 3) * 8));
+            }
+        }
+    }
+    uint32_t bw[2] = {0, 0}, rw[2] = {0, 0};
+#pragma unroll
+    for (int m = 0; m < kT420Strip / 2; m++) {
+        bw[m >> 2] |= (uint32_t)((cb[m] + 2) >> 2) << ((m & 3) * 8);
+        rw[m >> 2] |= (uint32_t)((cr[m] + 2) >> 2) << ((m & 3) * 8);
+    }
+    const uint64_t plane = (uint64_t)p.ch * p.cw, at = (uint64_t)jc * p.cw + x0 / 2;
+    if (FULL) {
+        const uint2v b = {bw[0], bw[1]}, r = {rw[0], rw[1]};
+        store_unaligned(c_tile + at, b);
+        store_unaligned(c_tile + plane + at, r);
+    } else {
+#pragma unroll
+        for (int m = 0; m < kT420Strip / 2; m++)
+            if (x0 / 2 + m < p.cw) {
+                c_tile[at + m] = (uint8_t)(bw[m >> 2] >> ((m & 3) * 8));
+                c_tile[plane + at + m] = (uint8_t)(rw[m >> 2] >> ((m & 3) * 8));
+            }
+    }
+}
+
+// item g = strip g % n_strips of chroma row (g / n_strips) % ch of tile g / (n_strips ch): the lanes of a wave walk along a tile row and on into the next
+__global__ void __launch_bounds__(kT420Threads) split_tiles420_kernel(const SplitTiles420Args p) {
+    const uint32_t g = blockIdx.x * kT420Threads + threadIdx.x;
+    if (g >= p.n_items) return;
+    const uint32_t row = g / p.n_strips, x0 = (g - row * p.n_strips) * kT420Strip;
+    const uint32_t t = row / p.ch, jc = row - t * p.ch;
+    const uint32_t ti = t % p.nx;
+    // whole: the strip lies in the tile row and in the image row - no clamp of either kind
+    if (x0 + kT420Strip <= p.tile_w && (uint64_t)ti * p.tile_w + x0 + kT420Strip <= p.width) split_tile_strip<true>(p, t, jc, x0);
+    else split_tile_strip<false>(p, t, jc, x0);
+}
+
+__device__ __forceinline__ void ycc_to_rgb(int Y, int cbv, int crv, int &R, int &G, int &B) {
+    const int db = cbv - 128, dr = crv - 128;
+    R = clamp255(Y + ((91881 * dr + 32768) >> 16));
+    G = clamp255(Y + ((-22554 * db - 46802 * dr + 32768) >> 16));
+    B = clamp255(Y + ((116130 * db + 32768) >> 16));
+}
+
+// v[m] = 3 plane[j][c] + plane[j2][c] at the chroma columns c = i0 - 1 + m, m = 0..9, clamped to the tile's plane; i0 + 8 <= cw
+__device__ __forceinline__ void load_tile_chroma(const uint8_t *plane, int cw, int j, int j2, int i0, int (&v)[kT420Strip / 2 + 2]) {
+    const uint8_t *a = plane + (uint64_t)j * cw, *b = plane + (uint64_t)j2 * cw;
+    constexpr int N = kT420Strip / 2;
+    const uint2v wa = load_unaligned<uint2v>(a + i0), wb = load_unaligned<uint2v>(b + i0);
+    const uint32_t ua[2] = {wa.x, wa.y}, ub[2] = {wb.x, wb.y};
+#pragma unroll
+    for (int m = 0; m < N; m++) v[m + 1] = 3 * byte_of(ua, m) + byte_of(ub, m);
+    const int l = max(i0 - 1, 0), r = min(i0 + N, cw - 1);
+    v[0] = 3 * a[l] + b[l];
+    v[N + 1] = 3 * a[r] + b[r];
+}
+
+// 16 pixels of tile row ty from tile column tx (tx & 1 == ODD), all inside the tile row: tx + 16 <= tile_w
+template <int ODD>
+__device__ __forceinline__ void merge_tile_strip(const MergeTiles420Args &p, const uint8_t *y_tile, const uint8_t *c_tile, int tx, int ty, uint8_t *dst) {
+    const int ch = (int)p.ch, cw = (int)p.cw;
+    const int j = ty >> 1, j2 = (ty & 1) ? min(j + 1, ch - 1) : max(j - 1, 0);
+    int vb[kT420Strip / 2 + 2], vr[kT420Strip / 2 + 2];
+    load_tile_chroma(c_tile, cw, j, j2, tx >> 1, vb);
+    load_tile_chroma(c_tile + (uint64_t)ch * cw, cw, j, j2, tx >> 1, vr);
+    const u32x4 yv = load_unaligned<u32x4>(y_tile + (uint64_t)ty * p.tile_w + tx);
+    const uint32_t yw[4] = {yv.x, yv.y, yv.z, yv.w};
+    uint32_t px[12];
+#pragma unroll
+    for (int i = 0; i < 12; i++) px[i] = 0;
+#pragma unroll
+    for (int k = 0; k < kT420Strip; k++) {
+        const int m = 1 + ((k + ODD) >> 1), n = ((k + ODD) & 1) ? m + 1 : m - 1; // the column's own sample and its neighbour on the pixel's side
+        int R, G, B;
+        ycc_to_rgb(byte_of(yw, k), (3 * vb[m] + vb[n] + 8) >> 4, (3 * vr[m] + vr[n] + 8) >> 4, R, G, B);
+        px[(3 * k) >> 2] |= (uint32_t)R << (((3 * k) & 3) * 8);
+        px[(3 * k + 1) >> 2] |= (uint32_t)G << (((3 * k + 1) & 3) * 8);
+        px[(3 * k + 2) >> 2] |= (uint32_t)B << (((3 * k + 2) & 3) * 8);
+    }
+#pragma unroll
+    for (int q = 0; q < 3; q++) {
+        const u32x4 v = {px[4 * q], px[4 * q + 1], px[4 * q + 2], px[4 * q + 3]};
+        store_unaligned(dst + 16 * q, v);
+    }
+}
+
+// one pixel (tx, ty) of a tile: inverse steps 2 - 3 by the header's formula
+__device__ __forceinline__ void merge_tile_pixel(const MergeTiles420Args &p, const uint8_t *y_tile, const uint8_t *c_tile, int tx, int ty, uint8_t *dst) {
+    const int ch = (int)p.ch, cw = (int)p.cw;
+    const int i = tx >> 1, i2 = (tx & 1) ? min(i + 1, cw - 1) : max(i - 1, 0);
+    const int j = ty >> 1, j2 = (ty & 1) ? min(j + 1, ch - 1) : max(j - 1, 0);
+    int up[2];
+#pragma unroll
+    for (int c = 0; c < 2; c++) {
+        const uint8_t *a = c_tile + (uint64_t)c * ch * cw + (uint64_t)j * cw, *b = c_tile + (uint64_t)c * ch * cw + (uint64_t)j2 * cw;
+        up[c] = (9 * a[i] + 3 * a[i2] + 3 * b[i] + b[i2] + 8) >> 4;
+    }
+    int R, G, B;
+    ycc_to_rgb(y_tile[(uint64_t)ty * p.tile_w + tx], up[0], up[1], R, G, B);
+    dst[0] = (uint8_t)R, dst[1] = (uint8_t)G, dst[2] = (uint8_t)B;
+}
+
+// item g = strip g % n_strips of region row g / n_strips
+__global__ void __launch_bounds__(kT420Threads) merge_tiles420_region_kernel(const MergeTiles420Args p) {
+    const uint32_t g = blockIdx.x * kT420Threads + threadIdx.x;
+    if (g >= p.n_items) return;
+    const uint32_t ry = g / p.n_strips, rx0 = (g - ry * p.n_strips) * kT420Strip;
+    const uint32_t n = min((uint32_t)kT420Strip, p.w - rx0);
+    const uint32_t gy = p.oy + ry, b = gy / p.tile_h, ty = gy - b * p.tile_h; // row ty of the tiles of sub-grid row b
+    const uint32_t gx = p.ox + rx0;                                          // the strip's first column in the sub-grid's row: < ni tile_w
+    uint32_t a = gx / p.tile_w, tx = gx - a * p.tile_w;                      // column tx of tile (b, a)
+    const uint64_t y_stride = (uint64_t)p.tile_h * p.tile_w, c_stride = 2ull * p.ch * p.cw;
+    const uint64_t s = (uint64_t)b * p.ni + a;
+    const uint8_t *y_tile = p.y + s * y_stride, *c_tile = p.c + s * c_stride;
+    uint8_t *dst = p.out + ((uint64_t)ry * p.w + rx0) * 3;
+    if (n == (uint32_t)kT420Strip && tx + kT420Strip <= p.tile_w) {
+        if (tx & 1) merge_tile_strip<1>(p, y_tile, c_tile, (int)tx, (int)ty, dst);
+        else merge_tile_strip<0>(p, y_tile, c_tile, (int)tx, (int)ty, dst);
+    } else { // the strip crosses a tile column, or is the row's last
+        for (uint32_t k = 0; k < n; k++) {
+            merge_tile_pixel(p, y_tile, c_tile, (int)tx, (int)ty, dst + 3 * k);
+            if (++tx == p.tile_w) tx = 0, y_tile += y_stride, c_tile += c_stride; // the same row of the next tile
+        }
+    }
+}
+
+// the limits both launchers share: sizes that keep every u32 product above in range; false for a shape outside them
+bool shape_ok(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint64_t &nx, uint64_t &ny) {
+    if (!width || !height || !tile_w || !tile_h || width > 0x3FFFFFFFu || height > 0x3FFFFFFFu || tile_w > 0x3FFFFFFFu || tile_h > 0x3FFFFFFFu) return false;
+    nx = ((uint64_t)width + tile_w - 1) / tile_w, ny = ((uint64_t)height + tile_h - 1) / tile_h;
+    return nx * tile_w <= 0xFFFFFFFFull && ny * tile_h <= 0xFFFFFFFFull && nx * ny <= 0xFFFFFFFFull;
+}
+
+} // namespace
+
+hipError_t launch_split_tiles420(const uint8_t *rgb, uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint8_t *y_tiles, uint8_t *c_tiles, hipStream_t stream) {
+    uint64_t nx = 0, ny = 0;
+    if (!rgb || !y_tiles || !c_tiles || !shape_ok(width, height, tile_w, tile_h, nx, ny)) return hipErrorInvalidValue;
+    SplitTiles420Args p{};
+    p.rgb = rgb, p.y = y_tiles, p.c = c_tiles;
+    p.width = width, p.height = height, p.tile_w = tile_w, p.tile_h = tile_h, p.nx = (uint32_t)nx, p.cw = (tile_w + 1) / 2, p.ch = (tile_h + 1) / 2;
+    p.n_strips = (tile_w + kT420Strip - 1) / kT420Strip;
+    const uint64_t rows = nx * ny * p.ch;
+    if (rows > 0xFFFFFFFFull || rows * p.n_strips > 0xFFFFFFFFull - kT420Threads) return hipErrorInvalidValue; // (one u32 item index per lane)
+    p.n_items = (uint32_t)(rows * p.n_strips);
+    const uint32_t groups = (uint32_t)((rows * p.n_strips + kT420Threads - 1) / kT420Threads);
+    hipLaunchKernelGGL(split_tiles420_kernel, dim3(groups), dim3(kT420Threads), 0, stream, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_merge_tiles420_region(const uint8_t *y_tiles, const uint8_t *c_tiles, uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t x, uint32_t y,
+                                        uint32_t w, uint32_t h, uint8_t *region, hipStream_t stream) {
+    uint64_t nx = 0, ny = 0;
+    if (!region || !y_tiles || !c_tiles || !shape_ok(width, height, tile_w, tile_h, nx, ny)) return hipErrorInvalidValue;
+    if (!w || !h || (uint64_t)x + w > width || (uint64_t)y + h > height) return hipErrorInvalidValue;
+    const uint32_t i0 = x / tile_w, j0 = y / tile_h;
+    MergeTiles420Args p{};
+    p.y = y_tiles, p.c = c_tiles, p.out = region;
+    p.tile_w = tile_w, p.tile_h = tile_h, p.cw = (tile_w + 1) / 2, p.ch = (tile_h + 1) / 2;
+    p.ni = (x + w - 1) / tile_w - i0 + 1;
+    p.ox = x - i0 * tile_w, p.oy = y - j0 * tile_h;
+    p.w = w;
+    p.n_strips = (w + kT420Strip - 1) / kT420Strip;
+    const uint64_t items = (uint64_t)h * p.n_strips;
+    if (items > 0xFFFFFFFFull - kT420Threads) return hipErrorInvalidValue; // (one u32 item index per lane)
+    p.n_items = (uint32_t)items;
+    const uint32_t groups = (uint32_t)((items + kT420Threads - 1) / kT420Threads);
+    hipLaunchKernelGGL(merge_tiles420_region_kernel, dim3(groups), dim3(kT420Threads), 0, stream, p);
+    return hipGetLastError();
+}
+
+} // namespace fri

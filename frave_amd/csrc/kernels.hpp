@@ -208,6 +208,14 @@ hipError_t launch_rans_encode(uint32_t n_planes, const uint16_t *symbols, size_t
                               uint32_t *words, size_t word_stride, uint32_t *n_words, uint32_t *models, uint16_t *off_values, uint32_t *status, void *scratch,
                               hipStream_t stream, const hipEvent_t *events = nullptr);
 
+// K12 (k12_tiles420.hip): the raster kernels of tiled 4:2:0 coding (include/fri_hip.h has the format). Split: the image [H][W][3] -> y_tiles [n][tile_h][tile_w]
+// and c_tiles [n][2][ch][cw], n = ny nx, cw = (tile_w + 1) / 2, ch = (tile_h + 1) / 2: K10's edge replication and K8's split of every tile in one pass. Region
+// merge: the planes of the sub-grid a region touches, [nj ni]... -> the region raster [h][w][3], every pixel upsampled within its own tile; the region must lie
+// in the width x height image (hipErrorInvalidValue otherwise). The whole-image merge is the region (0, 0, width, height). Any shape, any pointer alignment.
+hipError_t launch_split_tiles420(const uint8_t *rgb, uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint8_t *y_tiles, uint8_t *c_tiles, hipStream_t stream);
+hipError_t launch_merge_tiles420_region(const uint8_t *y_tiles, const uint8_t *c_tiles, uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t x, uint32_t y,
+                                        uint32_t w, uint32_t h, uint8_t *region, hipStream_t stream);
+
 // K2's per-node neighbour offsets (LDS halfword offsets relative to the own slot, two per word) from the static neighbour table
 void build_lf_deltas(const uint16_t *nbr_table, int8_t *out /* [8] */);
 void build_gather_tables(const uint16_t *nbr_table, uint32_t *gather_off /* [512][4] */, uint16_t *pair_pos /* [256] */, uint16_t *heap_of_pos /* [512] */);

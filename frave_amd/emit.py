@@ -47,6 +47,7 @@ def load_library():
         L.fri_emit_stream_order.argtypes = [vp, u32, vp, vp, vp]
         L.fri_emit_encode_image_from_streams.argtypes = [u32, u32, u32, vp, C.c_uint64, vp, vp, vp, vp, sz, vp, C.c_char_p, sz]
         L.fri_tiled_encode_from_streams.argtypes = [u32, u32, u32, u32, u32, vp, C.c_uint64, vp, vp, vp, u32, vp, sz, vp, C.c_char_p, sz]
+        L.fri_tiled_encode_from_streams420.argtypes = [u32, u32, u32, u32, u32, vp, C.c_uint64, C.c_uint64, vp, vp, vp, u32, vp, sz, vp, C.c_char_p, sz]
         L.fri_tiled_encode_from_coded.argtypes = [u32, u32, u32, u32, u32, vp, C.c_uint64, vp, vp, vp, vp, vp, u32, vp, sz, vp, C.c_char_p, sz]
         L.fri_coded_encode_image.argtypes = [u32, u32, u32, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, sz, vp, C.c_char_p, sz]
         L.fri_tiled_info.argtypes = [vp, sz, vp]
@@ -233,18 +234,61 @@ def decode_image(frv):
 
 # ---- the tile container `frit` (include/fri_emit.h) ---------------------------------------------------------------------------
 class TiledInfo(tuple):
-    """(width, height, tile_w, tile_h, nx, ny, channels, n_cells) of a tiled file, and .rct / .quality / .ycbcr as DecodedImage has them: what every tile is."""
+    """(width, height, tile_w, tile_h, nx, ny, channels, n_cells) of a tiled file, and .rct / .quality / .ycbcr / .s420 as DecodedImage has them: what every tile
+    is. A tiled 4:2:0 file (.s420): n_cells is F_y, the cells of the tile's luma lattice."""
 
     rct = False
     quality = 0
     ycbcr = False
+    s420 = False
 
 
 def _tiled_info(info):
     w, h, tw, th, nx, ny, c, f = (int(x) for x in info)
     out = TiledInfo((w, h, tw, th, nx, ny, c & 0xFF, f))
-    out.rct, out.ycbcr, out.quality = bool(c & RCT), bool(c & YCBCR), (c >> 16) & 0x7F
+    out.rct, out.ycbcr, out.quality, out.s420 = bool(c & RCT), bool(c & YCBCR), (c >> 16) & 0x7F, bool(c & S420)
     return out
+
+
+def _chroma_cells(ti):
+    """F_c of a tiled 4:2:0 file: the cells of the lattice of a tile's chroma planes, from a host-only plan (no GPU involved)"""
+    from .api import Plan
+
+    sub = Plan(None, (ti[2] + 1) // 2, (ti[3] + 1) // 2, 1)
+    fc = sub.num_cells
+    sub.close()
+    return fc
+
+
+def _tiled_coefs(ti, n):
+    """the array fri_tiled_decode[_region] fills for n tiles: [n][C][F][512], or flat in plane order - n (F_y + 2 F_c) x 512 - for a tiled 4:2:0 file"""
+    if ti.s420:
+        return np.empty(n * (ti[7] + 2 * _chroma_cells(ti)) * 512, np.int32)
+    return np.empty((n, ti[6], ti[7], 512), np.int32)
+
+
+def tiled_encode_from_streams420(width, height, tile_w, tile_h, streams, n_luma, n_chroma, hist, value_params, width_params, quality, threads=0):
+    """fri_tiled_encode_from_streams420: the `frit` bytes of a tiled 4:2:0 file from what PlanTiled420.encode_image_tiled420_symbols returns, all in plane order
+    (plane(t, Y) = t, plane(t, Cb) = n + 2 t, plane(t, Cr) = n + 2 t + 1): streams uint16 [n][n_luma] then [n][2][n_chroma] (flat), hist [3 n][10][1024], params
+    [3 n][3][6]; quality 1..99. The bytes do not depend on `threads`."""
+    st = np.ascontiguousarray(streams, np.uint16).reshape(-1)
+    h = np.ascontiguousarray(hist, np.uint32)
+    vp, wp = np.ascontiguousarray(value_params, np.float32), np.ascontiguousarray(width_params, np.float32)
+    n_tiles = -(-width // tile_w) * -(-height // tile_h)
+    planes = 3 * n_tiles
+    assert h.size == planes * 10240 and vp.size == planes * 18 and wp.size == planes * 18 and st.size == n_tiles * (n_luma + 2 * n_chroma)
+    n = C.c_size_t(0)
+    err = C.create_string_buffer(256)
+    out = np.empty(st.size * 4 + planes * (10 * 2070 + 256) + n_tiles * 72 + 64, np.uint8)
+    args = (width, height, tile_w, tile_h, _arg(3, False, quality, True, True), _p(st), n_luma, n_chroma, _p(h), _p(vp), _p(wp), threads)
+    L = load_library()
+    rc = L.fri_tiled_encode_from_streams420(*args, _p(out), out.size, C.addressof(n), err, 256)
+    if rc == -3:
+        out = np.empty(n.value, np.uint8)
+        rc = L.fri_tiled_encode_from_streams420(*args, _p(out), out.size, C.addressof(n), err, 256)
+    if rc != 0:
+        raise EmitError(err.value.decode() or f"fri_tiled_encode_from_streams420: {rc}")
+    return out[: n.value].tobytes()
 
 
 def tiled_encode_from_streams(width, height, tile_w, tile_h, streams, hist, value_params, width_params, rct=False, quality=0, ycbcr=False, threads=0):
@@ -326,7 +370,8 @@ def tiled_info(frv):
 
 def tiled_decode(frv, threads=0):
     """fri_tiled_decode: (TiledInfo, coefs int32 [n_tiles][C][F][512] with None = INT32_MIN) - what PlanTiled.decode_image_tiled takes. Tiles are decoded on
-    `threads` workers (0: the hardware concurrency, capped at 16)."""
+    `threads` workers (0: the hardware concurrency, capped at 16). A tiled 4:2:0 file (TiledInfo.s420): coefs is flat and in plane order, [n][F_y][512] then
+    [n][2][F_c][512] - what PlanTiled420.decode_image_tiled420 takes."""
     data = np.frombuffer(frv, np.uint8)
     info = np.zeros(8, np.uint32)
     err = C.create_string_buffer(256)
@@ -335,7 +380,7 @@ def tiled_decode(frv, threads=0):
     if rc != -3:
         raise EmitError(err.value.decode() or f"fri_tiled_decode: {rc}")
     ti = _tiled_info(info)
-    coefs = np.empty((ti[4] * ti[5], ti[6], ti[7], 512), np.int32)
+    coefs = _tiled_coefs(ti, ti[4] * ti[5])
     rc = L.fri_tiled_decode(_p(data), data.size, threads, _p(info), _p(coefs), coefs.size, err, 256)
     if rc != 0:
         raise EmitError(err.value.decode() or f"fri_tiled_decode: {rc}")
@@ -354,7 +399,8 @@ def tiled_region_tiles(width, height, tile_w, tile_h, x, y, w, h):
 
 def tiled_decode_region(frv, x, y, w, h, threads=0):
     """fri_tiled_decode_region: (TiledInfo, (i0, j0, ni, nj), coefs int32 [nj ni][C][F][512]) - what PlanTiled.decode_region_tiled takes. The file is checked as
-    tiled_decode checks it; only the tiles the region touches are decoded, and damage inside the body of an untouched tile is not looked at."""
+    tiled_decode checks it; only the tiles the region touches are decoded, and damage inside the body of an untouched tile is not looked at. A tiled 4:2:0 file:
+    coefs is flat and in the sub-grid's plane order - what PlanTiled420.decode_region_tiled420 takes."""
     data = np.frombuffer(frv, np.uint8)
     info, tiles = np.zeros(8, np.uint32), np.zeros(4, np.uint32)
     err = C.create_string_buffer(256)
@@ -363,7 +409,7 @@ def tiled_decode_region(frv, x, y, w, h, threads=0):
     if rc != -3:
         raise EmitError(err.value.decode() or f"fri_tiled_decode_region: {rc}")
     ti = _tiled_info(info)
-    coefs = np.empty((int(tiles[2]) * int(tiles[3]), ti[6], ti[7], 512), np.int32)
+    coefs = _tiled_coefs(ti, int(tiles[2]) * int(tiles[3]))
     rc = L.fri_tiled_decode_region(_p(data), data.size, threads, x, y, w, h, _p(info), _p(tiles), _p(coefs), coefs.size, err, 256)
     if rc != 0:
         raise EmitError(err.value.decode() or f"fri_tiled_decode_region: {rc}")

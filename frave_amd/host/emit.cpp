@@ -1061,6 +1061,44 @@ std::string encode_tiled_from_streams(uint32_t width, uint32_t height, uint32_t 
     return "";
 }
 
+std::string encode_tiled_from_streams420(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t quality, const uint16_t *streams, size_t n_luma,
+                                         size_t n_chroma, const uint32_t *hist, const float *value_params, const float *width_params, unsigned threads,
+                                         std::vector<uint8_t> &out) {
+    if (!width || !height || !tile_w || !tile_h || quality < 1 || quality > 99) return "invalid argument";
+    const uint64_t nx = ((uint64_t)width + tile_w - 1) / tile_w, ny = ((uint64_t)height + tile_h - 1) / tile_h;
+    if (nx * ny > 0xFFFFFFFFull) return "invalid argument";
+    const size_t n = (size_t)(nx * ny);
+    { // the two tile lattices, once: every tile's streams are streams of these
+        uint32_t cells = 0;
+        uint64_t want_y = 0, want_c = 0;
+        std::string ge = lattice_counts(tile_w, tile_h, cells, want_y);
+        if (ge.empty()) ge = lattice_counts((uint32_t)(((uint64_t)tile_w + 1) / 2), (uint32_t)(((uint64_t)tile_h + 1) / 2), cells, want_c);
+        if (!ge.empty()) return ge;
+        if (want_y != n_luma) return "n_luma is not the symbol count of the tile_w x tile_h lattice";
+        if (want_c != n_chroma) return "n_chroma is not the symbol count of the lattice of the tile's chroma planes";
+    }
+    std::vector<std::vector<uint8_t>> payload(n);
+    const uint16_t *chroma = streams + n * n_luma;
+    const size_t table = (size_t)kContexts * kAlphabet;
+    const std::string e = for_each_tile(n, threads, [&](size_t t) -> std::string {
+        const size_t plane[3] = {t, n + 2 * t, n + 2 * t + 1}; // plane order: the luma planes, then Cb and Cr tile by tile
+        std::vector<ChannelStream> chans(3);
+        std::vector<ChannelParams> params(3);
+        for (uint32_t ch = 0; ch < 3; ch++) {
+            const uint16_t *stream = ch == 0 ? streams + t * n_luma : chroma + (2 * t + ch - 1) * n_chroma;
+            const std::string ce = encode_channel_from_stream(stream, ch == 0 ? n_luma : n_chroma, hist + plane[ch] * table, chans[ch], true, true);
+            if (!ce.empty()) return "channel " + std::to_string(ch) + ": " + ce;
+            std::memcpy(params[ch].value, value_params + plane[ch] * 18, sizeof(params[ch].value));
+            std::memcpy(params[ch].width, width_params + plane[ch] * 18, sizeof(params[ch].width));
+        }
+        payload[t] = serialize(tile_h, tile_w, kYCbCr, chans, params, false, quality, true, true);
+        return "";
+    });
+    if (!e.empty()) return e;
+    assemble_tiled(width, height, tile_w, tile_h, nx, ny, payload, out);
+    return "";
+}
+
 // A channel from its coded parts (the device coder K11, include/fri_hip.h): serialize reads a context's max_freq_bits and off-distribution list and the data bytes, nothing else
 static std::string channel_from_coded(const uint32_t *words, uint32_t n_words, const uint32_t *models /* [10][4] */, const uint16_t *off_values /* [10][1024] */, ChannelStream &out) {
     if (n_words < 2u * kContexts) return "coded plane: fewer words than the flush of the ten states";
@@ -1161,7 +1199,9 @@ std::string parse_tiled(const uint8_t *b, size_t len, TiledInfo &info, std::vect
         const uint8_t *p = b + offset[t];
         if (std::memcmp(p, "frif", 4) != 0 || get_u32(p + 4) != info.tile_h || get_u32(p + 8) != info.tile_w || get_u32(p + 12) != info.mdat) return kMalformedTiled;
     }
-    if ((cs == kYCbCr && (info.mdat & kMdat420)) || (cs != kLuma && (info.mdat & kMdatAlpha))) return kMalformedTiled; // 4:2:0 and alpha inside tiles are refused
+    info.s420 = cs == kYCbCr && (info.mdat & kMdat420);
+    if (cs != kLuma && (info.mdat & kMdatAlpha)) return kMalformedTiled; // alpha inside tiles is refused
+    if (info.s420 && (!info.ycbcr || info.rct)) return kMalformedTiled;  // 4:2:0 tiles are lossy YCbCr tiles ("Invalid metadata" otherwise)
     if (info.quality >= 100 || (info.ycbcr && (info.rct || info.quality == 0))) return kMalformedTiled;
     return "";
 }
@@ -1185,14 +1225,41 @@ std::string decode_tiled(const uint8_t *b, size_t len, unsigned threads, TiledIn
     if (region && !region_tiles(info.width, info.height, info.tile_w, info.tile_h, *region, tr)) return "invalid region";
     if (range) *range = tr;
     fri::Geometry g; // one geometry and one symbol order for all tiles
-    e = fri::build_geometry(info.tile_w, info.tile_h, info.channels, fri::TilingParams{}, g);
+    e = fri::build_geometry(info.tile_w, info.tile_h, info.s420 ? 1u : info.channels, fri::TilingParams{}, g);
     if (!e.empty()) return e;
     const size_t F = g.centers.size(), plane = F * kNodes, n_tiles = (size_t)tr.ni * tr.nj;
     const auto file_tile = [&](size_t s) { return ((size_t)tr.j0 + s / tr.ni) * info.nx + tr.i0 + s % tr.ni; }; // sub-tile s of the range in the file's grid
     info.n_cells = (uint32_t)F;
-    if (!coefs || coef_cap < n_tiles * info.channels * plane) return too_small = true, "";
     std::vector<int32_t> centers(F * 2);
     for (size_t c = 0; c < F; c++) centers[2 * c] = g.centers[c].x, centers[2 * c + 1] = g.centers[c].y;
+    if (info.s420) { // a tile is a 4:2:0 image: its luma plane on the tile lattice g, Cb and Cr on the lattice of the half-resolution planes; plane order
+        fri::Geometry gc;
+        e = fri::build_geometry((info.tile_w + 1) / 2, (info.tile_h + 1) / 2, 1, fri::TilingParams{}, gc);
+        if (!e.empty()) return e;
+        const size_t Fc = gc.centers.size(), plane_c = Fc * kNodes;
+        info.n_cells_chroma = (uint32_t)Fc;
+        if (!coefs || coef_cap < n_tiles * (plane + 2 * plane_c)) return too_small = true, "";
+        std::vector<int32_t> cc(Fc * 2);
+        for (size_t c = 0; c < Fc; c++) cc[2 * c] = gc.centers[c].x, cc[2 * c + 1] = gc.centers[c].y;
+        const auto order_y = shared_symbol_order(centers.data(), (uint32_t)F), order_c = shared_symbol_order(cc.data(), (uint32_t)Fc);
+        return for_each_tile(n_tiles, threads, [&](size_t s) -> std::string {
+            const size_t t = file_tile(s);
+            ParsedImage img;
+            const std::string de = deserialize(std::vector<uint8_t>(b + offset[t], b + offset[t + 1]), img);
+            if (!de.empty()) return de;
+            if (img.channels.size() != 3 || !img.s420) return kMalformedTiled;
+            for (const ChannelStream &c : img.channels)
+                for (const AnsContext &a : c.contexts)
+                    if (a.max_freq_bits == 0) return "Malformed image bytes"; // fewer than ten EHD segments
+            for (uint32_t ch = 0; ch < 3; ch++) {
+                int32_t *dst = ch == 0 ? coefs + s * plane : coefs + n_tiles * plane + (2 * s + ch - 1) * plane_c;
+                const std::string ce = decode_channel(ch == 0 ? g : gc, ch == 0 ? *order_y : *order_c, img.channels[ch], img.params[ch], dst);
+                if (!ce.empty()) return "channel " + std::to_string(ch) + ": " + ce;
+            }
+            return "";
+        }, file_tile);
+    }
+    if (!coefs || coef_cap < n_tiles * info.channels * plane) return too_small = true, "";
     const auto order = shared_symbol_order(centers.data(), (uint32_t)F);
     return for_each_tile(n_tiles, threads, [&](size_t s) -> std::string {
         const size_t t = file_tile(s);

@@ -200,13 +200,22 @@ struct TiledInfo {
     uint32_t mdat = 0; // the metadata word every tile carries, and what it says:
     uint32_t channels = 0, quality = 0;
     bool rct = false, ycbcr = false;
-    uint32_t n_cells = 0; // F of the tile lattice (decode_tiled only)
+    bool s420 = false;    // every tile is a 4:2:0 image (include/fri_hip.h, "Tiled 4:2:0 coding"): the planes are in plane order
+    uint32_t n_cells = 0; // F of the tile lattice (decode_tiled only); 4:2:0: F_y, of the tile's luma lattice
+    uint32_t n_cells_chroma = 0; // 4:2:0: F_c, of the lattice of the tile's chroma planes (decode_tiled only)
 };
 // streams [n_tiles][channels][n_symbols], hist [n_tiles][channels][10][1024], value_params / width_params [n_tiles][channels][3][6]: what
 // fri_hip_encode_image_tiled_symbols returns. Returns "" or the error ("tile t: channel c: reason" from a tile).
 std::string encode_tiled_from_streams(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t channels, bool rct, uint32_t quality, bool ycbcr,
                                       const uint16_t *streams, size_t n_symbols, const uint32_t *hist, const float *value_params, const float *width_params, unsigned threads,
                                       std::vector<uint8_t> &out);
+// A tiled 4:2:0 file (include/fri_hip.h, "Tiled 4:2:0 coding"): every payload is what fri_emit_encode_image_from_streams writes for the tile with
+// 3 | FRI_EMIT_YCBCR | FRI_EMIT_420 | FRI_EMIT_QUALITY(quality) | FRI_EMIT_EMPTY_OK. The arrays are in plane order - plane(t, Y) = t, plane(t, Cb) = n + 2 t,
+// plane(t, Cr) = n + 2 t + 1: streams [n][n_luma] then [n][2][n_chroma], hist [3 n][10][1024], value_params / width_params [3 n][3][6] - what
+// fri_hip_encode_image_tiled420_symbols returns. n_luma and n_chroma must be the symbol counts of the two tile lattices.
+std::string encode_tiled_from_streams420(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t quality, const uint16_t *streams, size_t n_luma,
+                                         size_t n_chroma, const uint32_t *hist, const float *value_params, const float *width_params, unsigned threads,
+                                         std::vector<uint8_t> &out);
 // The same file from planes the device coded (K11; include/fri_hip.h, fri_hip_rans_encode_planes_dev, has the layouts): words [n_tiles channels][word_stride] of which
 // the first n_words [n_tiles channels] of a plane are its rANS data as little-endian words, models [n_tiles channels][10][4] = {max_freq_bits, n_off, -, -}, off_values
 // [n_tiles channels][10][1024] of which a context's first n_off are its list. Through the same serialize: byte for byte encode_tiled_from_streams's file when the planes
@@ -230,6 +239,7 @@ struct TileRange {
 };
 // false for a zero size or a region that leaves the width x height image (compared in 64 bits)
 bool region_tiles(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, const Region &r, TileRange &out);
+// A tiled 4:2:0 file (info.s420): coefs in plane order, [n][F_y][512] then [n][2][F_c][512] with n the tiles decoded - the whole grid or the region's sub-grid.
 // coefs [n_tiles][channels][F][512]. too_small: coefs is NULL or coef_cap (elements) does not hold them - `info` is filled, nothing is decoded.
 // With a region: the file is checked as without one, then only the tiles the region touches are decoded, coefs [nj ni][channels][F][512] in the sub-grid's order;
 // `range` is filled whenever `info` is. "invalid region" for a region region_tiles refuses. A tile's error names its index in the file's grid.

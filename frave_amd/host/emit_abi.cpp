@@ -225,7 +225,7 @@ int fri_emit_decode_image(const uint8_t *frv, size_t len, uint32_t info[4], int3
 namespace {
 void fill_tiled_info(const TiledInfo &t, uint32_t info[8]) {
     info[0] = t.width, info[1] = t.height, info[2] = t.tile_w, info[3] = t.tile_h, info[4] = t.nx, info[5] = t.ny;
-    info[6] = channels_info(t.channels, t.rct, t.quality, t.ycbcr, false, false), info[7] = t.n_cells;
+    info[6] = channels_info(t.channels, t.rct, t.quality, t.ycbcr, t.s420, false), info[7] = t.n_cells;
 }
 } // namespace
 
@@ -241,6 +241,24 @@ int fri_tiled_encode_from_streams(uint32_t width, uint32_t height, uint32_t tile
         return fail(err, err_cap, "invalid argument");
     std::vector<uint8_t> bytes;
     const std::string e = encode_tiled_from_streams(width, height, tile_w, tile_h, channels, rct, quality, ycbcr, streams, (size_t)n_symbols, hist, value_params, width_params, threads, bytes);
+    if (e == "invalid argument") return fail(err, err_cap, e);
+    if (!e.empty()) return fail(err, err_cap, e, -2);
+    *len = bytes.size();
+    if (!out || cap < bytes.size()) return -3;
+    std::memcpy(out, bytes.data(), bytes.size());
+    return 0;
+}
+
+int fri_tiled_encode_from_streams420(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t channels_arg, const uint16_t *streams, uint64_t n_luma,
+                                     uint64_t n_chroma, const uint32_t *hist, const float *value_params, const float *width_params, uint32_t threads, uint8_t *out, size_t cap,
+                                     size_t *len, char *err, size_t err_cap) {
+    uint32_t channels, quality;
+    bool rct, ycbcr, s420 = false, empty_ok = false;
+    // 3 | FRI_EMIT_YCBCR | FRI_EMIT_420 | FRI_EMIT_QUALITY(1..99) and nothing else (no place for alpha; FRI_EMIT_EMPTY_OK is always on and may be passed)
+    if (!streams || !hist || !value_params || !width_params || !len || !split_channels(channels_arg, channels, rct, quality, ycbcr, &s420, nullptr, &empty_ok) || !s420)
+        return fail(err, err_cap, "invalid argument");
+    std::vector<uint8_t> bytes;
+    const std::string e = encode_tiled_from_streams420(width, height, tile_w, tile_h, quality, streams, (size_t)n_luma, (size_t)n_chroma, hist, value_params, width_params, threads, bytes);
     if (e == "invalid argument") return fail(err, err_cap, e);
     if (!e.empty()) return fail(err, err_cap, e, -2);
     *len = bytes.size();

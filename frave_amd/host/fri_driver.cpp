@@ -22,13 +22,15 @@
 //                                                            --tile-size T (any mode flag but --420; no alpha): the image as a batch of independently coded tiles
 //                                                            of about T x T (fri_hip_tile_shape), a `frit` file; --psnr / --ssim / --size search on the tiled plan
 //                                                            (fri_hip_search_quality*_tiled): the target holds for the file that is written
+//                                                            --tile-size-420 T --quality Q: the tiles are 4:2:0 images (fri_hip_tile_shape420, K12); no targets.
+//                                                            --tile-size T --420 stays refused: tiled 4:2:0 has this option of its own
 //                                                            --device-rans (with --tile-size): the rANS coder runs on the device too (K11), the host writes the
 //                                                            container around the coded planes - the same file
 //   fri_driver decode-file <in.frv> <out.pgm|.ppm|.bmp|.pam> [--region X,Y,W,H]  (.pam for a file with an alpha plane, and for no other) container -> rANS / context decoding on the host -> dequantisation + inverse
 //                                                            transform on the device (fri-cli decode, crates/fri-cli/src/commands/decode.rs); a flagged file
 //                                                            comes back as RGB, a lossy file with its quality's matrix and the midpoint dequantiser
 //                                                            --region X,Y,W,H: only that rectangle of the image (FRIDecoder::decode_region) - of a `frit` file only
-//                                                            the tiles it touches are decoded; a `frif` file is decoded whole and cropped; no 4:2:0 or alpha file
+//                                                            the tiles it touches are decoded; a `frif` file is decoded whole and cropped; no untiled 4:2:0 file and no alpha file
 //   fri_driver batch <width> <height> <channels> <n_images> [--gpus N]
 //                                                            BASELINE config 3: host batch with H2D / kernel / D2H overlap; with --gpus N
 //                                                            BASELINE config 4: the batch sharded over N GPUs of this node (image i -> GPU i mod N,
@@ -521,6 +523,43 @@ static int encode_image_tiled_to_file(const std::vector<uint8_t> &img, uint32_t 
     return 0;
 }
 
+// encode-file --tile-size-420 T --quality Q: the image as a batch of independently coded 4:2:0 tiles (libfri::encode_bytes_tiled420; a `frit` file whose tiles are
+// 4:2:0 images). Self-check: the file decodes (FRIDecoder) to the direct device round trip (libfri::round_trip_tiled420: K12's split, the forward kernel plane by
+// plane, fri_hip_decode_image_tiled420).
+static int encode_image_tiled420_to_file(const std::vector<uint8_t> &img, uint32_t w, uint32_t h, const libfri::EncoderOpts &opts, uint32_t tile_size, const char *out_path) {
+    auto t0 = std::chrono::steady_clock::now();
+    auto enc = libfri::encode_bytes_tiled420(img, h, w, opts.quality, tile_size, opts.device);
+    const double t_enc = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (!enc.ok) {
+        std::fprintf(stderr, "%s\n", enc.error.c_str());
+        return 1;
+    }
+    const std::vector<uint8_t> &bytes = enc.value.bytes;
+    auto back = libfri::FRIDecoder().decode(bytes, opts);
+    auto direct = libfri::round_trip_tiled420(img, h, w, enc.value.tile_w, enc.value.tile_h, enc.value.quality, opts.device);
+    if (!direct.ok) {
+        std::fprintf(stderr, "self-check failed: direct round trip: %s\n", direct.error.c_str());
+        return 1;
+    }
+    if (!back.ok || back.value.metadata.width != w || back.value.metadata.height != h || back.value.data != direct.value.data) {
+        std::fprintf(stderr, "self-check failed: %s\n", back.ok ? "decoded image differs from the direct tiled 4:2:0 round trip" : back.error.c_str());
+        return 1;
+    }
+    if (FILE *f = std::fopen(out_path, "wb")) {
+        std::fwrite(bytes.data(), 1, bytes.size(), f);
+        std::fclose(f);
+    } else {
+        std::fprintf(stderr, "cannot write %s\n", out_path);
+        return 1;
+    }
+    std::printf("%ux%ux3 in %u x %u 4:2:0 tiles of %ux%u: %zu bytes, %.3f bits per pixel; device chain and emit %.3f s; self-check: decodes to the direct tiled 4:2:0 round trip\n", w, h,
+                enc.value.nx, enc.value.ny, enc.value.tile_w, enc.value.tile_h, bytes.size(), 8.0 * bytes.size() / ((double)w * h), t_enc);
+    double sse = 0;
+    for (size_t i = 0; i < img.size(); i++) sse += ((double)back.value.data[i] - img[i]) * ((double)back.value.data[i] - img[i]);
+    std::printf("quality %d in YCbCr 4:2:0: PSNR %.2f dB\n", enc.value.quality, sse > 0 ? 10.0 * std::log10(255.0 * 255.0 * (double)img.size() / sse) : HUGE_VAL);
+    return 0;
+}
+
 int main(int argc, char **argv) {
     if (argc >= 4 && std::string(argv[1]) == "encode-file") {
         std::vector<uint8_t> img;
@@ -533,8 +572,8 @@ int main(int argc, char **argv) {
         }
         libfri::EncoderOpts file_opts; // parameters are fitted on the device sums (fit_parameters defaults to true)
         double bpp = 0;
-        bool has_size = false, has_bpp = false, has_ssim = false, sub420 = false, clean_alpha = false, tiled = false;
-        long tile_size = 0;
+        bool has_size = false, has_bpp = false, has_ssim = false, sub420 = false, clean_alpha = false, tiled = false, tiled420 = false;
+        long tile_size = 0, tile_size420 = 0;
         for (int i = 4; i < argc; i++) {
             const std::string a = argv[i];
             if (a == "--rct") file_opts.colour_transform = true;
@@ -547,6 +586,7 @@ int main(int argc, char **argv) {
             else if (a == "--size" && i + 1 < argc) file_opts.target_bytes = std::strtoull(argv[++i], nullptr, 10), has_size = true;
             else if (a == "--bpp" && i + 1 < argc) bpp = std::atof(argv[++i]), has_bpp = true;
             else if (a == "--tile-size" && i + 1 < argc) tile_size = std::atol(argv[++i]), tiled = true;
+            else if (a == "--tile-size-420" && i + 1 < argc) tile_size420 = std::atol(argv[++i]), tiled420 = true;
             else if (a == "--device-rans") file_opts.device_rans = true;
             else {
                 std::fprintf(stderr, "encode-file: unknown option %s\n", a.c_str());
@@ -559,6 +599,18 @@ int main(int argc, char **argv) {
             return 2;
         }
         const bool sized = has_size || has_bpp;
+        if (tiled420) { // tiled 4:2:0 has an option of its own: --tile-size T --420 stays refused (below)
+            if (file_opts.target_psnr > 0 || has_ssim || sized) {
+                std::fprintf(stderr, "encode-file: --tile-size-420 takes --quality Q only: --psnr, --ssim, --size and --bpp are refused (the searches and the size estimate on tiled 4:2:0 are out of scope)\n");
+                return 2;
+            }
+            if (tile_size420 < 1 || tile_size420 > 65535 || rgba || fc != 3 || tiled || sub420 || file_opts.ycbcr || file_opts.colour_transform || file_opts.device_rans || clean_alpha ||
+                file_opts.quality < 1) {
+                std::fprintf(stderr, "encode-file: --tile-size-420 T (1..65535) takes an RGB image (PPM or BMP) and --quality Q (1..99), and no other mode flag\n");
+                return 2;
+            }
+            return encode_image_tiled420_to_file(img, fw, fh, file_opts, (uint32_t)tile_size420, argv[3]);
+        }
         if (has_ssim && (!(file_opts.target_ssim > 0 && file_opts.target_ssim <= 1) || file_opts.quality || file_opts.target_psnr > 0 || sized || file_opts.colour_transform)) {
             std::fprintf(stderr, "encode-file: --ssim S (0 < S <= 1), not with --quality, --psnr, --size, --bpp or --rct\n");
             return 2;
@@ -582,7 +634,7 @@ int main(int argc, char **argv) {
             return 2;
         }
         if (tiled && (tile_size < 1 || tile_size > 65535 || rgba || sub420)) {
-            std::fprintf(stderr, "encode-file: --tile-size T (1..65535) takes a PGM, PPM or BMP and every mode flag but --420; no alpha (4:2:0 and alpha in tiles are out of scope)\n");
+            std::fprintf(stderr, "encode-file: --tile-size T (1..65535) takes a PGM, PPM or BMP and every mode flag but --420; no alpha (alpha in tiles is out of scope; tiled 4:2:0 is --tile-size-420 T --quality Q)\n");
             return 2;
         }
         if (file_opts.device_rans && !tiled) {
@@ -656,7 +708,7 @@ int main(int argc, char **argv) {
         return 0;
     }
     if (argc < 5) {
-        std::fprintf(stderr, "usage: %s roundtrip|encode|batch|batch-frv <width> <height> <channels> [n_images | out.frv]\n       %s encode-file <in.pgm|in.ppm|in.bmp|in.pam> <out.frv> [--rct | [--ycbcr | --420] (--quality Q | --psnr DB | --ssim S | --size BYTES | --bpp B)] [--clean-alpha] [--tile-size T [--device-rans]]\n       %s decode-file <in.frv> <out.pgm|out.ppm|out.bmp|out.pam> [--region X,Y,W,H]\n", argv[0], argv[0], argv[0]);
+        std::fprintf(stderr, "usage: %s roundtrip|encode|batch|batch-frv <width> <height> <channels> [n_images | out.frv]\n       %s encode-file <in.pgm|in.ppm|in.bmp|in.pam> <out.frv> [--rct | [--ycbcr | --420] (--quality Q | --psnr DB | --ssim S | --size BYTES | --bpp B)] [--clean-alpha] [--tile-size T [--device-rans]]\n       %s encode-file <in.ppm|in.bmp> <out.frv> --tile-size-420 T --quality Q   (tiled 4:2:0; --tile-size T --420 stays refused: the option of its own is this one)\n       %s decode-file <in.frv> <out.pgm|out.ppm|out.bmp|out.pam> [--region X,Y,W,H]\n", argv[0], argv[0], argv[0], argv[0]);
         return 2;
     }
     const std::string cmd = argv[1];

@@ -471,6 +471,10 @@ struct TiledPlanDelete {
     void operator()(fri_hip_plan_tiled *p) const { fri_hip_plan_tiled_destroy(p); }
 };
 using TiledPlan = std::unique_ptr<fri_hip_plan_tiled, TiledPlanDelete>;
+struct Tiled420PlanDelete {
+    void operator()(fri_hip_plan_tiled420 *p) const { fri_hip_plan_tiled420_destroy(p); }
+};
+using Tiled420Plan = std::unique_ptr<fri_hip_plan_tiled420, Tiled420PlanDelete>;
 
 // a `frit` file: the tiles' planes from the emitter's workers, then the inverse kernel over all tiles and the merge. With a region: only the tiles it touches, on
 // both sides (emit::decode_tiled with the region, fri_hip_decode_region_tiled), and the raster is the region's.
@@ -485,11 +489,27 @@ Result<RasterImage> decode_tiled_bytes(const std::vector<uint8_t> &data, const E
     bool too_small = false;
     std::string e = emit::decode_tiled(data.data(), data.size(), 0, ti, nullptr, 0, too_small, region, &range); // header, table, geometry
     if (!e.empty()) return fail(e);
-    std::vector<int32_t> coefs((size_t)range.ni * range.nj * ti.channels * ti.n_cells * FRI_HIP_CELL_SIZE);
+    const size_t tile_cells = ti.s420 ? (size_t)ti.n_cells + 2 * (size_t)ti.n_cells_chroma : (size_t)ti.channels * ti.n_cells; // (4:2:0: plane order, F_y + 2 F_c per tile)
+    std::vector<int32_t> coefs((size_t)range.ni * range.nj * tile_cells * FRI_HIP_CELL_SIZE);
     e = emit::decode_tiled(data.data(), data.size(), 0, ti, coefs.data(), coefs.size(), too_small, region, &range);
     if (!e.empty() || too_small) return fail(e.empty() ? "coefficient array does not match the tile geometry" : e);
     Device dev(opts.device);
     if (!dev.ok()) return fail(dev.error());
+    if (ti.s420) { // 4:2:0 tiles: the inverse kernel on both inner plans at the file's quality, then K12's merge
+        fri_hip_plan_tiled420 *raw420 = nullptr;
+        if (const int rc = fri_hip_plan_tiled420_create(dev.ctx(), ti.width, ti.height, ti.tile_w, ti.tile_h, FRI_HIP_TILED_ALLOW_HOLES, &raw420); rc != FRI_HIP_OK) return fail(dev.describe(rc));
+        Tiled420Plan plan420(raw420);
+        if (fri_hip_plan_num_cells(fri_hip_plan_tiled420_luma(raw420)) != ti.n_cells || fri_hip_plan_num_cells(fri_hip_plan_tiled420_chroma(raw420)) != ti.n_cells_chroma)
+            return fail("coefficient array does not match the tile geometry");
+        const uint32_t out_w = region ? region->w : ti.width, out_h = region ? region->h : ti.height;
+        r.value.metadata = ImageMetadata{out_h, out_w, ColorSpace::RGB};
+        r.value.data.resize((size_t)out_w * out_h * 3);
+        const int rc = region ? fri_hip_decode_region_tiled420(raw420, coefs.data(), (int)ti.quality, region->x, region->y, region->w, region->h, r.value.data.data())
+                              : fri_hip_decode_image_tiled420(raw420, coefs.data(), (int)ti.quality, r.value.data.data());
+        if (rc != FRI_HIP_OK) return fail(dev.describe(rc));
+        r.ok = true;
+        return r;
+    }
     fri_hip_plan_tiled *raw = nullptr;
     // (a file may hold tiles with holes: whoever wrote it asked for them)
     if (const int rc = fri_hip_plan_tiled_create(dev.ctx(), ti.width, ti.height, ti.channels, ti.tile_w, ti.tile_h, FRI_HIP_TILED_ALLOW_HOLES, &raw); rc != FRI_HIP_OK) return fail(dev.describe(rc));
@@ -1220,6 +1240,96 @@ Result<RasterImage> round_trip_tiled(const std::vector<uint8_t> &pixels, uint32_
     r.value.metadata = ImageMetadata{height, width, channels == 1 ? ColorSpace::Luma : ColorSpace::RGB};
     r.value.data.resize(pixels.size());
     if (rc == FRI_HIP_OK) rc = fri_hip_decode_image_tiled(raw, coefs.data(), qm, r.value.data.data());
+    if (rc != FRI_HIP_OK) r.error = dev.describe(rc);
+    r.ok = rc == FRI_HIP_OK;
+    return r;
+}
+
+// ---- tiled 4:2:0 coding ----------------------------------------------------------------------------------------------------------------------------
+Result<EncodedTiled> encode_bytes_tiled420(const std::vector<uint8_t> &rgb, uint32_t height, uint32_t width, int quality, uint32_t tile_size, int device, unsigned threads) {
+    Result<EncodedTiled> r;
+    auto fail = [&](const std::string &why) {
+        r.error = "Failed to decode: " + why; // sic, encoder.rs:106
+        return r;
+    };
+    if (quality < 1 || quality > 99) return fail("tiled 4:2:0 coding needs a quality of 1..99");
+    if (!width || !height || rgb.size() != (size_t)width * height * 3) return fail("tiled 4:2:0 coding takes width x height RGB pixels");
+    uint32_t tw = 0, th = 0;
+    if (const int rc = fri_hip_tile_shape420(width, height, tile_size, &tw, &th); rc != FRI_HIP_OK)
+        return fail(std::string("no tile shape of that size owns every pixel in both lattices: ") + fri_hip_strerror(rc));
+    Device dev(device);
+    if (!dev.ok()) return fail(dev.error());
+    fri_hip_plan_tiled420 *raw = nullptr;
+    if (const int rc = fri_hip_plan_tiled420_create(dev.ctx(), width, height, tw, th, 0, &raw); rc != FRI_HIP_OK) return fail(dev.describe(rc));
+    Tiled420Plan plan(raw);
+    fri_hip_plan *luma = fri_hip_plan_tiled420_luma(raw), *chroma = fri_hip_plan_tiled420_chroma(raw);
+    for (fri_hip_plan *inner : {luma, chroma})
+        if (const std::string e = set_plan_stream_order(inner, dev); !e.empty()) return fail(e);
+    uint32_t grid[4];
+    fri_hip_plan_tiled420_grid(raw, grid);
+    r.value.tile_w = tw, r.value.tile_h = th, r.value.nx = grid[0], r.value.ny = grid[1];
+    const size_t n = (size_t)grid[0] * grid[1], planes = 3 * n;
+    const uint64_t n_y = fri_hip_plan_num_some(luma), n_c = fri_hip_plan_num_some(chroma);
+    std::vector<uint16_t> symbols(n * (size_t)(n_y + 2 * n_c));
+    std::vector<uint32_t> hist(planes * CONTEXT_AMOUNT * ALPHABET_SIZE);
+    std::vector<float> vp(planes * 18), wp(planes * 18);
+    std::vector<uint64_t> oob(planes, 0);
+    if (const int rc = fri_hip_encode_image_tiled420_symbols(raw, rgb.data(), quality, vp.data(), wp.data(), symbols.data(), hist.data(), oob.data()); rc != FRI_HIP_OK)
+        return fail(dev.describe(rc));
+    for (uint64_t v : oob)
+        if (v) return fail("symbol outside the 1024-entry alphabet"); // the reference panics: bump_freq, entropy_coding.rs:99
+    const std::string e = emit::encode_tiled_from_streams420(width, height, tw, th, (uint32_t)quality, symbols.data(), (size_t)n_y, (size_t)n_c, hist.data(), vp.data(), wp.data(), threads,
+                                                             r.value.bytes);
+    if (!e.empty()) return fail(e);
+    r.value.quality = quality, r.value.ycbcr = true;
+    r.ok = true;
+    return r;
+}
+
+Result<RasterImage> round_trip_tiled420(const std::vector<uint8_t> &rgb, uint32_t height, uint32_t width, uint32_t tile_w, uint32_t tile_h, int quality, int device) {
+    Result<RasterImage> r;
+    int32_t qm[32];
+    if (!width || !height || !tile_w || !tile_h || rgb.size() != (size_t)width * height * 3 || quality < 1 || quality > 99 || fri_hip_quality_matrix(quality, qm) != FRI_HIP_OK) {
+        r.error = "invalid argument";
+        return r;
+    }
+    Device dev(device);
+    if (!dev.ok()) {
+        r.error = dev.error();
+        return r;
+    }
+    fri_hip_plan_tiled420 *raw = nullptr;
+    int rc = fri_hip_plan_tiled420_create(dev.ctx(), width, height, tile_w, tile_h, FRI_HIP_TILED_ALLOW_HOLES, &raw);
+    if (rc != FRI_HIP_OK) {
+        r.error = dev.describe(rc);
+        return r;
+    }
+    Tiled420Plan plan(raw);
+    fri_hip_plan *luma = fri_hip_plan_tiled420_luma(raw), *chroma = fri_hip_plan_tiled420_chroma(raw);
+    uint32_t grid[4];
+    fri_hip_plan_tiled420_grid(raw, grid);
+    const size_t n = (size_t)grid[0] * grid[1], y_bytes = fri_hip_plan_pixel_bytes(luma), c_bytes = fri_hip_plan_pixel_bytes(chroma);
+    const size_t fy = fri_hip_plan_coef_count(luma), fc = fri_hip_plan_coef_count(chroma);
+    // the device split (K12), then the forward kernel plane by plane in plane order: no scan, no coder
+    uint8_t *d_rgb = nullptr, *d_y = nullptr, *d_c = nullptr;
+    std::vector<uint8_t> y_tiles(n * y_bytes), c_tiles(2 * n * c_bytes);
+    auto release = [&] { (void)hipFree(d_rgb), (void)hipFree(d_y), (void)hipFree(d_c); };
+    if (hipMalloc((void **)&d_rgb, rgb.size()) != hipSuccess || hipMalloc((void **)&d_y, y_tiles.size()) != hipSuccess || hipMalloc((void **)&d_c, c_tiles.size()) != hipSuccess ||
+        hipMemcpy(d_rgb, rgb.data(), rgb.size(), hipMemcpyHostToDevice) != hipSuccess) {
+        release();
+        r.error = "device allocation failed";
+        return r;
+    }
+    rc = fri_hip_split_tiles420_dev(raw, d_rgb, d_y, d_c, nullptr);
+    if (rc == FRI_HIP_OK && (hipMemcpy(y_tiles.data(), d_y, y_tiles.size(), hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(c_tiles.data(), d_c, c_tiles.size(), hipMemcpyDeviceToHost) != hipSuccess))
+        rc = FRI_HIP_ERR_HIP;
+    release();
+    std::vector<int32_t> coefs(n * (fy + 2 * fc));
+    for (size_t t = 0; t < n && rc == FRI_HIP_OK; t++) rc = fri_hip_transform_quant(luma, y_tiles.data() + t * y_bytes, qm, coefs.data() + t * fy);
+    for (size_t k = 0; k < 2 * n && rc == FRI_HIP_OK; k++) rc = fri_hip_transform_quant(chroma, c_tiles.data() + k * c_bytes, qm, coefs.data() + n * fy + k * fc);
+    r.value.metadata = ImageMetadata{height, width, ColorSpace::RGB};
+    r.value.data.resize(rgb.size());
+    if (rc == FRI_HIP_OK) rc = fri_hip_decode_image_tiled420(raw, coefs.data(), quality, r.value.data.data());
     if (rc != FRI_HIP_OK) r.error = dev.describe(rc);
     r.ok = rc == FRI_HIP_OK;
     return r;

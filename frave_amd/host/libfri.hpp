@@ -289,16 +289,25 @@ Result<EncodedTiled> encode_bytes_tiled(const std::vector<uint8_t> &pixels, uint
 Result<RasterImage> round_trip_tiled(const std::vector<uint8_t> &pixels, uint32_t height, uint32_t width, uint32_t channels, uint32_t tile_w, uint32_t tile_h, int quality, bool rct,
                                      bool ycbcr, int device = 0);
 
+// Tiled 4:2:0 coding (include/fri_hip.h, "Tiled 4:2:0 coding") of width x height RGB pixels at `quality` (1..99): tiles of about tile_size x tile_size at which
+// both lattices own every pixel (fri_hip_tile_shape420), the device splits and codes them in two batches (fri_hip_encode_image_tiled420_symbols), the emitter codes
+// them on `threads` workers (emit::encode_tiled_from_streams420). The result's ycbcr is true. No targets: the searches on tiled 4:2:0 are out of scope.
+// FRIDecoder::decode and decode_region read such files.
+Result<EncodedTiled> encode_bytes_tiled420(const std::vector<uint8_t> &rgb, uint32_t height, uint32_t width, int quality, uint32_t tile_size, int device = 0, unsigned threads = 0);
+// The direct round trip without the entropy coder, for self-checks: fri_hip_split_tiles420_dev, the forward kernel on both inner plans over all planes, then
+// fri_hip_decode_image_tiled420 - what such a file decodes to.
+Result<RasterImage> round_trip_tiled420(const std::vector<uint8_t> &rgb, uint32_t height, uint32_t width, uint32_t tile_w, uint32_t tile_h, int quality, int device = 0);
+
 class FRIDecoder { // decoder.rs:44-59
   public:
     // the whole pipeline of decoder.rs:16-40: EncodedImage -> EntropyDecoding -> Dequantization -> WaveletTransform -> RawImage.
     // Container parsing and entropy decoding run on the host, dequantisation + inverse transform on the device. A tiled file (`frit`) is recognised by its magic:
-    // fri_tiled_decode's workers, then fri_hip_decode_image_tiled.
+    // fri_tiled_decode's workers, then fri_hip_decode_image_tiled - or, for a tiled 4:2:0 file, fri_hip_decode_image_tiled420.
     Result<RasterImage> decode(const std::vector<uint8_t> &data, const EncoderOpts &opts = EncoderOpts());
     // The region x, y, w, h (image pixels; include/fri_emit.h, "Region decode") of the image `data` holds: the crop [y : y + h, x : x + w] of what decode returns,
     // as a raster of w x h. A tiled file pays for the tiles the region touches and no others: fri_tiled_decode_region's workers, then
     // fri_hip_decode_region_tiled. An ordinary `frif` file has no tiles: it is decoded whole and cropped on the host, which buys nothing and only makes the call
-    // work on any file. 4:2:0 and alpha files are refused.
+    // work on any file. Untiled 4:2:0 files and alpha files are refused; a tiled 4:2:0 file goes through fri_hip_decode_region_tiled420.
     Result<RasterImage> decode_region(const std::vector<uint8_t> &data, uint32_t x, uint32_t y, uint32_t w, uint32_t h, const EncoderOpts &opts = EncoderOpts());
     // from the WaveletTransform stage on
     Result<RasterImage> decode(const WaveletImage &image, const EncoderOpts &opts = EncoderOpts());

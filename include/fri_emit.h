@@ -69,8 +69,9 @@
  *            32  u64 offset[ny nx + 1]
  * The payloads follow the table: tile t = j nx + i is the bytes [offset[t], offset[t + 1]). offset[0] = 32 + 8 (ny nx + 1), offset[ny nx] is the file length and
  * the offsets are strictly increasing. A payload is a complete `frif` file of a tile_h x tile_w image: exactly what fri_emit_encode_image_from_streams writes
- * for that tile's streams, histograms and parameters with FRI_EMIT_EMPTY_OK set. All tiles carry the same metadata word. 4:2:0 and alpha inside tiles are
- * refused, by the encoder (-1) and by the decoder ("Malformed tiled image"). fri_emit_decode_image does not know the magic: a `frit` file is "Invalid signature"
+ * for that tile's streams, histograms and parameters with FRI_EMIT_EMPTY_OK set. All tiles carry the same metadata word. Alpha inside tiles is refused, by
+ * the encoder (-1) and by the decoder ("Malformed tiled image"); 4:2:0 inside tiles is "Tiled 4:2:0" below: fri_tiled_encode_from_streams and
+ * fri_tiled_encode_from_coded keep refusing FRI_EMIT_420 (-1), such files have an encoder of their own. fri_emit_decode_image does not know the magic: a `frit` file is "Invalid signature"
  * to it. The size of such a file is estimated from the tiles' histograms, without the coder, by fri_hip_estimate_size_tiled_dev (include/fri_hip.h), which knows
  * the rule of FRI_EMIT_EMPTY_OK.
  *
@@ -81,7 +82,26 @@
  *     ni = (x + w - 1) / tile_w - i0 + 1       nj = (y + h - 1) / tile_h - j0 + 1
  * stored row-major: sub-tile s = b ni + a is tile (j0 + b) nx + (i0 + a) of the file. The region raster is [h][w][C] without a pitch; its pixel (ry, rx) is image
  * pixel (y + ry, x + rx), which is pixel (y + ry - j tile_h, x + rx - i tile_w) of tile (j, i): no replicated pixel is ever copied. By definition the region
- * raster is the crop [y : y + h, x : x + w] of what fri_hip_decode_image_tiled returns for the same file. */
+ * raster is the crop [y : y + h, x : x + w] of what fri_hip_decode_image_tiled returns for the same file.
+ *
+ * Tiled 4:2:0 (fri_tiled_encode_from_streams420 below; include/fri_hip.h, "Tiled 4:2:0 coding", has the device side): the `frit` container is unchanged and stays
+ * at version 1. In a tiled 4:2:0 file every payload is a `frif` file of a tile_h x tile_w image with colour space YCbCr, metadata bits 1 and 2 set, and a quality of
+ * 1..99: exactly what fri_emit_encode_image_from_streams writes for that tile with 3 | FRI_EMIT_YCBCR | FRI_EMIT_420 | FRI_EMIT_QUALITY(q) | FRI_EMIT_EMPTY_OK.
+ * All tiles carry the same metadata word, as today.
+ *   tile          the tile of "tiled coding": the same grid, and edge replication tile(t, y, x, c) = image(min(j tile_h + y, H - 1), min(i tile_w + x, W - 1), c).
+ *                 It is then treated as an R, G, B image of tile_w x tile_h by "4:2:0 chroma subsampling" (include/fri_hip.h), unchanged: forward steps 1-3 give
+ *                 Y [tile_h][tile_w] and Cb, Cr [ch][cw], cw = (tile_w + 1) / 2, ch = (tile_h + 1) / 2; inverse steps 2-4 give the tile back; the clamping of
+ *                 i' and j' is to the tile's own chroma planes.
+ *   independence  no sample of one tile is read for another: the merge copies only pixels with j tile_h + y < H and i tile_w + x < W, and a region is by
+ *                 definition the crop of the whole decode.
+ *   plane order   one rule for every per-plane array of n = nx ny tiles, the luma planes first, then the chroma planes:
+ *                     plane(t, Y) = t        plane(t, Cb) = n + 2 t        plane(t, Cr) = n + 2 t + 1
+ *   arrays        symbols [n][n_y], then [n][2][n_c], in one buffer; coefficients [n][F_y][512], then [n][2][F_c][512], in one buffer; histograms
+ *                 [3 n][10][1024]; parameters [3 n][3][6]. n_y, F_y are the tile_w x tile_h lattice's (C = 1), n_c, F_c the cw x ch lattice's.
+ *   region        a region's sub-grid (ni nj tiles, the arithmetic of "Region decode" unchanged) uses the same order with n = ni nj.
+ * fri_tiled_info, fri_tiled_decode and fri_tiled_decode_region accept such files: info[6] carries FRI_EMIT_420, info[7] stays F_y, the coefficients come back in
+ * plane order and the needed element count is n (F_y + 2 F_c) x 512. A file whose tiles have bit 2 without bit 1, or with bit 0, and every alpha payload stays
+ * "Malformed tiled image". */
 #define FRI_EMIT_EMPTY_OK 0x2000u
 #define FRI_EMIT_RCT 0x100u
 #define FRI_EMIT_YCBCR 0x400u
@@ -158,6 +178,14 @@ int fri_emit_rans_selfcheck(uint64_t n_symbols, uint64_t seed, char *err, size_t
 int fri_tiled_encode_from_streams(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t channels, const uint16_t *streams, uint64_t n_symbols,
                                   const uint32_t *hist, const float *value_params, const float *width_params, uint32_t threads, uint8_t *out, size_t cap, size_t *len, char *err,
                                   size_t err_cap);
+/* A tiled 4:2:0 file ("Tiled 4:2:0" above) from the arrays fri_hip_encode_image_tiled420_symbols returns, all in plane order: streams [n][n_luma] then
+ * [n][2][n_chroma] u16, hist [3 n][10][1024], value_params / width_params [3 n][3][6]. `channels` must be 3 | FRI_EMIT_YCBCR | FRI_EMIT_420 | FRI_EMIT_QUALITY(q),
+ * q = 1..99, with or without FRI_EMIT_EMPTY_OK (always in force) - anything else -1. n_luma and n_chroma must be the symbol counts of the tile_w x tile_h lattice and
+ * of the (tile_w + 1) / 2 x (tile_h + 1) / 2 lattice (-2 otherwise). Tiles are coded on `threads` workers exactly as in fri_tiled_encode_from_streams; the bytes are
+ * the same for every thread count. Returns 0 and *len, or -3 with *len = needed size. */
+int fri_tiled_encode_from_streams420(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t channels, const uint16_t *streams, uint64_t n_luma,
+                                     uint64_t n_chroma, const uint32_t *hist, const float *value_params, const float *width_params, uint32_t threads, uint8_t *out, size_t cap,
+                                     size_t *len, char *err, size_t err_cap);
 /* The same file from planes the device coded (K11: fri_hip_rans_encode_planes_dev / fri_hip_encode_image_tiled_coded, include/fri_hip.h, which defines the layouts): the
  * arguments of fri_tiled_encode_from_streams with the coded planes in the place of the streams and histograms. words uint32 [n_tiles C][word_stride]: the first
  * n_words[p] of plane p are its rANS data as little-endian words (at least 20, at most word_stride, -2 otherwise); models uint32 [n_tiles C][10][4], of which
@@ -170,13 +198,14 @@ int fri_tiled_encode_from_coded(uint32_t width, uint32_t height, uint32_t tile_w
 /* ... and one ordinary `frif` image of 1 or 3 channels from its C coded planes (`channels` as above): byte for byte fri_emit_encode_image_from_streams's file. */
 int fri_coded_encode_image(uint32_t width, uint32_t height, uint32_t channels, const uint32_t *words, uint64_t word_stride, const uint32_t *n_words, const uint32_t *models,
                            const uint16_t *off_values, const float *value_params, const float *width_params, uint8_t *out, size_t cap, size_t *len, char *err, size_t err_cap);
-/* info = {W, H, tile_w, tile_h, nx, ny, the info[2] fri_emit_decode_image reports for tile 0, F = the cells of the tile lattice}. Checks the header, the table
+/* info = {W, H, tile_w, tile_h, nx, ny, the info[2] fri_emit_decode_image reports for tile 0, F = the cells of the tile lattice; tiled 4:2:0: F_y}. Checks the header, the table
  * and every payload's 16-byte header, decodes nothing. -2 for a file that is not a well-formed `frit` file. */
 int fri_tiled_info(const uint8_t *frv, size_t len, uint32_t info[8]);
 /* A `frit` file back to the coefficient planes fri_hip_decode_image_tiled takes: coefs [n_tiles][C][F][512] int32, None = INT32_MIN. Checks the table, and each
  * payload's height, width and metadata word against the header and tile 0: a mismatch - and any file that is not a `frit` file, a `frif` file among them -
  * returns "Malformed tiled image" (-2). Tiles are decoded on `threads` workers (0 as above) that share one geometry and one symbol order. Returns -3 with `info`
- * filled when coefs is NULL or coef_cap (in elements) is too small. */
+ * filled when coefs is NULL or coef_cap (in elements) is too small. A tiled 4:2:0 file: coefs in plane order, n (F_y + 2 F_c) x 512 elements - what
+ * fri_hip_decode_image_tiled420 takes. */
 int fri_tiled_decode(const uint8_t *frv, size_t len, uint32_t threads, uint32_t info[8], int32_t *coefs, size_t coef_cap, char *err, size_t err_cap);
 /* The tile range of a region ("Region decode" above): out = {i0, j0, ni, nj} by that arithmetic and nothing else. -1 for a zero size (of the image, the tile or
  * the region), a region that leaves the image, or out = NULL. */

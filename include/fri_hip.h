@@ -596,14 +596,15 @@ int fri_hip_decode_image_rgba(fri_hip_plan_rgba *p, const int32_t *coefs, const 
  * (owned by p) for the getters, fri_hip_plan_set_colour_transform, fri_hip_plan_set_dequantiser and fri_hip_plan_set_stream_order, which the encodes need and
  * create does not do. fri_hip_plan_tiled_grid: out[4] = {nx, ny, tile_w, tile_h}. The plan owns the tile staging buffers: calls on one fri_hip_plan_tiled must
  * be ordered on one stream, as for fri_hip_plan_rgba.
- * Out of scope: per-tile qualities (all tiles of a file carry one metadata word: one quality per file, which is what the searches below return), 4:2:0 and alpha
- * in tiles, multi-GPU forms.
+ * Out of scope: per-tile qualities (all tiles of a file carry one metadata word: one quality per file, which is what the searches below return), alpha in
+ * tiles, multi-GPU forms. 4:2:0 in tiles is a plan of its own: "Tiled 4:2:0 coding" below.
  * Region decode: a region x, y, w, h in image pixels (w, h >= 1, x + w <= W, y + h <= H, compared in 64 bits) touches the sub-grid of ni x nj tiles from column
  * i0 = x / tile_w and row j0 = y / tile_h, ni = (x + w - 1) / tile_w - i0 + 1, nj = (y + h - 1) / tile_h - j0 + 1, stored row-major: sub-tile s = b ni + a is
  * tile (j0 + b) nx + (i0 + a). The region raster is [h][w][C] without a pitch: pixel (ry, rx) is image pixel (y + ry, x + rx), which is pixel
  * (y + ry - j tile_h, x + rx - i tile_w) of tile (j, i); no replicated pixel is ever copied. By definition it is the crop [y : y + h, x : x + w] of what
  * fri_hip_decode_image_tiled returns for the same file. Only the touched tiles are entropy-decoded (fri_tiled_decode_region, include/fri_emit.h), inverted and
- * copied, and the plan's buffers grow to the region's size, never to the image's. Out of scope: regions of 4:2:0 and alpha files, several regions in one call. */
+ * copied, and the plan's buffers grow to the region's size, never to the image's. Out of scope: regions of untiled 4:2:0 files and of alpha files, several regions
+ * in one call; a region of a tiled 4:2:0 file is fri_hip_decode_region_tiled420 below. */
 #define FRI_HIP_TILED_ALLOW_HOLES 1u
 typedef struct fri_hip_plan_tiled fri_hip_plan_tiled;
 uint64_t fri_hip_plan_owned_pixels(const fri_hip_plan *plan);
@@ -690,6 +691,77 @@ int fri_hip_search_quality_ssim_tiled(fri_hip_plan_tiled *p, const uint8_t *pixe
 int fri_hip_search_quality_ssim_tiled_dev(fri_hip_plan_tiled *p, const uint8_t *d_pixels, double target, int32_t *quality, double *ssim, void *stream);
 int fri_hip_search_quality_for_size_tiled(fri_hip_plan_tiled *p, const uint8_t *pixels, uint64_t max_bytes, int32_t *quality, uint64_t *est_bytes);
 int fri_hip_search_quality_for_size_tiled_dev(fri_hip_plan_tiled *p, const uint8_t *d_pixels, uint64_t max_bytes, int32_t *quality, uint64_t *est_bytes, void *stream);
+
+/* ---- tiled 4:2:0 coding: subsampled tiles --------------------------------------------------------- */
+/* Tiled coding and 4:2:0 together: every tile of a `frit` file (include/fri_emit.h; the container is unchanged, version 1) is a 4:2:0 image. Part of the file
+ * format. In a tiled 4:2:0 file every payload is a `frif` file of a tile_h x tile_w image with colour space YCbCr, metadata bits 1 and 2 set, and a quality of
+ * 1..99: exactly what fri_emit_encode_image_from_streams writes for that tile with 3 | FRI_EMIT_YCBCR | FRI_EMIT_420 | FRI_EMIT_QUALITY(q) | FRI_EMIT_EMPTY_OK.
+ * All tiles carry the same metadata word, as in every `frit` file.
+ *   tile          the tile of "tiled coding": the same grid, and edge replication tile(t, y, x, c) = image(min(j tile_h + y, H - 1), min(i tile_w + x, W - 1), c).
+ *                 It is then treated as an R, G, B IMAGE of tile_w x tile_h by "4:2:0 chroma subsampling" above, unchanged: forward steps 1-3 give Y
+ *                 [tile_h][tile_w] and Cb, Cr [ch][cw] with cw = (tile_w + 1) / 2 and ch = (tile_h + 1) / 2; inverse steps 2-4 give the tile back; the clamping
+ *                 of i' and j' is to the tile's own chroma planes.
+ *   independence  no sample of one tile is read for another. Therefore the merge copies only pixels with j tile_h + y < H and i tile_w + x < W, and a region is
+ *                 by definition the crop of the whole decode.
+ *   plane order   one rule covers every per-plane array of n = nx ny tiles - the luma planes first, then the chroma planes:
+ *                     plane(t, Y) = t        plane(t, Cb) = n + 2 t        plane(t, Cr) = n + 2 t + 1
+ *   arrays        in plane order. Tile rasters: y_tiles [n][tile_h][tile_w], c_tiles [n][2][ch][cw]. Symbols: [n][n_y], then [n][2][n_c], in one buffer.
+ *                 Coefficients: [n][F_y][512], then [n][2][F_c][512], in one buffer. Histograms: [3 n][10][1024]. Parameters: [3 n]... Out-of-alphabet and
+ *                 fit-out-of-range counts: [3 n]. n_y, F_y and n_c, F_c = fri_hip_plan_num_some and fri_hip_plan_num_cells of the two inner plans.
+ *   batches       with this order the luma planes are one batch of n on a C = 1 plan of tile_w x tile_h and the chroma planes one batch of 2 n on a C = 1 plan
+ *                 of cw x ch: the _batch_dev entry points take them with constant strides.
+ *   region        a region's sub-grid (ni nj tiles, the arithmetic of "Region decode" above unchanged) uses the same order with n = ni nj.
+ *   tile shape    BOTH lattices must own every pixel, and the one does not imply the other: a 128 x 128 tile is fine, but its 64 x 64 chroma lattice leaves 8
+ *                 samples to no cell.
+ * fri_hip_tile_shape420 (host only): the walk of fri_hip_tile_shape; the first shape (w, h) at which the C = 1 lattice of w x h and the C = 1 lattice of
+ * (w + 1) / 2 x (h + 1) / 2 both own every pixel. The same s <= 64 limit and the same errors.
+ * fri_hip_plan_tiled420_create: refuses (FRI_HIP_ERR_INVALID_ARGUMENT) zero sizes, unknown flag bits, 2 nx ny > 65535 (one batch launch takes all chroma planes)
+ * and - without FRI_HIP_TILED_ALLOW_HOLES - a shape at which either lattice has holes. ctx may be NULL: the plan is then host-only (the getters work, compute
+ * returns FRI_HIP_ERR_NO_DEVICE). The plan owns the two inner C = 1 plans - fri_hip_plan_tiled420_luma / _chroma, for the getters and for
+ * fri_hip_plan_set_stream_order, which the encodes need on both and create does not do - and the staging buffers: calls on one plan must be ordered on one stream.
+ * fri_hip_plan_tiled420_grid: out[4] = {nx, ny, tile_w, tile_h}. fri_hip_plan_tiled420_region: out[4] = {i0, j0, ni, nj}; both work on host-only plans.
+ * fri_hip_plan_tiled420_buffer_tiles (diagnostics): out[2] = the tiles the plan's luma and chroma tile buffers hold room for at the moment.
+ * The raster kernels (K12, k12_tiles420.hip), any pointer alignment; they only enqueue on `stream` and can be captured into a graph:
+ *   fri_hip_split_tiles420_dev          d_rgb [H][W][3] -> d_y_tiles, d_c_tiles in one pass: the tile split and forward steps 1-3 of every tile.
+ *   fri_hip_merge_tiles420_region_dev   a sub-grid's d_y_tiles, d_c_tiles -> d_region [h][w][3]: inverse steps 2-3 per pixel within the pixel's own tile. Nothing
+ *                                       outside the region raster is written; no replicated pixel is stored.
+ *   fri_hip_merge_tiles420_dev          the same kernel with the region (0, 0, W, H) on the full grid.
+ * fri_hip_encode_symbols_tiled420_dev: everything in device memory and on `stream`, nothing but enqueues - the split into the plan's buffers, then
+ * fri_hip_encode_symbols_batch_dev in its direct form (d_coefs = NULL, d_node_words = NULL) twice: on the luma plan with n tiles, on the chroma plan with 2 n, both
+ * with fri_hip_quality_matrix(quality), quality 1..99 (anything else FRI_HIP_ERR_INVALID_ARGUMENT). Both inner plans need their stream order; a capturing stream
+ * is refused before anything is enqueued. fit = 0 reads every plane's parameters from d_params. Outputs in plane order: d_symbols, d_params [3 n][2][3][6], d_hist,
+ * d_n_out_of_alphabet, d_fit_out_of_range (may be NULL).
+ * fri_hip_encode_image_tiled420_symbols: the host form - the pixels are staged, the call above runs with the fit on, everything is read back: what
+ * fri_tiled_encode_from_streams420 (include/fri_emit.h) takes. value_params / width_params [3 n][3][6]. Synchronous. FRI_HIP_ERR_OUT_OF_RANGE as in
+ * fri_hip_encode_image.
+ * fri_hip_decode_image_tiled420: coefs in plane order (what fri_tiled_decode returns for such a file) -> pixels [H][W][3]: the inverse kernel with
+ * fri_hip_quality_matrix(quality) and FRI_HIP_DEQUANT_MIDPOINT on both plans, whatever is set on them (as fri_hip_decode_image420), then the merge. Synchronous.
+ * fri_hip_decode_region_tiled420 / _dev: the same for the sub-grid's planes (what fri_tiled_decode_region returns; d_coefs in device memory) -> the region raster
+ * [h][w][3]. The plan's tile buffers grow to the region's tiles only. The _dev form refuses a capturing stream (FRI_HIP_ERR_INVALID_ARGUMENT) before anything is
+ * enqueued or allocated. FRI_HIP_ERR_INVALID_ARGUMENT for a NULL pointer, a quality outside 1..99 or a region that is empty or leaves the image.
+ * Out of scope: the quality searches and the size estimate on tiled 4:2:0; K11, the device rANS coder, for such files (they have two symbol counts per tile);
+ * alpha in tiles; multi-GPU forms. */
+typedef struct fri_hip_plan_tiled420 fri_hip_plan_tiled420;
+int fri_hip_tile_shape420(uint32_t width, uint32_t height, uint32_t target, uint32_t *tile_w, uint32_t *tile_h);
+int fri_hip_plan_tiled420_create(fri_hip_ctx *ctx, uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t flags, fri_hip_plan_tiled420 **out);
+int fri_hip_plan_tiled420_destroy(fri_hip_plan_tiled420 *p);
+fri_hip_plan *fri_hip_plan_tiled420_luma(fri_hip_plan_tiled420 *p);
+fri_hip_plan *fri_hip_plan_tiled420_chroma(fri_hip_plan_tiled420 *p);
+int fri_hip_plan_tiled420_grid(const fri_hip_plan_tiled420 *p, uint32_t out[4]);
+int fri_hip_plan_tiled420_region(const fri_hip_plan_tiled420 *p, uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint32_t out[4]);
+int fri_hip_plan_tiled420_buffer_tiles(const fri_hip_plan_tiled420 *p, uint64_t out[2]);
+int fri_hip_split_tiles420_dev(fri_hip_plan_tiled420 *p, const uint8_t *d_rgb, uint8_t *d_y_tiles, uint8_t *d_c_tiles, void *stream);
+int fri_hip_merge_tiles420_dev(fri_hip_plan_tiled420 *p, const uint8_t *d_y_tiles, const uint8_t *d_c_tiles, uint8_t *d_rgb, void *stream);
+int fri_hip_merge_tiles420_region_dev(fri_hip_plan_tiled420 *p, const uint8_t *d_y_tiles, const uint8_t *d_c_tiles, uint32_t x, uint32_t y, uint32_t w, uint32_t h,
+                                      uint8_t *d_region, void *stream);
+int fri_hip_encode_symbols_tiled420_dev(fri_hip_plan_tiled420 *p, const uint8_t *d_rgb, int quality, int fit, float *d_params, uint16_t *d_symbols, uint32_t *d_hist,
+                                        uint64_t *d_n_out_of_alphabet, uint64_t *d_fit_out_of_range, void *stream);
+int fri_hip_encode_image_tiled420_symbols(fri_hip_plan_tiled420 *p, const uint8_t *pixels, int quality, float *value_params, float *width_params, uint16_t *symbols,
+                                          uint32_t *hist, uint64_t *n_out_of_alphabet);
+int fri_hip_decode_image_tiled420(fri_hip_plan_tiled420 *p, const int32_t *coefs, int quality, uint8_t *pixels);
+int fri_hip_decode_region_tiled420_dev(fri_hip_plan_tiled420 *p, const int32_t *d_coefs, int quality, uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint8_t *d_region,
+                                       void *stream);
+int fri_hip_decode_region_tiled420(fri_hip_plan_tiled420 *p, const int32_t *coefs, int quality, uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint8_t *pixels);
 
 /* ---- the rANS coder on the device (K11, k11_rans.hip) ------------------------------------------- */
 /* The emitter's last stage - symbols to rANS words (host/emit.cpp, encode_symbols) - for a batch of planes, a plane being one channel of one tile or of an
