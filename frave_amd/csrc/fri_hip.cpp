@@ -1,187 +1,22 @@
-// fri_hip.cpp -- the C ABI of libfri_hip.so (include/fri_hip.h). Host-side glue only: plan construction,
-// table upload, staging for the host-pointer entry points, launches. No CPU compute fallback.
-#include "fri_hip.h"
+// fri_hip.cpp -- the C ABI of libfri_hip.so (include/fri_hip.h): the context, the ordinary plan and every entry point that takes a fri_hip_plan or a
+// fri_hip_multi, the forward tuner and its process-wide cache included. Host-side glue only: plan construction, table upload, staging for the host-pointer
+// entry points, launches. No CPU compute fallback. The further plan kinds have a source each (fri_hip_420.cpp, fri_hip_rgba.cpp, fri_hip_tiled.cpp,
+// fri_hip_tiled420.cpp), K11's plane entry points are in fri_hip_rans.cpp, and what all of them share is fri_hip_internal.hpp.
+#include "fri_hip_internal.hpp"
 
-#include <hip/hip_runtime_api.h>
-
-#include <algorithm>
+#include <atomic>
 #include <cstdio>
 #include <cstdlib>
-#include <cmath>
-#include <atomic>
-#include <cstring>
-#include <memory>
 #include <mutex>
 #include <new>
 #include <optional>
-#include <string>
 #include <thread>
-#include <utility>
-#include <vector>
 
-#include "geometry.hpp"
-#include "kernels.hpp"
+#include "quality_search.hpp"
 #include "solve6.hpp"
 
 using namespace fri;
-
-struct fri_hip_ctx {
-    int device = -1;
-    std::string arch;
-    int cu_count = 256;
-    std::string last_error;
-    float *rans_laplace = nullptr; // K11's [10][1024] Laplace shapes (laplace_table), uploaded with the context: fri_hip_rans_encode_planes_dev takes no plan
-};
-
-namespace {
-
-// Owners of the library's HIP resources: move-only, each gives its resource back when it goes. A plan's go with the plan's device current
-// (fri_hip_plan_destroy): a plan of fri_hip_multi's device d > 0 frees on that device.
-template <typename T, auto Release>
-class Owned {
-  public:
-    Owned() = default;
-    Owned(Owned &&o) noexcept : h_(std::exchange(o.h_, T{})) {}
-    Owned &operator=(Owned &&o) noexcept {
-        if (this != &o) reset(), h_ = std::exchange(o.h_, T{});
-        return *this;
-    }
-    ~Owned() { reset(); }
-    operator T() const { return h_; }
-    T get() const { return h_; }
-    T *put() { // the out-parameter of a hipMalloc / hipEventCreate / ...: whatever was held goes first
-        reset();
-        return &h_;
-    }
-    void reset() {
-        if (h_) (void)Release(h_);
-        h_ = T{};
-    }
-
-  private:
-    T h_{};
-};
-template <typename T> using DevMem = Owned<T *, hipFree>;
-template <typename T> using HostMem = Owned<T *, hipHostFree>; // pinned
-using Event = Owned<hipEvent_t, hipEventDestroy>;
-using Stream = Owned<hipStream_t, hipStreamDestroy>;
-
-// a grow-only device buffer of n elements (the plan's staging, its compact planes)
-template <typename T>
-struct Grown : DevMem<T> {
-    size_t n = 0;
-};
-
-// staging of the host-pointer entry points: each call grows the buffers it uses to what it needs of them (grow)
-struct Staging {
-    Grown<uint8_t> pixels, bucket;
-    Grown<int32_t> coefs, prediction;
-    Grown<uint32_t> hist;            // [channels][10][1024]
-    Grown<unsigned long long> oob;   // [channels]
-    Grown<uint16_t> symbols;         // fri_hip_encode_image_symbols: [C][geo.n_some]
-    Grown<int32_t> search_coefs;     // fri_hip_search_quality*: the probes' coefficient planes [C][F][512]
-    Grown<unsigned long long> measure; // fri_hip_search_quality*: a probe's distortion sums [2 C + 1]
-    Grown<uint32_t> search_hist;       // fri_hip_search_quality_for_size*: a probe's histograms [C][10][1024] ...
-    Grown<unsigned long long> search_oob; // ... its out-of-alphabet counts [C]
-    Grown<float> search_params;        // ... its fitted parameters [C][2][3][6]
-    Grown<unsigned long long> rate;    // fri_hip_estimate_size, fri_hip_search_quality_for_size*: the estimate [1]
-    Grown<uint8_t> ssim_pixels;        // fri_hip_measure_ssim: the second raster; fri_hip_search_quality_ssim*: a probe's reconstruction
-    Grown<unsigned long long> ssim;    // fri_hip_measure_ssim, fri_hip_search_quality_ssim*: the SSIM sums [C + 1]
-};
-
-constexpr int kBatchSlots = 3;
-
-struct Slot {
-    Stream stream;
-    HostMem<uint8_t> h_pixels;
-    HostMem<int32_t> h_coefs;
-    DevMem<uint8_t> d_pixels;
-    DevMem<int32_t> d_coefs;
-    int pending = -1; // image index whose result sits in h_coefs once the stream drains
-    // the rest of an image's encode outputs (fri_hip_encode_image_batch), allocated on first use
-    HostMem<uint8_t> h_bucket;
-    DevMem<uint8_t> d_bucket;
-    HostMem<int32_t> h_prediction;
-    DevMem<int32_t> d_prediction;
-    HostMem<uint32_t> h_hist;
-    DevMem<uint32_t> d_hist;             // [C][10][1024]
-    HostMem<unsigned long long> h_oob;
-    DevMem<unsigned long long> d_oob;    // [C] out of alphabet, then [C] the fit's out-of-range counts
-    HostMem<float> h_params;
-    DevMem<float> d_params;              // [C][2][3][6]
-};
-
-// (a deleter of this file's own: std::default_delete<fri_hip_plan> would be exported with the ABI's types)
-struct PlanDelete {
-    void operator()(fri_hip_plan *p) const;
-};
-
-// the device buffers of an accumulator slot (fri_hip_plan::acc_slots)
-struct AccBufs {
-    DevMem<uint32_t> pred_acc;           // [planes][kPredAccWords]: K2's hand-over bookkeeping (kernels.hpp), grown on demand, zero when allocated
-    DevMem<unsigned long long> fit_acc;  // [planes][kFitShards][kFitAccWords]
-    // scratch of the device-side fit (fit_chain): the sums of a launch's planes on their way to the solve kernels, their out-of-range
-    // counts, and parameter sets for callers that keep theirs on the host. Per stream like the accumulators: chains of several streams
-    // (fri_hip_multi_encode_image's slots) run side by side on one plan.
-    DevMem<unsigned long long> sums_int; // [planes][3][28]
-    DevMem<double> sums_dbl;             // [planes][3][6]
-    DevMem<unsigned long long> range;    // [planes]
-    DevMem<float> params;                // [planes][2][3][6]
-};
-
-} // namespace
-
-struct fri_hip_plan {
-    fri_hip_ctx *ctx = nullptr;
-    Geometry geo;
-    DevicePlan dev;
-    // The inverse kernel walks tiles of its own (round 4): what suits the forward kernel's loads and stores (bands of 16 rows) is not what suits the inverse's
-    // write-out (bands of 32 for planes). geo_inv holds only the tiling (tiles, cell records, shares, write-out lists); dev_inv is dev with those swapped in.
-    // Host-only plans and plans created with FRI_HIP_INV_SHARED=1 (tuning) keep one tiling: inv_geo() == geo.
-    Geometry geo_inv;
-    bool own_inverse_tiling = false;
-    DevicePlan dev_inv;
-    const Geometry &inv_geo() const { return own_inverse_tiling ? geo_inv : geo; }
-    std::vector<DevMem<void>> owned; // device allocations backing dev.*
-    Staging staging;
-    Slot slots[kBatchSlots];
-    bool slots_ready = false;
-    // K2 / K4 hand their sums over through plan-owned accumulators that are all zero between launches (kernels.hpp). One
-    // accumulator per stream that launches on this plan: launches of one stream are ordered anyway; when more streams than
-    // accumulators are in play a stream taking over an accumulator first waits (on the device) for its previous user.
-    struct AccSlot : AccBufs {
-        hipStream_t stream = nullptr;
-        bool used = false;
-        Event handed_over;
-        uint32_t pred_serial = 0; // launches of K2 on this accumulator so far: every launch publishes and polls for its own number
-        uint32_t planes = 0;
-    } acc_slots[kPredAccRing];
-    std::vector<AccBufs> retired_acc; // accumulators outgrown by a larger batch: freed with the plan (a launch may still be draining them)
-    // host-facing fit (fri_hip_encode_image_dev / fri_hip_predict_image_dev with fit != 0): the fitted parameters and the range counts come
-    // back through pinned memory behind an event, while the scan kernel that follows them is already queued
-    HostMem<void> h_fit;       // pinned + mapped: [3] PredictParams + [3] u64
-    void *d_h_fit = nullptr;   // the device's address of h_fit
-    Event ev_fit;
-    const float *laplace = nullptr; // the rate kernel's [10][1024] Laplace shapes (laplace_table), uploaded with the plan
-    bool assume_forward = false; // fri_hip_plan_assume_forward_coefficients
-    DevMem<uint32_t> d_stream_order; // fri_hip_plan_set_stream_order: node index of the i-th symbol of a channel, [geo.n_some]
-    DevMem<uint32_t> d_stream_pos;   // ... and its inverse, [F][512]: the position of a node's symbol in a channel's stream (None nodes: ~0, never used) - the scan's STREAM form
-    // The symbol-stream chains' compact coefficient planes (round 5): int16, None as 0, [planes][F][512] - between the forward kernel, the fit and the scan when the
-    // caller does not ask for the coefficients (fri_hip_encode_image_symbols; fri_hip_encode_symbols_batch_dev with d_coefs == NULL). Half the bytes written and read three times.
-    // A chain holds them through a Coefs16Lease.
-    Grown<int16_t> coefs16;
-    Event ev_coefs16;                   // behind the last chain that used them: a chain on ANOTHER stream waits for it before it overwrites the planes
-    hipStream_t coefs16_stream = nullptr;
-    bool coefs16_used = false;
-    uint32_t acc_next = 0;
-    bool acc_dirty = false; // a launch on this plan failed: the accumulators are re-zeroed before the next use
-    Event ev_begin, ev_end; // timing helper's events, created with the plan (creating an event is not work to be timed)
-    // fri_hip_plan_tune_forward: the parameters the forward tiling was built with, and whether the plan may exchange it (a plan whose tiling the
-    // environment pinned, whose inverse kernel shares the forward tiles, or that is cut into many short shares keeps what it has)
-    TilingParams fwd_tp;
-    bool fwd_tunable = false;
-    std::string fwd_tiling_note = "default";
-};
+using namespace fri::host;
 
 void PlanDelete::operator()(fri_hip_plan *p) const { delete p; }
 
@@ -191,19 +26,6 @@ struct fri_hip_multi {
 };
 
 namespace {
-
-int fail_hip(fri_hip_ctx *ctx, hipError_t e, const char *what) {
-    if (ctx) {
-        ctx->last_error = std::string(what) + ": " + hipGetErrorString(e);
-    }
-    return e == hipErrorOutOfMemory ? FRI_HIP_ERR_OUT_OF_MEMORY : FRI_HIP_ERR_HIP;
-}
-
-#define HIP_TRY(ctx, expr)                                 \
-    do {                                                   \
-        hipError_t e_ = (expr);                            \
-        if (e_ != hipSuccess) return fail_hip(ctx, e_, #expr); \
-    } while (0)
 
 // copies v into a new device buffer that `bufs` owns, followed by `pad` zeroed elements (an empty array still gets one element)
 template <typename T>
@@ -230,23 +52,6 @@ std::vector<float> laplace_table() {
             t[b * 1024 + j] = std::exp(-std::fabs(x - 0.0f) / width[b]) / (2.0f * width[b]);
         }
     return t;
-}
-// the container around the rANS data (serialize.rs:40-117, host/emit.cpp serialize): "frif" + height + width + metadata word + EOI; per channel PRD +
-// 36 f32, DAT + u64 length, EOC, plus the estimate of the flush of the ten rANS states; per context EHD + u32 max_freq_bits + u64 n_off (+ 2 bytes per listed value)
-constexpr RateLayout kRateLayout = {16 + 2, (2 + 36 * 4) + (2 + 8) + 2 + 60, 2 + 4 + 8};
-
-int check_q(const int32_t q[32], QMatrix &out) {
-    if (!q) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    for (int i = 0; i < 32; i++) out.q[i] = q[i];
-    for (int i = 0; i <= 9; i++) // layers a depth-9 cell can reach (quantization.rs:13)
-        if (q[i] == 0) return FRI_HIP_ERR_DIVIDE_BY_ZERO;
-    return FRI_HIP_OK;
-}
-
-int need_device(const fri_hip_plan *p) {
-    if (!p) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    if (!p->ctx) return FRI_HIP_ERR_NO_DEVICE;
-    return FRI_HIP_OK;
 }
 
 // Tuning knobs (tile shapes, share weights, kernel A/B switches, trace) are read from the environment only when the caller opts
@@ -296,16 +101,6 @@ Knobs read_knobs() {
     k.k1_ablate = num(env("FRI_HIP_K1_ABLATE")), k.k2_ablate = num(env("FRI_HIP_K2_ABLATE")), k.k3_ablate = num(env("FRI_HIP_K3_ABLATE")), k.k4_ablate = num(env("FRI_HIP_K4_ABLATE"));
     k.k1_cached_stores = opt(env("FRI_HIP_K1_CACHED_STORES")), k.k1_batch_shares = opt(env("FRI_HIP_K1_BATCH_SHARES")), k.k4_older_eighths = opt(env("FRI_HIP_K4_OLDER_EIGHTHS"));
     return k;
-}
-
-// at least n elements in b (n == 0: the call does not use it). Growing frees the old buffer first: hipFree waits for the device, so nothing queued still uses it.
-template <typename T>
-int grow(fri_hip_ctx *c, Grown<T> &b, size_t n) {
-    if (b.n >= n) return FRI_HIP_OK;
-    b.n = 0;
-    HIP_TRY(c, hipMalloc((void **)b.put(), n * sizeof(T)));
-    b.n = n;
-    return FRI_HIP_OK;
 }
 
 // Accumulators for a K2 / K4 launch over n_planes planes on `stream` (see fri_hip_plan::acc_slots). Returns the slot index, or a negative error code.
@@ -702,41 +497,6 @@ int wait_event_polling(fri_hip_ctx *c, hipEvent_t ev) {
     }
 }
 
-// The scan's histogram hand-over numbers its launches on the HOST (pred_serial, a kernel argument): a captured launch would freeze that number, and from the
-// second replay on the clearing workgroups' flags already hold it - nothing would order the clearing of the histogram before the other workgroups' adds any more
-// (counts wiped or doubled). So every entry point that reaches the scan refuses a capturing stream, loudly, before it queues or allocates anything,
-// instead of recording something that must not be replayed.
-int refuse_capture(fri_hip_plan *p, hipStream_t stream,
-                   const char *why = "the predict + histogram kernel cannot be captured into a HIP graph (its hand-over counts launches on the host): launch it on a stream") {
-    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-    if (stream && hipStreamIsCapturing(stream, &capturing) == hipSuccess && capturing != hipStreamCaptureStatusNone) {
-        if (p->ctx) p->ctx->last_error = why;
-        return FRI_HIP_ERR_INVALID_ARGUMENT;
-    }
-    return FRI_HIP_OK;
-}
-
-// PSNR of a measurement (fri_hip_measure_distortion_dev's d_out): 10 log10(255^2 N / SSE) pooled over the channels, N = owned pixels x C; +inf for SSE = 0.
-double distortion_psnr(const unsigned long long *m, uint32_t channels) {
-    unsigned long long sse = 0;
-    for (uint32_t c = 0; c < channels; c++) sse += m[2 * c];
-    if (sse == 0) return HUGE_VAL;
-    return 10.0 * std::log10(255.0 * 255.0 * (double)m[2 * channels] * (double)channels / (double)sse);
-}
-
-// The SSIM window grid of a plan's shape (fri_hip_measure_ssim_dev): FRI_HIP_ERR_INVALID_ARGUMENT without a window or with more than 2^29 per channel.
-int ssim_shape(const fri_hip_plan *p) {
-    if (p->geo.width < 8 || p->geo.height < 8) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    return (uint64_t)(p->geo.width / 4 - 1) * (p->geo.height / 4 - 1) > (1ull << 29) ? FRI_HIP_ERR_INVALID_ARGUMENT : FRI_HIP_OK;
-}
-
-// SSIM of a measurement (d_out of fri_hip_measure_ssim_dev): the channels' integer sums added first, then one division.
-double ssim_of(const unsigned long long *m, uint32_t channels) {
-    long long total = 0;
-    for (uint32_t c = 0; c < channels; c++) total += (long long)m[c];
-    return (double)total / ((double)((unsigned long long)channels * m[channels]) * 4294967296.0);
-}
-
 } // namespace
 
 extern "C" {
@@ -904,6 +664,7 @@ uint32_t fri_hip_plan_num_interior_cells(const fri_hip_plan *p) { return p ? p->
 size_t fri_hip_plan_coef_count(const fri_hip_plan *p) { return p ? (size_t)p->geo.channels * p->geo.centers.size() * kCell : 0; }
 size_t fri_hip_plan_pixel_bytes(const fri_hip_plan *p) { return p ? (size_t)p->geo.width * p->geo.height * p->geo.channels : 0; }
 uint64_t fri_hip_plan_num_some(const fri_hip_plan *p) { return p ? p->geo.n_some : 0; }
+uint64_t fri_hip_plan_owned_pixels(const fri_hip_plan *p) { return p ? p->geo.n_valid_leaves : 0; }
 
 int fri_hip_plan_assume_forward_coefficients(fri_hip_plan *p, int on) {
     if (!p) return FRI_HIP_ERR_INVALID_ARGUMENT;
@@ -1787,14 +1548,8 @@ int fri_hip_search_quality_dev(fri_hip_plan *p, const uint8_t *d_pixels, double 
     auto &st = p->staging;
     int rc;
     if ((rc = grow(c, st.search_coefs, fri_hip_plan_coef_count(p))) || (rc = grow(c, st.measure, 2 * (size_t)C + 1))) return rc;
-    // the probes' K3: the plan's inverse tiling with the midpoint dequantiser, whatever the caller has set on the plan
-    DevicePlan inv = p->dev_inv;
-    inv.k3_multiply = false;
-    inv.k3_midpoint = true;
-    int lo = 0, hi = 100; // lo: a failure (0 is never probed), hi: a success (100 = lossless is never probed)
-    double hi_db = HUGE_VAL;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) / 2;
+    const DevicePlan inv = midpoint_inverse(p->dev_inv); // the probes' K3: the plan's inverse tiling
+    auto probe = [&](int mid, double &db) -> int {
         int32_t qm[32];
         QMatrix q;
         fri_hip_quality_matrix(mid, qm);
@@ -1805,21 +1560,16 @@ int fri_hip_search_quality_dev(fri_hip_plan *p, const uint8_t *d_pixels, double 
         unsigned long long m[7];
         HIP_TRY(c, hipMemcpyAsync(m, st.measure, (2 * (size_t)C + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipStreamSynchronize(s));
-        const double db = distortion_psnr(m, C);
-        if (db >= target_db) hi = mid, hi_db = db;
-        else lo = mid;
-    }
-    *quality = hi;
-    *psnr_db = hi_db;
-    return FRI_HIP_OK;
+        db = distortion_psnr(m, C);
+        return FRI_HIP_OK;
+    };
+    return search_at_least(target_db, HUGE_VAL, probe, quality, psnr_db); // (100 = lossless is never probed)
 }
 
 int fri_hip_search_quality(fri_hip_plan *p, const uint8_t *pixels, double target_db, int32_t *quality, double *psnr_db) {
     if (!p || !pixels || !quality || !psnr_db || !(target_db > 0) || p->dev.rct) return FRI_HIP_ERR_INVALID_ARGUMENT;
     if (int rc = need_device(p)) return rc;
-    HIP_TRY(p->ctx, hipSetDevice(p->ctx->device));
-    if (int rc = grow(p->ctx, p->staging.pixels, fri_hip_plan_pixel_bytes(p))) return rc;
-    HIP_TRY(p->ctx, hipMemcpy(p->staging.pixels, pixels, fri_hip_plan_pixel_bytes(p), hipMemcpyHostToDevice));
+    if (int rc = stage_pixels(p->ctx, p->staging.pixels, pixels, fri_hip_plan_pixel_bytes(p))) return rc;
     return fri_hip_search_quality_dev(p, p->staging.pixels, target_db, quality, psnr_db, nullptr);
 }
 
@@ -1876,26 +1626,14 @@ int fri_hip_search_quality_for_size_dev(fri_hip_plan *p, const uint8_t *d_pixels
         HIP_TRY(c, hipStreamSynchronize(s));
         return FRI_HIP_OK;
     };
-    // lo: fits (0 is never probed), hi: does not fit (never probed): 101, or 100 on a YCbCr plan, whose quality 100 is not lossless and has no file (fri_emit)
-    int lo = 0, hi = p->dev.ycc ? 100 : 101;
-    uint64_t lo_est = 0, last = UINT64_MAX;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) / 2;
-        if ((rc = probe(mid, last))) return rc;
-        if (last != UINT64_MAX && last <= max_bytes) lo = mid, lo_est = last;
-        else hi = mid;
-    }
-    *quality = lo;
-    *est_bytes = lo ? lo_est : last; // nothing fits: the last probe was quality 1
-    return lo ? FRI_HIP_OK : FRI_HIP_ERR_OUT_OF_RANGE;
+    // the first quality without a file: 101, or 100 on a YCbCr plan, whose quality 100 is not lossless and has no file (fri_emit)
+    return search_at_most<FRI_HIP_ERR_OUT_OF_RANGE>(max_bytes, p->dev.ycc ? 100 : 101, probe, quality, est_bytes);
 }
 
 int fri_hip_search_quality_for_size(fri_hip_plan *p, const uint8_t *pixels, uint64_t max_bytes, int32_t *quality, uint64_t *est_bytes) {
     if (!p || !pixels || !quality || !est_bytes || max_bytes == 0 || p->dev.rct) return FRI_HIP_ERR_INVALID_ARGUMENT;
     if (int rc = need_device(p)) return rc;
-    HIP_TRY(p->ctx, hipSetDevice(p->ctx->device));
-    if (int rc = grow(p->ctx, p->staging.pixels, fri_hip_plan_pixel_bytes(p))) return rc;
-    HIP_TRY(p->ctx, hipMemcpy(p->staging.pixels, pixels, fri_hip_plan_pixel_bytes(p), hipMemcpyHostToDevice));
+    if (int rc = stage_pixels(p->ctx, p->staging.pixels, pixels, fri_hip_plan_pixel_bytes(p))) return rc;
     return fri_hip_search_quality_for_size_dev(p, p->staging.pixels, max_bytes, quality, est_bytes, nullptr);
 }
 
@@ -1943,40 +1681,29 @@ int fri_hip_search_quality_ssim_dev(fri_hip_plan *p, const uint8_t *d_pixels, do
     int rc;
     if ((rc = grow(c, st.search_coefs, fri_hip_plan_coef_count(p))) || (rc = grow(c, st.ssim_pixels, fri_hip_plan_pixel_bytes(p))) || (rc = grow(c, st.ssim, C + 1)))
         return rc;
-    // the probes' K3: the plan's inverse tiling with the midpoint dequantiser, whatever the caller has set on the plan, writing the raster a decoder gets
-    DevicePlan inv = p->dev_inv;
-    inv.k3_multiply = false;
-    inv.k3_midpoint = true;
-    int lo = 0, hi = 100; // lo: a failure (0 is never probed), hi: a success (100 = lossless is never probed)
-    double hi_ssim = 1.0;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) / 2;
+    const DevicePlan inv = midpoint_inverse(p->dev_inv); // the probes' K3: the plan's inverse tiling, writing the raster a decoder gets
+    auto probe = [&](int mid, double &v) -> int {
         int32_t qm[32];
         QMatrix q;
         fri_hip_quality_matrix(mid, qm);
         check_q(qm, q);
         HIP_TRY(c, launch_fwd_transform_quant(p->dev, 1, d_pixels, 0, st.search_coefs, 0, q, s));
         HIP_TRY(c, launch_inverse_transform(inv, 1, st.search_coefs, 0, q, st.ssim_pixels, 0, s));
-        if ((rc = fri_hip_measure_ssim_dev(p, 1, d_pixels, st.ssim_pixels, 0, (int64_t *)st.ssim.get(), stream))) return rc;
+        if (int r = fri_hip_measure_ssim_dev(p, 1, d_pixels, st.ssim_pixels, 0, (int64_t *)st.ssim.get(), stream)) return r;
         unsigned long long m[4];
         HIP_TRY(c, hipMemcpyAsync(m, st.ssim, (C + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipStreamSynchronize(s));
-        const double v = ssim_of(m, C);
-        if (v >= target) hi = mid, hi_ssim = v;
-        else lo = mid;
-    }
-    *quality = hi;
-    *ssim = hi_ssim;
-    return FRI_HIP_OK;
+        v = ssim_of(m, C);
+        return FRI_HIP_OK;
+    };
+    return search_at_least(target, 1.0, probe, quality, ssim); // (100 = lossless is never probed)
 }
 
 int fri_hip_search_quality_ssim(fri_hip_plan *p, const uint8_t *pixels, double target, int32_t *quality, double *ssim) {
     if (!p || !pixels || !quality || !ssim || !(target > 0 && target <= 1) || p->dev.rct) return FRI_HIP_ERR_INVALID_ARGUMENT;
     if (int rc = ssim_shape(p)) return rc;
     if (int rc = need_device(p)) return rc;
-    HIP_TRY(p->ctx, hipSetDevice(p->ctx->device));
-    if (int rc = grow(p->ctx, p->staging.pixels, fri_hip_plan_pixel_bytes(p))) return rc;
-    HIP_TRY(p->ctx, hipMemcpy(p->staging.pixels, pixels, fri_hip_plan_pixel_bytes(p), hipMemcpyHostToDevice));
+    if (int rc = stage_pixels(p->ctx, p->staging.pixels, pixels, fri_hip_plan_pixel_bytes(p))) return rc;
     return fri_hip_search_quality_ssim_dev(p, p->staging.pixels, target, quality, ssim, nullptr);
 }
 
@@ -2229,1242 +1956,6 @@ int fri_hip_plan_tune_forward(fri_hip_plan *p, uint32_t launches, char *report, 
     const int rc = tune_forward(p, launches, rep);
     if (report && report_bytes) std::snprintf(report, report_bytes, "%s", rep.c_str());
     return rc;
-}
-
-} // extern "C"
-
-/* ---- 4:2:0 chroma subsampling ------------------------------------------------------------------------ */
-// A subsampled plan: two ordinary C = 1 plans (luma W x H; chroma cw x ch, Cb and Cr as a batch of two) and the buffers of the host forms and the searches.
-struct fri_hip_plan420 {
-    fri_hip_ctx *ctx = nullptr;
-    uint32_t width = 0, height = 0, cw = 0, ch = 0;
-    std::unique_ptr<fri_hip_plan, PlanDelete> luma, chroma;
-    Grown<uint8_t> rgb;                // the host forms' pixels
-    Grown<uint8_t> planes;             // the split's output: Y [H][W], Cb [ch][cw], Cr [ch][cw]
-    Grown<uint8_t> recon;              // the inverse kernels' planes, the same layout
-    Grown<uint8_t> recon_rgb;          // fri_hip_search_quality_ssim420*: a probe's merged raster
-    Grown<int32_t> coefs;              // Y [F_y][512], Cb [F_c][512], Cr [F_c][512]
-    Grown<uint16_t> symbols;           // Y [n_y], Cb [n_c], Cr [n_c]
-    Grown<uint32_t> hist;              // [3][10][1024]
-    Grown<unsigned long long> counts;  // [3] out of alphabet, then [3] the fit's out-of-range counts
-    Grown<float> params;               // [3][2][3][6]
-    Grown<unsigned long long> measure; // a probe's sums: distortion [7], SSIM [4] or the rate [1]
-    size_t y_bytes() const { return (size_t)width * height; }
-    size_t c_bytes() const { return (size_t)cw * ch; }
-    size_t plane_bytes() const { return y_bytes() + 2 * c_bytes(); }
-    size_t y_coefs() const { return luma->geo.centers.size() * kCell; }
-    size_t c_coefs() const { return chroma->geo.centers.size() * kCell; }
-};
-
-namespace {
-
-int need_device420(const fri_hip_plan420 *p) {
-    if (!p) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    return p->ctx ? FRI_HIP_OK : FRI_HIP_ERR_NO_DEVICE;
-}
-
-int quality_q(int quality, int32_t qm[32], QMatrix &q) {
-    if (quality < 1 || quality > 99) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    fri_hip_quality_matrix(quality, qm);
-    return check_q(qm, q);
-}
-
-// K1 on the three planes at p->planes into p->coefs: the luma plane, then Cb and Cr as a batch of two
-int forward420(fri_hip_plan420 *p, const QMatrix &q, hipStream_t s) {
-    HIP_TRY(p->ctx, launch_fwd_transform_quant(p->luma->dev, 1, p->planes, 0, p->coefs, 0, q, s));
-    HIP_TRY(p->ctx, launch_fwd_transform_quant(p->chroma->dev, 2, p->planes + p->y_bytes(), p->c_bytes(), p->coefs + p->y_coefs(), p->c_coefs(), q, s));
-    return FRI_HIP_OK;
-}
-
-// K3 with the midpoint dequantiser on the three coefficient planes at d_coefs into p->recon, whatever dequantiser the inner plans are set to
-int inverse420(fri_hip_plan420 *p, const int32_t *d_coefs, const QMatrix &q, hipStream_t s) {
-    DevicePlan il = p->luma->dev_inv, ic = p->chroma->dev_inv;
-    il.k3_multiply = ic.k3_multiply = false;
-    il.k3_midpoint = ic.k3_midpoint = true;
-    HIP_TRY(p->ctx, launch_inverse_transform(il, 1, d_coefs, 0, q, p->recon, 0, s));
-    HIP_TRY(p->ctx, launch_inverse_transform(ic, 2, d_coefs + p->y_coefs(), p->c_coefs(), q, p->recon + p->y_bytes(), p->c_bytes(), s));
-    return FRI_HIP_OK;
-}
-
-// the host forms' pixels into p->rgb
-int stage_pixels420(fri_hip_plan420 *p, const uint8_t *pixels) {
-    HIP_TRY(p->ctx, hipSetDevice(p->ctx->device));
-    if (int rc = grow(p->ctx, p->rgb, 3 * p->y_bytes())) return rc;
-    HIP_TRY(p->ctx, hipMemcpy(p->rgb, pixels, 3 * p->y_bytes(), hipMemcpyHostToDevice));
-    return FRI_HIP_OK;
-}
-
-} // namespace
-
-extern "C" {
-
-int fri_hip_plan420_create(fri_hip_ctx *ctx, uint32_t width, uint32_t height, fri_hip_plan420 **out) {
-    if (!out) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    *out = nullptr;
-    if (!width || !height) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    fri_hip_plan420 *p = new (std::nothrow) fri_hip_plan420;
-    if (!p) return FRI_HIP_ERR_OUT_OF_MEMORY;
-    p->ctx = ctx, p->width = width, p->height = height, p->cw = (width + 1) / 2, p->ch = (height + 1) / 2;
-    fri_hip_plan *inner = nullptr;
-    int rc = fri_hip_plan_create(ctx, width, height, 1, &inner);
-    p->luma.reset(inner);
-    if (!rc) {
-        rc = fri_hip_plan_create(ctx, p->cw, p->ch, 1, &inner);
-        p->chroma.reset(inner);
-    }
-    if (rc) { // a plan that fails part-way goes with what it has
-        fri_hip_plan420_destroy(p);
-        return rc;
-    }
-    *out = p;
-    return FRI_HIP_OK;
-}
-
-int fri_hip_plan420_destroy(fri_hip_plan420 *p) {
-    if (p && p->ctx) (void)hipSetDevice(p->ctx->device); // the buffers and the inner plans free their resources on the plan's device
-    delete p;
-    return FRI_HIP_OK;
-}
-
-fri_hip_plan *fri_hip_plan420_luma(fri_hip_plan420 *p) { return p ? p->luma.get() : nullptr; }
-fri_hip_plan *fri_hip_plan420_chroma(fri_hip_plan420 *p) { return p ? p->chroma.get() : nullptr; }
-
-int fri_hip_split420_dev(fri_hip_plan420 *p, const uint8_t *d_rgb, uint8_t *d_y, uint8_t *d_cbcr, void *stream) {
-    if (int rc = need_device420(p)) return rc;
-    if (!d_rgb || !d_y || !d_cbcr) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    HIP_TRY(p->ctx, launch_split420(d_rgb, p->width, p->height, d_y, d_cbcr, (hipStream_t)stream));
-    return FRI_HIP_OK;
-}
-
-int fri_hip_merge420_dev(fri_hip_plan420 *p, const uint8_t *d_y, const uint8_t *d_cbcr, uint8_t *d_rgb, void *stream) {
-    if (int rc = need_device420(p)) return rc;
-    if (!d_rgb || !d_y || !d_cbcr) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    HIP_TRY(p->ctx, launch_merge420(d_y, d_cbcr, p->width, p->height, d_rgb, (hipStream_t)stream));
-    return FRI_HIP_OK;
-}
-
-int fri_hip_measure_distortion420_dev(fri_hip_plan420 *p, const uint8_t *d_y, const uint8_t *d_cbcr, const uint8_t *d_reference_rgb, uint64_t *d_out, void *stream) {
-    if (int rc = need_device420(p)) return rc;
-    if (!d_reference_rgb || !d_y || !d_cbcr || !d_out) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    auto *out = reinterpret_cast<unsigned long long *>(d_out);
-    HIP_TRY(p->ctx, launch_clear_sums(out, 7, (hipStream_t)stream));
-    HIP_TRY(p->ctx, launch_merge420(d_y, d_cbcr, p->width, p->height, const_cast<uint8_t *>(d_reference_rgb), (hipStream_t)stream, out));
-    return FRI_HIP_OK;
-}
-
-int fri_hip_encode_image420_symbols(fri_hip_plan420 *p, const uint8_t *pixels, int quality, float *value_params, float *width_params, uint16_t *symbols, uint32_t *hist,
-                                    uint64_t *n_out_of_alphabet) {
-    if (int rc = need_device420(p)) return rc;
-    int32_t qm[32];
-    QMatrix q;
-    if (!pixels || !value_params || !width_params || !symbols || !hist || !n_out_of_alphabet || quality_q(quality, qm, q)) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    fri_hip_ctx *c = p->ctx;
-    int rc;
-    if ((rc = stage_pixels420(p, pixels))) return rc;
-    const size_t n_y = p->luma->geo.n_some, n_c = p->chroma->geo.n_some;
-    if ((rc = grow(c, p->planes, p->plane_bytes())) || (rc = grow(c, p->symbols, std::max<size_t>(n_y + 2 * n_c, 1))) || (rc = grow(c, p->hist, 3 * 10 * 1024)) ||
-        (rc = grow(c, p->counts, 6)) || (rc = grow(c, p->params, 3 * 36)))
-        return rc;
-    HIP_TRY(c, launch_split420(p->rgb, p->width, p->height, p->planes, p->planes + p->y_bytes(), nullptr));
-    uint64_t *oob = reinterpret_cast<uint64_t *>(p->counts.get());
-    if ((rc = fri_hip_encode_symbols_batch_dev(p->luma.get(), 1, p->planes, 0, qm, 1, p->params, nullptr, 0, nullptr, 0, p->symbols, n_y, p->hist, oob, oob + 3, nullptr)))
-        return rc;
-    if ((rc = fri_hip_encode_symbols_batch_dev(p->chroma.get(), 2, p->planes + p->y_bytes(), p->c_bytes(), qm, 1, p->params + 36, nullptr, 0, nullptr, 0, p->symbols + n_y, n_c,
-                                               p->hist + 10 * 1024, oob + 1, oob + 4, nullptr)))
-        return rc;
-    float params[3][2][3][6];
-    uint64_t counts[6];
-    HIP_TRY(c, hipMemcpy(symbols, p->symbols, (n_y + 2 * n_c) * sizeof(uint16_t), hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(hist, p->hist, 3 * 10 * 1024 * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(params, p->params, sizeof(params), hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(counts, p->counts, sizeof(counts), hipMemcpyDeviceToHost));
-    for (int k = 0; k < 3; k++) {
-        std::memcpy(value_params + k * 18, params[k][0], 18 * sizeof(float));
-        std::memcpy(width_params + k * 18, params[k][1], 18 * sizeof(float));
-        n_out_of_alphabet[k] = counts[k];
-    }
-    return counts[3] || counts[4] || counts[5] ? FRI_HIP_ERR_OUT_OF_RANGE : FRI_HIP_OK;
-}
-
-int fri_hip_decode_image420(fri_hip_plan420 *p, const int32_t *coefs, int quality, uint8_t *pixels) {
-    if (int rc = need_device420(p)) return rc;
-    int32_t qm[32];
-    QMatrix q;
-    if (!coefs || !pixels || quality_q(quality, qm, q)) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    fri_hip_ctx *c = p->ctx;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t n = p->y_coefs() + 2 * p->c_coefs();
-    int rc;
-    if ((rc = grow(c, p->coefs, n)) || (rc = grow(c, p->recon, p->plane_bytes())) || (rc = grow(c, p->rgb, 3 * p->y_bytes()))) return rc;
-    HIP_TRY(c, hipMemcpy(p->coefs, coefs, n * sizeof(int32_t), hipMemcpyHostToDevice));
-    if ((rc = inverse420(p, p->coefs, q, nullptr))) return rc;
-    HIP_TRY(c, launch_merge420(p->recon, p->recon + p->y_bytes(), p->width, p->height, p->rgb, nullptr));
-    HIP_TRY(c, hipMemcpy(pixels, p->rgb, 3 * p->y_bytes(), hipMemcpyDeviceToHost));
-    return FRI_HIP_OK;
-}
-
-int fri_hip_search_quality420_dev(fri_hip_plan420 *p, const uint8_t *d_pixels, double target_db, int32_t *quality, double *psnr_db, void *stream) {
-    if (!p || !d_pixels || !quality || !psnr_db || !(target_db > 0)) return FRI_HIP_ERR_INVALID_ARGUMENT; // (!(x > 0): NaN too)
-    if (int rc = need_device420(p)) return rc;
-    const hipStream_t s = (hipStream_t)stream;
-    if (int rc = refuse_capture(p->luma.get(), s, "fri_hip_search_quality420_dev reads every probe back: it cannot be captured into a HIP graph")) return rc;
-    fri_hip_ctx *c = p->ctx;
-    HIP_TRY(c, hipSetDevice(c->device));
-    int rc;
-    if ((rc = grow(c, p->planes, p->plane_bytes())) || (rc = grow(c, p->recon, p->plane_bytes())) || (rc = grow(c, p->coefs, p->y_coefs() + 2 * p->c_coefs())) ||
-        (rc = grow(c, p->measure, 7)))
-        return rc;
-    HIP_TRY(c, launch_split420(d_pixels, p->width, p->height, p->planes, p->planes + p->y_bytes(), s));
-    int lo = 0, hi = 100; // lo: a failure (0 is never probed), hi: a success (100 is never probed)
-    double hi_db = HUGE_VAL;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) / 2;
-        int32_t qm[32];
-        QMatrix q;
-        quality_q(mid, qm, q);
-        if ((rc = forward420(p, q, s)) || (rc = inverse420(p, p->coefs, q, s))) return rc;
-        HIP_TRY(c, launch_clear_sums(p->measure, 7, s));
-        HIP_TRY(c, launch_merge420(p->recon, p->recon + p->y_bytes(), p->width, p->height, const_cast<uint8_t *>(d_pixels), s, p->measure));
-        unsigned long long m[7];
-        HIP_TRY(c, hipMemcpyAsync(m, p->measure, sizeof(m), hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
-        const double db = distortion_psnr(m, 3);
-        if (db >= target_db) hi = mid, hi_db = db;
-        else lo = mid;
-    }
-    *quality = hi;
-    *psnr_db = hi_db;
-    return FRI_HIP_OK;
-}
-
-int fri_hip_search_quality420(fri_hip_plan420 *p, const uint8_t *pixels, double target_db, int32_t *quality, double *psnr_db) {
-    if (!p || !pixels || !quality || !psnr_db || !(target_db > 0)) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    if (int rc = need_device420(p)) return rc;
-    if (int rc = stage_pixels420(p, pixels)) return rc;
-    return fri_hip_search_quality420_dev(p, p->rgb, target_db, quality, psnr_db, nullptr);
-}
-
-int fri_hip_search_quality_ssim420_dev(fri_hip_plan420 *p, const uint8_t *d_pixels, double target, int32_t *quality, double *ssim, void *stream) {
-    if (!p || !d_pixels || !quality || !ssim || !(target > 0 && target <= 1)) return FRI_HIP_ERR_INVALID_ARGUMENT; // (NaN fails both)
-    if (int rc = ssim_shape(p->luma.get())) return rc;
-    if (int rc = need_device420(p)) return rc;
-    const hipStream_t s = (hipStream_t)stream;
-    if (int rc = refuse_capture(p->luma.get(), s, "fri_hip_search_quality_ssim420_dev reads every probe back: it cannot be captured into a HIP graph")) return rc;
-    fri_hip_ctx *c = p->ctx;
-    HIP_TRY(c, hipSetDevice(c->device));
-    int rc;
-    if ((rc = grow(c, p->planes, p->plane_bytes())) || (rc = grow(c, p->recon, p->plane_bytes())) || (rc = grow(c, p->coefs, p->y_coefs() + 2 * p->c_coefs())) ||
-        (rc = grow(c, p->recon_rgb, 3 * p->y_bytes())) || (rc = grow(c, p->measure, 7)))
-        return rc;
-    HIP_TRY(c, launch_split420(d_pixels, p->width, p->height, p->planes, p->planes + p->y_bytes(), s));
-    int lo = 0, hi = 100; // lo: a failure (0 is never probed), hi: a success (100 is never probed)
-    double hi_ssim = 1.0;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) / 2;
-        int32_t qm[32];
-        QMatrix q;
-        quality_q(mid, qm, q);
-        if ((rc = forward420(p, q, s)) || (rc = inverse420(p, p->coefs, q, s))) return rc;
-        HIP_TRY(c, launch_merge420(p->recon, p->recon + p->y_bytes(), p->width, p->height, p->recon_rgb, s));
-        HIP_TRY(c, hipMemsetAsync(p->measure, 0, 4 * sizeof(uint64_t), s));
-        HIP_TRY(c, launch_ssim(1, d_pixels, p->recon_rgb, 0, p->width, p->height, 3, p->measure, s));
-        unsigned long long m[4];
-        HIP_TRY(c, hipMemcpyAsync(m, p->measure, sizeof(m), hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
-        const double v = ssim_of(m, 3);
-        if (v >= target) hi = mid, hi_ssim = v;
-        else lo = mid;
-    }
-    *quality = hi;
-    *ssim = hi_ssim;
-    return FRI_HIP_OK;
-}
-
-int fri_hip_search_quality_ssim420(fri_hip_plan420 *p, const uint8_t *pixels, double target, int32_t *quality, double *ssim) {
-    if (!p || !pixels || !quality || !ssim || !(target > 0 && target <= 1)) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    if (int rc = ssim_shape(p->luma.get())) return rc;
-    if (int rc = need_device420(p)) return rc;
-    if (int rc = stage_pixels420(p, pixels)) return rc;
-    return fri_hip_search_quality_ssim420_dev(p, p->rgb, target, quality, ssim, nullptr);
-}
-
-int fri_hip_search_quality_for_size420_dev(fri_hip_plan420 *p, const uint8_t *d_pixels, uint64_t max_bytes, int32_t *quality, uint64_t *est_bytes, void *stream) {
-    if (!p || !d_pixels || !quality || !est_bytes || max_bytes == 0) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    if (int rc = need_device420(p)) return rc;
-    const hipStream_t s = (hipStream_t)stream;
-    if (int rc = refuse_capture(p->luma.get(), s, "fri_hip_search_quality_for_size420_dev reads every probe back: it cannot be captured into a HIP graph")) return rc;
-    fri_hip_ctx *c = p->ctx;
-    HIP_TRY(c, hipSetDevice(c->device));
-    int rc;
-    if ((rc = grow(c, p->planes, p->plane_bytes())) || (rc = grow(c, p->coefs, p->y_coefs() + 2 * p->c_coefs())) || (rc = grow(c, p->hist, 3 * 10 * 1024)) ||
-        (rc = grow(c, p->counts, 6)) || (rc = grow(c, p->params, 3 * 36)) || (rc = grow(c, p->measure, 7)))
-        return rc;
-    HIP_TRY(c, launch_split420(d_pixels, p->width, p->height, p->planes, p->planes + p->y_bytes(), s));
-    uint64_t *oob = reinterpret_cast<uint64_t *>(p->counts.get());
-    // a probe: K1, the device-side fit and K2 on both plans at quality q (the histograms of fri_hip_encode_image420_symbols), then the rate kernel over the three
-    // histograms as one C = 3 image
-    auto probe = [&](int quality_, uint64_t &est) -> int {
-        int32_t qm[32];
-        fri_hip_quality_matrix(quality_, qm);
-        if (int r = fri_hip_encode_image_batch_dev(p->luma.get(), 1, p->planes, 0, qm, 1, p->params, p->coefs, 0, nullptr, nullptr, 0, p->hist, oob, nullptr, stream)) return r;
-        if (int r = fri_hip_encode_image_batch_dev(p->chroma.get(), 2, p->planes + p->y_bytes(), p->c_bytes(), qm, 1, p->params + 36, p->coefs + p->y_coefs(), p->c_coefs(), nullptr,
-                                                   nullptr, 0, p->hist + 10 * 1024, oob + 1, nullptr, stream))
-            return r;
-        HIP_TRY(c, launch_rate_estimate(1, 3, p->hist, p->counts, p->luma->laplace, p->measure, nullptr, kRateLayout, s));
-        HIP_TRY(c, hipMemcpyAsync(&est, p->measure, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
-        return FRI_HIP_OK;
-    };
-    int lo = 0, hi = 100; // lo: fits (0 is never probed), hi: does not fit (never probed): a 4:2:0 file has a quality of 1..99
-    uint64_t lo_est = 0, last = UINT64_MAX;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) / 2;
-        if ((rc = probe(mid, last))) return rc;
-        if (last != UINT64_MAX && last <= max_bytes) lo = mid, lo_est = last;
-        else hi = mid;
-    }
-    *quality = lo;
-    *est_bytes = lo ? lo_est : last; // nothing fits: the last probe was quality 1
-    return lo ? FRI_HIP_OK : FRI_HIP_ERR_OUT_OF_RANGE;
-}
-
-int fri_hip_search_quality_for_size420(fri_hip_plan420 *p, const uint8_t *pixels, uint64_t max_bytes, int32_t *quality, uint64_t *est_bytes) {
-    if (!p || !pixels || !quality || !est_bytes || max_bytes == 0) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    if (int rc = need_device420(p)) return rc;
-    if (int rc = stage_pixels420(p, pixels)) return rc;
-    return fri_hip_search_quality_for_size420_dev(p, p->rgb, max_bytes, quality, est_bytes, nullptr);
-}
-
-} // extern "C"
-
-/* ---- RGBA: a lossless alpha plane ---------------------------------------------------------------------- */
-// An RGBA plan: two ordinary plans on the same W x H lattice (colour C = 3, alpha C = 1) and the staging buffers, which every call on the plan shares.
-struct fri_hip_plan_rgba {
-    fri_hip_ctx *ctx = nullptr;
-    uint32_t width = 0, height = 0;
-    std::unique_ptr<fri_hip_plan, PlanDelete> colour, alpha;
-    Grown<uint8_t> rgba;              // the host forms' pixels
-    Grown<uint8_t> rgb, a;            // the split's output, the merge's input
-    Grown<int32_t> coefs;             // fri_hip_decode_image_rgba: [4][F][512]
-    Grown<uint16_t> symbols;          // the host encode's outputs: [4][n_some] ...
-    Grown<uint32_t> hist;             // ... [4][10][1024]
-    Grown<unsigned long long> counts; // ... [4] out of alphabet, then [4] the fit's out-of-range counts
-    Grown<float> params;              // ... [4][2][3][6]
-    size_t n_pixels() const { return (size_t)width * height; }
-    size_t plane_coefs() const { return colour->geo.centers.size() * kCell; }
-};
-
-namespace {
-
-int need_device_rgba(const fri_hip_plan_rgba *p) {
-    if (!p) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    return p->ctx ? FRI_HIP_OK : FRI_HIP_ERR_NO_DEVICE;
-}
-
-const int32_t kOnesMatrix[32] = {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1};
-
-} // namespace
-
-extern "C" {
-
-int fri_hip_plan_rgba_create(fri_hip_ctx *ctx, uint32_t width, uint32_t height, fri_hip_plan_rgba **out) {
-    if (!out) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    *out = nullptr;
-    if (!width || !height) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    fri_hip_plan_rgba *p = new (std::nothrow) fri_hip_plan_rgba;
-    if (!p) return FRI_HIP_ERR_OUT_OF_MEMORY;
-    p->ctx = ctx, p->width = width, p->height = height;
-    fri_hip_plan *inner = nullptr;
-    int rc = fri_hip_plan_create(ctx, width, height, 3, &inner);
-    p->colour.reset(inner);
-    if (!rc) {
-        rc = fri_hip_plan_create(ctx, width, height, 1, &inner);
-        p->alpha.reset(inner);
-    }
-    // one lattice for all four channels: the emitter writes and reads the fourth channel with the geometry of the first three
-    if (!rc && (p->colour->geo.centers.size() != p->alpha->geo.centers.size() || p->colour->geo.n_some != p->alpha->geo.n_some)) rc = FRI_HIP_ERR_INVALID_ARGUMENT;
-    if (rc) { // a plan that fails part-way goes with what it has
-        fri_hip_plan_rgba_destroy(p);
-        return rc;
-    }
-    *out = p;
-    return FRI_HIP_OK;
-}
-
-int fri_hip_plan_rgba_destroy(fri_hip_plan_rgba *p) {
-    if (p && p->ctx) (void)hipSetDevice(p->ctx->device); // the buffers and the inner plans free their resources on the plan's device
-    delete p;
-    return FRI_HIP_OK;
-}
-
-fri_hip_plan *fri_hip_plan_rgba_colour(fri_hip_plan_rgba *p) { return p ? p->colour.get() : nullptr; }
-fri_hip_plan *fri_hip_plan_rgba_alpha(fri_hip_plan_rgba *p) { return p ? p->alpha.get() : nullptr; }
-
-int fri_hip_split_rgba_dev(fri_hip_plan_rgba *p, const uint8_t *d_rgba, int clean, uint8_t *d_rgb, uint8_t *d_a, void *stream) {
-    if (int rc = need_device_rgba(p)) return rc;
-    if (!d_rgba || !d_rgb || !d_a || (clean != FRI_HIP_ALPHA_KEEP && clean != FRI_HIP_ALPHA_CLEAN)) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    HIP_TRY(p->ctx, launch_split_rgba(d_rgba, p->width, p->height, clean == FRI_HIP_ALPHA_CLEAN, d_rgb, d_a, (hipStream_t)stream));
-    return FRI_HIP_OK;
-}
-
-int fri_hip_merge_rgba_dev(fri_hip_plan_rgba *p, const uint8_t *d_rgb, const uint8_t *d_a, uint8_t *d_rgba, void *stream) {
-    if (int rc = need_device_rgba(p)) return rc;
-    if (!d_rgba || !d_rgb || !d_a) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    HIP_TRY(p->ctx, launch_merge_rgba(d_rgb, d_a, p->width, p->height, d_rgba, (hipStream_t)stream));
-    return FRI_HIP_OK;
-}
-
-int fri_hip_encode_symbols_rgba_dev(fri_hip_plan_rgba *p, const uint8_t *d_rgba, int clean, const int32_t qmatrix[32], int fit, float *d_params, uint16_t *d_symbols,
-                                    uint32_t *d_hist, uint64_t *d_n_out_of_alphabet, uint64_t *d_fit_out_of_range, void *stream) {
-    if (int rc = need_device_rgba(p)) return rc;
-    if (!d_rgba || !qmatrix || !d_params || !d_symbols || !d_hist || !d_n_out_of_alphabet || (clean != FRI_HIP_ALPHA_KEEP && clean != FRI_HIP_ALPHA_CLEAN))
-        return FRI_HIP_ERR_INVALID_ARGUMENT;
-    if (!p->colour->d_stream_order || !p->alpha->d_stream_order) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    fri_hip_ctx *c = p->ctx;
-    const hipStream_t s = (hipStream_t)stream;
-    if (int rc = refuse_capture(p->colour.get(), s)) return rc; // (what the inner calls refuse, before anything is enqueued or allocated)
-    HIP_TRY(c, hipSetDevice(c->device));
-    int rc;
-    if ((rc = grow(c, p->rgb, 3 * p->n_pixels())) || (rc = grow(c, p->a, p->n_pixels()))) return rc;
-    HIP_TRY(c, launch_split_rgba(d_rgba, p->width, p->height, clean == FRI_HIP_ALPHA_CLEAN, p->rgb, p->a, s));
-    const size_t n = p->colour->geo.n_some;
-    if ((rc = fri_hip_encode_symbols_batch_dev(p->colour.get(), 1, p->rgb, 0, qmatrix, fit, d_params, nullptr, 0, nullptr, 0, d_symbols, 3 * n, d_hist, d_n_out_of_alphabet,
-                                               d_fit_out_of_range, stream)))
-        return rc;
-    return fri_hip_encode_symbols_batch_dev(p->alpha.get(), 1, p->a, 0, kOnesMatrix, fit, d_params + 3 * 36, nullptr, 0, nullptr, 0, d_symbols + 3 * n, n, d_hist + 3 * 10 * 1024,
-                                            d_n_out_of_alphabet + 3, d_fit_out_of_range ? d_fit_out_of_range + 3 : nullptr, stream);
-}
-
-int fri_hip_encode_image_rgba_symbols(fri_hip_plan_rgba *p, const uint8_t *pixels, int clean, const int32_t qmatrix[32], float *value_params, float *width_params,
-                                      uint16_t *symbols, uint32_t *hist, uint64_t *n_out_of_alphabet) {
-    if (int rc = need_device_rgba(p)) return rc;
-    if (!pixels || !qmatrix || !value_params || !width_params || !symbols || !hist || !n_out_of_alphabet) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    fri_hip_ctx *c = p->ctx;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t n = p->colour->geo.n_some;
-    int rc;
-    if ((rc = grow(c, p->rgba, 4 * p->n_pixels())) || (rc = grow(c, p->symbols, std::max<size_t>(4 * n, 1))) || (rc = grow(c, p->hist, 4 * 10 * 1024)) ||
-        (rc = grow(c, p->counts, 8)) || (rc = grow(c, p->params, 4 * 36)))
-        return rc;
-    HIP_TRY(c, hipMemcpy(p->rgba, pixels, 4 * p->n_pixels(), hipMemcpyHostToDevice));
-    uint64_t *oob = reinterpret_cast<uint64_t *>(p->counts.get());
-    if ((rc = fri_hip_encode_symbols_rgba_dev(p, p->rgba, clean, qmatrix, 1, p->params, p->symbols, p->hist, oob, oob + 4, nullptr))) return rc;
-    float params[4][2][3][6];
-    uint64_t counts[8];
-    HIP_TRY(c, hipMemcpy(symbols, p->symbols, 4 * n * sizeof(uint16_t), hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(hist, p->hist, 4 * 10 * 1024 * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(params, p->params, sizeof(params), hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(counts, p->counts, sizeof(counts), hipMemcpyDeviceToHost));
-    for (int k = 0; k < 4; k++) {
-        std::memcpy(value_params + k * 18, params[k][0], 18 * sizeof(float));
-        std::memcpy(width_params + k * 18, params[k][1], 18 * sizeof(float));
-        n_out_of_alphabet[k] = counts[k];
-    }
-    return counts[4] || counts[5] || counts[6] || counts[7] ? FRI_HIP_ERR_OUT_OF_RANGE : FRI_HIP_OK;
-}
-
-int fri_hip_decode_image_rgba(fri_hip_plan_rgba *p, const int32_t *coefs, const int32_t qmatrix[32], uint8_t *pixels) {
-    if (int rc = need_device_rgba(p)) return rc;
-    if (!coefs || !qmatrix || !pixels) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    fri_hip_ctx *c = p->ctx;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t plane = p->plane_coefs();
-    int rc;
-    if ((rc = grow(c, p->coefs, 4 * plane)) || (rc = grow(c, p->rgb, 3 * p->n_pixels())) || (rc = grow(c, p->a, p->n_pixels())) || (rc = grow(c, p->rgba, 4 * p->n_pixels())))
-        return rc;
-    HIP_TRY(c, hipMemcpy(p->coefs, coefs, 4 * plane * sizeof(int32_t), hipMemcpyHostToDevice));
-    if ((rc = fri_hip_inverse_transform_dev(p->colour.get(), p->coefs, qmatrix, p->rgb, nullptr))) return rc;
-    // the alpha plane decodes with the reference dequantiser whatever the caller set on its plan; the setting comes back afterwards
-    fri_hip_plan *al = p->alpha.get();
-    const bool multiply = al->dev_inv.k3_multiply, midpoint = al->dev_inv.k3_midpoint;
-    fri_hip_plan_set_dequantiser(al, FRI_HIP_DEQUANT_REFERENCE);
-    rc = fri_hip_inverse_transform_dev(al, p->coefs + 3 * plane, kOnesMatrix, p->a, nullptr);
-    fri_hip_plan_set_dequantiser(al, multiply ? FRI_HIP_DEQUANT_MULTIPLY : midpoint ? FRI_HIP_DEQUANT_MIDPOINT : FRI_HIP_DEQUANT_REFERENCE);
-    if (rc) return rc;
-    HIP_TRY(c, launch_merge_rgba(p->rgb, p->a, p->width, p->height, p->rgba, nullptr));
-    HIP_TRY(c, hipMemcpy(pixels, p->rgba, 4 * p->n_pixels(), hipMemcpyDeviceToHost));
-    return FRI_HIP_OK;
-}
-
-} // extern "C"
-
-/* ---- tiled coding: an image as a batch of independently coded tiles ---------------------------------------- */
-// A tiled plan: one ordinary plan of the tile's shape, the grid, and the staging buffers, which every call on the plan shares.
-struct fri_hip_plan_tiled {
-    fri_hip_ctx *ctx = nullptr;
-    uint32_t width = 0, height = 0, channels = 0, tile_w = 0, tile_h = 0, nx = 0, ny = 0;
-    std::unique_ptr<fri_hip_plan, PlanDelete> tile;
-    Grown<uint8_t> raster;            // the host forms' pixels
-    Grown<uint8_t> tiles;             // the split's output, the merge's input: [ny nx][tile_h][tile_w][C]
-    Grown<int32_t> coefs;             // fri_hip_decode_image_tiled: [n_tiles][C][F][512]
-    Grown<uint16_t> symbols;          // the host encode's outputs: [n_tiles][C][n_some] ...
-    Grown<uint32_t> hist;             // ... [n_tiles][C][10][1024]
-    Grown<unsigned long long> counts; // ... [n_tiles][C] out of alphabet, then [n_tiles][C] the fit's out-of-range counts
-    Grown<float> params;              // ... [n_tiles][C][2][3][6]
-    Grown<uint8_t> recon;             // the searches: a probe's reconstructed tiles, the tile raster's layout (zeroed once per call: a pixel no cell owns stays 0)
-    Grown<uint8_t> recon_raster;      // fri_hip_search_quality_ssim_tiled*: a probe's merged raster
-    Grown<unsigned long long> measure; // a probe's sums: distortion [2 C + 1], SSIM [C + 1] or the file's bytes [1]
-    Grown<unsigned long long> rate;   // the size estimate: the tiles' payload bytes [n_tiles]
-    Grown<unsigned long long> oob_in; // fri_hip_estimate_size_tiled: the host's out-of-alphabet counts [n_tiles][C]
-    Grown<uint32_t> rans_words;       // fri_hip_encode_image_tiled_coded: K11's outputs [n_tiles C][stride] ...
-    Grown<uint32_t> rans_counts;      // ... n_words [n_tiles C], then status [n_tiles C][4], then models [n_tiles C][10][4]
-    Grown<uint16_t> rans_off;         // ... [n_tiles C][10][1024]
-    Grown<uint8_t> rans_scratch;      // ... and its scratch
-    Grown<uint8_t> region;            // fri_hip_decode_region_tiled: the region raster [h][w][C]
-    size_t n_tiles() const { return (size_t)nx * ny; }
-    size_t raster_bytes() const { return (size_t)width * height * channels; }
-    size_t tile_bytes() const { return (size_t)tile_w * tile_h * channels; }
-};
-
-namespace {
-
-int need_device_tiled(const fri_hip_plan_tiled *p) {
-    if (!p) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    return p->ctx ? FRI_HIP_OK : FRI_HIP_ERR_NO_DEVICE;
-}
-
-// the host forms' pixels into p->raster
-int stage_pixels_tiled(fri_hip_plan_tiled *p, const uint8_t *pixels) {
-    HIP_TRY(p->ctx, hipSetDevice(p->ctx->device));
-    if (int rc = grow(p->ctx, p->raster, p->raster_bytes())) return rc;
-    HIP_TRY(p->ctx, hipMemcpy(p->raster, pixels, p->raster_bytes(), hipMemcpyHostToDevice));
-    return FRI_HIP_OK;
-}
-
-// What the PSNR and SSIM searches share: the image split once into p->tiles, and a probe that runs K1 over all tiles into p->coefs and K3 - the inner plan's
-// inverse tiling with the midpoint dequantiser, whatever the caller has set on that plan - into p->recon, zeroed once before the first probe.
-struct TiledProbe {
-    fri_hip_plan_tiled *p;
-    hipStream_t s;
-    DevicePlan inv;
-    size_t image; // coefficients of one tile
-    int begin(const uint8_t *d_pixels) {
-        fri_hip_ctx *c = p->ctx;
-        const size_t n = p->n_tiles();
-        image = fri_hip_plan_coef_count(p->tile.get());
-        int rc;
-        if ((rc = grow(c, p->tiles, n * p->tile_bytes())) || (rc = grow(c, p->recon, n * p->tile_bytes())) || (rc = grow(c, p->coefs, n * image))) return rc;
-        inv = p->tile->dev_inv;
-        inv.k3_multiply = false;
-        inv.k3_midpoint = true;
-        HIP_TRY(c, launch_split_tiles(d_pixels, p->width, p->height, p->channels, p->tile_w, p->tile_h, p->tiles, s));
-        HIP_TRY(c, hipMemsetAsync(p->recon, 0, n * p->tile_bytes(), s));
-        return FRI_HIP_OK;
-    }
-    int round_trip(int quality) {
-        int32_t qm[32];
-        QMatrix q;
-        fri_hip_quality_matrix(quality, qm);
-        check_q(qm, q);
-        const uint32_t n = (uint32_t)p->n_tiles();
-        HIP_TRY(p->ctx, launch_fwd_transform_quant(p->tile->dev, n, p->tiles, p->tile_bytes(), p->coefs, image, q, s));
-        HIP_TRY(p->ctx, launch_inverse_transform(inv, n, p->coefs, image, q, p->recon, p->tile_bytes(), s));
-        return FRI_HIP_OK;
-    }
-};
-
-} // namespace
-
-extern "C" {
-
-uint64_t fri_hip_plan_owned_pixels(const fri_hip_plan *p) { return p ? p->geo.n_valid_leaves : 0; }
-
-int fri_hip_tile_shape(uint32_t width, uint32_t height, uint32_t target, uint32_t *tile_w, uint32_t *tile_h) {
-    if (!width || !height || !target || !tile_w || !tile_h) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    auto first = [&](uint32_t size) { // ceil(size / max(1, round(size / target)))
-        const uint64_t parts = std::max<uint64_t>(1, (2ull * size + target) / (2ull * target));
-        return (uint32_t)((size + parts - 1) / parts);
-    };
-    const uint32_t w0 = first(width), h0 = first(height);
-    for (uint32_t s = 0; s <= 64; s++)
-        for (uint32_t a = 0; a <= s; a++) {
-            const uint64_t w = (uint64_t)w0 + a, h = (uint64_t)h0 + (s - a);
-            if (w > 0xFFFFFFFFull || h > 0xFFFFFFFFull) continue;
-            Geometry g;
-            if (!build_geometry((uint32_t)w, (uint32_t)h, 1, TilingParams{}, g).empty()) continue;
-            if (g.n_valid_leaves == w * h) return *tile_w = (uint32_t)w, *tile_h = (uint32_t)h, FRI_HIP_OK;
-        }
-    return FRI_HIP_ERR_OUT_OF_RANGE;
-}
-
-int fri_hip_plan_tiled_create(fri_hip_ctx *ctx, uint32_t width, uint32_t height, uint32_t channels, uint32_t tile_w, uint32_t tile_h, uint32_t flags,
-                              fri_hip_plan_tiled **out) {
-    if (!out) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    *out = nullptr;
-    if (!width || !height || !tile_w || !tile_h || (channels != 1 && channels != 3) || (flags & ~(uint32_t)FRI_HIP_TILED_ALLOW_HOLES)) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    const uint64_t nx = ((uint64_t)width + tile_w - 1) / tile_w, ny = ((uint64_t)height + tile_h - 1) / tile_h;
-    if (nx * ny * channels > 65535u) return FRI_HIP_ERR_INVALID_ARGUMENT; // one batch launch of the inner plan takes all tiles
-    fri_hip_plan_tiled *p = new (std::nothrow) fri_hip_plan_tiled;
-    if (!p) return FRI_HIP_ERR_OUT_OF_MEMORY;
-    p->ctx = ctx, p->width = width, p->height = height, p->channels = channels, p->tile_w = tile_w, p->tile_h = tile_h, p->nx = (uint32_t)nx, p->ny = (uint32_t)ny;
-    fri_hip_plan *inner = nullptr;
-    int rc = fri_hip_plan_create(ctx, tile_w, tile_h, channels, &inner);
-    p->tile.reset(inner);
-    // a pixel no retained cell owns would be a defect in the middle of the picture
-    if (!rc && !(flags & FRI_HIP_TILED_ALLOW_HOLES) && p->tile->geo.n_valid_leaves != (uint64_t)tile_w * tile_h) rc = FRI_HIP_ERR_INVALID_ARGUMENT;
-    if (rc) { // a plan that fails part-way goes with what it has
-        fri_hip_plan_tiled_destroy(p);
-        return rc;
-    }
-    *out = p;
-    return FRI_HIP_OK;
-}
-
-int fri_hip_plan_tiled_destroy(fri_hip_plan_tiled *p) {
-    if (p && p->ctx) (void)hipSetDevice(p->ctx->device); // the buffers and the inner plan free their resources on the plan's device
-    delete p;
-    return FRI_HIP_OK;
-}
-
-fri_hip_plan *fri_hip_plan_tiled_tile(fri_hip_plan_tiled *p) { return p ? p->tile.get() : nullptr; }
-
-int fri_hip_plan_tiled_grid(const fri_hip_plan_tiled *p, uint32_t out[4]) {
-    if (!p || !out) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    out[0] = p->nx, out[1] = p->ny, out[2] = p->tile_w, out[3] = p->tile_h;
-    return FRI_HIP_OK;
-}
-
-int fri_hip_split_tiles_dev(fri_hip_plan_tiled *p, const uint8_t *d_raster, uint8_t *d_tiles, void *stream) {
-    if (int rc = need_device_tiled(p)) return rc;
-    if (!d_raster || !d_tiles) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    HIP_TRY(p->ctx, launch_split_tiles(d_raster, p->width, p->height, p->channels, p->tile_w, p->tile_h, d_tiles, (hipStream_t)stream));
-    return FRI_HIP_OK;
-}
-
-int fri_hip_merge_tiles_dev(fri_hip_plan_tiled *p, const uint8_t *d_tiles, uint8_t *d_raster, void *stream) {
-    if (int rc = need_device_tiled(p)) return rc;
-    if (!d_raster || !d_tiles) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    HIP_TRY(p->ctx, launch_merge_tiles(d_tiles, p->width, p->height, p->channels, p->tile_w, p->tile_h, d_raster, (hipStream_t)stream));
-    return FRI_HIP_OK;
-}
-
-int fri_hip_encode_symbols_tiled_dev(fri_hip_plan_tiled *p, const uint8_t *d_raster, const int32_t qmatrix[32], int fit, float *d_params, uint16_t *d_symbols, uint32_t *d_hist,
-                                     uint64_t *d_n_out_of_alphabet, uint64_t *d_fit_out_of_range, void *stream) {
-    if (int rc = need_device_tiled(p)) return rc;
-    if (!d_raster || !qmatrix || !d_params || !d_symbols || !d_hist || !d_n_out_of_alphabet || !p->tile->d_stream_order) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    fri_hip_ctx *c = p->ctx;
-    const hipStream_t s = (hipStream_t)stream;
-    QMatrix q;
-    if (int rc = check_q(qmatrix, q)) return rc;
-    if (int rc = refuse_capture(p->tile.get(), s)) return rc; // (what the inner call refuses, before anything is enqueued or allocated)
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (int rc = grow(c, p->tiles, p->n_tiles() * p->tile_bytes())) return rc;
-    HIP_TRY(c, launch_split_tiles(d_raster, p->width, p->height, p->channels, p->tile_w, p->tile_h, p->tiles, s));
-    return fri_hip_encode_symbols_batch_dev(p->tile.get(), (uint32_t)p->n_tiles(), p->tiles, p->tile_bytes(), qmatrix, fit, d_params, nullptr, 0, nullptr, 0, d_symbols,
-                                            (size_t)p->channels * p->tile->geo.n_some, d_hist, d_n_out_of_alphabet, d_fit_out_of_range, stream);
-}
-
-int fri_hip_encode_image_tiled_symbols(fri_hip_plan_tiled *p, const uint8_t *pixels, const int32_t qmatrix[32], float *value_params, float *width_params, uint16_t *symbols,
-                                       uint32_t *hist, uint64_t *n_out_of_alphabet) {
-    if (int rc = need_device_tiled(p)) return rc;
-    if (!pixels || !qmatrix || !value_params || !width_params || !symbols || !hist || !n_out_of_alphabet) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    fri_hip_ctx *c = p->ctx;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t planes = p->n_tiles() * p->channels, n = p->tile->geo.n_some;
-    int rc;
-    if ((rc = grow(c, p->raster, p->raster_bytes())) || (rc = grow(c, p->symbols, std::max<size_t>(planes * n, 1))) || (rc = grow(c, p->hist, planes * 10 * 1024)) ||
-        (rc = grow(c, p->counts, 2 * planes)) || (rc = grow(c, p->params, planes * 36)))
-        return rc;
-    HIP_TRY(c, hipMemcpy(p->raster, pixels, p->raster_bytes(), hipMemcpyHostToDevice));
-    uint64_t *oob = reinterpret_cast<uint64_t *>(p->counts.get());
-    if ((rc = fri_hip_encode_symbols_tiled_dev(p, p->raster, qmatrix, 1, p->params, p->symbols, p->hist, oob, oob + planes, nullptr))) return rc;
-    std::vector<float> params(planes * 36);
-    std::vector<uint64_t> counts(2 * planes);
-    HIP_TRY(c, hipMemcpy(symbols, p->symbols, planes * n * sizeof(uint16_t), hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(hist, p->hist, planes * 10 * 1024 * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(params.data(), p->params, planes * 36 * sizeof(float), hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(counts.data(), p->counts, 2 * planes * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    bool out_of_range = false;
-    for (size_t k = 0; k < planes; k++) {
-        std::memcpy(value_params + k * 18, params.data() + k * 36, 18 * sizeof(float));
-        std::memcpy(width_params + k * 18, params.data() + k * 36 + 18, 18 * sizeof(float));
-        n_out_of_alphabet[k] = counts[k];
-        out_of_range = out_of_range || counts[planes + k];
-    }
-    return out_of_range ? FRI_HIP_ERR_OUT_OF_RANGE : FRI_HIP_OK;
-}
-
-int fri_hip_decode_image_tiled(fri_hip_plan_tiled *p, const int32_t *coefs, const int32_t qmatrix[32], uint8_t *pixels) {
-    if (int rc = need_device_tiled(p)) return rc;
-    if (!coefs || !qmatrix || !pixels) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    fri_hip_ctx *c = p->ctx;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t image = fri_hip_plan_coef_count(p->tile.get()), n = p->n_tiles();
-    int rc;
-    if ((rc = grow(c, p->coefs, n * image)) || (rc = grow(c, p->tiles, n * p->tile_bytes())) || (rc = grow(c, p->raster, p->raster_bytes()))) return rc;
-    HIP_TRY(c, hipMemcpy(p->coefs, coefs, n * image * sizeof(int32_t), hipMemcpyHostToDevice));
-    if ((rc = fri_hip_inverse_transform_batch_dev(p->tile.get(), (uint32_t)n, p->coefs, image, qmatrix, p->tiles, p->tile_bytes(), nullptr))) return rc;
-    HIP_TRY(c, launch_merge_tiles(p->tiles, p->width, p->height, p->channels, p->tile_w, p->tile_h, p->raster, nullptr));
-    HIP_TRY(c, hipMemcpy(pixels, p->raster, p->raster_bytes(), hipMemcpyDeviceToHost));
-    return FRI_HIP_OK;
-}
-
-/* ---- region decode: only the tiles a rectangle touches ---- */
-int fri_hip_plan_tiled_region(const fri_hip_plan_tiled *p, uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint32_t out[4]) {
-    if (!p || !out || !w || !h || (uint64_t)x + w > p->width || (uint64_t)y + h > p->height) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    out[0] = x / p->tile_w, out[1] = y / p->tile_h;
-    out[2] = (uint32_t)(((uint64_t)x + w - 1) / p->tile_w) - out[0] + 1, out[3] = (uint32_t)(((uint64_t)y + h - 1) / p->tile_h) - out[1] + 1;
-    return FRI_HIP_OK;
-}
-
-int fri_hip_merge_tiles_region_dev(fri_hip_plan_tiled *p, const uint8_t *d_tiles, uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint8_t *d_region, void *stream) {
-    uint32_t range[4];
-    if (!p || !d_tiles || !d_region || fri_hip_plan_tiled_region(p, x, y, w, h, range)) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    if (int rc = need_device_tiled(p)) return rc;
-    HIP_TRY(p->ctx, launch_merge_tiles_region(d_tiles, p->width, p->height, p->channels, p->tile_w, p->tile_h, x, y, w, h, d_region, (hipStream_t)stream));
-    return FRI_HIP_OK;
-}
-
-int fri_hip_decode_region_tiled_dev(fri_hip_plan_tiled *p, const int32_t *d_coefs, const int32_t qmatrix[32], uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint8_t *d_region,
-                                    void *stream) {
-    uint32_t range[4];
-    if (!p || !d_coefs || !qmatrix || !d_region || fri_hip_plan_tiled_region(p, x, y, w, h, range)) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    if (int rc = need_device_tiled(p)) return rc;
-    fri_hip_ctx *c = p->ctx;
-    const hipStream_t s = (hipStream_t)stream;
-    QMatrix q;
-    if (int rc = check_q(qmatrix, q)) return rc;
-    if (int rc = refuse_capture(p->tile.get(), s, "fri_hip_decode_region_tiled_dev grows the plan's tile buffer: it cannot be captured into a HIP graph")) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t n = (size_t)range[2] * range[3]; // the touched tiles: the buffer grows to the region's size, never to the image's
-    if (int rc = grow(c, p->tiles, n * p->tile_bytes())) return rc;
-    if (int rc = fri_hip_inverse_transform_batch_dev(p->tile.get(), (uint32_t)n, d_coefs, fri_hip_plan_coef_count(p->tile.get()), qmatrix, p->tiles, p->tile_bytes(), stream)) return rc;
-    HIP_TRY(c, launch_merge_tiles_region(p->tiles, p->width, p->height, p->channels, p->tile_w, p->tile_h, x, y, w, h, d_region, s));
-    return FRI_HIP_OK;
-}
-
-int fri_hip_decode_region_tiled(fri_hip_plan_tiled *p, const int32_t *coefs, const int32_t qmatrix[32], uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint8_t *pixels) {
-    uint32_t range[4];
-    if (!p || !coefs || !qmatrix || !pixels || fri_hip_plan_tiled_region(p, x, y, w, h, range)) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    if (int rc = need_device_tiled(p)) return rc;
-    fri_hip_ctx *c = p->ctx;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t n = (size_t)range[2] * range[3], image = fri_hip_plan_coef_count(p->tile.get()), bytes = (size_t)w * h * p->channels;
-    int rc;
-    if ((rc = grow(c, p->coefs, n * image)) || (rc = grow(c, p->region, bytes))) return rc;
-    HIP_TRY(c, hipMemcpy(p->coefs, coefs, n * image * sizeof(int32_t), hipMemcpyHostToDevice));
-    if ((rc = fri_hip_decode_region_tiled_dev(p, p->coefs, qmatrix, x, y, w, h, p->region, nullptr))) return rc;
-    HIP_TRY(c, hipMemcpy(pixels, p->region, bytes, hipMemcpyDeviceToHost));
-    return FRI_HIP_OK;
-}
-
-/* ---- the measure, the size estimate and the searches over tiles ---- */
-int fri_hip_measure_distortion_tiled_dev(fri_hip_plan_tiled *p, const uint8_t *d_tiles, const uint8_t *d_reference_raster, uint64_t *d_out, void *stream) {
-    if (!p || !d_tiles || !d_reference_raster || !d_out) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    if (int rc = need_device_tiled(p)) return rc;
-    auto *out = reinterpret_cast<unsigned long long *>(d_out);
-    HIP_TRY(p->ctx, launch_clear_sums(out, 2 * p->channels + 1, (hipStream_t)stream));
-    HIP_TRY(p->ctx, launch_measure_tiles(d_tiles, p->width, p->height, p->channels, p->tile_w, p->tile_h, d_reference_raster, out, (hipStream_t)stream));
-    return FRI_HIP_OK;
-}
-
-int fri_hip_estimate_size_tiled_dev(fri_hip_plan_tiled *p, const uint32_t *d_hist, const uint64_t *d_n_out_of_alphabet, uint64_t *d_file_bytes, uint64_t *d_tile_bytes,
-                                    uint32_t *d_models, void *stream) {
-    if (!p || !d_hist || !d_file_bytes || !d_tile_bytes) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    if (int rc = need_device_tiled(p)) return rc;
-    HIP_TRY(p->ctx, hipSetDevice(p->ctx->device));
-    HIP_TRY(p->ctx, launch_rate_estimate_tiled((uint32_t)p->n_tiles(), p->channels, d_hist, reinterpret_cast<const unsigned long long *>(d_n_out_of_alphabet), p->tile->laplace,
-                                               reinterpret_cast<unsigned long long *>(d_tile_bytes), reinterpret_cast<unsigned long long *>(d_file_bytes), d_models, kRateLayout,
-                                               (hipStream_t)stream));
-    return FRI_HIP_OK;
-}
-
-int fri_hip_estimate_size_tiled(fri_hip_plan_tiled *p, const uint32_t *hist, const uint64_t *n_out_of_alphabet, uint64_t *file_bytes, uint64_t *tile_bytes) {
-    if (!p || !hist || !file_bytes) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    if (int rc = need_device_tiled(p)) return rc;
-    fri_hip_ctx *c = p->ctx;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t n = p->n_tiles(), planes = n * p->channels;
-    int rc;
-    if ((rc = grow(c, p->hist, planes * 10 * 1024)) || (rc = grow(c, p->oob_in, planes)) || (rc = grow(c, p->rate, n)) || (rc = grow(c, p->measure, 2 * (size_t)p->channels + 1)))
-        return rc;
-    HIP_TRY(c, hipMemcpy(p->hist, hist, planes * 10 * 1024 * sizeof(uint32_t), hipMemcpyHostToDevice));
-    if (n_out_of_alphabet) HIP_TRY(c, hipMemcpy(p->oob_in, n_out_of_alphabet, planes * sizeof(uint64_t), hipMemcpyHostToDevice));
-    if ((rc = fri_hip_estimate_size_tiled_dev(p, p->hist, n_out_of_alphabet ? (const uint64_t *)p->oob_in.get() : nullptr, (uint64_t *)p->measure.get(), (uint64_t *)p->rate.get(),
-                                              nullptr, nullptr)))
-        return rc;
-    HIP_TRY(c, hipMemcpy(file_bytes, p->measure, sizeof(uint64_t), hipMemcpyDeviceToHost));
-    if (tile_bytes) HIP_TRY(c, hipMemcpy(tile_bytes, p->rate, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    return FRI_HIP_OK;
-}
-
-int fri_hip_search_quality_tiled_dev(fri_hip_plan_tiled *p, const uint8_t *d_pixels, double target_db, int32_t *quality, double *psnr_db, void *stream) {
-    if (!p || !d_pixels || !quality || !psnr_db || !(target_db > 0) || p->tile->dev.rct) return FRI_HIP_ERR_INVALID_ARGUMENT; // (!(x > 0): NaN too)
-    if (int rc = need_device_tiled(p)) return rc;
-    const hipStream_t s = (hipStream_t)stream;
-    if (int rc = refuse_capture(p->tile.get(), s, "fri_hip_search_quality_tiled_dev reads every probe back: it cannot be captured into a HIP graph")) return rc;
-    fri_hip_ctx *c = p->ctx;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const uint32_t C = p->channels;
-    TiledProbe probe{p, s, {}, 0};
-    int rc;
-    if ((rc = grow(c, p->measure, 2 * (size_t)C + 1)) || (rc = probe.begin(d_pixels))) return rc;
-    int lo = 0, hi = 100; // lo: a failure (0 is never probed), hi: a success (100 = lossless is never probed)
-    double hi_db = HUGE_VAL;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) / 2;
-        if ((rc = probe.round_trip(mid))) return rc;
-        HIP_TRY(c, launch_clear_sums(p->measure, 2 * C + 1, s));
-        HIP_TRY(c, launch_measure_tiles(p->recon, p->width, p->height, C, p->tile_w, p->tile_h, d_pixels, p->measure, s));
-        unsigned long long m[7];
-        HIP_TRY(c, hipMemcpyAsync(m, p->measure, (2 * (size_t)C + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
-        const double db = distortion_psnr(m, C);
-        if (db >= target_db) hi = mid, hi_db = db;
-        else lo = mid;
-    }
-    *quality = hi;
-    *psnr_db = hi_db;
-    return FRI_HIP_OK;
-}
-
-int fri_hip_search_quality_tiled(fri_hip_plan_tiled *p, const uint8_t *pixels, double target_db, int32_t *quality, double *psnr_db) {
-    if (!p || !pixels || !quality || !psnr_db || !(target_db > 0) || p->tile->dev.rct) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    if (int rc = need_device_tiled(p)) return rc;
-    if (int rc = stage_pixels_tiled(p, pixels)) return rc;
-    return fri_hip_search_quality_tiled_dev(p, p->raster, target_db, quality, psnr_db, nullptr);
-}
-
-// The SSIM window grid of the whole image, as ssim_shape gives it for a plan's shape
-static int ssim_shape_tiled(const fri_hip_plan_tiled *p) {
-    if (p->width < 8 || p->height < 8) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    return (uint64_t)(p->width / 4 - 1) * (p->height / 4 - 1) > (1ull << 29) ? FRI_HIP_ERR_INVALID_ARGUMENT : FRI_HIP_OK;
-}
-
-int fri_hip_search_quality_ssim_tiled_dev(fri_hip_plan_tiled *p, const uint8_t *d_pixels, double target, int32_t *quality, double *ssim, void *stream) {
-    if (!p || !d_pixels || !quality || !ssim || !(target > 0 && target <= 1) || p->tile->dev.rct) return FRI_HIP_ERR_INVALID_ARGUMENT; // (NaN fails both)
-    if (int rc = ssim_shape_tiled(p)) return rc;
-    if (int rc = need_device_tiled(p)) return rc;
-    const hipStream_t s = (hipStream_t)stream;
-    if (int rc = refuse_capture(p->tile.get(), s, "fri_hip_search_quality_ssim_tiled_dev reads every probe back: it cannot be captured into a HIP graph")) return rc;
-    fri_hip_ctx *c = p->ctx;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const uint32_t C = p->channels;
-    TiledProbe probe{p, s, {}, 0};
-    int rc;
-    if ((rc = grow(c, p->measure, 2 * (size_t)C + 1)) || (rc = grow(c, p->recon_raster, p->raster_bytes())) || (rc = probe.begin(d_pixels))) return rc;
-    int lo = 0, hi = 100; // lo: a failure (0 is never probed), hi: a success (100 = lossless is never probed)
-    double hi_ssim = 1.0;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) / 2;
-        if ((rc = probe.round_trip(mid))) return rc;
-        HIP_TRY(c, launch_merge_tiles(p->recon, p->width, p->height, C, p->tile_w, p->tile_h, p->recon_raster, s));
-        HIP_TRY(c, hipMemsetAsync(p->measure, 0, ((size_t)C + 1) * sizeof(uint64_t), s));
-        HIP_TRY(c, launch_ssim(1, d_pixels, p->recon_raster, 0, p->width, p->height, C, p->measure, s));
-        unsigned long long m[4];
-        HIP_TRY(c, hipMemcpyAsync(m, p->measure, ((size_t)C + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
-        const double v = ssim_of(m, C);
-        if (v >= target) hi = mid, hi_ssim = v;
-        else lo = mid;
-    }
-    *quality = hi;
-    *ssim = hi_ssim;
-    return FRI_HIP_OK;
-}
-
-int fri_hip_search_quality_ssim_tiled(fri_hip_plan_tiled *p, const uint8_t *pixels, double target, int32_t *quality, double *ssim) {
-    if (!p || !pixels || !quality || !ssim || !(target > 0 && target <= 1) || p->tile->dev.rct) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    if (int rc = ssim_shape_tiled(p)) return rc;
-    if (int rc = need_device_tiled(p)) return rc;
-    if (int rc = stage_pixels_tiled(p, pixels)) return rc;
-    return fri_hip_search_quality_ssim_tiled_dev(p, p->raster, target, quality, ssim, nullptr);
-}
-
-int fri_hip_search_quality_for_size_tiled_dev(fri_hip_plan_tiled *p, const uint8_t *d_pixels, uint64_t max_bytes, int32_t *quality, uint64_t *est_bytes, void *stream) {
-    if (!p || !d_pixels || !quality || !est_bytes || max_bytes == 0 || p->tile->dev.rct) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    if (int rc = need_device_tiled(p)) return rc;
-    if (!p->tile->d_stream_order) return FRI_HIP_ERR_INVALID_ARGUMENT; // (the probes run the encode's chain, which needs it)
-    const hipStream_t s = (hipStream_t)stream;
-    if (int rc = refuse_capture(p->tile.get(), s, "fri_hip_search_quality_for_size_tiled_dev reads every probe back: it cannot be captured into a HIP graph")) return rc;
-    fri_hip_ctx *c = p->ctx;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t n = p->n_tiles(), planes = n * p->channels, n_some = p->tile->geo.n_some;
-    int rc;
-    if ((rc = grow(c, p->tiles, n * p->tile_bytes())) || (rc = grow(c, p->symbols, std::max<size_t>(planes * n_some, 1))) || (rc = grow(c, p->hist, planes * 10 * 1024)) ||
-        (rc = grow(c, p->counts, 2 * planes)) || (rc = grow(c, p->params, planes * 36)) || (rc = grow(c, p->rate, n)) || (rc = grow(c, p->measure, 2 * (size_t)p->channels + 1)))
-        return rc;
-    HIP_TRY(c, launch_split_tiles(d_pixels, p->width, p->height, p->channels, p->tile_w, p->tile_h, p->tiles, s));
-    uint64_t *oob = reinterpret_cast<uint64_t *>(p->counts.get());
-    // a probe: the chain of fri_hip_encode_image_tiled_symbols at quality q on the tiles cut above (K1, the device-side fit, K2 over all tiles; the same histograms),
-    // then the tiled estimate
-    auto probe = [&](int q, uint64_t &est) -> int {
-        int32_t qm[32];
-        fri_hip_quality_matrix(q, qm);
-        if (int r = fri_hip_encode_symbols_batch_dev(p->tile.get(), (uint32_t)n, p->tiles, p->tile_bytes(), qm, 1, p->params, nullptr, 0, nullptr, 0, p->symbols,
-                                                     (size_t)p->channels * n_some, p->hist, oob, nullptr, stream))
-            return r;
-        if (int r = fri_hip_estimate_size_tiled_dev(p, p->hist, oob, (uint64_t *)p->measure.get(), (uint64_t *)p->rate.get(), nullptr, stream)) return r;
-        HIP_TRY(c, hipMemcpyAsync(&est, p->measure, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
-        return FRI_HIP_OK;
-    };
-    // lo: fits (0 is never probed), hi: does not fit (never probed): 101, or 100 on a YCbCr inner plan, whose quality 100 is not lossless and has no file
-    int lo = 0, hi = p->tile->dev.ycc ? 100 : 101;
-    uint64_t lo_est = 0, last = UINT64_MAX;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) / 2;
-        if ((rc = probe(mid, last))) return rc;
-        if (last != UINT64_MAX && last <= max_bytes) lo = mid, lo_est = last;
-        else hi = mid;
-    }
-    *quality = lo;
-    *est_bytes = lo ? lo_est : last; // nothing fits: the last probe was quality 1
-    return lo ? FRI_HIP_OK : FRI_HIP_ERR_OUT_OF_RANGE;
-}
-
-int fri_hip_search_quality_for_size_tiled(fri_hip_plan_tiled *p, const uint8_t *pixels, uint64_t max_bytes, int32_t *quality, uint64_t *est_bytes) {
-    if (!p || !pixels || !quality || !est_bytes || max_bytes == 0 || p->tile->dev.rct) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    if (int rc = need_device_tiled(p)) return rc;
-    if (int rc = stage_pixels_tiled(p, pixels)) return rc;
-    return fri_hip_search_quality_for_size_tiled_dev(p, p->raster, max_bytes, quality, est_bytes, nullptr);
-}
-
-} // extern "C"
-
-/* ---- tiled 4:2:0 coding: subsampled tiles ------------------------------------------------------------------------ */
-// A tiled 4:2:0 plan: two ordinary C = 1 plans (a tile's luma plane tile_w x tile_h; its chroma planes cw x ch), the grid, and the staging buffers, which every
-// call on the plan shares. Every per-plane array is in plane order: the n luma planes, then Cb and Cr of tile 0, of tile 1, ...
-struct fri_hip_plan_tiled420 {
-    fri_hip_ctx *ctx = nullptr;
-    uint32_t width = 0, height = 0, tile_w = 0, tile_h = 0, nx = 0, ny = 0, cw = 0, ch = 0;
-    std::unique_ptr<fri_hip_plan, PlanDelete> luma, chroma;
-    Grown<uint8_t> raster;            // the host forms' pixels [H][W][3]
-    Grown<uint8_t> y_tiles, c_tiles;  // the split's output, the merge's input: [n][tile_h][tile_w] and [n][2][ch][cw]
-    Grown<int32_t> coefs;             // the decodes: [n][F_y][512], then [n][2][F_c][512]
-    Grown<uint16_t> symbols;          // the host encode's outputs: [n][n_y], then [n][2][n_c] ...
-    Grown<uint32_t> hist;             // ... [3 n][10][1024]
-    Grown<unsigned long long> counts; // ... [3 n] out of alphabet, then [3 n] the fit's out-of-range counts
-    Grown<float> params;              // ... [3 n][2][3][6]
-    Grown<uint8_t> region;            // fri_hip_decode_region_tiled420: the region raster [h][w][3]
-    size_t n_tiles() const { return (size_t)nx * ny; }
-    size_t raster_bytes() const { return (size_t)width * height * 3; }
-    size_t y_bytes() const { return (size_t)tile_w * tile_h; }
-    size_t c_bytes() const { return (size_t)cw * ch; }
-    size_t y_coefs() const { return luma->geo.centers.size() * kCell; }
-    size_t c_coefs() const { return chroma->geo.centers.size() * kCell; }
-};
-
-namespace {
-
-int need_device_tiled420(const fri_hip_plan_tiled420 *p) {
-    if (!p) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    return p->ctx ? FRI_HIP_OK : FRI_HIP_ERR_NO_DEVICE;
-}
-
-// K3 with the midpoint dequantiser over n tiles' planes at d_coefs (plane order) into p->y_tiles and p->c_tiles, whatever dequantiser the inner plans are set to
-int inverse_tiled420(fri_hip_plan_tiled420 *p, uint32_t n, const int32_t *d_coefs, const QMatrix &q, hipStream_t s) {
-    DevicePlan il = p->luma->dev_inv, ic = p->chroma->dev_inv;
-    il.k3_multiply = ic.k3_multiply = false;
-    il.k3_midpoint = ic.k3_midpoint = true;
-    HIP_TRY(p->ctx, launch_inverse_transform(il, n, d_coefs, p->y_coefs(), q, p->y_tiles, p->y_bytes(), s));
-    HIP_TRY(p->ctx, launch_inverse_transform(ic, 2 * n, d_coefs + (size_t)n * p->y_coefs(), p->c_coefs(), q, p->c_tiles, p->c_bytes(), s));
-    return FRI_HIP_OK;
-}
-
-} // namespace
-
-extern "C" {
-
-int fri_hip_tile_shape420(uint32_t width, uint32_t height, uint32_t target, uint32_t *tile_w, uint32_t *tile_h) {
-    if (!width || !height || !target || !tile_w || !tile_h) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    auto first = [&](uint32_t size) { // ceil(size / max(1, round(size / target)))
-        const uint64_t parts = std::max<uint64_t>(1, (2ull * size + target) / (2ull * target));
-        return (uint32_t)((size + parts - 1) / parts);
-    };
-    auto whole = [](uint64_t w, uint64_t h) { // the C = 1 lattice of w x h owns every pixel
-        Geometry g;
-        return build_geometry((uint32_t)w, (uint32_t)h, 1, TilingParams{}, g).empty() && g.n_valid_leaves == w * h;
-    };
-    const uint32_t w0 = first(width), h0 = first(height);
-    for (uint32_t s = 0; s <= 64; s++)
-        for (uint32_t a = 0; a <= s; a++) {
-            const uint64_t w = (uint64_t)w0 + a, h = (uint64_t)h0 + (s - a);
-            if (w > 0xFFFFFFFFull || h > 0xFFFFFFFFull) continue;
-            if (whole(w, h) && whole((w + 1) / 2, (h + 1) / 2)) return *tile_w = (uint32_t)w, *tile_h = (uint32_t)h, FRI_HIP_OK;
-        }
-    return FRI_HIP_ERR_OUT_OF_RANGE;
-}
-
-int fri_hip_plan_tiled420_create(fri_hip_ctx *ctx, uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t flags, fri_hip_plan_tiled420 **out) {
-    if (!out) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    *out = nullptr;
-    if (!width || !height || !tile_w || !tile_h || (flags & ~(uint32_t)FRI_HIP_TILED_ALLOW_HOLES)) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    const uint64_t nx = ((uint64_t)width + tile_w - 1) / tile_w, ny = ((uint64_t)height + tile_h - 1) / tile_h;
-    if (2 * nx * ny > 65535u) return FRI_HIP_ERR_INVALID_ARGUMENT; // one batch launch of the chroma plan takes both planes of all tiles
-    fri_hip_plan_tiled420 *p = new (std::nothrow) fri_hip_plan_tiled420;
-    if (!p) return FRI_HIP_ERR_OUT_OF_MEMORY;
-    p->ctx = ctx, p->width = width, p->height = height, p->tile_w = tile_w, p->tile_h = tile_h, p->nx = (uint32_t)nx, p->ny = (uint32_t)ny;
-    p->cw = (uint32_t)(((uint64_t)tile_w + 1) / 2), p->ch = (uint32_t)(((uint64_t)tile_h + 1) / 2);
-    fri_hip_plan *inner = nullptr;
-    int rc = fri_hip_plan_create(ctx, tile_w, tile_h, 1, &inner);
-    p->luma.reset(inner);
-    if (!rc) {
-        rc = fri_hip_plan_create(ctx, p->cw, p->ch, 1, &inner);
-        p->chroma.reset(inner);
-    }
-    // a pixel or a chroma sample no retained cell owns would be a defect in the middle of the picture
-    if (!rc && !(flags & FRI_HIP_TILED_ALLOW_HOLES) &&
-        (p->luma->geo.n_valid_leaves != (uint64_t)tile_w * tile_h || p->chroma->geo.n_valid_leaves != (uint64_t)p->cw * p->ch))
-        rc = FRI_HIP_ERR_INVALID_ARGUMENT;
-    if (rc) { // a plan that fails part-way goes with what it has
-        fri_hip_plan_tiled420_destroy(p);
-        return rc;
-    }
-    *out = p;
-    return FRI_HIP_OK;
-}
-
-int fri_hip_plan_tiled420_destroy(fri_hip_plan_tiled420 *p) {
-    if (p && p->ctx) (void)hipSetDevice(p->ctx->device); // the buffers and the inner plans free their resources on the plan's device
-    delete p;
-    return FRI_HIP_OK;
-}
-
-fri_hip_plan *fri_hip_plan_tiled420_luma(fri_hip_plan_tiled420 *p) { return p ? p->luma.get() : nullptr; }
-fri_hip_plan *fri_hip_plan_tiled420_chroma(fri_hip_plan_tiled420 *p) { return p ? p->chroma.get() : nullptr; }
-
-int fri_hip_plan_tiled420_grid(const fri_hip_plan_tiled420 *p, uint32_t out[4]) {
-    if (!p || !out) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    out[0] = p->nx, out[1] = p->ny, out[2] = p->tile_w, out[3] = p->tile_h;
-    return FRI_HIP_OK;
-}
-
-int fri_hip_plan_tiled420_region(const fri_hip_plan_tiled420 *p, uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint32_t out[4]) {
-    if (!p || !out || !w || !h || (uint64_t)x + w > p->width || (uint64_t)y + h > p->height) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    out[0] = x / p->tile_w, out[1] = y / p->tile_h;
-    out[2] = (uint32_t)(((uint64_t)x + w - 1) / p->tile_w) - out[0] + 1, out[3] = (uint32_t)(((uint64_t)y + h - 1) / p->tile_h) - out[1] + 1;
-    return FRI_HIP_OK;
-}
-
-int fri_hip_plan_tiled420_buffer_tiles(const fri_hip_plan_tiled420 *p, uint64_t out[2]) {
-    if (!p || !out) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    out[0] = p->y_tiles.n / p->y_bytes(), out[1] = p->c_tiles.n / (2 * p->c_bytes());
-    return FRI_HIP_OK;
-}
-
-int fri_hip_split_tiles420_dev(fri_hip_plan_tiled420 *p, const uint8_t *d_rgb, uint8_t *d_y_tiles, uint8_t *d_c_tiles, void *stream) {
-    if (int rc = need_device_tiled420(p)) return rc;
-    if (!d_rgb || !d_y_tiles || !d_c_tiles) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    HIP_TRY(p->ctx, launch_split_tiles420(d_rgb, p->width, p->height, p->tile_w, p->tile_h, d_y_tiles, d_c_tiles, (hipStream_t)stream));
-    return FRI_HIP_OK;
-}
-
-int fri_hip_merge_tiles420_region_dev(fri_hip_plan_tiled420 *p, const uint8_t *d_y_tiles, const uint8_t *d_c_tiles, uint32_t x, uint32_t y, uint32_t w, uint32_t h,
-                                      uint8_t *d_region, void *stream) {
-    uint32_t range[4];
-    if (!p || !d_y_tiles || !d_c_tiles || !d_region || fri_hip_plan_tiled420_region(p, x, y, w, h, range)) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    if (int rc = need_device_tiled420(p)) return rc;
-    HIP_TRY(p->ctx, launch_merge_tiles420_region(d_y_tiles, d_c_tiles, p->width, p->height, p->tile_w, p->tile_h, x, y, w, h, d_region, (hipStream_t)stream));
-    return FRI_HIP_OK;
-}
-
-int fri_hip_merge_tiles420_dev(fri_hip_plan_tiled420 *p, const uint8_t *d_y_tiles, const uint8_t *d_c_tiles, uint8_t *d_rgb, void *stream) {
-    if (!p) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    return fri_hip_merge_tiles420_region_dev(p, d_y_tiles, d_c_tiles, 0, 0, p->width, p->height, d_rgb, stream);
-}
-
-int fri_hip_encode_symbols_tiled420_dev(fri_hip_plan_tiled420 *p, const uint8_t *d_rgb, int quality, int fit, float *d_params, uint16_t *d_symbols, uint32_t *d_hist,
-                                        uint64_t *d_n_out_of_alphabet, uint64_t *d_fit_out_of_range, void *stream) {
-    if (int rc = need_device_tiled420(p)) return rc;
-    int32_t qm[32];
-    QMatrix q;
-    if (!d_rgb || !d_params || !d_symbols || !d_hist || !d_n_out_of_alphabet || !p->luma->d_stream_order || !p->chroma->d_stream_order || quality_q(quality, qm, q))
-        return FRI_HIP_ERR_INVALID_ARGUMENT;
-    fri_hip_ctx *c = p->ctx;
-    const hipStream_t s = (hipStream_t)stream;
-    if (int rc = refuse_capture(p->luma.get(), s)) return rc; // (what the inner calls refuse, before anything is enqueued or allocated)
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t n = p->n_tiles(), n_y = p->luma->geo.n_some, n_c = p->chroma->geo.n_some;
-    int rc;
-    if ((rc = grow(c, p->y_tiles, n * p->y_bytes())) || (rc = grow(c, p->c_tiles, 2 * n * p->c_bytes()))) return rc;
-    HIP_TRY(c, launch_split_tiles420(d_rgb, p->width, p->height, p->tile_w, p->tile_h, p->y_tiles, p->c_tiles, s));
-    if ((rc = fri_hip_encode_symbols_batch_dev(p->luma.get(), (uint32_t)n, p->y_tiles, p->y_bytes(), qm, fit, d_params, nullptr, 0, nullptr, 0, d_symbols, n_y, d_hist,
-                                               d_n_out_of_alphabet, d_fit_out_of_range, stream)))
-        return rc;
-    return fri_hip_encode_symbols_batch_dev(p->chroma.get(), (uint32_t)(2 * n), p->c_tiles, p->c_bytes(), qm, fit, d_params + n * 36, nullptr, 0, nullptr, 0, d_symbols + n * n_y,
-                                            n_c, d_hist + n * 10 * 1024, d_n_out_of_alphabet + n, d_fit_out_of_range ? d_fit_out_of_range + n : nullptr, stream);
-}
-
-int fri_hip_encode_image_tiled420_symbols(fri_hip_plan_tiled420 *p, const uint8_t *pixels, int quality, float *value_params, float *width_params, uint16_t *symbols,
-                                          uint32_t *hist, uint64_t *n_out_of_alphabet) {
-    if (int rc = need_device_tiled420(p)) return rc;
-    if (!pixels || !value_params || !width_params || !symbols || !hist || !n_out_of_alphabet) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    fri_hip_ctx *c = p->ctx;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t n = p->n_tiles(), planes = 3 * n, n_sym = n * (p->luma->geo.n_some + 2 * p->chroma->geo.n_some);
-    int rc;
-    if ((rc = grow(c, p->raster, p->raster_bytes())) || (rc = grow(c, p->symbols, std::max<size_t>(n_sym, 1))) || (rc = grow(c, p->hist, planes * 10 * 1024)) ||
-        (rc = grow(c, p->counts, 2 * planes)) || (rc = grow(c, p->params, planes * 36)))
-        return rc;
-    HIP_TRY(c, hipMemcpy(p->raster, pixels, p->raster_bytes(), hipMemcpyHostToDevice));
-    uint64_t *oob = reinterpret_cast<uint64_t *>(p->counts.get());
-    if ((rc = fri_hip_encode_symbols_tiled420_dev(p, p->raster, quality, 1, p->params, p->symbols, p->hist, oob, oob + planes, nullptr))) return rc;
-    std::vector<float> params(planes * 36);
-    std::vector<uint64_t> counts(2 * planes);
-    HIP_TRY(c, hipMemcpy(symbols, p->symbols, n_sym * sizeof(uint16_t), hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(hist, p->hist, planes * 10 * 1024 * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(params.data(), p->params, planes * 36 * sizeof(float), hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(counts.data(), p->counts, 2 * planes * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    bool out_of_range = false;
-    for (size_t k = 0; k < planes; k++) {
-        std::memcpy(value_params + k * 18, params.data() + k * 36, 18 * sizeof(float));
-        std::memcpy(width_params + k * 18, params.data() + k * 36 + 18, 18 * sizeof(float));
-        n_out_of_alphabet[k] = counts[k];
-        out_of_range = out_of_range || counts[planes + k];
-    }
-    return out_of_range ? FRI_HIP_ERR_OUT_OF_RANGE : FRI_HIP_OK;
-}
-
-int fri_hip_decode_region_tiled420_dev(fri_hip_plan_tiled420 *p, const int32_t *d_coefs, int quality, uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint8_t *d_region,
-                                       void *stream) {
-    uint32_t range[4];
-    int32_t qm[32];
-    QMatrix q;
-    if (!p || !d_coefs || !d_region || fri_hip_plan_tiled420_region(p, x, y, w, h, range) || quality_q(quality, qm, q)) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    if (int rc = need_device_tiled420(p)) return rc;
-    fri_hip_ctx *c = p->ctx;
-    const hipStream_t s = (hipStream_t)stream;
-    if (int rc = refuse_capture(p->luma.get(), s, "fri_hip_decode_region_tiled420_dev grows the plan's tile buffers: it cannot be captured into a HIP graph")) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t n = (size_t)range[2] * range[3]; // the touched tiles: the buffers grow to the region's size, never to the image's
-    int rc;
-    if ((rc = grow(c, p->y_tiles, n * p->y_bytes())) || (rc = grow(c, p->c_tiles, 2 * n * p->c_bytes()))) return rc;
-    if ((rc = inverse_tiled420(p, (uint32_t)n, d_coefs, q, s))) return rc;
-    HIP_TRY(c, launch_merge_tiles420_region(p->y_tiles, p->c_tiles, p->width, p->height, p->tile_w, p->tile_h, x, y, w, h, d_region, s));
-    return FRI_HIP_OK;
-}
-
-int fri_hip_decode_region_tiled420(fri_hip_plan_tiled420 *p, const int32_t *coefs, int quality, uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint8_t *pixels) {
-    uint32_t range[4];
-    if (!p || !coefs || !pixels || fri_hip_plan_tiled420_region(p, x, y, w, h, range)) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    if (int rc = need_device_tiled420(p)) return rc;
-    fri_hip_ctx *c = p->ctx;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t n = (size_t)range[2] * range[3], count = n * (p->y_coefs() + 2 * p->c_coefs()), bytes = (size_t)w * h * 3;
-    int rc;
-    if ((rc = grow(c, p->coefs, count)) || (rc = grow(c, p->region, bytes))) return rc;
-    HIP_TRY(c, hipMemcpy(p->coefs, coefs, count * sizeof(int32_t), hipMemcpyHostToDevice));
-    if ((rc = fri_hip_decode_region_tiled420_dev(p, p->coefs, quality, x, y, w, h, p->region, nullptr))) return rc;
-    HIP_TRY(c, hipMemcpy(pixels, p->region, bytes, hipMemcpyDeviceToHost));
-    return FRI_HIP_OK;
-}
-
-int fri_hip_decode_image_tiled420(fri_hip_plan_tiled420 *p, const int32_t *coefs, int quality, uint8_t *pixels) {
-    if (!p) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    return fri_hip_decode_region_tiled420(p, coefs, quality, 0, 0, p->width, p->height, pixels);
-}
-
-} // extern "C"
-
-/* ---- K11: the rANS coder on the device ---------------------------------------------------------------------- */
-namespace {
-bool rans_counts_ok(uint32_t n_planes, uint64_t n_symbols) { return n_planes >= 1 && n_planes <= 65535u && n_symbols >= 1 && n_symbols < (1ull << 31); }
-
-int rans_encode(fri_hip_ctx *ctx, uint32_t n_planes, const uint16_t *d_symbols, size_t symbol_stride, uint64_t n_symbols, const uint32_t *d_hist, uint32_t flags,
-                uint32_t *d_words, size_t word_stride, uint32_t *d_n_words, uint32_t *d_models, uint16_t *d_off_values, uint32_t *d_status, void *d_scratch, void *stream,
-                const hipEvent_t *events) {
-    if (!ctx) return FRI_HIP_ERR_NO_DEVICE;
-    if (!d_symbols || !d_hist || !d_words || !d_n_words || !d_models || !d_off_values || !d_status || !d_scratch || (flags & ~(uint32_t)FRI_HIP_RANS_EMPTY_OK) ||
-        !rans_counts_ok(n_planes, n_symbols) || symbol_stride < n_symbols || ((uintptr_t)d_scratch & 255u))
-        return FRI_HIP_ERR_INVALID_ARGUMENT;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, launch_rans_encode(n_planes, d_symbols, symbol_stride, (uint32_t)n_symbols, d_hist, (flags & FRI_HIP_RANS_EMPTY_OK) != 0, ctx->rans_laplace, d_words, word_stride,
-                                    d_n_words, d_models, d_off_values, d_status, d_scratch, (hipStream_t)stream, events));
-    return FRI_HIP_OK;
-}
-} // namespace
-
-extern "C" {
-
-uint64_t fri_hip_rans_scratch_bytes(uint32_t n_planes, uint64_t n_symbols) { return rans_counts_ok(n_planes, n_symbols) ? rans_scratch_layout(n_planes, n_symbols).total : 0; }
-
-int fri_hip_rans_encode_planes_dev(fri_hip_ctx *ctx, uint32_t n_planes, const uint16_t *d_symbols, size_t symbol_stride, uint64_t n_symbols, const uint32_t *d_hist,
-                                   uint32_t flags, uint32_t *d_words, size_t word_stride, uint32_t *d_n_words, uint32_t *d_models, uint16_t *d_off_values,
-                                   uint32_t *d_status, void *d_scratch, void *stream) {
-    return rans_encode(ctx, n_planes, d_symbols, symbol_stride, n_symbols, d_hist, flags, d_words, word_stride, d_n_words, d_models, d_off_values, d_status, d_scratch, stream,
-                       nullptr);
-}
-
-int fri_hip_rans_time_planes_dev(fri_hip_ctx *ctx, uint32_t n_planes, const uint16_t *d_symbols, size_t symbol_stride, uint64_t n_symbols, const uint32_t *d_hist,
-                                 uint32_t flags, uint32_t *d_words, size_t word_stride, uint32_t *d_n_words, uint32_t *d_models, uint16_t *d_off_values,
-                                 uint32_t *d_status, void *d_scratch, void *stream, double us[3]) {
-    if (!ctx) return FRI_HIP_ERR_NO_DEVICE;
-    if (!us) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    Event ev[4];
-    hipEvent_t raw[4];
-    for (int i = 0; i < 4; i++) {
-        HIP_TRY(ctx, hipEventCreate(ev[i].put()));
-        raw[i] = ev[i];
-    }
-    if (int rc = rans_encode(ctx, n_planes, d_symbols, symbol_stride, n_symbols, d_hist, flags, d_words, word_stride, d_n_words, d_models, d_off_values, d_status, d_scratch,
-                             stream, raw))
-        return rc;
-    HIP_TRY(ctx, hipEventSynchronize(raw[3]));
-    for (int i = 0; i < 3; i++) {
-        float ms = 0;
-        HIP_TRY(ctx, hipEventElapsedTime(&ms, raw[i], raw[i + 1]));
-        us[i] = 1000.0 * ms;
-    }
-    return FRI_HIP_OK;
-}
-
-int fri_hip_encode_image_tiled_coded(fri_hip_plan_tiled *p, const uint8_t *pixels, const int32_t qmatrix[32], float *value_params, float *width_params, uint32_t *words,
-                                     size_t word_stride, uint32_t *n_words, uint32_t *models, uint16_t *off_values, uint32_t *status) {
-    if (int rc = need_device_tiled(p)) return rc;
-    if (!pixels || !qmatrix || !value_params || !width_params || !words || !n_words || !models || !off_values || !status) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    fri_hip_ctx *c = p->ctx;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t planes = p->n_tiles() * p->channels, n = p->tile->geo.n_some;
-    if (!rans_counts_ok((uint32_t)planes, n)) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    int rc;
-    if ((rc = grow(c, p->raster, p->raster_bytes())) || (rc = grow(c, p->symbols, planes * n)) || (rc = grow(c, p->hist, planes * 10 * 1024)) ||
-        (rc = grow(c, p->counts, 2 * planes)) || (rc = grow(c, p->params, planes * 36)) || (rc = grow(c, p->rans_counts, planes * 45)) ||
-        (rc = grow(c, p->rans_off, planes * 10 * 1024)) || (rc = grow(c, p->rans_scratch, rans_scratch_layout((uint32_t)planes, n).total)))
-        return rc;
-    HIP_TRY(c, hipMemcpy(p->raster, pixels, p->raster_bytes(), hipMemcpyHostToDevice));
-    uint64_t *oob = reinterpret_cast<uint64_t *>(p->counts.get());
-    if ((rc = fri_hip_encode_symbols_tiled_dev(p, p->raster, qmatrix, 1, p->params, p->symbols, p->hist, oob, oob + planes, nullptr))) return rc;
-    // K11 into a buffer with room for 8 bits per symbol; a plane that needs more makes the one second pass, with the hard bound: a step emits at most one word
-    uint32_t *d_n_words = p->rans_counts, *d_status = d_n_words + planes, *d_models = d_status + 4 * planes;
-    const size_t bound = n + 20;
-    size_t stride = std::min(bound, n / 4 + 20);
-    std::vector<uint32_t> counts(planes * 45);
-    for (;;) {
-        if ((rc = grow(c, p->rans_words, planes * stride))) return rc;
-        if ((rc = fri_hip_rans_encode_planes_dev(c, (uint32_t)planes, p->symbols, n, n, p->hist, FRI_HIP_RANS_EMPTY_OK, p->rans_words, stride, d_n_words, d_models, p->rans_off,
-                                                 d_status, p->rans_scratch, nullptr)))
-            return rc;
-        HIP_TRY(c, hipMemcpy(counts.data(), p->rans_counts, counts.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        bool too_small = false;
-        for (size_t k = 0; k < planes; k++) too_small = too_small || (counts[planes + 4 * k] & FRI_HIP_RANS_TOO_SMALL);
-        if (!too_small || stride == bound) break;
-        stride = bound;
-    }
-    std::vector<float> params(planes * 36);
-    std::vector<uint64_t> range(2 * planes);
-    HIP_TRY(c, hipMemcpy(params.data(), p->params, planes * 36 * sizeof(float), hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(range.data(), p->counts, 2 * planes * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    std::memcpy(n_words, counts.data(), planes * sizeof(uint32_t));
-    std::memcpy(status, counts.data() + planes, planes * 4 * sizeof(uint32_t));
-    std::memcpy(models, counts.data() + 5 * planes, planes * 40 * sizeof(uint32_t));
-    bool out_of_range = false, refused = false;
-    size_t most_words = 0, most_off = 0;
-    for (size_t k = 0; k < planes; k++) {
-        std::memcpy(value_params + k * 18, params.data() + k * 36, 18 * sizeof(float));
-        std::memcpy(width_params + k * 18, params.data() + k * 36 + 18, 18 * sizeof(float));
-        out_of_range = out_of_range || range[k] || range[planes + k] || n_words[k] > word_stride;
-        refused = refused || status[4 * k];
-        if (n_words[k] <= word_stride && n_words[k] <= stride) most_words = std::max<size_t>(most_words, n_words[k]);
-        for (int b = 0; b < 10; b++) most_off = std::max<size_t>(most_off, std::min<uint32_t>(models[(k * 10 + b) * 4 + 1], 1024u));
-    }
-    // the coded planes only: every plane's row up to the longest row that fits the caller's, every context's list up to the longest list
-    if (most_words)
-        HIP_TRY(c, hipMemcpy2D(words, word_stride * sizeof(uint32_t), p->rans_words, stride * sizeof(uint32_t), most_words * sizeof(uint32_t), planes, hipMemcpyDeviceToHost));
-    if (most_off)
-        HIP_TRY(c, hipMemcpy2D(off_values, 1024 * sizeof(uint16_t), p->rans_off, 1024 * sizeof(uint16_t), most_off * sizeof(uint16_t), planes * 10, hipMemcpyDeviceToHost));
-    return out_of_range ? FRI_HIP_ERR_OUT_OF_RANGE : refused ? FRI_HIP_ERR_INVALID_ARGUMENT : FRI_HIP_OK;
 }
 
 } // extern "C"
