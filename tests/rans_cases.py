@@ -11,10 +11,11 @@ WIDTHS = [2.5, 4.5, 6.3, 8.5, 12.7, 16.0, 20.0, 24.0, 28.0, 36.0]
 SHARE = np.array([47, 15, 10, 8, 6, 5, 4, 3, 1.5, 0.5]) / 100.0  # uneven contexts: the largest holds 47 % of a plane
 
 
-def random_stream(n, seed, outliers=0.02):
-    """n entries `bucket << 10 | symbol`: Laplace-like symbols of each context's own width, a few anywhere in 0..1022 (off-distribution values)"""
+def random_stream(n, seed, outliers=0.02, share=None):
+    """n entries `bucket << 10 | symbol`: Laplace-like symbols of each context's own width, a few anywhere in 0..1022 (off-distribution values); share: the
+    contexts' probabilities (SHARE unless given)"""
     rng = np.random.default_rng(seed)
-    b = rng.choice(10, size=n, p=SHARE)
+    b = rng.choice(10, size=n, p=SHARE if share is None else share)
     k = np.rint(rng.laplace(0.0, np.array(WIDTHS)[b])).astype(np.int64)
     sym = np.where(k >= 0, 2 * k, -2 * k - 1)
     far = rng.random(n) < outliers

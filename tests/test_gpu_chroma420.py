@@ -16,6 +16,7 @@ import pytest
 from frave_amd.api import Plan420  # noqa: F401  (without the feature the module fails here)
 from tests.chroma420_ref import chroma_shape, measure420, merge420, planes_flat, split420
 from tests.common import gen_image
+from tests.later_cases import C420_SATURATED
 from tests.oracle_ref import MIDPOINT, oracle_raster
 from tests.test_gpu_instances import Guarded
 from tests.test_rct_host import correlated_image
@@ -100,6 +101,31 @@ def test_split_merge_and_measure_equal_the_restatement(ctx, shape, kind):
         assert src.get(torch)[1] and pl.get(torch)[1]
         (again,), _ = src.get(torch)
         assert np.array_equal(again, img)
+    P.close()
+
+
+def test_measuring_merge_on_the_saturated_pair(ctx):
+    """the reconstruction all 255 (Y = 255 under neutral chroma) against a reference of zeros, whole strips in whole workgroups: the largest sums the
+    measuring kernel's 32-bit partials can meet, against the analytic values"""
+    import torch
+
+    import frave_amd as fa
+
+    w, h = C420_SATURATED
+    P = fa.Plan420(ctx, w, h)
+    n_y = w * h
+    planes = np.concatenate([np.full(n_y, 255, np.uint8), np.full(P.plane_bytes - n_y, 128, np.uint8)])
+    y, cb, cr = planes[:n_y].reshape(h, w), planes[n_y : n_y + P.cw * P.ch].reshape(P.ch, P.cw), planes[n_y + P.cw * P.ch :].reshape(P.ch, P.cw)
+    assert (merge420(y, cb, cr, w, h) == 255).all()  # the restatement agrees that this is the saturated reconstruction
+    pl = Guarded(torch, P.plane_bytes, offset=1, salt=1)
+    pl.put(torch, [planes])
+    ref = Guarded(torch, P.pixel_bytes, offset=1, salt=2)
+    ref.put(torch, [np.zeros(P.pixel_bytes, np.uint8)])
+    d_out = torch.full((7,), 77, dtype=torch.int64, device="cuda")
+    P.measure_distortion420_dev(pl.ptr, pl.ptr + n_y, ref.ptr, d_out.data_ptr())
+    torch.cuda.synchronize()
+    assert [int(x) for x in d_out.cpu().numpy().astype(np.uint64)] == [255 * 255 * n_y, 255] * 3 + [n_y]
+    assert pl.get(torch)[1] and ref.get(torch)[1]
     P.close()
 
 

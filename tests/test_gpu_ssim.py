@@ -15,6 +15,7 @@ import pytest
 
 from tests import ssim_ref
 from tests.common import gen_image
+from tests.later_cases import SSIM_BAND_CASES, SSIM_EDGE_SHAPES
 from tests.oracle_ref import MIDPOINT
 from tests.test_rct_host import correlated_image
 from tests.ycbcr_ref import COLOUR_YCBCR
@@ -22,6 +23,7 @@ from tests.ycbcr_ref import COLOUR_YCBCR
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPES = [(8, 8, 1), (9, 13, 3), (8, 300, 1), (300, 9, 3), (640, 480, 1), (1001, 613, 3), (4096, 4096, 1), (2048, 1536, 3)]
+SHAPES += SSIM_EDGE_SHAPES  # W / 4 = 1 and 2 mod 128: the last strip `full` with its third block the row's last, and a last strip of one lane with two blocks
 RELAXED = 2  # hipStreamCaptureModeRelaxed
 
 
@@ -112,6 +114,37 @@ def test_n_image_form_equals_single_calls(ctx, shape):
         runs.append(d_out.cpu().numpy())
     assert all(np.array_equal(r, runs[0]) for r in runs)
     assert np.array_equal(runs[0], np.stack(want))
+    P.close()
+
+
+@pytest.mark.parametrize("case", [c for c, _ in SSIM_BAND_CASES], ids=lambda c: "x".join(map(str, c)))
+def test_n_image_form_with_bands_above_four_rows(ctx, case):
+    """launch_ssim's band size above 4 and at its clamp of 64 (tests/later_cases.py has the arithmetic, tests/test_later_cases_host.py checks it): a ragged
+    last band, waves whose band starts past the last window row. Narrow, tall rasters, many images; every image against tests/ssim_ref.py."""
+    import torch
+
+    import frave_amd as fa
+
+    w, h, c, k = case
+    P = fa.Plan(ctx, w, h, c)
+    n = P.pixel_bytes
+    stride = n + 5  # image k starts at byte 5 k (+ 1 and + 3 below): no dword alignment
+    rng = np.random.default_rng(k)
+    A = rng.integers(0, 256, k * stride, dtype=np.uint8)  # garbage in the gaps
+    B = rng.integers(0, 256, k * stride, dtype=np.uint8)
+    want = []
+    for i in range(k):
+        a = A[i * stride : i * stride + n]
+        if i % 3 == 0:  # every third pair is close: source and source + small noise
+            B[i * stride : i * stride + n] = np.clip(a.astype(np.int32) + rng.integers(-6, 7, n), 0, 255).astype(np.uint8)
+        want.append(ssim_ref.measure(a, B[i * stride : i * stride + n], w, h, c))
+    d_a = torch.from_numpy(np.concatenate([np.zeros(1, np.uint8), A])).cuda()
+    d_b = torch.from_numpy(np.concatenate([np.zeros(3, np.uint8), B])).cuda()
+    d_out = torch.full((k, c + 1), 12345, dtype=torch.int64, device="cuda")
+    P.measure_ssim_dev(d_a.data_ptr() + 1, d_b.data_ptr() + 3, d_out.data_ptr(), n_images=k, pixel_stride=stride)
+    torch.cuda.synchronize()
+    got = d_out.cpu().numpy()
+    assert np.array_equal(got, np.stack(want)), np.flatnonzero((got != np.stack(want)).any(axis=1))[:8].tolist()
     P.close()
 
 

@@ -20,6 +20,7 @@ from frave_amd import api
 from frave_amd.api import TILED_ALLOW_HOLES, PlanTiled
 from tests import ssim_ref, tiled_rate_ref
 from tests.common import gen_image
+from tests.later_cases import MEASURE_CLAMPED, MEASURE_RAGGED
 from tests.oracle_ref import MIDPOINT, REFERENCE
 from tests.test_gpu_instances import Guarded
 from tests.tiled_ref import merge_tiles, mixed_image, parse_frit, split_tiles
@@ -105,6 +106,55 @@ def test_measure_sums_pass_2_to_the_32_and_count_every_pixel_once(ctx):
     got = _device_measure(torch, T, d_tiles.data_ptr(), d_ref.data_ptr())
     assert 255 * 255 * w * h > 2 ** 32
     assert got.tolist() == [255 * 255 * w * h, 255] * c + [w * h]
+    T.close()
+
+
+def test_measure_with_a_ragged_last_round_of_strips(ctx):
+    """more than one strip per lane and a workgroup count the strips per lane do not divide (tests/later_cases.py): the last round's workgroups past the end"""
+    import torch
+
+    shape, _ = MEASURE_RAGGED
+    w, h, c, tw, th = shape
+    T = PlanTiled(ctx, w, h, c, tw, th, TILED_ALLOW_HOLES)
+    ref = gen_image("noise", w, h, c, 17).reshape(-1)
+    tiles = np.random.default_rng(18).integers(0, 256, (T.n_tiles, th, tw, c), dtype=np.uint8)
+    d_tiles = Guarded(torch, tiles.size, offset=3, salt=1)
+    d_tiles.put(torch, [tiles.reshape(-1)])
+    d_ref = Guarded(torch, ref.size, offset=1, salt=2)
+    d_ref.put(torch, [ref])
+    got = _device_measure(torch, T, d_tiles.ptr, d_ref.ptr)
+    want = _numpy_measure(tiles, ref, w, h, c)
+    assert np.array_equal(got, want), (got.tolist(), want.tolist())
+    assert d_tiles.get(torch)[1] and d_ref.get(torch)[1]
+    T.close()
+
+
+@pytest.mark.parametrize("content", ["saturated", "noise"])
+def test_measure_past_the_clamp_of_strips_per_lane(ctx, content):
+    """more than 16 384 workgroups of one-strip lanes: 32 strips per lane, the clamp. Saturated (every tile byte 255 against a raster of zeros, the analytic
+    sums) is the worst case for the kernel's 32-bit sums per lane and per wave; noise is held to numpy, the reference summed in row blocks."""
+    import torch
+
+    shape, _ = MEASURE_CLAMPED
+    w, h, c, tw, th = shape
+    T = PlanTiled(ctx, w, h, c, tw, th, TILED_ALLOW_HOLES)
+    if content == "saturated":
+        d_tiles = torch.full((T.tile_bytes,), 255, dtype=torch.uint8, device="cuda")
+        d_ref = torch.zeros(T.pixel_bytes, dtype=torch.uint8, device="cuda")
+        want = [255 * 255 * w * h, 255] * c + [w * h]
+    else:
+        rng = np.random.default_rng(5)
+        tiles = rng.integers(0, 256, (T.n_tiles, th, tw, c), dtype=np.uint8)
+        ref = rng.integers(0, 256, (h, w, c), dtype=np.uint8)
+        merged = merge_tiles(tiles, w, h)
+        sse, worst = 0, 0
+        for y in range(0, h, 512):  # no int64 array of the whole raster
+            d = merged[y : y + 512].astype(np.int64) - ref[y : y + 512]
+            sse, worst = sse + int((d * d).sum()), max(worst, int(np.abs(d).max()))
+        want = [sse, worst, w * h]
+        d_tiles, d_ref = torch.from_numpy(tiles.reshape(-1)).cuda(), torch.from_numpy(ref.reshape(-1)).cuda()
+    got = _device_measure(torch, T, d_tiles.data_ptr(), d_ref.data_ptr())
+    assert got.tolist() == want
     T.close()
 
 
