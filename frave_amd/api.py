@@ -48,6 +48,9 @@ SYMBOLS = [
     "fri_hip_plan_tiled420_grid", "fri_hip_plan_tiled420_region", "fri_hip_plan_tiled420_buffer_tiles", "fri_hip_split_tiles420_dev", "fri_hip_merge_tiles420_dev",
     "fri_hip_merge_tiles420_region_dev", "fri_hip_encode_symbols_tiled420_dev", "fri_hip_encode_image_tiled420_symbols", "fri_hip_decode_image_tiled420",
     "fri_hip_decode_region_tiled420_dev", "fri_hip_decode_region_tiled420",
+    "fri_hip_measure_distortion_tiled420_dev", "fri_hip_estimate_size_tiled420_dev", "fri_hip_estimate_size_tiled420", "fri_hip_search_quality_tiled420",
+    "fri_hip_search_quality_tiled420_dev", "fri_hip_search_quality_ssim_tiled420", "fri_hip_search_quality_ssim_tiled420_dev", "fri_hip_search_quality_for_size_tiled420",
+    "fri_hip_search_quality_for_size_tiled420_dev", "fri_hip_encode_image_tiled420_coded",
 ]
 RANS_EMPTY_OK = 1  # FRI_HIP_RANS_EMPTY_OK: `flags` of fri_hip_rans_encode_planes_dev - a context without counts is coded (the emitter's FRI_EMIT_EMPTY_OK)
 RANS_TOO_SMALL, RANS_BAD_MODEL, RANS_ZERO_FREQ, RANS_BAD_BUCKET = 1, 2, 4, 8  # bits of a plane's status word (include/fri_hip.h)
@@ -261,6 +264,16 @@ def load_library():
     L.fri_hip_decode_image_tiled420.argtypes = [vp, vp, i32, vp]
     L.fri_hip_decode_region_tiled420_dev.argtypes = [vp, vp, i32, u32, u32, u32, u32, vp, vp]
     L.fri_hip_decode_region_tiled420.argtypes = [vp, vp, i32, u32, u32, u32, u32, vp]
+    L.fri_hip_measure_distortion_tiled420_dev.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.fri_hip_estimate_size_tiled420_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.fri_hip_estimate_size_tiled420.argtypes = [vp, vp, vp, vp, vp]
+    L.fri_hip_search_quality_tiled420.argtypes = [vp, vp, C.c_double, vp, vp]
+    L.fri_hip_search_quality_tiled420_dev.argtypes = [vp, vp, C.c_double, vp, vp, vp]
+    L.fri_hip_search_quality_ssim_tiled420.argtypes = [vp, vp, C.c_double, vp, vp]
+    L.fri_hip_search_quality_ssim_tiled420_dev.argtypes = [vp, vp, C.c_double, vp, vp, vp]
+    L.fri_hip_search_quality_for_size_tiled420.argtypes = [vp, vp, C.c_uint64, vp, vp]
+    L.fri_hip_search_quality_for_size_tiled420_dev.argtypes = [vp, vp, C.c_uint64, vp, vp, vp]
+    L.fri_hip_encode_image_tiled420_coded.argtypes = [vp, vp, i32, vp, vp, vp, sz, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -1365,3 +1378,70 @@ class PlanTiled420:
         out = np.empty(w * h * 3, np.uint8)
         _check(load_library().fri_hip_decode_region_tiled420(self._h, _p(co), int(quality), x, y, w, h, _p(out)), "fri_hip_decode_region_tiled420", self.ctx)
         return out
+
+    def encode_image_tiled420_coded(self, pixels, quality, word_stride=None):
+        """fri_hip_encode_image_tiled420_coded: the tiled 4:2:0 chain with the fit, then the device rANS coder over the luma batch and the chroma batch - (words
+        uint32 [3 n][word_stride], n_words uint32 [3 n], models uint32 [3 n][10][4], off_values uint16 [3 n][10][1024], status uint32 [3 n][4], value_params,
+        width_params [3 n][3][6]), all in plane order: what emit.tiled_encode_from_coded420 takes. word_stride: words per plane of the returned array (default
+        max(n_luma, n_chroma) + 20, which always suffices). Needs set_stream_order()."""
+        px = np.ascontiguousarray(pixels, np.uint8).reshape(-1)
+        assert px.size == self.pixel_bytes
+        planes = 3 * self.n_tiles
+        stride = max(self.n_luma, self.n_chroma) + 20 if word_stride is None else int(word_stride)
+        vp, wp = np.zeros((planes, 3, 6), np.float32), np.zeros((planes, 3, 6), np.float32)
+        words = np.zeros((planes, stride), np.uint32)
+        n_words, models = np.zeros(planes, np.uint32), np.zeros((planes, 10, 4), np.uint32)
+        off, status = np.zeros((planes, 10, 1024), np.uint16), np.zeros((planes, 4), np.uint32)
+        _check(load_library().fri_hip_encode_image_tiled420_coded(self._h, _p(px), int(quality), _p(vp), _p(wp), _p(words), stride, _p(n_words), _p(models), _p(off),
+                                                                 _p(status)), "fri_hip_encode_image_tiled420_coded", self.ctx)
+        return words, n_words, models, off, status, vp, wp
+
+    # ---- the measure, the size estimate and the searches over subsampled tiles ------------------------
+    def measure_distortion_tiled420_dev(self, d_y_tiles, d_c_tiles, d_reference_rgb, d_out, stream=0):
+        """fri_hip_measure_distortion_tiled420_dev: the merge of the tiles' planes against a raster [H][W][3] with nothing stored; d_out (uint64 [7], device) = per
+        channel c (R, G, B) the sum of squared differences at 2 c and the largest absolute difference at 2 c + 1, the pixels counted (W H) at 6. Only enqueues."""
+        _check(load_library().fri_hip_measure_distortion_tiled420_dev(self._h, d_y_tiles, d_c_tiles, d_reference_rgb, d_out, stream),
+               "fri_hip_measure_distortion_tiled420_dev", self.ctx)
+
+    def estimate_size_tiled420_dev(self, d_hist, d_oob, d_file_bytes, d_tile_bytes, d_models=None, stream=0):
+        """fri_hip_estimate_size_tiled420_dev: d_hist uint32 [3 n][10][1024], d_oob uint64 [3 n] or None, in plane order -> d_file_bytes uint64 [1], d_tile_bytes
+        uint64 [n] and, if given, d_models uint32 [3 n][10][4]; device pointers. Only enqueues."""
+        _check(load_library().fri_hip_estimate_size_tiled420_dev(self._h, d_hist, d_oob or None, d_file_bytes, d_tile_bytes, d_models or None, stream),
+               "fri_hip_estimate_size_tiled420_dev", self.ctx)
+
+    def estimate_size_tiled420(self, hist, oob=None):
+        """fri_hip_estimate_size_tiled420: hist [3 n][10][1024] (oob [3 n] or None) in plane order, host arrays -> (file bytes, tile bytes uint64 [n]): the
+        estimated size of the tiled 4:2:0 `frit` file and of its payloads; UINT64_MAX where the emitter would refuse a tile."""
+        h = np.ascontiguousarray(hist, np.uint32)
+        assert h.size == 3 * self.n_tiles * 10 * 1024
+        o = None if oob is None else np.ascontiguousarray(oob, np.uint64)
+        assert o is None or o.size == 3 * self.n_tiles
+        total, tiles = C.c_uint64(0), np.zeros(self.n_tiles, np.uint64)
+        _check(load_library().fri_hip_estimate_size_tiled420(self._h, _p(h), None if o is None else _p(o), C.byref(total), _p(tiles)), "fri_hip_estimate_size_tiled420",
+               self.ctx)
+        return total.value, tiles
+
+    def _search(self, name, pixels, target, ctype, stream):
+        qual, v = C.c_int32(0), ctype(0)
+        L = load_library()
+        if isinstance(pixels, int):
+            _check(getattr(L, name + "_dev")(self._h, pixels, target, C.byref(qual), C.byref(v), stream), name + "_dev", self.ctx)
+        else:
+            px = np.ascontiguousarray(pixels, np.uint8)
+            assert px.size == self.pixel_bytes
+            _check(getattr(L, name)(self._h, _p(px), target, C.byref(qual), C.byref(v)), name, self.ctx)
+        return qual.value, v.value
+
+    def search_quality(self, pixels, target_db, stream=0):
+        """fri_hip_search_quality_tiled420[_dev] (pixels: a host array or a device pointer): (quality, PSNR in dB of the tiled 4:2:0 round trip); 100 = no 4:2:0
+        quality reaches the target."""
+        return self._search("fri_hip_search_quality_tiled420", pixels, float(target_db), C.c_double, stream)
+
+    def search_quality_ssim(self, pixels, target, stream=0):
+        """fri_hip_search_quality_ssim_tiled420[_dev]: (quality, SSIM of the tiled 4:2:0 round trip); 100 = no 4:2:0 quality reaches the target."""
+        return self._search("fri_hip_search_quality_ssim_tiled420", pixels, float(target), C.c_double, stream)
+
+    def search_quality_for_size(self, pixels, max_bytes, stream=0):
+        """fri_hip_search_quality_for_size_tiled420[_dev]: (quality, estimated bytes of the `frit` file); FriHipError with code -7 when nothing fits. Needs
+        set_stream_order()."""
+        return self._search("fri_hip_search_quality_for_size_tiled420", pixels, int(max_bytes), C.c_uint64, stream)

@@ -1,8 +1,11 @@
 // fri_hip_tiled420.cpp -- the tiled 4:2:0 plan kind of the C ABI (fri_hip_plan_tiled420: include/fri_hip.h): the plan and its grid, the fused split and merge,
-// the encode chain, and the image and region decodes. Host-side glue like fri_hip.cpp, on two ordinary plans.
+// the encode chain and its coded form (K11), the image and region decodes, the measure, the size estimate and the quality searches. Host-side glue like
+// fri_hip.cpp, on two ordinary plans.
 #include "fri_hip_internal.hpp"
 
 #include <new>
+
+#include "quality_search.hpp"
 
 using namespace fri;
 using namespace fri::host;
@@ -22,6 +25,15 @@ struct fri_hip_plan_tiled420 {
     Grown<unsigned long long> counts; // ... [3 n] out of alphabet, then [3 n] the fit's out-of-range counts
     Grown<float> params;              // ... [3 n][2][3][6]
     Grown<uint8_t> region;            // fri_hip_decode_region_tiled420: the region raster [h][w][3]
+    Grown<uint8_t> recon_y, recon_c;  // the searches: a probe's reconstructed planes, the layouts of y_tiles and c_tiles (zeroed once per call: a sample no cell owns stays 0)
+    Grown<uint8_t> recon_raster;      // fri_hip_search_quality_ssim_tiled420*: a probe's merged raster
+    Grown<unsigned long long> measure; // a probe's sums: distortion [7], SSIM [4] or the file's bytes [1]
+    Grown<unsigned long long> rate;   // the size estimate: the tiles' payload bytes [n]
+    Grown<unsigned long long> oob_in; // fri_hip_estimate_size_tiled420: the host's out-of-alphabet counts [3 n]
+    Grown<uint32_t> rans_words_y, rans_words_c; // fri_hip_encode_image_tiled420_coded: K11's outputs [n][stride_y] and [2 n][stride_c] ...
+    Grown<uint32_t> rans_counts;      // ... n_words [3 n], then status [3 n][4], then models [3 n][10][4]
+    Grown<uint16_t> rans_off;         // ... [3 n][10][1024]
+    Grown<uint8_t> rans_scratch;      // ... and its scratch, the larger of the two batches'
     size_t n_tiles() const { return (size_t)nx * ny; }
     size_t raster_bytes() const { return (size_t)width * height * 3; }
     size_t y_bytes() const { return (size_t)tile_w * tile_h; }
@@ -32,12 +44,52 @@ struct fri_hip_plan_tiled420 {
 
 namespace {
 
-// K3 with the midpoint dequantiser over n tiles' planes at d_coefs (plane order) into p->y_tiles and p->c_tiles, whatever dequantiser the inner plans are set to
-int inverse_tiled420(fri_hip_plan_tiled420 *p, uint32_t n, const int32_t *d_coefs, const QMatrix &q, hipStream_t s) {
+// K3 with the midpoint dequantiser over n tiles' planes at d_coefs (plane order) into d_y and d_c, whatever dequantiser the inner plans are set to
+int inverse_tiled420(fri_hip_plan_tiled420 *p, uint32_t n, const int32_t *d_coefs, const QMatrix &q, uint8_t *d_y, uint8_t *d_c, hipStream_t s) {
     const DevicePlan il = midpoint_inverse(p->luma->dev_inv), ic = midpoint_inverse(p->chroma->dev_inv);
-    HIP_TRY(p->ctx, launch_inverse_transform(il, n, d_coefs, p->y_coefs(), q, p->y_tiles, p->y_bytes(), s));
-    HIP_TRY(p->ctx, launch_inverse_transform(ic, 2 * n, d_coefs + (size_t)n * p->y_coefs(), p->c_coefs(), q, p->c_tiles, p->c_bytes(), s));
+    HIP_TRY(p->ctx, launch_inverse_transform(il, n, d_coefs, p->y_coefs(), q, d_y, p->y_bytes(), s));
+    HIP_TRY(p->ctx, launch_inverse_transform(ic, 2 * n, d_coefs + (size_t)n * p->y_coefs(), p->c_coefs(), q, d_c, p->c_bytes(), s));
     return FRI_HIP_OK;
+}
+
+// What the PSNR and SSIM searches share: the image split once into p->y_tiles and p->c_tiles, and a probe that runs K1 on the luma plan over n planes and on the
+// chroma plan over 2 n planes into p->coefs, then K3 with the midpoint dequantiser into p->recon_y and p->recon_c, zeroed once before the first probe.
+struct Tiled420Probe {
+    fri_hip_plan_tiled420 *p;
+    hipStream_t s;
+    int begin(const uint8_t *d_pixels) {
+        fri_hip_ctx *c = p->ctx;
+        const size_t n = p->n_tiles();
+        int rc;
+        if ((rc = grow(c, p->y_tiles, n * p->y_bytes())) || (rc = grow(c, p->c_tiles, 2 * n * p->c_bytes())) || (rc = grow(c, p->recon_y, n * p->y_bytes())) ||
+            (rc = grow(c, p->recon_c, 2 * n * p->c_bytes())) || (rc = grow(c, p->coefs, n * (p->y_coefs() + 2 * p->c_coefs()))) || (rc = grow(c, p->measure, 7)))
+            return rc;
+        HIP_TRY(c, launch_split_tiles420(d_pixels, p->width, p->height, p->tile_w, p->tile_h, p->y_tiles, p->c_tiles, s));
+        HIP_TRY(c, hipMemsetAsync(p->recon_y, 0, n * p->y_bytes(), s));
+        HIP_TRY(c, hipMemsetAsync(p->recon_c, 0, 2 * n * p->c_bytes(), s));
+        return FRI_HIP_OK;
+    }
+    int round_trip(int quality) {
+        int32_t qm[32];
+        QMatrix q;
+        quality_q(quality, qm, q);
+        const uint32_t n = (uint32_t)p->n_tiles();
+        int32_t *chroma_coefs = p->coefs + (size_t)n * p->y_coefs();
+        HIP_TRY(p->ctx, launch_fwd_transform_quant(p->luma->dev, n, p->y_tiles, p->y_bytes(), p->coefs, p->y_coefs(), q, s));
+        HIP_TRY(p->ctx, launch_fwd_transform_quant(p->chroma->dev, 2 * n, p->c_tiles, p->c_bytes(), chroma_coefs, p->c_coefs(), q, s));
+        return inverse_tiled420(p, n, p->coefs, q, p->recon_y, p->recon_c, s);
+    }
+};
+
+// the chain of fri_hip_encode_symbols_tiled420_dev behind its split: the two batches with quality_matrix(quality), outputs in plane order
+int encode_planes_tiled420(fri_hip_plan_tiled420 *p, const int32_t qm[32], int fit, float *d_params, uint16_t *d_symbols, uint32_t *d_hist, uint64_t *d_n_out_of_alphabet,
+                           uint64_t *d_fit_out_of_range, void *stream) {
+    const size_t n = p->n_tiles(), n_y = p->luma->geo.n_some, n_c = p->chroma->geo.n_some;
+    if (int rc = fri_hip_encode_symbols_batch_dev(p->luma.get(), (uint32_t)n, p->y_tiles, p->y_bytes(), qm, fit, d_params, nullptr, 0, nullptr, 0, d_symbols, n_y, d_hist,
+                                                  d_n_out_of_alphabet, d_fit_out_of_range, stream))
+        return rc;
+    return fri_hip_encode_symbols_batch_dev(p->chroma.get(), (uint32_t)(2 * n), p->c_tiles, p->c_bytes(), qm, fit, d_params + n * 36, nullptr, 0, nullptr, 0, d_symbols + n * n_y,
+                                            n_c, d_hist + n * 10 * 1024, d_n_out_of_alphabet + n, d_fit_out_of_range ? d_fit_out_of_range + n : nullptr, stream);
 }
 
 } // namespace
@@ -153,15 +205,11 @@ int fri_hip_encode_symbols_tiled420_dev(fri_hip_plan_tiled420 *p, const uint8_t 
     const hipStream_t s = (hipStream_t)stream;
     if (int rc = refuse_capture(p->luma.get(), s)) return rc; // (what the inner calls refuse, before anything is enqueued or allocated)
     HIP_TRY(c, hipSetDevice(c->device));
-    const size_t n = p->n_tiles(), n_y = p->luma->geo.n_some, n_c = p->chroma->geo.n_some;
+    const size_t n = p->n_tiles();
     int rc;
     if ((rc = grow(c, p->y_tiles, n * p->y_bytes())) || (rc = grow(c, p->c_tiles, 2 * n * p->c_bytes()))) return rc;
     HIP_TRY(c, launch_split_tiles420(d_rgb, p->width, p->height, p->tile_w, p->tile_h, p->y_tiles, p->c_tiles, s));
-    if ((rc = fri_hip_encode_symbols_batch_dev(p->luma.get(), (uint32_t)n, p->y_tiles, p->y_bytes(), qm, fit, d_params, nullptr, 0, nullptr, 0, d_symbols, n_y, d_hist,
-                                               d_n_out_of_alphabet, d_fit_out_of_range, stream)))
-        return rc;
-    return fri_hip_encode_symbols_batch_dev(p->chroma.get(), (uint32_t)(2 * n), p->c_tiles, p->c_bytes(), qm, fit, d_params + n * 36, nullptr, 0, nullptr, 0, d_symbols + n * n_y,
-                                            n_c, d_hist + n * 10 * 1024, d_n_out_of_alphabet + n, d_fit_out_of_range ? d_fit_out_of_range + n : nullptr, stream);
+    return encode_planes_tiled420(p, qm, fit, d_params, d_symbols, d_hist, d_n_out_of_alphabet, d_fit_out_of_range, stream);
 }
 
 int fri_hip_encode_image_tiled420_symbols(fri_hip_plan_tiled420 *p, const uint8_t *pixels, int quality, float *value_params, float *width_params, uint16_t *symbols,
@@ -199,7 +247,7 @@ int fri_hip_decode_region_tiled420_dev(fri_hip_plan_tiled420 *p, const int32_t *
     const size_t n = (size_t)range[2] * range[3]; // the touched tiles: the buffers grow to the region's size, never to the image's
     int rc;
     if ((rc = grow(c, p->y_tiles, n * p->y_bytes())) || (rc = grow(c, p->c_tiles, 2 * n * p->c_bytes()))) return rc;
-    if ((rc = inverse_tiled420(p, (uint32_t)n, d_coefs, q, s))) return rc;
+    if ((rc = inverse_tiled420(p, (uint32_t)n, d_coefs, q, p->y_tiles, p->c_tiles, s))) return rc;
     HIP_TRY(c, launch_merge_tiles420_region(p->y_tiles, p->c_tiles, p->width, p->height, p->tile_w, p->tile_h, x, y, w, h, d_region, s));
     return FRI_HIP_OK;
 }
@@ -222,6 +270,209 @@ int fri_hip_decode_region_tiled420(fri_hip_plan_tiled420 *p, const int32_t *coef
 int fri_hip_decode_image_tiled420(fri_hip_plan_tiled420 *p, const int32_t *coefs, int quality, uint8_t *pixels) {
     if (!p) return FRI_HIP_ERR_INVALID_ARGUMENT;
     return fri_hip_decode_region_tiled420(p, coefs, quality, 0, 0, p->width, p->height, pixels);
+}
+
+/* ---- the measure, the size estimate and the searches over subsampled tiles ---- */
+int fri_hip_measure_distortion_tiled420_dev(fri_hip_plan_tiled420 *p, const uint8_t *d_y_tiles, const uint8_t *d_c_tiles, const uint8_t *d_reference_rgb, uint64_t *d_out,
+                                            void *stream) {
+    if (!p || !d_y_tiles || !d_c_tiles || !d_reference_rgb || !d_out) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    if (int rc = need_device(p)) return rc;
+    auto *out = reinterpret_cast<unsigned long long *>(d_out);
+    HIP_TRY(p->ctx, launch_clear_sums(out, 7, (hipStream_t)stream));
+    HIP_TRY(p->ctx, launch_measure_tiles420(d_y_tiles, d_c_tiles, p->width, p->height, p->tile_w, p->tile_h, d_reference_rgb, out, (hipStream_t)stream));
+    return FRI_HIP_OK;
+}
+
+int fri_hip_estimate_size_tiled420_dev(fri_hip_plan_tiled420 *p, const uint32_t *d_hist, const uint64_t *d_n_out_of_alphabet, uint64_t *d_file_bytes, uint64_t *d_tile_bytes,
+                                       uint32_t *d_models, void *stream) {
+    if (!p || !d_hist || !d_file_bytes || !d_tile_bytes) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    if (int rc = need_device(p)) return rc;
+    HIP_TRY(p->ctx, hipSetDevice(p->ctx->device));
+    HIP_TRY(p->ctx, launch_rate_estimate_tiled420((uint32_t)p->n_tiles(), d_hist, reinterpret_cast<const unsigned long long *>(d_n_out_of_alphabet), p->luma->laplace,
+                                                  reinterpret_cast<unsigned long long *>(d_tile_bytes), reinterpret_cast<unsigned long long *>(d_file_bytes), d_models,
+                                                  kRateLayout, (hipStream_t)stream));
+    return FRI_HIP_OK;
+}
+
+int fri_hip_estimate_size_tiled420(fri_hip_plan_tiled420 *p, const uint32_t *hist, const uint64_t *n_out_of_alphabet, uint64_t *file_bytes, uint64_t *tile_bytes) {
+    if (!p || !hist || !file_bytes) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    if (int rc = need_device(p)) return rc;
+    fri_hip_ctx *c = p->ctx;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t n = p->n_tiles(), planes = 3 * n;
+    int rc;
+    if ((rc = grow(c, p->hist, planes * 10 * 1024)) || (rc = grow(c, p->oob_in, planes)) || (rc = grow(c, p->rate, n)) || (rc = grow(c, p->measure, 7))) return rc;
+    HIP_TRY(c, hipMemcpy(p->hist, hist, planes * 10 * 1024 * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (n_out_of_alphabet) HIP_TRY(c, hipMemcpy(p->oob_in, n_out_of_alphabet, planes * sizeof(uint64_t), hipMemcpyHostToDevice));
+    if ((rc = fri_hip_estimate_size_tiled420_dev(p, p->hist, n_out_of_alphabet ? (const uint64_t *)p->oob_in.get() : nullptr, (uint64_t *)p->measure.get(),
+                                                 (uint64_t *)p->rate.get(), nullptr, nullptr)))
+        return rc;
+    HIP_TRY(c, hipMemcpy(file_bytes, p->measure, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (tile_bytes) HIP_TRY(c, hipMemcpy(tile_bytes, p->rate, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return FRI_HIP_OK;
+}
+
+int fri_hip_search_quality_tiled420_dev(fri_hip_plan_tiled420 *p, const uint8_t *d_pixels, double target_db, int32_t *quality, double *psnr_db, void *stream) {
+    if (!p || !d_pixels || !quality || !psnr_db || !(target_db > 0)) return FRI_HIP_ERR_INVALID_ARGUMENT; // (!(x > 0): NaN too)
+    if (int rc = need_device(p)) return rc;
+    const hipStream_t s = (hipStream_t)stream;
+    if (int rc = refuse_capture(p->luma.get(), s, "fri_hip_search_quality_tiled420_dev reads every probe back: it cannot be captured into a HIP graph")) return rc;
+    fri_hip_ctx *c = p->ctx;
+    HIP_TRY(c, hipSetDevice(c->device));
+    Tiled420Probe tiles{p, s};
+    if (int rc = tiles.begin(d_pixels)) return rc;
+    auto probe = [&](int mid, double &db) -> int {
+        if (int r = tiles.round_trip(mid)) return r;
+        HIP_TRY(c, launch_clear_sums(p->measure, 7, s));
+        HIP_TRY(c, launch_measure_tiles420(p->recon_y, p->recon_c, p->width, p->height, p->tile_w, p->tile_h, d_pixels, p->measure, s));
+        unsigned long long m[7];
+        HIP_TRY(c, hipMemcpyAsync(m, p->measure, sizeof(m), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        db = distortion_psnr(m, 3);
+        return FRI_HIP_OK;
+    };
+    return search_at_least(target_db, HUGE_VAL, probe, quality, psnr_db); // (100 is never probed: a 4:2:0 file has a quality of 1..99)
+}
+
+int fri_hip_search_quality_tiled420(fri_hip_plan_tiled420 *p, const uint8_t *pixels, double target_db, int32_t *quality, double *psnr_db) {
+    if (!p || !pixels || !quality || !psnr_db || !(target_db > 0)) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    if (int rc = need_device(p)) return rc;
+    if (int rc = stage_pixels(p->ctx, p->raster, pixels, p->raster_bytes())) return rc;
+    return fri_hip_search_quality_tiled420_dev(p, p->raster, target_db, quality, psnr_db, nullptr);
+}
+
+int fri_hip_search_quality_ssim_tiled420_dev(fri_hip_plan_tiled420 *p, const uint8_t *d_pixels, double target, int32_t *quality, double *ssim, void *stream) {
+    if (!p || !d_pixels || !quality || !ssim || !(target > 0 && target <= 1)) return FRI_HIP_ERR_INVALID_ARGUMENT; // (NaN fails both)
+    if (int rc = ssim_shape(p->width, p->height)) return rc;
+    if (int rc = need_device(p)) return rc;
+    const hipStream_t s = (hipStream_t)stream;
+    if (int rc = refuse_capture(p->luma.get(), s, "fri_hip_search_quality_ssim_tiled420_dev reads every probe back: it cannot be captured into a HIP graph")) return rc;
+    fri_hip_ctx *c = p->ctx;
+    HIP_TRY(c, hipSetDevice(c->device));
+    Tiled420Probe tiles{p, s};
+    int rc;
+    if ((rc = grow(c, p->recon_raster, p->raster_bytes())) || (rc = tiles.begin(d_pixels))) return rc;
+    auto probe = [&](int mid, double &v) -> int {
+        if (int r = tiles.round_trip(mid)) return r;
+        HIP_TRY(c, launch_merge_tiles420_region(p->recon_y, p->recon_c, p->width, p->height, p->tile_w, p->tile_h, 0, 0, p->width, p->height, p->recon_raster, s));
+        HIP_TRY(c, hipMemsetAsync(p->measure, 0, 4 * sizeof(uint64_t), s));
+        HIP_TRY(c, launch_ssim(1, d_pixels, p->recon_raster, 0, p->width, p->height, 3, p->measure, s));
+        unsigned long long m[4];
+        HIP_TRY(c, hipMemcpyAsync(m, p->measure, sizeof(m), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        v = ssim_of(m, 3);
+        return FRI_HIP_OK;
+    };
+    return search_at_least(target, 1.0, probe, quality, ssim);
+}
+
+int fri_hip_search_quality_ssim_tiled420(fri_hip_plan_tiled420 *p, const uint8_t *pixels, double target, int32_t *quality, double *ssim) {
+    if (!p || !pixels || !quality || !ssim || !(target > 0 && target <= 1)) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    if (int rc = ssim_shape(p->width, p->height)) return rc;
+    if (int rc = need_device(p)) return rc;
+    if (int rc = stage_pixels(p->ctx, p->raster, pixels, p->raster_bytes())) return rc;
+    return fri_hip_search_quality_ssim_tiled420_dev(p, p->raster, target, quality, ssim, nullptr);
+}
+
+int fri_hip_search_quality_for_size_tiled420_dev(fri_hip_plan_tiled420 *p, const uint8_t *d_pixels, uint64_t max_bytes, int32_t *quality, uint64_t *est_bytes, void *stream) {
+    if (!p || !d_pixels || !quality || !est_bytes || max_bytes == 0) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    if (int rc = need_device(p)) return rc;
+    if (!p->luma->d_stream_order || !p->chroma->d_stream_order) return FRI_HIP_ERR_INVALID_ARGUMENT; // (the probes run the encode's chain, which needs it)
+    const hipStream_t s = (hipStream_t)stream;
+    if (int rc = refuse_capture(p->luma.get(), s, "fri_hip_search_quality_for_size_tiled420_dev reads every probe back: it cannot be captured into a HIP graph")) return rc;
+    fri_hip_ctx *c = p->ctx;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t n = p->n_tiles(), planes = 3 * n, n_sym = n * (p->luma->geo.n_some + 2 * p->chroma->geo.n_some);
+    int rc;
+    if ((rc = grow(c, p->y_tiles, n * p->y_bytes())) || (rc = grow(c, p->c_tiles, 2 * n * p->c_bytes())) || (rc = grow(c, p->symbols, std::max<size_t>(n_sym, 1))) ||
+        (rc = grow(c, p->hist, planes * 10 * 1024)) || (rc = grow(c, p->counts, 2 * planes)) || (rc = grow(c, p->params, planes * 36)) || (rc = grow(c, p->rate, n)) ||
+        (rc = grow(c, p->measure, 7)))
+        return rc;
+    HIP_TRY(c, launch_split_tiles420(d_pixels, p->width, p->height, p->tile_w, p->tile_h, p->y_tiles, p->c_tiles, s));
+    uint64_t *oob = reinterpret_cast<uint64_t *>(p->counts.get());
+    // a probe: the chain of fri_hip_encode_image_tiled420_symbols at quality q on the planes cut above (K1, the device-side fit, K2 on both plans; the same
+    // histograms), then the plane-order estimate
+    auto probe = [&](int q, uint64_t &est) -> int {
+        int32_t qm[32];
+        fri_hip_quality_matrix(q, qm);
+        if (int r = encode_planes_tiled420(p, qm, 1, p->params, p->symbols, p->hist, oob, nullptr, stream)) return r;
+        if (int r = fri_hip_estimate_size_tiled420_dev(p, p->hist, oob, (uint64_t *)p->measure.get(), (uint64_t *)p->rate.get(), nullptr, stream)) return r;
+        HIP_TRY(c, hipMemcpyAsync(&est, p->measure, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        return FRI_HIP_OK;
+    };
+    return search_at_most<FRI_HIP_ERR_OUT_OF_RANGE>(max_bytes, 100, probe, quality, est_bytes); // (a 4:2:0 file has a quality of 1..99)
+}
+
+int fri_hip_search_quality_for_size_tiled420(fri_hip_plan_tiled420 *p, const uint8_t *pixels, uint64_t max_bytes, int32_t *quality, uint64_t *est_bytes) {
+    if (!p || !pixels || !quality || !est_bytes || max_bytes == 0) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    if (int rc = need_device(p)) return rc;
+    if (int rc = stage_pixels(p->ctx, p->raster, pixels, p->raster_bytes())) return rc;
+    return fri_hip_search_quality_for_size_tiled420_dev(p, p->raster, max_bytes, quality, est_bytes, nullptr);
+}
+
+/* ---- the coded form: K11 over the luma batch, then over the chroma batch ---- */
+int fri_hip_encode_image_tiled420_coded(fri_hip_plan_tiled420 *p, const uint8_t *pixels, int quality, float *value_params, float *width_params, uint32_t *words,
+                                        size_t word_stride, uint32_t *n_words, uint32_t *models, uint16_t *off_values, uint32_t *status) {
+    if (int rc = need_device(p)) return rc;
+    if (!pixels || !value_params || !width_params || !words || !n_words || !models || !off_values || !status || quality < 1 || quality > 99) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    fri_hip_ctx *c = p->ctx;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t n = p->n_tiles(), planes = 3 * n, n_y = p->luma->geo.n_some, n_c = p->chroma->geo.n_some, n_sym = n * (n_y + 2 * n_c);
+    if (!rans_counts_ok((uint32_t)n, n_y) || !rans_counts_ok((uint32_t)(2 * n), n_c)) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    const size_t scratch = std::max(rans_scratch_layout((uint32_t)n, n_y).total, rans_scratch_layout((uint32_t)(2 * n), n_c).total); // (the batches run one after the other)
+    int rc;
+    if ((rc = grow(c, p->raster, p->raster_bytes())) || (rc = grow(c, p->symbols, n_sym)) || (rc = grow(c, p->hist, planes * 10 * 1024)) || (rc = grow(c, p->counts, 2 * planes)) ||
+        (rc = grow(c, p->params, planes * 36)) || (rc = grow(c, p->rans_counts, planes * 45)) || (rc = grow(c, p->rans_off, planes * 10 * 1024)) ||
+        (rc = grow(c, p->rans_scratch, scratch)))
+        return rc;
+    HIP_TRY(c, hipMemcpy(p->raster, pixels, p->raster_bytes(), hipMemcpyHostToDevice));
+    uint64_t *oob = reinterpret_cast<uint64_t *>(p->counts.get());
+    if ((rc = fri_hip_encode_symbols_tiled420_dev(p, p->raster, quality, 1, p->params, p->symbols, p->hist, oob, oob + planes, nullptr))) return rc;
+    // K11 per batch - n planes of n_y symbols, then 2 n planes of n_c - each into rows of its own with room for 8 bits per symbol; a batch with a plane that
+    // needs more makes the one second pass, with the hard bound: a step emits at most one word
+    uint32_t *d_n_words = p->rans_counts, *d_status = d_n_words + planes, *d_models = d_status + 4 * planes;
+    std::vector<uint32_t> counts(planes * 45);
+    size_t stride_y = 0, stride_c = 0;
+    auto code = [&](size_t first, size_t count, const uint16_t *d_symbols, size_t n_symbols, Grown<uint32_t> &d_words, size_t &stride) -> int {
+        const size_t bound = n_symbols + 20;
+        stride = std::min(bound, n_symbols / 4 + 20);
+        for (;;) {
+            if (int r = grow(c, d_words, count * stride)) return r;
+            if (int r = fri_hip_rans_encode_planes_dev(c, (uint32_t)count, d_symbols, n_symbols, n_symbols, p->hist + first * 10 * 1024, FRI_HIP_RANS_EMPTY_OK, d_words, stride,
+                                                       d_n_words + first, d_models + first * 40, p->rans_off + first * 10 * 1024, d_status + first * 4, p->rans_scratch, nullptr))
+                return r;
+            HIP_TRY(c, hipMemcpy(counts.data() + planes + 4 * first, d_status + 4 * first, count * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            bool too_small = false;
+            for (size_t k = first; k < first + count; k++) too_small = too_small || (counts[planes + 4 * k] & FRI_HIP_RANS_TOO_SMALL);
+            if (!too_small || stride == bound) return FRI_HIP_OK;
+            stride = bound;
+        }
+    };
+    if ((rc = code(0, n, p->symbols, n_y, p->rans_words_y, stride_y)) || (rc = code(n, 2 * n, p->symbols + n * n_y, n_c, p->rans_words_c, stride_c))) return rc;
+    HIP_TRY(c, hipMemcpy(counts.data(), p->rans_counts, counts.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    std::vector<uint64_t> out_of_alphabet(planes); // (this form has no such output: a plane with any is out of range)
+    bool out_of_range = false, refused = false;
+    if ((rc = read_back_plane_results(c, planes, p->params, p->counts, value_params, width_params, out_of_alphabet.data(), &out_of_range))) return rc;
+    std::memcpy(n_words, counts.data(), planes * sizeof(uint32_t));
+    std::memcpy(status, counts.data() + planes, planes * 4 * sizeof(uint32_t));
+    std::memcpy(models, counts.data() + 5 * planes, planes * 40 * sizeof(uint32_t));
+    size_t most_y = 0, most_c = 0, most_off = 0;
+    for (size_t k = 0; k < planes; k++) {
+        out_of_range = out_of_range || out_of_alphabet[k] || n_words[k] > word_stride;
+        refused = refused || status[4 * k];
+        size_t &most = k < n ? most_y : most_c;
+        if (n_words[k] <= word_stride && n_words[k] <= (k < n ? stride_y : stride_c)) most = std::max<size_t>(most, n_words[k]);
+        for (int b = 0; b < 10; b++) most_off = std::max<size_t>(most_off, std::min<uint32_t>(models[(k * 10 + b) * 4 + 1], 1024u));
+    }
+    // the coded planes only: every plane's row up to the batch's longest row that fits the caller's, every context's list up to the longest list
+    if (most_y) HIP_TRY(c, hipMemcpy2D(words, word_stride * sizeof(uint32_t), p->rans_words_y, stride_y * sizeof(uint32_t), most_y * sizeof(uint32_t), n, hipMemcpyDeviceToHost));
+    if (most_c)
+        HIP_TRY(c, hipMemcpy2D(words + n * word_stride, word_stride * sizeof(uint32_t), p->rans_words_c, stride_c * sizeof(uint32_t), most_c * sizeof(uint32_t), 2 * n,
+                               hipMemcpyDeviceToHost));
+    if (most_off)
+        HIP_TRY(c, hipMemcpy2D(off_values, 1024 * sizeof(uint16_t), p->rans_off, 1024 * sizeof(uint16_t), most_off * sizeof(uint16_t), planes * 10, hipMemcpyDeviceToHost));
+    return out_of_range ? FRI_HIP_ERR_OUT_OF_RANGE : refused ? FRI_HIP_ERR_INVALID_ARGUMENT : FRI_HIP_OK;
 }
 
 } // extern "C"

@@ -13,8 +13,11 @@
 // The whole-image merge is this kernel with the region (0, 0, W, H) on the full grid. Nothing outside the region raster is written and no replicated pixel is
 // read for it.
 //
+// measure_tiles420_kernel: the whole-image merge's walk with nothing stored - each pixel is compared with the reference raster's and only seven sums leave the kernel
+// (several strips per lane on large images, wave reduction, LDS, one 64-bit atomic per sum and workgroup).
+//
 // No raster has a row pitch and every buffer starts at any byte: the vector accesses are the target's unaligned global loads and stores (the compiler is told
-// the alignment is 1). Every byte offset is 64-bit. No LDS, no atomics: the kernels only enqueue and can be captured into a graph.
+// the alignment is 1). Every byte offset is 64-bit. Split and merge use no LDS and no atomics; every kernel only enqueues and can be captured into a graph.
 #include "device_common.hpp"
 
 namespace fri {
@@ -235,7 +238,136 @@ __global__ void __launch_bounds__(kT420Threads) merge_tiles420_region_kernel(con
     }
 }
 
-// the limits both launchers share: sizes that keep every u32 product above in range; false for a shape outside them
+// measure_tiles420_kernel: the whole-image merge walk - the region (0, 0, W, H) on the full grid - with nothing stored. A lane owns the same 16 pixels of an image
+// row, classifies its strip as the merge does and, where the merge stores 48 bytes, loads the same 48 bytes of the reference raster [H][W][3] instead (byte loads on
+// the pixel-by-pixel path). The strip bodies are the measuring form's own, so that the merge's instances compile to what they were. Both inputs are only read.
+struct MeasureTiles420Args {
+    const uint8_t *y, *c;    // the full grid's planes
+    const uint8_t *ref;      // the reference raster
+    unsigned long long *out; // [7], zeroed: SSE and largest error of R, G, B, then the pixels counted
+    uint32_t tile_w, tile_h, cw, ch, nx;
+    uint32_t w;        // the image's width
+    uint32_t n_strips; // strips per image row
+    uint32_t n_items;  // H x n_strips
+    uint32_t per_lane; // strips per lane
+};
+
+__device__ __forceinline__ void measure_add(int got, int want, uint32_t &sse, uint32_t &worst) {
+    const int d = got - want;
+    const uint32_t a = (uint32_t)(d < 0 ? -d : d);
+    sse += a * a;
+    worst = max(worst, a);
+}
+
+// merge_tile_strip<ODD>'s 16 pixels against 48 bytes of the reference at ref
+template <int ODD>
+__device__ __forceinline__ void measure_tile_strip(const MeasureTiles420Args &p, const uint8_t *y_tile, const uint8_t *c_tile, int tx, int ty, const uint8_t *ref,
+                                                   uint32_t (&sse)[3], uint32_t (&worst)[3]) {
+    const int ch = (int)p.ch, cw = (int)p.cw;
+    const int j = ty >> 1, j2 = (ty & 1) ? min(j + 1, ch - 1) : max(j - 1, 0);
+    int vb[kT420Strip / 2 + 2], vr[kT420Strip / 2 + 2];
+    load_tile_chroma(c_tile, cw, j, j2, tx >> 1, vb);
+    load_tile_chroma(c_tile + (uint64_t)ch * cw, cw, j, j2, tx >> 1, vr);
+    const u32x4 yv = load_unaligned<u32x4>(y_tile + (uint64_t)ty * p.tile_w + tx);
+    const uint32_t yw[4] = {yv.x, yv.y, yv.z, yv.w};
+    uint32_t rw[12];
+#pragma unroll
+    for (int q = 0; q < 3; q++) {
+        const u32x4 v = load_unaligned<u32x4>(ref + 16 * q);
+        rw[4 * q] = v.x, rw[4 * q + 1] = v.y, rw[4 * q + 2] = v.z, rw[4 * q + 3] = v.w;
+    }
+#pragma unroll
+    for (int k = 0; k < kT420Strip; k++) {
+        const int m = 1 + ((k + ODD) >> 1), n = ((k + ODD) & 1) ? m + 1 : m - 1; // the column's own sample and its neighbour on the pixel's side
+        int R, G, B;
+        ycc_to_rgb(byte_of(yw, k), (3 * vb[m] + vb[n] + 8) >> 4, (3 * vr[m] + vr[n] + 8) >> 4, R, G, B);
+        measure_add(R, byte_of(rw, 3 * k), sse[0], worst[0]);
+        measure_add(G, byte_of(rw, 3 * k + 1), sse[1], worst[1]);
+        measure_add(B, byte_of(rw, 3 * k + 2), sse[2], worst[2]);
+    }
+}
+
+// merge_tile_pixel's pixel against the three bytes at ref
+__device__ __forceinline__ void measure_tile_pixel(const MeasureTiles420Args &p, const uint8_t *y_tile, const uint8_t *c_tile, int tx, int ty, const uint8_t *ref,
+                                                   uint32_t (&sse)[3], uint32_t (&worst)[3]) {
+    const int ch = (int)p.ch, cw = (int)p.cw;
+    const int i = tx >> 1, i2 = (tx & 1) ? min(i + 1, cw - 1) : max(i - 1, 0);
+    const int j = ty >> 1, j2 = (ty & 1) ? min(j + 1, ch - 1) : max(j - 1, 0);
+    int up[2];
+#pragma unroll
+    for (int c = 0; c < 2; c++) {
+        const uint8_t *a = c_tile + (uint64_t)c * ch * cw + (uint64_t)j * cw, *b = c_tile + (uint64_t)c * ch * cw + (uint64_t)j2 * cw;
+        up[c] = (9 * a[i] + 3 * a[i2] + 3 * b[i] + b[i2] + 8) >> 4;
+    }
+    int R, G, B;
+    ycc_to_rgb(y_tile[(uint64_t)ty * p.tile_w + tx], up[0], up[1], R, G, B);
+    measure_add(R, ref[0], sse[0], worst[0]);
+    measure_add(G, ref[1], sse[1], worst[1]);
+    measure_add(B, ref[2], sse[2], worst[2]);
+}
+
+// item g = strip g % n_strips of image row g / n_strips. The sums leave a workgroup as seven 64-bit atomics on the same seven words, which take some 8 ns each there,
+// one after the other (K10's measure_tiles_kernel, k10_tiles.hip, has the figures): with one strip per lane a 4096^2 image's 4096 workgroups spend four times the
+// merge's time on them. A lane therefore walks up to kMeasure420Strips strips, a whole grid apart (so a wave's loads stay runs): 32 x 16 x 255^2 < 2^25 per lane and
+// < 2^31 per wave in 32 bits; the waves are added in 64. Integer sums only - a run gives the same seven numbers every time.
+constexpr uint32_t kMeasure420Strips = 32, kMeasure420Groups = 512; // strips per lane at most; the grid up to which a lane keeps to one strip
+__global__ void __launch_bounds__(kT420Threads) measure_tiles420_kernel(const MeasureTiles420Args p) {
+    uint32_t sse[3] = {0, 0, 0}, worst[3] = {0, 0, 0};
+    uint32_t count = 0;
+    for (uint32_t it = 0; it < p.per_lane; it++) {
+        const uint64_t g64 = ((uint64_t)it * gridDim.x + blockIdx.x) * kT420Threads + threadIdx.x; // the lane of workgroup b walks strips (it gridDim.x + b) 256 + thread
+        if (g64 >= p.n_items) break;
+        const uint32_t g = (uint32_t)g64;
+        const uint32_t gy = g / p.n_strips, gx = (g - gy * p.n_strips) * kT420Strip;
+        const uint32_t n = min((uint32_t)kT420Strip, p.w - gx);
+        const uint32_t b = gy / p.tile_h, ty = gy - b * p.tile_h; // row ty of the tiles of grid row b
+        const uint32_t a = gx / p.tile_w;
+        uint32_t tx = gx - a * p.tile_w;                          // column tx of tile (b, a)
+        const uint64_t y_stride = (uint64_t)p.tile_h * p.tile_w, c_stride = 2ull * p.ch * p.cw;
+        const uint64_t s = (uint64_t)b * p.nx + a;
+        const uint8_t *y_tile = p.y + s * y_stride, *c_tile = p.c + s * c_stride;
+        const uint8_t *ref = p.ref + ((uint64_t)gy * p.w + gx) * 3;
+        if (n == (uint32_t)kT420Strip && tx + kT420Strip <= p.tile_w) {
+            if (tx & 1) measure_tile_strip<1>(p, y_tile, c_tile, (int)tx, (int)ty, ref, sse, worst);
+            else measure_tile_strip<0>(p, y_tile, c_tile, (int)tx, (int)ty, ref, sse, worst);
+        } else { // the strip crosses a tile column, or is the row's last
+            for (uint32_t k = 0; k < n; k++) {
+                measure_tile_pixel(p, y_tile, c_tile, (int)tx, (int)ty, ref + 3 * k, sse, worst);
+                if (++tx == p.tile_w) tx = 0, y_tile += y_stride, c_tile += c_stride; // the same row of the next tile
+            }
+        }
+        count += n;
+    }
+    __shared__ uint32_t s_part[kT420Threads / 64][7];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            sse[c] += __shfl_xor(sse[c], o);
+            worst[c] = max(worst[c], (uint32_t)__shfl_xor(worst[c], o));
+        }
+        count += __shfl_xor(count, o);
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int c = 0; c < 3; c++) s_part[wave][2 * c] = sse[c], s_part[wave][2 * c + 1] = worst[c];
+        s_part[wave][6] = count;
+    }
+    __syncthreads();
+    if (threadIdx.x < 7) {
+        const bool is_max = threadIdx.x < 6 && (threadIdx.x & 1);
+        unsigned long long v = 0;
+#pragma unroll
+        for (int w = 0; w < kT420Threads / 64; w++) v = is_max ? max(v, (unsigned long long)s_part[w][threadIdx.x]) : v + s_part[w][threadIdx.x];
+        if (v) {
+            if (is_max) atomicMax(p.out + threadIdx.x, v);
+            else atomicAdd(p.out + threadIdx.x, v);
+        }
+    }
+}
+
+// the limits all launchers share: sizes that keep every u32 product above in range; false for a shape outside them
 bool shape_ok(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint64_t &nx, uint64_t &ny) {
     if (!width || !height || !tile_w || !tile_h || width > 0x3FFFFFFFu || height > 0x3FFFFFFFu || tile_w > 0x3FFFFFFFu || tile_h > 0x3FFFFFFFu) return false;
     nx = ((uint64_t)width + tile_w - 1) / tile_w, ny = ((uint64_t)height + tile_h - 1) / tile_h;
@@ -277,6 +409,26 @@ hipError_t launch_merge_tiles420_region(const uint8_t *y_tiles, const uint8_t *c
     p.n_items = (uint32_t)items;
     const uint32_t groups = (uint32_t)((items + kT420Threads - 1) / kT420Threads);
     hipLaunchKernelGGL(merge_tiles420_region_kernel, dim3(groups), dim3(kT420Threads), 0, stream, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_measure_tiles420(const uint8_t *y_tiles, const uint8_t *c_tiles, uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, const uint8_t *reference,
+                                   unsigned long long *sums, hipStream_t stream) {
+    uint64_t nx = 0, ny = 0;
+    if (!reference || !sums || !y_tiles || !c_tiles || !shape_ok(width, height, tile_w, tile_h, nx, ny)) return hipErrorInvalidValue;
+    MeasureTiles420Args p{};
+    p.y = y_tiles, p.c = c_tiles, p.ref = reference, p.out = sums;
+    p.tile_w = tile_w, p.tile_h = tile_h, p.cw = (tile_w + 1) / 2, p.ch = (tile_h + 1) / 2, p.nx = (uint32_t)nx;
+    p.w = width;
+    p.n_strips = (width + kT420Strip - 1) / kT420Strip;
+    const uint64_t items = (uint64_t)height * p.n_strips;
+    if (items > 0xFFFFFFFFull - kT420Threads) return hipErrorInvalidValue; // (one u32 item index per lane)
+    p.n_items = (uint32_t)items;
+    uint32_t groups = (uint32_t)((items + kT420Threads - 1) / kT420Threads);
+    // one strip per lane up to kMeasure420Groups workgroups, then more strips per lane, and past kMeasure420Strips of them more workgroups again
+    p.per_lane = std::min(kMeasure420Strips, (groups + kMeasure420Groups - 1) / kMeasure420Groups);
+    groups = (groups + p.per_lane - 1) / p.per_lane;
+    hipLaunchKernelGGL(measure_tiles420_kernel, dim3(groups), dim3(kT420Threads), 0, stream, p);
     return hipGetLastError();
 }
 

@@ -25,7 +25,7 @@ struct RateArgs {
     const float *laplace;            // [10][1024] exp(-|x| / w) / (2 w), built on the host with libm's expf (fri_hip.cpp)
     unsigned long long *total;       // [n_images] zeroed: 2^-16 bit units, bit 63 = uncodable
     uint32_t *models;                // [n_planes][10][4] or NULL: {max_freq_bits, n_off, collapsed slots, status}
-    uint32_t channels;
+    uint32_t channels;               // PLANE_ORDER: the number of tiles instead (a tile has three channels)
     uint32_t header_bits, channel_bits, context_bits; // container bytes x 8 (fri_hip.h)
 };
 
@@ -47,9 +47,20 @@ __device__ long long block_sum_i64(long long v, long long *scratch) {
 // EMPTY_OK: the emitter's FRI_EMIT_EMPTY_OK, which codes the tiles of a `frit` file - a context whose counts sum to zero takes max_freq_bits = 0 before the floor,
 // its model is rebuilt like any other (models[0] is the max_freq_bits the file carries), it costs its container bytes and 16 bits (the flush of a rANS state that
 // never moved is 8 bytes, the channel's constant counts 6 per state) and its status 1 no longer marks the image uncodable. <false> is the kernel as it always was.
-template <bool EMPTY_OK>
+// PLANE_ORDER: the planes of n_tiles three-channel tiles in the plane order of tiled 4:2:0 - the n_tiles luma planes, then Cb and Cr of tile 0, of tile 1, ...
+template <bool EMPTY_OK, bool PLANE_ORDER = false>
 __global__ void __launch_bounds__(kRateThreads) rate_kernel(const RateArgs a) {
-    const uint32_t b = blockIdx.x, plane = blockIdx.y, image = plane / a.channels, ch = plane % a.channels;
+    const uint32_t b = blockIdx.x, plane = PLANE_ORDER ? blockIdx.z * gridDim.y + blockIdx.y : blockIdx.y; // (a grid's y has 16 bits, 3 n_tiles may need 17)
+    uint32_t image, ch;
+    if (PLANE_ORDER) {
+        const uint32_t n_tiles = a.channels;
+        if (plane >= 3 * n_tiles) return; // (the last slice of the grid)
+        const bool luma = plane < n_tiles;
+        image = luma ? plane : (plane - n_tiles) >> 1;
+        ch = luma ? 0u : 1u + ((plane - n_tiles) & 1u);
+    } else {
+        image = plane / a.channels, ch = plane % a.channels;
+    }
     const int t = threadIdx.x;
     __shared__ AnsModelLds s_model;
     __shared__ long long s_i64[kRateWaves];
@@ -128,6 +139,9 @@ __global__ void __launch_bounds__(kRateThreads) rate_file_kernel(const unsigned 
 
 } // namespace
 
+// (The plane-order instance lives in a module of its own, k6_rate_planes.hip, which compiles this file's kernels again: a third caller of the shared reductions
+// in this module would change how the two instances below are compiled.)
+#ifndef FRI_K6_PLANE_ORDER_INSTANCE
 hipError_t launch_rate_estimate(uint32_t n_images, uint32_t channels, const uint32_t *hist, const unsigned long long *oob, const float *laplace,
                                 unsigned long long *bytes, uint32_t *models, const RateLayout &layout, hipStream_t stream) {
     if (hipError_t e = hipMemsetAsync(bytes, 0, (size_t)n_images * sizeof(unsigned long long), stream)) return e;
@@ -150,5 +164,20 @@ hipError_t launch_rate_estimate_tiled(uint32_t n_tiles, uint32_t channels, const
     hipLaunchKernelGGL(rate_file_kernel, dim3(1), dim3(kRateThreads), 0, stream, tile_bytes, n_tiles, file_bytes);
     return hipGetLastError();
 }
+
+#else // FRI_K6_PLANE_ORDER_INSTANCE
+hipError_t launch_rate_estimate_tiled420(uint32_t n_tiles, const uint32_t *hist, const unsigned long long *oob, const float *laplace, unsigned long long *tile_bytes,
+                                         unsigned long long *file_bytes, uint32_t *models, const RateLayout &layout, hipStream_t stream) {
+    if (hipError_t e = hipMemsetAsync(tile_bytes, 0, (size_t)n_tiles * sizeof(unsigned long long), stream)) return e;
+    RateArgs a;
+    a.hist = hist, a.oob = oob, a.laplace = laplace, a.total = tile_bytes, a.models = models, a.channels = n_tiles;
+    a.header_bits = 8u * layout.header_bytes, a.channel_bits = 8u * layout.channel_bytes, a.context_bits = 8u * layout.context_bytes;
+    const uint32_t planes = 3 * n_tiles, rows = std::min(planes, 32768u);
+    hipLaunchKernelGGL((rate_kernel<true, true>), dim3(10, rows, (planes + rows - 1) / rows), dim3(kRateThreads), 0, stream, a);
+    hipLaunchKernelGGL(rate_bytes_kernel, dim3((n_tiles + 63) / 64), dim3(64), 0, stream, tile_bytes, n_tiles);
+    hipLaunchKernelGGL(rate_file_kernel, dim3(1), dim3(kRateThreads), 0, stream, tile_bytes, n_tiles, file_bytes);
+    return hipGetLastError();
+}
+#endif // FRI_K6_PLANE_ORDER_INSTANCE
 
 } // namespace fri

@@ -162,6 +162,12 @@ hipError_t launch_rate_estimate(uint32_t n_images, uint32_t channels, const uint
 hipError_t launch_rate_estimate_tiled(uint32_t n_tiles, uint32_t channels, const uint32_t *hist, const unsigned long long *oob, const float *laplace,
                                       unsigned long long *tile_bytes, unsigned long long *file_bytes, uint32_t *models, const RateLayout &layout, hipStream_t stream);
 
+// The same for the tiles of a tiled 4:2:0 `frit` file, whose arrays are in plane order (include/fri_hip.h, "Tiled 4:2:0 coding"): hist [3 n_tiles][10][1024], oob
+// [3 n_tiles] or NULL, models [3 n_tiles][10][4] or NULL; plane p < n_tiles is channel 0 of tile p, any other channel 1 + ((p - n_tiles) & 1) of tile
+// (p - n_tiles) >> 1. A tile is a three-channel payload: the formula per tile is unchanged.
+hipError_t launch_rate_estimate_tiled420(uint32_t n_tiles, const uint32_t *hist, const unsigned long long *oob, const float *laplace, unsigned long long *tile_bytes,
+                                         unsigned long long *file_bytes, uint32_t *models, const RateLayout &layout, hipStream_t stream);
+
 // K7 (k7_ssim.hip): the SSIM sums of n_images raster pairs of width x height x channels (interleaved u8; image k at a / b + k * pixel_stride bytes):
 // out[k][c] += the sum of the window values of channel c, out[k][channels] += the number of windows (include/fri_hip.h, fri_hip_measure_ssim_dev).
 // The caller zeroes out. width, height >= 8, channels 1 or 3.
@@ -215,6 +221,12 @@ hipError_t launch_rans_encode(uint32_t n_planes, const uint16_t *symbols, size_t
 hipError_t launch_split_tiles420(const uint8_t *rgb, uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint8_t *y_tiles, uint8_t *c_tiles, hipStream_t stream);
 hipError_t launch_merge_tiles420_region(const uint8_t *y_tiles, const uint8_t *c_tiles, uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t x, uint32_t y,
                                         uint32_t w, uint32_t h, uint8_t *region, hipStream_t stream);
+
+// Measure: the whole-image merge's walk with nothing stored - every image pixel, upsampled within its own tile, against `reference` [H][W][3]: sums[2 c] += the sum
+// of squared differences of channel c (R, G, B), sums[2 c + 1] = max(.., largest absolute difference), sums[6] += pixels (W H in all; no replicated sample is
+// counted). The caller zeroes sums with launch_clear_sums. Both inputs are only read.
+hipError_t launch_measure_tiles420(const uint8_t *y_tiles, const uint8_t *c_tiles, uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, const uint8_t *reference,
+                                   unsigned long long *sums, hipStream_t stream);
 
 // K2's per-node neighbour offsets (LDS halfword offsets relative to the own slot, two per word) from the static neighbour table
 void build_lf_deltas(const uint16_t *nbr_table, int8_t *out /* [8] */);

@@ -49,6 +49,7 @@ def load_library():
         L.fri_tiled_encode_from_streams.argtypes = [u32, u32, u32, u32, u32, vp, C.c_uint64, vp, vp, vp, u32, vp, sz, vp, C.c_char_p, sz]
         L.fri_tiled_encode_from_streams420.argtypes = [u32, u32, u32, u32, u32, vp, C.c_uint64, C.c_uint64, vp, vp, vp, u32, vp, sz, vp, C.c_char_p, sz]
         L.fri_tiled_encode_from_coded.argtypes = [u32, u32, u32, u32, u32, vp, C.c_uint64, vp, vp, vp, vp, vp, u32, vp, sz, vp, C.c_char_p, sz]
+        L.fri_tiled_encode_from_coded420.argtypes = [u32, u32, u32, u32, u32, vp, C.c_uint64, vp, vp, vp, vp, vp, u32, vp, sz, vp, C.c_char_p, sz]
         L.fri_coded_encode_image.argtypes = [u32, u32, u32, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, sz, vp, C.c_char_p, sz]
         L.fri_tiled_info.argtypes = [vp, sz, vp]
         L.fri_tiled_decode.argtypes = [vp, sz, u32, vp, vp, sz, C.c_char_p, sz]
@@ -341,6 +342,27 @@ def tiled_encode_from_coded(width, height, tile_w, tile_h, words, n_words, model
                                                     threads, _p(out), out.size, C.addressof(n), err, 256)
     if rc != 0:
         raise EmitError(err.value.decode() or f"fri_tiled_encode_from_coded: {rc}")
+    return out[: n.value].tobytes()
+
+
+def tiled_encode_from_coded420(width, height, tile_w, tile_h, words, n_words, models, off_values, value_params, width_params, quality, threads=0):
+    """fri_tiled_encode_from_coded420: the `frit` bytes of a tiled 4:2:0 file from what PlanTiled420.encode_image_tiled420_coded returns, all in plane order -
+    words uint32 [3 n][word_stride], n_words [3 n], models [3 n][10][4], off_values uint16 [3 n][10][1024], params [3 n][3][6]; quality 1..99. Nothing is coded
+    here; the file is tiled_encode_from_streams420's, byte for byte, and does not depend on `threads`."""
+    w, stride, nw, m, off, vp, wp, planes = _coded(words, n_words, models, off_values, value_params, width_params)
+    n_tiles = -(-width // tile_w) * -(-height // tile_h)
+    assert planes == 3 * n_tiles
+    n = C.c_size_t(0)
+    err = C.create_string_buffer(256)
+    out = np.empty(int(nw.sum()) * 4 + planes * (10 * 2070 + 256) + n_tiles * 72 + 64, np.uint8)
+    args = (width, height, tile_w, tile_h, _arg(3, False, quality, True, True), _p(w), stride, _p(nw), _p(m), _p(off), _p(vp), _p(wp), threads)
+    L = load_library()
+    rc = L.fri_tiled_encode_from_coded420(*args, _p(out), out.size, C.addressof(n), err, 256)
+    if rc == -3:
+        out = np.empty(n.value, np.uint8)
+        rc = L.fri_tiled_encode_from_coded420(*args, _p(out), out.size, C.addressof(n), err, 256)
+    if rc != 0:
+        raise EmitError(err.value.decode() or f"fri_tiled_encode_from_coded420: {rc}")
     return out[: n.value].tobytes()
 
 

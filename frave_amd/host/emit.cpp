@@ -1173,6 +1173,34 @@ std::string encode_tiled_from_coded(uint32_t width, uint32_t height, uint32_t ti
     return "";
 }
 
+std::string encode_tiled_from_coded420(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t quality, const uint32_t *words, size_t word_stride,
+                                       const uint32_t *n_words, const uint32_t *models, const uint16_t *off_values, const float *value_params, const float *width_params,
+                                       unsigned threads, std::vector<uint8_t> &out) {
+    if (!width || !height || !tile_w || !tile_h || quality < 1 || quality > 99) return "invalid argument";
+    const uint64_t nx = ((uint64_t)width + tile_w - 1) / tile_w, ny = ((uint64_t)height + tile_h - 1) / tile_h;
+    if (nx * ny > 0xFFFFFFFFull) return "invalid argument";
+    const size_t n = (size_t)(nx * ny);
+    std::vector<std::vector<uint8_t>> payload(n);
+    const std::string e = for_each_tile(n, threads, [&](size_t t) -> std::string {
+        const size_t plane[3] = {t, n + 2 * t, n + 2 * t + 1}; // plane order: the luma planes, then Cb and Cr tile by tile
+        std::vector<ChannelStream> chans(3);
+        std::vector<ChannelParams> params(3);
+        for (uint32_t ch = 0; ch < 3; ch++) {
+            const size_t k = plane[ch];
+            if (n_words[k] > word_stride) return "channel " + std::to_string(ch) + ": coded plane: more words than the stride holds";
+            const std::string ce = channel_from_coded(words + k * word_stride, n_words[k], models + k * kContexts * 4, off_values + k * kContexts * kAlphabet, chans[ch]);
+            if (!ce.empty()) return "channel " + std::to_string(ch) + ": " + ce;
+            std::memcpy(params[ch].value, value_params + k * 18, sizeof(params[ch].value));
+            std::memcpy(params[ch].width, width_params + k * 18, sizeof(params[ch].width));
+        }
+        payload[t] = serialize(tile_h, tile_w, kYCbCr, chans, params, false, quality, true, true);
+        return "";
+    });
+    if (!e.empty()) return e;
+    assemble_tiled(width, height, tile_w, tile_h, nx, ny, payload, out);
+    return "";
+}
+
 std::string parse_tiled(const uint8_t *b, size_t len, TiledInfo &info, std::vector<uint64_t> &offset) {
     if (len < kTiledHeader + 16 || std::memcmp(b, "frit", 4) != 0 || get_u32(b + 4) != 1) return kMalformedTiled;
     info.height = get_u32(b + 8), info.width = get_u32(b + 12), info.tile_h = get_u32(b + 16), info.tile_w = get_u32(b + 20), info.ny = get_u32(b + 24), info.nx = get_u32(b + 28);

@@ -223,6 +223,11 @@ std::string encode_tiled_from_streams420(uint32_t width, uint32_t height, uint32
 std::string encode_tiled_from_coded(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t channels, bool rct, uint32_t quality, bool ycbcr,
                                     const uint32_t *words, size_t word_stride, const uint32_t *n_words, const uint32_t *models, const uint16_t *off_values,
                                     const float *value_params, const float *width_params, unsigned threads, std::vector<uint8_t> &out);
+// A tiled 4:2:0 file from coded planes in plane order (fri_hip_encode_image_tiled420_coded): words [3 n][word_stride], n_words [3 n], models [3 n][10][4], off_values
+// [3 n][10][1024], value_params / width_params [3 n][3][6]. Byte for byte encode_tiled_from_streams420's file when the planes are what the host coder makes of the streams.
+std::string encode_tiled_from_coded420(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t quality, const uint32_t *words, size_t word_stride,
+                                       const uint32_t *n_words, const uint32_t *models, const uint16_t *off_values, const float *value_params, const float *width_params,
+                                       unsigned threads, std::vector<uint8_t> &out);
 // ... and one ordinary image (`frif`) of 1 or 3 channels from its coded planes [channels]
 std::string encode_image_from_coded(uint32_t width, uint32_t height, uint32_t channels, bool rct, uint32_t quality, bool ycbcr, const uint32_t *words, size_t word_stride,
                                     const uint32_t *n_words, const uint32_t *models, const uint16_t *off_values, const float *value_params, const float *width_params,

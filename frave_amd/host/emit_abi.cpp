@@ -285,6 +285,26 @@ int fri_tiled_encode_from_coded(uint32_t width, uint32_t height, uint32_t tile_w
     return 0;
 }
 
+int fri_tiled_encode_from_coded420(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t channels_arg, const uint32_t *words, uint64_t word_stride,
+                                   const uint32_t *n_words, const uint32_t *models, const uint16_t *off_values, const float *value_params, const float *width_params,
+                                   uint32_t threads, uint8_t *out, size_t cap, size_t *len, char *err, size_t err_cap) {
+    uint32_t channels, quality;
+    bool rct, ycbcr, s420 = false, empty_ok = false;
+    // 3 | FRI_EMIT_YCBCR | FRI_EMIT_420 | FRI_EMIT_QUALITY(1..99) and nothing else (no place for alpha; FRI_EMIT_EMPTY_OK is always on and may be passed)
+    if (!words || !n_words || !models || !off_values || !value_params || !width_params || !len ||
+        !split_channels(channels_arg, channels, rct, quality, ycbcr, &s420, nullptr, &empty_ok) || !s420)
+        return fail(err, err_cap, "invalid argument");
+    std::vector<uint8_t> bytes;
+    const std::string e = encode_tiled_from_coded420(width, height, tile_w, tile_h, quality, words, (size_t)word_stride, n_words, models, off_values, value_params, width_params,
+                                                     threads, bytes);
+    if (e == "invalid argument") return fail(err, err_cap, e);
+    if (!e.empty()) return fail(err, err_cap, e, -2);
+    *len = bytes.size();
+    if (!out || cap < bytes.size()) return -3;
+    std::memcpy(out, bytes.data(), bytes.size());
+    return 0;
+}
+
 int fri_coded_encode_image(uint32_t width, uint32_t height, uint32_t channels_arg, const uint32_t *words, uint64_t word_stride, const uint32_t *n_words, const uint32_t *models,
                            const uint16_t *off_values, const float *value_params, const float *width_params, uint8_t *out, size_t cap, size_t *len, char *err, size_t err_cap) {
     uint32_t channels, quality;

@@ -22,9 +22,9 @@
 //                                                            --tile-size T (any mode flag but --420; no alpha): the image as a batch of independently coded tiles
 //                                                            of about T x T (fri_hip_tile_shape), a `frit` file; --psnr / --ssim / --size search on the tiled plan
 //                                                            (fri_hip_search_quality*_tiled): the target holds for the file that is written
-//                                                            --tile-size-420 T --quality Q: the tiles are 4:2:0 images (fri_hip_tile_shape420, K12); no targets.
+//                                                            --tile-size-420 T (--quality Q | --target psnr=DB|ssim=S|size=BYTES|bpp=B) [--device-rans]: the tiles are 4:2:0 images (K12).
 //                                                            --tile-size T --420 stays refused: tiled 4:2:0 has this option of its own
-//                                                            --device-rans (with --tile-size): the rANS coder runs on the device too (K11), the host writes the
+//                                                            --device-rans (with --tile-size or --tile-size-420): the rANS coder runs on the device too (K11), the host writes the
 //                                                            container around the coded planes - the same file
 //   fri_driver decode-file <in.frv> <out.pgm|.ppm|.bmp|.pam> [--region X,Y,W,H]  (.pam for a file with an alpha plane, and for no other) container -> rANS / context decoding on the host -> dequantisation + inverse
 //                                                            transform on the device (fri-cli decode, crates/fri-cli/src/commands/decode.rs); a flagged file
@@ -523,12 +523,12 @@ static int encode_image_tiled_to_file(const std::vector<uint8_t> &img, uint32_t 
     return 0;
 }
 
-// encode-file --tile-size-420 T --quality Q: the image as a batch of independently coded 4:2:0 tiles (libfri::encode_bytes_tiled420; a `frit` file whose tiles are
+// encode-file --tile-size-420 T (--quality Q | --target ...) [--device-rans]: the image as a batch of independently coded 4:2:0 tiles (libfri::encode_bytes_tiled420; a `frit` file whose tiles are
 // 4:2:0 images). Self-check: the file decodes (FRIDecoder) to the direct device round trip (libfri::round_trip_tiled420: K12's split, the forward kernel plane by
 // plane, fri_hip_decode_image_tiled420).
 static int encode_image_tiled420_to_file(const std::vector<uint8_t> &img, uint32_t w, uint32_t h, const libfri::EncoderOpts &opts, uint32_t tile_size, const char *out_path) {
     auto t0 = std::chrono::steady_clock::now();
-    auto enc = libfri::encode_bytes_tiled420(img, h, w, opts.quality, tile_size, opts.device);
+    auto enc = libfri::encode_bytes_tiled420(img, h, w, opts, tile_size);
     const double t_enc = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (!enc.ok) {
         std::fprintf(stderr, "%s\n", enc.error.c_str());
@@ -554,6 +554,12 @@ static int encode_image_tiled420_to_file(const std::vector<uint8_t> &img, uint32
     }
     std::printf("%ux%ux3 in %u x %u 4:2:0 tiles of %ux%u: %zu bytes, %.3f bits per pixel; device chain and emit %.3f s; self-check: decodes to the direct tiled 4:2:0 round trip\n", w, h,
                 enc.value.nx, enc.value.ny, enc.value.tile_w, enc.value.tile_h, bytes.size(), 8.0 * bytes.size() / ((double)w * h), t_enc);
+    if (opts.device_rans) std::printf("rANS coder on the device (K11): the host wrote the container around the coded planes\n");
+    if (opts.target_psnr > 0) std::printf("target %.2f dB: search returned quality %d (%.2f dB on the tiled 4:2:0 round trip)\n", opts.target_psnr, enc.value.search_quality, enc.value.psnr_db);
+    if (opts.target_ssim > 0) std::printf("target SSIM %.4f: search returned quality %d (SSIM %.6f on the tiled 4:2:0 round trip)\n", opts.target_ssim, enc.value.search_quality, enc.value.ssim);
+    if (opts.target_bytes)
+        std::printf("target %llu bytes: search returned quality %d (estimate %llu bytes%s)\n", (unsigned long long)opts.target_bytes, enc.value.search_quality,
+                    (unsigned long long)enc.value.est_bytes, enc.value.quality != enc.value.search_quality ? "; the file was over, coded at a lower quality" : "");
     double sse = 0;
     for (size_t i = 0; i < img.size(); i++) sse += ((double)back.value.data[i] - img[i]) * ((double)back.value.data[i] - img[i]);
     std::printf("quality %d in YCbCr 4:2:0: PSNR %.2f dB\n", enc.value.quality, sse > 0 ? 10.0 * std::log10(255.0 * 255.0 * (double)img.size() / sse) : HUGE_VAL);
@@ -574,6 +580,8 @@ int main(int argc, char **argv) {
         double bpp = 0;
         bool has_size = false, has_bpp = false, has_ssim = false, sub420 = false, clean_alpha = false, tiled = false, tiled420 = false;
         long tile_size = 0, tile_size420 = 0;
+        std::string target; // --target KIND=VALUE: the targets of --tile-size-420
+        bool has_target = false;
         for (int i = 4; i < argc; i++) {
             const std::string a = argv[i];
             if (a == "--rct") file_opts.colour_transform = true;
@@ -588,6 +596,7 @@ int main(int argc, char **argv) {
             else if (a == "--tile-size" && i + 1 < argc) tile_size = std::atol(argv[++i]), tiled = true;
             else if (a == "--tile-size-420" && i + 1 < argc) tile_size420 = std::atol(argv[++i]), tiled420 = true;
             else if (a == "--device-rans") file_opts.device_rans = true;
+            else if (a == "--target" && i + 1 < argc) target = argv[++i], has_target = true;
             else {
                 std::fprintf(stderr, "encode-file: unknown option %s\n", a.c_str());
                 return 2;
@@ -599,15 +608,32 @@ int main(int argc, char **argv) {
             return 2;
         }
         const bool sized = has_size || has_bpp;
+        if (has_target && !tiled420) {
+            std::fprintf(stderr, "encode-file: --target psnr=DB | ssim=S | size=BYTES | bpp=B is the target of --tile-size-420 T; the other modes take --psnr, --ssim, --size and --bpp\n");
+            return 2;
+        }
         if (tiled420) { // tiled 4:2:0 has an option of its own: --tile-size T --420 stays refused (below)
             if (file_opts.target_psnr > 0 || has_ssim || sized) {
-                std::fprintf(stderr, "encode-file: --tile-size-420 takes --quality Q only: --psnr, --ssim, --size and --bpp are refused (the searches and the size estimate on tiled 4:2:0 are out of scope)\n");
+                std::fprintf(stderr, "encode-file: --tile-size-420 takes --quality Q or --target psnr=DB | ssim=S | size=BYTES | bpp=B: --psnr, --ssim, --size and --bpp are refused with it\n");
                 return 2;
             }
-            if (tile_size420 < 1 || tile_size420 > 65535 || rgba || fc != 3 || tiled || sub420 || file_opts.ycbcr || file_opts.colour_transform || file_opts.device_rans || clean_alpha ||
-                file_opts.quality < 1) {
-                std::fprintf(stderr, "encode-file: --tile-size-420 T (1..65535) takes an RGB image (PPM or BMP) and --quality Q (1..99), and no other mode flag\n");
+            if (tile_size420 < 1 || tile_size420 > 65535 || rgba || fc != 3 || tiled || sub420 || file_opts.ycbcr || file_opts.colour_transform || clean_alpha ||
+                (has_target ? file_opts.quality != 0 : file_opts.quality < 1)) {
+                std::fprintf(stderr, "encode-file: --tile-size-420 T (1..65535) takes an RGB image (PPM or BMP) and --quality Q (1..99) or --target, not both, --device-rans, and no other mode flag\n");
                 return 2;
+            }
+            if (has_target) {
+                const size_t eq = target.find('=');
+                const std::string kind = target.substr(0, eq), value = eq == std::string::npos ? "" : target.substr(eq + 1);
+                const double v = std::atof(value.c_str());
+                if (kind == "psnr" && v > 0) file_opts.target_psnr = v;
+                else if (kind == "ssim" && v > 0 && v <= 1) file_opts.target_ssim = v;
+                else if (kind == "size") file_opts.target_bytes = std::strtoull(value.c_str(), nullptr, 10);
+                else if (kind == "bpp" && v > 0) file_opts.target_bytes = (uint64_t)std::floor(v * fw * fh / 8.0);
+                if (!(file_opts.target_psnr > 0) && !(file_opts.target_ssim > 0) && !file_opts.target_bytes) {
+                    std::fprintf(stderr, "encode-file: --target takes psnr=DB (> 0), ssim=S (0 < S <= 1), size=BYTES (> 0) or bpp=B (> 0)\n");
+                    return 2;
+                }
             }
             return encode_image_tiled420_to_file(img, fw, fh, file_opts, (uint32_t)tile_size420, argv[3]);
         }
@@ -638,7 +664,7 @@ int main(int argc, char **argv) {
             return 2;
         }
         if (file_opts.device_rans && !tiled) {
-            std::fprintf(stderr, "encode-file: --device-rans codes the tiles of --tile-size T on the device (ordinary, 4:2:0 and RGBA files are coded on the host)\n");
+            std::fprintf(stderr, "encode-file: --device-rans codes the tiles of --tile-size T or --tile-size-420 T on the device (ordinary, 4:2:0 and RGBA files are coded on the host)\n");
             return 2;
         }
         if (tiled) return encode_image_tiled_to_file(img, fw, fh, fc, file_opts, (uint32_t)tile_size, argv[3]);
@@ -708,7 +734,7 @@ int main(int argc, char **argv) {
         return 0;
     }
     if (argc < 5) {
-        std::fprintf(stderr, "usage: %s roundtrip|encode|batch|batch-frv <width> <height> <channels> [n_images | out.frv]\n       %s encode-file <in.pgm|in.ppm|in.bmp|in.pam> <out.frv> [--rct | [--ycbcr | --420] (--quality Q | --psnr DB | --ssim S | --size BYTES | --bpp B)] [--clean-alpha] [--tile-size T [--device-rans]]\n       %s encode-file <in.ppm|in.bmp> <out.frv> --tile-size-420 T --quality Q   (tiled 4:2:0; --tile-size T --420 stays refused: the option of its own is this one)\n       %s decode-file <in.frv> <out.pgm|out.ppm|out.bmp|out.pam> [--region X,Y,W,H]\n", argv[0], argv[0], argv[0], argv[0]);
+        std::fprintf(stderr, "usage: %s roundtrip|encode|batch|batch-frv <width> <height> <channels> [n_images | out.frv]\n       %s encode-file <in.pgm|in.ppm|in.bmp|in.pam> <out.frv> [--rct | [--ycbcr | --420] (--quality Q | --psnr DB | --ssim S | --size BYTES | --bpp B)] [--clean-alpha] [--tile-size T [--device-rans]]\n       %s encode-file <in.ppm|in.bmp> <out.frv> --tile-size-420 T (--quality Q | --target psnr=DB|ssim=S|size=BYTES|bpp=B) [--device-rans]   (tiled 4:2:0; --tile-size T --420 stays refused: the option of its own is this one)\n       %s decode-file <in.frv> <out.pgm|out.ppm|out.bmp|out.pam> [--region X,Y,W,H]\n", argv[0], argv[0], argv[0], argv[0]);
         return 2;
     }
     const std::string cmd = argv[1];

@@ -1247,17 +1247,25 @@ Result<RasterImage> round_trip_tiled(const std::vector<uint8_t> &pixels, uint32_
 
 // ---- tiled 4:2:0 coding ----------------------------------------------------------------------------------------------------------------------------
 Result<EncodedTiled> encode_bytes_tiled420(const std::vector<uint8_t> &rgb, uint32_t height, uint32_t width, int quality, uint32_t tile_size, int device, unsigned threads) {
+    EncoderOpts opts;
+    opts.quality = quality, opts.device = device;
+    return encode_bytes_tiled420(rgb, height, width, opts, tile_size, threads);
+}
+
+Result<EncodedTiled> encode_bytes_tiled420(const std::vector<uint8_t> &rgb, uint32_t height, uint32_t width, const EncoderOpts &opts, uint32_t tile_size, unsigned threads) {
     Result<EncodedTiled> r;
     auto fail = [&](const std::string &why) {
         r.error = "Failed to decode: " + why; // sic, encoder.rs:106
         return r;
     };
-    if (quality < 1 || quality > 99) return fail("tiled 4:2:0 coding needs a quality of 1..99");
+    const int n_targets = (opts.target_psnr > 0) + (opts.target_ssim > 0) + (opts.target_bytes != 0);
+    if (n_targets > 1 || (n_targets && opts.quality)) return fail("tiled 4:2:0 coding takes a quality or one target");
+    if (!n_targets && (opts.quality < 1 || opts.quality > 99)) return fail("tiled 4:2:0 coding needs a quality of 1..99");
     if (!width || !height || rgb.size() != (size_t)width * height * 3) return fail("tiled 4:2:0 coding takes width x height RGB pixels");
     uint32_t tw = 0, th = 0;
     if (const int rc = fri_hip_tile_shape420(width, height, tile_size, &tw, &th); rc != FRI_HIP_OK)
         return fail(std::string("no tile shape of that size owns every pixel in both lattices: ") + fri_hip_strerror(rc));
-    Device dev(device);
+    Device dev(opts.device);
     if (!dev.ok()) return fail(dev.error());
     fri_hip_plan_tiled420 *raw = nullptr;
     if (const int rc = fri_hip_plan_tiled420_create(dev.ctx(), width, height, tw, th, 0, &raw); rc != FRI_HIP_OK) return fail(dev.describe(rc));
@@ -1270,18 +1278,77 @@ Result<EncodedTiled> encode_bytes_tiled420(const std::vector<uint8_t> &rgb, uint
     r.value.tile_w = tw, r.value.tile_h = th, r.value.nx = grid[0], r.value.ny = grid[1];
     const size_t n = (size_t)grid[0] * grid[1], planes = 3 * n;
     const uint64_t n_y = fri_hip_plan_num_some(luma), n_c = fri_hip_plan_num_some(chroma);
-    std::vector<uint16_t> symbols(n * (size_t)(n_y + 2 * n_c));
-    std::vector<uint32_t> hist(planes * CONTEXT_AMOUNT * ALPHABET_SIZE);
+    std::vector<uint16_t> symbols(opts.device_rans ? 0 : n * (size_t)(n_y + 2 * n_c)); // (the device coder's route reads neither streams nor histograms back)
+    std::vector<uint32_t> hist(opts.device_rans ? 0 : planes * CONTEXT_AMOUNT * ALPHABET_SIZE);
     std::vector<float> vp(planes * 18), wp(planes * 18);
     std::vector<uint64_t> oob(planes, 0);
-    if (const int rc = fri_hip_encode_image_tiled420_symbols(raw, rgb.data(), quality, vp.data(), wp.data(), symbols.data(), hist.data(), oob.data()); rc != FRI_HIP_OK)
-        return fail(dev.describe(rc));
-    for (uint64_t v : oob)
-        if (v) return fail("symbol outside the 1024-entry alphabet"); // the reference panics: bump_freq, entropy_coding.rs:99
-    const std::string e = emit::encode_tiled_from_streams420(width, height, tw, th, (uint32_t)quality, symbols.data(), (size_t)n_y, (size_t)n_c, hist.data(), vp.data(), wp.data(), threads,
-                                                             r.value.bytes);
-    if (!e.empty()) return fail(e);
-    r.value.quality = quality, r.value.ycbcr = true;
+    // the device batches and the emitter at `quality`: "" or the error; the file in r.value.bytes
+    auto code = [&](int quality) -> std::string {
+        r.value.bytes.clear();
+        if (opts.device_rans) { // K11: the planes come back coded, the host writes the container around them
+            const size_t stride = (size_t)std::max(n_y, n_c) + 20; // a step emits at most one word
+            std::vector<uint32_t> words(planes * stride), n_words(planes), models(planes * CONTEXT_AMOUNT * 4), status(planes * 4);
+            std::vector<uint16_t> off(planes * CONTEXT_AMOUNT * ALPHABET_SIZE);
+            if (const int rc = fri_hip_encode_image_tiled420_coded(raw, rgb.data(), quality, vp.data(), wp.data(), words.data(), stride, n_words.data(), models.data(), off.data(),
+                                                                   status.data());
+                rc != FRI_HIP_OK) {
+                for (size_t k = 0; k < planes; k++)
+                    if (status[4 * k]) {
+                        const size_t tile = k < n ? k : (k - n) / 2, ch = k < n ? 0 : 1 + (k - n) % 2;
+                        return "tile " + std::to_string(tile) + ": channel " + std::to_string(ch) + ": the device coder refuses the plane (status " + std::to_string(status[4 * k]) + ")";
+                    }
+                return dev.describe(rc);
+            }
+            if (const std::string e = emit::encode_tiled_from_coded420(width, height, tw, th, (uint32_t)quality, words.data(), stride, n_words.data(), models.data(), off.data(),
+                                                                       vp.data(), wp.data(), threads, r.value.bytes);
+                !e.empty())
+                return e;
+        } else {
+            if (const int rc = fri_hip_encode_image_tiled420_symbols(raw, rgb.data(), quality, vp.data(), wp.data(), symbols.data(), hist.data(), oob.data()); rc != FRI_HIP_OK)
+                return dev.describe(rc);
+            for (uint64_t v : oob)
+                if (v) return "symbol outside the 1024-entry alphabet"; // the reference panics: bump_freq, entropy_coding.rs:99
+            if (const std::string e = emit::encode_tiled_from_streams420(width, height, tw, th, (uint32_t)quality, symbols.data(), (size_t)n_y, (size_t)n_c, hist.data(), vp.data(),
+                                                                         wp.data(), threads, r.value.bytes);
+                !e.empty())
+                return e;
+        }
+        r.value.quality = quality, r.value.ycbcr = true;
+        return std::string();
+    };
+    int quality = opts.quality;
+    if (opts.target_bytes) { // the highest quality whose estimated file fits
+        int32_t q = 0;
+        uint64_t est = 0;
+        const int rc = fri_hip_search_quality_for_size_tiled420(raw, rgb.data(), opts.target_bytes, &q, &est);
+        if (rc == FRI_HIP_ERR_OUT_OF_RANGE) return fail("no quality fits in " + std::to_string(opts.target_bytes) + " bytes (quality 1: about " + std::to_string(est) + ")");
+        if (rc != FRI_HIP_OK) return fail(dev.describe(rc));
+        r.value.search_quality = q;
+        // the estimate is a few bytes per channel and tile off the coder's output: code at q, emit, and go one quality lower while the file is over
+        constexpr int kMaxSteps = 8;
+        for (int step = 0; step <= kMaxSteps && q >= 1; step++, q--) {
+            if (const std::string e = code(q); !e.empty()) return fail(e);
+            if (r.value.bytes.size() <= opts.target_bytes) {
+                r.value.est_bytes = est;
+                r.ok = true;
+                return r;
+            }
+            est = 0; // (est_bytes is the estimate of the searched quality: a stepped-down result reports 0)
+        }
+        r.value.bytes.clear();
+        return fail("no file of at most " + std::to_string(opts.target_bytes) + " bytes within " + std::to_string(kMaxSteps) + " qualities below the estimate's");
+    }
+    if (n_targets) { // the lowest quality that reaches the target; 100: none does, and a 4:2:0 file has no lossless form to fall back to
+        int32_t q = 100;
+        int rc;
+        if (opts.target_psnr > 0) rc = fri_hip_search_quality_tiled420(raw, rgb.data(), opts.target_psnr, &q, &r.value.psnr_db);
+        else rc = fri_hip_search_quality_ssim_tiled420(raw, rgb.data(), opts.target_ssim, &q, &r.value.ssim);
+        if (rc != FRI_HIP_OK) return fail(dev.describe(rc));
+        r.value.search_quality = q;
+        if (q == 100) return fail("no 4:2:0 quality reaches the target");
+        quality = q;
+    }
+    if (const std::string e = code(quality); !e.empty()) return fail(e);
     r.ok = true;
     return r;
 }

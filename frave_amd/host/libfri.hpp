@@ -82,8 +82,8 @@ struct EncoderOpts { // encoder.rs:58-64
     // and measure in R, G, B; a PSNR or SSIM search that returns 100 codes a lossless RCT file instead (EncodedStages::lossless_rct says so); a size search covers
     // qualities 1..99 only and never falls back to a lossless file.
     bool ycbcr = false;
-    // encode_bytes_tiled only: the rANS coder runs on the device too (K11, fri_hip_encode_image_tiled_coded) and the host only assembles the container
-    // (emit::encode_tiled_from_coded) - the same file, byte for byte, as the host coder writes.
+    // encode_bytes_tiled and encode_bytes_tiled420 only: the rANS coder runs on the device too (K11, fri_hip_encode_image_tiled_coded / _tiled420_coded) and the host
+    // only assembles the container (emit::encode_tiled_from_coded / _coded420) - the same file, byte for byte, as the host coder writes.
     bool device_rans = false;
     EncoderOpts() { quantization_matrix.fill(1); }
 };
@@ -291,9 +291,15 @@ Result<RasterImage> round_trip_tiled(const std::vector<uint8_t> &pixels, uint32_
 
 // Tiled 4:2:0 coding (include/fri_hip.h, "Tiled 4:2:0 coding") of width x height RGB pixels at `quality` (1..99): tiles of about tile_size x tile_size at which
 // both lattices own every pixel (fri_hip_tile_shape420), the device splits and codes them in two batches (fri_hip_encode_image_tiled420_symbols), the emitter codes
-// them on `threads` workers (emit::encode_tiled_from_streams420). The result's ycbcr is true. No targets: the searches on tiled 4:2:0 are out of scope.
-// FRIDecoder::decode and decode_region read such files.
+// them on `threads` workers (emit::encode_tiled_from_streams420). The result's ycbcr is true. FRIDecoder::decode and decode_region read such files.
+// The EncoderOpts form takes opts.quality (1..99) or exactly one target, handled as encode_bytes_tiled handles them on the tiled 4:2:0 plan: target_psnr /
+// target_ssim - fri_hip_search_quality_tiled420 / fri_hip_search_quality_ssim_tiled420, the lowest quality at which the round trip of the tiled 4:2:0 file reaches the
+// target; a result of 100 is an error ("no 4:2:0 quality reaches the target": such a file has no lossless form to fall back to). target_bytes:
+// fri_hip_search_quality_for_size_tiled420, then code, emit and step one quality down while the file is over the budget, at most 8 steps. opts.device_rans: the
+// device codes the planes as well (fri_hip_encode_image_tiled420_coded, emit::encode_tiled_from_coded420); the file is the same. Of opts only quality, the three
+// targets, device_rans and device are read.
 Result<EncodedTiled> encode_bytes_tiled420(const std::vector<uint8_t> &rgb, uint32_t height, uint32_t width, int quality, uint32_t tile_size, int device = 0, unsigned threads = 0);
+Result<EncodedTiled> encode_bytes_tiled420(const std::vector<uint8_t> &rgb, uint32_t height, uint32_t width, const EncoderOpts &opts, uint32_t tile_size, unsigned threads = 0);
 // The direct round trip without the entropy coder, for self-checks: fri_hip_split_tiles420_dev, the forward kernel on both inner plans over all planes, then
 // fri_hip_decode_image_tiled420 - what such a file decodes to.
 Result<RasterImage> round_trip_tiled420(const std::vector<uint8_t> &rgb, uint32_t height, uint32_t width, uint32_t tile_w, uint32_t tile_h, int quality, int device = 0);

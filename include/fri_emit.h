@@ -71,9 +71,9 @@
  * the offsets are strictly increasing. A payload is a complete `frif` file of a tile_h x tile_w image: exactly what fri_emit_encode_image_from_streams writes
  * for that tile's streams, histograms and parameters with FRI_EMIT_EMPTY_OK set. All tiles carry the same metadata word. Alpha inside tiles is refused, by
  * the encoder (-1) and by the decoder ("Malformed tiled image"); 4:2:0 inside tiles is "Tiled 4:2:0" below: fri_tiled_encode_from_streams and
- * fri_tiled_encode_from_coded keep refusing FRI_EMIT_420 (-1), such files have an encoder of their own. fri_emit_decode_image does not know the magic: a `frit` file is "Invalid signature"
- * to it. The size of such a file is estimated from the tiles' histograms, without the coder, by fri_hip_estimate_size_tiled_dev (include/fri_hip.h), which knows
- * the rule of FRI_EMIT_EMPTY_OK.
+ * fri_tiled_encode_from_coded keep refusing FRI_EMIT_420 (-1), such files have encoders of their own. fri_emit_decode_image does not know the magic: a `frit` file is "Invalid signature"
+ * to it. The size of such a file is estimated from the tiles' histograms, without the coder, by fri_hip_estimate_size_tiled_dev (include/fri_hip.h; fri_hip_estimate_size_tiled420_dev for tiled 4:2:0),
+ * which knows the rule of FRI_EMIT_EMPTY_OK.
  *
  * Region decode (fri_tiled_region_tiles, fri_tiled_decode_region below; the device side is fri_hip_decode_region_tiled, include/fri_hip.h): the offset table and
  * the independence of the tiles are what random access needs. A region is x, y, w, h in image pixels with w, h >= 1, x + w <= W and y + h <= H, compared in 64
@@ -84,7 +84,7 @@
  * pixel (y + ry, x + rx), which is pixel (y + ry - j tile_h, x + rx - i tile_w) of tile (j, i): no replicated pixel is ever copied. By definition the region
  * raster is the crop [y : y + h, x : x + w] of what fri_hip_decode_image_tiled returns for the same file.
  *
- * Tiled 4:2:0 (fri_tiled_encode_from_streams420 below; include/fri_hip.h, "Tiled 4:2:0 coding", has the device side): the `frit` container is unchanged and stays
+ * Tiled 4:2:0 (fri_tiled_encode_from_streams420 and fri_tiled_encode_from_coded420 below; include/fri_hip.h, "Tiled 4:2:0 coding", has the device side): the `frit` container is unchanged and stays
  * at version 1. In a tiled 4:2:0 file every payload is a `frif` file of a tile_h x tile_w image with colour space YCbCr, metadata bits 1 and 2 set, and a quality of
  * 1..99: exactly what fri_emit_encode_image_from_streams writes for that tile with 3 | FRI_EMIT_YCBCR | FRI_EMIT_420 | FRI_EMIT_QUALITY(q) | FRI_EMIT_EMPTY_OK.
  * All tiles carry the same metadata word, as today.
@@ -195,6 +195,15 @@ int fri_tiled_encode_from_streams420(uint32_t width, uint32_t height, uint32_t t
 int fri_tiled_encode_from_coded(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t channels, const uint32_t *words, uint64_t word_stride,
                                 const uint32_t *n_words, const uint32_t *models, const uint16_t *off_values, const float *value_params, const float *width_params,
                                 uint32_t threads, uint8_t *out, size_t cap, size_t *len, char *err, size_t err_cap);
+/* A tiled 4:2:0 file ("Tiled 4:2:0" above) from planes the device coded (fri_hip_encode_image_tiled420_coded, include/fri_hip.h): the arguments of
+ * fri_tiled_encode_from_coded with every per-plane array in plane order - words uint32 [3 n][word_stride], n_words [3 n] (at least 20, at most word_stride, -2
+ * otherwise), models [3 n][10][4], off_values uint16 [3 n][10][1024], value_params / width_params [3 n][3][6]. `channels` must be
+ * 3 | FRI_EMIT_YCBCR | FRI_EMIT_420 | FRI_EMIT_QUALITY(q), q = 1..99, with or without FRI_EMIT_EMPTY_OK - anything else, alpha among it, -1. Nothing is coded
+ * here: the file is byte for byte fri_tiled_encode_from_streams420's when the planes are what the host coder makes of the streams, for every thread count.
+ * Returns 0 and *len, or -3 with *len = needed size. */
+int fri_tiled_encode_from_coded420(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t channels, const uint32_t *words, uint64_t word_stride,
+                                   const uint32_t *n_words, const uint32_t *models, const uint16_t *off_values, const float *value_params, const float *width_params,
+                                   uint32_t threads, uint8_t *out, size_t cap, size_t *len, char *err, size_t err_cap);
 /* ... and one ordinary `frif` image of 1 or 3 channels from its C coded planes (`channels` as above): byte for byte fri_emit_encode_image_from_streams's file. */
 int fri_coded_encode_image(uint32_t width, uint32_t height, uint32_t channels, const uint32_t *words, uint64_t word_stride, const uint32_t *n_words, const uint32_t *models,
                            const uint16_t *off_values, const float *value_params, const float *width_params, uint8_t *out, size_t cap, size_t *len, char *err, size_t err_cap);

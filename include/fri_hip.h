@@ -739,8 +739,7 @@ int fri_hip_search_quality_for_size_tiled_dev(fri_hip_plan_tiled *p, const uint8
  * fri_hip_decode_region_tiled420 / _dev: the same for the sub-grid's planes (what fri_tiled_decode_region returns; d_coefs in device memory) -> the region raster
  * [h][w][3]. The plan's tile buffers grow to the region's tiles only. The _dev form refuses a capturing stream (FRI_HIP_ERR_INVALID_ARGUMENT) before anything is
  * enqueued or allocated. FRI_HIP_ERR_INVALID_ARGUMENT for a NULL pointer, a quality outside 1..99 or a region that is empty or leaves the image.
- * Out of scope: the quality searches and the size estimate on tiled 4:2:0; K11, the device rANS coder, for such files (they have two symbol counts per tile);
- * alpha in tiles; multi-GPU forms. */
+ * Out of scope: alpha in tiles; per-tile qualities; multi-GPU forms. */
 typedef struct fri_hip_plan_tiled420 fri_hip_plan_tiled420;
 int fri_hip_tile_shape420(uint32_t width, uint32_t height, uint32_t target, uint32_t *tile_w, uint32_t *tile_h);
 int fri_hip_plan_tiled420_create(fri_hip_ctx *ctx, uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t flags, fri_hip_plan_tiled420 **out);
@@ -762,6 +761,44 @@ int fri_hip_decode_image_tiled420(fri_hip_plan_tiled420 *p, const int32_t *coefs
 int fri_hip_decode_region_tiled420_dev(fri_hip_plan_tiled420 *p, const int32_t *d_coefs, int quality, uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint8_t *d_region,
                                        void *stream);
 int fri_hip_decode_region_tiled420(fri_hip_plan_tiled420 *p, const int32_t *coefs, int quality, uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint8_t *pixels);
+/* The distortion of a tiled 4:2:0 reconstruction against a raster (K12's measuring kernel): the whole-image merge's walk with nothing stored. Every image pixel
+ * is upsampled and converted within its own tile exactly as fri_hip_merge_tiles420_dev does it (the same strip classes, filter, clamping and arithmetic) and
+ * compared with the same byte of d_reference_rgb [H][W][3]; replicated rows and columns of edge tiles are never counted. d_out uint64 [7], the layout of
+ * fri_hip_measure_distortion420_dev: d_out[2 c] = the sum of (merged - reference)^2 of channel c (R, G, B), d_out[2 c + 1] = the largest |merged - reference| of
+ * channel c, d_out[6] = the pixels counted, W H exactly. Exact integers, the same in every run. Zeroes d_out on `stream`, then one kernel; only enqueues,
+ * capturable; any pointer alignment; the inputs are only read. FRI_HIP_ERR_INVALID_ARGUMENT for a NULL pointer, FRI_HIP_ERR_NO_DEVICE on a host-only plan. */
+int fri_hip_measure_distortion_tiled420_dev(fri_hip_plan_tiled420 *p, const uint8_t *d_y_tiles, const uint8_t *d_c_tiles, const uint8_t *d_reference_rgb, uint64_t *d_out,
+                                            void *stream);
+/* The size of the tiled 4:2:0 `frit` file the emitter writes from the planes' histograms, without running the coder. A 4:2:0 tile is a `frif` payload of three
+ * channels, so the formula of fri_hip_estimate_size_tiled_dev holds per tile, unchanged, with C = 3 and the rule of FRI_EMIT_EMPTY_OK; only the arrays are in
+ * plane order: d_hist [3 n][10][1024] as fri_hip_encode_symbols_tiled420_dev writes it, d_n_out_of_alphabet [3 n] (may be NULL: not looked at), d_models (may be
+ * NULL) [3 n][10][4]; d_tile_bytes [n] (required: the payloads, and the kernels' scratch); d_file_bytes [1] = 32 + 8 (n + 1) + the sum of the payloads. A tile
+ * with an uncodable plane has the payload UINT64_MAX, and so has the file, as in the tiled estimate. Integer sums, the same bytes in every run. The _dev form
+ * only enqueues (a memset and three kernels) and is capturable. The host form stages the histograms (n_out_of_alphabet and tile_bytes may be NULL) and
+ * synchronises. */
+int fri_hip_estimate_size_tiled420_dev(fri_hip_plan_tiled420 *p, const uint32_t *d_hist, const uint64_t *d_n_out_of_alphabet, uint64_t *d_file_bytes, uint64_t *d_tile_bytes,
+                                       uint32_t *d_models, void *stream);
+int fri_hip_estimate_size_tiled420(fri_hip_plan_tiled420 *p, const uint32_t *hist, const uint64_t *n_out_of_alphabet, uint64_t *file_bytes, uint64_t *tile_bytes);
+/* The searches of fri_hip_search_quality420, fri_hip_search_quality_ssim420 and fri_hip_search_quality_for_size420 on a tiled 4:2:0 plan: exactly those
+ * bisections, return values, argument checks and refusals (qualities 1..99; a PSNR or SSIM result of 100 means "no 4:2:0 quality reaches the target", 100 is
+ * never probed; the size search returns FRI_HIP_ERR_OUT_OF_RANGE with quality 0 and the estimate of quality 1 when even that exceeds max_bytes; SSIM needs
+ * W, H >= 8; a capturing stream is refused before anything is enqueued or allocated; a host-only plan: FRI_HIP_ERR_NO_DEVICE; the size search needs the stream
+ * order on both inner plans), measured on what the tiled file of that quality holds. The image is split once per call into the plan's tile buffers and every
+ * probe runs on plan-owned buffers that grow on first use. The inner plans' dequantiser settings are left as they are; the probes' inverse kernel uses the
+ * midpoint dequantiser whatever is set.
+ *   PSNR  a probe = the forward kernel on the luma plan over n planes and on the chroma plan over 2 n, the inverse kernel on both into a second pair of tile
+ *         buffers (zeroed once per call, so a sample that no cell owns - FRI_HIP_TILED_ALLOW_HOLES - counts as the 0 the decoder writes), the measuring kernel
+ *         above against d_pixels: the PSNR of fri_hip_search_quality's formula over W H pixels and three channels.
+ *   SSIM  a probe = the same two kernel pairs, the whole-image merge into a raster the plan owns, K7 on the W x H image against d_pixels.
+ *   size  a probe = the chain of fri_hip_encode_image_tiled420_symbols with the fit on both plans (the same histograms), then
+ *         fri_hip_estimate_size_tiled420_dev: est_bytes is the file's estimate.
+ * The host forms stage the pixels through the plan's raster buffer. */
+int fri_hip_search_quality_tiled420(fri_hip_plan_tiled420 *p, const uint8_t *pixels, double target_db, int32_t *quality, double *psnr_db);
+int fri_hip_search_quality_tiled420_dev(fri_hip_plan_tiled420 *p, const uint8_t *d_pixels, double target_db, int32_t *quality, double *psnr_db, void *stream);
+int fri_hip_search_quality_ssim_tiled420(fri_hip_plan_tiled420 *p, const uint8_t *pixels, double target, int32_t *quality, double *ssim);
+int fri_hip_search_quality_ssim_tiled420_dev(fri_hip_plan_tiled420 *p, const uint8_t *d_pixels, double target, int32_t *quality, double *ssim, void *stream);
+int fri_hip_search_quality_for_size_tiled420(fri_hip_plan_tiled420 *p, const uint8_t *pixels, uint64_t max_bytes, int32_t *quality, uint64_t *est_bytes);
+int fri_hip_search_quality_for_size_tiled420_dev(fri_hip_plan_tiled420 *p, const uint8_t *d_pixels, uint64_t max_bytes, int32_t *quality, uint64_t *est_bytes, void *stream);
 
 /* ---- the rANS coder on the device (K11, k11_rans.hip) ------------------------------------------- */
 /* The emitter's last stage - symbols to rANS words (host/emit.cpp, encode_symbols) - for a batch of planes, a plane being one channel of one tile or of an
@@ -823,6 +860,14 @@ int fri_hip_rans_time_planes_dev(fri_hip_ctx *ctx, uint32_t n_planes, const uint
  * for another reason. Synchronous. */
 int fri_hip_encode_image_tiled_coded(fri_hip_plan_tiled *p, const uint8_t *pixels, const int32_t qmatrix[32], float *value_params, float *width_params, uint32_t *words,
                                      size_t word_stride, uint32_t *n_words, uint32_t *models, uint16_t *off_values, uint32_t *status);
+/* The same for a tiled 4:2:0 image: fri_hip_encode_image_tiled420_symbols's chain with the fit at `quality` (1..99; both inner plans need their stream order),
+ * then K11 with FRI_HIP_RANS_EMPTY_OK twice on one stream - the n luma planes of n_y symbols, then the 2 n chroma planes of n_c symbols - and only the coded
+ * planes come back: what fri_tiled_encode_from_coded420 (include/fri_emit.h) takes. Every per-plane output is in plane order: value_params / width_params
+ * [3 n][3][6]; words uint32 [3 n][word_stride], of which the first n_words[p] of plane p are written; n_words [3 n]; models [3 n][10][4]; off_values uint16
+ * [3 n][10][1024]; status [3 n][4]. Each batch is coded with room for 8 bits per symbol, and a batch in which a plane reports FRI_HIP_RANS_TOO_SMALL is coded
+ * once more with n_symbols + 20 words per plane, the hard upper bound. Return values as for fri_hip_encode_image_tiled_coded. Synchronous. */
+int fri_hip_encode_image_tiled420_coded(fri_hip_plan_tiled420 *p, const uint8_t *pixels, int quality, float *value_params, float *width_params, uint32_t *words,
+                                        size_t word_stride, uint32_t *n_words, uint32_t *models, uint16_t *off_values, uint32_t *status);
 
 /* ---- timing helper ---------------------------------------------------------------------------- */
 /* Runs the forward kernel `iters` times on `stream` bracketed by HIP events recorded on that same
