@@ -404,6 +404,19 @@ def fit_width_params(wtw_tri, wtr, rows):
     return out
 
 
+def _search(plan, name, pixels, target, ctype, stream):
+    """A quality search of any plan kind: entry point `name` (pixels: a host array) or `name`_dev (pixels: a device pointer, an int) -> (quality, the value there)."""
+    qual, v = C.c_int32(0), ctype(0)
+    L = load_library()
+    if isinstance(pixels, int):
+        _check(getattr(L, name + "_dev")(plan._h, pixels, target, C.byref(qual), C.byref(v), stream), name + "_dev", plan.ctx)
+    else:
+        px = np.ascontiguousarray(pixels, np.uint8)
+        assert px.size == plan.pixel_bytes
+        _check(getattr(L, name)(plan._h, _p(px), target, C.byref(qual), C.byref(v)), name, plan.ctx)
+    return qual.value, v.value
+
+
 def _encode_batch(fn, handle, where, ctx, images, channels, num_cells, qmatrix, fit, params, want_bucket, want_prediction):
     """Shared marshalling of fri_hip_encode_image_batch / fri_hip_multi_encode_image: lists of per-image arrays."""
     imgs = [np.ascontiguousarray(i, np.uint8).reshape(-1) for i in images]
@@ -573,15 +586,7 @@ class Plan:
     def search_quality(self, pixels, target_db, stream=0):
         """fri_hip_search_quality (pixels: a host array) or fri_hip_search_quality_dev (pixels: a device pointer, an int): the lowest quality whose
         midpoint-dequantised round trip reaches target_db, by the bisection the header describes. Returns (quality, psnr_db)."""
-        qual, db = C.c_int32(0), C.c_double(0.0)
-        L = load_library()
-        if isinstance(pixels, int):
-            _check(L.fri_hip_search_quality_dev(self._h, pixels, float(target_db), C.byref(qual), C.byref(db), stream), "fri_hip_search_quality_dev", self.ctx)
-        else:
-            px = np.ascontiguousarray(pixels, np.uint8)
-            assert px.size == self.pixel_bytes
-            _check(L.fri_hip_search_quality(self._h, _p(px), float(target_db), C.byref(qual), C.byref(db)), "fri_hip_search_quality", self.ctx)
-        return qual.value, db.value
+        return _search(self, "fri_hip_search_quality", pixels, float(target_db), C.c_double, stream)
 
     def measure_ssim(self, a, b):
         """fri_hip_measure_ssim: the SSIM sums of two host rasters of the plan's shape (a the source, b the reconstruction) - int64 [C + 1], per channel
@@ -600,15 +605,7 @@ class Plan:
     def search_quality_ssim(self, pixels, target, stream=0):
         """fri_hip_search_quality_ssim (pixels: a host array) or its _dev form (pixels: a device pointer, an int): the lowest quality whose midpoint-dequantised
         round trip reaches an SSIM of target (0 < target <= 1), by the bisection of search_quality. Returns (quality, ssim); 100 means "code losslessly"."""
-        qual, v = C.c_int32(0), C.c_double(0.0)
-        L = load_library()
-        if isinstance(pixels, int):
-            _check(L.fri_hip_search_quality_ssim_dev(self._h, pixels, float(target), C.byref(qual), C.byref(v), stream), "fri_hip_search_quality_ssim_dev", self.ctx)
-        else:
-            px = np.ascontiguousarray(pixels, np.uint8)
-            assert px.size == self.pixel_bytes
-            _check(L.fri_hip_search_quality_ssim(self._h, _p(px), float(target), C.byref(qual), C.byref(v)), "fri_hip_search_quality_ssim", self.ctx)
-        return qual.value, v.value
+        return _search(self, "fri_hip_search_quality_ssim", pixels, float(target), C.c_double, stream)
 
     def estimate_size(self, hist, oob=None, stream=0, n_images=1, d_bytes=None, d_models=None):
         """The estimated .frv bytes of the histograms (include/fri_hip.h gives the formula); UINT64_MAX where the emitter would refuse the image.
@@ -631,15 +628,7 @@ class Plan:
     def search_quality_for_size(self, pixels, max_bytes, stream=0):
         """fri_hip_search_quality_for_size (pixels: a host array) or its _dev form (pixels: a device pointer, an int): the highest quality whose estimated
         file is at most max_bytes, by the bisection the header describes. Returns (quality, estimated bytes); FriHipError with code -7 when nothing fits."""
-        qual, est = C.c_int32(0), C.c_uint64(0)
-        L = load_library()
-        if isinstance(pixels, int):
-            _check(L.fri_hip_search_quality_for_size_dev(self._h, pixels, int(max_bytes), C.byref(qual), C.byref(est), stream), "fri_hip_search_quality_for_size_dev", self.ctx)
-        else:
-            px = np.ascontiguousarray(pixels, np.uint8)
-            assert px.size == self.pixel_bytes
-            _check(L.fri_hip_search_quality_for_size(self._h, _p(px), int(max_bytes), C.byref(qual), C.byref(est)), "fri_hip_search_quality_for_size", self.ctx)
-        return qual.value, est.value
+        return _search(self, "fri_hip_search_quality_for_size", pixels, int(max_bytes), C.c_uint64, stream)
 
     def set_colour_transform(self, mode):
         """fri_hip_plan_set_colour_transform: COLOUR_NONE (default), COLOUR_RCT or COLOUR_YCBCR (C = 3 plans): every forward entry point then codes the
@@ -983,28 +972,17 @@ class Plan420:
         _check(load_library().fri_hip_decode_image420(self._h, _p(co), int(quality), _p(out)), "fri_hip_decode_image420", self.ctx)
         return out
 
-    def _search(self, name, pixels, target, ctype, stream):
-        qual, v = C.c_int32(0), ctype(0)
-        L = load_library()
-        if isinstance(pixels, int):
-            _check(getattr(L, name + "_dev")(self._h, pixels, target, C.byref(qual), C.byref(v), stream), name + "_dev", self.ctx)
-        else:
-            px = np.ascontiguousarray(pixels, np.uint8)
-            assert px.size == self.pixel_bytes
-            _check(getattr(L, name)(self._h, _p(px), target, C.byref(qual), C.byref(v)), name, self.ctx)
-        return qual.value, v.value
-
     def search_quality(self, pixels, target_db, stream=0):
         """fri_hip_search_quality420[_dev] (pixels: a host array or a device pointer): (quality, RGB PSNR in dB); 100 = code losslessly."""
-        return self._search("fri_hip_search_quality420", pixels, float(target_db), C.c_double, stream)
+        return _search(self, "fri_hip_search_quality420", pixels, float(target_db), C.c_double, stream)
 
     def search_quality_ssim(self, pixels, target, stream=0):
         """fri_hip_search_quality_ssim420[_dev]: (quality, RGB SSIM); 100 = code losslessly."""
-        return self._search("fri_hip_search_quality_ssim420", pixels, float(target), C.c_double, stream)
+        return _search(self, "fri_hip_search_quality_ssim420", pixels, float(target), C.c_double, stream)
 
     def search_quality_for_size(self, pixels, max_bytes, stream=0):
         """fri_hip_search_quality_for_size420[_dev]: (quality, estimated bytes); FriHipError with code -7 when nothing fits."""
-        return self._search("fri_hip_search_quality_for_size420", pixels, int(max_bytes), C.c_uint64, stream)
+        return _search(self, "fri_hip_search_quality_for_size420", pixels, int(max_bytes), C.c_uint64, stream)
 
 
 class PlanRGBA:
@@ -1235,29 +1213,18 @@ class PlanTiled:
         _check(load_library().fri_hip_estimate_size_tiled(self._h, _p(h), None if o is None else _p(o), C.byref(total), _p(tiles)), "fri_hip_estimate_size_tiled", self.ctx)
         return total.value, tiles
 
-    def _search(self, name, pixels, target, ctype, stream):
-        qual, v = C.c_int32(0), ctype(0)
-        L = load_library()
-        if isinstance(pixels, int):
-            _check(getattr(L, name + "_dev")(self._h, pixels, target, C.byref(qual), C.byref(v), stream), name + "_dev", self.ctx)
-        else:
-            px = np.ascontiguousarray(pixels, np.uint8)
-            assert px.size == self.pixel_bytes
-            _check(getattr(L, name)(self._h, _p(px), target, C.byref(qual), C.byref(v)), name, self.ctx)
-        return qual.value, v.value
-
     def search_quality(self, pixels, target_db, stream=0):
         """fri_hip_search_quality_tiled[_dev] (pixels: a host array or a device pointer): (quality, PSNR in dB of the tiled round trip); 100 = code losslessly."""
-        return self._search("fri_hip_search_quality_tiled", pixels, float(target_db), C.c_double, stream)
+        return _search(self, "fri_hip_search_quality_tiled", pixels, float(target_db), C.c_double, stream)
 
     def search_quality_ssim(self, pixels, target, stream=0):
         """fri_hip_search_quality_ssim_tiled[_dev]: (quality, SSIM of the tiled round trip); 100 = code losslessly."""
-        return self._search("fri_hip_search_quality_ssim_tiled", pixels, float(target), C.c_double, stream)
+        return _search(self, "fri_hip_search_quality_ssim_tiled", pixels, float(target), C.c_double, stream)
 
     def search_quality_for_size(self, pixels, max_bytes, stream=0):
         """fri_hip_search_quality_for_size_tiled[_dev]: (quality, estimated bytes of the `frit` file); FriHipError with code -7 when nothing fits. Needs
         set_stream_order()."""
-        return self._search("fri_hip_search_quality_for_size_tiled", pixels, int(max_bytes), C.c_uint64, stream)
+        return _search(self, "fri_hip_search_quality_for_size_tiled", pixels, int(max_bytes), C.c_uint64, stream)
 
 
 class PlanTiled420:
@@ -1421,27 +1388,16 @@ class PlanTiled420:
                self.ctx)
         return total.value, tiles
 
-    def _search(self, name, pixels, target, ctype, stream):
-        qual, v = C.c_int32(0), ctype(0)
-        L = load_library()
-        if isinstance(pixels, int):
-            _check(getattr(L, name + "_dev")(self._h, pixels, target, C.byref(qual), C.byref(v), stream), name + "_dev", self.ctx)
-        else:
-            px = np.ascontiguousarray(pixels, np.uint8)
-            assert px.size == self.pixel_bytes
-            _check(getattr(L, name)(self._h, _p(px), target, C.byref(qual), C.byref(v)), name, self.ctx)
-        return qual.value, v.value
-
     def search_quality(self, pixels, target_db, stream=0):
         """fri_hip_search_quality_tiled420[_dev] (pixels: a host array or a device pointer): (quality, PSNR in dB of the tiled 4:2:0 round trip); 100 = no 4:2:0
         quality reaches the target."""
-        return self._search("fri_hip_search_quality_tiled420", pixels, float(target_db), C.c_double, stream)
+        return _search(self, "fri_hip_search_quality_tiled420", pixels, float(target_db), C.c_double, stream)
 
     def search_quality_ssim(self, pixels, target, stream=0):
         """fri_hip_search_quality_ssim_tiled420[_dev]: (quality, SSIM of the tiled 4:2:0 round trip); 100 = no 4:2:0 quality reaches the target."""
-        return self._search("fri_hip_search_quality_ssim_tiled420", pixels, float(target), C.c_double, stream)
+        return _search(self, "fri_hip_search_quality_ssim_tiled420", pixels, float(target), C.c_double, stream)
 
     def search_quality_for_size(self, pixels, max_bytes, stream=0):
         """fri_hip_search_quality_for_size_tiled420[_dev]: (quality, estimated bytes of the `frit` file); FriHipError with code -7 when nothing fits. Needs
         set_stream_order()."""
-        return self._search("fri_hip_search_quality_for_size_tiled420", pixels, int(max_bytes), C.c_uint64, stream)
+        return _search(self, "fri_hip_search_quality_for_size_tiled420", pixels, int(max_bytes), C.c_uint64, stream)

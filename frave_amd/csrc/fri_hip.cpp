@@ -1,7 +1,8 @@
 // fri_hip.cpp -- the C ABI of libfri_hip.so (include/fri_hip.h): the context, the ordinary plan and every entry point that takes a fri_hip_plan or a
 // fri_hip_multi, the forward tuner and its process-wide cache included. Host-side glue only: plan construction, table upload, staging for the host-pointer
 // entry points, launches. No CPU compute fallback. The further plan kinds have a source each (fri_hip_420.cpp, fri_hip_rgba.cpp, fri_hip_tiled.cpp,
-// fri_hip_tiled420.cpp), K11's plane entry points are in fri_hip_rans.cpp, and what all of them share is fri_hip_internal.hpp.
+// fri_hip_tiled420.cpp), K11's plane entry points are in fri_hip_rans.cpp, and what all of them share is fri_hip_internal.hpp; the quality searches of every kind
+// run on search_scaffold.hpp, with the kind's probe steps beside its plan (here: PlanSearch).
 #include "fri_hip_internal.hpp"
 
 #include <atomic>
@@ -12,7 +13,7 @@
 #include <optional>
 #include <thread>
 
-#include "quality_search.hpp"
+#include "search_scaffold.hpp"
 #include "solve6.hpp"
 
 using namespace fri;
@@ -496,6 +497,65 @@ int wait_event_polling(fri_hip_ctx *c, hipEvent_t ev) {
         }
     }
 }
+
+// The ordinary plan's part of the quality searches (search_scaffold.hpp): the image itself is the plane, nothing is split. Its K3 measures while it reconstructs,
+// so a round trip is K1 here and ends in measure() (K3 against the pixels, nothing stored) or in raster() (K3 into the raster SSIM reads).
+struct PlanSearch {
+    fri_hip_plan *p;
+    hipStream_t s;
+    unsigned long long *sums = nullptr;
+    uint8_t *recon_raster = nullptr;
+    const uint8_t *d_pixels = nullptr;
+    DevicePlan inv{}; // the probes' K3: the plan's inverse tiling with the midpoint dequantiser
+    QMatrix q{};      // of the round trip under way
+    fri_hip_plan *inner() const { return p; }
+    uint32_t width() const { return p->geo.width; }
+    uint32_t height() const { return p->geo.height; }
+    uint32_t channels() const { return p->geo.channels; }
+    bool refused() const { return p->dev.rct; }
+    bool chain_ready() const { return true; } // (the probes' chain writes no stream)
+    Grown<uint8_t> &staging() const { return p->staging.pixels; }
+    int size_top() const { return p->dev.ycc ? 100 : 101; } // a YCbCr plan's quality 100 is not lossless and has no file (fri_emit)
+    int begin(Search what, const uint8_t *pixels) {
+        fri_hip_ctx *c = p->ctx;
+        auto &st = p->staging;
+        const size_t C = channels();
+        Grown<unsigned long long> &d_sums = what == Search::Psnr ? st.measure : what == Search::Ssim ? st.ssim : st.rate;
+        int rc;
+        if ((rc = grow(c, st.search_coefs, fri_hip_plan_coef_count(p)))) return rc;
+        if (what == Search::Ssim && (rc = grow(c, st.ssim_pixels, fri_hip_plan_pixel_bytes(p)))) return rc;
+        if (what == Search::Size && ((rc = grow(c, st.search_hist, C * 10 * 1024)) || (rc = grow(c, st.search_oob, C)) || (rc = grow(c, st.search_params, C * 36)))) return rc;
+        if ((rc = grow(c, d_sums, what == Search::Psnr ? 2 * C + 1 : what == Search::Ssim ? C + 1 : 1))) return rc;
+        d_pixels = pixels, sums = d_sums, recon_raster = st.ssim_pixels, inv = midpoint_inverse(p->dev_inv);
+        return FRI_HIP_OK;
+    }
+    int round_trip(int quality) {
+        int32_t qm[32];
+        fri_hip_quality_matrix(quality, qm);
+        check_q(qm, q);
+        HIP_TRY(p->ctx, launch_fwd_transform_quant(p->dev, 1, d_pixels, 0, p->staging.search_coefs, 0, q, s));
+        return FRI_HIP_OK;
+    }
+    int measure() {
+        HIP_TRY(p->ctx, hipMemsetAsync(sums, 0, (2 * (size_t)channels() + 1) * sizeof(uint64_t), s));
+        HIP_TRY(p->ctx, launch_inverse_transform(inv, 1, p->staging.search_coefs, 0, q, const_cast<uint8_t *>(d_pixels), 0, s, sums));
+        return FRI_HIP_OK;
+    }
+    int raster() {
+        HIP_TRY(p->ctx, launch_inverse_transform(inv, 1, p->staging.search_coefs, 0, q, recon_raster, 0, s));
+        return FRI_HIP_OK;
+    }
+    // the chain of fri_hip_encode_image_symbols at `quality` (K1, the device-side fit, K2; the same histograms), then the rate kernel
+    int estimate(int quality) {
+        auto &st = p->staging;
+        int32_t qm[32];
+        fri_hip_quality_matrix(quality, qm);
+        if (int r = fri_hip_encode_image_batch_dev(p, 1, d_pixels, 0, qm, 1, st.search_params, st.search_coefs, 0, nullptr, nullptr, 0, st.search_hist,
+                                                   (uint64_t *)st.search_oob.get(), nullptr, s))
+            return r;
+        return fri_hip_estimate_size_dev(p, 1, st.search_hist, (const uint64_t *)st.search_oob.get(), (uint64_t *)st.rate.get(), nullptr, s);
+    }
+};
 
 } // namespace
 
@@ -1538,39 +1598,11 @@ int fri_hip_measure_distortion_dev(fri_hip_plan *p, const int32_t *d_coefs, cons
 }
 
 int fri_hip_search_quality_dev(fri_hip_plan *p, const uint8_t *d_pixels, double target_db, int32_t *quality, double *psnr_db, void *stream) {
-    if (!p || !d_pixels || !quality || !psnr_db || !(target_db > 0) || p->dev.rct) return FRI_HIP_ERR_INVALID_ARGUMENT; // (!(x > 0): NaN too)
-    if (int rc = need_device(p)) return rc;
-    const hipStream_t s = (hipStream_t)stream;
-    if (int rc = refuse_capture(p, s, "fri_hip_search_quality_dev reads every probe back: it cannot be captured into a HIP graph")) return rc;
-    fri_hip_ctx *c = p->ctx;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const uint32_t C = p->geo.channels;
-    auto &st = p->staging;
-    int rc;
-    if ((rc = grow(c, st.search_coefs, fri_hip_plan_coef_count(p))) || (rc = grow(c, st.measure, 2 * (size_t)C + 1))) return rc;
-    const DevicePlan inv = midpoint_inverse(p->dev_inv); // the probes' K3: the plan's inverse tiling
-    auto probe = [&](int mid, double &db) -> int {
-        int32_t qm[32];
-        QMatrix q;
-        fri_hip_quality_matrix(mid, qm);
-        check_q(qm, q);
-        HIP_TRY(c, launch_fwd_transform_quant(p->dev, 1, d_pixels, 0, st.search_coefs, 0, q, s));
-        HIP_TRY(c, hipMemsetAsync(st.measure, 0, (2 * (size_t)C + 1) * sizeof(uint64_t), s));
-        HIP_TRY(c, launch_inverse_transform(inv, 1, st.search_coefs, 0, q, const_cast<uint8_t *>(d_pixels), 0, s, st.measure));
-        unsigned long long m[7];
-        HIP_TRY(c, hipMemcpyAsync(m, st.measure, (2 * (size_t)C + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
-        db = distortion_psnr(m, C);
-        return FRI_HIP_OK;
-    };
-    return search_at_least(target_db, HUGE_VAL, probe, quality, psnr_db); // (100 = lossless is never probed)
+    return search_dev<Search::Psnr, PlanSearch>(__func__, p, d_pixels, target_db, quality, psnr_db, stream);
 }
 
 int fri_hip_search_quality(fri_hip_plan *p, const uint8_t *pixels, double target_db, int32_t *quality, double *psnr_db) {
-    if (!p || !pixels || !quality || !psnr_db || !(target_db > 0) || p->dev.rct) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    if (int rc = need_device(p)) return rc;
-    if (int rc = stage_pixels(p->ctx, p->staging.pixels, pixels, fri_hip_plan_pixel_bytes(p))) return rc;
-    return fri_hip_search_quality_dev(p, p->staging.pixels, target_db, quality, psnr_db, nullptr);
+    return search_host<Search::Psnr, PlanSearch>(fri_hip_search_quality_dev, p, pixels, target_db, quality, psnr_db);
 }
 
 /* ---- lossy coding to a target size ---------------------------------------------------------------- */
@@ -1602,39 +1634,11 @@ int fri_hip_estimate_size(fri_hip_plan *p, const uint32_t *hist, const uint64_t 
 }
 
 int fri_hip_search_quality_for_size_dev(fri_hip_plan *p, const uint8_t *d_pixels, uint64_t max_bytes, int32_t *quality, uint64_t *est_bytes, void *stream) {
-    if (!p || !d_pixels || !quality || !est_bytes || max_bytes == 0 || p->dev.rct) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    if (int rc = need_device(p)) return rc;
-    const hipStream_t s = (hipStream_t)stream;
-    if (int rc = refuse_capture(p, s, "fri_hip_search_quality_for_size_dev reads every probe back: it cannot be captured into a HIP graph")) return rc;
-    fri_hip_ctx *c = p->ctx;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t C = p->geo.channels;
-    auto &st = p->staging;
-    int rc;
-    if ((rc = grow(c, st.search_coefs, fri_hip_plan_coef_count(p))) || (rc = grow(c, st.search_hist, C * 10 * 1024)) || (rc = grow(c, st.search_oob, C)) ||
-        (rc = grow(c, st.search_params, C * 36)) || (rc = grow(c, st.rate, 1)))
-        return rc;
-    // a probe: the chain of fri_hip_encode_image_symbols at quality q (K1, the device-side fit, K2; the same histograms), then the rate kernel
-    auto probe = [&](int q, uint64_t &est) -> int {
-        int32_t qm[32];
-        fri_hip_quality_matrix(q, qm);
-        if (int r = fri_hip_encode_image_batch_dev(p, 1, d_pixels, 0, qm, 1, st.search_params, st.search_coefs, 0, nullptr, nullptr, 0, st.search_hist,
-                                                   (uint64_t *)st.search_oob.get(), nullptr, stream))
-            return r;
-        if (int r = fri_hip_estimate_size_dev(p, 1, st.search_hist, (const uint64_t *)st.search_oob.get(), (uint64_t *)st.rate.get(), nullptr, stream)) return r;
-        HIP_TRY(c, hipMemcpyAsync(&est, st.rate, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
-        return FRI_HIP_OK;
-    };
-    // the first quality without a file: 101, or 100 on a YCbCr plan, whose quality 100 is not lossless and has no file (fri_emit)
-    return search_at_most<FRI_HIP_ERR_OUT_OF_RANGE>(max_bytes, p->dev.ycc ? 100 : 101, probe, quality, est_bytes);
+    return search_dev<Search::Size, PlanSearch>(__func__, p, d_pixels, max_bytes, quality, est_bytes, stream);
 }
 
 int fri_hip_search_quality_for_size(fri_hip_plan *p, const uint8_t *pixels, uint64_t max_bytes, int32_t *quality, uint64_t *est_bytes) {
-    if (!p || !pixels || !quality || !est_bytes || max_bytes == 0 || p->dev.rct) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    if (int rc = need_device(p)) return rc;
-    if (int rc = stage_pixels(p->ctx, p->staging.pixels, pixels, fri_hip_plan_pixel_bytes(p))) return rc;
-    return fri_hip_search_quality_for_size_dev(p, p->staging.pixels, max_bytes, quality, est_bytes, nullptr);
+    return search_host<Search::Size, PlanSearch>(fri_hip_search_quality_for_size_dev, p, pixels, max_bytes, quality, est_bytes);
 }
 
 /* ---- SSIM ------------------------------------------------------------------------------------------- */
@@ -1669,42 +1673,11 @@ int fri_hip_measure_ssim(fri_hip_plan *p, const uint8_t *a, const uint8_t *b, in
 }
 
 int fri_hip_search_quality_ssim_dev(fri_hip_plan *p, const uint8_t *d_pixels, double target, int32_t *quality, double *ssim, void *stream) {
-    if (!p || !d_pixels || !quality || !ssim || !(target > 0 && target <= 1) || p->dev.rct) return FRI_HIP_ERR_INVALID_ARGUMENT; // (NaN fails both)
-    if (int rc = ssim_shape(p)) return rc;
-    if (int rc = need_device(p)) return rc;
-    const hipStream_t s = (hipStream_t)stream;
-    if (int rc = refuse_capture(p, s, "fri_hip_search_quality_ssim_dev reads every probe back: it cannot be captured into a HIP graph")) return rc;
-    fri_hip_ctx *c = p->ctx;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const uint32_t C = p->geo.channels;
-    auto &st = p->staging;
-    int rc;
-    if ((rc = grow(c, st.search_coefs, fri_hip_plan_coef_count(p))) || (rc = grow(c, st.ssim_pixels, fri_hip_plan_pixel_bytes(p))) || (rc = grow(c, st.ssim, C + 1)))
-        return rc;
-    const DevicePlan inv = midpoint_inverse(p->dev_inv); // the probes' K3: the plan's inverse tiling, writing the raster a decoder gets
-    auto probe = [&](int mid, double &v) -> int {
-        int32_t qm[32];
-        QMatrix q;
-        fri_hip_quality_matrix(mid, qm);
-        check_q(qm, q);
-        HIP_TRY(c, launch_fwd_transform_quant(p->dev, 1, d_pixels, 0, st.search_coefs, 0, q, s));
-        HIP_TRY(c, launch_inverse_transform(inv, 1, st.search_coefs, 0, q, st.ssim_pixels, 0, s));
-        if (int r = fri_hip_measure_ssim_dev(p, 1, d_pixels, st.ssim_pixels, 0, (int64_t *)st.ssim.get(), stream)) return r;
-        unsigned long long m[4];
-        HIP_TRY(c, hipMemcpyAsync(m, st.ssim, (C + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
-        v = ssim_of(m, C);
-        return FRI_HIP_OK;
-    };
-    return search_at_least(target, 1.0, probe, quality, ssim); // (100 = lossless is never probed)
+    return search_dev<Search::Ssim, PlanSearch>(__func__, p, d_pixels, target, quality, ssim, stream);
 }
 
 int fri_hip_search_quality_ssim(fri_hip_plan *p, const uint8_t *pixels, double target, int32_t *quality, double *ssim) {
-    if (!p || !pixels || !quality || !ssim || !(target > 0 && target <= 1) || p->dev.rct) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    if (int rc = ssim_shape(p)) return rc;
-    if (int rc = need_device(p)) return rc;
-    if (int rc = stage_pixels(p->ctx, p->staging.pixels, pixels, fri_hip_plan_pixel_bytes(p))) return rc;
-    return fri_hip_search_quality_ssim_dev(p, p->staging.pixels, target, quality, ssim, nullptr);
+    return search_host<Search::Ssim, PlanSearch>(fri_hip_search_quality_ssim_dev, p, pixels, target, quality, ssim);
 }
 
 /* ---- timing helper ------------------------------------------------------------------------------ */

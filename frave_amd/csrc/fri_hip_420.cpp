@@ -1,10 +1,10 @@
 // fri_hip_420.cpp -- the 4:2:0 plan kind of the C ABI (fri_hip_plan420: include/fri_hip.h): the plan, its split, merge and measure, the host encode and decode,
-// and its quality searches. Host-side glue like fri_hip.cpp, on two ordinary plans.
+// and its quality searches (Search420 on search_scaffold.hpp). Host-side glue like fri_hip.cpp, on two ordinary plans.
 #include "fri_hip_internal.hpp"
 
 #include <new>
 
-#include "quality_search.hpp"
+#include "search_scaffold.hpp"
 
 using namespace fri;
 using namespace fri::host;
@@ -48,6 +48,64 @@ int inverse420(fri_hip_plan420 *p, const int32_t *d_coefs, const QMatrix &q, hip
     HIP_TRY(p->ctx, launch_inverse_transform(ic, 2, d_coefs + p->y_coefs(), p->c_coefs(), q, p->recon + p->y_bytes(), p->c_bytes(), s));
     return FRI_HIP_OK;
 }
+
+// The 4:2:0 plan's part of the quality searches (search_scaffold.hpp): the image split once into p->planes; a round trip is forward420 and inverse420 into
+// p->recon, which the merge measures against the pixels or writes as the raster SSIM reads.
+struct Search420 {
+    fri_hip_plan420 *p;
+    hipStream_t s;
+    unsigned long long *sums = nullptr;
+    uint8_t *recon_raster = nullptr;
+    const uint8_t *d_pixels = nullptr;
+    fri_hip_plan *inner() const { return p->luma.get(); }
+    uint32_t width() const { return p->width; }
+    uint32_t height() const { return p->height; }
+    uint32_t channels() const { return 3; }
+    bool refused() const { return false; }
+    bool chain_ready() const { return true; } // (the probes' chain writes no stream)
+    Grown<uint8_t> &staging() const { return p->rgb; }
+    int size_top() const { return 100; } // a 4:2:0 file has a quality of 1..99
+    int begin(Search what, const uint8_t *pixels) {
+        fri_hip_ctx *c = p->ctx;
+        int rc;
+        if ((rc = grow(c, p->planes, p->plane_bytes())) || (rc = grow(c, p->coefs, p->y_coefs() + 2 * p->c_coefs())) || (rc = grow(c, p->measure, 7))) return rc;
+        if (what != Search::Size && (rc = grow(c, p->recon, p->plane_bytes()))) return rc;
+        if (what == Search::Ssim && (rc = grow(c, p->recon_rgb, 3 * p->y_bytes()))) return rc;
+        if (what == Search::Size && ((rc = grow(c, p->hist, 3 * 10 * 1024)) || (rc = grow(c, p->counts, 6)) || (rc = grow(c, p->params, 3 * 36)))) return rc;
+        d_pixels = pixels, sums = p->measure, recon_raster = p->recon_rgb;
+        HIP_TRY(c, launch_split420(d_pixels, p->width, p->height, p->planes, p->planes + p->y_bytes(), s));
+        return FRI_HIP_OK;
+    }
+    int round_trip(int quality) {
+        int32_t qm[32];
+        QMatrix q;
+        quality_q(quality, qm, q);
+        if (int r = forward420(p, q, s)) return r;
+        return inverse420(p, p->coefs, q, s);
+    }
+    int measure() {
+        HIP_TRY(p->ctx, launch_clear_sums(sums, 7, s));
+        HIP_TRY(p->ctx, launch_merge420(p->recon, p->recon + p->y_bytes(), p->width, p->height, const_cast<uint8_t *>(d_pixels), s, sums));
+        return FRI_HIP_OK;
+    }
+    int raster() {
+        HIP_TRY(p->ctx, launch_merge420(p->recon, p->recon + p->y_bytes(), p->width, p->height, recon_raster, s));
+        return FRI_HIP_OK;
+    }
+    // K1, the device-side fit and K2 on both plans at `quality` (the histograms of fri_hip_encode_image420_symbols), then the rate kernel over the three
+    // histograms as one C = 3 image
+    int estimate(int quality) {
+        uint64_t *oob = reinterpret_cast<uint64_t *>(p->counts.get());
+        int32_t qm[32];
+        fri_hip_quality_matrix(quality, qm);
+        if (int r = fri_hip_encode_image_batch_dev(p->luma.get(), 1, p->planes, 0, qm, 1, p->params, p->coefs, 0, nullptr, nullptr, 0, p->hist, oob, nullptr, s)) return r;
+        if (int r = fri_hip_encode_image_batch_dev(p->chroma.get(), 2, p->planes + p->y_bytes(), p->c_bytes(), qm, 1, p->params + 36, p->coefs + p->y_coefs(), p->c_coefs(), nullptr,
+                                                   nullptr, 0, p->hist + 10 * 1024, oob + 1, nullptr, s))
+            return r;
+        HIP_TRY(p->ctx, launch_rate_estimate(1, 3, p->hist, p->counts, p->luma->laplace, sums, nullptr, kRateLayout, s));
+        return FRI_HIP_OK;
+    }
+};
 
 } // namespace
 
@@ -127,11 +185,7 @@ int fri_hip_encode_image420_symbols(fri_hip_plan420 *p, const uint8_t *pixels, i
     if ((rc = fri_hip_encode_symbols_batch_dev(p->chroma.get(), 2, p->planes + p->y_bytes(), p->c_bytes(), qm, 1, p->params + 36, nullptr, 0, nullptr, 0, p->symbols + n_y, n_c,
                                                p->hist + 10 * 1024, oob + 1, oob + 4, nullptr)))
         return rc;
-    HIP_TRY(c, hipMemcpy(symbols, p->symbols, (n_y + 2 * n_c) * sizeof(uint16_t), hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(hist, p->hist, 3 * 10 * 1024 * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    bool out_of_range = false;
-    if ((rc = read_back_plane_results(c, 3, p->params, p->counts, value_params, width_params, n_out_of_alphabet, &out_of_range))) return rc;
-    return out_of_range ? FRI_HIP_ERR_OUT_OF_RANGE : FRI_HIP_OK;
+    return read_back_symbols(c, 3, n_y + 2 * n_c, p->symbols, p->hist, p->params, p->counts, symbols, hist, value_params, width_params, n_out_of_alphabet);
 }
 
 int fri_hip_decode_image420(fri_hip_plan420 *p, const int32_t *coefs, int quality, uint8_t *pixels) {
@@ -152,115 +206,27 @@ int fri_hip_decode_image420(fri_hip_plan420 *p, const int32_t *coefs, int qualit
 }
 
 int fri_hip_search_quality420_dev(fri_hip_plan420 *p, const uint8_t *d_pixels, double target_db, int32_t *quality, double *psnr_db, void *stream) {
-    if (!p || !d_pixels || !quality || !psnr_db || !(target_db > 0)) return FRI_HIP_ERR_INVALID_ARGUMENT; // (!(x > 0): NaN too)
-    if (int rc = need_device(p)) return rc;
-    const hipStream_t s = (hipStream_t)stream;
-    if (int rc = refuse_capture(p->luma.get(), s, "fri_hip_search_quality420_dev reads every probe back: it cannot be captured into a HIP graph")) return rc;
-    fri_hip_ctx *c = p->ctx;
-    HIP_TRY(c, hipSetDevice(c->device));
-    int rc;
-    if ((rc = grow(c, p->planes, p->plane_bytes())) || (rc = grow(c, p->recon, p->plane_bytes())) || (rc = grow(c, p->coefs, p->y_coefs() + 2 * p->c_coefs())) ||
-        (rc = grow(c, p->measure, 7)))
-        return rc;
-    HIP_TRY(c, launch_split420(d_pixels, p->width, p->height, p->planes, p->planes + p->y_bytes(), s));
-    auto probe = [&](int mid, double &db) -> int {
-        int32_t qm[32];
-        QMatrix q;
-        quality_q(mid, qm, q);
-        if (int r = forward420(p, q, s)) return r;
-        if (int r = inverse420(p, p->coefs, q, s)) return r;
-        HIP_TRY(c, launch_clear_sums(p->measure, 7, s));
-        HIP_TRY(c, launch_merge420(p->recon, p->recon + p->y_bytes(), p->width, p->height, const_cast<uint8_t *>(d_pixels), s, p->measure));
-        unsigned long long m[7];
-        HIP_TRY(c, hipMemcpyAsync(m, p->measure, sizeof(m), hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
-        db = distortion_psnr(m, 3);
-        return FRI_HIP_OK;
-    };
-    return search_at_least(target_db, HUGE_VAL, probe, quality, psnr_db);
+    return search_dev<Search::Psnr, Search420>(__func__, p, d_pixels, target_db, quality, psnr_db, stream);
 }
 
 int fri_hip_search_quality420(fri_hip_plan420 *p, const uint8_t *pixels, double target_db, int32_t *quality, double *psnr_db) {
-    if (!p || !pixels || !quality || !psnr_db || !(target_db > 0)) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    if (int rc = need_device(p)) return rc;
-    if (int rc = stage_pixels(p->ctx, p->rgb, pixels, 3 * p->y_bytes())) return rc;
-    return fri_hip_search_quality420_dev(p, p->rgb, target_db, quality, psnr_db, nullptr);
+    return search_host<Search::Psnr, Search420>(fri_hip_search_quality420_dev, p, pixels, target_db, quality, psnr_db);
 }
 
 int fri_hip_search_quality_ssim420_dev(fri_hip_plan420 *p, const uint8_t *d_pixels, double target, int32_t *quality, double *ssim, void *stream) {
-    if (!p || !d_pixels || !quality || !ssim || !(target > 0 && target <= 1)) return FRI_HIP_ERR_INVALID_ARGUMENT; // (NaN fails both)
-    if (int rc = ssim_shape(p->luma.get())) return rc;
-    if (int rc = need_device(p)) return rc;
-    const hipStream_t s = (hipStream_t)stream;
-    if (int rc = refuse_capture(p->luma.get(), s, "fri_hip_search_quality_ssim420_dev reads every probe back: it cannot be captured into a HIP graph")) return rc;
-    fri_hip_ctx *c = p->ctx;
-    HIP_TRY(c, hipSetDevice(c->device));
-    int rc;
-    if ((rc = grow(c, p->planes, p->plane_bytes())) || (rc = grow(c, p->recon, p->plane_bytes())) || (rc = grow(c, p->coefs, p->y_coefs() + 2 * p->c_coefs())) ||
-        (rc = grow(c, p->recon_rgb, 3 * p->y_bytes())) || (rc = grow(c, p->measure, 7)))
-        return rc;
-    HIP_TRY(c, launch_split420(d_pixels, p->width, p->height, p->planes, p->planes + p->y_bytes(), s));
-    auto probe = [&](int mid, double &v) -> int {
-        int32_t qm[32];
-        QMatrix q;
-        quality_q(mid, qm, q);
-        if (int r = forward420(p, q, s)) return r;
-        if (int r = inverse420(p, p->coefs, q, s)) return r;
-        HIP_TRY(c, launch_merge420(p->recon, p->recon + p->y_bytes(), p->width, p->height, p->recon_rgb, s));
-        HIP_TRY(c, hipMemsetAsync(p->measure, 0, 4 * sizeof(uint64_t), s));
-        HIP_TRY(c, launch_ssim(1, d_pixels, p->recon_rgb, 0, p->width, p->height, 3, p->measure, s));
-        unsigned long long m[4];
-        HIP_TRY(c, hipMemcpyAsync(m, p->measure, sizeof(m), hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
-        v = ssim_of(m, 3);
-        return FRI_HIP_OK;
-    };
-    return search_at_least(target, 1.0, probe, quality, ssim);
+    return search_dev<Search::Ssim, Search420>(__func__, p, d_pixels, target, quality, ssim, stream);
 }
 
 int fri_hip_search_quality_ssim420(fri_hip_plan420 *p, const uint8_t *pixels, double target, int32_t *quality, double *ssim) {
-    if (!p || !pixels || !quality || !ssim || !(target > 0 && target <= 1)) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    if (int rc = ssim_shape(p->luma.get())) return rc;
-    if (int rc = need_device(p)) return rc;
-    if (int rc = stage_pixels(p->ctx, p->rgb, pixels, 3 * p->y_bytes())) return rc;
-    return fri_hip_search_quality_ssim420_dev(p, p->rgb, target, quality, ssim, nullptr);
+    return search_host<Search::Ssim, Search420>(fri_hip_search_quality_ssim420_dev, p, pixels, target, quality, ssim);
 }
 
 int fri_hip_search_quality_for_size420_dev(fri_hip_plan420 *p, const uint8_t *d_pixels, uint64_t max_bytes, int32_t *quality, uint64_t *est_bytes, void *stream) {
-    if (!p || !d_pixels || !quality || !est_bytes || max_bytes == 0) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    if (int rc = need_device(p)) return rc;
-    const hipStream_t s = (hipStream_t)stream;
-    if (int rc = refuse_capture(p->luma.get(), s, "fri_hip_search_quality_for_size420_dev reads every probe back: it cannot be captured into a HIP graph")) return rc;
-    fri_hip_ctx *c = p->ctx;
-    HIP_TRY(c, hipSetDevice(c->device));
-    int rc;
-    if ((rc = grow(c, p->planes, p->plane_bytes())) || (rc = grow(c, p->coefs, p->y_coefs() + 2 * p->c_coefs())) || (rc = grow(c, p->hist, 3 * 10 * 1024)) ||
-        (rc = grow(c, p->counts, 6)) || (rc = grow(c, p->params, 3 * 36)) || (rc = grow(c, p->measure, 7)))
-        return rc;
-    HIP_TRY(c, launch_split420(d_pixels, p->width, p->height, p->planes, p->planes + p->y_bytes(), s));
-    uint64_t *oob = reinterpret_cast<uint64_t *>(p->counts.get());
-    // a probe: K1, the device-side fit and K2 on both plans at quality q (the histograms of fri_hip_encode_image420_symbols), then the rate kernel over the three
-    // histograms as one C = 3 image
-    auto probe = [&](int quality_, uint64_t &est) -> int {
-        int32_t qm[32];
-        fri_hip_quality_matrix(quality_, qm);
-        if (int r = fri_hip_encode_image_batch_dev(p->luma.get(), 1, p->planes, 0, qm, 1, p->params, p->coefs, 0, nullptr, nullptr, 0, p->hist, oob, nullptr, stream)) return r;
-        if (int r = fri_hip_encode_image_batch_dev(p->chroma.get(), 2, p->planes + p->y_bytes(), p->c_bytes(), qm, 1, p->params + 36, p->coefs + p->y_coefs(), p->c_coefs(), nullptr,
-                                                   nullptr, 0, p->hist + 10 * 1024, oob + 1, nullptr, stream))
-            return r;
-        HIP_TRY(c, launch_rate_estimate(1, 3, p->hist, p->counts, p->luma->laplace, p->measure, nullptr, kRateLayout, s));
-        HIP_TRY(c, hipMemcpyAsync(&est, p->measure, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
-        return FRI_HIP_OK;
-    };
-    return search_at_most<FRI_HIP_ERR_OUT_OF_RANGE>(max_bytes, 100, probe, quality, est_bytes); // (a 4:2:0 file has a quality of 1..99)
+    return search_dev<Search::Size, Search420>(__func__, p, d_pixels, max_bytes, quality, est_bytes, stream);
 }
 
 int fri_hip_search_quality_for_size420(fri_hip_plan420 *p, const uint8_t *pixels, uint64_t max_bytes, int32_t *quality, uint64_t *est_bytes) {
-    if (!p || !pixels || !quality || !est_bytes || max_bytes == 0) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    if (int rc = need_device(p)) return rc;
-    if (int rc = stage_pixels(p->ctx, p->rgb, pixels, 3 * p->y_bytes())) return rc;
-    return fri_hip_search_quality_for_size420_dev(p, p->rgb, max_bytes, quality, est_bytes, nullptr);
+    return search_host<Search::Size, Search420>(fri_hip_search_quality_for_size420_dev, p, pixels, max_bytes, quality, est_bytes);
 }
 
 } // extern "C"

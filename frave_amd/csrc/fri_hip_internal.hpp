@@ -1,5 +1,6 @@
 // fri_hip_internal.hpp -- what the sources of the C ABI share (fri_hip.cpp and one fri_hip_<kind>.cpp per further plan kind): the context and the ordinary plan,
-// the owners of the library's HIP resources, and the small helpers every entry point is written with. Private to libfri_hip.so: the types a caller sees as opaque
+// the owners of the library's HIP resources, and the small helpers every entry point is written with. Two headers build on it: search_scaffold.hpp (what the
+// quality searches of all kinds share) and tiled_common.hpp (what the two tiled kinds share). Private to libfri_hip.so: the types a caller sees as opaque
 // (include/fri_hip.h) are global, everything else lives in fri::host, and -fvisibility=hidden keeps all of it out of the dynamic symbol table.
 #pragma once
 #include "fri_hip.h"
@@ -299,6 +300,17 @@ inline int read_back_plane_results(fri_hip_ctx *c, size_t planes, const float *d
         *fit_out_of_range = *fit_out_of_range || counts[planes + k];
     }
     return FRI_HIP_OK;
+}
+
+// The tail of the host forms of the symbol chains (fri_hip_encode_image420_symbols, fri_hip_encode_image_tiled*_symbols): the streams and the histograms of all
+// planes down, then read_back_plane_results; FRI_HIP_ERR_OUT_OF_RANGE when the fit clamped anything.
+inline int read_back_symbols(fri_hip_ctx *c, size_t planes, size_t n_symbols, const uint16_t *d_symbols, const uint32_t *d_hist, const float *d_params,
+                             const unsigned long long *d_counts, uint16_t *symbols, uint32_t *hist, float *value_params, float *width_params, uint64_t *n_out_of_alphabet) {
+    HIP_TRY(c, hipMemcpy(symbols, d_symbols, n_symbols * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(hist, d_hist, planes * 10 * 1024 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    bool out_of_range = false;
+    if (int rc = read_back_plane_results(c, planes, d_params, d_counts, value_params, width_params, n_out_of_alphabet, &out_of_range)) return rc;
+    return out_of_range ? FRI_HIP_ERR_OUT_OF_RANGE : FRI_HIP_OK;
 }
 
 // K11's limits on a batch of planes (fri_hip_rans_*; fri_hip_encode_image_tiled_coded checks them before it stages anything)

@@ -1,11 +1,9 @@
 // fri_hip_tiled420.cpp -- the tiled 4:2:0 plan kind of the C ABI (fri_hip_plan_tiled420: include/fri_hip.h): the plan and its grid, the fused split and merge,
 // the encode chain and its coded form (K11), the image and region decodes, the measure, the size estimate and the quality searches. Host-side glue like
-// fri_hip.cpp, on two ordinary plans.
-#include "fri_hip_internal.hpp"
-
-#include <new>
-
-#include "quality_search.hpp"
+// fri_hip.cpp, on two ordinary plans. The grid, plan creation, the host size estimate and the coded route are tiled_common.hpp's, shared with fri_hip_tiled.cpp
+// (the coded route runs two batches here); the searches are Tiled420Search on search_scaffold.hpp.
+#include "search_scaffold.hpp"
+#include "tiled_common.hpp"
 
 using namespace fri;
 using namespace fri::host;
@@ -15,7 +13,8 @@ using namespace fri::host;
 // call on the plan shares. Every per-plane array is in plane order: the n luma planes, then Cb and Cr of tile 0, of tile 1, ...
 struct fri_hip_plan_tiled420 {
     fri_hip_ctx *ctx = nullptr;
-    uint32_t width = 0, height = 0, tile_w = 0, tile_h = 0, nx = 0, ny = 0, cw = 0, ch = 0;
+    TileGrid grid;
+    uint32_t cw = 0, ch = 0;
     std::unique_ptr<fri_hip_plan, PlanDelete> luma, chroma;
     Grown<uint8_t> raster;            // the host forms' pixels [H][W][3]
     Grown<uint8_t> y_tiles, c_tiles;  // the split's output, the merge's input: [n][tile_h][tile_w] and [n][2][ch][cw]
@@ -34,9 +33,9 @@ struct fri_hip_plan_tiled420 {
     Grown<uint32_t> rans_counts;      // ... n_words [3 n], then status [3 n][4], then models [3 n][10][4]
     Grown<uint16_t> rans_off;         // ... [3 n][10][1024]
     Grown<uint8_t> rans_scratch;      // ... and its scratch, the larger of the two batches'
-    size_t n_tiles() const { return (size_t)nx * ny; }
-    size_t raster_bytes() const { return (size_t)width * height * 3; }
-    size_t y_bytes() const { return (size_t)tile_w * tile_h; }
+    size_t n_tiles() const { return grid.n_tiles(); }
+    size_t raster_bytes() const { return (size_t)grid.width * grid.height * 3; }
+    size_t y_bytes() const { return (size_t)grid.tile_w * grid.tile_h; }
     size_t c_bytes() const { return (size_t)cw * ch; }
     size_t y_coefs() const { return luma->geo.centers.size() * kCell; }
     size_t c_coefs() const { return chroma->geo.centers.size() * kCell; }
@@ -52,21 +51,53 @@ int inverse_tiled420(fri_hip_plan_tiled420 *p, uint32_t n, const int32_t *d_coef
     return FRI_HIP_OK;
 }
 
-// What the PSNR and SSIM searches share: the image split once into p->y_tiles and p->c_tiles, and a probe that runs K1 on the luma plan over n planes and on the
-// chroma plan over 2 n planes into p->coefs, then K3 with the midpoint dequantiser into p->recon_y and p->recon_c, zeroed once before the first probe.
-struct Tiled420Probe {
+// the chain of fri_hip_encode_symbols_tiled420_dev behind its split: the two batches with quality_matrix(quality), outputs in plane order
+int encode_planes_tiled420(fri_hip_plan_tiled420 *p, const int32_t qm[32], int fit, float *d_params, uint16_t *d_symbols, uint32_t *d_hist, uint64_t *d_n_out_of_alphabet,
+                           uint64_t *d_fit_out_of_range, void *stream) {
+    const size_t n = p->n_tiles(), n_y = p->luma->geo.n_some, n_c = p->chroma->geo.n_some;
+    if (int rc = fri_hip_encode_symbols_batch_dev(p->luma.get(), (uint32_t)n, p->y_tiles, p->y_bytes(), qm, fit, d_params, nullptr, 0, nullptr, 0, d_symbols, n_y, d_hist,
+                                                  d_n_out_of_alphabet, d_fit_out_of_range, stream))
+        return rc;
+    return fri_hip_encode_symbols_batch_dev(p->chroma.get(), (uint32_t)(2 * n), p->c_tiles, p->c_bytes(), qm, fit, d_params + n * 36, nullptr, 0, nullptr, 0, d_symbols + n * n_y,
+                                            n_c, d_hist + n * 10 * 1024, d_n_out_of_alphabet + n, d_fit_out_of_range ? d_fit_out_of_range + n : nullptr, stream);
+}
+
+// The tiled 4:2:0 plan's part of the quality searches (search_scaffold.hpp): the image split once into p->y_tiles and p->c_tiles; a round trip is K1 on the luma
+// plan over n planes and on the chroma plan over 2 n planes into p->coefs, then K3 with the midpoint dequantiser into p->recon_y and p->recon_c, zeroed once
+// before the first probe.
+struct Tiled420Search {
     fri_hip_plan_tiled420 *p;
     hipStream_t s;
-    int begin(const uint8_t *d_pixels) {
+    unsigned long long *sums = nullptr;
+    uint8_t *recon_raster = nullptr;
+    const uint8_t *d_pixels = nullptr;
+    fri_hip_plan *inner() const { return p->luma.get(); }
+    uint32_t width() const { return p->grid.width; }
+    uint32_t height() const { return p->grid.height; }
+    uint32_t channels() const { return 3; }
+    bool refused() const { return false; }
+    bool chain_ready() const { return p->luma->d_stream_order != nullptr && p->chroma->d_stream_order != nullptr; }
+    Grown<uint8_t> &staging() const { return p->raster; }
+    int size_top() const { return 100; } // a 4:2:0 file has a quality of 1..99
+    int begin(Search what, const uint8_t *pixels) {
         fri_hip_ctx *c = p->ctx;
-        const size_t n = p->n_tiles();
+        const TileGrid &g = p->grid;
+        const size_t n = p->n_tiles(), planes = 3 * n, n_sym = n * (p->luma->geo.n_some + 2 * p->chroma->geo.n_some);
         int rc;
-        if ((rc = grow(c, p->y_tiles, n * p->y_bytes())) || (rc = grow(c, p->c_tiles, 2 * n * p->c_bytes())) || (rc = grow(c, p->recon_y, n * p->y_bytes())) ||
-            (rc = grow(c, p->recon_c, 2 * n * p->c_bytes())) || (rc = grow(c, p->coefs, n * (p->y_coefs() + 2 * p->c_coefs()))) || (rc = grow(c, p->measure, 7)))
+        if ((rc = grow(c, p->y_tiles, n * p->y_bytes())) || (rc = grow(c, p->c_tiles, 2 * n * p->c_bytes())) || (rc = grow(c, p->measure, 7))) return rc;
+        if (what != Search::Size && ((rc = grow(c, p->recon_y, n * p->y_bytes())) || (rc = grow(c, p->recon_c, 2 * n * p->c_bytes())) ||
+                                     (rc = grow(c, p->coefs, n * (p->y_coefs() + 2 * p->c_coefs())))))
             return rc;
-        HIP_TRY(c, launch_split_tiles420(d_pixels, p->width, p->height, p->tile_w, p->tile_h, p->y_tiles, p->c_tiles, s));
-        HIP_TRY(c, hipMemsetAsync(p->recon_y, 0, n * p->y_bytes(), s));
-        HIP_TRY(c, hipMemsetAsync(p->recon_c, 0, 2 * n * p->c_bytes(), s));
+        if (what == Search::Ssim && (rc = grow(c, p->recon_raster, p->raster_bytes()))) return rc;
+        if (what == Search::Size && ((rc = grow(c, p->symbols, std::max<size_t>(n_sym, 1))) || (rc = grow(c, p->hist, planes * 10 * 1024)) || (rc = grow(c, p->counts, 2 * planes)) ||
+                                     (rc = grow(c, p->params, planes * 36)) || (rc = grow(c, p->rate, n))))
+            return rc;
+        d_pixels = pixels, sums = p->measure, recon_raster = p->recon_raster;
+        HIP_TRY(c, launch_split_tiles420(d_pixels, g.width, g.height, g.tile_w, g.tile_h, p->y_tiles, p->c_tiles, s));
+        if (what != Search::Size) {
+            HIP_TRY(c, hipMemsetAsync(p->recon_y, 0, n * p->y_bytes(), s));
+            HIP_TRY(c, hipMemsetAsync(p->recon_c, 0, 2 * n * p->c_bytes(), s));
+        }
         return FRI_HIP_OK;
     }
     int round_trip(int quality) {
@@ -79,92 +110,66 @@ struct Tiled420Probe {
         HIP_TRY(p->ctx, launch_fwd_transform_quant(p->chroma->dev, 2 * n, p->c_tiles, p->c_bytes(), chroma_coefs, p->c_coefs(), q, s));
         return inverse_tiled420(p, n, p->coefs, q, p->recon_y, p->recon_c, s);
     }
+    int measure() {
+        const TileGrid &g = p->grid;
+        HIP_TRY(p->ctx, launch_clear_sums(sums, 7, s));
+        HIP_TRY(p->ctx, launch_measure_tiles420(p->recon_y, p->recon_c, g.width, g.height, g.tile_w, g.tile_h, d_pixels, sums, s));
+        return FRI_HIP_OK;
+    }
+    int raster() {
+        const TileGrid &g = p->grid;
+        HIP_TRY(p->ctx, launch_merge_tiles420_region(p->recon_y, p->recon_c, g.width, g.height, g.tile_w, g.tile_h, 0, 0, g.width, g.height, recon_raster, s));
+        return FRI_HIP_OK;
+    }
+    // the chain of fri_hip_encode_image_tiled420_symbols at `quality` on the planes cut in begin (K1, the device-side fit, K2 on both plans; the same
+    // histograms), then the plane-order estimate
+    int estimate(int quality) {
+        uint64_t *oob = reinterpret_cast<uint64_t *>(p->counts.get());
+        int32_t qm[32];
+        fri_hip_quality_matrix(quality, qm);
+        if (int r = encode_planes_tiled420(p, qm, 1, p->params, p->symbols, p->hist, oob, nullptr, s)) return r;
+        return fri_hip_estimate_size_tiled420_dev(p, p->hist, oob, (uint64_t *)sums, (uint64_t *)p->rate.get(), nullptr, s);
+    }
 };
-
-// the chain of fri_hip_encode_symbols_tiled420_dev behind its split: the two batches with quality_matrix(quality), outputs in plane order
-int encode_planes_tiled420(fri_hip_plan_tiled420 *p, const int32_t qm[32], int fit, float *d_params, uint16_t *d_symbols, uint32_t *d_hist, uint64_t *d_n_out_of_alphabet,
-                           uint64_t *d_fit_out_of_range, void *stream) {
-    const size_t n = p->n_tiles(), n_y = p->luma->geo.n_some, n_c = p->chroma->geo.n_some;
-    if (int rc = fri_hip_encode_symbols_batch_dev(p->luma.get(), (uint32_t)n, p->y_tiles, p->y_bytes(), qm, fit, d_params, nullptr, 0, nullptr, 0, d_symbols, n_y, d_hist,
-                                                  d_n_out_of_alphabet, d_fit_out_of_range, stream))
-        return rc;
-    return fri_hip_encode_symbols_batch_dev(p->chroma.get(), (uint32_t)(2 * n), p->c_tiles, p->c_bytes(), qm, fit, d_params + n * 36, nullptr, 0, nullptr, 0, d_symbols + n * n_y,
-                                            n_c, d_hist + n * 10 * 1024, d_n_out_of_alphabet + n, d_fit_out_of_range ? d_fit_out_of_range + n : nullptr, stream);
-}
 
 } // namespace
 
 extern "C" {
 
 int fri_hip_tile_shape420(uint32_t width, uint32_t height, uint32_t target, uint32_t *tile_w, uint32_t *tile_h) {
-    if (!width || !height || !target || !tile_w || !tile_h) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    auto first = [&](uint32_t size) { // ceil(size / max(1, round(size / target)))
-        const uint64_t parts = std::max<uint64_t>(1, (2ull * size + target) / (2ull * target));
-        return (uint32_t)((size + parts - 1) / parts);
-    };
-    auto whole = [](uint64_t w, uint64_t h) { // the C = 1 lattice of w x h owns every pixel
-        Geometry g;
-        return build_geometry((uint32_t)w, (uint32_t)h, 1, TilingParams{}, g).empty() && g.n_valid_leaves == w * h;
-    };
-    const uint32_t w0 = first(width), h0 = first(height);
-    for (uint32_t s = 0; s <= 64; s++)
-        for (uint32_t a = 0; a <= s; a++) {
-            const uint64_t w = (uint64_t)w0 + a, h = (uint64_t)h0 + (s - a);
-            if (w > 0xFFFFFFFFull || h > 0xFFFFFFFFull) continue;
-            if (whole(w, h) && whole((w + 1) / 2, (h + 1) / 2)) return *tile_w = (uint32_t)w, *tile_h = (uint32_t)h, FRI_HIP_OK;
-        }
-    return FRI_HIP_ERR_OUT_OF_RANGE;
+    return first_fit_tile_shape(width, height, target, tile_w, tile_h, [](uint64_t w, uint64_t h) { return lattice_is_whole(w, h) && lattice_is_whole((w + 1) / 2, (h + 1) / 2); });
 }
 
 int fri_hip_plan_tiled420_create(fri_hip_ctx *ctx, uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t flags, fri_hip_plan_tiled420 **out) {
-    if (!out) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    *out = nullptr;
-    if (!width || !height || !tile_w || !tile_h || (flags & ~(uint32_t)FRI_HIP_TILED_ALLOW_HOLES)) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    const uint64_t nx = ((uint64_t)width + tile_w - 1) / tile_w, ny = ((uint64_t)height + tile_h - 1) / tile_h;
-    if (2 * nx * ny > 65535u) return FRI_HIP_ERR_INVALID_ARGUMENT; // one batch launch of the chroma plan takes both planes of all tiles
-    fri_hip_plan_tiled420 *p = new (std::nothrow) fri_hip_plan_tiled420;
-    if (!p) return FRI_HIP_ERR_OUT_OF_MEMORY;
-    p->ctx = ctx, p->width = width, p->height = height, p->tile_w = tile_w, p->tile_h = tile_h, p->nx = (uint32_t)nx, p->ny = (uint32_t)ny;
-    p->cw = (uint32_t)(((uint64_t)tile_w + 1) / 2), p->ch = (uint32_t)(((uint64_t)tile_h + 1) / 2);
-    fri_hip_plan *inner = nullptr;
-    int rc = fri_hip_plan_create(ctx, tile_w, tile_h, 1, &inner);
-    p->luma.reset(inner);
-    if (!rc) {
-        rc = fri_hip_plan_create(ctx, p->cw, p->ch, 1, &inner);
-        p->chroma.reset(inner);
-    }
-    // a pixel or a chroma sample no retained cell owns would be a defect in the middle of the picture
-    if (!rc && !(flags & FRI_HIP_TILED_ALLOW_HOLES) &&
-        (p->luma->geo.n_valid_leaves != (uint64_t)tile_w * tile_h || p->chroma->geo.n_valid_leaves != (uint64_t)p->cw * p->ch))
-        rc = FRI_HIP_ERR_INVALID_ARGUMENT;
-    if (rc) { // a plan that fails part-way goes with what it has
-        fri_hip_plan_tiled420_destroy(p);
+    // (2 planes per tile: one batch launch of the chroma plan takes both planes of all tiles)
+    return create_tiled_plan(ctx, width, height, tile_w, tile_h, flags, 2, out, [&](fri_hip_plan_tiled420 *p, bool whole) {
+        p->cw = (uint32_t)(((uint64_t)tile_w + 1) / 2), p->ch = (uint32_t)(((uint64_t)tile_h + 1) / 2);
+        fri_hip_plan *inner = nullptr;
+        int rc = fri_hip_plan_create(ctx, tile_w, tile_h, 1, &inner);
+        p->luma.reset(inner);
+        if (!rc) {
+            rc = fri_hip_plan_create(ctx, p->cw, p->ch, 1, &inner);
+            p->chroma.reset(inner);
+        }
+        if (!rc && whole && (p->luma->geo.n_valid_leaves != (uint64_t)tile_w * tile_h || p->chroma->geo.n_valid_leaves != (uint64_t)p->cw * p->ch))
+            rc = FRI_HIP_ERR_INVALID_ARGUMENT;
         return rc;
-    }
-    *out = p;
-    return FRI_HIP_OK;
+    });
 }
 
-int fri_hip_plan_tiled420_destroy(fri_hip_plan_tiled420 *p) {
-    if (p && p->ctx) (void)hipSetDevice(p->ctx->device); // the buffers and the inner plans free their resources on the plan's device
-    delete p;
-    return FRI_HIP_OK;
-}
+int fri_hip_plan_tiled420_destroy(fri_hip_plan_tiled420 *p) { return destroy_tiled_plan(p); }
 
 fri_hip_plan *fri_hip_plan_tiled420_luma(fri_hip_plan_tiled420 *p) { return p ? p->luma.get() : nullptr; }
 fri_hip_plan *fri_hip_plan_tiled420_chroma(fri_hip_plan_tiled420 *p) { return p ? p->chroma.get() : nullptr; }
 
 int fri_hip_plan_tiled420_grid(const fri_hip_plan_tiled420 *p, uint32_t out[4]) {
     if (!p || !out) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    out[0] = p->nx, out[1] = p->ny, out[2] = p->tile_w, out[3] = p->tile_h;
+    p->grid.shape(out);
     return FRI_HIP_OK;
 }
 
 int fri_hip_plan_tiled420_region(const fri_hip_plan_tiled420 *p, uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint32_t out[4]) {
-    if (!p || !out || !w || !h || (uint64_t)x + w > p->width || (uint64_t)y + h > p->height) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    out[0] = x / p->tile_w, out[1] = y / p->tile_h;
-    out[2] = (uint32_t)(((uint64_t)x + w - 1) / p->tile_w) - out[0] + 1, out[3] = (uint32_t)(((uint64_t)y + h - 1) / p->tile_h) - out[1] + 1;
-    return FRI_HIP_OK;
+    return p ? p->grid.region(x, y, w, h, out) : FRI_HIP_ERR_INVALID_ARGUMENT;
 }
 
 int fri_hip_plan_tiled420_buffer_tiles(const fri_hip_plan_tiled420 *p, uint64_t out[2]) {
@@ -176,7 +181,7 @@ int fri_hip_plan_tiled420_buffer_tiles(const fri_hip_plan_tiled420 *p, uint64_t 
 int fri_hip_split_tiles420_dev(fri_hip_plan_tiled420 *p, const uint8_t *d_rgb, uint8_t *d_y_tiles, uint8_t *d_c_tiles, void *stream) {
     if (int rc = need_device(p)) return rc;
     if (!d_rgb || !d_y_tiles || !d_c_tiles) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    HIP_TRY(p->ctx, launch_split_tiles420(d_rgb, p->width, p->height, p->tile_w, p->tile_h, d_y_tiles, d_c_tiles, (hipStream_t)stream));
+    HIP_TRY(p->ctx, launch_split_tiles420(d_rgb, p->grid.width, p->grid.height, p->grid.tile_w, p->grid.tile_h, d_y_tiles, d_c_tiles, (hipStream_t)stream));
     return FRI_HIP_OK;
 }
 
@@ -185,13 +190,13 @@ int fri_hip_merge_tiles420_region_dev(fri_hip_plan_tiled420 *p, const uint8_t *d
     uint32_t range[4];
     if (!p || !d_y_tiles || !d_c_tiles || !d_region || fri_hip_plan_tiled420_region(p, x, y, w, h, range)) return FRI_HIP_ERR_INVALID_ARGUMENT;
     if (int rc = need_device(p)) return rc;
-    HIP_TRY(p->ctx, launch_merge_tiles420_region(d_y_tiles, d_c_tiles, p->width, p->height, p->tile_w, p->tile_h, x, y, w, h, d_region, (hipStream_t)stream));
+    HIP_TRY(p->ctx, launch_merge_tiles420_region(d_y_tiles, d_c_tiles, p->grid.width, p->grid.height, p->grid.tile_w, p->grid.tile_h, x, y, w, h, d_region, (hipStream_t)stream));
     return FRI_HIP_OK;
 }
 
 int fri_hip_merge_tiles420_dev(fri_hip_plan_tiled420 *p, const uint8_t *d_y_tiles, const uint8_t *d_c_tiles, uint8_t *d_rgb, void *stream) {
     if (!p) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    return fri_hip_merge_tiles420_region_dev(p, d_y_tiles, d_c_tiles, 0, 0, p->width, p->height, d_rgb, stream);
+    return fri_hip_merge_tiles420_region_dev(p, d_y_tiles, d_c_tiles, 0, 0, p->grid.width, p->grid.height, d_rgb, stream);
 }
 
 int fri_hip_encode_symbols_tiled420_dev(fri_hip_plan_tiled420 *p, const uint8_t *d_rgb, int quality, int fit, float *d_params, uint16_t *d_symbols, uint32_t *d_hist,
@@ -208,7 +213,7 @@ int fri_hip_encode_symbols_tiled420_dev(fri_hip_plan_tiled420 *p, const uint8_t 
     const size_t n = p->n_tiles();
     int rc;
     if ((rc = grow(c, p->y_tiles, n * p->y_bytes())) || (rc = grow(c, p->c_tiles, 2 * n * p->c_bytes()))) return rc;
-    HIP_TRY(c, launch_split_tiles420(d_rgb, p->width, p->height, p->tile_w, p->tile_h, p->y_tiles, p->c_tiles, s));
+    HIP_TRY(c, launch_split_tiles420(d_rgb, p->grid.width, p->grid.height, p->grid.tile_w, p->grid.tile_h, p->y_tiles, p->c_tiles, s));
     return encode_planes_tiled420(p, qm, fit, d_params, d_symbols, d_hist, d_n_out_of_alphabet, d_fit_out_of_range, stream);
 }
 
@@ -226,11 +231,7 @@ int fri_hip_encode_image_tiled420_symbols(fri_hip_plan_tiled420 *p, const uint8_
     HIP_TRY(c, hipMemcpy(p->raster, pixels, p->raster_bytes(), hipMemcpyHostToDevice));
     uint64_t *oob = reinterpret_cast<uint64_t *>(p->counts.get());
     if ((rc = fri_hip_encode_symbols_tiled420_dev(p, p->raster, quality, 1, p->params, p->symbols, p->hist, oob, oob + planes, nullptr))) return rc;
-    HIP_TRY(c, hipMemcpy(symbols, p->symbols, n_sym * sizeof(uint16_t), hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(hist, p->hist, planes * 10 * 1024 * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    bool out_of_range = false;
-    if ((rc = read_back_plane_results(c, planes, p->params, p->counts, value_params, width_params, n_out_of_alphabet, &out_of_range))) return rc;
-    return out_of_range ? FRI_HIP_ERR_OUT_OF_RANGE : FRI_HIP_OK;
+    return read_back_symbols(c, planes, n_sym, p->symbols, p->hist, p->params, p->counts, symbols, hist, value_params, width_params, n_out_of_alphabet);
 }
 
 int fri_hip_decode_region_tiled420_dev(fri_hip_plan_tiled420 *p, const int32_t *d_coefs, int quality, uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint8_t *d_region,
@@ -248,7 +249,7 @@ int fri_hip_decode_region_tiled420_dev(fri_hip_plan_tiled420 *p, const int32_t *
     int rc;
     if ((rc = grow(c, p->y_tiles, n * p->y_bytes())) || (rc = grow(c, p->c_tiles, 2 * n * p->c_bytes()))) return rc;
     if ((rc = inverse_tiled420(p, (uint32_t)n, d_coefs, q, p->y_tiles, p->c_tiles, s))) return rc;
-    HIP_TRY(c, launch_merge_tiles420_region(p->y_tiles, p->c_tiles, p->width, p->height, p->tile_w, p->tile_h, x, y, w, h, d_region, s));
+    HIP_TRY(c, launch_merge_tiles420_region(p->y_tiles, p->c_tiles, p->grid.width, p->grid.height, p->grid.tile_w, p->grid.tile_h, x, y, w, h, d_region, s));
     return FRI_HIP_OK;
 }
 
@@ -269,7 +270,7 @@ int fri_hip_decode_region_tiled420(fri_hip_plan_tiled420 *p, const int32_t *coef
 
 int fri_hip_decode_image_tiled420(fri_hip_plan_tiled420 *p, const int32_t *coefs, int quality, uint8_t *pixels) {
     if (!p) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    return fri_hip_decode_region_tiled420(p, coefs, quality, 0, 0, p->width, p->height, pixels);
+    return fri_hip_decode_region_tiled420(p, coefs, quality, 0, 0, p->grid.width, p->grid.height, pixels);
 }
 
 /* ---- the measure, the size estimate and the searches over subsampled tiles ---- */
@@ -279,7 +280,7 @@ int fri_hip_measure_distortion_tiled420_dev(fri_hip_plan_tiled420 *p, const uint
     if (int rc = need_device(p)) return rc;
     auto *out = reinterpret_cast<unsigned long long *>(d_out);
     HIP_TRY(p->ctx, launch_clear_sums(out, 7, (hipStream_t)stream));
-    HIP_TRY(p->ctx, launch_measure_tiles420(d_y_tiles, d_c_tiles, p->width, p->height, p->tile_w, p->tile_h, d_reference_rgb, out, (hipStream_t)stream));
+    HIP_TRY(p->ctx, launch_measure_tiles420(d_y_tiles, d_c_tiles, p->grid.width, p->grid.height, p->grid.tile_w, p->grid.tile_h, d_reference_rgb, out, (hipStream_t)stream));
     return FRI_HIP_OK;
 }
 
@@ -295,120 +296,32 @@ int fri_hip_estimate_size_tiled420_dev(fri_hip_plan_tiled420 *p, const uint32_t 
 }
 
 int fri_hip_estimate_size_tiled420(fri_hip_plan_tiled420 *p, const uint32_t *hist, const uint64_t *n_out_of_alphabet, uint64_t *file_bytes, uint64_t *tile_bytes) {
-    if (!p || !hist || !file_bytes) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    if (int rc = need_device(p)) return rc;
-    fri_hip_ctx *c = p->ctx;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t n = p->n_tiles(), planes = 3 * n;
-    int rc;
-    if ((rc = grow(c, p->hist, planes * 10 * 1024)) || (rc = grow(c, p->oob_in, planes)) || (rc = grow(c, p->rate, n)) || (rc = grow(c, p->measure, 7))) return rc;
-    HIP_TRY(c, hipMemcpy(p->hist, hist, planes * 10 * 1024 * sizeof(uint32_t), hipMemcpyHostToDevice));
-    if (n_out_of_alphabet) HIP_TRY(c, hipMemcpy(p->oob_in, n_out_of_alphabet, planes * sizeof(uint64_t), hipMemcpyHostToDevice));
-    if ((rc = fri_hip_estimate_size_tiled420_dev(p, p->hist, n_out_of_alphabet ? (const uint64_t *)p->oob_in.get() : nullptr, (uint64_t *)p->measure.get(),
-                                                 (uint64_t *)p->rate.get(), nullptr, nullptr)))
-        return rc;
-    HIP_TRY(c, hipMemcpy(file_bytes, p->measure, sizeof(uint64_t), hipMemcpyDeviceToHost));
-    if (tile_bytes) HIP_TRY(c, hipMemcpy(tile_bytes, p->rate, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    return FRI_HIP_OK;
+    if (!p) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    return estimate_size_tiled_host(p, 3 * p->n_tiles(), 7, hist, n_out_of_alphabet, file_bytes, tile_bytes, fri_hip_estimate_size_tiled420_dev);
 }
 
 int fri_hip_search_quality_tiled420_dev(fri_hip_plan_tiled420 *p, const uint8_t *d_pixels, double target_db, int32_t *quality, double *psnr_db, void *stream) {
-    if (!p || !d_pixels || !quality || !psnr_db || !(target_db > 0)) return FRI_HIP_ERR_INVALID_ARGUMENT; // (!(x > 0): NaN too)
-    if (int rc = need_device(p)) return rc;
-    const hipStream_t s = (hipStream_t)stream;
-    if (int rc = refuse_capture(p->luma.get(), s, "fri_hip_search_quality_tiled420_dev reads every probe back: it cannot be captured into a HIP graph")) return rc;
-    fri_hip_ctx *c = p->ctx;
-    HIP_TRY(c, hipSetDevice(c->device));
-    Tiled420Probe tiles{p, s};
-    if (int rc = tiles.begin(d_pixels)) return rc;
-    auto probe = [&](int mid, double &db) -> int {
-        if (int r = tiles.round_trip(mid)) return r;
-        HIP_TRY(c, launch_clear_sums(p->measure, 7, s));
-        HIP_TRY(c, launch_measure_tiles420(p->recon_y, p->recon_c, p->width, p->height, p->tile_w, p->tile_h, d_pixels, p->measure, s));
-        unsigned long long m[7];
-        HIP_TRY(c, hipMemcpyAsync(m, p->measure, sizeof(m), hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
-        db = distortion_psnr(m, 3);
-        return FRI_HIP_OK;
-    };
-    return search_at_least(target_db, HUGE_VAL, probe, quality, psnr_db); // (100 is never probed: a 4:2:0 file has a quality of 1..99)
+    return search_dev<Search::Psnr, Tiled420Search>(__func__, p, d_pixels, target_db, quality, psnr_db, stream);
 }
 
 int fri_hip_search_quality_tiled420(fri_hip_plan_tiled420 *p, const uint8_t *pixels, double target_db, int32_t *quality, double *psnr_db) {
-    if (!p || !pixels || !quality || !psnr_db || !(target_db > 0)) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    if (int rc = need_device(p)) return rc;
-    if (int rc = stage_pixels(p->ctx, p->raster, pixels, p->raster_bytes())) return rc;
-    return fri_hip_search_quality_tiled420_dev(p, p->raster, target_db, quality, psnr_db, nullptr);
+    return search_host<Search::Psnr, Tiled420Search>(fri_hip_search_quality_tiled420_dev, p, pixels, target_db, quality, psnr_db);
 }
 
 int fri_hip_search_quality_ssim_tiled420_dev(fri_hip_plan_tiled420 *p, const uint8_t *d_pixels, double target, int32_t *quality, double *ssim, void *stream) {
-    if (!p || !d_pixels || !quality || !ssim || !(target > 0 && target <= 1)) return FRI_HIP_ERR_INVALID_ARGUMENT; // (NaN fails both)
-    if (int rc = ssim_shape(p->width, p->height)) return rc;
-    if (int rc = need_device(p)) return rc;
-    const hipStream_t s = (hipStream_t)stream;
-    if (int rc = refuse_capture(p->luma.get(), s, "fri_hip_search_quality_ssim_tiled420_dev reads every probe back: it cannot be captured into a HIP graph")) return rc;
-    fri_hip_ctx *c = p->ctx;
-    HIP_TRY(c, hipSetDevice(c->device));
-    Tiled420Probe tiles{p, s};
-    int rc;
-    if ((rc = grow(c, p->recon_raster, p->raster_bytes())) || (rc = tiles.begin(d_pixels))) return rc;
-    auto probe = [&](int mid, double &v) -> int {
-        if (int r = tiles.round_trip(mid)) return r;
-        HIP_TRY(c, launch_merge_tiles420_region(p->recon_y, p->recon_c, p->width, p->height, p->tile_w, p->tile_h, 0, 0, p->width, p->height, p->recon_raster, s));
-        HIP_TRY(c, hipMemsetAsync(p->measure, 0, 4 * sizeof(uint64_t), s));
-        HIP_TRY(c, launch_ssim(1, d_pixels, p->recon_raster, 0, p->width, p->height, 3, p->measure, s));
-        unsigned long long m[4];
-        HIP_TRY(c, hipMemcpyAsync(m, p->measure, sizeof(m), hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
-        v = ssim_of(m, 3);
-        return FRI_HIP_OK;
-    };
-    return search_at_least(target, 1.0, probe, quality, ssim);
+    return search_dev<Search::Ssim, Tiled420Search>(__func__, p, d_pixels, target, quality, ssim, stream);
 }
 
 int fri_hip_search_quality_ssim_tiled420(fri_hip_plan_tiled420 *p, const uint8_t *pixels, double target, int32_t *quality, double *ssim) {
-    if (!p || !pixels || !quality || !ssim || !(target > 0 && target <= 1)) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    if (int rc = ssim_shape(p->width, p->height)) return rc;
-    if (int rc = need_device(p)) return rc;
-    if (int rc = stage_pixels(p->ctx, p->raster, pixels, p->raster_bytes())) return rc;
-    return fri_hip_search_quality_ssim_tiled420_dev(p, p->raster, target, quality, ssim, nullptr);
+    return search_host<Search::Ssim, Tiled420Search>(fri_hip_search_quality_ssim_tiled420_dev, p, pixels, target, quality, ssim);
 }
 
 int fri_hip_search_quality_for_size_tiled420_dev(fri_hip_plan_tiled420 *p, const uint8_t *d_pixels, uint64_t max_bytes, int32_t *quality, uint64_t *est_bytes, void *stream) {
-    if (!p || !d_pixels || !quality || !est_bytes || max_bytes == 0) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    if (int rc = need_device(p)) return rc;
-    if (!p->luma->d_stream_order || !p->chroma->d_stream_order) return FRI_HIP_ERR_INVALID_ARGUMENT; // (the probes run the encode's chain, which needs it)
-    const hipStream_t s = (hipStream_t)stream;
-    if (int rc = refuse_capture(p->luma.get(), s, "fri_hip_search_quality_for_size_tiled420_dev reads every probe back: it cannot be captured into a HIP graph")) return rc;
-    fri_hip_ctx *c = p->ctx;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t n = p->n_tiles(), planes = 3 * n, n_sym = n * (p->luma->geo.n_some + 2 * p->chroma->geo.n_some);
-    int rc;
-    if ((rc = grow(c, p->y_tiles, n * p->y_bytes())) || (rc = grow(c, p->c_tiles, 2 * n * p->c_bytes())) || (rc = grow(c, p->symbols, std::max<size_t>(n_sym, 1))) ||
-        (rc = grow(c, p->hist, planes * 10 * 1024)) || (rc = grow(c, p->counts, 2 * planes)) || (rc = grow(c, p->params, planes * 36)) || (rc = grow(c, p->rate, n)) ||
-        (rc = grow(c, p->measure, 7)))
-        return rc;
-    HIP_TRY(c, launch_split_tiles420(d_pixels, p->width, p->height, p->tile_w, p->tile_h, p->y_tiles, p->c_tiles, s));
-    uint64_t *oob = reinterpret_cast<uint64_t *>(p->counts.get());
-    // a probe: the chain of fri_hip_encode_image_tiled420_symbols at quality q on the planes cut above (K1, the device-side fit, K2 on both plans; the same
-    // histograms), then the plane-order estimate
-    auto probe = [&](int q, uint64_t &est) -> int {
-        int32_t qm[32];
-        fri_hip_quality_matrix(q, qm);
-        if (int r = encode_planes_tiled420(p, qm, 1, p->params, p->symbols, p->hist, oob, nullptr, stream)) return r;
-        if (int r = fri_hip_estimate_size_tiled420_dev(p, p->hist, oob, (uint64_t *)p->measure.get(), (uint64_t *)p->rate.get(), nullptr, stream)) return r;
-        HIP_TRY(c, hipMemcpyAsync(&est, p->measure, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
-        return FRI_HIP_OK;
-    };
-    return search_at_most<FRI_HIP_ERR_OUT_OF_RANGE>(max_bytes, 100, probe, quality, est_bytes); // (a 4:2:0 file has a quality of 1..99)
+    return search_dev<Search::Size, Tiled420Search>(__func__, p, d_pixels, max_bytes, quality, est_bytes, stream);
 }
 
 int fri_hip_search_quality_for_size_tiled420(fri_hip_plan_tiled420 *p, const uint8_t *pixels, uint64_t max_bytes, int32_t *quality, uint64_t *est_bytes) {
-    if (!p || !pixels || !quality || !est_bytes || max_bytes == 0) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    if (int rc = need_device(p)) return rc;
-    if (int rc = stage_pixels(p->ctx, p->raster, pixels, p->raster_bytes())) return rc;
-    return fri_hip_search_quality_for_size_tiled420_dev(p, p->raster, max_bytes, quality, est_bytes, nullptr);
+    return search_host<Search::Size, Tiled420Search>(fri_hip_search_quality_for_size_tiled420_dev, p, pixels, max_bytes, quality, est_bytes);
 }
 
 /* ---- the coded form: K11 over the luma batch, then over the chroma batch ---- */
@@ -429,50 +342,11 @@ int fri_hip_encode_image_tiled420_coded(fri_hip_plan_tiled420 *p, const uint8_t 
     HIP_TRY(c, hipMemcpy(p->raster, pixels, p->raster_bytes(), hipMemcpyHostToDevice));
     uint64_t *oob = reinterpret_cast<uint64_t *>(p->counts.get());
     if ((rc = fri_hip_encode_symbols_tiled420_dev(p, p->raster, quality, 1, p->params, p->symbols, p->hist, oob, oob + planes, nullptr))) return rc;
-    // K11 per batch - n planes of n_y symbols, then 2 n planes of n_c - each into rows of its own with room for 8 bits per symbol; a batch with a plane that
-    // needs more makes the one second pass, with the hard bound: a step emits at most one word
-    uint32_t *d_n_words = p->rans_counts, *d_status = d_n_words + planes, *d_models = d_status + 4 * planes;
-    std::vector<uint32_t> counts(planes * 45);
-    size_t stride_y = 0, stride_c = 0;
-    auto code = [&](size_t first, size_t count, const uint16_t *d_symbols, size_t n_symbols, Grown<uint32_t> &d_words, size_t &stride) -> int {
-        const size_t bound = n_symbols + 20;
-        stride = std::min(bound, n_symbols / 4 + 20);
-        for (;;) {
-            if (int r = grow(c, d_words, count * stride)) return r;
-            if (int r = fri_hip_rans_encode_planes_dev(c, (uint32_t)count, d_symbols, n_symbols, n_symbols, p->hist + first * 10 * 1024, FRI_HIP_RANS_EMPTY_OK, d_words, stride,
-                                                       d_n_words + first, d_models + first * 40, p->rans_off + first * 10 * 1024, d_status + first * 4, p->rans_scratch, nullptr))
-                return r;
-            HIP_TRY(c, hipMemcpy(counts.data() + planes + 4 * first, d_status + 4 * first, count * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost));
-            bool too_small = false;
-            for (size_t k = first; k < first + count; k++) too_small = too_small || (counts[planes + 4 * k] & FRI_HIP_RANS_TOO_SMALL);
-            if (!too_small || stride == bound) return FRI_HIP_OK;
-            stride = bound;
-        }
-    };
-    if ((rc = code(0, n, p->symbols, n_y, p->rans_words_y, stride_y)) || (rc = code(n, 2 * n, p->symbols + n * n_y, n_c, p->rans_words_c, stride_c))) return rc;
-    HIP_TRY(c, hipMemcpy(counts.data(), p->rans_counts, counts.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    std::vector<uint64_t> out_of_alphabet(planes); // (this form has no such output: a plane with any is out of range)
-    bool out_of_range = false, refused = false;
-    if ((rc = read_back_plane_results(c, planes, p->params, p->counts, value_params, width_params, out_of_alphabet.data(), &out_of_range))) return rc;
-    std::memcpy(n_words, counts.data(), planes * sizeof(uint32_t));
-    std::memcpy(status, counts.data() + planes, planes * 4 * sizeof(uint32_t));
-    std::memcpy(models, counts.data() + 5 * planes, planes * 40 * sizeof(uint32_t));
-    size_t most_y = 0, most_c = 0, most_off = 0;
-    for (size_t k = 0; k < planes; k++) {
-        out_of_range = out_of_range || out_of_alphabet[k] || n_words[k] > word_stride;
-        refused = refused || status[4 * k];
-        size_t &most = k < n ? most_y : most_c;
-        if (n_words[k] <= word_stride && n_words[k] <= (k < n ? stride_y : stride_c)) most = std::max<size_t>(most, n_words[k]);
-        for (int b = 0; b < 10; b++) most_off = std::max<size_t>(most_off, std::min<uint32_t>(models[(k * 10 + b) * 4 + 1], 1024u));
-    }
-    // the coded planes only: every plane's row up to the batch's longest row that fits the caller's, every context's list up to the longest list
-    if (most_y) HIP_TRY(c, hipMemcpy2D(words, word_stride * sizeof(uint32_t), p->rans_words_y, stride_y * sizeof(uint32_t), most_y * sizeof(uint32_t), n, hipMemcpyDeviceToHost));
-    if (most_c)
-        HIP_TRY(c, hipMemcpy2D(words + n * word_stride, word_stride * sizeof(uint32_t), p->rans_words_c, stride_c * sizeof(uint32_t), most_c * sizeof(uint32_t), 2 * n,
-                               hipMemcpyDeviceToHost));
-    if (most_off)
-        HIP_TRY(c, hipMemcpy2D(off_values, 1024 * sizeof(uint16_t), p->rans_off, 1024 * sizeof(uint16_t), most_off * sizeof(uint16_t), planes * 10, hipMemcpyDeviceToHost));
-    return out_of_range ? FRI_HIP_ERR_OUT_OF_RANGE : refused ? FRI_HIP_ERR_INVALID_ARGUMENT : FRI_HIP_OK;
+    // K11 per batch: n planes of n_y symbols, then 2 n planes of n_c
+    const RansOutputs out{planes, p->rans_counts, p->rans_off};
+    RansBatch luma{0, n, p->symbols, n_y, &p->rans_words_y}, chroma{n, 2 * n, p->symbols + n * n_y, n_c, &p->rans_words_c};
+    if ((rc = rans_code_batch(c, out, luma, p->hist, p->rans_scratch)) || (rc = rans_code_batch(c, out, chroma, p->hist, p->rans_scratch))) return rc;
+    return read_back_coded(c, out, {luma, chroma}, p->params, p->counts, value_params, width_params, words, word_stride, n_words, models, off_values, status);
 }
 
 } // extern "C"
