@@ -31,7 +31,7 @@ SYMBOLS = [
     "fri_hip_plan_set_dequantiser", "fri_hip_plan_tune_forward", "fri_hip_time_transform_quant_streams_dev",
     "fri_hip_plan_set_colour_transform", "fri_hip_quality_matrix", "fri_hip_measure_distortion_dev", "fri_hip_search_quality",
     "fri_hip_search_quality_dev", "fri_hip_estimate_size_dev", "fri_hip_estimate_size", "fri_hip_search_quality_for_size",
-    "fri_hip_search_quality_for_size_dev", "fri_hip_plan_predict_grid", "fri_hip_measure_ssim_dev", "fri_hip_measure_ssim", "fri_hip_search_quality_ssim",
+    "fri_hip_search_quality_for_size_dev", "fri_hip_plan_predict_grid", "fri_hip_plan_pred_slots", "fri_hip_measure_ssim_dev", "fri_hip_measure_ssim", "fri_hip_search_quality_ssim",
     "fri_hip_search_quality_ssim_dev",
     "fri_hip_plan420_create", "fri_hip_plan420_destroy", "fri_hip_plan420_luma", "fri_hip_plan420_chroma", "fri_hip_split420_dev", "fri_hip_merge420_dev",
     "fri_hip_measure_distortion420_dev", "fri_hip_encode_image420_symbols", "fri_hip_decode_image420", "fri_hip_search_quality420", "fri_hip_search_quality420_dev",
@@ -150,6 +150,7 @@ def load_library():
     L.fri_hip_plan_read_trace.argtypes = [vp, vp]
     L.fri_hip_plan_inverse_lists.argtypes = [vp, vp]
     L.fri_hip_plan_predict_grid.argtypes = [vp, vp]
+    L.fri_hip_plan_pred_slots.argtypes = [vp, vp]
     L.fri_hip_time_transform_quant_dev.argtypes = [vp, u32, vp, sz, vp, vp, sz, u32, vp, C.POINTER(C.c_double)]
     L.fri_hip_time_transform_quant_streams_dev.argtypes = [vp, u32, vp, sz, vp, vp, sz, u32, u32, C.POINTER(C.c_double)]
     L.fri_hip_plan_tune_forward.argtypes = [vp, u32, C.c_char_p, sz]
@@ -672,6 +673,12 @@ class Plan:
         out = np.zeros(4, np.uint32)
         _check(load_library().fri_hip_plan_predict_grid(self._h, _p(out)), "fri_hip_plan_predict_grid")
         return dict(zip(("n_pred_tiles", "pred_blocks", "hist_blocks", "k4_older_eighths"), (int(v) for v in out)))
+
+    def pred_slots(self):
+        """fri_hip_plan_pred_slots: int32 [n_pred_tiles][36], the 6 x 6 slot squares of the prediction tiles (cell id, | 0x40000000 for an interior cell, -1: none)."""
+        out = np.empty((self.predict_grid()["n_pred_tiles"], 36), np.int32)
+        _check(load_library().fri_hip_plan_pred_slots(self._h, _p(out)), "fri_hip_plan_pred_slots")
+        return out
 
     def inverse_lists(self):
         out = np.zeros(5, np.uint64)

@@ -773,6 +773,11 @@ int fri_hip_plan_neighbour_cells(const fri_hip_plan *p, int32_t *ids) {
     std::memcpy(ids, p->geo.nbr_cells.data(), p->geo.nbr_cells.size() * sizeof(int32_t));
     return FRI_HIP_OK;
 }
+int fri_hip_plan_pred_slots(const fri_hip_plan *p, int32_t *out) {
+    if (!p || !out) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    std::memcpy(out, p->geo.pred_slots.data(), p->geo.pred_slots.size() * sizeof(int32_t));
+    return FRI_HIP_OK;
+}
 int fri_hip_plan_tiling(const fri_hip_plan *p, int32_t out[8]) {
     if (!p || !out) return FRI_HIP_ERR_INVALID_ARGUMENT;
     const Geometry &g = p->geo;

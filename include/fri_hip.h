@@ -106,6 +106,12 @@ int fri_hip_plan_tiling(const fri_hip_plan *plan, int32_t out[8]);
  * walk and the grid limits their launchers start from (FRI_HIP_PRED_BLOCKS, FRI_HIP_HIST_BLOCKS, FRI_HIP_K4_OLDER_EIGHTHS override
  * the defaults at plan creation). A host-only plan has no device: out[1..3] are the knobs it was created under, 0 where none is set. */
 int fri_hip_plan_predict_grid(const fri_hip_plan *plan, uint32_t out[4]);
+/* out[n_pred_tiles][36] (n_pred_tiles = out[0] of fri_hip_plan_predict_grid): the prediction tiles themselves. A tile is a 4 x 4 block of lattice
+ * cells with a halo ring of one cell, a 6 x 6 square of slots, row major: slot 6 i + j, block cells at i, j in 1..4. An entry is the cell id
+ * held by the slot, | 0x40000000 for an interior cell (all 512 leaves inside the image, hence all 512 coefficients Some; a cell without the
+ * flag may have all of them Some as well), -1 where the lattice retains no cell. Every cell is a block
+ * cell of exactly one tile. Works on host-only plans. The order of W^T r's f32 partial sums is stated in these terms (fri_hip_fit_width_sums). */
+int fri_hip_plan_pred_slots(const fri_hip_plan *plan, int32_t *out);
 /* The decomposition itself (any pointer may be NULL): tiles[n_tiles][6] = {x_lo, y_lo, width_px, n_rows, cell_begin,
  * cell_count}; tile_cells[F] = cell ids in tile order; wg_tiles[n_wg + 1] = tile range of each workgroup share. */
 int fri_hip_plan_tile_table(const fri_hip_plan *plan, int32_t *tiles, int32_t *tile_cells, int32_t *wg_tiles);
@@ -210,7 +216,24 @@ int fri_hip_fit_value_sums_dev(fri_hip_plan *plan, const int32_t *d_coefs, uint3
  * plane's sum stays below 8.8e12 (a 16384 x 16384 noise plane: ~1.6e12) and every partial sum below 2^24: a partial sum that is not (value parameters
  * that are huge, infinite or NaN) is clamped and COUNTED with the out-of-range coefficients - the host forms return FRI_HIP_ERR_OUT_OF_RANGE, the
  * device forms report the count - so a meaningless W^T r never leaves silently. rows[g] = height of the reference's matrix (F*256, F*128, F*128): its
- * all-zero rows still carry the constant feature 1 with residual 0, so add rows[g] - wtw[g][0] to entry (0,0). */
+ * all-zero rows still carry the constant feature 1 with residual 0, so add rows[g] - wtw[g][0] to entry (0,0).
+ *
+ * W^T r, exactly (files written with fitted parameters depend on these bits; tests/fit_ref.py restates them in numpy and the tests compare bit for bit):
+ * - Tiles. fri_hip_plan_pred_slots gives the prediction tiles: 4 x 4 blocks of lattice cells inside a 6 x 6 square of slots.
+ * - Partial sums. One per (tile, half h in {0, 1}, pair group pg in 0..3, lane in 0..63), six f32 values s0..s5 starting at +0.
+ *   Its cells are block rows 2 h and 2 h + 1 of the tile, four columns each, visited in the order C = 0..7:
+ *   slot (1 + 2 h + (C >> 2)) * 6 + 1 + (C & 3); a slot without a cell is skipped.
+ *   Its nodes (heap indices) are n0 and n0 + 1 with n0 = 128 + 2 lane (pg 0: level 7, group 1), 2 lane (pg 1: levels 0..6, group 2),
+ *   256 + 4 lane (pg 2) and 256 + 4 lane + 2 (pg 3: level 8, group 0). Heap nodes 0 and 1 are no rows of the fit and contribute nothing.
+ * - Per cell, for node a = n0 and node b = n0 + 1, with rn() = one IEEE round-to-nearest-even f32 operation, v0..v5 the node's neighbour
+ *   values (None and absent neighbours: 0), x = value_params[group]:
+ *     p = rn(v0 x0), then p = rn(p + rn(vk xk)) for k = 1..5;  r = |rn(value - p)|;  d_j = |v_D0[j] - v_D1[j]|, D0 = {0, 1, 4, 1, 2},
+ *     D1 = {3, 2, 5, 5, 4} (exact integers);
+ *     s0 = rn(rn(s0 + r_a) + r_b);  s_(1+j) = fma(d_b_j, r_b, fma(d_a_j, r_a, s_(1+j))) for j = 0..4 - fused multiply-adds, one rounding each.
+ *   A None node is an all-zero row: value, neighbours and features 0, r = 0 (finite parameters). f32 denormals are not pinned.
+ * - Conversion. Each of the six sums s of a partial sum becomes the integer floor(min(s, 2^24) * 2^20) (NaN counts as 2^24).
+ * - Total. wtr[g][k] = (double)(the 64-bit integer total over all partial sums of group g) * 2^-20.
+ * - Saturation. A partial sum with some s not < 2^24 enters as 2^24 and raises the plane's out-of-range count (> 0; how many is not defined). */
 int fri_hip_fit_width_sums(fri_hip_plan *plan, const int32_t *coefs, uint32_t channel, const float value_params[3][6], int64_t wtw[3][21],
                            double wtr[3][6], uint64_t rows[3]);
 int fri_hip_fit_width_sums_dev(fri_hip_plan *plan, const int32_t *d_coefs, uint32_t channel, const float value_params[3][6], int64_t *d_wtw,

@@ -95,11 +95,12 @@ def _fit_groups():
     return np.where(level == 8, 0, np.where(level == 7, 1, 2)), p >= 2
 
 
-def cpu_fit_sums(oracle, W, ch, value_params):
-    """the sums K4 accumulates for channel ch of the oracle Wavelet W: gram [3][7][7] and wtw [3][6][6] (exact int64), wtr [3][6] (float64)"""
+def cpu_fit_sums(oracle, W, ch, value_params, nv=None):
+    """the sums K4 accumulates for channel ch of the oracle Wavelet W: gram [3][7][7] and wtw [3][6][6] (exact int64), wtr [3][6] (float64); nv:
+    W.neighbour_values(ch), if the caller has it"""
     co = W.coefficients()[ch].astype(np.int64)  # [F][512]
     some = co != oracle.NONE
-    nv = W.neighbour_values(ch).astype(np.int64)  # [F][512][6]
+    nv = (W.neighbour_values(ch) if nv is None else nv).astype(np.int64)  # [F][512][6]
     g, fit_row = _fit_groups()
     use = some & fit_row[None, :]
     gram = np.zeros((3, 7, 7), np.int64)

@@ -1,11 +1,13 @@
 """Fit accumulators against sums computed on the CPU from the oracle's restatement of
-ContextModeler::get_neighbour_values (context_modeling.rs:25-77). Integer sums are bit-exact; the f64 residual sums are
-compared with a tolerance (summation order is not fixed on the device)."""
+ContextModeler::get_neighbour_values (context_modeling.rs:25-77). Every sum is compared bit for bit: the integer sums with plain numpy sums, W^T r with
+the restatement of its f32 partial sums and their fixed-point total in tests/fit_ref.py (anchored on the host by tests/test_fit_ref_host.py)."""
 import numpy as np
 import pytest
 
+from tests import fit_ref
 from tests.common import KAT_VALUE_PARAMS, gen_image, random_params
 from tests.oracle_ref import cpu_fit_sums
+from tests.test_fit_ref_host import SATURATION_SEED, SATURATION_SHAPE, saturating_params
 
 pytestmark = pytest.mark.gpu
 
@@ -26,9 +28,11 @@ def _groups():
     return g, p >= 2
 
 
-@pytest.mark.parametrize("shape", [(10, 10, 3), (100, 37, 3), (300, 200, 1), (512, 512, 3)])
-@pytest.mark.parametrize("kind", ["noise", "smooth"])
+@pytest.mark.parametrize("shape", [(10, 10, 3), (100, 37, 3), (300, 200, 1), (512, 512, 3), (3, 300, 1), (401, 3, 3)])
+@pytest.mark.parametrize("kind", ["noise", "smooth", "const"])
 def test_fit_sums_match_cpu(ctx, oracle, shape, kind):
+    """(3, 300, 1) and (401, 3, 3): every cell is a boundary cell. const: nothing but the boundary cells' rows is non-zero. smooth: partial sums below 16,
+    where the truncation to 20 fraction bits bites."""
     import frave_amd
 
     w, h, c = shape
@@ -43,9 +47,10 @@ def test_fit_sums_match_cpu(ctx, oracle, shape, kind):
         assert np.array_equal(gram, want_gram)
         wtw, wtr, rows = P.fit_width_sums(co, ch, vp)
         assert np.array_equal(wtw, want_wtw)
-        # W^T r: f32 partial sums over the 16 nodes a lane has in a tile (the reference's whole fit is f32), fixed point with 20 fraction bits from there on
-        # (each of the <= 512 partial sums per tile truncated by < 2^-20: k4_fit.hip, fit_f32_to_fixed)
-        assert np.allclose(wtr, want_wtr, rtol=1e-6, atol=1e-3 + P.num_cells * 32 * 2.0 ** -20)
+        # W^T r: f32 partial sums over the 16 nodes a lane has in a tile, in the order include/fri_hip.h states, fixed point with 20 fraction bits from there on
+        exact_wtw, exact_fixed, exact_wtr, n_sat = fit_ref.oracle_width_sums(W, ch, P, vp)
+        assert np.array_equal(exact_wtw, want_wtw) and n_sat == 0
+        assert np.array_equal(wtr.view(np.uint64), exact_wtr.view(np.uint64)), (ch, (np.round(wtr * 2.0 ** 20).astype(np.int64) - exact_fixed.astype(np.int64)).tolist())
         assert rows.tolist() == [P.num_cells * 256, P.num_cells * 128, P.num_cells * 128]
 
 
@@ -157,6 +162,47 @@ def test_width_sums_report_value_parameters_from_nowhere(ctx):
     assert all(np.array_equal(a, b) for a, b in zip(again, good))
 
 
+def test_width_sums_saturate_as_defined(ctx, oracle):
+    """Value parameters scaled so that some partial sums reach 2^24 and others do not (tests/test_fit_ref_host.py checks that of the case): the device form still
+    returns sums, and they are the restatement's with every such partial sum entered as 2^24, bit for bit; the host form reports the count (> 0) as
+    FRI_HIP_ERR_OUT_OF_RANGE; sane parameters right afterwards give the bits they always gave."""
+    import torch
+
+    import frave_amd as fa
+
+    w, h, c = SATURATION_SHAPE
+    img = gen_image("noise", w, h, c, SATURATION_SEED)
+    P = fa.Plan(ctx, w, h, c)
+    W = oracle.Wavelet(img, h, w, c)
+    co = P.transform_quant(img)
+    assert np.array_equal(co, W.coefficients())
+    d_co = torch.from_numpy(co.reshape(-1)).cuda()
+    d_w, d_r = torch.zeros((3, 21), dtype=torch.int64, device="cuda"), torch.zeros((3, 6), dtype=torch.float64, device="cuda")
+
+    def sums(vp):
+        P.fit_width_sums_dev(d_co.data_ptr(), 0, vp, d_w.data_ptr(), d_r.data_ptr(), stream=torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        return d_w.cpu().numpy(), d_r.cpu().numpy()
+
+    iu6 = np.triu_indices(6)
+    before = sums(KAT_VALUE_PARAMS)
+    sane_wtw, _, sane_wtr, sane_sat = fit_ref.oracle_width_sums(W, 0, P, KAT_VALUE_PARAMS)
+    assert sane_sat == 0 and np.array_equal(before[1].view(np.uint64), sane_wtr.view(np.uint64))
+    vp = saturating_params()
+    want_wtw, want_fixed, want_wtr, n_sat = fit_ref.oracle_width_sums(W, 0, P, vp)
+    assert n_sat > 0
+    wtw, wtr = sums(vp)
+    assert np.array_equal(wtw, np.stack([want_wtw[g][iu6] for g in range(3)]))
+    assert np.array_equal(wtr.view(np.uint64), want_wtr.view(np.uint64)), (np.round(wtr * 2.0 ** 20).astype(np.int64) - want_fixed.astype(np.int64)).tolist()
+    with pytest.raises(fa.FriHipError) as e:  # the count, > 0
+        P.fit_width_sums(co, 0, vp)
+    assert e.value.code == -7
+    after = sums(KAT_VALUE_PARAMS)
+    assert np.array_equal(after[0], before[0]) and np.array_equal(after[1].view(np.uint64), before[1].view(np.uint64))
+    W.close()
+    P.close()
+
+
 def test_device_solves_return_the_bits_of_the_host_solves(ctx):
     """The 6 x 6 solves of the asynchronous chain run on the device (fit_solve_kernel) from the source the host functions are built from
     (csrc/solve6.hpp): for the same sums the same parameters, bit for bit - on the LDL^T route (textured data), on the eigen-decomposition
@@ -206,9 +252,9 @@ def test_device_solves_return_the_bits_of_the_host_solves(ctx):
 
 def test_fit_at_4096_against_the_oracle(ctx, oracle):
     """BASELINE config 2's size: the fit sums of a 4096 x 4096 plane against sums built with numpy from the oracle's get_neighbour_values
-    (17 M rows), then the whole chain with the fit (fri_hip_encode_image: K1 -> sums -> device solves -> sums -> device solves -> K2): the
-    value parameters are the host solve of the oracle's exact sums bit for bit, the width parameters agree to rounding, and the scan's outputs
-    are the oracle's predictor run with the chain's parameters."""
+    (17 M rows) and W^T r against its restatement, then the whole chain with the fit (fri_hip_encode_image: K1 -> sums -> device solves -> sums ->
+    device solves -> K2): value and width parameters are the host solves of those sums bit for bit, and the scan's outputs are the oracle's
+    predictor run with the chain's parameters."""
     import frave_amd as fa
 
     w = h = 4096
@@ -219,13 +265,16 @@ def test_fit_at_4096_against_the_oracle(ctx, oracle):
     co, vp, wp, b, p, hist, oob = P.encode_image(img, fit=True)
     assert np.array_equal(co, W.coefficients())
     iu7, iu6 = np.triu_indices(7), np.triu_indices(6)
-    want_gram, want_wtw, want_wtr = cpu_fit_sums(oracle, W, 0, vp[0])
+    nv = W.neighbour_values(0)
+    want_gram, want_wtw, _ = cpu_fit_sums(oracle, W, 0, vp[0], nv)
     assert np.array_equal(P.fit_value_sums(co, 0), want_gram)
     assert np.array_equal(vp[0].view(np.uint32), fa.fit_value_params(np.stack([want_gram[g][iu7] for g in range(3)])).view(np.uint32))
     wtw, wtr, rows = P.fit_width_sums(co, 0, vp[0])
     assert np.array_equal(wtw, want_wtw)
-    assert np.allclose(wtr, want_wtr, rtol=1e-6, atol=1e-3)
-    assert np.allclose(wp[0], fa.fit_width_params(np.stack([want_wtw[g][iu6] for g in range(3)]), want_wtr, rows), rtol=1e-4, atol=1e-6)
+    exact_wtw, exact_fixed, exact_wtr, n_sat = fit_ref.oracle_width_sums(W, 0, P, vp[0], nv)
+    assert np.array_equal(exact_wtw, want_wtw) and n_sat == 0
+    assert np.array_equal(wtr.view(np.uint64), exact_wtr.view(np.uint64)), (np.round(wtr * 2.0 ** 20).astype(np.int64) - exact_fixed.astype(np.int64)).tolist()
+    assert np.array_equal(wp[0].view(np.uint32), fa.fit_width_params(np.stack([want_wtw[g][iu6] for g in range(3)]), exact_wtr, rows).view(np.uint32))
     W.quantize(np.ones(32, np.int32))
     wb, wpred, whist, woob = W.predict(0, vp[0], wp[0])
     assert np.array_equal(b[0], wb) and np.array_equal(p[0], wpred) and np.array_equal(hist[0], whist) and int(oob[0]) == woob

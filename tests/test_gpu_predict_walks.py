@@ -3,15 +3,16 @@ reaches are checked on the host by tests/test_predict_cases_host.py).
 
 - K2: buckets, predictions, histograms and out-of-alphabet counts bit for bit against oracle.Wavelet.predict; the word and stream forms through the symbol
   streams, as tests/test_gpu_instances.py checks them.
-- K4: the integer sums (gram, wtw) exactly against the numpy sums over the oracle's neighbour values; W^T r within the tolerance of its float64 sum and bit
-  for bit the same as on a default plan and as plane 0 of a two-plane launch; value parameters from the tail solve and the solve kernel bit for bit the
-  host solve of the numpy sums; width parameters bit for bit the default plan's; the out-of-range count of injected coefficients the default plan's, and
-  not zero.
+- K4: the integer sums (gram, wtw) exactly against the numpy sums over the oracle's neighbour values; W^T r bit for bit against the restatement of its f32
+  partial sums and fixed-point total (tests/fit_ref.py), hence the same on a default plan and as plane 0 of a two-plane launch; value and width parameters
+  from the tail solve and the solve kernel bit for bit the host solves of those sums; the out-of-range count of injected coefficients the default plan's,
+  and not zero.
 Every device output starts as a non-zero fill pattern between guard bytes, the histogram too (the kernel clears it). Every case runs twice on one plan, with
 a launch of another plane count in between, and must give the same results the second time (hand-over serial numbers, tickets, accumulator shards)."""
 import numpy as np
 import pytest
 
+from tests import fit_ref
 from tests.common import gen_image, random_params
 from tests.oracle_ref import cpu_fit_sums, oracle_coefficients
 from tests.predict_cases import CASES, knobs
@@ -237,10 +238,13 @@ def _run_case(torch, oracle, P, case):
             W = _wavelet(oracle, case, co[i])
             for ch in range(c):
                 k = i * c + ch
-                wg, ww, wr = cpu_fit_sums(oracle, W, ch, params[k, 0])
+                nv = W.neighbour_values(ch)
+                wg, ww, _ = cpu_fit_sums(oracle, W, ch, params[k, 0], nv)
                 assert np.array_equal(gram[k], np.stack([wg[g][IU7] for g in range(3)])), (case.id, k, "gram")
                 assert np.array_equal(wtw[k], np.stack([ww[g][IU6] for g in range(3)])), (case.id, k, "wtw")
-                assert np.allclose(wtr[k], wr, rtol=1e-6, atol=1e-3 + F * 32 * 2.0 ** -20), (case.id, k, "wtr")
+                xw, xfixed, xr, n_sat = _exact_width(case, W, ch, k, P, params[k, 0], nv)
+                assert np.array_equal(xw, ww) and n_sat == 0, (case.id, k, "restated wtw")
+                assert np.array_equal(wtr[k].view(np.uint64), xr.view(np.uint64)), (case.id, k, "wtr", (np.round(wtr[k] * 2.0 ** 20).astype(np.int64) - xfixed.astype(np.int64)).tolist())
             W.close()
         import frave_amd as fa
 
@@ -260,7 +264,7 @@ def _run_case(torch, oracle, P, case):
         co = _coefs(oracle, case)
         got, rng = _fit_chain(torch, P, co)
         assert (rng == 0).all(), (case.id, rng)
-        _check_value_params(oracle, case, co, got)
+        _check_fitted_params(oracle, case, co, got, P)
         res.update(params=got.view(np.uint32))
         if case.inexact:
             res["range"] = _fit_chain(torch, P, _inject(co, case.inexact, case.seed))[1]
@@ -276,7 +280,7 @@ def _run_case(torch, oracle, P, case):
         assert np.array_equal(out[0], co), (case.id, "K1 coefficients")
     if case.fit:
         assert (rng == 0).all(), (case.id, rng)
-        _check_value_params(oracle, case, co, par)
+        _check_fitted_params(oracle, case, co, par, P)
     if case.route == "encode_batch":
         want = _k2_expect(oracle, case, co, par)
         _check_k2(case, (out[1], out[2], hist, oob), want)
@@ -295,17 +299,36 @@ def _run_case(torch, oracle, P, case):
 ORDER = {}
 
 
-def _check_value_params(oracle, case, co, par):
-    """value parameters of the device fit = the host solve of the numpy sums, bit for bit"""
+EXACT = {}  # (case id, plane, value parameters' bytes) -> fit_ref.oracle_width_sums: a case runs up to three times on the same inputs
+
+
+def _exact_width(case, W, ch, k, P, vp, nv=None):
+    key = (case.id, k, np.asarray(vp, np.float32).tobytes())
+    if key not in EXACT:
+        EXACT[key] = fit_ref.oracle_width_sums(W, ch, P, vp, nv)
+    return EXACT[key]
+
+
+def _check_fitted_params(oracle, case, co, par, P):
+    """the parameters of the device fit = the host solves of sums that involve no GPU code, bit for bit: the value parameters of the numpy Gram sums, the
+    width parameters of the restated W^T W and W^T r (tests/fit_ref.py) for those value parameters"""
     import frave_amd as fa
 
     c = case.shape[2]
+    F = P.num_cells
+    rows = np.array([F * 256, F * 128, F * 128], np.uint64)
     for i in range(co.shape[0]):
         W = _wavelet(oracle, case, co[i])
         for ch in range(c):
-            wg, _, _ = cpu_fit_sums(oracle, W, ch, np.zeros((3, 6), np.float32))
+            k = i * c + ch
+            nv = W.neighbour_values(ch)
+            wg, ww, _ = cpu_fit_sums(oracle, W, ch, np.zeros((3, 6), np.float32), nv)
             want = fa.fit_value_params(np.stack([wg[g][IU7] for g in range(3)]))
-            assert np.array_equal(par[i * c + ch, 0].view(np.uint32), want.view(np.uint32)), (case.id, i, ch, "value parameters")
+            assert np.array_equal(par[k, 0].view(np.uint32), want.view(np.uint32)), (case.id, i, ch, "value parameters")
+            xw, _, xr, n_sat = _exact_width(case, W, ch, k, P, want, nv)
+            assert n_sat == 0 and np.array_equal(xw, ww)
+            want = fa.fit_width_params(np.stack([xw[g][IU6] for g in range(3)]), xr, rows)
+            assert np.array_equal(par[k, 1].view(np.uint32), want.view(np.uint32)), (case.id, i, ch, "width parameters")
         W.close()
 
 

@@ -10,6 +10,7 @@ import torch
 
 import frave_amd
 from oracle import fri_oracle as O
+from tests import fit_ref
 from tests.common import gen_image, random_params
 from tests.instance_cases import knobs
 from tests.oracle_ref import numpy_measure, oracle_coefficients, oracle_owned, oracle_raster
@@ -117,6 +118,11 @@ def run(n_cases, seed, ctx=None):
                     iu = np.triu_indices(7)
                     vh = frave_amd.api.fit_value_params(np.stack([gram[g][iu] for g in range(3)]))
                     wtw, wtr, rows = P.fit_width_sums(co, cc, vh)
+                    # W^T W and W^T r against their restatement from the oracle's neighbour values (tests/fit_ref.py), bit for bit
+                    xw, xfixed, xr, n_sat = fit_ref.oracle_width_sums(W, cc, P, vh)
+                    if not (np.array_equal(wtw, xw) and n_sat == 0 and np.array_equal(wtr.view(np.uint64), xr.view(np.uint64))):
+                        units = (np.round(wtr * 2.0 ** 20).astype(np.int64) - xfixed.astype(np.int64)).tolist()
+                        msgs.append(f"K4 width sums ch{cc} (value params {vh.tolist()}, saturated {n_sat}, W^T r off by {units} fixed-point units)")
                     iu6 = np.triu_indices(6)
                     wh = frave_amd.api.fit_width_params(np.stack([wtw[g][iu6] for g in range(3)]), wtr, rows)
                     ok_fit = ok_fit and np.array_equal(vh.view(np.uint32), vpf[cc].view(np.uint32)) and np.array_equal(wh.view(np.uint32), wpf[cc].view(np.uint32))
