@@ -51,7 +51,9 @@ SYMBOLS = [
     "fri_hip_measure_distortion_tiled420_dev", "fri_hip_estimate_size_tiled420_dev", "fri_hip_estimate_size_tiled420", "fri_hip_search_quality_tiled420",
     "fri_hip_search_quality_tiled420_dev", "fri_hip_search_quality_ssim_tiled420", "fri_hip_search_quality_ssim_tiled420_dev", "fri_hip_search_quality_for_size_tiled420",
     "fri_hip_search_quality_for_size_tiled420_dev", "fri_hip_encode_image_tiled420_coded",
+    "fri_hip_decode_scratch_bytes", "fri_hip_decode_planes_dev", "fri_hip_decode_time_planes_dev", "fri_hip_decode_image_tiled_coded", "fri_hip_decode_image_tiled420_coded",
 ]
+DECODE_TRUNCATED, DECODE_BAD_MODEL, DECODE_BAD_SLOT = 1, 2, 4  # FRI_HIP_DECODE_*: bits of a plane's status word of fri_hip_decode_planes_dev (include/fri_hip.h)
 RANS_EMPTY_OK = 1  # FRI_HIP_RANS_EMPTY_OK: `flags` of fri_hip_rans_encode_planes_dev - a context without counts is coded (the emitter's FRI_EMIT_EMPTY_OK)
 RANS_TOO_SMALL, RANS_BAD_MODEL, RANS_ZERO_FREQ, RANS_BAD_BUCKET = 1, 2, 4, 8  # bits of a plane's status word (include/fri_hip.h)
 TILED_ALLOW_HOLES = 1  # FRI_HIP_TILED_ALLOW_HOLES: `flags` of fri_hip_plan_tiled_create - accept a tile shape whose lattice does not own every pixel
@@ -275,6 +277,11 @@ def load_library():
     L.fri_hip_search_quality_for_size_tiled420.argtypes = [vp, vp, C.c_uint64, vp, vp]
     L.fri_hip_search_quality_for_size_tiled420_dev.argtypes = [vp, vp, C.c_uint64, vp, vp, vp]
     L.fri_hip_encode_image_tiled420_coded.argtypes = [vp, vp, i32, vp, vp, vp, sz, vp, vp, vp, vp]
+    L.fri_hip_decode_scratch_bytes.restype, L.fri_hip_decode_scratch_bytes.argtypes = C.c_uint64, [u32]
+    L.fri_hip_decode_planes_dev.argtypes = [vp, u32, vp, sz, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp]
+    L.fri_hip_decode_time_planes_dev.argtypes = [vp, u32, vp, sz, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp]
+    L.fri_hip_decode_image_tiled_coded.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.fri_hip_decode_image_tiled420_coded.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, i32, vp, vp]
     _lib = L
     return L
 
@@ -360,6 +367,48 @@ def rans_encode_planes_dev(ctx, n_planes, d_symbols, symbol_stride, n_symbols, d
         _check(L.fri_hip_rans_time_planes_dev(*args, _p(us)), "fri_hip_rans_time_planes_dev", ctx)
         return us
     _check(L.fri_hip_rans_encode_planes_dev(*args), "fri_hip_rans_encode_planes_dev", ctx)
+
+
+def decode_scratch_bytes(n_planes):
+    """fri_hip_decode_scratch_bytes: the device scratch fri_hip_decode_planes_dev needs for n_planes planes (0: count out of range)."""
+    return int(load_library().fri_hip_decode_scratch_bytes(n_planes))
+
+
+def decode_planes_dev(plan, n_planes, d_words, word_stride, d_n_words, d_models, d_off_values, d_value_params, d_width_params, d_coefs, coef_stride, d_status, d_scratch,
+                      stream=0, timed=False):
+    """fri_hip_decode_planes_dev (K13), device pointers as ints: the coded planes of emit.tiled_parse_coded - d_words uint32 [n_planes][word_stride], d_n_words
+    [n_planes], d_models [n_planes][10][4], d_off_values uint16 [n_planes][10][1024], d_value_params / d_width_params f32 [n_planes][3][6] - on the lattice of `plan`
+    (which needs its stream order) -> d_coefs int32, plane p at + p * coef_stride elements, and d_status uint32 [n_planes][4] = {bits, at, 0, 0}. d_scratch:
+    decode_scratch_bytes(..) bytes, 256-byte aligned. Only enqueues. timed=True: fri_hip_decode_time_planes_dev - synchronises and returns the microseconds of the
+    model and decode kernels."""
+    L = load_library()
+    args = (plan._h if plan else None, n_planes, d_words, word_stride, d_n_words, d_models, d_off_values, d_value_params, d_width_params, d_coefs, coef_stride, d_status,
+            d_scratch, stream)
+    ctx = plan.ctx if plan else None
+    if timed:
+        us = np.zeros(2, np.float64)
+        _check(L.fri_hip_decode_time_planes_dev(*args, _p(us)), "fri_hip_decode_time_planes_dev", ctx)
+        return us
+    _check(L.fri_hip_decode_planes_dev(*args), "fri_hip_decode_planes_dev", ctx)
+
+
+def _coded_planes(coded, planes):
+    """the arrays of emit.tiled_parse_coded (with or without its leading TiledInfo) as the C ABI takes them"""
+    words, n_words, models, off, vp, wp = coded[-6:]
+    words, n_words, models = np.ascontiguousarray(words, np.uint32), np.ascontiguousarray(n_words, np.uint32), np.ascontiguousarray(models, np.uint32)
+    off, vp, wp = np.ascontiguousarray(off, np.uint16), np.ascontiguousarray(vp, np.float32), np.ascontiguousarray(wp, np.float32)
+    assert n_words.size == planes and words.ndim == 2 and words.shape[0] == planes and models.size == planes * 40 and off.size == planes * 10240
+    assert vp.size == planes * 18 and wp.size == planes * 18
+    return words, n_words, models, off, vp, wp
+
+
+def _check_decode(rc, where, ctx, status):
+    """_check, with the planes' status on the error a refused plane raises (-1 with the status filled)"""
+    try:
+        _check(rc, where, ctx)
+    except FriHipError as e:
+        e.status = status
+        raise
 
 
 def quality_matrix(quality):
@@ -1170,6 +1219,18 @@ class PlanTiled:
         _check(load_library().fri_hip_decode_image_tiled(self._h, _p(co), _p(_q(qmatrix)), _p(out)), "fri_hip_decode_image_tiled", self.ctx)
         return out
 
+    def decode_coded(self, coded, qmatrix=None):
+        """fri_hip_decode_image_tiled_coded: the coded planes of a `frit` file - what emit.tiled_parse_coded returns, with or without its TiledInfo - through the
+        device decoder (K13), the inverse kernel and the merge -> (pixels uint8 [H * W * C], status uint32 [n_tiles C][4]); the pixels are decode_image_tiled's of
+        emit.tiled_decode's planes. A plane the decoder refuses raises FriHipError (-1) with the status as .status. Needs set_stream_order()."""
+        planes = self.n_tiles * self.channels
+        words, n_words, models, off, vp, wp = _coded_planes(coded, planes)
+        out, status = np.empty(self.pixel_bytes, np.uint8), np.zeros((planes, 4), np.uint32)
+        rc = load_library().fri_hip_decode_image_tiled_coded(self._h, _p(words), words.shape[1], _p(n_words), _p(models), _p(off), _p(vp), _p(wp), _p(_q(qmatrix)), _p(out),
+                                                             _p(status))
+        _check_decode(rc, "fri_hip_decode_image_tiled_coded", self.ctx, status)
+        return out, status
+
     # ---- region decode: only the tiles a rectangle touches -------------------------------------------
     def region_tiles(self, x, y, w, h):
         """fri_hip_plan_tiled_region: (i0, j0, ni, nj), the sub-grid of tiles the region x, y, w, h (image pixels) touches; sub-tile b ni + a is tile
@@ -1342,6 +1403,18 @@ class PlanTiled420:
         out = np.empty(self.pixel_bytes, np.uint8)
         _check(load_library().fri_hip_decode_image_tiled420(self._h, _p(co), int(quality), _p(out)), "fri_hip_decode_image_tiled420", self.ctx)
         return out
+
+    def decode_coded(self, coded, quality):
+        """fri_hip_decode_image_tiled420_coded: the coded planes of a tiled 4:2:0 file in plane order - what emit.tiled_parse_coded returns, with or without its
+        TiledInfo - through the device decoder (K13) on both lattices, the inverse kernels and the merge -> (pixels uint8 [H * W * 3], status uint32 [3 n][4]).
+        A plane the decoder refuses raises FriHipError (-1) with the status as .status. Needs set_stream_order()."""
+        planes = 3 * self.n_tiles
+        words, n_words, models, off, vp, wp = _coded_planes(coded, planes)
+        out, status = np.empty(self.pixel_bytes, np.uint8), np.zeros((planes, 4), np.uint32)
+        rc = load_library().fri_hip_decode_image_tiled420_coded(self._h, _p(words), words.shape[1], _p(n_words), _p(models), _p(off), _p(vp), _p(wp), int(quality), _p(out),
+                                                                _p(status))
+        _check_decode(rc, "fri_hip_decode_image_tiled420_coded", self.ctx, status)
+        return out, status
 
     def decode_region_tiled420(self, coefs, quality, x, y, w, h):
         """fri_hip_decode_region_tiled420: coefs int32, the sub-grid's planes in plane order (what emit.tiled_decode_region returns) -> pixels uint8 [h * w * 3]:

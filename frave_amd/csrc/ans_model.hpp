@@ -1,7 +1,8 @@
 // ans_model.hpp -- the emitter's ANS model of a context rebuilt on the device from K2's counts, bit for bit what AnsContext::finalize (host/emit.cpp,
 // entropy_coding.rs:82-159) builds: the fixed Laplace shape scaled to 2^max_freq_bits, a frequency of 1 for a used symbol the shape rounds to 0 (listed
 // as off-distribution), the total normalised to 2^max_freq_bits, and one count stolen from the smallest slot > 1 for every used symbol whose slot
-// collapsed. Shared by K6 (k6_rate.hip), which prices the model, and K11 (k11_rans.hip), which codes with it. A workgroup of kRateThreads threads
+// collapsed. Shared by K6 (k6_rate.hip), which prices the model, K11 (k11_rans.hip), which codes with it,
+// and K13 (k13_decode.hip), which rebuilds it from what a file carries (ans_model_rebuild_file). A workgroup of kRateThreads threads
 // rebuilds one context; thread t owns symbols 4t .. 4t + 3. Include after device_common.hpp, inside no namespace.
 #pragma once
 #include <cstdint>
@@ -85,11 +86,13 @@ struct AnsModel {
     bool empty;               // EMPTY_OK and the counts sum to zero
 };
 
+__device__ __forceinline__ void ans_model_finish(const uint32_t (&f)[kRatePer], uint32_t n_off, uint32_t target, AnsModelLds &s, AnsModel &m);
+
 // EMPTY_OK: the emitter's FRI_EMIT_EMPTY_OK, which codes the tiles of a `frit` file - a context whose counts sum to zero takes max_freq_bits = 0 before the floor
 // and its model is rebuilt like any other. laplace: this context's [1024] shape values. Every thread of the workgroup calls it; it ends behind a barrier.
 template <bool EMPTY_OK>
 __device__ __forceinline__ void ans_model_rebuild(const uint32_t *hist, const float *laplace, AnsModelLds &s, AnsModel &m) {
-    const int t = threadIdx.x, lane = t & 63;
+    const int t = threadIdx.x;
 #pragma unroll
     for (int k = 0; k < kRatePer; k++) m.count[k] = hist[kRatePer * t + k];
 
@@ -116,6 +119,13 @@ __device__ __forceinline__ void ans_model_rebuild(const uint32_t *hist, const fl
         m.off |= (uint32_t)off << k;
     }
 
+    ans_model_finish(f, n_off, target, s, m);
+}
+
+// Everything behind the Laplace fill, shared by the two entries: the frequencies f of the thread's four symbols (and how many of them it listed as
+// off-distribution) normalised to `target`, the collapse loop, the last slot as written and the recomputed max_freq_bits.
+__device__ __forceinline__ void ans_model_finish(const uint32_t (&f)[kRatePer], uint32_t n_off, uint32_t target, AnsModelLds &s, AnsModel &m) {
+    const int t = threadIdx.x, lane = t & 63;
     uint32_t excl[kRatePer];
     const uint32_t cur_total = block_exclusive_scan_u32(f, excl, s.scan);
 
@@ -189,6 +199,39 @@ __device__ __forceinline__ void ans_model_rebuild(const uint32_t *hist, const fl
     }
     m.max_freq_bits = log2_floor_or_64(block_sum_u32(fsum, s.u32)); // entropy_coding.rs:113-114
     block_exclusive_scan_u32(m.fin, m.start, s.scan); // the final cumulative frequencies: the slot sizes summed (the emitter's cdf)
+}
+
+// The file side (K13, k13_decode.hip): the decoder's model of a context from what a file carries of it - max_freq_bits and the first n_off (<= 1024) entries of
+// the off-distribution list - which is AnsContext::finalize on a context whose freqs are all zero (host/emit.cpp, deserialize): a symbol the shape gives 0
+// takes frequency 1 if it is listed, every other symbol its Laplace value; behind that, ans_model_finish. listed: [1024] bytes of the workgroup's LDS. A listed
+// value above 1023 names no symbol and is passed over, as the host's search for it finds nothing. m.count is zero, m.off marks the listed symbols that took
+// frequency 1. Every thread of the workgroup calls it; it ends behind a barrier.
+__device__ __forceinline__ void ans_model_rebuild_file(uint32_t max_freq_bits, const uint16_t *off_values, uint32_t n_off, const float *laplace, uint8_t *listed,
+                                                       AnsModelLds &s, AnsModel &m) {
+    const int t = threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < kRatePer; k++) listed[kRatePer * t + k] = 0, m.count[k] = 0;
+    __syncthreads();
+    for (uint32_t i = t; i < n_off; i += kRateThreads) {
+        const uint32_t v = off_values[i];
+        if (v < (uint32_t)kRateAlphabet) listed[v] = 1; // (a value listed twice: the same byte, the same store)
+    }
+    __syncthreads();
+    uint32_t mfb = max_freq_bits;
+    if (mfb < 8) mfb = 8;
+    const uint32_t target = 1u << (mfb & 31u); // shl1_release
+    const float scale = (float)(int32_t)target;
+    uint32_t f[kRatePer], n_listed = 0;
+    m.off = 0, m.empty = false;
+#pragma unroll
+    for (int k = 0; k < kRatePer; k++) {
+        const uint32_t lv = f32_as_u32(laplace[kRatePer * t + k] * scale);
+        const bool one = lv == 0 && listed[kRatePer * t + k];
+        f[k] = one ? 1u : lv;
+        n_listed += one;
+        m.off |= (uint32_t)one << k;
+    }
+    ans_model_finish(f, n_listed, target, s, m);
 }
 
 } // namespace

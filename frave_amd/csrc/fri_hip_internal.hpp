@@ -316,4 +316,7 @@ inline int read_back_symbols(fri_hip_ctx *c, size_t planes, size_t n_symbols, co
 // K11's limits on a batch of planes (fri_hip_rans_*; fri_hip_encode_image_tiled_coded checks them before it stages anything)
 inline bool rans_counts_ok(uint32_t n_planes, uint64_t n_symbols) { return n_planes >= 1 && n_planes <= 65535u && n_symbols >= 1 && n_symbols < (1ull << 31); }
 
+// K13's limit on a batch of planes (fri_hip_decode_*)
+inline bool decode_counts_ok(uint32_t n_planes) { return n_planes >= 1 && n_planes <= 65535u; }
+
 } // namespace fri::host

@@ -1,5 +1,5 @@
 // fri_hip_tiled.cpp -- the tiled plan kind of the C ABI (fri_hip_plan_tiled: include/fri_hip.h): the plan and its grid, split and merge, the encode chain and
-// its coded form (K11), the image and region decodes, the measure, the size estimate and the quality searches. Host-side glue like fri_hip.cpp, on one ordinary
+// its coded form (K11), the image and region decodes and the decode from coded planes (K13), the measure, the size estimate and the quality searches. Host-side glue like fri_hip.cpp, on one ordinary
 // plan of the tile's shape. The grid, plan creation, the host size estimate and the coded route are tiled_common.hpp's, shared with fri_hip_tiled420.cpp; the
 // searches are TiledSearch on search_scaffold.hpp.
 #include "search_scaffold.hpp"
@@ -320,6 +320,28 @@ int fri_hip_encode_image_tiled_coded(fri_hip_plan_tiled *p, const uint8_t *pixel
     RansBatch all{0, planes, p->symbols, n, &p->rans_words};
     if ((rc = rans_code_batch(c, out, all, p->hist, p->rans_scratch))) return rc;
     return read_back_coded(c, out, {all}, p->params, p->counts, value_params, width_params, words, word_stride, n_words, models, off_values, status);
+}
+
+/* ---- the coded decode: K13 in front of the inverse kernel ---- */
+int fri_hip_decode_image_tiled_coded(fri_hip_plan_tiled *p, const uint32_t *words, size_t word_stride, const uint32_t *n_words, const uint32_t *models,
+                                     const uint16_t *off_values, const float *value_params, const float *width_params, const int32_t qmatrix[32], uint8_t *pixels,
+                                     uint32_t *status) {
+    if (int rc = need_device(p)) return rc;
+    const CodedPlanes in{words, word_stride, n_words, models, off_values, value_params, width_params};
+    if (!in.complete() || !qmatrix || !pixels || !status || !p->tile->d_stream_order) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    fri_hip_ctx *c = p->ctx;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t image = fri_hip_plan_coef_count(p->tile.get()), n = p->n_tiles(), planes = n * p->channels;
+    if (!decode_counts_ok((uint32_t)planes)) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    int rc;
+    if ((rc = grow(c, p->coefs, n * image)) || (rc = grow(c, p->tiles, n * p->tile_bytes())) || (rc = grow(c, p->raster, p->raster_bytes()))) return rc;
+    CodedOnDevice d;
+    if ((rc = upload_coded(p, in, planes, p->rans_words, d)) || (rc = decode_coded_batch(p->tile.get(), d, 0, planes, p->coefs, image / p->channels))) return rc;
+    if ((rc = read_back_decode_status(c, d, status))) return rc;
+    if ((rc = fri_hip_inverse_transform_batch_dev(p->tile.get(), (uint32_t)n, p->coefs, image, qmatrix, p->tiles, p->tile_bytes(), nullptr))) return rc;
+    HIP_TRY(c, launch_merge_tiles(p->tiles, p->grid.width, p->grid.height, p->channels, p->grid.tile_w, p->grid.tile_h, p->raster, nullptr));
+    HIP_TRY(c, hipMemcpy(pixels, p->raster, p->raster_bytes(), hipMemcpyDeviceToHost));
+    return FRI_HIP_OK;
 }
 
 } // extern "C"

@@ -349,4 +349,26 @@ int fri_hip_encode_image_tiled420_coded(fri_hip_plan_tiled420 *p, const uint8_t 
     return read_back_coded(c, out, {luma, chroma}, p->params, p->counts, value_params, width_params, words, word_stride, n_words, models, off_values, status);
 }
 
+/* ---- the coded decode: K13 over the luma batch, then over the chroma batch, in front of the inverse kernels ---- */
+int fri_hip_decode_image_tiled420_coded(fri_hip_plan_tiled420 *p, const uint32_t *words, size_t word_stride, const uint32_t *n_words, const uint32_t *models,
+                                        const uint16_t *off_values, const float *value_params, const float *width_params, int quality, uint8_t *pixels, uint32_t *status) {
+    if (int rc = need_device(p)) return rc;
+    const CodedPlanes in{words, word_stride, n_words, models, off_values, value_params, width_params};
+    if (!in.complete() || !pixels || !status || quality < 1 || quality > 99 || !p->luma->d_stream_order || !p->chroma->d_stream_order) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    fri_hip_ctx *c = p->ctx;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t n = p->n_tiles(), planes = 3 * n, bytes = p->raster_bytes();
+    if (!decode_counts_ok((uint32_t)(2 * n))) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    int rc;
+    if ((rc = grow(c, p->coefs, n * (p->y_coefs() + 2 * p->c_coefs()))) || (rc = grow(c, p->region, bytes))) return rc;
+    CodedOnDevice d;
+    if ((rc = upload_coded(p, in, planes, p->rans_words_y, d)) || (rc = decode_coded_batch(p->luma.get(), d, 0, n, p->coefs, p->y_coefs())) ||
+        (rc = decode_coded_batch(p->chroma.get(), d, n, 2 * n, p->coefs + n * p->y_coefs(), p->c_coefs())))
+        return rc;
+    if ((rc = read_back_decode_status(c, d, status))) return rc;
+    if ((rc = fri_hip_decode_region_tiled420_dev(p, p->coefs, quality, 0, 0, p->grid.width, p->grid.height, p->region, nullptr))) return rc;
+    HIP_TRY(c, hipMemcpy(pixels, p->region, bytes, hipMemcpyDeviceToHost));
+    return FRI_HIP_OK;
+}
+
 } // extern "C"

@@ -88,5 +88,17 @@ FRI_RANS_HD bool put_division(uint64_t &x, uint32_t start, uint32_t freq, uint32
     return emit;
 }
 
+// The decoder step (rans64.h, Rans64DecGet / Rans64DecAdvance), one source for RansDecoderMulti (host/emit.cpp) and the device decoder (k13_decode.hip).
+// get: the slot of state x, its low scale_bits bits. advance: the symbol [start, start + freq) taken out of x; true when the new state fell below
+// kInitialState and wants the stream's next word, which refill shifts in. The shift amounts are masked like the encoder's, so a scale of 0 or of 64 gives the
+// same state on both sides (slot 0 always, the state multiplied by freq).
+FRI_RANS_HD uint32_t get(uint64_t x, uint32_t scale_bits) { return (uint32_t)(x & ((1ull << (scale_bits & 63u)) - 1ull)); }
+FRI_RANS_HD bool advance(uint64_t &x, uint32_t start, uint32_t freq, uint32_t scale_bits) {
+    const uint64_t mask = (1ull << (scale_bits & 63u)) - 1ull;
+    x = (uint64_t)freq * (x >> (scale_bits & 63u)) + (x & mask) - start;
+    return x < kInitialState;
+}
+FRI_RANS_HD void refill(uint64_t &x, uint32_t word) { x = (x << 32) | word; }
+
 } // namespace rans
 } // namespace fri

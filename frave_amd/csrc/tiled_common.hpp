@@ -1,6 +1,6 @@
 // tiled_common.hpp -- what the two tiled plan kinds of the C ABI share (fri_hip_tiled.cpp, fri_hip_tiled420.cpp): the tile grid, the first-fit search for a
-// tile shape, the skeleton of a tiled plan's creation, the host form of the size estimate, and the coded route - K11 over a batch of planes with its one second
-// pass, and the read-back behind it. Private to libfri_hip.so.
+// tile shape, the skeleton of a tiled plan's creation, the host form of the size estimate, and the coded routes - K11 over a batch of planes with its one second
+// pass, and the read-back behind it; the upload of coded planes and K13 over them. Private to libfri_hip.so.
 #pragma once
 #include "fri_hip_internal.hpp"
 
@@ -167,6 +167,70 @@ inline int read_back_coded(fri_hip_ctx *c, const RansOutputs &out, std::initiali
     if (most_off)
         HIP_TRY(c, hipMemcpy2D(off_values, 1024 * sizeof(uint16_t), out.d_off, 1024 * sizeof(uint16_t), most_off * sizeof(uint16_t), planes * 10, hipMemcpyDeviceToHost));
     return out_of_range ? FRI_HIP_ERR_OUT_OF_RANGE : refused ? FRI_HIP_ERR_INVALID_ARGUMENT : FRI_HIP_OK;
+}
+
+/* ---- the coded decode: fri_hip_decode_image_tiled*_coded in front of the inverse kernel ---- */
+// The caller's coded planes (fri_tiled_parse_coded's layout) on the host, and the same on the device once upload_coded has run: every plane's row up to the longest
+// plane (rows `stride` words apart), every context's list up to the longest list; d_counts = n_words [planes], then models [planes][10][4], then K13's status
+// [planes][4]; d_params = value_params [planes][3][6], then width_params.
+struct CodedPlanes {
+    const uint32_t *words;
+    size_t word_stride;
+    const uint32_t *n_words, *models;
+    const uint16_t *off_values;
+    const float *value_params, *width_params;
+    bool complete() const { return words && n_words && models && off_values && value_params && width_params; }
+};
+struct CodedOnDevice {
+    size_t planes = 0, stride = 0;
+    uint32_t *d_words = nullptr, *d_counts = nullptr;
+    uint16_t *d_off = nullptr;
+    float *d_params = nullptr;
+    uint8_t *d_scratch = nullptr;
+    uint32_t *d_n_words() const { return d_counts; }
+    uint32_t *d_models() const { return d_counts + planes; }
+    uint32_t *d_status() const { return d_counts + 41 * planes; }
+};
+
+// P holds the buffers under the same names in both kinds (rans_counts, rans_off, rans_scratch, params); the word rows go into `d_words`.
+template <typename P>
+int upload_coded(P *p, const CodedPlanes &in, size_t planes, Grown<uint32_t> &d_words, CodedOnDevice &out) {
+    fri_hip_ctx *c = p->ctx;
+    size_t longest = 1, most_off = 0;
+    for (size_t k = 0; k < planes; k++) {
+        longest = std::max(longest, std::min<size_t>(in.n_words[k], in.word_stride));
+        for (int b = 0; b < 10; b++) most_off = std::max<size_t>(most_off, std::min<uint32_t>(in.models[(k * 10 + b) * 4 + 1], 1024u));
+    }
+    int rc;
+    if ((rc = grow(c, d_words, planes * longest)) || (rc = grow(c, p->rans_counts, planes * 45)) || (rc = grow(c, p->rans_off, planes * 10 * 1024)) ||
+        (rc = grow(c, p->params, planes * 36)) || (rc = grow(c, p->rans_scratch, decode_scratch_layout((uint32_t)planes).total + 1024))) // (two batches: each layout rounds up on its own)
+        return rc;
+    out.planes = planes, out.stride = longest, out.d_words = d_words, out.d_counts = p->rans_counts, out.d_off = p->rans_off, out.d_params = p->params, out.d_scratch = p->rans_scratch;
+    if (in.word_stride) // (a stride of 0 has no rows: every plane is then truncated)
+        HIP_TRY(c, hipMemcpy2D(out.d_words, longest * sizeof(uint32_t), in.words, in.word_stride * sizeof(uint32_t), std::min(longest, in.word_stride) * sizeof(uint32_t), planes,
+                               hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(out.d_n_words(), in.n_words, planes * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(out.d_models(), in.models, planes * 40 * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (most_off)
+        HIP_TRY(c, hipMemcpy2D(out.d_off, 1024 * sizeof(uint16_t), in.off_values, 1024 * sizeof(uint16_t), most_off * sizeof(uint16_t), planes * 10, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(out.d_params, in.value_params, planes * 18 * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(out.d_params + planes * 18, in.width_params, planes * 18 * sizeof(float), hipMemcpyHostToDevice));
+    return FRI_HIP_OK;
+}
+
+// K13 over the planes first .. first + count - 1 on `plan`, plane first + k into d_coefs + k * coef_stride; on the null stream
+inline int decode_coded_batch(fri_hip_plan *plan, const CodedOnDevice &d, size_t first, size_t count, int32_t *d_coefs, size_t coef_stride) {
+    return fri_hip_decode_planes_dev(plan, (uint32_t)count, d.d_words + first * d.stride, d.stride, d.d_n_words() + first, d.d_models() + first * 40, d.d_off + first * 10 * 1024,
+                                     d.d_params + first * 18, d.d_params + (d.planes + first) * 18, d_coefs, coef_stride, d.d_status() + first * 4,
+                                     d.d_scratch + (first ? decode_scratch_layout((uint32_t)first).total : 0), nullptr);
+}
+
+// the status down; FRI_HIP_ERR_INVALID_ARGUMENT when a plane's bits are non-zero
+inline int read_back_decode_status(fri_hip_ctx *c, const CodedOnDevice &d, uint32_t *status) {
+    HIP_TRY(c, hipMemcpy(status, d.d_status(), d.planes * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < d.planes; k++)
+        if (status[4 * k]) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    return FRI_HIP_OK;
 }
 
 } // namespace fri::host

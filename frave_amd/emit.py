@@ -53,6 +53,7 @@ def load_library():
         L.fri_coded_encode_image.argtypes = [u32, u32, u32, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, sz, vp, C.c_char_p, sz]
         L.fri_tiled_info.argtypes = [vp, sz, vp]
         L.fri_tiled_decode.argtypes = [vp, sz, u32, vp, vp, sz, C.c_char_p, sz]
+        L.fri_tiled_parse_coded.argtypes = [vp, sz, vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp, vp, vp, C.c_char_p, sz]
         L.fri_tiled_region_tiles.argtypes = [u32, u32, u32, u32, u32, u32, u32, u32, vp]
         L.fri_tiled_decode_region.argtypes = [vp, sz, u32, u32, u32, u32, u32, vp, vp, vp, sz, C.c_char_p, sz]
         _lib = L
@@ -407,6 +408,36 @@ def tiled_decode(frv, threads=0):
     if rc != 0:
         raise EmitError(err.value.decode() or f"fri_tiled_decode: {rc}")
     return ti, coefs
+
+
+def tiled_parse_coded(frv, word_stride=None):
+    """fri_tiled_parse_coded: a `frit` file back to its coded planes, the inverse of tiled_encode_from_coded[420] and what PlanTiled[420].decode_coded takes -
+    (TiledInfo, words uint32 [P][word_stride], n_words [P], models [P][10][4] = {max_freq_bits as the file carries it, n_off, 0, 0}, off_values uint16 [P][10][1024],
+    value_params, width_params [P][3][6]), P = n_tiles C planes in the file's plane order. Nothing is decoded. word_stride: None sizes the rows by the longest plane
+    (one size query first); a stride shorter than a plane raises an EmitError that names the plane and carries the complete counts as .n_words."""
+    data = np.frombuffer(frv, np.uint8)
+    info = np.zeros(8, np.uint32)
+    err = C.create_string_buffer(256)
+    L = load_library()
+    rc = L.fri_tiled_parse_coded(_p(data), data.size, _p(info), 0, None, 0, None, None, None, None, None, err, 256)
+    if rc != -3:
+        raise EmitError(err.value.decode() or f"fri_tiled_parse_coded: {rc}")
+    ti = _tiled_info(info)
+    planes = ti[4] * ti[5] * ti[6]
+    nw = np.zeros(planes, np.uint32)
+    rc = L.fri_tiled_parse_coded(_p(data), data.size, _p(info), planes, None, 0, _p(nw), None, None, None, None, err, 256)
+    if rc != 0:
+        raise EmitError(err.value.decode() or f"fri_tiled_parse_coded: {rc}")
+    stride = max(int(nw.max()), 1) if word_stride is None else int(word_stride)
+    words = np.zeros((planes, stride), np.uint32)
+    models, off = np.zeros((planes, 10, 4), np.uint32), np.zeros((planes, 10, 1024), np.uint16)
+    vp, wp = np.zeros((planes, 3, 6), np.float32), np.zeros((planes, 3, 6), np.float32)
+    rc = L.fri_tiled_parse_coded(_p(data), data.size, _p(info), planes, _p(words), stride, _p(nw), _p(models), _p(off), _p(vp), _p(wp), err, 256)
+    if rc != 0:
+        e = EmitError(err.value.decode() or f"fri_tiled_parse_coded: {rc}")
+        e.n_words = nw
+        raise e
+    return ti, words, nw, models, off, vp, wp
 
 
 def tiled_region_tiles(width, height, tile_w, tile_h, x, y, w, h):

@@ -228,14 +228,12 @@ RansDecoderMulti::RansDecoderMulti(const std::vector<uint8_t> &d) {
         pos_ += 2;
     }
 }
-uint32_t RansDecoderMulti::get_at(int s, uint32_t scale_bits) const { return (uint32_t)(x_[s] & (((uint64_t)1 << scale_bits) - 1)); }
+uint32_t RansDecoderMulti::get_at(int s, uint32_t scale_bits) const { return fri::rans::get(x_[s], scale_bits); }
 void RansDecoderMulti::advance_at(int s, uint32_t start, uint32_t freq, uint32_t scale_bits) {
-    const uint64_t mask = ((uint64_t)1 << scale_bits) - 1;
     uint64_t x = x_[s];
-    x = (uint64_t)freq * (x >> scale_bits) + (x & mask) - start;
-    if (x < (1ull << 31)) {
+    if (fri::rans::advance(x, start, freq, scale_bits)) { // (the step the device decoder runs: csrc/rans_step.hpp)
         if (pos_ < w_.size())
-            x = (x << 32) | w_[pos_++];
+            fri::rans::refill(x, w_[pos_++]);
         else
             ok_ = false;
     }
@@ -904,7 +902,7 @@ std::vector<uint8_t> serialize(uint32_t height, uint32_t width, ColorSpaceCode c
     return s;
 }
 
-std::string deserialize(const std::vector<uint8_t> &b, ParsedImage &out) {
+std::string deserialize(const std::vector<uint8_t> &b, ParsedImage &out, bool models) {
     size_t o = 0;
     auto need = [&](size_t n) { return o + n <= b.size(); };
     auto u32 = [&]() {
@@ -963,8 +961,10 @@ std::string deserialize(const std::vector<uint8_t> &b, ParsedImage &out) {
                 c.off_distribution_values.push_back((uint16_t)(b[o] | b[o + 1] << 8));
                 o += 2;
             }
-            const std::string err = c.finalize(n_ctx); // serialize.rs:232: the decoder rebuilds the table from the two fields
-            if (!err.empty()) return err;
+            if (models) { // serialize.rs:232: the decoder rebuilds the table from the two fields (without: they stay as the file carries them)
+                const std::string err = c.finalize(n_ctx);
+                if (!err.empty()) return err;
+            }
             cur.contexts[n_ctx++] = c;
         } else if (m1 == kDAT[1]) {
             if (!need(8)) return "Malformed image bytes";
@@ -973,6 +973,7 @@ std::string deserialize(const std::vector<uint8_t> &b, ParsedImage &out) {
             cur.data.assign(b.begin() + o, b.begin() + o + n);
             o += n;
         } else if (m1 == kEOC[1]) {
+            cur.n_contexts = (uint32_t)n_ctx;
             out.channels.push_back(cur);
             out.params.push_back(prm);
             cur = ChannelStream{};
@@ -1305,6 +1306,65 @@ std::string decode_tiled(const uint8_t *b, size_t len, unsigned threads, TiledIn
         }
         return "";
     }, file_tile);
+}
+
+// The inverse of encode_tiled_from_coded / encode_tiled_from_coded420: nothing is decoded and no model is built, deserialize walks every payload's markers and the
+// parts are copied out in K11's layout. One thread: the work is a copy of the file.
+std::string parse_tiled_coded(const uint8_t *b, size_t len, TiledInfo &info, size_t plane_cap, bool &too_small, uint32_t *words, size_t word_stride, uint32_t *n_words,
+                              uint32_t *models, uint16_t *off_values, float *value_params, float *width_params) {
+    too_small = false;
+    std::vector<uint64_t> offset;
+    std::string e = parse_tiled(b, len, info, offset);
+    if (!e.empty()) return e;
+    { // the cells of the tile lattices, as decode_tiled reports them
+        uint32_t cells = 0;
+        uint64_t n_some = 0;
+        e = lattice_counts(info.tile_w, info.tile_h, cells, n_some);
+        if (!e.empty()) return e;
+        info.n_cells = cells;
+        if (info.s420) {
+            e = lattice_counts((info.tile_w + 1) / 2, (info.tile_h + 1) / 2, cells, n_some);
+            if (!e.empty()) return e;
+            info.n_cells_chroma = cells;
+        }
+    }
+    const size_t n = (size_t)info.nx * info.ny, planes = n * info.channels;
+    if (!n_words || plane_cap < planes) return too_small = true, "";
+    const bool fill = words != nullptr;
+    std::string over; // the first plane longer than word_stride: n_words is completed before it is reported
+    for (size_t t = 0; t < n; t++) {
+        const auto tile_error = [&](const std::string &why) { return "tile " + std::to_string(t) + ": " + why; };
+        ParsedImage img;
+        const std::string de = deserialize(std::vector<uint8_t>(b + offset[t], b + offset[t + 1]), img, false);
+        if (!de.empty()) return tile_error(de);
+        if (img.channels.size() != info.channels || img.s420 != info.s420) return tile_error(kMalformedTiled);
+        for (const ChannelStream &c : img.channels)
+            if (c.n_contexts != (uint32_t)kContexts) return tile_error("Malformed image bytes"); // fewer than ten EHD segments (decode_tiled's check)
+        for (uint32_t ch = 0; ch < info.channels; ch++) {
+            // plane order: tile by tile and channel by channel, or - 4:2:0 - the luma planes, then Cb and Cr tile by tile
+            const size_t k = info.s420 ? (ch == 0 ? t : n + 2 * t + ch - 1) : t * info.channels + ch;
+            const ChannelStream &c = img.channels[ch];
+            const size_t nw = c.data.size() / 4; // (a tail of one to three bytes is not a word: RansDecoderMulti)
+            if (nw > 0xFFFFFFFFull) return tile_error("channel " + std::to_string(ch) + ": more than 2^32 words");
+            n_words[k] = (uint32_t)nw;
+            if (!fill) continue;
+            if (nw > word_stride) {
+                if (over.empty()) over = "plane " + std::to_string(k) + ": " + std::to_string(nw) + " words, the stride holds " + std::to_string(word_stride);
+                continue;
+            }
+            uint32_t *w = words + k * word_stride;
+            for (size_t i = 0; i < nw; i++) w[i] = get_u32(c.data.data() + 4 * i);
+            for (int ctx = 0; ctx < kContexts; ctx++) {
+                const AnsContext &a = c.contexts[ctx];
+                uint32_t *m = models + (k * kContexts + ctx) * 4;
+                m[0] = a.max_freq_bits, m[1] = (uint32_t)a.off_distribution_values.size(), m[2] = 0, m[3] = 0; // (deserialize holds a list to 1024 entries)
+                std::copy(a.off_distribution_values.begin(), a.off_distribution_values.end(), off_values + (k * kContexts + ctx) * kAlphabet);
+            }
+            std::memcpy(value_params + k * 18, img.params[ch].value, sizeof(img.params[ch].value));
+            std::memcpy(width_params + k * 18, img.params[ch].width, sizeof(img.params[ch].width));
+        }
+    }
+    return over;
 }
 
 } // namespace emit

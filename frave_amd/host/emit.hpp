@@ -98,6 +98,7 @@ struct ChannelStream {
     std::array<AnsContext, kContexts> contexts;
     std::vector<uint8_t> data;
     uint64_t n_symbols = 0;
+    uint32_t n_contexts = 0; // deserialize: the EHD segments the file carried for this channel (a decoder wants all ten)
 };
 // coefs / bucket / prediction: this channel's [n_cells][512] planes; hist: [10][1024] counts of K2.
 // Returns "" or an error (conditions under which the reference panics).
@@ -165,7 +166,9 @@ struct ParsedImage {
     std::vector<ChannelStream> channels; // contexts rebuilt from (max_freq_bits, off_distribution_values) like serialize.rs:214-237
     std::vector<ChannelParams> params;
 };
-std::string deserialize(const std::vector<uint8_t> &bytes, ParsedImage &out);
+// models = false: the contexts are not finalised - max_freq_bits and the off-distribution list stay what the file carries, freqs and cdf stay zero
+// (parse_tiled_coded: the device rebuilds the models)
+std::string deserialize(const std::vector<uint8_t> &bytes, ParsedImage &out, bool models = true);
 
 // ---- decoder -------------------------------------------------------------------------------------------------------
 // entropy_coding::decode (:352-443) for one channel: the symbols come back in stream order, each one's context (bucket and
@@ -250,6 +253,14 @@ bool region_tiles(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t til
 // `range` is filled whenever `info` is. "invalid region" for a region region_tiles refuses. A tile's error names its index in the file's grid.
 std::string decode_tiled(const uint8_t *frv, size_t len, unsigned threads, TiledInfo &info, int32_t *coefs, size_t coef_cap, bool &too_small, const Region *region = nullptr,
                          TileRange *range = nullptr);
+// A `frit` file back to the coded planes it was written from (encode_tiled_from_coded, encode_tiled_from_coded420; the device decoder K13 reads them): per plane, in
+// the plane order the header defines, words [planes][word_stride] and n_words [planes] (the bytes between DAT and EOC as little-endian words, len / 4 rounded down),
+// models [planes][10][4] = {max_freq_bits as the file carries it, n_off, 0, 0}, off_values [planes][10][1024] (a context's first n_off, in file order) and
+// value_params / width_params [planes][3][6]. Checks what decode_tiled checks; info as decode_tiled fills it. too_small: n_words is NULL or plane_cap holds fewer than
+// n_tiles x channels entries - `info` is filled, nothing else. words == NULL: only info and n_words. A plane longer than word_stride is the error, naming the
+// plane, with n_words complete.
+std::string parse_tiled_coded(const uint8_t *frv, size_t len, TiledInfo &info, size_t plane_cap, bool &too_small, uint32_t *words, size_t word_stride, uint32_t *n_words,
+                              uint32_t *models, uint16_t *off_values, float *value_params, float *width_params);
 
 } // namespace emit
 } // namespace libfri

@@ -340,6 +340,17 @@ int fri_tiled_decode(const uint8_t *frv, size_t len, uint32_t threads, uint32_t 
     return too_small ? -3 : 0;
 }
 
+int fri_tiled_parse_coded(const uint8_t *frv, size_t len, uint32_t info[8], uint64_t n_planes, uint32_t *words, uint64_t word_stride, uint32_t *n_words, uint32_t *models,
+                          uint16_t *off_values, float *value_params, float *width_params, char *err, size_t err_cap) {
+    if (!frv || !info || (words && (!n_words || !models || !off_values || !value_params || !width_params))) return fail(err, err_cap, "invalid argument");
+    TiledInfo t;
+    bool too_small = false;
+    const std::string e = parse_tiled_coded(frv, len, t, (size_t)n_planes, too_small, words, (size_t)word_stride, n_words, models, off_values, value_params, width_params);
+    if (!e.empty()) return fail(err, err_cap, e, -2);
+    fill_tiled_info(t, info);
+    return too_small ? -3 : 0;
+}
+
 int fri_tiled_region_tiles(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint32_t out[4]) {
     TileRange r;
     if (!out || !region_tiles(width, height, tile_w, tile_h, Region{x, y, w, h}, r)) return -1;

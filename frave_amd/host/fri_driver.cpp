@@ -26,9 +26,11 @@
 //                                                            --tile-size T --420 stays refused: tiled 4:2:0 has this option of its own
 //                                                            --device-rans (with --tile-size or --tile-size-420): the rANS coder runs on the device too (K11), the host writes the
 //                                                            container around the coded planes - the same file
-//   fri_driver decode-file <in.frv> <out.pgm|.ppm|.bmp|.pam> [--region X,Y,W,H]  (.pam for a file with an alpha plane, and for no other) container -> rANS / context decoding on the host -> dequantisation + inverse
+//   fri_driver decode-file <in.frv> <out.pgm|.ppm|.bmp|.pam> [--region X,Y,W,H | --device-rans]  (.pam for a file with an alpha plane, and for no other) container -> rANS / context decoding on the host -> dequantisation + inverse
 //                                                            transform on the device (fri-cli decode, crates/fri-cli/src/commands/decode.rs); a flagged file
 //                                                            comes back as RGB, a lossy file with its quality's matrix and the midpoint dequantiser
+//                                                            --device-rans: a `frit` file (4:4:4 or 4:2:0) is entropy-decoded on the device too (K13: parse -> fri_hip_decode_image_tiled_coded);
+//                                                            refused on a `frif` file (one chain per channel) and together with --region (out of scope)
 //                                                            --region X,Y,W,H: only that rectangle of the image (FRIDecoder::decode_region) - of a `frit` file only
 //                                                            the tiles it touches are decoded; a `frif` file is decoded whole and cropped; no untiled 4:2:0 file and no alpha file
 //   fri_driver batch <width> <height> <channels> <n_images> [--gpus N]
@@ -682,17 +684,24 @@ int main(int argc, char **argv) {
             std::fprintf(stderr, "cannot open %s\n", argv[2]);
             return 1;
         }
-        bool has_region = false;
+        bool has_region = false, device_rans = false;
         unsigned rx = 0, ry = 0, rw = 0, rh = 0;
         for (int i = 4; i < argc; i++) {
             char tail = 0;
-            if (std::string(argv[i]) == "--region" && i + 1 < argc && std::sscanf(argv[i + 1], "%u,%u,%u,%u%c", &rx, &ry, &rw, &rh, &tail) == 4) has_region = true, i++;
+            if (std::string(argv[i]) == "--device-rans") device_rans = true;
+            else if (std::string(argv[i]) == "--region" && i + 1 < argc && std::sscanf(argv[i + 1], "%u,%u,%u,%u%c", &rx, &ry, &rw, &rh, &tail) == 4) has_region = true, i++;
             else {
-                std::fprintf(stderr, "decode-file: unknown or incomplete option %s (--region X,Y,W,H)\n", argv[i]);
+                std::fprintf(stderr, "decode-file: unknown or incomplete option %s (--region X,Y,W,H, --device-rans)\n", argv[i]);
                 return 2;
             }
         }
-        auto img = has_region ? libfri::FRIDecoder().decode_region(bytes, rx, ry, rw, rh) : libfri::FRIDecoder().decode(bytes);
+        if (device_rans && has_region) {
+            std::fprintf(stderr, "decode-file: --device-rans with --region is out of scope: the device decoder takes whole tiled files (drop one of the two)\n");
+            return 2;
+        }
+        libfri::EncoderOpts dec_opts;
+        dec_opts.device_rans = device_rans;
+        auto img = has_region ? libfri::FRIDecoder().decode_region(bytes, rx, ry, rw, rh) : libfri::FRIDecoder().decode(bytes, dec_opts);
         if (!img.ok) {
             std::fprintf(stderr, "%s\n", img.error.c_str());
             return 1;

@@ -530,10 +530,82 @@ Result<RasterImage> decode_tiled_bytes(const std::vector<uint8_t> &data, const E
     r.ok = true;
     return r;
 }
+
+std::string set_plan_stream_order(fri_hip_plan *plan, Device &dev);
+
+// a `frit` file through the device decoder (opts.device_rans): the container walked on the host, the coded planes up - about a tenth of the int32 planes - then K13,
+// the inverse kernel over all tiles and the merge
+Result<RasterImage> decode_tiled_coded_bytes(const std::vector<uint8_t> &data, const EncoderOpts &opts) {
+    Result<RasterImage> r;
+    auto fail = [&](const std::string &why) {
+        r.error = "Failed to decode: " + why;
+        return r;
+    };
+    emit::TiledInfo ti;
+    bool too_small = false;
+    std::string e = emit::parse_tiled_coded(data.data(), data.size(), ti, 0, too_small, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr); // header, table, lattice
+    if (!e.empty()) return fail(e);
+    const size_t planes = (size_t)ti.nx * ti.ny * ti.channels;
+    std::vector<uint32_t> n_words(planes);
+    e = emit::parse_tiled_coded(data.data(), data.size(), ti, planes, too_small, nullptr, 0, n_words.data(), nullptr, nullptr, nullptr, nullptr);
+    if (!e.empty()) return fail(e);
+    const size_t stride = std::max<uint32_t>(1, *std::max_element(n_words.begin(), n_words.end()));
+    std::vector<uint32_t> words(planes * stride), models(planes * 40), status(planes * 4);
+    std::vector<uint16_t> off(planes * 10 * 1024);
+    std::vector<float> vp(planes * 18), wp(planes * 18);
+    e = emit::parse_tiled_coded(data.data(), data.size(), ti, planes, too_small, words.data(), stride, n_words.data(), models.data(), off.data(), vp.data(), wp.data());
+    if (!e.empty()) return fail(e);
+    Device dev(opts.device);
+    if (!dev.ok()) return fail(dev.error());
+    auto refused = [&](int rc) { // the first plane the device refused, as the host decoder words it
+        for (size_t k = 0; k < planes; k++)
+            if (status[4 * k]) {
+                const uint32_t bits = status[4 * k];
+                return "plane " + std::to_string(k) + ": " + (bits & FRI_HIP_DECODE_BAD_MODEL ? "Malformed image bytes" : bits & FRI_HIP_DECODE_BAD_SLOT ? "stream does not match the model" : "stream truncated") +
+                       " (symbol " + std::to_string(status[4 * k + 1]) + ")";
+            }
+        return dev.describe(rc);
+    };
+    if (ti.s420) {
+        fri_hip_plan_tiled420 *raw420 = nullptr;
+        if (const int rc = fri_hip_plan_tiled420_create(dev.ctx(), ti.width, ti.height, ti.tile_w, ti.tile_h, FRI_HIP_TILED_ALLOW_HOLES, &raw420); rc != FRI_HIP_OK) return fail(dev.describe(rc));
+        Tiled420Plan plan420(raw420);
+        for (fri_hip_plan *inner : {fri_hip_plan_tiled420_luma(raw420), fri_hip_plan_tiled420_chroma(raw420)})
+            if (e = set_plan_stream_order(inner, dev); !e.empty()) return fail(e);
+        r.value.metadata = ImageMetadata{ti.height, ti.width, ColorSpace::RGB};
+        r.value.data.resize((size_t)ti.width * ti.height * 3);
+        const int rc = fri_hip_decode_image_tiled420_coded(raw420, words.data(), stride, n_words.data(), models.data(), off.data(), vp.data(), wp.data(), (int)ti.quality,
+                                                           r.value.data.data(), status.data());
+        if (rc != FRI_HIP_OK) return fail(refused(rc));
+        r.ok = true;
+        return r;
+    }
+    fri_hip_plan_tiled *raw = nullptr;
+    if (const int rc = fri_hip_plan_tiled_create(dev.ctx(), ti.width, ti.height, ti.channels, ti.tile_w, ti.tile_h, FRI_HIP_TILED_ALLOW_HOLES, &raw); rc != FRI_HIP_OK) return fail(dev.describe(rc));
+    TiledPlan plan(raw);
+    fri_hip_plan *tile = fri_hip_plan_tiled_tile(raw);
+    if (e = set_plan_stream_order(tile, dev); !e.empty()) return fail(e);
+    if (e = set_colour_transform(tile, ti.rct, dev, ti.ycbcr); !e.empty()) return fail(e);
+    std::array<int32_t, 32> qm = opts.quantization_matrix;
+    if (ti.quality && fri_hip_quality_matrix((int)ti.quality, qm.data()) != FRI_HIP_OK) return fail("invalid quality");
+    int rc = fri_hip_plan_set_dequantiser(tile, ti.quality ? FRI_HIP_DEQUANT_MIDPOINT : FRI_HIP_DEQUANT_REFERENCE);
+    r.value.metadata = ImageMetadata{ti.height, ti.width, ti.channels == 1 ? ColorSpace::Luma : ColorSpace::RGB};
+    r.value.data.resize((size_t)ti.width * ti.height * ti.channels);
+    if (rc == FRI_HIP_OK)
+        rc = fri_hip_decode_image_tiled_coded(raw, words.data(), stride, n_words.data(), models.data(), off.data(), vp.data(), wp.data(), qm.data(), r.value.data.data(), status.data());
+    if (rc != FRI_HIP_OK) return fail(refused(rc));
+    r.ok = true;
+    return r;
+}
 } // namespace
 
 Result<RasterImage> FRIDecoder::decode_region(const std::vector<uint8_t> &data, uint32_t x, uint32_t y, uint32_t w, uint32_t h, const EncoderOpts &opts) {
     const emit::Region region{x, y, w, h};
+    if (opts.device_rans) {
+        Result<RasterImage> refused;
+        refused.error = "Failed to decode: region decode on the device decoder is out of scope (decode the region on the host, or the whole image on the device)";
+        return refused;
+    }
     if (data.size() >= 4 && std::memcmp(data.data(), "frit", 4) == 0) return decode_tiled_bytes(data, opts, &region);
     // an ordinary file has no tiles to choose from: all of it is decoded and the region cut out on the host
     Result<RasterImage> r;
@@ -563,8 +635,12 @@ Result<RasterImage> FRIDecoder::decode_region(const std::vector<uint8_t> &data, 
 }
 
 Result<RasterImage> FRIDecoder::decode(const std::vector<uint8_t> &data, const EncoderOpts &opts) {
-    if (data.size() >= 4 && std::memcmp(data.data(), "frit", 4) == 0) return decode_tiled_bytes(data, opts);
+    if (data.size() >= 4 && std::memcmp(data.data(), "frit", 4) == 0) return opts.device_rans ? decode_tiled_coded_bytes(data, opts) : decode_tiled_bytes(data, opts);
     Result<RasterImage> r;
+    if (opts.device_rans) {
+        r.error = "Failed to decode: the device decoder reads tiled (`frit`) files only: an untiled file is one dependent chain per channel, which the host decodes faster";
+        return r;
+    }
     auto c = stages::serialize::decode(data);
     if (!c.ok) {
         r.error = "Failed to decode: " + c.error; // decoder.rs:56

@@ -84,6 +84,8 @@ struct EncoderOpts { // encoder.rs:58-64
     bool ycbcr = false;
     // encode_bytes_tiled and encode_bytes_tiled420 only: the rANS coder runs on the device too (K11, fri_hip_encode_image_tiled_coded / _tiled420_coded) and the host
     // only assembles the container (emit::encode_tiled_from_coded / _coded420) - the same file, byte for byte, as the host coder writes.
+    // FRIDecoder::decode of a `frit` file: entropy decoding runs on the device too (K13: emit::parse_tiled_coded, then fri_hip_decode_image_tiled_coded /
+    // _tiled420_coded) - the same pixels. An untiled `frif` file is refused with it (one dependent chain per channel), and so is decode_region (out of scope).
     bool device_rans = false;
     EncoderOpts() { quantization_matrix.fill(1); }
 };
@@ -308,7 +310,8 @@ class FRIDecoder { // decoder.rs:44-59
   public:
     // the whole pipeline of decoder.rs:16-40: EncodedImage -> EntropyDecoding -> Dequantization -> WaveletTransform -> RawImage.
     // Container parsing and entropy decoding run on the host, dequantisation + inverse transform on the device. A tiled file (`frit`) is recognised by its magic:
-    // fri_tiled_decode's workers, then fri_hip_decode_image_tiled - or, for a tiled 4:2:0 file, fri_hip_decode_image_tiled420.
+    // fri_tiled_decode's workers, then fri_hip_decode_image_tiled - or, for a tiled 4:2:0 file, fri_hip_decode_image_tiled420. With opts.device_rans the tiles'
+    // planes are decoded on the device instead (fri_tiled_parse_coded, then fri_hip_decode_image_tiled_coded / _tiled420_coded).
     Result<RasterImage> decode(const std::vector<uint8_t> &data, const EncoderOpts &opts = EncoderOpts());
     // The region x, y, w, h (image pixels; include/fri_emit.h, "Region decode") of the image `data` holds: the crop [y : y + h, x : x + w] of what decode returns,
     // as a raster of w x h. A tiled file pays for the tiles the region touches and no others: fri_tiled_decode_region's workers, then

@@ -216,6 +216,18 @@ int fri_tiled_info(const uint8_t *frv, size_t len, uint32_t info[8]);
  * filled when coefs is NULL or coef_cap (in elements) is too small. A tiled 4:2:0 file: coefs in plane order, n (F_y + 2 F_c) x 512 elements - what
  * fri_hip_decode_image_tiled420 takes. */
 int fri_tiled_decode(const uint8_t *frv, size_t len, uint32_t threads, uint32_t info[8], int32_t *coefs, size_t coef_cap, char *err, size_t err_cap);
+/* A `frit` file back to the coded planes it is made of: the inverse of fri_tiled_encode_from_coded and fri_tiled_encode_from_coded420, and what the device decoder
+ * reads (K13: fri_hip_decode_planes_dev, fri_hip_decode_image_tiled_coded, include/fri_hip.h). One function for both kinds of file; P = n_tiles C planes in the
+ * order the header defines - tile by tile and channel by channel, or plane order for a tiled 4:2:0 file. Per plane p: words uint32 [P][word_stride], of which the
+ * first n_words[p] are the bytes between DAT and EOC as little-endian words (length / 4 rounded down: a tail of one to three bytes is no word, as in the decoder);
+ * models uint32 [P][10][4] = {max_freq_bits as the file carries it, n_off, 0, 0}; off_values uint16 [P][10][1024], of which a context's first n_off are written, in
+ * file order; value_params / width_params [P][3][6]. A context the file does not carry reads {0, 0, 0, 0}. n_planes: the capacity of the per-plane arrays in planes.
+ * Checks what fri_tiled_decode checks - the header, the table, every payload's 16-byte header, the markers of every payload - and `info` is fri_tiled_info's;
+ * builds no model and decodes nothing, on the calling thread. Returns -3 with `info` filled when n_words is NULL or n_planes < P. With words == NULL only `info` and
+ * n_words are filled (0): the size query for word_stride. A plane with n_words[p] > word_stride is an error that names the first such plane (-2), with n_words
+ * complete; planes that fit are written. */
+int fri_tiled_parse_coded(const uint8_t *frv, size_t len, uint32_t info[8], uint64_t n_planes, uint32_t *words, uint64_t word_stride, uint32_t *n_words, uint32_t *models,
+                          uint16_t *off_values, float *value_params, float *width_params, char *err, size_t err_cap);
 /* The tile range of a region ("Region decode" above): out = {i0, j0, ni, nj} by that arithmetic and nothing else. -1 for a zero size (of the image, the tile or
  * the region), a region that leaves the image, or out = NULL. */
 int fri_tiled_region_tiles(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint32_t out[4]);

@@ -892,6 +892,69 @@ int fri_hip_encode_image_tiled_coded(fri_hip_plan_tiled *p, const uint8_t *pixel
 int fri_hip_encode_image_tiled420_coded(fri_hip_plan_tiled420 *p, const uint8_t *pixels, int quality, float *value_params, float *width_params, uint32_t *words,
                                         size_t word_stride, uint32_t *n_words, uint32_t *models, uint16_t *off_values, uint32_t *status);
 
+/* ---- the rANS and context decoder on the device (K13, k13_decode.hip) ---------------------------- */
+/* The decoder's entropy stage - rANS words back to coefficient planes (host/emit.cpp, decode_channel) - for a batch of planes that live on one lattice: the
+ * channels of the tiles of a `frit` file. A plane is ONE dependent chain of num_some steps, since every symbol's context is computed from the coefficients
+ * decoded before it; the planes are what runs side by side. An untiled `frif` image is one such chain per channel and has no business here. The coder step is
+ * the host's, from one header (csrc/rans_step.hpp, get / advance / refill), the model is the one AnsContext::finalize builds from what the file carries
+ * (csrc/ans_model.hpp, ans_model_rebuild_file), and the context arithmetic is K2's exact statement of it: the planes are bit for bit fri_tiled_decode's.
+ *
+ * plan: the C = 1 or C = 3 plan whose lattice every plane lives on; it supplies the geometry, the Laplace table and the stream order
+ * (fri_hip_plan_set_stream_order) - without the order the call returns FRI_HIP_ERR_INVALID_ARGUMENT, as the symbol chains do.
+ *
+ * Inputs (device memory), per plane p, in K11's layout - what fri_tiled_parse_coded (include/fri_emit.h) returns for a file:
+ *   d_words   uint32 [n_planes][word_stride], of which the first min(d_n_words[p], word_stride) are read: the channel's rANS data as little-endian words, the
+ *             twenty words of the ten states first (state k = word 2k | word 2k + 1 << 32; state k decodes context 9 - k).
+ *   d_n_words uint32 [n_planes].
+ *   d_models  uint32 [n_planes][10][4], of which {max_freq_bits, n_off} are read, as the container's EHD segment carries them.
+ *   d_off_values uint16 [n_planes][10][1024], of which a context's first min(n_off, 1024) are read; a value above 1023 names no symbol.
+ *   d_value_params / d_width_params f32 [n_planes][3][6].
+ *
+ * Outputs (device memory):
+ *   d_coefs   plane p at d_coefs + p * coef_stride, int32 [F][512] in heap order, None = FRI_HIP_NONE: first 0 on every Some node and FRI_HIP_NONE elsewhere (a
+ *             node not yet decoded reads as 0 in a later context), then one coefficient per step. d_coefs is 16-byte aligned, coef_stride a multiple of 4 and at
+ *             least F * 512; nothing is written beyond a plane's F * 512 elements.
+ *   d_status  uint32 [n_planes][4] = {bits, at, 0, 0}. bits = 0: the plane is what the host decoder returns. Otherwise decoding stopped - the plane holds the
+ *             coefficients decoded so far over the initial values - and bits says why:
+ *               FRI_HIP_DECODE_TRUNCATED (1)  fewer than 20 words, or a renormalisation wanted a word at or past min(n_words, word_stride): "stream truncated"
+ *               FRI_HIP_DECODE_BAD_MODEL (2)  one of the plane's ten models is refused - finalize's error, a final max_freq_bits of 0, or n_off > 1024 (the
+ *                                             host's "Malformed image bytes"); nothing is decoded
+ *               FRI_HIP_DECODE_BAD_SLOT  (4)  a state's slot falls into no symbol's interval, or into an empty one: "stream does not match the model"
+ *             at = 1 + the index of the symbol at which decoding stopped (1 when it never started), 0 when bits is 0.
+ *
+ * Whatever the words, the models and the lists hold, every read stays inside the arrays as laid out here and every write inside the plane: the step loop runs
+ * num_some times at most, a word is read below min(n_words, word_stride) only, a symbol is found among 1024, and every address a coefficient is read from or
+ * written to comes from the plan's tables. A damaged file gives a status.
+ *
+ * d_scratch: fri_hip_decode_scratch_bytes(n_planes) bytes of device memory, 256-byte aligned, the caller's - 80 KiB of model tables per plane (0 for a count
+ * out of range). The _dev call only enqueues on `stream` - two kernels, neither of which waits for another workgroup - and can be captured into a graph.
+ * Nothing is accumulated with atomics: the same inputs give the same bytes in every run. FRI_HIP_ERR_INVALID_ARGUMENT for a null pointer, a count out of range
+ * (1 <= n_planes <= 65535), a misaligned d_coefs or d_scratch, or a coef_stride that is too small or no multiple of 4. */
+#define FRI_HIP_DECODE_TRUNCATED 1u
+#define FRI_HIP_DECODE_BAD_MODEL 2u
+#define FRI_HIP_DECODE_BAD_SLOT 4u
+uint64_t fri_hip_decode_scratch_bytes(uint32_t n_planes);
+int fri_hip_decode_planes_dev(fri_hip_plan *plan, uint32_t n_planes, const uint32_t *d_words, size_t word_stride, const uint32_t *d_n_words, const uint32_t *d_models,
+                              const uint16_t *d_off_values, const float *d_value_params, const float *d_width_params, int32_t *d_coefs, size_t coef_stride,
+                              uint32_t *d_status, void *d_scratch, void *stream);
+/* The same launch bracketed by events on `stream`: us[2] = the microseconds of the model and decode kernels. Synchronises; for measurements. */
+int fri_hip_decode_time_planes_dev(fri_hip_plan *plan, uint32_t n_planes, const uint32_t *d_words, size_t word_stride, const uint32_t *d_n_words, const uint32_t *d_models,
+                                   const uint16_t *d_off_values, const float *d_value_params, const float *d_width_params, int32_t *d_coefs, size_t coef_stride,
+                                   uint32_t *d_status, void *d_scratch, void *stream, double us[2]);
+/* A tiled image from the coded planes of its file (fri_tiled_parse_coded) to pixels: the planes up - every plane's row up to the longest plane, every context's
+ * list up to the longest list - K13 over all n_tiles C planes into the plan's tile coefficient buffer, then exactly what fri_hip_decode_image_tiled runs behind
+ * its upload: the inverse kernel over all tiles with the inner plan's dequantiser and colour transform, then the merge. words uint32 [n_tiles C][word_stride],
+ * n_words [n_tiles C], models [n_tiles C][10][4], off_values uint16 [n_tiles C][10][1024], value_params / width_params [n_tiles C][3][6]; status [n_tiles C][4]
+ * comes back. The inner plan needs its stream order. Returns FRI_HIP_ERR_INVALID_ARGUMENT with the status filled (and no pixels) when a plane's bits are
+ * non-zero. Synchronous. */
+int fri_hip_decode_image_tiled_coded(fri_hip_plan_tiled *p, const uint32_t *words, size_t word_stride, const uint32_t *n_words, const uint32_t *models,
+                                     const uint16_t *off_values, const float *value_params, const float *width_params, const int32_t qmatrix[32], uint8_t *pixels,
+                                     uint32_t *status);
+/* The same for a tiled 4:2:0 image, every per-plane array in plane order ([3 n]...): K13 twice on one stream - the n luma planes on the luma plan, then the 2 n
+ * chroma planes on the chroma plan (both need their stream order) - then what fri_hip_decode_image_tiled420 runs behind its upload, at `quality` (1..99). */
+int fri_hip_decode_image_tiled420_coded(fri_hip_plan_tiled420 *p, const uint32_t *words, size_t word_stride, const uint32_t *n_words, const uint32_t *models,
+                                        const uint16_t *off_values, const float *value_params, const float *width_params, int quality, uint8_t *pixels, uint32_t *status);
+
 /* ---- timing helper ---------------------------------------------------------------------------- */
 /* Runs the forward kernel `iters` times on `stream` bracketed by HIP events recorded on that same
  * stream and returns the mean kernel-to-kernel time per launch in microseconds (bench.py uses it
