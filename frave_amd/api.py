@@ -52,6 +52,8 @@ SYMBOLS = [
     "fri_hip_search_quality_tiled420_dev", "fri_hip_search_quality_ssim_tiled420", "fri_hip_search_quality_ssim_tiled420_dev", "fri_hip_search_quality_for_size_tiled420",
     "fri_hip_search_quality_for_size_tiled420_dev", "fri_hip_encode_image_tiled420_coded",
     "fri_hip_decode_scratch_bytes", "fri_hip_decode_planes_dev", "fri_hip_decode_time_planes_dev", "fri_hip_decode_image_tiled_coded", "fri_hip_decode_image_tiled420_coded",
+    "fri_hip_plan_num_some_levels", "fri_hip_preview_size", "fri_hip_decode_planes_levels_dev", "fri_hip_preview_tiles_dev", "fri_hip_preview_image_tiled",
+    "fri_hip_preview_image_tiled_coded",
 ]
 DECODE_TRUNCATED, DECODE_BAD_MODEL, DECODE_BAD_SLOT = 1, 2, 4  # FRI_HIP_DECODE_*: bits of a plane's status word of fri_hip_decode_planes_dev (include/fri_hip.h)
 RANS_EMPTY_OK = 1  # FRI_HIP_RANS_EMPTY_OK: `flags` of fri_hip_rans_encode_planes_dev - a context without counts is coded (the emitter's FRI_EMIT_EMPTY_OK)
@@ -282,6 +284,12 @@ def load_library():
     L.fri_hip_decode_time_planes_dev.argtypes = [vp, u32, vp, sz, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp]
     L.fri_hip_decode_image_tiled_coded.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp]
     L.fri_hip_decode_image_tiled420_coded.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, i32, vp, vp]
+    L.fri_hip_plan_num_some_levels.argtypes = [vp, u32, vp]
+    L.fri_hip_preview_size.argtypes = [u32, u32, u32, vp]
+    L.fri_hip_decode_planes_levels_dev.argtypes = [vp, u32, vp, sz, vp, vp, vp, vp, vp, vp, sz, u32, vp, vp, vp]
+    L.fri_hip_preview_tiles_dev.argtypes = [vp, vp, sz, u32, u32, u32, vp, vp, vp]
+    L.fri_hip_preview_image_tiled.argtypes = [vp, vp, u32, u32, vp, vp]
+    L.fri_hip_preview_image_tiled_coded.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, u32, u32, vp, vp, vp]
     _lib = L
     return L
 
@@ -375,21 +383,32 @@ def decode_scratch_bytes(n_planes):
 
 
 def decode_planes_dev(plan, n_planes, d_words, word_stride, d_n_words, d_models, d_off_values, d_value_params, d_width_params, d_coefs, coef_stride, d_status, d_scratch,
-                      stream=0, timed=False):
+                      stream=0, timed=False, levels=None):
     """fri_hip_decode_planes_dev (K13), device pointers as ints: the coded planes of emit.tiled_parse_coded - d_words uint32 [n_planes][word_stride], d_n_words
     [n_planes], d_models [n_planes][10][4], d_off_values uint16 [n_planes][10][1024], d_value_params / d_width_params f32 [n_planes][3][6] - on the lattice of `plan`
     (which needs its stream order) -> d_coefs int32, plane p at + p * coef_stride elements, and d_status uint32 [n_planes][4] = {bits, at, 0, 0}. d_scratch:
     decode_scratch_bytes(..) bytes, 256-byte aligned. Only enqueues. timed=True: fri_hip_decode_time_planes_dev - synchronises and returns the microseconds of the
-    model and decode kernels."""
+    model and decode kernels. levels (0..9): fri_hip_decode_planes_levels_dev - the step loop stops behind the nodes with heap index < 2^levels."""
     L = load_library()
     args = (plan._h if plan else None, n_planes, d_words, word_stride, d_n_words, d_models, d_off_values, d_value_params, d_width_params, d_coefs, coef_stride, d_status,
             d_scratch, stream)
     ctx = plan.ctx if plan else None
+    if levels is not None:
+        assert not timed
+        _check(L.fri_hip_decode_planes_levels_dev(*args[:11], int(levels), *args[11:]), "fri_hip_decode_planes_levels_dev", ctx)
+        return
     if timed:
         us = np.zeros(2, np.float64)
         _check(L.fri_hip_decode_time_planes_dev(*args, _p(us)), "fri_hip_decode_time_planes_dev", ctx)
         return us
     _check(L.fri_hip_decode_planes_dev(*args), "fri_hip_decode_planes_dev", ctx)
+
+
+def preview_size(width, height, shift):
+    """fri_hip_preview_size: (w', h') = (ceil(W / 2^shift), ceil(H / 2^shift)) of a thumbnail, shift 0..4. Needs no GPU."""
+    out = np.zeros(2, np.uint32)
+    _check(load_library().fri_hip_preview_size(width, height, shift, _p(out)), "fri_hip_preview_size")
+    return int(out[0]), int(out[1])
 
 
 def _coded_planes(coded, planes):
@@ -593,6 +612,13 @@ class Plan:
             self.close()
         except Exception:
             pass
+
+    def num_some_levels(self, levels):
+        """fri_hip_plan_num_some_levels: the Some coefficients with heap index < 2^levels per channel (levels 0..9) - the length of the stream's prefix that holds
+        them; num_some_levels(9) == num_some. Works on a host-only plan."""
+        out = C.c_uint64(0)
+        _check(load_library().fri_hip_plan_num_some_levels(self._h, int(levels), C.byref(out)), "fri_hip_plan_num_some_levels", self.ctx)
+        return int(out.value)
 
     def owned_pixels(self):
         """fri_hip_plan_owned_pixels: the pixels that are a leaf of a retained cell (width * height unless the lattice has holes)."""
@@ -1229,6 +1255,37 @@ class PlanTiled:
         rc = load_library().fri_hip_decode_image_tiled_coded(self._h, _p(words), words.shape[1], _p(n_words), _p(models), _p(off), _p(vp), _p(wp), _p(_q(qmatrix)), _p(out),
                                                              _p(status))
         _check_decode(rc, "fri_hip_decode_image_tiled_coded", self.ctx, status)
+        return out, status
+
+    # ---- preview decode: stop at a level, write a thumbnail (K14) ---------------------------------------
+    def preview_tiles_dev(self, d_coefs, coef_stride, node_stride, levels, shift, d_out, qmatrix=None, stream=0):
+        """fri_hip_preview_tiles_dev (K14), device pointers as ints: planes [n_tiles][C] coef_stride elements apart, node h of cell k at k * node_stride + h
+        (node_stride 512 or 2^levels) -> d_out uint8 [h'][w'][C], any alignment. Only enqueues; capturable."""
+        _check(load_library().fri_hip_preview_tiles_dev(self._h, d_coefs, coef_stride, node_stride, int(levels), int(shift), _p(_q(qmatrix)), d_out, stream),
+               "fri_hip_preview_tiles_dev", self.ctx)
+
+    def preview(self, coefs, levels, shift, qmatrix=None):
+        """fri_hip_preview_image_tiled: the compact planes int32 [n_tiles][C][F][2^levels] (what emit.tiled_decode_levels returns) -> the thumbnail uint8
+        [h'][w'][C], (w', h') = preview_size(W, H, shift): sample (Y, X) is pixel (min(Y S + S / 2, H - 1), min(X S + S / 2, W - 1)), S = 2^shift, of what
+        decode_image_tiled returns for the planes with every node at or above 2^levels set to 0."""
+        co = np.ascontiguousarray(coefs, np.int32).reshape(-1)
+        assert not 0 <= levels <= 9 or co.size == self.n_tiles * self.channels * self.num_cells << levels  # (levels out of range: the library's refusal)
+        w, h = preview_size(self.width, self.height, shift)
+        out = np.empty((h, w, self.channels), np.uint8)
+        _check(load_library().fri_hip_preview_image_tiled(self._h, _p(co), int(levels), int(shift), _p(_q(qmatrix)), _p(out)), "fri_hip_preview_image_tiled", self.ctx)
+        return out
+
+    def preview_coded(self, coded, levels, shift, qmatrix=None):
+        """fri_hip_preview_image_tiled_coded: the coded planes of a `frit` file (emit.tiled_parse_coded) through the device decoder bounded by `levels` and K14 ->
+        (thumbnail uint8 [h'][w'][C], status uint32 [n_tiles C][4]); the thumbnail is preview()'s of emit.tiled_decode_levels's planes. A plane the decoder refuses
+        raises FriHipError (-1) with the status as .status. Needs set_stream_order()."""
+        planes = self.n_tiles * self.channels
+        words, n_words, models, off, vp, wp = _coded_planes(coded, planes)
+        w, h = preview_size(self.width, self.height, shift)
+        out, status = np.empty((h, w, self.channels), np.uint8), np.zeros((planes, 4), np.uint32)
+        rc = load_library().fri_hip_preview_image_tiled_coded(self._h, _p(words), words.shape[1], _p(n_words), _p(models), _p(off), _p(vp), _p(wp), int(levels), int(shift),
+                                                              _p(_q(qmatrix)), _p(out), _p(status))
+        _check_decode(rc, "fri_hip_preview_image_tiled_coded", self.ctx, status)
         return out, status
 
     # ---- region decode: only the tiles a rectangle touches -------------------------------------------

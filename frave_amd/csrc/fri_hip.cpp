@@ -724,6 +724,17 @@ uint32_t fri_hip_plan_num_interior_cells(const fri_hip_plan *p) { return p ? p->
 size_t fri_hip_plan_coef_count(const fri_hip_plan *p) { return p ? (size_t)p->geo.channels * p->geo.centers.size() * kCell : 0; }
 size_t fri_hip_plan_pixel_bytes(const fri_hip_plan *p) { return p ? (size_t)p->geo.width * p->geo.height * p->geo.channels : 0; }
 uint64_t fri_hip_plan_num_some(const fri_hip_plan *p) { return p ? p->geo.n_some : 0; }
+int fri_hip_plan_num_some_levels(const fri_hip_plan *p, uint32_t levels, uint64_t *out) {
+    if (!p || !out || levels > (uint32_t)kDepth) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    *out = num_some_levels(p->geo, levels);
+    return FRI_HIP_OK;
+}
+int fri_hip_preview_size(uint32_t width, uint32_t height, uint32_t shift, uint32_t out[2]) {
+    if (!width || !height || shift > 4 || !out) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    const uint32_t S = 1u << shift;
+    out[0] = (uint32_t)(((uint64_t)width + S - 1) / S), out[1] = (uint32_t)(((uint64_t)height + S - 1) / S);
+    return FRI_HIP_OK;
+}
 uint64_t fri_hip_plan_owned_pixels(const fri_hip_plan *p) { return p ? p->geo.n_valid_leaves : 0; }
 
 int fri_hip_plan_assume_forward_coefficients(fri_hip_plan *p, int on) {

@@ -9,14 +9,15 @@ using namespace fri::host;
 namespace {
 int decode_planes(fri_hip_plan *p, uint32_t n_planes, const uint32_t *d_words, size_t word_stride, const uint32_t *d_n_words, const uint32_t *d_models,
                   const uint16_t *d_off_values, const float *d_value_params, const float *d_width_params, int32_t *d_coefs, size_t coef_stride, uint32_t *d_status,
-                  void *d_scratch, void *stream, const hipEvent_t *events) {
+                  void *d_scratch, void *stream, const hipEvent_t *events, uint32_t levels = kDepth) {
     if (int rc = need_device(p)) return rc;
+    if (levels > (uint32_t)kDepth) return FRI_HIP_ERR_INVALID_ARGUMENT;
     if (!d_words || !d_n_words || !d_models || !d_off_values || !d_value_params || !d_width_params || !d_coefs || !d_status || !d_scratch || !decode_counts_ok(n_planes) ||
         ((uintptr_t)d_scratch & 255u) || ((uintptr_t)d_coefs & 15u) || (coef_stride & 3u) || coef_stride < (size_t)p->geo.centers.size() * 512 || !p->d_stream_order ||
         p->geo.n_some < 1 || p->geo.n_some >= (1ull << 31))
         return FRI_HIP_ERR_INVALID_ARGUMENT;
     HIP_TRY(p->ctx, hipSetDevice(p->ctx->device));
-    HIP_TRY(p->ctx, launch_decode_planes(p->dev, p->d_stream_order, (uint32_t)p->geo.n_some, p->laplace, n_planes, d_words, word_stride, d_n_words, d_models, d_off_values,
+    HIP_TRY(p->ctx, launch_decode_planes(p->dev, p->d_stream_order, (uint32_t)p->geo.n_some, (uint32_t)num_some_levels(p->geo, levels), p->laplace, n_planes, d_words, word_stride, d_n_words, d_models, d_off_values,
                                          d_value_params, d_width_params, d_coefs, coef_stride, d_status, d_scratch, (hipStream_t)stream, events));
     return FRI_HIP_OK;
 }
@@ -31,6 +32,13 @@ int fri_hip_decode_planes_dev(fri_hip_plan *plan, uint32_t n_planes, const uint3
                               uint32_t *d_status, void *d_scratch, void *stream) {
     return decode_planes(plan, n_planes, d_words, word_stride, d_n_words, d_models, d_off_values, d_value_params, d_width_params, d_coefs, coef_stride, d_status, d_scratch, stream,
                          nullptr);
+}
+
+int fri_hip_decode_planes_levels_dev(fri_hip_plan *plan, uint32_t n_planes, const uint32_t *d_words, size_t word_stride, const uint32_t *d_n_words, const uint32_t *d_models,
+                                     const uint16_t *d_off_values, const float *d_value_params, const float *d_width_params, int32_t *d_coefs, size_t coef_stride, uint32_t levels,
+                                     uint32_t *d_status, void *d_scratch, void *stream) {
+    return decode_planes(plan, n_planes, d_words, word_stride, d_n_words, d_models, d_off_values, d_value_params, d_width_params, d_coefs, coef_stride, d_status, d_scratch, stream,
+                         nullptr, levels);
 }
 
 int fri_hip_decode_time_planes_dev(fri_hip_plan *plan, uint32_t n_planes, const uint32_t *d_words, size_t word_stride, const uint32_t *d_n_words, const uint32_t *d_models,

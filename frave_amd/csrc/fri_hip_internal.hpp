@@ -316,6 +316,20 @@ inline int read_back_symbols(fri_hip_ctx *c, size_t planes, size_t n_symbols, co
 // K11's limits on a batch of planes (fri_hip_rans_*; fri_hip_encode_image_tiled_coded checks them before it stages anything)
 inline bool rans_counts_ok(uint32_t n_planes, uint64_t n_symbols) { return n_planes >= 1 && n_planes <= 65535u && n_symbols >= 1 && n_symbols < (1ull << 31); }
 
+// fri_hip_plan_num_some_levels: the Some nodes with heap index < 2^levels (levels 0..9) - the length of the stream's prefix that holds them, a function of
+// valid_mask alone; levels = 9 gives n_some
+inline uint64_t num_some_levels(const Geometry &g, uint32_t levels) {
+    if (levels >= (uint32_t)kDepth) return g.n_some;
+    const uint32_t nodes = 1u << levels; // <= 256: whole words, or the low bits of word 0
+    uint64_t n = 0;
+    for (size_t c = 0; c < g.centers.size(); c++)
+        for (uint32_t w = 0; w * 32 < nodes; w++) {
+            const uint32_t m = g.valid_mask[c * 16 + w];
+            n += (uint64_t)__builtin_popcount(nodes - w * 32 >= 32 ? m : m & ((1u << (nodes - w * 32)) - 1u));
+        }
+    return n;
+}
+
 // K13's limit on a batch of planes (fri_hip_decode_*)
 inline bool decode_counts_ok(uint32_t n_planes) { return n_planes >= 1 && n_planes <= 65535u; }
 

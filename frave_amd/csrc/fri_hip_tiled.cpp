@@ -1,5 +1,5 @@
 // fri_hip_tiled.cpp -- the tiled plan kind of the C ABI (fri_hip_plan_tiled: include/fri_hip.h): the plan and its grid, split and merge, the encode chain and
-// its coded form (K11), the image and region decodes and the decode from coded planes (K13), the measure, the size estimate and the quality searches. Host-side glue like fri_hip.cpp, on one ordinary
+// its coded form (K11), the image and region decodes and the decode from coded planes (K13), the preview decode (K14), the measure, the size estimate and the quality searches. Host-side glue like fri_hip.cpp, on one ordinary
 // plan of the tile's shape. The grid, plan creation, the host size estimate and the coded route are tiled_common.hpp's, shared with fri_hip_tiled420.cpp; the
 // searches are TiledSearch on search_scaffold.hpp.
 #include "search_scaffold.hpp"
@@ -32,6 +32,8 @@ struct fri_hip_plan_tiled {
     Grown<uint16_t> rans_off;         // ... [n_tiles C][10][1024]
     Grown<uint8_t> rans_scratch;      // ... and its scratch
     Grown<uint8_t> region;            // fri_hip_decode_region_tiled: the region raster [h][w][C]
+    DevMem<uint32_t> owner;           // K14: [tile_h][tile_w] cell << 9 | leaf of the retained cell that owns a tile pixel, ~0 where none does; uploaded with the plan
+    Grown<uint8_t> preview;           // fri_hip_preview_image_tiled*: the thumbnail [h'][w'][C]
     size_t n_tiles() const { return grid.n_tiles(); }
     size_t raster_bytes() const { return (size_t)grid.width * grid.height * channels; }
     size_t tile_bytes() const { return (size_t)grid.tile_w * grid.tile_h * channels; }
@@ -109,6 +111,27 @@ struct TiledSearch {
     }
 };
 
+// K14's owner table: every pixel of the tile has at most one retained cell of which it is a leaf (geometry.cpp: the leaf offsets are a complete residue system
+// of the cell lattice), so the table is a function of the tile's shape alone.
+int upload_owner_table(fri_hip_plan_tiled *p) {
+    const Geometry &g = p->tile->geo;
+    const StaticTables &st = static_tables();
+    const uint32_t tw = p->grid.tile_w, th = p->grid.tile_h;
+    std::vector<uint32_t> owner((size_t)tw * th, 0xFFFFFFFFu);
+    for (size_t c = 0; c < g.centers.size(); c++)
+        for (int s = 0; s < kCell; s++) {
+            const int64_t x = (int64_t)g.centers[c].x + st.leaf_off[s].x, y = (int64_t)g.centers[c].y + st.leaf_off[s].y;
+            if (x >= 0 && y >= 0 && x < (int64_t)tw && y < (int64_t)th) owner[(size_t)y * tw + (size_t)x] = (uint32_t)c << 9 | (uint32_t)s;
+        }
+    fri_hip_ctx *c = p->ctx;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMalloc((void **)p->owner.put(), owner.size() * sizeof(uint32_t)));
+    HIP_TRY(c, hipMemcpy(p->owner, owner.data(), owner.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return FRI_HIP_OK;
+}
+
+bool preview_args_ok(uint32_t levels, uint32_t shift) { return levels <= (uint32_t)kDepth && shift <= 4; }
+
 } // namespace
 
 extern "C" {
@@ -128,6 +151,7 @@ int fri_hip_plan_tiled_create(fri_hip_ctx *ctx, uint32_t width, uint32_t height,
         int rc = fri_hip_plan_create(ctx, tile_w, tile_h, channels, &inner);
         p->tile.reset(inner);
         if (!rc && whole && p->tile->geo.n_valid_leaves != (uint64_t)tile_w * tile_h) rc = FRI_HIP_ERR_INVALID_ARGUMENT;
+        if (!rc && ctx) rc = upload_owner_table(p);
         return rc;
     });
 }
@@ -341,6 +365,59 @@ int fri_hip_decode_image_tiled_coded(fri_hip_plan_tiled *p, const uint32_t *word
     if ((rc = fri_hip_inverse_transform_batch_dev(p->tile.get(), (uint32_t)n, p->coefs, image, qmatrix, p->tiles, p->tile_bytes(), nullptr))) return rc;
     HIP_TRY(c, launch_merge_tiles(p->tiles, p->grid.width, p->grid.height, p->channels, p->grid.tile_w, p->grid.tile_h, p->raster, nullptr));
     HIP_TRY(c, hipMemcpy(pixels, p->raster, p->raster_bytes(), hipMemcpyDeviceToHost));
+    return FRI_HIP_OK;
+}
+
+/* ---- preview decode: stop at a level, write a thumbnail (K14) ---- */
+int fri_hip_preview_tiles_dev(fri_hip_plan_tiled *p, const int32_t *d_coefs, size_t coef_stride, uint32_t node_stride, uint32_t levels, uint32_t shift, const int32_t qmatrix[32],
+                              uint8_t *d_out, void *stream) {
+    if (int rc = need_device(p)) return rc;
+    if (!d_coefs || !qmatrix || !d_out || !preview_args_ok(levels, shift) || (node_stride != (uint32_t)kCell && node_stride != (1u << levels)) ||
+        coef_stride < p->tile->geo.centers.size() * (size_t)node_stride || !p->owner)
+        return FRI_HIP_ERR_INVALID_ARGUMENT;
+    QMatrix q;
+    if (int rc = check_q(qmatrix, q)) return rc;
+    HIP_TRY(p->ctx, hipSetDevice(p->ctx->device));
+    HIP_TRY(p->ctx, launch_preview_tiles(p->tile->dev_inv, p->owner, p->grid.width, p->grid.height, p->grid.tile_w, p->grid.tile_h, d_coefs, coef_stride, node_stride, levels, shift, q,
+                                         d_out, (hipStream_t)stream));
+    return FRI_HIP_OK;
+}
+
+int fri_hip_preview_image_tiled(fri_hip_plan_tiled *p, const int32_t *coefs, uint32_t levels, uint32_t shift, const int32_t qmatrix[32], uint8_t *pixels) {
+    if (int rc = need_device(p)) return rc;
+    if (!coefs || !qmatrix || !pixels || !preview_args_ok(levels, shift)) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    fri_hip_ctx *c = p->ctx;
+    HIP_TRY(c, hipSetDevice(c->device));
+    uint32_t size[2];
+    fri_hip_preview_size(p->grid.width, p->grid.height, shift, size);
+    const size_t plane = p->tile->geo.centers.size() << levels, n = p->n_tiles() * p->channels * plane, bytes = (size_t)size[0] * size[1] * p->channels;
+    int rc;
+    if ((rc = grow(c, p->coefs, n)) || (rc = grow(c, p->preview, bytes))) return rc;
+    HIP_TRY(c, hipMemcpy(p->coefs, coefs, n * sizeof(int32_t), hipMemcpyHostToDevice)); // the compact planes: 2^(levels - 9) of a full decode's upload
+    if ((rc = fri_hip_preview_tiles_dev(p, p->coefs, plane, 1u << levels, levels, shift, qmatrix, p->preview, nullptr))) return rc;
+    HIP_TRY(c, hipMemcpy(pixels, p->preview, bytes, hipMemcpyDeviceToHost));
+    return FRI_HIP_OK;
+}
+
+int fri_hip_preview_image_tiled_coded(fri_hip_plan_tiled *p, const uint32_t *words, size_t word_stride, const uint32_t *n_words, const uint32_t *models,
+                                      const uint16_t *off_values, const float *value_params, const float *width_params, uint32_t levels, uint32_t shift,
+                                      const int32_t qmatrix[32], uint8_t *pixels, uint32_t *status) {
+    if (int rc = need_device(p)) return rc;
+    const CodedPlanes in{words, word_stride, n_words, models, off_values, value_params, width_params};
+    if (!in.complete() || !qmatrix || !pixels || !status || !preview_args_ok(levels, shift) || !p->tile->d_stream_order) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    fri_hip_ctx *c = p->ctx;
+    HIP_TRY(c, hipSetDevice(c->device));
+    uint32_t size[2];
+    fri_hip_preview_size(p->grid.width, p->grid.height, shift, size);
+    const size_t image = fri_hip_plan_coef_count(p->tile.get()), n = p->n_tiles(), planes = n * p->channels, bytes = (size_t)size[0] * size[1] * p->channels;
+    if (!decode_counts_ok((uint32_t)planes)) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    int rc;
+    if ((rc = grow(c, p->coefs, n * image)) || (rc = grow(c, p->preview, bytes))) return rc;
+    CodedOnDevice d;
+    if ((rc = upload_coded(p, in, planes, p->rans_words, d)) || (rc = decode_coded_batch(p->tile.get(), d, 0, planes, p->coefs, image / p->channels, levels))) return rc;
+    if ((rc = read_back_decode_status(c, d, status))) return rc;
+    if ((rc = fri_hip_preview_tiles_dev(p, p->coefs, image / p->channels, kCell, levels, shift, qmatrix, p->preview, nullptr))) return rc;
+    HIP_TRY(c, hipMemcpy(pixels, p->preview, bytes, hipMemcpyDeviceToHost));
     return FRI_HIP_OK;
 }
 

@@ -11,7 +11,8 @@
 //           data. Step s then runs on lane s alone up to the bucket and the prediction (six coefficient loads, the LF or HF context), which two lane reads
 //           make wave-uniform; the rANS step is uniform: the ten states sit one per lane, the slot's symbol comes from two LDS rounds - 64 coarse cdf entries
 //           compared by all lanes and one ballot, then 16 fine ones - the next stream word from a lane read of the 64 words the lanes hold. Lane s stores
-//           the coefficient.
+//           the coefficient. The step loop runs n_steps <= n_some times: the stream order lists the nodes with heap index < 2^L first (the DC scan, the root
+//           scan, levels 1..L-1), so a bound of num_some_levels(L) decodes exactly those (fri_hip_decode_planes_levels_dev) and n_some the whole plane.
 //
 // The coefficient plane is read back by the wave that wrote it, a few steps later and from another lane: its pointer is neither const nor __restrict__ (the loads
 // must not take the constant path, which does not see vector stores), every store is an ordinary vector store, and a wavefront-scope fence between a step's
@@ -35,6 +36,7 @@ struct DecodeArgs {
     // the plan's lattice
     const uint32_t *order;      // [n_some] cell << 9 | heap, the decoder's walk
     uint32_t n_some, F;
+    uint32_t n_steps;           // <= n_some: the step loop's bound (fri_hip_decode_planes_levels_dev: the nodes with heap index < 2^levels are a prefix of the walk)
     const uint16_t *nbr_table;  // [512][6]
     const int32_t *nbr_cells;   // [F][kNbr]
     const uint32_t *valid_mask; // [F][16]
@@ -179,10 +181,10 @@ __global__ void __launch_bounds__(64) decode_kernel(const DecodeArgs a) {
     };
 
     DecEntry next = prepare(lane);
-    for (uint32_t i0 = 0; i0 < a.n_some && !bits; i0 += 64) {
+    for (uint32_t i0 = 0; i0 < a.n_steps && !bits; i0 += 64) {
         const DecEntry cur = next;
         next = prepare(i0 + 64 + lane); // in flight behind the chain of this chunk
-        const uint32_t count = a.n_some - i0 < 64u ? a.n_some - i0 : 64u;
+        const uint32_t count = a.n_steps - i0 < 64u ? a.n_steps - i0 : 64u;
         // The steps of the chunk. MIXED: the chunk holds DC or root entries (the first 2 F of the stream, heap index < 2) - both contexts are computed and one is
         // selected per entry; every other chunk computes the HF context alone.
         auto steps = [&](auto mixed) {
@@ -284,13 +286,14 @@ DecodeScratch decode_scratch_layout(uint32_t n_planes) {
     return s;
 }
 
-hipError_t launch_decode_planes(const DevicePlan &p, const uint32_t *order, uint32_t n_some, const float *laplace, uint32_t n_planes, const uint32_t *words, size_t word_stride,
+hipError_t launch_decode_planes(const DevicePlan &p, const uint32_t *order, uint32_t n_some, uint32_t n_steps, const float *laplace, uint32_t n_planes, const uint32_t *words, size_t word_stride,
                                 const uint32_t *n_words, const uint32_t *models, const uint16_t *off_values, const float *value_params, const float *width_params, int32_t *coefs,
                                 size_t coef_stride, uint32_t *status, void *scratch, hipStream_t stream, const hipEvent_t *events) {
     const DecodeScratch s = decode_scratch_layout(n_planes);
     uint8_t *base = static_cast<uint8_t *>(scratch);
+    if (n_steps > n_some) return hipErrorInvalidValue;
     DecodeArgs a;
-    a.order = order, a.n_some = n_some, a.F = p.F, a.nbr_table = p.nbr_table, a.nbr_cells = p.nbr_cells, a.valid_mask = p.valid_mask, a.laplace = laplace;
+    a.order = order, a.n_some = n_some, a.n_steps = n_steps, a.F = p.F, a.nbr_table = p.nbr_table, a.nbr_cells = p.nbr_cells, a.valid_mask = p.valid_mask, a.laplace = laplace;
     a.words = words, a.word_stride = word_stride, a.n_words = n_words, a.models = models, a.off_values = off_values, a.value_params = value_params, a.width_params = width_params;
     a.coefs = coefs, a.coef_stride = coef_stride, a.status = status;
     a.cdf = reinterpret_cast<uint32_t *>(base + s.cdf), a.freq = reinterpret_cast<uint32_t *>(base + s.freq), a.ctx = reinterpret_cast<uint32_t *>(base + s.ctx);

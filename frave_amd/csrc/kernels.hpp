@@ -1,5 +1,5 @@
 // kernels.hpp -- launch interface between the C ABI (fri_hip.cpp) and the gfx950 kernels (k1_forward.hip, k2_predict.hip, k3_inverse.hip, k4_fit.hip,
-// k5_stream.hip, k6_rate.hip, ..., k11_rans.hip, k13_decode.hip).
+// k5_stream.hip, k6_rate.hip, ..., k11_rans.hip, k13_decode.hip, k14_preview.hip).
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -218,14 +218,22 @@ hipError_t launch_rans_encode(uint32_t n_planes, const uint16_t *symbols, size_t
 // on `stream`: the decoder's models from {max_freq_bits, off list} and the planes' coefficients initialised, then one wave per plane that restates the host's
 // decode_channel. p: the plan whose lattice every plane lives on (F, nbr_table, nbr_cells, valid_mask); order [n_some]: its stream order; laplace [10][1024]. coefs:
 // plane k at + k * coef_stride elements, 16-byte aligned. scratch: decode_scratch_layout(..).total bytes, 256-byte aligned. n_planes <= 65535. events (may be NULL):
-// three events recorded in front of, between and behind the two kernels.
+// three events recorded in front of, between and behind the two kernels. n_steps <= n_some: the step loop's bound - the first n_steps entries of the order are
+// decoded (fri_hip_decode_planes_levels_dev: num_some_levels(L), the nodes with heap index < 2^L; n_some is the whole plane); the model kernel initialises whole planes.
 struct DecodeScratch {
     size_t cdf, freq, ctx, total; // byte offsets, and the size
 };
 DecodeScratch decode_scratch_layout(uint32_t n_planes);
-hipError_t launch_decode_planes(const DevicePlan &p, const uint32_t *order, uint32_t n_some, const float *laplace, uint32_t n_planes, const uint32_t *words, size_t word_stride,
+hipError_t launch_decode_planes(const DevicePlan &p, const uint32_t *order, uint32_t n_some, uint32_t n_steps, const float *laplace, uint32_t n_planes, const uint32_t *words, size_t word_stride,
                                 const uint32_t *n_words, const uint32_t *models, const uint16_t *off_values, const float *value_params, const float *width_params, int32_t *coefs,
                                 size_t coef_stride, uint32_t *status, void *scratch, hipStream_t stream, const hipEvent_t *events = nullptr);
+
+// K14 (k14_preview.hip): the thumbnail of a tiled image from the first 2^levels nodes of every cell (include/fri_hip.h, "Preview decode", has the definition).
+// inner: the tile's plan (F, channels, dequantiser, colour transform); owner [tile_h][tile_w]: cell << 9 | leaf of the retained cell that owns a tile pixel, ~0 where
+// none does; coefs: plane (tile, channel) at (tile * C + channel) * coef_stride, node h of cell c at c * node_stride + h, node_stride >= 2^levels; out
+// [ceil(H / 2^shift)][ceil(W / 2^shift)][C], any alignment. One thread per output sample, every output byte written exactly once, no atomics.
+hipError_t launch_preview_tiles(const DevicePlan &inner, const uint32_t *owner, uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, const int32_t *coefs,
+                                size_t coef_stride, uint32_t node_stride, uint32_t levels, uint32_t shift, const QMatrix &q, uint8_t *out, hipStream_t stream);
 
 // K12 (k12_tiles420.hip): the raster kernels of tiled 4:2:0 coding (include/fri_hip.h has the format). Split: the image [H][W][3] -> y_tiles [n][tile_h][tile_w]
 // and c_tiles [n][2][ch][cw], n = ny nx, cw = (tile_w + 1) / 2, ch = (tile_h + 1) / 2: K10's edge replication and K8's split of every tile in one pass. Region

@@ -218,10 +218,11 @@ int upload_coded(P *p, const CodedPlanes &in, size_t planes, Grown<uint32_t> &d_
     return FRI_HIP_OK;
 }
 
-// K13 over the planes first .. first + count - 1 on `plan`, plane first + k into d_coefs + k * coef_stride; on the null stream
-inline int decode_coded_batch(fri_hip_plan *plan, const CodedOnDevice &d, size_t first, size_t count, int32_t *d_coefs, size_t coef_stride) {
-    return fri_hip_decode_planes_dev(plan, (uint32_t)count, d.d_words + first * d.stride, d.stride, d.d_n_words() + first, d.d_models() + first * 40, d.d_off + first * 10 * 1024,
-                                     d.d_params + first * 18, d.d_params + (d.planes + first) * 18, d_coefs, coef_stride, d.d_status() + first * 4,
+// K13 over the planes first .. first + count - 1 on `plan`, plane first + k into d_coefs + k * coef_stride; on the null stream. levels < 9: the preview's bounded
+// step loop (fri_hip_decode_planes_levels_dev)
+inline int decode_coded_batch(fri_hip_plan *plan, const CodedOnDevice &d, size_t first, size_t count, int32_t *d_coefs, size_t coef_stride, uint32_t levels = 9) {
+    return fri_hip_decode_planes_levels_dev(plan, (uint32_t)count, d.d_words + first * d.stride, d.stride, d.d_n_words() + first, d.d_models() + first * 40, d.d_off + first * 10 * 1024,
+                                     d.d_params + first * 18, d.d_params + (d.planes + first) * 18, d_coefs, coef_stride, levels, d.d_status() + first * 4,
                                      d.d_scratch + (first ? decode_scratch_layout((uint32_t)first).total : 0), nullptr);
 }
 

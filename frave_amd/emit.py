@@ -53,6 +53,7 @@ def load_library():
         L.fri_coded_encode_image.argtypes = [u32, u32, u32, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, sz, vp, C.c_char_p, sz]
         L.fri_tiled_info.argtypes = [vp, sz, vp]
         L.fri_tiled_decode.argtypes = [vp, sz, u32, vp, vp, sz, C.c_char_p, sz]
+        L.fri_tiled_decode_levels.argtypes = [vp, sz, u32, u32, vp, vp, sz, C.c_char_p, sz]
         L.fri_tiled_parse_coded.argtypes = [vp, sz, vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp, vp, vp, C.c_char_p, sz]
         L.fri_tiled_region_tiles.argtypes = [u32, u32, u32, u32, u32, u32, u32, u32, vp]
         L.fri_tiled_decode_region.argtypes = [vp, sz, u32, u32, u32, u32, u32, vp, vp, vp, sz, C.c_char_p, sz]
@@ -407,6 +408,27 @@ def tiled_decode(frv, threads=0):
     rc = L.fri_tiled_decode(_p(data), data.size, threads, _p(info), _p(coefs), coefs.size, err, 256)
     if rc != 0:
         raise EmitError(err.value.decode() or f"fri_tiled_decode: {rc}")
+    return ti, coefs
+
+
+def tiled_decode_levels(frv, levels, threads=0):
+    """fri_tiled_decode_levels: (TiledInfo, compact coefs int32 [n_tiles][C][F][2^levels]) - tiled_decode stopped behind the nodes with heap index < 2^levels (0: the
+    DC alone, 1: DC and root, 9: everything), which are a prefix of every channel's stream; equal to tiled_decode's planes sliced to [..., :2^levels]. What
+    PlanTiled.preview takes. EmitError for levels > 9 and for a tiled 4:2:0 file."""
+    data = np.frombuffer(frv, np.uint8)
+    info = np.zeros(8, np.uint32)
+    err = C.create_string_buffer(256)
+    L = load_library()
+    if not 0 <= int(levels) <= 9:
+        raise EmitError("fri_tiled_decode_levels: levels must be 0..9")
+    rc = L.fri_tiled_decode_levels(_p(data), data.size, threads, int(levels), _p(info), None, 0, err, 256)
+    if rc != -3:
+        raise EmitError(err.value.decode() or f"fri_tiled_decode_levels: {rc}")
+    ti = _tiled_info(info)
+    coefs = np.empty((ti[4] * ti[5], ti[6], ti[7], 1 << int(levels)), np.int32)
+    rc = L.fri_tiled_decode_levels(_p(data), data.size, threads, int(levels), _p(info), _p(coefs), coefs.size, err, 256)
+    if rc != 0:
+        raise EmitError(err.value.decode() or f"fri_tiled_decode_levels: {rc}")
     return ti, coefs
 
 

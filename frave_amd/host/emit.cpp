@@ -658,14 +658,18 @@ int32_t wadd(int32_t a, int32_t b) { return (int32_t)((uint32_t)a + (uint32_t)b)
 int32_t wabs(int32_t a) { return a < 0 ? (int32_t)(0u - (uint32_t)a) : a; }
 } // namespace
 
-std::string decode_channel(const fri::Geometry &g, const SymbolOrder &order, const ChannelStream &s, const ChannelParams &prm, int32_t *coefs) {
+std::string decode_channel(const fri::Geometry &g, const SymbolOrder &order, const ChannelStream &s, const ChannelParams &prm, int32_t *coefs, int levels) {
     const fri::StaticTables &st = fri::static_tables();
     const size_t F = g.centers.size();
     if (order.level[0].size() != F) return "symbol order does not match the geometry";
+    if (levels < 0 || levels > kDepth) return "invalid argument";
+    // The level limit: the nodes with heap index < 2^levels are a prefix of the stream - the DC scan, the root scan, levels 1..levels - 1 - and the context of
+    // such a node reads its own level and its parents only. The planes are then compact, 2^levels nodes per cell; levels = 9 is the whole plane.
+    const size_t stride = (size_t)1 << levels;
     // WaveletImage::from_metadata (wavelet_transform.rs:392-404): the transform of an all-zero image, i.e. Some(0) wherever the
     // geometry has a node and None elsewhere. Values not decoded yet are read as that 0 by the context of later symbols.
     for (size_t c = 0; c < F; c++)
-        for (int p = 0; p < kNodes; p++) coefs[c * kNodes + p] = (g.valid_mask[c * 16 + (p >> 5)] >> (p & 31) & 1u) ? 0 : kNone;
+        for (size_t p = 0; p < stride; p++) coefs[c * stride + p] = (g.valid_mask[c * 16 + (p >> 5)] >> (p & 31) & 1u) ? 0 : kNone;
     RansDecoderMulti dec(s.data);
     if (!dec.ok()) return "stream truncated";
     const char *failure = nullptr;
@@ -677,7 +681,8 @@ std::string decode_channel(const fri::Geometry &g, const SymbolOrder &order, con
             const int slot = (e >> 9) & 7;
             const int32_t nc = g.nbr_cells[(size_t)cell * fri::kNbr + slot];
             if (nc < 0) continue; // no retained cell there
-            const int32_t x = coefs[(size_t)nc * kNodes + (e & 511u)];
+            if ((e & 511u) >= stride) continue; // (never: a context reads no level below its own)
+            const int32_t x = coefs[(size_t)nc * stride + (e & 511u)];
             v[k] = x == kNone ? 0 : x; // .unwrap_or(0)
         }
     };
@@ -712,7 +717,7 @@ std::string decode_channel(const fri::Geometry &g, const SymbolOrder &order, con
             failure = "stream truncated";
             return;
         }
-        coefs[(size_t)cell * kNodes + heap] = wadd(unpack_signed((uint32_t)sym), prediction); // :263
+        coefs[(size_t)cell * stride + heap] = wadd(unpack_signed((uint32_t)sym), prediction); // :263
     };
     auto lf = [&](uint32_t cell, uint32_t heap) { // get_lf_context_bucket, prediction.rs:86-149
         int32_t v[3];
@@ -726,16 +731,17 @@ std::string decode_channel(const fri::Geometry &g, const SymbolOrder &order, con
         lf(e >> 9, 0);
         if (failure) return failure;
     }
+    if (levels < 1) return "";
     for (uint32_t e : order.level[0]) { // second scan: root (:391-410)
         lf(e >> 9, 1);
         if (failure) return failure;
     }
-    for (int level = 1; level < kDepth; level++) { // :413-443
+    for (int level = 1; level < levels; level++) { // :413-443
         const int grp = level < kDepth - 2 ? 2 : level == kDepth - 2 ? 1 : 0; // prediction.rs:165-179
         const float *wp = prm.width[grp], *vp = prm.value[grp];
         for (uint32_t e : order.level[level]) {
             const uint32_t cell = e >> 9, heap = e & 511u;
-            if (coefs[(size_t)cell * kNodes + heap] == kNone) continue; // :421-425
+            if (coefs[(size_t)cell * stride + heap] == kNone) continue; // :421-425
             int32_t v[6];
             gather(cell, heap, 6, v);
             // get_hf_context_bucket, prediction.rs:190-206: f32, left to right, one rounding per operation (this file is built with
@@ -1245,18 +1251,21 @@ bool region_tiles(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t til
 }
 
 std::string decode_tiled(const uint8_t *b, size_t len, unsigned threads, TiledInfo &info, int32_t *coefs, size_t coef_cap, bool &too_small, const Region *region,
-                         TileRange *range) {
+                         TileRange *range, int levels) {
     too_small = false;
     std::vector<uint64_t> offset;
     std::string e = parse_tiled(b, len, info, offset);
     if (!e.empty()) return e;
+    if (levels > kDepth) return "invalid argument";
+    if (levels >= 0 && info.s420) return kNoLevels420;
+    if (levels < 0) levels = kDepth;
     TileRange tr{0, 0, info.nx, info.ny}; // without a region: the whole grid
     if (region && !region_tiles(info.width, info.height, info.tile_w, info.tile_h, *region, tr)) return "invalid region";
     if (range) *range = tr;
     fri::Geometry g; // one geometry and one symbol order for all tiles
     e = fri::build_geometry(info.tile_w, info.tile_h, info.s420 ? 1u : info.channels, fri::TilingParams{}, g);
     if (!e.empty()) return e;
-    const size_t F = g.centers.size(), plane = F * kNodes, n_tiles = (size_t)tr.ni * tr.nj;
+    const size_t F = g.centers.size(), plane = F << levels, n_tiles = (size_t)tr.ni * tr.nj; // (compact planes below levels = 9; 4:2:0 is whole planes only)
     const auto file_tile = [&](size_t s) { return ((size_t)tr.j0 + s / tr.ni) * info.nx + tr.i0 + s % tr.ni; }; // sub-tile s of the range in the file's grid
     info.n_cells = (uint32_t)F;
     std::vector<int32_t> centers(F * 2);
@@ -1301,7 +1310,7 @@ std::string decode_tiled(const uint8_t *b, size_t len, unsigned threads, TiledIn
             for (const AnsContext &a : c.contexts)
                 if (a.max_freq_bits == 0) return "Malformed image bytes"; // fewer than ten EHD segments
         for (uint32_t ch = 0; ch < info.channels; ch++) {
-            const std::string ce = decode_channel(g, *order, img.channels[ch], img.params[ch], coefs + (s * info.channels + ch) * plane);
+            const std::string ce = decode_channel(g, *order, img.channels[ch], img.params[ch], coefs + (s * info.channels + ch) * plane, levels);
             if (!ce.empty()) return "channel " + std::to_string(ch) + ": " + ce;
         }
         return "";

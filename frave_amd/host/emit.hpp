@@ -176,7 +176,9 @@ std::string deserialize(const std::vector<uint8_t> &bytes, ParsedImage &out, boo
 // side from the complete image - which is the same thing iff the stream order is causal (left / up_left / up_right of a node
 // precede it, the level above is complete). Inherently sequential per channel; the channels run on threads of their own.
 // coefs: [n_cells][512] output in heap order, None = INT32_MIN.
-std::string decode_channel(const fri::Geometry &g, const SymbolOrder &order, const ChannelStream &s, const ChannelParams &p, int32_t *coefs);
+// levels (0..9): decode the nodes with heap index < 2^levels only - a prefix of the stream: the DC scan, the root scan, levels 1..levels - 1 - into compact planes
+// [n_cells][2^levels]; nothing behind the prefix is read, so damage there is not seen. 9 is the whole plane.
+std::string decode_channel(const fri::Geometry &g, const SymbolOrder &order, const ChannelStream &s, const ChannelParams &p, int32_t *coefs, int levels = kDepth);
 struct DecodedImage {
     uint32_t height = 0, width = 0, colorspace = 0, channels = 0, n_cells = 0;
     bool rct = false; // the planes are Y, Cb, Cr of the reversible colour transform (ParsedImage::rct)
@@ -251,8 +253,11 @@ bool region_tiles(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t til
 // coefs [n_tiles][channels][F][512]. too_small: coefs is NULL or coef_cap (elements) does not hold them - `info` is filled, nothing is decoded.
 // With a region: the file is checked as without one, then only the tiles the region touches are decoded, coefs [nj ni][channels][F][512] in the sub-grid's order;
 // `range` is filled whenever `info` is. "invalid region" for a region region_tiles refuses. A tile's error names its index in the file's grid.
+// what a level-limited decode answers for a tiled 4:2:0 file (decode_tiled with levels >= 0; FRIDecoder::decode_preview's device route)
+inline constexpr const char *kNoLevels420 =
+    "a tiled 4:2:0 file has no level-limited decode (its chroma lattice is a level pair of its own): decode it whole with fri_tiled_decode";
 std::string decode_tiled(const uint8_t *frv, size_t len, unsigned threads, TiledInfo &info, int32_t *coefs, size_t coef_cap, bool &too_small, const Region *region = nullptr,
-                         TileRange *range = nullptr);
+                         TileRange *range = nullptr, int levels = -1 /* 0..9: compact planes [..][channels][F][2^levels], see decode_channel; "invalid argument" above 9 and for a tiled 4:2:0 file, with the reason */);
 // A `frit` file back to the coded planes it was written from (encode_tiled_from_coded, encode_tiled_from_coded420; the device decoder K13 reads them): per plane, in
 // the plane order the header defines, words [planes][word_stride] and n_words [planes] (the bytes between DAT and EOC as little-endian words, len / 4 rounded down),
 // models [planes][10][4] = {max_freq_bits as the file carries it, n_off, 0, 0}, off_values [planes][10][1024] (a context's first n_off, in file order) and

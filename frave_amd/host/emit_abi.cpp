@@ -340,6 +340,17 @@ int fri_tiled_decode(const uint8_t *frv, size_t len, uint32_t threads, uint32_t 
     return too_small ? -3 : 0;
 }
 
+int fri_tiled_decode_levels(const uint8_t *frv, size_t len, uint32_t threads, uint32_t levels, uint32_t info[8], int32_t *coefs, size_t coef_cap, char *err, size_t err_cap) {
+    if (!frv || !info || levels > 9) return fail(err, err_cap, "invalid argument");
+    TiledInfo t;
+    bool too_small = false;
+    const std::string e = decode_tiled(frv, len, threads, t, coefs, coef_cap, too_small, nullptr, nullptr, (int)levels);
+    if (e == "invalid argument" || e == kNoLevels420) return fail(err, err_cap, e); // (a tiled 4:2:0 file: -1 with the reason)
+    if (!e.empty()) return fail(err, err_cap, e, -2);
+    fill_tiled_info(t, info);
+    return too_small ? -3 : 0;
+}
+
 int fri_tiled_parse_coded(const uint8_t *frv, size_t len, uint32_t info[8], uint64_t n_planes, uint32_t *words, uint64_t word_stride, uint32_t *n_words, uint32_t *models,
                           uint16_t *off_values, float *value_params, float *width_params, char *err, size_t err_cap) {
     if (!frv || !info || (words && (!n_words || !models || !off_values || !value_params || !width_params))) return fail(err, err_cap, "invalid argument");

@@ -31,6 +31,9 @@
 //                                                            comes back as RGB, a lossy file with its quality's matrix and the midpoint dequantiser
 //                                                            --device-rans: a `frit` file (4:4:4 or 4:2:0) is entropy-decoded on the device too (K13: parse -> fri_hip_decode_image_tiled_coded);
 //                                                            refused on a `frif` file (one chain per channel) and together with --region (out of scope)
+//                                                            --preview M (1..4): the thumbnail of ceil(W / 2^M) x ceil(H / 2^M) from the first L = 9 - 2 M levels of a `frit` file's tiles
+//                                                            (FRIDecoder::decode_preview: fri_tiled_decode_levels + K14; with --device-rans K13 bounded by L + K14); refused with
+//                                                            --region, on a `frif` file and on a tiled 4:2:0 file, naming what to do instead
 //                                                            --region X,Y,W,H: only that rectangle of the image (FRIDecoder::decode_region) - of a `frit` file only
 //                                                            the tiles it touches are decoded; a `frif` file is decoded whole and cropped; no untiled 4:2:0 file and no alpha file
 //   fri_driver batch <width> <height> <channels> <n_images> [--gpus N]
@@ -685,13 +688,14 @@ int main(int argc, char **argv) {
             return 1;
         }
         bool has_region = false, device_rans = false;
-        unsigned rx = 0, ry = 0, rw = 0, rh = 0;
+        unsigned rx = 0, ry = 0, rw = 0, rh = 0, preview = 0; // preview M: 1..4, 0 = none
         for (int i = 4; i < argc; i++) {
             char tail = 0;
             if (std::string(argv[i]) == "--device-rans") device_rans = true;
+            else if (std::string(argv[i]) == "--preview" && i + 1 < argc && std::sscanf(argv[i + 1], "%u%c", &preview, &tail) == 1 && preview >= 1 && preview <= 4) i++;
             else if (std::string(argv[i]) == "--region" && i + 1 < argc && std::sscanf(argv[i + 1], "%u,%u,%u,%u%c", &rx, &ry, &rw, &rh, &tail) == 4) has_region = true, i++;
             else {
-                std::fprintf(stderr, "decode-file: unknown or incomplete option %s (--region X,Y,W,H, --device-rans)\n", argv[i]);
+                std::fprintf(stderr, "decode-file: unknown or incomplete option %s (--region X,Y,W,H, --device-rans, --preview M with M = 1..4)\n", argv[i]);
                 return 2;
             }
         }
@@ -699,9 +703,13 @@ int main(int argc, char **argv) {
             std::fprintf(stderr, "decode-file: --device-rans with --region is out of scope: the device decoder takes whole tiled files (drop one of the two)\n");
             return 2;
         }
+        if (preview && has_region) {
+            std::fprintf(stderr, "decode-file: --preview with --region is out of scope: a preview is of the whole image (drop --region, or decode the region at full size)\n");
+            return 2;
+        }
         libfri::EncoderOpts dec_opts;
         dec_opts.device_rans = device_rans;
-        auto img = has_region ? libfri::FRIDecoder().decode_region(bytes, rx, ry, rw, rh) : libfri::FRIDecoder().decode(bytes, dec_opts);
+        auto img = preview ? libfri::FRIDecoder().decode_preview(bytes, preview, dec_opts) : has_region ? libfri::FRIDecoder().decode_region(bytes, rx, ry, rw, rh) : libfri::FRIDecoder().decode(bytes, dec_opts);
         if (!img.ok) {
             std::fprintf(stderr, "%s\n", img.error.c_str());
             return 1;
@@ -743,7 +751,7 @@ int main(int argc, char **argv) {
         return 0;
     }
     if (argc < 5) {
-        std::fprintf(stderr, "usage: %s roundtrip|encode|batch|batch-frv <width> <height> <channels> [n_images | out.frv]\n       %s encode-file <in.pgm|in.ppm|in.bmp|in.pam> <out.frv> [--rct | [--ycbcr | --420] (--quality Q | --psnr DB | --ssim S | --size BYTES | --bpp B)] [--clean-alpha] [--tile-size T [--device-rans]]\n       %s encode-file <in.ppm|in.bmp> <out.frv> --tile-size-420 T (--quality Q | --target psnr=DB|ssim=S|size=BYTES|bpp=B) [--device-rans]   (tiled 4:2:0; --tile-size T --420 stays refused: the option of its own is this one)\n       %s decode-file <in.frv> <out.pgm|out.ppm|out.bmp|out.pam> [--region X,Y,W,H]\n", argv[0], argv[0], argv[0], argv[0]);
+        std::fprintf(stderr, "usage: %s roundtrip|encode|batch|batch-frv <width> <height> <channels> [n_images | out.frv]\n       %s encode-file <in.pgm|in.ppm|in.bmp|in.pam> <out.frv> [--rct | [--ycbcr | --420] (--quality Q | --psnr DB | --ssim S | --size BYTES | --bpp B)] [--clean-alpha] [--tile-size T [--device-rans]]\n       %s encode-file <in.ppm|in.bmp> <out.frv> --tile-size-420 T (--quality Q | --target psnr=DB|ssim=S|size=BYTES|bpp=B) [--device-rans]   (tiled 4:2:0; --tile-size T --420 stays refused: the option of its own is this one)\n       %s decode-file <in.frv> <out.pgm|out.ppm|out.bmp|out.pam> [--region X,Y,W,H | --device-rans | --preview M [--device-rans]]\n", argv[0], argv[0], argv[0], argv[0]);
         return 2;
     }
     const std::string cmd = argv[1];

@@ -477,8 +477,9 @@ struct Tiled420PlanDelete {
 using Tiled420Plan = std::unique_ptr<fri_hip_plan_tiled420, Tiled420PlanDelete>;
 
 // a `frit` file: the tiles' planes from the emitter's workers, then the inverse kernel over all tiles and the merge. With a region: only the tiles it touches, on
-// both sides (emit::decode_tiled with the region, fri_hip_decode_region_tiled), and the raster is the region's.
-Result<RasterImage> decode_tiled_bytes(const std::vector<uint8_t> &data, const EncoderOpts &opts, const emit::Region *region = nullptr) {
+// both sides (emit::decode_tiled with the region, fri_hip_decode_region_tiled), and the raster is the region's. With preview_shift m >= 0 (FRIDecoder::decode_preview;
+// no region): the decode stops at level L = 9 - 2 m (compact planes) and K14 writes the thumbnail of ceil(W / 2^m) x ceil(H / 2^m).
+Result<RasterImage> decode_tiled_bytes(const std::vector<uint8_t> &data, const EncoderOpts &opts, const emit::Region *region = nullptr, int preview_shift = -1) {
     Result<RasterImage> r;
     auto fail = [&](const std::string &why) {
         r.error = "Failed to decode: " + why;
@@ -487,11 +488,12 @@ Result<RasterImage> decode_tiled_bytes(const std::vector<uint8_t> &data, const E
     emit::TiledInfo ti;
     emit::TileRange range;
     bool too_small = false;
-    std::string e = emit::decode_tiled(data.data(), data.size(), 0, ti, nullptr, 0, too_small, region, &range); // header, table, geometry
+    const int levels = preview_shift < 0 ? -1 : 9 - 2 * preview_shift; // (-1: whole planes, 4:2:0 among them)
+    std::string e = emit::decode_tiled(data.data(), data.size(), 0, ti, nullptr, 0, too_small, region, &range, levels); // header, table, geometry
     if (!e.empty()) return fail(e);
     const size_t tile_cells = ti.s420 ? (size_t)ti.n_cells + 2 * (size_t)ti.n_cells_chroma : (size_t)ti.channels * ti.n_cells; // (4:2:0: plane order, F_y + 2 F_c per tile)
-    std::vector<int32_t> coefs((size_t)range.ni * range.nj * tile_cells * FRI_HIP_CELL_SIZE);
-    e = emit::decode_tiled(data.data(), data.size(), 0, ti, coefs.data(), coefs.size(), too_small, region, &range);
+    std::vector<int32_t> coefs((size_t)range.ni * range.nj * tile_cells * (levels < 0 ? (size_t)FRI_HIP_CELL_SIZE : (size_t)1 << levels));
+    e = emit::decode_tiled(data.data(), data.size(), 0, ti, coefs.data(), coefs.size(), too_small, region, &range, levels);
     if (!e.empty() || too_small) return fail(e.empty() ? "coefficient array does not match the tile geometry" : e);
     Device dev(opts.device);
     if (!dev.ok()) return fail(dev.error());
@@ -520,12 +522,18 @@ Result<RasterImage> decode_tiled_bytes(const std::vector<uint8_t> &data, const E
     std::array<int32_t, 32> qm = opts.quantization_matrix;
     if (ti.quality && fri_hip_quality_matrix((int)ti.quality, qm.data()) != FRI_HIP_OK) return fail("invalid quality");
     int rc = fri_hip_plan_set_dequantiser(tile, ti.quality ? FRI_HIP_DEQUANT_MIDPOINT : FRI_HIP_DEQUANT_REFERENCE);
-    const uint32_t out_w = region ? region->w : ti.width, out_h = region ? region->h : ti.height;
+    uint32_t out_w = region ? region->w : ti.width, out_h = region ? region->h : ti.height;
+    if (levels >= 0) {
+        uint32_t size[2];
+        if (fri_hip_preview_size(ti.width, ti.height, (uint32_t)preview_shift, size) != FRI_HIP_OK) return fail("invalid preview shift");
+        out_w = size[0], out_h = size[1];
+    }
     r.value.metadata = ImageMetadata{out_h, out_w, ti.channels == 1 ? ColorSpace::Luma : ColorSpace::RGB};
     r.value.data.resize((size_t)out_w * out_h * ti.channels);
     if (rc == FRI_HIP_OK)
-        rc = region ? fri_hip_decode_region_tiled(raw, coefs.data(), qm.data(), region->x, region->y, region->w, region->h, r.value.data.data())
-                    : fri_hip_decode_image_tiled(raw, coefs.data(), qm.data(), r.value.data.data());
+        rc = levels >= 0 ? fri_hip_preview_image_tiled(raw, coefs.data(), (uint32_t)levels, (uint32_t)preview_shift, qm.data(), r.value.data.data())
+             : region    ? fri_hip_decode_region_tiled(raw, coefs.data(), qm.data(), region->x, region->y, region->w, region->h, r.value.data.data())
+                         : fri_hip_decode_image_tiled(raw, coefs.data(), qm.data(), r.value.data.data());
     if (rc != FRI_HIP_OK) return fail(dev.describe(rc));
     r.ok = true;
     return r;
@@ -534,8 +542,8 @@ Result<RasterImage> decode_tiled_bytes(const std::vector<uint8_t> &data, const E
 std::string set_plan_stream_order(fri_hip_plan *plan, Device &dev);
 
 // a `frit` file through the device decoder (opts.device_rans): the container walked on the host, the coded planes up - about a tenth of the int32 planes - then K13,
-// the inverse kernel over all tiles and the merge
-Result<RasterImage> decode_tiled_coded_bytes(const std::vector<uint8_t> &data, const EncoderOpts &opts) {
+// the inverse kernel over all tiles and the merge. With preview_shift m >= 0: K13 bounded by L = 9 - 2 m, then K14 (fri_hip_preview_image_tiled_coded).
+Result<RasterImage> decode_tiled_coded_bytes(const std::vector<uint8_t> &data, const EncoderOpts &opts, int preview_shift = -1) {
     Result<RasterImage> r;
     auto fail = [&](const std::string &why) {
         r.error = "Failed to decode: " + why;
@@ -545,6 +553,7 @@ Result<RasterImage> decode_tiled_coded_bytes(const std::vector<uint8_t> &data, c
     bool too_small = false;
     std::string e = emit::parse_tiled_coded(data.data(), data.size(), ti, 0, too_small, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr); // header, table, lattice
     if (!e.empty()) return fail(e);
+    if (preview_shift >= 0 && ti.s420) return fail(emit::kNoLevels420);
     const size_t planes = (size_t)ti.nx * ti.ny * ti.channels;
     std::vector<uint32_t> n_words(planes);
     e = emit::parse_tiled_coded(data.data(), data.size(), ti, planes, too_small, nullptr, 0, n_words.data(), nullptr, nullptr, nullptr, nullptr);
@@ -589,10 +598,15 @@ Result<RasterImage> decode_tiled_coded_bytes(const std::vector<uint8_t> &data, c
     std::array<int32_t, 32> qm = opts.quantization_matrix;
     if (ti.quality && fri_hip_quality_matrix((int)ti.quality, qm.data()) != FRI_HIP_OK) return fail("invalid quality");
     int rc = fri_hip_plan_set_dequantiser(tile, ti.quality ? FRI_HIP_DEQUANT_MIDPOINT : FRI_HIP_DEQUANT_REFERENCE);
-    r.value.metadata = ImageMetadata{ti.height, ti.width, ti.channels == 1 ? ColorSpace::Luma : ColorSpace::RGB};
-    r.value.data.resize((size_t)ti.width * ti.height * ti.channels);
+    uint32_t size[2] = {ti.width, ti.height};
+    if (preview_shift >= 0 && fri_hip_preview_size(ti.width, ti.height, (uint32_t)preview_shift, size) != FRI_HIP_OK) return fail("invalid preview shift");
+    r.value.metadata = ImageMetadata{size[1], size[0], ti.channels == 1 ? ColorSpace::Luma : ColorSpace::RGB};
+    r.value.data.resize((size_t)size[0] * size[1] * ti.channels);
     if (rc == FRI_HIP_OK)
-        rc = fri_hip_decode_image_tiled_coded(raw, words.data(), stride, n_words.data(), models.data(), off.data(), vp.data(), wp.data(), qm.data(), r.value.data.data(), status.data());
+        rc = preview_shift >= 0 ? fri_hip_preview_image_tiled_coded(raw, words.data(), stride, n_words.data(), models.data(), off.data(), vp.data(), wp.data(),
+                                                                    (uint32_t)(9 - 2 * preview_shift), (uint32_t)preview_shift, qm.data(), r.value.data.data(), status.data())
+                                : fri_hip_decode_image_tiled_coded(raw, words.data(), stride, n_words.data(), models.data(), off.data(), vp.data(), wp.data(), qm.data(),
+                                                                   r.value.data.data(), status.data());
     if (rc != FRI_HIP_OK) return fail(refused(rc));
     r.ok = true;
     return r;
@@ -631,6 +645,18 @@ Result<RasterImage> FRIDecoder::decode_region(const std::vector<uint8_t> &data, 
     for (uint32_t ry = 0; ry < h; ry++)
         std::memcpy(r.value.data.data() + (size_t)ry * w * pixel, whole.value.data.data() + (((size_t)y + ry) * whole.value.metadata.width + x) * pixel, (size_t)w * pixel);
     r.ok = true;
+    return r;
+}
+
+Result<RasterImage> FRIDecoder::decode_preview(const std::vector<uint8_t> &data, uint32_t shift, const EncoderOpts &opts) {
+    Result<RasterImage> r;
+    if (shift > 4) {
+        r.error = "Failed to decode: a preview's shift is 0..4";
+        return r;
+    }
+    if (data.size() >= 4 && std::memcmp(data.data(), "frit", 4) == 0)
+        return opts.device_rans ? decode_tiled_coded_bytes(data, opts, (int)shift) : decode_tiled_bytes(data, opts, nullptr, (int)shift);
+    r.error = "Failed to decode: a preview reads tiled (`frit`) files only: decode an untiled file whole and scale it down";
     return r;
 }
 

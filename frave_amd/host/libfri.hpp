@@ -318,6 +318,11 @@ class FRIDecoder { // decoder.rs:44-59
     // fri_hip_decode_region_tiled. An ordinary `frif` file has no tiles: it is decoded whole and cropped on the host, which buys nothing and only makes the call
     // work on any file. Untiled 4:2:0 files and alpha files are refused; a tiled 4:2:0 file goes through fri_hip_decode_region_tiled420.
     Result<RasterImage> decode_region(const std::vector<uint8_t> &data, uint32_t x, uint32_t y, uint32_t w, uint32_t h, const EncoderOpts &opts = EncoderOpts());
+    // The thumbnail of a tiled file (include/fri_hip.h, "Preview decode"): shift m is 0..4, the raster is ceil(W / 2^m) x ceil(H / 2^m), sample (Y, X) the pixel
+    // (min(Y S + S / 2, H - 1), min(X S + S / 2, W - 1)), S = 2^m, of the image whose detail below level L = 9 - 2 m is 0. Only the first L levels of every tile are
+    // entropy-decoded: fri_tiled_decode_levels's workers, then fri_hip_preview_image_tiled - with opts.device_rans, fri_hip_preview_image_tiled_coded (K13 bounded by
+    // L, then K14). An untiled `frif` file and a tiled 4:2:0 file are refused, and the error says what to do instead.
+    Result<RasterImage> decode_preview(const std::vector<uint8_t> &data, uint32_t shift, const EncoderOpts &opts = EncoderOpts());
     // from the WaveletTransform stage on
     Result<RasterImage> decode(const WaveletImage &image, const EncoderOpts &opts = EncoderOpts());
 };

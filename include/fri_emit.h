@@ -216,6 +216,14 @@ int fri_tiled_info(const uint8_t *frv, size_t len, uint32_t info[8]);
  * filled when coefs is NULL or coef_cap (in elements) is too small. A tiled 4:2:0 file: coefs in plane order, n (F_y + 2 F_c) x 512 elements - what
  * fri_hip_decode_image_tiled420 takes. */
 int fri_tiled_decode(const uint8_t *frv, size_t len, uint32_t threads, uint32_t info[8], int32_t *coefs, size_t coef_cap, char *err, size_t err_cap);
+/* Preview decode: fri_tiled_decode stopped at a level. `levels` L is 0..9: the nodes with heap index < 2^L are decoded - L = 0 the DC alone, L = 1 DC and root,
+ * L = 9 everything. A channel's stream is ten scans - DC, root, levels 1..8 - and the context of a symbol reads its own level and its parents only, so these
+ * nodes are a prefix of the stream (the DC scan, the root scan, levels 1..L-1) and the decoder stops behind it: nothing further is read, damage there is neither
+ * seen nor reported. The result is COMPACT planes, coefs [n_tiles][C][F][2^L] int32: node h of cell c at c 2^L + h, None = INT32_MIN, a Some node always
+ * decoded - fri_tiled_decode's planes sliced to [..., :2^L], for every thread count; what fri_hip_preview_image_tiled (include/fri_hip.h) takes. Parsing, refusals,
+ * workers and the size query (-3 with `info` filled when coefs is NULL or coef_cap, in elements, is too small) are fri_tiled_decode's. -1 for levels > 9 and, with
+ * a message that names fri_tiled_decode, for a tiled 4:2:0 file, whose chroma lattice is a level pair of its own. */
+int fri_tiled_decode_levels(const uint8_t *frv, size_t len, uint32_t threads, uint32_t levels, uint32_t info[8], int32_t *coefs, size_t coef_cap, char *err, size_t err_cap);
 /* A `frit` file back to the coded planes it is made of: the inverse of fri_tiled_encode_from_coded and fri_tiled_encode_from_coded420, and what the device decoder
  * reads (K13: fri_hip_decode_planes_dev, fri_hip_decode_image_tiled_coded, include/fri_hip.h). One function for both kinds of file; P = n_tiles C planes in the
  * order the header defines - tile by tile and channel by channel, or plane order for a tiled 4:2:0 file. Per plane p: words uint32 [P][word_stride], of which the

@@ -92,6 +92,9 @@ int fri_hip_plan_centers(const fri_hip_plan *plan, int32_t *centers);
 int fri_hip_plan_valid_mask(const fri_hip_plan *plan, uint32_t *mask);
 /* Number of Some coefficients per channel (= histogram total per channel). */
 uint64_t fri_hip_plan_num_some(const fri_hip_plan *plan);
+/* *out = num_some_levels(levels): the Some coefficients with heap index < 2^levels per channel, levels 0..9 - a function of the valid mask alone;
+ * num_some_levels(9) = num_some. In stream order these nodes are a prefix of that length ("Preview decode" below). Works on host-only plans. */
+int fri_hip_plan_num_some_levels(const fri_hip_plan *plan, uint32_t levels, uint64_t *out);
 /* ids[F][8]: cell ids of {self, +V9[0..5]} neighbours (stages/wavelet_transform.rs:71-95), -1 = absent. */
 int fri_hip_plan_neighbour_cells(const fri_hip_plan *plan, int32_t *ids);
 /* table[512][6] u16: static neighbour map used by the gather kernel (context_modeling.rs:25-77):
@@ -937,6 +940,13 @@ uint64_t fri_hip_decode_scratch_bytes(uint32_t n_planes);
 int fri_hip_decode_planes_dev(fri_hip_plan *plan, uint32_t n_planes, const uint32_t *d_words, size_t word_stride, const uint32_t *d_n_words, const uint32_t *d_models,
                               const uint16_t *d_off_values, const float *d_value_params, const float *d_width_params, int32_t *d_coefs, size_t coef_stride,
                               uint32_t *d_status, void *d_scratch, void *stream);
+/* fri_hip_decode_planes_dev with the step loop bounded by num_some_levels(levels) instead of num_some ("Preview decode" below; levels 0..9): the first
+ * num_some_levels(levels) entries of the stream order - the nodes with heap index < 2^levels - are decoded into the same full-stride planes, and every other Some
+ * node keeps its initial 0: the model kernel still initialises whole planes. fri_hip_decode_planes_dev is the levels = 9 case of the same launch. `at` and the three
+ * status bits keep their meaning; damage beyond the prefix is not seen and not reported. FRI_HIP_ERR_INVALID_ARGUMENT also for levels > 9. */
+int fri_hip_decode_planes_levels_dev(fri_hip_plan *plan, uint32_t n_planes, const uint32_t *d_words, size_t word_stride, const uint32_t *d_n_words, const uint32_t *d_models,
+                                     const uint16_t *d_off_values, const float *d_value_params, const float *d_width_params, int32_t *d_coefs, size_t coef_stride,
+                                     uint32_t levels, uint32_t *d_status, void *d_scratch, void *stream);
 /* The same launch bracketed by events on `stream`: us[2] = the microseconds of the model and decode kernels. Synchronises; for measurements. */
 int fri_hip_decode_time_planes_dev(fri_hip_plan *plan, uint32_t n_planes, const uint32_t *d_words, size_t word_stride, const uint32_t *d_n_words, const uint32_t *d_models,
                                    const uint16_t *d_off_values, const float *d_value_params, const float *d_width_params, int32_t *d_coefs, size_t coef_stride,
@@ -954,6 +964,49 @@ int fri_hip_decode_image_tiled_coded(fri_hip_plan_tiled *p, const uint32_t *word
  * chroma planes on the chroma plan (both need their stream order) - then what fri_hip_decode_image_tiled420 runs behind its upload, at `quality` (1..99). */
 int fri_hip_decode_image_tiled420_coded(fri_hip_plan_tiled420 *p, const uint32_t *words, size_t word_stride, const uint32_t *n_words, const uint32_t *models,
                                         const uint16_t *off_values, const float *value_params, const float *width_params, int quality, uint8_t *pixels, uint32_t *status);
+
+/* ---- Preview decode: stop at a level, write a thumbnail (K14, k14_preview.hip) ------------------- */
+/* A channel's stream is ten scans - DC, root, levels 1..8 - and the context of a symbol reads its own level and its parents only; the decoder starts from Some(0)
+ * on every node and checks nothing at the end of the stream. So decoding can stop behind any scan, and what is left is exactly the planes of an image whose finer
+ * detail coefficients are 0. A detail of 0 inverts to l = r = s: every pixel then carries the low value of its ancestor at that depth.
+ *
+ * levels  L is 0..9: the nodes with heap index < 2^L are decoded - L = 0 the DC alone, L = 1 DC and root, L = 9 everything. In stream order they are a prefix: the
+ *         DC scan, the root scan, then levels 1..L-1, num_some_levels(L) entries (fri_hip_plan_num_some_levels).
+ * Preview image  P_L is what fri_hip_decode_image_tiled returns for planes whose Some nodes with heap index >= 2^L are 0, with the same qmatrix and the
+ *         dequantiser and colour transform set on the inner plan.
+ * Thumbnail  shift m is 0..4, S = 2^m: w' x h' x C with w' = ceil(W / S), h' = ceil(H / S) (fri_hip_preview_size), and
+ *         out(Y, X, c) = P_L(min(Y S + S / 2, H - 1), min(X S + S / 2, W - 1), c). m = 0 is P_L itself. A sample that no cell owns (FRI_HIP_TILED_ALLOW_HOLES) is 0.
+ *         The natural pairing is L = 9 - 2 m, where a node covers S^2 pixels; L and m are independent here.
+ *
+ * Out of scope: untiled `frif` files (one chain per channel: nothing runs side by side); tiled 4:2:0, where the chroma lattice is a level pair of its own; the
+ * preview of a region; a filter other than the node mean.
+ *
+ * fri_hip_preview_size: out = {w', h'}; host only. FRI_HIP_ERR_INVALID_ARGUMENT for a zero size, shift > 4 or out = NULL.
+ *
+ * fri_hip_preview_tiles_dev (K14): d_coefs holds the planes [n_tiles][C], plane (t, c) at (t C + c) * coef_stride elements, node h of cell k at k * node_stride + h;
+ * node_stride is 512 (K13's planes, fri_tiled_decode's) or 2^L (the compact planes of fri_tiled_decode_levels, include/fri_emit.h), anything else is
+ * FRI_HIP_ERR_INVALID_ARGUMENT, as is a coef_stride below F * node_stride. Nodes at or above 2^L are not read. d_out [h'][w'][C], any alignment. One thread per
+ * output sample: the plan's table gives the retained cell and the leaf s that own the sample's tile pixel (tile origin + centre + leaf_off[s]); the thread
+ * dequantises the L + 1 coefficients on the leaf's path as K3 does (reference, multiply or midpoint; all three map 0 to 0), runs the L inverse levels - the leaf
+ * carries low value s >> (9 - L) - and applies K3's per-pixel colour inverse (RCT, YCbCr) and clamp. A pixel of the image is a sample when x mod S == S / 2, or when
+ * x == W - 1 and (W - 1) mod S < S / 2 (y alike); its output column is x / S. Replicated tile pixels are never samples. The call only enqueues on `stream` and can be
+ * captured into a graph; it uses no atomics and every output byte is written exactly once. m = 0 is there so that the definition is complete, not as a fast path:
+ * the inverse kernel and the merge stay the full-size route.
+ *
+ * fri_hip_preview_image_tiled: the compact planes of fri_tiled_decode_levels, coefs [n_tiles][C][F][2^L], up - 2^(L - 9) of a full decode's upload - then K14;
+ * pixels [h'][w'][C]. Synchronous.
+ *
+ * fri_hip_preview_image_tiled_coded: the shape of fri_hip_decode_image_tiled_coded - the coded planes up, K13 bounded by L (fri_hip_decode_planes_levels_dev), then
+ * K14 on its planes. The inner plan needs its stream order. A non-zero status gives FRI_HIP_ERR_INVALID_ARGUMENT with the status filled and no pixels. Synchronous.
+ *
+ * All compute forms return FRI_HIP_ERR_NO_DEVICE on a host-only plan; levels > 9, shift > 4 or a null pointer FRI_HIP_ERR_INVALID_ARGUMENT. */
+int fri_hip_preview_size(uint32_t width, uint32_t height, uint32_t shift, uint32_t out[2]);
+int fri_hip_preview_tiles_dev(fri_hip_plan_tiled *p, const int32_t *d_coefs, size_t coef_stride, uint32_t node_stride, uint32_t levels, uint32_t shift,
+                              const int32_t qmatrix[32], uint8_t *d_out, void *stream);
+int fri_hip_preview_image_tiled(fri_hip_plan_tiled *p, const int32_t *coefs, uint32_t levels, uint32_t shift, const int32_t qmatrix[32], uint8_t *pixels);
+int fri_hip_preview_image_tiled_coded(fri_hip_plan_tiled *p, const uint32_t *words, size_t word_stride, const uint32_t *n_words, const uint32_t *models,
+                                      const uint16_t *off_values, const float *value_params, const float *width_params, uint32_t levels, uint32_t shift,
+                                      const int32_t qmatrix[32], uint8_t *pixels, uint32_t *status);
 
 /* ---- timing helper ---------------------------------------------------------------------------- */
 /* Runs the forward kernel `iters` times on `stream` bracketed by HIP events recorded on that same
