@@ -44,6 +44,7 @@ SYMBOLS = [
     "fri_hip_search_quality_ssim_tiled", "fri_hip_search_quality_ssim_tiled_dev", "fri_hip_search_quality_for_size_tiled", "fri_hip_search_quality_for_size_tiled_dev",
     "fri_hip_rans_scratch_bytes", "fri_hip_rans_encode_planes_dev", "fri_hip_rans_time_planes_dev", "fri_hip_encode_image_tiled_coded",
     "fri_hip_plan_tiled_region", "fri_hip_merge_tiles_region_dev", "fri_hip_decode_region_tiled_dev", "fri_hip_decode_region_tiled",
+    "fri_hip_plan_tiled_region_cover", "fri_hip_split_tiles_region_dev", "fri_hip_encode_symbols_region_tiled_dev", "fri_hip_encode_region_tiled_symbols",
     "fri_hip_tile_shape420", "fri_hip_plan_tiled420_create", "fri_hip_plan_tiled420_destroy", "fri_hip_plan_tiled420_luma", "fri_hip_plan_tiled420_chroma",
     "fri_hip_plan_tiled420_grid", "fri_hip_plan_tiled420_region", "fri_hip_plan_tiled420_buffer_tiles", "fri_hip_split_tiles420_dev", "fri_hip_merge_tiles420_dev",
     "fri_hip_merge_tiles420_region_dev", "fri_hip_encode_symbols_tiled420_dev", "fri_hip_encode_image_tiled420_symbols", "fri_hip_decode_image_tiled420",
@@ -240,6 +241,10 @@ def load_library():
     L.fri_hip_merge_tiles_region_dev.argtypes = [vp, vp, u32, u32, u32, u32, vp, vp]
     L.fri_hip_decode_region_tiled_dev.argtypes = [vp, vp, vp, u32, u32, u32, u32, vp, vp]
     L.fri_hip_decode_region_tiled.argtypes = [vp, vp, vp, u32, u32, u32, u32, vp]
+    L.fri_hip_plan_tiled_region_cover.argtypes = [vp, u32, u32, u32, u32, vp]
+    L.fri_hip_split_tiles_region_dev.argtypes = [vp, vp, C.c_size_t, u32, u32, u32, u32, u32, u32, u32, u32, vp, vp]
+    L.fri_hip_encode_symbols_region_tiled_dev.argtypes = [vp, vp, C.c_size_t, u32, u32, u32, u32, u32, u32, u32, u32, vp, i32, vp, vp, vp, vp, vp, vp]
+    L.fri_hip_encode_region_tiled_symbols.argtypes = [vp, vp, u32, u32, u32, u32, vp, vp, vp, vp, vp, vp]
     L.fri_hip_measure_distortion_tiled_dev.argtypes = [vp, vp, vp, vp, vp]
     L.fri_hip_estimate_size_tiled_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.fri_hip_estimate_size_tiled.argtypes = [vp, vp, vp, vp, vp]
@@ -1314,6 +1319,44 @@ class PlanTiled:
         out = np.empty(w * h * self.channels, np.uint8)
         _check(load_library().fri_hip_decode_region_tiled(self._h, _p(co), _p(_q(qmatrix)), x, y, w, h, _p(out)), "fri_hip_decode_region_tiled", self.ctx)
         return out
+
+    # ---- region update: only the tiles a rectangle touches are split and coded ------------------------
+    def region_cover(self, x, y, w, h):
+        """fri_hip_plan_tiled_region_cover: (cx, cy, cw, ch), the covered rectangle of the region x, y, w, h - the in-image pixels of the tiles it touches, the
+        only pixels a region encode reads. Works on a host-only plan. FriHipError (-1) as region_tiles."""
+        out = np.zeros(4, np.uint32)
+        _check(load_library().fri_hip_plan_tiled_region_cover(self._h, x, y, w, h, _p(out)), "fri_hip_plan_tiled_region_cover", self.ctx)
+        return tuple(int(v) for v in out)
+
+    def split_tiles_region_dev(self, d_src, src_pitch, src_x, src_y, src_w, src_h, x, y, w, h, d_tiles, stream=0):
+        """fri_hip_split_tiles_region_dev: a pitched rectangle of the image (d_src points at image pixel (src_y, src_x); it must contain the covered rectangle) ->
+        the sub-grid's tile raster [nj ni][tile_h][tile_w][C], the sub-grid's rows of split_tiles_dev; only enqueues."""
+        _check(load_library().fri_hip_split_tiles_region_dev(self._h, d_src, src_pitch, src_x, src_y, src_w, src_h, x, y, w, h, d_tiles, stream),
+               "fri_hip_split_tiles_region_dev", self.ctx)
+
+    def encode_symbols_region_tiled_dev(self, d_src, src_pitch, src_x, src_y, src_w, src_h, x, y, w, h, d_params, d_symbols, d_hist, d_oob, d_fit_out_of_range=None,
+                                        qmatrix=None, fit=True, stream=0):
+        """fri_hip_encode_symbols_region_tiled_dev: the region split and one direct stream chain over the touched tiles, everything on the device, the outputs in
+        the sub-grid's order with the layouts of encode_symbols_tiled_dev. Needs set_stream_order(); refuses a capturing stream."""
+        _check(load_library().fri_hip_encode_symbols_region_tiled_dev(self._h, d_src, src_pitch, src_x, src_y, src_w, src_h, x, y, w, h, _p(_q(qmatrix)), int(bool(fit)),
+                                                                     d_params, d_symbols, d_hist, d_oob, d_fit_out_of_range, stream),
+               "fri_hip_encode_symbols_region_tiled_dev", self.ctx)
+
+    def encode_region_tiled_symbols(self, pixels, x, y, w, h, qmatrix=None):
+        """fri_hip_encode_region_tiled_symbols: pixels is the whole raster [H][W][C], of which only the covered rectangle is copied to the device - (symbols uint16
+        [nj ni][C][num_some], value_params, width_params [nj ni][C][3][6], hist [nj ni][C][10][1024], oob [nj ni][C]) in the sub-grid's order: what
+        emit.tiled_update_from_streams takes; the fit is on. Needs set_stream_order()."""
+        px = np.ascontiguousarray(pixels, np.uint8).reshape(-1)
+        assert px.size == self.pixel_bytes
+        _, _, ni, nj = self.region_tiles(x, y, w, h)
+        n, c = ni * nj, self.channels
+        vp, wp = np.zeros((n, c, 3, 6), np.float32), np.zeros((n, c, 3, 6), np.float32)
+        sym = np.empty((n, c, self.num_some), np.uint16)
+        hist = np.empty((n, c, 10, 1024), np.uint32)
+        oob = np.zeros((n, c), np.uint64)
+        _check(load_library().fri_hip_encode_region_tiled_symbols(self._h, _p(px), x, y, w, h, _p(_q(qmatrix)), _p(vp), _p(wp), _p(sym), _p(hist), _p(oob)),
+               "fri_hip_encode_region_tiled_symbols", self.ctx)
+        return sym, vp, wp, hist, oob
 
     # ---- the measure, the size estimate and the searches over tiles ----------------------------------
     def measure_distortion_tiled_dev(self, d_tiles, d_reference_raster, d_out, stream=0):

@@ -274,6 +274,88 @@ int fri_hip_decode_region_tiled(fri_hip_plan_tiled *p, const int32_t *coefs, con
     return FRI_HIP_OK;
 }
 
+/* ---- region update: only the tiles a rectangle touches are split and coded ---- */
+namespace {
+// {cx, cy, cw, ch}: the in-image pixels of the sub-grid `range` = {i0, j0, ni, nj}
+void cover_of(const TileGrid &g, const uint32_t range[4], uint32_t out[4]) {
+    out[0] = range[0] * g.tile_w, out[1] = range[1] * g.tile_h;
+    out[2] = (uint32_t)(std::min<uint64_t>(((uint64_t)range[0] + range[2]) * g.tile_w, g.width) - out[0]);
+    out[3] = (uint32_t)(std::min<uint64_t>(((uint64_t)range[1] + range[3]) * g.tile_h, g.height) - out[1]);
+}
+// the source rectangle lies in the image and contains the covered rectangle; its pitch holds a row
+bool source_ok(const fri_hip_plan_tiled *p, size_t src_pitch, uint32_t src_x, uint32_t src_y, uint32_t src_w, uint32_t src_h, const uint32_t range[4]) {
+    uint32_t c[4];
+    cover_of(p->grid, range, c);
+    if (!src_w || !src_h || (uint64_t)src_x + src_w > p->grid.width || (uint64_t)src_y + src_h > p->grid.height) return false;
+    if (src_x > c[0] || src_y > c[1] || (uint64_t)src_x + src_w < (uint64_t)c[0] + c[2] || (uint64_t)src_y + src_h < (uint64_t)c[1] + c[3]) return false;
+    return src_pitch >= (uint64_t)src_w * p->channels;
+}
+} // namespace
+
+int fri_hip_plan_tiled_region_cover(const fri_hip_plan_tiled *p, uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint32_t out[4]) {
+    uint32_t range[4];
+    if (!p || !out || p->grid.region(x, y, w, h, range)) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    cover_of(p->grid, range, out);
+    return FRI_HIP_OK;
+}
+
+int fri_hip_split_tiles_region_dev(fri_hip_plan_tiled *p, const uint8_t *d_src, size_t src_pitch, uint32_t src_x, uint32_t src_y, uint32_t src_w, uint32_t src_h, uint32_t x,
+                                   uint32_t y, uint32_t w, uint32_t h, uint8_t *d_tiles, void *stream) {
+    uint32_t range[4];
+    if (!p || !d_src || !d_tiles || fri_hip_plan_tiled_region(p, x, y, w, h, range) || !source_ok(p, src_pitch, src_x, src_y, src_w, src_h, range)) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    if (int rc = need_device(p)) return rc;
+    HIP_TRY(p->ctx, launch_split_tiles_region(d_src, src_pitch, src_x, src_y, src_w, src_h, p->grid.width, p->grid.height, p->channels, p->grid.tile_w, p->grid.tile_h, x, y, w, h,
+                                              d_tiles, (hipStream_t)stream));
+    return FRI_HIP_OK;
+}
+
+int fri_hip_encode_symbols_region_tiled_dev(fri_hip_plan_tiled *p, const uint8_t *d_src, size_t src_pitch, uint32_t src_x, uint32_t src_y, uint32_t src_w, uint32_t src_h,
+                                            uint32_t x, uint32_t y, uint32_t w, uint32_t h, const int32_t qmatrix[32], int fit, float *d_params, uint16_t *d_symbols,
+                                            uint32_t *d_hist, uint64_t *d_n_out_of_alphabet, uint64_t *d_fit_out_of_range, void *stream) {
+    uint32_t range[4];
+    if (!p || !d_src || !qmatrix || !d_params || !d_symbols || !d_hist || !d_n_out_of_alphabet || fri_hip_plan_tiled_region(p, x, y, w, h, range) ||
+        !source_ok(p, src_pitch, src_x, src_y, src_w, src_h, range))
+        return FRI_HIP_ERR_INVALID_ARGUMENT;
+    if (int rc = need_device(p)) return rc;
+    if (!p->tile->d_stream_order) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    fri_hip_ctx *c = p->ctx;
+    const hipStream_t s = (hipStream_t)stream;
+    QMatrix q;
+    if (int rc = check_q(qmatrix, q)) return rc;
+    if (int rc = refuse_capture(p->tile.get(), s)) return rc; // (what the inner call refuses, before anything is enqueued or allocated)
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t n = (size_t)range[2] * range[3]; // the touched tiles: the buffer grows to the region's size, never to the image's
+    if (int rc = grow(c, p->tiles, n * p->tile_bytes())) return rc;
+    HIP_TRY(c, launch_split_tiles_region(d_src, src_pitch, src_x, src_y, src_w, src_h, p->grid.width, p->grid.height, p->channels, p->grid.tile_w, p->grid.tile_h, x, y, w, h,
+                                         p->tiles, s));
+    return fri_hip_encode_symbols_batch_dev(p->tile.get(), (uint32_t)n, p->tiles, p->tile_bytes(), qmatrix, fit, d_params, nullptr, 0, nullptr, 0, d_symbols,
+                                            (size_t)p->channels * p->tile->geo.n_some, d_hist, d_n_out_of_alphabet, d_fit_out_of_range, stream);
+}
+
+int fri_hip_encode_region_tiled_symbols(fri_hip_plan_tiled *p, const uint8_t *pixels, uint32_t x, uint32_t y, uint32_t w, uint32_t h, const int32_t qmatrix[32],
+                                        float *value_params, float *width_params, uint16_t *symbols, uint32_t *hist, uint64_t *n_out_of_alphabet) {
+    uint32_t range[4], cover[4];
+    if (!p || !pixels || !qmatrix || !value_params || !width_params || !symbols || !hist || !n_out_of_alphabet || fri_hip_plan_tiled_region(p, x, y, w, h, range))
+        return FRI_HIP_ERR_INVALID_ARGUMENT;
+    if (int rc = need_device(p)) return rc;
+    fri_hip_ctx *c = p->ctx;
+    HIP_TRY(c, hipSetDevice(c->device));
+    cover_of(p->grid, range, cover);
+    const size_t planes = (size_t)range[2] * range[3] * p->channels, n = p->tile->geo.n_some;
+    const size_t cover_row = (size_t)cover[2] * p->channels, image_row = (size_t)p->grid.width * p->channels;
+    int rc;
+    if ((rc = grow(c, p->raster, cover_row * cover[3])) || (rc = grow(c, p->symbols, std::max<size_t>(planes * n, 1))) || (rc = grow(c, p->hist, planes * 10 * 1024)) ||
+        (rc = grow(c, p->counts, 2 * planes)) || (rc = grow(c, p->params, planes * 36)))
+        return rc;
+    // only the covered rectangle goes up: one 2-D copy out of the host raster
+    HIP_TRY(c, hipMemcpy2D(p->raster, cover_row, pixels + (size_t)cover[1] * image_row + (size_t)cover[0] * p->channels, image_row, cover_row, cover[3], hipMemcpyHostToDevice));
+    uint64_t *oob = reinterpret_cast<uint64_t *>(p->counts.get());
+    if ((rc = fri_hip_encode_symbols_region_tiled_dev(p, p->raster, cover_row, cover[0], cover[1], cover[2], cover[3], x, y, w, h, qmatrix, 1, p->params, p->symbols, p->hist, oob,
+                                                      oob + planes, nullptr)))
+        return rc;
+    return read_back_symbols(c, planes, planes * n, p->symbols, p->hist, p->params, p->counts, symbols, hist, value_params, width_params, n_out_of_alphabet);
+}
+
 /* ---- the measure, the size estimate and the searches over tiles ---- */
 int fri_hip_measure_distortion_tiled_dev(fri_hip_plan_tiled *p, const uint8_t *d_tiles, const uint8_t *d_reference_raster, uint64_t *d_out, void *stream) {
     if (!p || !d_tiles || !d_reference_raster || !d_out) return FRI_HIP_ERR_INVALID_ARGUMENT;

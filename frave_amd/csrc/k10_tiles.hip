@@ -5,7 +5,9 @@
 // j tile_h + y < H and i tile_w + x < W. measure_tiles_kernel<C>: the merge's pixels compared with a reference raster instead of stored (the tiled searches' PSNR).
 //
 // merge_tiles_region_kernel<C>: a sub-grid's tile raster [nj ni][tile_h][tile_w][C] -> the region raster [h][w][C] (include/fri_emit.h, "Region decode", has the
-// arithmetic); region pixel (ry, rx) is image pixel (y + ry, x + rx), never a replicated one.
+// arithmetic); region pixel (ry, rx) is image pixel (y + ry, x + rx), never a replicated one. split_tiles_region_kernel<C>: the write-side twin - a pitched
+// rectangle of the image that contains the covered rectangle of a region's sub-grid -> that sub-grid's tile raster, the rows {(j0 + b) nx + i0 + a} of the split
+// (include/fri_emit.h, "Region update").
 //
 // Neither raster has a row pitch. The tile raster is a flat run of ny nx tile_h rows of tile_w C bytes, and a lane owns one strip of 16 consecutive bytes of one
 // such row. Away from the clamped edge those are 16 consecutive bytes of one image row: one 16-byte load and one 16-byte store, the target's unaligned global
@@ -135,6 +137,48 @@ __global__ void __launch_bounds__(kTileThreads) merge_tiles_region_kernel(const 
         for (uint32_t k = 0; k < n; k++) {
             dst[k] = src[xb];
             if (++xb == p.row_bytes) xb = 0, src += tile_stride; // the same row of the next tile
+        }
+    }
+}
+
+// split_tiles_region_kernel<C>: the split for the sub-grid a region touches (include/fri_emit.h, "Region update"). The work follows the output, the sub-grid's
+// tile raster [nj ni][tile_h][tile_w][C]: a lane owns 16 bytes of one of its rows, exactly as in split_tiles_kernel, and row (b ni + a) tile_h + y is image row
+// min((j0 + b) tile_h + y, H - 1) from byte (i0 + a) tile_w C. The source is a pitched rectangle: `src` points at image pixel (src_y, src_x_bytes / C) and its rows
+// are src_pitch bytes apart, so image byte (gy, at) is src[(gy - src_y) src_pitch + at - src_x_bytes]. The launcher has checked that the rectangle contains the
+// covered rectangle, and every byte read below lies in it: an unclamped byte belongs to a touched tile's in-image pixels, and a clamped one is the image's last row
+// or column, which the covered rectangle reaches whenever an edge tile is touched. The whole raster (pitch W C, origin 0) and a staged copy of the covered
+// rectangle alone (pitch cw C, origin cx, cy) are the same kernel.
+struct SplitRegionArgs {
+    const uint8_t *src;
+    uint8_t *out; // the sub-grid's tile raster
+    uint64_t src_pitch;
+    uint32_t src_x_bytes, src_y;
+    uint32_t width, height, tile_w, tile_h;
+    uint32_t i0, j0, ni;
+    uint32_t row_bytes;      // tile_w C
+    uint32_t strips_per_row; // ceil(row_bytes / 16)
+    uint32_t n_strips;       // nj ni tile_h strips_per_row
+};
+
+template <uint32_t C>
+__global__ void __launch_bounds__(kTileThreads) split_tiles_region_kernel(const SplitRegionArgs p) {
+    const uint32_t g = blockIdx.x * kTileThreads + threadIdx.x;
+    if (g >= p.n_strips) return;
+    const uint32_t row = g / p.strips_per_row, b0 = (g - row * p.strips_per_row) * kTileStrip; // row = s tile_h + y
+    const uint32_t s = row / p.tile_h, y = row - s * p.tile_h;
+    const uint32_t b = s / p.ni, a = s - b * p.ni;
+    const uint32_t n = min(kTileStrip, p.row_bytes - b0);
+    const uint32_t gy = min((p.j0 + b) * p.tile_h + y, p.height - 1);
+    const uint32_t x0 = (p.i0 + a) * p.tile_w, x0_bytes = x0 * C; // where the tile's columns start in an image row
+    const uint32_t image_row_bytes = p.width * C;
+    const uint8_t *src_row = p.src + (uint64_t)(gy - p.src_y) * p.src_pitch; // image byte `at` of that row is src_row[at - src_x_bytes]
+    uint8_t *dst = p.out + (uint64_t)row * p.row_bytes + b0;
+    if (n == kTileStrip && (uint64_t)x0_bytes + b0 + kTileStrip <= image_row_bytes) {
+        store_unaligned(dst, load_unaligned<u32x4>(src_row + (x0_bytes + b0 - p.src_x_bytes)));
+    } else { // the replicated edge, or the row's last strip
+        for (uint32_t k = 0; k < n; k++) {
+            const uint32_t at = b0 + k, x = at / C, c = at - x * C;
+            dst[k] = src_row[min(x0 + x, p.width - 1) * C + c - p.src_x_bytes];
         }
     }
 }
@@ -294,6 +338,34 @@ hipError_t launch_merge_tiles_region(const uint8_t *tiles, uint32_t width, uint3
     groups = (uint32_t)((n_strips + kTileThreads - 1) / kTileThreads);
     if (channels == 3) hipLaunchKernelGGL(merge_tiles_region_kernel<3>, dim3(groups), dim3(kTileThreads), 0, stream, p);
     else hipLaunchKernelGGL(merge_tiles_region_kernel<1>, dim3(groups), dim3(kTileThreads), 0, stream, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_split_tiles_region(const uint8_t *src, size_t src_pitch, uint32_t src_x, uint32_t src_y, uint32_t src_w, uint32_t src_h, uint32_t width, uint32_t height,
+                                     uint32_t channels, uint32_t tile_w, uint32_t tile_h, uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint8_t *tiles, hipStream_t stream) {
+    TileArgs whole{};
+    uint32_t groups = 0;
+    if (!src || !tiles || !grid_of(width, height, channels, tile_w, tile_h, whole, groups)) return hipErrorInvalidValue; // (the shape's limits: a row's bytes fit 31 bits)
+    if (!w || !h || (uint64_t)x + w > width || (uint64_t)y + h > height) return hipErrorInvalidValue;
+    const uint32_t i0 = x / tile_w, j0 = y / tile_h, ni = (x + w - 1) / tile_w - i0 + 1, nj = (y + h - 1) / tile_h - j0 + 1;
+    // the covered rectangle: the in-image pixels of the touched tiles, in 64 bits
+    const uint64_t cx = (uint64_t)i0 * tile_w, cy = (uint64_t)j0 * tile_h;
+    const uint64_t cx1 = std::min<uint64_t>(((uint64_t)i0 + ni) * tile_w, width), cy1 = std::min<uint64_t>(((uint64_t)j0 + nj) * tile_h, height);
+    // the source rectangle lies in the image, contains the covered rectangle, and its rows do not overlap
+    if (!src_w || !src_h || (uint64_t)src_x + src_w > width || (uint64_t)src_y + src_h > height) return hipErrorInvalidValue;
+    if (src_x > cx || src_y > cy || (uint64_t)src_x + src_w < cx1 || (uint64_t)src_y + src_h < cy1) return hipErrorInvalidValue;
+    if (src_pitch < (uint64_t)src_w * channels) return hipErrorInvalidValue;
+    SplitRegionArgs p{};
+    p.src = src, p.out = tiles;
+    p.src_pitch = src_pitch, p.src_x_bytes = src_x * channels, p.src_y = src_y;
+    p.width = width, p.height = height, p.tile_w = tile_w, p.tile_h = tile_h;
+    p.i0 = i0, p.j0 = j0, p.ni = ni;
+    p.row_bytes = whole.row_bytes, p.strips_per_row = whole.strips_per_row;
+    const uint64_t n_strips = (uint64_t)ni * nj * tile_h * p.strips_per_row; // (at most the whole grid's, which grid_of has checked)
+    p.n_strips = (uint32_t)n_strips;
+    groups = (uint32_t)((n_strips + kTileThreads - 1) / kTileThreads);
+    if (channels == 3) hipLaunchKernelGGL(split_tiles_region_kernel<3>, dim3(groups), dim3(kTileThreads), 0, stream, p);
+    else hipLaunchKernelGGL(split_tiles_region_kernel<1>, dim3(groups), dim3(kTileThreads), 0, stream, p);
     return hipGetLastError();
 }
 

@@ -196,6 +196,12 @@ hipError_t launch_merge_tiles(const uint8_t *tiles, uint32_t width, uint32_t hei
 // region must lie in the width x height image (hipErrorInvalidValue otherwise).
 hipError_t launch_merge_tiles_region(const uint8_t *tiles, uint32_t width, uint32_t height, uint32_t channels, uint32_t tile_w, uint32_t tile_h, uint32_t x, uint32_t y, uint32_t w,
                                      uint32_t h, uint8_t *region, hipStream_t stream);
+// Region split (include/fri_emit.h, "Region update"): the tile raster of the sub-grid the region x, y, w, h touches, [nj ni][tile_h][tile_w][C] - the rows
+// {(j0 + b) nx + i0 + a} of the split - from a pitched rectangle of the image: `src` points at image pixel (src_y, src_x), rows src_pitch bytes apart, src_w x src_h
+// pixels. hipErrorInvalidValue for a region that leaves the image, a rectangle that leaves it or does not contain the covered rectangle, src_pitch < src_w C.
+// Nothing outside the covered rectangle is read.
+hipError_t launch_split_tiles_region(const uint8_t *src, size_t src_pitch, uint32_t src_x, uint32_t src_y, uint32_t src_w, uint32_t src_h, uint32_t width, uint32_t height,
+                                     uint32_t channels, uint32_t tile_w, uint32_t tile_h, uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint8_t *tiles, hipStream_t stream);
 // Measure: the merge's walk with nothing stored - the tile raster's in-image pixels against `reference` [H][W][C]: sums[2 c] += the sum of squared differences of
 // channel c, sums[2 c + 1] = max(.., largest absolute difference), sums[2 C] += pixels (W H in all). The caller zeroes sums with launch_clear_sums.
 hipError_t launch_measure_tiles(const uint8_t *tiles, uint32_t width, uint32_t height, uint32_t channels, uint32_t tile_w, uint32_t tile_h, const uint8_t *reference,

@@ -57,6 +57,7 @@ def load_library():
         L.fri_tiled_parse_coded.argtypes = [vp, sz, vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp, vp, vp, C.c_char_p, sz]
         L.fri_tiled_region_tiles.argtypes = [u32, u32, u32, u32, u32, u32, u32, u32, vp]
         L.fri_tiled_decode_region.argtypes = [vp, sz, u32, u32, u32, u32, u32, vp, vp, vp, sz, C.c_char_p, sz]
+        L.fri_tiled_update_from_streams.argtypes = [vp, sz, u32, u32, u32, u32, u32, vp, C.c_uint64, vp, vp, vp, u32, vp, vp, sz, vp, C.c_char_p, sz]
         _lib = L
     return _lib
 
@@ -489,3 +490,39 @@ def tiled_decode_region(frv, x, y, w, h, threads=0):
     if rc != 0:
         raise EmitError(err.value.decode() or f"fri_tiled_decode_region: {rc}")
     return ti, tuple(int(v) for v in tiles), coefs
+
+
+def tiled_update_from_streams(frv, x, y, w, h, streams, hist, value_params, width_params, rct=False, quality=0, ycbcr=False, threads=0, flags=0):
+    """fri_tiled_update_from_streams: (the updated `frit` bytes, (i0, j0, ni, nj)) - the file `frv` with the payloads of the tiles the region x, y, w, h touches
+    coded from what PlanTiled.encode_region_tiled_symbols returns, in the sub-grid's order: streams uint16 [nj ni][C][n_symbols], hist [nj ni][C][10][1024],
+    params [nj ni][C][3][6] (C is read from hist's second axis). Every other payload is copied and not looked into. rct, quality, ycbcr must be the file's own: the
+    metadata word they make must be tile 0's. `flags` is or-ed into the channels word as it is. An EmitError carries the C return value as .code. The buffer of
+    the first call is sized generously, so the touched tiles are coded once as a rule (a size query would code them too)."""
+    data = np.frombuffer(frv, np.uint8)
+    st = np.ascontiguousarray(streams, np.uint16)
+    hi = np.ascontiguousarray(hist, np.uint32)
+    vp, wp = np.ascontiguousarray(value_params, np.float32), np.ascontiguousarray(width_params, np.float32)
+    assert hi.ndim == 4 and hi.shape[2:] == (10, 1024), "hist is [nj ni][C][10][1024]"
+    planes, channels = hi.shape[0] * hi.shape[1], hi.shape[1]
+    assert planes and vp.size == planes * 18 and wp.size == planes * 18 and st.size % planes == 0
+    info, tiles = np.zeros(8, np.uint32), np.zeros(4, np.uint32)
+    n = C.c_size_t(0)
+    err = C.create_string_buffer(256)
+    L = load_library()
+    # the arrays must hold the tiles the region touches before the library reads them (a malformed file or a bad region is the library's to refuse: it does so first)
+    if L.fri_tiled_info(_p(data), data.size, _p(info)) == 0 and L.fri_tiled_region_tiles(*(int(v) for v in info[:4]), x, y, w, h, _p(tiles)) == 0:
+        if int(tiles[2]) * int(tiles[3]) != hi.shape[0]:
+            e = EmitError(f"fri_tiled_update_from_streams: the region touches {int(tiles[2]) * int(tiles[3])} tiles, the arrays hold {hi.shape[0]}")
+            e.code = -1
+            raise e
+    args = (_p(data), data.size, x, y, w, h, _arg(channels, rct, quality, ycbcr) | flags, _p(st), st.size // planes, _p(hi), _p(vp), _p(wp), threads, _p(tiles))
+    out = np.empty(data.size + st.size * 4 + planes * (10 * 2070 + 256) + hi.shape[0] * 72 + 64, np.uint8)  # the file and, generously, the new payloads: one call as a rule
+    rc = L.fri_tiled_update_from_streams(*args, _p(out), out.size, C.addressof(n), err, 256)
+    if rc == -3:
+        out = np.empty(n.value, np.uint8)
+        rc = L.fri_tiled_update_from_streams(*args, _p(out), out.size, C.addressof(n), err, 256)
+    if rc != 0:
+        e = EmitError(err.value.decode() or f"fri_tiled_update_from_streams: {rc}")
+        e.code = rc
+        raise e
+    return out[: n.value].tobytes(), tuple(int(v) for v in tiles)

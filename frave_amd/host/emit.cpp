@@ -880,13 +880,18 @@ void put_f32(std::vector<uint8_t> &v, float f) {
 constexpr uint8_t kEHD[2] = {0xFF, 0xB2}, kDAT[2] = {0xFF, 0xB4}, kEOC[2] = {0xFF, 0xB8}, kPRD[2] = {0xFF, 0xBB}, kEOI[2] = {0xFF, 0xDF}; // serialize.rs:41-47
 } // namespace
 
+uint32_t metadata_word(ColorSpaceCode cs, bool rct, uint32_t quality, bool ycbcr, bool s420, bool alpha) {
+    return (uint32_t)cs << 30 | 1u << 28 | (rct ? kMdatRct : 0u) | (ycbcr ? kMdatYcbcr : 0u) | (s420 ? kMdat420 : 0u) | (alpha ? kMdatAlpha : 0u) |
+           (quality & kMdatQualityMask) << kMdatQualityShift; // variant: TameTwindragon = 0b01 (images.rs:49-55)
+}
+
 std::vector<uint8_t> serialize(uint32_t height, uint32_t width, ColorSpaceCode cs, const std::vector<ChannelStream> &channels, const std::vector<ChannelParams> &params,
                                bool rct, uint32_t quality, bool ycbcr, bool s420, bool alpha) {
     std::vector<uint8_t> s;
     s.insert(s.end(), {'f', 'r', 'i', 'f'});
     put_u32(s, height);
     put_u32(s, width);
-    put_u32(s, (uint32_t)cs << 30 | 1u << 28 | (rct ? kMdatRct : 0u) | (ycbcr ? kMdatYcbcr : 0u) | (s420 ? kMdat420 : 0u) | (alpha ? kMdatAlpha : 0u) | (quality & kMdatQualityMask) << kMdatQualityShift); // variant: TameTwindragon = 0b01 (images.rs:49-55)
+    put_u32(s, metadata_word(cs, rct, quality, ycbcr, s420, alpha));
     for (size_t ch = 0; ch < channels.size(); ch++) {
         s.insert(s.end(), kPRD, kPRD + 2);
         for (int g = 0; g < 3; g++)
@@ -1035,6 +1040,23 @@ std::string for_each_tile(size_t n_tiles, unsigned threads, Work &&work) {
 static void assemble_tiled(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint64_t nx, uint64_t ny, const std::vector<std::vector<uint8_t>> &payload,
                            std::vector<uint8_t> &out);
 
+// The payload of one tile: the `frif` file of plane group t of the arrays ([..][channels][n_symbols] streams and so on), FRI_EMIT_EMPTY_OK in force, coded on the
+// calling thread. The one per-tile path of encode_tiled_from_streams and update_tiled_from_streams.
+static std::string tile_payload_from_streams(uint32_t tile_w, uint32_t tile_h, uint32_t channels, bool rct, uint32_t quality, bool ycbcr, size_t t, const uint16_t *streams,
+                                             size_t n_symbols, const uint32_t *hist, const float *value_params, const float *width_params, std::vector<uint8_t> &payload) {
+    const size_t plane0 = t * channels;
+    std::vector<ChannelStream> chans;
+    const std::string ce = encode_channels_from_streams(channels, streams + plane0 * n_symbols, n_symbols, hist + plane0 * kContexts * kAlphabet, chans, 0, true, true);
+    if (!ce.empty()) return ce;
+    std::vector<ChannelParams> params(channels);
+    for (uint32_t ch = 0; ch < channels; ch++) {
+        std::memcpy(params[ch].value, value_params + (plane0 + ch) * 18, sizeof(params[ch].value));
+        std::memcpy(params[ch].width, width_params + (plane0 + ch) * 18, sizeof(params[ch].width));
+    }
+    payload = serialize(tile_h, tile_w, channels == 1 ? kLuma : rct || ycbcr ? kYCbCr : kRGB, chans, params, rct, quality, ycbcr);
+    return "";
+}
+
 std::string encode_tiled_from_streams(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t channels, bool rct, uint32_t quality, bool ycbcr,
                                       const uint16_t *streams, size_t n_symbols, const uint32_t *hist, const float *value_params, const float *width_params, unsigned threads,
                                       std::vector<uint8_t> &out) {
@@ -1048,24 +1070,70 @@ std::string encode_tiled_from_streams(uint32_t width, uint32_t height, uint32_t 
         if (!ge.empty()) return ge;
         if (g.n_some != n_symbols) return "n_symbols is not the symbol count of the tile_w x tile_h lattice";
     }
-    const ColorSpaceCode cs = channels == 1 ? kLuma : rct || ycbcr ? kYCbCr : kRGB;
     std::vector<std::vector<uint8_t>> payload(n_tiles);
     const std::string e = for_each_tile(n_tiles, threads, [&](size_t t) -> std::string {
-        const size_t plane0 = t * channels;
-        std::vector<ChannelStream> chans;
-        const std::string ce = encode_channels_from_streams(channels, streams + plane0 * n_symbols, n_symbols, hist + plane0 * kContexts * kAlphabet, chans, 0, true, true);
-        if (!ce.empty()) return ce;
-        std::vector<ChannelParams> params(channels);
-        for (uint32_t ch = 0; ch < channels; ch++) {
-            std::memcpy(params[ch].value, value_params + (plane0 + ch) * 18, sizeof(params[ch].value));
-            std::memcpy(params[ch].width, width_params + (plane0 + ch) * 18, sizeof(params[ch].width));
-        }
-        payload[t] = serialize(tile_h, tile_w, cs, chans, params, rct, quality, ycbcr);
-        return "";
+        return tile_payload_from_streams(tile_w, tile_h, channels, rct, quality, ycbcr, t, streams, n_symbols, hist, value_params, width_params, payload[t]);
     });
     if (!e.empty()) return e;
     assemble_tiled(width, height, tile_w, tile_h, nx, ny, payload, out);
     return "";
+}
+
+// Region update (include/fri_emit.h, "Region update"): the touched sub-grid's payloads are coded from the streams, sub-tile by sub-tile, through the per-tile path
+// of encode_tiled_from_streams; every other payload is the file's own bytes, copied and not looked into; the table is rebuilt around them.
+std::string update_tiled_from_streams(const uint8_t *b, size_t len, const Region &region, uint32_t channels, bool rct, uint32_t quality, bool ycbcr, const uint16_t *streams,
+                                      size_t n_symbols, const uint32_t *hist, const float *value_params, const float *width_params, unsigned threads, TileRange &range,
+                                      const std::function<uint8_t *(size_t)> &place) {
+    TiledInfo info;
+    std::vector<uint64_t> offset;
+    std::string e = parse_tiled(b, len, info, offset);
+    if (!e.empty()) return e;
+    if (info.s420) return kNoUpdate420;
+    if (!region_tiles(info.width, info.height, info.tile_w, info.tile_h, region, range)) return "invalid region";
+    const ColorSpaceCode cs = channels == 1 ? kLuma : rct || ycbcr ? kYCbCr : kRGB;
+    if (metadata_word(cs, rct, quality, ycbcr, false, false) != info.mdat) return "the metadata word of `channels` is not the one the file's tiles carry";
+    {
+        fri::Geometry g;
+        const std::string ge = fri::build_geometry(info.tile_w, info.tile_h, channels, fri::TilingParams{}, g);
+        if (!ge.empty()) return ge;
+        if (g.n_some != n_symbols) return "n_symbols is not the symbol count of the tile_w x tile_h lattice";
+    }
+    const size_t n_sub = (size_t)range.ni * range.nj;
+    const auto file_tile = [&](size_t s) { return ((size_t)range.j0 + s / range.ni) * info.nx + range.i0 + s % range.ni; };
+    std::vector<std::vector<uint8_t>> coded(n_sub);
+    e = for_each_tile(n_sub, threads, [&](size_t s) -> std::string {
+        return tile_payload_from_streams(info.tile_w, info.tile_h, channels, rct, quality, ycbcr, s, streams, n_symbols, hist, value_params, width_params, coded[s]);
+    }, file_tile);
+    if (!e.empty()) return e;
+    // the new table: a touched tile's length is its new payload's, any other keeps its own
+    const size_t n_tiles = (size_t)info.nx * info.ny;
+    std::vector<const std::vector<uint8_t> *> fresh(n_tiles, nullptr);
+    for (size_t s = 0; s < n_sub; s++) fresh[file_tile(s)] = &coded[s];
+    std::vector<uint8_t> table;
+    table.reserve(8 * (n_tiles + 1));
+    uint64_t at = offset[0];
+    for (size_t t = 0; t < n_tiles; t++) put_u64(table, at), at += fresh[t] ? fresh[t]->size() : offset[t + 1] - offset[t];
+    put_u64(table, at);
+    uint8_t *dst = place((size_t)at); // the file's size, exactly: the caller says where it goes, or that it does not fit
+    if (!dst) return "";
+    std::memcpy(dst, b, kTiledHeader); // the header is kept
+    std::memcpy(dst + kTiledHeader, table.data(), table.size());
+    dst += offset[0];
+    for (size_t t = 0; t < n_tiles; t++) { // straight into its place: an untouched payload is read once and written once
+        const uint8_t *src = fresh[t] ? fresh[t]->data() : b + offset[t];
+        const size_t n = fresh[t] ? fresh[t]->size() : (size_t)(offset[t + 1] - offset[t]);
+        std::memcpy(dst, src, n), dst += n;
+    }
+    return "";
+}
+
+std::string update_tiled_from_streams(const uint8_t *b, size_t len, const Region &region, uint32_t channels, bool rct, uint32_t quality, bool ycbcr, const uint16_t *streams,
+                                      size_t n_symbols, const uint32_t *hist, const float *value_params, const float *width_params, unsigned threads, TileRange &range,
+                                      std::vector<uint8_t> &out) {
+    return update_tiled_from_streams(b, len, region, channels, rct, quality, ycbcr, streams, n_symbols, hist, value_params, width_params, threads, range, [&](size_t n) {
+        out.resize(n);
+        return out.data();
+    });
 }
 
 std::string encode_tiled_from_streams420(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t quality, const uint16_t *streams, size_t n_luma,

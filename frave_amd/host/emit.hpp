@@ -13,6 +13,7 @@
 #pragma once
 #include <array>
 #include <cstdint>
+#include <functional>
 #include <memory>
 #include <string>
 #include <vector>
@@ -150,6 +151,7 @@ constexpr uint32_t kMdat420 = 4u;
 // width x height lattice, byte for byte the channel of a Luma file of that stream. The colour-space field, bits 0..2 and the quality describe the three colour
 // channels only. Together with bit 2 it is invalid; bit 3 of a Luma file stays ignored.
 constexpr uint32_t kMdatAlpha = 8u;
+uint32_t metadata_word(ColorSpaceCode cs, bool rct, uint32_t quality, bool ycbcr, bool s420 = false, bool alpha = false); // the word serialize writes at offset 12
 std::vector<uint8_t> serialize(uint32_t height, uint32_t width, ColorSpaceCode cs, const std::vector<ChannelStream> &channels,
                                const std::vector<ChannelParams> &params, bool rct = false, uint32_t quality = 0, bool ycbcr = false, bool s420 = false,
                                bool alpha = false);
@@ -249,6 +251,21 @@ struct TileRange {
 };
 // false for a zero size or a region that leaves the width x height image (compared in 64 bits)
 bool region_tiles(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, const Region &r, TileRange &out);
+// Region update (include/fri_emit.h, "Region update"): the file `frv` with the payloads of the tiles the region touches replaced. streams [nj ni][channels][n_symbols],
+// hist [nj ni][channels][10][1024], value_params / width_params [nj ni][channels][3][6] in the sub-grid's order - what fri_hip_encode_region_tiled_symbols returns;
+// those tiles are coded on `threads` workers through the per-tile path of encode_tiled_from_streams, every other payload is copied and not looked into, the header
+// is kept and the table rebuilt. `range` is filled once the region is known to be good. Errors: parse_tiled's, "invalid region", kNoUpdate420 for a tiled 4:2:0
+// file, a metadata word (of channels, rct, quality, ycbcr) that is not tile 0's, a wrong n_symbols, "tile t: channel c: reason" with t the index in the file's grid.
+inline constexpr const char *kNoUpdate420 =
+    "a tiled 4:2:0 file has no region update (the region split of subsampled tiles is not built): tiled 4:2:0 files are re-encoded whole";
+std::string update_tiled_from_streams(const uint8_t *frv, size_t len, const Region &region, uint32_t channels, bool rct, uint32_t quality, bool ycbcr, const uint16_t *streams,
+                                      size_t n_symbols, const uint32_t *hist, const float *value_params, const float *width_params, unsigned threads, TileRange &range,
+                                      std::vector<uint8_t> &out);
+// ... the same written where the caller says: once the touched tiles are coded the file's size is known, place(size) returns where its bytes go - they are then
+// written straight there, every untouched payload read once and written once - or NULL, and nothing is written (the C entry point's -3).
+std::string update_tiled_from_streams(const uint8_t *frv, size_t len, const Region &region, uint32_t channels, bool rct, uint32_t quality, bool ycbcr, const uint16_t *streams,
+                                      size_t n_symbols, const uint32_t *hist, const float *value_params, const float *width_params, unsigned threads, TileRange &range,
+                                      const std::function<uint8_t *(size_t)> &place);
 // A tiled 4:2:0 file (info.s420): coefs in plane order, [n][F_y][512] then [n][2][F_c][512] with n the tiles decoded - the whole grid or the region's sub-grid.
 // coefs [n_tiles][channels][F][512]. too_small: coefs is NULL or coef_cap (elements) does not hold them - `info` is filled, nothing is decoded.
 // With a region: the file is checked as without one, then only the tiles the region touches are decoded, coefs [nj ni][channels][F][512] in the sub-grid's order;

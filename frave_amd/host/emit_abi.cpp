@@ -384,5 +384,29 @@ int fri_tiled_decode_region(const uint8_t *frv, size_t len, uint32_t threads, ui
     return too_small ? -3 : 0;
 }
 
+int fri_tiled_update_from_streams(const uint8_t *frv, size_t len, uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint32_t channels_arg, const uint16_t *streams,
+                                  uint64_t n_symbols, const uint32_t *hist, const float *value_params, const float *width_params, uint32_t threads, uint32_t tiles[4],
+                                  uint8_t *out, size_t cap, size_t *out_len, char *err, size_t err_cap) {
+    uint32_t channels, quality;
+    bool rct, ycbcr, empty_ok = false;
+    // (FRI_EMIT_420 and FRI_EMIT_ALPHA are refused: split_channels is not given a place for them; FRI_EMIT_EMPTY_OK is always on and may be passed)
+    if (!frv || !streams || !hist || !value_params || !width_params || !tiles || !out_len ||
+        !split_channels(channels_arg, channels, rct, quality, ycbcr, nullptr, nullptr, &empty_ok))
+        return fail(err, err_cap, "invalid argument");
+    TileRange r;
+    size_t needed = 0;
+    bool fits = false;
+    const std::string e = update_tiled_from_streams(frv, len, Region{x, y, w, h}, channels, rct, quality, ycbcr, streams, (size_t)n_symbols, hist, value_params, width_params,
+                                                    threads, r, [&](size_t n) -> uint8_t * {
+                                                        needed = n, fits = out && cap >= n;
+                                                        return fits ? out : nullptr; // (written straight into the caller's buffer)
+                                                    });
+    if (e == "invalid region" || e == "invalid argument" || e == kNoUpdate420) return fail(err, err_cap, e);
+    if (!e.empty()) return fail(err, err_cap, e, -2);
+    tiles[0] = r.i0, tiles[1] = r.j0, tiles[2] = r.ni, tiles[3] = r.nj;
+    *out_len = needed;
+    return fits ? 0 : -3;
+}
+
 #pragma GCC visibility pop
 } // extern "C"

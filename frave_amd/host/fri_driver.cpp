@@ -36,6 +36,12 @@
 //                                                            --region, on a `frif` file and on a tiled 4:2:0 file, naming what to do instead
 //                                                            --region X,Y,W,H: only that rectangle of the image (FRIDecoder::decode_region) - of a `frit` file only
 //                                                            the tiles it touches are decoded; a `frif` file is decoded whole and cropped; no untiled 4:2:0 file and no alpha file
+//   fri_driver update-file <in.frv> <new.pgm|.ppm|.bmp> <out.frv> --region X,Y,W,H   the tiles of the `frit` file in.frv that the rectangle touches are coded anew from
+//                                                            the image, which has the file's size and channels; every other tile's bytes are copied
+//                                                            (libfri::update_bytes_tiled: fri_hip_encode_region_tiled_symbols + fri_tiled_update_from_streams). No mode
+//                                                            flags: the tile shape, the quality and the colour transform are the file's. Refused, naming what to do
+//                                                            instead: a `frif` file, a tiled 4:2:0 file, an image of another size or channel count, no --region.
+//                                                            Self-check: the covered rectangle of out.frv decodes (--region) to the direct round trip of its tiles
 //   fri_driver batch <width> <height> <channels> <n_images> [--gpus N]
 //                                                            BASELINE config 3: host batch with H2D / kernel / D2H overlap; with --gpus N
 //                                                            BASELINE config 4: the batch sharded over N GPUs of this node (image i -> GPU i mod N,
@@ -571,7 +577,102 @@ static int encode_image_tiled420_to_file(const std::vector<uint8_t> &img, uint32
     return 0;
 }
 
+// update-file: the tiles of a `frit` file that a region touches coded anew from an image of the file's size, every other payload copied (libfri::update_bytes_tiled).
+// Self-check: decode-file --region of the covered rectangle of the new file (FRIDecoder::decode_region) equals the direct round trip of those tiles - the covered
+// rectangle is an image of its own whose tiles, edge replication included, are the touched ones (libfri::round_trip_tiled on it); for a lossless file the pixels.
+static int update_file(const std::vector<uint8_t> &file, const std::vector<uint8_t> &img, uint32_t w, uint32_t h, uint32_t c, uint32_t x, uint32_t y, uint32_t rw, uint32_t rh,
+                       const char *out_path) {
+    auto t0 = std::chrono::steady_clock::now();
+    auto upd = libfri::update_bytes_tiled(file, img, h, w, x, y, rw, rh);
+    const double t_upd = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (!upd.ok) {
+        std::fprintf(stderr, "%s\n", upd.error.c_str());
+        return 1;
+    }
+    const libfri::EncodedTiled &u = upd.value;
+    const uint32_t i0 = x / u.tile_w, j0 = y / u.tile_h, ni = (x + rw - 1) / u.tile_w - i0 + 1, nj = (y + rh - 1) / u.tile_h - j0 + 1;
+    const uint32_t cx = i0 * u.tile_w, cy = j0 * u.tile_h;
+    const uint32_t cw = (uint32_t)std::min<uint64_t>(((uint64_t)i0 + ni) * u.tile_w, w) - cx, ch = (uint32_t)std::min<uint64_t>(((uint64_t)j0 + nj) * u.tile_h, h) - cy;
+    std::vector<uint8_t> expected((size_t)cw * ch * c);
+    for (uint32_t row = 0; row < ch; row++) std::memcpy(&expected[(size_t)row * cw * c], &img[(((size_t)cy + row) * w + cx) * c], (size_t)cw * c);
+    if (u.quality) {
+        auto direct = libfri::round_trip_tiled(expected, ch, cw, c, u.tile_w, u.tile_h, u.quality, u.rct, u.ycbcr);
+        if (!direct.ok) {
+            std::fprintf(stderr, "self-check failed: direct round trip: %s\n", direct.error.c_str());
+            return 1;
+        }
+        expected = std::move(direct.value.data);
+    }
+    auto back = libfri::FRIDecoder().decode_region(u.bytes, cx, cy, cw, ch);
+    if (!back.ok || back.value.data != expected) {
+        std::fprintf(stderr, "self-check failed: %s\n", back.ok ? "the covered rectangle of the new file differs from the direct round trip of its tiles" : back.error.c_str());
+        return 1;
+    }
+    if (FILE *f = std::fopen(out_path, "wb")) {
+        std::fwrite(u.bytes.data(), 1, u.bytes.size(), f);
+        std::fclose(f);
+    } else {
+        std::fprintf(stderr, "cannot write %s\n", out_path);
+        return 1;
+    }
+    std::printf("%ux%ux%u in %u x %u tiles of %ux%u: %u x %u tiles from (%u, %u) coded anew, %u copied: %zu bytes (were %zu); region encode and emit %.3f s; self-check: the "
+                "covered rectangle %u,%u,%u,%u decodes to %s\n", w, h, c, u.nx, u.ny, u.tile_w, u.tile_h, ni, nj, i0, j0, u.nx * u.ny - ni * nj, u.bytes.size(), file.size(), t_upd, cx, cy,
+                cw, ch, u.quality ? "the direct round trip of its tiles" : "the new pixels");
+    return 0;
+}
+
 int main(int argc, char **argv) {
+    if (argc >= 2 && std::string(argv[1]) == "update-file") {
+        const char *usage = "usage: fri_driver update-file <in.frv> <new.pgm|new.ppm|new.bmp> <out.frv> --region X,Y,W,H   (no mode flags: the file says what it is)\n";
+        unsigned rx = 0, ry = 0, rw = 0, rh = 0;
+        bool has_region = false;
+        if (argc < 5) {
+            std::fprintf(stderr, "%s", usage);
+            return 2;
+        }
+        for (int i = 5; i < argc; i++) {
+            char tail = 0;
+            if (std::string(argv[i]) == "--region" && i + 1 < argc && std::sscanf(argv[i + 1], "%u,%u,%u,%u%c", &rx, &ry, &rw, &rh, &tail) == 4) has_region = true, i++;
+            else {
+                std::fprintf(stderr, "update-file: unknown or incomplete option %s: it takes --region X,Y,W,H and no mode flags (the tile shape, the channels, the quality and the "
+                                     "colour transform are the file's)\n%s", argv[i], usage);
+                return 2;
+            }
+        }
+        if (!has_region) {
+            std::fprintf(stderr, "update-file: --region X,Y,W,H is missing: name the rectangle that changed (to code the whole image anew use encode-file --tile-size T)\n%s", usage);
+            return 2;
+        }
+        std::vector<uint8_t> file, img;
+        if (FILE *f = std::fopen(argv[2], "rb")) {
+            uint8_t buf[1 << 16];
+            for (size_t n; (n = std::fread(buf, 1, sizeof buf, f)) > 0;) file.insert(file.end(), buf, buf + n);
+            std::fclose(f);
+        } else {
+            std::fprintf(stderr, "cannot open %s\n", argv[2]);
+            return 1;
+        }
+        uint32_t fw = 0, fh = 0, fc = 0;
+        std::string err;
+        if (has_suffix(argv[3], ".pam")) {
+            std::fprintf(stderr, "update-file: an RGBA image (.pam) cannot update a tiled file: alpha in tiles is out of scope (give a PGM, PPM or BMP)\n");
+            return 1;
+        }
+        if (!(has_suffix(argv[3], ".bmp") ? read_bmp(argv[3], img, fw, fh, fc, err) : read_pnm(argv[3], img, fw, fh, fc, err))) {
+            std::fprintf(stderr, "%s\n", err.c_str());
+            return 1;
+        }
+        if (file.size() >= 4 && std::memcmp(file.data(), "frit", 4) == 0) { // the channel count, before libfri sees a raster whose size it cannot tell from its width and height
+            libfri::emit::TiledInfo ti;
+            std::vector<uint64_t> offset;
+            if (libfri::emit::parse_tiled(file.data(), file.size(), ti, offset).empty() && ti.channels != fc) {
+                std::fprintf(stderr, "update-file: the image has %u channel(s), the file %u: convert the image (a PGM for a grey file, a PPM or BMP for a colour file), or encode it whole\n",
+                             fc, ti.channels);
+                return 1;
+            }
+        }
+        return update_file(file, img, fw, fh, fc, rx, ry, rw, rh, argv[4]);
+    }
     if (argc >= 4 && std::string(argv[1]) == "encode-file") {
         std::vector<uint8_t> img;
         uint32_t fw = 0, fh = 0, fc = 0;
@@ -751,7 +852,7 @@ int main(int argc, char **argv) {
         return 0;
     }
     if (argc < 5) {
-        std::fprintf(stderr, "usage: %s roundtrip|encode|batch|batch-frv <width> <height> <channels> [n_images | out.frv]\n       %s encode-file <in.pgm|in.ppm|in.bmp|in.pam> <out.frv> [--rct | [--ycbcr | --420] (--quality Q | --psnr DB | --ssim S | --size BYTES | --bpp B)] [--clean-alpha] [--tile-size T [--device-rans]]\n       %s encode-file <in.ppm|in.bmp> <out.frv> --tile-size-420 T (--quality Q | --target psnr=DB|ssim=S|size=BYTES|bpp=B) [--device-rans]   (tiled 4:2:0; --tile-size T --420 stays refused: the option of its own is this one)\n       %s decode-file <in.frv> <out.pgm|out.ppm|out.bmp|out.pam> [--region X,Y,W,H | --device-rans | --preview M [--device-rans]]\n", argv[0], argv[0], argv[0], argv[0]);
+        std::fprintf(stderr, "usage: %s roundtrip|encode|batch|batch-frv <width> <height> <channels> [n_images | out.frv]\n       %s encode-file <in.pgm|in.ppm|in.bmp|in.pam> <out.frv> [--rct | [--ycbcr | --420] (--quality Q | --psnr DB | --ssim S | --size BYTES | --bpp B)] [--clean-alpha] [--tile-size T [--device-rans]]\n       %s encode-file <in.ppm|in.bmp> <out.frv> --tile-size-420 T (--quality Q | --target psnr=DB|ssim=S|size=BYTES|bpp=B) [--device-rans]   (tiled 4:2:0; --tile-size T --420 stays refused: the option of its own is this one)\n       %s decode-file <in.frv> <out.pgm|out.ppm|out.bmp|out.pam> [--region X,Y,W,H | --device-rans | --preview M [--device-rans]]\n       %s update-file <in.frv> <new.pgm|new.ppm|new.bmp> <out.frv> --region X,Y,W,H\n", argv[0], argv[0], argv[0], argv[0], argv[0]);
         return 2;
     }
     const std::string cmd = argv[1];

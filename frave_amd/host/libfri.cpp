@@ -1347,6 +1347,58 @@ Result<RasterImage> round_trip_tiled(const std::vector<uint8_t> &pixels, uint32_
     return r;
 }
 
+Result<EncodedTiled> update_bytes_tiled(const std::vector<uint8_t> &file, const std::vector<uint8_t> &pixels, uint32_t height, uint32_t width, uint32_t x, uint32_t y, uint32_t w,
+                                        uint32_t h, int device, unsigned threads) {
+    Result<EncodedTiled> r;
+    auto fail = [&](const std::string &why) {
+        r.error = "Failed to update: " + why;
+        return r;
+    };
+    if (file.size() >= 4 && std::memcmp(file.data(), "frif", 4) == 0)
+        return fail("an untiled `frif` file has no tiles to update: encode the new image whole (encode-file), or tile it (encode-file --tile-size)");
+    emit::TiledInfo ti;
+    std::vector<uint64_t> offset;
+    if (const std::string e = emit::parse_tiled(file.data(), file.size(), ti, offset); !e.empty()) return fail(e);
+    if (ti.s420) return fail(emit::kNoUpdate420);
+    if (width != ti.width || height != ti.height)
+        return fail("the image is " + std::to_string(width) + "x" + std::to_string(height) + ", the file's is " + std::to_string(ti.width) + "x" + std::to_string(ti.height) +
+                    ": a region update keeps the file's size, encode an image of another size whole");
+    if (pixels.size() != (size_t)width * height * ti.channels)
+        return fail("the image does not have the file's " + std::to_string(ti.channels) + " channel(s): convert it, or encode it whole");
+    emit::TileRange range;
+    if (!emit::region_tiles(ti.width, ti.height, ti.tile_w, ti.tile_h, emit::Region{x, y, w, h}, range)) return fail("invalid region");
+    std::array<int32_t, 32> qm;
+    qm.fill(1); // a lossless file: ones
+    if (ti.quality && fri_hip_quality_matrix((int)ti.quality, qm.data()) != FRI_HIP_OK) return fail("invalid quality");
+    Device dev(device);
+    if (!dev.ok()) return fail(dev.error());
+    fri_hip_plan_tiled *raw = nullptr;
+    // (a file may hold tiles with holes: whoever wrote it asked for them)
+    if (const int rc = fri_hip_plan_tiled_create(dev.ctx(), ti.width, ti.height, ti.channels, ti.tile_w, ti.tile_h, FRI_HIP_TILED_ALLOW_HOLES, &raw); rc != FRI_HIP_OK) return fail(dev.describe(rc));
+    TiledPlan plan(raw);
+    fri_hip_plan *tile = fri_hip_plan_tiled_tile(raw);
+    if (const std::string e = set_colour_transform(tile, ti.rct, dev, ti.ycbcr); !e.empty()) return fail(e);
+    if (const std::string e = set_plan_stream_order(tile, dev); !e.empty()) return fail(e);
+    const size_t planes = (size_t)range.ni * range.nj * ti.channels;
+    const uint64_t n = fri_hip_plan_num_some(tile);
+    std::vector<uint16_t> symbols(planes * (size_t)n);
+    std::vector<uint32_t> hist(planes * CONTEXT_AMOUNT * ALPHABET_SIZE);
+    std::vector<float> vp(planes * 18), wp(planes * 18);
+    std::vector<uint64_t> oob(planes, 0);
+    if (const int rc = fri_hip_encode_region_tiled_symbols(raw, pixels.data(), x, y, w, h, qm.data(), vp.data(), wp.data(), symbols.data(), hist.data(), oob.data()); rc != FRI_HIP_OK)
+        return fail(dev.describe(rc));
+    for (uint64_t v : oob)
+        if (v) return fail("symbol outside the 1024-entry alphabet");
+    if (const std::string e = emit::update_tiled_from_streams(file.data(), file.size(), emit::Region{x, y, w, h}, ti.channels, ti.rct, ti.quality, ti.ycbcr, symbols.data(), (size_t)n,
+                                                              hist.data(), vp.data(), wp.data(), threads, range, r.value.bytes);
+        !e.empty())
+        return fail(e);
+    r.value.tile_w = ti.tile_w, r.value.tile_h = ti.tile_h, r.value.nx = ti.nx, r.value.ny = ti.ny;
+    r.value.quality = (int)ti.quality, r.value.rct = ti.rct, r.value.ycbcr = ti.ycbcr;
+    r.ok = true;
+    return r;
+}
+
 // ---- tiled 4:2:0 coding ----------------------------------------------------------------------------------------------------------------------------
 Result<EncodedTiled> encode_bytes_tiled420(const std::vector<uint8_t> &rgb, uint32_t height, uint32_t width, int quality, uint32_t tile_size, int device, unsigned threads) {
     EncoderOpts opts;

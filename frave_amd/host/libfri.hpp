@@ -290,6 +290,13 @@ Result<EncodedTiled> encode_bytes_tiled(const std::vector<uint8_t> &pixels, uint
 // (quality 0: ones, else the quality's matrix; rct / ycbcr: the colour transform), then fri_hip_decode_image_tiled - what such a file decodes to.
 Result<RasterImage> round_trip_tiled(const std::vector<uint8_t> &pixels, uint32_t height, uint32_t width, uint32_t channels, uint32_t tile_w, uint32_t tile_h, int quality, bool rct,
                                      bool ycbcr, int device = 0);
+// Region update (include/fri_emit.h, "Region update"): the tiled file `file` with the tiles that the region x, y, w, h touches coded anew from `pixels`, the
+// whole raster [height][width][C] of the file's size, and every other payload copied. The tile shape, the channels and the mode are read from the file
+// (fri_tiled_info) and the tiled plan is set up accordingly - a quality gives fri_hip_quality_matrix, a lossless file the all-ones matrix, RCT / YCbCr the colour
+// transform - then fri_hip_encode_region_tiled_symbols (only the covered rectangle goes to the device) and emit::update_tiled_from_streams on `threads` workers.
+// The result's fields describe the file; bytes is the updated file. A `frif` file, a tiled 4:2:0 file and a raster of another size or channel count are refused.
+Result<EncodedTiled> update_bytes_tiled(const std::vector<uint8_t> &file, const std::vector<uint8_t> &pixels, uint32_t height, uint32_t width, uint32_t x, uint32_t y, uint32_t w,
+                                        uint32_t h, int device = 0, unsigned threads = 0);
 
 // Tiled 4:2:0 coding (include/fri_hip.h, "Tiled 4:2:0 coding") of width x height RGB pixels at `quality` (1..99): tiles of about tile_size x tile_size at which
 // both lattices own every pixel (fri_hip_tile_shape420), the device splits and codes them in two batches (fri_hip_encode_image_tiled420_symbols), the emitter codes

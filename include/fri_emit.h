@@ -84,6 +84,23 @@
  * pixel (y + ry, x + rx), which is pixel (y + ry - j tile_h, x + rx - i tile_w) of tile (j, i): no replicated pixel is ever copied. By definition the region
  * raster is the crop [y : y + h, x : x + w] of what fri_hip_decode_image_tiled returns for the same file.
  *
+ * Region update (fri_tiled_update_from_streams below; the device side is fri_hip_encode_region_tiled_symbols, include/fri_hip.h): the write-side twin of region
+ * decode. A tile's payload depends on that tile's pixels, the matrix and the mode and on nothing else, so a file F_A (tiled 4:4:4, C = 1 or 3, any mode), a raster
+ * B [H][W][C] of the file's size and a region x, y, w, h (the rules above) define an updated file. The sub-grid {i0, j0, ni, nj} is the one above, unchanged.
+ *   covered rectangle  cx = i0 tile_w, cy = j0 tile_h, cw = min((i0 + ni) tile_w, W) - cx, ch = min((j0 + nj) tile_h, H) - cy: the image pixels the touched
+ *                      tiles are made of, and the only pixels of B that are read.
+ *   region split       the sub-grid tile raster [nj ni][tile_h][tile_w][C]: sub(s, yy, xx, c) = B(min((j0 + b) tile_h + yy, H - 1), min((i0 + a) tile_w + xx, W - 1), c)
+ *                      for s = b ni + a - by definition rows {(j0 + b) nx + i0 + a} of what fri_hip_split_tiles_dev makes of B.
+ *   updated file       the header of F_A is kept; tile t of the sub-grid carries the payload fri_tiled_encode_from_streams writes for that tile of B; every other
+ *                      tile carries F_A's payload bytes, copied and not looked into (their 16-byte headers are checked, as fri_tiled_decode_region checks them);
+ *                      the offset table is rebuilt.
+ *   consequences       if A and B agree outside the covered rectangle the updated file is byte for byte the file a whole encode of B writes; for any A and B it
+ *                      is the splice of the two whole files' payloads; a region that touches every tile gives the whole encode of B.
+ *   metadata           all tiles of a file carry one metadata word and an update keeps that true: the `channels` word given must produce tile 0's word,
+ *                      otherwise the call is refused and nothing is written.
+ * Out of scope: tiled 4:2:0 files (a region split of subsampled tiles, K12, is a follow-up; such files are re-encoded whole); the device rANS route for the
+ * sub-grid (K11 loses with few planes); several regions per call; updating a file in place; changing a file's quality or mode.
+ *
  * Tiled 4:2:0 (fri_tiled_encode_from_streams420 and fri_tiled_encode_from_coded420 below; include/fri_hip.h, "Tiled 4:2:0 coding", has the device side): the `frit` container is unchanged and stays
  * at version 1. In a tiled 4:2:0 file every payload is a `frif` file of a tile_h x tile_w image with colour space YCbCr, metadata bits 1 and 2 set, and a quality of
  * 1..99: exactly what fri_emit_encode_image_from_streams writes for that tile with 3 | FRI_EMIT_YCBCR | FRI_EMIT_420 | FRI_EMIT_QUALITY(q) | FRI_EMIT_EMPTY_OK.
@@ -248,6 +265,18 @@ int fri_tiled_region_tiles(uint32_t width, uint32_t height, uint32_t tile_w, uin
  * coef_cap (in elements) is too small. */
 int fri_tiled_decode_region(const uint8_t *frv, size_t len, uint32_t threads, uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint32_t info[8], uint32_t tiles[4],
                             int32_t *coefs, size_t coef_cap, char *err, size_t err_cap);
+/* Region update ("Region update" above): the file `frv` with the payloads of the tiles the region touches coded anew. streams [nj ni][C][n_symbols] u16, hist
+ * [nj ni][C][10][1024], value_params / width_params [nj ni][C][3][6] in the sub-grid's order: what fri_hip_encode_region_tiled_symbols returns. `channels` is what
+ * fri_tiled_encode_from_streams takes (flags + quality, FRI_EMIT_EMPTY_OK always in force) and must produce the metadata word of tile 0. The touched tiles are
+ * coded on `threads` workers through the same per-tile path as fri_tiled_encode_from_streams, the bytes are the same for every thread count; the other payloads
+ * are copied and not looked into, so damage inside their bodies is copied, not reported. -1 for a region fri_tiled_region_tiles refuses ("invalid region"), for
+ * FRI_EMIT_420 / FRI_EMIT_ALPHA and for a tiled 4:2:0 file (the message says tiled 4:2:0 files are re-encoded whole); -2 for anything that is not a well-formed
+ * `frit` file (a `frif` file among them), a wrong n_symbols, a metadata word that differs from tile 0's, or a tile's error ("tile t: channel c: reason", t in the
+ * file's grid). Returns 0 with *out_len and tiles = {i0, j0, ni, nj}, or -3 with *out_len = the needed size and `tiles` filled when out is NULL or cap is too
+ * small. The size is exact because the touched tiles are coded before it is known: a size query codes them, and the call that follows codes them again. */
+int fri_tiled_update_from_streams(const uint8_t *frv, size_t len, uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint32_t channels, const uint16_t *streams,
+                                  uint64_t n_symbols, const uint32_t *hist, const float *value_params, const float *width_params, uint32_t threads, uint32_t tiles[4],
+                                  uint8_t *out, size_t cap, size_t *out_len, char *err, size_t err_cap);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

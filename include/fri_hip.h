@@ -673,6 +673,40 @@ int fri_hip_merge_tiles_region_dev(fri_hip_plan_tiled *p, const uint8_t *d_tiles
 int fri_hip_decode_region_tiled_dev(fri_hip_plan_tiled *p, const int32_t *d_coefs, const int32_t qmatrix[32], uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint8_t *d_region,
                                     void *stream);
 int fri_hip_decode_region_tiled(fri_hip_plan_tiled *p, const int32_t *coefs, const int32_t qmatrix[32], uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint8_t *pixels);
+/* Region update: the write-side twin of region decode - only the tiles a rectangle touches are split and coded, fri_tiled_update_from_streams (include/fri_emit.h)
+ * copies every other payload of the file. A tile's payload depends on that tile's pixels, the matrix and the mode and on nothing else, so this is exact. The
+ * region x, y, w, h and its sub-grid {i0, j0, ni, nj} are those of region decode, unchanged; sub-tile s = b ni + a is tile (j0 + b) nx + (i0 + a).
+ *   covered rectangle  cx = i0 tile_w, cy = j0 tile_h, cw = min((i0 + ni) tile_w, W) - cx, ch = min((j0 + nj) tile_h, H) - cy: the image pixels the touched
+ *                      tiles are made of, and the only pixels that are read.
+ *   region split       the sub-grid tile raster [nj ni][tile_h][tile_w][C]: sub(s, yy, xx, c) = B(min((j0 + b) tile_h + yy, H - 1), min((i0 + a) tile_w + xx, W - 1), c)
+ *                      of the raster B [H][W][C] - by definition rows {(j0 + b) nx + i0 + a} of what fri_hip_split_tiles_dev makes of B. Clamping is to the image's
+ *                      last row and column, which lie inside the covered rectangle whenever an edge tile is touched.
+ *   source             d_src, src_pitch (bytes), src_x, src_y, src_w, src_h: d_src points at image pixel (src_y, src_x) of a pitched rectangle of src_w x src_h
+ *                      pixels that lies in the image and contains the covered rectangle. The whole raster on the device is src_pitch = W C, origin 0, 0, size
+ *                      W, H; a staged copy of the covered rectangle alone is src_pitch = cw C, origin cx, cy, size cw, ch.
+ * fri_hip_plan_tiled_region_cover: out[4] = {cx, cy, cw, ch}; works on host-only plans; FRI_HIP_ERR_INVALID_ARGUMENT as fri_hip_plan_tiled_region.
+ * fri_hip_split_tiles_region_dev (K10's split_tiles_region_kernel): the source -> d_tiles, the sub-grid's tile raster. Nothing outside the covered rectangle is
+ * read, nothing but the ni nj tile_h tile_w C bytes of d_tiles is written; only enqueues on `stream`, can be captured into a graph, any pointer alignment.
+ * FRI_HIP_ERR_INVALID_ARGUMENT for a NULL pointer, a bad region, a source rectangle that does not contain the covered rectangle or leaves the image, and
+ * src_pitch < src_w C; FRI_HIP_ERR_NO_DEVICE on a host-only plan.
+ * fri_hip_encode_symbols_region_tiled_dev: grows the plan's tile buffer to ni nj tiles, never to the image's, runs the region split, then the direct-form
+ * fri_hip_encode_symbols_batch_dev call fri_hip_encode_symbols_tiled_dev makes, with n_images = ni nj, all on `stream`. The outputs are in the sub-grid's order with
+ * the layouts of the whole-image call: d_symbols u16 [nj ni][C][num_some], d_params [nj ni][C][2][3][6], d_hist [nj ni][C][10][1024], d_n_out_of_alphabet and
+ * d_fit_out_of_range [nj ni][C] (the latter may be NULL) - bit for bit the sub-grid's rows of fri_hip_encode_symbols_tiled_dev's for the same raster. The inner
+ * plan needs its stream order; a capturing stream is refused (FRI_HIP_ERR_INVALID_ARGUMENT) before anything is enqueued or allocated.
+ * fri_hip_encode_region_tiled_symbols: the host form - `pixels` is the whole host raster [H][W][C], of which only the covered rectangle goes up: one 2-D copy
+ * into a plan-owned buffer that grows to cw ch C. The fit is on; synchronous; everything is read back in the sub-grid's order, laid out as
+ * fri_hip_encode_image_tiled_symbols lays it out: what fri_tiled_update_from_streams takes. FRI_HIP_ERR_OUT_OF_RANGE as in fri_hip_encode_image.
+ * Out of scope: tiled 4:2:0 plans (a region split of subsampled tiles, K12, is a follow-up); the device rANS route for the sub-grid (K11 loses with few planes,
+ * profiles/rans_time.txt); several regions per call; updating a file in place; changing a file's quality or mode. */
+int fri_hip_plan_tiled_region_cover(const fri_hip_plan_tiled *p, uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint32_t out[4]);
+int fri_hip_split_tiles_region_dev(fri_hip_plan_tiled *p, const uint8_t *d_src, size_t src_pitch, uint32_t src_x, uint32_t src_y, uint32_t src_w, uint32_t src_h, uint32_t x,
+                                   uint32_t y, uint32_t w, uint32_t h, uint8_t *d_tiles, void *stream);
+int fri_hip_encode_symbols_region_tiled_dev(fri_hip_plan_tiled *p, const uint8_t *d_src, size_t src_pitch, uint32_t src_x, uint32_t src_y, uint32_t src_w, uint32_t src_h,
+                                            uint32_t x, uint32_t y, uint32_t w, uint32_t h, const int32_t qmatrix[32], int fit, float *d_params, uint16_t *d_symbols,
+                                            uint32_t *d_hist, uint64_t *d_n_out_of_alphabet, uint64_t *d_fit_out_of_range, void *stream);
+int fri_hip_encode_region_tiled_symbols(fri_hip_plan_tiled *p, const uint8_t *pixels, uint32_t x, uint32_t y, uint32_t w, uint32_t h, const int32_t qmatrix[32],
+                                        float *value_params, float *width_params, uint16_t *symbols, uint32_t *hist, uint64_t *n_out_of_alphabet);
 /* The distortion of a tile raster against a raster (K10's measuring kernel): the merge's walk with nothing stored. d_tiles [ny nx][tile_h][tile_w][C] is compared
  * with the same bytes of d_reference_raster [H][W][C]; replicated rows and columns are skipped, so every image pixel is counted once and no replicated one.
  * d_out uint64 [2 C + 1], the layout of fri_hip_measure_distortion_dev: d_out[2 c] = the sum of (tile - reference)^2 of channel c, d_out[2 c + 1] = the largest
