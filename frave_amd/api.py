@@ -55,6 +55,8 @@ SYMBOLS = [
     "fri_hip_decode_scratch_bytes", "fri_hip_decode_planes_dev", "fri_hip_decode_time_planes_dev", "fri_hip_decode_image_tiled_coded", "fri_hip_decode_image_tiled420_coded",
     "fri_hip_plan_num_some_levels", "fri_hip_preview_size", "fri_hip_decode_planes_levels_dev", "fri_hip_preview_tiles_dev", "fri_hip_preview_image_tiled",
     "fri_hip_preview_image_tiled_coded",
+    "fri_hip_plan_tiled_regions", "fri_hip_merge_tiles_regions_dev", "fri_hip_decode_regions_tiled_dev", "fri_hip_decode_regions_tiled",
+    "fri_hip_decode_regions_tiled_coded",
 ]
 DECODE_TRUNCATED, DECODE_BAD_MODEL, DECODE_BAD_SLOT = 1, 2, 4  # FRI_HIP_DECODE_*: bits of a plane's status word of fri_hip_decode_planes_dev (include/fri_hip.h)
 RANS_EMPTY_OK = 1  # FRI_HIP_RANS_EMPTY_OK: `flags` of fri_hip_rans_encode_planes_dev - a context without counts is coded (the emitter's FRI_EMIT_EMPTY_OK)
@@ -241,6 +243,11 @@ def load_library():
     L.fri_hip_merge_tiles_region_dev.argtypes = [vp, vp, u32, u32, u32, u32, vp, vp]
     L.fri_hip_decode_region_tiled_dev.argtypes = [vp, vp, vp, u32, u32, u32, u32, vp, vp]
     L.fri_hip_decode_region_tiled.argtypes = [vp, vp, vp, u32, u32, u32, u32, vp]
+    L.fri_hip_plan_tiled_regions.argtypes = [vp, u32, vp, vp, C.c_size_t, vp, vp, C.c_size_t]
+    L.fri_hip_merge_tiles_regions_dev.argtypes = [vp, vp, u32, u32, vp, vp, vp]
+    L.fri_hip_decode_regions_tiled_dev.argtypes = [vp, vp, vp, u32, vp, vp, vp]
+    L.fri_hip_decode_regions_tiled.argtypes = [vp, vp, vp, u32, vp, vp]
+    L.fri_hip_decode_regions_tiled_coded.argtypes = [vp, u32, vp, vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp]
     L.fri_hip_plan_tiled_region_cover.argtypes = [vp, u32, u32, u32, u32, vp]
     L.fri_hip_split_tiles_region_dev.argtypes = [vp, vp, C.c_size_t, u32, u32, u32, u32, u32, u32, u32, u32, vp, vp]
     L.fri_hip_encode_symbols_region_tiled_dev.argtypes = [vp, vp, C.c_size_t, u32, u32, u32, u32, u32, u32, u32, u32, vp, i32, vp, vp, vp, vp, vp, vp]
@@ -1319,6 +1326,84 @@ class PlanTiled:
         out = np.empty(w * h * self.channels, np.uint8)
         _check(load_library().fri_hip_decode_region_tiled(self._h, _p(co), _p(_q(qmatrix)), x, y, w, h, _p(out)), "fri_hip_decode_region_tiled", self.ctx)
         return out
+
+    # ---- several regions per call: the tile list, the region table and K15 ----------------------------
+    @staticmethod
+    def _regions(regions):
+        """regions as the contiguous uint32 [R][4] array the C side reads; a shape or a value it cannot hold is the library's refusal (-1)"""
+        try:
+            wide = np.asarray(regions, np.int64).reshape(-1, 4)
+        except (ValueError, TypeError, OverflowError):
+            raise FriHipError(-1, "regions must be rows of (x, y, w, h)", "") from None
+        if (wide < 0).any() or (wide > 0xFFFFFFFF).any():
+            raise FriHipError(-1, "regions must be rows of (x, y, w, h), each in 32 bits", "")
+        return np.ascontiguousarray(wide, np.uint32)
+
+    def _split_regions(self, packed, rg):
+        """the packed rasters as a list of [h][w][C] views, region after region"""
+        out, at = [], 0
+        for _, _, w, h in rg.tolist():
+            out.append(packed[at : at + w * h * self.channels].reshape(h, w, self.channels))
+            at += w * h * self.channels
+        return out
+
+    def regions(self, regions):
+        """fri_hip_plan_tiled_regions: (list uint32 [T], table uint32 [8 (R + 1) + nx ny]) of `regions` [(x, y, w, h), ...] - the strictly ascending file-grid
+        indices of the tiles at least one region touches, and the region table K15 reads (include/fri_hip.h, "Several regions"; its row R holds the packed
+        output's bytes in words 4, 5 and n_groups in word 6). Works on a host-only plan. FriHipError (-1) for no regions, more than 65535, a region that is
+        empty or leaves the image, n_groups >= 2^31. The plan remembers the last table it wrote: merge_tiles_regions_dev takes that one."""
+        rg = self._regions(regions)
+        n = C.c_size_t(0)
+        L = load_library()
+        rc = L.fri_hip_plan_tiled_regions(self._h, rg.shape[0], _p(rg), None, 0, C.addressof(n), None, 0)
+        if rc != -3:  # (the size query's answer: the buffers are too small, n is filled)
+            _check(rc or -1, "fri_hip_plan_tiled_regions", self.ctx)
+        tiles, table = np.zeros(n.value, np.uint32), np.zeros(8 * (rg.shape[0] + 1) + self.n_tiles, np.uint32)
+        _check(L.fri_hip_plan_tiled_regions(self._h, rg.shape[0], _p(rg), _p(tiles), tiles.size, C.addressof(n), _p(table), table.size), "fri_hip_plan_tiled_regions", self.ctx)
+        return tiles, table
+
+    def merge_tiles_regions_dev(self, d_tiles, n_list, n_regions, d_table, d_out, stream=0):
+        """fri_hip_merge_tiles_regions_dev (K15 alone), device pointers as ints: the tile-list raster [T][tile_h][tile_w][C] -> the packed region rasters. d_table
+        must be, in device memory, the table regions() LAST returned on this plan, n_list and n_regions its T and R. Only enqueues; capturable."""
+        _check(load_library().fri_hip_merge_tiles_regions_dev(self._h, d_tiles, int(n_list), int(n_regions), d_table, d_out, stream), "fri_hip_merge_tiles_regions_dev", self.ctx)
+
+    def decode_regions_tiled_dev(self, d_coefs, regions, d_out, qmatrix=None, stream=0):
+        """fri_hip_decode_regions_tiled_dev: d_coefs int32 [T][C][F][512] in list order -> d_out, the packed region rasters, device pointers: the inverse kernel
+        over the listed tiles into the plan's tile buffer, then K15. `regions` is host memory. Refuses a capturing stream."""
+        rg = self._regions(regions)
+        _check(load_library().fri_hip_decode_regions_tiled_dev(self._h, d_coefs, _p(_q(qmatrix)), rg.shape[0], _p(rg), d_out, stream), "fri_hip_decode_regions_tiled_dev", self.ctx)
+
+    def decode_regions_tiled(self, coefs, regions, qmatrix=None):
+        """fri_hip_decode_regions_tiled: coefs int32 [T][C][F][512] (what emit.tiled_decode_tiles returns for regions()'s list) -> a list of uint8 [h][w][C]
+        arrays, one per region: each the crop [y : y + h, x : x + w] of what decode_image_tiled returns for the same file."""
+        rg = self._regions(regions)
+        tiles, table = self.regions(rg)
+        co = np.ascontiguousarray(coefs, np.int32).reshape(-1)
+        assert co.size == tiles.size * self.channels * self.num_cells * 512
+        out = np.empty(int(table[8 * rg.shape[0] + 4]) | int(table[8 * rg.shape[0] + 5]) << 32, np.uint8)
+        _check(load_library().fri_hip_decode_regions_tiled(self._h, _p(co), _p(_q(qmatrix)), rg.shape[0], _p(rg), _p(out)), "fri_hip_decode_regions_tiled", self.ctx)
+        return self._split_regions(out, rg)
+
+    def decode_regions_coded(self, coded, regions, qmatrix=None):
+        """fri_hip_decode_regions_tiled_coded: the coded planes of regions()'s tile list - what emit.tiled_parse_coded_tiles returns, with or without its TiledInfo -
+        through the device decoder (K13) over the T C planes, the inverse kernel and K15 -> (a list of uint8 [h][w][C] arrays, status uint32 [T C][4]); the arrays
+        are decode_regions_tiled's of emit.tiled_decode_tiles's planes. A plane the decoder refuses raises FriHipError (-1) with the status as .status and the
+        file-grid index of the first refused plane's tile as .tile. Needs set_stream_order()."""
+        rg = self._regions(regions)
+        tiles, table = self.regions(rg)
+        planes = tiles.size * self.channels
+        words, n_words, models, off, vp, wp = _coded_planes(coded, planes)
+        out = np.empty(int(table[8 * rg.shape[0] + 4]) | int(table[8 * rg.shape[0] + 5]) << 32, np.uint8)
+        status = np.zeros((planes, 4), np.uint32)
+        rc = load_library().fri_hip_decode_regions_tiled_coded(self._h, rg.shape[0], _p(rg), _p(words), words.shape[1], _p(n_words), _p(models), _p(off), _p(vp), _p(wp),
+                                                               _p(_q(qmatrix)), _p(out), _p(status))
+        try:
+            _check_decode(rc, "fri_hip_decode_regions_tiled_coded", self.ctx, status)
+        except FriHipError as e:
+            bad = np.flatnonzero(status[:, 0])
+            e.tile = int(tiles[bad[0] // self.channels]) if bad.size else None
+            raise
+        return self._split_regions(out, rg), status
 
     # ---- region update: only the tiles a rectangle touches are split and coded ------------------------
     def region_cover(self, x, y, w, h):

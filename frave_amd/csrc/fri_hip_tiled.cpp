@@ -1,5 +1,5 @@
 // fri_hip_tiled.cpp -- the tiled plan kind of the C ABI (fri_hip_plan_tiled: include/fri_hip.h): the plan and its grid, split and merge, the encode chain and
-// its coded form (K11), the image and region decodes and the decode from coded planes (K13), the preview decode (K14), the measure, the size estimate and the quality searches. Host-side glue like fri_hip.cpp, on one ordinary
+// its coded form (K11), the image and region decodes, several regions in one call (K15) and the decode from coded planes (K13), the preview decode (K14), the measure, the size estimate and the quality searches. Host-side glue like fri_hip.cpp, on one ordinary
 // plan of the tile's shape. The grid, plan creation, the host size estimate and the coded route are tiled_common.hpp's, shared with fri_hip_tiled420.cpp; the
 // searches are TiledSearch on search_scaffold.hpp.
 #include "search_scaffold.hpp"
@@ -34,6 +34,12 @@ struct fri_hip_plan_tiled {
     Grown<uint8_t> region;            // fri_hip_decode_region_tiled: the region raster [h][w][C]
     DevMem<uint32_t> owner;           // K14: [tile_h][tile_w] cell << 9 | leaf of the retained cell that owns a tile pixel, ~0 where none does; uploaded with the plan
     Grown<uint8_t> preview;           // fri_hip_preview_image_tiled*: the thumbnail [h'][w'][C]
+    Grown<uint32_t> region_table;     // fri_hip_decode_regions_tiled*: the region table, 8 (R + 1) + nx ny words
+    Grown<uint8_t> regions_out;       // fri_hip_decode_regions_tiled[_coded]: the packed region rasters
+    // what the last table fri_hip_plan_tiled_regions wrote was made for: the launch of fri_hip_merge_tiles_regions_dev has n_groups workgroups, and the host alone knows it
+    struct {
+        uint32_t n_regions = 0, n_list = 0, n_groups = 0;
+    } planned;
     size_t n_tiles() const { return grid.n_tiles(); }
     size_t raster_bytes() const { return (size_t)grid.width * grid.height * channels; }
     size_t tile_bytes() const { return (size_t)grid.tile_w * grid.tile_h * channels; }
@@ -271,6 +277,141 @@ int fri_hip_decode_region_tiled(fri_hip_plan_tiled *p, const int32_t *coefs, con
     HIP_TRY(c, hipMemcpy(p->coefs, coefs, n * image * sizeof(int32_t), hipMemcpyHostToDevice));
     if ((rc = fri_hip_decode_region_tiled_dev(p, p->coefs, qmatrix, x, y, w, h, p->region, nullptr))) return rc;
     HIP_TRY(c, hipMemcpy(pixels, p->region, bytes, hipMemcpyDeviceToHost));
+    return FRI_HIP_OK;
+}
+
+/* ---- several regions per call: the tile list, the region table and K15 ---- */
+namespace {
+// What R regions make on the plan's grid (include/fri_emit.h, "Several regions"): the tile list, the region table, its n_groups and the packed output's bytes.
+struct RegionsPlan {
+    std::vector<uint32_t> list, table;
+    uint32_t n_groups = 0;
+    uint64_t total = 0; // off_R
+};
+// false for R = 0, R > 65535, a region the grid refuses and n_groups >= 2^31
+bool plan_regions(const fri_hip_plan_tiled *p, uint32_t n_regions, const uint32_t *regions, RegionsPlan &out) {
+    const TileGrid &g = p->grid;
+    if (!regions || !n_regions || n_regions > 65535u || (uint64_t)g.width * p->channels > 0x7FFFFFFFull) return false;
+    const size_t n_grid = g.n_tiles(), rows = 8 * ((size_t)n_regions + 1);
+    out.table.assign(rows + n_grid, 0);
+    uint32_t *slot = out.table.data() + rows;
+    uint64_t off = 0, groups = 0;
+    for (uint32_t r = 0; r < n_regions; r++) {
+        const uint32_t *q = regions + 4 * (size_t)r;
+        uint32_t range[4];
+        if (g.region(q[0], q[1], q[2], q[3], range)) return false;
+        for (uint32_t b = 0; b < range[3]; b++) std::fill_n(slot + ((size_t)range[1] + b) * g.nx + range[0], range[2], 1u); // touched
+        uint32_t *row = out.table.data() + 8 * (size_t)r;
+        row[0] = q[0], row[1] = q[1], row[2] = q[2], row[3] = q[3];
+        row[4] = (uint32_t)off, row[5] = (uint32_t)(off >> 32), row[6] = (uint32_t)groups;
+        const uint64_t strips = ((uint64_t)q[2] * p->channels + 15) / 16; // of one row: a lane owns 16 bytes of it
+        off += (uint64_t)q[2] * q[3] * p->channels;
+        groups += ((uint64_t)q[3] * strips + 255) / 256;
+        if (groups >= 0x80000000ull) return false; // (w C < 2^31 and h < 2^32: neither sum can have wrapped before this is seen)
+    }
+    uint32_t *last = out.table.data() + 8 * (size_t)n_regions;
+    last[4] = (uint32_t)off, last[5] = (uint32_t)(off >> 32), last[6] = (uint32_t)groups;
+    out.list.clear();
+    for (size_t t = 0; t < n_grid; t++) {
+        if (slot[t]) slot[t] = (uint32_t)out.list.size(), out.list.push_back((uint32_t)t);
+        else slot[t] = 0xFFFFFFFFu;
+    }
+    out.n_groups = (uint32_t)groups, out.total = off;
+    return true;
+}
+void remember(fri_hip_plan_tiled *p, uint32_t n_regions, const RegionsPlan &r) {
+    p->planned.n_regions = n_regions, p->planned.n_list = (uint32_t)r.list.size(), p->planned.n_groups = r.n_groups;
+}
+} // namespace
+
+int fri_hip_plan_tiled_regions(fri_hip_plan_tiled *p, uint32_t n_regions, const uint32_t *regions, uint32_t *list, size_t list_cap, size_t *n_list, uint32_t *table,
+                               size_t table_cap_words) {
+    RegionsPlan r;
+    if (!p || !n_list || !plan_regions(p, n_regions, regions, r)) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    *n_list = r.list.size();
+    if (!list || list_cap < r.list.size() || !table || table_cap_words < r.table.size()) return -3; // the size query (the emitter's code for a buffer that is too small)
+    std::copy(r.list.begin(), r.list.end(), list);
+    std::copy(r.table.begin(), r.table.end(), table);
+    remember(p, n_regions, r);
+    return FRI_HIP_OK;
+}
+
+int fri_hip_merge_tiles_regions_dev(fri_hip_plan_tiled *p, const uint8_t *d_tiles, uint32_t n_list, uint32_t n_regions, const uint32_t *d_table, uint8_t *d_out, void *stream) {
+    if (!p || !d_tiles || !d_table || !d_out || !n_list || n_list > p->n_tiles() || !n_regions || n_regions > 65535u) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    if (int rc = need_device(p)) return rc;
+    if (p->planned.n_regions != n_regions || p->planned.n_list != n_list) {
+        p->ctx->last_error = "fri_hip_merge_tiles_regions_dev: d_table must hold the table fri_hip_plan_tiled_regions last wrote on this plan (n_regions or n_list differ)";
+        return FRI_HIP_ERR_INVALID_ARGUMENT;
+    }
+    HIP_TRY(p->ctx, launch_merge_tiles_regions(d_tiles, p->channels, p->grid.tile_w, p->grid.tile_h, p->grid.nx, n_regions, p->planned.n_groups, d_table, d_out, (hipStream_t)stream));
+    return FRI_HIP_OK;
+}
+
+int fri_hip_decode_regions_tiled_dev(fri_hip_plan_tiled *p, const int32_t *d_coefs, const int32_t qmatrix[32], uint32_t n_regions, const uint32_t *regions, uint8_t *d_out,
+                                     void *stream) {
+    RegionsPlan r;
+    if (!p || !d_coefs || !qmatrix || !d_out || !plan_regions(p, n_regions, regions, r)) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    if (int rc = need_device(p)) return rc;
+    fri_hip_ctx *c = p->ctx;
+    const hipStream_t s = (hipStream_t)stream;
+    QMatrix q;
+    if (int rc = check_q(qmatrix, q)) return rc;
+    if (int rc = refuse_capture(p->tile.get(), s, "fri_hip_decode_regions_tiled_dev grows the plan's tile and table buffers: it cannot be captured into a HIP graph")) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t n = r.list.size(); // the listed tiles: the buffer grows to the regions' tiles, never to the image's
+    int rc;
+    if ((rc = grow(c, p->tiles, n * p->tile_bytes())) || (rc = grow(c, p->region_table, r.table.size()))) return rc;
+    // the table goes up in stream order; the wait is for the source, which is this call's own memory (a few KiB, ahead of everything this call enqueues)
+    HIP_TRY(c, hipMemcpyAsync(p->region_table, r.table.data(), r.table.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    remember(p, n_regions, r);
+    if ((rc = fri_hip_inverse_transform_batch_dev(p->tile.get(), (uint32_t)n, d_coefs, fri_hip_plan_coef_count(p->tile.get()), qmatrix, p->tiles, p->tile_bytes(), stream))) return rc;
+    HIP_TRY(c, launch_merge_tiles_regions(p->tiles, p->channels, p->grid.tile_w, p->grid.tile_h, p->grid.nx, n_regions, r.n_groups, p->region_table, d_out, s));
+    return FRI_HIP_OK;
+}
+
+int fri_hip_decode_regions_tiled(fri_hip_plan_tiled *p, const int32_t *coefs, const int32_t qmatrix[32], uint32_t n_regions, const uint32_t *regions, uint8_t *pixels) {
+    RegionsPlan r;
+    if (!p || !coefs || !qmatrix || !pixels || !plan_regions(p, n_regions, regions, r)) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    if (int rc = need_device(p)) return rc;
+    fri_hip_ctx *c = p->ctx;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t n = r.list.size(), image = fri_hip_plan_coef_count(p->tile.get());
+    int rc;
+    if ((rc = grow(c, p->coefs, n * image)) || (rc = grow(c, p->regions_out, (size_t)r.total))) return rc;
+    HIP_TRY(c, hipMemcpy(p->coefs, coefs, n * image * sizeof(int32_t), hipMemcpyHostToDevice));
+    if ((rc = fri_hip_decode_regions_tiled_dev(p, p->coefs, qmatrix, n_regions, regions, p->regions_out, nullptr))) return rc;
+    HIP_TRY(c, hipMemcpy(pixels, p->regions_out, (size_t)r.total, hipMemcpyDeviceToHost));
+    return FRI_HIP_OK;
+}
+
+int fri_hip_decode_regions_tiled_coded(fri_hip_plan_tiled *p, uint32_t n_regions, const uint32_t *regions, const uint32_t *words, size_t word_stride, const uint32_t *n_words,
+                                       const uint32_t *models, const uint16_t *off_values, const float *value_params, const float *width_params, const int32_t qmatrix[32],
+                                       uint8_t *pixels, uint32_t *status) {
+    RegionsPlan r;
+    const CodedPlanes in{words, word_stride, n_words, models, off_values, value_params, width_params};
+    if (!p || !in.complete() || !qmatrix || !pixels || !status || !plan_regions(p, n_regions, regions, r)) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    if (int rc = need_device(p)) return rc;
+    if (!p->tile->d_stream_order) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    fri_hip_ctx *c = p->ctx;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t image = fri_hip_plan_coef_count(p->tile.get()), n = r.list.size(), planes = n * p->channels;
+    if (!decode_counts_ok((uint32_t)planes)) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    int rc;
+    if ((rc = grow(c, p->coefs, n * image)) || (rc = grow(c, p->regions_out, (size_t)r.total))) return rc;
+    CodedOnDevice d;
+    if ((rc = upload_coded(p, in, planes, p->rans_words, d)) || (rc = decode_coded_batch(p->tile.get(), d, 0, planes, p->coefs, image / p->channels))) return rc;
+    if ((rc = read_back_decode_status(c, d, status))) {
+        for (size_t k = 0; k < planes && rc == FRI_HIP_ERR_INVALID_ARGUMENT; k++)
+            if (status[4 * k]) { // the first refused plane, by its tile's index in the file's grid
+                c->last_error = "fri_hip_decode_regions_tiled_coded: tile " + std::to_string(r.list[k / p->channels]) + ": channel " + std::to_string(k % p->channels) +
+                                ": the device decoder refused the plane (status " + std::to_string(status[4 * k]) + ")";
+                break;
+            }
+        return rc;
+    }
+    if ((rc = fri_hip_decode_regions_tiled_dev(p, p->coefs, qmatrix, n_regions, regions, p->regions_out, nullptr))) return rc;
+    HIP_TRY(c, hipMemcpy(pixels, p->regions_out, (size_t)r.total, hipMemcpyDeviceToHost));
     return FRI_HIP_OK;
 }
 

@@ -196,6 +196,12 @@ hipError_t launch_merge_tiles(const uint8_t *tiles, uint32_t width, uint32_t hei
 // region must lie in the width x height image (hipErrorInvalidValue otherwise).
 hipError_t launch_merge_tiles_region(const uint8_t *tiles, uint32_t width, uint32_t height, uint32_t channels, uint32_t tile_w, uint32_t tile_h, uint32_t x, uint32_t y, uint32_t w,
                                      uint32_t h, uint8_t *region, hipStream_t stream);
+// K15 (k15_regions.hip): the merge for several regions in one launch (include/fri_emit.h, "Several regions"). tiles: the tile-list raster [T][tile_h][tile_w][C];
+// table: the region table on the device - rows [n_regions + 1][8], then slot[ny nx] - as the host wrote it, n_groups its row R's word 6; out: the packed region
+// rasters, any alignment. n_groups workgroups of 256 lanes; no atomics, no LDS, only enqueues. hipErrorInvalidValue for a NULL pointer, a zero size, channels other
+// than 1 or 3, n_regions = 0 or > 65535, n_groups = 0 or >= 2^31. The table's contents are not checked: they are read on the device.
+hipError_t launch_merge_tiles_regions(const uint8_t *tiles, uint32_t channels, uint32_t tile_w, uint32_t tile_h, uint32_t nx, uint32_t n_regions, uint32_t n_groups,
+                                      const uint32_t *table, uint8_t *out, hipStream_t stream);
 // Region split (include/fri_emit.h, "Region update"): the tile raster of the sub-grid the region x, y, w, h touches, [nj ni][tile_h][tile_w][C] - the rows
 // {(j0 + b) nx + i0 + a} of the split - from a pitched rectangle of the image: `src` points at image pixel (src_y, src_x), rows src_pitch bytes apart, src_w x src_h
 // pixels. hipErrorInvalidValue for a region that leaves the image, a rectangle that leaves it or does not contain the covered rectangle, src_pitch < src_w C.

@@ -58,6 +58,9 @@ def load_library():
         L.fri_tiled_region_tiles.argtypes = [u32, u32, u32, u32, u32, u32, u32, u32, vp]
         L.fri_tiled_decode_region.argtypes = [vp, sz, u32, u32, u32, u32, u32, vp, vp, vp, sz, C.c_char_p, sz]
         L.fri_tiled_update_from_streams.argtypes = [vp, sz, u32, u32, u32, u32, u32, vp, C.c_uint64, vp, vp, vp, u32, vp, vp, sz, vp, C.c_char_p, sz]
+        L.fri_tiled_regions_tiles.argtypes = [u32, u32, u32, u32, u32, vp, vp, sz, vp]
+        L.fri_tiled_decode_tiles.argtypes = [vp, sz, u32, vp, sz, vp, vp, sz, C.c_char_p, sz]
+        L.fri_tiled_parse_coded_tiles.argtypes = [vp, sz, vp, sz, vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp, vp, vp, C.c_char_p, sz]
         _lib = L
     return _lib
 
@@ -490,6 +493,96 @@ def tiled_decode_region(frv, x, y, w, h, threads=0):
     if rc != 0:
         raise EmitError(err.value.decode() or f"fri_tiled_decode_region: {rc}")
     return ti, tuple(int(v) for v in tiles), coefs
+
+
+def _regions(regions):
+    """regions as the contiguous uint32 [R][4] array the C side reads; EmitError for anything that is not R >= 1 rows of (x, y, w, h) in 32 bits"""
+    try:
+        wide = np.asarray(regions, np.int64).reshape(-1, 4)
+    except (ValueError, TypeError, OverflowError) as e:
+        raise EmitError(f"regions must be rows of (x, y, w, h): {e}") from None
+    if wide.shape[0] == 0 or (wide < 0).any() or (wide > 0xFFFFFFFF).any():
+        raise EmitError("regions must be one or more rows of (x, y, w, h), each in 32 bits")
+    return np.ascontiguousarray(wide, np.uint32)
+
+
+def tiled_regions_tiles(width, height, tile_w, tile_h, regions):
+    """fri_tiled_regions_tiles: the tile list of `regions` [(x, y, w, h), ...] - uint32 [T], the strictly ascending file-grid indices t = j nx + i of the tiles at
+    least one region touches, each once. EmitError for no regions, a zero size or a region that leaves the image."""
+    rg = _regions(regions)
+    n = C.c_size_t(0)
+    L = load_library()
+    rc = L.fri_tiled_regions_tiles(width, height, tile_w, tile_h, rg.shape[0], _p(rg), None, 0, C.addressof(n))
+    if rc != -3:
+        raise EmitError(f"fri_tiled_regions_tiles: {rc}")
+    out = np.zeros(n.value, np.uint32)
+    rc = L.fri_tiled_regions_tiles(width, height, tile_w, tile_h, rg.shape[0], _p(rg), _p(out), out.size, C.addressof(n))
+    if rc != 0:
+        raise EmitError(f"fri_tiled_regions_tiles: {rc}")
+    return out
+
+
+def tiled_decode_tiles(frv, tiles, threads=0):
+    """fri_tiled_decode_tiles: (TiledInfo, coefs int32 [T][C][F][512]) for the strictly ascending tile list `tiles` (file-grid indices), in list order - what
+    PlanTiled.decode_regions_tiled takes. The file is checked as tiled_decode checks it; only the listed tiles are decoded, and damage inside the body of an
+    unlisted tile is not looked at. A tiled 4:2:0 file: coefs is flat and in plane order with n = T. An EmitError carries the C return value as .code."""
+    data = np.frombuffer(frv, np.uint8)
+    tl = np.ascontiguousarray(tiles, np.uint32).reshape(-1)
+    info = np.zeros(8, np.uint32)
+    err = C.create_string_buffer(256)
+    L = load_library()
+
+    def fail(rc):
+        e = EmitError(err.value.decode() or f"fri_tiled_decode_tiles: {rc}")
+        e.code = rc
+        return e
+
+    rc = L.fri_tiled_decode_tiles(_p(data), data.size, threads, _p(tl), tl.size, _p(info), None, 0, err, 256)
+    if rc != -3:
+        raise fail(rc)
+    ti = _tiled_info(info)
+    coefs = _tiled_coefs(ti, tl.size)
+    rc = L.fri_tiled_decode_tiles(_p(data), data.size, threads, _p(tl), tl.size, _p(info), _p(coefs), coefs.size, err, 256)
+    if rc != 0:
+        raise fail(rc)
+    return ti, coefs
+
+
+def tiled_parse_coded_tiles(frv, tiles, word_stride=None):
+    """fri_tiled_parse_coded_tiles: tiled_parse_coded for the strictly ascending tile list `tiles` - the same tuple with P = T C planes in list order (plane order
+    with n = T for a tiled 4:2:0 file); only the listed payloads' markers are walked. What PlanTiled.decode_regions_coded takes. An EmitError carries the C return
+    value as .code."""
+    data = np.frombuffer(frv, np.uint8)
+    tl = np.ascontiguousarray(tiles, np.uint32).reshape(-1)
+    info = np.zeros(8, np.uint32)
+    err = C.create_string_buffer(256)
+    L = load_library()
+
+    def fail(rc):
+        e = EmitError(err.value.decode() or f"fri_tiled_parse_coded_tiles: {rc}")
+        e.code = rc
+        return e
+
+    head = (_p(data), data.size, _p(tl), tl.size, _p(info))
+    rc = L.fri_tiled_parse_coded_tiles(*head, 0, None, 0, None, None, None, None, None, err, 256)
+    if rc != -3:
+        raise fail(rc)
+    ti = _tiled_info(info)
+    planes = tl.size * ti[6]
+    nw = np.zeros(planes, np.uint32)
+    rc = L.fri_tiled_parse_coded_tiles(*head, planes, None, 0, _p(nw), None, None, None, None, err, 256)
+    if rc != 0:
+        raise fail(rc)
+    stride = max(int(nw.max()), 1) if word_stride is None else int(word_stride)
+    words = np.zeros((planes, stride), np.uint32)
+    models, off = np.zeros((planes, 10, 4), np.uint32), np.zeros((planes, 10, 1024), np.uint16)
+    vp, wp = np.zeros((planes, 3, 6), np.float32), np.zeros((planes, 3, 6), np.float32)
+    rc = L.fri_tiled_parse_coded_tiles(*head, planes, _p(words), stride, _p(nw), _p(models), _p(off), _p(vp), _p(wp), err, 256)
+    if rc != 0:
+        e = fail(rc)
+        e.n_words = nw
+        raise e
+    return ti, words, nw, models, off, vp, wp
 
 
 def tiled_update_from_streams(frv, x, y, w, h, streams, hist, value_params, width_params, rct=False, quality=0, ycbcr=False, threads=0, flags=0):

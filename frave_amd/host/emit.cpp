@@ -1318,8 +1318,31 @@ bool region_tiles(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t til
     return true;
 }
 
+bool regions_tiles(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, const Region *regions, size_t n_regions, std::vector<uint32_t> &list) {
+    list.clear();
+    if (!regions || !n_regions || !width || !height || !tile_w || !tile_h) return false;
+    const uint64_t nx = ((uint64_t)width + tile_w - 1) / tile_w, ny = ((uint64_t)height + tile_h - 1) / tile_h;
+    std::vector<uint8_t> touched(nx * ny, 0); // (nx ny < 2^32: both are at most the image's sides)
+    for (size_t r = 0; r < n_regions; r++) {
+        TileRange tr;
+        if (!region_tiles(width, height, tile_w, tile_h, regions[r], tr)) return false;
+        for (uint32_t b = 0; b < tr.nj; b++) std::fill_n(touched.begin() + ((uint64_t)tr.j0 + b) * nx + tr.i0, tr.ni, (uint8_t)1);
+    }
+    for (uint64_t t = 0; t < nx * ny; t++)
+        if (touched[t]) list.push_back((uint32_t)t);
+    return true;
+}
+
+// a tile list is strictly ascending, not empty and inside the grid
+static bool tile_list_ok(const TileList &l, uint64_t n_grid) {
+    if (!l.tiles || !l.n) return false;
+    for (size_t k = 0; k < l.n; k++)
+        if (l.tiles[k] >= n_grid || (k && l.tiles[k] <= l.tiles[k - 1])) return false;
+    return true;
+}
+
 std::string decode_tiled(const uint8_t *b, size_t len, unsigned threads, TiledInfo &info, int32_t *coefs, size_t coef_cap, bool &too_small, const Region *region,
-                         TileRange *range, int levels) {
+                         TileRange *range, int levels, const TileList *list) {
     too_small = false;
     std::vector<uint64_t> offset;
     std::string e = parse_tiled(b, len, info, offset);
@@ -1330,11 +1353,13 @@ std::string decode_tiled(const uint8_t *b, size_t len, unsigned threads, TiledIn
     TileRange tr{0, 0, info.nx, info.ny}; // without a region: the whole grid
     if (region && !region_tiles(info.width, info.height, info.tile_w, info.tile_h, *region, tr)) return "invalid region";
     if (range) *range = tr;
+    if (list && !tile_list_ok(*list, (uint64_t)info.nx * info.ny)) return kBadTileList;
     fri::Geometry g; // one geometry and one symbol order for all tiles
     e = fri::build_geometry(info.tile_w, info.tile_h, info.s420 ? 1u : info.channels, fri::TilingParams{}, g);
     if (!e.empty()) return e;
-    const size_t F = g.centers.size(), plane = F << levels, n_tiles = (size_t)tr.ni * tr.nj; // (compact planes below levels = 9; 4:2:0 is whole planes only)
-    const auto file_tile = [&](size_t s) { return ((size_t)tr.j0 + s / tr.ni) * info.nx + tr.i0 + s % tr.ni; }; // sub-tile s of the range in the file's grid
+    const size_t F = g.centers.size(), plane = F << levels, n_tiles = list ? list->n : (size_t)tr.ni * tr.nj; // (compact planes below levels = 9; 4:2:0 is whole planes only)
+    // sub-tile s of the range, or entry s of the tile list, in the file's grid
+    const auto file_tile = [&](size_t s) { return list ? (size_t)list->tiles[s] : ((size_t)tr.j0 + s / tr.ni) * info.nx + tr.i0 + s % tr.ni; };
     info.n_cells = (uint32_t)F;
     std::vector<int32_t> centers(F * 2);
     for (size_t c = 0; c < F; c++) centers[2 * c] = g.centers[c].x, centers[2 * c + 1] = g.centers[c].y;
@@ -1388,11 +1413,12 @@ std::string decode_tiled(const uint8_t *b, size_t len, unsigned threads, TiledIn
 // The inverse of encode_tiled_from_coded / encode_tiled_from_coded420: nothing is decoded and no model is built, deserialize walks every payload's markers and the
 // parts are copied out in K11's layout. One thread: the work is a copy of the file.
 std::string parse_tiled_coded(const uint8_t *b, size_t len, TiledInfo &info, size_t plane_cap, bool &too_small, uint32_t *words, size_t word_stride, uint32_t *n_words,
-                              uint32_t *models, uint16_t *off_values, float *value_params, float *width_params) {
+                              uint32_t *models, uint16_t *off_values, float *value_params, float *width_params, const TileList *list) {
     too_small = false;
     std::vector<uint64_t> offset;
     std::string e = parse_tiled(b, len, info, offset);
     if (!e.empty()) return e;
+    if (list && !tile_list_ok(*list, (uint64_t)info.nx * info.ny)) return kBadTileList;
     { // the cells of the tile lattices, as decode_tiled reports them
         uint32_t cells = 0;
         uint64_t n_some = 0;
@@ -1405,11 +1431,12 @@ std::string parse_tiled_coded(const uint8_t *b, size_t len, TiledInfo &info, siz
             info.n_cells_chroma = cells;
         }
     }
-    const size_t n = (size_t)info.nx * info.ny, planes = n * info.channels;
+    const size_t n = list ? list->n : (size_t)info.nx * info.ny, planes = n * info.channels; // the tiles walked: the list's, or the grid's
     if (!n_words || plane_cap < planes) return too_small = true, "";
     const bool fill = words != nullptr;
     std::string over; // the first plane longer than word_stride: n_words is completed before it is reported
-    for (size_t t = 0; t < n; t++) {
+    for (size_t s = 0; s < n; s++) {
+        const size_t t = list ? (size_t)list->tiles[s] : s; // the tile in the file's grid; its planes are those of entry s
         const auto tile_error = [&](const std::string &why) { return "tile " + std::to_string(t) + ": " + why; };
         ParsedImage img;
         const std::string de = deserialize(std::vector<uint8_t>(b + offset[t], b + offset[t + 1]), img, false);
@@ -1419,7 +1446,7 @@ std::string parse_tiled_coded(const uint8_t *b, size_t len, TiledInfo &info, siz
             if (c.n_contexts != (uint32_t)kContexts) return tile_error("Malformed image bytes"); // fewer than ten EHD segments (decode_tiled's check)
         for (uint32_t ch = 0; ch < info.channels; ch++) {
             // plane order: tile by tile and channel by channel, or - 4:2:0 - the luma planes, then Cb and Cr tile by tile
-            const size_t k = info.s420 ? (ch == 0 ? t : n + 2 * t + ch - 1) : t * info.channels + ch;
+            const size_t k = info.s420 ? (ch == 0 ? s : n + 2 * s + ch - 1) : s * info.channels + ch;
             const ChannelStream &c = img.channels[ch];
             const size_t nw = c.data.size() / 4; // (a tail of one to three bytes is not a word: RansDecoderMulti)
             if (nw > 0xFFFFFFFFull) return tile_error("channel " + std::to_string(ch) + ": more than 2^32 words");

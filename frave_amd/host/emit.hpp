@@ -251,6 +251,16 @@ struct TileRange {
 };
 // false for a zero size or a region that leaves the width x height image (compared in 64 bits)
 bool region_tiles(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, const Region &r, TileRange &out);
+// Several regions (include/fri_emit.h, "Several regions"): the strictly ascending list of the file-grid tiles t = j nx + i that at least one region touches, each
+// once. false for no regions, a zero size or a region region_tiles refuses.
+bool regions_tiles(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, const Region *regions, size_t n_regions, std::vector<uint32_t> &list);
+// A tile list for decode_tiled and parse_tiled_coded: n file-grid tile indices, strictly ascending; kBadTileList for an empty, unsorted or repeating list and for
+// an index outside the grid.
+struct TileList {
+    const uint32_t *tiles = nullptr;
+    size_t n = 0;
+};
+inline constexpr const char *kBadTileList = "invalid tile list";
 // Region update (include/fri_emit.h, "Region update"): the file `frv` with the payloads of the tiles the region touches replaced. streams [nj ni][channels][n_symbols],
 // hist [nj ni][channels][10][1024], value_params / width_params [nj ni][channels][3][6] in the sub-grid's order - what fri_hip_encode_region_tiled_symbols returns;
 // those tiles are coded on `threads` workers through the per-tile path of encode_tiled_from_streams, every other payload is copied and not looked into, the header
@@ -274,7 +284,8 @@ std::string update_tiled_from_streams(const uint8_t *frv, size_t len, const Regi
 inline constexpr const char *kNoLevels420 =
     "a tiled 4:2:0 file has no level-limited decode (its chroma lattice is a level pair of its own): decode it whole with fri_tiled_decode";
 std::string decode_tiled(const uint8_t *frv, size_t len, unsigned threads, TiledInfo &info, int32_t *coefs, size_t coef_cap, bool &too_small, const Region *region = nullptr,
-                         TileRange *range = nullptr, int levels = -1 /* 0..9: compact planes [..][channels][F][2^levels], see decode_channel; "invalid argument" above 9 and for a tiled 4:2:0 file, with the reason */);
+                         TileRange *range = nullptr, int levels = -1 /* 0..9: compact planes [..][channels][F][2^levels], see decode_channel; "invalid argument" above 9 and for a tiled 4:2:0 file, with the reason */,
+                         const TileList *list = nullptr /* the tiles to decode, in list order, in the place of a region's sub-grid: coefs [list->n][channels][F][512], or plane order with n = list->n */);
 // A `frit` file back to the coded planes it was written from (encode_tiled_from_coded, encode_tiled_from_coded420; the device decoder K13 reads them): per plane, in
 // the plane order the header defines, words [planes][word_stride] and n_words [planes] (the bytes between DAT and EOC as little-endian words, len / 4 rounded down),
 // models [planes][10][4] = {max_freq_bits as the file carries it, n_off, 0, 0}, off_values [planes][10][1024] (a context's first n_off, in file order) and
@@ -282,7 +293,8 @@ std::string decode_tiled(const uint8_t *frv, size_t len, unsigned threads, Tiled
 // n_tiles x channels entries - `info` is filled, nothing else. words == NULL: only info and n_words. A plane longer than word_stride is the error, naming the
 // plane, with n_words complete.
 std::string parse_tiled_coded(const uint8_t *frv, size_t len, TiledInfo &info, size_t plane_cap, bool &too_small, uint32_t *words, size_t word_stride, uint32_t *n_words,
-                              uint32_t *models, uint16_t *off_values, float *value_params, float *width_params);
+                              uint32_t *models, uint16_t *off_values, float *value_params, float *width_params,
+                              const TileList *list = nullptr /* only the listed tiles' markers are walked: planes = list->n x channels, in list order */);
 
 } // namespace emit
 } // namespace libfri

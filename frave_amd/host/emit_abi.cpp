@@ -384,6 +384,46 @@ int fri_tiled_decode_region(const uint8_t *frv, size_t len, uint32_t threads, ui
     return too_small ? -3 : 0;
 }
 
+int fri_tiled_regions_tiles(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t n_regions, const uint32_t *regions, uint32_t *list, size_t cap,
+                            size_t *n_list) {
+    if (!regions || !n_regions || !n_list) return -1;
+    std::vector<Region> rs(n_regions);
+    for (uint32_t r = 0; r < n_regions; r++) rs[r] = Region{regions[4 * r], regions[4 * r + 1], regions[4 * r + 2], regions[4 * r + 3]};
+    std::vector<uint32_t> tiles;
+    if (!regions_tiles(width, height, tile_w, tile_h, rs.data(), rs.size(), tiles)) return -1;
+    *n_list = tiles.size();
+    if (!list || cap < tiles.size()) return -3;
+    std::copy(tiles.begin(), tiles.end(), list);
+    return 0;
+}
+
+int fri_tiled_decode_tiles(const uint8_t *frv, size_t len, uint32_t threads, const uint32_t *list, size_t n_list, uint32_t info[8], int32_t *coefs, size_t coef_cap, char *err,
+                           size_t err_cap) {
+    if (!frv || !info || !list || !n_list) return fail(err, err_cap, "invalid argument");
+    TiledInfo t;
+    const TileList tiles{list, n_list};
+    bool too_small = false;
+    const std::string e = decode_tiled(frv, len, threads, t, coefs, coef_cap, too_small, nullptr, nullptr, -1, &tiles);
+    if (e == kBadTileList) return fail(err, err_cap, e);
+    if (!e.empty()) return fail(err, err_cap, e, -2);
+    fill_tiled_info(t, info);
+    return too_small ? -3 : 0;
+}
+
+int fri_tiled_parse_coded_tiles(const uint8_t *frv, size_t len, const uint32_t *list, size_t n_list, uint32_t info[8], uint64_t n_planes, uint32_t *words, uint64_t word_stride,
+                                uint32_t *n_words, uint32_t *models, uint16_t *off_values, float *value_params, float *width_params, char *err, size_t err_cap) {
+    if (!frv || !info || !list || !n_list || (words && (!n_words || !models || !off_values || !value_params || !width_params))) return fail(err, err_cap, "invalid argument");
+    TiledInfo t;
+    const TileList tiles{list, n_list};
+    bool too_small = false;
+    const std::string e =
+        parse_tiled_coded(frv, len, t, (size_t)n_planes, too_small, words, (size_t)word_stride, n_words, models, off_values, value_params, width_params, &tiles);
+    if (e == kBadTileList) return fail(err, err_cap, e);
+    if (!e.empty()) return fail(err, err_cap, e, -2);
+    fill_tiled_info(t, info);
+    return too_small ? -3 : 0;
+}
+
 int fri_tiled_update_from_streams(const uint8_t *frv, size_t len, uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint32_t channels_arg, const uint16_t *streams,
                                   uint64_t n_symbols, const uint32_t *hist, const float *value_params, const float *width_params, uint32_t threads, uint32_t tiles[4],
                                   uint8_t *out, size_t cap, size_t *out_len, char *err, size_t err_cap) {

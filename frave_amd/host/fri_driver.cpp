@@ -36,6 +36,12 @@
 //                                                            --region, on a `frif` file and on a tiled 4:2:0 file, naming what to do instead
 //                                                            --region X,Y,W,H: only that rectangle of the image (FRIDecoder::decode_region) - of a `frit` file only
 //                                                            the tiles it touches are decoded; a `frif` file is decoded whole and cropped; no untiled 4:2:0 file and no alpha file
+//   fri_driver decode-regions <in.frv> <out_prefix> --region X,Y,W,H [--region X,Y,W,H ...] [--device-rans]   several rectangles of a `frit` file in one call
+//                                                            (FRIDecoder::decode_regions: every tile a region touches is entropy-decoded once, one inverse launch, one
+//                                                            merge launch, K15); writes out_prefix.K.ppm (.pgm for one plane), K = 0, 1, ... in the order given. Regions
+//                                                            may overlap and repeat. --device-rans: the touched tiles are entropy-decoded on the device too (K13).
+//                                                            Refused with nothing written, naming what to use instead: a `frif` file, a tiled 4:2:0 file, a region that
+//                                                            is empty or leaves the image, no --region
 //   fri_driver update-file <in.frv> <new.pgm|.ppm|.bmp> <out.frv> --region X,Y,W,H   the tiles of the `frit` file in.frv that the rectangle touches are coded anew from
 //                                                            the image, which has the file's size and channels; every other tile's bytes are copied
 //                                                            (libfri::update_bytes_tiled: fri_hip_encode_region_tiled_symbols + fri_tiled_update_from_streams). No mode
@@ -778,6 +784,59 @@ int main(int argc, char **argv) {
         if (sub420) return encode_image_420_to_file(img, fw, fh, file_opts, argv[3]); // (the --ycbcr checks above hold: an RGB image, a lossy target, no --rct)
         return encode_image_to_file(std::move(img), fw, fh, fc, file_opts, argv[3]);
     }
+    if (argc >= 2 && std::string(argv[1]) == "decode-regions") {
+        const char *usage = "decode-regions <in.frv> <out_prefix> --region X,Y,W,H [--region X,Y,W,H ...] [--device-rans]";
+        if (argc < 4) {
+            std::fprintf(stderr, "%s\n", usage);
+            return 2;
+        }
+        std::vector<libfri::emit::Region> regions;
+        libfri::EncoderOpts dec_opts;
+        for (int i = 4; i < argc; i++) {
+            char tail = 0;
+            unsigned rx = 0, ry = 0, rw = 0, rh = 0;
+            if (std::string(argv[i]) == "--device-rans") dec_opts.device_rans = true;
+            else if (std::string(argv[i]) == "--region" && i + 1 < argc && std::sscanf(argv[i + 1], "%u,%u,%u,%u%c", &rx, &ry, &rw, &rh, &tail) == 4) regions.push_back({rx, ry, rw, rh}), i++;
+            else {
+                std::fprintf(stderr, "decode-regions: unknown or incomplete option %s (%s)\n", argv[i], usage);
+                return 2;
+            }
+        }
+        if (regions.empty()) {
+            std::fprintf(stderr, "decode-regions: no --region given (%s); decode-file decodes the whole image\n", usage);
+            return 2;
+        }
+        std::vector<uint8_t> bytes;
+        if (FILE *f = std::fopen(argv[2], "rb")) {
+            uint8_t buf[1 << 16];
+            for (size_t n; (n = std::fread(buf, 1, sizeof buf, f)) > 0;) bytes.insert(bytes.end(), buf, buf + n);
+            std::fclose(f);
+        } else {
+            std::fprintf(stderr, "cannot open %s\n", argv[2]);
+            return 1;
+        }
+        auto out = libfri::FRIDecoder().decode_regions(bytes, regions, dec_opts); // (every refusal comes before anything is written)
+        if (!out.ok) {
+            std::fprintf(stderr, "%s\n", out.error.c_str());
+            return 1;
+        }
+        for (size_t k = 0; k < out.value.size(); k++) {
+            const libfri::RasterImage &img = out.value[k];
+            const uint32_t ch = libfri::num_channels(img.metadata.colorspace);
+            const std::string name = std::string(argv[3]) + "." + std::to_string(k) + (ch == 1 ? ".pgm" : ".ppm");
+            FILE *f = std::fopen(name.c_str(), "wb");
+            if (!f) {
+                std::fprintf(stderr, "cannot write %s\n", name.c_str());
+                return 1;
+            }
+            std::fprintf(f, "%s\n%u %u\n255\n", ch == 1 ? "P5" : "P6", img.metadata.width, img.metadata.height);
+            std::fwrite(img.data.data(), 1, img.data.size(), f);
+            std::fclose(f);
+            std::printf("%s: %ux%ux%u decoded\n", name.c_str(), img.metadata.width, img.metadata.height, ch);
+        }
+        if (dec_opts.device_rans) std::printf("rANS decoder on the device (K13) over the regions' tiles\n");
+        return 0;
+    }
     if (argc >= 4 && std::string(argv[1]) == "decode-file") {
         std::vector<uint8_t> bytes;
         if (FILE *f = std::fopen(argv[2], "rb")) {
@@ -852,7 +911,7 @@ int main(int argc, char **argv) {
         return 0;
     }
     if (argc < 5) {
-        std::fprintf(stderr, "usage: %s roundtrip|encode|batch|batch-frv <width> <height> <channels> [n_images | out.frv]\n       %s encode-file <in.pgm|in.ppm|in.bmp|in.pam> <out.frv> [--rct | [--ycbcr | --420] (--quality Q | --psnr DB | --ssim S | --size BYTES | --bpp B)] [--clean-alpha] [--tile-size T [--device-rans]]\n       %s encode-file <in.ppm|in.bmp> <out.frv> --tile-size-420 T (--quality Q | --target psnr=DB|ssim=S|size=BYTES|bpp=B) [--device-rans]   (tiled 4:2:0; --tile-size T --420 stays refused: the option of its own is this one)\n       %s decode-file <in.frv> <out.pgm|out.ppm|out.bmp|out.pam> [--region X,Y,W,H | --device-rans | --preview M [--device-rans]]\n       %s update-file <in.frv> <new.pgm|new.ppm|new.bmp> <out.frv> --region X,Y,W,H\n", argv[0], argv[0], argv[0], argv[0], argv[0]);
+        std::fprintf(stderr, "usage: %s roundtrip|encode|batch|batch-frv <width> <height> <channels> [n_images | out.frv]\n       %s encode-file <in.pgm|in.ppm|in.bmp|in.pam> <out.frv> [--rct | [--ycbcr | --420] (--quality Q | --psnr DB | --ssim S | --size BYTES | --bpp B)] [--clean-alpha] [--tile-size T [--device-rans]]\n       %s encode-file <in.ppm|in.bmp> <out.frv> --tile-size-420 T (--quality Q | --target psnr=DB|ssim=S|size=BYTES|bpp=B) [--device-rans]   (tiled 4:2:0; --tile-size T --420 stays refused: the option of its own is this one)\n       %s decode-file <in.frv> <out.pgm|out.ppm|out.bmp|out.pam> [--region X,Y,W,H | --device-rans | --preview M [--device-rans]]\n       %s decode-regions <in.frv> <out_prefix> --region X,Y,W,H [--region X,Y,W,H ...] [--device-rans]\n       %s update-file <in.frv> <new.pgm|new.ppm|new.bmp> <out.frv> --region X,Y,W,H\n", argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
         return 2;
     }
     const std::string cmd = argv[1];

@@ -648,6 +648,88 @@ Result<RasterImage> FRIDecoder::decode_region(const std::vector<uint8_t> &data, 
     return r;
 }
 
+Result<std::vector<RasterImage>> FRIDecoder::decode_regions(const std::vector<uint8_t> &data, const std::vector<emit::Region> &regions, const EncoderOpts &opts) {
+    Result<std::vector<RasterImage>> r;
+    auto fail = [&](const std::string &why) {
+        r.error = "Failed to decode: " + why;
+        return r;
+    };
+    if (data.size() >= 4 && std::memcmp(data.data(), "frif", 4) == 0)
+        return fail("an ordinary `frif` file has no tiles to choose from: decode it whole, or crop one rectangle with decode_region (decode-file --region)");
+    emit::TiledInfo ti;
+    std::vector<uint64_t> offset;
+    if (std::string e = emit::parse_tiled(data.data(), data.size(), ti, offset); !e.empty()) return fail(e);
+    if (ti.s420) return fail("several regions of a tiled 4:2:0 file are out of scope: decode one rectangle per call with decode_region (decode-file --region)");
+    if (regions.empty() || regions.size() > 65535) return fail("several regions: give 1 to 65535 regions");
+    std::vector<uint32_t> list, flat;
+    if (!emit::regions_tiles(ti.width, ti.height, ti.tile_w, ti.tile_h, regions.data(), regions.size(), list)) return fail("invalid region");
+    size_t total = 0;
+    for (const emit::Region &g : regions) flat.insert(flat.end(), {g.x, g.y, g.w, g.h}), total += (size_t)g.w * g.h * ti.channels;
+    const emit::TileList tiles{list.data(), list.size()};
+    const size_t planes = list.size() * ti.channels;
+    bool too_small = false;
+    // the host's part: the listed tiles' planes decoded on the workers, or - device_rans - their coded planes copied out
+    std::vector<int32_t> coefs;
+    std::vector<uint32_t> n_words, words, models, status;
+    std::vector<uint16_t> off;
+    std::vector<float> vp, wp;
+    size_t stride = 1;
+    if (opts.device_rans) {
+        n_words.resize(planes);
+        std::string e = emit::parse_tiled_coded(data.data(), data.size(), ti, planes, too_small, nullptr, 0, n_words.data(), nullptr, nullptr, nullptr, nullptr, &tiles);
+        if (!e.empty()) return fail(e);
+        stride = std::max<uint32_t>(1, *std::max_element(n_words.begin(), n_words.end()));
+        words.resize(planes * stride), models.resize(planes * 40), status.resize(planes * 4), off.resize(planes * 10 * 1024), vp.resize(planes * 18), wp.resize(planes * 18);
+        e = emit::parse_tiled_coded(data.data(), data.size(), ti, planes, too_small, words.data(), stride, n_words.data(), models.data(), off.data(), vp.data(), wp.data(), &tiles);
+        if (!e.empty()) return fail(e);
+    } else {
+        std::string e = emit::decode_tiled(data.data(), data.size(), 0, ti, nullptr, 0, too_small, nullptr, nullptr, -1, &tiles); // header, table, geometry
+        if (!e.empty()) return fail(e);
+        coefs.resize(planes * (size_t)ti.n_cells * FRI_HIP_CELL_SIZE);
+        e = emit::decode_tiled(data.data(), data.size(), 0, ti, coefs.data(), coefs.size(), too_small, nullptr, nullptr, -1, &tiles);
+        if (!e.empty() || too_small) return fail(e.empty() ? "coefficient array does not match the tile geometry" : e);
+    }
+    Device dev(opts.device);
+    if (!dev.ok()) return fail(dev.error());
+    fri_hip_plan_tiled *raw = nullptr;
+    if (const int rc = fri_hip_plan_tiled_create(dev.ctx(), ti.width, ti.height, ti.channels, ti.tile_w, ti.tile_h, FRI_HIP_TILED_ALLOW_HOLES, &raw); rc != FRI_HIP_OK) return fail(dev.describe(rc));
+    TiledPlan plan(raw);
+    fri_hip_plan *tile = fri_hip_plan_tiled_tile(raw);
+    if (fri_hip_plan_num_cells(tile) != ti.n_cells) return fail("coefficient array does not match the tile geometry");
+    if (opts.device_rans)
+        if (std::string e = set_plan_stream_order(tile, dev); !e.empty()) return fail(e);
+    if (std::string e = set_colour_transform(tile, ti.rct, dev, ti.ycbcr); !e.empty()) return fail(e);
+    std::array<int32_t, 32> qm = opts.quantization_matrix;
+    if (ti.quality && fri_hip_quality_matrix((int)ti.quality, qm.data()) != FRI_HIP_OK) return fail("invalid quality");
+    int rc = fri_hip_plan_set_dequantiser(tile, ti.quality ? FRI_HIP_DEQUANT_MIDPOINT : FRI_HIP_DEQUANT_REFERENCE);
+    std::vector<uint8_t> packed(total);
+    if (rc == FRI_HIP_OK)
+        rc = opts.device_rans ? fri_hip_decode_regions_tiled_coded(raw, (uint32_t)regions.size(), flat.data(), words.data(), stride, n_words.data(), models.data(), off.data(), vp.data(),
+                                                                   wp.data(), qm.data(), packed.data(), status.data())
+                              : fri_hip_decode_regions_tiled(raw, coefs.data(), qm.data(), (uint32_t)regions.size(), flat.data(), packed.data());
+    if (rc != FRI_HIP_OK) {
+        for (size_t k = 0; k < status.size() / 4; k++) // the first plane the device refused, as the host decoder words it: by its tile in the file's grid
+            if (status[4 * k]) {
+                const uint32_t bits = status[4 * k];
+                return fail("tile " + std::to_string(list[k / ti.channels]) + ": channel " + std::to_string(k % ti.channels) + ": " +
+                            (bits & FRI_HIP_DECODE_BAD_MODEL ? "Malformed image bytes" : bits & FRI_HIP_DECODE_BAD_SLOT ? "stream does not match the model" : "stream truncated") +
+                            " (symbol " + std::to_string(status[4 * k + 1]) + ")");
+            }
+        return fail(dev.describe(rc));
+    }
+    size_t at = 0;
+    for (const emit::Region &g : regions) {
+        RasterImage img;
+        img.metadata = ImageMetadata{g.h, g.w, ti.channels == 1 ? ColorSpace::Luma : ColorSpace::RGB};
+        const size_t bytes = (size_t)g.w * g.h * ti.channels;
+        img.data.assign(packed.begin() + at, packed.begin() + at + bytes);
+        at += bytes;
+        r.value.push_back(std::move(img));
+    }
+    r.ok = true;
+    return r;
+}
+
 Result<RasterImage> FRIDecoder::decode_preview(const std::vector<uint8_t> &data, uint32_t shift, const EncoderOpts &opts) {
     Result<RasterImage> r;
     if (shift > 4) {

@@ -84,6 +84,22 @@
  * pixel (y + ry, x + rx), which is pixel (y + ry - j tile_h, x + rx - i tile_w) of tile (j, i): no replicated pixel is ever copied. By definition the region
  * raster is the crop [y : y + h, x : x + w] of what fri_hip_decode_image_tiled returns for the same file.
  *
+ * Several regions (fri_tiled_regions_tiles, fri_tiled_decode_tiles, fri_tiled_parse_coded_tiles below; the device side is fri_hip_decode_regions_tiled and K15,
+ * include/fri_hip.h): the input is R >= 1 regions r = (x, y, w, h), each by the rules of "Region decode"; regions may overlap and may repeat. C is the channel count.
+ *   tile list         the strictly ascending list list[0..T) of the file-grid tile indices t = j nx + i that at least one region touches: the union of the
+ *                     regions' sub-grids, each tile once. slot(t) = k for list[k] = t.
+ *   tile-list arrays  everything per tile is in list order: coefficients [T][C][F][512], the tile raster [T][tile_h][tile_w][C], coded planes [T C].
+ *   packed output     region r is a raster [h_r][w_r][C] without a pitch; it sits at byte off_r = sum_{q<r} w_q h_q C of one buffer, and off_R is the total.
+ *   result            by definition region r is the crop [y : y + h, x : x + w] of what fri_hip_decode_image_tiled returns for the file. No replicated pixel is read.
+ *   region table      uint32 words that the host writes and the kernel reads. A group is 256 lanes, and a lane owns 16 bytes of one row of one region.
+ *                       groups_r = ceil(h_r ceil(w_r C / 16) / 256)
+ *                       rows r = 0..R-1 of 8 words: {x, y, w, h, off_r low, off_r high, first_group_r = sum_{q<r} groups_q, 0}
+ *                       row R: {0, 0, 0, 0, total low, total high, n_groups, 0}
+ *                       then slot[ny nx], with 0xFFFFFFFF for a tile that is not in the list
+ *                     The table is 8 (R + 1) + nx ny words long. Refused: R = 0, R > 65535 and n_groups >= 2^31.
+ * Out of scope: regions of tiled 4:2:0 files on the device (K12's region merge with a slot table is a follow-up; the host functions here return such a file's
+ * planes in plane order with n = T); preview of regions; several regions in region update; regions of `frif` files.
+ *
  * Region update (fri_tiled_update_from_streams below; the device side is fri_hip_encode_region_tiled_symbols, include/fri_hip.h): the write-side twin of region
  * decode. A tile's payload depends on that tile's pixels, the matrix and the mode and on nothing else, so a file F_A (tiled 4:4:4, C = 1 or 3, any mode), a raster
  * B [H][W][C] of the file's size and a region x, y, w, h (the rules above) define an updated file. The sub-grid {i0, j0, ni, nj} is the one above, unchanged.
@@ -99,7 +115,7 @@
  *   metadata           all tiles of a file carry one metadata word and an update keeps that true: the `channels` word given must produce tile 0's word,
  *                      otherwise the call is refused and nothing is written.
  * Out of scope: tiled 4:2:0 files (a region split of subsampled tiles, K12, is a follow-up; such files are re-encoded whole); the device rANS route for the
- * sub-grid (K11 loses with few planes); several regions per call; updating a file in place; changing a file's quality or mode.
+ * sub-grid (K11 loses with few planes); several regions in one update; updating a file in place; changing a file's quality or mode.
  *
  * Tiled 4:2:0 (fri_tiled_encode_from_streams420 and fri_tiled_encode_from_coded420 below; include/fri_hip.h, "Tiled 4:2:0 coding", has the device side): the `frit` container is unchanged and stays
  * at version 1. In a tiled 4:2:0 file every payload is a `frif` file of a tile_h x tile_w image with colour space YCbCr, metadata bits 1 and 2 set, and a quality of
@@ -265,6 +281,23 @@ int fri_tiled_region_tiles(uint32_t width, uint32_t height, uint32_t tile_w, uin
  * coef_cap (in elements) is too small. */
 int fri_tiled_decode_region(const uint8_t *frv, size_t len, uint32_t threads, uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint32_t info[8], uint32_t tiles[4],
                             int32_t *coefs, size_t coef_cap, char *err, size_t err_cap);
+/* The tile list of R regions ("Several regions" above): by that definition and nothing else. regions [n_regions][4] = {x, y, w, h}; list: capacity `cap` entries;
+ * *n_list = T. -1 for n_regions = 0, a NULL regions or n_list, or a region fri_tiled_region_tiles refuses; -3 with *n_list filled when list is NULL or cap < T. */
+int fri_tiled_regions_tiles(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t n_regions, const uint32_t *regions, uint32_t *list, size_t cap,
+                            size_t *n_list);
+/* fri_tiled_decode for a strictly ascending tile list: coefs [T][C][F][512] int32 in list order, T = n_list - what fri_hip_decode_regions_tiled takes. The header,
+ * the table and every payload's 16-byte header are checked as fri_tiled_decode_region checks them, and `info` is the same. Only the listed tiles are
+ * entropy-decoded, on the shared workers through the same per-tile path; the bytes are the same for every thread count and equal those tiles' planes of
+ * fri_tiled_decode. Damage inside the body of an unlisted payload is not seen. A tile's error names its index in the file's grid ("tile t: channel c: ..."). -1 for
+ * an empty, unsorted or repeating list and for an index >= nx ny ("invalid tile list"); -3 with `info` filled when coefs is NULL or coef_cap (in elements) is too
+ * small. A tiled 4:2:0 file comes back in plane order with n = T, as fri_tiled_decode_region returns it for a sub-grid. */
+int fri_tiled_decode_tiles(const uint8_t *frv, size_t len, uint32_t threads, const uint32_t *list, size_t n_list, uint32_t info[8], int32_t *coefs, size_t coef_cap, char *err,
+                           size_t err_cap);
+/* fri_tiled_parse_coded for a tile list (the rules of fri_tiled_decode_tiles, -1 included): P = T C planes in list order - plane order with n = T for a tiled 4:2:0
+ * file - and the markers of the listed payloads alone are walked. The arrays, the size queries and the error for a plane longer than word_stride are
+ * fri_tiled_parse_coded's; a tile's error names its index in the file's grid. What fri_hip_decode_regions_tiled_coded takes. */
+int fri_tiled_parse_coded_tiles(const uint8_t *frv, size_t len, const uint32_t *list, size_t n_list, uint32_t info[8], uint64_t n_planes, uint32_t *words, uint64_t word_stride,
+                                uint32_t *n_words, uint32_t *models, uint16_t *off_values, float *value_params, float *width_params, char *err, size_t err_cap);
 /* Region update ("Region update" above): the file `frv` with the payloads of the tiles the region touches coded anew. streams [nj ni][C][n_symbols] u16, hist
  * [nj ni][C][10][1024], value_params / width_params [nj ni][C][3][6] in the sub-grid's order: what fri_hip_encode_region_tiled_symbols returns. `channels` is what
  * fri_tiled_encode_from_streams takes (flags + quality, FRI_EMIT_EMPTY_OK always in force) and must produce the metadata word of tile 0. The touched tiles are

@@ -629,8 +629,8 @@ int fri_hip_decode_image_rgba(fri_hip_plan_rgba *p, const int32_t *coefs, const 
  * tile (j0 + b) nx + (i0 + a). The region raster is [h][w][C] without a pitch: pixel (ry, rx) is image pixel (y + ry, x + rx), which is pixel
  * (y + ry - j tile_h, x + rx - i tile_w) of tile (j, i); no replicated pixel is ever copied. By definition it is the crop [y : y + h, x : x + w] of what
  * fri_hip_decode_image_tiled returns for the same file. Only the touched tiles are entropy-decoded (fri_tiled_decode_region, include/fri_emit.h), inverted and
- * copied, and the plan's buffers grow to the region's size, never to the image's. Out of scope: regions of untiled 4:2:0 files and of alpha files, several regions
- * in one call; a region of a tiled 4:2:0 file is fri_hip_decode_region_tiled420 below. */
+ * copied, and the plan's buffers grow to the region's size, never to the image's. Out of scope: regions of untiled 4:2:0 files and of alpha files; a region
+ * of a tiled 4:2:0 file is fri_hip_decode_region_tiled420 below; several regions in one call are "Several regions" below. */
 #define FRI_HIP_TILED_ALLOW_HOLES 1u
 typedef struct fri_hip_plan_tiled fri_hip_plan_tiled;
 uint64_t fri_hip_plan_owned_pixels(const fri_hip_plan *plan);
@@ -673,6 +673,48 @@ int fri_hip_merge_tiles_region_dev(fri_hip_plan_tiled *p, const uint8_t *d_tiles
 int fri_hip_decode_region_tiled_dev(fri_hip_plan_tiled *p, const int32_t *d_coefs, const int32_t qmatrix[32], uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint8_t *d_region,
                                     void *stream);
 int fri_hip_decode_region_tiled(fri_hip_plan_tiled *p, const int32_t *coefs, const int32_t qmatrix[32], uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint8_t *pixels);
+/* Several regions (K15, k15_regions.hip): many rectangles of one file in one call. The input is R >= 1 regions r = (x, y, w, h), `regions` uint32 [R][4] in host
+ * memory, each by the rules of "Region decode" above; regions may overlap and may repeat. C is the channel count.
+ *   tile list         the strictly ascending list list[0..T) of the file-grid tile indices t = j nx + i that at least one region touches: the union of the
+ *                     regions' sub-grids, each tile once. slot(t) = k for list[k] = t.
+ *   tile-list arrays  everything per tile is in list order: coefficients [T][C][F][512], the tile raster [T][tile_h][tile_w][C], coded planes [T C].
+ *   packed output     region r is a raster [h_r][w_r][C] without a pitch; it sits at byte off_r = sum_{q<r} w_q h_q C of one buffer, and off_R is the total.
+ *   result            by definition region r is the crop [y : y + h, x : x + w] of what fri_hip_decode_image_tiled returns for the file. No replicated pixel is read.
+ *   region table      uint32 words that the host writes and the kernel reads. A group is 256 lanes, and a lane owns 16 bytes of one row of one region.
+ *                       groups_r = ceil(h_r ceil(w_r C / 16) / 256)
+ *                       rows r = 0..R-1 of 8 words: {x, y, w, h, off_r low, off_r high, first_group_r = sum_{q<r} groups_q, 0}
+ *                       row R: {0, 0, 0, 0, total low, total high, n_groups, 0}
+ *                       then slot[ny nx], with 0xFFFFFFFF for a tile that is not in the list
+ *                     The table is 8 (R + 1) + nx ny words long. Refused: R = 0, R > 65535 and n_groups >= 2^31.
+ * fri_hip_plan_tiled_regions: host only, works on host-only plans. Writes the tile list (*n_list = T) and the region table. Returns -3 - here, as in
+ * include/fri_emit.h, "the buffer is too small", with *n_list filled and nothing else written - when list is NULL, list_cap < T, table is NULL or table_cap_words
+ * < 8 (R + 1) + nx ny. The plan remembers R, T and n_groups of the last table it wrote: the kernel's launch has n_groups workgroups and the host alone knows that.
+ * fri_hip_merge_tiles_regions_dev (K15's merge_tiles_regions_kernel alone): d_tiles, the tile-list raster [T][tile_h][tile_w][C] -> d_out, the packed region rasters.
+ * One launch of n_groups workgroups of 256 lanes; a workgroup belongs to exactly one region, which it finds by a search over first_group; every output byte is
+ * written once; no atomics, no LDS; only enqueues on `stream`, can be captured into a graph; any pointer alignment of d_tiles and d_out. d_table must be, in device
+ * memory, the table fri_hip_plan_tiled_regions LAST wrote on this plan, n_list and n_regions the T and R of that call: the entry checks the pointers, n_list <= nx ny
+ * and that R and T are the remembered ones, and cannot check the words themselves - a table from anywhere else makes the kernel read and write out of bounds.
+ * fri_hip_decode_regions_tiled_dev: d_coefs [T][C][F][512] int32 in list order (what fri_tiled_decode_tiles returns, in device memory) -> d_out. Builds the table,
+ * grows the plan's tile buffer to T tiles - never to the image's size - and a plan-owned table buffer, uploads the table on `stream` (and waits for that small
+ * copy), runs fri_hip_inverse_transform_batch_dev on the inner plan with n_images = T (`qmatrix` and the colour transform and dequantiser set on that plan), then
+ * K15, all on `stream`. A capturing stream is refused (FRI_HIP_ERR_INVALID_ARGUMENT) before anything is enqueued or allocated.
+ * fri_hip_decode_regions_tiled: the host form - coefs and the packed rasters `pixels` (off_R bytes) are host memory. Synchronous.
+ * fri_hip_decode_regions_tiled_coded: the coded planes of the tile list go up (what fri_tiled_parse_coded_tiles returns: the layouts of
+ * fri_hip_decode_image_tiled_coded with P = T C planes in list order), K13 (fri_hip_decode_planes_dev) runs over the T C planes, then the inverse kernel, then K15;
+ * the packed rasters come back. status uint32 [T C][4] goes to the caller; a plane the decoder refuses makes the call FRI_HIP_ERR_INVALID_ARGUMENT with the status
+ * filled, nothing decoded further, and fri_hip_last_hip_error naming the first such plane by its tile's index in the file's grid ("tile t: channel c: ..."). The inner
+ * plan needs its stream order. Synchronous.
+ * All: FRI_HIP_ERR_INVALID_ARGUMENT for a NULL pointer, a bad region and a bad R; FRI_HIP_ERR_NO_DEVICE on a host-only plan for everything that computes.
+ * Out of scope: regions of tiled 4:2:0 files on the device (K12's region merge with a slot table); preview of regions; several regions in region update. */
+int fri_hip_plan_tiled_regions(fri_hip_plan_tiled *p, uint32_t n_regions, const uint32_t *regions, uint32_t *list, size_t list_cap, size_t *n_list, uint32_t *table,
+                               size_t table_cap_words);
+int fri_hip_merge_tiles_regions_dev(fri_hip_plan_tiled *p, const uint8_t *d_tiles, uint32_t n_list, uint32_t n_regions, const uint32_t *d_table, uint8_t *d_out, void *stream);
+int fri_hip_decode_regions_tiled_dev(fri_hip_plan_tiled *p, const int32_t *d_coefs, const int32_t qmatrix[32], uint32_t n_regions, const uint32_t *regions, uint8_t *d_out,
+                                     void *stream);
+int fri_hip_decode_regions_tiled(fri_hip_plan_tiled *p, const int32_t *coefs, const int32_t qmatrix[32], uint32_t n_regions, const uint32_t *regions, uint8_t *pixels);
+int fri_hip_decode_regions_tiled_coded(fri_hip_plan_tiled *p, uint32_t n_regions, const uint32_t *regions, const uint32_t *words, size_t word_stride, const uint32_t *n_words,
+                                       const uint32_t *models, const uint16_t *off_values, const float *value_params, const float *width_params, const int32_t qmatrix[32],
+                                       uint8_t *pixels, uint32_t *status);
 /* Region update: the write-side twin of region decode - only the tiles a rectangle touches are split and coded, fri_tiled_update_from_streams (include/fri_emit.h)
  * copies every other payload of the file. A tile's payload depends on that tile's pixels, the matrix and the mode and on nothing else, so this is exact. The
  * region x, y, w, h and its sub-grid {i0, j0, ni, nj} are those of region decode, unchanged; sub-tile s = b ni + a is tile (j0 + b) nx + (i0 + a).
@@ -698,7 +740,7 @@ int fri_hip_decode_region_tiled(fri_hip_plan_tiled *p, const int32_t *coefs, con
  * into a plan-owned buffer that grows to cw ch C. The fit is on; synchronous; everything is read back in the sub-grid's order, laid out as
  * fri_hip_encode_image_tiled_symbols lays it out: what fri_tiled_update_from_streams takes. FRI_HIP_ERR_OUT_OF_RANGE as in fri_hip_encode_image.
  * Out of scope: tiled 4:2:0 plans (a region split of subsampled tiles, K12, is a follow-up); the device rANS route for the sub-grid (K11 loses with few planes,
- * profiles/rans_time.txt); several regions per call; updating a file in place; changing a file's quality or mode. */
+ * profiles/rans_time.txt); several regions in one update; updating a file in place; changing a file's quality or mode. */
 int fri_hip_plan_tiled_region_cover(const fri_hip_plan_tiled *p, uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint32_t out[4]);
 int fri_hip_split_tiles_region_dev(fri_hip_plan_tiled *p, const uint8_t *d_src, size_t src_pitch, uint32_t src_x, uint32_t src_y, uint32_t src_w, uint32_t src_h, uint32_t x,
                                    uint32_t y, uint32_t w, uint32_t h, uint8_t *d_tiles, void *stream);
