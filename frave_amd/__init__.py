@@ -15,6 +15,7 @@ from .api import (  # noqa: F401
     PlanRGBA,
     PlanTiled,
     PlanTiled420,
+    PlanTiledRgba,
     TILED_ALLOW_HOLES,
     DEQUANT_MIDPOINT,
     DEQUANT_MULTIPLY,

@@ -57,6 +57,10 @@ SYMBOLS = [
     "fri_hip_preview_image_tiled_coded",
     "fri_hip_plan_tiled_regions", "fri_hip_merge_tiles_regions_dev", "fri_hip_decode_regions_tiled_dev", "fri_hip_decode_regions_tiled",
     "fri_hip_decode_regions_tiled_coded",
+    "fri_hip_plan_tiled_rgba_create", "fri_hip_plan_tiled_rgba_destroy", "fri_hip_plan_tiled_rgba_colour", "fri_hip_plan_tiled_rgba_alpha", "fri_hip_plan_tiled_rgba_grid",
+    "fri_hip_plan_tiled_rgba_region", "fri_hip_plan_tiled_rgba_buffer_tiles", "fri_hip_split_tiles_rgba_dev", "fri_hip_merge_tiles_rgba_dev",
+    "fri_hip_merge_tiles_rgba_region_dev", "fri_hip_encode_symbols_tiled_rgba_dev", "fri_hip_encode_image_tiled_rgba_symbols", "fri_hip_decode_image_tiled_rgba",
+    "fri_hip_decode_region_tiled_rgba_dev", "fri_hip_decode_region_tiled_rgba",
 ]
 DECODE_TRUNCATED, DECODE_BAD_MODEL, DECODE_BAD_SLOT = 1, 2, 4  # FRI_HIP_DECODE_*: bits of a plane's status word of fri_hip_decode_planes_dev (include/fri_hip.h)
 RANS_EMPTY_OK = 1  # FRI_HIP_RANS_EMPTY_OK: `flags` of fri_hip_rans_encode_planes_dev - a context without counts is coded (the emitter's FRI_EMIT_EMPTY_OK)
@@ -290,6 +294,21 @@ def load_library():
     L.fri_hip_search_quality_ssim_tiled420_dev.argtypes = [vp, vp, C.c_double, vp, vp, vp]
     L.fri_hip_search_quality_for_size_tiled420.argtypes = [vp, vp, C.c_uint64, vp, vp]
     L.fri_hip_search_quality_for_size_tiled420_dev.argtypes = [vp, vp, C.c_uint64, vp, vp, vp]
+    L.fri_hip_plan_tiled_rgba_create.argtypes = [vp, u32, u32, u32, u32, u32, C.POINTER(vp)]
+    L.fri_hip_plan_tiled_rgba_destroy.argtypes = [vp]
+    L.fri_hip_plan_tiled_rgba_colour.restype, L.fri_hip_plan_tiled_rgba_colour.argtypes = vp, [vp]
+    L.fri_hip_plan_tiled_rgba_alpha.restype, L.fri_hip_plan_tiled_rgba_alpha.argtypes = vp, [vp]
+    L.fri_hip_plan_tiled_rgba_grid.argtypes = [vp, vp]
+    L.fri_hip_plan_tiled_rgba_region.argtypes = [vp, u32, u32, u32, u32, vp]
+    L.fri_hip_plan_tiled_rgba_buffer_tiles.argtypes = [vp, vp]
+    L.fri_hip_split_tiles_rgba_dev.argtypes = [vp, vp, i32, vp, vp, vp]
+    L.fri_hip_merge_tiles_rgba_dev.argtypes = [vp, vp, vp, vp, vp]
+    L.fri_hip_merge_tiles_rgba_region_dev.argtypes = [vp, vp, vp, u32, u32, u32, u32, vp, vp]
+    L.fri_hip_encode_symbols_tiled_rgba_dev.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp]
+    L.fri_hip_encode_image_tiled_rgba_symbols.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp]
+    L.fri_hip_decode_image_tiled_rgba.argtypes = [vp, vp, vp, vp]
+    L.fri_hip_decode_region_tiled_rgba_dev.argtypes = [vp, vp, vp, u32, u32, u32, u32, vp, vp]
+    L.fri_hip_decode_region_tiled_rgba.argtypes = [vp, vp, vp, u32, u32, u32, u32, vp]
     L.fri_hip_encode_image_tiled420_coded.argtypes = [vp, vp, i32, vp, vp, vp, sz, vp, vp, vp, vp]
     L.fri_hip_decode_scratch_bytes.restype, L.fri_hip_decode_scratch_bytes.argtypes = C.c_uint64, [u32]
     L.fri_hip_decode_planes_dev.argtypes = [vp, u32, vp, sz, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp]
@@ -1666,3 +1685,133 @@ class PlanTiled420:
         """fri_hip_search_quality_for_size_tiled420[_dev]: (quality, estimated bytes of the `frit` file); FriHipError with code -7 when nothing fits. Needs
         set_stream_order()."""
         return _search(self, "fri_hip_search_quality_for_size_tiled420", pixels, int(max_bytes), C.c_uint64, stream)
+
+
+class PlanTiledRgba:
+    """fri_hip_plan_tiled_rgba: an RGBA image as a batch of independently coded RGBA tiles (include/fri_hip.h, "Tiled RGBA coding", has the format). Owns two
+    ordinary plans of the tile's shape on one lattice, .colour (C = 3: set the colour transform and the dequantiser of a decode here) and .alpha (C = 1) - Plan
+    views that do not own their handle and die with this object. Every per-plane array is in plane order: with n tiles, plane(t, c) = 3 t + c for the colour
+    channels and plane(t, A) = 3 n + t. ctx=None gives a host-only plan (getters only). flags: TILED_ALLOW_HOLES accepts a tile shape whose lattice does not own
+    every pixel. Calls on one PlanTiledRgba must be ordered on one stream: they share the plan's staging buffers."""
+
+    def __init__(self, ctx, width, height, tile_w, tile_h, flags=0):
+        self._h = None
+        self.ctx = ctx
+        self.width, self.height = width, height
+        h = C.c_void_p()
+        L = load_library()
+        _check(L.fri_hip_plan_tiled_rgba_create(ctx._h if ctx else None, width, height, tile_w, tile_h, flags, C.byref(h)), "fri_hip_plan_tiled_rgba_create", ctx)
+        self._h = h
+        self.colour = Plan(ctx, tile_w, tile_h, 3, _handle=L.fri_hip_plan_tiled_rgba_colour(h))
+        self.alpha = Plan(ctx, tile_w, tile_h, 1, _handle=L.fri_hip_plan_tiled_rgba_alpha(h))
+        grid = np.zeros(4, np.uint32)
+        _check(L.fri_hip_plan_tiled_rgba_grid(h, _p(grid)), "fri_hip_plan_tiled_rgba_grid", ctx)
+        self.nx, self.ny, self.tile_w, self.tile_h = (int(v) for v in grid)
+        self.n_tiles = self.nx * self.ny
+        self.pixel_bytes = width * height * 4
+        self.colour_tile_bytes = self.n_tiles * tile_w * tile_h * 3  # colour_tiles [n][tile_h][tile_w][3]
+        self.alpha_tile_bytes = self.n_tiles * tile_w * tile_h       # alpha_tiles [n][tile_h][tile_w]
+        self.num_cells = self.colour.num_cells
+        self.num_some = self.colour.num_some  # symbols per plane, the same for all four channels of a tile
+        self.num_symbols = 4 * self.n_tiles * self.num_some
+        self.tile_coef_count = 4 * self.num_cells * 512
+        self.coef_count = self.n_tiles * self.tile_coef_count
+
+    def close(self):
+        if self._h:
+            self.colour.close()
+            self.alpha.close()
+            load_library().fri_hip_plan_tiled_rgba_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_stream_order(self):
+        """fri_hip_plan_set_stream_order on both inner plans (the encodes need it)."""
+        self.colour.set_stream_order()
+        self.alpha.set_stream_order()
+
+    def grid(self):
+        """fri_hip_plan_tiled_rgba_grid: (nx, ny, tile_w, tile_h). Works on a host-only plan."""
+        out = np.zeros(4, np.uint32)
+        _check(load_library().fri_hip_plan_tiled_rgba_grid(self._h, _p(out)), "fri_hip_plan_tiled_rgba_grid", self.ctx)
+        return tuple(int(v) for v in out)
+
+    def region(self, x, y, w, h):
+        """fri_hip_plan_tiled_rgba_region: (i0, j0, ni, nj), the sub-grid of tiles the region touches. Works on a host-only plan. FriHipError (-1) for an empty
+        region or one that leaves the image."""
+        out = np.zeros(4, np.uint32)
+        _check(load_library().fri_hip_plan_tiled_rgba_region(self._h, x, y, w, h, _p(out)), "fri_hip_plan_tiled_rgba_region", self.ctx)
+        return tuple(int(v) for v in out)
+
+    def buffer_tiles(self):
+        """fri_hip_plan_tiled_rgba_buffer_tiles: the tiles the plan's (colour, alpha) tile buffers hold room for at the moment."""
+        out = np.zeros(2, np.uint64)
+        _check(load_library().fri_hip_plan_tiled_rgba_buffer_tiles(self._h, _p(out)), "fri_hip_plan_tiled_rgba_buffer_tiles", self.ctx)
+        return int(out[0]), int(out[1])
+
+    # ---- device-pointer entry points (pointers are ints) --------------------------------------------
+    def split_tiles_rgba_dev(self, d_rgba, d_colour_tiles, d_alpha_tiles, clean=ALPHA_KEEP, stream=0):
+        """fri_hip_split_tiles_rgba_dev (K16): [H][W][4] -> colour_tiles [n][tile_h][tile_w][3] and alpha_tiles [n][tile_h][tile_w] in one pass; ALPHA_CLEAN zeroes
+        the colour where A == 0; only enqueues."""
+        _check(load_library().fri_hip_split_tiles_rgba_dev(self._h, d_rgba, int(clean), d_colour_tiles, d_alpha_tiles, stream), "fri_hip_split_tiles_rgba_dev", self.ctx)
+
+    def merge_tiles_rgba_dev(self, d_colour_tiles, d_alpha_tiles, d_rgba, stream=0):
+        """fri_hip_merge_tiles_rgba_dev (K16): the tile rasters -> [H][W][4], no replicated pixel read; only enqueues."""
+        _check(load_library().fri_hip_merge_tiles_rgba_dev(self._h, d_colour_tiles, d_alpha_tiles, d_rgba, stream), "fri_hip_merge_tiles_rgba_dev", self.ctx)
+
+    def merge_tiles_rgba_region_dev(self, d_colour_tiles, d_alpha_tiles, x, y, w, h, d_region, stream=0):
+        """fri_hip_merge_tiles_rgba_region_dev (K16): the sub-grid's tile rasters -> the region raster [h][w][4]; only enqueues."""
+        _check(load_library().fri_hip_merge_tiles_rgba_region_dev(self._h, d_colour_tiles, d_alpha_tiles, x, y, w, h, d_region, stream), "fri_hip_merge_tiles_rgba_region_dev",
+               self.ctx)
+
+    def encode_symbols_tiled_rgba_dev(self, d_rgba, d_params, d_symbols, d_hist, d_oob, d_fit_out_of_range=None, clean=ALPHA_KEEP, qmatrix=None, fit=True, stream=0):
+        """fri_hip_encode_symbols_tiled_rgba_dev: the split and the direct stream chain on both inner plans, everything on the device and in plane order: d_params
+        float32 [4 n][2][3][6], d_symbols uint16 [n][3][num_some] then [n][num_some], d_hist uint32 [4 n][10][1024], d_oob uint64 [4 n], d_fit_out_of_range uint64
+        [4 n] or None. qmatrix is the colour's; alpha always takes ones. Needs set_stream_order()."""
+        _check(load_library().fri_hip_encode_symbols_tiled_rgba_dev(self._h, d_rgba, int(clean), _p(_q(qmatrix)), int(bool(fit)), d_params, d_symbols, d_hist, d_oob,
+                                                                   d_fit_out_of_range, stream), "fri_hip_encode_symbols_tiled_rgba_dev", self.ctx)
+
+    def decode_region_tiled_rgba_dev(self, d_coefs, x, y, w, h, d_region, qmatrix=None, stream=0):
+        """fri_hip_decode_region_tiled_rgba_dev: d_coefs int32, the sub-grid's planes in plane order -> d_region uint8 [h][w][4], device pointers. Refuses a
+        capturing stream."""
+        _check(load_library().fri_hip_decode_region_tiled_rgba_dev(self._h, d_coefs, _p(_q(qmatrix)), x, y, w, h, d_region, stream), "fri_hip_decode_region_tiled_rgba_dev",
+               self.ctx)
+
+    # ---- host-pointer entry points ----------------------------------------------------------------
+    def encode_image_tiled_rgba_symbols(self, pixels, qmatrix=None, clean=ALPHA_KEEP):
+        """fri_hip_encode_image_tiled_rgba_symbols: (symbols uint16 [4 n][num_some], value_params [4 n][3][6], width_params [4 n][3][6], hist [4 n][10][1024],
+        oob [4 n]), all in plane order - what emit.tiled_encode_from_streams_rgba takes; the fit is on. Needs set_stream_order()."""
+        px = np.ascontiguousarray(pixels, np.uint8).reshape(-1)
+        assert px.size == self.pixel_bytes
+        planes = 4 * self.n_tiles
+        vp, wp = np.zeros((planes, 3, 6), np.float32), np.zeros((planes, 3, 6), np.float32)
+        sym = np.empty((planes, self.num_some), np.uint16)
+        hist = np.empty((planes, 10, 1024), np.uint32)
+        oob = np.zeros(planes, np.uint64)
+        _check(load_library().fri_hip_encode_image_tiled_rgba_symbols(self._h, _p(px), int(clean), _p(_q(qmatrix)), _p(vp), _p(wp), _p(sym), _p(hist), _p(oob)),
+               "fri_hip_encode_image_tiled_rgba_symbols", self.ctx)
+        return sym, vp, wp, hist, oob
+
+    def decode_image_tiled_rgba(self, coefs, qmatrix=None):
+        """fri_hip_decode_image_tiled_rgba: coefs int32 in plane order (what emit.tiled_decode returns for a tiled RGBA file) -> pixels uint8 [H * W * 4]. The
+        colour planes go through the inverse kernel with qmatrix and the colour plan's transform and dequantiser, the alpha planes with ones."""
+        co = np.ascontiguousarray(coefs, np.int32).reshape(-1)
+        assert co.size == self.coef_count
+        out = np.empty(self.pixel_bytes, np.uint8)
+        _check(load_library().fri_hip_decode_image_tiled_rgba(self._h, _p(co), _p(_q(qmatrix)), _p(out)), "fri_hip_decode_image_tiled_rgba", self.ctx)
+        return out
+
+    def decode_region_tiled_rgba(self, coefs, x, y, w, h, qmatrix=None):
+        """fri_hip_decode_region_tiled_rgba: coefs int32, the sub-grid's planes in plane order (what emit.tiled_decode_region returns) -> pixels uint8 [h * w * 4]:
+        the crop [y : y + h, x : x + w] of what decode_image_tiled_rgba returns for the same file."""
+        _, _, ni, nj = self.region(x, y, w, h)
+        co = np.ascontiguousarray(coefs, np.int32).reshape(-1)
+        assert co.size == ni * nj * self.tile_coef_count
+        out = np.empty(w * h * 4, np.uint8)
+        _check(load_library().fri_hip_decode_region_tiled_rgba(self._h, _p(co), _p(_q(qmatrix)), x, y, w, h, _p(out)), "fri_hip_decode_region_tiled_rgba", self.ctx)
+        return out

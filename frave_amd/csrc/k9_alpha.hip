@@ -5,10 +5,9 @@
 //
 // None of the three rasters has a row pitch, so the kernels see a flat run of N = W H pixels. A lane owns one strip of 16 consecutive pixels: 64 bytes of
 // R, G, B, A as four 16-byte accesses, 48 bytes of R, G, B as three and 16 bytes of A as one. The bytes change places in registers with v_perm_b32
-// (__builtin_amdgcn_perm(a, b, sel): selector values 0..3 take a byte of b, 4..7 a byte of a) - four pixels are four dwords on one side and three + one on the
-// other - and CLEAN is one select per pixel. The buffers start at any byte: the vector accesses are the target's unaligned global loads and stores (the compiler
-// is told the alignment is 1). Only the last strip, when N is no multiple of 16, is walked byte by byte. Every byte offset is 64-bit: 4 W H can pass 2^32.
-#include "device_common.hpp"
+// (rgba_shuffle.hpp, shared with K16) - four pixels are four dwords on one side and three + one on the other - and CLEAN is one select per pixel. The
+// buffers start at any byte: the vector accesses are the target's unaligned global loads and stores (the compiler is told the alignment is 1). Only the last strip, when N is no multiple of 16, is walked byte by byte. Every byte offset is 64-bit: 4 W H can pass 2^32.
+#include "rgba_shuffle.hpp"
 
 namespace fri {
 namespace {
@@ -23,17 +22,6 @@ struct RgbaArgs {
     uint32_t n_strips;
 };
 
-template <typename V>
-__device__ __forceinline__ V load_unaligned(const uint8_t *p) {
-    V v;
-    __builtin_memcpy(&v, p, sizeof(V));
-    return v;
-}
-template <typename V>
-__device__ __forceinline__ void store_unaligned(uint8_t *p, const V &v) {
-    __builtin_memcpy(p, &v, sizeof(V));
-}
-
 template <bool CLEAN>
 __global__ void __launch_bounds__(kAlphaThreads) split_rgba_kernel(const RgbaArgs p) {
     const uint32_t t = blockIdx.x * kAlphaThreads + threadIdx.x;
@@ -42,33 +30,7 @@ __global__ void __launch_bounds__(kAlphaThreads) split_rgba_kernel(const RgbaArg
     const uint8_t *src = p.in0 + first * 4;
     uint8_t *rgb = p.out0 + first * 3, *al = p.out1 + first;
     if (first + kAlphaStrip <= p.n_pixels) {
-        uint32_t px[16];
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const u32x4 v = load_unaligned<u32x4>(src + 16 * q);
-            px[4 * q] = v.x, px[4 * q + 1] = v.y, px[4 * q + 2] = v.z, px[4 * q + 3] = v.w;
-        }
-        if (CLEAN) {
-#pragma unroll
-            for (int k = 0; k < 16; k++) px[k] = px[k] >> 24 ? px[k] : 0u;
-        }
-        uint32_t c[12], a[4];
-#pragma unroll
-        for (int g = 0; g < 4; g++) { // four pixels R G B A x 4 -> R0 G0 B0 R1 | G1 B1 R2 G2 | B2 R3 G3 B3 and A0 A1 A2 A3
-            const uint32_t p0 = px[4 * g], p1 = px[4 * g + 1], p2 = px[4 * g + 2], p3 = px[4 * g + 3];
-            c[3 * g] = __builtin_amdgcn_perm(p1, p0, 0x04020100u);
-            c[3 * g + 1] = __builtin_amdgcn_perm(p2, p1, 0x05040201u);
-            c[3 * g + 2] = __builtin_amdgcn_perm(p3, p2, 0x06050402u);
-            const uint32_t a01 = __builtin_amdgcn_perm(p1, p0, 0x07030703u), a23 = __builtin_amdgcn_perm(p3, p2, 0x07030703u);
-            a[g] = __builtin_amdgcn_perm(a23, a01, 0x05040100u);
-        }
-#pragma unroll
-        for (int q = 0; q < 3; q++) {
-            const u32x4 v = {c[4 * q], c[4 * q + 1], c[4 * q + 2], c[4 * q + 3]};
-            store_unaligned(rgb + 16 * q, v);
-        }
-        const u32x4 v = {a[0], a[1], a[2], a[3]};
-        store_unaligned(al, v);
+        rgba_split_strip<CLEAN>(src, rgb, al);
     } else { // the last, partial strip
         const int n = (int)(p.n_pixels - first);
         for (int k = 0; k < n; k++) {
@@ -89,28 +51,7 @@ __global__ void __launch_bounds__(kAlphaThreads) merge_rgba_kernel(const RgbaArg
     const uint8_t *rgb = p.in0 + first * 3, *al = p.in1 + first;
     uint8_t *dst = p.out0 + first * 4;
     if (first + kAlphaStrip <= p.n_pixels) {
-        uint32_t c[12];
-#pragma unroll
-        for (int q = 0; q < 3; q++) {
-            const u32x4 v = load_unaligned<u32x4>(rgb + 16 * q);
-            c[4 * q] = v.x, c[4 * q + 1] = v.y, c[4 * q + 2] = v.z, c[4 * q + 3] = v.w;
-        }
-        const u32x4 av = load_unaligned<u32x4>(al);
-        const uint32_t a[4] = {av.x, av.y, av.z, av.w};
-        uint32_t px[16];
-#pragma unroll
-        for (int g = 0; g < 4; g++) { // R0 G0 B0 R1 | G1 B1 R2 G2 | B2 R3 G3 B3 and A0 A1 A2 A3 -> four pixels
-            const uint32_t c0 = c[3 * g], c1 = c[3 * g + 1], c2 = c[3 * g + 2];
-            px[4 * g] = __builtin_amdgcn_perm(a[g], c0, 0x04020100u);
-            px[4 * g + 1] = __builtin_amdgcn_perm(a[g], __builtin_amdgcn_perm(c1, c0, 0x00050403u), 0x05020100u);
-            px[4 * g + 2] = __builtin_amdgcn_perm(a[g], __builtin_amdgcn_perm(c2, c1, 0x00040302u), 0x06020100u);
-            px[4 * g + 3] = __builtin_amdgcn_perm(a[g], c2, 0x07030201u);
-        }
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const u32x4 v = {px[4 * q], px[4 * q + 1], px[4 * q + 2], px[4 * q + 3]};
-            store_unaligned(dst + 16 * q, v);
-        }
+        rgba_merge_strip(rgb, al, dst);
     } else { // the last, partial strip
         const int n = (int)(p.n_pixels - first);
         for (int k = 0; k < n; k++) {

@@ -261,6 +261,16 @@ hipError_t launch_merge_tiles420_region(const uint8_t *y_tiles, const uint8_t *c
 hipError_t launch_measure_tiles420(const uint8_t *y_tiles, const uint8_t *c_tiles, uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, const uint8_t *reference,
                                    unsigned long long *sums, hipStream_t stream);
 
+// K16 (k16_tiles_rgba.hip): the raster kernels of tiled RGBA coding (include/fri_hip.h has the format). Split: interleaved R, G, B, A [H][W][4] -> colour_tiles
+// [n][tile_h][tile_w][3] and alpha_tiles [n][tile_h][tile_w], n = ny nx: K9's split and K10's edge replication of both rasters in one pass; clean: a pixel with
+// A == 0 gets R = G = B = 0. Region merge: the tile rasters of the sub-grid a region touches, [nj ni]... -> the region raster [h][w][4]; the region must lie in
+// the width x height image (hipErrorInvalidValue otherwise). The whole-image merge is the region (0, 0, width, height). Any shape whose strips fit a u32, any
+// pointer alignment; only enqueues.
+hipError_t launch_split_tiles_rgba(const uint8_t *rgba, uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, bool clean, uint8_t *colour_tiles, uint8_t *alpha_tiles,
+                                   hipStream_t stream);
+hipError_t launch_merge_tiles_rgba_region(const uint8_t *colour_tiles, const uint8_t *alpha_tiles, uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t x,
+                                          uint32_t y, uint32_t w, uint32_t h, uint8_t *region, hipStream_t stream);
+
 // K2's per-node neighbour offsets (LDS halfword offsets relative to the own slot, two per word) from the static neighbour table
 void build_lf_deltas(const uint16_t *nbr_table, int8_t *out /* [8] */);
 void build_gather_tables(const uint16_t *nbr_table, uint32_t *gather_off /* [512][4] */, uint16_t *pair_pos /* [256] */, uint16_t *heap_of_pos /* [512] */);

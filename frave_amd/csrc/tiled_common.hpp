@@ -1,6 +1,6 @@
-// tiled_common.hpp -- what the two tiled plan kinds of the C ABI share (fri_hip_tiled.cpp, fri_hip_tiled420.cpp): the tile grid, the first-fit search for a
-// tile shape, the skeleton of a tiled plan's creation, the host form of the size estimate, and the coded routes - K11 over a batch of planes with its one second
-// pass, and the read-back behind it; the upload of coded planes and K13 over them. Private to libfri_hip.so.
+// tiled_common.hpp -- what the tiled plan kinds of the C ABI share (fri_hip_tiled.cpp, fri_hip_tiled420.cpp, fri_hip_tiled_rgba.cpp): the tile grid, the
+// first-fit search for a tile shape, the skeleton of a tiled plan's creation, the host form of the size estimate, and the coded routes - K11 over a batch of
+// planes with its one second pass, and the read-back behind it; the upload of coded planes and K13 over them. Private to libfri_hip.so.
 #pragma once
 #include "fri_hip_internal.hpp"
 

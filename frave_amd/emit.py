@@ -48,6 +48,7 @@ def load_library():
         L.fri_emit_encode_image_from_streams.argtypes = [u32, u32, u32, vp, C.c_uint64, vp, vp, vp, vp, sz, vp, C.c_char_p, sz]
         L.fri_tiled_encode_from_streams.argtypes = [u32, u32, u32, u32, u32, vp, C.c_uint64, vp, vp, vp, u32, vp, sz, vp, C.c_char_p, sz]
         L.fri_tiled_encode_from_streams420.argtypes = [u32, u32, u32, u32, u32, vp, C.c_uint64, C.c_uint64, vp, vp, vp, u32, vp, sz, vp, C.c_char_p, sz]
+        L.fri_tiled_encode_from_streams_rgba.argtypes = [u32, u32, u32, u32, u32, vp, C.c_uint64, vp, vp, vp, u32, vp, sz, vp, C.c_char_p, sz]
         L.fri_tiled_encode_from_coded.argtypes = [u32, u32, u32, u32, u32, vp, C.c_uint64, vp, vp, vp, vp, vp, u32, vp, sz, vp, C.c_char_p, sz]
         L.fri_tiled_encode_from_coded420.argtypes = [u32, u32, u32, u32, u32, vp, C.c_uint64, vp, vp, vp, vp, vp, u32, vp, sz, vp, C.c_char_p, sz]
         L.fri_coded_encode_image.argtypes = [u32, u32, u32, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, sz, vp, C.c_char_p, sz]
@@ -242,18 +243,21 @@ def decode_image(frv):
 # ---- the tile container `frit` (include/fri_emit.h) ---------------------------------------------------------------------------
 class TiledInfo(tuple):
     """(width, height, tile_w, tile_h, nx, ny, channels, n_cells) of a tiled file, and .rct / .quality / .ycbcr / .s420 as DecodedImage has them: what every tile
-    is. A tiled 4:2:0 file (.s420): n_cells is F_y, the cells of the tile's luma lattice."""
+    is. A tiled 4:2:0 file (.s420): n_cells is F_y, the cells of the tile's luma lattice. A tiled RGBA file (.alpha): channels stays 3, every tile has a fourth
+    plane on the same lattice."""
 
     rct = False
     quality = 0
     ycbcr = False
     s420 = False
+    alpha = False
 
 
 def _tiled_info(info):
     w, h, tw, th, nx, ny, c, f = (int(x) for x in info)
     out = TiledInfo((w, h, tw, th, nx, ny, c & 0xFF, f))
     out.rct, out.ycbcr, out.quality, out.s420 = bool(c & RCT), bool(c & YCBCR), (c >> 16) & 0x7F, bool(c & S420)
+    out.alpha = bool(c & ALPHA)
     return out
 
 
@@ -268,9 +272,12 @@ def _chroma_cells(ti):
 
 
 def _tiled_coefs(ti, n):
-    """the array fri_tiled_decode[_region] fills for n tiles: [n][C][F][512], or flat in plane order - n (F_y + 2 F_c) x 512 - for a tiled 4:2:0 file"""
+    """the array fri_tiled_decode[_region] fills for n tiles: [n][C][F][512], or flat in plane order - n (F_y + 2 F_c) x 512 - for a tiled 4:2:0 file, or
+    the planes in plane order, [4 n][F][512] = [n][3][F][512] then [n][F][512], for a tiled RGBA file"""
     if ti.s420:
         return np.empty(n * (ti[7] + 2 * _chroma_cells(ti)) * 512, np.int32)
+    if ti.alpha:
+        return np.empty((4 * n, ti[7], 512), np.int32)
     return np.empty((n, ti[6], ti[7], 512), np.int32)
 
 
@@ -295,6 +302,35 @@ def tiled_encode_from_streams420(width, height, tile_w, tile_h, streams, n_luma,
         rc = L.fri_tiled_encode_from_streams420(*args, _p(out), out.size, C.addressof(n), err, 256)
     if rc != 0:
         raise EmitError(err.value.decode() or f"fri_tiled_encode_from_streams420: {rc}")
+    return out[: n.value].tobytes()
+
+
+def tiled_encode_from_streams_rgba(width, height, tile_w, tile_h, streams, hist, value_params, width_params, rct=False, quality=0, ycbcr=False, threads=0, flags=None):
+    """fri_tiled_encode_from_streams_rgba: the `frit` bytes of a tiled RGBA file from what PlanTiledRgba.encode_image_tiled_rgba_symbols returns, all in plane
+    order (plane(t, c) = 3 t + c, plane(t, A) = 3 n + t): streams uint16 [4 n][n_symbols], hist [4 n][10][1024], params [4 n][3][6]. rct / quality / ycbcr say
+    how the colour was coded; the alpha planes are lossless. `flags`: the whole `channels` word in their place (for the refusals). The bytes do not depend on
+    `threads`."""
+    st = np.ascontiguousarray(streams, np.uint16)
+    h = np.ascontiguousarray(hist, np.uint32)
+    vp, wp = np.ascontiguousarray(value_params, np.float32), np.ascontiguousarray(width_params, np.float32)
+    n_tiles = -(-width // tile_w) * -(-height // tile_h)
+    planes = 4 * n_tiles
+    assert h.size == planes * 10240 and vp.size == planes * 18 and wp.size == planes * 18 and st.size % planes == 0
+    n_symbols = st.size // planes
+    n = C.c_size_t(0)
+    err = C.create_string_buffer(256)
+    out = np.empty(st.size * 4 + planes * (10 * 2070 + 256) + n_tiles * 72 + 64, np.uint8)
+    word = _arg(3, rct, quality, ycbcr, False, True) if flags is None else int(flags)
+    args = (width, height, tile_w, tile_h, word, _p(st), n_symbols, _p(h), _p(vp), _p(wp), threads)
+    L = load_library()
+    rc = L.fri_tiled_encode_from_streams_rgba(*args, _p(out), out.size, C.addressof(n), err, 256)
+    if rc == -3:
+        out = np.empty(n.value, np.uint8)
+        rc = L.fri_tiled_encode_from_streams_rgba(*args, _p(out), out.size, C.addressof(n), err, 256)
+    if rc != 0:
+        e = EmitError(err.value.decode() or f"fri_tiled_encode_from_streams_rgba: {rc}")
+        e.code = rc
+        raise e
     return out[: n.value].tobytes()
 
 
@@ -399,7 +435,8 @@ def tiled_info(frv):
 def tiled_decode(frv, threads=0):
     """fri_tiled_decode: (TiledInfo, coefs int32 [n_tiles][C][F][512] with None = INT32_MIN) - what PlanTiled.decode_image_tiled takes. Tiles are decoded on
     `threads` workers (0: the hardware concurrency, capped at 16). A tiled 4:2:0 file (TiledInfo.s420): coefs is flat and in plane order, [n][F_y][512] then
-    [n][2][F_c][512] - what PlanTiled420.decode_image_tiled420 takes."""
+    [n][2][F_c][512] - what PlanTiled420.decode_image_tiled420 takes. A tiled RGBA file (TiledInfo.alpha): coefs is [4 n][F][512] in plane order - what
+    PlanTiledRgba.decode_image_tiled_rgba takes."""
     data = np.frombuffer(frv, np.uint8)
     info = np.zeros(8, np.uint32)
     err = C.create_string_buffer(256)
@@ -479,7 +516,8 @@ def tiled_region_tiles(width, height, tile_w, tile_h, x, y, w, h):
 def tiled_decode_region(frv, x, y, w, h, threads=0):
     """fri_tiled_decode_region: (TiledInfo, (i0, j0, ni, nj), coefs int32 [nj ni][C][F][512]) - what PlanTiled.decode_region_tiled takes. The file is checked as
     tiled_decode checks it; only the tiles the region touches are decoded, and damage inside the body of an untouched tile is not looked at. A tiled 4:2:0 file:
-    coefs is flat and in the sub-grid's plane order - what PlanTiled420.decode_region_tiled420 takes."""
+    coefs is flat and in the sub-grid's plane order - what PlanTiled420.decode_region_tiled420 takes. A tiled RGBA file: coefs is [4 ni nj][F][512] in the
+    sub-grid's plane order - what PlanTiledRgba.decode_region_tiled_rgba takes."""
     data = np.frombuffer(frv, np.uint8)
     info, tiles = np.zeros(8, np.uint32), np.zeros(4, np.uint32)
     err = C.create_string_buffer(256)
@@ -525,7 +563,7 @@ def tiled_regions_tiles(width, height, tile_w, tile_h, regions):
 def tiled_decode_tiles(frv, tiles, threads=0):
     """fri_tiled_decode_tiles: (TiledInfo, coefs int32 [T][C][F][512]) for the strictly ascending tile list `tiles` (file-grid indices), in list order - what
     PlanTiled.decode_regions_tiled takes. The file is checked as tiled_decode checks it; only the listed tiles are decoded, and damage inside the body of an
-    unlisted tile is not looked at. A tiled 4:2:0 file: coefs is flat and in plane order with n = T. An EmitError carries the C return value as .code."""
+    unlisted tile is not looked at. A tiled 4:2:0 file: coefs is flat and in plane order with n = T; a tiled RGBA file: [4 T][F][512] in plane order. An EmitError carries the C return value as .code."""
     data = np.frombuffer(frv, np.uint8)
     tl = np.ascontiguousarray(tiles, np.uint32).reshape(-1)
     info = np.zeros(8, np.uint32)

@@ -1041,19 +1041,30 @@ static void assemble_tiled(uint32_t width, uint32_t height, uint32_t tile_w, uin
                            std::vector<uint8_t> &out);
 
 // The payload of one tile: the `frif` file of plane group t of the arrays ([..][channels][n_symbols] streams and so on), FRI_EMIT_EMPTY_OK in force, coded on the
-// calling thread. The one per-tile path of encode_tiled_from_streams and update_tiled_from_streams.
+// calling thread. The one per-tile path of encode_tiled_from_streams, encode_tiled_from_streams_rgba and update_tiled_from_streams. alpha_plane: the plane that
+// holds the tile's alpha channel - an RGBA tile, its fourth channel behind the three colour channels - or kNoAlphaPlane.
+constexpr size_t kNoAlphaPlane = ~(size_t)0;
 static std::string tile_payload_from_streams(uint32_t tile_w, uint32_t tile_h, uint32_t channels, bool rct, uint32_t quality, bool ycbcr, size_t t, const uint16_t *streams,
-                                             size_t n_symbols, const uint32_t *hist, const float *value_params, const float *width_params, std::vector<uint8_t> &payload) {
+                                             size_t n_symbols, const uint32_t *hist, const float *value_params, const float *width_params, std::vector<uint8_t> &payload,
+                                             size_t alpha_plane = kNoAlphaPlane) {
     const size_t plane0 = t * channels;
+    const bool alpha = alpha_plane != kNoAlphaPlane;
     std::vector<ChannelStream> chans;
     const std::string ce = encode_channels_from_streams(channels, streams + plane0 * n_symbols, n_symbols, hist + plane0 * kContexts * kAlphabet, chans, 0, true, true);
     if (!ce.empty()) return ce;
-    std::vector<ChannelParams> params(channels);
+    std::vector<ChannelParams> params(channels + (alpha ? 1u : 0u));
     for (uint32_t ch = 0; ch < channels; ch++) {
         std::memcpy(params[ch].value, value_params + (plane0 + ch) * 18, sizeof(params[ch].value));
         std::memcpy(params[ch].width, width_params + (plane0 + ch) * 18, sizeof(params[ch].width));
     }
-    payload = serialize(tile_h, tile_w, channels == 1 ? kLuma : rct || ycbcr ? kYCbCr : kRGB, chans, params, rct, quality, ycbcr);
+    if (alpha) {
+        chans.emplace_back();
+        const std::string ae = encode_channel_from_stream(streams + alpha_plane * n_symbols, n_symbols, hist + alpha_plane * kContexts * kAlphabet, chans[channels], true, true);
+        if (!ae.empty()) return "channel " + std::to_string(channels) + ": " + ae;
+        std::memcpy(params[channels].value, value_params + alpha_plane * 18, sizeof(params[channels].value));
+        std::memcpy(params[channels].width, width_params + alpha_plane * 18, sizeof(params[channels].width));
+    }
+    payload = serialize(tile_h, tile_w, channels == 1 ? kLuma : rct || ycbcr ? kYCbCr : kRGB, chans, params, rct, quality, ycbcr, false, alpha);
     return "";
 }
 
@@ -1079,6 +1090,28 @@ std::string encode_tiled_from_streams(uint32_t width, uint32_t height, uint32_t 
     return "";
 }
 
+std::string encode_tiled_from_streams_rgba(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, bool rct, uint32_t quality, bool ycbcr, const uint16_t *streams,
+                                           size_t n_symbols, const uint32_t *hist, const float *value_params, const float *width_params, unsigned threads,
+                                           std::vector<uint8_t> &out) {
+    if (!width || !height || !tile_w || !tile_h) return "invalid argument";
+    const uint64_t nx = ((uint64_t)width + tile_w - 1) / tile_w, ny = ((uint64_t)height + tile_h - 1) / tile_h;
+    if (nx * ny > 0xFFFFFFFFull) return "invalid argument";
+    const size_t n_tiles = (size_t)(nx * ny);
+    { // the tile geometry, once: all four planes of every tile are streams of this lattice
+        fri::Geometry g;
+        const std::string ge = fri::build_geometry(tile_w, tile_h, 3, fri::TilingParams{}, g);
+        if (!ge.empty()) return ge;
+        if (g.n_some != n_symbols) return "n_symbols is not the symbol count of the tile_w x tile_h lattice";
+    }
+    std::vector<std::vector<uint8_t>> payload(n_tiles);
+    const std::string e = for_each_tile(n_tiles, threads, [&](size_t t) -> std::string { // plane order: the colour planes 3 t + c, the alpha plane 3 n + t
+        return tile_payload_from_streams(tile_w, tile_h, 3, rct, quality, ycbcr, t, streams, n_symbols, hist, value_params, width_params, payload[t], 3 * n_tiles + t);
+    });
+    if (!e.empty()) return e;
+    assemble_tiled(width, height, tile_w, tile_h, nx, ny, payload, out);
+    return "";
+}
+
 // Region update (include/fri_emit.h, "Region update"): the touched sub-grid's payloads are coded from the streams, sub-tile by sub-tile, through the per-tile path
 // of encode_tiled_from_streams; every other payload is the file's own bytes, copied and not looked into; the table is rebuilt around them.
 std::string update_tiled_from_streams(const uint8_t *b, size_t len, const Region &region, uint32_t channels, bool rct, uint32_t quality, bool ycbcr, const uint16_t *streams,
@@ -1089,6 +1122,7 @@ std::string update_tiled_from_streams(const uint8_t *b, size_t len, const Region
     std::string e = parse_tiled(b, len, info, offset);
     if (!e.empty()) return e;
     if (info.s420) return kNoUpdate420;
+    if (info.alpha) return kNoUpdateRgba;
     if (!region_tiles(info.width, info.height, info.tile_w, info.tile_h, region, range)) return "invalid region";
     const ColorSpaceCode cs = channels == 1 ? kLuma : rct || ycbcr ? kYCbCr : kRGB;
     if (metadata_word(cs, rct, quality, ycbcr, false, false) != info.mdat) return "the metadata word of `channels` is not the one the file's tiles carry";
@@ -1303,7 +1337,8 @@ std::string parse_tiled(const uint8_t *b, size_t len, TiledInfo &info, std::vect
         if (std::memcmp(p, "frif", 4) != 0 || get_u32(p + 4) != info.tile_h || get_u32(p + 8) != info.tile_w || get_u32(p + 12) != info.mdat) return kMalformedTiled;
     }
     info.s420 = cs == kYCbCr && (info.mdat & kMdat420);
-    if (cs != kLuma && (info.mdat & kMdatAlpha)) return kMalformedTiled; // alpha inside tiles is refused
+    info.alpha = cs != kLuma && (info.mdat & kMdatAlpha);                // RGBA tiles; bit 3 of a Luma tile is ignored
+    if (info.alpha && (info.mdat & kMdat420)) return kMalformedTiled;    // bits 2 and 3 together ("Invalid metadata" in a `frif` file)
     if (info.s420 && (!info.ycbcr || info.rct)) return kMalformedTiled;  // 4:2:0 tiles are lossy YCbCr tiles ("Invalid metadata" otherwise)
     if (info.quality >= 100 || (info.ycbcr && (info.rct || info.quality == 0))) return kMalformedTiled;
     return "";
@@ -1349,6 +1384,7 @@ std::string decode_tiled(const uint8_t *b, size_t len, unsigned threads, TiledIn
     if (!e.empty()) return e;
     if (levels > kDepth) return "invalid argument";
     if (levels >= 0 && info.s420) return kNoLevels420;
+    if (levels >= 0 && info.alpha) return kNoLevelsRgba;
     if (levels < 0) levels = kDepth;
     TileRange tr{0, 0, info.nx, info.ny}; // without a region: the whole grid
     if (region && !region_tiles(info.width, info.height, info.tile_w, info.tile_h, *region, tr)) return "invalid region";
@@ -1390,7 +1426,9 @@ std::string decode_tiled(const uint8_t *b, size_t len, unsigned threads, TiledIn
             return "";
         }, file_tile);
     }
-    if (!coefs || coef_cap < n_tiles * info.channels * plane) return too_small = true, "";
+    // RGBA tiles: a fourth channel on the tile lattice; plane order - the colour planes 3 s + c, then the alpha planes 3 n + s
+    const uint32_t planes = info.channels + (info.alpha ? 1u : 0u);
+    if (!coefs || coef_cap < n_tiles * planes * plane) return too_small = true, "";
     const auto order = shared_symbol_order(centers.data(), (uint32_t)F);
     return for_each_tile(n_tiles, threads, [&](size_t s) -> std::string {
         const size_t t = file_tile(s);
@@ -1398,12 +1436,13 @@ std::string decode_tiled(const uint8_t *b, size_t len, unsigned threads, TiledIn
         ParsedImage img;
         const std::string de = deserialize(std::vector<uint8_t>(p, b + offset[t + 1]), img);
         if (!de.empty()) return de;
-        if (img.channels.size() != info.channels) return kMalformedTiled;
+        if (img.channels.size() != planes) return kMalformedTiled;
         for (const ChannelStream &c : img.channels)
             for (const AnsContext &a : c.contexts)
                 if (a.max_freq_bits == 0) return "Malformed image bytes"; // fewer than ten EHD segments
-        for (uint32_t ch = 0; ch < info.channels; ch++) {
-            const std::string ce = decode_channel(g, *order, img.channels[ch], img.params[ch], coefs + (s * info.channels + ch) * plane, levels);
+        for (uint32_t ch = 0; ch < planes; ch++) {
+            const size_t k = ch < info.channels ? s * info.channels + ch : info.channels * n_tiles + s;
+            const std::string ce = decode_channel(g, *order, img.channels[ch], img.params[ch], coefs + k * plane, levels);
             if (!ce.empty()) return "channel " + std::to_string(ch) + ": " + ce;
         }
         return "";
@@ -1418,6 +1457,7 @@ std::string parse_tiled_coded(const uint8_t *b, size_t len, TiledInfo &info, siz
     std::vector<uint64_t> offset;
     std::string e = parse_tiled(b, len, info, offset);
     if (!e.empty()) return e;
+    if (info.alpha) return kNoCodedRgba;
     if (list && !tile_list_ok(*list, (uint64_t)info.nx * info.ny)) return kBadTileList;
     { // the cells of the tile lattices, as decode_tiled reports them
         uint32_t cells = 0;

@@ -208,6 +208,7 @@ struct TiledInfo {
     uint32_t channels = 0, quality = 0;
     bool rct = false, ycbcr = false;
     bool s420 = false;    // every tile is a 4:2:0 image (include/fri_hip.h, "Tiled 4:2:0 coding"): the planes are in plane order
+    bool alpha = false;   // every tile is an RGBA image (include/fri_hip.h, "Tiled RGBA coding"): `channels` stays 3, the planes are in plane order
     uint32_t n_cells = 0; // F of the tile lattice (decode_tiled only); 4:2:0: F_y, of the tile's luma lattice
     uint32_t n_cells_chroma = 0; // 4:2:0: F_c, of the lattice of the tile's chroma planes (decode_tiled only)
 };
@@ -223,7 +224,20 @@ std::string encode_tiled_from_streams(uint32_t width, uint32_t height, uint32_t 
 std::string encode_tiled_from_streams420(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t quality, const uint16_t *streams, size_t n_luma,
                                          size_t n_chroma, const uint32_t *hist, const float *value_params, const float *width_params, unsigned threads,
                                          std::vector<uint8_t> &out);
-// The same file from planes the device coded (K11; include/fri_hip.h, fri_hip_rans_encode_planes_dev, has the layouts): words [n_tiles channels][word_stride] of which
+// A tiled RGBA file (include/fri_hip.h, "Tiled RGBA coding"): every payload is what fri_emit_encode_image_from_streams writes for the tile with
+// 3 | FRI_EMIT_ALPHA | <colour flags> | FRI_EMIT_EMPTY_OK. The arrays are in plane order - plane(t, c) = 3 t + c, plane(t, A) = 3 n + t: streams [n][3][n_symbols]
+// then [n][n_symbols], hist [4 n][10][1024], value_params / width_params [4 n][3][6] - what fri_hip_encode_image_tiled_rgba_symbols returns.
+std::string encode_tiled_from_streams_rgba(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, bool rct, uint32_t quality, bool ycbcr, const uint16_t *streams,
+                                           size_t n_symbols, const uint32_t *hist, const float *value_params, const float *width_params, unsigned threads,
+                                           std::vector<uint8_t> &out);
+// what the entry points without a tiled RGBA form answer for such a file: the level-limited decode, the coded parse, the region update
+inline constexpr const char *kNoLevelsRgba =
+    "a tiled RGBA file has no level-limited decode (the preview of alpha tiles is not built): decode it whole with fri_tiled_decode";
+inline constexpr const char *kNoCodedRgba =
+    "a tiled RGBA file has no coded parse (the device decoder does not take alpha tiles): decode it with fri_tiled_decode";
+inline constexpr const char *kNoUpdateRgba =
+    "a tiled RGBA file has no region update (the region split of alpha tiles is not built): tiled RGBA files are re-encoded whole";
+// encode_tiled_from_streams's file from planes the device coded (K11; include/fri_hip.h, fri_hip_rans_encode_planes_dev, has the layouts): words [n_tiles channels][word_stride] of which
 // the first n_words [n_tiles channels] of a plane are its rANS data as little-endian words, models [n_tiles channels][10][4] = {max_freq_bits, n_off, -, -}, off_values
 // [n_tiles channels][10][1024] of which a context's first n_off are its list. Through the same serialize: byte for byte encode_tiled_from_streams's file when the planes
 // are what the host coder makes of the streams.

@@ -225,7 +225,7 @@ int fri_emit_decode_image(const uint8_t *frv, size_t len, uint32_t info[4], int3
 namespace {
 void fill_tiled_info(const TiledInfo &t, uint32_t info[8]) {
     info[0] = t.width, info[1] = t.height, info[2] = t.tile_w, info[3] = t.tile_h, info[4] = t.nx, info[5] = t.ny;
-    info[6] = channels_info(t.channels, t.rct, t.quality, t.ycbcr, t.s420, false), info[7] = t.n_cells;
+    info[6] = channels_info(t.channels, t.rct, t.quality, t.ycbcr, t.s420, t.alpha), info[7] = t.n_cells;
 }
 } // namespace
 
@@ -259,6 +259,25 @@ int fri_tiled_encode_from_streams420(uint32_t width, uint32_t height, uint32_t t
         return fail(err, err_cap, "invalid argument");
     std::vector<uint8_t> bytes;
     const std::string e = encode_tiled_from_streams420(width, height, tile_w, tile_h, quality, streams, (size_t)n_luma, (size_t)n_chroma, hist, value_params, width_params, threads, bytes);
+    if (e == "invalid argument") return fail(err, err_cap, e);
+    if (!e.empty()) return fail(err, err_cap, e, -2);
+    *len = bytes.size();
+    if (!out || cap < bytes.size()) return -3;
+    std::memcpy(out, bytes.data(), bytes.size());
+    return 0;
+}
+
+int fri_tiled_encode_from_streams_rgba(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t channels_arg, const uint16_t *streams, uint64_t n_symbols,
+                                       const uint32_t *hist, const float *value_params, const float *width_params, uint32_t threads, uint8_t *out, size_t cap, size_t *len, char *err,
+                                       size_t err_cap) {
+    uint32_t channels, quality;
+    bool rct, ycbcr, s420 = false, alpha = false, empty_ok = false;
+    // 3 | FRI_EMIT_ALPHA with none, FRI_EMIT_RCT, FRI_EMIT_QUALITY(q) or FRI_EMIT_YCBCR | FRI_EMIT_QUALITY(q), and nothing else (FRI_EMIT_EMPTY_OK is always on and may be passed)
+    if (!streams || !hist || !value_params || !width_params || !len || !split_channels(channels_arg, channels, rct, quality, ycbcr, &s420, &alpha, &empty_ok) || !alpha || s420 ||
+        channels != 3)
+        return fail(err, err_cap, "invalid argument");
+    std::vector<uint8_t> bytes;
+    const std::string e = encode_tiled_from_streams_rgba(width, height, tile_w, tile_h, rct, quality, ycbcr, streams, (size_t)n_symbols, hist, value_params, width_params, threads, bytes);
     if (e == "invalid argument") return fail(err, err_cap, e);
     if (!e.empty()) return fail(err, err_cap, e, -2);
     *len = bytes.size();
@@ -345,7 +364,7 @@ int fri_tiled_decode_levels(const uint8_t *frv, size_t len, uint32_t threads, ui
     TiledInfo t;
     bool too_small = false;
     const std::string e = decode_tiled(frv, len, threads, t, coefs, coef_cap, too_small, nullptr, nullptr, (int)levels);
-    if (e == "invalid argument" || e == kNoLevels420) return fail(err, err_cap, e); // (a tiled 4:2:0 file: -1 with the reason)
+    if (e == "invalid argument" || e == kNoLevels420 || e == kNoLevelsRgba) return fail(err, err_cap, e); // (a tiled 4:2:0 or RGBA file: -1 with the reason)
     if (!e.empty()) return fail(err, err_cap, e, -2);
     fill_tiled_info(t, info);
     return too_small ? -3 : 0;
@@ -357,6 +376,7 @@ int fri_tiled_parse_coded(const uint8_t *frv, size_t len, uint32_t info[8], uint
     TiledInfo t;
     bool too_small = false;
     const std::string e = parse_tiled_coded(frv, len, t, (size_t)n_planes, too_small, words, (size_t)word_stride, n_words, models, off_values, value_params, width_params);
+    if (e == kNoCodedRgba) return fail(err, err_cap, e); // (a tiled RGBA file: -1 with the reason)
     if (!e.empty()) return fail(err, err_cap, e, -2);
     fill_tiled_info(t, info);
     return too_small ? -3 : 0;
@@ -418,7 +438,7 @@ int fri_tiled_parse_coded_tiles(const uint8_t *frv, size_t len, const uint32_t *
     bool too_small = false;
     const std::string e =
         parse_tiled_coded(frv, len, t, (size_t)n_planes, too_small, words, (size_t)word_stride, n_words, models, off_values, value_params, width_params, &tiles);
-    if (e == kBadTileList) return fail(err, err_cap, e);
+    if (e == kBadTileList || e == kNoCodedRgba) return fail(err, err_cap, e);
     if (!e.empty()) return fail(err, err_cap, e, -2);
     fill_tiled_info(t, info);
     return too_small ? -3 : 0;
@@ -441,7 +461,7 @@ int fri_tiled_update_from_streams(const uint8_t *frv, size_t len, uint32_t x, ui
                                                         needed = n, fits = out && cap >= n;
                                                         return fits ? out : nullptr; // (written straight into the caller's buffer)
                                                     });
-    if (e == "invalid region" || e == "invalid argument" || e == kNoUpdate420) return fail(err, err_cap, e);
+    if (e == "invalid region" || e == "invalid argument" || e == kNoUpdate420 || e == kNoUpdateRgba) return fail(err, err_cap, e);
     if (!e.empty()) return fail(err, err_cap, e, -2);
     tiles[0] = r.i0, tiles[1] = r.j0, tiles[2] = r.ni, tiles[3] = r.nj;
     *out_len = needed;

@@ -19,7 +19,7 @@
 //                                                            in.pam: a binary PAM (P7, DEPTH 4, MAXVAL 255, TUPLTYPE RGB_ALPHA) - RGBA: the colour as the options
 //                                                            say (--rct, --quality, --psnr, --ssim, --ycbcr; no --size / --bpp / --420), the alpha plane
 //                                                            losslessly beside it; --clean-alpha: the colour of pixels with A = 0 is coded as 0
-//                                                            --tile-size T (any mode flag but --420; no alpha): the image as a batch of independently coded tiles
+//                                                            --tile-size T (any mode flag but --420; a .pam gives tiled RGBA, which takes --rct, --quality Q or --ycbcr --quality Q, and --clean-alpha): the image as a batch of independently coded tiles
 //                                                            of about T x T (fri_hip_tile_shape), a `frit` file; --psnr / --ssim / --size search on the tiled plan
 //                                                            (fri_hip_search_quality*_tiled): the target holds for the file that is written
 //                                                            --tile-size-420 T (--quality Q | --target psnr=DB|ssim=S|size=BYTES|bpp=B) [--device-rans]: the tiles are 4:2:0 images (K12).
@@ -35,7 +35,7 @@
 //                                                            (FRIDecoder::decode_preview: fri_tiled_decode_levels + K14; with --device-rans K13 bounded by L + K14); refused with
 //                                                            --region, on a `frif` file and on a tiled 4:2:0 file, naming what to do instead
 //                                                            --region X,Y,W,H: only that rectangle of the image (FRIDecoder::decode_region) - of a `frit` file only
-//                                                            the tiles it touches are decoded; a `frif` file is decoded whole and cropped; no untiled 4:2:0 file and no alpha file
+//                                                            the tiles it touches are decoded; a `frif` file is decoded whole and cropped; no untiled 4:2:0 file and no untiled alpha file (a tiled RGBA file works)
 //   fri_driver decode-regions <in.frv> <out_prefix> --region X,Y,W,H [--region X,Y,W,H ...] [--device-rans]   several rectangles of a `frit` file in one call
 //                                                            (FRIDecoder::decode_regions: every tile a region touches is entropy-decoded once, one inverse launch, one
 //                                                            merge launch, K15); writes out_prefix.K.ppm (.pgm for one plane), K = 0, 1, ... in the order given. Regions
@@ -540,6 +540,55 @@ static int encode_image_tiled_to_file(const std::vector<uint8_t> &img, uint32_t 
     return 0;
 }
 
+// encode-file in.pam --tile-size T: tiled RGBA (libfri::encode_bytes_tiled_rgba; a `frit` file whose tiles are RGBA images). Self-check: the file decodes
+// (FRIDecoder) to an R, G, B, A raster whose alpha plane is the input's and whose colour is the direct tiled round trip (libfri::round_trip_tiled on the same
+// tile shape) of the colour raster, cleaned if --clean-alpha says so - for a lossless file that is the input itself.
+static int encode_image_tiled_rgba_to_file(const std::vector<uint8_t> &img, uint32_t w, uint32_t h, const libfri::EncoderOpts &opts, uint32_t tile_size, bool clean, const char *out_path) {
+    auto t0 = std::chrono::steady_clock::now();
+    auto enc = libfri::encode_bytes_tiled_rgba(img, h, w, opts, tile_size, clean);
+    const double t_enc = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (!enc.ok) {
+        std::fprintf(stderr, "%s\n", enc.error.c_str());
+        return 1;
+    }
+    const std::vector<uint8_t> &bytes = enc.value.bytes;
+    const size_t n_pixels = (size_t)w * h;
+    std::vector<uint8_t> colour(3 * n_pixels); // the split restated on the host
+    for (size_t i = 0; i < n_pixels; i++) {
+        const bool zero = clean && img[4 * i + 3] == 0;
+        for (int k = 0; k < 3; k++) colour[3 * i + k] = zero ? (uint8_t)0 : img[4 * i + k];
+    }
+    auto back = libfri::FRIDecoder().decode(bytes, opts);
+    if (enc.value.quality && back.ok) {
+        auto direct = libfri::round_trip_tiled(colour, h, w, 3, enc.value.tile_w, enc.value.tile_h, enc.value.quality, enc.value.rct, enc.value.ycbcr, opts.device);
+        if (!direct.ok) {
+            std::fprintf(stderr, "self-check failed: direct round trip: %s\n", direct.error.c_str());
+            return 1;
+        }
+        colour = std::move(direct.value.data);
+    }
+    bool same = back.ok && back.value.metadata.alpha && back.value.metadata.width == w && back.value.metadata.height == h && back.value.data.size() == 4 * n_pixels;
+    for (size_t i = 0; i < n_pixels && same; i++)
+        same = back.value.data[4 * i] == colour[3 * i] && back.value.data[4 * i + 1] == colour[3 * i + 1] && back.value.data[4 * i + 2] == colour[3 * i + 2] &&
+               back.value.data[4 * i + 3] == img[4 * i + 3];
+    if (!same) {
+        std::fprintf(stderr, "self-check failed: %s\n", !back.ok ? back.error.c_str() : enc.value.quality ? "decoded image differs from the direct tiled round trip, or the alpha plane is not exact"
+                                                                                                           : "the lossless file does not decode to the input");
+        return 1;
+    }
+    if (FILE *f = std::fopen(out_path, "wb")) {
+        std::fwrite(bytes.data(), 1, bytes.size(), f);
+        std::fclose(f);
+    } else {
+        std::fprintf(stderr, "cannot write %s\n", out_path);
+        return 1;
+    }
+    std::printf("%ux%ux4 RGBA in %u x %u tiles of %ux%u: %zu bytes, %.3f bits per pixel; device chain and emit %.3f s; self-check: decodes to %s, alpha exact\n", w, h, enc.value.nx,
+                enc.value.ny, enc.value.tile_w, enc.value.tile_h, bytes.size(), 8.0 * bytes.size() / ((double)w * h), t_enc, enc.value.quality ? "the direct tiled round trip" : "the input");
+    if (enc.value.quality) std::printf("quality %d%s\n", enc.value.quality, enc.value.ycbcr ? " in YCbCr" : "");
+    return 0;
+}
+
 // encode-file --tile-size-420 T (--quality Q | --target ...) [--device-rans]: the image as a batch of independently coded 4:2:0 tiles (libfri::encode_bytes_tiled420; a `frit` file whose tiles are
 // 4:2:0 images). Self-check: the file decodes (FRIDecoder) to the direct device round trip (libfri::round_trip_tiled420: K12's split, the forward kernel plane by
 // plane, fri_hip_decode_image_tiled420).
@@ -661,7 +710,7 @@ int main(int argc, char **argv) {
         uint32_t fw = 0, fh = 0, fc = 0;
         std::string err;
         if (has_suffix(argv[3], ".pam")) {
-            std::fprintf(stderr, "update-file: an RGBA image (.pam) cannot update a tiled file: alpha in tiles is out of scope (give a PGM, PPM or BMP)\n");
+            std::fprintf(stderr, "update-file: an RGBA image (.pam) cannot update a tiled file: tiled RGBA files have no region update, they are re-encoded whole (give a PGM, PPM or BMP)\n");
             return 1;
         }
         if (!(has_suffix(argv[3], ".bmp") ? read_bmp(argv[3], img, fw, fh, fc, err) : read_pnm(argv[3], img, fw, fh, fc, err))) {
@@ -720,6 +769,11 @@ int main(int argc, char **argv) {
             return 2;
         }
         const bool sized = has_size || has_bpp;
+        if (tiled && rgba && (file_opts.target_psnr > 0 || has_ssim || sized || has_target || file_opts.device_rans)) {
+            std::fprintf(stderr, "encode-file: tiled RGBA (a .pam with --tile-size T) takes --rct, --quality Q or --ycbcr --quality Q, and --clean-alpha: --psnr, --ssim, --size, --bpp, --target and "
+                                 "--device-rans are refused (the tiled RGBA plan has no searches and no device rANS route)\n");
+            return 2;
+        }
         if (has_target && !tiled420) {
             std::fprintf(stderr, "encode-file: --target psnr=DB | ssim=S | size=BYTES | bpp=B is the target of --tile-size-420 T; the other modes take --psnr, --ssim, --size and --bpp\n");
             return 2;
@@ -771,14 +825,15 @@ int main(int argc, char **argv) {
             std::fprintf(stderr, "encode-file: an RGBA image takes no --420, --size or --bpp (alpha with 4:2:0 and a size search with alpha are out of scope)\n");
             return 2;
         }
-        if (tiled && (tile_size < 1 || tile_size > 65535 || rgba || sub420)) {
-            std::fprintf(stderr, "encode-file: --tile-size T (1..65535) takes a PGM, PPM or BMP and every mode flag but --420; no alpha (alpha in tiles is out of scope; tiled 4:2:0 is --tile-size-420 T --quality Q)\n");
+        if (tiled && (tile_size < 1 || tile_size > 65535 || sub420)) {
+            std::fprintf(stderr, "encode-file: --tile-size T (1..65535) takes every mode flag but --420 (tiled 4:2:0 is --tile-size-420 T --quality Q)\n");
             return 2;
         }
         if (file_opts.device_rans && !tiled) {
             std::fprintf(stderr, "encode-file: --device-rans codes the tiles of --tile-size T or --tile-size-420 T on the device (ordinary, 4:2:0 and RGBA files are coded on the host)\n");
             return 2;
         }
+        if (tiled && rgba) return encode_image_tiled_rgba_to_file(img, fw, fh, file_opts, (uint32_t)tile_size, clean_alpha, argv[3]);
         if (tiled) return encode_image_tiled_to_file(img, fw, fh, fc, file_opts, (uint32_t)tile_size, argv[3]);
         if (rgba) return encode_image_rgba_to_file(img, fw, fh, file_opts, clean_alpha, argv[3]);
         if (sub420) return encode_image_420_to_file(img, fw, fh, file_opts, argv[3]); // (the --ycbcr checks above hold: an RGB image, a lossy target, no --rct)

@@ -475,6 +475,10 @@ struct Tiled420PlanDelete {
     void operator()(fri_hip_plan_tiled420 *p) const { fri_hip_plan_tiled420_destroy(p); }
 };
 using Tiled420Plan = std::unique_ptr<fri_hip_plan_tiled420, Tiled420PlanDelete>;
+struct TiledRgbaPlanDelete {
+    void operator()(fri_hip_plan_tiled_rgba *p) const { fri_hip_plan_tiled_rgba_destroy(p); }
+};
+using TiledRgbaPlan = std::unique_ptr<fri_hip_plan_tiled_rgba, TiledRgbaPlanDelete>;
 
 // a `frit` file: the tiles' planes from the emitter's workers, then the inverse kernel over all tiles and the merge. With a region: only the tiles it touches, on
 // both sides (emit::decode_tiled with the region, fri_hip_decode_region_tiled), and the raster is the region's. With preview_shift m >= 0 (FRIDecoder::decode_preview;
@@ -491,7 +495,7 @@ Result<RasterImage> decode_tiled_bytes(const std::vector<uint8_t> &data, const E
     const int levels = preview_shift < 0 ? -1 : 9 - 2 * preview_shift; // (-1: whole planes, 4:2:0 among them)
     std::string e = emit::decode_tiled(data.data(), data.size(), 0, ti, nullptr, 0, too_small, region, &range, levels); // header, table, geometry
     if (!e.empty()) return fail(e);
-    const size_t tile_cells = ti.s420 ? (size_t)ti.n_cells + 2 * (size_t)ti.n_cells_chroma : (size_t)ti.channels * ti.n_cells; // (4:2:0: plane order, F_y + 2 F_c per tile)
+    const size_t tile_cells = ti.s420 ? (size_t)ti.n_cells + 2 * (size_t)ti.n_cells_chroma : ((size_t)ti.channels + (ti.alpha ? 1 : 0)) * ti.n_cells; // (4:2:0: plane order, F_y + 2 F_c per tile; RGBA: plane order, 4 F)
     std::vector<int32_t> coefs((size_t)range.ni * range.nj * tile_cells * (levels < 0 ? (size_t)FRI_HIP_CELL_SIZE : (size_t)1 << levels));
     e = emit::decode_tiled(data.data(), data.size(), 0, ti, coefs.data(), coefs.size(), too_small, region, &range, levels);
     if (!e.empty() || too_small) return fail(e.empty() ? "coefficient array does not match the tile geometry" : e);
@@ -508,6 +512,27 @@ Result<RasterImage> decode_tiled_bytes(const std::vector<uint8_t> &data, const E
         r.value.data.resize((size_t)out_w * out_h * 3);
         const int rc = region ? fri_hip_decode_region_tiled420(raw420, coefs.data(), (int)ti.quality, region->x, region->y, region->w, region->h, r.value.data.data())
                               : fri_hip_decode_image_tiled420(raw420, coefs.data(), (int)ti.quality, r.value.data.data());
+        if (rc != FRI_HIP_OK) return fail(dev.describe(rc));
+        r.ok = true;
+        return r;
+    }
+    if (ti.alpha) { // RGBA tiles: the inverse kernel on the colour and the alpha batch, then K16's merge (a level-limited decode was refused above)
+        fri_hip_plan_tiled_rgba *raw_rgba = nullptr;
+        if (const int rc = fri_hip_plan_tiled_rgba_create(dev.ctx(), ti.width, ti.height, ti.tile_w, ti.tile_h, FRI_HIP_TILED_ALLOW_HOLES, &raw_rgba); rc != FRI_HIP_OK) return fail(dev.describe(rc));
+        TiledRgbaPlan plan_rgba(raw_rgba);
+        fri_hip_plan *colour = fri_hip_plan_tiled_rgba_colour(raw_rgba);
+        if (fri_hip_plan_num_cells(colour) != ti.n_cells) return fail("coefficient array does not match the tile geometry");
+        if (e = set_colour_transform(colour, ti.rct, dev, ti.ycbcr); !e.empty()) return fail(e);
+        std::array<int32_t, 32> qm = opts.quantization_matrix;
+        if (ti.quality && fri_hip_quality_matrix((int)ti.quality, qm.data()) != FRI_HIP_OK) return fail("invalid quality");
+        int rc = fri_hip_plan_set_dequantiser(colour, ti.quality ? FRI_HIP_DEQUANT_MIDPOINT : FRI_HIP_DEQUANT_REFERENCE);
+        const uint32_t out_w = region ? region->w : ti.width, out_h = region ? region->h : ti.height;
+        r.value.metadata = ImageMetadata{out_h, out_w, ColorSpace::RGB};
+        r.value.metadata.alpha = true;
+        r.value.data.resize((size_t)out_w * out_h * 4);
+        if (rc == FRI_HIP_OK)
+            rc = region ? fri_hip_decode_region_tiled_rgba(raw_rgba, coefs.data(), qm.data(), region->x, region->y, region->w, region->h, r.value.data.data())
+                        : fri_hip_decode_image_tiled_rgba(raw_rgba, coefs.data(), qm.data(), r.value.data.data());
         if (rc != FRI_HIP_OK) return fail(dev.describe(rc));
         r.ok = true;
         return r;
@@ -660,6 +685,7 @@ Result<std::vector<RasterImage>> FRIDecoder::decode_regions(const std::vector<ui
     std::vector<uint64_t> offset;
     if (std::string e = emit::parse_tiled(data.data(), data.size(), ti, offset); !e.empty()) return fail(e);
     if (ti.s420) return fail("several regions of a tiled 4:2:0 file are out of scope: decode one rectangle per call with decode_region (decode-file --region)");
+    if (ti.alpha) return fail("several regions of a tiled RGBA file are out of scope: decode one rectangle per call with decode_region (decode-file --region)");
     if (regions.empty() || regions.size() > 65535) return fail("several regions: give 1 to 65535 regions");
     std::vector<uint32_t> list, flat;
     if (!emit::regions_tiles(ti.width, ti.height, ti.tile_w, ti.tile_h, regions.data(), regions.size(), list)) return fail("invalid region");
@@ -1442,6 +1468,7 @@ Result<EncodedTiled> update_bytes_tiled(const std::vector<uint8_t> &file, const 
     std::vector<uint64_t> offset;
     if (const std::string e = emit::parse_tiled(file.data(), file.size(), ti, offset); !e.empty()) return fail(e);
     if (ti.s420) return fail(emit::kNoUpdate420);
+    if (ti.alpha) return fail(emit::kNoUpdateRgba);
     if (width != ti.width || height != ti.height)
         return fail("the image is " + std::to_string(width) + "x" + std::to_string(height) + ", the file's is " + std::to_string(ti.width) + "x" + std::to_string(ti.height) +
                     ": a region update keeps the file's size, encode an image of another size whole");
@@ -1482,6 +1509,56 @@ Result<EncodedTiled> update_bytes_tiled(const std::vector<uint8_t> &file, const 
 }
 
 // ---- tiled 4:2:0 coding ----------------------------------------------------------------------------------------------------------------------------
+Result<EncodedTiled> encode_bytes_tiled_rgba(const std::vector<uint8_t> &rgba, uint32_t height, uint32_t width, const EncoderOpts &opts, uint32_t tile_size, bool clean_alpha,
+                                             unsigned threads) {
+    Result<EncodedTiled> r;
+    auto fail = [&](const std::string &why) {
+        r.error = "Failed to decode: " + why; // sic, encoder.rs:106
+        return r;
+    };
+    std::array<int32_t, 32> qm;
+    if (const std::string e = coding_matrix(opts, qm); !e.empty()) return fail(e);
+    if (opts.target_psnr > 0 || opts.target_ssim > 0 || opts.target_bytes)
+        return fail("tiled RGBA coding has no quality or size search (target_psnr, target_ssim, target_bytes): pass a quality, or code the image untiled");
+    if (opts.device_rans) return fail("tiled RGBA coding has no device rANS route (K11 does not take alpha tiles): code it without device_rans");
+    if (!width || !height || rgba.size() != (size_t)width * height * 4) return fail("tiled RGBA coding takes width x height R, G, B, A pixels");
+    uint32_t tw = 0, th = 0;
+    if (const int rc = fri_hip_tile_shape(width, height, tile_size, &tw, &th); rc != FRI_HIP_OK)
+        return fail(std::string("no tile shape of that size owns every pixel: ") + fri_hip_strerror(rc));
+    Device dev(opts.device);
+    if (!dev.ok()) return fail(dev.error());
+    fri_hip_plan_tiled_rgba *raw = nullptr;
+    if (const int rc = fri_hip_plan_tiled_rgba_create(dev.ctx(), width, height, tw, th, 0, &raw); rc != FRI_HIP_OK) return fail(dev.describe(rc));
+    TiledRgbaPlan plan(raw);
+    fri_hip_plan *colour = fri_hip_plan_tiled_rgba_colour(raw), *alpha = fri_hip_plan_tiled_rgba_alpha(raw);
+    for (fri_hip_plan *inner : {colour, alpha})
+        if (const std::string e = set_plan_stream_order(inner, dev); !e.empty()) return fail(e);
+    const ImageMetadata md = coded_metadata(height, width, ColorSpace::RGB, opts);
+    if (const std::string e = set_colour_transform(colour, md.rct, dev, md.ycbcr); !e.empty()) return fail(e);
+    uint32_t grid[4];
+    fri_hip_plan_tiled_rgba_grid(raw, grid);
+    r.value.tile_w = tw, r.value.tile_h = th, r.value.nx = grid[0], r.value.ny = grid[1];
+    const size_t planes = 4 * (size_t)grid[0] * grid[1]; // plane order: the colour planes tile by tile, then the alpha planes
+    const uint64_t n = fri_hip_plan_num_some(colour);
+    std::vector<uint16_t> symbols(planes * (size_t)n);
+    std::vector<uint32_t> hist(planes * CONTEXT_AMOUNT * ALPHABET_SIZE);
+    std::vector<float> vp(planes * 18), wp(planes * 18);
+    std::vector<uint64_t> oob(planes, 0);
+    if (const int rc = fri_hip_encode_image_tiled_rgba_symbols(raw, rgba.data(), clean_alpha ? FRI_HIP_ALPHA_CLEAN : FRI_HIP_ALPHA_KEEP, qm.data(), vp.data(), wp.data(),
+                                                               symbols.data(), hist.data(), oob.data());
+        rc != FRI_HIP_OK)
+        return fail(dev.describe(rc));
+    for (uint64_t v : oob)
+        if (v) return fail("symbol outside the 1024-entry alphabet"); // the reference panics: bump_freq, entropy_coding.rs:99
+    if (const std::string e = emit::encode_tiled_from_streams_rgba(width, height, tw, th, md.rct, md.quality, md.ycbcr, symbols.data(), (size_t)n, hist.data(), vp.data(), wp.data(),
+                                                                   threads, r.value.bytes);
+        !e.empty())
+        return fail(e);
+    r.value.quality = (int)md.quality, r.value.rct = md.rct, r.value.ycbcr = md.ycbcr;
+    r.ok = true;
+    return r;
+}
+
 Result<EncodedTiled> encode_bytes_tiled420(const std::vector<uint8_t> &rgb, uint32_t height, uint32_t width, int quality, uint32_t tile_size, int device, unsigned threads) {
     EncoderOpts opts;
     opts.quality = quality, opts.device = device;

@@ -313,17 +313,27 @@ Result<EncodedTiled> encode_bytes_tiled420(const std::vector<uint8_t> &rgb, uint
 // fri_hip_decode_image_tiled420 - what such a file decodes to.
 Result<RasterImage> round_trip_tiled420(const std::vector<uint8_t> &rgb, uint32_t height, uint32_t width, uint32_t tile_w, uint32_t tile_h, int quality, int device = 0);
 
+// Tiled RGBA coding (include/fri_hip.h, "Tiled RGBA coding") of width x height R, G, B, A pixels: tiles of about tile_size x tile_size whose lattice owns every
+// pixel (fri_hip_tile_shape), the device splits them (K16) and codes the colour and the alpha batch (fri_hip_encode_image_tiled_rgba_symbols), the emitter codes
+// them on `threads` workers (emit::encode_tiled_from_streams_rgba). The colour is coded as opts says - lossless (plain or colour_transform) or lossy in RGB or
+// YCbCr at opts.quality - and the alpha plane losslessly, always. clean_alpha: FRI_HIP_ALPHA_CLEAN. The targets (target_psnr, target_ssim, target_bytes) and
+// device_rans are refused: the tiled RGBA plan has no searches and no K11 route. FRIDecoder::decode and decode_region read such files.
+Result<EncodedTiled> encode_bytes_tiled_rgba(const std::vector<uint8_t> &rgba, uint32_t height, uint32_t width, const EncoderOpts &opts, uint32_t tile_size, bool clean_alpha = false,
+                                             unsigned threads = 0);
+
 class FRIDecoder { // decoder.rs:44-59
   public:
     // the whole pipeline of decoder.rs:16-40: EncodedImage -> EntropyDecoding -> Dequantization -> WaveletTransform -> RawImage.
     // Container parsing and entropy decoding run on the host, dequantisation + inverse transform on the device. A tiled file (`frit`) is recognised by its magic:
-    // fri_tiled_decode's workers, then fri_hip_decode_image_tiled - or, for a tiled 4:2:0 file, fri_hip_decode_image_tiled420. With opts.device_rans the tiles'
+    // fri_tiled_decode's workers, then fri_hip_decode_image_tiled - or, for a tiled 4:2:0 file, fri_hip_decode_image_tiled420, for a tiled RGBA file fri_hip_decode_image_tiled_rgba (a raster of
+    // R, G, B, A, metadata.alpha set; the device decoder does not take such files). With opts.device_rans the tiles'
     // planes are decoded on the device instead (fri_tiled_parse_coded, then fri_hip_decode_image_tiled_coded / _tiled420_coded).
     Result<RasterImage> decode(const std::vector<uint8_t> &data, const EncoderOpts &opts = EncoderOpts());
     // The region x, y, w, h (image pixels; include/fri_emit.h, "Region decode") of the image `data` holds: the crop [y : y + h, x : x + w] of what decode returns,
     // as a raster of w x h. A tiled file pays for the tiles the region touches and no others: fri_tiled_decode_region's workers, then
     // fri_hip_decode_region_tiled. An ordinary `frif` file has no tiles: it is decoded whole and cropped on the host, which buys nothing and only makes the call
-    // work on any file. Untiled 4:2:0 files and alpha files are refused; a tiled 4:2:0 file goes through fri_hip_decode_region_tiled420.
+    // work on any file. Untiled 4:2:0 files and alpha files are refused; a tiled 4:2:0 file goes through fri_hip_decode_region_tiled420, a tiled
+    // RGBA file through fri_hip_decode_region_tiled_rgba.
     Result<RasterImage> decode_region(const std::vector<uint8_t> &data, uint32_t x, uint32_t y, uint32_t w, uint32_t h, const EncoderOpts &opts = EncoderOpts());
     // Several regions of a tiled file in one call (include/fri_emit.h, "Several regions"): one image per region, region r the crop [y : y + h, x : x + w] of what
     // decode returns. The container is walked once and every tile that at least one region touches is entropy-decoded once - fri_tiled_decode_tiles's workers - then

@@ -69,9 +69,9 @@
  *            32  u64 offset[ny nx + 1]
  * The payloads follow the table: tile t = j nx + i is the bytes [offset[t], offset[t + 1]). offset[0] = 32 + 8 (ny nx + 1), offset[ny nx] is the file length and
  * the offsets are strictly increasing. A payload is a complete `frif` file of a tile_h x tile_w image: exactly what fri_emit_encode_image_from_streams writes
- * for that tile's streams, histograms and parameters with FRI_EMIT_EMPTY_OK set. All tiles carry the same metadata word. Alpha inside tiles is refused, by
- * the encoder (-1) and by the decoder ("Malformed tiled image"); 4:2:0 inside tiles is "Tiled 4:2:0" below: fri_tiled_encode_from_streams and
- * fri_tiled_encode_from_coded keep refusing FRI_EMIT_420 (-1), such files have encoders of their own. fri_emit_decode_image does not know the magic: a `frit` file is "Invalid signature"
+ * for that tile's streams, histograms and parameters with FRI_EMIT_EMPTY_OK set. All tiles carry the same metadata word. 4:2:0 inside tiles is "Tiled 4:2:0" and
+ * alpha inside tiles "Tiled RGBA" below: fri_tiled_encode_from_streams and fri_tiled_encode_from_coded keep refusing FRI_EMIT_420 and FRI_EMIT_ALPHA (-1), such
+ * files have encoders of their own. fri_emit_decode_image does not know the magic: a `frit` file is "Invalid signature"
  * to it. The size of such a file is estimated from the tiles' histograms, without the coder, by fri_hip_estimate_size_tiled_dev (include/fri_hip.h; fri_hip_estimate_size_tiled420_dev for tiled 4:2:0),
  * which knows the rule of FRI_EMIT_EMPTY_OK.
  *
@@ -133,8 +133,25 @@
  *                 [3 n][10][1024]; parameters [3 n][3][6]. n_y, F_y are the tile_w x tile_h lattice's (C = 1), n_c, F_c the cw x ch lattice's.
  *   region        a region's sub-grid (ni nj tiles, the arithmetic of "Region decode" unchanged) uses the same order with n = ni nj.
  * fri_tiled_info, fri_tiled_decode and fri_tiled_decode_region accept such files: info[6] carries FRI_EMIT_420, info[7] stays F_y, the coefficients come back in
- * plane order and the needed element count is n (F_y + 2 F_c) x 512. A file whose tiles have bit 2 without bit 1, or with bit 0, and every alpha payload stays
- * "Malformed tiled image". */
+ * plane order and the needed element count is n (F_y + 2 F_c) x 512. A file whose tiles have bit 2 without bit 1, or with bit 0, or with bit 3, stays "Malformed tiled
+ * image".
+ *
+ * Tiled RGBA (fri_tiled_encode_from_streams_rgba below; include/fri_hip.h, "Tiled RGBA coding", has the device side): the `frit` container is unchanged and stays
+ * at version 1. A tiled RGBA file is a `frit` file whose payloads are alpha files: payload t is exactly what fri_emit_encode_image_from_streams writes for a
+ * tile_h x tile_w image with 3 | FRI_EMIT_ALPHA | <colour flags> | FRI_EMIT_EMPTY_OK, the colour flags being none, FRI_EMIT_RCT, FRI_EMIT_QUALITY(q) or
+ * FRI_EMIT_YCBCR | FRI_EMIT_QUALITY(q). All tiles carry the same metadata word; bit 3 is set; bits 2 and 3 together stay "Malformed tiled image"; bit 3 of a Luma
+ * tile is ignored, as in a `frif` file.
+ *   tile          the tile of "tiled coding" of the R, G, B, A image [H][W][4]: the same grid and edge replication, for all four channels.
+ *   plane order   one rule for every per-plane array of n = nx ny tiles, the colour batch first:
+ *                     plane(t, c) = 3 t + c for c = 0, 1, 2        plane(t, A) = 3 n + t
+ *   arrays        symbols [n][3][n_some], then [n][n_some], in one buffer; coefficients [n][3][F][512], then [n][F][512], in one buffer; histograms
+ *                 [4 n][10][1024]; parameters [4 n][3][6]. n_some and F are the tile_w x tile_h lattice's, the same for all four channels.
+ *   region        a region's sub-grid (the arithmetic of "Region decode" unchanged) or a tile list uses the same order with n = ni nj or n = T.
+ * fri_tiled_info, fri_tiled_decode, fri_tiled_decode_region and fri_tiled_decode_tiles accept such files: info[6] carries FRI_EMIT_ALPHA (its channel count stays
+ * 3), the coefficients come back in plane order and the needed element count is 4 n F x 512. A payload that does not have four channels is "Malformed tiled
+ * image". fri_tiled_decode_levels, fri_tiled_parse_coded, fri_tiled_parse_coded_tiles and fri_tiled_update_from_streams refuse such a file: -1, and `err` names
+ * tiled RGBA.
+ * Out of scope: preview, the coded forms (K11, K13), several regions on the device and region update of tiled RGBA files; alpha with 4:2:0. */
 #define FRI_EMIT_EMPTY_OK 0x2000u
 #define FRI_EMIT_RCT 0x100u
 #define FRI_EMIT_YCBCR 0x400u
@@ -219,7 +236,15 @@ int fri_tiled_encode_from_streams(uint32_t width, uint32_t height, uint32_t tile
 int fri_tiled_encode_from_streams420(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t channels, const uint16_t *streams, uint64_t n_luma,
                                      uint64_t n_chroma, const uint32_t *hist, const float *value_params, const float *width_params, uint32_t threads, uint8_t *out, size_t cap,
                                      size_t *len, char *err, size_t err_cap);
-/* The same file from planes the device coded (K11: fri_hip_rans_encode_planes_dev / fri_hip_encode_image_tiled_coded, include/fri_hip.h, which defines the layouts): the
+/* A tiled RGBA file ("Tiled RGBA" above) from the arrays fri_hip_encode_image_tiled_rgba_symbols returns, all in plane order: streams [n][3][n_symbols] then
+ * [n][n_symbols] u16, hist [4 n][10][1024], value_params / width_params [4 n][3][6]. `channels` must be 3 | FRI_EMIT_ALPHA, alone or with FRI_EMIT_RCT,
+ * FRI_EMIT_QUALITY(q) or FRI_EMIT_YCBCR | FRI_EMIT_QUALITY(q), with or without FRI_EMIT_EMPTY_OK (always in force) - anything else, FRI_EMIT_420 among it, -1.
+ * n_symbols must be the symbol count of the tile_w x tile_h lattice (-2 otherwise). Tiles are coded on `threads` workers through the per-tile path of
+ * fri_tiled_encode_from_streams; the bytes are the same for every thread count. Sizes and errors as there: 0 and *len, or -3 with *len = needed size. */
+int fri_tiled_encode_from_streams_rgba(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t channels, const uint16_t *streams, uint64_t n_symbols,
+                                       const uint32_t *hist, const float *value_params, const float *width_params, uint32_t threads, uint8_t *out, size_t cap, size_t *len, char *err,
+                                       size_t err_cap);
+/* fri_tiled_encode_from_streams's file from planes the device coded (K11: fri_hip_rans_encode_planes_dev / fri_hip_encode_image_tiled_coded, include/fri_hip.h, which defines the layouts): the
  * arguments of fri_tiled_encode_from_streams with the coded planes in the place of the streams and histograms. words uint32 [n_tiles C][word_stride]: the first
  * n_words[p] of plane p are its rANS data as little-endian words (at least 20, at most word_stride, -2 otherwise); models uint32 [n_tiles C][10][4], of which
  * {max_freq_bits, n_off} are read; off_values uint16 [n_tiles C][10][1024], of which a context's first n_off (<= 1024) are read. Nothing is coded here: the
@@ -247,7 +272,7 @@ int fri_tiled_info(const uint8_t *frv, size_t len, uint32_t info[8]);
  * payload's height, width and metadata word against the header and tile 0: a mismatch - and any file that is not a `frit` file, a `frif` file among them -
  * returns "Malformed tiled image" (-2). Tiles are decoded on `threads` workers (0 as above) that share one geometry and one symbol order. Returns -3 with `info`
  * filled when coefs is NULL or coef_cap (in elements) is too small. A tiled 4:2:0 file: coefs in plane order, n (F_y + 2 F_c) x 512 elements - what
- * fri_hip_decode_image_tiled420 takes. */
+ * fri_hip_decode_image_tiled420 takes. A tiled RGBA file: coefs in plane order, 4 n F x 512 elements - what fri_hip_decode_image_tiled_rgba takes. */
 int fri_tiled_decode(const uint8_t *frv, size_t len, uint32_t threads, uint32_t info[8], int32_t *coefs, size_t coef_cap, char *err, size_t err_cap);
 /* Preview decode: fri_tiled_decode stopped at a level. `levels` L is 0..9: the nodes with heap index < 2^L are decoded - L = 0 the DC alone, L = 1 DC and root,
  * L = 9 everything. A channel's stream is ten scans - DC, root, levels 1..8 - and the context of a symbol reads its own level and its parents only, so these
@@ -255,7 +280,7 @@ int fri_tiled_decode(const uint8_t *frv, size_t len, uint32_t threads, uint32_t 
  * seen nor reported. The result is COMPACT planes, coefs [n_tiles][C][F][2^L] int32: node h of cell c at c 2^L + h, None = INT32_MIN, a Some node always
  * decoded - fri_tiled_decode's planes sliced to [..., :2^L], for every thread count; what fri_hip_preview_image_tiled (include/fri_hip.h) takes. Parsing, refusals,
  * workers and the size query (-3 with `info` filled when coefs is NULL or coef_cap, in elements, is too small) are fri_tiled_decode's. -1 for levels > 9 and, with
- * a message that names fri_tiled_decode, for a tiled 4:2:0 file, whose chroma lattice is a level pair of its own. */
+ * a message that names fri_tiled_decode, for a tiled 4:2:0 file, whose chroma lattice is a level pair of its own, and for a tiled RGBA file (the message names tiled RGBA). */
 int fri_tiled_decode_levels(const uint8_t *frv, size_t len, uint32_t threads, uint32_t levels, uint32_t info[8], int32_t *coefs, size_t coef_cap, char *err, size_t err_cap);
 /* A `frit` file back to the coded planes it is made of: the inverse of fri_tiled_encode_from_coded and fri_tiled_encode_from_coded420, and what the device decoder
  * reads (K13: fri_hip_decode_planes_dev, fri_hip_decode_image_tiled_coded, include/fri_hip.h). One function for both kinds of file; P = n_tiles C planes in the
@@ -266,7 +291,7 @@ int fri_tiled_decode_levels(const uint8_t *frv, size_t len, uint32_t threads, ui
  * Checks what fri_tiled_decode checks - the header, the table, every payload's 16-byte header, the markers of every payload - and `info` is fri_tiled_info's;
  * builds no model and decodes nothing, on the calling thread. Returns -3 with `info` filled when n_words is NULL or n_planes < P. With words == NULL only `info` and
  * n_words are filled (0): the size query for word_stride. A plane with n_words[p] > word_stride is an error that names the first such plane (-2), with n_words
- * complete; planes that fit are written. */
+ * complete; planes that fit are written. -1 for a tiled RGBA file (the message names tiled RGBA): it has no coded form. */
 int fri_tiled_parse_coded(const uint8_t *frv, size_t len, uint32_t info[8], uint64_t n_planes, uint32_t *words, uint64_t word_stride, uint32_t *n_words, uint32_t *models,
                           uint16_t *off_values, float *value_params, float *width_params, char *err, size_t err_cap);
 /* The tile range of a region ("Region decode" above): out = {i0, j0, ni, nj} by that arithmetic and nothing else. -1 for a zero size (of the image, the tile or
@@ -303,7 +328,7 @@ int fri_tiled_parse_coded_tiles(const uint8_t *frv, size_t len, const uint32_t *
  * fri_tiled_encode_from_streams takes (flags + quality, FRI_EMIT_EMPTY_OK always in force) and must produce the metadata word of tile 0. The touched tiles are
  * coded on `threads` workers through the same per-tile path as fri_tiled_encode_from_streams, the bytes are the same for every thread count; the other payloads
  * are copied and not looked into, so damage inside their bodies is copied, not reported. -1 for a region fri_tiled_region_tiles refuses ("invalid region"), for
- * FRI_EMIT_420 / FRI_EMIT_ALPHA and for a tiled 4:2:0 file (the message says tiled 4:2:0 files are re-encoded whole); -2 for anything that is not a well-formed
+ * FRI_EMIT_420 / FRI_EMIT_ALPHA and for a tiled 4:2:0 or tiled RGBA file (the message says such files are re-encoded whole); -2 for anything that is not a well-formed
  * `frit` file (a `frif` file among them), a wrong n_symbols, a metadata word that differs from tile 0's, or a tile's error ("tile t: channel c: reason", t in the
  * file's grid). Returns 0 with *out_len and tiles = {i0, j0, ni, nj}, or -3 with *out_len = the needed size and `tiles` filled when out is NULL or cap is too
  * small. The size is exact because the touched tiles are coded before it is known: a size query codes them, and the call that follows codes them again. */

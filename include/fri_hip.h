@@ -622,15 +622,15 @@ int fri_hip_decode_image_rgba(fri_hip_plan_rgba *p, const int32_t *coefs, const 
  * (owned by p) for the getters, fri_hip_plan_set_colour_transform, fri_hip_plan_set_dequantiser and fri_hip_plan_set_stream_order, which the encodes need and
  * create does not do. fri_hip_plan_tiled_grid: out[4] = {nx, ny, tile_w, tile_h}. The plan owns the tile staging buffers: calls on one fri_hip_plan_tiled must
  * be ordered on one stream, as for fri_hip_plan_rgba.
- * Out of scope: per-tile qualities (all tiles of a file carry one metadata word: one quality per file, which is what the searches below return), alpha in
- * tiles, multi-GPU forms. 4:2:0 in tiles is a plan of its own: "Tiled 4:2:0 coding" below.
+ * Out of scope: per-tile qualities (all tiles of a file carry one metadata word: one quality per file, which is what the searches below return),
+ * multi-GPU forms. 4:2:0 in tiles and alpha in tiles are plans of their own: "Tiled 4:2:0 coding" and "Tiled RGBA coding" below.
  * Region decode: a region x, y, w, h in image pixels (w, h >= 1, x + w <= W, y + h <= H, compared in 64 bits) touches the sub-grid of ni x nj tiles from column
  * i0 = x / tile_w and row j0 = y / tile_h, ni = (x + w - 1) / tile_w - i0 + 1, nj = (y + h - 1) / tile_h - j0 + 1, stored row-major: sub-tile s = b ni + a is
  * tile (j0 + b) nx + (i0 + a). The region raster is [h][w][C] without a pitch: pixel (ry, rx) is image pixel (y + ry, x + rx), which is pixel
  * (y + ry - j tile_h, x + rx - i tile_w) of tile (j, i); no replicated pixel is ever copied. By definition it is the crop [y : y + h, x : x + w] of what
  * fri_hip_decode_image_tiled returns for the same file. Only the touched tiles are entropy-decoded (fri_tiled_decode_region, include/fri_emit.h), inverted and
- * copied, and the plan's buffers grow to the region's size, never to the image's. Out of scope: regions of untiled 4:2:0 files and of alpha files; a region
- * of a tiled 4:2:0 file is fri_hip_decode_region_tiled420 below; several regions in one call are "Several regions" below. */
+ * copied, and the plan's buffers grow to the region's size, never to the image's. Out of scope: regions of untiled 4:2:0 files and of untiled alpha files; a
+ * region of a tiled 4:2:0 file is fri_hip_decode_region_tiled420 below, of a tiled RGBA file fri_hip_decode_region_tiled_rgba; several regions in one call are "Several regions" below. */
 #define FRI_HIP_TILED_ALLOW_HOLES 1u
 typedef struct fri_hip_plan_tiled fri_hip_plan_tiled;
 uint64_t fri_hip_plan_owned_pixels(const fri_hip_plan *plan);
@@ -841,7 +841,7 @@ int fri_hip_search_quality_for_size_tiled_dev(fri_hip_plan_tiled *p, const uint8
  * fri_hip_decode_region_tiled420 / _dev: the same for the sub-grid's planes (what fri_tiled_decode_region returns; d_coefs in device memory) -> the region raster
  * [h][w][3]. The plan's tile buffers grow to the region's tiles only. The _dev form refuses a capturing stream (FRI_HIP_ERR_INVALID_ARGUMENT) before anything is
  * enqueued or allocated. FRI_HIP_ERR_INVALID_ARGUMENT for a NULL pointer, a quality outside 1..99 or a region that is empty or leaves the image.
- * Out of scope: alpha in tiles; per-tile qualities; multi-GPU forms. */
+ * Out of scope: alpha with 4:2:0 (tiled RGBA tiles are 4:4:4: "Tiled RGBA coding" below); per-tile qualities; multi-GPU forms. */
 typedef struct fri_hip_plan_tiled420 fri_hip_plan_tiled420;
 int fri_hip_tile_shape420(uint32_t width, uint32_t height, uint32_t target, uint32_t *tile_w, uint32_t *tile_h);
 int fri_hip_plan_tiled420_create(fri_hip_ctx *ctx, uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t flags, fri_hip_plan_tiled420 **out);
@@ -901,6 +901,80 @@ int fri_hip_search_quality_ssim_tiled420(fri_hip_plan_tiled420 *p, const uint8_t
 int fri_hip_search_quality_ssim_tiled420_dev(fri_hip_plan_tiled420 *p, const uint8_t *d_pixels, double target, int32_t *quality, double *ssim, void *stream);
 int fri_hip_search_quality_for_size_tiled420(fri_hip_plan_tiled420 *p, const uint8_t *pixels, uint64_t max_bytes, int32_t *quality, uint64_t *est_bytes);
 int fri_hip_search_quality_for_size_tiled420_dev(fri_hip_plan_tiled420 *p, const uint8_t *d_pixels, uint64_t max_bytes, int32_t *quality, uint64_t *est_bytes, void *stream);
+
+/* ---- Tiled RGBA coding: alpha in tiles ------------------------------------------------------------- */
+/* Tiled coding and RGBA together: every tile of a `frit` file (include/fri_emit.h; the container is unchanged, version 1) is an RGBA image. Part of the file
+ * format. In a tiled RGBA file every payload is a `frif` file of a tile_h x tile_w image with four channels: exactly what fri_emit_encode_image_from_streams
+ * writes for that tile with 3 | FRI_EMIT_ALPHA | <colour flags> | FRI_EMIT_EMPTY_OK, the colour flags being none, FRI_EMIT_RCT, FRI_EMIT_QUALITY(q) or
+ * FRI_EMIT_YCBCR | FRI_EMIT_QUALITY(q). All tiles carry the same metadata word, as in every `frit` file; bit 3 is set, bits 2 and 3 together stay malformed,
+ * and bit 3 of a Luma tile is ignored as in a `frif` file.
+ * The image is W x H interleaved R, G, B, A bytes, [H][W][4], without a row pitch; n = nx ny tiles on the grid of "tiled coding", t = j nx + i.
+ *   split         with gy = min(j tile_h + y, H - 1) and gx = min(i tile_w + x, W - 1): alpha(t, y, x) = image(gy, gx, 3); colour(t, y, x, c) = image(gy, gx, c)
+ *                 for c < 3, and with FRI_HIP_ALPHA_CLEAN 0 where image(gy, gx, 3) == 0. By definition the colour tile raster [n][tile_h][tile_w][3] is
+ *                 fri_hip_split_tiles_dev of the colour raster fri_hip_split_rgba_dev produces, and the alpha tile raster [n][tile_h][tile_w] the same of the
+ *                 alpha plane.
+ *   merge/region  the region raster is [h][w][4] without a pitch: pixel (ry, rx) is image pixel (y + ry, x + rx), R, G, B from the colour tile that owns it
+ *                 and A from the alpha tile. No replicated pixel is ever read. The sub-grid arithmetic is that of "Region decode" above, unchanged; the whole
+ *                 merge is the region (0, 0, W, H) over the whole grid.
+ *   plane order   one rule covers every per-plane array - the colour batch first, as in "Tiled 4:2:0 coding":
+ *                     plane(t, c) = 3 t + c for c = 0, 1, 2        plane(t, A) = 3 n + t
+ *                 (the colour batch lies back to back because fri_hip_encode_symbols_batch_dev with C = 3 needs symbol_stride == 3 num_some).
+ *   arrays        in plane order. Symbols: [n][3][n_some], then [n][n_some], in one buffer. Coefficients: [n][3][F][512], then [n][F][512], in one buffer.
+ *                 Histograms: [4 n][10][1024]. Value / width parameters: [4 n][3][6]; device parameters: [4 n][2][3][6]. Out-of-alphabet and fit-out-of-range
+ *                 counts: [4 n]. n_some and F = fri_hip_plan_num_some and fri_hip_plan_num_cells of the inner plans, equal for the two.
+ *   region        a region's sub-grid or a tile list uses the same order with n = ni nj or n = T.
+ *   alpha plane   always coded with the all-ones matrix and decoded with FRI_HIP_DEQUANT_REFERENCE, whatever the caller set on the plans, as in "RGBA" above.
+ * fri_hip_plan_tiled_rgba_create: refuses (FRI_HIP_ERR_INVALID_ARGUMENT) zero sizes, unknown flag bits, 3 nx ny > 65535 (one batch launch takes all colour
+ * planes), inner plans whose lattices differ (the check of fri_hip_plan_rgba_create) and - without FRI_HIP_TILED_ALLOW_HOLES - a tile shape whose lattice does
+ * not own all tile_w tile_h pixels. The tile-shape rule is fri_hip_tile_shape: the lattice is the same. ctx may be NULL: the plan is then host-only (the getters
+ * work, compute returns FRI_HIP_ERR_NO_DEVICE). The plan owns two ordinary plans of the tile's shape - fri_hip_plan_tiled_rgba_colour (C = 3) and _alpha
+ * (C = 1), for the getters, fri_hip_plan_set_colour_transform and fri_hip_plan_set_dequantiser on the colour plan and fri_hip_plan_set_stream_order, which the
+ * encodes need on both and create does not do - and the staging buffers: calls on one plan must be ordered on one stream.
+ * fri_hip_plan_tiled_rgba_grid: out[4] = {nx, ny, tile_w, tile_h}. fri_hip_plan_tiled_rgba_region: out[4] = {i0, j0, ni, nj}; both work on host-only plans.
+ * fri_hip_plan_tiled_rgba_buffer_tiles (diagnostics): out[2] = the tiles the plan's colour and alpha tile buffers hold room for at the moment.
+ * The raster kernels (K16, k16_tiles_rgba.hip), any pointer alignment; they only enqueue on `stream` and can be captured into a graph. `clean` is
+ * FRI_HIP_ALPHA_KEEP or FRI_HIP_ALPHA_CLEAN, anything else FRI_HIP_ERR_INVALID_ARGUMENT:
+ *   fri_hip_split_tiles_rgba_dev          d_rgba [H][W][4] -> d_colour_tiles, d_alpha_tiles in one pass.
+ *   fri_hip_merge_tiles_rgba_region_dev   a sub-grid's d_colour_tiles, d_alpha_tiles -> d_region [h][w][4]. Nothing outside the region raster is written.
+ *   fri_hip_merge_tiles_rgba_dev          the same kernel with the region (0, 0, W, H) on the full grid.
+ * fri_hip_encode_symbols_tiled_rgba_dev: everything in device memory and on `stream`, nothing but enqueues - the split into the plan's buffers, then
+ * fri_hip_encode_symbols_batch_dev in its direct form (d_coefs = NULL, d_node_words = NULL) twice: on the colour plan over n images with `qmatrix`, on the alpha
+ * plan over n images with the all-ones matrix. Both inner plans need their stream order; a capturing stream is refused before anything is enqueued or allocated.
+ * fit = 0 reads every plane's parameters from d_params. Outputs in plane order: d_symbols, d_params [4 n][2][3][6], d_hist, d_n_out_of_alphabet,
+ * d_fit_out_of_range (may be NULL).
+ * fri_hip_encode_image_tiled_rgba_symbols: the host form - the pixels are staged, the call above runs with the fit on, everything is read back: what
+ * fri_tiled_encode_from_streams_rgba (include/fri_emit.h) takes. value_params / width_params [4 n][3][6]. Synchronous. FRI_HIP_ERR_OUT_OF_RANGE as in
+ * fri_hip_encode_image.
+ * fri_hip_decode_image_tiled_rgba: coefs in plane order (what fri_tiled_decode returns for such a file) -> pixels [H][W][4]: the inverse kernel on the colour
+ * batch with `qmatrix` and the colour transform and dequantiser set on the colour plan; on the alpha batch with ones and FRI_HIP_DEQUANT_REFERENCE, whatever is
+ * set on the alpha plan - that setting is restored afterwards; then the merge. Synchronous.
+ * fri_hip_decode_region_tiled_rgba / _dev: the same for the sub-grid's planes (what fri_tiled_decode_region returns; d_coefs in device memory) -> the region
+ * raster [h][w][4]. The plan's tile buffers grow to the region's tiles, never to the image's. The _dev form refuses a capturing stream
+ * (FRI_HIP_ERR_INVALID_ARGUMENT) before anything is enqueued or allocated. FRI_HIP_ERR_INVALID_ARGUMENT for a NULL pointer or a region that is empty or leaves
+ * the image.
+ * Out of scope: the quality and size searches and the size estimate on this plan; the device coders (K11, K13); preview, several regions and region update of
+ * tiled RGBA files; alpha with 4:2:0; per-tile qualities; multi-GPU forms. */
+typedef struct fri_hip_plan_tiled_rgba fri_hip_plan_tiled_rgba;
+int fri_hip_plan_tiled_rgba_create(fri_hip_ctx *ctx, uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t flags, fri_hip_plan_tiled_rgba **out);
+int fri_hip_plan_tiled_rgba_destroy(fri_hip_plan_tiled_rgba *p);
+fri_hip_plan *fri_hip_plan_tiled_rgba_colour(fri_hip_plan_tiled_rgba *p);
+fri_hip_plan *fri_hip_plan_tiled_rgba_alpha(fri_hip_plan_tiled_rgba *p);
+int fri_hip_plan_tiled_rgba_grid(const fri_hip_plan_tiled_rgba *p, uint32_t out[4]);
+int fri_hip_plan_tiled_rgba_region(const fri_hip_plan_tiled_rgba *p, uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint32_t out[4]);
+int fri_hip_plan_tiled_rgba_buffer_tiles(const fri_hip_plan_tiled_rgba *p, uint64_t out[2]);
+int fri_hip_split_tiles_rgba_dev(fri_hip_plan_tiled_rgba *p, const uint8_t *d_rgba, int clean, uint8_t *d_colour_tiles, uint8_t *d_alpha_tiles, void *stream);
+int fri_hip_merge_tiles_rgba_dev(fri_hip_plan_tiled_rgba *p, const uint8_t *d_colour_tiles, const uint8_t *d_alpha_tiles, uint8_t *d_rgba, void *stream);
+int fri_hip_merge_tiles_rgba_region_dev(fri_hip_plan_tiled_rgba *p, const uint8_t *d_colour_tiles, const uint8_t *d_alpha_tiles, uint32_t x, uint32_t y, uint32_t w, uint32_t h,
+                                        uint8_t *d_region, void *stream);
+int fri_hip_encode_symbols_tiled_rgba_dev(fri_hip_plan_tiled_rgba *p, const uint8_t *d_rgba, int clean, const int32_t qmatrix[32], int fit, float *d_params, uint16_t *d_symbols,
+                                          uint32_t *d_hist, uint64_t *d_n_out_of_alphabet, uint64_t *d_fit_out_of_range, void *stream);
+int fri_hip_encode_image_tiled_rgba_symbols(fri_hip_plan_tiled_rgba *p, const uint8_t *pixels, int clean, const int32_t qmatrix[32], float *value_params, float *width_params,
+                                            uint16_t *symbols, uint32_t *hist, uint64_t *n_out_of_alphabet);
+int fri_hip_decode_image_tiled_rgba(fri_hip_plan_tiled_rgba *p, const int32_t *coefs, const int32_t qmatrix[32], uint8_t *pixels);
+int fri_hip_decode_region_tiled_rgba_dev(fri_hip_plan_tiled_rgba *p, const int32_t *d_coefs, const int32_t qmatrix[32], uint32_t x, uint32_t y, uint32_t w, uint32_t h,
+                                         uint8_t *d_region, void *stream);
+int fri_hip_decode_region_tiled_rgba(fri_hip_plan_tiled_rgba *p, const int32_t *coefs, const int32_t qmatrix[32], uint32_t x, uint32_t y, uint32_t w, uint32_t h,
+                                     uint8_t *pixels);
 
 /* ---- the rANS coder on the device (K11, k11_rans.hip) ------------------------------------------- */
 /* The emitter's last stage - symbols to rANS words (host/emit.cpp, encode_symbols) - for a batch of planes, a plane being one channel of one tile or of an
