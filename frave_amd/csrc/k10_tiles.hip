@@ -13,15 +13,19 @@
 // such row. Away from the clamped edge those are 16 consecutive bytes of one image row: one 16-byte load and one 16-byte store, the target's unaligned global
 // accesses (the compiler is told the alignment is 1), so both buffers start at any byte. A strip that reaches past the image row (the replicated edge) and a
 // row's last, partial strip go byte by byte. Every byte offset is 64-bit: W H C can pass 2^32.
+//
+// Where a region's or a sub-grid's strip lies (strip_of, region_strip_of), the unaligned accesses and measure_add are raster_common.hpp's, shared with K12, K15 and K16; the
+// shape's limits, the region check with its sub-grid and the strips-per-lane rule are raster_launch.hpp's.
 #include <algorithm>
 
-#include "device_common.hpp"
+#include "raster_common.hpp"
+#include "raster_launch.hpp"
 
 namespace fri {
 namespace {
 
-constexpr int kTileThreads = 256;
-constexpr uint32_t kTileStrip = 16; // bytes per lane
+constexpr int kTileThreads = kRasterThreads;
+constexpr uint32_t kTileStrip = kRasterStrip; // bytes per lane
 
 struct TileArgs {
     const uint8_t *in;
@@ -32,17 +36,6 @@ struct TileArgs {
     uint32_t n_strips;       // ny nx tile_h strips_per_row
 };
 
-template <typename V>
-__device__ __forceinline__ V load_unaligned(const uint8_t *p) {
-    V v;
-    __builtin_memcpy(&v, p, sizeof(V));
-    return v;
-}
-template <typename V>
-__device__ __forceinline__ void store_unaligned(uint8_t *p, const V &v) {
-    __builtin_memcpy(p, &v, sizeof(V));
-}
-
 // What a lane's strip is: its place in the tile raster, the image row it maps to and how many of its bytes lie in the image row without clamping.
 struct Strip {
     uint64_t tile_off; // byte offset of the strip in the tile raster
@@ -52,6 +45,7 @@ struct Strip {
     uint32_t n;        // the strip's bytes: 16, or fewer for a row's last strip
 };
 
+// (raster_common.hpp's strip_of, written out: taken from there the whole-raster kernels compile to other instructions - profiles/raster_common_time.txt.)
 __device__ __forceinline__ Strip strip_of(const TileArgs &p, uint32_t g, uint32_t channels) {
     const uint32_t row = g / p.strips_per_row, s = g - row * p.strips_per_row; // row = t tile_h + y
     const uint32_t t = row / p.tile_h, y = row - t * p.tile_h;
@@ -123,18 +117,15 @@ template <uint32_t C>
 __global__ void __launch_bounds__(kTileThreads) merge_tiles_region_kernel(const RegionArgs p) {
     const uint32_t g = blockIdx.x * kTileThreads + threadIdx.x;
     if (g >= p.n_strips) return;
-    const uint32_t ry = g / p.strips_per_row, b0 = (g - ry * p.strips_per_row) * kTileStrip;
-    const uint32_t n = min(kTileStrip, p.region_row_bytes - b0);
-    const uint32_t gy = p.oy + ry, b = gy / p.tile_h, y = gy - b * p.tile_h; // row y of the tiles of sub-grid row b
-    const uint32_t gx = p.ox_bytes + b0;                                     // the strip's first byte in the sub-grid's row: < ni row_bytes
-    uint32_t a = gx / p.row_bytes, xb = gx - a * p.row_bytes;                // byte xb of the row of tile (b, a)
+    const RegionStrip st = region_strip_of(g, p.strips_per_row, p.region_row_bytes, p.ox_bytes, p.oy, p.row_bytes, p.tile_h);
     const uint64_t tile_stride = (uint64_t)p.tile_h * p.row_bytes;
-    const uint8_t *src = p.in + ((uint64_t)b * p.ni + a) * tile_stride + (uint64_t)y * p.row_bytes;
-    uint8_t *dst = p.out + (uint64_t)ry * p.region_row_bytes + b0;
-    if (n == kTileStrip && xb + kTileStrip <= p.row_bytes) {
+    const uint8_t *src = p.in + ((uint64_t)st.b * p.ni + st.a) * tile_stride + (uint64_t)st.y * p.row_bytes;
+    uint8_t *dst = p.out + (uint64_t)st.ry * p.region_row_bytes + st.u0;
+    uint32_t xb = st.xu;
+    if (st.n == kRasterStrip && st.xu + kRasterStrip <= p.row_bytes) {
         store_unaligned(dst, load_unaligned<u32x4>(src + xb));
     } else { // the strip crosses a tile column, or is the row's last
-        for (uint32_t k = 0; k < n; k++) {
+        for (uint32_t k = 0; k < st.n; k++) {
             dst[k] = src[xb];
             if (++xb == p.row_bytes) xb = 0, src += tile_stride; // the same row of the next tile
         }
@@ -164,10 +155,8 @@ template <uint32_t C>
 __global__ void __launch_bounds__(kTileThreads) split_tiles_region_kernel(const SplitRegionArgs p) {
     const uint32_t g = blockIdx.x * kTileThreads + threadIdx.x;
     if (g >= p.n_strips) return;
-    const uint32_t row = g / p.strips_per_row, b0 = (g - row * p.strips_per_row) * kTileStrip; // row = s tile_h + y
-    const uint32_t s = row / p.tile_h, y = row - s * p.tile_h;
-    const uint32_t b = s / p.ni, a = s - b * p.ni;
-    const uint32_t n = min(kTileStrip, p.row_bytes - b0);
+    const TileStrip st = strip_of(g, p.strips_per_row, p.tile_h, p.ni); // tile (b, a) = (st.j, st.i) of the sub-grid
+    const uint32_t row = st.row, b0 = st.u0, y = st.y, b = st.j, a = st.i, n = strip_units(p.row_bytes, b0);
     const uint32_t gy = min((p.j0 + b) * p.tile_h + y, p.height - 1);
     const uint32_t x0 = (p.i0 + a) * p.tile_w, x0_bytes = x0 * C; // where the tile's columns start in an image row
     const uint32_t image_row_bytes = p.width * C;
@@ -189,20 +178,14 @@ __global__ void __launch_bounds__(kTileThreads) split_tiles_region_kernel(const 
 // slot k mod C - constant indices, registers - and turns the slots into channels after each strip. Reduced as merge420_kernel<true> does (k8_chroma420.hip):
 // 32-bit sums per lane, a wave reduction, LDS, one 64-bit atomic per sum and workgroup. Those atomics all go to the same 2 C + 1 words and take some 8 ns each
 // there, one after the other: with one strip per lane a 4096^2 plane's 4096 workgroups spent 100 us on them, 13 times what the merge takes. A lane therefore
-// walks up to kMeasureStrips strips, a whole grid apart (so a wave's loads stay 1 KiB runs): 32 x 16 x 255^2 < 2^25 per lane and < 2^31 per wave in 32 bits,
-// the waves added in 64. Integers: a run is the same sums every time.
-constexpr uint32_t kMeasureStrips = 32, kMeasureGroups = 512; // strips per lane at most; the grid up to which a lane keeps to one strip
+// walks up to 32 strips, a whole grid apart (so a wave's loads stay 1 KiB runs; raster_launch.hpp, measure_per_lane): 32 x 16 x 255^2 < 2^25 per lane and
+// < 2^31 per wave in 32 bits, the waves added in 64. Integers: a run is the same sums every time. (K8 and K12 reduce their seven sums by raster_sums7.inc.)
 struct MeasureTileArgs {
     TileArgs g;              // in: the tile raster; out is not used
     const uint8_t *ref;      // the reference raster, only read
     unsigned long long *out; // [2 C + 1], zeroed by the caller
     uint32_t per_lane;       // strips per lane: the lane of workgroup b walks strips ((k gridDim.x + b) 256 + thread), k < per_lane
 };
-
-__device__ __forceinline__ int byte_of(const u32x4 &v, int k) {
-    const uint32_t w = (k >> 2) == 0 ? v.x : (k >> 2) == 1 ? v.y : (k >> 2) == 2 ? v.z : v.w;
-    return (int)((w >> ((k & 3) * 8)) & 0xFFu);
-}
 
 template <uint32_t C>
 __global__ void __launch_bounds__(kTileThreads) measure_tiles_kernel(const MeasureTileArgs a) {
@@ -212,7 +195,7 @@ __global__ void __launch_bounds__(kTileThreads) measure_tiles_kernel(const Measu
 #pragma unroll
     for (uint32_t i = 0; i < 2 * C + 1; i++) part[i] = 0;
     for (uint32_t it = 0; it < a.per_lane; it++) {
-        const uint64_t g64 = ((uint64_t)it * gridDim.x + blockIdx.x) * kTileThreads + threadIdx.x;
+        const uint64_t g64 = measure_strip_index(it);
         if (g64 >= p.n_strips) break;
         const Strip st = strip_of(p, (uint32_t)g64, C);
         if (st.gy >= p.height) continue; // a replicated row counts nothing
@@ -223,23 +206,19 @@ __global__ void __launch_bounds__(kTileThreads) measure_tiles_kernel(const Measu
         const uint8_t *ref_row = a.ref + (uint64_t)st.gy * image_row_bytes;
         const uint32_t at0 = st.x0_bytes + st.b0;
         if (st.n == kTileStrip && at0 + kTileStrip <= image_row_bytes) {
-            const u32x4 tv = load_unaligned<u32x4>(src), rv = load_unaligned<u32x4>(ref_row + at0);
+            uint32_t tv[4], rv[4];
+            load_dwords(src, tv);
+            load_dwords(ref_row + at0, rv);
 #pragma unroll
             for (int k = 0; k < (int)kTileStrip; k++) {
-                const int d = byte_of(tv, k) - byte_of(rv, k);
-                const uint32_t e = (uint32_t)(d < 0 ? -d : d);
-                sse[k % C] += e * e;
-                worst[k % C] = max(worst[k % C], e);
+                measure_add(byte_of(tv, k), byte_of(rv, k), sse[k % C], worst[k % C]);
                 seen[k % C] += 1;
             }
         } else { // the strip reaches past the image row, or is the row's last
 #pragma unroll
             for (uint32_t k = 0; k < kTileStrip; k++) {
                 if (k < st.n && at0 + k < image_row_bytes) {
-                    const int d = (int)src[k] - (int)ref_row[at0 + k];
-                    const uint32_t e = (uint32_t)(d < 0 ? -d : d);
-                    sse[k % C] += e * e;
-                    worst[k % C] = max(worst[k % C], e);
+                    measure_add(src[k], ref_row[at0 + k], sse[k % C], worst[k % C]);
                     seen[k % C] += 1;
                 }
             }
@@ -283,16 +262,11 @@ __global__ void __launch_bounds__(kTileThreads) measure_tiles_kernel(const Measu
 
 // The tile raster's strips as a 1-D grid of kTileThreads-thread workgroups, one strip per lane; false for a shape that does not fit one
 bool grid_of(uint32_t width, uint32_t height, uint32_t channels, uint32_t tile_w, uint32_t tile_h, TileArgs &p, uint32_t &groups) {
-    if (!width || !height || !tile_w || !tile_h || (channels != 1 && channels != 3)) return false;
-    const uint64_t nx = ((uint64_t)width + tile_w - 1) / tile_w, ny = ((uint64_t)height + tile_h - 1) / tile_h;
-    const uint64_t row_bytes = (uint64_t)tile_w * channels, image_row_bytes = (uint64_t)width * channels;
-    if (row_bytes > 0x7FFFFFFFull || image_row_bytes > 0x7FFFFFFFull || nx * tile_w * channels > 0xFFFFFFFFull || ny * tile_h > 0xFFFFFFFFull) return false;
-    const uint64_t spr = (row_bytes + kTileStrip - 1) / kTileStrip;
-    const uint64_t rows = nx * ny * tile_h;
-    if (rows > 0xFFFFFFFFull || rows * spr > 0xFFFFFFFFull - kTileThreads) return false; // (one u32 strip index per lane)
-    p.width = width, p.height = height, p.tile_w = tile_w, p.tile_h = tile_h, p.nx = (uint32_t)nx;
-    p.row_bytes = (uint32_t)row_bytes, p.strips_per_row = (uint32_t)spr, p.n_strips = (uint32_t)(rows * spr);
-    groups = (uint32_t)((rows * spr + kTileThreads - 1) / kTileThreads);
+    raster::TileGrid g;
+    if ((channels != 1 && channels != 3) || !raster::tile_grid(width, height, tile_w, tile_h, channels, channels, g)) return false;
+    p.width = width, p.height = height, p.tile_w = tile_w, p.tile_h = tile_h, p.nx = g.nx;
+    p.row_bytes = g.row_units, p.strips_per_row = g.strips_per_row, p.n_strips = g.n_strips;
+    groups = g.groups;
     return true;
 }
 
@@ -303,8 +277,7 @@ hipError_t launch_split_tiles(const uint8_t *image, uint32_t width, uint32_t hei
     uint32_t groups = 0;
     if (!image || !tiles || !grid_of(width, height, channels, tile_w, tile_h, p, groups)) return hipErrorInvalidValue;
     p.in = image, p.out = tiles;
-    if (channels == 3) hipLaunchKernelGGL(split_tiles_kernel<3>, dim3(groups), dim3(kTileThreads), 0, stream, p);
-    else hipLaunchKernelGGL(split_tiles_kernel<1>, dim3(groups), dim3(kTileThreads), 0, stream, p);
+    FRI_RASTER_LAUNCH_C(split_tiles_kernel, channels, groups, stream, p);
     return hipGetLastError();
 }
 
@@ -313,8 +286,7 @@ hipError_t launch_merge_tiles(const uint8_t *tiles, uint32_t width, uint32_t hei
     uint32_t groups = 0;
     if (!image || !tiles || !grid_of(width, height, channels, tile_w, tile_h, p, groups)) return hipErrorInvalidValue;
     p.in = tiles, p.out = image;
-    if (channels == 3) hipLaunchKernelGGL(merge_tiles_kernel<3>, dim3(groups), dim3(kTileThreads), 0, stream, p);
-    else hipLaunchKernelGGL(merge_tiles_kernel<1>, dim3(groups), dim3(kTileThreads), 0, stream, p);
+    FRI_RASTER_LAUNCH_C(merge_tiles_kernel, channels, groups, stream, p);
     return hipGetLastError();
 }
 
@@ -322,22 +294,18 @@ hipError_t launch_merge_tiles_region(const uint8_t *tiles, uint32_t width, uint3
                                      uint32_t h, uint8_t *region, hipStream_t stream) {
     TileArgs whole{};
     uint32_t groups = 0;
+    raster::SubGrid s;
     if (!region || !tiles || !grid_of(width, height, channels, tile_w, tile_h, whole, groups)) return hipErrorInvalidValue; // (the shape's limits: a row's bytes fit 31 bits)
-    if (!w || !h || (uint64_t)x + w > width || (uint64_t)y + h > height) return hipErrorInvalidValue;
-    const uint32_t i0 = x / tile_w, j0 = y / tile_h;
+    if (!raster::sub_grid_of(width, height, tile_w, tile_h, x, y, w, h, s)) return hipErrorInvalidValue;
     RegionArgs p{};
     p.in = tiles, p.out = region;
-    p.tile_h = tile_h, p.ni = (x + w - 1) / tile_w - i0 + 1;
+    p.tile_h = tile_h, p.ni = s.ni;
     p.row_bytes = whole.row_bytes;
-    p.ox_bytes = (x - i0 * tile_w) * channels, p.oy = y - j0 * tile_h;
+    p.ox_bytes = s.ox * channels, p.oy = s.oy;
     p.region_row_bytes = w * channels;
-    p.strips_per_row = (p.region_row_bytes + kTileStrip - 1) / kTileStrip;
-    const uint64_t n_strips = (uint64_t)h * p.strips_per_row;
-    if (n_strips > 0xFFFFFFFFull - kTileThreads) return hipErrorInvalidValue; // (one u32 strip index per lane)
-    p.n_strips = (uint32_t)n_strips;
-    groups = (uint32_t)((n_strips + kTileThreads - 1) / kTileThreads);
-    if (channels == 3) hipLaunchKernelGGL(merge_tiles_region_kernel<3>, dim3(groups), dim3(kTileThreads), 0, stream, p);
-    else hipLaunchKernelGGL(merge_tiles_region_kernel<1>, dim3(groups), dim3(kTileThreads), 0, stream, p);
+    p.strips_per_row = (uint32_t)raster::strips_of(p.region_row_bytes);
+    if (!raster::groups_of((uint64_t)h * p.strips_per_row, raster::kMaxStrips, p.n_strips, groups)) return hipErrorInvalidValue; // (one u32 strip index per lane)
+    FRI_RASTER_LAUNCH_C(merge_tiles_region_kernel, channels, groups, stream, p);
     return hipGetLastError();
 }
 
@@ -346,8 +314,9 @@ hipError_t launch_split_tiles_region(const uint8_t *src, size_t src_pitch, uint3
     TileArgs whole{};
     uint32_t groups = 0;
     if (!src || !tiles || !grid_of(width, height, channels, tile_w, tile_h, whole, groups)) return hipErrorInvalidValue; // (the shape's limits: a row's bytes fit 31 bits)
-    if (!w || !h || (uint64_t)x + w > width || (uint64_t)y + h > height) return hipErrorInvalidValue;
-    const uint32_t i0 = x / tile_w, j0 = y / tile_h, ni = (x + w - 1) / tile_w - i0 + 1, nj = (y + h - 1) / tile_h - j0 + 1;
+    raster::SubGrid s;
+    if (!raster::sub_grid_of(width, height, tile_w, tile_h, x, y, w, h, s)) return hipErrorInvalidValue;
+    const uint32_t i0 = s.i0, j0 = s.j0, ni = s.ni, nj = s.nj;
     // the covered rectangle: the in-image pixels of the touched tiles, in 64 bits
     const uint64_t cx = (uint64_t)i0 * tile_w, cy = (uint64_t)j0 * tile_h;
     const uint64_t cx1 = std::min<uint64_t>(((uint64_t)i0 + ni) * tile_w, width), cy1 = std::min<uint64_t>(((uint64_t)j0 + nj) * tile_h, height);
@@ -361,11 +330,9 @@ hipError_t launch_split_tiles_region(const uint8_t *src, size_t src_pitch, uint3
     p.width = width, p.height = height, p.tile_w = tile_w, p.tile_h = tile_h;
     p.i0 = i0, p.j0 = j0, p.ni = ni;
     p.row_bytes = whole.row_bytes, p.strips_per_row = whole.strips_per_row;
-    const uint64_t n_strips = (uint64_t)ni * nj * tile_h * p.strips_per_row; // (at most the whole grid's, which grid_of has checked)
-    p.n_strips = (uint32_t)n_strips;
-    groups = (uint32_t)((n_strips + kTileThreads - 1) / kTileThreads);
-    if (channels == 3) hipLaunchKernelGGL(split_tiles_region_kernel<3>, dim3(groups), dim3(kTileThreads), 0, stream, p);
-    else hipLaunchKernelGGL(split_tiles_region_kernel<1>, dim3(groups), dim3(kTileThreads), 0, stream, p);
+    // (the strips are at most the whole grid's, which grid_of has checked: this refuses nothing)
+    if (!raster::groups_of((uint64_t)ni * nj * tile_h * p.strips_per_row, raster::kMaxStrips, p.n_strips, groups)) return hipErrorInvalidValue;
+    FRI_RASTER_LAUNCH_C(split_tiles_region_kernel, channels, groups, stream, p);
     return hipGetLastError();
 }
 
@@ -375,11 +342,8 @@ hipError_t launch_measure_tiles(const uint8_t *tiles, uint32_t width, uint32_t h
     uint32_t groups = 0;
     if (!reference || !tiles || !sums || !grid_of(width, height, channels, tile_w, tile_h, a.g, groups)) return hipErrorInvalidValue;
     a.g.in = tiles, a.ref = reference, a.out = sums;
-    // one strip per lane up to kMeasureGroups workgroups, then more strips per lane, and past kMeasureStrips of them more workgroups again
-    a.per_lane = std::min(kMeasureStrips, (groups + kMeasureGroups - 1) / kMeasureGroups);
-    groups = (groups + a.per_lane - 1) / a.per_lane;
-    if (channels == 3) hipLaunchKernelGGL(measure_tiles_kernel<3>, dim3(groups), dim3(kTileThreads), 0, stream, a);
-    else hipLaunchKernelGGL(measure_tiles_kernel<1>, dim3(groups), dim3(kTileThreads), 0, stream, a);
+    a.per_lane = raster::measure_per_lane(groups);
+    FRI_RASTER_LAUNCH_C(measure_tiles_kernel, channels, groups, stream, a);
     return hipGetLastError();
 }
 

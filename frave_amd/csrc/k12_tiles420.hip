@@ -16,15 +16,17 @@
 // measure_tiles420_kernel: the whole-image merge's walk with nothing stored - each pixel is compared with the reference raster's and only seven sums leave the kernel
 // (several strips per lane on large images, wave reduction, LDS, one 64-bit atomic per sum and workgroup).
 //
-// No raster has a row pitch and every buffer starts at any byte: the vector accesses are the target's unaligned global loads and stores (the compiler is told
-// the alignment is 1). Every byte offset is 64-bit. Split and merge use no LDS and no atomics; every kernel only enqueues and can be captured into a graph.
-#include "device_common.hpp"
+// The 4:2:0 arithmetic, the region strip locator and measure_add are raster_common.hpp's, shared with K8 and K10; the launch geometry is raster_launch.hpp's. No raster has a
+// row pitch and every buffer starts at any byte. Every byte offset is 64-bit. Split and merge use no LDS and no atomics; every kernel only enqueues and can be
+// captured into a graph.
+#include "raster_common.hpp"
+#include "raster_launch.hpp"
 
 namespace fri {
 namespace {
 
-constexpr int kT420Threads = 256;
-constexpr int kT420Strip = 16; // pixels of a row per lane
+constexpr int kT420Threads = kRasterThreads;
+constexpr int kT420Strip = (int)kRasterStrip; // pixels of a row per lane
 
 struct SplitTiles420Args {
     const uint8_t *rgb;
@@ -44,29 +46,12 @@ struct MergeTiles420Args {
     uint32_t n_items;  // h x n_strips
 };
 
-template <typename V>
-__device__ __forceinline__ V load_unaligned(const uint8_t *p) {
-    V v;
-    __builtin_memcpy(&v, p, sizeof(V));
-    return v;
-}
-template <typename V>
-__device__ __forceinline__ void store_unaligned(uint8_t *p, const V &v) {
-    __builtin_memcpy(p, &v, sizeof(V));
-}
-__device__ __forceinline__ int byte_of(const uint32_t *w, int n) { return (int)((w[n >> 2] >> ((n & 3) * 8)) & 255u); }
-__device__ __forceinline__ int clamp255(int v) { return min(max(v, 0), 255); }
-
 // 16 pixels of the image row at src_row for the tile columns x0 .. x0 + 15 of a tile whose columns start at image column gx0, as 12 dwords. !FULL: a tile
 // column past the tile repeats the tile's last one (the chroma's odd column), an image column past the image repeats the image's last one (the tile's edge).
 template <bool FULL>
 __device__ __forceinline__ void load_tile_pixels(const uint8_t *src_row, const SplitTiles420Args &p, uint32_t gx0, uint32_t x0, uint32_t (&px)[12]) {
     if (FULL) {
-#pragma unroll
-        for (int q = 0; q < 3; q++) {
-            const u32x4 v = load_unaligned<u32x4>(src_row + (uint64_t)(gx0 + x0) * 3 + 16 * q);
-            px[4 * q] = v.x, px[4 * q + 1] = v.y, px[4 * q + 2] = v.z, px[4 * q + 3] = v.w;
-        }
+        load_dwords(src_row + (uint64_t)(gx0 + x0) * 3, px);
     } else {
 #pragma unroll
         for (int i = 0; i < 12; i++) px[i] = 0;
@@ -75,7 +60,7 @@ __device__ __forceinline__ void load_tile_pixels(const uint8_t *src_row, const S
             const uint32_t tx = min(x0 + (uint32_t)k, p.tile_w - 1);
             const uint8_t *s = src_row + (uint64_t)min(gx0 + tx, p.width - 1) * 3;
 #pragma unroll
-            for (int c = 0; c < 3; c++) px[(3 * k + c) >> 2] |= (uint32_t)s[c] << (((3 * k + c) & 3) * 8);
+            for (int c = 0; c < 3; c++) put_byte(px, 3 * k + c, s[c]);
         }
     }
 }
@@ -97,31 +82,21 @@ __device__ __forceinline__ void split_tile_strip(const SplitTiles420Args &p, uin
         load_tile_pixels<FULL>(p.rgb + (uint64_t)gy * p.width * 3, p, gx0, x0, px);
         uint32_t yw[4] = {0, 0, 0, 0};
 #pragma unroll
-        for (int k = 0; k < kT420Strip; k++) {
-            const int R = byte_of(px, 3 * k), G = byte_of(px, 3 * k + 1), B = byte_of(px, 3 * k + 2);
-            const int Y = (19595 * R + 38470 * G + 7471 * B + 32768) >> 16;
-            yw[k >> 2] |= (uint32_t)Y << ((k & 3) * 8);
-            cb[k >> 1] += (-11059 * R - 21709 * G + 32768 * B + (128 << 16) + 32767) >> 16;
-            cr[k >> 1] += (32768 * R - 27439 * G - 5329 * B + (128 << 16) + 32767) >> 16;
-        }
+        for (int k = 0; k < kT420Strip; k++) ycc_pixel(px, k, yw, cb, cr);
         if (2 * jc + r < p.tile_h) { // (an odd last row of the tile has no second luma row)
             uint8_t *dst = y_tile + (uint64_t)ty * p.tile_w + x0;
             if (FULL) {
-                const u32x4 v = {yw[0], yw[1], yw[2], yw[3]};
-                store_unaligned(dst, v);
+                store_dwords(dst, yw);
             } else {
 #pragma unroll
                 for (int k = 0; k < kT420Strip; k++)
-                    if (x0 + k < p.tile_w) dst[k] = (uint8_t)(yw[k >> 2] >> ((k & 3) * 8));
+                    if (x0 + k < p.tile_w) dst[k] = (uint8_t)byte_of(yw, k);
             }
         }
     }
     uint32_t bw[2] = {0, 0}, rw[2] = {0, 0};
 #pragma unroll
-    for (int m = 0; m < kT420Strip / 2; m++) {
-        bw[m >> 2] |= (uint32_t)((cb[m] + 2) >> 2) << ((m & 3) * 8);
-        rw[m >> 2] |= (uint32_t)((cr[m] + 2) >> 2) << ((m & 3) * 8);
-    }
+    for (int m = 0; m < kT420Strip / 2; m++) pack_chroma(cb, cr, m, bw, rw);
     const uint64_t plane = (uint64_t)p.ch * p.cw, at = (uint64_t)jc * p.cw + x0 / 2;
     if (FULL) {
         const uint2v b = {bw[0], bw[1]}, r = {rw[0], rw[1]};
@@ -131,8 +106,8 @@ __device__ __forceinline__ void split_tile_strip(const SplitTiles420Args &p, uin
 #pragma unroll
         for (int m = 0; m < kT420Strip / 2; m++)
             if (x0 / 2 + m < p.cw) {
-                c_tile[at + m] = (uint8_t)(bw[m >> 2] >> ((m & 3) * 8));
-                c_tile[plane + at + m] = (uint8_t)(rw[m >> 2] >> ((m & 3) * 8));
+                c_tile[at + m] = (uint8_t)byte_of(bw, m);
+                c_tile[plane + at + m] = (uint8_t)byte_of(rw, m);
             }
     }
 }
@@ -149,25 +124,8 @@ __global__ void __launch_bounds__(kT420Threads) split_tiles420_kernel(const Spli
     else split_tile_strip<false>(p, t, jc, x0);
 }
 
-__device__ __forceinline__ void ycc_to_rgb(int Y, int cbv, int crv, int &R, int &G, int &B) {
-    const int db = cbv - 128, dr = crv - 128;
-    R = clamp255(Y + ((91881 * dr + 32768) >> 16));
-    G = clamp255(Y + ((-22554 * db - 46802 * dr + 32768) >> 16));
-    B = clamp255(Y + ((116130 * db + 32768) >> 16));
-}
-
-// v[m] = 3 plane[j][c] + plane[j2][c] at the chroma columns c = i0 - 1 + m, m = 0..9, clamped to the tile's plane; i0 + 8 <= cw
-__device__ __forceinline__ void load_tile_chroma(const uint8_t *plane, int cw, int j, int j2, int i0, int (&v)[kT420Strip / 2 + 2]) {
-    const uint8_t *a = plane + (uint64_t)j * cw, *b = plane + (uint64_t)j2 * cw;
-    constexpr int N = kT420Strip / 2;
-    const uint2v wa = load_unaligned<uint2v>(a + i0), wb = load_unaligned<uint2v>(b + i0);
-    const uint32_t ua[2] = {wa.x, wa.y}, ub[2] = {wb.x, wb.y};
-#pragma unroll
-    for (int m = 0; m < N; m++) v[m + 1] = 3 * byte_of(ua, m) + byte_of(ub, m);
-    const int l = max(i0 - 1, 0), r = min(i0 + N, cw - 1);
-    v[0] = 3 * a[l] + b[l];
-    v[N + 1] = 3 * a[r] + b[r];
-}
+// the header's inverse formula from Cb and Cr
+__device__ __forceinline__ void tile_ycc_to_rgb(int Y, int cbv, int crv, int &R, int &G, int &B) { ycc_to_rgb(Y, cbv - 128, crv - 128, R, G, B); }
 
 // 16 pixels of tile row ty from tile column tx (tx & 1 == ODD), all inside the tile row: tx + 16 <= tile_w
 template <int ODD>
@@ -175,8 +133,8 @@ __device__ __forceinline__ void merge_tile_strip(const MergeTiles420Args &p, con
     const int ch = (int)p.ch, cw = (int)p.cw;
     const int j = ty >> 1, j2 = (ty & 1) ? min(j + 1, ch - 1) : max(j - 1, 0);
     int vb[kT420Strip / 2 + 2], vr[kT420Strip / 2 + 2];
-    load_tile_chroma(c_tile, cw, j, j2, tx >> 1, vb);
-    load_tile_chroma(c_tile + (uint64_t)ch * cw, cw, j, j2, tx >> 1, vr);
+    load_chroma<true>(c_tile, cw, j, j2, tx >> 1, vb);
+    load_chroma<true>(c_tile + (uint64_t)ch * cw, cw, j, j2, tx >> 1, vr);
     const u32x4 yv = load_unaligned<u32x4>(y_tile + (uint64_t)ty * p.tile_w + tx);
     const uint32_t yw[4] = {yv.x, yv.y, yv.z, yv.w};
     uint32_t px[12];
@@ -186,10 +144,8 @@ __device__ __forceinline__ void merge_tile_strip(const MergeTiles420Args &p, con
     for (int k = 0; k < kT420Strip; k++) {
         const int m = 1 + ((k + ODD) >> 1), n = ((k + ODD) & 1) ? m + 1 : m - 1; // the column's own sample and its neighbour on the pixel's side
         int R, G, B;
-        ycc_to_rgb(byte_of(yw, k), (3 * vb[m] + vb[n] + 8) >> 4, (3 * vr[m] + vr[n] + 8) >> 4, R, G, B);
-        px[(3 * k) >> 2] |= (uint32_t)R << (((3 * k) & 3) * 8);
-        px[(3 * k + 1) >> 2] |= (uint32_t)G << (((3 * k + 1) & 3) * 8);
-        px[(3 * k + 2) >> 2] |= (uint32_t)B << (((3 * k + 2) & 3) * 8);
+        tile_ycc_to_rgb(byte_of(yw, k), (3 * vb[m] + vb[n] + 8) >> 4, (3 * vr[m] + vr[n] + 8) >> 4, R, G, B);
+        put_rgb(px, k, R, G, B);
     }
 #pragma unroll
     for (int q = 0; q < 3; q++) {
@@ -200,17 +156,8 @@ __device__ __forceinline__ void merge_tile_strip(const MergeTiles420Args &p, con
 
 // one pixel (tx, ty) of a tile: inverse steps 2 - 3 by the header's formula
 __device__ __forceinline__ void merge_tile_pixel(const MergeTiles420Args &p, const uint8_t *y_tile, const uint8_t *c_tile, int tx, int ty, uint8_t *dst) {
-    const int ch = (int)p.ch, cw = (int)p.cw;
-    const int i = tx >> 1, i2 = (tx & 1) ? min(i + 1, cw - 1) : max(i - 1, 0);
-    const int j = ty >> 1, j2 = (ty & 1) ? min(j + 1, ch - 1) : max(j - 1, 0);
-    int up[2];
-#pragma unroll
-    for (int c = 0; c < 2; c++) {
-        const uint8_t *a = c_tile + (uint64_t)c * ch * cw + (uint64_t)j * cw, *b = c_tile + (uint64_t)c * ch * cw + (uint64_t)j2 * cw;
-        up[c] = (9 * a[i] + 3 * a[i2] + 3 * b[i] + b[i2] + 8) >> 4;
-    }
     int R, G, B;
-    ycc_to_rgb(y_tile[(uint64_t)ty * p.tile_w + tx], up[0], up[1], R, G, B);
+    upsample_pixel(y_tile, c_tile, p.tile_w, (int)p.cw, (int)p.ch, tx, ty, R, G, B);
     dst[0] = (uint8_t)R, dst[1] = (uint8_t)G, dst[2] = (uint8_t)B;
 }
 
@@ -218,11 +165,9 @@ __device__ __forceinline__ void merge_tile_pixel(const MergeTiles420Args &p, con
 __global__ void __launch_bounds__(kT420Threads) merge_tiles420_region_kernel(const MergeTiles420Args p) {
     const uint32_t g = blockIdx.x * kT420Threads + threadIdx.x;
     if (g >= p.n_items) return;
-    const uint32_t ry = g / p.n_strips, rx0 = (g - ry * p.n_strips) * kT420Strip;
-    const uint32_t n = min((uint32_t)kT420Strip, p.w - rx0);
-    const uint32_t gy = p.oy + ry, b = gy / p.tile_h, ty = gy - b * p.tile_h; // row ty of the tiles of sub-grid row b
-    const uint32_t gx = p.ox + rx0;                                          // the strip's first column in the sub-grid's row: < ni tile_w
-    uint32_t a = gx / p.tile_w, tx = gx - a * p.tile_w;                      // column tx of tile (b, a)
+    const RegionStrip st = region_strip_of(g, p.n_strips, p.w, p.ox, p.oy, p.tile_w, p.tile_h);
+    const uint32_t ry = st.ry, rx0 = st.u0, n = st.n, b = st.b, ty = st.y, a = st.a; // row ty, from column tx, of tile (b, a) of the sub-grid
+    uint32_t tx = st.xu;
     const uint64_t y_stride = (uint64_t)p.tile_h * p.tile_w, c_stride = 2ull * p.ch * p.cw;
     const uint64_t s = (uint64_t)b * p.ni + a;
     const uint8_t *y_tile = p.y + s * y_stride, *c_tile = p.c + s * c_stride;
@@ -240,7 +185,8 @@ __global__ void __launch_bounds__(kT420Threads) merge_tiles420_region_kernel(con
 
 // measure_tiles420_kernel: the whole-image merge walk - the region (0, 0, W, H) on the full grid - with nothing stored. A lane owns the same 16 pixels of an image
 // row, classifies its strip as the merge does and, where the merge stores 48 bytes, loads the same 48 bytes of the reference raster [H][W][3] instead (byte loads on
-// the pixel-by-pixel path). The strip bodies are the measuring form's own, so that the merge's instances compile to what they were. Both inputs are only read.
+// the pixel-by-pixel path). Both inputs are only read. The strip and the pixel are the measuring form's own, the merge's with the store replaced by a
+// compare: as one body (template <bool MEASURE>) both kernels compile to other instructions, which measured 0.1 - 1 % slower (profiles/raster_common_time.txt).
 struct MeasureTiles420Args {
     const uint8_t *y, *c;    // the full grid's planes
     const uint8_t *ref;      // the reference raster
@@ -252,13 +198,6 @@ struct MeasureTiles420Args {
     uint32_t per_lane; // strips per lane
 };
 
-__device__ __forceinline__ void measure_add(int got, int want, uint32_t &sse, uint32_t &worst) {
-    const int d = got - want;
-    const uint32_t a = (uint32_t)(d < 0 ? -d : d);
-    sse += a * a;
-    worst = max(worst, a);
-}
-
 // merge_tile_strip<ODD>'s 16 pixels against 48 bytes of the reference at ref
 template <int ODD>
 __device__ __forceinline__ void measure_tile_strip(const MeasureTiles420Args &p, const uint8_t *y_tile, const uint8_t *c_tile, int tx, int ty, const uint8_t *ref,
@@ -266,8 +205,8 @@ __device__ __forceinline__ void measure_tile_strip(const MeasureTiles420Args &p,
     const int ch = (int)p.ch, cw = (int)p.cw;
     const int j = ty >> 1, j2 = (ty & 1) ? min(j + 1, ch - 1) : max(j - 1, 0);
     int vb[kT420Strip / 2 + 2], vr[kT420Strip / 2 + 2];
-    load_tile_chroma(c_tile, cw, j, j2, tx >> 1, vb);
-    load_tile_chroma(c_tile + (uint64_t)ch * cw, cw, j, j2, tx >> 1, vr);
+    load_chroma<true>(c_tile, cw, j, j2, tx >> 1, vb);
+    load_chroma<true>(c_tile + (uint64_t)ch * cw, cw, j, j2, tx >> 1, vr);
     const u32x4 yv = load_unaligned<u32x4>(y_tile + (uint64_t)ty * p.tile_w + tx);
     const uint32_t yw[4] = {yv.x, yv.y, yv.z, yv.w};
     uint32_t rw[12];
@@ -280,7 +219,7 @@ __device__ __forceinline__ void measure_tile_strip(const MeasureTiles420Args &p,
     for (int k = 0; k < kT420Strip; k++) {
         const int m = 1 + ((k + ODD) >> 1), n = ((k + ODD) & 1) ? m + 1 : m - 1; // the column's own sample and its neighbour on the pixel's side
         int R, G, B;
-        ycc_to_rgb(byte_of(yw, k), (3 * vb[m] + vb[n] + 8) >> 4, (3 * vr[m] + vr[n] + 8) >> 4, R, G, B);
+        tile_ycc_to_rgb(byte_of(yw, k), (3 * vb[m] + vb[n] + 8) >> 4, (3 * vr[m] + vr[n] + 8) >> 4, R, G, B);
         measure_add(R, byte_of(rw, 3 * k), sse[0], worst[0]);
         measure_add(G, byte_of(rw, 3 * k + 1), sse[1], worst[1]);
         measure_add(B, byte_of(rw, 3 * k + 2), sse[2], worst[2]);
@@ -290,17 +229,8 @@ __device__ __forceinline__ void measure_tile_strip(const MeasureTiles420Args &p,
 // merge_tile_pixel's pixel against the three bytes at ref
 __device__ __forceinline__ void measure_tile_pixel(const MeasureTiles420Args &p, const uint8_t *y_tile, const uint8_t *c_tile, int tx, int ty, const uint8_t *ref,
                                                    uint32_t (&sse)[3], uint32_t (&worst)[3]) {
-    const int ch = (int)p.ch, cw = (int)p.cw;
-    const int i = tx >> 1, i2 = (tx & 1) ? min(i + 1, cw - 1) : max(i - 1, 0);
-    const int j = ty >> 1, j2 = (ty & 1) ? min(j + 1, ch - 1) : max(j - 1, 0);
-    int up[2];
-#pragma unroll
-    for (int c = 0; c < 2; c++) {
-        const uint8_t *a = c_tile + (uint64_t)c * ch * cw + (uint64_t)j * cw, *b = c_tile + (uint64_t)c * ch * cw + (uint64_t)j2 * cw;
-        up[c] = (9 * a[i] + 3 * a[i2] + 3 * b[i] + b[i2] + 8) >> 4;
-    }
     int R, G, B;
-    ycc_to_rgb(y_tile[(uint64_t)ty * p.tile_w + tx], up[0], up[1], R, G, B);
+    upsample_pixel(y_tile, c_tile, p.tile_w, (int)p.cw, (int)p.ch, tx, ty, R, G, B);
     measure_add(R, ref[0], sse[0], worst[0]);
     measure_add(G, ref[1], sse[1], worst[1]);
     measure_add(B, ref[2], sse[2], worst[2]);
@@ -308,21 +238,18 @@ __device__ __forceinline__ void measure_tile_pixel(const MeasureTiles420Args &p,
 
 // item g = strip g % n_strips of image row g / n_strips. The sums leave a workgroup as seven 64-bit atomics on the same seven words, which take some 8 ns each there,
 // one after the other (K10's measure_tiles_kernel, k10_tiles.hip, has the figures): with one strip per lane a 4096^2 image's 4096 workgroups spend four times the
-// merge's time on them. A lane therefore walks up to kMeasure420Strips strips, a whole grid apart (so a wave's loads stay runs): 32 x 16 x 255^2 < 2^25 per lane and
+// merge's time on them. A lane therefore walks up to 32 strips (raster_launch.hpp, measure_per_lane), a whole grid apart (so a wave's loads stay runs): 32 x 16 x 255^2 < 2^25 per lane and
 // < 2^31 per wave in 32 bits; the waves are added in 64. Integer sums only - a run gives the same seven numbers every time.
-constexpr uint32_t kMeasure420Strips = 32, kMeasure420Groups = 512; // strips per lane at most; the grid up to which a lane keeps to one strip
 __global__ void __launch_bounds__(kT420Threads) measure_tiles420_kernel(const MeasureTiles420Args p) {
     uint32_t sse[3] = {0, 0, 0}, worst[3] = {0, 0, 0};
     uint32_t count = 0;
     for (uint32_t it = 0; it < p.per_lane; it++) {
-        const uint64_t g64 = ((uint64_t)it * gridDim.x + blockIdx.x) * kT420Threads + threadIdx.x; // the lane of workgroup b walks strips (it gridDim.x + b) 256 + thread
+        const uint64_t g64 = measure_strip_index(it);
         if (g64 >= p.n_items) break;
         const uint32_t g = (uint32_t)g64;
-        const uint32_t gy = g / p.n_strips, gx = (g - gy * p.n_strips) * kT420Strip;
-        const uint32_t n = min((uint32_t)kT420Strip, p.w - gx);
-        const uint32_t b = gy / p.tile_h, ty = gy - b * p.tile_h; // row ty of the tiles of grid row b
-        const uint32_t a = gx / p.tile_w;
-        uint32_t tx = gx - a * p.tile_w;                          // column tx of tile (b, a)
+        const RegionStrip st = region_strip_of(g, p.n_strips, p.w, 0, 0, p.tile_w, p.tile_h); // the region (0, 0, W, H) of the full grid
+        const uint32_t gy = st.ry, gx = st.u0, n = st.n, b = st.b, ty = st.y, a = st.a;       // row ty, from column tx, of tile (b, a)
+        uint32_t tx = st.xu;
         const uint64_t y_stride = (uint64_t)p.tile_h * p.tile_w, c_stride = 2ull * p.ch * p.cw;
         const uint64_t s = (uint64_t)b * p.nx + a;
         const uint8_t *y_tile = p.y + s * y_stride, *c_tile = p.c + s * c_stride;
@@ -338,96 +265,58 @@ __global__ void __launch_bounds__(kT420Threads) measure_tiles420_kernel(const Me
         }
         count += n;
     }
-    __shared__ uint32_t s_part[kT420Threads / 64][7];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            sse[c] += __shfl_xor(sse[c], o);
-            worst[c] = max(worst[c], (uint32_t)__shfl_xor(worst[c], o));
-        }
-        count += __shfl_xor(count, o);
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (int c = 0; c < 3; c++) s_part[wave][2 * c] = sse[c], s_part[wave][2 * c + 1] = worst[c];
-        s_part[wave][6] = count;
-    }
-    __syncthreads();
-    if (threadIdx.x < 7) {
-        const bool is_max = threadIdx.x < 6 && (threadIdx.x & 1);
-        unsigned long long v = 0;
-#pragma unroll
-        for (int w = 0; w < kT420Threads / 64; w++) v = is_max ? max(v, (unsigned long long)s_part[w][threadIdx.x]) : v + s_part[w][threadIdx.x];
-        if (v) {
-            if (is_max) atomicMax(p.out + threadIdx.x, v);
-            else atomicAdd(p.out + threadIdx.x, v);
-        }
-    }
+#include "raster_sums7.inc"
 }
 
-// the limits all launchers share: sizes that keep every u32 product above in range; false for a shape outside them
-bool shape_ok(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint64_t &nx, uint64_t &ny) {
-    if (!width || !height || !tile_w || !tile_h || width > 0x3FFFFFFFu || height > 0x3FFFFFFFu || tile_w > 0x3FFFFFFFu || tile_h > 0x3FFFFFFFu) return false;
-    nx = ((uint64_t)width + tile_w - 1) / tile_w, ny = ((uint64_t)height + tile_h - 1) / tile_h;
-    return nx * tile_w <= 0xFFFFFFFFull && ny * tile_h <= 0xFFFFFFFFull && nx * ny <= 0xFFFFFFFFull;
+// the shape's limits and the strips of the region (x, y, w, h) as workgroups; false outside the limits
+bool region_grid(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint32_t &nx, raster::SubGrid &s,
+                 uint32_t &n_strips, uint32_t &n_items, uint32_t &groups) {
+    uint32_t ny = 0;
+    if (!raster::tile_grid420(width, height, tile_w, tile_h, nx, ny) || !raster::sub_grid_of(width, height, tile_w, tile_h, x, y, w, h, s)) return false;
+    n_strips = (uint32_t)raster::strips_of(w);
+    return raster::groups_of((uint64_t)h * n_strips, raster::kMaxStrips, n_items, groups); // (one u32 item index per lane)
 }
 
 } // namespace
 
 hipError_t launch_split_tiles420(const uint8_t *rgb, uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint8_t *y_tiles, uint8_t *c_tiles, hipStream_t stream) {
-    uint64_t nx = 0, ny = 0;
-    if (!rgb || !y_tiles || !c_tiles || !shape_ok(width, height, tile_w, tile_h, nx, ny)) return hipErrorInvalidValue;
+    uint32_t nx = 0, ny = 0, groups = 0;
+    if (!rgb || !y_tiles || !c_tiles || !raster::tile_grid420(width, height, tile_w, tile_h, nx, ny)) return hipErrorInvalidValue;
     SplitTiles420Args p{};
     p.rgb = rgb, p.y = y_tiles, p.c = c_tiles;
-    p.width = width, p.height = height, p.tile_w = tile_w, p.tile_h = tile_h, p.nx = (uint32_t)nx, p.cw = (tile_w + 1) / 2, p.ch = (tile_h + 1) / 2;
-    p.n_strips = (tile_w + kT420Strip - 1) / kT420Strip;
-    const uint64_t rows = nx * ny * p.ch;
-    if (rows > 0xFFFFFFFFull || rows * p.n_strips > 0xFFFFFFFFull - kT420Threads) return hipErrorInvalidValue; // (one u32 item index per lane)
-    p.n_items = (uint32_t)(rows * p.n_strips);
-    const uint32_t groups = (uint32_t)((rows * p.n_strips + kT420Threads - 1) / kT420Threads);
+    p.width = width, p.height = height, p.tile_w = tile_w, p.tile_h = tile_h, p.nx = nx, p.cw = (tile_w + 1) / 2, p.ch = (tile_h + 1) / 2;
+    p.n_strips = (uint32_t)raster::strips_of(tile_w);
+    const uint64_t rows = (uint64_t)nx * ny * p.ch;
+    if (rows > 0xFFFFFFFFull || !raster::groups_of(rows * p.n_strips, raster::kMaxStrips, p.n_items, groups)) return hipErrorInvalidValue; // (one u32 item index per lane)
     hipLaunchKernelGGL(split_tiles420_kernel, dim3(groups), dim3(kT420Threads), 0, stream, p);
     return hipGetLastError();
 }
 
 hipError_t launch_merge_tiles420_region(const uint8_t *y_tiles, const uint8_t *c_tiles, uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t x, uint32_t y,
                                         uint32_t w, uint32_t h, uint8_t *region, hipStream_t stream) {
-    uint64_t nx = 0, ny = 0;
-    if (!region || !y_tiles || !c_tiles || !shape_ok(width, height, tile_w, tile_h, nx, ny)) return hipErrorInvalidValue;
-    if (!w || !h || (uint64_t)x + w > width || (uint64_t)y + h > height) return hipErrorInvalidValue;
-    const uint32_t i0 = x / tile_w, j0 = y / tile_h;
     MergeTiles420Args p{};
+    raster::SubGrid s;
+    uint32_t nx = 0, groups = 0;
+    if (!region || !y_tiles || !c_tiles || !region_grid(width, height, tile_w, tile_h, x, y, w, h, nx, s, p.n_strips, p.n_items, groups)) return hipErrorInvalidValue;
     p.y = y_tiles, p.c = c_tiles, p.out = region;
     p.tile_w = tile_w, p.tile_h = tile_h, p.cw = (tile_w + 1) / 2, p.ch = (tile_h + 1) / 2;
-    p.ni = (x + w - 1) / tile_w - i0 + 1;
-    p.ox = x - i0 * tile_w, p.oy = y - j0 * tile_h;
+    p.ni = s.ni, p.ox = s.ox, p.oy = s.oy;
     p.w = w;
-    p.n_strips = (w + kT420Strip - 1) / kT420Strip;
-    const uint64_t items = (uint64_t)h * p.n_strips;
-    if (items > 0xFFFFFFFFull - kT420Threads) return hipErrorInvalidValue; // (one u32 item index per lane)
-    p.n_items = (uint32_t)items;
-    const uint32_t groups = (uint32_t)((items + kT420Threads - 1) / kT420Threads);
     hipLaunchKernelGGL(merge_tiles420_region_kernel, dim3(groups), dim3(kT420Threads), 0, stream, p);
     return hipGetLastError();
 }
 
 hipError_t launch_measure_tiles420(const uint8_t *y_tiles, const uint8_t *c_tiles, uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, const uint8_t *reference,
                                    unsigned long long *sums, hipStream_t stream) {
-    uint64_t nx = 0, ny = 0;
-    if (!reference || !sums || !y_tiles || !c_tiles || !shape_ok(width, height, tile_w, tile_h, nx, ny)) return hipErrorInvalidValue;
     MeasureTiles420Args p{};
+    raster::SubGrid s;
+    uint32_t groups = 0;
+    // the whole image is the region (0, 0, W, H) of the full grid
+    if (!reference || !sums || !y_tiles || !c_tiles || !region_grid(width, height, tile_w, tile_h, 0, 0, width, height, p.nx, s, p.n_strips, p.n_items, groups)) return hipErrorInvalidValue;
     p.y = y_tiles, p.c = c_tiles, p.ref = reference, p.out = sums;
-    p.tile_w = tile_w, p.tile_h = tile_h, p.cw = (tile_w + 1) / 2, p.ch = (tile_h + 1) / 2, p.nx = (uint32_t)nx;
+    p.tile_w = tile_w, p.tile_h = tile_h, p.cw = (tile_w + 1) / 2, p.ch = (tile_h + 1) / 2;
     p.w = width;
-    p.n_strips = (width + kT420Strip - 1) / kT420Strip;
-    const uint64_t items = (uint64_t)height * p.n_strips;
-    if (items > 0xFFFFFFFFull - kT420Threads) return hipErrorInvalidValue; // (one u32 item index per lane)
-    p.n_items = (uint32_t)items;
-    uint32_t groups = (uint32_t)((items + kT420Threads - 1) / kT420Threads);
-    // one strip per lane up to kMeasure420Groups workgroups, then more strips per lane, and past kMeasure420Strips of them more workgroups again
-    p.per_lane = std::min(kMeasure420Strips, (groups + kMeasure420Groups - 1) / kMeasure420Groups);
-    groups = (groups + p.per_lane - 1) / p.per_lane;
+    p.per_lane = raster::measure_per_lane(groups);
     hipLaunchKernelGGL(measure_tiles420_kernel, dim3(groups), dim3(kT420Threads), 0, stream, p);
     return hipGetLastError();
 }

@@ -10,25 +10,15 @@
 // difference: the tile of grid position (j, i) is slot[j nx + i] of the tile-list raster, not b ni + a of a sub-grid, and the next tile of a row is looked up
 // again, because neighbours in the grid are not neighbours in the list. Every output byte is written once, by one lane; overlapping and repeated regions only
 // read the same tile bytes twice. No atomics, no LDS, nothing but enqueues: capturable. Nothing outside the regions is read: a replicated pixel never is.
-#include "device_common.hpp"
+// The strip's place in the grid (region_strip_at) and the unaligned accesses are raster_common.hpp's, the ones K10's region kernel uses.
+#include "raster_common.hpp"
 
 namespace fri {
 namespace {
 
-constexpr int kRegionsThreads = 256;
-constexpr uint32_t kRegionsStrip = 16; // bytes per lane
-constexpr uint32_t kRegionsRow = 8;    // words per row of the region table
-
-template <typename V>
-__device__ __forceinline__ V load_unaligned(const uint8_t *p) {
-    V v;
-    __builtin_memcpy(&v, p, sizeof(V));
-    return v;
-}
-template <typename V>
-__device__ __forceinline__ void store_unaligned(uint8_t *p, const V &v) {
-    __builtin_memcpy(p, &v, sizeof(V));
-}
+constexpr int kRegionsThreads = kRasterThreads;
+constexpr uint32_t kRegionsStrip = kRasterStrip; // bytes per lane
+constexpr uint32_t kRegionsRow = 8; // words per row of the region table
 
 struct RegionsArgs {
     const uint8_t *in;     // the tile-list raster
@@ -55,21 +45,19 @@ __global__ void __launch_bounds__(kRegionsThreads) merge_tiles_regions_kernel(co
     const uint64_t g = (uint64_t)(blockIdx.x - row[6]) * kRegionsThreads + threadIdx.x;
     if (g >= (uint64_t)h * strips_per_row) return;
     const uint32_t ry = (g >> 32) ? (uint32_t)(g / strips_per_row) : (uint32_t)g / strips_per_row;
-    const uint32_t b0 = (uint32_t)(g - (uint64_t)ry * strips_per_row) * kRegionsStrip;
-    const uint32_t n = min(kRegionsStrip, region_row_bytes - b0);
-    const uint32_t gy = y + ry, j = gy / p.tile_h, yy = gy - j * p.tile_h; // row yy of the tiles of grid row j
-    const uint32_t gx = x * C + b0;                                        // the strip's first byte in the image row: < W C < 2^31
-    uint32_t i = gx / p.row_bytes, xb = gx - i * p.row_bytes;              // byte xb of the row of tile (j, i)
-    const uint32_t *slot = p.table + (p.n_regions + 1) * kRegionsRow + (uint64_t)j * p.nx;
-    const uint64_t tile_stride = (uint64_t)p.tile_h * p.row_bytes, row_off = (uint64_t)yy * p.row_bytes;
+    // the region's corner lies at byte x C of row y of the image's own grid: tile (st.b, st.a) is grid position (j, i)
+    const RegionStrip st = region_strip_at(ry, (uint32_t)(g - (uint64_t)ry * strips_per_row) * kRegionsStrip, region_row_bytes, x * C, y, p.row_bytes, p.tile_h);
+    uint32_t i = st.a, xb = st.xu;
+    const uint32_t *slot = p.table + (p.n_regions + 1) * kRegionsRow + (uint64_t)st.b * p.nx;
+    const uint64_t tile_stride = (uint64_t)p.tile_h * p.row_bytes, row_off = (uint64_t)st.y * p.row_bytes;
     const uint8_t *src = p.in + slot[i] * tile_stride + row_off;
-    uint8_t *dst = p.out + off + (uint64_t)ry * region_row_bytes + b0;
-    if (n == kRegionsStrip && xb + kRegionsStrip <= p.row_bytes) {
+    uint8_t *dst = p.out + off + (uint64_t)ry * region_row_bytes + st.u0;
+    if (st.n == kRasterStrip && st.xu + kRasterStrip <= p.row_bytes) {
         store_unaligned(dst, load_unaligned<u32x4>(src + xb));
     } else { // the strip crosses a tile column, or is the row's last
-        for (uint32_t k = 0; k < n; k++) {
+        for (uint32_t k = 0; k < st.n; k++) {
             dst[k] = src[xb];
-            if (++xb == p.row_bytes && k + 1 < n) xb = 0, src = p.in + slot[++i] * tile_stride + row_off; // the same row of the next tile of the grid
+            if (++xb == p.row_bytes && k + 1 < st.n) xb = 0, src = p.in + slot[++i] * tile_stride + row_off; // the same row of the next tile of the grid
         }
     }
 }
@@ -83,8 +71,7 @@ hipError_t launch_merge_tiles_regions(const uint8_t *tiles, uint32_t channels, u
     RegionsArgs p{};
     p.in = tiles, p.out = out, p.table = table;
     p.n_regions = n_regions, p.nx = nx, p.tile_h = tile_h, p.row_bytes = tile_w * channels;
-    if (channels == 3) hipLaunchKernelGGL(merge_tiles_regions_kernel<3>, dim3(n_groups), dim3(kRegionsThreads), 0, stream, p);
-    else hipLaunchKernelGGL(merge_tiles_regions_kernel<1>, dim3(n_groups), dim3(kRegionsThreads), 0, stream, p);
+    FRI_RASTER_LAUNCH_C(merge_tiles_regions_kernel, channels, n_groups, stream, p);
     return hipGetLastError();
 }
 

@@ -11,13 +11,15 @@
 // All are the target's unaligned global accesses, so every buffer starts at any byte. A strip that reaches past the image row (the replicated edge) or crosses a
 // tile column, and a row's last, partial strip go pixel by pixel. Every output byte is written once; no atomics, no LDS. Every byte offset is 64-bit: 4 W H can
 // pass 2^32.
+// The strip locators (strip_of, region_strip_of) are raster_common.hpp's, the ones K10 uses with bytes; the shape's limits and the region check are raster_launch.hpp's.
+#include "raster_launch.hpp"
 #include "rgba_shuffle.hpp"
 
 namespace fri {
 namespace {
 
-constexpr int kTileRgbaThreads = 256;
-constexpr uint32_t kTileRgbaStrip = 16; // pixels per lane
+constexpr int kTileRgbaThreads = kRasterThreads;
+constexpr uint32_t kTileRgbaStrip = kRasterStrip; // pixels per lane
 
 struct SplitTilesRgbaArgs {
     const uint8_t *rgba;
@@ -31,11 +33,9 @@ template <bool CLEAN>
 __global__ void __launch_bounds__(kTileRgbaThreads) split_tiles_rgba_kernel(const SplitTilesRgbaArgs p) {
     const uint32_t g = blockIdx.x * kTileRgbaThreads + threadIdx.x;
     if (g >= p.n_strips) return;
-    const uint32_t row = g / p.strips_per_row, x0 = (g - row * p.strips_per_row) * kTileRgbaStrip; // row = t tile_h + y
-    const uint32_t t = row / p.tile_h, y = row - t * p.tile_h;
-    const uint32_t j = t / p.nx, i = t - j * p.nx;
-    const uint32_t n = min(kTileRgbaStrip, p.tile_w - x0);
-    const uint32_t gy = min(j * p.tile_h + y, p.height - 1), gx0 = i * p.tile_w + x0; // the strip's first pixel in the image, its column unclamped
+    const TileStrip st = strip_of(g, p.strips_per_row, p.tile_h, p.nx);
+    const uint32_t row = st.row, x0 = st.u0, n = strip_units(p.tile_w, x0);
+    const uint32_t gy = min(st.j * p.tile_h + st.y, p.height - 1), gx0 = st.i * p.tile_w + x0; // the strip's first pixel in the image, its column unclamped
     const uint8_t *src_row = p.rgba + (uint64_t)gy * p.width * 4;
     const uint64_t first = (uint64_t)row * p.tile_w + x0; // the strip's first pixel in the tile rasters
     uint8_t *rgb = p.colour + first * 3, *al = p.alpha + first;
@@ -69,18 +69,15 @@ struct MergeTilesRgbaArgs {
 __global__ void __launch_bounds__(kTileRgbaThreads) merge_tiles_rgba_region_kernel(const MergeTilesRgbaArgs p) {
     const uint32_t g = blockIdx.x * kTileRgbaThreads + threadIdx.x;
     if (g >= p.n_strips) return;
-    const uint32_t ry = g / p.strips_per_row, x0 = (g - ry * p.strips_per_row) * kTileRgbaStrip;
-    const uint32_t n = min(kTileRgbaStrip, p.region_w - x0);
-    const uint32_t gy = p.oy + ry, b = gy / p.tile_h, y = gy - b * p.tile_h; // row y of the tiles of sub-grid row b
-    const uint32_t gx = p.ox + x0;                                           // the strip's first pixel in the sub-grid's row: < ni tile_w
-    uint32_t a = gx / p.tile_w, xp = gx - a * p.tile_w;                      // pixel xp of the row of tile (b, a)
-    const uint64_t tile_stride = (uint64_t)p.tile_h * p.tile_w;              // pixels
-    uint64_t at = ((uint64_t)b * p.ni + a) * tile_stride + (uint64_t)y * p.tile_w; // the first pixel of that tile row in the tile rasters
-    uint8_t *dst = p.out + ((uint64_t)ry * p.region_w + x0) * 4;
-    if (n == kTileRgbaStrip && xp + kTileRgbaStrip <= p.tile_w) {
+    const RegionStrip st = region_strip_of(g, p.strips_per_row, p.region_w, p.ox, p.oy, p.tile_w, p.tile_h);
+    const uint64_t tile_stride = (uint64_t)p.tile_h * p.tile_w;                                // pixels
+    uint64_t at = ((uint64_t)st.b * p.ni + st.a) * tile_stride + (uint64_t)st.y * p.tile_w;    // the first pixel of that tile row in the tile rasters
+    uint32_t xp = st.xu;
+    uint8_t *dst = p.out + ((uint64_t)st.ry * p.region_w + st.u0) * 4;
+    if (st.n == kRasterStrip && st.xu + kRasterStrip <= p.tile_w) {
         rgba_merge_strip(p.colour + (at + xp) * 3, p.alpha + at + xp, dst);
     } else { // the strip crosses a tile column, or is the row's last
-        for (uint32_t k = 0; k < n; k++) {
+        for (uint32_t k = 0; k < st.n; k++) {
             const uint8_t *rgb = p.colour + (at + xp) * 3;
             dst[4 * k] = rgb[0], dst[4 * k + 1] = rgb[1], dst[4 * k + 2] = rgb[2];
             dst[4 * k + 3] = p.alpha[at + xp];
@@ -89,29 +86,20 @@ __global__ void __launch_bounds__(kTileRgbaThreads) merge_tiles_rgba_region_kern
     }
 }
 
-// The shape's limits, K10's: a row of the image and of the grid fits 31 and 32 bits of bytes, and the tile rasters' strips one u32 index per lane
-bool shape_ok(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint64_t &nx, uint64_t &ny, uint64_t &strips_per_row, uint64_t &n_strips) {
-    if (!width || !height || !tile_w || !tile_h) return false;
-    nx = ((uint64_t)width + tile_w - 1) / tile_w, ny = ((uint64_t)height + tile_h - 1) / tile_h;
-    if ((uint64_t)tile_w * 4 > 0x7FFFFFFFull || (uint64_t)width * 4 > 0x7FFFFFFFull || nx * tile_w * 4 > 0xFFFFFFFFull || ny * tile_h > 0xFFFFFFFFull) return false;
-    strips_per_row = ((uint64_t)tile_w + kTileRgbaStrip - 1) / kTileRgbaStrip;
-    const uint64_t rows = nx * ny * tile_h;
-    if (rows > 0xFFFFFFFFull || rows * strips_per_row > 0xFFFFFFFFull - kTileRgbaThreads) return false;
-    n_strips = rows * strips_per_row;
-    return true;
-}
+// The shape's limits are the tile grid's (raster_launch.hpp) with the four bytes of an R, G, B, A pixel, its strips counted in pixels
+bool shape_ok(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, raster::TileGrid &g) { return raster::tile_grid(width, height, tile_w, tile_h, 4, 1, g); }
 
 } // namespace
 
 hipError_t launch_split_tiles_rgba(const uint8_t *rgba, uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, bool clean, uint8_t *colour_tiles, uint8_t *alpha_tiles,
                                    hipStream_t stream) {
-    uint64_t nx, ny, spr, n_strips;
-    if (!rgba || !colour_tiles || !alpha_tiles || !shape_ok(width, height, tile_w, tile_h, nx, ny, spr, n_strips)) return hipErrorInvalidValue;
+    raster::TileGrid g;
+    if (!rgba || !colour_tiles || !alpha_tiles || !shape_ok(width, height, tile_w, tile_h, g)) return hipErrorInvalidValue;
     SplitTilesRgbaArgs p{};
     p.rgba = rgba, p.colour = colour_tiles, p.alpha = alpha_tiles;
-    p.width = width, p.height = height, p.tile_w = tile_w, p.tile_h = tile_h, p.nx = (uint32_t)nx;
-    p.strips_per_row = (uint32_t)spr, p.n_strips = (uint32_t)n_strips;
-    const uint32_t groups = (uint32_t)((n_strips + kTileRgbaThreads - 1) / kTileRgbaThreads);
+    p.width = width, p.height = height, p.tile_w = tile_w, p.tile_h = tile_h, p.nx = g.nx;
+    p.strips_per_row = g.strips_per_row, p.n_strips = g.n_strips;
+    const uint32_t groups = g.groups;
     if (clean) hipLaunchKernelGGL(split_tiles_rgba_kernel<true>, dim3(groups), dim3(kTileRgbaThreads), 0, stream, p);
     else hipLaunchKernelGGL(split_tiles_rgba_kernel<false>, dim3(groups), dim3(kTileRgbaThreads), 0, stream, p);
     return hipGetLastError();
@@ -119,20 +107,18 @@ hipError_t launch_split_tiles_rgba(const uint8_t *rgba, uint32_t width, uint32_t
 
 hipError_t launch_merge_tiles_rgba_region(const uint8_t *colour_tiles, const uint8_t *alpha_tiles, uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t x,
                                           uint32_t y, uint32_t w, uint32_t h, uint8_t *region, hipStream_t stream) {
-    uint64_t nx, ny, spr, whole_strips;
-    if (!colour_tiles || !alpha_tiles || !region || !shape_ok(width, height, tile_w, tile_h, nx, ny, spr, whole_strips)) return hipErrorInvalidValue;
-    if (!w || !h || (uint64_t)x + w > width || (uint64_t)y + h > height) return hipErrorInvalidValue;
-    const uint32_t i0 = x / tile_w, j0 = y / tile_h;
+    raster::TileGrid whole;
+    raster::SubGrid s;
+    if (!colour_tiles || !alpha_tiles || !region || !shape_ok(width, height, tile_w, tile_h, whole)) return hipErrorInvalidValue;
+    if (!raster::sub_grid_of(width, height, tile_w, tile_h, x, y, w, h, s)) return hipErrorInvalidValue;
     MergeTilesRgbaArgs p{};
     p.colour = colour_tiles, p.alpha = alpha_tiles, p.out = region;
-    p.tile_w = tile_w, p.tile_h = tile_h, p.ni = (x + w - 1) / tile_w - i0 + 1;
-    p.ox = x - i0 * tile_w, p.oy = y - j0 * tile_h;
+    p.tile_w = tile_w, p.tile_h = tile_h, p.ni = s.ni;
+    p.ox = s.ox, p.oy = s.oy;
     p.region_w = w;
-    p.strips_per_row = (w + kTileRgbaStrip - 1) / kTileRgbaStrip;
-    const uint64_t n_strips = (uint64_t)h * p.strips_per_row;
-    if (n_strips > 0xFFFFFFFFull - kTileRgbaThreads) return hipErrorInvalidValue; // (one u32 strip index per lane)
-    p.n_strips = (uint32_t)n_strips;
-    const uint32_t groups = (uint32_t)((n_strips + kTileRgbaThreads - 1) / kTileRgbaThreads);
+    p.strips_per_row = (uint32_t)raster::strips_of(w);
+    uint32_t groups = 0;
+    if (!raster::groups_of((uint64_t)h * p.strips_per_row, raster::kMaxStrips, p.n_strips, groups)) return hipErrorInvalidValue; // (one u32 strip index per lane)
     hipLaunchKernelGGL(merge_tiles_rgba_region_kernel, dim3(groups), dim3(kTileRgbaThreads), 0, stream, p);
     return hipGetLastError();
 }

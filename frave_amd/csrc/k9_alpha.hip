@@ -7,13 +7,15 @@
 // R, G, B, A as four 16-byte accesses, 48 bytes of R, G, B as three and 16 bytes of A as one. The bytes change places in registers with v_perm_b32
 // (rgba_shuffle.hpp, shared with K16) - four pixels are four dwords on one side and three + one on the other - and CLEAN is one select per pixel. The
 // buffers start at any byte: the vector accesses are the target's unaligned global loads and stores (the compiler is told the alignment is 1). Only the last strip, when N is no multiple of 16, is walked byte by byte. Every byte offset is 64-bit: 4 W H can pass 2^32.
+// The 16-byte accesses are raster_common.hpp's, the strips-to-workgroups rule raster_launch.hpp's.
+#include "raster_launch.hpp"
 #include "rgba_shuffle.hpp"
 
 namespace fri {
 namespace {
 
-constexpr int kAlphaThreads = 256;
-constexpr int kAlphaStrip = 16; // pixels per lane
+constexpr int kAlphaThreads = kRasterThreads;
+constexpr int kAlphaStrip = (int)kRasterStrip; // pixels per lane
 
 struct RgbaArgs {
     const uint8_t *in0, *in1; // split: rgba, -; merge: rgb, a
@@ -63,14 +65,10 @@ __global__ void __launch_bounds__(kAlphaThreads) merge_rgba_kernel(const RgbaArg
     }
 }
 
-// N pixels as a 1-D grid of kAlphaThreads-thread workgroups, one strip per lane; false when the shape does not fit one
+// N pixels as a 1-D grid, one strip per lane; false when the shape does not fit one
 bool grid_of(uint32_t width, uint32_t height, RgbaArgs &p, uint32_t &groups) {
     p.n_pixels = (uint64_t)width * height;
-    const uint64_t strips = (p.n_pixels + kAlphaStrip - 1) / kAlphaStrip;
-    if (!width || !height || strips > 0x7FFFFFFFull) return false;
-    p.n_strips = (uint32_t)strips;
-    groups = (uint32_t)((strips + kAlphaThreads - 1) / kAlphaThreads);
-    return true;
+    return width && height && raster::groups_of(raster::strips_of(p.n_pixels), raster::kMaxStrips31, p.n_strips, groups);
 }
 
 } // namespace

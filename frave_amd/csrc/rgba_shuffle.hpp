@@ -1,21 +1,10 @@
 // rgba_shuffle.hpp -- the two byte shuffles of RGBA coding, shared by K9 (k9_alpha.hip) and K16 (k16_tiles_rgba.hip): 16 pixels of interleaved R, G, B, A as 16
 // dwords <-> the same pixels as 12 dwords of R, G, B and 4 dwords of A, with v_perm_b32 (__builtin_amdgcn_perm(a, b, sel): selector values 0..3 take a byte of
-// b, 4..7 a byte of a). Four pixels are four dwords on one side and three + one on the other. And the unaligned 16-byte accesses both kernels use.
+// b, 4..7 a byte of a). Four pixels are four dwords on one side and three + one on the other. The 16-byte accesses around them are raster_common.hpp's.
 #pragma once
-#include "device_common.hpp"
+#include "raster_common.hpp"
 
 namespace fri {
-
-template <typename V>
-__device__ __forceinline__ V rgba_load_unaligned(const uint8_t *p) {
-    V v;
-    __builtin_memcpy(&v, p, sizeof(V));
-    return v;
-}
-template <typename V>
-__device__ __forceinline__ void rgba_store_unaligned(uint8_t *p, const V &v) {
-    __builtin_memcpy(p, &v, sizeof(V));
-}
 
 // CLEAN: a pixel with A == 0 gets R = G = B = 0
 template <bool CLEAN>
@@ -46,13 +35,13 @@ __device__ __forceinline__ void rgba_merge16(const uint32_t (&c)[12], const uint
     }
 }
 
-// 16 pixels of R, G, B, A at src (64 bytes, any alignment) -> 48 bytes at rgb and 16 at al
+// 16 pixels of R, G, B, A at src (64 bytes, any alignment) -> 48 bytes at rgb and 16 at al. (Written out: with load_dwords / store_dwords K9's and K16's splits compile differently.)
 template <bool CLEAN>
 __device__ __forceinline__ void rgba_split_strip(const uint8_t *src, uint8_t *rgb, uint8_t *al) {
     uint32_t px[16];
 #pragma unroll
     for (int q = 0; q < 4; q++) {
-        const u32x4 v = rgba_load_unaligned<u32x4>(src + 16 * q);
+        const u32x4 v = load_unaligned<u32x4>(src + 16 * q);
         px[4 * q] = v.x, px[4 * q + 1] = v.y, px[4 * q + 2] = v.z, px[4 * q + 3] = v.w;
     }
     uint32_t c[12], a[4];
@@ -60,29 +49,19 @@ __device__ __forceinline__ void rgba_split_strip(const uint8_t *src, uint8_t *rg
 #pragma unroll
     for (int q = 0; q < 3; q++) {
         const u32x4 v = {c[4 * q], c[4 * q + 1], c[4 * q + 2], c[4 * q + 3]};
-        rgba_store_unaligned(rgb + 16 * q, v);
+        store_unaligned(rgb + 16 * q, v);
     }
     const u32x4 v = {a[0], a[1], a[2], a[3]};
-    rgba_store_unaligned(al, v);
+    store_unaligned(al, v);
 }
 
 // the inverse: 48 bytes at rgb and 16 at al -> 16 pixels of R, G, B, A at dst
 __device__ __forceinline__ void rgba_merge_strip(const uint8_t *rgb, const uint8_t *al, uint8_t *dst) {
-    uint32_t c[12];
-#pragma unroll
-    for (int q = 0; q < 3; q++) {
-        const u32x4 v = rgba_load_unaligned<u32x4>(rgb + 16 * q);
-        c[4 * q] = v.x, c[4 * q + 1] = v.y, c[4 * q + 2] = v.z, c[4 * q + 3] = v.w;
-    }
-    const u32x4 av = rgba_load_unaligned<u32x4>(al);
-    const uint32_t a[4] = {av.x, av.y, av.z, av.w};
-    uint32_t px[16];
+    uint32_t c[12], a[4], px[16];
+    load_dwords(rgb, c);
+    load_dwords(al, a);
     rgba_merge16(c, a, px);
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const u32x4 v = {px[4 * q], px[4 * q + 1], px[4 * q + 2], px[4 * q + 3]};
-        rgba_store_unaligned(dst + 16 * q, v);
-    }
+    store_dwords(dst, px);
 }
 
 } // namespace fri
