@@ -57,6 +57,7 @@ SYMBOLS = [
     "fri_hip_preview_image_tiled_coded",
     "fri_hip_plan_tiled_regions", "fri_hip_merge_tiles_regions_dev", "fri_hip_decode_regions_tiled_dev", "fri_hip_decode_regions_tiled",
     "fri_hip_decode_regions_tiled_coded",
+    "fri_hip_plan_tiled_preview_regions", "fri_hip_preview_tiles_regions_dev", "fri_hip_preview_regions_tiled", "fri_hip_preview_regions_tiled_coded",
     "fri_hip_plan_tiled_rgba_create", "fri_hip_plan_tiled_rgba_destroy", "fri_hip_plan_tiled_rgba_colour", "fri_hip_plan_tiled_rgba_alpha", "fri_hip_plan_tiled_rgba_grid",
     "fri_hip_plan_tiled_rgba_region", "fri_hip_plan_tiled_rgba_buffer_tiles", "fri_hip_split_tiles_rgba_dev", "fri_hip_merge_tiles_rgba_dev",
     "fri_hip_merge_tiles_rgba_region_dev", "fri_hip_encode_symbols_tiled_rgba_dev", "fri_hip_encode_image_tiled_rgba_symbols", "fri_hip_decode_image_tiled_rgba",
@@ -321,6 +322,10 @@ def load_library():
     L.fri_hip_preview_tiles_dev.argtypes = [vp, vp, sz, u32, u32, u32, vp, vp, vp]
     L.fri_hip_preview_image_tiled.argtypes = [vp, vp, u32, u32, vp, vp]
     L.fri_hip_preview_image_tiled_coded.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, u32, u32, vp, vp, vp]
+    L.fri_hip_plan_tiled_preview_regions.argtypes = [vp, u32, u32, vp, vp, sz, vp, vp, sz]
+    L.fri_hip_preview_tiles_regions_dev.argtypes = [vp, vp, sz, u32, u32, u32, vp, u32, u32, vp, vp, vp]
+    L.fri_hip_preview_regions_tiled.argtypes = [vp, vp, u32, u32, vp, u32, vp, vp]
+    L.fri_hip_preview_regions_tiled_coded.argtypes = [vp, u32, vp, vp, sz, vp, vp, vp, vp, vp, u32, u32, vp, vp, vp]
     _lib = L
     return L
 
@@ -1418,6 +1423,63 @@ class PlanTiled:
                                                                _p(_q(qmatrix)), _p(out), _p(status))
         try:
             _check_decode(rc, "fri_hip_decode_regions_tiled_coded", self.ctx, status)
+        except FriHipError as e:
+            bad = np.flatnonzero(status[:, 0])
+            e.tile = int(tiles[bad[0] // self.channels]) if bad.size else None
+            raise
+        return self._split_regions(out, rg), status
+
+    # ---- preview of regions: several rectangles of the thumbnail in one call (K17) ---------------------
+    def preview_regions_table(self, shift, regions):
+        """fri_hip_plan_tiled_preview_regions: (list uint32 [T], table uint32 [8 (R + 1) + nx ny]) of `regions` [(X, Y, w, h), ...] in the coordinates of the
+        thumbnail at `shift` - the tile list of their source rectangles and the preview-region table K17 reads (include/fri_hip.h, "Preview of regions"; its row R
+        holds the packed output's bytes in words 4, 5 and n_groups in word 6). Works on a host-only plan. FriHipError (-1) for shift > 4, no regions, more than
+        65535, a region that is empty or leaves the thumbnail, n_groups >= 2^31. The plan remembers the last such table: preview_tiles_regions_dev takes that one."""
+        rg = self._regions(regions)
+        n = C.c_size_t(0)
+        L = load_library()
+        rc = L.fri_hip_plan_tiled_preview_regions(self._h, int(shift), rg.shape[0], _p(rg), None, 0, C.addressof(n), None, 0)
+        if rc != -3:  # (the size query's answer: the buffers are too small, n is filled)
+            _check(rc or -1, "fri_hip_plan_tiled_preview_regions", self.ctx)
+        tiles, table = np.zeros(n.value, np.uint32), np.zeros(8 * (rg.shape[0] + 1) + self.n_tiles, np.uint32)
+        _check(L.fri_hip_plan_tiled_preview_regions(self._h, int(shift), rg.shape[0], _p(rg), _p(tiles), tiles.size, C.addressof(n), _p(table), table.size),
+               "fri_hip_plan_tiled_preview_regions", self.ctx)
+        return tiles, table
+
+    def preview_tiles_regions_dev(self, d_coefs, coef_stride, node_stride, levels, shift, n_list, n_regions, d_table, d_out, qmatrix=None, stream=0):
+        """fri_hip_preview_tiles_regions_dev (K17 alone), device pointers as ints: the listed tiles' planes [T][C] coef_stride elements apart, node h of cell k at
+        k * node_stride + h (node_stride 512 or 2^levels) -> the packed region rasters, any alignment. d_table must be, in device memory, the table
+        preview_regions_table() LAST returned on this plan, n_list, n_regions and shift its T, R and m. Only enqueues; capturable."""
+        _check(load_library().fri_hip_preview_tiles_regions_dev(self._h, d_coefs, coef_stride, node_stride, int(levels), int(shift), _p(_q(qmatrix)), int(n_list), int(n_regions),
+                                                                d_table, d_out, stream), "fri_hip_preview_tiles_regions_dev", self.ctx)
+
+    def preview_regions(self, coefs, levels, shift, regions, qmatrix=None):
+        """fri_hip_preview_regions_tiled: the compact planes int32 [T][C][F][2^levels] (what emit.tiled_decode_tiles_levels returns for preview_regions_table()'s list)
+        -> a list of uint8 [h][w][C] arrays, one per region: each the crop [Y : Y + h, X : X + w] of what preview() returns for the same file, levels and shift."""
+        rg = self._regions(regions)
+        tiles, table = self.preview_regions_table(shift, rg)
+        co = np.ascontiguousarray(coefs, np.int32).reshape(-1)
+        assert not 0 <= levels <= 9 or co.size == tiles.size * self.channels * self.num_cells << levels  # (levels out of range: the library's refusal)
+        out = np.empty(int(table[8 * rg.shape[0] + 4]) | int(table[8 * rg.shape[0] + 5]) << 32, np.uint8)
+        _check(load_library().fri_hip_preview_regions_tiled(self._h, _p(co), int(levels), int(shift), _p(_q(qmatrix)), rg.shape[0], _p(rg), _p(out)),
+               "fri_hip_preview_regions_tiled", self.ctx)
+        return self._split_regions(out, rg)
+
+    def preview_regions_coded(self, coded, levels, shift, regions, qmatrix=None):
+        """fri_hip_preview_regions_tiled_coded: the coded planes of preview_regions_table()'s tile list - what emit.tiled_parse_coded_tiles returns, with or without
+        its TiledInfo - through the device decoder bounded by `levels` over the T C planes and K17 -> (a list of uint8 [h][w][C] arrays, status uint32 [T C][4]); the
+        arrays are preview_regions()'s of emit.tiled_decode_tiles_levels's planes. A plane the decoder refuses raises FriHipError (-1) with the status as .status
+        and the file-grid index of the first refused plane's tile as .tile. Needs set_stream_order()."""
+        rg = self._regions(regions)
+        tiles, table = self.preview_regions_table(shift, rg)
+        planes = tiles.size * self.channels
+        words, n_words, models, off, vp, wp = _coded_planes(coded, planes)
+        out = np.empty(int(table[8 * rg.shape[0] + 4]) | int(table[8 * rg.shape[0] + 5]) << 32, np.uint8)
+        status = np.zeros((planes, 4), np.uint32)
+        rc = load_library().fri_hip_preview_regions_tiled_coded(self._h, rg.shape[0], _p(rg), _p(words), words.shape[1], _p(n_words), _p(models), _p(off), _p(vp), _p(wp),
+                                                                int(levels), int(shift), _p(_q(qmatrix)), _p(out), _p(status))
+        try:
+            _check_decode(rc, "fri_hip_preview_regions_tiled_coded", self.ctx, status)
         except FriHipError as e:
             bad = np.flatnonzero(status[:, 0])
             e.tile = int(tiles[bad[0] // self.channels]) if bad.size else None

@@ -1,5 +1,5 @@
 // fri_hip_tiled.cpp -- the tiled plan kind of the C ABI (fri_hip_plan_tiled: include/fri_hip.h): the plan and its grid, split and merge, the encode chain and
-// its coded form (K11), the image and region decodes, several regions in one call (K15) and the decode from coded planes (K13), the preview decode (K14), the measure, the size estimate and the quality searches. Host-side glue like fri_hip.cpp, on one ordinary
+// its coded form (K11), the image and region decodes, several regions in one call (K15) and the decode from coded planes (K13), the preview decode (K14) and the preview of regions (K17), the measure, the size estimate and the quality searches. Host-side glue like fri_hip.cpp, on one ordinary
 // plan of the tile's shape. The grid, plan creation, the host size estimate and the coded route are tiled_common.hpp's, shared with fri_hip_tiled420.cpp; the
 // searches are TiledSearch on search_scaffold.hpp.
 #include "search_scaffold.hpp"
@@ -40,6 +40,11 @@ struct fri_hip_plan_tiled {
     struct {
         uint32_t n_regions = 0, n_list = 0, n_groups = 0;
     } planned;
+    // the same for the last table fri_hip_plan_tiled_preview_regions wrote (fri_hip_preview_tiles_regions_dev): a memory of its own, so that neither kind of
+    // table changes what the other kind's kernel entry accepts
+    struct {
+        uint32_t n_regions = 0, n_list = 0, n_groups = 0, shift = 0;
+    } planned_preview;
     size_t n_tiles() const { return grid.n_tiles(); }
     size_t raster_bytes() const { return (size_t)grid.width * grid.height * channels; }
     size_t tile_bytes() const { return (size_t)grid.tile_w * grid.tile_h * channels; }
@@ -288,6 +293,17 @@ struct RegionsPlan {
     uint32_t n_groups = 0;
     uint64_t total = 0; // off_R
 };
+// the end of both kinds of table: row R, and slot[] from the marks the regions left in it - the tile list in ascending order
+void finish_regions_plan(RegionsPlan &out, uint32_t n_regions, size_t n_grid, uint64_t total, uint64_t groups) {
+    uint32_t *last = out.table.data() + 8 * (size_t)n_regions, *slot = last + 8;
+    last[4] = (uint32_t)total, last[5] = (uint32_t)(total >> 32), last[6] = (uint32_t)groups;
+    out.list.clear();
+    for (size_t t = 0; t < n_grid; t++) {
+        if (slot[t]) slot[t] = (uint32_t)out.list.size(), out.list.push_back((uint32_t)t);
+        else slot[t] = 0xFFFFFFFFu;
+    }
+    out.n_groups = (uint32_t)groups, out.total = total;
+}
 // false for R = 0, R > 65535, a region the grid refuses and n_groups >= 2^31
 bool plan_regions(const fri_hip_plan_tiled *p, uint32_t n_regions, const uint32_t *regions, RegionsPlan &out) {
     const TileGrid &g = p->grid;
@@ -309,14 +325,7 @@ bool plan_regions(const fri_hip_plan_tiled *p, uint32_t n_regions, const uint32_
         groups += ((uint64_t)q[3] * strips + 255) / 256;
         if (groups >= 0x80000000ull) return false; // (w C < 2^31 and h < 2^32: neither sum can have wrapped before this is seen)
     }
-    uint32_t *last = out.table.data() + 8 * (size_t)n_regions;
-    last[4] = (uint32_t)off, last[5] = (uint32_t)(off >> 32), last[6] = (uint32_t)groups;
-    out.list.clear();
-    for (size_t t = 0; t < n_grid; t++) {
-        if (slot[t]) slot[t] = (uint32_t)out.list.size(), out.list.push_back((uint32_t)t);
-        else slot[t] = 0xFFFFFFFFu;
-    }
-    out.n_groups = (uint32_t)groups, out.total = off;
+    finish_regions_plan(out, n_regions, n_grid, off, groups);
     return true;
 }
 void remember(fri_hip_plan_tiled *p, uint32_t n_regions, const RegionsPlan &r) {
@@ -642,6 +651,133 @@ int fri_hip_preview_image_tiled_coded(fri_hip_plan_tiled *p, const uint32_t *wor
     if ((rc = fri_hip_preview_tiles_dev(p, p->coefs, image / p->channels, kCell, levels, shift, qmatrix, p->preview, nullptr))) return rc;
     HIP_TRY(c, hipMemcpy(pixels, p->preview, bytes, hipMemcpyDeviceToHost));
     return FRI_HIP_OK;
+}
+
+/* ---- preview of regions: the tile list of the source rectangles, the preview-region table and K17 ---- */
+namespace {
+// What R regions of the thumbnail at `shift` make on the plan's grid (include/fri_hip.h, "Preview of regions"): the tile list of their source rectangles, the
+// preview-region table, its n_groups and the packed output's bytes. false for shift > 4, R = 0, R > 65535, a region that is empty or leaves the thumbnail and
+// n_groups >= 2^31.
+bool plan_preview_regions(const fri_hip_plan_tiled *p, uint32_t shift, uint32_t n_regions, const uint32_t *regions, RegionsPlan &out) {
+    const TileGrid &g = p->grid;
+    uint32_t size[2];
+    if (!regions || !n_regions || n_regions > 65535u || fri_hip_preview_size(g.width, g.height, shift, size)) return false;
+    const size_t n_grid = g.n_tiles(), rows = 8 * ((size_t)n_regions + 1);
+    out.table.assign(rows + n_grid, 0);
+    uint32_t *slot = out.table.data() + rows;
+    const uint64_t S = 1ull << shift;
+    const auto xs = [&](uint64_t X) { return (uint32_t)std::min<uint64_t>(X * S + S / 2, (uint64_t)g.width - 1); };
+    const auto ys = [&](uint64_t Y) { return (uint32_t)std::min<uint64_t>(Y * S + S / 2, (uint64_t)g.height - 1); };
+    uint64_t off = 0, groups = 0;
+    for (uint32_t r = 0; r < n_regions; r++) {
+        const uint32_t *q = regions + 4 * (size_t)r;
+        if (!q[2] || !q[3] || (uint64_t)q[0] + q[2] > size[0] || (uint64_t)q[1] + q[3] > size[1]) return false;
+        const uint32_t x0 = xs(q[0]), y0 = ys(q[1]);
+        uint32_t range[4];
+        if (g.region(x0, y0, xs((uint64_t)q[0] + q[2] - 1) - x0 + 1, ys((uint64_t)q[1] + q[3] - 1) - y0 + 1, range)) return false; // the source rectangle
+        for (uint32_t b = 0; b < range[3]; b++) std::fill_n(slot + ((size_t)range[1] + b) * g.nx + range[0], range[2], 1u); // touched
+        const uint32_t blocks_x = (uint32_t)(((uint64_t)q[2] + 15) / 16);
+        uint32_t *row = out.table.data() + 8 * (size_t)r;
+        row[0] = q[0], row[1] = q[1], row[2] = q[2], row[3] = q[3];
+        row[4] = (uint32_t)off, row[5] = (uint32_t)(off >> 32), row[6] = (uint32_t)groups, row[7] = blocks_x;
+        off += (uint64_t)q[2] * q[3] * p->channels;
+        groups += (uint64_t)blocks_x * (((uint64_t)q[3] + 15) / 16);
+        if (groups >= 0x80000000ull) return false; // (each term is below 2^56: the sum cannot have wrapped before this is seen)
+    }
+    finish_regions_plan(out, n_regions, n_grid, off, groups);
+    return true;
+}
+void remember_preview(fri_hip_plan_tiled *p, uint32_t shift, uint32_t n_regions, const RegionsPlan &r) {
+    p->planned_preview.n_regions = n_regions, p->planned_preview.n_list = (uint32_t)r.list.size(), p->planned_preview.n_groups = r.n_groups, p->planned_preview.shift = shift;
+}
+// the table up on the null stream, K17 over the plan's coefficient buffer into its packed-output buffer, the rasters down
+int preview_regions_run(fri_hip_plan_tiled *p, const RegionsPlan &r, size_t coef_stride, uint32_t node_stride, uint32_t levels, uint32_t shift, const int32_t qmatrix[32],
+                        uint32_t n_regions, uint8_t *pixels) {
+    fri_hip_ctx *c = p->ctx;
+    HIP_TRY(c, hipMemcpy(p->region_table, r.table.data(), r.table.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    remember_preview(p, shift, n_regions, r);
+    if (int rc = fri_hip_preview_tiles_regions_dev(p, p->coefs, coef_stride, node_stride, levels, shift, qmatrix, (uint32_t)r.list.size(), n_regions, p->region_table,
+                                                   p->regions_out, nullptr))
+        return rc;
+    HIP_TRY(c, hipMemcpy(pixels, p->regions_out, (size_t)r.total, hipMemcpyDeviceToHost));
+    return FRI_HIP_OK;
+}
+} // namespace
+
+int fri_hip_plan_tiled_preview_regions(fri_hip_plan_tiled *p, uint32_t shift, uint32_t n_regions, const uint32_t *regions, uint32_t *list, size_t list_cap, size_t *n_list,
+                                       uint32_t *table, size_t table_cap_words) {
+    RegionsPlan r;
+    if (!p || !n_list || !plan_preview_regions(p, shift, n_regions, regions, r)) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    *n_list = r.list.size();
+    if (!list || list_cap < r.list.size() || !table || table_cap_words < r.table.size()) return -3; // the size query, as in fri_hip_plan_tiled_regions
+    std::copy(r.list.begin(), r.list.end(), list);
+    std::copy(r.table.begin(), r.table.end(), table);
+    remember_preview(p, shift, n_regions, r);
+    return FRI_HIP_OK;
+}
+
+int fri_hip_preview_tiles_regions_dev(fri_hip_plan_tiled *p, const int32_t *d_coefs, size_t coef_stride, uint32_t node_stride, uint32_t levels, uint32_t shift,
+                                      const int32_t qmatrix[32], uint32_t n_list, uint32_t n_regions, const uint32_t *d_table, uint8_t *d_out, void *stream) {
+    if (!p || !d_coefs || !qmatrix || !d_table || !d_out || !preview_args_ok(levels, shift) || !n_list || n_list > p->n_tiles() || !n_regions || n_regions > 65535u ||
+        (node_stride != (uint32_t)kCell && node_stride != (1u << levels)) || coef_stride < p->tile->geo.centers.size() * (size_t)node_stride)
+        return FRI_HIP_ERR_INVALID_ARGUMENT;
+    if (int rc = need_device(p)) return rc;
+    if (!p->owner) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    if (p->planned_preview.n_regions != n_regions || p->planned_preview.n_list != n_list || p->planned_preview.shift != shift) {
+        p->ctx->last_error =
+            "fri_hip_preview_tiles_regions_dev: d_table must hold the table fri_hip_plan_tiled_preview_regions last wrote on this plan (n_regions, n_list or shift differ)";
+        return FRI_HIP_ERR_INVALID_ARGUMENT;
+    }
+    QMatrix q;
+    if (int rc = check_q(qmatrix, q)) return rc;
+    HIP_TRY(p->ctx, hipSetDevice(p->ctx->device));
+    HIP_TRY(p->ctx, launch_preview_regions(p->tile->dev_inv, p->owner, p->grid.width, p->grid.height, p->grid.tile_w, p->grid.tile_h, d_coefs, coef_stride, node_stride, levels, shift,
+                                           q, n_list, n_regions, p->planned_preview.n_groups, d_table, d_out, (hipStream_t)stream));
+    return FRI_HIP_OK;
+}
+
+int fri_hip_preview_regions_tiled(fri_hip_plan_tiled *p, const int32_t *coefs, uint32_t levels, uint32_t shift, const int32_t qmatrix[32], uint32_t n_regions,
+                                  const uint32_t *regions, uint8_t *pixels) {
+    RegionsPlan r;
+    if (!p || !coefs || !qmatrix || !pixels || !preview_args_ok(levels, shift) || !plan_preview_regions(p, shift, n_regions, regions, r)) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    if (int rc = need_device(p)) return rc;
+    fri_hip_ctx *c = p->ctx;
+    HIP_TRY(c, hipSetDevice(c->device));
+    // the listed tiles' compact planes: the buffers grow to the regions' tiles, never to the image's
+    const size_t plane = p->tile->geo.centers.size() << levels, n = r.list.size() * p->channels * plane;
+    int rc;
+    if ((rc = grow(c, p->coefs, n)) || (rc = grow(c, p->region_table, r.table.size())) || (rc = grow(c, p->regions_out, (size_t)r.total))) return rc;
+    HIP_TRY(c, hipMemcpy(p->coefs, coefs, n * sizeof(int32_t), hipMemcpyHostToDevice)); // 2^(levels - 9) of fri_hip_decode_regions_tiled's upload
+    return preview_regions_run(p, r, plane, 1u << levels, levels, shift, qmatrix, n_regions, pixels);
+}
+
+int fri_hip_preview_regions_tiled_coded(fri_hip_plan_tiled *p, uint32_t n_regions, const uint32_t *regions, const uint32_t *words, size_t word_stride, const uint32_t *n_words,
+                                        const uint32_t *models, const uint16_t *off_values, const float *value_params, const float *width_params, uint32_t levels,
+                                        uint32_t shift, const int32_t qmatrix[32], uint8_t *pixels, uint32_t *status) {
+    RegionsPlan r;
+    const CodedPlanes in{words, word_stride, n_words, models, off_values, value_params, width_params};
+    if (!p || !in.complete() || !qmatrix || !pixels || !status || !preview_args_ok(levels, shift) || !plan_preview_regions(p, shift, n_regions, regions, r))
+        return FRI_HIP_ERR_INVALID_ARGUMENT;
+    if (int rc = need_device(p)) return rc;
+    if (!p->tile->d_stream_order) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    fri_hip_ctx *c = p->ctx;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t image = fri_hip_plan_coef_count(p->tile.get()), n = r.list.size(), planes = n * p->channels;
+    if (!decode_counts_ok((uint32_t)planes)) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    int rc;
+    if ((rc = grow(c, p->coefs, n * image)) || (rc = grow(c, p->region_table, r.table.size())) || (rc = grow(c, p->regions_out, (size_t)r.total))) return rc;
+    CodedOnDevice d;
+    if ((rc = upload_coded(p, in, planes, p->rans_words, d)) || (rc = decode_coded_batch(p->tile.get(), d, 0, planes, p->coefs, image / p->channels, levels))) return rc;
+    if ((rc = read_back_decode_status(c, d, status))) {
+        for (size_t k = 0; k < planes && rc == FRI_HIP_ERR_INVALID_ARGUMENT; k++)
+            if (status[4 * k]) { // the first refused plane, by its tile's index in the file's grid
+                c->last_error = "fri_hip_preview_regions_tiled_coded: tile " + std::to_string(r.list[k / p->channels]) + ": channel " + std::to_string(k % p->channels) +
+                                ": the device decoder refused the plane (status " + std::to_string(status[4 * k]) + ")";
+                break;
+            }
+        return rc;
+    }
+    return preview_regions_run(p, r, image / p->channels, kCell, levels, shift, qmatrix, n_regions, pixels);
 }
 
 } // extern "C"

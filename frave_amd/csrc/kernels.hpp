@@ -247,6 +247,15 @@ hipError_t launch_decode_planes(const DevicePlan &p, const uint32_t *order, uint
 hipError_t launch_preview_tiles(const DevicePlan &inner, const uint32_t *owner, uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, const int32_t *coefs,
                                 size_t coef_stride, uint32_t node_stride, uint32_t levels, uint32_t shift, const QMatrix &q, uint8_t *out, hipStream_t stream);
 
+// K17 (k17_preview_regions.hip): several regions of that thumbnail in one launch (include/fri_hip.h, "Preview of regions"). inner, owner, levels, shift, q and the
+// strides as for K14; coefs: the listed tiles' planes, plane (k, channel) at (k * C + channel) * coef_stride for tile list[k]; table: the preview-region table on the
+// device - rows [n_regions + 1][8], then slot[ny nx] - as the host wrote it, n_groups its row R's word 6; out: the packed region rasters, any alignment. One
+// workgroup per 16 x 16 block of one region, one thread per sample, every output byte written once, no atomics. hipErrorInvalidValue for what K14's launcher
+// refuses, n_list = 0, n_regions = 0 or > 65535, n_groups = 0 or >= 2^31. The table's contents are not checked: they are read on the device.
+hipError_t launch_preview_regions(const DevicePlan &inner, const uint32_t *owner, uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, const int32_t *coefs,
+                                  size_t coef_stride, uint32_t node_stride, uint32_t levels, uint32_t shift, const QMatrix &q, uint32_t n_list, uint32_t n_regions,
+                                  uint32_t n_groups, const uint32_t *table, uint8_t *out, hipStream_t stream);
+
 // K12 (k12_tiles420.hip): the raster kernels of tiled 4:2:0 coding (include/fri_hip.h has the format). Split: the image [H][W][3] -> y_tiles [n][tile_h][tile_w]
 // and c_tiles [n][2][ch][cw], n = ny nx, cw = (tile_w + 1) / 2, ch = (tile_h + 1) / 2: K10's edge replication and K8's split of every tile in one pass. Region
 // merge: the planes of the sub-grid a region touches, [nj ni]... -> the region raster [h][w][3], every pixel upsampled within its own tile; the region must lie

@@ -62,6 +62,8 @@ def load_library():
         L.fri_tiled_regions_tiles.argtypes = [u32, u32, u32, u32, u32, vp, vp, sz, vp]
         L.fri_tiled_decode_tiles.argtypes = [vp, sz, u32, vp, sz, vp, vp, sz, C.c_char_p, sz]
         L.fri_tiled_parse_coded_tiles.argtypes = [vp, sz, vp, sz, vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp, vp, vp, C.c_char_p, sz]
+        L.fri_tiled_preview_regions_tiles.argtypes = [u32, u32, u32, u32, u32, u32, vp, vp, sz, vp]
+        L.fri_tiled_decode_tiles_levels.argtypes = [vp, sz, u32, vp, sz, u32, vp, vp, sz, C.c_char_p, sz]
         _lib = L
     return _lib
 
@@ -581,6 +583,53 @@ def tiled_decode_tiles(frv, tiles, threads=0):
     ti = _tiled_info(info)
     coefs = _tiled_coefs(ti, tl.size)
     rc = L.fri_tiled_decode_tiles(_p(data), data.size, threads, _p(tl), tl.size, _p(info), _p(coefs), coefs.size, err, 256)
+    if rc != 0:
+        raise fail(rc)
+    return ti, coefs
+
+
+def tiled_preview_regions_tiles(width, height, tile_w, tile_h, shift, regions):
+    """fri_tiled_preview_regions_tiles: the tile list of `regions` [(X, Y, w, h), ...] given in the coordinates of the thumbnail at `shift` - uint32 [T], the tile list
+    tiled_regions_tiles makes of their source rectangles (include/fri_emit.h, "Preview of regions"). EmitError for no regions, a zero size, shift > 4 or a region
+    that is empty or leaves the thumbnail."""
+    rg = _regions(regions)
+    n = C.c_size_t(0)
+    L = load_library()
+    if not 0 <= int(shift) <= 0xFFFFFFFF:
+        raise EmitError("fri_tiled_preview_regions_tiles: shift must be 0..4")
+    rc = L.fri_tiled_preview_regions_tiles(width, height, tile_w, tile_h, int(shift), rg.shape[0], _p(rg), None, 0, C.addressof(n))
+    if rc != -3:
+        raise EmitError(f"fri_tiled_preview_regions_tiles: {rc}")
+    out = np.zeros(n.value, np.uint32)
+    rc = L.fri_tiled_preview_regions_tiles(width, height, tile_w, tile_h, int(shift), rg.shape[0], _p(rg), _p(out), out.size, C.addressof(n))
+    if rc != 0:
+        raise EmitError(f"fri_tiled_preview_regions_tiles: {rc}")
+    return out
+
+
+def tiled_decode_tiles_levels(frv, tiles, levels, threads=0):
+    """fri_tiled_decode_tiles_levels: (TiledInfo, compact coefs int32 [T][C][F][2^levels]) for the strictly ascending tile list `tiles`, in list order - tiled_decode_tiles
+    stopped behind the nodes with heap index < 2^levels; equal to tiled_decode_levels's planes at the listed tiles and to tiled_decode_tiles's sliced to
+    [..., :2^levels]. What PlanTiled.preview_regions takes. EmitError (with the C return value as .code) for levels > 9, a bad list, and a tiled 4:2:0 or RGBA file."""
+    data = np.frombuffer(frv, np.uint8)
+    tl = np.ascontiguousarray(tiles, np.uint32).reshape(-1)
+    info = np.zeros(8, np.uint32)
+    err = C.create_string_buffer(256)
+    L = load_library()
+
+    def fail(rc):
+        e = EmitError(err.value.decode() or f"fri_tiled_decode_tiles_levels: {rc}")
+        e.code = rc
+        return e
+
+    if not 0 <= int(levels) <= 9:
+        raise EmitError("fri_tiled_decode_tiles_levels: levels must be 0..9")
+    rc = L.fri_tiled_decode_tiles_levels(_p(data), data.size, threads, _p(tl), tl.size, int(levels), _p(info), None, 0, err, 256)
+    if rc != -3:
+        raise fail(rc)
+    ti = _tiled_info(info)
+    coefs = np.empty((tl.size, ti[6], ti[7], 1 << int(levels)), np.int32)
+    rc = L.fri_tiled_decode_tiles_levels(_p(data), data.size, threads, _p(tl), tl.size, int(levels), _p(info), _p(coefs), coefs.size, err, 256)
     if rc != 0:
         raise fail(rc)
     return ti, coefs

@@ -1368,6 +1368,21 @@ bool regions_tiles(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t ti
     return true;
 }
 
+bool preview_source_regions(uint32_t width, uint32_t height, uint32_t shift, const Region *regions, size_t n_regions, std::vector<Region> &source) {
+    source.clear();
+    if (!regions || !n_regions || !width || !height || shift > 4) return false;
+    const uint64_t S = 1ull << shift, tw = (width + S - 1) / S, th = (height + S - 1) / S; // the thumbnail w' x h'
+    const auto xs = [&](uint64_t X) { return (uint32_t)std::min<uint64_t>(X * S + S / 2, (uint64_t)width - 1); };
+    const auto ys = [&](uint64_t Y) { return (uint32_t)std::min<uint64_t>(Y * S + S / 2, (uint64_t)height - 1); };
+    for (size_t r = 0; r < n_regions; r++) {
+        const Region &q = regions[r];
+        if (!q.w || !q.h || (uint64_t)q.x + q.w > tw || (uint64_t)q.y + q.h > th) return false;
+        const uint32_t x0 = xs(q.x), y0 = ys(q.y);
+        source.push_back(Region{x0, y0, xs((uint64_t)q.x + q.w - 1) - x0 + 1, ys((uint64_t)q.y + q.h - 1) - y0 + 1});
+    }
+    return true;
+}
+
 // a tile list is strictly ascending, not empty and inside the grid
 static bool tile_list_ok(const TileList &l, uint64_t n_grid) {
     if (!l.tiles || !l.n) return false;

@@ -268,6 +268,9 @@ bool region_tiles(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t til
 // Several regions (include/fri_emit.h, "Several regions"): the strictly ascending list of the file-grid tiles t = j nx + i that at least one region touches, each
 // once. false for no regions, a zero size or a region region_tiles refuses.
 bool regions_tiles(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, const Region *regions, size_t n_regions, std::vector<uint32_t> &list);
+// Preview of regions (include/fri_emit.h, "Preview of regions"): the source rectangles, in image pixels, of regions given in the coordinates of the thumbnail at
+// `shift`; the tile list of such regions is regions_tiles of these. false for no regions, a zero size, shift > 4 and a region that is empty or leaves the thumbnail.
+bool preview_source_regions(uint32_t width, uint32_t height, uint32_t shift, const Region *regions, size_t n_regions, std::vector<Region> &source);
 // A tile list for decode_tiled and parse_tiled_coded: n file-grid tile indices, strictly ascending; kBadTileList for an empty, unsorted or repeating list and for
 // an index outside the grid.
 struct TileList {

@@ -430,6 +430,32 @@ int fri_tiled_decode_tiles(const uint8_t *frv, size_t len, uint32_t threads, con
     return too_small ? -3 : 0;
 }
 
+int fri_tiled_preview_regions_tiles(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t shift, uint32_t n_regions, const uint32_t *regions,
+                                    uint32_t *list, size_t cap, size_t *n_list) {
+    if (!regions || !n_regions || !n_list) return -1;
+    std::vector<Region> rs(n_regions), source;
+    for (uint32_t r = 0; r < n_regions; r++) rs[r] = Region{regions[4 * r], regions[4 * r + 1], regions[4 * r + 2], regions[4 * r + 3]};
+    std::vector<uint32_t> tiles;
+    if (!preview_source_regions(width, height, shift, rs.data(), rs.size(), source) || !regions_tiles(width, height, tile_w, tile_h, source.data(), source.size(), tiles)) return -1;
+    *n_list = tiles.size();
+    if (!list || cap < tiles.size()) return -3;
+    std::copy(tiles.begin(), tiles.end(), list);
+    return 0;
+}
+
+int fri_tiled_decode_tiles_levels(const uint8_t *frv, size_t len, uint32_t threads, const uint32_t *list, size_t n_list, uint32_t levels, uint32_t info[8], int32_t *coefs,
+                                  size_t coef_cap, char *err, size_t err_cap) {
+    if (!frv || !info || !list || !n_list || levels > 9) return fail(err, err_cap, "invalid argument");
+    TiledInfo t;
+    const TileList tiles{list, n_list};
+    bool too_small = false;
+    const std::string e = decode_tiled(frv, len, threads, t, coefs, coef_cap, too_small, nullptr, nullptr, (int)levels, &tiles);
+    if (e == kBadTileList || e == "invalid argument" || e == kNoLevels420 || e == kNoLevelsRgba) return fail(err, err_cap, e); // (a tiled 4:2:0 or RGBA file: -1 with the reason)
+    if (!e.empty()) return fail(err, err_cap, e, -2);
+    fill_tiled_info(t, info);
+    return too_small ? -3 : 0;
+}
+
 int fri_tiled_parse_coded_tiles(const uint8_t *frv, size_t len, const uint32_t *list, size_t n_list, uint32_t info[8], uint64_t n_planes, uint32_t *words, uint64_t word_stride,
                                 uint32_t *n_words, uint32_t *models, uint16_t *off_values, float *value_params, float *width_params, char *err, size_t err_cap) {
     if (!frv || !info || !list || !n_list || (words && (!n_words || !models || !off_values || !value_params || !width_params))) return fail(err, err_cap, "invalid argument");

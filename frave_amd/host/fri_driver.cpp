@@ -42,6 +42,10 @@
 //                                                            may overlap and repeat. --device-rans: the touched tiles are entropy-decoded on the device too (K13).
 //                                                            Refused with nothing written, naming what to use instead: a `frif` file, a tiled 4:2:0 file, a region that
 //                                                            is empty or leaves the image, no --region
+//                                                            --preview M (1..4): the regions are rectangles of decode-file --preview M's thumbnail, in its coordinates
+//                                                            (FRIDecoder::decode_preview_regions: only the first L = 9 - 2 M levels of the tiles that the regions'
+//                                                            source rectangles touch are entropy-decoded, one launch for all regions, K17); refused as above, and for
+//                                                            a tiled RGBA file, M outside 1..4 and a region that leaves the thumbnail
 //   fri_driver update-file <in.frv> <new.pgm|.ppm|.bmp> <out.frv> --region X,Y,W,H   the tiles of the `frit` file in.frv that the rectangle touches are coded anew from
 //                                                            the image, which has the file's size and channels; every other tile's bytes are copied
 //                                                            (libfri::update_bytes_tiled: fri_hip_encode_region_tiled_symbols + fri_tiled_update_from_streams). No mode
@@ -840,17 +844,19 @@ int main(int argc, char **argv) {
         return encode_image_to_file(std::move(img), fw, fh, fc, file_opts, argv[3]);
     }
     if (argc >= 2 && std::string(argv[1]) == "decode-regions") {
-        const char *usage = "decode-regions <in.frv> <out_prefix> --region X,Y,W,H [--region X,Y,W,H ...] [--device-rans]";
+        const char *usage = "decode-regions <in.frv> <out_prefix> [--preview M] --region X,Y,W,H [--region X,Y,W,H ...] [--device-rans]";
         if (argc < 4) {
             std::fprintf(stderr, "%s\n", usage);
             return 2;
         }
         std::vector<libfri::emit::Region> regions;
         libfri::EncoderOpts dec_opts;
+        unsigned preview = 0; // preview M: 1..4, 0 = none; the regions are then in the thumbnail's coordinates
         for (int i = 4; i < argc; i++) {
             char tail = 0;
             unsigned rx = 0, ry = 0, rw = 0, rh = 0;
             if (std::string(argv[i]) == "--device-rans") dec_opts.device_rans = true;
+            else if (std::string(argv[i]) == "--preview" && i + 1 < argc && std::sscanf(argv[i + 1], "%u%c", &preview, &tail) == 1 && preview >= 1 && preview <= 4) i++;
             else if (std::string(argv[i]) == "--region" && i + 1 < argc && std::sscanf(argv[i + 1], "%u,%u,%u,%u%c", &rx, &ry, &rw, &rh, &tail) == 4) regions.push_back({rx, ry, rw, rh}), i++;
             else {
                 std::fprintf(stderr, "decode-regions: unknown or incomplete option %s (%s)\n", argv[i], usage);
@@ -870,7 +876,8 @@ int main(int argc, char **argv) {
             std::fprintf(stderr, "cannot open %s\n", argv[2]);
             return 1;
         }
-        auto out = libfri::FRIDecoder().decode_regions(bytes, regions, dec_opts); // (every refusal comes before anything is written)
+        // (every refusal comes before anything is written)
+        auto out = preview ? libfri::FRIDecoder().decode_preview_regions(bytes, preview, regions, dec_opts) : libfri::FRIDecoder().decode_regions(bytes, regions, dec_opts);
         if (!out.ok) {
             std::fprintf(stderr, "%s\n", out.error.c_str());
             return 1;
@@ -889,6 +896,7 @@ int main(int argc, char **argv) {
             std::fclose(f);
             std::printf("%s: %ux%ux%u decoded\n", name.c_str(), img.metadata.width, img.metadata.height, ch);
         }
+        if (preview) std::printf("preview of regions (K17): thumbnail scale 1/%u, %u of 9 levels decoded\n", 1u << preview, 9 - 2 * preview);
         if (dec_opts.device_rans) std::printf("rANS decoder on the device (K13) over the regions' tiles\n");
         return 0;
     }

@@ -673,22 +673,35 @@ Result<RasterImage> FRIDecoder::decode_region(const std::vector<uint8_t> &data, 
     return r;
 }
 
-Result<std::vector<RasterImage>> FRIDecoder::decode_regions(const std::vector<uint8_t> &data, const std::vector<emit::Region> &regions, const EncoderOpts &opts) {
+// decode_regions (shift < 0: image coordinates, all nine levels, K15) and decode_preview_regions (shift m = 0..4: thumbnail coordinates, L = 9 - 2 m levels, K17): one
+// walk of the container, one tile list, one upload, one launch for all regions
+static Result<std::vector<RasterImage>> decode_regions_at(const std::vector<uint8_t> &data, const std::vector<emit::Region> &regions, const EncoderOpts &opts, int shift) {
     Result<std::vector<RasterImage>> r;
+    const bool preview = shift >= 0;
+    const int levels = preview ? 9 - 2 * shift : -1;
     auto fail = [&](const std::string &why) {
         r.error = "Failed to decode: " + why;
         return r;
     };
+    if (preview && shift > 4) return fail("a preview's shift is 0..4");
     if (data.size() >= 4 && std::memcmp(data.data(), "frif", 4) == 0)
-        return fail("an ordinary `frif` file has no tiles to choose from: decode it whole, or crop one rectangle with decode_region (decode-file --region)");
+        return fail(preview ? "a preview reads tiled (`frit`) files only: decode an untiled file whole and scale it down"
+                            : "an ordinary `frif` file has no tiles to choose from: decode it whole, or crop one rectangle with decode_region (decode-file --region)");
     emit::TiledInfo ti;
     std::vector<uint64_t> offset;
     if (std::string e = emit::parse_tiled(data.data(), data.size(), ti, offset); !e.empty()) return fail(e);
-    if (ti.s420) return fail("several regions of a tiled 4:2:0 file are out of scope: decode one rectangle per call with decode_region (decode-file --region)");
-    if (ti.alpha) return fail("several regions of a tiled RGBA file are out of scope: decode one rectangle per call with decode_region (decode-file --region)");
+    if (ti.s420)
+        return fail(preview ? "the preview of regions of a tiled 4:2:0 file is out of scope: decode one rectangle per call with decode_region (decode-file --region) and scale it down"
+                            : "several regions of a tiled 4:2:0 file are out of scope: decode one rectangle per call with decode_region (decode-file --region)");
+    if (ti.alpha)
+        return fail(preview ? "the preview of regions of a tiled RGBA file is out of scope: decode one rectangle per call with decode_region (decode-file --region) and scale it down"
+                            : "several regions of a tiled RGBA file are out of scope: decode one rectangle per call with decode_region (decode-file --region)");
     if (regions.empty() || regions.size() > 65535) return fail("several regions: give 1 to 65535 regions");
     std::vector<uint32_t> list, flat;
-    if (!emit::regions_tiles(ti.width, ti.height, ti.tile_w, ti.tile_h, regions.data(), regions.size(), list)) return fail("invalid region");
+    std::vector<emit::Region> source; // a preview's regions are in thumbnail coordinates: the tiles are those of their source rectangles
+    if (preview && !emit::preview_source_regions(ti.width, ti.height, (uint32_t)shift, regions.data(), regions.size(), source)) return fail("invalid region");
+    const std::vector<emit::Region> &touching = preview ? source : regions;
+    if (!emit::regions_tiles(ti.width, ti.height, ti.tile_w, ti.tile_h, touching.data(), touching.size(), list)) return fail("invalid region");
     size_t total = 0;
     for (const emit::Region &g : regions) flat.insert(flat.end(), {g.x, g.y, g.w, g.h}), total += (size_t)g.w * g.h * ti.channels;
     const emit::TileList tiles{list.data(), list.size()};
@@ -709,10 +722,10 @@ Result<std::vector<RasterImage>> FRIDecoder::decode_regions(const std::vector<ui
         e = emit::parse_tiled_coded(data.data(), data.size(), ti, planes, too_small, words.data(), stride, n_words.data(), models.data(), off.data(), vp.data(), wp.data(), &tiles);
         if (!e.empty()) return fail(e);
     } else {
-        std::string e = emit::decode_tiled(data.data(), data.size(), 0, ti, nullptr, 0, too_small, nullptr, nullptr, -1, &tiles); // header, table, geometry
+        std::string e = emit::decode_tiled(data.data(), data.size(), 0, ti, nullptr, 0, too_small, nullptr, nullptr, levels, &tiles); // header, table, geometry
         if (!e.empty()) return fail(e);
-        coefs.resize(planes * (size_t)ti.n_cells * FRI_HIP_CELL_SIZE);
-        e = emit::decode_tiled(data.data(), data.size(), 0, ti, coefs.data(), coefs.size(), too_small, nullptr, nullptr, -1, &tiles);
+        coefs.resize(planes * ((size_t)ti.n_cells << (preview ? levels : 9))); // (a preview: compact planes, 2^L nodes per cell)
+        e = emit::decode_tiled(data.data(), data.size(), 0, ti, coefs.data(), coefs.size(), too_small, nullptr, nullptr, levels, &tiles);
         if (!e.empty() || too_small) return fail(e.empty() ? "coefficient array does not match the tile geometry" : e);
     }
     Device dev(opts.device);
@@ -729,7 +742,11 @@ Result<std::vector<RasterImage>> FRIDecoder::decode_regions(const std::vector<ui
     if (ti.quality && fri_hip_quality_matrix((int)ti.quality, qm.data()) != FRI_HIP_OK) return fail("invalid quality");
     int rc = fri_hip_plan_set_dequantiser(tile, ti.quality ? FRI_HIP_DEQUANT_MIDPOINT : FRI_HIP_DEQUANT_REFERENCE);
     std::vector<uint8_t> packed(total);
-    if (rc == FRI_HIP_OK)
+    if (rc == FRI_HIP_OK && preview)
+        rc = opts.device_rans ? fri_hip_preview_regions_tiled_coded(raw, (uint32_t)regions.size(), flat.data(), words.data(), stride, n_words.data(), models.data(), off.data(), vp.data(),
+                                                                    wp.data(), (uint32_t)levels, (uint32_t)shift, qm.data(), packed.data(), status.data())
+                              : fri_hip_preview_regions_tiled(raw, coefs.data(), (uint32_t)levels, (uint32_t)shift, qm.data(), (uint32_t)regions.size(), flat.data(), packed.data());
+    else if (rc == FRI_HIP_OK)
         rc = opts.device_rans ? fri_hip_decode_regions_tiled_coded(raw, (uint32_t)regions.size(), flat.data(), words.data(), stride, n_words.data(), models.data(), off.data(), vp.data(),
                                                                    wp.data(), qm.data(), packed.data(), status.data())
                               : fri_hip_decode_regions_tiled(raw, coefs.data(), qm.data(), (uint32_t)regions.size(), flat.data(), packed.data());
@@ -754,6 +771,15 @@ Result<std::vector<RasterImage>> FRIDecoder::decode_regions(const std::vector<ui
     }
     r.ok = true;
     return r;
+}
+
+Result<std::vector<RasterImage>> FRIDecoder::decode_regions(const std::vector<uint8_t> &data, const std::vector<emit::Region> &regions, const EncoderOpts &opts) {
+    return decode_regions_at(data, regions, opts, -1);
+}
+
+Result<std::vector<RasterImage>> FRIDecoder::decode_preview_regions(const std::vector<uint8_t> &data, uint32_t shift, const std::vector<emit::Region> &regions,
+                                                                    const EncoderOpts &opts) {
+    return decode_regions_at(data, regions, opts, (int)std::min<uint32_t>(shift, 5)); // (5: refused like every shift above 4)
 }
 
 Result<RasterImage> FRIDecoder::decode_preview(const std::vector<uint8_t> &data, uint32_t shift, const EncoderOpts &opts) {

@@ -347,6 +347,12 @@ class FRIDecoder { // decoder.rs:44-59
     // entropy-decoded: fri_tiled_decode_levels's workers, then fri_hip_preview_image_tiled - with opts.device_rans, fri_hip_preview_image_tiled_coded (K13 bounded by
     // L, then K14). An untiled `frif` file and a tiled 4:2:0 file are refused, and the error says what to do instead.
     Result<RasterImage> decode_preview(const std::vector<uint8_t> &data, uint32_t shift, const EncoderOpts &opts = EncoderOpts());
+    // Several regions of that thumbnail in one call (include/fri_emit.h, "Preview of regions"): the regions are in the thumbnail's coordinates, region r the crop
+    // [y : y + h, x : x + w] of what decode_preview returns for the same shift (L = 9 - 2 m). Only the tiles that the regions' source rectangles touch are
+    // entropy-decoded, and only their first L levels - fri_tiled_decode_tiles_levels's workers, then fri_hip_preview_regions_tiled (K17); with opts.device_rans,
+    // fri_tiled_parse_coded_tiles and fri_hip_preview_regions_tiled_coded. Refused: what decode_regions refuses, a shift above 4, a region that leaves the thumbnail.
+    Result<std::vector<RasterImage>> decode_preview_regions(const std::vector<uint8_t> &data, uint32_t shift, const std::vector<emit::Region> &regions,
+                                                            const EncoderOpts &opts = EncoderOpts());
     // from the WaveletTransform stage on
     Result<RasterImage> decode(const WaveletImage &image, const EncoderOpts &opts = EncoderOpts());
 };

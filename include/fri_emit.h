@@ -98,7 +98,28 @@
  *                       then slot[ny nx], with 0xFFFFFFFF for a tile that is not in the list
  *                     The table is 8 (R + 1) + nx ny words long. Refused: R = 0, R > 65535 and n_groups >= 2^31.
  * Out of scope: regions of tiled 4:2:0 files on the device (K12's region merge with a slot table is a follow-up; the host functions here return such a file's
- * planes in plane order with n = T); preview of regions; several regions in region update; regions of `frif` files.
+ * planes in plane order with n = T); several regions in region update; regions of `frif` files. Several regions at reduced scale are "Preview of regions" below.
+ *
+ * Preview of regions (fri_tiled_preview_regions_tiles, fri_tiled_decode_tiles_levels below; the device side is fri_hip_preview_regions_tiled and K17,
+ * include/fri_hip.h): many rectangles of one file at reduced scale. L, m, S = 2^m, w' x h', P_L and the thumbnail are those of "Preview decode" (include/fri_hip.h;
+ * fri_tiled_decode_levels below); xs(X) = min(X S + S / 2, W - 1) and ys(Y) = min(Y S + S / 2, H - 1) are the image column and row of thumbnail column X and row Y. C is the channel count.
+ *   input             R >= 1 regions r = (X, Y, w, h) in THUMBNAIL coordinates, `regions` uint32 [R][4] in host memory, each with w, h >= 1, X + w <= w' and
+ *                     Y + h <= h', compared in 64 bits; regions may overlap and may repeat. Refused: R = 0, R > 65535 and n_groups >= 2^31.
+ *   result            by definition region r is the crop [Y : Y + h, X : X + w] of what fri_hip_preview_image_tiled returns for the file with the same L, m,
+ *                     qmatrix and inner-plan settings. At m = 0, L = 9 it is the result of fri_hip_decode_regions_tiled.
+ *   source rectangle  of r: (xs(X), ys(Y), xs(X + w - 1) - xs(X) + 1, ys(Y + h - 1) - ys(Y) + 1), an image region by the rules of "Region decode".
+ *   tile list         the "Several regions" tile list of the R source rectangles: strictly ascending, slot(t) as defined there. Every sample of a region lies in
+ *                     its source rectangle, so its tile is listed. The list can hold a tile without a sample only when a tile side is below S (samples are S
+ *                     apart, and a source rectangle spans every tile between two of them); such a tile is decoded and never read.
+ *   tile-list arrays  everything per tile is in list order: compact planes [T][C][F][2^L], full planes [T][C][F][512], coded planes [T C].
+ *   packed output     region r is a raster [h_r][w_r][C] without a pitch; it sits at byte off_r = sum_{q<r} w_q h_q C of one buffer, and off_R is the total.
+ *   preview-region table  uint32 words that the host writes and the kernel reads. A group is one 16 x 16 block of samples of one region.
+ *                       groups_r = ceil(w_r / 16) ceil(h_r / 16)
+ *                       rows r = 0..R-1 of 8 words: {X, Y, w, h, off_r low, off_r high, first_group_r = sum_{q<r} groups_q, ceil(w_r / 16)}
+ *                       row R: {0, 0, 0, 0, total low, total high, n_groups, 0}
+ *                       then slot[ny nx], with 0xFFFFFFFF for a tile that is not in the list
+ *                     The table is 8 (R + 1) + nx ny words long.
+ * Out of scope: tiled 4:2:0 and tiled RGBA files; `frif` files; a filter other than the node mean.
  *
  * Region update (fri_tiled_update_from_streams below; the device side is fri_hip_encode_region_tiled_symbols, include/fri_hip.h): the write-side twin of region
  * decode. A tile's payload depends on that tile's pixels, the matrix and the mode and on nothing else, so a file F_A (tiled 4:4:4, C = 1 or 3, any mode), a raster
@@ -149,7 +170,7 @@
  *   region        a region's sub-grid (the arithmetic of "Region decode" unchanged) or a tile list uses the same order with n = ni nj or n = T.
  * fri_tiled_info, fri_tiled_decode, fri_tiled_decode_region and fri_tiled_decode_tiles accept such files: info[6] carries FRI_EMIT_ALPHA (its channel count stays
  * 3), the coefficients come back in plane order and the needed element count is 4 n F x 512. A payload that does not have four channels is "Malformed tiled
- * image". fri_tiled_decode_levels, fri_tiled_parse_coded, fri_tiled_parse_coded_tiles and fri_tiled_update_from_streams refuse such a file: -1, and `err` names
+ * image". fri_tiled_decode_levels, fri_tiled_decode_tiles_levels, fri_tiled_parse_coded, fri_tiled_parse_coded_tiles and fri_tiled_update_from_streams refuse such a file: -1, and `err` names
  * tiled RGBA.
  * Out of scope: preview, the coded forms (K11, K13), several regions on the device and region update of tiled RGBA files; alpha with 4:2:0. */
 #define FRI_EMIT_EMPTY_OK 0x2000u
@@ -318,6 +339,19 @@ int fri_tiled_regions_tiles(uint32_t width, uint32_t height, uint32_t tile_w, ui
  * small. A tiled 4:2:0 file comes back in plane order with n = T, as fri_tiled_decode_region returns it for a sub-grid. */
 int fri_tiled_decode_tiles(const uint8_t *frv, size_t len, uint32_t threads, const uint32_t *list, size_t n_list, uint32_t info[8], int32_t *coefs, size_t coef_cap, char *err,
                            size_t err_cap);
+/* The tile list of R regions of the thumbnail ("Preview of regions" above): the source rectangles are formed by that definition and handed to the tile-list code of
+ * fri_tiled_regions_tiles, whose return values and size query these are. regions [n_regions][4] = {X, Y, w, h} in thumbnail coordinates at shift m. -1 as there, and
+ * for shift > 4 and a region that is empty or leaves the w' x h' thumbnail. */
+int fri_tiled_preview_regions_tiles(uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t shift, uint32_t n_regions, const uint32_t *regions,
+                                    uint32_t *list, size_t cap, size_t *n_list);
+/* fri_tiled_decode_tiles stopped at a level (fri_tiled_decode_levels has `levels`): COMPACT planes coefs [T][C][F][2^L] int32 in list order - what
+ * fri_hip_preview_regions_tiled takes. For every thread count they equal fri_tiled_decode_levels's planes taken at the listed tiles and fri_tiled_decode_tiles's planes
+ * sliced to [..., :2^L]. The same per-tile path, the same workers and the same error wording ("tile t: channel c: ...", t in the file's grid) as
+ * fri_tiled_decode_tiles; damage behind the prefix, or inside the body of an unlisted payload, is not seen. -1 for levels > 9, for a bad tile list ("invalid tile
+ * list") and, with the messages of fri_tiled_decode_levels, for a tiled 4:2:0 file (names 4:2:0) and a tiled RGBA file (names tiled RGBA); -3 with `info` filled when
+ * coefs is NULL or coef_cap (in elements) is too small. */
+int fri_tiled_decode_tiles_levels(const uint8_t *frv, size_t len, uint32_t threads, const uint32_t *list, size_t n_list, uint32_t levels, uint32_t info[8], int32_t *coefs,
+                                  size_t coef_cap, char *err, size_t err_cap);
 /* fri_tiled_parse_coded for a tile list (the rules of fri_tiled_decode_tiles, -1 included): P = T C planes in list order - plane order with n = T for a tiled 4:2:0
  * file - and the markers of the listed payloads alone are walked. The arrays, the size queries and the error for a plane longer than word_stride are
  * fri_tiled_parse_coded's; a tile's error names its index in the file's grid. What fri_hip_decode_regions_tiled_coded takes. */

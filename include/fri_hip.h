@@ -705,7 +705,8 @@ int fri_hip_decode_region_tiled(fri_hip_plan_tiled *p, const int32_t *coefs, con
  * filled, nothing decoded further, and fri_hip_last_hip_error naming the first such plane by its tile's index in the file's grid ("tile t: channel c: ..."). The inner
  * plan needs its stream order. Synchronous.
  * All: FRI_HIP_ERR_INVALID_ARGUMENT for a NULL pointer, a bad region and a bad R; FRI_HIP_ERR_NO_DEVICE on a host-only plan for everything that computes.
- * Out of scope: regions of tiled 4:2:0 files on the device (K12's region merge with a slot table); preview of regions; several regions in region update. */
+ * Out of scope: regions of tiled 4:2:0 files on the device (K12's region merge with a slot table); several regions in region update. Several regions at reduced
+ * scale are "Preview of regions" below. */
 int fri_hip_plan_tiled_regions(fri_hip_plan_tiled *p, uint32_t n_regions, const uint32_t *regions, uint32_t *list, size_t list_cap, size_t *n_list, uint32_t *table,
                                size_t table_cap_words);
 int fri_hip_merge_tiles_regions_dev(fri_hip_plan_tiled *p, const uint8_t *d_tiles, uint32_t n_list, uint32_t n_regions, const uint32_t *d_table, uint8_t *d_out, void *stream);
@@ -1128,8 +1129,8 @@ int fri_hip_decode_image_tiled420_coded(fri_hip_plan_tiled420 *p, const uint32_t
  *         out(Y, X, c) = P_L(min(Y S + S / 2, H - 1), min(X S + S / 2, W - 1), c). m = 0 is P_L itself. A sample that no cell owns (FRI_HIP_TILED_ALLOW_HOLES) is 0.
  *         The natural pairing is L = 9 - 2 m, where a node covers S^2 pixels; L and m are independent here.
  *
- * Out of scope: untiled `frif` files (one chain per channel: nothing runs side by side); tiled 4:2:0, where the chroma lattice is a level pair of its own; the
- * preview of a region; a filter other than the node mean.
+ * Out of scope: untiled `frif` files (one chain per channel: nothing runs side by side); tiled 4:2:0, where the chroma lattice is a level pair of its own; a
+ * filter other than the node mean. The preview of regions is "Preview of regions" below.
  *
  * fri_hip_preview_size: out = {w', h'}; host only. FRI_HIP_ERR_INVALID_ARGUMENT for a zero size, shift > 4 or out = NULL.
  *
@@ -1157,6 +1158,58 @@ int fri_hip_preview_image_tiled(fri_hip_plan_tiled *p, const int32_t *coefs, uin
 int fri_hip_preview_image_tiled_coded(fri_hip_plan_tiled *p, const uint32_t *words, size_t word_stride, const uint32_t *n_words, const uint32_t *models,
                                       const uint16_t *off_values, const float *value_params, const float *width_params, uint32_t levels, uint32_t shift,
                                       const int32_t qmatrix[32], uint8_t *pixels, uint32_t *status);
+
+/* ---- Preview of regions: several rectangles of the thumbnail in one call (K17, k17_preview_regions.hip) ---- */
+/* What a viewer that pans and zooms asks for: many rectangles of one file at reduced scale. L, m, S = 2^m, w' x h', P_L and the thumbnail are those of "Preview
+ * decode" above; xs(X) = min(X S + S / 2, W - 1) and ys(Y) = min(Y S + S / 2, H - 1) are the image column and row of thumbnail column X and row Y. C is the channel count.
+ *   input             R >= 1 regions r = (X, Y, w, h) in THUMBNAIL coordinates, `regions` uint32 [R][4] in host memory, each with w, h >= 1, X + w <= w' and
+ *                     Y + h <= h', compared in 64 bits; regions may overlap and may repeat. Refused: R = 0, R > 65535 and n_groups >= 2^31.
+ *   result            by definition region r is the crop [Y : Y + h, X : X + w] of what fri_hip_preview_image_tiled returns for the file with the same L, m,
+ *                     qmatrix and inner-plan settings. At m = 0, L = 9 it is the result of fri_hip_decode_regions_tiled.
+ *   source rectangle  of r: (xs(X), ys(Y), xs(X + w - 1) - xs(X) + 1, ys(Y + h - 1) - ys(Y) + 1), an image region by the rules of "Region decode".
+ *   tile list         the "Several regions" tile list of the R source rectangles: strictly ascending, slot(t) as defined there. Every sample of a region lies in
+ *                     its source rectangle, so its tile is listed. The list can hold a tile without a sample only when a tile side is below S (samples are S
+ *                     apart, and a source rectangle spans every tile between two of them); such a tile is decoded and never read.
+ *   tile-list arrays  everything per tile is in list order: compact planes [T][C][F][2^L], full planes [T][C][F][512], coded planes [T C].
+ *   packed output     region r is a raster [h_r][w_r][C] without a pitch; it sits at byte off_r = sum_{q<r} w_q h_q C of one buffer, and off_R is the total.
+ *   preview-region table  uint32 words that the host writes and the kernel reads. A group is one 16 x 16 block of samples of one region.
+ *                       groups_r = ceil(w_r / 16) ceil(h_r / 16)
+ *                       rows r = 0..R-1 of 8 words: {X, Y, w, h, off_r low, off_r high, first_group_r = sum_{q<r} groups_q, ceil(w_r / 16)}
+ *                       row R: {0, 0, 0, 0, total low, total high, n_groups, 0}
+ *                       then slot[ny nx], with 0xFFFFFFFF for a tile that is not in the list
+ *                     The table is 8 (R + 1) + nx ny words long.
+ * fri_hip_plan_tiled_preview_regions: host only, works on host-only plans. Writes the tile list (*n_list = T) and the preview-region table. The size query is
+ * fri_hip_plan_tiled_regions's: -3 with *n_list filled and nothing else written when list is NULL, list_cap < T, table is NULL or table_cap_words < 8 (R + 1) + nx ny.
+ * The plan remembers R, T, n_groups and shift of the last such table. That memory is separate from the one fri_hip_plan_tiled_regions keeps: a call here does not
+ * change what fri_hip_merge_tiles_regions_dev accepts, and a call there does not change what fri_hip_preview_tiles_regions_dev accepts.
+ * fri_hip_preview_tiles_regions_dev (K17's preview_regions_kernel alone): d_coefs holds the listed tiles' planes [T][C], plane (k, c) at (k C + c) * coef_stride
+ * elements, node h of a cell at cell * node_stride + h; node_stride is 512 or 2^L and coef_stride at least F * node_stride, as in fri_hip_preview_tiles_dev -> d_out, the
+ * packed region rasters. One launch of n_groups workgroups of 256 threads; a workgroup is one 16 x 16 block of one region, which it finds by a search over
+ * first_group; a thread is one sample (Y + ty, X + tx): its image pixel (ys, xs), the tile (tj, ti) of that pixel, the planes at slot[tj nx + ti], then exactly
+ * K14's per-sample work (the owner table, the L + 1 dequantised coefficients on the leaf's path, the clamp, the colour inverse). A sample that no cell owns is 0.
+ * Every output byte is written exactly once, by one thread; no atomics, no LDS beyond the quantiser row; every byte offset is 64-bit; any alignment of d_out; only
+ * enqueues on `stream`, can be captured into a graph. d_table must be, in device memory, the table fri_hip_plan_tiled_preview_regions LAST wrote on this plan, and
+ * n_list, n_regions and shift the T, R and m of that call: the entry checks the pointers, levels, shift, the strides, n_list <= nx ny and that R, T and shift are the
+ * remembered ones. It cannot check the table's words - a table from anywhere else makes the kernel read and write out of bounds.
+ * fri_hip_preview_regions_tiled: the host form. coefs are the compact planes [T][C][F][2^L] in list order (what fri_tiled_decode_tiles_levels returns for the list,
+ * include/fri_emit.h) and go up - 2^(L - 9) of fri_hip_decode_regions_tiled's upload; the table goes up, K17 runs, the packed rasters `pixels` (off_R bytes) come
+ * back. The plan's buffers grow to T tiles, never to the image. Synchronous, on the null stream.
+ * fri_hip_preview_regions_tiled_coded: the coded planes of the tile list go up (what fri_tiled_parse_coded_tiles returns for the list), K13 bounded by L
+ * (fri_hip_decode_planes_levels_dev) runs over the T C planes, then K17 at node stride 512. status uint32 [T C][4] goes to the caller; a plane the decoder
+ * refuses makes the call FRI_HIP_ERR_INVALID_ARGUMENT with the status filled, no pixels written, and fri_hip_last_hip_error naming the first such plane by its
+ * tile's index in the file's grid ("tile t: channel c: ..."), as in fri_hip_decode_regions_tiled_coded. The inner plan needs its stream order. Synchronous.
+ * All: FRI_HIP_ERR_INVALID_ARGUMENT for a NULL pointer, levels > 9, shift > 4, a bad region and a bad R; FRI_HIP_ERR_NO_DEVICE on a host-only plan for everything
+ * that computes. The two forms that grow buffers take no stream: they run on the null stream, which cannot be capturing, so no captured graph can record them.
+ * Out of scope: tiled 4:2:0 and tiled RGBA files; `frif` files; a filter other than the node mean. */
+int fri_hip_plan_tiled_preview_regions(fri_hip_plan_tiled *p, uint32_t shift, uint32_t n_regions, const uint32_t *regions, uint32_t *list, size_t list_cap, size_t *n_list,
+                                       uint32_t *table, size_t table_cap_words);
+int fri_hip_preview_tiles_regions_dev(fri_hip_plan_tiled *p, const int32_t *d_coefs, size_t coef_stride, uint32_t node_stride, uint32_t levels, uint32_t shift,
+                                      const int32_t qmatrix[32], uint32_t n_list, uint32_t n_regions, const uint32_t *d_table, uint8_t *d_out, void *stream);
+int fri_hip_preview_regions_tiled(fri_hip_plan_tiled *p, const int32_t *coefs, uint32_t levels, uint32_t shift, const int32_t qmatrix[32], uint32_t n_regions,
+                                  const uint32_t *regions, uint8_t *pixels);
+int fri_hip_preview_regions_tiled_coded(fri_hip_plan_tiled *p, uint32_t n_regions, const uint32_t *regions, const uint32_t *words, size_t word_stride, const uint32_t *n_words,
+                                        const uint32_t *models, const uint16_t *off_values, const float *value_params, const float *width_params, uint32_t levels,
+                                        uint32_t shift, const int32_t qmatrix[32], uint8_t *pixels, uint32_t *status);
 
 /* ---- timing helper ---------------------------------------------------------------------------- */
 /* Runs the forward kernel `iters` times on `stream` bracketed by HIP events recorded on that same
