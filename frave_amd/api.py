@@ -1371,20 +1371,44 @@ class PlanTiled:
             at += w * h * self.channels
         return out
 
+    @staticmethod
+    def _packed_bytes(table, n_regions):
+        """the packed output's bytes: words 4, 5 of row R of a region table"""
+        return int(table[8 * n_regions + 4]) | int(table[8 * n_regions + 5]) << 32
+
+    def _regions_table(self, entry, lead, rg):
+        """the size query of fri_hip_plan_tiled[_preview]_regions (`entry`, after the plan its arguments `lead`), then the call -> (list, table)"""
+        n = C.c_size_t(0)
+        call = getattr(load_library(), entry)
+        rc = call(self._h, *lead, rg.shape[0], _p(rg), None, 0, C.addressof(n), None, 0)
+        if rc != -3:  # (the size query's answer: the buffers are too small, n is filled)
+            _check(rc or -1, entry, self.ctx)
+        tiles, table = np.zeros(n.value, np.uint32), np.zeros(8 * (rg.shape[0] + 1) + self.n_tiles, np.uint32)
+        _check(call(self._h, *lead, rg.shape[0], _p(rg), _p(tiles), tiles.size, C.addressof(n), _p(table), table.size), entry, self.ctx)
+        return tiles, table
+
+    def _regions_coded(self, entry, coded, rg, tiles, table, tail):
+        """a coded regions call `entry` (after the coded planes its arguments `tail`, then the output and the status) -> (a list of [h][w][C] arrays, status); a
+        refusal carries the file-grid index of the first refused plane's tile as .tile"""
+        planes = tiles.size * self.channels
+        words, n_words, models, off, vp, wp = _coded_planes(coded, planes)
+        out = np.empty(self._packed_bytes(table, rg.shape[0]), np.uint8)
+        status = np.zeros((planes, 4), np.uint32)
+        rc = getattr(load_library(), entry)(self._h, rg.shape[0], _p(rg), _p(words), words.shape[1], _p(n_words), _p(models), _p(off), _p(vp), _p(wp), *tail, _p(out), _p(status))
+        try:
+            _check_decode(rc, entry, self.ctx, status)
+        except FriHipError as e:
+            bad = np.flatnonzero(status[:, 0])
+            e.tile = int(tiles[bad[0] // self.channels]) if bad.size else None
+            raise
+        return self._split_regions(out, rg), status
+
     def regions(self, regions):
         """fri_hip_plan_tiled_regions: (list uint32 [T], table uint32 [8 (R + 1) + nx ny]) of `regions` [(x, y, w, h), ...] - the strictly ascending file-grid
         indices of the tiles at least one region touches, and the region table K15 reads (include/fri_hip.h, "Several regions"; its row R holds the packed
         output's bytes in words 4, 5 and n_groups in word 6). Works on a host-only plan. FriHipError (-1) for no regions, more than 65535, a region that is
         empty or leaves the image, n_groups >= 2^31. The plan remembers the last table it wrote: merge_tiles_regions_dev takes that one."""
-        rg = self._regions(regions)
-        n = C.c_size_t(0)
-        L = load_library()
-        rc = L.fri_hip_plan_tiled_regions(self._h, rg.shape[0], _p(rg), None, 0, C.addressof(n), None, 0)
-        if rc != -3:  # (the size query's answer: the buffers are too small, n is filled)
-            _check(rc or -1, "fri_hip_plan_tiled_regions", self.ctx)
-        tiles, table = np.zeros(n.value, np.uint32), np.zeros(8 * (rg.shape[0] + 1) + self.n_tiles, np.uint32)
-        _check(L.fri_hip_plan_tiled_regions(self._h, rg.shape[0], _p(rg), _p(tiles), tiles.size, C.addressof(n), _p(table), table.size), "fri_hip_plan_tiled_regions", self.ctx)
-        return tiles, table
+        return self._regions_table("fri_hip_plan_tiled_regions", (), self._regions(regions))
 
     def merge_tiles_regions_dev(self, d_tiles, n_list, n_regions, d_table, d_out, stream=0):
         """fri_hip_merge_tiles_regions_dev (K15 alone), device pointers as ints: the tile-list raster [T][tile_h][tile_w][C] -> the packed region rasters. d_table
@@ -1404,7 +1428,7 @@ class PlanTiled:
         tiles, table = self.regions(rg)
         co = np.ascontiguousarray(coefs, np.int32).reshape(-1)
         assert co.size == tiles.size * self.channels * self.num_cells * 512
-        out = np.empty(int(table[8 * rg.shape[0] + 4]) | int(table[8 * rg.shape[0] + 5]) << 32, np.uint8)
+        out = np.empty(self._packed_bytes(table, rg.shape[0]), np.uint8)
         _check(load_library().fri_hip_decode_regions_tiled(self._h, _p(co), _p(_q(qmatrix)), rg.shape[0], _p(rg), _p(out)), "fri_hip_decode_regions_tiled", self.ctx)
         return self._split_regions(out, rg)
 
@@ -1415,19 +1439,7 @@ class PlanTiled:
         file-grid index of the first refused plane's tile as .tile. Needs set_stream_order()."""
         rg = self._regions(regions)
         tiles, table = self.regions(rg)
-        planes = tiles.size * self.channels
-        words, n_words, models, off, vp, wp = _coded_planes(coded, planes)
-        out = np.empty(int(table[8 * rg.shape[0] + 4]) | int(table[8 * rg.shape[0] + 5]) << 32, np.uint8)
-        status = np.zeros((planes, 4), np.uint32)
-        rc = load_library().fri_hip_decode_regions_tiled_coded(self._h, rg.shape[0], _p(rg), _p(words), words.shape[1], _p(n_words), _p(models), _p(off), _p(vp), _p(wp),
-                                                               _p(_q(qmatrix)), _p(out), _p(status))
-        try:
-            _check_decode(rc, "fri_hip_decode_regions_tiled_coded", self.ctx, status)
-        except FriHipError as e:
-            bad = np.flatnonzero(status[:, 0])
-            e.tile = int(tiles[bad[0] // self.channels]) if bad.size else None
-            raise
-        return self._split_regions(out, rg), status
+        return self._regions_coded("fri_hip_decode_regions_tiled_coded", coded, rg, tiles, table, (_p(_q(qmatrix)),))
 
     # ---- preview of regions: several rectangles of the thumbnail in one call (K17) ---------------------
     def preview_regions_table(self, shift, regions):
@@ -1435,16 +1447,7 @@ class PlanTiled:
         thumbnail at `shift` - the tile list of their source rectangles and the preview-region table K17 reads (include/fri_hip.h, "Preview of regions"; its row R
         holds the packed output's bytes in words 4, 5 and n_groups in word 6). Works on a host-only plan. FriHipError (-1) for shift > 4, no regions, more than
         65535, a region that is empty or leaves the thumbnail, n_groups >= 2^31. The plan remembers the last such table: preview_tiles_regions_dev takes that one."""
-        rg = self._regions(regions)
-        n = C.c_size_t(0)
-        L = load_library()
-        rc = L.fri_hip_plan_tiled_preview_regions(self._h, int(shift), rg.shape[0], _p(rg), None, 0, C.addressof(n), None, 0)
-        if rc != -3:  # (the size query's answer: the buffers are too small, n is filled)
-            _check(rc or -1, "fri_hip_plan_tiled_preview_regions", self.ctx)
-        tiles, table = np.zeros(n.value, np.uint32), np.zeros(8 * (rg.shape[0] + 1) + self.n_tiles, np.uint32)
-        _check(L.fri_hip_plan_tiled_preview_regions(self._h, int(shift), rg.shape[0], _p(rg), _p(tiles), tiles.size, C.addressof(n), _p(table), table.size),
-               "fri_hip_plan_tiled_preview_regions", self.ctx)
-        return tiles, table
+        return self._regions_table("fri_hip_plan_tiled_preview_regions", (int(shift),), self._regions(regions))
 
     def preview_tiles_regions_dev(self, d_coefs, coef_stride, node_stride, levels, shift, n_list, n_regions, d_table, d_out, qmatrix=None, stream=0):
         """fri_hip_preview_tiles_regions_dev (K17 alone), device pointers as ints: the listed tiles' planes [T][C] coef_stride elements apart, node h of cell k at
@@ -1460,7 +1463,7 @@ class PlanTiled:
         tiles, table = self.preview_regions_table(shift, rg)
         co = np.ascontiguousarray(coefs, np.int32).reshape(-1)
         assert not 0 <= levels <= 9 or co.size == tiles.size * self.channels * self.num_cells << levels  # (levels out of range: the library's refusal)
-        out = np.empty(int(table[8 * rg.shape[0] + 4]) | int(table[8 * rg.shape[0] + 5]) << 32, np.uint8)
+        out = np.empty(self._packed_bytes(table, rg.shape[0]), np.uint8)
         _check(load_library().fri_hip_preview_regions_tiled(self._h, _p(co), int(levels), int(shift), _p(_q(qmatrix)), rg.shape[0], _p(rg), _p(out)),
                "fri_hip_preview_regions_tiled", self.ctx)
         return self._split_regions(out, rg)
@@ -1472,19 +1475,7 @@ class PlanTiled:
         and the file-grid index of the first refused plane's tile as .tile. Needs set_stream_order()."""
         rg = self._regions(regions)
         tiles, table = self.preview_regions_table(shift, rg)
-        planes = tiles.size * self.channels
-        words, n_words, models, off, vp, wp = _coded_planes(coded, planes)
-        out = np.empty(int(table[8 * rg.shape[0] + 4]) | int(table[8 * rg.shape[0] + 5]) << 32, np.uint8)
-        status = np.zeros((planes, 4), np.uint32)
-        rc = load_library().fri_hip_preview_regions_tiled_coded(self._h, rg.shape[0], _p(rg), _p(words), words.shape[1], _p(n_words), _p(models), _p(off), _p(vp), _p(wp),
-                                                                int(levels), int(shift), _p(_q(qmatrix)), _p(out), _p(status))
-        try:
-            _check_decode(rc, "fri_hip_preview_regions_tiled_coded", self.ctx, status)
-        except FriHipError as e:
-            bad = np.flatnonzero(status[:, 0])
-            e.tile = int(tiles[bad[0] // self.channels]) if bad.size else None
-            raise
-        return self._split_regions(out, rg), status
+        return self._regions_coded("fri_hip_preview_regions_tiled_coded", coded, rg, tiles, table, (int(levels), int(shift), _p(_q(qmatrix))))
 
     # ---- region update: only the tiles a rectangle touches are split and coded ------------------------
     def region_cover(self, x, y, w, h):

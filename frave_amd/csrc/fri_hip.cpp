@@ -4,6 +4,7 @@
 // fri_hip_tiled420.cpp), K11's plane entry points are in fri_hip_rans.cpp, and what all of them share is fri_hip_internal.hpp; the quality searches of every kind
 // run on search_scaffold.hpp, with the kind's probe steps beside its plan (here: PlanSearch).
 #include "fri_hip_internal.hpp"
+#include "region_table.hpp"
 
 #include <atomic>
 #include <cstdio>
@@ -729,12 +730,7 @@ int fri_hip_plan_num_some_levels(const fri_hip_plan *p, uint32_t levels, uint64_
     *out = num_some_levels(p->geo, levels);
     return FRI_HIP_OK;
 }
-int fri_hip_preview_size(uint32_t width, uint32_t height, uint32_t shift, uint32_t out[2]) {
-    if (!width || !height || shift > 4 || !out) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    const uint32_t S = 1u << shift;
-    out[0] = (uint32_t)(((uint64_t)width + S - 1) / S), out[1] = (uint32_t)(((uint64_t)height + S - 1) / S);
-    return FRI_HIP_OK;
-}
+int fri_hip_preview_size(uint32_t width, uint32_t height, uint32_t shift, uint32_t out[2]) { return preview_size(width, height, shift, out); }
 uint64_t fri_hip_plan_owned_pixels(const fri_hip_plan *p) { return p ? p->geo.n_valid_leaves : 0; }
 
 int fri_hip_plan_assume_forward_coefficients(fri_hip_plan *p, int on) {

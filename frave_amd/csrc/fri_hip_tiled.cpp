@@ -1,7 +1,8 @@
 // fri_hip_tiled.cpp -- the tiled plan kind of the C ABI (fri_hip_plan_tiled: include/fri_hip.h): the plan and its grid, split and merge, the encode chain and
 // its coded form (K11), the image and region decodes, several regions in one call (K15) and the decode from coded planes (K13), the preview decode (K14) and the preview of regions (K17), the measure, the size estimate and the quality searches. Host-side glue like fri_hip.cpp, on one ordinary
-// plan of the tile's shape. The grid, plan creation, the host size estimate and the coded route are tiled_common.hpp's, shared with fri_hip_tiled420.cpp; the
-// searches are TiledSearch on search_scaffold.hpp.
+// plan of the tile's shape. The grid and the region tables are region_table.hpp's (plain C++); plan creation, the host size estimate and the coded route are
+// tiled_common.hpp's, shared with fri_hip_tiled420.cpp; the searches are TiledSearch on search_scaffold.hpp. The decodes' host forms share their way up and down
+// (coefs_up, run_down) and their coded forms one front (decode_coded_front), below.
 #include "search_scaffold.hpp"
 #include "tiled_common.hpp"
 
@@ -36,18 +37,15 @@ struct fri_hip_plan_tiled {
     Grown<uint8_t> preview;           // fri_hip_preview_image_tiled*: the thumbnail [h'][w'][C]
     Grown<uint32_t> region_table;     // fri_hip_decode_regions_tiled*: the region table, 8 (R + 1) + nx ny words
     Grown<uint8_t> regions_out;       // fri_hip_decode_regions_tiled[_coded]: the packed region rasters
-    // what the last table fri_hip_plan_tiled_regions wrote was made for: the launch of fri_hip_merge_tiles_regions_dev has n_groups workgroups, and the host alone knows it
-    struct {
-        uint32_t n_regions = 0, n_list = 0, n_groups = 0;
-    } planned;
-    // the same for the last table fri_hip_plan_tiled_preview_regions wrote (fri_hip_preview_tiles_regions_dev): a memory of its own, so that neither kind of
-    // table changes what the other kind's kernel entry accepts
-    struct {
-        uint32_t n_regions = 0, n_list = 0, n_groups = 0, shift = 0;
-    } planned_preview;
+    // what the last table fri_hip_plan_tiled_regions wrote was made for (fri_hip_merge_tiles_regions_dev), and the same for the last table
+    // fri_hip_plan_tiled_preview_regions wrote (fri_hip_preview_tiles_regions_dev): a memory each, so that neither kind of table changes what the other kind's
+    // kernel entry accepts
+    Planned planned, planned_preview;
     size_t n_tiles() const { return grid.n_tiles(); }
     size_t raster_bytes() const { return (size_t)grid.width * grid.height * channels; }
     size_t tile_bytes() const { return (size_t)grid.tile_w * grid.tile_h * channels; }
+    size_t tile_coefs() const { return fri_hip_plan_coef_count(tile.get()); }                                         // a tile's coefficients [C][F][512]: the full decodes
+    size_t preview_coefs(uint32_t levels) const { return (tile->geo.centers.size() << levels) * channels; }          // ... and its compact planes [C][F][2^levels]: the previews
 };
 
 namespace {
@@ -143,6 +141,90 @@ int upload_owner_table(fri_hip_plan_tiled *p) {
 
 bool preview_args_ok(uint32_t levels, uint32_t shift) { return levels <= (uint32_t)kDepth && shift <= 4; }
 
+// The two region tables on the plan's grid (region_table.hpp): K15's, in image coordinates, and K17's, in those of the thumbnail at `shift` (a shift past 4
+// stays past 4 as an int: the builder refuses it).
+bool plan_regions(const fri_hip_plan_tiled *p, uint32_t n_regions, const uint32_t *regions, RegionsPlan &out) {
+    return build_region_table(p->grid, p->channels, -1, n_regions, regions, out);
+}
+bool plan_preview_regions(const fri_hip_plan_tiled *p, uint32_t shift, uint32_t n_regions, const uint32_t *regions, RegionsPlan &out) {
+    return build_region_table(p->grid, p->channels, (int)std::min(shift, 5u), n_regions, regions, out);
+}
+// fri_hip_plan_tiled[_preview]_regions behind the builder: the size query, or the list and the table out and the table remembered in `memory`
+int write_regions_plan(const RegionsPlan &r, uint32_t n_regions, uint32_t shift, Planned &memory, uint32_t *list, size_t list_cap, size_t *n_list, uint32_t *table,
+                       size_t table_cap_words) {
+    *n_list = r.list.size();
+    if (!list || list_cap < r.list.size() || !table || table_cap_words < r.table.size()) return -3; // the size query (the emitter's code for a buffer that is too small)
+    std::copy(r.list.begin(), r.list.end(), list);
+    std::copy(r.table.begin(), r.table.end(), table);
+    remember(memory, n_regions, shift, r);
+    return FRI_HIP_OK;
+}
+
+/* ---- what the decodes' host and coded forms share ---- */
+// The way up of a host form: the plan's coefficient buffer grown to `count`, the caller's coefficients in it.
+int coefs_up(fri_hip_plan_tiled *p, const int32_t *coefs, size_t count) {
+    fri_hip_ctx *c = p->ctx;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int rc = grow(c, p->coefs, count)) return rc;
+    HIP_TRY(c, hipMemcpy(p->coefs, coefs, count * sizeof(int32_t), hipMemcpyHostToDevice));
+    return FRI_HIP_OK;
+}
+// The way down of a host or coded form: `out` grown to `bytes`, `run` - the _dev form on the null stream, from p->coefs into `out` -, the bytes down.
+template <typename Run>
+int run_down(fri_hip_plan_tiled *p, Grown<uint8_t> &out, size_t bytes, uint8_t *pixels, Run &&run) {
+    fri_hip_ctx *c = p->ctx;
+    int rc;
+    if ((rc = grow(c, out, bytes)) || (rc = run())) return rc;
+    HIP_TRY(c, hipMemcpy(pixels, out, bytes, hipMemcpyDeviceToHost));
+    return FRI_HIP_OK;
+}
+// The front of a coded form, K13 in front of its kernels: the stream order the decoder needs, the coded planes of `n` tiles up, the decoder bounded by `levels`
+// into p->coefs (full planes, whatever the bound), the status down. With a tile list, a refused plane is named in last_error by its tile's index in the file's grid.
+int decode_coded_front(fri_hip_plan_tiled *p, const CodedPlanes &in, size_t n, uint32_t levels, uint32_t *status, const std::vector<uint32_t> *list, const char *entry) {
+    if (!p->tile->d_stream_order) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    fri_hip_ctx *c = p->ctx;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t image = p->tile_coefs(), planes = n * p->channels;
+    if (!decode_counts_ok((uint32_t)planes)) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    int rc;
+    if ((rc = grow(c, p->coefs, n * image))) return rc;
+    CodedOnDevice d;
+    if ((rc = upload_coded(p, in, planes, p->rans_words, d)) || (rc = decode_coded_batch(p->tile.get(), d, 0, planes, p->coefs, image / p->channels, levels))) return rc;
+    rc = read_back_decode_status(c, d, status);
+    for (size_t k = 0; list && k < planes && rc == FRI_HIP_ERR_INVALID_ARGUMENT; k++)
+        if (status[4 * k]) { // the first refused plane
+            c->last_error = std::string(entry) + ": tile " + std::to_string((*list)[k / p->channels]) + ": channel " + std::to_string(k % p->channels) +
+                            ": the device decoder refused the plane (status " + std::to_string(status[4 * k]) + ")";
+            break;
+        }
+    return rc;
+}
+// the tail of the whole image's decodes: the inverse kernel over all tiles of p->coefs, the merge, the raster down
+int decode_image_down(fri_hip_plan_tiled *p, const int32_t qmatrix[32], uint8_t *pixels) {
+    return run_down(p, p->raster, p->raster_bytes(), pixels, [&]() -> int {
+        fri_hip_ctx *c = p->ctx;
+        const size_t n = p->n_tiles();
+        int rc;
+        if ((rc = grow(c, p->tiles, n * p->tile_bytes())) ||
+            (rc = fri_hip_inverse_transform_batch_dev(p->tile.get(), (uint32_t)n, p->coefs, p->tile_coefs(), qmatrix, p->tiles, p->tile_bytes(), nullptr)))
+            return rc;
+        HIP_TRY(c, launch_merge_tiles(p->tiles, p->grid.width, p->grid.height, p->channels, p->grid.tile_w, p->grid.tile_h, p->raster, nullptr));
+        return FRI_HIP_OK;
+    });
+}
+// the tail of the preview of regions: the table up on the null stream, K17 over p->coefs into the plan's packed-output buffer, the rasters down
+int preview_regions_down(fri_hip_plan_tiled *p, const RegionsPlan &r, size_t coef_stride, uint32_t node_stride, uint32_t levels, uint32_t shift, const int32_t qmatrix[32],
+                         uint32_t n_regions, uint8_t *pixels) {
+    return run_down(p, p->regions_out, (size_t)r.total, pixels, [&]() -> int {
+        fri_hip_ctx *c = p->ctx;
+        if (int rc = grow(c, p->region_table, r.table.size())) return rc;
+        HIP_TRY(c, hipMemcpy(p->region_table, r.table.data(), r.table.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        remember(p->planned_preview, n_regions, shift, r);
+        return fri_hip_preview_tiles_regions_dev(p, p->coefs, coef_stride, node_stride, levels, shift, qmatrix, (uint32_t)r.list.size(), n_regions, p->region_table, p->regions_out,
+                                                 nullptr);
+    });
+}
+
 } // namespace
 
 extern "C" {
@@ -227,16 +309,8 @@ int fri_hip_encode_image_tiled_symbols(fri_hip_plan_tiled *p, const uint8_t *pix
 int fri_hip_decode_image_tiled(fri_hip_plan_tiled *p, const int32_t *coefs, const int32_t qmatrix[32], uint8_t *pixels) {
     if (int rc = need_device(p)) return rc;
     if (!coefs || !qmatrix || !pixels) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    fri_hip_ctx *c = p->ctx;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t image = fri_hip_plan_coef_count(p->tile.get()), n = p->n_tiles();
-    int rc;
-    if ((rc = grow(c, p->coefs, n * image)) || (rc = grow(c, p->tiles, n * p->tile_bytes())) || (rc = grow(c, p->raster, p->raster_bytes()))) return rc;
-    HIP_TRY(c, hipMemcpy(p->coefs, coefs, n * image * sizeof(int32_t), hipMemcpyHostToDevice));
-    if ((rc = fri_hip_inverse_transform_batch_dev(p->tile.get(), (uint32_t)n, p->coefs, image, qmatrix, p->tiles, p->tile_bytes(), nullptr))) return rc;
-    HIP_TRY(c, launch_merge_tiles(p->tiles, p->grid.width, p->grid.height, p->channels, p->grid.tile_w, p->grid.tile_h, p->raster, nullptr));
-    HIP_TRY(c, hipMemcpy(pixels, p->raster, p->raster_bytes(), hipMemcpyDeviceToHost));
-    return FRI_HIP_OK;
+    if (int rc = coefs_up(p, coefs, p->n_tiles() * p->tile_coefs())) return rc;
+    return decode_image_down(p, qmatrix, pixels);
 }
 
 /* ---- region decode: only the tiles a rectangle touches ---- */
@@ -265,7 +339,7 @@ int fri_hip_decode_region_tiled_dev(fri_hip_plan_tiled *p, const int32_t *d_coef
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t n = (size_t)range[2] * range[3]; // the touched tiles: the buffer grows to the region's size, never to the image's
     if (int rc = grow(c, p->tiles, n * p->tile_bytes())) return rc;
-    if (int rc = fri_hip_inverse_transform_batch_dev(p->tile.get(), (uint32_t)n, d_coefs, fri_hip_plan_coef_count(p->tile.get()), qmatrix, p->tiles, p->tile_bytes(), stream)) return rc;
+    if (int rc = fri_hip_inverse_transform_batch_dev(p->tile.get(), (uint32_t)n, d_coefs, p->tile_coefs(), qmatrix, p->tiles, p->tile_bytes(), stream)) return rc;
     HIP_TRY(c, launch_merge_tiles_region(p->tiles, p->grid.width, p->grid.height, p->channels, p->grid.tile_w, p->grid.tile_h, x, y, w, h, d_region, s));
     return FRI_HIP_OK;
 }
@@ -274,75 +348,16 @@ int fri_hip_decode_region_tiled(fri_hip_plan_tiled *p, const int32_t *coefs, con
     uint32_t range[4];
     if (!p || !coefs || !qmatrix || !pixels || fri_hip_plan_tiled_region(p, x, y, w, h, range)) return FRI_HIP_ERR_INVALID_ARGUMENT;
     if (int rc = need_device(p)) return rc;
-    fri_hip_ctx *c = p->ctx;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t n = (size_t)range[2] * range[3], image = fri_hip_plan_coef_count(p->tile.get()), bytes = (size_t)w * h * p->channels;
-    int rc;
-    if ((rc = grow(c, p->coefs, n * image)) || (rc = grow(c, p->region, bytes))) return rc;
-    HIP_TRY(c, hipMemcpy(p->coefs, coefs, n * image * sizeof(int32_t), hipMemcpyHostToDevice));
-    if ((rc = fri_hip_decode_region_tiled_dev(p, p->coefs, qmatrix, x, y, w, h, p->region, nullptr))) return rc;
-    HIP_TRY(c, hipMemcpy(pixels, p->region, bytes, hipMemcpyDeviceToHost));
-    return FRI_HIP_OK;
+    if (int rc = coefs_up(p, coefs, (size_t)range[2] * range[3] * p->tile_coefs())) return rc;
+    return run_down(p, p->region, (size_t)w * h * p->channels, pixels, [&] { return fri_hip_decode_region_tiled_dev(p, p->coefs, qmatrix, x, y, w, h, p->region, nullptr); });
 }
 
 /* ---- several regions per call: the tile list, the region table and K15 ---- */
-namespace {
-// What R regions make on the plan's grid (include/fri_emit.h, "Several regions"): the tile list, the region table, its n_groups and the packed output's bytes.
-struct RegionsPlan {
-    std::vector<uint32_t> list, table;
-    uint32_t n_groups = 0;
-    uint64_t total = 0; // off_R
-};
-// the end of both kinds of table: row R, and slot[] from the marks the regions left in it - the tile list in ascending order
-void finish_regions_plan(RegionsPlan &out, uint32_t n_regions, size_t n_grid, uint64_t total, uint64_t groups) {
-    uint32_t *last = out.table.data() + 8 * (size_t)n_regions, *slot = last + 8;
-    last[4] = (uint32_t)total, last[5] = (uint32_t)(total >> 32), last[6] = (uint32_t)groups;
-    out.list.clear();
-    for (size_t t = 0; t < n_grid; t++) {
-        if (slot[t]) slot[t] = (uint32_t)out.list.size(), out.list.push_back((uint32_t)t);
-        else slot[t] = 0xFFFFFFFFu;
-    }
-    out.n_groups = (uint32_t)groups, out.total = total;
-}
-// false for R = 0, R > 65535, a region the grid refuses and n_groups >= 2^31
-bool plan_regions(const fri_hip_plan_tiled *p, uint32_t n_regions, const uint32_t *regions, RegionsPlan &out) {
-    const TileGrid &g = p->grid;
-    if (!regions || !n_regions || n_regions > 65535u || (uint64_t)g.width * p->channels > 0x7FFFFFFFull) return false;
-    const size_t n_grid = g.n_tiles(), rows = 8 * ((size_t)n_regions + 1);
-    out.table.assign(rows + n_grid, 0);
-    uint32_t *slot = out.table.data() + rows;
-    uint64_t off = 0, groups = 0;
-    for (uint32_t r = 0; r < n_regions; r++) {
-        const uint32_t *q = regions + 4 * (size_t)r;
-        uint32_t range[4];
-        if (g.region(q[0], q[1], q[2], q[3], range)) return false;
-        for (uint32_t b = 0; b < range[3]; b++) std::fill_n(slot + ((size_t)range[1] + b) * g.nx + range[0], range[2], 1u); // touched
-        uint32_t *row = out.table.data() + 8 * (size_t)r;
-        row[0] = q[0], row[1] = q[1], row[2] = q[2], row[3] = q[3];
-        row[4] = (uint32_t)off, row[5] = (uint32_t)(off >> 32), row[6] = (uint32_t)groups;
-        const uint64_t strips = ((uint64_t)q[2] * p->channels + 15) / 16; // of one row: a lane owns 16 bytes of it
-        off += (uint64_t)q[2] * q[3] * p->channels;
-        groups += ((uint64_t)q[3] * strips + 255) / 256;
-        if (groups >= 0x80000000ull) return false; // (w C < 2^31 and h < 2^32: neither sum can have wrapped before this is seen)
-    }
-    finish_regions_plan(out, n_regions, n_grid, off, groups);
-    return true;
-}
-void remember(fri_hip_plan_tiled *p, uint32_t n_regions, const RegionsPlan &r) {
-    p->planned.n_regions = n_regions, p->planned.n_list = (uint32_t)r.list.size(), p->planned.n_groups = r.n_groups;
-}
-} // namespace
-
 int fri_hip_plan_tiled_regions(fri_hip_plan_tiled *p, uint32_t n_regions, const uint32_t *regions, uint32_t *list, size_t list_cap, size_t *n_list, uint32_t *table,
                                size_t table_cap_words) {
     RegionsPlan r;
     if (!p || !n_list || !plan_regions(p, n_regions, regions, r)) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    *n_list = r.list.size();
-    if (!list || list_cap < r.list.size() || !table || table_cap_words < r.table.size()) return -3; // the size query (the emitter's code for a buffer that is too small)
-    std::copy(r.list.begin(), r.list.end(), list);
-    std::copy(r.table.begin(), r.table.end(), table);
-    remember(p, n_regions, r);
-    return FRI_HIP_OK;
+    return write_regions_plan(r, n_regions, 0, p->planned, list, list_cap, n_list, table, table_cap_words);
 }
 
 int fri_hip_merge_tiles_regions_dev(fri_hip_plan_tiled *p, const uint8_t *d_tiles, uint32_t n_list, uint32_t n_regions, const uint32_t *d_table, uint8_t *d_out, void *stream) {
@@ -373,8 +388,8 @@ int fri_hip_decode_regions_tiled_dev(fri_hip_plan_tiled *p, const int32_t *d_coe
     // the table goes up in stream order; the wait is for the source, which is this call's own memory (a few KiB, ahead of everything this call enqueues)
     HIP_TRY(c, hipMemcpyAsync(p->region_table, r.table.data(), r.table.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
     HIP_TRY(c, hipStreamSynchronize(s));
-    remember(p, n_regions, r);
-    if ((rc = fri_hip_inverse_transform_batch_dev(p->tile.get(), (uint32_t)n, d_coefs, fri_hip_plan_coef_count(p->tile.get()), qmatrix, p->tiles, p->tile_bytes(), stream))) return rc;
+    remember(p->planned, n_regions, 0, r);
+    if ((rc = fri_hip_inverse_transform_batch_dev(p->tile.get(), (uint32_t)n, d_coefs, p->tile_coefs(), qmatrix, p->tiles, p->tile_bytes(), stream))) return rc;
     HIP_TRY(c, launch_merge_tiles_regions(p->tiles, p->channels, p->grid.tile_w, p->grid.tile_h, p->grid.nx, n_regions, r.n_groups, p->region_table, d_out, s));
     return FRI_HIP_OK;
 }
@@ -383,15 +398,8 @@ int fri_hip_decode_regions_tiled(fri_hip_plan_tiled *p, const int32_t *coefs, co
     RegionsPlan r;
     if (!p || !coefs || !qmatrix || !pixels || !plan_regions(p, n_regions, regions, r)) return FRI_HIP_ERR_INVALID_ARGUMENT;
     if (int rc = need_device(p)) return rc;
-    fri_hip_ctx *c = p->ctx;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t n = r.list.size(), image = fri_hip_plan_coef_count(p->tile.get());
-    int rc;
-    if ((rc = grow(c, p->coefs, n * image)) || (rc = grow(c, p->regions_out, (size_t)r.total))) return rc;
-    HIP_TRY(c, hipMemcpy(p->coefs, coefs, n * image * sizeof(int32_t), hipMemcpyHostToDevice));
-    if ((rc = fri_hip_decode_regions_tiled_dev(p, p->coefs, qmatrix, n_regions, regions, p->regions_out, nullptr))) return rc;
-    HIP_TRY(c, hipMemcpy(pixels, p->regions_out, (size_t)r.total, hipMemcpyDeviceToHost));
-    return FRI_HIP_OK;
+    if (int rc = coefs_up(p, coefs, r.list.size() * p->tile_coefs())) return rc;
+    return run_down(p, p->regions_out, (size_t)r.total, pixels, [&] { return fri_hip_decode_regions_tiled_dev(p, p->coefs, qmatrix, n_regions, regions, p->regions_out, nullptr); });
 }
 
 int fri_hip_decode_regions_tiled_coded(fri_hip_plan_tiled *p, uint32_t n_regions, const uint32_t *regions, const uint32_t *words, size_t word_stride, const uint32_t *n_words,
@@ -401,37 +409,12 @@ int fri_hip_decode_regions_tiled_coded(fri_hip_plan_tiled *p, uint32_t n_regions
     const CodedPlanes in{words, word_stride, n_words, models, off_values, value_params, width_params};
     if (!p || !in.complete() || !qmatrix || !pixels || !status || !plan_regions(p, n_regions, regions, r)) return FRI_HIP_ERR_INVALID_ARGUMENT;
     if (int rc = need_device(p)) return rc;
-    if (!p->tile->d_stream_order) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    fri_hip_ctx *c = p->ctx;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t image = fri_hip_plan_coef_count(p->tile.get()), n = r.list.size(), planes = n * p->channels;
-    if (!decode_counts_ok((uint32_t)planes)) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    int rc;
-    if ((rc = grow(c, p->coefs, n * image)) || (rc = grow(c, p->regions_out, (size_t)r.total))) return rc;
-    CodedOnDevice d;
-    if ((rc = upload_coded(p, in, planes, p->rans_words, d)) || (rc = decode_coded_batch(p->tile.get(), d, 0, planes, p->coefs, image / p->channels))) return rc;
-    if ((rc = read_back_decode_status(c, d, status))) {
-        for (size_t k = 0; k < planes && rc == FRI_HIP_ERR_INVALID_ARGUMENT; k++)
-            if (status[4 * k]) { // the first refused plane, by its tile's index in the file's grid
-                c->last_error = "fri_hip_decode_regions_tiled_coded: tile " + std::to_string(r.list[k / p->channels]) + ": channel " + std::to_string(k % p->channels) +
-                                ": the device decoder refused the plane (status " + std::to_string(status[4 * k]) + ")";
-                break;
-            }
-        return rc;
-    }
-    if ((rc = fri_hip_decode_regions_tiled_dev(p, p->coefs, qmatrix, n_regions, regions, p->regions_out, nullptr))) return rc;
-    HIP_TRY(c, hipMemcpy(pixels, p->regions_out, (size_t)r.total, hipMemcpyDeviceToHost));
-    return FRI_HIP_OK;
+    if (int rc = decode_coded_front(p, in, r.list.size(), kDepth, status, &r.list, __func__)) return rc;
+    return run_down(p, p->regions_out, (size_t)r.total, pixels, [&] { return fri_hip_decode_regions_tiled_dev(p, p->coefs, qmatrix, n_regions, regions, p->regions_out, nullptr); });
 }
 
 /* ---- region update: only the tiles a rectangle touches are split and coded ---- */
 namespace {
-// {cx, cy, cw, ch}: the in-image pixels of the sub-grid `range` = {i0, j0, ni, nj}
-void cover_of(const TileGrid &g, const uint32_t range[4], uint32_t out[4]) {
-    out[0] = range[0] * g.tile_w, out[1] = range[1] * g.tile_h;
-    out[2] = (uint32_t)(std::min<uint64_t>(((uint64_t)range[0] + range[2]) * g.tile_w, g.width) - out[0]);
-    out[3] = (uint32_t)(std::min<uint64_t>(((uint64_t)range[1] + range[3]) * g.tile_h, g.height) - out[1]);
-}
 // the source rectangle lies in the image and contains the covered rectangle; its pitch holds a row
 bool source_ok(const fri_hip_plan_tiled *p, size_t src_pitch, uint32_t src_x, uint32_t src_y, uint32_t src_w, uint32_t src_h, const uint32_t range[4]) {
     uint32_t c[4];
@@ -584,20 +567,9 @@ int fri_hip_decode_image_tiled_coded(fri_hip_plan_tiled *p, const uint32_t *word
                                      uint32_t *status) {
     if (int rc = need_device(p)) return rc;
     const CodedPlanes in{words, word_stride, n_words, models, off_values, value_params, width_params};
-    if (!in.complete() || !qmatrix || !pixels || !status || !p->tile->d_stream_order) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    fri_hip_ctx *c = p->ctx;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t image = fri_hip_plan_coef_count(p->tile.get()), n = p->n_tiles(), planes = n * p->channels;
-    if (!decode_counts_ok((uint32_t)planes)) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    int rc;
-    if ((rc = grow(c, p->coefs, n * image)) || (rc = grow(c, p->tiles, n * p->tile_bytes())) || (rc = grow(c, p->raster, p->raster_bytes()))) return rc;
-    CodedOnDevice d;
-    if ((rc = upload_coded(p, in, planes, p->rans_words, d)) || (rc = decode_coded_batch(p->tile.get(), d, 0, planes, p->coefs, image / p->channels))) return rc;
-    if ((rc = read_back_decode_status(c, d, status))) return rc;
-    if ((rc = fri_hip_inverse_transform_batch_dev(p->tile.get(), (uint32_t)n, p->coefs, image, qmatrix, p->tiles, p->tile_bytes(), nullptr))) return rc;
-    HIP_TRY(c, launch_merge_tiles(p->tiles, p->grid.width, p->grid.height, p->channels, p->grid.tile_w, p->grid.tile_h, p->raster, nullptr));
-    HIP_TRY(c, hipMemcpy(pixels, p->raster, p->raster_bytes(), hipMemcpyDeviceToHost));
-    return FRI_HIP_OK;
+    if (!in.complete() || !qmatrix || !pixels || !status) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    if (int rc = decode_coded_front(p, in, p->n_tiles(), kDepth, status, nullptr, __func__)) return rc;
+    return decode_image_down(p, qmatrix, pixels);
 }
 
 /* ---- preview decode: stop at a level, write a thumbnail (K14) ---- */
@@ -617,18 +589,12 @@ int fri_hip_preview_tiles_dev(fri_hip_plan_tiled *p, const int32_t *d_coefs, siz
 
 int fri_hip_preview_image_tiled(fri_hip_plan_tiled *p, const int32_t *coefs, uint32_t levels, uint32_t shift, const int32_t qmatrix[32], uint8_t *pixels) {
     if (int rc = need_device(p)) return rc;
-    if (!coefs || !qmatrix || !pixels || !preview_args_ok(levels, shift)) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    fri_hip_ctx *c = p->ctx;
-    HIP_TRY(c, hipSetDevice(c->device));
     uint32_t size[2];
-    fri_hip_preview_size(p->grid.width, p->grid.height, shift, size);
-    const size_t plane = p->tile->geo.centers.size() << levels, n = p->n_tiles() * p->channels * plane, bytes = (size_t)size[0] * size[1] * p->channels;
-    int rc;
-    if ((rc = grow(c, p->coefs, n)) || (rc = grow(c, p->preview, bytes))) return rc;
-    HIP_TRY(c, hipMemcpy(p->coefs, coefs, n * sizeof(int32_t), hipMemcpyHostToDevice)); // the compact planes: 2^(levels - 9) of a full decode's upload
-    if ((rc = fri_hip_preview_tiles_dev(p, p->coefs, plane, 1u << levels, levels, shift, qmatrix, p->preview, nullptr))) return rc;
-    HIP_TRY(c, hipMemcpy(pixels, p->preview, bytes, hipMemcpyDeviceToHost));
-    return FRI_HIP_OK;
+    if (!coefs || !qmatrix || !pixels || !preview_args_ok(levels, shift) || preview_size(p->grid.width, p->grid.height, shift, size)) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    if (int rc = coefs_up(p, coefs, p->n_tiles() * p->preview_coefs(levels))) return rc; // the compact planes: 2^(levels - 9) of a full decode's upload
+    return run_down(p, p->preview, (size_t)size[0] * size[1] * p->channels, pixels, [&] {
+        return fri_hip_preview_tiles_dev(p, p->coefs, p->preview_coefs(levels) / p->channels, 1u << levels, levels, shift, qmatrix, p->preview, nullptr);
+    });
 }
 
 int fri_hip_preview_image_tiled_coded(fri_hip_plan_tiled *p, const uint32_t *words, size_t word_stride, const uint32_t *n_words, const uint32_t *models,
@@ -636,84 +602,21 @@ int fri_hip_preview_image_tiled_coded(fri_hip_plan_tiled *p, const uint32_t *wor
                                       const int32_t qmatrix[32], uint8_t *pixels, uint32_t *status) {
     if (int rc = need_device(p)) return rc;
     const CodedPlanes in{words, word_stride, n_words, models, off_values, value_params, width_params};
-    if (!in.complete() || !qmatrix || !pixels || !status || !preview_args_ok(levels, shift) || !p->tile->d_stream_order) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    fri_hip_ctx *c = p->ctx;
-    HIP_TRY(c, hipSetDevice(c->device));
     uint32_t size[2];
-    fri_hip_preview_size(p->grid.width, p->grid.height, shift, size);
-    const size_t image = fri_hip_plan_coef_count(p->tile.get()), n = p->n_tiles(), planes = n * p->channels, bytes = (size_t)size[0] * size[1] * p->channels;
-    if (!decode_counts_ok((uint32_t)planes)) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    int rc;
-    if ((rc = grow(c, p->coefs, n * image)) || (rc = grow(c, p->preview, bytes))) return rc;
-    CodedOnDevice d;
-    if ((rc = upload_coded(p, in, planes, p->rans_words, d)) || (rc = decode_coded_batch(p->tile.get(), d, 0, planes, p->coefs, image / p->channels, levels))) return rc;
-    if ((rc = read_back_decode_status(c, d, status))) return rc;
-    if ((rc = fri_hip_preview_tiles_dev(p, p->coefs, image / p->channels, kCell, levels, shift, qmatrix, p->preview, nullptr))) return rc;
-    HIP_TRY(c, hipMemcpy(pixels, p->preview, bytes, hipMemcpyDeviceToHost));
-    return FRI_HIP_OK;
+    if (!in.complete() || !qmatrix || !pixels || !status || !preview_args_ok(levels, shift) || preview_size(p->grid.width, p->grid.height, shift, size))
+        return FRI_HIP_ERR_INVALID_ARGUMENT;
+    if (int rc = decode_coded_front(p, in, p->n_tiles(), levels, status, nullptr, __func__)) return rc;
+    return run_down(p, p->preview, (size_t)size[0] * size[1] * p->channels, pixels, [&] {
+        return fri_hip_preview_tiles_dev(p, p->coefs, p->tile_coefs() / p->channels, kCell, levels, shift, qmatrix, p->preview, nullptr);
+    });
 }
 
 /* ---- preview of regions: the tile list of the source rectangles, the preview-region table and K17 ---- */
-namespace {
-// What R regions of the thumbnail at `shift` make on the plan's grid (include/fri_hip.h, "Preview of regions"): the tile list of their source rectangles, the
-// preview-region table, its n_groups and the packed output's bytes. false for shift > 4, R = 0, R > 65535, a region that is empty or leaves the thumbnail and
-// n_groups >= 2^31.
-bool plan_preview_regions(const fri_hip_plan_tiled *p, uint32_t shift, uint32_t n_regions, const uint32_t *regions, RegionsPlan &out) {
-    const TileGrid &g = p->grid;
-    uint32_t size[2];
-    if (!regions || !n_regions || n_regions > 65535u || fri_hip_preview_size(g.width, g.height, shift, size)) return false;
-    const size_t n_grid = g.n_tiles(), rows = 8 * ((size_t)n_regions + 1);
-    out.table.assign(rows + n_grid, 0);
-    uint32_t *slot = out.table.data() + rows;
-    const uint64_t S = 1ull << shift;
-    const auto xs = [&](uint64_t X) { return (uint32_t)std::min<uint64_t>(X * S + S / 2, (uint64_t)g.width - 1); };
-    const auto ys = [&](uint64_t Y) { return (uint32_t)std::min<uint64_t>(Y * S + S / 2, (uint64_t)g.height - 1); };
-    uint64_t off = 0, groups = 0;
-    for (uint32_t r = 0; r < n_regions; r++) {
-        const uint32_t *q = regions + 4 * (size_t)r;
-        if (!q[2] || !q[3] || (uint64_t)q[0] + q[2] > size[0] || (uint64_t)q[1] + q[3] > size[1]) return false;
-        const uint32_t x0 = xs(q[0]), y0 = ys(q[1]);
-        uint32_t range[4];
-        if (g.region(x0, y0, xs((uint64_t)q[0] + q[2] - 1) - x0 + 1, ys((uint64_t)q[1] + q[3] - 1) - y0 + 1, range)) return false; // the source rectangle
-        for (uint32_t b = 0; b < range[3]; b++) std::fill_n(slot + ((size_t)range[1] + b) * g.nx + range[0], range[2], 1u); // touched
-        const uint32_t blocks_x = (uint32_t)(((uint64_t)q[2] + 15) / 16);
-        uint32_t *row = out.table.data() + 8 * (size_t)r;
-        row[0] = q[0], row[1] = q[1], row[2] = q[2], row[3] = q[3];
-        row[4] = (uint32_t)off, row[5] = (uint32_t)(off >> 32), row[6] = (uint32_t)groups, row[7] = blocks_x;
-        off += (uint64_t)q[2] * q[3] * p->channels;
-        groups += (uint64_t)blocks_x * (((uint64_t)q[3] + 15) / 16);
-        if (groups >= 0x80000000ull) return false; // (each term is below 2^56: the sum cannot have wrapped before this is seen)
-    }
-    finish_regions_plan(out, n_regions, n_grid, off, groups);
-    return true;
-}
-void remember_preview(fri_hip_plan_tiled *p, uint32_t shift, uint32_t n_regions, const RegionsPlan &r) {
-    p->planned_preview.n_regions = n_regions, p->planned_preview.n_list = (uint32_t)r.list.size(), p->planned_preview.n_groups = r.n_groups, p->planned_preview.shift = shift;
-}
-// the table up on the null stream, K17 over the plan's coefficient buffer into its packed-output buffer, the rasters down
-int preview_regions_run(fri_hip_plan_tiled *p, const RegionsPlan &r, size_t coef_stride, uint32_t node_stride, uint32_t levels, uint32_t shift, const int32_t qmatrix[32],
-                        uint32_t n_regions, uint8_t *pixels) {
-    fri_hip_ctx *c = p->ctx;
-    HIP_TRY(c, hipMemcpy(p->region_table, r.table.data(), r.table.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    remember_preview(p, shift, n_regions, r);
-    if (int rc = fri_hip_preview_tiles_regions_dev(p, p->coefs, coef_stride, node_stride, levels, shift, qmatrix, (uint32_t)r.list.size(), n_regions, p->region_table,
-                                                   p->regions_out, nullptr))
-        return rc;
-    HIP_TRY(c, hipMemcpy(pixels, p->regions_out, (size_t)r.total, hipMemcpyDeviceToHost));
-    return FRI_HIP_OK;
-}
-} // namespace
-
 int fri_hip_plan_tiled_preview_regions(fri_hip_plan_tiled *p, uint32_t shift, uint32_t n_regions, const uint32_t *regions, uint32_t *list, size_t list_cap, size_t *n_list,
                                        uint32_t *table, size_t table_cap_words) {
     RegionsPlan r;
     if (!p || !n_list || !plan_preview_regions(p, shift, n_regions, regions, r)) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    *n_list = r.list.size();
-    if (!list || list_cap < r.list.size() || !table || table_cap_words < r.table.size()) return -3; // the size query, as in fri_hip_plan_tiled_regions
-    std::copy(r.list.begin(), r.list.end(), list);
-    std::copy(r.table.begin(), r.table.end(), table);
-    remember_preview(p, shift, n_regions, r);
-    return FRI_HIP_OK;
+    return write_regions_plan(r, n_regions, shift, p->planned_preview, list, list_cap, n_list, table, table_cap_words);
 }
 
 int fri_hip_preview_tiles_regions_dev(fri_hip_plan_tiled *p, const int32_t *d_coefs, size_t coef_stride, uint32_t node_stride, uint32_t levels, uint32_t shift,
@@ -741,14 +644,9 @@ int fri_hip_preview_regions_tiled(fri_hip_plan_tiled *p, const int32_t *coefs, u
     RegionsPlan r;
     if (!p || !coefs || !qmatrix || !pixels || !preview_args_ok(levels, shift) || !plan_preview_regions(p, shift, n_regions, regions, r)) return FRI_HIP_ERR_INVALID_ARGUMENT;
     if (int rc = need_device(p)) return rc;
-    fri_hip_ctx *c = p->ctx;
-    HIP_TRY(c, hipSetDevice(c->device));
-    // the listed tiles' compact planes: the buffers grow to the regions' tiles, never to the image's
-    const size_t plane = p->tile->geo.centers.size() << levels, n = r.list.size() * p->channels * plane;
-    int rc;
-    if ((rc = grow(c, p->coefs, n)) || (rc = grow(c, p->region_table, r.table.size())) || (rc = grow(c, p->regions_out, (size_t)r.total))) return rc;
-    HIP_TRY(c, hipMemcpy(p->coefs, coefs, n * sizeof(int32_t), hipMemcpyHostToDevice)); // 2^(levels - 9) of fri_hip_decode_regions_tiled's upload
-    return preview_regions_run(p, r, plane, 1u << levels, levels, shift, qmatrix, n_regions, pixels);
+    // the listed tiles' compact planes, 2^(levels - 9) of fri_hip_decode_regions_tiled's upload: the buffers grow to the regions' tiles, never to the image's
+    if (int rc = coefs_up(p, coefs, r.list.size() * p->preview_coefs(levels))) return rc;
+    return preview_regions_down(p, r, p->preview_coefs(levels) / p->channels, 1u << levels, levels, shift, qmatrix, n_regions, pixels);
 }
 
 int fri_hip_preview_regions_tiled_coded(fri_hip_plan_tiled *p, uint32_t n_regions, const uint32_t *regions, const uint32_t *words, size_t word_stride, const uint32_t *n_words,
@@ -759,25 +657,8 @@ int fri_hip_preview_regions_tiled_coded(fri_hip_plan_tiled *p, uint32_t n_region
     if (!p || !in.complete() || !qmatrix || !pixels || !status || !preview_args_ok(levels, shift) || !plan_preview_regions(p, shift, n_regions, regions, r))
         return FRI_HIP_ERR_INVALID_ARGUMENT;
     if (int rc = need_device(p)) return rc;
-    if (!p->tile->d_stream_order) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    fri_hip_ctx *c = p->ctx;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t image = fri_hip_plan_coef_count(p->tile.get()), n = r.list.size(), planes = n * p->channels;
-    if (!decode_counts_ok((uint32_t)planes)) return FRI_HIP_ERR_INVALID_ARGUMENT;
-    int rc;
-    if ((rc = grow(c, p->coefs, n * image)) || (rc = grow(c, p->region_table, r.table.size())) || (rc = grow(c, p->regions_out, (size_t)r.total))) return rc;
-    CodedOnDevice d;
-    if ((rc = upload_coded(p, in, planes, p->rans_words, d)) || (rc = decode_coded_batch(p->tile.get(), d, 0, planes, p->coefs, image / p->channels, levels))) return rc;
-    if ((rc = read_back_decode_status(c, d, status))) {
-        for (size_t k = 0; k < planes && rc == FRI_HIP_ERR_INVALID_ARGUMENT; k++)
-            if (status[4 * k]) { // the first refused plane, by its tile's index in the file's grid
-                c->last_error = "fri_hip_preview_regions_tiled_coded: tile " + std::to_string(r.list[k / p->channels]) + ": channel " + std::to_string(k % p->channels) +
-                                ": the device decoder refused the plane (status " + std::to_string(status[4 * k]) + ")";
-                break;
-            }
-        return rc;
-    }
-    return preview_regions_run(p, r, image / p->channels, kCell, levels, shift, qmatrix, n_regions, pixels);
+    if (int rc = decode_coded_front(p, in, r.list.size(), levels, status, &r.list, __func__)) return rc;
+    return preview_regions_down(p, r, p->tile_coefs() / p->channels, kCell, levels, shift, qmatrix, n_regions, pixels);
 }
 
 } // extern "C"

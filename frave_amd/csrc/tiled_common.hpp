@@ -1,28 +1,14 @@
-// tiled_common.hpp -- what the tiled plan kinds of the C ABI share (fri_hip_tiled.cpp, fri_hip_tiled420.cpp, fri_hip_tiled_rgba.cpp): the tile grid, the
-// first-fit search for a tile shape, the skeleton of a tiled plan's creation, the host form of the size estimate, and the coded routes - K11 over a batch of
+// tiled_common.hpp -- what the tiled plan kinds of the C ABI share (fri_hip_tiled.cpp, fri_hip_tiled420.cpp, fri_hip_tiled_rgba.cpp): the tile grid and the
+// region tables on it (region_table.hpp, plain C++, included here), the first-fit search for a tile shape, the skeleton of a tiled plan's creation, the host form of the size estimate, and the coded routes - K11 over a batch of
 // planes with its one second pass, and the read-back behind it; the upload of coded planes and K13 over them. Private to libfri_hip.so.
 #pragma once
 #include "fri_hip_internal.hpp"
+#include "region_table.hpp"
 
 #include <initializer_list>
 #include <new>
 
 namespace fri::host {
-
-// An image cut into nx x ny tiles of tile_w x tile_h, row by row; the last column and row may reach past the image.
-struct TileGrid {
-    uint32_t width = 0, height = 0, tile_w = 0, tile_h = 0, nx = 0, ny = 0;
-    size_t n_tiles() const { return (size_t)nx * ny; }
-    // fri_hip_plan_tiled*_grid
-    void shape(uint32_t out[4]) const { out[0] = nx, out[1] = ny, out[2] = tile_w, out[3] = tile_h; }
-    // fri_hip_plan_tiled*_region: the sub-grid (i0, j0, ni, nj) of tiles that the rectangle x, y, w, h touches; refused when empty or leaving the image
-    int region(uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint32_t out[4]) const {
-        if (!out || !w || !h || (uint64_t)x + w > width || (uint64_t)y + h > height) return FRI_HIP_ERR_INVALID_ARGUMENT;
-        out[0] = x / tile_w, out[1] = y / tile_h;
-        out[2] = (uint32_t)(((uint64_t)x + w - 1) / tile_w) - out[0] + 1, out[3] = (uint32_t)(((uint64_t)y + h - 1) / tile_h) - out[1] + 1;
-        return FRI_HIP_OK;
-    }
-};
 
 // the C = 1 lattice of w x h owns every pixel
 inline bool lattice_is_whole(uint64_t w, uint64_t h) {

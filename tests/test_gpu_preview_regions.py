@@ -7,6 +7,7 @@
 - the output at an odd byte offset between guard bytes, the input the listed tiles only, between planes of a value that would show;
 - a replay from a captured graph of the one kernel node; refused arguments launch nothing; the memory of the last table is not the one K15's entry keeps;
 - the coded route, the host route and the definition agree; a refused plane is reported by its tile in the file's grid and no pixel is written;
+- the decode routes of a tiled plan one after another on ONE plan, a small call first, give what each gives on a fresh plan (they share the staging buffers);
 - fri_driver decode-regions --preview M writes the crops of decode-file --preview M, with and without --device-rans, and its refusals write nothing.
 
 The forms that grow buffers (fri_hip_preview_regions_tiled, ..._coded) take no stream argument, so there is no capturing stream to hand them: what can be
@@ -288,6 +289,42 @@ def test_coded_route_host_route_and_definition_agree(ctx, name):
         got, status = T.preview_regions_coded(emit.tiled_parse_coded_tiles(frv, tiles), levels, shift, regs, qm)
         assert status.shape == (tiles.size * c, 4) and not status.any()
         _same(got, want, ("coded", levels, shift))
+    T.close()
+
+
+def test_routes_in_turn_on_one_plan_equal_fresh_plans(ctx):
+    """The decode routes share the plan's staging buffers (coefs, rans_words, region_table, regions_out, preview) and each grows what it needs: on ONE plan a
+    small call first and larger ones behind it - regions coded in one tile, the whole image coded, a preview of two regions coded, the preview coded, every tile
+    as one region from host planes - each give the bytes of the same call on a fresh plan. The lossless RGB file of this module (2 x 3 tiles, the smallest
+    lossless RGB file the GPU tests build)."""
+    w, h, c, tw, th, quality, flags = FILES["rct"]
+    frv = tiled_file(w, h, c, tw, th, quality, **flags)[0]
+    ti = emit.tiled_info(frv)
+    whole, one, two, every = emit.tiled_parse_coded(frv), [(5, 7, 20, 10)], [(3, 3, 20, 20), (100, 120, 40, 30)], [(0, 0, w, h)]
+    routes = [
+        lambda T, qm: T.decode_regions_coded(emit.tiled_parse_coded_tiles(frv, T.regions(one)[0]), one, qm),
+        lambda T, qm: T.decode_coded(whole, qm),
+        lambda T, qm: T.preview_regions_coded(emit.tiled_parse_coded_tiles(frv, plan_table(T, 1, two)[0]), 7, 1, two, qm),
+        lambda T, qm: T.preview_coded(whole, 5, 2, qm),
+        lambda T, qm: (T.decode_regions_tiled(emit.tiled_decode_tiles(frv, T.regions(every)[0])[1], every, qm), None),
+    ]
+
+    def parts(result):
+        pixels, status = result
+        return list(pixels) if isinstance(pixels, list) else [pixels], status
+
+    T, qm = _decoder_plan(ctx, ti)
+    assert (T.nx, T.ny) == (2, 3) and T.regions(one)[0].tolist() == [0] and plan_table(T, 1, two)[0].tolist() == [0, 5] and T.regions(every)[0].size == 6
+    seen = []
+    for k, route in enumerate(routes):
+        got, status = parts(route(T, qm))
+        F, _ = _decoder_plan(ctx, ti)
+        want, want_status = parts(route(F, qm))
+        F.close()
+        assert len(got) == len(want) and all(a.shape == b.shape and np.array_equal(a, b) for a, b in zip(got, want)), k
+        assert status is None or (np.array_equal(status, want_status) and not status.any()), k
+        seen.append(got)
+    assert np.array_equal(seen[4][0].reshape(-1), seen[1][0])  # the last route's one region is the whole image
     T.close()
 
 
