@@ -1,5 +1,5 @@
-// libfri.cpp -- see libfri.hpp. Host glue over the C ABI; no compute here.
-#include "libfri.hpp"
+// libfri.cpp -- see libfri.hpp. Host glue over the C ABI; no compute here. The tiled routes are in libfri_tiled.cpp, the steps both share in libfri_glue.hpp.
+#include "libfri_glue.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -54,20 +54,17 @@ fri_hip_plan *Device::plan(uint32_t width, uint32_t height, uint32_t channels, s
     return p;
 }
 
-namespace {
-// The colour transform is plan state and a Device's plans are shared by shape: every caller sets the mode its launches need.
-std::string set_colour_transform(fri_hip_plan *plan, bool rct, Device &dev, bool ycbcr = false) {
+// (these three and set_plan_stream_order below are declared in libfri_glue.hpp, which says what they are for: libfri_tiled.cpp calls them too)
+std::string set_colour_transform(fri_hip_plan *plan, bool rct, Device &dev, bool ycbcr) {
     const int rc = fri_hip_plan_set_colour_transform(plan, ycbcr ? FRI_HIP_COLOUR_YCBCR : rct ? FRI_HIP_COLOUR_RCT : FRI_HIP_COLOUR_NONE);
     return rc == FRI_HIP_OK ? std::string() : dev.describe(rc);
 }
-// what an encode of `colorspace` pixels codes: RGB with either option on goes out as Y, Cb, Cr (colour space YCbCr, flagged); YCbCr only with a quality
 ImageMetadata coded_metadata(uint32_t height, uint32_t width, ColorSpace colorspace, const EncoderOpts &opts) {
     const bool rct = opts.colour_transform && colorspace == ColorSpace::RGB;
     const uint32_t quality = (uint32_t)(opts.quality > 0 && opts.quality < 100 ? opts.quality : 0);
     const bool ycbcr = opts.ycbcr && colorspace == ColorSpace::RGB && quality;
     return ImageMetadata{height, width, rct || ycbcr ? ColorSpace::YCbCr : colorspace, rct, quality, ycbcr};
 }
-// The matrix an encode quantises with: fri_hip_quality_matrix(opts.quality) for a lossy encode, else opts.quantization_matrix. "" or the error.
 std::string coding_matrix(const EncoderOpts &opts, std::array<int32_t, 32> &q) {
     if (opts.quality < 0 || opts.quality > 99) return "quality must be 0 (lossless) or 1..99";
     if (!(opts.target_psnr >= 0)) return "target_psnr must be >= 0";
@@ -86,8 +83,7 @@ std::string coding_matrix(const EncoderOpts &opts, std::array<int32_t, 32> &q) {
     if (opts.quality) fri_hip_quality_matrix(opts.quality, q.data());
     return std::string();
 }
-emit::ColorSpaceCode colour_code(ColorSpace c) { return c == ColorSpace::Luma ? emit::kLuma : c == ColorSpace::RGB ? emit::kRGB : emit::kYCbCr; }
-} // namespace
+static emit::ColorSpaceCode colour_code(ColorSpace c) { return c == ColorSpace::Luma ? emit::kLuma : c == ColorSpace::RGB ? emit::kRGB : emit::kYCbCr; }
 
 std::array<double, 6> ContextModeler::solve_normal_equations(const double (&m)[6][6], const double (&y)[6]) {
     std::array<double, 6> x{};
@@ -179,17 +175,12 @@ Result<RasterImage> decode(const WaveletImage &image, const EncoderOpts &opts, D
             r.error = "coefficient array does not match the image geometry";
             return r;
         }
-        if (!(r.error = set_colour_transform(colour, image.metadata.rct, dev, image.metadata.ycbcr)).empty()) return r;
-        std::array<int32_t, 32> qm = opts.quantization_matrix;
-        if (image.metadata.quality && fri_hip_quality_matrix((int)image.metadata.quality, qm.data()) != FRI_HIP_OK) {
-            r.error = "invalid quality";
-            return r;
-        }
-        int rc = fri_hip_plan_set_dequantiser(colour, image.metadata.quality ? FRI_HIP_DEQUANT_MIDPOINT : FRI_HIP_DEQUANT_REFERENCE);
+        std::array<int32_t, 32> qm;
+        if (!(r.error = prepare_decode(colour, image.metadata.rct, image.metadata.ycbcr, image.metadata.quality, opts, dev, qm)).empty()) return r;
         r.value.metadata = ImageMetadata{image.metadata.height, image.metadata.width, ColorSpace::RGB};
         r.value.metadata.alpha = true;
         r.value.data.resize((size_t)image.metadata.width * image.metadata.height * 4);
-        if (rc == FRI_HIP_OK) rc = fri_hip_decode_image_rgba(both, image.coefficients.data(), qm.data(), r.value.data.data());
+        const int rc = fri_hip_decode_image_rgba(both, image.coefficients.data(), qm.data(), r.value.data.data());
         if (rc != FRI_HIP_OK) r.error = dev.describe(rc);
         r.ok = rc == FRI_HIP_OK;
         return r;
@@ -201,17 +192,9 @@ Result<RasterImage> decode(const WaveletImage &image, const EncoderOpts &opts, D
         r.error = "coefficient array does not match the image geometry";
         return r;
     }
-    if (!(r.error = set_colour_transform(plan, image.metadata.rct, dev, image.metadata.ycbcr)).empty()) return r;
     // a lossy image: the matrix of its quality and the midpoint dequantiser; otherwise the caller's matrix and the reference's dequantiser
-    std::array<int32_t, 32> qm = opts.quantization_matrix;
-    if (image.metadata.quality && fri_hip_quality_matrix((int)image.metadata.quality, qm.data()) != FRI_HIP_OK) {
-        r.error = "invalid quality";
-        return r;
-    }
-    if (int rc = fri_hip_plan_set_dequantiser(plan, image.metadata.quality ? FRI_HIP_DEQUANT_MIDPOINT : FRI_HIP_DEQUANT_REFERENCE); rc != FRI_HIP_OK) {
-        r.error = dev.describe(rc);
-        return r;
-    }
+    std::array<int32_t, 32> qm;
+    if (!(r.error = prepare_decode(plan, image.metadata.rct, image.metadata.ycbcr, image.metadata.quality, opts, dev, qm)).empty()) return r;
     r.value.metadata = image.metadata;
     r.value.metadata.quality = 0; // (the raster is what the lossy planes decode to)
     if (image.metadata.rct || image.metadata.ycbcr) // the kernel writes R, G, B
@@ -281,7 +264,7 @@ Result<std::array<std::vector<AnsContext>, 3>> encode(WaveletImage &image, Encod
     }
     params_from_flat(opts, c, vp, wp);
     if (oob[0] | oob[1] | oob[2]) { // the reference panics here: index out of bounds in bump_freq (entropy_coding.rs:99)
-        r.error = "symbol outside the 1024-entry alphabet";
+        r.error = kOutOfAlphabet;
         return r;
     }
     contexts_from_hist(hist, c, r.value);
@@ -293,76 +276,66 @@ Result<std::array<std::vector<AnsContext>, 3>> encode(WaveletImage &image, Encod
 
 Result<EncodedStages> FRIEncoder::encode(std::vector<uint8_t> data, uint32_t height, uint32_t width, ColorSpace colorspace) {
     Result<EncodedStages> r;
-    auto fail = [&](const std::string &msg) {
-        r.error = "Failed to decode: " + msg; // sic, encoder.rs:106
-        return r;
-    };
     Device dev(opts_.device);
-    if (!dev.ok()) return fail(dev.error());
+    if (!dev.ok()) return failed(r, dev.error());
     const uint32_t c = num_channels(colorspace);
-    if (data.size() != (size_t)width * height * c) return fail("raster size does not match its metadata");
+    if (data.size() != (size_t)width * height * c) return failed(r, "raster size does not match its metadata");
     std::string err;
     fri_hip_plan *plan = dev.plan(width, height, c, err);
-    if (!plan) return fail(err);
+    if (!plan) return failed(r, err);
     // RawImage -> ChannelTransform (identity, channel_transform.rs:4-10) -> WaveletTransform -> Quantization -> Prediction (encoder.rs:19-38) as
     // ONE device-resident call: the pixels go up once, the coefficients stay in device memory between the stages, every output comes down once.
     WaveletImage &w = r.value.image;
     std::array<int32_t, 32> qm;
-    if (const std::string e = coding_matrix(opts_, qm); !e.empty()) return fail(e);
+    if (const std::string e = coding_matrix(opts_, qm); !e.empty()) return failed(r, e);
     EncoderOpts coded = opts_;
     // the searches probe the planes the file will hold: YCbCr for an RGB image with the option (a fresh plan of this Device otherwise has no transform)
-    if (const std::string e = set_colour_transform(plan, false, dev, opts_.ycbcr && colorspace == ColorSpace::RGB); !e.empty()) return fail(e);
+    if (const std::string e = set_colour_transform(plan, false, dev, opts_.ycbcr && colorspace == ColorSpace::RGB); !e.empty()) return failed(r, e);
     if (opts_.target_bytes) { // the highest quality whose estimated file fits, searched on the device; 100 = lossless
         int32_t q = 0;
         uint64_t est = 0;
         const int rc = fri_hip_search_quality_for_size(plan, data.data(), opts_.target_bytes, &q, &est);
-        if (rc == FRI_HIP_ERR_OUT_OF_RANGE) return fail("no quality fits in " + std::to_string(opts_.target_bytes) + " bytes (quality 1: about " + std::to_string(est) + ")");
-        if (rc != FRI_HIP_OK) return fail(dev.describe(rc));
-        // the estimate is a few bytes per channel off the coder's output: code at q, emit, and go one quality lower while the file is over
-        constexpr int kMaxSteps = 8;
-        EncoderOpts at = opts_;
+        if (rc == FRI_HIP_ERR_OUT_OF_RANGE) return failed(r, "no quality fits in " + std::to_string(opts_.target_bytes) + " bytes (quality 1: about " + std::to_string(est) + ")");
+        if (rc != FRI_HIP_OK) return failed(r, dev.describe(rc));
+        EncoderOpts at = opts_, fitted;
         at.target_bytes = 0;
-        for (int step = 0; step <= kMaxSteps && q >= 1; step++, q--) {
-            at.quality = q < 100 ? q : 0;
+        Result<EncodedStages> st;
+        bool worded = false; // an inner encode's error comes back with the prefix, and goes out as it is
+        const std::string e = step_down_to_size(q, est, opts_.target_bytes, true, [&](int quality, uint64_t &size) {
+            at.quality = quality;
             FRIEncoder inner(at);
-            Result<EncodedStages> st = inner.encode(data, height, width, colorspace);
-            if (!st.ok) return st;
+            st = inner.encode(data, height, width, colorspace);
+            if ((worded = !st.ok)) return st.error;
             auto comp = stages::entropy_coding::encode(st.value.image, st.value.contexts, inner.opts());
-            if (!comp.ok) return fail(comp.error);
-            const uint64_t size = stages::serialize::encode(comp.value).size();
-            if (size <= opts_.target_bytes) {
-                st.value.est_bytes = est, st.value.file_bytes = size;
-                const uint64_t target = opts_.target_bytes;
-                opts_ = inner.opts(); // the fitted parameters, as a plain encode leaves them; the options stay a size target
-                opts_.quality = 0, opts_.target_bytes = target;
-                return st;
-            }
-            est = 0; // (est_bytes is the estimate of the searched quality: a stepped-down result reports 0)
-        }
-        return fail("no file of at most " + std::to_string(opts_.target_bytes) + " bytes within " + std::to_string(kMaxSteps) + " qualities below the estimate's");
+            if (!comp.ok) return comp.error;
+            st.value.file_bytes = size = stages::serialize::encode(comp.value).size();
+            fitted = inner.opts();
+            return std::string();
+        });
+        if (!e.empty()) return worded ? st : failed(r, e);
+        st.value.est_bytes = est;
+        fitted.quality = 0, fitted.target_bytes = opts_.target_bytes;
+        opts_ = fitted; // the fitted parameters, as a plain encode leaves them; the options stay a size target
+        return st;
     }
     if (opts_.target_psnr > 0) { // the lowest quality that reaches the target, searched on the device; 100 = lossless
         int32_t q = 100;
         double db = 0;
-        if (int rc = fri_hip_search_quality(plan, data.data(), opts_.target_psnr, &q, &db); rc != FRI_HIP_OK) return fail(dev.describe(rc));
-        coded.quality = q < 100 ? q : 0;
+        if (int rc = fri_hip_search_quality(plan, data.data(), opts_.target_psnr, &q, &db); rc != FRI_HIP_OK) return failed(r, dev.describe(rc));
         r.value.psnr_db = db;
-        if (q == 100 && coded.ycbcr && colorspace == ColorSpace::RGB) // YCbCr does not reach the target at any quality: a lossless file, with the RCT
-            coded.ycbcr = false, coded.colour_transform = true, r.value.lossless_rct = true;
+        fall_back_to_lossless_rct(q, coded.ycbcr && colorspace == ColorSpace::RGB, coded, r.value.lossless_rct);
         if (coded.quality) fri_hip_quality_matrix(coded.quality, qm.data());
     }
     if (opts_.target_ssim > 0) { // the same with the SSIM of the round trip (K7): the lowest quality that reaches it; 100 = lossless
         int32_t q = 100;
         double v = 0;
-        if (int rc = fri_hip_search_quality_ssim(plan, data.data(), opts_.target_ssim, &q, &v); rc != FRI_HIP_OK) return fail(dev.describe(rc));
-        coded.quality = q < 100 ? q : 0;
+        if (int rc = fri_hip_search_quality_ssim(plan, data.data(), opts_.target_ssim, &q, &v); rc != FRI_HIP_OK) return failed(r, dev.describe(rc));
         r.value.ssim = v;
-        if (q == 100 && coded.ycbcr && colorspace == ColorSpace::RGB) // YCbCr does not reach the target at any quality: a lossless file, with the RCT
-            coded.ycbcr = false, coded.colour_transform = true, r.value.lossless_rct = true;
+        fall_back_to_lossless_rct(q, coded.ycbcr && colorspace == ColorSpace::RGB, coded, r.value.lossless_rct);
         if (coded.quality) fri_hip_quality_matrix(coded.quality, qm.data());
     }
     w.metadata = coded_metadata(height, width, colorspace, coded);
-    if (const std::string e = set_colour_transform(plan, w.metadata.rct, dev, w.metadata.ycbcr); !e.empty()) return fail(e);
+    if (const std::string e = set_colour_transform(plan, w.metadata.rct, dev, w.metadata.ycbcr); !e.empty()) return failed(r, e);
     w.num_cells = fri_hip_plan_num_cells(plan);
     w.centers.resize((size_t)w.num_cells * 2);
     w.coefficients.resize(fri_hip_plan_coef_count(plan));
@@ -376,10 +349,10 @@ Result<EncodedStages> FRIEncoder::encode(std::vector<uint8_t> data, uint32_t hei
     if (rc == FRI_HIP_OK)
         rc = fri_hip_encode_image(plan, data.data(), qm.data(), opts_.fit_parameters ? 1 : 0, &vp[0][0][0], &wp[0][0][0], w.coefficients.data(),
                                   w.bucket.data(), w.prediction.data(), hist.data(), oob);
-    if (rc != FRI_HIP_OK) return fail(dev.describe(rc));
+    if (rc != FRI_HIP_OK) return failed(r, dev.describe(rc));
     w.quantized = true;
     stages::prediction::params_from_flat(opts_, c, vp, wp);
-    if (oob[0] | oob[1] | oob[2]) return fail("symbol outside the 1024-entry alphabet"); // the reference panics: bump_freq, entropy_coding.rs:99
+    if (oob[0] | oob[1] | oob[2]) return failed(r, kOutOfAlphabet); // the reference panics: bump_freq, entropy_coding.rs:99
     stages::prediction::contexts_from_hist(hist, c, r.value.contexts);
     r.ok = true;
     return r;
@@ -466,362 +439,17 @@ Result<WaveletImage> stages::entropy_coding::decode(const CompressedImage &image
     return r;
 }
 
-namespace {
-struct TiledPlanDelete {
-    void operator()(fri_hip_plan_tiled *p) const { fri_hip_plan_tiled_destroy(p); }
-};
-using TiledPlan = std::unique_ptr<fri_hip_plan_tiled, TiledPlanDelete>;
-struct Tiled420PlanDelete {
-    void operator()(fri_hip_plan_tiled420 *p) const { fri_hip_plan_tiled420_destroy(p); }
-};
-using Tiled420Plan = std::unique_ptr<fri_hip_plan_tiled420, Tiled420PlanDelete>;
-struct TiledRgbaPlanDelete {
-    void operator()(fri_hip_plan_tiled_rgba *p) const { fri_hip_plan_tiled_rgba_destroy(p); }
-};
-using TiledRgbaPlan = std::unique_ptr<fri_hip_plan_tiled_rgba, TiledRgbaPlanDelete>;
-
-// a `frit` file: the tiles' planes from the emitter's workers, then the inverse kernel over all tiles and the merge. With a region: only the tiles it touches, on
-// both sides (emit::decode_tiled with the region, fri_hip_decode_region_tiled), and the raster is the region's. With preview_shift m >= 0 (FRIDecoder::decode_preview;
-// no region): the decode stops at level L = 9 - 2 m (compact planes) and K14 writes the thumbnail of ceil(W / 2^m) x ceil(H / 2^m).
-Result<RasterImage> decode_tiled_bytes(const std::vector<uint8_t> &data, const EncoderOpts &opts, const emit::Region *region = nullptr, int preview_shift = -1) {
-    Result<RasterImage> r;
-    auto fail = [&](const std::string &why) {
-        r.error = "Failed to decode: " + why;
-        return r;
-    };
-    emit::TiledInfo ti;
-    emit::TileRange range;
-    bool too_small = false;
-    const int levels = preview_shift < 0 ? -1 : 9 - 2 * preview_shift; // (-1: whole planes, 4:2:0 among them)
-    std::string e = emit::decode_tiled(data.data(), data.size(), 0, ti, nullptr, 0, too_small, region, &range, levels); // header, table, geometry
-    if (!e.empty()) return fail(e);
-    const size_t tile_cells = ti.s420 ? (size_t)ti.n_cells + 2 * (size_t)ti.n_cells_chroma : ((size_t)ti.channels + (ti.alpha ? 1 : 0)) * ti.n_cells; // (4:2:0: plane order, F_y + 2 F_c per tile; RGBA: plane order, 4 F)
-    std::vector<int32_t> coefs((size_t)range.ni * range.nj * tile_cells * (levels < 0 ? (size_t)FRI_HIP_CELL_SIZE : (size_t)1 << levels));
-    e = emit::decode_tiled(data.data(), data.size(), 0, ti, coefs.data(), coefs.size(), too_small, region, &range, levels);
-    if (!e.empty() || too_small) return fail(e.empty() ? "coefficient array does not match the tile geometry" : e);
-    Device dev(opts.device);
-    if (!dev.ok()) return fail(dev.error());
-    if (ti.s420) { // 4:2:0 tiles: the inverse kernel on both inner plans at the file's quality, then K12's merge
-        fri_hip_plan_tiled420 *raw420 = nullptr;
-        if (const int rc = fri_hip_plan_tiled420_create(dev.ctx(), ti.width, ti.height, ti.tile_w, ti.tile_h, FRI_HIP_TILED_ALLOW_HOLES, &raw420); rc != FRI_HIP_OK) return fail(dev.describe(rc));
-        Tiled420Plan plan420(raw420);
-        if (fri_hip_plan_num_cells(fri_hip_plan_tiled420_luma(raw420)) != ti.n_cells || fri_hip_plan_num_cells(fri_hip_plan_tiled420_chroma(raw420)) != ti.n_cells_chroma)
-            return fail("coefficient array does not match the tile geometry");
-        const uint32_t out_w = region ? region->w : ti.width, out_h = region ? region->h : ti.height;
-        r.value.metadata = ImageMetadata{out_h, out_w, ColorSpace::RGB};
-        r.value.data.resize((size_t)out_w * out_h * 3);
-        const int rc = region ? fri_hip_decode_region_tiled420(raw420, coefs.data(), (int)ti.quality, region->x, region->y, region->w, region->h, r.value.data.data())
-                              : fri_hip_decode_image_tiled420(raw420, coefs.data(), (int)ti.quality, r.value.data.data());
-        if (rc != FRI_HIP_OK) return fail(dev.describe(rc));
-        r.ok = true;
-        return r;
-    }
-    if (ti.alpha) { // RGBA tiles: the inverse kernel on the colour and the alpha batch, then K16's merge (a level-limited decode was refused above)
-        fri_hip_plan_tiled_rgba *raw_rgba = nullptr;
-        if (const int rc = fri_hip_plan_tiled_rgba_create(dev.ctx(), ti.width, ti.height, ti.tile_w, ti.tile_h, FRI_HIP_TILED_ALLOW_HOLES, &raw_rgba); rc != FRI_HIP_OK) return fail(dev.describe(rc));
-        TiledRgbaPlan plan_rgba(raw_rgba);
-        fri_hip_plan *colour = fri_hip_plan_tiled_rgba_colour(raw_rgba);
-        if (fri_hip_plan_num_cells(colour) != ti.n_cells) return fail("coefficient array does not match the tile geometry");
-        if (e = set_colour_transform(colour, ti.rct, dev, ti.ycbcr); !e.empty()) return fail(e);
-        std::array<int32_t, 32> qm = opts.quantization_matrix;
-        if (ti.quality && fri_hip_quality_matrix((int)ti.quality, qm.data()) != FRI_HIP_OK) return fail("invalid quality");
-        int rc = fri_hip_plan_set_dequantiser(colour, ti.quality ? FRI_HIP_DEQUANT_MIDPOINT : FRI_HIP_DEQUANT_REFERENCE);
-        const uint32_t out_w = region ? region->w : ti.width, out_h = region ? region->h : ti.height;
-        r.value.metadata = ImageMetadata{out_h, out_w, ColorSpace::RGB};
-        r.value.metadata.alpha = true;
-        r.value.data.resize((size_t)out_w * out_h * 4);
-        if (rc == FRI_HIP_OK)
-            rc = region ? fri_hip_decode_region_tiled_rgba(raw_rgba, coefs.data(), qm.data(), region->x, region->y, region->w, region->h, r.value.data.data())
-                        : fri_hip_decode_image_tiled_rgba(raw_rgba, coefs.data(), qm.data(), r.value.data.data());
-        if (rc != FRI_HIP_OK) return fail(dev.describe(rc));
-        r.ok = true;
-        return r;
-    }
-    fri_hip_plan_tiled *raw = nullptr;
-    // (a file may hold tiles with holes: whoever wrote it asked for them)
-    if (const int rc = fri_hip_plan_tiled_create(dev.ctx(), ti.width, ti.height, ti.channels, ti.tile_w, ti.tile_h, FRI_HIP_TILED_ALLOW_HOLES, &raw); rc != FRI_HIP_OK) return fail(dev.describe(rc));
-    TiledPlan plan(raw);
-    fri_hip_plan *tile = fri_hip_plan_tiled_tile(raw);
-    if (fri_hip_plan_num_cells(tile) != ti.n_cells) return fail("coefficient array does not match the tile geometry");
-    if (e = set_colour_transform(tile, ti.rct, dev, ti.ycbcr); !e.empty()) return fail(e);
-    std::array<int32_t, 32> qm = opts.quantization_matrix;
-    if (ti.quality && fri_hip_quality_matrix((int)ti.quality, qm.data()) != FRI_HIP_OK) return fail("invalid quality");
-    int rc = fri_hip_plan_set_dequantiser(tile, ti.quality ? FRI_HIP_DEQUANT_MIDPOINT : FRI_HIP_DEQUANT_REFERENCE);
-    uint32_t out_w = region ? region->w : ti.width, out_h = region ? region->h : ti.height;
-    if (levels >= 0) {
-        uint32_t size[2];
-        if (fri_hip_preview_size(ti.width, ti.height, (uint32_t)preview_shift, size) != FRI_HIP_OK) return fail("invalid preview shift");
-        out_w = size[0], out_h = size[1];
-    }
-    r.value.metadata = ImageMetadata{out_h, out_w, ti.channels == 1 ? ColorSpace::Luma : ColorSpace::RGB};
-    r.value.data.resize((size_t)out_w * out_h * ti.channels);
-    if (rc == FRI_HIP_OK)
-        rc = levels >= 0 ? fri_hip_preview_image_tiled(raw, coefs.data(), (uint32_t)levels, (uint32_t)preview_shift, qm.data(), r.value.data.data())
-             : region    ? fri_hip_decode_region_tiled(raw, coefs.data(), qm.data(), region->x, region->y, region->w, region->h, r.value.data.data())
-                         : fri_hip_decode_image_tiled(raw, coefs.data(), qm.data(), r.value.data.data());
-    if (rc != FRI_HIP_OK) return fail(dev.describe(rc));
-    r.ok = true;
-    return r;
-}
-
-std::string set_plan_stream_order(fri_hip_plan *plan, Device &dev);
-
-// a `frit` file through the device decoder (opts.device_rans): the container walked on the host, the coded planes up - about a tenth of the int32 planes - then K13,
-// the inverse kernel over all tiles and the merge. With preview_shift m >= 0: K13 bounded by L = 9 - 2 m, then K14 (fri_hip_preview_image_tiled_coded).
-Result<RasterImage> decode_tiled_coded_bytes(const std::vector<uint8_t> &data, const EncoderOpts &opts, int preview_shift = -1) {
-    Result<RasterImage> r;
-    auto fail = [&](const std::string &why) {
-        r.error = "Failed to decode: " + why;
-        return r;
-    };
-    emit::TiledInfo ti;
-    bool too_small = false;
-    std::string e = emit::parse_tiled_coded(data.data(), data.size(), ti, 0, too_small, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr); // header, table, lattice
-    if (!e.empty()) return fail(e);
-    if (preview_shift >= 0 && ti.s420) return fail(emit::kNoLevels420);
-    const size_t planes = (size_t)ti.nx * ti.ny * ti.channels;
-    std::vector<uint32_t> n_words(planes);
-    e = emit::parse_tiled_coded(data.data(), data.size(), ti, planes, too_small, nullptr, 0, n_words.data(), nullptr, nullptr, nullptr, nullptr);
-    if (!e.empty()) return fail(e);
-    const size_t stride = std::max<uint32_t>(1, *std::max_element(n_words.begin(), n_words.end()));
-    std::vector<uint32_t> words(planes * stride), models(planes * 40), status(planes * 4);
-    std::vector<uint16_t> off(planes * 10 * 1024);
-    std::vector<float> vp(planes * 18), wp(planes * 18);
-    e = emit::parse_tiled_coded(data.data(), data.size(), ti, planes, too_small, words.data(), stride, n_words.data(), models.data(), off.data(), vp.data(), wp.data());
-    if (!e.empty()) return fail(e);
-    Device dev(opts.device);
-    if (!dev.ok()) return fail(dev.error());
-    auto refused = [&](int rc) { // the first plane the device refused, as the host decoder words it
-        for (size_t k = 0; k < planes; k++)
-            if (status[4 * k]) {
-                const uint32_t bits = status[4 * k];
-                return "plane " + std::to_string(k) + ": " + (bits & FRI_HIP_DECODE_BAD_MODEL ? "Malformed image bytes" : bits & FRI_HIP_DECODE_BAD_SLOT ? "stream does not match the model" : "stream truncated") +
-                       " (symbol " + std::to_string(status[4 * k + 1]) + ")";
-            }
-        return dev.describe(rc);
-    };
-    if (ti.s420) {
-        fri_hip_plan_tiled420 *raw420 = nullptr;
-        if (const int rc = fri_hip_plan_tiled420_create(dev.ctx(), ti.width, ti.height, ti.tile_w, ti.tile_h, FRI_HIP_TILED_ALLOW_HOLES, &raw420); rc != FRI_HIP_OK) return fail(dev.describe(rc));
-        Tiled420Plan plan420(raw420);
-        for (fri_hip_plan *inner : {fri_hip_plan_tiled420_luma(raw420), fri_hip_plan_tiled420_chroma(raw420)})
-            if (e = set_plan_stream_order(inner, dev); !e.empty()) return fail(e);
-        r.value.metadata = ImageMetadata{ti.height, ti.width, ColorSpace::RGB};
-        r.value.data.resize((size_t)ti.width * ti.height * 3);
-        const int rc = fri_hip_decode_image_tiled420_coded(raw420, words.data(), stride, n_words.data(), models.data(), off.data(), vp.data(), wp.data(), (int)ti.quality,
-                                                           r.value.data.data(), status.data());
-        if (rc != FRI_HIP_OK) return fail(refused(rc));
-        r.ok = true;
-        return r;
-    }
-    fri_hip_plan_tiled *raw = nullptr;
-    if (const int rc = fri_hip_plan_tiled_create(dev.ctx(), ti.width, ti.height, ti.channels, ti.tile_w, ti.tile_h, FRI_HIP_TILED_ALLOW_HOLES, &raw); rc != FRI_HIP_OK) return fail(dev.describe(rc));
-    TiledPlan plan(raw);
-    fri_hip_plan *tile = fri_hip_plan_tiled_tile(raw);
-    if (e = set_plan_stream_order(tile, dev); !e.empty()) return fail(e);
-    if (e = set_colour_transform(tile, ti.rct, dev, ti.ycbcr); !e.empty()) return fail(e);
-    std::array<int32_t, 32> qm = opts.quantization_matrix;
-    if (ti.quality && fri_hip_quality_matrix((int)ti.quality, qm.data()) != FRI_HIP_OK) return fail("invalid quality");
-    int rc = fri_hip_plan_set_dequantiser(tile, ti.quality ? FRI_HIP_DEQUANT_MIDPOINT : FRI_HIP_DEQUANT_REFERENCE);
-    uint32_t size[2] = {ti.width, ti.height};
-    if (preview_shift >= 0 && fri_hip_preview_size(ti.width, ti.height, (uint32_t)preview_shift, size) != FRI_HIP_OK) return fail("invalid preview shift");
-    r.value.metadata = ImageMetadata{size[1], size[0], ti.channels == 1 ? ColorSpace::Luma : ColorSpace::RGB};
-    r.value.data.resize((size_t)size[0] * size[1] * ti.channels);
-    if (rc == FRI_HIP_OK)
-        rc = preview_shift >= 0 ? fri_hip_preview_image_tiled_coded(raw, words.data(), stride, n_words.data(), models.data(), off.data(), vp.data(), wp.data(),
-                                                                    (uint32_t)(9 - 2 * preview_shift), (uint32_t)preview_shift, qm.data(), r.value.data.data(), status.data())
-                                : fri_hip_decode_image_tiled_coded(raw, words.data(), stride, n_words.data(), models.data(), off.data(), vp.data(), wp.data(), qm.data(),
-                                                                   r.value.data.data(), status.data());
-    if (rc != FRI_HIP_OK) return fail(refused(rc));
-    r.ok = true;
-    return r;
-}
-} // namespace
-
-Result<RasterImage> FRIDecoder::decode_region(const std::vector<uint8_t> &data, uint32_t x, uint32_t y, uint32_t w, uint32_t h, const EncoderOpts &opts) {
-    const emit::Region region{x, y, w, h};
-    if (opts.device_rans) {
-        Result<RasterImage> refused;
-        refused.error = "Failed to decode: region decode on the device decoder is out of scope (decode the region on the host, or the whole image on the device)";
-        return refused;
-    }
-    if (data.size() >= 4 && std::memcmp(data.data(), "frit", 4) == 0) return decode_tiled_bytes(data, opts, &region);
-    // an ordinary file has no tiles to choose from: all of it is decoded and the region cut out on the host
-    Result<RasterImage> r;
-    auto c = stages::serialize::decode(data);
-    if (!c.ok) {
-        r.error = "Failed to decode: " + c.error;
-        return r;
-    }
-    if (c.value.metadata.s420 || c.value.metadata.alpha) {
-        r.error = "Failed to decode: a region of a 4:2:0 or alpha file is not supported";
-        return r;
-    }
-    if (!w || !h || (uint64_t)x + w > c.value.metadata.width || (uint64_t)y + h > c.value.metadata.height) {
-        r.error = "Failed to decode: invalid region";
-        return r;
-    }
-    auto whole = decode(data, opts);
-    if (!whole.ok) return whole;
-    const size_t pixel = whole.value.data.size() / ((size_t)whole.value.metadata.width * whole.value.metadata.height);
-    r.value.metadata = whole.value.metadata;
-    r.value.metadata.width = w, r.value.metadata.height = h;
-    r.value.data.resize((size_t)w * h * pixel);
-    for (uint32_t ry = 0; ry < h; ry++)
-        std::memcpy(r.value.data.data() + (size_t)ry * w * pixel, whole.value.data.data() + (((size_t)y + ry) * whole.value.metadata.width + x) * pixel, (size_t)w * pixel);
-    r.ok = true;
-    return r;
-}
-
-// decode_regions (shift < 0: image coordinates, all nine levels, K15) and decode_preview_regions (shift m = 0..4: thumbnail coordinates, L = 9 - 2 m levels, K17): one
-// walk of the container, one tile list, one upload, one launch for all regions
-static Result<std::vector<RasterImage>> decode_regions_at(const std::vector<uint8_t> &data, const std::vector<emit::Region> &regions, const EncoderOpts &opts, int shift) {
-    Result<std::vector<RasterImage>> r;
-    const bool preview = shift >= 0;
-    const int levels = preview ? 9 - 2 * shift : -1;
-    auto fail = [&](const std::string &why) {
-        r.error = "Failed to decode: " + why;
-        return r;
-    };
-    if (preview && shift > 4) return fail("a preview's shift is 0..4");
-    if (data.size() >= 4 && std::memcmp(data.data(), "frif", 4) == 0)
-        return fail(preview ? "a preview reads tiled (`frit`) files only: decode an untiled file whole and scale it down"
-                            : "an ordinary `frif` file has no tiles to choose from: decode it whole, or crop one rectangle with decode_region (decode-file --region)");
-    emit::TiledInfo ti;
-    std::vector<uint64_t> offset;
-    if (std::string e = emit::parse_tiled(data.data(), data.size(), ti, offset); !e.empty()) return fail(e);
-    if (ti.s420)
-        return fail(preview ? "the preview of regions of a tiled 4:2:0 file is out of scope: decode one rectangle per call with decode_region (decode-file --region) and scale it down"
-                            : "several regions of a tiled 4:2:0 file are out of scope: decode one rectangle per call with decode_region (decode-file --region)");
-    if (ti.alpha)
-        return fail(preview ? "the preview of regions of a tiled RGBA file is out of scope: decode one rectangle per call with decode_region (decode-file --region) and scale it down"
-                            : "several regions of a tiled RGBA file are out of scope: decode one rectangle per call with decode_region (decode-file --region)");
-    if (regions.empty() || regions.size() > 65535) return fail("several regions: give 1 to 65535 regions");
-    std::vector<uint32_t> list, flat;
-    std::vector<emit::Region> source; // a preview's regions are in thumbnail coordinates: the tiles are those of their source rectangles
-    if (preview && !emit::preview_source_regions(ti.width, ti.height, (uint32_t)shift, regions.data(), regions.size(), source)) return fail("invalid region");
-    const std::vector<emit::Region> &touching = preview ? source : regions;
-    if (!emit::regions_tiles(ti.width, ti.height, ti.tile_w, ti.tile_h, touching.data(), touching.size(), list)) return fail("invalid region");
-    size_t total = 0;
-    for (const emit::Region &g : regions) flat.insert(flat.end(), {g.x, g.y, g.w, g.h}), total += (size_t)g.w * g.h * ti.channels;
-    const emit::TileList tiles{list.data(), list.size()};
-    const size_t planes = list.size() * ti.channels;
-    bool too_small = false;
-    // the host's part: the listed tiles' planes decoded on the workers, or - device_rans - their coded planes copied out
-    std::vector<int32_t> coefs;
-    std::vector<uint32_t> n_words, words, models, status;
-    std::vector<uint16_t> off;
-    std::vector<float> vp, wp;
-    size_t stride = 1;
-    if (opts.device_rans) {
-        n_words.resize(planes);
-        std::string e = emit::parse_tiled_coded(data.data(), data.size(), ti, planes, too_small, nullptr, 0, n_words.data(), nullptr, nullptr, nullptr, nullptr, &tiles);
-        if (!e.empty()) return fail(e);
-        stride = std::max<uint32_t>(1, *std::max_element(n_words.begin(), n_words.end()));
-        words.resize(planes * stride), models.resize(planes * 40), status.resize(planes * 4), off.resize(planes * 10 * 1024), vp.resize(planes * 18), wp.resize(planes * 18);
-        e = emit::parse_tiled_coded(data.data(), data.size(), ti, planes, too_small, words.data(), stride, n_words.data(), models.data(), off.data(), vp.data(), wp.data(), &tiles);
-        if (!e.empty()) return fail(e);
-    } else {
-        std::string e = emit::decode_tiled(data.data(), data.size(), 0, ti, nullptr, 0, too_small, nullptr, nullptr, levels, &tiles); // header, table, geometry
-        if (!e.empty()) return fail(e);
-        coefs.resize(planes * ((size_t)ti.n_cells << (preview ? levels : 9))); // (a preview: compact planes, 2^L nodes per cell)
-        e = emit::decode_tiled(data.data(), data.size(), 0, ti, coefs.data(), coefs.size(), too_small, nullptr, nullptr, levels, &tiles);
-        if (!e.empty() || too_small) return fail(e.empty() ? "coefficient array does not match the tile geometry" : e);
-    }
-    Device dev(opts.device);
-    if (!dev.ok()) return fail(dev.error());
-    fri_hip_plan_tiled *raw = nullptr;
-    if (const int rc = fri_hip_plan_tiled_create(dev.ctx(), ti.width, ti.height, ti.channels, ti.tile_w, ti.tile_h, FRI_HIP_TILED_ALLOW_HOLES, &raw); rc != FRI_HIP_OK) return fail(dev.describe(rc));
-    TiledPlan plan(raw);
-    fri_hip_plan *tile = fri_hip_plan_tiled_tile(raw);
-    if (fri_hip_plan_num_cells(tile) != ti.n_cells) return fail("coefficient array does not match the tile geometry");
-    if (opts.device_rans)
-        if (std::string e = set_plan_stream_order(tile, dev); !e.empty()) return fail(e);
-    if (std::string e = set_colour_transform(tile, ti.rct, dev, ti.ycbcr); !e.empty()) return fail(e);
-    std::array<int32_t, 32> qm = opts.quantization_matrix;
-    if (ti.quality && fri_hip_quality_matrix((int)ti.quality, qm.data()) != FRI_HIP_OK) return fail("invalid quality");
-    int rc = fri_hip_plan_set_dequantiser(tile, ti.quality ? FRI_HIP_DEQUANT_MIDPOINT : FRI_HIP_DEQUANT_REFERENCE);
-    std::vector<uint8_t> packed(total);
-    if (rc == FRI_HIP_OK && preview)
-        rc = opts.device_rans ? fri_hip_preview_regions_tiled_coded(raw, (uint32_t)regions.size(), flat.data(), words.data(), stride, n_words.data(), models.data(), off.data(), vp.data(),
-                                                                    wp.data(), (uint32_t)levels, (uint32_t)shift, qm.data(), packed.data(), status.data())
-                              : fri_hip_preview_regions_tiled(raw, coefs.data(), (uint32_t)levels, (uint32_t)shift, qm.data(), (uint32_t)regions.size(), flat.data(), packed.data());
-    else if (rc == FRI_HIP_OK)
-        rc = opts.device_rans ? fri_hip_decode_regions_tiled_coded(raw, (uint32_t)regions.size(), flat.data(), words.data(), stride, n_words.data(), models.data(), off.data(), vp.data(),
-                                                                   wp.data(), qm.data(), packed.data(), status.data())
-                              : fri_hip_decode_regions_tiled(raw, coefs.data(), qm.data(), (uint32_t)regions.size(), flat.data(), packed.data());
-    if (rc != FRI_HIP_OK) {
-        for (size_t k = 0; k < status.size() / 4; k++) // the first plane the device refused, as the host decoder words it: by its tile in the file's grid
-            if (status[4 * k]) {
-                const uint32_t bits = status[4 * k];
-                return fail("tile " + std::to_string(list[k / ti.channels]) + ": channel " + std::to_string(k % ti.channels) + ": " +
-                            (bits & FRI_HIP_DECODE_BAD_MODEL ? "Malformed image bytes" : bits & FRI_HIP_DECODE_BAD_SLOT ? "stream does not match the model" : "stream truncated") +
-                            " (symbol " + std::to_string(status[4 * k + 1]) + ")");
-            }
-        return fail(dev.describe(rc));
-    }
-    size_t at = 0;
-    for (const emit::Region &g : regions) {
-        RasterImage img;
-        img.metadata = ImageMetadata{g.h, g.w, ti.channels == 1 ? ColorSpace::Luma : ColorSpace::RGB};
-        const size_t bytes = (size_t)g.w * g.h * ti.channels;
-        img.data.assign(packed.begin() + at, packed.begin() + at + bytes);
-        at += bytes;
-        r.value.push_back(std::move(img));
-    }
-    r.ok = true;
-    return r;
-}
-
-Result<std::vector<RasterImage>> FRIDecoder::decode_regions(const std::vector<uint8_t> &data, const std::vector<emit::Region> &regions, const EncoderOpts &opts) {
-    return decode_regions_at(data, regions, opts, -1);
-}
-
-Result<std::vector<RasterImage>> FRIDecoder::decode_preview_regions(const std::vector<uint8_t> &data, uint32_t shift, const std::vector<emit::Region> &regions,
-                                                                    const EncoderOpts &opts) {
-    return decode_regions_at(data, regions, opts, (int)std::min<uint32_t>(shift, 5)); // (5: refused like every shift above 4)
-}
-
-Result<RasterImage> FRIDecoder::decode_preview(const std::vector<uint8_t> &data, uint32_t shift, const EncoderOpts &opts) {
-    Result<RasterImage> r;
-    if (shift > 4) {
-        r.error = "Failed to decode: a preview's shift is 0..4";
-        return r;
-    }
-    if (data.size() >= 4 && std::memcmp(data.data(), "frit", 4) == 0)
-        return opts.device_rans ? decode_tiled_coded_bytes(data, opts, (int)shift) : decode_tiled_bytes(data, opts, nullptr, (int)shift);
-    r.error = "Failed to decode: a preview reads tiled (`frit`) files only: decode an untiled file whole and scale it down";
-    return r;
-}
-
 Result<RasterImage> FRIDecoder::decode(const std::vector<uint8_t> &data, const EncoderOpts &opts) {
     if (data.size() >= 4 && std::memcmp(data.data(), "frit", 4) == 0) return opts.device_rans ? decode_tiled_coded_bytes(data, opts) : decode_tiled_bytes(data, opts);
     Result<RasterImage> r;
-    if (opts.device_rans) {
-        r.error = "Failed to decode: the device decoder reads tiled (`frit`) files only: an untiled file is one dependent chain per channel, which the host decodes faster";
-        return r;
-    }
+    if (opts.device_rans) return failed(r, "the device decoder reads tiled (`frit`) files only: an untiled file is one dependent chain per channel, which the host decodes faster");
     auto c = stages::serialize::decode(data);
-    if (!c.ok) {
-        r.error = "Failed to decode: " + c.error; // decoder.rs:56
-        return r;
-    }
+    if (!c.ok) return failed(r, c.error); // decoder.rs:56
     auto w = stages::entropy_coding::decode(c.value);
-    if (!w.ok) {
-        r.error = "Failed to decode: " + w.error;
-        return r;
-    }
+    if (!w.ok) return failed(r, w.error);
     return decode(w.value, opts); // quantization::decode + wavelet_transform::decode: one kernel (fri_hip_inverse_transform)
 }
 
-namespace {
-// what the device hands the emitter for one image
-struct StreamedImage {
-    size_t index = 0;
-    std::vector<uint16_t> symbols; // [C][num_some]
-    std::vector<uint32_t> hist;    // [C][10][1024]
-    float vp[3][3][6], wp[3][3][6];
-};
 std::string set_plan_stream_order(fri_hip_plan *plan, Device &dev) {
     const uint32_t F = fri_hip_plan_num_cells(plan);
     std::vector<int32_t> centers((size_t)F * 2);
@@ -833,14 +461,20 @@ std::string set_plan_stream_order(fri_hip_plan *plan, Device &dev) {
     rc = fri_hip_plan_set_stream_order(plan, order.data(), order.size());
     return rc == FRI_HIP_OK ? std::string() : dev.describe(rc);
 }
+
+namespace {
+// what the device hands the emitter for one image
+struct StreamedImage {
+    size_t index = 0;
+    std::vector<uint16_t> symbols; // [C][num_some]
+    std::vector<uint32_t> hist;    // [C][10][1024]
+    float vp[3][3][6], wp[3][3][6];
+};
 std::string emit_streamed(const StreamedImage &im, uint32_t c, uint64_t n, const ImageMetadata &md, std::vector<uint8_t> &out) {
     std::vector<emit::ChannelStream> streams;
     const std::string e = emit::encode_channels_from_streams(c, im.symbols.data(), (size_t)n, im.hist.data(), streams);
     if (!e.empty()) return e;
-    std::vector<emit::ChannelParams> params(c);
-    for (uint32_t ch = 0; ch < c; ch++)
-        for (int g = 0; g < 3; g++)
-            for (int k = 0; k < 6; k++) params[ch].value[g][k] = im.vp[ch][g][k], params[ch].width[g][k] = im.wp[ch][g][k];
+    const std::vector<emit::ChannelParams> params = channel_params(&im.vp[0][0][0], &im.wp[0][0][0], c);
     out = emit::serialize(md.height, md.width, colour_code(md.colorspace), streams, params, md.rct, md.quality, md.ycbcr);
     return std::string();
 }
@@ -881,29 +515,25 @@ fri_hip_plan420 *Device::plan420(uint32_t width, uint32_t height, std::string &e
 
 Result<Encoded420> encode_bytes_420(const std::vector<uint8_t> &rgb, uint32_t height, uint32_t width, const EncoderOpts &opts) {
     Result<Encoded420> r;
-    auto fail = [&](const std::string &why) {
-        r.error = "Failed to decode: " + why; // sic, encoder.rs:106
-        return r;
-    };
     const int targets = (opts.quality != 0) + (opts.target_psnr > 0) + (opts.target_ssim > 0) + (opts.target_bytes != 0);
     if (targets != 1 || opts.colour_transform || opts.quality < 0 || opts.quality > 99 || !(opts.target_psnr >= 0) || !(opts.target_ssim >= 0 && opts.target_ssim <= 1))
-        return fail("4:2:0 coding needs exactly one of quality (1..99), target_psnr, target_ssim and target_bytes, and no colour_transform");
-    if (rgb.size() != (size_t)width * height * 3) return fail("4:2:0 coding takes width x height RGB pixels");
+        return failed(r, "4:2:0 coding needs exactly one of quality (1..99), target_psnr, target_ssim and target_bytes, and no colour_transform");
+    if (rgb.size() != (size_t)width * height * 3) return failed(r, "4:2:0 coding takes width x height RGB pixels");
     Device dev(opts.device);
     std::string err;
     fri_hip_plan420 *sub = dev.ok() ? dev.plan420(width, height, err) : nullptr;
-    if (!sub) return fail(dev.ok() ? err : dev.error());
+    if (!sub) return failed(r, dev.ok() ? err : dev.error());
     int32_t q = opts.quality;
     int rc = FRI_HIP_OK;
     if (opts.target_psnr > 0) rc = fri_hip_search_quality420(sub, rgb.data(), opts.target_psnr, &q, &r.value.psnr_db);
     if (opts.target_ssim > 0) rc = fri_hip_search_quality_ssim420(sub, rgb.data(), opts.target_ssim, &q, &r.value.ssim);
     if (opts.target_bytes) rc = fri_hip_search_quality_for_size420(sub, rgb.data(), opts.target_bytes, &q, &r.value.est_bytes);
-    if (rc != FRI_HIP_OK) return fail(rc == FRI_HIP_ERR_OUT_OF_RANGE ? "no quality fits in target_bytes" : dev.describe(rc));
+    if (rc != FRI_HIP_OK) return failed(r, rc == FRI_HIP_ERR_OUT_OF_RANGE ? "no quality fits in target_bytes" : dev.describe(rc));
     if (q == 100) { // no quality 1..99 reaches the target: code losslessly, with the RCT
         EncoderOpts lossless = opts;
         lossless.quality = 0, lossless.target_psnr = 0, lossless.target_ssim = 0, lossless.ycbcr = false, lossless.colour_transform = true;
         auto out = FRIEncoder(lossless).encode_bytes_streamed(rgb, height, width, ColorSpace::RGB);
-        if (!out.ok) return fail(out.error);
+        if (!out.ok) return failed(r, out.error);
         r.value.bytes = std::move(out.value), r.value.lossless_rct = true, r.ok = true;
         return r;
     }
@@ -914,19 +544,16 @@ Result<Encoded420> encode_bytes_420(const std::vector<uint8_t> &rgb, uint32_t he
         im.hist.resize(3 * 10 * 1024);
         uint64_t oob[3] = {0, 0, 0};
         rc = fri_hip_encode_image420_symbols(sub, rgb.data(), q, &im.vp[0][0][0], &im.wp[0][0][0], im.symbols.data(), im.hist.data(), oob);
-        if (rc != FRI_HIP_OK) return fail(dev.describe(rc));
-        if (oob[0] || oob[1] || oob[2]) return fail("symbol outside the alphabet (libfri panics, entropy_coding.rs:99)");
+        if (rc != FRI_HIP_OK) return failed(r, dev.describe(rc));
+        if (oob[0] || oob[1] || oob[2]) return failed(r, "symbol outside the alphabet (libfri panics, entropy_coding.rs:99)");
         std::vector<emit::ChannelStream> streams;
         const std::string e = emit::encode_channels_from_streams(3, im.symbols.data(), (size_t)n_y, im.hist.data(), streams, (size_t)n_c);
-        if (!e.empty()) return fail(e);
-        std::vector<emit::ChannelParams> params(3);
-        for (uint32_t ch = 0; ch < 3; ch++)
-            for (int g = 0; g < 3; g++)
-                for (int k = 0; k < 6; k++) params[ch].value[g][k] = im.vp[ch][g][k], params[ch].width[g][k] = im.wp[ch][g][k];
+        if (!e.empty()) return failed(r, e);
+        const std::vector<emit::ChannelParams> params = channel_params(&im.vp[0][0][0], &im.wp[0][0][0], 3);
         r.value.bytes = emit::serialize(height, width, emit::kYCbCr, streams, params, false, (uint32_t)q, true, true);
         if (!opts.target_bytes || r.value.bytes.size() <= opts.target_bytes) break;
         r.value.est_bytes = 0;
-        if (q == 1) return fail("the file of quality 1 is over target_bytes");
+        if (q == 1) return failed(r, "the file of quality 1 is over target_bytes");
     }
     r.value.quality = q;
     r.ok = true;
@@ -1015,56 +642,47 @@ struct DeviceBytes {
 
 Result<EncodedRGBA> encode_bytes_rgba(const std::vector<uint8_t> &rgba, uint32_t height, uint32_t width, const EncoderOpts &opts, bool clean_alpha) {
     Result<EncodedRGBA> r;
-    auto fail = [&](const std::string &why) {
-        r.error = "Failed to decode: " + why; // sic, encoder.rs:106
-        return r;
-    };
     std::array<int32_t, 32> qm;
-    if (const std::string e = coding_matrix(opts, qm); !e.empty()) return fail(e);
-    if (opts.target_bytes) return fail("target_bytes is not supported with an alpha plane: there is no size search with alpha (pass a quality, target_psnr or target_ssim)");
+    if (const std::string e = coding_matrix(opts, qm); !e.empty()) return failed(r, e);
+    if (opts.target_bytes) return failed(r, "target_bytes is not supported with an alpha plane: there is no size search with alpha (pass a quality, target_psnr or target_ssim)");
     const size_t n_pixels = (size_t)width * height;
-    if (!n_pixels || rgba.size() != n_pixels * 4) return fail("RGBA coding takes width x height R, G, B, A pixels");
+    if (!n_pixels || rgba.size() != n_pixels * 4) return failed(r, "RGBA coding takes width x height R, G, B, A pixels");
     Device dev(opts.device);
     std::string err;
     fri_hip_plan_rgba *both = dev.ok() ? dev.plan_rgba(width, height, err) : nullptr;
-    if (!both) return fail(dev.ok() ? err : dev.error());
+    if (!both) return failed(r, dev.ok() ? err : dev.error());
     fri_hip_plan *colour = fri_hip_plan_rgba_colour(both);
     const int clean = clean_alpha ? FRI_HIP_ALPHA_CLEAN : FRI_HIP_ALPHA_KEEP;
     EncoderOpts coded = opts;
     if (opts.target_psnr > 0 || opts.target_ssim > 0) { // the lowest quality at which the colour reaches the target: split once, search on the inner colour plan
-        if (const std::string e = set_colour_transform(colour, false, dev, opts.ycbcr); !e.empty()) return fail(e);
+        if (const std::string e = set_colour_transform(colour, false, dev, opts.ycbcr); !e.empty()) return failed(r, e);
         DeviceBytes buf; // R, G, B, A [4 N], then R, G, B [3 N], then A [N]
-        if (hipSetDevice(opts.device) != hipSuccess || hipMalloc((void **)&buf.p, 8 * n_pixels) != hipSuccess) return fail("no device memory for the search");
-        if (hipMemcpy(buf.p, rgba.data(), 4 * n_pixels, hipMemcpyHostToDevice) != hipSuccess) return fail("staging the pixels failed");
+        if (hipSetDevice(opts.device) != hipSuccess || hipMalloc((void **)&buf.p, 8 * n_pixels) != hipSuccess) return failed(r, "no device memory for the search");
+        if (hipMemcpy(buf.p, rgba.data(), 4 * n_pixels, hipMemcpyHostToDevice) != hipSuccess) return failed(r, "staging the pixels failed");
         int rc = fri_hip_split_rgba_dev(both, buf.p, clean, buf.p + 4 * n_pixels, buf.p + 7 * n_pixels, nullptr);
         int32_t q = 100;
         if (rc == FRI_HIP_OK && opts.target_psnr > 0) rc = fri_hip_search_quality_dev(colour, buf.p + 4 * n_pixels, opts.target_psnr, &q, &r.value.psnr_db, nullptr);
         if (rc == FRI_HIP_OK && opts.target_ssim > 0) rc = fri_hip_search_quality_ssim_dev(colour, buf.p + 4 * n_pixels, opts.target_ssim, &q, &r.value.ssim, nullptr);
-        if (rc != FRI_HIP_OK) return fail(dev.describe(rc));
+        if (rc != FRI_HIP_OK) return failed(r, dev.describe(rc));
         coded.target_psnr = 0, coded.target_ssim = 0;
-        coded.quality = q < 100 ? q : 0;
-        if (q == 100 && coded.ycbcr) // YCbCr does not reach the target at any quality: a lossless file, with the RCT
-            coded.ycbcr = false, coded.colour_transform = true, r.value.lossless_rct = true;
+        fall_back_to_lossless_rct(q, coded.ycbcr, coded, r.value.lossless_rct);
         if (coded.quality) fri_hip_quality_matrix(coded.quality, qm.data());
     }
     ImageMetadata md = coded_metadata(height, width, ColorSpace::RGB, coded);
     md.alpha = true;
-    if (const std::string e = set_colour_transform(colour, md.rct, dev, md.ycbcr); !e.empty()) return fail(e);
+    if (const std::string e = set_colour_transform(colour, md.rct, dev, md.ycbcr); !e.empty()) return failed(r, e);
     const uint64_t n = fri_hip_plan_num_some(colour);
     std::vector<uint16_t> symbols(4 * (size_t)n);
     std::vector<uint32_t> hist(4 * (size_t)CONTEXT_AMOUNT * ALPHABET_SIZE);
     float vp[4][3][6], wp[4][3][6];
     uint64_t oob[4] = {0, 0, 0, 0};
     const int rc = fri_hip_encode_image_rgba_symbols(both, rgba.data(), clean, qm.data(), &vp[0][0][0], &wp[0][0][0], symbols.data(), hist.data(), oob);
-    if (rc != FRI_HIP_OK) return fail(dev.describe(rc));
-    if (oob[0] | oob[1] | oob[2] | oob[3]) return fail("symbol outside the 1024-entry alphabet"); // the reference panics: bump_freq, entropy_coding.rs:99
+    if (rc != FRI_HIP_OK) return failed(r, dev.describe(rc));
+    if (oob[0] | oob[1] | oob[2] | oob[3]) return failed(r, kOutOfAlphabet); // the reference panics: bump_freq, entropy_coding.rs:99
     std::vector<emit::ChannelStream> streams;
     const std::string e = emit::encode_channels_from_streams(4, symbols.data(), (size_t)n, hist.data(), streams);
-    if (!e.empty()) return fail(e);
-    std::vector<emit::ChannelParams> params(4);
-    for (uint32_t ch = 0; ch < 4; ch++)
-        for (int g = 0; g < 3; g++)
-            for (int k = 0; k < 6; k++) params[ch].value[g][k] = vp[ch][g][k], params[ch].width[g][k] = wp[ch][g][k];
+    if (!e.empty()) return failed(r, e);
+    const std::vector<emit::ChannelParams> params = channel_params(&vp[0][0][0], &wp[0][0][0], 4);
     r.value.bytes = emit::serialize(height, width, colour_code(md.colorspace), streams, params, md.rct, md.quality, md.ycbcr, false, true);
     r.value.quality = (int)md.quality, r.value.rct = md.rct, r.value.ycbcr = md.ycbcr;
     r.ok = true;
@@ -1099,7 +717,7 @@ Result<RasterImage> round_trip_rgba(const std::vector<uint8_t> &rgba, uint32_t h
     std::vector<int32_t> coefs(4 * plane);
     int rc = fri_hip_transform_quant(colour, rgb.data(), qm, coefs.data());
     if (rc == FRI_HIP_OK) rc = fri_hip_transform_quant(alpha, a.data(), ones, coefs.data() + 3 * plane);
-    if (rc == FRI_HIP_OK) rc = fri_hip_plan_set_dequantiser(colour, quality ? FRI_HIP_DEQUANT_MIDPOINT : FRI_HIP_DEQUANT_REFERENCE);
+    if (rc == FRI_HIP_OK) rc = fri_hip_plan_set_dequantiser(colour, dequantiser_of((uint32_t)quality));
     r.value.metadata = ImageMetadata{height, width, ColorSpace::RGB};
     r.value.metadata.alpha = true;
     r.value.data.resize(rgba.size());
@@ -1114,26 +732,22 @@ Result<RasterImage> round_trip_rgba(const std::vector<uint8_t> &rgba, uint32_t h
 // the .frv of encode_bytes below (tests/test_emit.py); 34 MB instead of 153 MB come down per 4096 x 4096 plane.
 Result<std::vector<uint8_t>> FRIEncoder::encode_bytes_streamed(std::vector<uint8_t> data, uint32_t height, uint32_t width, ColorSpace colorspace) {
     Result<std::vector<uint8_t>> r;
-    auto fail = [&](const std::string &msg) {
-        r.error = "Failed to decode: " + msg; // sic, encoder.rs:106
-        return r;
-    };
     Device dev(opts_.device);
-    if (!dev.ok()) return fail(dev.error());
+    if (!dev.ok()) return failed(r, dev.error());
     const uint32_t c = num_channels(colorspace);
-    if (data.size() != (size_t)width * height * c) return fail("raster size does not match its metadata");
+    if (data.size() != (size_t)width * height * c) return failed(r, "raster size does not match its metadata");
     std::string err;
     fri_hip_plan *plan = dev.plan(width, height, c, err);
-    if (!plan) return fail(err);
+    if (!plan) return failed(r, err);
     const ImageMetadata md = coded_metadata(height, width, colorspace, opts_);
     std::array<int32_t, 32> qm;
-    if (const std::string e = coding_matrix(opts_, qm); !e.empty()) return fail(e);
-    if (opts_.target_psnr > 0) return fail("target_psnr: FRIEncoder::encode only (search first, then pass the quality)");
-    if (opts_.target_bytes) return fail("target_bytes: FRIEncoder::encode only (search first, then pass the quality)");
-    if (opts_.target_ssim > 0) return fail("target_ssim: FRIEncoder::encode only (search first, then pass the quality)");
-    if (const std::string e = set_colour_transform(plan, md.rct, dev, md.ycbcr); !e.empty()) return fail(e);
+    if (const std::string e = coding_matrix(opts_, qm); !e.empty()) return failed(r, e);
+    if (opts_.target_psnr > 0) return failed(r, "target_psnr: FRIEncoder::encode only (search first, then pass the quality)");
+    if (opts_.target_bytes) return failed(r, "target_bytes: FRIEncoder::encode only (search first, then pass the quality)");
+    if (opts_.target_ssim > 0) return failed(r, "target_ssim: FRIEncoder::encode only (search first, then pass the quality)");
+    if (const std::string e = set_colour_transform(plan, md.rct, dev, md.ycbcr); !e.empty()) return failed(r, e);
     const uint64_t n = fri_hip_plan_num_some(plan);
-    if (const std::string e = set_plan_stream_order(plan, dev); !e.empty()) return fail(e); // geometry only, once per plan (the plan is new here: Device lives for this call, as in encode())
+    if (const std::string e = set_plan_stream_order(plan, dev); !e.empty()) return failed(r, e); // geometry only, once per plan (the plan is new here: Device lives for this call, as in encode())
     std::vector<uint16_t> symbols((size_t)c * n);
     std::vector<uint32_t> hist((size_t)c * CONTEXT_AMOUNT * ALPHABET_SIZE);
     float vp[3][3][6], wp[3][3][6];
@@ -1141,16 +755,13 @@ Result<std::vector<uint8_t>> FRIEncoder::encode_bytes_streamed(std::vector<uint8
     uint64_t oob[3] = {0, 0, 0};
     const int rc = fri_hip_encode_image_symbols(plan, data.data(), qm.data(), opts_.fit_parameters ? 1 : 0, &vp[0][0][0], &wp[0][0][0], symbols.data(),
                                                 hist.data(), oob);
-    if (rc != FRI_HIP_OK) return fail(dev.describe(rc));
+    if (rc != FRI_HIP_OK) return failed(r, dev.describe(rc));
     stages::prediction::params_from_flat(opts_, c, vp, wp);
-    if (oob[0] | oob[1] | oob[2]) return fail("symbol outside the 1024-entry alphabet"); // the reference panics: bump_freq, entropy_coding.rs:99
+    if (oob[0] | oob[1] | oob[2]) return failed(r, kOutOfAlphabet); // the reference panics: bump_freq, entropy_coding.rs:99
     std::vector<emit::ChannelStream> streams;
     const std::string e = emit::encode_channels_from_streams(c, symbols.data(), (size_t)n, hist.data(), streams);
-    if (!e.empty()) return fail(e);
-    std::vector<emit::ChannelParams> params(c);
-    for (uint32_t ch = 0; ch < c; ch++)
-        for (int g = 0; g < 3; g++)
-            for (int k = 0; k < 6; k++) params[ch].value[g][k] = vp[ch][g][k], params[ch].width[g][k] = wp[ch][g][k];
+    if (!e.empty()) return failed(r, e);
+    const std::vector<emit::ChannelParams> params = channel_params(&vp[0][0][0], &wp[0][0][0], c);
     r.value = emit::serialize(height, width, colour_code(md.colorspace), streams, params, md.rct, md.quality, md.ycbcr);
     r.ok = true;
     return r;
@@ -1246,7 +857,7 @@ Result<std::vector<std::vector<uint8_t>>> encode_batch_bytes(const std::vector<c
                     break;
                 }
                 if (oob[0] | oob[1] | oob[2]) {
-                    fail("symbol outside the 1024-entry alphabet"); // the reference panics: bump_freq, entropy_coding.rs:99
+                    fail(kOutOfAlphabet); // the reference panics: bump_freq, entropy_coding.rs:99
                     break;
                 }
                 std::unique_lock<std::mutex> lk(mu);
@@ -1304,10 +915,7 @@ Result<std::vector<uint8_t>> FRIEncoder::encode_bytes(std::vector<uint8_t> data,
         return r;
     }
     auto c = stages::entropy_coding::encode(st.value.image, st.value.contexts, opts_);
-    if (!c.ok) {
-        r.error = "Failed to decode: " + c.error; // sic, encoder.rs:106
-        return r;
-    }
+    if (!c.ok) return failed(r, c.error);
     r.value = stages::serialize::encode(c.value);
     r.ok = true;
     return r;
@@ -1316,428 +924,9 @@ Result<std::vector<uint8_t>> FRIEncoder::encode_bytes(std::vector<uint8_t> data,
 Result<RasterImage> FRIDecoder::decode(const WaveletImage &image, const EncoderOpts &opts) {
     Device dev(opts.device);
     Result<RasterImage> r;
-    if (!dev.ok()) {
-        r.error = "Failed to decode: " + dev.error();
-        return r;
-    }
+    if (!dev.ok()) return failed(r, dev.error());
     r = stages::wavelet_transform::decode(image, opts, dev);
     if (!r.ok) r.error = "Failed to decode: " + r.error;
-    return r;
-}
-
-// ---- tiled coding ----------------------------------------------------------------------------------------------------------------------------------
-Result<EncodedTiled> encode_bytes_tiled(const std::vector<uint8_t> &pixels, uint32_t height, uint32_t width, ColorSpace colorspace, const EncoderOpts &opts, uint32_t tile_size,
-                                        unsigned threads) {
-    Result<EncodedTiled> r;
-    auto fail = [&](const std::string &why) {
-        r.error = "Failed to decode: " + why; // sic, encoder.rs:106
-        return r;
-    };
-    std::array<int32_t, 32> qm;
-    if (const std::string e = coding_matrix(opts, qm); !e.empty()) return fail(e);
-    const uint32_t c = num_channels(colorspace);
-    if (!width || !height || pixels.size() != (size_t)width * height * c) return fail("raster size does not match its metadata");
-    uint32_t tw = 0, th = 0;
-    if (const int rc = fri_hip_tile_shape(width, height, tile_size, &tw, &th); rc != FRI_HIP_OK) return fail(std::string("no tile shape of that size owns every pixel: ") + fri_hip_strerror(rc));
-    Device dev(opts.device);
-    if (!dev.ok()) return fail(dev.error());
-    fri_hip_plan_tiled *raw = nullptr;
-    if (const int rc = fri_hip_plan_tiled_create(dev.ctx(), width, height, c, tw, th, 0, &raw); rc != FRI_HIP_OK) return fail(dev.describe(rc));
-    TiledPlan plan(raw);
-    fri_hip_plan *tile = fri_hip_plan_tiled_tile(raw);
-    if (const std::string e = set_plan_stream_order(tile, dev); !e.empty()) return fail(e);
-    uint32_t grid[4];
-    fri_hip_plan_tiled_grid(raw, grid);
-    r.value.tile_w = tw, r.value.tile_h = th, r.value.nx = grid[0], r.value.ny = grid[1];
-    const size_t planes = (size_t)grid[0] * grid[1] * c;
-    const uint64_t n = fri_hip_plan_num_some(tile);
-    std::vector<uint16_t> symbols(opts.device_rans ? 0 : planes * (size_t)n); // (the device coder's route reads neither streams nor histograms back)
-    std::vector<uint32_t> hist(opts.device_rans ? 0 : planes * CONTEXT_AMOUNT * ALPHABET_SIZE);
-    std::vector<float> vp(planes * 18), wp(planes * 18);
-    std::vector<uint64_t> oob(planes, 0);
-    // the device batch and the emitter for what `coded` says (a quality or lossless, no targets): "" or the error; the file in r.value.bytes
-    auto code = [&](const EncoderOpts &coded) -> std::string {
-        if (const std::string e = coding_matrix(coded, qm); !e.empty()) return e;
-        const ImageMetadata md = coded_metadata(th, tw, colorspace, coded);
-        if (const std::string e = set_colour_transform(tile, md.rct, dev, md.ycbcr); !e.empty()) return e;
-        r.value.bytes.clear();
-        if (opts.device_rans) { // K11: the planes come back coded, the host writes the container around them
-            const size_t stride = (size_t)n + 20; // a step emits at most one word
-            std::vector<uint32_t> words(planes * stride), n_words(planes), models(planes * CONTEXT_AMOUNT * 4), status(planes * 4);
-            std::vector<uint16_t> off(planes * CONTEXT_AMOUNT * ALPHABET_SIZE);
-            if (const int rc = fri_hip_encode_image_tiled_coded(raw, pixels.data(), qm.data(), vp.data(), wp.data(), words.data(), stride, n_words.data(), models.data(), off.data(),
-                                                                status.data());
-                rc != FRI_HIP_OK) {
-                for (size_t k = 0; k < planes; k++)
-                    if (status[4 * k]) return "tile " + std::to_string(k / c) + ": channel " + std::to_string(k % c) + ": the device coder refuses the plane (status " + std::to_string(status[4 * k]) + ")";
-                return dev.describe(rc);
-            }
-            const std::string e = emit::encode_tiled_from_coded(width, height, tw, th, c, md.rct, md.quality, md.ycbcr, words.data(), stride, n_words.data(), models.data(), off.data(),
-                                                                vp.data(), wp.data(), threads, r.value.bytes);
-            if (!e.empty()) return e;
-            r.value.quality = (int)md.quality, r.value.rct = md.rct, r.value.ycbcr = md.ycbcr;
-            return std::string();
-        }
-        if (const int rc = fri_hip_encode_image_tiled_symbols(raw, pixels.data(), qm.data(), vp.data(), wp.data(), symbols.data(), hist.data(), oob.data()); rc != FRI_HIP_OK)
-            return dev.describe(rc);
-        for (uint64_t v : oob)
-            if (v) return "symbol outside the 1024-entry alphabet"; // the reference panics: bump_freq, entropy_coding.rs:99
-        const std::string e = emit::encode_tiled_from_streams(width, height, tw, th, c, md.rct, md.quality, md.ycbcr, symbols.data(), (size_t)n, hist.data(), vp.data(), wp.data(), threads,
-                                                              r.value.bytes);
-        if (!e.empty()) return e;
-        r.value.quality = (int)md.quality, r.value.rct = md.rct, r.value.ycbcr = md.ycbcr;
-        return std::string();
-    };
-    EncoderOpts coded = opts;
-    coded.target_psnr = 0, coded.target_ssim = 0, coded.target_bytes = 0;
-    const bool ycc = opts.ycbcr && colorspace == ColorSpace::RGB;
-    if (opts.target_psnr > 0 || opts.target_ssim > 0 || opts.target_bytes) {
-        // the searches run on the tiled plan and probe the planes the file will hold: what they return holds for the file that is written
-        if (const std::string e = set_colour_transform(tile, false, dev, ycc); !e.empty()) return fail(e);
-    }
-    if (opts.target_bytes) { // the highest quality whose estimated file fits; 100 = lossless
-        int32_t q = 0;
-        uint64_t est = 0;
-        const int rc = fri_hip_search_quality_for_size_tiled(raw, pixels.data(), opts.target_bytes, &q, &est);
-        if (rc == FRI_HIP_ERR_OUT_OF_RANGE) return fail("no quality fits in " + std::to_string(opts.target_bytes) + " bytes (quality 1: about " + std::to_string(est) + ")");
-        if (rc != FRI_HIP_OK) return fail(dev.describe(rc));
-        r.value.search_quality = q;
-        // the estimate is a few bytes per channel and tile off the coder's output: code at q, emit, and go one quality lower while the file is over
-        constexpr int kMaxSteps = 8;
-        for (int step = 0; step <= kMaxSteps && q >= 1; step++, q--) {
-            coded.quality = q < 100 ? q : 0;
-            if (const std::string e = code(coded); !e.empty()) return fail(e);
-            if (r.value.bytes.size() <= opts.target_bytes) {
-                r.value.est_bytes = est;
-                r.ok = true;
-                return r;
-            }
-            est = 0; // (est_bytes is the estimate of the searched quality: a stepped-down result reports 0)
-        }
-        r.value.bytes.clear();
-        return fail("no file of at most " + std::to_string(opts.target_bytes) + " bytes within " + std::to_string(kMaxSteps) + " qualities below the estimate's");
-    }
-    if (opts.target_psnr > 0 || opts.target_ssim > 0) { // the lowest quality that reaches the target; 100 = lossless
-        int32_t q = 100;
-        int rc;
-        if (opts.target_psnr > 0) rc = fri_hip_search_quality_tiled(raw, pixels.data(), opts.target_psnr, &q, &r.value.psnr_db);
-        else rc = fri_hip_search_quality_ssim_tiled(raw, pixels.data(), opts.target_ssim, &q, &r.value.ssim);
-        if (rc != FRI_HIP_OK) return fail(dev.describe(rc));
-        r.value.search_quality = q;
-        coded.quality = q < 100 ? q : 0;
-        if (q == 100 && ycc) // YCbCr does not reach the target at any quality: a lossless file, with the RCT
-            coded.ycbcr = false, coded.colour_transform = true, r.value.lossless_rct = true;
-    }
-    if (const std::string e = code(coded); !e.empty()) return fail(e);
-    r.ok = true;
-    return r;
-}
-
-Result<RasterImage> round_trip_tiled(const std::vector<uint8_t> &pixels, uint32_t height, uint32_t width, uint32_t channels, uint32_t tile_w, uint32_t tile_h, int quality, bool rct,
-                                     bool ycbcr, int device) {
-    Result<RasterImage> r;
-    int32_t qm[32];
-    if (!width || !height || !tile_w || !tile_h || (channels != 1 && channels != 3) || pixels.size() != (size_t)width * height * channels || quality < 0 || quality > 99 ||
-        (rct && (ycbcr || quality)) || (ycbcr && !quality) || fri_hip_quality_matrix(quality ? quality : 100, qm) != FRI_HIP_OK) {
-        r.error = "invalid argument";
-        return r;
-    }
-    Device dev(device);
-    if (!dev.ok()) {
-        r.error = dev.error();
-        return r;
-    }
-    fri_hip_plan_tiled *raw = nullptr;
-    int rc = fri_hip_plan_tiled_create(dev.ctx(), width, height, channels, tile_w, tile_h, FRI_HIP_TILED_ALLOW_HOLES, &raw);
-    if (rc != FRI_HIP_OK) {
-        r.error = dev.describe(rc);
-        return r;
-    }
-    TiledPlan plan(raw);
-    fri_hip_plan *tile = fri_hip_plan_tiled_tile(raw);
-    if (!(r.error = set_colour_transform(tile, rct, dev, ycbcr)).empty()) return r;
-    uint32_t grid[4];
-    fri_hip_plan_tiled_grid(raw, grid);
-    const size_t image = fri_hip_plan_coef_count(tile), n_tiles = (size_t)grid[0] * grid[1];
-    std::vector<int32_t> coefs(n_tiles * image);
-    std::vector<uint8_t> one((size_t)tile_w * tile_h * channels);
-    for (size_t t = 0; t < n_tiles && rc == FRI_HIP_OK; t++) { // the format's split with edge replication on the host (include/fri_hip.h)
-        const size_t j = t / grid[0], i = t % grid[0];
-        for (uint32_t y = 0; y < tile_h; y++) {
-            const size_t sy = std::min<size_t>(j * tile_h + y, height - 1);
-            for (uint32_t x = 0; x < tile_w; x++) {
-                const size_t sx = std::min<size_t>(i * tile_w + x, width - 1);
-                for (uint32_t k = 0; k < channels; k++) one[((size_t)y * tile_w + x) * channels + k] = pixels[(sy * width + sx) * channels + k];
-            }
-        }
-        rc = fri_hip_transform_quant(tile, one.data(), qm, coefs.data() + t * image);
-    }
-    if (rc == FRI_HIP_OK) rc = fri_hip_plan_set_dequantiser(tile, quality ? FRI_HIP_DEQUANT_MIDPOINT : FRI_HIP_DEQUANT_REFERENCE);
-    r.value.metadata = ImageMetadata{height, width, channels == 1 ? ColorSpace::Luma : ColorSpace::RGB};
-    r.value.data.resize(pixels.size());
-    if (rc == FRI_HIP_OK) rc = fri_hip_decode_image_tiled(raw, coefs.data(), qm, r.value.data.data());
-    if (rc != FRI_HIP_OK) r.error = dev.describe(rc);
-    r.ok = rc == FRI_HIP_OK;
-    return r;
-}
-
-Result<EncodedTiled> update_bytes_tiled(const std::vector<uint8_t> &file, const std::vector<uint8_t> &pixels, uint32_t height, uint32_t width, uint32_t x, uint32_t y, uint32_t w,
-                                        uint32_t h, int device, unsigned threads) {
-    Result<EncodedTiled> r;
-    auto fail = [&](const std::string &why) {
-        r.error = "Failed to update: " + why;
-        return r;
-    };
-    if (file.size() >= 4 && std::memcmp(file.data(), "frif", 4) == 0)
-        return fail("an untiled `frif` file has no tiles to update: encode the new image whole (encode-file), or tile it (encode-file --tile-size)");
-    emit::TiledInfo ti;
-    std::vector<uint64_t> offset;
-    if (const std::string e = emit::parse_tiled(file.data(), file.size(), ti, offset); !e.empty()) return fail(e);
-    if (ti.s420) return fail(emit::kNoUpdate420);
-    if (ti.alpha) return fail(emit::kNoUpdateRgba);
-    if (width != ti.width || height != ti.height)
-        return fail("the image is " + std::to_string(width) + "x" + std::to_string(height) + ", the file's is " + std::to_string(ti.width) + "x" + std::to_string(ti.height) +
-                    ": a region update keeps the file's size, encode an image of another size whole");
-    if (pixels.size() != (size_t)width * height * ti.channels)
-        return fail("the image does not have the file's " + std::to_string(ti.channels) + " channel(s): convert it, or encode it whole");
-    emit::TileRange range;
-    if (!emit::region_tiles(ti.width, ti.height, ti.tile_w, ti.tile_h, emit::Region{x, y, w, h}, range)) return fail("invalid region");
-    std::array<int32_t, 32> qm;
-    qm.fill(1); // a lossless file: ones
-    if (ti.quality && fri_hip_quality_matrix((int)ti.quality, qm.data()) != FRI_HIP_OK) return fail("invalid quality");
-    Device dev(device);
-    if (!dev.ok()) return fail(dev.error());
-    fri_hip_plan_tiled *raw = nullptr;
-    // (a file may hold tiles with holes: whoever wrote it asked for them)
-    if (const int rc = fri_hip_plan_tiled_create(dev.ctx(), ti.width, ti.height, ti.channels, ti.tile_w, ti.tile_h, FRI_HIP_TILED_ALLOW_HOLES, &raw); rc != FRI_HIP_OK) return fail(dev.describe(rc));
-    TiledPlan plan(raw);
-    fri_hip_plan *tile = fri_hip_plan_tiled_tile(raw);
-    if (const std::string e = set_colour_transform(tile, ti.rct, dev, ti.ycbcr); !e.empty()) return fail(e);
-    if (const std::string e = set_plan_stream_order(tile, dev); !e.empty()) return fail(e);
-    const size_t planes = (size_t)range.ni * range.nj * ti.channels;
-    const uint64_t n = fri_hip_plan_num_some(tile);
-    std::vector<uint16_t> symbols(planes * (size_t)n);
-    std::vector<uint32_t> hist(planes * CONTEXT_AMOUNT * ALPHABET_SIZE);
-    std::vector<float> vp(planes * 18), wp(planes * 18);
-    std::vector<uint64_t> oob(planes, 0);
-    if (const int rc = fri_hip_encode_region_tiled_symbols(raw, pixels.data(), x, y, w, h, qm.data(), vp.data(), wp.data(), symbols.data(), hist.data(), oob.data()); rc != FRI_HIP_OK)
-        return fail(dev.describe(rc));
-    for (uint64_t v : oob)
-        if (v) return fail("symbol outside the 1024-entry alphabet");
-    if (const std::string e = emit::update_tiled_from_streams(file.data(), file.size(), emit::Region{x, y, w, h}, ti.channels, ti.rct, ti.quality, ti.ycbcr, symbols.data(), (size_t)n,
-                                                              hist.data(), vp.data(), wp.data(), threads, range, r.value.bytes);
-        !e.empty())
-        return fail(e);
-    r.value.tile_w = ti.tile_w, r.value.tile_h = ti.tile_h, r.value.nx = ti.nx, r.value.ny = ti.ny;
-    r.value.quality = (int)ti.quality, r.value.rct = ti.rct, r.value.ycbcr = ti.ycbcr;
-    r.ok = true;
-    return r;
-}
-
-// ---- tiled 4:2:0 coding ----------------------------------------------------------------------------------------------------------------------------
-Result<EncodedTiled> encode_bytes_tiled_rgba(const std::vector<uint8_t> &rgba, uint32_t height, uint32_t width, const EncoderOpts &opts, uint32_t tile_size, bool clean_alpha,
-                                             unsigned threads) {
-    Result<EncodedTiled> r;
-    auto fail = [&](const std::string &why) {
-        r.error = "Failed to decode: " + why; // sic, encoder.rs:106
-        return r;
-    };
-    std::array<int32_t, 32> qm;
-    if (const std::string e = coding_matrix(opts, qm); !e.empty()) return fail(e);
-    if (opts.target_psnr > 0 || opts.target_ssim > 0 || opts.target_bytes)
-        return fail("tiled RGBA coding has no quality or size search (target_psnr, target_ssim, target_bytes): pass a quality, or code the image untiled");
-    if (opts.device_rans) return fail("tiled RGBA coding has no device rANS route (K11 does not take alpha tiles): code it without device_rans");
-    if (!width || !height || rgba.size() != (size_t)width * height * 4) return fail("tiled RGBA coding takes width x height R, G, B, A pixels");
-    uint32_t tw = 0, th = 0;
-    if (const int rc = fri_hip_tile_shape(width, height, tile_size, &tw, &th); rc != FRI_HIP_OK)
-        return fail(std::string("no tile shape of that size owns every pixel: ") + fri_hip_strerror(rc));
-    Device dev(opts.device);
-    if (!dev.ok()) return fail(dev.error());
-    fri_hip_plan_tiled_rgba *raw = nullptr;
-    if (const int rc = fri_hip_plan_tiled_rgba_create(dev.ctx(), width, height, tw, th, 0, &raw); rc != FRI_HIP_OK) return fail(dev.describe(rc));
-    TiledRgbaPlan plan(raw);
-    fri_hip_plan *colour = fri_hip_plan_tiled_rgba_colour(raw), *alpha = fri_hip_plan_tiled_rgba_alpha(raw);
-    for (fri_hip_plan *inner : {colour, alpha})
-        if (const std::string e = set_plan_stream_order(inner, dev); !e.empty()) return fail(e);
-    const ImageMetadata md = coded_metadata(height, width, ColorSpace::RGB, opts);
-    if (const std::string e = set_colour_transform(colour, md.rct, dev, md.ycbcr); !e.empty()) return fail(e);
-    uint32_t grid[4];
-    fri_hip_plan_tiled_rgba_grid(raw, grid);
-    r.value.tile_w = tw, r.value.tile_h = th, r.value.nx = grid[0], r.value.ny = grid[1];
-    const size_t planes = 4 * (size_t)grid[0] * grid[1]; // plane order: the colour planes tile by tile, then the alpha planes
-    const uint64_t n = fri_hip_plan_num_some(colour);
-    std::vector<uint16_t> symbols(planes * (size_t)n);
-    std::vector<uint32_t> hist(planes * CONTEXT_AMOUNT * ALPHABET_SIZE);
-    std::vector<float> vp(planes * 18), wp(planes * 18);
-    std::vector<uint64_t> oob(planes, 0);
-    if (const int rc = fri_hip_encode_image_tiled_rgba_symbols(raw, rgba.data(), clean_alpha ? FRI_HIP_ALPHA_CLEAN : FRI_HIP_ALPHA_KEEP, qm.data(), vp.data(), wp.data(),
-                                                               symbols.data(), hist.data(), oob.data());
-        rc != FRI_HIP_OK)
-        return fail(dev.describe(rc));
-    for (uint64_t v : oob)
-        if (v) return fail("symbol outside the 1024-entry alphabet"); // the reference panics: bump_freq, entropy_coding.rs:99
-    if (const std::string e = emit::encode_tiled_from_streams_rgba(width, height, tw, th, md.rct, md.quality, md.ycbcr, symbols.data(), (size_t)n, hist.data(), vp.data(), wp.data(),
-                                                                   threads, r.value.bytes);
-        !e.empty())
-        return fail(e);
-    r.value.quality = (int)md.quality, r.value.rct = md.rct, r.value.ycbcr = md.ycbcr;
-    r.ok = true;
-    return r;
-}
-
-Result<EncodedTiled> encode_bytes_tiled420(const std::vector<uint8_t> &rgb, uint32_t height, uint32_t width, int quality, uint32_t tile_size, int device, unsigned threads) {
-    EncoderOpts opts;
-    opts.quality = quality, opts.device = device;
-    return encode_bytes_tiled420(rgb, height, width, opts, tile_size, threads);
-}
-
-Result<EncodedTiled> encode_bytes_tiled420(const std::vector<uint8_t> &rgb, uint32_t height, uint32_t width, const EncoderOpts &opts, uint32_t tile_size, unsigned threads) {
-    Result<EncodedTiled> r;
-    auto fail = [&](const std::string &why) {
-        r.error = "Failed to decode: " + why; // sic, encoder.rs:106
-        return r;
-    };
-    const int n_targets = (opts.target_psnr > 0) + (opts.target_ssim > 0) + (opts.target_bytes != 0);
-    if (n_targets > 1 || (n_targets && opts.quality)) return fail("tiled 4:2:0 coding takes a quality or one target");
-    if (!n_targets && (opts.quality < 1 || opts.quality > 99)) return fail("tiled 4:2:0 coding needs a quality of 1..99");
-    if (!width || !height || rgb.size() != (size_t)width * height * 3) return fail("tiled 4:2:0 coding takes width x height RGB pixels");
-    uint32_t tw = 0, th = 0;
-    if (const int rc = fri_hip_tile_shape420(width, height, tile_size, &tw, &th); rc != FRI_HIP_OK)
-        return fail(std::string("no tile shape of that size owns every pixel in both lattices: ") + fri_hip_strerror(rc));
-    Device dev(opts.device);
-    if (!dev.ok()) return fail(dev.error());
-    fri_hip_plan_tiled420 *raw = nullptr;
-    if (const int rc = fri_hip_plan_tiled420_create(dev.ctx(), width, height, tw, th, 0, &raw); rc != FRI_HIP_OK) return fail(dev.describe(rc));
-    Tiled420Plan plan(raw);
-    fri_hip_plan *luma = fri_hip_plan_tiled420_luma(raw), *chroma = fri_hip_plan_tiled420_chroma(raw);
-    for (fri_hip_plan *inner : {luma, chroma})
-        if (const std::string e = set_plan_stream_order(inner, dev); !e.empty()) return fail(e);
-    uint32_t grid[4];
-    fri_hip_plan_tiled420_grid(raw, grid);
-    r.value.tile_w = tw, r.value.tile_h = th, r.value.nx = grid[0], r.value.ny = grid[1];
-    const size_t n = (size_t)grid[0] * grid[1], planes = 3 * n;
-    const uint64_t n_y = fri_hip_plan_num_some(luma), n_c = fri_hip_plan_num_some(chroma);
-    std::vector<uint16_t> symbols(opts.device_rans ? 0 : n * (size_t)(n_y + 2 * n_c)); // (the device coder's route reads neither streams nor histograms back)
-    std::vector<uint32_t> hist(opts.device_rans ? 0 : planes * CONTEXT_AMOUNT * ALPHABET_SIZE);
-    std::vector<float> vp(planes * 18), wp(planes * 18);
-    std::vector<uint64_t> oob(planes, 0);
-    // the device batches and the emitter at `quality`: "" or the error; the file in r.value.bytes
-    auto code = [&](int quality) -> std::string {
-        r.value.bytes.clear();
-        if (opts.device_rans) { // K11: the planes come back coded, the host writes the container around them
-            const size_t stride = (size_t)std::max(n_y, n_c) + 20; // a step emits at most one word
-            std::vector<uint32_t> words(planes * stride), n_words(planes), models(planes * CONTEXT_AMOUNT * 4), status(planes * 4);
-            std::vector<uint16_t> off(planes * CONTEXT_AMOUNT * ALPHABET_SIZE);
-            if (const int rc = fri_hip_encode_image_tiled420_coded(raw, rgb.data(), quality, vp.data(), wp.data(), words.data(), stride, n_words.data(), models.data(), off.data(),
-                                                                   status.data());
-                rc != FRI_HIP_OK) {
-                for (size_t k = 0; k < planes; k++)
-                    if (status[4 * k]) {
-                        const size_t tile = k < n ? k : (k - n) / 2, ch = k < n ? 0 : 1 + (k - n) % 2;
-                        return "tile " + std::to_string(tile) + ": channel " + std::to_string(ch) + ": the device coder refuses the plane (status " + std::to_string(status[4 * k]) + ")";
-                    }
-                return dev.describe(rc);
-            }
-            if (const std::string e = emit::encode_tiled_from_coded420(width, height, tw, th, (uint32_t)quality, words.data(), stride, n_words.data(), models.data(), off.data(),
-                                                                       vp.data(), wp.data(), threads, r.value.bytes);
-                !e.empty())
-                return e;
-        } else {
-            if (const int rc = fri_hip_encode_image_tiled420_symbols(raw, rgb.data(), quality, vp.data(), wp.data(), symbols.data(), hist.data(), oob.data()); rc != FRI_HIP_OK)
-                return dev.describe(rc);
-            for (uint64_t v : oob)
-                if (v) return "symbol outside the 1024-entry alphabet"; // the reference panics: bump_freq, entropy_coding.rs:99
-            if (const std::string e = emit::encode_tiled_from_streams420(width, height, tw, th, (uint32_t)quality, symbols.data(), (size_t)n_y, (size_t)n_c, hist.data(), vp.data(),
-                                                                         wp.data(), threads, r.value.bytes);
-                !e.empty())
-                return e;
-        }
-        r.value.quality = quality, r.value.ycbcr = true;
-        return std::string();
-    };
-    int quality = opts.quality;
-    if (opts.target_bytes) { // the highest quality whose estimated file fits
-        int32_t q = 0;
-        uint64_t est = 0;
-        const int rc = fri_hip_search_quality_for_size_tiled420(raw, rgb.data(), opts.target_bytes, &q, &est);
-        if (rc == FRI_HIP_ERR_OUT_OF_RANGE) return fail("no quality fits in " + std::to_string(opts.target_bytes) + " bytes (quality 1: about " + std::to_string(est) + ")");
-        if (rc != FRI_HIP_OK) return fail(dev.describe(rc));
-        r.value.search_quality = q;
-        // the estimate is a few bytes per channel and tile off the coder's output: code at q, emit, and go one quality lower while the file is over
-        constexpr int kMaxSteps = 8;
-        for (int step = 0; step <= kMaxSteps && q >= 1; step++, q--) {
-            if (const std::string e = code(q); !e.empty()) return fail(e);
-            if (r.value.bytes.size() <= opts.target_bytes) {
-                r.value.est_bytes = est;
-                r.ok = true;
-                return r;
-            }
-            est = 0; // (est_bytes is the estimate of the searched quality: a stepped-down result reports 0)
-        }
-        r.value.bytes.clear();
-        return fail("no file of at most " + std::to_string(opts.target_bytes) + " bytes within " + std::to_string(kMaxSteps) + " qualities below the estimate's");
-    }
-    if (n_targets) { // the lowest quality that reaches the target; 100: none does, and a 4:2:0 file has no lossless form to fall back to
-        int32_t q = 100;
-        int rc;
-        if (opts.target_psnr > 0) rc = fri_hip_search_quality_tiled420(raw, rgb.data(), opts.target_psnr, &q, &r.value.psnr_db);
-        else rc = fri_hip_search_quality_ssim_tiled420(raw, rgb.data(), opts.target_ssim, &q, &r.value.ssim);
-        if (rc != FRI_HIP_OK) return fail(dev.describe(rc));
-        r.value.search_quality = q;
-        if (q == 100) return fail("no 4:2:0 quality reaches the target");
-        quality = q;
-    }
-    if (const std::string e = code(quality); !e.empty()) return fail(e);
-    r.ok = true;
-    return r;
-}
-
-Result<RasterImage> round_trip_tiled420(const std::vector<uint8_t> &rgb, uint32_t height, uint32_t width, uint32_t tile_w, uint32_t tile_h, int quality, int device) {
-    Result<RasterImage> r;
-    int32_t qm[32];
-    if (!width || !height || !tile_w || !tile_h || rgb.size() != (size_t)width * height * 3 || quality < 1 || quality > 99 || fri_hip_quality_matrix(quality, qm) != FRI_HIP_OK) {
-        r.error = "invalid argument";
-        return r;
-    }
-    Device dev(device);
-    if (!dev.ok()) {
-        r.error = dev.error();
-        return r;
-    }
-    fri_hip_plan_tiled420 *raw = nullptr;
-    int rc = fri_hip_plan_tiled420_create(dev.ctx(), width, height, tile_w, tile_h, FRI_HIP_TILED_ALLOW_HOLES, &raw);
-    if (rc != FRI_HIP_OK) {
-        r.error = dev.describe(rc);
-        return r;
-    }
-    Tiled420Plan plan(raw);
-    fri_hip_plan *luma = fri_hip_plan_tiled420_luma(raw), *chroma = fri_hip_plan_tiled420_chroma(raw);
-    uint32_t grid[4];
-    fri_hip_plan_tiled420_grid(raw, grid);
-    const size_t n = (size_t)grid[0] * grid[1], y_bytes = fri_hip_plan_pixel_bytes(luma), c_bytes = fri_hip_plan_pixel_bytes(chroma);
-    const size_t fy = fri_hip_plan_coef_count(luma), fc = fri_hip_plan_coef_count(chroma);
-    // the device split (K12), then the forward kernel plane by plane in plane order: no scan, no coder
-    uint8_t *d_rgb = nullptr, *d_y = nullptr, *d_c = nullptr;
-    std::vector<uint8_t> y_tiles(n * y_bytes), c_tiles(2 * n * c_bytes);
-    auto release = [&] { (void)hipFree(d_rgb), (void)hipFree(d_y), (void)hipFree(d_c); };
-    if (hipMalloc((void **)&d_rgb, rgb.size()) != hipSuccess || hipMalloc((void **)&d_y, y_tiles.size()) != hipSuccess || hipMalloc((void **)&d_c, c_tiles.size()) != hipSuccess ||
-        hipMemcpy(d_rgb, rgb.data(), rgb.size(), hipMemcpyHostToDevice) != hipSuccess) {
-        release();
-        r.error = "device allocation failed";
-        return r;
-    }
-    rc = fri_hip_split_tiles420_dev(raw, d_rgb, d_y, d_c, nullptr);
-    if (rc == FRI_HIP_OK && (hipMemcpy(y_tiles.data(), d_y, y_tiles.size(), hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(c_tiles.data(), d_c, c_tiles.size(), hipMemcpyDeviceToHost) != hipSuccess))
-        rc = FRI_HIP_ERR_HIP;
-    release();
-    std::vector<int32_t> coefs(n * (fy + 2 * fc));
-    for (size_t t = 0; t < n && rc == FRI_HIP_OK; t++) rc = fri_hip_transform_quant(luma, y_tiles.data() + t * y_bytes, qm, coefs.data() + t * fy);
-    for (size_t k = 0; k < 2 * n && rc == FRI_HIP_OK; k++) rc = fri_hip_transform_quant(chroma, c_tiles.data() + k * c_bytes, qm, coefs.data() + n * fy + k * fc);
-    r.value.metadata = ImageMetadata{height, width, ColorSpace::RGB};
-    r.value.data.resize(rgb.size());
-    if (rc == FRI_HIP_OK) rc = fri_hip_decode_image_tiled420(raw, coefs.data(), quality, r.value.data.data());
-    if (rc != FRI_HIP_OK) r.error = dev.describe(rc);
-    r.ok = rc == FRI_HIP_OK;
     return r;
 }
 
