@@ -1052,6 +1052,10 @@ int fri_hip_encode_image_tiled420_coded(fri_hip_plan_tiled420 *p, const uint8_t 
  * decoded before it; the planes are what runs side by side. An untiled `frif` image is one such chain per channel and has no business here. The coder step is
  * the host's, from one header (csrc/rans_step.hpp, get / advance / refill), the model is the one AnsContext::finalize builds from what the file carries
  * (csrc/ans_model.hpp, ans_model_rebuild_file), and the context arithmetic is K2's exact statement of it: the planes are bit for bit fri_tiled_decode's.
+ * One limit comes with the flat planes: None is FRI_HIP_NONE = INT32_MIN, so a plane cannot hold Some(i32::MIN), a value that saturating or non-finite
+ * predictor parameters in a file can make a stream decode to. The host decoder and K13 both store such a coefficient as it is and read it back as None - 0 in
+ * every later context, `x == kNone ? 0 : x` - and so agree with each other on every file, where the reference, which keeps the two apart, decodes other
+ * coefficients from that node on.
  *
  * plan: the C = 1 or C = 3 plan whose lattice every plane lives on; it supplies the geometry, the Laplace table and the stream order
  * (fri_hip_plan_set_stream_order) - without the order the call returns FRI_HIP_ERR_INVALID_ARGUMENT, as the symbol chains do.

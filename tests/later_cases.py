@@ -16,7 +16,7 @@ K12_STRIP = 16
 
 SEED = 20261019
 # cases per kind of the second sweep: the smallest counts (not below 40) at which the fixed-seed dry run reaches every cell test_later_cases_host.py asks for
-N_CASES = {"ycbcr": 40, "ssim": 40, "rate": 40, "c420": 40, "rgba": 40, "tiled": 60, "tiled420": 60, "rans": 40}
+N_CASES = {"ycbcr": 40, "ssim": 40, "rate": 40, "c420": 40, "rgba": 40, "tiled": 60, "tiled420": 60, "rans": 40, "decode": 59}
 
 
 def _ceil(a, b):

@@ -4,6 +4,9 @@ the host decoder, emit.tiled_decode, which tests/test_emit.py holds to the oracl
 - the planes entry on the coded planes of whole files (emit.tiled_parse_coded): coefficients exact, None entries included, every status 0, with strides larger
   than needed and every array between guard bytes;
 - damaged planes - cut short, one word flipped - give the host decoder's verdict as a status, the other planes of the batch stay exact, and the run ends clean;
+- crafted planes (tests/decode_cases.py: parameters, symbols and models no encoder of ours makes) three ways - the oracle's walk, the host decoder, the device -
+  whole and bounded by a level; cut short, the status names the very step at which a Python replay of the coder runs dry; a decoded Some(i32::MIN); model lists
+  the host parser never produces, against the file that carries the same list;
 - the composed entries against the inverse kernel on the host decoder's planes, byte for byte; files K11 coded parse back to the planes that went in;
 - the same bytes in every run, and from a captured graph; argument errors; fri_driver decode-file --device-rans."""
 import ctypes as C
@@ -19,6 +22,8 @@ import frave_amd as fa
 import frave_amd.api as api
 import frave_amd.emit as emit
 from frave_amd.api import DECODE_BAD_MODEL, DECODE_BAD_SLOT, DECODE_TRUNCATED, PlanTiled, PlanTiled420  # noqa: F401  (without the feature the module fails here)
+from tests import decode_cases as D
+from tests import preview_ref
 from tests.coded_cases import file_of_image, tiled420_file, tiled_file
 from tests.common import gen_image
 from tests.test_gpu_instances import Guarded
@@ -113,7 +118,7 @@ class Decode:
         a = dict(plan=self.plan, n_planes=self.planes, word_stride=self.word_stride, coef_stride=self.coef_stride, coefs=self.coefs.ptr, scratch=self.scratch_ptr, words=i["words"].ptr)
         a.update(override)
         return api.decode_planes_dev(a["plan"], a["n_planes"], a["words"], a["word_stride"], i["n_words"].ptr, i["models"].ptr, i["off"].ptr, i["vp"].ptr, i["wp"].ptr, a["coefs"],
-                                     a["coef_stride"], self.status.ptr, a["scratch"], stream, timed=override.get("timed", False))
+                                     a["coef_stride"], self.status.ptr, a["scratch"], stream, timed=override.get("timed", False), levels=override.get("levels"))
 
     def read(self):
         """(coefs int32 [P][F][512], status uint32 [P][4]); asserts that nothing outside the outputs changed, the inputs included"""
@@ -272,6 +277,193 @@ def test_a_bad_model_is_reported_and_nothing_is_decoded(ctx):
     assert status[1].tolist() == [DECODE_BAD_MODEL, 1, 0, 0] and not status[[0, 2, 3]].any()
     assert _first_difference(coefs[[0, 2, 3]], want[[0, 2, 3]]) == ""
     assert np.array_equal(coefs[1], np.where(want[1] == NONE, NONE, 0))  # the initial values: 0 on a Some node, None elsewhere
+
+
+# ---- crafted planes (tests/decode_cases.py) ---------------------------------------------------------------------------------------------------------------------
+# Planes no encoder of ours makes: saturated, NaN and infinite parameters, widths on the bucket edges, coefficients at the int32 limits, models scaled up to
+# max_freq_bits 30 and lists of 700 symbols. tests/test_decode_cases_host.py holds them to the host decoder and to the cells they reach.
+
+@pytest.mark.parametrize("name", sorted(D.BATCHES))
+def test_crafted_planes_equal_the_host_decoder(ctx, name):
+    frv, tw, th, oracle = D.batch(name)
+    want = _reference(frv)
+    assert _first_difference(want, oracle) == ""
+    d = Decode(ctx, tw, th, tiled_parse_coded(frv))  # one launch: every plane its own parameters, models and word count
+    assert d.planes == len(D.BATCHES[name]) <= 16
+    d.launch()
+    coefs, status = d.read()
+    d.close()
+    assert not status.any(), [(D.BATCHES[name][k], status[k].tolist()) for k in np.flatnonzero(status.any(axis=1))]
+    for k, case in enumerate(D.BATCHES[name]):
+        assert _first_difference(coefs[k : k + 1], want[k : k + 1]) == "", case
+
+
+def test_crafted_planes_level_bounded(ctx):
+    frv, tw, th, oracle = D.batch("small")
+    d = Decode(ctx, tw, th, tiled_parse_coded(frv))
+    bits = d.plan.valid_bits()
+    for levels in (0, 1, 2, 5, 8):
+        d.clear()
+        d.launch(levels=levels)
+        coefs, status = d.read()
+        assert not status.any(), (levels, status)
+        compact = emit.tiled_decode_levels(frv, levels)[1].reshape(-1, d.F, 1 << levels)
+        assert np.array_equal(compact, oracle[:, :, : 1 << levels])
+        want = preview_ref.expand(compact, bits)
+        for k, case in enumerate(D.BATCHES["small"]):
+            assert _first_difference(coefs[k : k + 1], want[k : k + 1]) == "", (levels, case)
+    d.close()
+
+
+TRUNCATED_CASES = ("groups", "negative_width_x2^20")  # every context at max_freq_bits 8; one at 30
+
+
+def _cut_plane(L, plane, step):
+    """what a plane refused at `step` holds: the reference up to that step, the initial values behind it"""
+    out = np.where(L.some, 0, NONE).astype(np.int32).reshape(-1)
+    out[L.own[:step]] = plane.reshape(-1)[L.own[:step]]
+    return out.reshape(plane.shape)
+
+
+def test_truncated_crafted_planes_stop_at_the_step_the_coder_runs_dry(ctx):
+    frv, tw, th, oracle = D.batch("small")
+    ti, words, n_words, models, off, vp, wp = tiled_parse_coded(frv)
+    L = D.lattice(tw, th)
+    rows, cuts, steps = [], [], {}
+    for name in TRUNCATED_CASES:
+        k, r = D.BATCHES["small"].index(name), D.built(name)
+        bits = [m[3] for m in r["models"] if m is not None]
+        assert (max(bits) == 8) if name == "groups" else (max(bits) >= 24)
+        n = int(n_words[k])
+        steps[k] = D.word_steps(words[k, :n], r["stream"], r["models"])
+        assert n > 20 + 65 and (steps[k][:20] == -1).all() and (np.diff(steps[k][20:]) >= 0).all()
+        # no body word, one, the 64th and the 65th (the window of 64 stream words turns there), all but the last; and the plane as it is
+        for cut in (20, 21, 20 + 63, 20 + 64, n - 1, n):
+            rows.append(k), cuts.append(cut)
+    rows = np.array(rows)
+    d = Decode(ctx, tw, th, (words[rows], np.array(cuts, np.uint32), models[rows], off[rows], vp[rows], wp[rows]))
+    d.launch()
+    coefs, status = d.read()
+    d.close()
+    for p, (k, cut) in enumerate(zip(rows, cuts)):
+        if cut == n_words[k]:
+            assert not status[p].any() and _first_difference(coefs[p : p + 1], oracle[k : k + 1]) == "", (D.BATCHES["small"][k], cut)
+            continue
+        step = int(steps[k][cut])  # the step that takes word `cut`
+        assert status[p].tolist() == [DECODE_TRUNCATED, 1 + step, 0, 0], (D.BATCHES["small"][k], cut, step, status[p].tolist())
+        assert _first_difference(coefs[p : p + 1], _cut_plane(L, oracle[k], step)[None]) == "", (D.BATCHES["small"][k], cut)
+    # the same through a word_stride smaller than n_words: no word is read at or past the stride
+    pair = np.array([D.BATCHES["small"].index(name) for name in TRUNCATED_CASES])
+    shortest = int(n_words[pair].min())
+    for stride in (20, 21, 20 + 63, 20 + 64, shortest - 1):
+        d = Decode(ctx, tw, th, (np.ascontiguousarray(words[pair, :stride]), n_words[pair], models[pair], off[pair], vp[pair], wp[pair]), word_pad=0)
+        assert d.word_stride == stride
+        d.launch()
+        coefs, status = d.read()
+        d.close()
+        for p, k in enumerate(pair):
+            step = int(steps[k][stride])
+            assert status[p].tolist() == [DECODE_TRUNCATED, 1 + step, 0, 0], (D.BATCHES["small"][k], stride, step, status[p].tolist())
+            assert _first_difference(coefs[p : p + 1], _cut_plane(L, oracle[k], step)[None]) == "", (D.BATCHES["small"][k], stride)
+
+
+def _verdict_matches(status, err):
+    """a refusal of the host decoder as a status: non-zero, and "stream truncated" is DECODE_TRUNCATED (as for the flipped words)"""
+    return status[0] != 0 and status[1] >= 1 and ("truncated" in err) == (status[0] == DECODE_TRUNCATED)
+
+
+def test_a_some_int_min_decodes_as_the_host_decodes_it(ctx):
+    """a decoded Some(i32::MIN) is a value the planes cannot hold (None is INT32_MIN): decode_channel reads it back as None, `x == kNone ? 0 : x`, and so does K13.
+    The oracle, which keeps the two apart, decodes other coefficients from there on (tests/test_decode_cases_host.py)."""
+    s = D.sentinel()
+    tw, th = s["shape"]
+    frv = D.file_of([s])
+    planes, err = _host_verdict(frv)
+    d = Decode(ctx, tw, th, tiled_parse_coded(frv))
+    d.launch()
+    coefs, status = d.read()
+    d.close()
+    if planes is None:
+        assert _verdict_matches(status[0], err), (err, status[0].tolist())
+    else:
+        assert not status.any() and _first_difference(coefs, planes) == ""
+        assert (planes[0][D.lattice(tw, th).some] == NONE).any() and _first_difference(coefs, s["plane"][None]) != ""
+
+
+def _list_variants(models, off):
+    """model lists the host parser never produces, from one plane's models [10][4] and lists [10][1024]: name -> (models, off, the model is unchanged)"""
+    out = {}
+
+    def variant(name, same):
+        m, o = models.copy(), off.copy()
+        out[name] = (m, o, same)
+        return m, o
+
+    b = int(np.argmax(models[:, 1]))  # the longest list
+    n = int(models[b, 1])
+    listed = off[b, :n].copy()
+    assert 512 <= n < 1024 and len(set(listed.tolist())) == n and (np.diff(listed.astype(int)) > 0).all() and listed.max() < 1024
+    variant("as the file carries it", True)
+    m, o = variant("duplicates up to n_off = 1024", True)
+    o[b, n:] = listed[: 1024 - n]
+    m[b, 1] = 1024
+    m, o = variant("every entry twice, side by side", True)
+    q = min(n, 1024 - n) - 1
+    o[b, : n + q] = np.concatenate([np.repeat(listed[:q], 2), listed[q:]])
+    m[b, 1] = n + q
+    m, o = variant("descending", True)
+    o[b, :n] = listed[::-1]
+    m, o = variant("values 1024..65535 between the entries", True)
+    extra = np.array([1024, 65535, 1023 + 1024, 2048, 40000, 1025], np.uint16)
+    o[b, : n + extra.size] = np.insert(listed, [0, 1, n // 2, n // 2, n - 1, n], extra)
+    m[b, 1] = n + extra.size
+    m, o = variant("n_off = 1024, the rest above the alphabet", True)
+    o[b, n:] = (1024 + 61 * np.arange(1024 - n)).astype(np.uint16)
+    m[b, 1] = 1024
+    assert o[b, n:].min() >= 1024
+    m, o = variant("entries moved above the alphabet", False)  # those symbols lose their slot: another model
+    o[b, : n : 5] += np.uint16(1024)
+    m, o = variant("symbols listed that the plane never used", False)  # they take a slot each: another model
+    unused = np.setdiff1d(np.arange(600, 1023), listed)[: 1024 - n].astype(np.uint16)
+    o[b, n : n + unused.size] = unused
+    m[b, 1] = n + unused.size
+    low = [c for c in range(10) if models[c, 0] == 8]
+    assert len(low) >= 8
+    m, o = variant("max_freq_bits 0..7 where the file has 8", True)  # finalize's floor to 8
+    for i, c in enumerate(low):
+        m[c, 0] = i % 8
+    return out
+
+
+def test_model_lists_the_host_parser_never_produces(ctx):
+    """duplicates, values past the alphabet, descending order, n_off = 1024 exactly, a max_freq_bits below the floor: in at the planes entry directly. The reference
+    is the file that carries the same list (emit.tiled_encode_from_coded) through the host decoder; where the host refuses it, a status."""
+    frv, tw, th, oracle = D.batch("small")
+    ti, words, n_words, models, off, vp, wp = tiled_parse_coded(frv)
+    k = D.BATCHES["small"].index("negative_width_lists")
+    variants = _list_variants(models[k], off[k])
+    names = sorted(variants)
+    assert len(names) <= 16
+    host = []
+    for name in names:
+        m, o, same = variants[name]
+        one = emit.tiled_encode_from_coded(tw, th, tw, th, words[k : k + 1], n_words[k : k + 1], m[None], o[None], vp[k : k + 1], wp[k : k + 1])
+        p_models, p_off = tiled_parse_coded(one)[3:5]
+        assert np.array_equal(p_models[0, :, :2], m[:, :2]) and all(np.array_equal(p_off[0, c, : m[c, 1]], o[c, : m[c, 1]]) for c in range(10)), name
+        planes, err = _host_verdict(one)
+        if same:  # the host reads the same model out of it: the oracle's plane
+            assert planes is not None and _first_difference(planes, oracle[k : k + 1]) == "", (name, err)
+        host.append((planes, err))
+    rows = np.full(len(names), k)
+    d = Decode(ctx, tw, th, (words[rows], n_words[rows], np.stack([variants[n][0] for n in names]), np.stack([variants[n][1] for n in names]), vp[rows], wp[rows]))
+    d.launch()
+    coefs, status = d.read()  # (every guard untouched)
+    d.close()
+    for p, (name, (planes, err)) in enumerate(zip(names, host)):
+        if planes is None:
+            assert _verdict_matches(status[p], err), (name, err, status[p].tolist())
+        else:
+            assert not status[p].any() and _first_difference(coefs[p : p + 1], planes) == "", (name, status[p].tolist())
 
 
 # ---- the composed entries ---------------------------------------------------------------------------------------------------------------------------------------

@@ -89,6 +89,7 @@ REQUIRED = {
     "tiled": LC.K10_CELLS | LC.K10_REGION_CELLS | {"C%d region: touches the last row and column" % c for c in (1, 3)} | {"C%d: composed encode" % c for c in (1, 3)},
     "tiled420": LC.K12_SPLIT_CELLS | LC.K12_REGION_CELLS | {"region: %s x, %s y" % (a, b) for a in ("odd", "even") for b in ("odd", "even")} | {"composed encode"},
     "rans": {"a refused plane", "every plane coded", "streams further than their length apart", "streams no further than their length apart"},
+    "decode": F.DECODE_CELLS,  # every cell of tests/decode_cases.py, both tile shapes, every level, family and symbol rule
 }
 
 
@@ -109,6 +110,8 @@ def test_dry_run_reaches_every_cell_and_draws_only_valid_cases(kind):
         assert F.violated(kind, p) == [], (kind, i, p)
     if kind in ("c420", "rgba", "tiled", "tiled420"):  # the composed encode on one case in four
         assert sum(p["composed"] for p in cases) == (len(cases) + 3) // 4
+    if kind == "decode":  # the count is the smallest that reaches every cell: one case fewer misses one
+        assert LC.N_CASES[kind] == 40 or REQUIRED[kind] - F.sweep(kind, LC.N_CASES[kind] - 1, LC.SEED, dry=True, only=-1)[1]
     if kind == "rans":
         p = next(p for p in cases if p["inject"] == "bad")  # an injected entry makes the reference refuse that plane, and only that one
         assert [bool(r.status) for r in F._rans_ref(p)["refs"]] == [k == p["inject_plane"] for k in range(p["planes"])]

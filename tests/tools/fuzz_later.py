@@ -1,5 +1,6 @@
 """Random-shape sweep of the kernels and plan kinds that came after tests/tools/fuzz_parity.py: YCbCr in K1 / K3, K6 (size estimate), K7 (SSIM), K8 (4:2:0),
-K9 (RGBA), K10 (tiles, region merge, measure), K11 (device rANS), K12 (tiled 4:2:0), and the composed encode entry points. Every comparison is bit-exact against
+K9 (RGBA), K10 (tiles, region merge, measure), K11 (device rANS), K12 (tiled 4:2:0), K13 (the device decoder, on the crafted planes of tests/decode_cases.py,
+bounded by a drawn level), and the composed encode entry points. Every comparison is bit-exact against
 a restatement that involves no GPU code (tests/*_ref.py, tests/rate_model.py, the CPU oracle); K6's bytes keep the +-1 byte of tests/test_gpu_rate.py. Every
 device buffer is a tests.test_gpu_instances.Guarded one, outputs start as a fill pattern, guards are checked after every call. The byte rasters, for which the
 headers promise any alignment, sit at a drawn byte offset of 0..15; the typed arrays (coefficients, histograms, streams, words, models) keep the 16-byte alignment
@@ -16,8 +17,9 @@ import numpy as np
 
 import frave_amd
 from frave_amd.api import TILED_ALLOW_HOLES, FriHipError
+from tests import decode_cases as DC
 from tests import later_cases as LC
-from tests import rans_cases, rans_ref, rate_model, ssim_ref
+from tests import preview_ref, rans_cases, rans_ref, rate_model, ssim_ref
 from tests.alpha_ref import alpha_plane, merge_rgba, rgba_image, split_rgba
 from tests.chroma420_ref import chroma_shape, measure420, merge420, planes_flat, split420
 from tests.common import gen_image
@@ -756,6 +758,106 @@ def _rans_dev(ctx, p, r):
     return D.msgs
 
 
+# ---- decode: K13 on crafted planes ----------------------------------------------------------------------------------------------------------------------------
+
+DECODE_FAMILIES = ["kat", "mild", "grow", "saturated", "negative width", "nan", "inf", "edges", "groups"]
+DECODE_EDGES = [2.999, 3.0, 29.999, 30.0, 31.0, 32.0, 4294967296.0]
+
+
+def _decode_params(rng, family):
+    """(value_params, width_params) float32 [3][6] of a family of tests/decode_cases.py, the magnitudes drawn"""
+    f = np.float32
+    sign = lambda: f(1 if rng.random() < 0.5 else -1)  # noqa: E731
+    vp, wp = DC.KAT_V.copy(), DC.KAT_W.copy()
+    if family == "kat":
+        vp, wp = vp * f(rng.uniform(0.5, 1.5)), wp * f(rng.uniform(0.5, 2.0))
+    elif family == "mild":
+        wp = DC.MILD_W * rng.uniform(0.3, 3.0, (3, 1)).astype(f)
+    elif family == "grow":
+        vp = np.full((3, 6), sign() * f(rng.uniform(1.1, 3.0)), f)
+        wp = DC.MILD_W.copy() if rng.random() < 0.5 else wp
+    elif family == "saturated":
+        vp, wp = np.full((3, 6), sign() * f(10.0 ** rng.uniform(9, 38)), f), np.full((3, 6), sign() * f(10.0 ** rng.uniform(9, 38)), f)
+    elif family == "negative width":
+        wp = np.full((3, 6), -f(10.0 ** rng.uniform(-1, 2)), f)
+    elif family == "nan":
+        k = _int(rng, 0, 2)
+        vp, wp = (np.full((3, 6), np.nan, f) if k != 1 else vp), (np.full((3, 6), np.nan, f) if k != 0 else wp)
+    elif family == "inf":
+        vp, wp = np.full((3, 6), sign() * f(np.inf), f), DC.INF_W * sign()
+    elif family == "edges":
+        wp = np.zeros((3, 6), f)
+        wp[:, 0] = [DECODE_EDGES[_int(rng, 0, 6)] if rng.random() < 0.6 else rng.uniform(0, 40) for _ in range(3)]
+    else:
+        vp, wp = DC.GROUP_V * rng.uniform(0.5, 1.5, (3, 1)).astype(f), DC.GROUP_W * rng.uniform(0.5, 1.5, (3, 1)).astype(f)
+    return vp.astype(f), wp.astype(f)
+
+
+def _decode_draw(rng, case):
+    family = DECODE_FAMILIES[case % len(DECODE_FAMILIES)] if case < 2 * len(DECODE_FAMILIES) else DECODE_FAMILIES[_int(rng, 0, len(DECODE_FAMILIES) - 1)]
+    vp, wp = _decode_params(rng, family)
+    rule = DC.RULES[_int(rng, 0, 3)]
+    return dict(shape=list(DC.LARGE if rng.random() < 0.2 else DC.SMALL), family=family, vp=[[float(v) for v in row] for row in vp], wp=[[float(v) for v in row] for row in wp],
+                rule=rule, p=round(float(rng.uniform(0.04, 0.5)), 3), multiplier=DC.MULTIPLIERS[_int(rng, 0, 3)], level=_int(rng, 0, 9), seed=_int(rng, 0, 1 << 30), off=_offsets(rng, 8))
+
+
+_decode_walks = {}
+
+
+def _decode_walk(p):
+    """the case's plane walked on the oracle (tests/decode_cases.walk), once per case"""
+    key = repr(sorted(p.items()))
+    if key not in _decode_walks:
+        rule = ("geometric", p["p"]) if p["rule"] == "geometric" else p["rule"]
+        vp, wp = np.array(p["vp"], np.float32), np.array(p["wp"], np.float32)
+        r = DC.walk(*p["shape"], vp, wp, rule, p["seed"])
+        r["hist_scaled"], r["multiplier_used"] = DC.scaled_histogram(r["hist"], p["multiplier"])
+        r.update(vp=vp, wp=wp, shape=tuple(p["shape"]))
+        _decode_walks[key] = r
+    return _decode_walks[key]
+
+
+def _decode_ref(p):
+    import frave_amd.emit as emit
+
+    r = _decode_walk(p)
+    frv = DC.file_of([r])
+    L = DC.lattice(*p["shape"])
+    compact = emit.tiled_decode_levels(frv, p["level"])[1].reshape(L.F, 1 << p["level"])
+    if not np.array_equal(compact, r["plane"][:, : 1 << p["level"]]):
+        raise AssertionError("the host decoder does not return the oracle walk's plane: %s" % p)
+    return dict(coded=emit.tiled_parse_coded(frv), want=preview_ref.expand(compact, L.some))
+
+
+def _decode_cells(p):
+    return DC.cells_of(_decode_walk(p)) | {"%d x %d" % tuple(p["shape"]), "level %d" % p["level"], "family: " + p["family"], "rule: " + p["rule"]}
+
+
+DECODE_CELLS = set(DC.CELLS) | {"%d x %d" % s for s in (DC.SMALL, DC.LARGE)} | {"level %d" % k for k in range(10)} | {"family: " + f for f in DECODE_FAMILIES} | {"rule: " + r for r in DC.RULES}
+
+
+def _decode_dev(ctx, p, r):
+    import frave_amd.api as api
+
+    D, off = _Dev(), p["off"]
+    ti, words, n_words, models, lists, vp, wp = r["coded"]
+    stride = words.shape[1]
+    P = frave_amd.Plan(ctx, *p["shape"], 1)
+    P.set_stream_order()
+    ins = [D.put(a, off[i], 16) for i, a in enumerate((words, n_words, models, lists, vp, wp))]
+    coefs, status = D.out(4 * P.num_cells * 512, off[6], 16), D.out(16, off[7], 16)
+    scratch = D.torch.empty(api.decode_scratch_bytes(1) + 256, dtype=D.torch.uint8, device="cuda")
+    api.decode_planes_dev(P, 1, ins[0].ptr, stride, *(g.ptr for g in ins[1:]), coefs.ptr, P.num_cells * 512, status.ptr, (scratch.data_ptr() + 255) & ~255, 0, levels=p["level"])
+    got_status = D.get(status, "K13 status").view(np.uint32)
+    if got_status.any():
+        D.msgs.append("K13 status %s" % got_status.tolist())
+    D.same("K13 coefficients", D.get(coefs, "K13 coefficients").view(np.int32), r["want"])
+    for g, name in zip(ins, ("words", "n_words", "models", "lists", "value parameters", "width parameters")):
+        D.untouched(g, name)
+    P.close()
+    return D.msgs
+
+
 # ---- preconditions and the sweep -----------------------------------------------------------------------------------------------------------------------------
 
 def violated(kind, p):
@@ -780,6 +882,16 @@ def violated(kind, p):
                 bad.append("region")
     if kind == "rans" and not (1 <= p["planes"] <= 65535 and 1 <= p["n"] <= 20000 and p["symbol_stride"] >= p["n"]):
         bad.append("K11 counts")
+    if kind == "decode":  # the generator conditions of tests/decode_cases.py
+        if tuple(p["shape"]) not in (DC.SMALL, DC.LARGE) or p["rule"] not in DC.RULES or p["multiplier"] not in DC.MULTIPLIERS or not 0 <= p["level"] <= 9:
+            bad.append("K13 draw")
+        else:
+            r = _decode_walk(p)
+            if r["symbol"].min() < 0 or r["symbol"].max() > 1022:
+                bad.append("a symbol outside 0..1022")
+            bad += DC.histogram_violations(r["hist_scaled"])
+            if (r["plane"][DC.lattice(*p["shape"]).some] == DC.NONE).any():
+                bad.append("a Some(INT32_MIN)")
     if any(not 0 <= o <= 15 for o in p["off"]):
         bad.append("offset")
     return bad
@@ -793,7 +905,8 @@ def _no_cells(p):
 KINDS = {"ycbcr": (1, _ycbcr_draw, _ycbcr_ref, _no_cells, _ycbcr_dev), "ssim": (2, _ssim_draw, _ssim_ref, _ssim_cells, _ssim_dev),
          "rate": (3, _rate_draw, _rate_ref, _rate_cells, _rate_dev), "c420": (4, _c420_draw, _c420_ref, _c420_cells, _c420_dev),
          "rgba": (5, _rgba_draw, _rgba_ref, _rgba_cells, _rgba_dev), "tiled": (6, _tiled_draw, _tiled_ref, _tiled_cells, _tiled_dev),
-         "tiled420": (7, _tiled420_draw, _tiled420_ref, _tiled420_cells, _tiled420_dev), "rans": (8, _rans_draw, _rans_ref, _rans_cells, _rans_dev)}
+         "tiled420": (7, _tiled420_draw, _tiled420_ref, _tiled420_cells, _tiled420_dev), "rans": (8, _rans_draw, _rans_ref, _rans_cells, _rans_dev),
+         "decode": (9, _decode_draw, _decode_ref, _decode_cells, _decode_dev)}
 
 
 def sweep(kind, n_cases, seed, ctx=None, dry=False, only=None):
