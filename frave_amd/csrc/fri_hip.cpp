@@ -64,6 +64,8 @@ struct Knobs {
     int band_rows = 0, cells_per_tile = 0, cells_per_wg = 0, target_wgs = 0, tile_bytes = 0;
     int ranks = 0; // FRI_HIP_RANKS, at most 4
     std::optional<int> strided_shares;
+    std::optional<int> k1_wave; // FRI_HIP_K1_WAVE: 1 = the plan carries the forward kernel's wave form and runs it wherever it applies, 0 = it never does
+    int k1_wave_band = 0, k1_wave_wgs = 0; // with it: FRI_HIP_K1_WAVE_BAND (rows per band, 0 = 16), FRI_HIP_K1_WAVE_WGS (workgroups per CU the shares are cut for, 0 = 4)
     bool has_rank_weights = false; // FRI_HIP_RANK_WEIGHTS="w0,w1,w2,w3" with all four parsed ("1,1,1,1" = equal shares)
     float rank_weight[4] = {0, 0, 0, 0};
     bool pins_forward = false;
@@ -93,6 +95,8 @@ Knobs read_knobs() {
     k.band_rows = num(pin("FRI_HIP_BAND_ROWS")), k.cells_per_tile = num(pin("FRI_HIP_CELLS_PER_TILE")), k.cells_per_wg = num(pin("FRI_HIP_CELLS_PER_WG"));
     k.target_wgs = num(pin("FRI_HIP_TARGET_WGS")), k.tile_bytes = num(pin("FRI_HIP_TILE_BYTES")), k.ranks = std::min(num(pin("FRI_HIP_RANKS")), 4);
     k.strided_shares = opt(pin("FRI_HIP_STRIDED_SHARES"));
+    k.k1_wave = opt(pin("FRI_HIP_K1_WAVE"));
+    k.k1_wave_band = num(pin("FRI_HIP_K1_WAVE_BAND")), k.k1_wave_wgs = num(pin("FRI_HIP_K1_WAVE_WGS"));
     if (const char *s = pin("FRI_HIP_RANK_WEIGHTS")) {
         float *w = k.rank_weight;
         k.has_rank_weights = std::sscanf(s, "%f,%f,%f,%f", &w[0], &w[1], &w[2], &w[3]) == 4;
@@ -229,11 +233,14 @@ void fill_forward_tiling(DevicePlan &d, const Geometry &g) {
     d.n_tiles = (uint32_t)g.tiles.size(), d.n_wg = (uint32_t)g.wg_tiles.size() - 1, d.n_wg_batch = (uint32_t)g.wg_tiles_batch.size() - 1;
     d.lds_pitch = g.lds_pitch, d.lds_rows = g.lds_rows, d.cells_per_tile = g.cells_per_tile, d.max_tile_cells = g.max_tile_cells;
     d.max_wg_tiles = std::max(g.max_wg_tiles, g.max_wg_tiles_batch), d.max_wg_cells = g.max_wg_cells;
+    d.n_wave_wg = g.wave_cells.empty() ? 0u : (uint32_t)g.wave_cells.size() - 1, d.max_wave_wg_cells = g.max_wave_wg_cells;
+    if (g.wave_cells.empty()) d.wave_meta = nullptr, d.wave_cells = nullptr;
 }
 // ... and the inverse kernel's: one share per workgroup, no batch shares
 void fill_inverse_tiling(DevicePlan &d, const Geometry &g) {
     fill_forward_tiling(d, g);
     d.wg_tiles_batch = nullptr, d.n_wg_batch = 0, d.max_wg_tiles = g.max_wg_tiles;
+    d.wave_meta = nullptr, d.wave_cells = nullptr, d.n_wave_wg = 0, d.max_wave_wg_cells = 0;
     d.inv_group = 1, d.inv_max_wg_tiles = g.max_wg_tiles, d.inv_max_wg_cells = g.max_wg_cells;
 }
 
@@ -243,6 +250,7 @@ hipError_t upload_tiling(std::vector<DevMem<void>> &bufs, const Geometry &g, Dev
     if ((e = upload(bufs, g.tiles, d.tiles)) || (e = upload(bufs, g.tile_cells, d.tile_cells)) || (e = upload(bufs, g.tile_meta, d.tile_meta)) ||
         (e = upload(bufs, g.wg_tiles, d.wg_tiles)) || (!inverse && (e = upload(bufs, g.wg_tiles_batch, d.wg_tiles_batch))))
         return e;
+    if (!inverse && !g.wave_cells.empty() && ((e = upload(bufs, g.wave_meta, d.wave_meta)) || (e = upload(bufs, g.wave_cells, d.wave_cells)))) return e;
     inverse ? fill_inverse_tiling(d, g) : fill_forward_tiling(d, g);
     return hipSuccess;
 }
@@ -318,6 +326,10 @@ int choose_forward_tiling(uint32_t width, uint32_t height, uint32_t channels, st
     // LDS budget of one forward tile buffer: 4 chunks of 16 bytes per thread for planes (the tuned variant), 6 for RGB
     tp.tile_buffer_bytes = k.tile_bytes > 0 ? k.tile_bytes : (channels == 1 ? 4 : 6) * 256 * 16;
     set_ranks(tp, k.ranks > 0 ? k.ranks : 4, cus, k);
+    // FRI_HIP_K1_WAVE=1: the wave form's share table beside the tiles, cut for FRI_HIP_K1_WAVE_WGS workgroups per CU (default four) from bands of
+    // FRI_HIP_K1_WAVE_BAND rows (default 16): any of the tuner's wave candidates can be pinned.
+    // A share that does not fit the wave kernel, like a launch the form does not serve, runs the tile kernel (launch_fwd_transform_quant).
+    if (k.k1_wave.value_or(0) > 0 && cus) tp.wave_ranks = std::min(k.k1_wave_wgs > 0 ? k.k1_wave_wgs : 4, fwd_wave_resident()), tp.wave_band_rows = std::max(k.k1_wave_band, 0);
     for (;;) {
         const std::string err = build_geometry(width, height, channels, tp, t.geo);
         if (!err.empty()) return err == "empty lattice" ? FRI_HIP_ERR_EMPTY_LATTICE : FRI_HIP_ERR_INVALID_ARGUMENT;
@@ -352,6 +364,7 @@ bool choose_inverse_tiling(uint32_t width, uint32_t height, uint32_t channels, s
     if (!cus || (k.inv_shared ? *k.inv_shared > 0 : fwd.geo.centers.size() >= kOwnInverseMaxCells)) return false;
     TilingParams &ti = inv.tp;
     ti = fwd.tp;
+    ti.wave_ranks = 0; // (the forward kernel's alone)
     set_ranks(ti, fwd.tp.ranks, cus, k); // (restores the dispatch-rank weights a many-shares forward tiling had flattened)
     ti.band_rows = k.inv_band_rows > 0 ? k.inv_band_rows : (channels == 1 ? 32 : 16);
     ti.cells_per_tile = k.cells_per_tile;
@@ -391,6 +404,12 @@ bool build_forward_candidate(const fri_hip_plan *p, FwdTiling &c) {
     if (!build_geometry(g0.width, g0.height, g0.channels, c.tp, c.geo).empty()) return false;
     if (c.geo.centers.size() != g0.centers.size()) return false;
     const int resident = fwd_resident(c.geo, g0.channels);
+    if (c.tp.wave_ranks > 0) { // the wave form beside the tiles: every share must fit the wave kernel, and the LDS the workgroups per CU the shares were cut for
+        DevicePlan d;
+        d.channels = (int32_t)g0.channels, d.width = (int32_t)g0.width;
+        fill_forward_tiling(d, c.geo);
+        if (!fwd_wave_fits(d) || c.tp.wave_ranks > fwd_wave_resident()) return false;
+    }
     return resident > 0 && resident >= c.tp.ranks; // the shares are sized for tp.ranks resident workgroups per CU
 }
 
@@ -406,8 +425,11 @@ void adopt_forward_tiling(fri_hip_plan *p, FwdTiling &c) {
     g.tiles.swap(c.geo.tiles), g.tile_cells.swap(c.geo.tile_cells), g.tile_meta.swap(c.geo.tile_meta), g.wg_tiles.swap(c.geo.wg_tiles), g.wg_tiles_batch.swap(c.geo.wg_tiles_batch);
     g.max_wg_tiles_batch = c.geo.max_wg_tiles_batch, g.lds_pitch = c.geo.lds_pitch, g.lds_rows = c.geo.lds_rows, g.band_rows = c.geo.band_rows, g.cells_per_tile = c.geo.cells_per_tile;
     g.cells_per_wg = c.geo.cells_per_wg, g.max_tile_cells = c.geo.max_tile_cells, g.max_wg_tiles = c.geo.max_wg_tiles, g.max_wg_cells = c.geo.max_wg_cells;
+    g.wave_meta.swap(c.geo.wave_meta), g.wave_cells.swap(c.geo.wave_cells);
+    g.wave_band_rows = c.geo.wave_band_rows, g.wave_ranks = c.geo.wave_ranks, g.max_wave_wg_cells = c.geo.max_wave_wg_cells;
     DevicePlan &d = p->dev;
     d.tiles = c.dev.tiles, d.tile_cells = c.dev.tile_cells, d.tile_meta = c.dev.tile_meta, d.wg_tiles = c.dev.wg_tiles, d.wg_tiles_batch = c.dev.wg_tiles_batch;
+    d.wave_meta = c.dev.wave_meta, d.wave_cells = c.dev.wave_cells;
     fill_forward_tiling(d, g);
     d.inv_max_wg_tiles = d.max_wg_tiles, d.inv_max_wg_cells = d.max_wg_cells; // (only read by an inverse kernel on the forward tiling; tunable plans have their own)
     for (auto &b : c.bufs) p->owned.push_back(std::move(b));
@@ -418,7 +440,9 @@ void adopt_forward_tiling(fri_hip_plan *p, FwdTiling &c) {
 
 std::string tiling_label(const TilingParams &tp, const Geometry &g) {
     char b[96];
-    std::snprintf(b, sizeof b, "%s/band%d/cells%d", tp.strided_shares ? "interleaved" : "contiguous", g.band_rows, g.cells_per_tile);
+    // the wave form is named by its own cut (bands, workgroups per CU): the tiles under it only serve the launches the form does not (include/fri_hip.h)
+    if (tp.wave_ranks > 0 && !g.wave_cells.empty()) std::snprintf(b, sizeof b, "wave/band%d/wg%d", g.wave_band_rows, g.wave_ranks);
+    else std::snprintf(b, sizeof b, "%s/band%d/cells%d", tp.strided_shares ? "interleaved" : "contiguous", g.band_rows, g.cells_per_tile);
     std::string l = b;
     if (tp.rank_weight[0] > 0) {
         std::snprintf(b, sizeof b, "/w%.2f-%.2f", tp.rank_weight[0], tp.rank_weight[std::max(0, std::min(tp.ranks, 4) - 1)]);
@@ -632,6 +656,7 @@ int fri_hip_plan_create(fri_hip_ctx *ctx, uint32_t width, uint32_t height, uint3
     p->own_inverse_tiling = choose_inverse_tiling(width, height, channels, cus, k, fwd, inv);
     p->geo = std::move(fwd.geo);
     p->fwd_tp = fwd.tp; // (fri_hip_plan_tune_forward starts from it)
+    if (!p->geo.wave_cells.empty()) p->fwd_tiling_note = tiling_label(fwd.tp, p->geo) + " (pinned: FRI_HIP_K1_WAVE)"; // what the tuner's report says it kept
     if (p->own_inverse_tiling) {
         p->geo_inv = std::move(inv.geo);
         // what the plan keeps of geo_inv on the host: the tiling and its lists (fri_hip_plan_inverse_lists reads their sizes); the lattice arrays are geo's
@@ -1784,6 +1809,7 @@ static int tune_forward(fri_hip_plan *p, uint32_t launches, std::string &rep) {
         if (strided >= 0) tp.strided_shares = strided != 0;
         if (band > 0) tp.band_rows = band;
         if (cells_delta) tp.cells_per_tile = g0.cells_per_tile + cells_delta;
+        if (!cand.empty()) tp.wave_ranks = 0; // the tile tilings compete first; the wave form is tried on the winner (third phase)
         add_tp(tp);
     };
     add(-1, 0, 0);
@@ -1894,6 +1920,35 @@ static int tune_forward(fri_hip_plan *p, uint32_t launches, std::string &rep) {
             for (size_t k : round2)
                 if (cand[k]->us < cand[b2]->us) b2 = k;
             if (cand[b2]->us < cand[best]->us * 0.99) best = b2; // (1 %: the winner of phase one was measured again in this phase, side by side)
+        }
+    }
+    // Third phase, planes: the kernel's wave form (k1_forward.hip: every wave stages and transforms pairs of cells on its own, no workgroup barrier) beside the
+    // winning tiling, with its shares cut for four or five workgroups per CU out of bands of 16 to 128 rows - measured together with the winner and kept only
+    // if it is more than 1.5 % faster. The tiles stay the winner's: they serve the launches the wave form does not (launch_fwd_transform_quant).
+    if (!rgb && g0.width % 16 == 0) { // (rows that do not start 16 bytes apart never run the form)
+        const TilingParams w = cand[best]->tp;
+        std::vector<size_t> round3{best};
+        const size_t n0 = cand.size();
+        // (4096^2, pinned plans side by side, us: bands of 16 / 48 / 72 / 96 / 112 / 128 rows with four workgroups per CU 19.2 / 18.9 / 18.4 / 17.8-18.0 / 17.8 / 17.9-18.1
+        // against 18.1-18.3 for the best tiles; five and six workgroups per CU 18.6-19.3 there, but first at 512^2 - profiles/k1_wave_form.txt)
+        for (int ranks : {4, 5})
+            for (int band : {16, 32, 72, 96, 112, 128}) {
+                if (ranks == 5 && band != 32 && band != 96) continue;
+                TilingParams tp = w;
+                tp.wave_ranks = ranks, tp.wave_band_rows = band;
+                add_tp(tp);
+                if (band >= (int)g0.height) break; // one band already: higher ones cut the same shares
+            }
+        for (size_t k = n0; k < cand.size(); k++) {
+            HIP_TRY(c, upload_forward_candidate(p, *cand[k]));
+            round3.push_back(k);
+        }
+        if (round3.size() > 1) {
+            HIP_TRY(c, measure(round3));
+            size_t b3 = best;
+            for (size_t k : round3)
+                if (cand[k]->us < cand[b3]->us) b3 = k;
+            if (cand[b3]->us < cand[best]->us * 0.985) best = b3;
         }
     }
     // How long each XCD's workgroups live under the winner (FwdArgs::xcd_stat; a diagnostic for the report: re-cutting the XCDs' shares in proportion was tried and

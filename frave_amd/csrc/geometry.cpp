@@ -186,6 +186,49 @@ void nearby_vectors(int depth, Int2 out[6]) {
     out[5] = zmd;
 }
 
+// The wave form's shares (geometry.hpp): the cells band-major, cut into one run per share. Share sh is run by workgroup b(sh) (the inverse of the kernels'
+// XCD-contiguous block -> share map, as for the tiles below), whose dispatch rank is b / CUs; a share's size in cells follows its rank's weight.
+static void build_wave_shares(const TilingParams &tp, Geometry &g) {
+    const size_t F = g.centers.size();
+    const int ranks = std::min(std::max(tp.wave_ranks, 1), 6), tile_ranks = std::min(std::max(tp.ranks, 1), 4);
+    const int band_rows = tp.wave_band_rows > 0 ? tp.wave_band_rows : 16;
+    const size_t cus = std::max<size_t>(1, (size_t)(tp.target_wgs > 0 ? tp.target_wgs : 1024) / tile_ranks);
+    g.wave_band_rows = band_rows, g.wave_ranks = ranks;
+    const int cy_min = g.centers.front().y;
+    std::vector<int32_t> order(F);
+    for (size_t k = 0; k < F; k++) order[k] = (int32_t)k;
+    std::sort(order.begin(), order.end(), [&](int32_t l, int32_t r) {
+        const int bl = (g.centers[l].y - cy_min) / band_rows, br = (g.centers[r].y - cy_min) / band_rows;
+        if (bl != br) return bl < br;
+        if (g.centers[l].x != g.centers[r].x) return g.centers[l].x < g.centers[r].x;
+        return g.centers[l].y < g.centers[r].y;
+    });
+    g.wave_meta.resize(F);
+    for (size_t k = 0; k < F; k++) g.wave_meta[k] = TileCell{g.centers[order[k]].x, g.centers[order[k]].y, order[k], g.interior[order[k]]};
+    // one share per resident workgroup, but no share without a pair of cells to work on
+    const size_t n_wg = std::max<size_t>(1, std::min(cus * ranks, (F + 1) / 2));
+    const bool weighted = tp.rank_weight[0] > 0 && tp.rank_weight[tile_ranks - 1] > 0;
+    auto weight = [&](size_t rank) {
+        if (!weighted || ranks == 1) return 1.0;
+        return (double)tp.rank_weight[0] + ((double)tp.rank_weight[tile_ranks - 1] - (double)tp.rank_weight[0]) * (double)rank / (double)(ranks - 1);
+    };
+    std::vector<double> cum(n_wg + 1, 0.0);
+    const size_t q = n_wg >> 3, r = n_wg & 7;
+    for (size_t x = 0, sh = 0; x < 8; x++) {
+        const size_t n_x = q + (x < r ? 1 : 0);
+        for (size_t idx = 0; idx < n_x; idx++, sh++) cum[sh + 1] = cum[sh] + weight(std::min<size_t>((idx * 8 + x) / cus, ranks - 1));
+    }
+    g.wave_cells.assign(n_wg + 1, 0);
+    for (size_t sh = 0; sh <= n_wg; sh++) g.wave_cells[sh] = (int32_t)((double)F * cum[sh] / cum[n_wg] + 0.5);
+    g.wave_cells[0] = 0;
+    g.wave_cells[n_wg] = (int32_t)F;
+    g.max_wave_wg_cells = 0;
+    for (size_t sh = 1; sh <= n_wg; sh++) { // every share keeps at least one cell (n_wg <= F)
+        g.wave_cells[sh] = (int32_t)std::min<size_t>(std::max<size_t>((size_t)g.wave_cells[sh], (size_t)g.wave_cells[sh - 1] + 1), F - (n_wg - sh));
+        g.max_wave_wg_cells = std::max(g.max_wave_wg_cells, g.wave_cells[sh] - g.wave_cells[sh - 1]);
+    }
+}
+
 const StaticTables &static_tables() {
     static const StaticTables t = make_static();
     return t;
@@ -499,6 +542,7 @@ std::string build_geometry(uint32_t width, uint32_t height, uint32_t channels, c
     while (((pitch / 4) % 32) != 8 && ((pitch / 4) % 32) != 24) pitch += 16;
     g.lds_pitch = pitch;
     g.lds_rows = max_r;
+    if (tp.wave_ranks > 0 && channels == 1) build_wave_shares(tp, g);
     return "";
 }
 

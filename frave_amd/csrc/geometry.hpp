@@ -84,6 +84,13 @@ struct Geometry {
     // per-workgroup start-up cost.
     std::vector<int32_t> wg_tiles_batch; // [n_wg_batch + 1]
     int32_t max_wg_tiles_batch = 0;
+    // The forward kernel's wave form (k1_forward.hip, fwd_wave_kernel; planes only): no tiles, a share is a run of cells. wave_meta holds all cells band-major (bands of
+    // wave_band_rows rows of centres, by x inside a band), share sh owns cells [wave_cells[sh], wave_cells[sh + 1]) of it and deals them to its four waves pair by
+    // pair (pair i of the share goes to wave i % 4), so the waves of a workgroup store adjacent cells at any moment. Empty unless TilingParams::wave_ranks is set.
+    std::vector<TileCell> wave_meta;  // [F]
+    std::vector<int32_t> wave_cells;  // [n_wave_wg + 1]
+    int32_t wave_band_rows = 0, wave_ranks = 0;
+    int32_t max_wave_wg_cells = 0;    // most cells in one share of the wave form
     std::vector<InvTileLists> inv_lists; // [n_tiles]; empty if the lists were not built (budget)
     std::vector<uint16_t> inv_quads, inv_dwords;
     std::vector<uint32_t> inv_parts;
@@ -119,6 +126,10 @@ struct TilingParams {
     // instead of sizing every buffer for them. 0 = no cap.
     int tile_buffer_bytes = 0;
     int batch_share_tiles = 0; // tiles' worth of cells per merged batch share (0 = 4)
+    // The wave form's cell-granular shares (Geometry::wave_cells), built next to the tiles when wave_ranks > 0 and the image is a plane: one share per resident
+    // workgroup with wave_ranks (4..6) workgroups per CU (the CU count is target_wgs / ranks), cut from bands of wave_band_rows rows (0 = 16). The dispatch-rank
+    // weights run linearly from rank_weight[0] to rank_weight[ranks - 1] over the wave_ranks ranks and apply to cells.
+    int wave_ranks = 0, wave_band_rows = 0;
     bool strided_shares = false; // deal the tiles to the shares round-robin (the resident set works on one sliding window of the image) instead of one contiguous run each
 };
 

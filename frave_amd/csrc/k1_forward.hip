@@ -683,6 +683,147 @@ __global__ void __launch_bounds__(kFwdThreads) fwd_transform_quant_kernel(const 
     }
 }
 
+// ---- the wave form: planes, FAST launches (aligned buffer, width % 16 == 0) ------------------------------------------------------------------------------------
+// The unit of progress is a wave's pair of cells, not a workgroup's tile: every wave stages the pixels of ITS pair into LDS slabs of its own and never waits for
+// another wave - no barrier anywhere. A cell's 512 leaves lie in a fixed box of 46 x 21 pixels around its centre (dx -15..+30, dy -8..+12: lane_dx + leaf_dx,
+// lane_dy + leaf_dy); with the lead-in to the 16-byte boundary below its first column (<= 15 bytes) a row of the box is four aligned 16-byte chunks, so a pair
+// is 2 x 21 x 4 = 168 chunks: at most three loads per lane, whose (item, row, chunk) are constants of the lane. In a FAST launch a chunk lies wholly inside or
+// wholly outside an image row; an outside chunk loads the image's first 16 bytes instead, and the leaves it would have held are masked like every leaf outside.
+// LDS: a pair's slab is 21 rows of 160 bytes - item A's 64 bytes, item B's 64, 32 bytes nobody reads (40 dwords = 8 mod 32: the bank rule of the tile form's
+// pitch). Two slabs per wave (double buffered): 26 880 bytes per workgroup, so the LDS holds six workgroups per CU.
+constexpr int kWavePitch = 160, kWaveRows = 21, kWaveItemBytes = 64;
+constexpr int kWaveSlab = kWaveRows * kWavePitch;        // one pair
+constexpr int kWaveItemChunks = kWaveRows * 4;           // 84
+constexpr int kWaveLoads = 3;                            // ceil(168 / 64)
+constexpr int kWaveLdsBytes = 2 * kFwdWaves * kWaveSlab; // 26 880
+constexpr int kWaveMaxWgCells = 64 * kFwdWaves;          // lane k of a wave keeps the record of the wave's k-th cell
+typedef u32x4 __attribute__((address_space(3))) *LdsQuadPtr;
+
+// A lane's part of the staging of a pair: where its chunks come from (relative to the box of item A or B) and where they go (relative to the slab).
+struct WaveChunks {
+    int row[kWaveLoads], k16[kWaveLoads]; // row of the box, 16 * chunk of the row
+    bool item_b[kWaveLoads], used[kWaveLoads];
+    uint32_t lds_off[kWaveLoads];
+};
+
+// grid = (shares, images), block = 256 (4 waves): share sh owns cells [wg_tiles[sh], wg_tiles[sh + 1]) of tile_meta (the plan's wave table, geometry.hpp) and
+// wave w takes its pairs w, w + 4, ...: while pair i is transformed out of one slab, pair i + 1's chunks are in flight in registers; they are committed to the
+// other slab before pair i's coefficient stores are issued - the tile form's load -> transform -> commit -> store order, per wave. The last iteration issues
+// its loads all the same, every lane's from the image's first bytes, instead of branching around them (see stage_issue: a load pending on one path around the
+// back edge costs a vmcnt(0) on every path).
+template <bool QID, bool MEASURE = false>
+__global__ void __launch_bounds__(kFwdThreads) fwd_wave_kernel(const FwdArgs a) {
+    __shared__ __attribute__((aligned(16))) uint8_t slabs[kWaveLdsBytes];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const uint32_t wg = xcd_contiguous_share(blockIdx.x, a.n_wg);
+    const int cb = a.wg_tiles[wg], ce = a.wg_tiles[wg + 1];
+    const unsigned long long t_entry = a.xcd_stat ? wall_clock64() : 0ull;
+    const int wg_pairs = (ce - cb + 1) >> 1;
+    const int n_pairs = wg_pairs > wave ? (wg_pairs - wave + kFwdWaves - 1) / kFwdWaves : 0;
+    if (n_pairs > 0) {
+        const uint8_t *img = a.pixels + (size_t)blockIdx.y * a.pixel_stride;
+        int32_t *coefs = a.coefs + (size_t)blockIdx.y * a.coef_stride;
+        // the records of the wave's cells, one per lane: cell 2 i + h of the wave is item h of its pair i, cell 2 (wave + 4 i) + h of the share. A lane past the
+        // share's end takes the share's last record, which makes item B of an odd last pair a mirror of item A (it is not stored).
+        const int mine = cb + 2 * (wave + kFwdWaves * (lane >> 1)) + (lane & 1);
+        const i32x4 rec = reinterpret_cast<const i32x4 *>(a.tile_meta)[min(mine, ce - 1)];
+        const uint32_t slab0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t *)slabs + (uint32_t)wave * (2u * kWaveSlab);
+
+        WaveChunks ch;
+#pragma unroll
+        for (int c = 0; c < kWaveLoads; c++) {
+            const int s = lane + 64 * c;
+            ch.used[c] = s < 2 * kWaveItemChunks;
+            ch.item_b[c] = s >= kWaveItemChunks;
+            const int w = ch.item_b[c] ? s - kWaveItemChunks : s;
+            ch.row[c] = ch.used[c] ? w >> 2 : 0;
+            ch.k16[c] = 16 * (w & 3);
+            // a lane without a chunk in slot c (lanes 40..63 of the last) commits what it loaded to 16 bytes of its own in the unread part of a row
+            ch.lds_off[c] = ch.used[c] ? (uint32_t)(ch.row[c] * kWavePitch + (ch.item_b[c] ? kWaveItemBytes : 0) + ch.k16[c])
+                                       : (uint32_t)(((s - 2 * kWaveItemChunks) >> 1) * kWavePitch + 2 * kWaveItemBytes + 16 * (s & 1));
+        }
+        const int ldx = lane_dx(lane), ldy = lane_dy(lane);
+        // the lane's three leaf windows (fetch_windows) relative to its item's 64 bytes of the slab's first row, the item's lead-in aside
+        const int wo0 = (ldy + 8) * kWavePitch + ldx + 15;
+        const int wo[3] = {wo0, wo0 + kWavePitch - 1, wo0 + 2 * kWavePitch - 1};
+
+        u32x4 st[kWaveLoads];
+        auto issue = [&](int pair, bool wanted) { // !wanted: the loads are issued all the same (no branch around them), every lane's from the image's first bytes
+            const int cxA = __builtin_amdgcn_readlane(rec.x, 2 * pair), cyA = __builtin_amdgcn_readlane(rec.y, 2 * pair);
+            const int cxB = __builtin_amdgcn_readlane(rec.x, 2 * pair + 1), cyB = __builtin_amdgcn_readlane(rec.y, 2 * pair + 1);
+            const int xA = (cxA - 15) & ~15, xB = (cxB - 15) & ~15; // the 16-byte boundary at or below the box's first column (the image base and every row are aligned)
+#pragma unroll
+            for (int c = 0; c < kWaveLoads; c++) {
+                const int x = (ch.item_b[c] ? xB : xA) + ch.k16[c], y = (ch.item_b[c] ? cyB : cyA) - 8 + ch.row[c];
+                const bool inside = wanted && ch.used[c] && (uint32_t)x < (uint32_t)a.width && (uint32_t)y < (uint32_t)a.height;
+                st[c] = *reinterpret_cast<const u32x4 *>(img + (inside ? (uint32_t)y * (uint32_t)a.width + (uint32_t)x : 0u));
+            }
+        };
+        auto commit = [&](uint32_t slab) {
+#pragma unroll
+            for (int c = 0; c < kWaveLoads; c++) *(LdsQuadPtr)(uintptr_t)(slab + ch.lds_off[c]) = st[c];
+        };
+        issue(0, true);
+        commit(slab0);
+
+        for (int i = 0; i < n_pairs; i++) {
+            const uint32_t cur = slab0 + (uint32_t)(i & 1) * kWaveSlab, nxt = slab0 + (uint32_t)((i & 1) ^ 1) * kWaveSlab;
+            issue(min(i + 1, n_pairs - 1), i + 1 < n_pairs); // in flight across the transform below
+            __builtin_amdgcn_s_setprio(3);
+            const int cxA = __builtin_amdgcn_readlane(rec.x, 2 * i), cyA = __builtin_amdgcn_readlane(rec.y, 2 * i);
+            const int cxB = __builtin_amdgcn_readlane(rec.x, 2 * i + 1), cyB = __builtin_amdgcn_readlane(rec.y, 2 * i + 1);
+            const uint32_t offA = (uint32_t)__builtin_amdgcn_readlane(rec.z, 2 * i) * kCell, offB = (uint32_t)__builtin_amdgcn_readlane(rec.z, 2 * i + 1) * kCell;
+            const int interior = __builtin_amdgcn_readlane(rec.w, 2 * i) & __builtin_amdgcn_readlane(rec.w, 2 * i + 1);
+            const bool store_b = cb + 2 * (wave + kFwdWaves * i) + 1 < ce;
+            const int baseA = (int)cur + ((cxA - 15) & 15), baseB = (int)cur + kWaveItemBytes + ((cxB - 15) & 15);
+            const int wbA[3] = {baseA + wo[0], baseA + wo[1], baseA + wo[2]}, wbB[3] = {baseB + wo[0], baseB + wo[1], baseB + wo[2]};
+            uint32_t wA[3], wB[3], maskA = 0xFFu, maskB = 0xFFu;
+            fetch_windows(wbA, wA);
+            fetch_windows(wbB, wB);
+            if (interior == 0) { // wave-uniform: a boundary cell in the pair - its leaves outside the image enter as 0
+                maskA = maskB = 0;
+#pragma unroll
+                for (int j = 0; j < 8; j++) {
+                    const int xa = cxA + ldx + leaf_dx(j), ya = cyA + ldy + leaf_dy(j), xb = cxB + ldx + leaf_dx(j), yb = cyB + ldy + leaf_dy(j);
+                    if (xa >= 0 && ya >= 0 && xa < a.width && ya < a.height) maskA |= 1u << j; // get_pixel, images.rs:90
+                    if (xb >= 0 && yb >= 0 && xb < a.width && yb < a.height) maskB |= 1u << j;
+                }
+                mask_windows(maskA, wA);
+                mask_windows(maskB, wB);
+            }
+            uint32_t leaf[8]; // window byte of leaf j: see fwd_transform_quant_kernel
+            leaf[0] = pair_bytes<0>(wA[0], wB[0]);
+            leaf[1] = pair_bytes<1>(wA[1], wB[1]);
+            leaf[2] = pair_bytes<0>(wA[1], wB[1]);
+            leaf[3] = pair_bytes<0>(wA[2], wB[2]);
+            leaf[4] = pair_bytes<2>(wA[0], wB[0]);
+            leaf[5] = pair_bytes<3>(wA[1], wB[1]);
+            leaf[6] = pair_bytes<2>(wA[1], wB[1]);
+            leaf[7] = pair_bytes<2>(wA[2], wB[2]);
+            int resA[8], resB[8];
+            fwd_wave_pk(leaf, lane, resA, resB);
+            __builtin_amdgcn_s_setprio(1);
+            uint32_t valid = 0xFFFFFFFFu;
+            if (interior == 0) valid = validity_tree_pk(maskA | (maskB << 16), lane);
+            commit(nxt);
+            __builtin_amdgcn_s_setprio(0);
+            if (__builtin_amdgcn_readfirstlane(valid == 0xFFFFFFFFu ? 1 : 0) && __all(valid == 0xFFFFFFFFu)) { // no None anywhere in the pair
+                store_item<0, false, QID, true>(coefs, offA, lane, resA, valid, a);
+                if (store_b) store_item<1, false, QID, true>(coefs, offB, lane, resB, valid, a);
+            } else {
+                store_item<0, true, QID, true>(coefs, offA, lane, resA, valid, a);
+                if (store_b) store_item<1, true, QID, true>(coefs, offB, lane, resB, valid, a);
+            }
+        }
+    }
+    if (a.xcd_stat && tid == 0) { // (as in the tile form; the workgroup's first wave speaks for it)
+        const uint32_t xcc = __builtin_amdgcn_s_getreg((3 << 11) | 20) & 7u;
+        (void)__hip_atomic_fetch_add(a.xcd_stat + 2 * xcc, wall_clock64() - t_entry, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        (void)__hip_atomic_fetch_add(a.xcd_stat + 2 * xcc + 1, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
 
 } // namespace
 
@@ -710,6 +851,11 @@ bool fwd_plan_fits(const DevicePlan &p) {
            (size_t)p.max_tile_cells * p.channels <= (size_t)kMaxItemsPerTile && p.max_tile_cells <= kFwdThreads &&
            p.max_wg_tiles <= kFwdThreads && fwd_lds_bytes(p) <= 160 * 1024;
 }
+
+bool fwd_wave_fits(const DevicePlan &p) {
+    return p.channels == 1 && p.n_wave_wg > 0 && p.max_wave_wg_cells > 0 && p.max_wave_wg_cells <= kWaveMaxWgCells && p.width >= 16;
+}
+int fwd_wave_resident() { return (160 * 1024) / kWaveLdsBytes; }
 
 hipError_t launch_fwd_transform_quant(const DevicePlan &p, uint32_t n_images, const uint8_t *pixels, size_t pixel_stride, int32_t *coefs,
                                       size_t coef_stride, const QMatrix &q, hipStream_t stream, bool cached_stores, int16_t *coefs16) {
@@ -749,6 +895,18 @@ hipError_t launch_fwd_transform_quant(const DevicePlan &p, uint32_t n_images, co
     const bool small = fwd_chunks(p) <= 4 * (size_t)kFwdThreads;           // 4 chunks per thread suffice (the common, tuned case)
     const bool rct = p.rct && p.channels == 3; // (fri_hip_plan_set_colour_transform refuses RCT on other plans)
     const bool ycc = p.ycc && p.channels == 3;  // (and YCbCr)
+    // The wave form, on a plan that carries its share table (the tuner measured it faster, or FRI_HIP_K1_WAVE=1 pinned it): what the tuner measures and nothing
+    // else - planes in FAST launches of a few images with nontemporal int32 stores. Batch launches (n_images >= 8), the chains' plain stores and compact planes,
+    // and the diagnostic builds' timelines and ablations keep the tile form.
+    if (fast && !plain && !coefs16 && n_images < 8 && !p.trace && !p.k1_ablate && fwd_wave_fits(p)) {
+        a.tile_meta = p.wave_meta;
+        a.wg_tiles = p.wave_cells;
+        a.n_wg = p.n_wave_wg;
+        void (*wk)(FwdArgs) = a.q_identity ? (p.k1_measuring ? fwd_wave_kernel<true, true> : fwd_wave_kernel<true>) : fwd_wave_kernel<false>;
+        (void)hipGetLastError();
+        hipLaunchKernelGGL(wk, dim3(a.n_wg, n_images), block, 0, stream, a);
+        return hipGetLastError();
+    }
     void (*kern)(FwdArgs);
 #define FRI_PICK_T(CH, E, FA, N, QI, R) (plain ? fwd_transform_quant_kernel<CH, E, FA, N, QI, false, false, false, R> : fwd_transform_quant_kernel<CH, E, FA, N, QI, true, false, false, R>)
 #define FRI_PICK_Q(CH, E, FA, N, R) (a.q_identity ? FRI_PICK_T(CH, E, FA, N, true, R) : FRI_PICK_T(CH, E, FA, N, false, R))

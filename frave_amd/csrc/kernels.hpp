@@ -19,6 +19,11 @@ struct DevicePlan {
     const int32_t *wg_tiles_batch = nullptr; // [n_wg_batch + 1] merged shares for launches over many images
     uint32_t n_wg_batch = 0;
     uint32_t n_wg = 0;
+    // K1's wave form (Geometry::wave_meta / wave_cells; null = the plan has none): launch_fwd_transform_quant runs it where it applies, see there
+    const TileCell *wave_meta = nullptr;  // [F] band-major
+    const int32_t *wave_cells = nullptr;  // [n_wave_wg + 1] cell range per workgroup share
+    uint32_t n_wave_wg = 0;
+    int32_t max_wave_wg_cells = 0;
     int32_t max_tile_cells = 0;
     bool covers_image = false;            // every pixel of the image is a leaf of a retained cell
     int32_t max_wg_tiles = 0;
@@ -291,6 +296,10 @@ size_t inv_lds_bytes(const DevicePlan &p);
 bool device_footprint_matches(const StaticTables &st);
 // True iff the plan's tiles fit the forward kernel's static register/LDS budget.
 bool fwd_plan_fits(const DevicePlan &p);
+// True iff the plan's tiling has the wave form's share table (n_wave_wg > 0) and every share fits the wave kernel (a wave keeps its cells' records in its 64 lanes).
+bool fwd_wave_fits(const DevicePlan &p);
+// Resident workgroups per CU of the wave kernel by its LDS (its registers allow as many).
+int fwd_wave_resident();
 constexpr size_t kInvListPad = 2048; // >= kInvListPre x kInvThreads of k3_inverse.hip
 bool inv_plan_fits(const DevicePlan &p, bool with_lists); // k3_inverse.hip: the inverse kernels' own limits (its tiling is its own since round 4)
 

@@ -1238,6 +1238,14 @@ int fri_hip_time_transform_quant_streams_dev(fri_hip_plan *plan, uint32_t n_imag
  * freed before it returns - large enough that every byte comes from HBM), keeps the fastest and remembers it for later plans of the same shape on the
  * same device in this process. Results never change; a plan whose tiling was pinned through the tuning environment, a host-only plan's, or one the
  * inverse kernel shares (>= 400 000 cells) is left alone. `report` (may be NULL): a JSON object with the candidates' microseconds per launch.
+ * The labels of the report ("winner", the keys of "candidates_us") name what ran:
+ *     interleaved|contiguous/band<R>/cells<N>[/w<first>-<last>]   the tile form: shares of tiles of N cells cut from bands of R rows, dealt round-robin or as runs
+ *     wave/band<R>/wg<K>[/w<first>-<last>]                        the wave form (planes whose width is a multiple of 16): no tiles, every wave of the kernel stages and
+ *                                                                 transforms its own pairs of cells; shares of cells cut from bands of R rows for K workgroups per CU
+ * (w: the shares' relative sizes by dispatch rank, first to last). Under a wave/ winner, single launches of fewer than eight 16-byte aligned images with the
+ * default (streaming) int32 coefficient stores run the wave form; batch launches of eight images or more, the encode chains and unaligned buffers keep the tile
+ * form on the tile tiling measured best. FRI_HIP_K1_WAVE=1 / 0 (with FRI_HIP_TUNING=1, read when the plan is created) pins the form on / off, and
+ * FRI_HIP_K1_WAVE_BAND / FRI_HIP_K1_WAVE_WGS its R and K; a pinned plan is left alone like any other.
  * Blocks for tens of milliseconds; call it once after fri_hip_plan_create, outside anything that is timed. Not thread-safe per plan. */
 int fri_hip_plan_tune_forward(fri_hip_plan *plan, uint32_t launches, char *report, size_t report_bytes);
 
