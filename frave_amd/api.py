@@ -57,6 +57,8 @@ SYMBOLS = [
     "fri_hip_preview_image_tiled_coded",
     "fri_hip_plan_tiled_regions", "fri_hip_merge_tiles_regions_dev", "fri_hip_decode_regions_tiled_dev", "fri_hip_decode_regions_tiled",
     "fri_hip_decode_regions_tiled_coded",
+    "fri_hip_plan_tiled420_regions", "fri_hip_merge_tiles420_regions_dev", "fri_hip_decode_regions_tiled420_dev", "fri_hip_decode_regions_tiled420",
+    "fri_hip_decode_regions_tiled420_coded",
     "fri_hip_plan_tiled_preview_regions", "fri_hip_preview_tiles_regions_dev", "fri_hip_preview_regions_tiled", "fri_hip_preview_regions_tiled_coded",
     "fri_hip_plan_tiled_rgba_create", "fri_hip_plan_tiled_rgba_destroy", "fri_hip_plan_tiled_rgba_colour", "fri_hip_plan_tiled_rgba_alpha", "fri_hip_plan_tiled_rgba_grid",
     "fri_hip_plan_tiled_rgba_region", "fri_hip_plan_tiled_rgba_buffer_tiles", "fri_hip_split_tiles_rgba_dev", "fri_hip_merge_tiles_rgba_dev",
@@ -286,6 +288,11 @@ def load_library():
     L.fri_hip_decode_image_tiled420.argtypes = [vp, vp, i32, vp]
     L.fri_hip_decode_region_tiled420_dev.argtypes = [vp, vp, i32, u32, u32, u32, u32, vp, vp]
     L.fri_hip_decode_region_tiled420.argtypes = [vp, vp, i32, u32, u32, u32, u32, vp]
+    L.fri_hip_plan_tiled420_regions.argtypes = [vp, u32, vp, vp, C.c_size_t, vp, vp, C.c_size_t]
+    L.fri_hip_merge_tiles420_regions_dev.argtypes = [vp, vp, vp, u32, u32, vp, vp, vp]
+    L.fri_hip_decode_regions_tiled420_dev.argtypes = [vp, vp, i32, u32, vp, vp, vp]
+    L.fri_hip_decode_regions_tiled420.argtypes = [vp, vp, i32, u32, vp, vp]
+    L.fri_hip_decode_regions_tiled420_coded.argtypes = [vp, u32, vp, vp, C.c_size_t, vp, vp, vp, vp, vp, i32, vp, vp]
     L.fri_hip_measure_distortion_tiled420_dev.argtypes = [vp, vp, vp, vp, vp, vp]
     L.fri_hip_estimate_size_tiled420_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.fri_hip_estimate_size_tiled420.argtypes = [vp, vp, vp, vp, vp]
@@ -1682,6 +1689,63 @@ class PlanTiled420:
         out = np.empty(w * h * 3, np.uint8)
         _check(load_library().fri_hip_decode_region_tiled420(self._h, _p(co), int(quality), x, y, w, h, _p(out)), "fri_hip_decode_region_tiled420", self.ctx)
         return out
+
+    # ---- several regions per call: the tile list, the 4:2:0 region table and K18 -----------------------
+    channels = 3  # of every raster this plan decodes (what PlanTiled's region helpers read)
+
+    def regions(self, regions):
+        """fri_hip_plan_tiled420_regions: (list uint32 [T], table uint32 [8 (R + 1) + nx ny]) of `regions` [(x, y, w, h), ...] - the strictly ascending file-grid
+        indices of the tiles at least one region touches, and the 4:2:0 region table K18 reads (include/fri_hip.h, "Several regions of tiled 4:2:0 files": strips
+        of 16 pixels; its row R holds the packed output's bytes in words 4, 5 and n_groups in word 6). Works on a host-only plan. FriHipError (-1) for no regions,
+        more than 65535, a region that is empty or leaves the image, n_groups >= 2^31. The plan remembers the last table it wrote: merge_tiles420_regions_dev
+        takes that one."""
+        return PlanTiled._regions_table(self, "fri_hip_plan_tiled420_regions", (), PlanTiled._regions(regions))
+
+    def merge_tiles420_regions_dev(self, d_y_tiles, d_c_tiles, n_list, n_regions, d_table, d_out, stream=0):
+        """fri_hip_merge_tiles420_regions_dev (K18 alone), device pointers as ints: the tile-list planes y_tiles [T][tile_h][tile_w] and c_tiles [T][2][ch][cw] ->
+        the packed region rasters [h][w][3]. d_table must be, in device memory, the table regions() LAST returned on this plan, n_list and n_regions its T and R.
+        Only enqueues; capturable."""
+        _check(load_library().fri_hip_merge_tiles420_regions_dev(self._h, d_y_tiles, d_c_tiles, int(n_list), int(n_regions), d_table, d_out, stream),
+               "fri_hip_merge_tiles420_regions_dev", self.ctx)
+
+    def decode_regions_tiled420_dev(self, d_coefs, quality, regions, d_out, stream=0):
+        """fri_hip_decode_regions_tiled420_dev: d_coefs int32, the listed tiles' planes in plane order with n = T -> d_out, the packed region rasters, device
+        pointers: the inverse kernels over the listed tiles into the plan's tile buffers, then K18. `regions` is host memory. Refuses a capturing stream."""
+        rg = PlanTiled._regions(regions)
+        _check(load_library().fri_hip_decode_regions_tiled420_dev(self._h, d_coefs, int(quality), rg.shape[0], _p(rg), d_out, stream), "fri_hip_decode_regions_tiled420_dev",
+               self.ctx)
+
+    def decode_regions_tiled420(self, coefs, quality, regions):
+        """fri_hip_decode_regions_tiled420: coefs int32 in plane order with n = T (what emit.tiled_decode_tiles returns for regions()'s list) -> a list of uint8
+        [h][w][3] arrays, one per region: each the crop [y : y + h, x : x + w] of what decode_image_tiled420 returns for the same file."""
+        rg = PlanTiled._regions(regions)
+        tiles, table = self.regions(rg)
+        co = np.ascontiguousarray(coefs, np.int32).reshape(-1)
+        assert co.size == tiles.size * self.tile_coef_count
+        out = np.empty(PlanTiled._packed_bytes(table, rg.shape[0]), np.uint8)
+        _check(load_library().fri_hip_decode_regions_tiled420(self._h, _p(co), int(quality), rg.shape[0], _p(rg), _p(out)), "fri_hip_decode_regions_tiled420", self.ctx)
+        return PlanTiled._split_regions(self, out, rg)
+
+    def decode_regions_coded(self, coded, quality, regions):
+        """fri_hip_decode_regions_tiled420_coded: the coded planes of regions()'s tile list in plane order with n = T - what emit.tiled_parse_coded_tiles returns,
+        with or without its TiledInfo - through the device decoder (K13) on both lattices, the inverse kernels and K18 -> (a list of uint8 [h][w][3] arrays, status
+        uint32 [3 T][4]); the arrays are decode_regions_tiled420's of emit.tiled_decode_tiles's planes. A plane the decoder refuses raises FriHipError (-1) with
+        the status as .status and the file-grid index of the first refused plane's tile as .tile. Needs set_stream_order()."""
+        rg = PlanTiled._regions(regions)
+        tiles, table = self.regions(rg)
+        n, planes = tiles.size, 3 * tiles.size
+        words, n_words, models, off, vp, wp = _coded_planes(coded, planes)
+        out = np.empty(PlanTiled._packed_bytes(table, rg.shape[0]), np.uint8)
+        status = np.zeros((planes, 4), np.uint32)
+        rc = load_library().fri_hip_decode_regions_tiled420_coded(self._h, rg.shape[0], _p(rg), _p(words), words.shape[1], _p(n_words), _p(models), _p(off), _p(vp), _p(wp),
+                                                                  int(quality), _p(out), _p(status))
+        try:
+            _check_decode(rc, "fri_hip_decode_regions_tiled420_coded", self.ctx, status)
+        except FriHipError as e:
+            bad = np.flatnonzero(status[:, 0])
+            e.tile = int(tiles[bad[0] if bad[0] < n else (bad[0] - n) // 2]) if bad.size else None
+            raise
+        return PlanTiled._split_regions(self, out, rg), status
 
     def encode_image_tiled420_coded(self, pixels, quality, word_stride=None):
         """fri_hip_encode_image_tiled420_coded: the tiled 4:2:0 chain with the fit, then the device rANS coder over the luma batch and the chroma batch - (words

@@ -149,16 +149,6 @@ bool plan_regions(const fri_hip_plan_tiled *p, uint32_t n_regions, const uint32_
 bool plan_preview_regions(const fri_hip_plan_tiled *p, uint32_t shift, uint32_t n_regions, const uint32_t *regions, RegionsPlan &out) {
     return build_region_table(p->grid, p->channels, (int)std::min(shift, 5u), n_regions, regions, out);
 }
-// fri_hip_plan_tiled[_preview]_regions behind the builder: the size query, or the list and the table out and the table remembered in `memory`
-int write_regions_plan(const RegionsPlan &r, uint32_t n_regions, uint32_t shift, Planned &memory, uint32_t *list, size_t list_cap, size_t *n_list, uint32_t *table,
-                       size_t table_cap_words) {
-    *n_list = r.list.size();
-    if (!list || list_cap < r.list.size() || !table || table_cap_words < r.table.size()) return -3; // the size query (the emitter's code for a buffer that is too small)
-    std::copy(r.list.begin(), r.list.end(), list);
-    std::copy(r.table.begin(), r.table.end(), table);
-    remember(memory, n_regions, shift, r);
-    return FRI_HIP_OK;
-}
 
 /* ---- what the decodes' host and coded forms share ---- */
 // The way up of a host form: the plan's coefficient buffer grown to `count`, the caller's coefficients in it.

@@ -1,5 +1,5 @@
 // fri_hip_tiled420.cpp -- the tiled 4:2:0 plan kind of the C ABI (fri_hip_plan_tiled420: include/fri_hip.h): the plan and its grid, the fused split and merge,
-// the encode chain and its coded form (K11), the image and region decodes, the measure, the size estimate and the quality searches. Host-side glue like
+// the encode chain and its coded form (K11), the image and region decodes, several regions in one call (K18), the measure, the size estimate and the quality searches. Host-side glue like
 // fri_hip.cpp, on two ordinary plans. The grid, plan creation, the host size estimate and the coded route are tiled_common.hpp's, shared with fri_hip_tiled.cpp
 // (the coded route runs two batches here); the searches are Tiled420Search on search_scaffold.hpp.
 #include "search_scaffold.hpp"
@@ -33,6 +33,9 @@ struct fri_hip_plan_tiled420 {
     Grown<uint32_t> rans_counts;      // ... n_words [3 n], then status [3 n][4], then models [3 n][10][4]
     Grown<uint16_t> rans_off;         // ... [3 n][10][1024]
     Grown<uint8_t> rans_scratch;      // ... and its scratch, the larger of the two batches'
+    Grown<uint32_t> region_table;     // fri_hip_decode_regions_tiled420*: the 4:2:0 region table, 8 (R + 1) + nx ny words
+    Grown<uint8_t> regions_out;       // fri_hip_decode_regions_tiled420[_coded]: the packed region rasters
+    Planned planned;                  // what the last table fri_hip_plan_tiled420_regions wrote was made for (fri_hip_merge_tiles420_regions_dev)
     size_t n_tiles() const { return grid.n_tiles(); }
     size_t raster_bytes() const { return (size_t)grid.width * grid.height * 3; }
     size_t y_bytes() const { return (size_t)grid.tile_w * grid.tile_h; }
@@ -49,6 +52,11 @@ int inverse_tiled420(fri_hip_plan_tiled420 *p, uint32_t n, const int32_t *d_coef
     HIP_TRY(p->ctx, launch_inverse_transform(il, n, d_coefs, p->y_coefs(), q, d_y, p->y_bytes(), s));
     HIP_TRY(p->ctx, launch_inverse_transform(ic, 2 * n, d_coefs + (size_t)n * p->y_coefs(), p->c_coefs(), q, d_c, p->c_bytes(), s));
     return FRI_HIP_OK;
+}
+
+// K18's region table on the plan's grid (region_table.hpp): K15's builder with strips of 16 pixels
+bool plan_regions420(const fri_hip_plan_tiled420 *p, uint32_t n_regions, const uint32_t *regions, RegionsPlan &out) {
+    return build_region_table(p->grid, 3, -1, n_regions, regions, out, StripUnit::Pixels);
 }
 
 // the chain of fri_hip_encode_symbols_tiled420_dev behind its split: the two batches with quality_matrix(quality), outputs in plane order
@@ -273,6 +281,71 @@ int fri_hip_decode_image_tiled420(fri_hip_plan_tiled420 *p, const int32_t *coefs
     return fri_hip_decode_region_tiled420(p, coefs, quality, 0, 0, p->grid.width, p->grid.height, pixels);
 }
 
+/* ---- several regions per call: the tile list, the 4:2:0 region table and K18 ---- */
+int fri_hip_plan_tiled420_regions(fri_hip_plan_tiled420 *p, uint32_t n_regions, const uint32_t *regions, uint32_t *list, size_t list_cap, size_t *n_list, uint32_t *table,
+                                  size_t table_cap_words) {
+    RegionsPlan r;
+    if (!p || !n_list || !plan_regions420(p, n_regions, regions, r)) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    return write_regions_plan(r, n_regions, 0, p->planned, list, list_cap, n_list, table, table_cap_words);
+}
+
+int fri_hip_merge_tiles420_regions_dev(fri_hip_plan_tiled420 *p, const uint8_t *d_y_tiles, const uint8_t *d_c_tiles, uint32_t n_list, uint32_t n_regions, const uint32_t *d_table,
+                                       uint8_t *d_out, void *stream) {
+    if (!p || !d_y_tiles || !d_c_tiles || !d_table || !d_out || !n_list || n_list > p->n_tiles() || !n_regions || n_regions > 65535u) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    if (int rc = need_device(p)) return rc;
+    if (p->planned.n_regions != n_regions || p->planned.n_list != n_list) {
+        p->ctx->last_error = "fri_hip_merge_tiles420_regions_dev: d_table must hold the table fri_hip_plan_tiled420_regions last wrote on this plan (n_regions or n_list differ)";
+        return FRI_HIP_ERR_INVALID_ARGUMENT;
+    }
+    HIP_TRY(p->ctx, launch_merge_tiles420_regions(d_y_tiles, d_c_tiles, p->grid.tile_w, p->grid.tile_h, p->grid.nx, n_regions, p->planned.n_groups, d_table, d_out, (hipStream_t)stream));
+    return FRI_HIP_OK;
+}
+
+int fri_hip_decode_regions_tiled420_dev(fri_hip_plan_tiled420 *p, const int32_t *d_coefs, int quality, uint32_t n_regions, const uint32_t *regions, uint8_t *d_out, void *stream) {
+    RegionsPlan r;
+    int32_t qm[32];
+    QMatrix q;
+    if (!p || !d_coefs || !d_out || !plan_regions420(p, n_regions, regions, r) || quality_q(quality, qm, q)) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    if (int rc = need_device(p)) return rc;
+    fri_hip_ctx *c = p->ctx;
+    const hipStream_t s = (hipStream_t)stream;
+    if (int rc = refuse_capture(p->luma.get(), s, "fri_hip_decode_regions_tiled420_dev grows the plan's tile and table buffers: it cannot be captured into a HIP graph")) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t n = r.list.size(); // the listed tiles: the buffers grow to the regions' tiles, never to the image's
+    int rc;
+    if ((rc = grow(c, p->y_tiles, n * p->y_bytes())) || (rc = grow(c, p->c_tiles, 2 * n * p->c_bytes())) || (rc = grow(c, p->region_table, r.table.size()))) return rc;
+    // the table goes up in stream order; the wait is for the source, which is this call's own memory (a few KiB, ahead of everything this call enqueues)
+    HIP_TRY(c, hipMemcpyAsync(p->region_table, r.table.data(), r.table.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    remember(p->planned, n_regions, 0, r);
+    if ((rc = inverse_tiled420(p, (uint32_t)n, d_coefs, q, p->y_tiles, p->c_tiles, s))) return rc;
+    HIP_TRY(c, launch_merge_tiles420_regions(p->y_tiles, p->c_tiles, p->grid.tile_w, p->grid.tile_h, p->grid.nx, n_regions, r.n_groups, p->region_table, d_out, s));
+    return FRI_HIP_OK;
+}
+
+namespace {
+// the tail of the host and the coded form: the packed-output buffer grown, the _dev form on the null stream from p->coefs, the rasters down
+int regions420_down(fri_hip_plan_tiled420 *p, const RegionsPlan &r, int quality, uint32_t n_regions, const uint32_t *regions, uint8_t *pixels) {
+    fri_hip_ctx *c = p->ctx;
+    int rc;
+    if ((rc = grow(c, p->regions_out, (size_t)r.total)) || (rc = fri_hip_decode_regions_tiled420_dev(p, p->coefs, quality, n_regions, regions, p->regions_out, nullptr))) return rc;
+    HIP_TRY(c, hipMemcpy(pixels, p->regions_out, (size_t)r.total, hipMemcpyDeviceToHost));
+    return FRI_HIP_OK;
+}
+} // namespace
+
+int fri_hip_decode_regions_tiled420(fri_hip_plan_tiled420 *p, const int32_t *coefs, int quality, uint32_t n_regions, const uint32_t *regions, uint8_t *pixels) {
+    RegionsPlan r;
+    if (!p || !coefs || !pixels || quality < 1 || quality > 99 || !plan_regions420(p, n_regions, regions, r)) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    if (int rc = need_device(p)) return rc;
+    fri_hip_ctx *c = p->ctx;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t count = r.list.size() * (p->y_coefs() + 2 * p->c_coefs());
+    if (int rc = grow(c, p->coefs, count)) return rc;
+    HIP_TRY(c, hipMemcpy(p->coefs, coefs, count * sizeof(int32_t), hipMemcpyHostToDevice));
+    return regions420_down(p, r, quality, n_regions, regions, pixels);
+}
+
 /* ---- the measure, the size estimate and the searches over subsampled tiles ---- */
 int fri_hip_measure_distortion_tiled420_dev(fri_hip_plan_tiled420 *p, const uint8_t *d_y_tiles, const uint8_t *d_c_tiles, const uint8_t *d_reference_rgb, uint64_t *d_out,
                                             void *stream) {
@@ -369,6 +442,37 @@ int fri_hip_decode_image_tiled420_coded(fri_hip_plan_tiled420 *p, const uint32_t
     if ((rc = fri_hip_decode_region_tiled420_dev(p, p->coefs, quality, 0, 0, p->grid.width, p->grid.height, p->region, nullptr))) return rc;
     HIP_TRY(c, hipMemcpy(pixels, p->region, bytes, hipMemcpyDeviceToHost));
     return FRI_HIP_OK;
+}
+
+/* ---- the coded decode of several regions: K13 over the T luma planes, then over the 2 T chroma planes, in front of the inverse kernels and K18 ---- */
+int fri_hip_decode_regions_tiled420_coded(fri_hip_plan_tiled420 *p, uint32_t n_regions, const uint32_t *regions, const uint32_t *words, size_t word_stride, const uint32_t *n_words,
+                                          const uint32_t *models, const uint16_t *off_values, const float *value_params, const float *width_params, int quality, uint8_t *pixels,
+                                          uint32_t *status) {
+    RegionsPlan r;
+    const CodedPlanes in{words, word_stride, n_words, models, off_values, value_params, width_params};
+    if (!p || !in.complete() || !pixels || !status || quality < 1 || quality > 99 || !plan_regions420(p, n_regions, regions, r)) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    if (int rc = need_device(p)) return rc;
+    if (!p->luma->d_stream_order || !p->chroma->d_stream_order) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    fri_hip_ctx *c = p->ctx;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t n = r.list.size(), planes = 3 * n;
+    if (!decode_counts_ok((uint32_t)(2 * n))) return FRI_HIP_ERR_INVALID_ARGUMENT;
+    int rc;
+    if ((rc = grow(c, p->coefs, n * (p->y_coefs() + 2 * p->c_coefs())))) return rc;
+    CodedOnDevice d;
+    if ((rc = upload_coded(p, in, planes, p->rans_words_y, d)) || (rc = decode_coded_batch(p->luma.get(), d, 0, n, p->coefs, p->y_coefs())) ||
+        (rc = decode_coded_batch(p->chroma.get(), d, n, 2 * n, p->coefs + n * p->y_coefs(), p->c_coefs())))
+        return rc;
+    rc = read_back_decode_status(c, d, status);
+    for (size_t k = 0; k < planes && rc == FRI_HIP_ERR_INVALID_ARGUMENT; k++)
+        if (status[4 * k]) { // the first refused plane, in plane order with n = T: named by its tile's index in the file's grid
+            const size_t t = k < n ? k : (k - n) / 2, channel = k < n ? 0 : 1 + (k - n) % 2;
+            c->last_error = std::string(__func__) + ": tile " + std::to_string(r.list[t]) + ": channel " + std::to_string(channel) + ": the device decoder refused the plane (status " +
+                            std::to_string(status[4 * k]) + ")";
+            break;
+        }
+    if (rc) return rc;
+    return regions420_down(p, r, quality, n_regions, regions, pixels);
 }
 
 } // extern "C"

@@ -16,17 +16,18 @@
 // measure_tiles420_kernel: the whole-image merge's walk with nothing stored - each pixel is compared with the reference raster's and only seven sums leave the kernel
 // (several strips per lane on large images, wave reduction, LDS, one 64-bit atomic per sum and workgroup).
 //
-// The 4:2:0 arithmetic, the region strip locator and measure_add are raster_common.hpp's, shared with K8 and K10; the launch geometry is raster_launch.hpp's. No raster has a
+// The 4:2:0 arithmetic, the region strip locator and measure_add are raster_common.hpp's, shared with K8 and K10; the merge's strip and pixel within a tile are
+// tiles420_merge.hpp's, shared with K18 (k18_regions420.hip); the launch geometry is raster_launch.hpp's. No raster has a
 // row pitch and every buffer starts at any byte. Every byte offset is 64-bit. Split and merge use no LDS and no atomics; every kernel only enqueues and can be
 // captured into a graph.
 #include "raster_common.hpp"
 #include "raster_launch.hpp"
+#include "tiles420_merge.hpp"
 
 namespace fri {
 namespace {
 
 constexpr int kT420Threads = kRasterThreads;
-constexpr int kT420Strip = (int)kRasterStrip; // pixels of a row per lane
 
 struct SplitTiles420Args {
     const uint8_t *rgb;
@@ -124,43 +125,6 @@ __global__ void __launch_bounds__(kT420Threads) split_tiles420_kernel(const Spli
     else split_tile_strip<false>(p, t, jc, x0);
 }
 
-// the header's inverse formula from Cb and Cr
-__device__ __forceinline__ void tile_ycc_to_rgb(int Y, int cbv, int crv, int &R, int &G, int &B) { ycc_to_rgb(Y, cbv - 128, crv - 128, R, G, B); }
-
-// 16 pixels of tile row ty from tile column tx (tx & 1 == ODD), all inside the tile row: tx + 16 <= tile_w
-template <int ODD>
-__device__ __forceinline__ void merge_tile_strip(const MergeTiles420Args &p, const uint8_t *y_tile, const uint8_t *c_tile, int tx, int ty, uint8_t *dst) {
-    const int ch = (int)p.ch, cw = (int)p.cw;
-    const int j = ty >> 1, j2 = (ty & 1) ? min(j + 1, ch - 1) : max(j - 1, 0);
-    int vb[kT420Strip / 2 + 2], vr[kT420Strip / 2 + 2];
-    load_chroma<true>(c_tile, cw, j, j2, tx >> 1, vb);
-    load_chroma<true>(c_tile + (uint64_t)ch * cw, cw, j, j2, tx >> 1, vr);
-    const u32x4 yv = load_unaligned<u32x4>(y_tile + (uint64_t)ty * p.tile_w + tx);
-    const uint32_t yw[4] = {yv.x, yv.y, yv.z, yv.w};
-    uint32_t px[12];
-#pragma unroll
-    for (int i = 0; i < 12; i++) px[i] = 0;
-#pragma unroll
-    for (int k = 0; k < kT420Strip; k++) {
-        const int m = 1 + ((k + ODD) >> 1), n = ((k + ODD) & 1) ? m + 1 : m - 1; // the column's own sample and its neighbour on the pixel's side
-        int R, G, B;
-        tile_ycc_to_rgb(byte_of(yw, k), (3 * vb[m] + vb[n] + 8) >> 4, (3 * vr[m] + vr[n] + 8) >> 4, R, G, B);
-        put_rgb(px, k, R, G, B);
-    }
-#pragma unroll
-    for (int q = 0; q < 3; q++) {
-        const u32x4 v = {px[4 * q], px[4 * q + 1], px[4 * q + 2], px[4 * q + 3]};
-        store_unaligned(dst + 16 * q, v);
-    }
-}
-
-// one pixel (tx, ty) of a tile: inverse steps 2 - 3 by the header's formula
-__device__ __forceinline__ void merge_tile_pixel(const MergeTiles420Args &p, const uint8_t *y_tile, const uint8_t *c_tile, int tx, int ty, uint8_t *dst) {
-    int R, G, B;
-    upsample_pixel(y_tile, c_tile, p.tile_w, (int)p.cw, (int)p.ch, tx, ty, R, G, B);
-    dst[0] = (uint8_t)R, dst[1] = (uint8_t)G, dst[2] = (uint8_t)B;
-}
-
 // item g = strip g % n_strips of region row g / n_strips
 __global__ void __launch_bounds__(kT420Threads) merge_tiles420_region_kernel(const MergeTiles420Args p) {
     const uint32_t g = blockIdx.x * kT420Threads + threadIdx.x;
@@ -172,12 +136,13 @@ __global__ void __launch_bounds__(kT420Threads) merge_tiles420_region_kernel(con
     const uint64_t s = (uint64_t)b * p.ni + a;
     const uint8_t *y_tile = p.y + s * y_stride, *c_tile = p.c + s * c_stride;
     uint8_t *dst = p.out + ((uint64_t)ry * p.w + rx0) * 3;
+    const TileShape420 tile{p.tile_w, p.tile_h, p.cw, p.ch};
     if (n == (uint32_t)kT420Strip && tx + kT420Strip <= p.tile_w) {
-        if (tx & 1) merge_tile_strip<1>(p, y_tile, c_tile, (int)tx, (int)ty, dst);
-        else merge_tile_strip<0>(p, y_tile, c_tile, (int)tx, (int)ty, dst);
+        if (tx & 1) merge_tile_strip<1>(tile, y_tile, c_tile, (int)tx, (int)ty, dst);
+        else merge_tile_strip<0>(tile, y_tile, c_tile, (int)tx, (int)ty, dst);
     } else { // the strip crosses a tile column, or is the row's last
         for (uint32_t k = 0; k < n; k++) {
-            merge_tile_pixel(p, y_tile, c_tile, (int)tx, (int)ty, dst + 3 * k);
+            merge_tile_pixel(tile, y_tile, c_tile, (int)tx, (int)ty, dst + 3 * k);
             if (++tx == p.tile_w) tx = 0, y_tile += y_stride, c_tile += c_stride; // the same row of the next tile
         }
     }

@@ -274,6 +274,13 @@ hipError_t launch_merge_tiles420_region(const uint8_t *y_tiles, const uint8_t *c
 // counted). The caller zeroes sums with launch_clear_sums. Both inputs are only read.
 hipError_t launch_measure_tiles420(const uint8_t *y_tiles, const uint8_t *c_tiles, uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, const uint8_t *reference,
                                    unsigned long long *sums, hipStream_t stream);
+// K18 (k18_regions420.hip): the merge for several regions of a tiled 4:2:0 image in one launch (include/fri_emit.h, "Several regions of tiled 4:2:0 files").
+// y_tiles [T][tile_h][tile_w] and c_tiles [T][2][ch][cw]: the tile-list planes; table: the 4:2:0 region table on the device - rows [n_regions + 1][8], then
+// slot[ny nx] - as the host wrote it, n_groups its row R's word 6; out: the packed region rasters [h_r][w_r][3], any alignment. n_groups workgroups of 256 lanes;
+// no atomics, no LDS, only enqueues. hipErrorInvalidValue for a NULL pointer, a zero size, a tile side past 2^30 - 1, n_regions = 0 or > 65535, n_groups = 0 or
+// >= 2^31. The table's contents are not checked: they are read on the device.
+hipError_t launch_merge_tiles420_regions(const uint8_t *y_tiles, const uint8_t *c_tiles, uint32_t tile_w, uint32_t tile_h, uint32_t nx, uint32_t n_regions, uint32_t n_groups,
+                                         const uint32_t *table, uint8_t *out, hipStream_t stream);
 
 // K16 (k16_tiles_rgba.hip): the raster kernels of tiled RGBA coding (include/fri_hip.h has the format). Split: interleaved R, G, B, A [H][W][4] -> colour_tiles
 // [n][tile_h][tile_w][3] and alpha_tiles [n][tile_h][tile_w], n = ny nx: K9's split and K10's edge replication of both rasters in one pass; clean: a pixel with

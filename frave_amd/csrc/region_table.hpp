@@ -1,5 +1,5 @@
 // region_table.hpp -- the tile grid of the tiled plan kinds and what several regions make on it, on the host: the sub-grid and the covered rectangle of a region,
-// the thumbnail's size, and the one builder of the region tables K15 and K17 read, with the tile list, n_groups and the packed output's bytes. Plain C++ with no
+// the thumbnail's size, and the one builder of the region tables K15, K17 and K18 read, with the tile list, n_groups and the packed output's bytes. Plain C++ with no
 // HIP in it (tests/tools/region_table_check.cpp compiles it alone); of the project it takes the error codes of fri_hip.h and the strip constants of
 // raster_launch.hpp.
 #pragma once
@@ -43,7 +43,7 @@ inline int preview_size(uint32_t width, uint32_t height, uint32_t shift, uint32_
     return FRI_HIP_OK;
 }
 
-/* ---- several regions per call: the tile list and the region table of K15 (image coordinates) and K17 (thumbnail coordinates) ---- */
+/* ---- several regions per call: the tile list and the region table of K15 and K18 (image coordinates) and K17 (thumbnail coordinates) ---- */
 // What R regions make on a grid (include/fri_hip.h, "Several regions" and "Preview of regions"): the tile list, the region table - rows
 // {x, y, w, h, off_lo, off_hi, first_group, word 7} for r < R, row R with the totals, then slot[nx ny] -, its n_groups and the packed output's bytes.
 struct RegionsPlan {
@@ -64,12 +64,16 @@ inline void finish_regions_plan(RegionsPlan &out, uint32_t n_regions, size_t n_g
 }
 
 constexpr uint32_t kPreviewBlock = 16; // a workgroup of K17 writes a block of 16 x 16 samples of one region
+// what a strip of 16 units counts in a table of image rectangles: bytes of a region row (K15) or pixels of it (K18, whose lane writes the 48 bytes of 16 pixels)
+enum class StripUnit { Bytes, Pixels };
 
 // The table of `n_regions` rectangles {x, y, w, h}. shift < 0: rectangles of the image, K15's table - a workgroup takes 256 strips of 16 bytes of a region's
-// rows, word 7 is 0; the grid's width must hold width C <= 2^31 - 1. shift 0..4: rectangles of the thumbnail at `shift`, K17's table - a rectangle marks the
+// rows, word 7 is 0; the grid's width must hold width C <= 2^31 - 1 - or, with unit = Pixels, K18's: the same rows with strips of 16 pixels, so that groups_r =
+// ceil(h_r ceil(w_r / 16) / 256) while off_r stays in bytes (w_q h_q C). shift 0..4: rectangles of the thumbnail at `shift`, K17's table - a rectangle marks the
 // tiles of its source rectangle, the image pixels from its first sample to its last; a workgroup takes a block of samples, word 7 is the blocks per row.
 // false for R = 0, R > 65535, shift > 4, a rectangle that is empty or leaves the image or the thumbnail, and n_groups >= 2^31.
-inline bool build_region_table(const TileGrid &g, uint32_t channels, int shift, uint32_t n_regions, const uint32_t *regions, RegionsPlan &out) {
+inline bool build_region_table(const TileGrid &g, uint32_t channels, int shift, uint32_t n_regions, const uint32_t *regions, RegionsPlan &out,
+                               StripUnit unit = StripUnit::Bytes) {
     const bool preview = shift >= 0;
     uint32_t bound[2] = {g.width, g.height}; // what a rectangle lies in
     if (!regions || !n_regions || n_regions > 65535u) return false;
@@ -90,8 +94,8 @@ inline bool build_region_table(const TileGrid &g, uint32_t channels, int shift, 
         }
         if (g.region(src[0], src[1], src[2], src[3], range)) return false;
         for (uint32_t b = 0; b < range[3]; b++) std::fill_n(slot + ((size_t)range[1] + b) * g.nx + range[0], range[2], 1u); // touched
-        // of one row: a lane of K15 owns a strip of its bytes, a workgroup of K17 a block of its samples
-        const uint64_t per_row = preview ? raster::ceil_div(q[2], kPreviewBlock) : raster::strips_of((uint64_t)q[2] * channels);
+        // of one row: a lane of K15 owns a strip of its bytes, a lane of K18 a strip of its pixels, a workgroup of K17 a block of its samples
+        const uint64_t per_row = preview ? raster::ceil_div(q[2], kPreviewBlock) : raster::strips_of(unit == StripUnit::Pixels ? (uint64_t)q[2] : (uint64_t)q[2] * channels);
         uint32_t *row = out.table.data() + 8 * (size_t)r;
         row[0] = q[0], row[1] = q[1], row[2] = q[2], row[3] = q[3];
         row[4] = (uint32_t)off, row[5] = (uint32_t)(off >> 32), row[6] = (uint32_t)groups, row[7] = preview ? (uint32_t)per_row : 0;

@@ -60,6 +60,17 @@ int create_tiled_plan(fri_hip_ctx *ctx, uint32_t width, uint32_t height, uint32_
     return FRI_HIP_OK;
 }
 
+// fri_hip_plan_tiled[420][_preview]_regions behind the builder: the size query, or the list and the table out and the table remembered in `memory`
+inline int write_regions_plan(const RegionsPlan &r, uint32_t n_regions, uint32_t shift, Planned &memory, uint32_t *list, size_t list_cap, size_t *n_list, uint32_t *table,
+                              size_t table_cap_words) {
+    *n_list = r.list.size();
+    if (!list || list_cap < r.list.size() || !table || table_cap_words < r.table.size()) return -3; // the size query (the emitter's code for a buffer that is too small)
+    std::copy(r.list.begin(), r.list.end(), list);
+    std::copy(r.table.begin(), r.table.end(), table);
+    remember(memory, n_regions, shift, r);
+    return FRI_HIP_OK;
+}
+
 // The host form of fri_hip_estimate_size_tiled*: `planes` histograms (and counts, if given) up, the _dev form `dev` on the null stream, the file's bytes and, if
 // asked for, the tiles' bytes down. P holds the buffers under the same names in both kinds.
 template <typename P, typename Dev>

@@ -46,6 +46,9 @@
 //                                                            (FRIDecoder::decode_preview_regions: only the first L = 9 - 2 M levels of the tiles that the regions'
 //                                                            source rectangles touch are entropy-decoded, one launch for all regions, K17); refused as above, and for
 //                                                            a tiled RGBA file, M outside 1..4 and a region that leaves the thumbnail
+//                                                            --420: the file is a tiled 4:2:0 file (FRIDecoder::decode_regions420: the listed tiles' planes in plane
+//                                                            order, the inverse kernels over them, one merge launch, K18), with or without --device-rans; refused with
+//                                                            nothing written: a file that is not tiled 4:2:0, and --preview
 //   fri_driver update-file <in.frv> <new.pgm|.ppm|.bmp> <out.frv> --region X,Y,W,H   the tiles of the `frit` file in.frv that the rectangle touches are coded anew from
 //                                                            the image, which has the file's size and channels; every other tile's bytes are copied
 //                                                            (libfri::update_bytes_tiled: fri_hip_encode_region_tiled_symbols + fri_tiled_update_from_streams). No mode
@@ -844,7 +847,7 @@ int main(int argc, char **argv) {
         return encode_image_to_file(std::move(img), fw, fh, fc, file_opts, argv[3]);
     }
     if (argc >= 2 && std::string(argv[1]) == "decode-regions") {
-        const char *usage = "decode-regions <in.frv> <out_prefix> [--preview M] --region X,Y,W,H [--region X,Y,W,H ...] [--device-rans]";
+        const char *usage = "decode-regions <in.frv> <out_prefix> [--preview M | --420] --region X,Y,W,H [--region X,Y,W,H ...] [--device-rans]";
         if (argc < 4) {
             std::fprintf(stderr, "%s\n", usage);
             return 2;
@@ -852,10 +855,12 @@ int main(int argc, char **argv) {
         std::vector<libfri::emit::Region> regions;
         libfri::EncoderOpts dec_opts;
         unsigned preview = 0; // preview M: 1..4, 0 = none; the regions are then in the thumbnail's coordinates
+        bool s420 = false;    // --420: a tiled 4:2:0 file, K18
         for (int i = 4; i < argc; i++) {
             char tail = 0;
             unsigned rx = 0, ry = 0, rw = 0, rh = 0;
             if (std::string(argv[i]) == "--device-rans") dec_opts.device_rans = true;
+            else if (std::string(argv[i]) == "--420") s420 = true;
             else if (std::string(argv[i]) == "--preview" && i + 1 < argc && std::sscanf(argv[i + 1], "%u%c", &preview, &tail) == 1 && preview >= 1 && preview <= 4) i++;
             else if (std::string(argv[i]) == "--region" && i + 1 < argc && std::sscanf(argv[i + 1], "%u,%u,%u,%u%c", &rx, &ry, &rw, &rh, &tail) == 4) regions.push_back({rx, ry, rw, rh}), i++;
             else {
@@ -865,6 +870,10 @@ int main(int argc, char **argv) {
         }
         if (regions.empty()) {
             std::fprintf(stderr, "decode-regions: no --region given (%s); decode-file decodes the whole image\n", usage);
+            return 2;
+        }
+        if (s420 && preview) {
+            std::fprintf(stderr, "decode-regions: --420 has no --preview (the preview of regions of a tiled 4:2:0 file is out of scope): decode the regions with --420 and scale them down\n");
             return 2;
         }
         std::vector<uint8_t> bytes;
@@ -877,7 +886,9 @@ int main(int argc, char **argv) {
             return 1;
         }
         // (every refusal comes before anything is written)
-        auto out = preview ? libfri::FRIDecoder().decode_preview_regions(bytes, preview, regions, dec_opts) : libfri::FRIDecoder().decode_regions(bytes, regions, dec_opts);
+        auto out = s420      ? libfri::FRIDecoder().decode_regions420(bytes, regions, dec_opts)
+                   : preview ? libfri::FRIDecoder().decode_preview_regions(bytes, preview, regions, dec_opts)
+                             : libfri::FRIDecoder().decode_regions(bytes, regions, dec_opts);
         if (!out.ok) {
             std::fprintf(stderr, "%s\n", out.error.c_str());
             return 1;
@@ -897,6 +908,7 @@ int main(int argc, char **argv) {
             std::printf("%s: %ux%ux%u decoded\n", name.c_str(), img.metadata.width, img.metadata.height, ch);
         }
         if (preview) std::printf("preview of regions (K17): thumbnail scale 1/%u, %u of 9 levels decoded\n", 1u << preview, 9 - 2 * preview);
+        if (s420) std::printf("several regions of a tiled 4:2:0 file (K18)\n");
         if (dec_opts.device_rans) std::printf("rANS decoder on the device (K13) over the regions' tiles\n");
         return 0;
     }
@@ -974,7 +986,7 @@ int main(int argc, char **argv) {
         return 0;
     }
     if (argc < 5) {
-        std::fprintf(stderr, "usage: %s roundtrip|encode|batch|batch-frv <width> <height> <channels> [n_images | out.frv]\n       %s encode-file <in.pgm|in.ppm|in.bmp|in.pam> <out.frv> [--rct | [--ycbcr | --420] (--quality Q | --psnr DB | --ssim S | --size BYTES | --bpp B)] [--clean-alpha] [--tile-size T [--device-rans]]\n       %s encode-file <in.ppm|in.bmp> <out.frv> --tile-size-420 T (--quality Q | --target psnr=DB|ssim=S|size=BYTES|bpp=B) [--device-rans]   (tiled 4:2:0; --tile-size T --420 stays refused: the option of its own is this one)\n       %s decode-file <in.frv> <out.pgm|out.ppm|out.bmp|out.pam> [--region X,Y,W,H | --device-rans | --preview M [--device-rans]]\n       %s decode-regions <in.frv> <out_prefix> --region X,Y,W,H [--region X,Y,W,H ...] [--device-rans]\n       %s update-file <in.frv> <new.pgm|new.ppm|new.bmp> <out.frv> --region X,Y,W,H\n", argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
+        std::fprintf(stderr, "usage: %s roundtrip|encode|batch|batch-frv <width> <height> <channels> [n_images | out.frv]\n       %s encode-file <in.pgm|in.ppm|in.bmp|in.pam> <out.frv> [--rct | [--ycbcr | --420] (--quality Q | --psnr DB | --ssim S | --size BYTES | --bpp B)] [--clean-alpha] [--tile-size T [--device-rans]]\n       %s encode-file <in.ppm|in.bmp> <out.frv> --tile-size-420 T (--quality Q | --target psnr=DB|ssim=S|size=BYTES|bpp=B) [--device-rans]   (tiled 4:2:0; --tile-size T --420 stays refused: the option of its own is this one)\n       %s decode-file <in.frv> <out.pgm|out.ppm|out.bmp|out.pam> [--region X,Y,W,H | --device-rans | --preview M [--device-rans]]\n       %s decode-regions <in.frv> <out_prefix> [--preview M | --420] --region X,Y,W,H [--region X,Y,W,H ...] [--device-rans]\n       %s update-file <in.frv> <new.pgm|new.ppm|new.bmp> <out.frv> --region X,Y,W,H\n", argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
         return 2;
     }
     const std::string cmd = argv[1];

@@ -339,9 +339,14 @@ class FRIDecoder { // decoder.rs:44-59
     // decode returns. The container is walked once and every tile that at least one region touches is entropy-decoded once - fri_tiled_decode_tiles's workers - then
     // one inverse launch over those tiles and one merge launch for all regions (fri_hip_decode_regions_tiled, K15). With opts.device_rans the listed tiles' planes
     // are decoded on the device instead (fri_tiled_parse_coded_tiles, then fri_hip_decode_regions_tiled_coded). Regions may overlap and repeat. Refused, saying what
-    // to use instead: a `frif` file (decode_region crops it), a tiled 4:2:0 file (decode_region, one rectangle per call), no region, more than 65535 and a region
+    // to use instead: a `frif` file (decode_region crops it), a tiled 4:2:0 file (decode_regions420, or decode_region, one rectangle per call), no region, more than 65535 and a region
     // that is empty or leaves the image.
     Result<std::vector<RasterImage>> decode_regions(const std::vector<uint8_t> &data, const std::vector<emit::Region> &regions, const EncoderOpts &opts = EncoderOpts());
+    // Several regions of a tiled 4:2:0 file in one call (include/fri_emit.h, "Several regions of tiled 4:2:0 files"): decode_regions' walk with the listed tiles'
+    // planes in plane order - fri_tiled_decode_tiles's workers, then fri_hip_decode_regions_tiled420 (the inverse kernels over the listed tiles, K18); with
+    // opts.device_rans, fri_tiled_parse_coded_tiles and fri_hip_decode_regions_tiled420_coded. Region r is the crop [y : y + h, x : x + w] of what decode returns.
+    // Refused: a file that is not tiled 4:2:0 (decode_regions takes the others), no region, more than 65535 and a region that is empty or leaves the image.
+    Result<std::vector<RasterImage>> decode_regions420(const std::vector<uint8_t> &data, const std::vector<emit::Region> &regions, const EncoderOpts &opts = EncoderOpts());
     // The thumbnail of a tiled file (include/fri_hip.h, "Preview decode"): shift m is 0..4, the raster is ceil(W / 2^m) x ceil(H / 2^m), sample (Y, X) the pixel
     // (min(Y S + S / 2, H - 1), min(X S + S / 2, W - 1)), S = 2^m, of the image whose detail below level L = 9 - 2 m is 0. Only the first L levels of every tile are
     // entropy-decoded: fri_tiled_decode_levels's workers, then fri_hip_preview_image_tiled - with opts.device_rans, fri_hip_preview_image_tiled_coded (K13 bounded by

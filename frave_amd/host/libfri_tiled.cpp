@@ -143,7 +143,7 @@ static Result<std::vector<RasterImage>> decode_regions_at(const std::vector<uint
     if (std::string e = emit::parse_tiled(data.data(), data.size(), ti, offset); !e.empty()) return failed(r, e);
     if (ti.s420)
         return failed(r, preview ? "the preview of regions of a tiled 4:2:0 file is out of scope: decode one rectangle per call with decode_region (decode-file --region) and scale it down"
-                            : "several regions of a tiled 4:2:0 file are out of scope: decode one rectangle per call with decode_region (decode-file --region)");
+                            : "several regions of a tiled 4:2:0 file go through decode_regions420 (decode-regions --420), or decode one rectangle per call with decode_region (decode-file --region)");
     if (ti.alpha)
         return failed(r, preview ? "the preview of regions of a tiled RGBA file is out of scope: decode one rectangle per call with decode_region (decode-file --region) and scale it down"
                             : "several regions of a tiled RGBA file are out of scope: decode one rectangle per call with decode_region (decode-file --region)");
@@ -206,6 +206,62 @@ static Result<std::vector<RasterImage>> decode_regions_at(const std::vector<uint
 
 Result<std::vector<RasterImage>> FRIDecoder::decode_regions(const std::vector<uint8_t> &data, const std::vector<emit::Region> &regions, const EncoderOpts &opts) {
     return decode_regions_at(data, regions, opts, -1);
+}
+
+// several regions of a tiled 4:2:0 file (K18): decode_regions_at's walk with the planes in plane order, n = T, on the tiled 4:2:0 plan at the file's quality
+Result<std::vector<RasterImage>> FRIDecoder::decode_regions420(const std::vector<uint8_t> &data, const std::vector<emit::Region> &regions, const EncoderOpts &opts) {
+    Result<std::vector<RasterImage>> r;
+    if (data.size() >= 4 && std::memcmp(data.data(), "frif", 4) == 0)
+        return failed(r, "an ordinary `frif` file has no tiles to choose from: decode it whole, or crop one rectangle with decode_region (decode-file --region)");
+    emit::TiledInfo ti;
+    std::vector<uint64_t> offset;
+    if (std::string e = emit::parse_tiled(data.data(), data.size(), ti, offset); !e.empty()) return failed(r, e);
+    if (!ti.s420) return failed(r, "not a tiled 4:2:0 file: decode_regions (decode-regions without --420) decodes several regions of every other tiled file");
+    if (regions.empty() || regions.size() > 65535) return failed(r, "several regions: give 1 to 65535 regions");
+    std::vector<uint32_t> list, flat;
+    if (!emit::regions_tiles(ti.width, ti.height, ti.tile_w, ti.tile_h, regions.data(), regions.size(), list)) return failed(r, "invalid region");
+    size_t total = 0;
+    for (const emit::Region &g : regions) flat.insert(flat.end(), {g.x, g.y, g.w, g.h}), total += (size_t)g.w * g.h * 3;
+    const emit::TileList tiles{list.data(), list.size()};
+    // the host's part: the listed tiles' planes decoded on the workers, or - device_rans - their coded planes copied out; both in plane order with n = T
+    std::vector<int32_t> coefs;
+    CodedPlanes cp;
+    if (opts.device_rans) {
+        if (std::string e = load_coded(data, ti, &tiles, cp); !e.empty()) return failed(r, e);
+    } else {
+        bool too_small = false;
+        std::string e = emit::decode_tiled(data.data(), data.size(), 0, ti, nullptr, 0, too_small, nullptr, nullptr, -1, &tiles); // header, table, geometry
+        if (!e.empty()) return failed(r, e);
+        coefs.resize(list.size() * ((size_t)ti.n_cells + 2 * (size_t)ti.n_cells_chroma) * FRI_HIP_CELL_SIZE);
+        e = emit::decode_tiled(data.data(), data.size(), 0, ti, coefs.data(), coefs.size(), too_small, nullptr, nullptr, -1, &tiles);
+        if (!e.empty() || too_small) return failed(r, e.empty() ? kNotTheTileGeometry : e);
+    }
+    Device dev(opts.device);
+    if (!dev.ok()) return failed(r, dev.error());
+    auto p = open_tiled420(dev, ti.width, ti.height, ti.tile_w, ti.tile_h, FRI_HIP_TILED_ALLOW_HOLES, opts.device_rans ? nullptr : &ti);
+    for (fri_hip_plan *inner : {p.a, p.b})
+        if (p.error.empty() && opts.device_rans) p.error = set_plan_stream_order(inner, dev);
+    if (!p.error.empty()) return failed(r, p.error);
+    std::vector<uint8_t> packed(total);
+    const int rc = opts.device_rans ? fri_hip_decode_regions_tiled420_coded(p.plan.get(), (uint32_t)regions.size(), flat.data(), cp.words.data(), cp.stride, cp.n_words.data(),
+                                                                            cp.models.data(), cp.off.data(), cp.vp.data(), cp.wp.data(), (int)ti.quality, packed.data(), cp.status.data())
+                                    : fri_hip_decode_regions_tiled420(p.plan.get(), coefs.data(), (int)ti.quality, (uint32_t)regions.size(), flat.data(), packed.data());
+    if (rc != FRI_HIP_OK) { // a refused plane is named by its tile in the file's grid
+        const size_t n = list.size();
+        const std::string e = refused_decode(cp.status.data(), cp.status.size() / 4, [&](size_t k) { return k < n ? tile_channel(list[k], 0) : tile_channel(list[(k - n) / 2], 1 + (k - n) % 2); });
+        return failed(r, e.empty() ? dev.describe(rc) : e);
+    }
+    size_t at = 0;
+    for (const emit::Region &g : regions) {
+        RasterImage img;
+        img.metadata = ImageMetadata{g.h, g.w, ColorSpace::RGB};
+        const size_t bytes = (size_t)g.w * g.h * 3;
+        img.data.assign(packed.begin() + at, packed.begin() + at + bytes);
+        at += bytes;
+        r.value.push_back(std::move(img));
+    }
+    r.ok = true;
+    return r;
 }
 
 Result<std::vector<RasterImage>> FRIDecoder::decode_preview_regions(const std::vector<uint8_t> &data, uint32_t shift, const std::vector<emit::Region> &regions,

@@ -97,8 +97,25 @@
  *                       row R: {0, 0, 0, 0, total low, total high, n_groups, 0}
  *                       then slot[ny nx], with 0xFFFFFFFF for a tile that is not in the list
  *                     The table is 8 (R + 1) + nx ny words long. Refused: R = 0, R > 65535 and n_groups >= 2^31.
- * Out of scope: regions of tiled 4:2:0 files on the device (K12's region merge with a slot table is a follow-up; the host functions here return such a file's
- * planes in plane order with n = T); several regions in region update; regions of `frif` files. Several regions at reduced scale are "Preview of regions" below.
+ * Out of scope: several regions in region update; regions of `frif` files. Several regions at reduced scale are "Preview of regions" below.
+ *
+ * Several regions of tiled 4:2:0 files (K18, k18_regions420.hip; the host side is the functions of "Several regions", which return such a file's planes in
+ * plane order with n = T; the device side is fri_hip_decode_regions_tiled420, include/fri_hip.h): many rectangles of one tiled 4:2:0 file in one call. The input
+ * is R >= 1 regions r = (x, y, w, h), `regions` uint32 [R][4] in host memory, each by the rules of "Region decode"; regions may overlap and may repeat.
+ *   tile list         the "Several regions" tile list, unchanged (fri_tiled_regions_tiles). slot(t) = k for list[k] = t.
+ *   tile-list arrays  plane order with n = T: the tile rasters y_tiles [T][tile_h][tile_w] and c_tiles [T][2][ch][cw]; the coefficients [T][F_y][512], then
+ *                     [T][2][F_c][512], in one buffer; coded planes [3 T] - plane(k, Y) = k, plane(k, Cb) = T + 2 k, plane(k, Cr) = T + 2 k + 1 for list entry k.
+ *   packed output     region r is a raster [h_r][w_r][3] without a pitch; it sits at byte off_r = sum_{q<r} 3 w_q h_q of one buffer, and off_R is the total.
+ *   result            by definition region r is the crop [y : y + h, x : x + w] of what fri_hip_decode_image_tiled420 returns for the file. Every pixel is
+ *                     upsampled within its own tile: no replicated pixel and no sample of another tile is read.
+ *   region table 4:2:0  the layout of the "Several regions" table. A group is 256 lanes, and a lane owns 16 pixels (48 output bytes) of one row of one region.
+ *                       groups_r = ceil(h_r ceil(w_r / 16) / 256)
+ *                       rows r = 0..R-1 of 8 words: {x, y, w, h, off_r low, off_r high, first_group_r = sum_{q<r} groups_q, 0}
+ *                       row R: {0, 0, 0, 0, total low, total high, n_groups, 0}
+ *                       then slot[ny nx], with 0xFFFFFFFF for a tile that is not in the list
+ *                     The table is 8 (R + 1) + nx ny words long. Refused: R = 0, R > 65535, n_groups >= 2^31 and 3 W > 2^31 - 1. This is NOT the "Several regions"
+ *                     table with C = 3: that table's strips are counted in bytes (ceil(3 w_r / 16) a row), this one's in pixels, so first_group and n_groups differ.
+ * Out of scope: preview of regions of tiled 4:2:0 files; tiled RGBA files; region update.
  *
  * Preview of regions (fri_tiled_preview_regions_tiles, fri_tiled_decode_tiles_levels below; the device side is fri_hip_preview_regions_tiled and K17,
  * include/fri_hip.h): many rectangles of one file at reduced scale. L, m, S = 2^m, w' x h', P_L and the thumbnail are those of "Preview decode" (include/fri_hip.h;

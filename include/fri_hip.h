@@ -705,8 +705,25 @@ int fri_hip_decode_region_tiled(fri_hip_plan_tiled *p, const int32_t *coefs, con
  * filled, nothing decoded further, and fri_hip_last_hip_error naming the first such plane by its tile's index in the file's grid ("tile t: channel c: ..."). The inner
  * plan needs its stream order. Synchronous.
  * All: FRI_HIP_ERR_INVALID_ARGUMENT for a NULL pointer, a bad region and a bad R; FRI_HIP_ERR_NO_DEVICE on a host-only plan for everything that computes.
- * Out of scope: regions of tiled 4:2:0 files on the device (K12's region merge with a slot table); several regions in region update. Several regions at reduced
- * scale are "Preview of regions" below. */
+ * Out of scope: several regions in region update. Several regions at reduced scale are "Preview of regions" below; several regions of a tiled 4:2:0 file are
+ * "Several regions of tiled 4:2:0 files" below (the entry points are declared with the tiled 4:2:0 plan).
+ *
+ * Several regions of tiled 4:2:0 files (K18, k18_regions420.hip; fri_hip_plan_tiled420_regions and fri_hip_decode_regions_tiled420* below, with the tiled 4:2:0 plan): many rectangles of one tiled 4:2:0 file in one call. The input is R >= 1 regions
+ * r = (x, y, w, h), `regions` uint32 [R][4] in host memory, each by the rules of "Region decode"; regions may overlap and may repeat.
+ *   tile list         the "Several regions" tile list, unchanged (fri_tiled_regions_tiles). slot(t) = k for list[k] = t.
+ *   tile-list arrays  plane order with n = T: the tile rasters y_tiles [T][tile_h][tile_w] and c_tiles [T][2][ch][cw]; the coefficients [T][F_y][512], then
+ *                     [T][2][F_c][512], in one buffer; coded planes [3 T] - plane(k, Y) = k, plane(k, Cb) = T + 2 k, plane(k, Cr) = T + 2 k + 1 for list entry k.
+ *   packed output     region r is a raster [h_r][w_r][3] without a pitch; it sits at byte off_r = sum_{q<r} 3 w_q h_q of one buffer, and off_R is the total.
+ *   result            by definition region r is the crop [y : y + h, x : x + w] of what fri_hip_decode_image_tiled420 returns for the file. Every pixel is
+ *                     upsampled within its own tile: no replicated pixel and no sample of another tile is read.
+ *   region table 4:2:0  the layout of the "Several regions" table. A group is 256 lanes, and a lane owns 16 pixels (48 output bytes) of one row of one region.
+ *                       groups_r = ceil(h_r ceil(w_r / 16) / 256)
+ *                       rows r = 0..R-1 of 8 words: {x, y, w, h, off_r low, off_r high, first_group_r = sum_{q<r} groups_q, 0}
+ *                       row R: {0, 0, 0, 0, total low, total high, n_groups, 0}
+ *                       then slot[ny nx], with 0xFFFFFFFF for a tile that is not in the list
+ *                     The table is 8 (R + 1) + nx ny words long. Refused: R = 0, R > 65535, n_groups >= 2^31 and 3 W > 2^31 - 1. This is NOT the "Several regions"
+ *                     table with C = 3: that table's strips are counted in bytes (ceil(3 w_r / 16) a row), this one's in pixels, so first_group and n_groups differ.
+ * Out of scope: preview of regions of tiled 4:2:0 files; tiled RGBA files; region update. */
 int fri_hip_plan_tiled_regions(fri_hip_plan_tiled *p, uint32_t n_regions, const uint32_t *regions, uint32_t *list, size_t list_cap, size_t *n_list, uint32_t *table,
                                size_t table_cap_words);
 int fri_hip_merge_tiles_regions_dev(fri_hip_plan_tiled *p, const uint8_t *d_tiles, uint32_t n_list, uint32_t n_regions, const uint32_t *d_table, uint8_t *d_out, void *stream);
@@ -864,6 +881,39 @@ int fri_hip_decode_image_tiled420(fri_hip_plan_tiled420 *p, const int32_t *coefs
 int fri_hip_decode_region_tiled420_dev(fri_hip_plan_tiled420 *p, const int32_t *d_coefs, int quality, uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint8_t *d_region,
                                        void *stream);
 int fri_hip_decode_region_tiled420(fri_hip_plan_tiled420 *p, const int32_t *coefs, int quality, uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint8_t *pixels);
+/* Several regions of a tiled 4:2:0 file in one call (K18; "Several regions of tiled 4:2:0 files" above has the definitions bit for bit).
+ * fri_hip_plan_tiled420_regions: host only, works on host-only plans. Writes the tile list (*n_list = T) and the 4:2:0 region table. The return values and the -3
+ * size query are those of fri_hip_plan_tiled_regions: -3 with *n_list filled and nothing else written when list is NULL, list_cap < T, table is NULL or
+ * table_cap_words < 8 (R + 1) + nx ny. The plan remembers R, T and n_groups of the last table it wrote: the kernel's launch has n_groups workgroups and the host
+ * alone knows that.
+ * fri_hip_merge_tiles420_regions_dev (K18's merge_tiles420_regions_kernel alone): d_y_tiles [T][tile_h][tile_w] and d_c_tiles [T][2][ch][cw], the tile-list planes
+ * -> d_out, the packed region rasters. One launch of n_groups workgroups of 256 lanes; a workgroup belongs to exactly one region, which it finds by a search over
+ * first_group; a full strip inside one tile row is merged as fri_hip_merge_tiles420_region_dev merges it, in both parities of its first column, a strip that crosses
+ * a tile column and a row's last strip pixel by pixel; every output byte is written once; no atomics, no LDS, every offset 64-bit; only enqueues on `stream`, can be
+ * captured into a graph; any pointer alignment. d_table must be, in device memory, the table fri_hip_plan_tiled420_regions LAST wrote on this plan, n_list and
+ * n_regions the T and R of that call: the entry checks the pointers, n_list <= nx ny and that R and T are the remembered ones - on a mismatch it returns
+ * FRI_HIP_ERR_INVALID_ARGUMENT and launches nothing - and cannot check the words themselves: a table from anywhere else makes the kernel read and write out of bounds.
+ * fri_hip_decode_regions_tiled420_dev: d_coefs int32 in plane order with n = T (what fri_tiled_decode_tiles returns for the file, in device memory) -> d_out. Builds
+ * the table, grows the plan's tile buffers to T tiles - never to the image's size - and a plan-owned table buffer, uploads the table on `stream` (and waits for that
+ * small copy), runs the inverse kernel with the midpoint dequantiser on the luma plan over T planes and on the chroma plan over 2 T planes at `quality`, then K18, all
+ * on `stream`. A capturing stream is refused (FRI_HIP_ERR_INVALID_ARGUMENT) before anything is enqueued or allocated.
+ * fri_hip_decode_regions_tiled420: the host form - coefs and the packed rasters `pixels` (off_R bytes) are host memory. Synchronous.
+ * fri_hip_decode_regions_tiled420_coded: the coded planes of the tile list go up (what fri_tiled_parse_coded_tiles returns: the layouts of
+ * fri_hip_decode_image_tiled420_coded with 3 T planes in plane order), K13 runs over the T luma planes and the 2 T chroma planes, then the inverse kernels, then K18;
+ * the packed rasters come back. status uint32 [3 T][4] goes to the caller; a plane the decoder refuses makes the call FRI_HIP_ERR_INVALID_ARGUMENT with the status
+ * filled, no pixel written, and fri_hip_last_hip_error naming the first such plane by its tile's index in the file's grid ("tile t: channel c: ..."). Both inner
+ * plans need their stream order. Synchronous.
+ * All: FRI_HIP_ERR_INVALID_ARGUMENT for a NULL pointer, a bad region, a bad R and a quality outside 1..99; FRI_HIP_ERR_NO_DEVICE on a host-only plan for everything
+ * that computes. */
+int fri_hip_plan_tiled420_regions(fri_hip_plan_tiled420 *p, uint32_t n_regions, const uint32_t *regions, uint32_t *list, size_t list_cap, size_t *n_list, uint32_t *table,
+                                  size_t table_cap_words);
+int fri_hip_merge_tiles420_regions_dev(fri_hip_plan_tiled420 *p, const uint8_t *d_y_tiles, const uint8_t *d_c_tiles, uint32_t n_list, uint32_t n_regions, const uint32_t *d_table,
+                                       uint8_t *d_out, void *stream);
+int fri_hip_decode_regions_tiled420_dev(fri_hip_plan_tiled420 *p, const int32_t *d_coefs, int quality, uint32_t n_regions, const uint32_t *regions, uint8_t *d_out, void *stream);
+int fri_hip_decode_regions_tiled420(fri_hip_plan_tiled420 *p, const int32_t *coefs, int quality, uint32_t n_regions, const uint32_t *regions, uint8_t *pixels);
+int fri_hip_decode_regions_tiled420_coded(fri_hip_plan_tiled420 *p, uint32_t n_regions, const uint32_t *regions, const uint32_t *words, size_t word_stride, const uint32_t *n_words,
+                                          const uint32_t *models, const uint16_t *off_values, const float *value_params, const float *width_params, int quality, uint8_t *pixels,
+                                          uint32_t *status);
 /* The distortion of a tiled 4:2:0 reconstruction against a raster (K12's measuring kernel): the whole-image merge's walk with nothing stored. Every image pixel
  * is upsampled and converted within its own tile exactly as fri_hip_merge_tiles420_dev does it (the same strip classes, filter, clamping and arithmetic) and
  * compared with the same byte of d_reference_rgb [H][W][3]; replicated rows and columns of edge tiles are never counted. d_out uint64 [7], the layout of
