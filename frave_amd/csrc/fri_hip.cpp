@@ -66,6 +66,7 @@ struct Knobs {
     std::optional<int> strided_shares;
     std::optional<int> k1_wave; // FRI_HIP_K1_WAVE: 1 = the plan carries the forward kernel's wave form and runs it wherever it applies, 0 = it never does
     int k1_wave_band = 0, k1_wave_wgs = 0; // with it: FRI_HIP_K1_WAVE_BAND (rows per band, 0 = 16), FRI_HIP_K1_WAVE_WGS (workgroups per CU the shares are cut for, 0 = 4)
+    int k1_wave_pace = 0; // FRI_HIP_K1_WAVE_PACE=<ticks of the 100 MHz counter>: pins the wave form like FRI_HIP_K1_WAVE=1, with its single-image launches paced to that lifetime of a wave
     bool has_rank_weights = false; // FRI_HIP_RANK_WEIGHTS="w0,w1,w2,w3" with all four parsed ("1,1,1,1" = equal shares)
     float rank_weight[4] = {0, 0, 0, 0};
     bool pins_forward = false;
@@ -97,6 +98,7 @@ Knobs read_knobs() {
     k.strided_shares = opt(pin("FRI_HIP_STRIDED_SHARES"));
     k.k1_wave = opt(pin("FRI_HIP_K1_WAVE"));
     k.k1_wave_band = num(pin("FRI_HIP_K1_WAVE_BAND")), k.k1_wave_wgs = num(pin("FRI_HIP_K1_WAVE_WGS"));
+    k.k1_wave_pace = num(pin("FRI_HIP_K1_WAVE_PACE"));
     if (const char *s = pin("FRI_HIP_RANK_WEIGHTS")) {
         float *w = k.rank_weight;
         k.has_rank_weights = std::sscanf(s, "%f,%f,%f,%f", &w[0], &w[1], &w[2], &w[3]) == 4;
@@ -234,13 +236,14 @@ void fill_forward_tiling(DevicePlan &d, const Geometry &g) {
     d.lds_pitch = g.lds_pitch, d.lds_rows = g.lds_rows, d.cells_per_tile = g.cells_per_tile, d.max_tile_cells = g.max_tile_cells;
     d.max_wg_tiles = std::max(g.max_wg_tiles, g.max_wg_tiles_batch), d.max_wg_cells = g.max_wg_cells;
     d.n_wave_wg = g.wave_cells.empty() ? 0u : (uint32_t)g.wave_cells.size() - 1, d.max_wave_wg_cells = g.max_wave_wg_cells;
+    d.wave_pace_ticks = g.wave_cells.empty() ? 0u : std::min((uint32_t)std::max(g.wave_pace_ticks, 0), kWavePaceMaxTicks);
     if (g.wave_cells.empty()) d.wave_meta = nullptr, d.wave_cells = nullptr;
 }
 // ... and the inverse kernel's: one share per workgroup, no batch shares
 void fill_inverse_tiling(DevicePlan &d, const Geometry &g) {
     fill_forward_tiling(d, g);
     d.wg_tiles_batch = nullptr, d.n_wg_batch = 0, d.max_wg_tiles = g.max_wg_tiles;
-    d.wave_meta = nullptr, d.wave_cells = nullptr, d.n_wave_wg = 0, d.max_wave_wg_cells = 0;
+    d.wave_meta = nullptr, d.wave_cells = nullptr, d.n_wave_wg = 0, d.max_wave_wg_cells = 0, d.wave_pace_ticks = 0;
     d.inv_group = 1, d.inv_max_wg_tiles = g.max_wg_tiles, d.inv_max_wg_cells = g.max_wg_cells;
 }
 
@@ -329,7 +332,10 @@ int choose_forward_tiling(uint32_t width, uint32_t height, uint32_t channels, st
     // FRI_HIP_K1_WAVE=1: the wave form's share table beside the tiles, cut for FRI_HIP_K1_WAVE_WGS workgroups per CU (default four) from bands of
     // FRI_HIP_K1_WAVE_BAND rows (default 16): any of the tuner's wave candidates can be pinned.
     // A share that does not fit the wave kernel, like a launch the form does not serve, runs the tile kernel (launch_fwd_transform_quant).
-    if (k.k1_wave.value_or(0) > 0 && cus) tp.wave_ranks = std::min(k.k1_wave_wgs > 0 ? k.k1_wave_wgs : 4, fwd_wave_resident()), tp.wave_band_rows = std::max(k.k1_wave_band, 0);
+    // FRI_HIP_K1_WAVE_PACE=<ticks> pins the form the same way (unless FRI_HIP_K1_WAVE=0 forbids it) and paces its single-image launches; the host clamps the ticks.
+    const bool wave_pinned = k.k1_wave ? *k.k1_wave > 0 : k.k1_wave_pace > 0;
+    if (wave_pinned && cus) tp.wave_ranks = std::min(k.k1_wave_wgs > 0 ? k.k1_wave_wgs : 4, fwd_wave_resident()), tp.wave_band_rows = std::max(k.k1_wave_band, 0);
+    if (wave_pinned && cus && k.k1_wave_pace > 0) tp.wave_pace_ticks = (int)std::min<uint32_t>((uint32_t)k.k1_wave_pace, kWavePaceMaxTicks);
     for (;;) {
         const std::string err = build_geometry(width, height, channels, tp, t.geo);
         if (!err.empty()) return err == "empty lattice" ? FRI_HIP_ERR_EMPTY_LATTICE : FRI_HIP_ERR_INVALID_ARGUMENT;
@@ -364,7 +370,7 @@ bool choose_inverse_tiling(uint32_t width, uint32_t height, uint32_t channels, s
     if (!cus || (k.inv_shared ? *k.inv_shared > 0 : fwd.geo.centers.size() >= kOwnInverseMaxCells)) return false;
     TilingParams &ti = inv.tp;
     ti = fwd.tp;
-    ti.wave_ranks = 0; // (the forward kernel's alone)
+    ti.wave_ranks = 0, ti.wave_pace_ticks = 0; // (the forward kernel's alone)
     set_ranks(ti, fwd.tp.ranks, cus, k); // (restores the dispatch-rank weights a many-shares forward tiling had flattened)
     ti.band_rows = k.inv_band_rows > 0 ? k.inv_band_rows : (channels == 1 ? 32 : 16);
     ti.cells_per_tile = k.cells_per_tile;
@@ -426,7 +432,7 @@ void adopt_forward_tiling(fri_hip_plan *p, FwdTiling &c) {
     g.max_wg_tiles_batch = c.geo.max_wg_tiles_batch, g.lds_pitch = c.geo.lds_pitch, g.lds_rows = c.geo.lds_rows, g.band_rows = c.geo.band_rows, g.cells_per_tile = c.geo.cells_per_tile;
     g.cells_per_wg = c.geo.cells_per_wg, g.max_tile_cells = c.geo.max_tile_cells, g.max_wg_tiles = c.geo.max_wg_tiles, g.max_wg_cells = c.geo.max_wg_cells;
     g.wave_meta.swap(c.geo.wave_meta), g.wave_cells.swap(c.geo.wave_cells);
-    g.wave_band_rows = c.geo.wave_band_rows, g.wave_ranks = c.geo.wave_ranks, g.max_wave_wg_cells = c.geo.max_wave_wg_cells;
+    g.wave_band_rows = c.geo.wave_band_rows, g.wave_ranks = c.geo.wave_ranks, g.max_wave_wg_cells = c.geo.max_wave_wg_cells, g.wave_pace_ticks = c.geo.wave_pace_ticks;
     DevicePlan &d = p->dev;
     d.tiles = c.dev.tiles, d.tile_cells = c.dev.tile_cells, d.tile_meta = c.dev.tile_meta, d.wg_tiles = c.dev.wg_tiles, d.wg_tiles_batch = c.dev.wg_tiles_batch;
     d.wave_meta = c.dev.wave_meta, d.wave_cells = c.dev.wave_cells;
@@ -440,11 +446,20 @@ void adopt_forward_tiling(fri_hip_plan *p, FwdTiling &c) {
 
 std::string tiling_label(const TilingParams &tp, const Geometry &g) {
     char b[96];
-    // the wave form is named by its own cut (bands, workgroups per CU): the tiles under it only serve the launches the form does not (include/fri_hip.h)
-    if (tp.wave_ranks > 0 && !g.wave_cells.empty()) std::snprintf(b, sizeof b, "wave/band%d/wg%d", g.wave_band_rows, g.wave_ranks);
+    // the wave form is named by its own cut (bands, workgroups per CU), its pace in tenths of a microsecond where it has one, and the weights its shares are cut
+    // with: the tiles under it only serve the launches the form does not (include/fri_hip.h)
+    const bool wave = tp.wave_ranks > 0 && !g.wave_cells.empty();
+    if (wave) std::snprintf(b, sizeof b, "wave/band%d/wg%d", g.wave_band_rows, g.wave_ranks);
     else std::snprintf(b, sizeof b, "%s/band%d/cells%d", tp.strided_shares ? "interleaved" : "contiguous", g.band_rows, g.cells_per_tile);
     std::string l = b;
-    if (tp.rank_weight[0] > 0) {
+    if (wave && g.wave_pace_ticks > 0) {
+        std::snprintf(b, sizeof b, "/pace%d", (g.wave_pace_ticks + 5) / 10);
+        l += b;
+    }
+    if (wave && tp.wave_weight[0] > 0) {
+        std::snprintf(b, sizeof b, "/w%.2f-%.2f", tp.wave_weight[0], tp.wave_weight[1]);
+        l += b;
+    } else if (tp.rank_weight[0] > 0) {
         std::snprintf(b, sizeof b, "/w%.2f-%.2f", tp.rank_weight[0], tp.rank_weight[std::max(0, std::min(tp.ranks, 4) - 1)]);
         l += b;
     }
@@ -656,7 +671,7 @@ int fri_hip_plan_create(fri_hip_ctx *ctx, uint32_t width, uint32_t height, uint3
     p->own_inverse_tiling = choose_inverse_tiling(width, height, channels, cus, k, fwd, inv);
     p->geo = std::move(fwd.geo);
     p->fwd_tp = fwd.tp; // (fri_hip_plan_tune_forward starts from it)
-    if (!p->geo.wave_cells.empty()) p->fwd_tiling_note = tiling_label(fwd.tp, p->geo) + " (pinned: FRI_HIP_K1_WAVE)"; // what the tuner's report says it kept
+    if (!p->geo.wave_cells.empty()) p->fwd_tiling_note = tiling_label(fwd.tp, p->geo) + (fwd.tp.wave_pace_ticks > 0 ? " (pinned: FRI_HIP_K1_WAVE_PACE)" : " (pinned: FRI_HIP_K1_WAVE)"); // what the tuner's report says it kept
     if (p->own_inverse_tiling) {
         p->geo_inv = std::move(inv.geo);
         // what the plan keeps of geo_inv on the host: the tiling and its lists (fri_hip_plan_inverse_lists reads their sizes); the lattice arrays are geo's
@@ -1784,7 +1799,14 @@ int fri_hip_time_transform_quant_streams_dev(fri_hip_plan *p, uint32_t n_images,
 /* Measures candidate tilings of the forward kernel on this plan's device and keeps the fastest (see "forward tiling chosen by measurement" above). */
 static int tune_forward(fri_hip_plan *p, uint32_t launches, std::string &rep) {
     if (!p->fwd_tunable) {
-        rep = "{\"tuned\": false, \"kept\": \"" + p->fwd_tiling_note + "\", \"why\": \"tiling pinned by the environment, shared with the inverse kernel, or a many-shares plan\"}";
+        rep = "{\"tuned\": false, \"kept\": \"" + p->fwd_tiling_note + "\", \"why\": \"tiling pinned by the environment, shared with the inverse kernel, or a many-shares plan\"";
+        if (p->dev.n_wave_wg > 0) { // a pinned wave form: its shares, its pace and the bound of a hold (kernels.hpp)
+            const int max_pairs = ((p->dev.max_wave_wg_cells + 1) / 2 + 3) / 4; // of one wave: pair i of a share goes to wave i % 4
+            rep += ", \"wave_form\": {\"shares\": " + std::to_string(p->dev.n_wave_wg) + ", \"max_pairs_per_wave\": " + std::to_string(max_pairs) + ", \"pace_ticks\": " +
+                   std::to_string(p->dev.wave_pace_ticks) + ", \"pace_step_cycles\": " + std::to_string(64 * kWavePaceSleep) + ", \"pace_max_steps\": " + std::to_string(kWavePaceMaxSteps) +
+                   ", \"pace_max_ticks\": " + std::to_string(kWavePaceMaxTicks) + "}";
+        }
+        rep += "}";
         return FRI_HIP_OK;
     }
     fri_hip_ctx *c = p->ctx;
@@ -1936,6 +1958,7 @@ static int tune_forward(fri_hip_plan *p, uint32_t launches, std::string &rep) {
                 if (ranks == 5 && band != 32 && band != 96) continue;
                 TilingParams tp = w;
                 tp.wave_ranks = ranks, tp.wave_band_rows = band;
+                tp.wave_pace_ticks = 0, tp.wave_weight[0] = tp.wave_weight[1] = 0.f; // unpaced, on the tiles' weights, whatever the plan started from (a paced winner of an earlier tuning)
                 add_tp(tp);
                 if (band >= (int)g0.height) break; // one band already: higher ones cut the same shares
             }
@@ -1949,6 +1972,42 @@ static int tune_forward(fri_hip_plan *p, uint32_t launches, std::string &rep) {
             for (size_t k : round3)
                 if (cand[k]->us < cand[b3]->us) b3 = k;
             if (cand[b3]->us < cand[best]->us * 0.985) best = b3;
+        }
+        // Fourth phase: the best wave candidate of the third (whether or not it beat the tiles; t_w its time) again, side by side with paced variants of it -
+        // target lifetimes of 0.70 / 0.75 / 0.80 / 0.85 t_w (the median and 90th-percentile exits and the batch figure over the last exit)
+        // crossed with the weights its shares are cut with: the tiles' own, 1.15 .. 0.85, equal (the weights exist to make up for the unfairness pacing is after).
+        // A paced variant is kept only if it is more than 1.5 % faster than the best of everything measured so far, measured again beside it.
+        size_t bw = cand.size();
+        for (size_t k : round3)
+            if (cand[k]->tp.wave_ranks > 0 && cand[k]->tp.wave_pace_ticks == 0 && (bw == cand.size() || cand[k]->us < cand[bw]->us)) bw = k; // (unpaced ones: t_w is an unpaced time)
+        if (bw != cand.size()) {
+            const TilingParams ww = cand[bw]->tp;
+            const double t_w = cand[bw]->us;
+            std::vector<size_t> round4{best};
+            if (bw != best) round4.push_back(bw);
+            const size_t n1 = cand.size();
+            static const float cuts[3][2] = {{0.f, 0.f}, {1.15f, 0.85f}, {1.f, 1.f}}; // {0, 0}: the tiling's own weights
+            for (const auto &cut : cuts) {
+                if (cut[0] == 1.f && !(ww.rank_weight[0] > 0)) continue; // a tiling without weights is cut into equal shares already
+                for (double ratio : {0.70, 0.75, 0.80, 0.85}) {
+                    TilingParams tp = ww;
+                    tp.wave_weight[0] = cut[0], tp.wave_weight[1] = cut[1];
+                    // in whole tenths of a microsecond, as the label says it (two ratios that give the same pace are one candidate)
+                    tp.wave_pace_ticks = (int)std::min<uint32_t>(kWavePaceMaxTicks, 10u * (uint32_t)std::max(1.0, ratio * t_w * 10.0 + 0.5));
+                    add_tp(tp);
+                }
+            }
+            for (size_t k = n1; k < cand.size(); k++) {
+                HIP_TRY(c, upload_forward_candidate(p, *cand[k]));
+                round4.push_back(k);
+            }
+            if (cand.size() > n1) {
+                HIP_TRY(c, measure(round4));
+                size_t b4 = best;
+                for (size_t k = n1; k < cand.size(); k++)
+                    if (cand[k]->us < cand[b4]->us) b4 = k;
+                if (cand[b4]->us < cand[best]->us * 0.985) best = b4;
+            }
         }
     }
     // How long each XCD's workgroups live under the winner (FwdArgs::xcd_stat; a diagnostic for the report: re-cutting the XCDs' shares in proportion was tried and

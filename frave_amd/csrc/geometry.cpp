@@ -193,7 +193,7 @@ static void build_wave_shares(const TilingParams &tp, Geometry &g) {
     const int ranks = std::min(std::max(tp.wave_ranks, 1), 6), tile_ranks = std::min(std::max(tp.ranks, 1), 4);
     const int band_rows = tp.wave_band_rows > 0 ? tp.wave_band_rows : 16;
     const size_t cus = std::max<size_t>(1, (size_t)(tp.target_wgs > 0 ? tp.target_wgs : 1024) / tile_ranks);
-    g.wave_band_rows = band_rows, g.wave_ranks = ranks;
+    g.wave_band_rows = band_rows, g.wave_ranks = ranks, g.wave_pace_ticks = std::max(tp.wave_pace_ticks, 0);
     const int cy_min = g.centers.front().y;
     std::vector<int32_t> order(F);
     for (size_t k = 0; k < F; k++) order[k] = (int32_t)k;
@@ -207,10 +207,12 @@ static void build_wave_shares(const TilingParams &tp, Geometry &g) {
     for (size_t k = 0; k < F; k++) g.wave_meta[k] = TileCell{g.centers[order[k]].x, g.centers[order[k]].y, order[k], g.interior[order[k]]};
     // one share per resident workgroup, but no share without a pair of cells to work on
     const size_t n_wg = std::max<size_t>(1, std::min(cus * ranks, (F + 1) / 2));
-    const bool weighted = tp.rank_weight[0] > 0 && tp.rank_weight[tile_ranks - 1] > 0;
+    const bool own = tp.wave_weight[0] > 0 && tp.wave_weight[1] > 0;
+    const double w_first = own ? tp.wave_weight[0] : tp.rank_weight[0], w_last = own ? tp.wave_weight[1] : tp.rank_weight[tile_ranks - 1];
+    const bool weighted = w_first > 0 && w_last > 0;
     auto weight = [&](size_t rank) {
         if (!weighted || ranks == 1) return 1.0;
-        return (double)tp.rank_weight[0] + ((double)tp.rank_weight[tile_ranks - 1] - (double)tp.rank_weight[0]) * (double)rank / (double)(ranks - 1);
+        return w_first + (w_last - w_first) * (double)rank / (double)(ranks - 1);
     };
     std::vector<double> cum(n_wg + 1, 0.0);
     const size_t q = n_wg >> 3, r = n_wg & 7;

@@ -91,6 +91,7 @@ struct Geometry {
     std::vector<int32_t> wave_cells;  // [n_wave_wg + 1]
     int32_t wave_band_rows = 0, wave_ranks = 0;
     int32_t max_wave_wg_cells = 0;    // most cells in one share of the wave form
+    int32_t wave_pace_ticks = 0;      // TilingParams::wave_pace_ticks of the shares (0: the form runs unpaced)
     std::vector<InvTileLists> inv_lists; // [n_tiles]; empty if the lists were not built (budget)
     std::vector<uint16_t> inv_quads, inv_dwords;
     std::vector<uint32_t> inv_parts;
@@ -130,6 +131,10 @@ struct TilingParams {
     // workgroup with wave_ranks (4..6) workgroups per CU (the CU count is target_wgs / ranks), cut from bands of wave_band_rows rows (0 = 16). The dispatch-rank
     // weights run linearly from rank_weight[0] to rank_weight[ranks - 1] over the wave_ranks ranks and apply to cells.
     int wave_ranks = 0, wave_band_rows = 0;
+    // > 0: single-image launches of the wave form are paced - a wave is held while it is ahead of a line that ends wave_pace_ticks (100 MHz ticks) after its entry
+    // (fwd_wave_kernel's PACED instance). Changes when the shares' cells are written, never which or what.
+    int wave_pace_ticks = 0;
+    float wave_weight[2] = {0, 0}; // the wave shares' first and last dispatch-rank weight where they differ from the tiles' ({0, 0}: rank_weight's first and last)
     bool strided_shares = false; // deal the tiles to the shares round-robin (the resident set works on one sliding window of the image) instead of one contiguous run each
 };
 

@@ -30,6 +30,7 @@ struct FwdArgs {
     uint32_t cpr, cpr_magic;
     int32_t q_identity;
     int32_t ablate; // timing-only ablation (FRI_HIP_K1_ABLATE): 1 = skip staging, 2 = skip the cell loop, 4 = skip stores, 8 = return at entry. 0 in production.
+    uint32_t pace_ticks; // fwd_wave_kernel's PACED instance: the target lifetime T of a wave in 100 MHz ticks, clamped by the host (in the padding in front of `trace`: no other field moves)
     unsigned long long *trace; // diagnostic timeline, null in production
     unsigned long long *xcd_stat; // fri_hip_plan_tune_forward only (null otherwise): [8][2] = per XCD {sum of workgroup lifetimes in 100 MHz ticks, workgroups}
     QMatrix q;
@@ -711,17 +712,32 @@ struct WaveChunks {
 // other slab before pair i's coefficient stores are issued - the tile form's load -> transform -> commit -> store order, per wave. The last iteration issues
 // its loads all the same, every lane's from the image's first bytes, instead of branching around them (see stage_issue: a load pending on one path around the
 // back edge costs a vmcnt(0) on every path).
-template <bool QID, bool MEASURE = false>
+// PACED (single-image launches of a plan whose shares carry a target lifetime T = FwdArgs::pace_ticks): a wave with n pairs reads the 100 MHz counter at entry and,
+// at the top of pair i >= 1, sleeps at priority 0 while the counter is before entry + T i / n - it is held only while it is ahead of a line that ends before
+// the launch would end anyway, and it looks at its own clock alone. The hold of one pair is bounded by a COUNT of steps (kWavePaceMaxSteps of s_sleep
+// kWavePaceSleep), so a wrong T or a clock that stands still costs at most that per pair. The counter is read at the top of the iteration, in front of the
+// loads and the window reads: what its s_waitcnt lgkmcnt(0) waits for is the previous pair's slab commit, long done. A template parameter, not a run-time
+// switch: the unpaced instances are the code they were.
+// Timeline (the tuning build, FRI_HIP_TRACE=1): wave 0 stamps slot 0 at entry, slot 1 when its first pair's stores are issued, slot 1 + i after pair i's, and the exit.
+template <bool QID, bool MEASURE = false, bool PACED = false>
 __global__ void __launch_bounds__(kFwdThreads) fwd_wave_kernel(const FwdArgs a) {
     __shared__ __attribute__((aligned(16))) uint8_t slabs[kWaveLdsBytes];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const uint32_t wg = xcd_contiguous_share(blockIdx.x, a.n_wg);
     const int cb = a.wg_tiles[wg], ce = a.wg_tiles[wg + 1];
+    trace_stamp(a.trace, wg, 0, tid);
     const unsigned long long t_entry = a.xcd_stat ? wall_clock64() : 0ull;
     const int wg_pairs = (ce - cb + 1) >> 1;
     const int n_pairs = wg_pairs > wave ? (wg_pairs - wave + kFwdWaves - 1) / kFwdWaves : 0;
     if (n_pairs > 0) {
+        // the line in 24.8 fixed point: pace_step = T / n, summed once per pair (T <= kWavePaceMaxTicks = 2^16: no overflow); the counter's low word and
+        // unsigned differences, so a wrap of it is harmless
+        uint32_t pace_entry = 0, pace_step = 0, pace_due = 0;
+        if constexpr (PACED) {
+            pace_entry = (uint32_t)wall_clock64();
+            pace_step = (a.pace_ticks << 8) / (uint32_t)n_pairs;
+        }
         const uint8_t *img = a.pixels + (size_t)blockIdx.y * a.pixel_stride;
         int32_t *coefs = a.coefs + (size_t)blockIdx.y * a.coef_stride;
         // the records of the wave's cells, one per lane: cell 2 i + h of the wave is item h of its pair i, cell 2 (wave + 4 i) + h of the share. A lane past the
@@ -769,6 +785,13 @@ __global__ void __launch_bounds__(kFwdThreads) fwd_wave_kernel(const FwdArgs a) 
 
         for (int i = 0; i < n_pairs; i++) {
             const uint32_t cur = slab0 + (uint32_t)(i & 1) * kWaveSlab, nxt = slab0 + (uint32_t)((i & 1) ^ 1) * kWaveSlab;
+            if constexpr (PACED) {
+                if (i > 0) { // (the first pair is never held; the priority is 0 here: the previous pair ended with its stores)
+                    pace_due += pace_step;
+#pragma nounroll
+                    for (int step = 0; step < kWavePaceMaxSteps && (uint32_t)wall_clock64() - pace_entry < (pace_due >> 8); step++) __builtin_amdgcn_s_sleep(kWavePaceSleep);
+                }
+            }
             issue(min(i + 1, n_pairs - 1), i + 1 < n_pairs); // in flight across the transform below
             __builtin_amdgcn_s_setprio(3);
             const int cxA = __builtin_amdgcn_readlane(rec.x, 2 * i), cyA = __builtin_amdgcn_readlane(rec.y, 2 * i);
@@ -815,8 +838,10 @@ __global__ void __launch_bounds__(kFwdThreads) fwd_wave_kernel(const FwdArgs a) 
                 store_item<0, true, QID, true>(coefs, offA, lane, resA, valid, a);
                 if (store_b) store_item<1, true, QID, true>(coefs, offB, lane, resB, valid, a);
             }
+            trace_stamp(a.trace, wg, 1 + i, tid);
         }
     }
+    trace_exit(a.trace, wg, tid);
     if (a.xcd_stat && tid == 0) { // (as in the tile form; the workgroup's first wave speaks for it)
         const uint32_t xcc = __builtin_amdgcn_s_getreg((3 << 11) | 20) & 7u;
         (void)__hip_atomic_fetch_add(a.xcd_stat + 2 * xcc, wall_clock64() - t_entry, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -898,11 +923,17 @@ hipError_t launch_fwd_transform_quant(const DevicePlan &p, uint32_t n_images, co
     // The wave form, on a plan that carries its share table (the tuner measured it faster, or FRI_HIP_K1_WAVE=1 pinned it): what the tuner measures and nothing
     // else - planes in FAST launches of a few images with nontemporal int32 stores. Batch launches (n_images >= 8), the chains' plain stores and compact planes,
     // and the diagnostic builds' timelines and ablations keep the tile form.
-    if (fast && !plain && !coefs16 && n_images < 8 && !p.trace && !p.k1_ablate && fwd_wave_fits(p)) {
+    // A traced plan runs the form too where its timeline has a record per share (the records are the tile shares': fri_hip_plan_create).
+    if (fast && !plain && !coefs16 && n_images < 8 && (!p.trace || p.n_wave_wg <= p.n_wg) && !p.k1_ablate && fwd_wave_fits(p)) {
         a.tile_meta = p.wave_meta;
         a.wg_tiles = p.wave_cells;
         a.n_wg = p.n_wave_wg;
         void (*wk)(FwdArgs) = a.q_identity ? (p.k1_measuring ? fwd_wave_kernel<true, true> : fwd_wave_kernel<true>) : fwd_wave_kernel<false>;
+        // the paced instance: one image per launch only - with more (2..7) the dispatcher meters the later images' workgroups in as the first ones leave
+        if (p.wave_pace_ticks > 0 && n_images == 1) {
+            a.pace_ticks = p.wave_pace_ticks < kWavePaceMaxTicks ? p.wave_pace_ticks : kWavePaceMaxTicks;
+            wk = a.q_identity ? (p.k1_measuring ? fwd_wave_kernel<true, true, true> : fwd_wave_kernel<true, false, true>) : fwd_wave_kernel<false, false, true>;
+        }
         (void)hipGetLastError();
         hipLaunchKernelGGL(wk, dim3(a.n_wg, n_images), block, 0, stream, a);
         return hipGetLastError();

@@ -24,6 +24,7 @@ struct DevicePlan {
     const int32_t *wave_cells = nullptr;  // [n_wave_wg + 1] cell range per workgroup share
     uint32_t n_wave_wg = 0;
     int32_t max_wave_wg_cells = 0;
+    uint32_t wave_pace_ticks = 0;         // > 0: single-image launches of the wave form run its paced instance with this target lifetime of a wave (100 MHz ticks, <= kWavePaceMaxTicks)
     int32_t max_tile_cells = 0;
     bool covers_image = false;            // every pixel of the image is a leaf of a retained cell
     int32_t max_wg_tiles = 0;
@@ -307,6 +308,11 @@ bool fwd_plan_fits(const DevicePlan &p);
 bool fwd_wave_fits(const DevicePlan &p);
 // Resident workgroups per CU of the wave kernel by its LDS (its registers allow as many).
 int fwd_wave_resident();
+// The paced instance of the wave kernel (k1_forward.hip) holds a wave that is ahead of its line in steps of s_sleep kWavePaceSleep (64 cycles each: 256 cycles a
+// step), at most kWavePaceMaxSteps steps per pair: a hold is bounded by this count, never by the clock alone, whatever the target lifetime is. The target is
+// clamped to kWavePaceMaxTicks (ticks of the 100 MHz counter) wherever it enters (the pin, the tuner, the launch).
+constexpr int kWavePaceSleep = 4, kWavePaceMaxSteps = 16;
+constexpr uint32_t kWavePaceMaxTicks = 1u << 16;
 constexpr size_t kInvListPad = 2048; // >= kInvListPre x kInvThreads of k3_inverse.hip
 bool inv_plan_fits(const DevicePlan &p, bool with_lists); // k3_inverse.hip: the inverse kernels' own limits (its tiling is its own since round 4)
 

@@ -1290,13 +1290,22 @@ int fri_hip_time_transform_quant_streams_dev(fri_hip_plan *plan, uint32_t n_imag
  * inverse kernel shares (>= 400 000 cells) is left alone. `report` (may be NULL): a JSON object with the candidates' microseconds per launch.
  * The labels of the report ("winner", the keys of "candidates_us") name what ran:
  *     interleaved|contiguous/band<R>/cells<N>[/w<first>-<last>]   the tile form: shares of tiles of N cells cut from bands of R rows, dealt round-robin or as runs
- *     wave/band<R>/wg<K>[/w<first>-<last>]                        the wave form (planes whose width is a multiple of 16): no tiles, every wave of the kernel stages and
- *                                                                 transforms its own pairs of cells; shares of cells cut from bands of R rows for K workgroups per CU
- * (w: the shares' relative sizes by dispatch rank, first to last). Under a wave/ winner, single launches of fewer than eight 16-byte aligned images with the
+ *     wave/band<R>/wg<K>[/pace<T>][/w<first>-<last>]              the wave form (planes whose width is a multiple of 16): no tiles, every wave of the kernel stages and
+ *                                                                 transforms its own pairs of cells; shares of cells cut from bands of R rows for K workgroups per CU.
+ *                                                                 pace<T>: launches of ONE image run the paced instance - a wave that is ahead of the line from its entry
+ *                                                                 to T tenths of a microsecond later sleeps before its next pair, in short steps whose number per pair
+ *                                                                 is bounded; launches of two to seven images run unpaced
+ * (w: the shares' relative sizes by dispatch rank, first to last; under wave/ the weights of the wave form's own shares). Whatever reads the first three fields
+ * of a wave/ label keeps working: pace and weights follow them. Under a wave/ winner, single launches of fewer than eight 16-byte aligned images with the
  * default (streaming) int32 coefficient stores run the wave form; batch launches of eight images or more, the encode chains and unaligned buffers keep the tile
  * form on the tile tiling measured best. FRI_HIP_K1_WAVE=1 / 0 (with FRI_HIP_TUNING=1, read when the plan is created) pins the form on / off, and
- * FRI_HIP_K1_WAVE_BAND / FRI_HIP_K1_WAVE_WGS its R and K; a pinned plan is left alone like any other.
- * Blocks for tens of milliseconds; call it once after fri_hip_plan_create, outside anything that is timed. Not thread-safe per plan. */
+ * FRI_HIP_K1_WAVE_BAND / FRI_HIP_K1_WAVE_WGS its R and K; FRI_HIP_K1_WAVE_PACE=<ticks of the 100 MHz counter> pins the form with that pace (clamped to 2^16
+ * ticks) on shares cut with FRI_HIP_RANK_WEIGHTS; a pinned plan is left alone like any other, and its report carries "wave_form": the shares, the pairs of
+ * the longest wave, the pace and the bound of a hold (cycles per step, steps per pair).
+ * A pace is an absolute time measured with every byte coming from HBM: where a launch's data is cache resident, or the device is faster, an unpaced launch can be
+ * shorter than T, and the paced one then holds its waves, by at most the bound of a hold per pair (DESIGN.md section 10.9 has the measurement).
+ * Blocks for tens of milliseconds on small images and a few hundred at 4096^2 (planes: up to some forty candidates, twelve of them the paced variants, each built,
+ * uploaded and run in five rounds of launches + 8 launches); call it once after fri_hip_plan_create, outside anything that is timed. Not thread-safe per plan. */
 int fri_hip_plan_tune_forward(fri_hip_plan *plan, uint32_t launches, char *report, size_t report_bytes);
 
 /* The inverse kernel's static write-out lists (diagnostics / tests): out[5] = {built (0/1), whole 16-byte quads, whole dwords inside

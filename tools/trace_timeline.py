@@ -34,6 +34,16 @@ _, _, wg_tiles = plan.tile_table()
 if os.environ.get("TRACE_DUMP"):  # the raw stamps (slot 14 = HW_ID | XCC_ID << 32: which CU a workgroup ran on) for an analysis off the box
     np.savez(os.environ["TRACE_DUMP"], trace=tr, wg_tiles=np.asarray(wg_tiles))
 n_tiles = np.diff(wg_tiles)
+# The wave form (a plan pinned with FRI_HIP_K1_WAVE=1 or FRI_HIP_K1_WAVE_PACE=<ticks>, forward only): a record is a share's wave 0 - slot 1 = its first pair's
+# stores issued, slot 1 + i = pair i's, so "prologue done" below reads "first stores issued" and "tile i" reads "pair i + 1 of wave 0" (its pairs = its stamps).
+wave_form = which == "k1" and C == 1 and (os.environ.get("FRI_HIP_K1_WAVE") == "1" or int(os.environ.get("FRI_HIP_K1_WAVE_PACE", "0")) > 0)
+if wave_form:
+    form = plan.tune_forward()["wave_form"]  # a pinned plan's report: how many shares the form has (the first records; the rest are the tile shares' and stay zero)
+    tr = tr[: form["shares"]]
+    n_tiles = (tr[:, 2:14] != 0).sum(axis=1)
+    if form["max_pairs_per_wave"] > 13:
+        print(f"NOTE: the longest wave has {form['max_pairs_per_wave']} pairs; a record holds 13 (the last slot is then the last pair's stamp)")
+    print(f"wave form, pace {os.environ.get('FRI_HIP_K1_WAVE_PACE', '0')} ticks: 'prologue done' = first stores issued, 'tile i' = pair i + 1 of a share's wave 0, exit = wave 0's")
 t0 = tr[:, 0].min()
 us = lambda a: (a - t0) / 100.0
 entry, pro, end = us(tr[:, 0]), us(tr[:, 1]), us(tr[:, 15])
